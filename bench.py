@@ -22,7 +22,11 @@
     python bench.py --gpus 8 ...          (no launcher needed: spawns python -m torch.distributed.run itself, before any GPU call)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (fields: see the driver contract; plus "roofline", "roofline_fragment" and "cpu_baseline").
+Prints ONE JSON line on rank 0 (fields: see the driver contract; plus "roofline" from the timed frames' events).  A plain run sets up,
+settles, warms up, times the steps and prints; --full adds the secondary measurements ("other_camera", "roofline_fragment",
+"cold_frames_ms", "api_latency_ms", "cpu_baseline", the plan chain's times in "roofline").
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     (DIR/rgba.npy: the last timed frame, float32)
 """
 from __future__ import annotations
 
@@ -45,6 +49,8 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SETTLE = 24                     # untimed frames of a new camera before the warm-up (see timed()): the plan's feedback settles, the handle probes its two line loops (frames 4..19)
+DUMP_BYTES = 48 << 20           # --dump-outputs: at most this many bytes of float32 (a C4 frame is 256 MiB as float32: a fixed sample of its pixels)
+DUMP_SEED = 0
 
 
 def parse():
@@ -56,12 +62,18 @@ def parse():
     ap.add_argument("--size", type=int, default=4096, help="c4: frame width = height")
     ap.add_argument("--grid", type=int, default=None, help="default: 4096 (c4), 2048 (c5)")
     ap.add_argument("--camera", choices=["default", "fill"], default="default")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary measurements (other camera, fragment stage, cold frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: four frames of their own for the plan chain's times before the timed steps; "
+                         "other camera, fragment stage, cold frames, the drop-in API's latency and the CPU baseline after them (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step produced to DIR/rgba.npy as float32 RGBA values (H, W, 4); a frame larger "
+                         "than 48 MiB as float32 is written as the (n, 4) pixels at n fixed, seeded positions in row-major order")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary measurements (other camera, fragment stage, cold frame)")
     ap.add_argument("--check", action="store_true", help="after timing, compare the gathered frame with a single-rank render "
                                                          "(always done at N > 1: a scaling number is only printed for a frame that was proven)")
     ap.add_argument("--no-api-latency", action="store_true",
-                    help="skip the end-to-end timing of the drop-in API (TerrainSpike / Scene render_png and render_rgba incl. read-back and PNG "
+                    help="--full: skip the end-to-end timing of the drop-in API (TerrainSpike / Scene render_png and render_rgba incl. read-back and PNG "
                          "encode at C2, C3 and C4; a few hundred ms)")
     ap.add_argument("--serial", action="store_true", help="N>1: finish each frame's exchange before rendering the next (no overlap)")
     ap.add_argument("--cabi-gather", action="store_true",
@@ -164,6 +176,21 @@ def lib_sha256(path):
         for chunk in iter(lambda: f.read(1 << 20), b""):
             h.update(chunk)
     return h.hexdigest()
+
+
+def dump_outputs(path, image):
+    """--dump-outputs: the (H, W, 4) uint8 device frame as float32 in path/rgba.npy -- whole when it fits in DUMP_BYTES, otherwise the
+    pixels at positions drawn by np.random.default_rng(DUMP_SEED) from H*W and sorted (the same positions for the same frame size)."""
+    import numpy as np
+    import torch
+    H, W = image.shape[:2]
+    out = image
+    n = DUMP_BYTES // 16
+    if H * W > n:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, n, replace=False))
+        out = image.reshape(H * W, 4).index_select(0, torch.from_numpy(idx).to(image.device))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rgba.npy"), out.to(torch.float32).cpu().numpy())
 
 
 def main():
@@ -422,7 +449,7 @@ def main():
         # the plan chain's times (side streams): from four frames of their own in front of the timed region -- event records between the plan's
         # kernels delay the chain, and the timed region carries none
         plan_tm = None
-        if not c5:
+        if not c5 and args.full:
             t.enable_timing(True, stats=False)
             for _ in range(4):
                 step()
@@ -473,6 +500,8 @@ def main():
 
     dt, tm = timed(args.camera, args.steps, args.warmup)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:                              # before anything below draws into `image` again
+        dump_outputs(args.dump_outputs, image)
     # per timed frame, this rank's HIP events: frame period (end of the previous frame's tile kernel -> end of this one's;
     # back-to-back frames overlap, so this is what a frame costs) and the kernels on the caller's stream
     frame_ms = {"period": frame_stats(tm["frame_period_ms"][1:]), "tile_kernel": frame_stats(tm["frame_tile_ms"]),
@@ -482,7 +511,7 @@ def main():
     value = W * H * frames / dt / 1e6
 
     extra = None
-    if not args.no_extra and not c5:
+    if args.full and not args.no_extra and not c5:
         other = "fill" if args.camera == "default" else "default"
         n2 = max(3, args.steps // 4)
         dt2, tm2 = timed(other, n2, 1)
@@ -515,7 +544,7 @@ def main():
 
     # ---- secondary measurements on one GPU: the fragment stage on its own, a frame without scheduling feedback --------------
     frag = cold = None
-    if rank == 0 and world == 1 and not args.no_extra:
+    if args.full and rank == 0 and world == 1 and not args.no_extra:
         probe = new_handle()
         cams = [("pose8", orbit_uniforms(8, W, H))] if c5 else [(c, camera_uniforms(c, W, H)) for c in ("default", "fill")]
         frag = {}
@@ -564,7 +593,7 @@ def main():
     # ---- the drop-in API end to end (src/terrain/mod.rs:410-491: render -> copy_texture_to_buffer -> map -> PNG): what a caller of the
     #      reference's classes waits for, per BASELINE configuration; never part of `value` -------------------------------------------
     api_latency = None
-    if rank == 0 and world == 1 and not args.no_extra and not args.no_api_latency and not c5:
+    if args.full and rank == 0 and world == 1 and not args.no_extra and not args.no_api_latency and not c5:
         import tempfile
         api_latency = {"clock": "host wall clock around the call, best of 8 after two warm-up calls", "png_threads": os.environ.get("VF_PNG_THREADS", "default (up to 16)")}
         with tempfile.TemporaryDirectory() as tmpd:
@@ -626,7 +655,7 @@ def main():
                 "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                 "traffic": traffic, "traffic_stale": stale, "counters_source": source,
                 "lib_sha256": lib_hash, "algorithmic_bytes_per_launch": rank_bytes, "kernel_ms": tm["tile_ms"],
-                "plan_on_side_stream_elapsed_ms": {"k_block_boxes+k_block_setup": tm["ranges_ms"], "k_plan+k_plan_sort": tm["plan_ms"]},
+                "plan_on_side_stream_elapsed_ms": {"k_block_boxes+k_block_setup": tm["ranges_ms"], "k_plan+k_plan_sort": tm["plan_ms"]} if args.full else None,
                 "frames_averaged": tm["frames"], "rank_share_of_frame": share,
                 "limiter": "valu",
                 "note": "the path has no contraction and does not reach the HBM roof: the tile kernel is limited by vector-ALU issue "
@@ -647,7 +676,7 @@ def main():
 
     # ---- CPU baseline: the oracle (a port, not the reference: it cannot be built here) on this box's host cores -----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         ncpu, aff, quota, model = host_cpus()
         threads = max(1, min(aff, int(quota) if quota and quota >= 1 else aff, oracle.max_threads()))

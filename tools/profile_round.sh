@@ -13,8 +13,8 @@ R="$GRAFT_REPO_ROOT"
 sha256sum vulkan_forge_amd/libvf_hip.so | cut -d' ' -f1 > "$out/lib_sha256.txt"
 if [[ $part == *a* ]]; then
 echo "== pytest -m gpu"; timeout -k 10 900 python -m pytest tests -m gpu -q > "$out/pytest_gpu.log" 2>&1; tail -2 "$out/pytest_gpu.log"
-echo "== bench (C4)"; timeout -k 10 600 python bench.py --steps 20 --warmup 3 --check > "$out/bench.json" 2> "$out/bench.err" || exit 1
-echo "== bench (C5)"; timeout -k 10 600 python bench.py --workload c5 --steps 64 --warmup 8 > "$out/bench_c5.json" 2> "$out/bench_c5.err" || exit 1
+echo "== bench (C4)"; timeout -k 10 600 python bench.py --steps 20 --warmup 3 --check --full > "$out/bench.json" 2> "$out/bench.err" || exit 1
+echo "== bench (C5)"; timeout -k 10 600 python bench.py --workload c5 --steps 64 --warmup 8 --full > "$out/bench_c5.json" 2> "$out/bench_c5.err" || exit 1
 echo "== kernel trace"; (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$out/trace" -o run -- python3 "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline --no-extra > "$R/$out/bench_traced.json" 2> "$R/$out/trace.err") || exit 1
 cp "$(find $out/trace -name '*kernel_stats.csv' | head -1)" "$out/kernel_stats.csv"
 pmc() {   # pmc <name> "<counters>" <program args...>      (every pass under a timeout: a counter set that cannot be collected hangs the run)
@@ -58,7 +58,7 @@ echo "== one-shot path, cold process"; timeout -k 10 200 python tools/one_shot.p
 echo "== C5: poses at rest, per-pose times of the orbit, schedules"; (VF_C5_STATIC=1 VF_C5_POSES=1 timeout -k 10 300 python tools/exp_c5.py r06) > "$out/c5_orbit.log" 2>&1; cat "$out/c5_orbit.log"
 if [ -f build/variants/libvf_gantt.so ]; then for c in pose8 pose0 orbit7 orbit60; do VF_C5=1 VF_HIP_LIB=$PWD/build/variants/libvf_gantt.so timeout -k 10 200 python tools/exp_gantt.py $c; done > "$out/c5_gantt.log" 2>&1; grep tile_ms "$out/c5_gantt.log"; fi
 echo "== eight virtual ranks"; timeout -k 10 600 python tools/rehearse_virtual.py 8 > "$out/rehearse_8ranks.json" 2> "$out/rehearse_8ranks.err"; echo "rc=$?"; tail -c 300 "$out/rehearse_8ranks.json"
-echo "== rehearsal"; for n in 2 4; do timeout -k 10 600 python bench.py --gpus $n --rehearse --no-cpu-baseline --steps 5 > "$out/rehearse_${n}ranks.json" 2> "$out/rehearse_${n}ranks.err"; echo "rc=$?"; tail -c 300 "$out/rehearse_${n}ranks.json"; done
+echo "== rehearsal"; for n in 2 4; do timeout -k 10 600 python bench.py --gpus $n --rehearse --no-cpu-baseline --steps 5 --full > "$out/rehearse_${n}ranks.json" 2> "$out/rehearse_${n}ranks.err"; echo "rc=$?"; tail -c 300 "$out/rehearse_${n}ranks.json"; done
 # round 4: where the tile kernel's time goes (build/variants/libvf_phase.so = tools/build_variant.sh phase -DVF_PHASE_PROF), one GPU and a rank of eight;
 # the rank's SQ counters; when each work item starts and ends (libvf_gantt.so = -DVF_DIAG_ITEM=3); which line loop the handle picks per view
 if [ -f build/variants/libvf_phase.so ]; then echo "== phase cycles"; timeout -k 10 200 python tools/exp_phases.py build/variants/libvf_phase.so > "$out/phase_cycles.log" 2>&1; echo "---- rank 2 of 8" >> "$out/phase_cycles.log"; timeout -k 10 200 python tools/exp_phases.py build/variants/libvf_phase.so 2 8 0 >> "$out/phase_cycles.log" 2>&1; grep -c cycles/pair "$out/phase_cycles.log"; fi
