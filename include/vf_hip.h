@@ -213,6 +213,33 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
 int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t n, uint8_t *const *host_rgba);
 int vf_terrain_sync(vf_terrain *t);
 
+/* Overlays (new; the reference plans them, ROADMAP.md Milestone B2, and never implemented them): points and polylines in the
+ * terrain's world frame, drawn over every frame the handle renders -- vf_terrain_render, _render_batch, _render_batch_host, and so
+ * every read-back -- as pixel-sized screen-space primitives with analytic anti-aliasing, blended in linear light in layer order
+ * (layers in the order they were added, features in input order), straight alpha; the terrain does not occlude them.  The
+ * conventions, bit for bit, are DESIGN.md "Overlays"; visibility read-backs and the fragment-stage diagnostics never show them.
+ * Data is copied to HBM by the call.  A handle has at most 2^24 primitives (a point is one; a path of m vertices at most 2m - 1).
+ * Overlays need a whole-frame handle: on a band- or tile-sharded handle these calls, and vf_terrain_set_shard /
+ * vf_terrain_set_tile_shard on a handle with overlays, fail with VF_ERR_INVALID.  A handle with overlays waits once per frame, between
+ * binning passes, for the number of (primitive, bin) pairs; a handle without overlays launches and allocates nothing for them.
+ *   vf_terrain_add_points: n points xyz[3n]; size_px[n] (diameter / side in pixels, clamped to [1, 64]) or NULL for default_size;
+ *     rgba[4n] sRGB8 bytes with alpha or NULL for default_rgba; shape VF_SHAPE_*; drape != 0: y is an offset above the rendered
+ *     surface.  Points with a non-finite coordinate are dropped.
+ *   vf_terrain_add_lines: npaths paths, path p = vertices path_offsets[p] .. path_offsets[p + 1] - 1 of xyz (>= 2 each, all finite);
+ *     width_px clamped to [1, 64]; one colour; cap VF_CAP_*; round joins.
+ *   *layer_id (may be NULL): the layer's number, counting from 0 since the handle's last vf_terrain_clear_overlays.
+ *   vf_terrain_clear_overlays: removes every layer and frees their memory (frames are then byte-identical to a handle that never had any). */
+#define VF_SHAPE_CIRCLE 0
+#define VF_SHAPE_SQUARE 1
+#define VF_CAP_BUTT 0
+#define VF_CAP_SQUARE 1
+#define VF_CAP_ROUND 2
+int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const float *size_px, const uint8_t *rgba, float default_size,
+                          const uint8_t default_rgba[4], int shape, int drape, uint32_t *layer_id);
+int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_offsets, uint32_t npaths, float width_px,
+                         const uint8_t rgba[4], int cap, int drape, uint32_t *layer_id);
+int vf_terrain_clear_overlays(vf_terrain *t);
+
 /* copy_texture_to_buffer + map + un-pad (src/terrain/mod.rs:439-485): local rows [y0, y0+rows)
  * into dst (rows*W*4 bytes).  Waits for the last render and for the copy (work the library queues behind the copy for the
  * caller's NEXT frame may still be running when this returns: later calls on the handle are ordered after it). */

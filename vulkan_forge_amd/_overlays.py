@@ -1,0 +1,110 @@
+"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines) and pack_lines.
+
+The extension calls these before it hands the arrays to the C-ABI (include/vf_hip.h, overlays); they need numpy only, no device.
+"""
+from __future__ import annotations
+
+import numbers
+
+import numpy as np
+
+SHAPES = {"circle": 0, "square": 1}
+CAPS = {"butt": 0, "square": 1, "round": 2}
+
+
+def _float_array(obj, what):
+    a = obj if isinstance(obj, np.ndarray) else np.asarray(obj)
+    if a.dtype not in (np.float32, np.float64):
+        raise TypeError(f"{what} must be a float32 or float64 array, got dtype {a.dtype}")
+    return a
+
+
+def _xyz(obj, what):
+    a = _float_array(obj, what)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError(f"{what} must have shape (N, 3), got {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _colour(rgba, n, per_feature):
+    """(default 4 bytes, per-feature (n, 4) uint8 array or None)"""
+    if isinstance(rgba, np.ndarray) and rgba.ndim == 2:
+        if not per_feature:
+            raise ValueError("rgba must be a 4-tuple of ints 0-255 for a line layer")
+        if rgba.dtype != np.uint8:
+            raise TypeError(f"rgba as an array must be uint8, got dtype {rgba.dtype}")
+        if rgba.shape != (n, 4):
+            raise ValueError(f"rgba must have shape ({n}, 4), got {rgba.shape}")
+        return np.zeros(4, np.uint8), np.ascontiguousarray(rgba)
+    try:
+        vals = tuple(rgba)
+    except TypeError:
+        raise TypeError("rgba must be a 4-tuple of ints 0-255" + (" or an (N, 4) uint8 array" if per_feature else "")) from None
+    if len(vals) != 4:
+        raise ValueError(f"rgba must hold 4 values (r, g, b, alpha), got {len(vals)}")
+    for v in vals:
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise TypeError(f"rgba values must be ints 0-255, got {v!r}")
+        if not 0 <= int(v) <= 255:
+            raise ValueError(f"rgba values must be in 0..255, got {int(v)}")
+    return np.array([int(v) for v in vals], np.uint8), None
+
+
+def _size(value, n, what):
+    """(default size, per-feature (n,) float32 array or None)"""
+    if isinstance(value, numbers.Real) and not isinstance(value, bool):
+        v = float(value)
+        if not np.isfinite(v) or v <= 0.0:
+            raise ValueError(f"{what} must be a positive finite number, got {v}")
+        return v, None
+    a = _float_array(value, what)
+    if a.shape != (n,):
+        raise ValueError(f"{what} must be a float or an array of shape ({n},), got shape {a.shape}")
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError(f"{what} values must be positive and finite")
+    return 0.0, np.ascontiguousarray(a, dtype=np.float32)
+
+
+def point_args(xyz, size_px, rgba, shape):
+    """-> (xyz (N, 3) f32, default size, sizes (N,) f32 or None, default rgba (4,) u8, rgba (N, 4) u8 or None, shape code)"""
+    if shape not in SHAPES:
+        raise ValueError(f"shape must be one of {sorted(SHAPES)}, got {shape!r}")
+    pts = _xyz(xyz, "xyz")
+    n = pts.shape[0]
+    dsize, sizes = _size(size_px, n, "size_px")
+    dcol, cols = _colour(rgba, n, True)
+    return pts, dsize, sizes, dcol, cols, SHAPES[shape]
+
+
+def pack_lines(paths):
+    """Paths (a sequence of (k, 3) float arrays) -> (coords (M, 3) float32, offsets (P + 1,) uint32), consecutive duplicate vertices
+    removed (ROADMAP V3.1).  A path with fewer than 2 distinct consecutive vertices, or with a non-finite coordinate, is refused."""
+    if isinstance(paths, np.ndarray):
+        paths = [paths] if paths.ndim == 2 else list(paths)
+    out, offsets = [], [0]
+    for k, p in enumerate(paths):
+        a = _xyz(p, f"path {k}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"path {k} has a non-finite coordinate")
+        if len(a) > 1:
+            keep = np.ones(len(a), bool)
+            keep[1:] = (a[1:] != a[:-1]).any(axis=1)
+            a = a[keep]
+        if len(a) < 2:
+            raise ValueError(f"path {k} has fewer than 2 points (after removing consecutive duplicates)")
+        out.append(a)
+        offsets.append(offsets[-1] + len(a))
+    coords = np.concatenate(out) if out else np.zeros((0, 3), np.float32)
+    return np.ascontiguousarray(coords, dtype=np.float32), np.asarray(offsets, dtype=np.uint32)
+
+
+def line_args(paths, width_px, rgba, cap):
+    """-> (coords (M, 3) f32, offsets (P + 1,) u32, width, rgba (4,) u8, cap code)"""
+    if cap not in CAPS:
+        raise ValueError(f"cap must be one of {sorted(CAPS)}, got {cap!r}")
+    if isinstance(width_px, bool) or not isinstance(width_px, numbers.Real):
+        raise TypeError(f"width_px must be a number, got {type(width_px).__name__}")
+    width, _ = _size(width_px, 0, "width_px")
+    dcol, _ = _colour(rgba, 0, False)
+    coords, offsets = pack_lines(paths)
+    return coords, offsets, width, dcol, CAPS[cap]

@@ -20,7 +20,8 @@ SYMBOLS = [
     "vf_terrain_create", "vf_terrain_destroy", "vf_terrain_set_uniforms", "vf_terrain_set_height",
     "vf_terrain_set_height_device", "vf_terrain_set_shade_mode", "vf_terrain_set_shade_precision", "vf_terrain_set_raster_groups", "vf_terrain_raster_groups", "vf_terrain_set_shard", "vf_terrain_local_rows", "vf_terrain_set_tile_shard",
     "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
-    "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
+    "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
+    "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
     "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
@@ -67,6 +68,9 @@ _PROTOS = {
     "vf_terrain_set_shard": (_i, [_vp, _u32, _u32, _u32]),
     "vf_terrain_local_rows": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_set_tile_shard": (_i, [_vp, _u32, _u32, _u32]),
+    "vf_terrain_add_points": (_i, [_vp, _vp, _u32, _vp, _vp, _f, _vp, _i, _i, C.POINTER(_u32)]),
+    "vf_terrain_add_lines": (_i, [_vp, _vp, _vp, _u32, _f, _vp, _i, _i, C.POINTER(_u32)]),
+    "vf_terrain_clear_overlays": (_i, [_vp]),
     "vf_terrain_local_tiles": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_read_tiles": (_i, [_vp, _vp, _u32, _u32]),
     "vf_tile_layout": (_i, [_u32, _u32, _u32, _u32, _u32, _vp, _u32, C.POINTER(_u32)]),
@@ -248,6 +252,34 @@ class Terrain:
     def set_tile_shard(self, rank, nranks, skew=3):
         """`skew`: the layout word skew | stripe_log2 << 16 (include/vf_hip.h, VF_TILE_LAYOUT)."""
         self._check(self.lib.vf_terrain_set_tile_shard(self.t, rank, nranks, skew))
+
+    def add_points(self, xyz, size_px=5.0, rgba=(255, 255, 255, 255), shape=0, drape=False):
+        """Point layer (include/vf_hip.h, overlays): xyz (N, 3); size_px a float or (N,); rgba a 4-tuple or (N, 4) uint8;
+        shape 0 circle / 1 square.  Returns the layer id."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        sizes = None if np.isscalar(size_px) else np.ascontiguousarray(size_px, dtype=np.float32).reshape(n)
+        cols = np.ascontiguousarray(rgba, dtype=np.uint8)
+        per = cols.ndim == 2
+        default = (C.c_uint8 * 4)(*([255] * 4 if per else [int(v) for v in cols.reshape(4)]))
+        layer = _u32()
+        self._check(self.lib.vf_terrain_add_points(self.t, xyz.ctypes.data, n, None if sizes is None else sizes.ctypes.data,
+                                                   cols.ctypes.data if per else None, float(size_px) if sizes is None else 0.0,
+                                                   C.cast(default, _vp), int(shape), int(bool(drape)), C.byref(layer)))
+        return layer.value
+
+    def add_lines(self, coords, offsets, width_px=2.0, rgba=(255, 255, 255, 255), cap=2, drape=False):
+        """Polyline layer: coords (M, 3), offsets (P + 1,) uint32 (vulkan_forge.pack_lines); cap 0 butt / 1 square / 2 round."""
+        coords = np.ascontiguousarray(coords, dtype=np.float32).reshape(-1, 3)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
+        col = (C.c_uint8 * 4)(*[int(v) for v in rgba])
+        layer = _u32()
+        self._check(self.lib.vf_terrain_add_lines(self.t, coords.ctypes.data, offsets.ctypes.data, max(len(offsets) - 1, 0),
+                                                  float(width_px), C.cast(col, _vp), int(cap), int(bool(drape)), C.byref(layer)))
+        return layer.value
+
+    def clear_overlays(self):
+        self._check(self.lib.vf_terrain_clear_overlays(self.t))
 
     def tile_times(self):
         """ms the last frame spent on each local tile (storage order: vf_tile_layout's)."""

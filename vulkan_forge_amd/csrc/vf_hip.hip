@@ -2,6 +2,7 @@
 // Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC + the -mllvm code-generation switches of HIPCC_TUNING
 #include "../../include/vf_hip.h"
 #include "vf_kernels.h"
+#include "vf_overlay.h"
 
 #include <algorithm>
 #include <cmath>
@@ -343,6 +344,21 @@ struct vf_terrain {
     // vf_dist_exchange_bands: the chunks this rank receives in the all-to-all ([nranks][chunk_tiles] tile slots) and the band it stitches from them
     uint8_t *d_xrecv = nullptr, *d_xband = nullptr;
     size_t xrecv_bytes = 0, xband_bytes = 0;
+    // Overlays (vf_terrain_add_points / _add_lines, vf_overlay.h): made by the first add, freed by vf_terrain_clear_overlays -- a handle
+    // without overlays holds none of it and launches nothing for them.
+    struct Overlays {
+        uint32_t nprims = 0, cap = 0, features = 0, layers = 0;
+        OvIn *d_in = nullptr;                // [cap] primitives as added, in feature order
+        OvPrim *d_prim = nullptr;            // [cap] ... as the frame sees them (k_ov_setup)
+        uint2 *d_box = nullptr;              // [cap] bin rectangle
+        uint32_t *d_cnt = nullptr;           // [nbins] pairs per bin (zero between frames)
+        uint32_t *d_start = nullptr;         // [nbins + 1] each bin's slice of the pair list; [nbins] = pairs in all
+        float *d_decode = nullptr;           // 256 sRGB8 -> linear (SrgbTables::decode)
+        uint32_t *d_list = nullptr;          // pair list (primitive indices)
+        size_t list_cap = 0;
+        uint32_t *h_total = nullptr;         // pinned: the frame's pair count (the list is sized by it)
+        hipEvent_t counted = nullptr;
+    } ov;
 };
 
 extern "C" {
@@ -550,6 +566,17 @@ static int refresh_tables(vf_terrain *t, hipStream_t s)
     return VF_OK;
 }
 
+// the overlay state: gone, as if the handle never had overlays (the caller has synchronised)
+static void ov_release(vf_terrain *t)
+{
+    vf_terrain::Overlays &O = t->ov;
+    void *ptrs[] = { O.d_in, O.d_prim, O.d_box, O.d_cnt, O.d_start, O.d_decode, O.d_list };
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (O.h_total) (void)hipHostFree(O.h_total);
+    if (O.counted) (void)hipEventDestroy(O.counted);
+    O = vf_terrain::Overlays();
+}
+
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
@@ -645,6 +672,7 @@ void vf_terrain_destroy(vf_terrain *t)
     if (t->entry) (void)hipEventDestroy(t->entry);
     if (t->copied) (void)hipEventDestroy(t->copied);
     for (auto &g : t->gprobe) { if (g.a) (void)hipEventDestroy(g.a); if (g.b) (void)hipEventDestroy(g.b); }
+    ov_release(t);
     delete t;
 }
 
@@ -755,6 +783,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!is_pow2(band_h) || band_h < (uint32_t)kTileH) return fail(VF_ERR_INVALID, "band_h must be a power of two >= 64 (the tile height)");
+    if (t->ov.layers) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
     t->inputs_gen++;
@@ -886,6 +915,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!layout_valid(skew)) return fail(VF_ERR_INVALID, "layout word is neither VF_TILE_LAYOUT(skew < 65536, stripe_log2 <= 15) nor a registered stripe map");
+    if (t->ov.layers) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
@@ -1198,6 +1228,39 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
     return VF_OK;
 }
 
+// The overlay pass of a frame (vf_overlay.h), on the draw stream behind the tile kernels.  The pair list is sized by the frame's pair
+// count, which the host reads back between the scan and the scatter: a handle with overlays waits once per frame for that word.
+static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P)
+{
+    vf_terrain::Overlays &O = t->ov;
+    const uint32_t nbx = (t->W + kOvBin - 1u) / kOvBin, nby = (t->H + kOvBin - 1u) / kOvBin, nbins = nbx * nby;
+    const dim3 per_prim((O.nprims + 255u) / 256u), threads(256);
+    hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx);
+    hipLaunchKernelGGL(k_ov_scan, dim3(1), dim3(1024), 0, s, nbins, O.d_cnt, O.d_start);
+    VF_HIP_TRY(hipGetLastError());
+    VF_HIP_TRY(hipMemcpyAsync(O.h_total, O.d_start + nbins, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipEventRecord(O.counted, s));
+    VF_HIP_TRY(hipEventSynchronize(O.counted));
+    const uint32_t total = *O.h_total;
+    if (total == 0u) return VF_OK;                          // (nothing on screen: the counts are zero again, the frame stays as drawn)
+    if (total == 0xFFFFFFFFu) return fail(VF_ERR_NOMEM, "overlays: more than 2^32 - 2 (primitive, screen bin) pairs in one frame");
+    if (total > O.list_cap) {
+        if (O.d_list) { (void)hipFree(O.d_list); O.d_list = nullptr; O.list_cap = 0; }
+        const size_t want = (size_t)total + total / 2u + 4096u;
+        const hipError_t e = hipMalloc(&O.d_list, want * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipMemsetAsync(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t), s);
+            return fail(VF_ERR_NOMEM, std::string("overlay pair list allocation failed: ") + hipGetErrorString(e));
+        }
+        O.list_cap = want;
+    }
+    hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.d_box, nbx, O.d_start, O.d_cnt, O.d_list);
+    hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
+                       t->ctx->d_thresh, t->d_rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool write_vis)
 {
     const FrameParams &P = K.P;
@@ -1314,6 +1377,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool wri
     }
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev[3], s)); t->timed_frames++; }
+    if (t->ov.nprims && !write_vis) { const int orc = overlay_pass(t, s, P); if (orc != VF_OK) return orc; }   // (visibility / diagnostics frames: none)
     VF_HIP_TRY(hipEventRecord(S.drawn, s));
     VF_HIP_TRY(hipGetLastError());
     std::memcpy(S.u_used, t->u, sizeof S.u_used);           // the camera this set's tile times (being measured now) belong to
@@ -1511,6 +1575,139 @@ int vf_terrain_sync(vf_terrain *t)
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    return VF_OK;
+}
+
+// ---- overlays (vf_overlay.h) ---------------------------------------------------------------------
+
+static float ov_clamp_px(float v) { return std::fmin(std::fmax(v, 1.0f), 64.0f); }
+
+// append primitives (feature order) to the handle's overlay array; the first call makes the overlay state
+static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *layer_id)
+{
+    vf_terrain::Overlays &O = t->ov;
+    if ((uint64_t)O.nprims + add.size() > kOvMaxPrims)
+        return fail(VF_ERR_INVALID, "overlays: more than 2^24 primitives on one handle (a point is one, a polyline of m vertices up to 2m)");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));   // (a frame in flight reads the arrays)
+    if (!O.d_cnt) {
+        const uint32_t nbins = ((t->W + kOvBin - 1u) / kOvBin) * ((t->H + kOvBin - 1u) / kOvBin);
+        hipError_t e = hipMalloc(&O.d_cnt, (size_t)nbins * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&O.d_start, ((size_t)nbins + 1u) * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&O.d_decode, 256 * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(O.d_decode, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&O.h_total, sizeof(uint32_t), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&O.counted, hipEventDisableTiming);
+        if (e != hipSuccess) { ov_release(t); return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e)); }
+    }
+    const uint32_t need = O.nprims + (uint32_t)add.size();
+    if (need > O.cap) {
+        const uint32_t cap = std::min<uint32_t>(kOvMaxPrims, std::max<uint32_t>({ need, 2u * O.cap, 1024u }));
+        OvIn *in = nullptr; OvPrim *pr = nullptr; uint2 *bx = nullptr;
+        hipError_t e = hipMalloc(&in, (size_t)cap * sizeof(OvIn));
+        if (e == hipSuccess) e = hipMalloc(&pr, (size_t)cap * sizeof(OvPrim));
+        if (e == hipSuccess) e = hipMalloc(&bx, (size_t)cap * sizeof(uint2));
+        if (e == hipSuccess && O.nprims) e = hipMemcpy(in, O.d_in, (size_t)O.nprims * sizeof(OvIn), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            for (void *p : { (void *)in, (void *)pr, (void *)bx }) if (p) (void)hipFree(p);
+            return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
+        }
+        for (void *p : { (void *)O.d_in, (void *)O.d_prim, (void *)O.d_box }) if (p) (void)hipFree(p);
+        O.d_in = in; O.d_prim = pr; O.d_box = bx; O.cap = cap;
+    }
+    if (!add.empty()) VF_HIP_TRY(hipMemcpy(O.d_in + O.nprims, add.data(), add.size() * sizeof(OvIn), hipMemcpyHostToDevice));
+    O.nprims = need;
+    if (layer_id) *layer_id = O.layers;
+    O.layers++;
+    return VF_OK;
+}
+
+static uint32_t ov_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
+
+static int ov_usable(const vf_terrain *t)
+{
+    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "overlays need a whole-frame handle: sharded compositing is not supported");
+    return VF_OK;
+}
+
+int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const float *size_px, const uint8_t *rgba, float default_size,
+                          const uint8_t default_rgba[4], int shape, int drape, uint32_t *layer_id)
+{
+    if (!t || (!xyz && n) || (!rgba && !default_rgba)) return fail(VF_ERR_INVALID, "NULL argument");
+    if (shape != VF_SHAPE_CIRCLE && shape != VF_SHAPE_SQUARE) return fail(VF_ERR_INVALID, "shape must be VF_SHAPE_CIRCLE or VF_SHAPE_SQUARE");
+    if (int rc = ov_usable(t)) return rc;
+    if (!size_px && !std::isfinite(default_size)) return fail(VF_ERR_INVALID, "size_px must be finite");
+    std::vector<OvIn> add;
+    add.reserve(n);
+    uint32_t feature = t->ov.features;
+    for (uint32_t k = 0; k < n; ++k) {
+        const float *p = xyz + 3u * k;
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;     // (dropped, ROADMAP V4.1)
+        const float sz = size_px ? size_px[k] : default_size;
+        if (!std::isfinite(sz)) return fail(VF_ERR_INVALID, "size_px must be finite");
+        OvIn q{};
+        for (int c = 0; c < 3; ++c) { q.p0[c] = p[c]; q.p1[c] = p[c]; }
+        q.size = ov_clamp_px(sz) * 0.5f;
+        q.flags = (shape == VF_SHAPE_SQUARE ? kOvSquare : kOvCircle) | (drape ? kOvDrape : 0u);
+        q.rgba = ov_rgba(rgba ? rgba + 4u * k : default_rgba);
+        q.feature = feature++;
+        add.push_back(q);
+    }
+    const int rc = ov_append(t, add, layer_id);
+    if (rc == VF_OK) t->ov.features = feature;
+    return rc;
+}
+
+int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_offsets, uint32_t npaths, float width_px,
+                         const uint8_t rgba[4], int cap, int drape, uint32_t *layer_id)
+{
+    if (!t || !path_offsets || !rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    if (cap != VF_CAP_BUTT && cap != VF_CAP_SQUARE && cap != VF_CAP_ROUND) return fail(VF_ERR_INVALID, "cap must be VF_CAP_BUTT, VF_CAP_SQUARE or VF_CAP_ROUND");
+    if (!std::isfinite(width_px)) return fail(VF_ERR_INVALID, "width_px must be finite");
+    if (int rc = ov_usable(t)) return rc;
+    if (npaths && !xyz) return fail(VF_ERR_INVALID, "NULL argument");
+    std::vector<OvIn> add;
+    uint32_t feature = t->ov.features;
+    const float hw = ov_clamp_px(width_px) * 0.5f;
+    const uint32_t base = (drape ? kOvDrape : 0u);
+    for (uint32_t p = 0; p < npaths; ++p) {
+        const uint32_t v0 = path_offsets[p], v1 = path_offsets[p + 1];
+        if (v1 < v0 || v1 - v0 < 2u) return fail(VF_ERR_INVALID, "every path needs at least 2 vertices (path_offsets ascending)");
+        for (uint32_t v = v0; v < v1; ++v)
+            for (int c = 0; c < 3; ++c)
+                if (!std::isfinite(xyz[3u * v + c])) return fail(VF_ERR_INVALID, "a line vertex is not finite");
+        if ((uint64_t)add.size() + 2ull * (v1 - v0) > kOvMaxPrims)
+            return fail(VF_ERR_INVALID, "overlays: more than 2^24 primitives on one handle (a point is one, a polyline of m vertices up to 2m)");
+        for (uint32_t v = v0; v < v1; ++v) {
+            const bool end = v == v0 || v + 1u == v1;
+            if (!end || cap == VF_CAP_ROUND) {                // disc: round join / round cap
+                OvIn q{};
+                for (int c = 0; c < 3; ++c) { q.p0[c] = xyz[3u * v + c]; q.p1[c] = q.p0[c]; }
+                q.size = hw; q.flags = kOvCircle | base; q.rgba = ov_rgba(rgba); q.feature = feature;
+                add.push_back(q);
+            }
+            if (v + 1u < v1) {                                // butt segment v -> v + 1 (square caps extend the path's first / last one)
+                OvIn q{};
+                for (int c = 0; c < 3; ++c) { q.p0[c] = xyz[3u * v + c]; q.p1[c] = xyz[3u * (v + 1u) + c]; }
+                q.size = hw; q.rgba = ov_rgba(rgba); q.feature = feature;
+                q.flags = kOvSegment | base | (cap == VF_CAP_SQUARE && v == v0 ? kOvExt0 : 0u) | (cap == VF_CAP_SQUARE && v + 2u == v1 ? kOvExt1 : 0u);
+                add.push_back(q);
+            }
+        }
+        feature++;
+    }
+    const int rc = ov_append(t, add, layer_id);
+    if (rc == VF_OK) t->ov.features = feature;
+    return rc;
+}
+
+int vf_terrain_clear_overlays(vf_terrain *t)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    ov_release(t);
     return VF_OK;
 }
 

@@ -1,0 +1,341 @@
+// vf_overlay.h -- point and polyline overlays composited over the terrain frame (DESIGN.md "Overlays").
+//
+// Every overlay feature is cut into primitives when it is added (host, vf_hip.hip): a point is one circle or square, a polyline is
+// its butt segments plus a disc (a circle of radius width/2) at every interior vertex and, for round caps, at both ends.  The
+// primitives of all layers lie in ONE array in feature order (layers in insertion order, features in input order, a feature's
+// primitives next to each other), so "feature order" is "primitive index order".  Per frame, on the draw stream behind the tile kernel:
+//   k_ov_setup      one thread per primitive: drape, vertex transform, near / far clipping, viewport, exact screen geometry,
+//                   a conservative pixel box, and one count per 16x16 screen bin the box reaches
+//   k_ov_scan       one workgroup: exclusive scan of the bin counts -> each bin's slice of the pair list (and the total, for the host)
+//   k_ov_scatter    one thread per primitive: its index into the slice of every bin its box reaches (atomic slots: any order)
+//   k_ov_composite  one workgroup per bin: the bin's indices sorted ascending in LDS (bitonic; a bin with more than kOvSortCap of
+//                   them is walked in windows of kOvSortCap consecutive primitive indices, each sorted), so every pixel sees its
+//                   primitives in feature order whatever the scatter's order; coverage folded with max over a feature's primitives,
+//                   blended in linear light, encoded once.  Pixels no feature covers are never written.
+// All arithmetic is binary32 in the order DESIGN.md states (compiled with -ffp-contract=off); tests/overlay_model/overlay_model.c
+// is the same contract on the CPU and the GPU frames equal it bit for bit.
+#pragma once
+#include "vf_device.h"
+
+namespace vf {
+
+constexpr uint32_t kOvBin = 16;                 // screen bin = 16 x 16 pixels = one composite workgroup (one pixel per thread)
+constexpr uint32_t kOvSortCap = 4096;           // indices a bin sorts in LDS at once
+constexpr uint32_t kOvMaxPrims = 1u << 24;      // primitive budget of a handle (all layers)
+constexpr uint32_t kOvCircle = 0u, kOvSquare = 1u, kOvSegment = 2u;
+constexpr uint32_t kOvKindMask = 3u, kOvDrape = 4u, kOvExt0 = 8u, kOvExt1 = 16u;
+
+// one primitive as added (host -> HBM once): world-space vertices, y an offset above the surface when kOvDrape is set
+struct OvIn {
+    float p0[3];
+    float p1[3];           // segment end (segments only)
+    float size;            // circle / square: r = clamp(size_px, 1, 64) / 2; segment: hw = clamp(width_px, 1, 64) / 2
+    uint32_t flags;        // kind | kOvDrape | kOvExt0 / kOvExt1 (square cap: the segment reaches hw past its path's first / last vertex)
+    uint32_t rgba;         // sRGB8 bytes, r | g << 8 | b << 16 | alpha << 24
+    uint32_t feature;      // feature number (ascending with the primitive index; equal for the primitives of one polyline)
+    uint32_t pad[2];
+};
+static_assert(sizeof(OvIn) == 48, "OvIn layout is shared with tests/overlay_model");
+
+// one primitive as a frame sees it (k_ov_setup)
+struct OvPrim {
+    float4 g;              // circle / square: (cx, cy, r, 0); segment: (ax, ay, ux, uy) -- start and unit direction
+    float4 h;              // segment: (L, hw, e0, e1)
+    uint32_t kind, rgba, feature, pad;
+};
+static_assert(sizeof(OvPrim) == 48, "OvPrim is staged in LDS");
+
+// ---- drape: the rendered surface's height under world (x, z) -----------------------------------------
+__device__ __forceinline__ float ov_drape(const FrameParams &P, const AxisTables &A, float x, float z)
+{
+    float mx = x / P.spacing, mz = z / P.spacing;
+    mx = fminf(fmaxf(mx, -1.5f), 1.5f);
+    mz = fminf(fmaxf(mz, -1.5f), 1.5f);
+    const float gx = (mx + 1.5f) / P.step, gz = (mz + 1.5f) / P.step;
+    int i = (int)floorf(gx), j = (int)floorf(gz);
+    i = min(max(i, 0), (int)P.nm1 - 1);
+    j = min(max(j, 0), (int)P.nm1 - 1);
+    const float fx = gx - (float)i, fz = gz - (float)j;
+    const uint32_t ui = (uint32_t)i, uj = (uint32_t)j;
+    if (fx + fz <= 1.0f) {                                              // triangle (a, b, c)
+        const float ha = displaced_height(A, P.tex, P.tw, ui, uj);
+        const float hb = displaced_height(A, P.tex, P.tw, ui + 1u, uj);
+        const float hc = displaced_height(A, P.tex, P.tw, ui, uj + 1u);
+        return (ha + fx * (hb - ha)) + fz * (hc - ha);
+    }
+    const float hb = displaced_height(A, P.tex, P.tw, ui + 1u, uj);     // triangle (b, c, d)
+    const float hc = displaced_height(A, P.tex, P.tw, ui, uj + 1u);
+    const float hd = displaced_height(A, P.tex, P.tw, ui + 1u, uj + 1u);
+    return (hd + (1.0f - fx) * (hc - hd)) + (1.0f - fz) * (hb - hd);
+}
+
+__device__ __forceinline__ void ov_clip(const FrameParams &P, const AxisTables &A, const float p[3], bool drape, float c[4])
+{
+    float y = p[1];
+    if (drape) y = ov_drape(P, A, p[0], p[2]) * P.exag + p[1];
+    float vp[4];
+    mat_vec(P.view, p[0], y, p[2], 1.0f, vp);
+    mat_vec(P.proj, vp[0], vp[1], vp[2], vp[3], c);
+}
+
+// pixel index range [lo, hi] of coordinate range [a, b] on an axis of n pixels (conservative; empty: lo > hi)
+__device__ __forceinline__ void ov_span(float a, float b, uint32_t n, int &lo, int &hi)
+{
+    const float lim = (float)n + 2.0f;
+    lo = (int)floorf(fminf(fmaxf(a, -2.0f), lim));
+    hi = (int)floorf(fminf(fmaxf(b, -2.0f), lim));
+    lo = max(lo, 0);
+    hi = min(hi, (int)n - 1);
+}
+
+__global__ __launch_bounds__(256) void k_ov_setup(FrameParams P, AxisTables A, uint32_t nprims, const OvIn *__restrict__ in,
+                                                  OvPrim *__restrict__ out, uint2 *__restrict__ box, uint32_t *__restrict__ cnt, uint32_t nbx)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nprims) return;
+    const OvIn q = in[i];
+    const uint32_t kind = q.flags & kOvKindMask;
+    const bool drape = (q.flags & kOvDrape) != 0u;
+    OvPrim o;
+    o.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f); o.h = o.g;
+    o.kind = kind; o.rgba = q.rgba; o.feature = q.feature; o.pad = 0u;
+    float x0 = 0.0f, x1 = -1.0f, y0 = 0.0f, y1 = -1.0f;                // conservative screen extent (empty by default)
+    float a[4];
+    ov_clip(P, A, q.p0, drape, a);
+    if (kind != kOvSegment) {
+        if (finite4(a[0], a[1], a[2], a[3]) && a[3] > 0.0f && !(a[2] < 0.0f) && !(a[2] > a[3])) {
+            const float rw = 1.0f / a[3];
+            const float sx = fmaf(a[0] * rw, P.hw, P.hw), sy = fmaf(-(a[1] * rw), P.hh, P.hh);
+            if (isfinite(sx) && isfinite(sy)) {
+                const float r = q.size, R = r + 1.0f;
+                o.g = make_float4(sx, sy, r, 0.0f);
+                x0 = sx - R; x1 = sx + R; y0 = sy - R; y1 = sy + R;
+            }
+        }
+    } else {
+        float b[4];
+        ov_clip(P, A, q.p1, drape, b);
+        bool keep = finite4(a[0], a[1], a[2], a[3]) && finite4(b[0], b[1], b[2], b[3]);
+        bool ext0 = (q.flags & kOvExt0) != 0u, ext1 = (q.flags & kOvExt1) != 0u;
+        for (int plane = 0; plane < 2 && keep; ++plane) {              // z >= 0, then z <= w; the crossing from the inside vertex outwards
+            const float da = plane == 0 ? a[2] : a[3] - a[2], db = plane == 0 ? b[2] : b[3] - b[2];
+            const bool ain = da >= 0.0f, bin = db >= 0.0f;
+            if (!ain && !bin) { keep = false; break; }
+            if (ain && bin) continue;
+            float *ou = ain ? b : a;
+            const float *inv = ain ? a : b;
+            const float di = ain ? da : db, dou = ain ? db : da;
+            const float t = di / (di - dou);
+            float r[4];
+            for (int k = 0; k < 4; ++k) r[k] = fmaf(t, ou[k] - inv[k], inv[k]);
+            for (int k = 0; k < 4; ++k) ou[k] = r[k];
+            if (ain) ext1 = false; else ext0 = false;                    // a clipped end has no cap
+        }
+        if (keep && a[3] > 0.0f && b[3] > 0.0f) {
+            const float rwa = 1.0f / a[3], rwb = 1.0f / b[3];
+            const float ax = fmaf(a[0] * rwa, P.hw, P.hw), ay = fmaf(-(a[1] * rwa), P.hh, P.hh);
+            const float bx = fmaf(b[0] * rwb, P.hw, P.hw), by = fmaf(-(b[1] * rwb), P.hh, P.hh);
+            const float ex = bx - ax, ey = by - ay;
+            const float L = sqrtf(ex * ex + ey * ey);
+            if (isfinite(ax) && isfinite(ay) && isfinite(bx) && isfinite(by) && L > 0.0f && isfinite(L)) {
+                const float hw = q.size, e0 = ext0 ? hw : 0.0f, e1 = ext1 ? hw : 0.0f;
+                o.g = make_float4(ax, ay, ex / L, ey / L);
+                o.h = make_float4(L, hw, e0, e1);
+                const float R = hw + fmaxf(e0, e1) + 1.0f;
+                x0 = fminf(ax, bx) - R; x1 = fmaxf(ax, bx) + R; y0 = fminf(ay, by) - R; y1 = fmaxf(ay, by) + R;
+            }
+        }
+    }
+    out[i] = o;
+    int px0 = 1, px1 = 0, py0 = 1, py1 = 0;
+    if (x0 <= x1) { ov_span(x0, x1, P.W, px0, px1); ov_span(y0, y1, P.H, py0, py1); }
+    if (px0 > px1 || py0 > py1) { box[i] = make_uint2(1u, 0u); return; }   // (bin x0 = 1 > x1 = 0: nothing)
+    const uint32_t bx0 = (uint32_t)px0 / kOvBin, bx1 = (uint32_t)px1 / kOvBin, by0 = (uint32_t)py0 / kOvBin, by1 = (uint32_t)py1 / kOvBin;
+    box[i] = make_uint2(bx0 | (by0 << 16), bx1 | (by1 << 16));
+    for (uint32_t by = by0; by <= by1; ++by)
+        for (uint32_t bx = bx0; bx <= bx1; ++bx) atomicAdd(&cnt[by * nbx + bx], 1u);
+}
+
+// exclusive scan of the bin counts into start[0..nbins), the total into start[nbins] (saturated at 2^32 - 1) and ovf[0]; counts reset to 0
+__global__ __launch_bounds__(1024) void k_ov_scan(uint32_t nbins, uint32_t *__restrict__ cnt, uint32_t *__restrict__ start)
+{
+    __shared__ uint32_t part[1024];
+    __shared__ unsigned long long carry;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) carry = 0ull;
+    __syncthreads();
+    for (uint32_t base = 0; base < nbins; base += 1024u) {
+        const uint32_t k = base + tid;
+        const uint32_t v = k < nbins ? cnt[k] : 0u;
+        part[tid] = v;
+        __syncthreads();
+        for (uint32_t d = 1; d < 1024u; d <<= 1) {                     // inclusive Hillis-Steele scan
+            const uint32_t add = tid >= d ? part[tid - d] : 0u;
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        const unsigned long long c = carry, excl = c + part[tid] - v;
+        if (k < nbins) { start[k] = excl > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)excl; cnt[k] = 0u; }
+        __syncthreads();
+        if (tid == 1023u) carry = c + part[1023];
+        __syncthreads();
+    }
+    if (tid == 0) start[nbins] = carry > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)carry;
+}
+
+__global__ __launch_bounds__(256) void k_ov_scatter(uint32_t nprims, const uint2 *__restrict__ box, uint32_t nbx,
+                                                    const uint32_t *__restrict__ start, uint32_t *__restrict__ cnt, uint32_t *__restrict__ list)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nprims) return;
+    const uint2 b = box[i];
+    const uint32_t bx0 = b.x & 0xFFFFu, by0 = b.x >> 16, bx1 = b.y & 0xFFFFu, by1 = b.y >> 16;
+    for (uint32_t by = by0; by <= by1 && bx0 <= bx1; ++by)
+        for (uint32_t bx = bx0; bx <= bx1; ++bx) {
+            const uint32_t bin = by * nbx + bx;
+            list[start[bin] + atomicAdd(&cnt[bin], 1u)] = i;
+        }
+}
+
+// coverage of pixel centre (qx, qy) by one primitive
+__device__ __forceinline__ float ov_cover(const OvPrim &p, float qx, float qy)
+{
+    float sd;
+    if (p.kind == kOvSegment) {
+        const float dx = qx - p.g.x, dy = qy - p.g.y;
+        const float u = dx * p.g.z + dy * p.g.w;
+        const float v = fabsf(dy * p.g.z - dx * p.g.w);
+        sd = fmaxf(v - p.h.y, fmaxf(-u - p.h.z, (u - p.h.x) - p.h.w));
+    } else {
+        const float dx = qx - p.g.x, dy = qy - p.g.y;
+        sd = p.kind == kOvCircle ? sqrtf(dx * dx + dy * dy) - p.g.z : fmaxf(fabsf(dx), fabsf(dy)) - p.g.z;
+    }
+    return fminf(fmaxf(0.5f - sd, 0.0f), 1.0f);
+}
+
+struct OvPixel {
+    float c[3];
+    bool touched;
+    uint32_t feature, rgba;
+    float cov;
+};
+
+// the feature in hand is done at this pixel: blend it (if it covers the pixel at all)
+__device__ __forceinline__ void ov_flush(OvPixel &S, const float *dec, const uint32_t *rgba, size_t o)
+{
+    if (!(S.cov > 0.0f)) return;
+    if (!S.touched) {
+        const uint32_t px = rgba[o];
+        S.c[0] = dec[px & 255u]; S.c[1] = dec[(px >> 8) & 255u]; S.c[2] = dec[(px >> 16) & 255u];
+        S.touched = true;
+    }
+    const float a = S.cov * ((float)(S.rgba >> 24) / 255.0f);
+    for (int k = 0; k < 3; ++k) {
+        const float s = dec[(S.rgba >> (8 * k)) & 255u];
+        S.c[k] = s * a + S.c[k] * (1.0f - a);
+    }
+}
+
+// bitonic sort of keys[0..m) ascending, m a power of two <= kOvSortCap (whole workgroup)
+__device__ __forceinline__ void ov_sort(uint32_t *keys, uint32_t m)
+{
+    for (uint32_t k = 2; k <= m; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
+                const uint32_t l = i ^ j;
+                if (l > i) {
+                    const uint32_t x = keys[i], y = keys[l];
+                    if ((x > y) == ((i & k) == 0u)) { keys[i] = y; keys[l] = x; }
+                }
+            }
+            __syncthreads();
+        }
+}
+
+__device__ __forceinline__ uint32_t ov_pow2(uint32_t n)
+{
+    uint32_t m = 1;
+    while (m < n) m <<= 1;
+    return m;
+}
+
+__global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
+                                                      uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
+                                                      const uint32_t *__restrict__ list, const float *__restrict__ decode,
+                                                      const float *__restrict__ thresh, uint32_t *__restrict__ rgba)
+{
+    __shared__ uint32_t keys[kOvSortCap];
+    __shared__ OvPrim recs[256];
+    __shared__ float sdec[256], sthr[256];
+    __shared__ uint32_t s_n, s_next;
+    // (built without the tuning switches this kernel takes exactly v0..v39 and a 64-bit shift by v39: the form isa_lint refuses, vf_device.h)
+    VF_RESERVE_VGPR(40);
+    const uint32_t bin = blockIdx.x, tid = threadIdx.x;
+    const uint32_t n = cnt[bin];
+    if (n == 0u) return;
+    sdec[tid] = decode[tid];
+    sthr[tid] = thresh[tid];
+    const uint32_t px = (bin % nbx) * kOvBin + (tid & (kOvBin - 1u)), py = (bin / nbx) * kOvBin + tid / kOvBin;
+    const bool on = px < W && py < H;
+    const size_t o = (size_t)py * W + px;
+    const float qx = (float)px + 0.5f, qy = (float)py + 0.5f;
+    OvPixel S;
+    S.c[0] = S.c[1] = S.c[2] = 0.0f; S.touched = false; S.feature = 0xFFFFFFFFu; S.rgba = 0u; S.cov = 0.0f;
+    const uint32_t *L = list + start[bin];
+    // composite keys[0..m) (sorted): records staged 256 at a time, every pixel walks them in order
+    auto run = [&](uint32_t m) {
+        for (uint32_t k0 = 0; k0 < m; k0 += 256u) {
+            __syncthreads();
+            if (k0 + tid < m) recs[tid] = prims[keys[k0 + tid]];
+            __syncthreads();
+            const uint32_t kn = min(256u, m - k0);
+            if (on)
+                for (uint32_t k = 0; k < kn; ++k) {
+                    const OvPrim &p = recs[k];
+                    if (p.feature != S.feature) { ov_flush(S, sdec, rgba, o); S.feature = p.feature; S.rgba = p.rgba; S.cov = 0.0f; }
+                    S.cov = fmaxf(S.cov, ov_cover(p, qx, qy));
+                }
+        }
+    };
+    if (n <= kOvSortCap) {
+        const uint32_t m = ov_pow2(n);
+        for (uint32_t k = tid; k < m; k += 256u) keys[k] = k < n ? L[k] : 0xFFFFFFFFu;
+        __syncthreads();
+        ov_sort(keys, m);
+        run(n);
+    } else {
+        // more than fit: windows of kOvSortCap consecutive primitive indices (indices are unique in a bin, so a window never holds more),
+        // each gathered, sorted and composited in turn; the next window starts at the smallest index beyond the current one
+        uint32_t lo = 0;
+        for (;;) {
+            __syncthreads();
+            if (tid == 0) { s_n = 0u; s_next = 0xFFFFFFFFu; }
+            __syncthreads();
+            uint32_t next = 0xFFFFFFFFu;
+            for (uint32_t k = tid; k < n; k += 256u) {
+                const uint32_t v = L[k];
+                if (v >= lo && v - lo < kOvSortCap) keys[atomicAdd(&s_n, 1u)] = v;
+                else if (v >= lo) next = min(next, v);
+            }
+            atomicMin(&s_next, next);
+            __syncthreads();
+            const uint32_t got = s_n, m = ov_pow2(got), nxt = s_next;
+            for (uint32_t k = got + tid; k < m; k += 256u) keys[k] = 0xFFFFFFFFu;
+            __syncthreads();
+            ov_sort(keys, m);
+            run(got);
+            if (nxt == 0xFFFFFFFFu) break;
+            lo = nxt;
+        }
+    }
+    if (on) {
+        ov_flush(S, sdec, rgba, o);
+        if (S.touched)
+            rgba[o] = srgb_encode(S.c[0], sthr) | (srgb_encode(S.c[1], sthr) << 8) | (srgb_encode(S.c[2], sthr) << 16) | 0xFF000000u;
+    }
+    __syncthreads();
+    if (tid == 0) cnt[bin] = 0u;                         // (the next frame's k_ov_setup counts from zero)
+}
+
+} // namespace vf

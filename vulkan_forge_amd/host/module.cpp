@@ -429,6 +429,36 @@ public:
     }
     void enable_timing(bool on) { Borrow b(busy); check(vf_terrain_enable_timing(t, on ? 1 : 0)); }
 
+    // extension: overlays over the terrain frame (include/vf_hip.h; argument rules: vulkan_forge_amd/_overlays.py)
+    uint32_t add_points(py::object xyz, py::object size_px, py::object rgba, py::object shape, bool drape)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("point_args")(xyz, size_px, rgba, shape);
+        py::array pts = a[0].cast<py::array>(), dcol = a[3].cast<py::array>();
+        const float dsize = a[1].cast<float>();
+        py::object sizes = a[2], cols = a[4];
+        const int shp = a[5].cast<int>();
+        const float *sz = sizes.is_none() ? nullptr : static_cast<const float *>(sizes.cast<py::array>().data());
+        const uint8_t *cl = cols.is_none() ? nullptr : static_cast<const uint8_t *>(cols.cast<py::array>().data());
+        Borrow b(busy);
+        uint32_t id = 0;
+        check(vf_terrain_add_points(t, static_cast<const float *>(pts.data()), (uint32_t)pts.shape(0), sz, cl, dsize,
+                                    static_cast<const uint8_t *>(dcol.data()), shp, drape ? 1 : 0, &id));
+        return id;
+    }
+    uint32_t add_lines(py::object paths, py::object width_px, py::object rgba, py::object cap, bool drape)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("line_args")(paths, width_px, rgba, cap);
+        py::array coords = a[0].cast<py::array>(), offsets = a[1].cast<py::array>(), col = a[3].cast<py::array>();
+        const float width = a[2].cast<float>();
+        const int cp = a[4].cast<int>();
+        Borrow b(busy);
+        uint32_t id = 0;
+        check(vf_terrain_add_lines(t, static_cast<const float *>(coords.data()), static_cast<const uint32_t *>(offsets.data()),
+                                   (uint32_t)(offsets.shape(0) - 1), width, static_cast<const uint8_t *>(col.data()), cp, drape ? 1 : 0, &id));
+        return id;
+    }
+    void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
+
     // src/terrain/mod.rs:537-546
     py::array_t<float> debug_uniforms_f32() const
     {
@@ -721,7 +751,12 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
         .def("set_shade_mode", &T::set_shade_mode, py::arg("mode"))
         .def("set_shade_precision", &T::set_shade_precision, py::arg("precision"))
         .def("enable_timing", &T::enable_timing, py::arg("on") = true)
-        .def("last_timings", &T::last_timings);
+        .def("last_timings", &T::last_timings)
+        .def("add_points", &T::add_points, py::arg("xyz"), py::kw_only(), py::arg("size_px") = 5.0f,
+             py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("shape") = "circle", py::arg("drape") = false)
+        .def("add_lines", &T::add_lines, py::arg("paths"), py::kw_only(), py::arg("width_px") = 2.0f,
+             py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("cap") = "round", py::arg("drape") = false)
+        .def("clear_overlays", &T::clear_overlays);
 }
 
 } // namespace
