@@ -239,6 +239,21 @@ int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const flo
 int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_offsets, uint32_t npaths, float width_px,
                          const uint8_t rgba[4], int cap, int drape, uint32_t *layer_id);
 int vf_terrain_clear_overlays(vf_terrain *t);
+/* Polygon overlays (new; the reference plans add_polygons in ROADMAP.md Milestone B2 and never implemented it): filled polygons with
+ * optional outlines, in the same layer order as points and lines.  The conventions, bit for bit, are DESIGN.md 4c.
+ *   vf_terrain_add_polygons: nfeatures polygons; polygon f is rings feature_offsets[f] .. feature_offsets[f + 1] - 1 (>= 1 each,
+ *     feature_offsets ascending, <= nrings), ring r is vertices ring_offsets[r] .. ring_offsets[r + 1] - 1 of xyz (>= 3 each, all
+ *     finite; the ring closes back to its first vertex by itself).  Any number of exteriors and holes: the fill rule is even-odd over
+ *     all of a polygon's rings, so orientation does not matter and a MultiPolygon is one polygon.  Fill colour: fill_rgba[4 nfeatures]
+ *     (one per polygon) or, if NULL, default_fill; both NULL: no fill.  line_rgba: the outline colour (NULL: no outline), drawn as
+ *     vf_terrain_add_lines of each closed ring with width line_width_px (clamped to [1, 64]), round caps and joins.  At least one of
+ *     fill and outline is required.  drape != 0: y is an offset above the rendered surface at each vertex (edges stay straight on
+ *     screen).  The layer holds every fill, in polygon order, then every outline.  Fills are clipped at the near plane only.  A fill
+ *     takes 1 + 2 primitives per ring edge of the 2^24 budget, an outline 2 per ring vertex + 1.  A handle with polygon fills reads
+ *     back, with the pair count, the number of (polygon, screen bin) backdrop masks of the frame (the same single wait per frame). */
+int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *ring_offsets, uint32_t nrings, const uint32_t *feature_offsets,
+                            uint32_t nfeatures, const uint8_t *fill_rgba, const uint8_t default_fill[4], const uint8_t line_rgba[4],
+                            float line_width_px, int drape, uint32_t *layer_id);
 
 /* copy_texture_to_buffer + map + un-pad (src/terrain/mod.rs:439-485): local rows [y0, y0+rows)
  * into dst (rows*W*4 bytes).  Waits for the last render and for the copy (work the library queues behind the copy for the

@@ -1,0 +1,133 @@
+"""ctypes loader of the polygon fill CPU model (polygon_model.c), with layers that mix polygons, points and lines.
+
+    import polygon_model as pm
+    layers = pm.Layers(); layers.points(xyz, size_px=4); layers.polygons(polys, fill_rgba=(0, 90, 255, 160), line_rgba=(0, 0, 0, 255))
+    out = pm.composite(frame_rgba, uniforms, height, grid, layers)
+
+A polygon layer is what include/vf_hip.h documents for vf_terrain_add_polygons: every polygon's fill (one feature each, in order),
+then the outline of every ring as its own polyline feature -- the ring closed back to its first vertex, round caps.  Rings are used
+as given (vulkan_forge.pack_polygons does the duplicate and closing-vertex removal).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
+import overlay_model as om  # noqa: E402
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        src = os.path.join(HERE, "polygon_model.c")
+        dep = os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")
+        out = os.path.join(ROOT, "build", "libpgmodel.so")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(dep)):
+            tmp = out + f".{os.getpid()}.tmp"
+            subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
+            os.replace(tmp, out)
+        L = C.CDLL(out)
+        vp, u32, i = C.c_void_p, C.c_uint32, C.c_int
+        L.pgm_composite.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.pgm_composite.restype = i
+        L.pgm_fill_coverage.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, u32, vp, vp, i]
+        L.pgm_fill_coverage.restype = i
+        L.pgm_ring_edges.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, i]
+        L.pgm_ring_edges.restype = i
+        _lib = L
+    return _lib
+
+
+def _rings(poly):
+    """a polygon (one (k, 3) ring or a sequence of rings) -> list of (k, 3) float32 arrays"""
+    if isinstance(poly, np.ndarray) and poly.ndim == 2:
+        poly = [poly]
+    return [np.ascontiguousarray(r, np.float32).reshape(-1, 3) for r in poly]
+
+
+class Layers(om.Layers):
+    """Primitive records of points and lines (overlay model) plus fill features, in one feature order."""
+
+    def __init__(self):
+        super().__init__()
+        self.fills = []                                        # (feature, rgba word, drape, rings)
+
+    def polygons(self, polygons, fill_rgba=(255, 255, 255, 255), line_rgba=None, line_width_px=1.0, drape=False):
+        polys = [_rings(p) for p in polygons]
+        if fill_rgba is not None:
+            cols = np.asarray(fill_rgba, np.uint8)
+            cols = np.broadcast_to(cols, (len(polys), 4)) if cols.ndim == 1 else cols
+            for p, c in zip(polys, cols):
+                self.fills.append((self.feature, om._rgba_word(c), bool(drape), p))
+                self.feature += 1
+        if line_rgba is not None:
+            closed = [np.concatenate([r, r[:1]]) for p in polys for r in p]
+            self.lines(closed, width_px=line_width_px, rgba=line_rgba, cap="round", drape=drape)
+        return self
+
+
+def _pack(rings):
+    offs = np.zeros(len(rings) + 1, np.uint32)
+    offs[1:] = np.cumsum([len(r) for r in rings])
+    xyz = np.ascontiguousarray(np.concatenate(rings) if rings else np.zeros((0, 3), np.float32), np.float32)
+    return offs, xyz
+
+
+def composite(frame, uniforms, height, grid, layers):
+    """frame (H, W, 4) uint8 -> a new frame with the layers composited over it (the contract, on the CPU)."""
+    out = np.array(frame, np.uint8, copy=True, order="C")
+    H, W = out.shape[:2]
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    recs = np.ascontiguousarray(layers.array())
+    fills = layers.fills
+    feat = np.array([f[0] for f in fills], np.uint32)
+    cols = np.array([f[1] for f in fills], np.uint32)
+    drape = np.array([f[2] for f in fills], np.uint8)
+    rings = [r for f in fills for r in f[3]]
+    fr = np.zeros(len(fills) + 1, np.uint32)
+    fr[1:] = np.cumsum([len(f[3]) for f in fills])
+    offs, xyz = _pack(rings)
+    rc = lib().pgm_composite(out.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
+                             recs.ctypes.data, len(recs), len(fills), feat.ctypes.data, cols.ctypes.data, drape.ctypes.data,
+                             fr.ctypes.data, offs.ctypes.data, xyz.ctypes.data)
+    assert rc == 0
+    return out
+
+
+def fill_coverage(W, H, uniforms, height, grid, polygon, drape=False):
+    """(H, W) float32 coverage of one polygon's fill"""
+    cov = np.zeros((H, W), np.float32)
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    rings = _rings(polygon)
+    offs, xyz = _pack(rings)
+    rc = lib().pgm_fill_coverage(cov.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid, len(rings),
+                                 offs.ctypes.data, xyz.ctypes.data, int(bool(drape)))
+    assert rc == 0
+    return cov
+
+
+EDGE = ("x0", "y0", "ex", "ey", "il2", "s", "xmin", "xmax", "ymin", "ymax")
+
+
+def ring_edges(W, H, uniforms, height, grid, ring, drape=False):
+    """(n, 10) float32: one ring's screen edge set after near-plane clipping, columns EDGE"""
+    ring = np.ascontiguousarray(ring, np.float32).reshape(-1, 3)
+    out = np.zeros((2 * len(ring), 10), np.float32)
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    n = lib().pgm_ring_edges(out.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid, ring.ctypes.data,
+                             len(ring), int(bool(drape)))
+    assert n >= 0
+    return out[:n]

@@ -17,6 +17,7 @@ import numpy as _np
 from ._validate import grid as _grid
 from ._validate import png_path, size_wh
 from ._overlays import pack_lines  # noqa: F401  (paths -> (coords, offsets) as add_lines packs them)
+from ._overlays import pack_polygons  # noqa: F401  (polygons -> (coords, ring offsets, feature offsets) as add_polygons packs them)
 
 try:
     _ext = importlib.import_module("vulkan_forge_amd._vulkan_forge")
@@ -111,5 +112,5 @@ __all__ = [
     "Renderer", "TerrainSpike", "Scene", "render_triangle_rgba", "render_triangle_png", "make_terrain",
     "colormap_supported", "camera_look_at", "camera_perspective", "camera_view_proj",
     "enumerate_adapters", "device_probe", "dem_stats", "dem_normalize", "grid_generate", "generate_grid",
-    "pack_lines", "__version__",
+    "pack_lines", "pack_polygons", "__version__",
 ]

@@ -1,4 +1,4 @@
-"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines) and pack_lines.
+"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines / .add_polygons), pack_lines and pack_polygons.
 
 The extension calls these before it hands the arrays to the C-ABI (include/vf_hip.h, overlays); they need numpy only, no device.
 """
@@ -108,3 +108,60 @@ def line_args(paths, width_px, rgba, cap):
     dcol, _ = _colour(rgba, 0, False)
     coords, offsets = pack_lines(paths)
     return coords, offsets, width, dcol, CAPS[cap]
+
+
+def _ring(a, f, r):
+    """one ring -> (k, 3) float32 with consecutive duplicates and a closing vertex equal to the first removed"""
+    a = _xyz(a, f"polygon {f} ring {r}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"polygon {f} ring {r} has a non-finite coordinate")
+    if len(a) > 1:
+        keep = np.ones(len(a), bool)
+        keep[1:] = (a[1:] != a[:-1]).any(axis=1)
+        a = a[keep]
+    if len(a) > 1 and (a[-1] == a[0]).all():
+        a = a[:-1]
+    if len(np.unique(a, axis=0)) < 3:
+        raise ValueError(f"polygon {f} ring {r} has fewer than 3 distinct vertices (after removing duplicates and the closing vertex)")
+    return a
+
+
+def pack_polygons(polygons):
+    """Polygons -> (coords (M, 3) float32, ring_offsets (R + 1,) uint32, feature_offsets (F + 1,) uint32).
+
+    A polygon is one (k, 3) ring array or a sequence of rings: exteriors and holes in any number and orientation (the fill rule is
+    even-odd), so a MultiPolygon is one polygon.  Consecutive duplicate vertices are removed, and so is a closing vertex equal to the
+    first (rings close by themselves).  A ring with fewer than 3 distinct vertices, or with a non-finite coordinate, is refused."""
+    if isinstance(polygons, np.ndarray):
+        polygons = [polygons] if polygons.ndim == 2 else list(polygons)
+    out, rings, feats = [], [0], [0]
+    for f, poly in enumerate(polygons):
+        ring_list = [poly] if isinstance(poly, np.ndarray) and poly.ndim == 2 else list(poly)
+        if not ring_list:
+            raise ValueError(f"polygon {f} has no ring")
+        for r, ring in enumerate(ring_list):
+            a = _ring(ring, f, r)
+            out.append(a)
+            rings.append(rings[-1] + len(a))
+        feats.append(len(rings) - 1)
+    coords = np.concatenate(out) if out else np.zeros((0, 3), np.float32)
+    return (np.ascontiguousarray(coords, dtype=np.float32), np.asarray(rings, dtype=np.uint32), np.asarray(feats, dtype=np.uint32))
+
+
+def polygon_args(polygons, fill_rgba, line_rgba, line_width_px):
+    """-> (coords, ring_offsets, feature_offsets, default fill (4,) u8 or None, fills (F, 4) u8 or None, line rgba (4,) u8 or None,
+    line width)"""
+    if fill_rgba is None and line_rgba is None:
+        raise ValueError("fill_rgba and line_rgba cannot both be None: a polygon layer needs a fill, an outline or both")
+    if isinstance(line_width_px, bool) or not isinstance(line_width_px, numbers.Real):
+        raise TypeError(f"line_width_px must be a number, got {type(line_width_px).__name__}")
+    width, _ = _size(line_width_px, 0, "line_width_px")
+    coords, rings, feats = pack_polygons(polygons)
+    dfill = fills = line = None
+    if fill_rgba is not None:
+        dfill, fills = _colour(fill_rgba, len(feats) - 1, True)
+        if fills is not None:
+            dfill = None
+    if line_rgba is not None:
+        line, _ = _colour(line_rgba, 0, False)
+    return coords, rings, feats, dfill, fills, line, width

@@ -21,7 +21,7 @@ SYMBOLS = [
     "vf_terrain_set_height_device", "vf_terrain_set_shade_mode", "vf_terrain_set_shade_precision", "vf_terrain_set_raster_groups", "vf_terrain_raster_groups", "vf_terrain_set_shard", "vf_terrain_local_rows", "vf_terrain_set_tile_shard",
     "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
     "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
-    "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
+    "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
     "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
@@ -70,6 +70,7 @@ _PROTOS = {
     "vf_terrain_set_tile_shard": (_i, [_vp, _u32, _u32, _u32]),
     "vf_terrain_add_points": (_i, [_vp, _vp, _u32, _vp, _vp, _f, _vp, _i, _i, C.POINTER(_u32)]),
     "vf_terrain_add_lines": (_i, [_vp, _vp, _vp, _u32, _f, _vp, _i, _i, C.POINTER(_u32)]),
+    "vf_terrain_add_polygons": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _f, _i, C.POINTER(_u32)]),
     "vf_terrain_clear_overlays": (_i, [_vp]),
     "vf_terrain_local_tiles": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_read_tiles": (_i, [_vp, _vp, _u32, _u32]),
@@ -276,6 +277,23 @@ class Terrain:
         layer = _u32()
         self._check(self.lib.vf_terrain_add_lines(self.t, coords.ctypes.data, offsets.ctypes.data, max(len(offsets) - 1, 0),
                                                   float(width_px), C.cast(col, _vp), int(cap), int(bool(drape)), C.byref(layer)))
+        return layer.value
+
+    def add_polygons(self, coords, ring_offsets, feature_offsets, fill_rgba=(255, 255, 255, 255), line_rgba=None, line_width_px=1.0,
+                     drape=False):
+        """Polygon layer: coords (M, 3), ring_offsets (R + 1,), feature_offsets (F + 1,) uint32 (vulkan_forge.pack_polygons);
+        fill_rgba a 4-tuple, an (F, 4) uint8 array or None; line_rgba a 4-tuple or None.  Returns the layer id."""
+        coords = np.ascontiguousarray(coords, dtype=np.float32).reshape(-1, 3)
+        rings = np.ascontiguousarray(ring_offsets, dtype=np.uint32)
+        feats = np.ascontiguousarray(feature_offsets, dtype=np.uint32)
+        fills = None if fill_rgba is None else np.ascontiguousarray(fill_rgba, dtype=np.uint8)
+        per = fills is not None and fills.ndim == 2
+        default = None if fills is None or per else C.cast((C.c_uint8 * 4)(*[int(v) for v in fills.reshape(4)]), _vp)
+        line = None if line_rgba is None else C.cast((C.c_uint8 * 4)(*[int(v) for v in line_rgba]), _vp)
+        layer = _u32()
+        self._check(self.lib.vf_terrain_add_polygons(self.t, coords.ctypes.data, rings.ctypes.data, max(len(rings) - 1, 0), feats.ctypes.data,
+                                                     max(len(feats) - 1, 0), fills.ctypes.data if per else None, default, line,
+                                                     float(line_width_px), int(bool(drape)), C.byref(layer)))
         return layer.value
 
     def clear_overlays(self):

@@ -356,8 +356,18 @@ struct vf_terrain {
         float *d_decode = nullptr;           // 256 sRGB8 -> linear (SrgbTables::decode)
         uint32_t *d_list = nullptr;          // pair list (primitive indices)
         size_t list_cap = 0;
-        uint32_t *h_total = nullptr;         // pinned: the frame's pair count (the list is sized by it)
+        uint32_t *h_total = nullptr;         // pinned: the frame's pair count (the list is sized by it); [2..3] the mask words (fills)
         hipEvent_t counted = nullptr;
+        // polygon fills (vf_terrain_add_polygons): made by the first polygon layer
+        uint32_t nfill = 0, fill_cap = 0;    // fill features (each: one header record and two slots per ring edge)
+        uint32_t pg_lo = 0, pg_hi = 0;       // record index range that holds every fill record
+        std::vector<uint32_t> hdr;           // [nfill] each fill feature's header record index (host copy of d_pg_hdr)
+        uint32_t *d_pg_hdr = nullptr;        // [fill_cap]
+        uint4 *d_pg_fbox = nullptr;          // [fill_cap] folded feature box (zero between frames)
+        uint4 *d_pg_fbin = nullptr;          // [fill_cap] the frame's mask base and bin box of each fill feature
+        unsigned long long *d_pg_total = nullptr;   // the frame's mask words (zero between frames)
+        uint32_t *d_mask = nullptr;          // (feature, bin) backdrop masks, bit r: parity of row r's crossings right of the bin
+        size_t mask_cap = 0;
     } ov;
 };
 
@@ -570,7 +580,7 @@ static int refresh_tables(vf_terrain *t, hipStream_t s)
 static void ov_release(vf_terrain *t)
 {
     vf_terrain::Overlays &O = t->ov;
-    void *ptrs[] = { O.d_in, O.d_prim, O.d_box, O.d_cnt, O.d_start, O.d_decode, O.d_list };
+    void *ptrs[] = { O.d_in, O.d_prim, O.d_box, O.d_cnt, O.d_start, O.d_decode, O.d_list, O.d_pg_hdr, O.d_pg_fbox, O.d_pg_fbin, O.d_pg_total, O.d_mask };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (O.h_total) (void)hipHostFree(O.h_total);
     if (O.counted) (void)hipEventDestroy(O.counted);
@@ -1236,14 +1246,45 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P)
     const uint32_t nbx = (t->W + kOvBin - 1u) / kOvBin, nby = (t->H + kOvBin - 1u) / kOvBin, nbins = nbx * nby;
     const dim3 per_prim((O.nprims + 255u) / 256u), threads(256);
     hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx);
+    const dim3 per_slot((O.pg_hi - O.pg_lo + 255u) / 256u);
+    if (O.nfill) {                                          // fill edges and headers: binned with the rest
+        hipLaunchKernelGGL(k_pg_setup, per_slot, threads, 0, s, P, axis(t), O.pg_lo, O.pg_hi, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx, O.d_pg_fbox);
+        hipLaunchKernelGGL(k_pg_header, dim3((O.nfill + 255u) / 256u), threads, 0, s, P, O.nfill, O.d_pg_hdr, O.d_in, O.d_pg_fbox, O.d_pg_fbin,
+                           O.d_prim, O.d_box, O.d_cnt, nbx, O.d_pg_total);
+    }
     hipLaunchKernelGGL(k_ov_scan, dim3(1), dim3(1024), 0, s, nbins, O.d_cnt, O.d_start);
     VF_HIP_TRY(hipGetLastError());
     VF_HIP_TRY(hipMemcpyAsync(O.h_total, O.d_start + nbins, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (O.nfill) {
+        VF_HIP_TRY(hipMemcpyAsync(O.h_total + 2, O.d_pg_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        VF_HIP_TRY(hipMemsetAsync(O.d_pg_total, 0, sizeof(unsigned long long), s));
+    }
     VF_HIP_TRY(hipEventRecord(O.counted, s));
     VF_HIP_TRY(hipEventSynchronize(O.counted));
     const uint32_t total = *O.h_total;
+    unsigned long long words = 0;
+    if (O.nfill) std::memcpy(&words, O.h_total + 2, sizeof words);
     if (total == 0u) return VF_OK;                          // (nothing on screen: the counts are zero again, the frame stays as drawn)
     if (total == 0xFFFFFFFFu) return fail(VF_ERR_NOMEM, "overlays: more than 2^32 - 2 (primitive, screen bin) pairs in one frame");
+    if (words > 0xFFFFFFFFull) {
+        (void)hipMemsetAsync(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t), s);
+        return fail(VF_ERR_NOMEM, "overlays: polygon fills reach more than 2^32 - 1 (feature, screen bin) pairs in one frame");
+    }
+    if (words > O.mask_cap) {
+        if (O.d_mask) { (void)hipFree(O.d_mask); O.d_mask = nullptr; O.mask_cap = 0; }
+        const size_t want = (size_t)words + (size_t)words / 2u + 4096u;
+        const hipError_t e = hipMalloc(&O.d_mask, want * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            (void)hipMemsetAsync(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t), s);
+            return fail(VF_ERR_NOMEM, std::string("polygon mask allocation failed: ") + hipGetErrorString(e));
+        }
+        O.mask_cap = want;
+    }
+    if (words) {                                            // the backdrop: row crossings right of each bin, per fill feature
+        VF_HIP_TRY(hipMemsetAsync(O.d_mask, 0, (size_t)words * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_pg_backdrop, per_slot, threads, 0, s, t->H, O.pg_lo, O.pg_hi, O.d_in, O.d_prim, O.d_pg_fbin, O.d_mask);
+        hipLaunchKernelGGL(k_pg_prefix, dim3((O.nfill + 3u) / 4u), threads, 0, s, O.nfill, O.d_pg_fbin, O.d_mask);
+    }
     if (total > O.list_cap) {
         if (O.d_list) { (void)hipFree(O.d_list); O.d_list = nullptr; O.list_cap = 0; }
         const size_t want = (size_t)total + total / 2u + 4096u;
@@ -1256,7 +1297,7 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P)
     }
     hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.d_box, nbx, O.d_start, O.d_cnt, O.d_list);
     hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
-                       t->ctx->d_thresh, t->d_rgba);
+                       t->ctx->d_thresh, O.d_mask, t->d_rgba);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
 }
@@ -1597,7 +1638,7 @@ static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *laye
         if (e == hipSuccess) e = hipMalloc(&O.d_start, ((size_t)nbins + 1u) * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(&O.d_decode, 256 * sizeof(float));
         if (e == hipSuccess) e = hipMemcpy(O.d_decode, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&O.h_total, sizeof(uint32_t), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&O.h_total, 4 * sizeof(uint32_t), hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&O.counted, hipEventDisableTiming);
         if (e != hipSuccess) { ov_release(t); return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e)); }
     }
@@ -1659,6 +1700,29 @@ int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const flo
     return rc;
 }
 
+// the primitives of one polyline (its vertices in path order): butt segments, discs at interior vertices (round joins) and, for round
+// caps, at both ends; square caps extend the path's first / last segment
+static void ov_path(const std::vector<const float *> &path, float hw, uint32_t rgba, int cap, uint32_t base, uint32_t feature, std::vector<OvIn> &add)
+{
+    const size_t m = path.size();
+    for (size_t v = 0; v < m; ++v) {
+        const bool end = v == 0 || v + 1u == m;
+        if (!end || cap == VF_CAP_ROUND) {                    // disc: round join / round cap
+            OvIn q{};
+            for (int c = 0; c < 3; ++c) { q.p0[c] = path[v][c]; q.p1[c] = q.p0[c]; }
+            q.size = hw; q.flags = kOvCircle | base; q.rgba = rgba; q.feature = feature;
+            add.push_back(q);
+        }
+        if (v + 1u < m) {                                     // butt segment v -> v + 1 (square caps extend the path's first / last one)
+            OvIn q{};
+            for (int c = 0; c < 3; ++c) { q.p0[c] = path[v][c]; q.p1[c] = path[v + 1u][c]; }
+            q.size = hw; q.rgba = rgba; q.feature = feature;
+            q.flags = kOvSegment | base | (cap == VF_CAP_SQUARE && v == 0 ? kOvExt0 : 0u) | (cap == VF_CAP_SQUARE && v + 2u == m ? kOvExt1 : 0u);
+            add.push_back(q);
+        }
+    }
+}
+
 int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_offsets, uint32_t npaths, float width_px,
                          const uint8_t rgba[4], int cap, int drape, uint32_t *layer_id)
 {
@@ -1679,27 +1743,128 @@ int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_o
                 if (!std::isfinite(xyz[3u * v + c])) return fail(VF_ERR_INVALID, "a line vertex is not finite");
         if ((uint64_t)add.size() + 2ull * (v1 - v0) > kOvMaxPrims)
             return fail(VF_ERR_INVALID, "overlays: more than 2^24 primitives on one handle (a point is one, a polyline of m vertices up to 2m)");
-        for (uint32_t v = v0; v < v1; ++v) {
-            const bool end = v == v0 || v + 1u == v1;
-            if (!end || cap == VF_CAP_ROUND) {                // disc: round join / round cap
-                OvIn q{};
-                for (int c = 0; c < 3; ++c) { q.p0[c] = xyz[3u * v + c]; q.p1[c] = q.p0[c]; }
-                q.size = hw; q.flags = kOvCircle | base; q.rgba = ov_rgba(rgba); q.feature = feature;
-                add.push_back(q);
-            }
-            if (v + 1u < v1) {                                // butt segment v -> v + 1 (square caps extend the path's first / last one)
-                OvIn q{};
-                for (int c = 0; c < 3; ++c) { q.p0[c] = xyz[3u * v + c]; q.p1[c] = xyz[3u * (v + 1u) + c]; }
-                q.size = hw; q.rgba = ov_rgba(rgba); q.feature = feature;
-                q.flags = kOvSegment | base | (cap == VF_CAP_SQUARE && v == v0 ? kOvExt0 : 0u) | (cap == VF_CAP_SQUARE && v + 2u == v1 ? kOvExt1 : 0u);
-                add.push_back(q);
-            }
-        }
+        std::vector<const float *> path;
+        for (uint32_t v = v0; v < v1; ++v) path.push_back(xyz + 3u * v);
+        ov_path(path, hw, ov_rgba(rgba), cap, base, feature, add);
         feature++;
     }
     const int rc = ov_append(t, add, layer_id);
     if (rc == VF_OK) t->ov.features = feature;
     return rc;
+}
+
+// room for `more` fill features in the per-feature arrays of the polygon pass (the caller has synchronised)
+static int pg_reserve(vf_terrain *t, uint32_t more)
+{
+    vf_terrain::Overlays &O = t->ov;
+    const uint32_t need = O.nfill + more;
+    hipError_t e = hipSuccess;
+    if (!O.d_pg_total) {
+        e = hipMalloc(&O.d_pg_total, sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemset(O.d_pg_total, 0, sizeof(unsigned long long));
+    }
+    if (e == hipSuccess && need > O.fill_cap) {
+        const uint32_t cap = std::max<uint32_t>({ need, 2u * O.fill_cap, 256u });
+        uint32_t *hdr = nullptr; uint4 *fbox = nullptr, *fbin = nullptr;
+        e = hipMalloc(&hdr, (size_t)cap * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&fbox, (size_t)cap * sizeof(uint4));
+        if (e == hipSuccess) e = hipMalloc(&fbin, (size_t)cap * sizeof(uint4));
+        if (e == hipSuccess) e = hipMemset(fbox, 0, (size_t)cap * sizeof(uint4));
+        if (e == hipSuccess && O.nfill) e = hipMemcpy(hdr, O.hdr.data(), (size_t)O.nfill * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            for (void *p : { (void *)hdr, (void *)fbox, (void *)fbin }) if (p) (void)hipFree(p);
+        } else {
+            for (void *p : { (void *)O.d_pg_hdr, (void *)O.d_pg_fbox, (void *)O.d_pg_fbin }) if (p) (void)hipFree(p);
+            O.d_pg_hdr = hdr; O.d_pg_fbox = fbox; O.d_pg_fbin = fbin; O.fill_cap = cap;
+        }
+    }
+    if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("polygon overlay allocation failed: ") + hipGetErrorString(e));
+    return VF_OK;
+}
+
+int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *ring_offsets, uint32_t nrings, const uint32_t *feature_offsets,
+                            uint32_t nfeatures, const uint8_t *fill_rgba, const uint8_t default_fill[4], const uint8_t line_rgba[4],
+                            float line_width_px, int drape, uint32_t *layer_id)
+{
+    if (!t || !ring_offsets || !feature_offsets) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!fill_rgba && !default_fill && !line_rgba) return fail(VF_ERR_INVALID, "a polygon layer needs a fill colour, an outline colour or both");
+    if (line_rgba && !std::isfinite(line_width_px)) return fail(VF_ERR_INVALID, "line_width_px must be finite");
+    if (int rc = ov_usable(t)) return rc;
+    if (nrings && !xyz) return fail(VF_ERR_INVALID, "NULL argument");
+    const bool fill = fill_rgba || default_fill;
+    for (uint32_t f = 0; f < nfeatures; ++f) {
+        const uint32_t r0 = feature_offsets[f], r1 = feature_offsets[f + 1];
+        if (r1 <= r0 || r1 > nrings) return fail(VF_ERR_INVALID, "every polygon needs at least 1 ring (feature_offsets ascending, <= nrings)");
+        for (uint32_t r = r0; r < r1; ++r) {
+            const uint32_t v0 = ring_offsets[r], v1 = ring_offsets[r + 1];
+            if (v1 < v0 || v1 - v0 < 3u) return fail(VF_ERR_INVALID, "every ring needs at least 3 vertices (ring_offsets ascending)");
+            for (uint32_t v = v0; v < v1; ++v)
+                for (int c = 0; c < 3; ++c)
+                    if (!std::isfinite(xyz[3u * v + c])) return fail(VF_ERR_INVALID, "a polygon vertex is not finite");
+        }
+    }
+    const char *too_many = "overlays: more than 2^24 primitives on one handle (a polygon fill is 1 + 2 per ring edge, its outline up to 2 per ring vertex + 1)";
+    vf_terrain::Overlays &O = t->ov;
+    std::vector<OvIn> add;
+    std::vector<uint32_t> hdr;
+    uint32_t feature = O.features;
+    const uint32_t base = drape ? kOvDrape : 0u;
+    if (fill)                                                 // fills: a header, then the two slots of every ring edge, in ring order
+        for (uint32_t f = 0; f < nfeatures; ++f) {
+            const uint32_t k = O.nfill + (uint32_t)hdr.size();
+            float kbits;
+            std::memcpy(&kbits, &k, sizeof kbits);
+            uint64_t n = 1;
+            for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) n += 2ull * (ring_offsets[r + 1] - ring_offsets[r]);
+            if ((uint64_t)O.nprims + add.size() + n > kOvMaxPrims) return fail(VF_ERR_INVALID, too_many);
+            hdr.push_back(O.nprims + (uint32_t)add.size());
+            OvIn h{};
+            h.size = kbits; h.flags = kOvPoly | kPgHeader; h.rgba = ov_rgba(fill_rgba ? fill_rgba + 4u * f : default_fill); h.feature = feature;
+            add.push_back(h);
+            for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) {
+                const uint32_t v0 = ring_offsets[r], nv = ring_offsets[r + 1] - v0, first = O.nprims + (uint32_t)add.size();
+                for (uint32_t e = 0; e < nv; ++e)
+                    for (uint32_t slot = 0; slot < 2u; ++slot) {
+                        OvIn q{};
+                        for (int c = 0; c < 3; ++c) { q.p0[c] = xyz[3u * (v0 + e) + c]; q.p1[c] = xyz[3u * (v0 + (e + 1u) % nv) + c]; }
+                        q.size = kbits; q.flags = kOvPoly | base | (slot ? kPgClose : 0u); q.feature = feature;
+                        q.pad[0] = first; q.pad[1] = nv;
+                        add.push_back(q);
+                    }
+            }
+            feature++;
+        }
+    const uint32_t nfillrec = (uint32_t)add.size();
+    if (line_rgba) {                                          // outlines: add_lines of each ring closed back to its first vertex, round caps
+        const float hw = ov_clamp_px(line_width_px) * 0.5f;
+        for (uint32_t f = 0; f < nfeatures; ++f)
+            for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) {
+                const uint32_t v0 = ring_offsets[r], v1 = ring_offsets[r + 1];
+                if ((uint64_t)O.nprims + add.size() + 2ull * (v1 - v0) + 1u > kOvMaxPrims) return fail(VF_ERR_INVALID, too_many);
+                std::vector<const float *> path;
+                for (uint32_t v = v0; v < v1; ++v) path.push_back(xyz + 3u * v);
+                path.push_back(xyz + 3u * v0);
+                ov_path(path, hw, ov_rgba(line_rgba), VF_CAP_ROUND, base, feature, add);
+                feature++;
+            }
+    }
+    if (!hdr.empty()) {                                       // (before ov_append: a failure here leaves the handle as it was)
+        VF_HIP_TRY(hipSetDevice(t->ctx->device));
+        VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+        if (int rc = pg_reserve(t, (uint32_t)hdr.size())) return rc;
+        VF_HIP_TRY(hipMemcpy(O.d_pg_hdr + O.nfill, hdr.data(), hdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    const uint32_t at = O.nprims;
+    const int rc = ov_append(t, add, layer_id);
+    if (rc != VF_OK) return rc;
+    O.features = feature;
+    if (!hdr.empty()) {
+        O.hdr.insert(O.hdr.end(), hdr.begin(), hdr.end());
+        if (!O.nfill) O.pg_lo = at;
+        O.pg_hi = at + nfillrec;
+        O.nfill += (uint32_t)hdr.size();
+    }
+    return VF_OK;
 }
 
 int vf_terrain_clear_overlays(vf_terrain *t)

@@ -12,8 +12,17 @@
 //                   them is walked in windows of kOvSortCap consecutive primitive indices, each sorted), so every pixel sees its
 //                   primitives in feature order whatever the scatter's order; coverage folded with max over a feature's primitives,
 //                   blended in linear light, encoded once.  Pixels no feature covers are never written.
+// Polygon fills add, for a handle that has them, between k_ov_setup and k_ov_scan:
+//   k_pg_setup      one thread per ring-edge slot: drape, transform, near-plane clip (the kept part, or for the closing slot of an exit
+//                   edge the segment along the plane to the ring's next entry point), exact screen edge, bin counts, feature box
+//   k_pg_header     one thread per fill feature: its box -> a header primitive counted in every bin of the box, and its mask storage
+// and after the pair count is read back, before k_ov_scatter:
+//   k_pg_backdrop   one thread per edge slot: one atomic XOR per crossed pixel row into the (feature, bin) mask of the bin left of x_c
+//   k_pg_prefix     one wave per fill feature: right-to-left prefix XOR along each bin row of its box
+// k_ov_composite walks a fill feature as its header (the mask bit of the pixel's row: crossings right of the bin) and its edges in
+// the bin (crossings between the pixel and the bin's right edge, and the nearest-edge distance).
 // All arithmetic is binary32 in the order DESIGN.md states (compiled with -ffp-contract=off); tests/overlay_model/overlay_model.c
-// is the same contract on the CPU and the GPU frames equal it bit for bit.
+// and tests/polygon_model/polygon_model.c are the same contract on the CPU and the GPU frames equal it bit for bit.
 #pragma once
 #include "vf_device.h"
 
@@ -24,6 +33,10 @@ constexpr uint32_t kOvSortCap = 4096;           // indices a bin sorts in LDS at
 constexpr uint32_t kOvMaxPrims = 1u << 24;      // primitive budget of a handle (all layers)
 constexpr uint32_t kOvCircle = 0u, kOvSquare = 1u, kOvSegment = 2u;
 constexpr uint32_t kOvKindMask = 3u, kOvDrape = 4u, kOvExt0 = 8u, kOvExt1 = 16u;
+// polygon fill records (OvIn kind kOvPoly): kPgHeader marks a feature's header, kPgClose an edge's closing-segment slot
+constexpr uint32_t kOvPoly = 3u, kPgHeader = kOvExt0, kPgClose = kOvExt1;
+constexpr uint32_t kOvFillHdr = 3u, kOvFillEdge = 4u, kOvNone = 7u;  // OvPrim kinds of fill records (kOvNone: nothing this frame)
+constexpr uint32_t kPgOff = 1u << 24;           // feature boxes are folded as kPgOff - lo (max) and hi + kPgOff (max): zero is empty
 
 // one primitive as added (host -> HBM once): world-space vertices, y an offset above the surface when kOvDrape is set
 struct OvIn {
@@ -33,8 +46,11 @@ struct OvIn {
     uint32_t flags;        // kind | kOvDrape | kOvExt0 / kOvExt1 (square cap: the segment reaches hw past its path's first / last vertex)
     uint32_t rgba;         // sRGB8 bytes, r | g << 8 | b << 16 | alpha << 24
     uint32_t feature;      // feature number (ascending with the primitive index; equal for the primitives of one polyline)
-    uint32_t pad[2];
+    uint32_t pad[2];       // polygon edge slot: the record index of its ring's first slot, the ring's vertex count
 };
+// A polygon fill feature is one header record (rgba = its fill colour) followed by two slots per ring edge (v_e -> v_e+1, ring order):
+// the kept part (flags without kPgClose) and the closing segment (kPgClose).  p0 / p1 = v_e / v_e+1; size holds the bits of the
+// feature's fill number (0, 1, ... over the handle's fill features), which indexes the per-feature arrays of the polygon pass.
 static_assert(sizeof(OvIn) == 48, "OvIn layout is shared with tests/overlay_model");
 
 // one primitive as a frame sees it (k_ov_setup)
@@ -42,6 +58,9 @@ struct OvPrim {
     float4 g;              // circle / square: (cx, cy, r, 0); segment: (ax, ay, ux, uy) -- start and unit direction
     float4 h;              // segment: (L, hw, e0, e1)
     uint32_t kind, rgba, feature, pad;
+    // fill edge (kOvFillEdge): g = (x0, y0, ex, ey), h = (1 / (ex ex + ey ey) or 0, ex / ey or 0, min x, max x), rgba / pad = bits of
+    // min y / max y.  fill header (kOvFillHdr): g = bits of (mask base, bin x0 | bin y0 << 16, bins across, the bin's mask word --
+    // filled in by the composite's staging), h = bits of the pixel box (x0, y0, x1, y1), rgba = the fill colour.
 };
 static_assert(sizeof(OvPrim) == 48, "OvPrim is staged in LDS");
 
@@ -95,6 +114,7 @@ __global__ __launch_bounds__(256) void k_ov_setup(FrameParams P, AxisTables A, u
     if (i >= nprims) return;
     const OvIn q = in[i];
     const uint32_t kind = q.flags & kOvKindMask;
+    if (kind == kOvPoly) return;                                        // (fill records: k_pg_setup / k_pg_header)
     const bool drape = (q.flags & kOvDrape) != 0u;
     OvPrim o;
     o.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f); o.h = o.g;
@@ -198,6 +218,195 @@ __global__ __launch_bounds__(256) void k_ov_scatter(uint32_t nprims, const uint2
         }
 }
 
+// ---- polygon fills ----------------------------------------------------------------
+
+// the near plane (z >= 0) crossing of clip-space segment in -> out, §4b's formula
+__device__ __forceinline__ void pg_cross(const float in[4], const float out[4], float r[4])
+{
+    const float di = in[2], dou = out[2];
+    const float t = di / (di - dou);
+    for (int k = 0; k < 4; ++k) r[k] = fmaf(t, out[k] - in[k], in[k]);
+}
+
+__device__ __forceinline__ bool pg_screen(const FrameParams &P, const float c[4], float &sx, float &sy)
+{
+    if (!(c[3] > 0.0f)) return false;
+    const float rw = 1.0f / c[3];
+    sx = fmaf(c[0] * rw, P.hw, P.hw);
+    sy = fmaf(-(c[1] * rw), P.hh, P.hh);
+    return isfinite(sx) && isfinite(sy);
+}
+
+// row crossing of a fill edge at pixel-centre row qy (the caller has checked min y <= qy < max y): x_c, clamped to the edge's x range
+__device__ __forceinline__ float pg_xc(const OvPrim &p, float qy)
+{
+    return fminf(fmaxf(fmaf(qy - p.g.y, p.h.y, p.g.x), p.h.z), p.h.w);
+}
+
+__global__ __launch_bounds__(256) void k_pg_setup(FrameParams P, AxisTables A, uint32_t lo, uint32_t hi, const OvIn *__restrict__ in,
+                                                  OvPrim *__restrict__ out, uint2 *__restrict__ box, uint32_t *__restrict__ cnt, uint32_t nbx,
+                                                  uint4 *__restrict__ fbox)
+{
+    // (no early return: the whole wave takes part in the feature-box fold below)
+    const uint32_t i = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    OvIn q{};
+    if (i < hi) q = in[i];
+    const bool slot = i < hi && (q.flags & kOvKindMask) == kOvPoly && (q.flags & kPgHeader) == 0u;
+    const bool drape = (q.flags & kOvDrape) != 0u;
+    float s0[4], s1[4];
+    bool have = false;
+    if (slot) {
+        float a[4], b[4];
+        ov_clip(P, A, q.p0, drape, a);
+        ov_clip(P, A, q.p1, drape, b);
+        const bool ain = a[2] >= 0.0f, bin = b[2] >= 0.0f;
+        if ((q.flags & kPgClose) == 0u) {                               // the kept part of v_e -> v_e+1
+            if (ain || bin) {
+                have = true;
+                for (int k = 0; k < 4; ++k) { s0[k] = a[k]; s1[k] = b[k]; }
+                if (!bin) pg_cross(a, b, s1);
+                else if (!ain) pg_cross(b, a, s0);
+            }
+        } else if (ain && !bin) {                                       // an exit: along the plane to the ring's next entry point
+            pg_cross(a, b, s0);
+            const uint32_t first = q.pad[0], nv = q.pad[1], e = (i - first) >> 1;
+            float prev[4] = { b[0], b[1], b[2], b[3] };
+            for (uint32_t k = 2; k <= nv; ++k) {                        // v_e+k; v_e+nv = v_e is inside, so this ends
+                const uint32_t j = (e + k) % nv;
+                float c[4];
+                ov_clip(P, A, in[first + 2u * j].p0, drape, c);
+                if (c[2] >= 0.0f) { pg_cross(c, prev, s1); have = true; break; }
+                for (int m = 0; m < 4; ++m) prev[m] = c[m];
+            }
+        }
+    }
+    OvPrim o;
+    o.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f); o.h = o.g;
+    o.kind = kOvNone; o.rgba = 0u; o.feature = q.feature; o.pad = 0u;
+    float ax, ay, bx, by;
+    uint4 f = make_uint4(0u, 0u, 0u, 0u);                               // this edge's share of the feature box (folded with max)
+    if (have && pg_screen(P, s0, ax, ay) && pg_screen(P, s1, bx, by)) {
+        const float ex = bx - ax, ey = by - ay;
+        const float l2 = ex * ex + ey * ey;
+        const float xmin = fminf(ax, bx), xmax = fmaxf(ax, bx), ymin = fminf(ay, by), ymax = fmaxf(ay, by);
+        o.g = make_float4(ax, ay, ex, ey);
+        o.h = make_float4(l2 > 0.0f ? 1.0f / l2 : 0.0f, ey != 0.0f ? ex / ey : 0.0f, xmin, xmax);
+        o.kind = kOvFillEdge; o.rgba = __float_as_uint(ymin); o.pad = __float_as_uint(ymax);
+        // the feature box folds every kept edge's extent +-1 px (each axis floored in [-2, n + 2]), clipped to the frame later
+        const float lim_x = (float)P.W + 2.0f, lim_y = (float)P.H + 2.0f;
+        const int fx0 = (int)floorf(fminf(fmaxf(xmin - 1.0f, -2.0f), lim_x)), fx1 = (int)floorf(fminf(fmaxf(xmax + 1.0f, -2.0f), lim_x));
+        const int fy0 = (int)floorf(fminf(fmaxf(ymin - 1.0f, -2.0f), lim_y)), fy1 = (int)floorf(fminf(fmaxf(ymax + 1.0f, -2.0f), lim_y));
+        f = make_uint4(kPgOff - (uint32_t)(fx0 + 2) + 2u, kPgOff - (uint32_t)(fy0 + 2) + 2u,   // (kPgOff - fx0, unsigned)
+                       (uint32_t)(fx1 + 2) + kPgOff - 2u, (uint32_t)(fy1 + 2) + kPgOff - 2u);
+    }
+    // fold into fbox[feature]: one set of atomics per wave when its edges all belong to one feature (a long ring's edges otherwise
+    // queue on the same four words), else one per edge
+    const bool edge = o.kind == kOvFillEdge;
+    const uint32_t kf = __float_as_uint(q.size);
+    const unsigned long long voters = __ballot(edge);
+    if (voters) {
+        const int leader = __ffsll((long long)voters) - 1;
+        const uint32_t k0 = __shfl(kf, leader);
+        if (__all(!edge || kf == k0)) {
+            for (int d = 1; d < 64; d <<= 1) {
+                f.x = max(f.x, __shfl_xor(f.x, d)); f.y = max(f.y, __shfl_xor(f.y, d));
+                f.z = max(f.z, __shfl_xor(f.z, d)); f.w = max(f.w, __shfl_xor(f.w, d));
+            }
+            if ((int)(threadIdx.x & 63u) == leader) {
+                uint4 *F = fbox + k0;
+                atomicMax(&F->x, f.x); atomicMax(&F->y, f.y); atomicMax(&F->z, f.z); atomicMax(&F->w, f.w);
+            }
+        } else if (edge) {
+            uint4 *F = fbox + kf;
+            atomicMax(&F->x, f.x); atomicMax(&F->y, f.y); atomicMax(&F->z, f.z); atomicMax(&F->w, f.w);
+        }
+    }
+    if (!slot) return;
+    out[i] = o;
+    int px0 = 1, px1 = 0, py0 = 1, py1 = 0;
+    if (edge) { ov_span(o.h.z - 1.0f, o.h.w + 1.0f, P.W, px0, px1); ov_span(__uint_as_float(o.rgba) - 1.0f, __uint_as_float(o.pad) + 1.0f, P.H, py0, py1); }
+    if (px0 > px1 || py0 > py1) { box[i] = make_uint2(1u, 0u); return; }
+    const uint32_t bx0 = (uint32_t)px0 / kOvBin, bx1 = (uint32_t)px1 / kOvBin, by0 = (uint32_t)py0 / kOvBin, by1 = (uint32_t)py1 / kOvBin;
+    box[i] = make_uint2(bx0 | (by0 << 16), bx1 | (by1 << 16));
+    for (uint32_t y = by0; y <= by1; ++y)
+        for (uint32_t x = bx0; x <= bx1; ++x) atomicAdd(&cnt[y * nbx + x], 1u);
+}
+
+// one thread per fill feature: the folded box (reset for the next frame) -> the header primitive, counted in every bin of the box,
+// and the feature's share of the mask storage: fbin = (mask base, bin x0 | bin y0 << 16, bins across, bins down)
+__global__ __launch_bounds__(256) void k_pg_header(FrameParams P, uint32_t nfill, const uint32_t *__restrict__ hdr, const OvIn *__restrict__ in,
+                                                   uint4 *__restrict__ fbox, uint4 *__restrict__ fbin, OvPrim *__restrict__ out,
+                                                   uint2 *__restrict__ box, uint32_t *__restrict__ cnt, uint32_t nbx,
+                                                   unsigned long long *__restrict__ mask_total)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nfill) return;
+    const uint32_t i = hdr[k];
+    const uint4 f = fbox[k];
+    fbox[k] = make_uint4(0u, 0u, 0u, 0u);
+    OvPrim o;
+    o.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f); o.h = o.g;
+    o.kind = kOvFillHdr; o.rgba = in[i].rgba; o.feature = in[i].feature; o.pad = 0u;
+    int px0 = 1, px1 = 0, py0 = 1, py1 = 0;
+    if (f.x != 0u) {
+        px0 = max((int)(kPgOff - f.x), 0); py0 = max((int)(kPgOff - f.y), 0);
+        px1 = min((int)(f.z - kPgOff), (int)P.W - 1); py1 = min((int)(f.w - kPgOff), (int)P.H - 1);
+    }
+    if (px0 > px1 || py0 > py1) {
+        o.kind = kOvNone; out[i] = o; box[i] = make_uint2(1u, 0u); fbin[k] = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint32_t bx0 = (uint32_t)px0 / kOvBin, bx1 = (uint32_t)px1 / kOvBin, by0 = (uint32_t)py0 / kOvBin, by1 = (uint32_t)py1 / kOvBin;
+    const uint32_t fw = bx1 - bx0 + 1u, fh = by1 - by0 + 1u;
+    const uint32_t base = (uint32_t)atomicAdd(mask_total, (unsigned long long)fw * fh);   // (the host refuses a total beyond 2^32 - 1)
+    o.g = make_float4(__uint_as_float(base), __uint_as_float(bx0 | (by0 << 16)), __uint_as_float(fw), 0.0f);
+    o.h = make_float4(__uint_as_float((uint32_t)px0), __uint_as_float((uint32_t)py0), __uint_as_float((uint32_t)px1), __uint_as_float((uint32_t)py1));
+    out[i] = o;
+    fbin[k] = make_uint4(base, bx0 | (by0 << 16), fw, fh);
+    box[i] = make_uint2(bx0 | (by0 << 16), bx1 | (by1 << 16));
+    for (uint32_t y = by0; y <= by1; ++y)
+        for (uint32_t x = bx0; x <= bx1; ++x) atomicAdd(&cnt[y * nbx + x], 1u);
+}
+
+// one thread per edge slot: for every pixel row the edge crosses (min y <= qy < max y), flip bit (row & 15) of the mask word of the
+// rightmost bin of the feature's box whose right edge is <= x_c (none left of the box: no flip)
+__global__ __launch_bounds__(256) void k_pg_backdrop(uint32_t H, uint32_t lo, uint32_t hi, const OvIn *__restrict__ in,
+                                                     const OvPrim *__restrict__ prims, const uint4 *__restrict__ fbin, uint32_t *__restrict__ mask)
+{
+    const uint32_t i = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hi) return;
+    const OvPrim p = prims[i];
+    if ((in[i].flags & kOvKindMask) != kOvPoly || p.kind != kOvFillEdge) return;
+    const uint4 f = fbin[__float_as_uint(in[i].size)];
+    if (f.z == 0u) return;
+    const int bx0 = (int)(f.y & 0xFFFFu), by0 = (int)(f.y >> 16), bx1 = bx0 + (int)f.z - 1;
+    const float ymin = __uint_as_float(p.rgba), ymax = __uint_as_float(p.pad);
+    int r0, r1;
+    ov_span(ymin - 1.0f, ymax + 1.0f, H, r0, r1);
+    for (int r = r0; r <= r1; ++r) {
+        const float qy = (float)r + 0.5f;
+        if (!(ymin <= qy && qy < ymax)) continue;
+        const float xc = pg_xc(p, qy);
+        int j = (int)floorf(fminf(fmaxf(xc * 0.0625f, -1.0f), 65536.0f)) - 1;       // (j + 1) * 16 <= x_c
+        if (j < bx0) continue;
+        j = min(j, bx1);
+        atomicXor(&mask[f.x + (uint32_t)(r / (int)kOvBin - by0) * f.z + (uint32_t)(j - bx0)], 1u << (r & 15));
+    }
+}
+
+// one wave per fill feature, a lane per bin row of its box: mask[b] ^= mask[b + 1] ^ ... (right to left)
+__global__ __launch_bounds__(256) void k_pg_prefix(uint32_t nfill, const uint4 *__restrict__ fbin, uint32_t *__restrict__ mask)
+{
+    const uint32_t k = (blockIdx.x * blockDim.x + threadIdx.x) / 64u, lane = threadIdx.x & 63u;
+    if (k >= nfill) return;
+    const uint4 f = fbin[k];
+    for (uint32_t row = lane; row < f.w; row += 64u) {
+        uint32_t *m = mask + f.x + row * f.z;
+        uint32_t acc = 0u;
+        for (uint32_t c = f.z; c-- > 0u;) { acc ^= m[c]; m[c] = acc; }
+    }
+}
+
 // coverage of pixel centre (qx, qy) by one primitive
 __device__ __forceinline__ float ov_cover(const OvPrim &p, float qx, float qy)
 {
@@ -219,7 +428,19 @@ struct OvPixel {
     bool touched;
     uint32_t feature, rgba;
     float cov;
+    bool fill;             // the feature in hand is a fill and the pixel is in its box: par / d2 give its coverage
+    uint32_t par;          // even-odd parity of the crossings right of the pixel so far
+    float d2;              // squared distance to the nearest edge so far
 };
+
+// a fill feature's coverage, once its header and every edge of the bin are folded in
+__device__ __forceinline__ void pg_fill_cover(OvPixel &S)
+{
+    if (!S.fill) return;
+    const float d = sqrtf(S.d2);
+    const float sd = S.par ? -d : d;
+    S.cov = fminf(fmaxf(0.5f - sd, 0.0f), 1.0f);
+}
 
 // the feature in hand is done at this pixel: blend it (if it covers the pixel at all)
 __device__ __forceinline__ void ov_flush(OvPixel &S, const float *dec, const uint32_t *rgba, size_t o)
@@ -263,7 +484,8 @@ __device__ __forceinline__ uint32_t ov_pow2(uint32_t n)
 __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
                                                       uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
                                                       const uint32_t *__restrict__ list, const float *__restrict__ decode,
-                                                      const float *__restrict__ thresh, uint32_t *__restrict__ rgba)
+                                                      const float *__restrict__ thresh, const uint32_t *__restrict__ mask,
+                                                      uint32_t *__restrict__ rgba)
 {
     __shared__ uint32_t keys[kOvSortCap];
     __shared__ OvPrim recs[256];
@@ -280,21 +502,50 @@ __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, ui
     const bool on = px < W && py < H;
     const size_t o = (size_t)py * W + px;
     const float qx = (float)px + 0.5f, qy = (float)py + 0.5f;
+    const float rb = (float)((bin % nbx + 1u) * kOvBin);                // the bin's right edge (fill crossings beyond it: the mask)
     OvPixel S;
     S.c[0] = S.c[1] = S.c[2] = 0.0f; S.touched = false; S.feature = 0xFFFFFFFFu; S.rgba = 0u; S.cov = 0.0f;
+    S.fill = false; S.par = 0u; S.d2 = 0.0f;
     const uint32_t *L = list + start[bin];
     // composite keys[0..m) (sorted): records staged 256 at a time, every pixel walks them in order
     auto run = [&](uint32_t m) {
         for (uint32_t k0 = 0; k0 < m; k0 += 256u) {
             __syncthreads();
-            if (k0 + tid < m) recs[tid] = prims[keys[k0 + tid]];
+            if (k0 + tid < m) {
+                recs[tid] = prims[keys[k0 + tid]];
+                OvPrim &r = recs[tid];
+                if (r.kind == kOvFillHdr) {                             // this bin's word of the feature's backdrop mask
+                    const uint32_t b0 = __float_as_uint(r.g.y), fw = __float_as_uint(r.g.z);
+                    const uint32_t w = __float_as_uint(r.g.x) + (bin / nbx - (b0 >> 16)) * fw + (bin % nbx - (b0 & 0xFFFFu));
+                    r.g.w = __uint_as_float(mask[w]);
+                }
+            }
             __syncthreads();
             const uint32_t kn = min(256u, m - k0);
             if (on)
                 for (uint32_t k = 0; k < kn; ++k) {
                     const OvPrim &p = recs[k];
-                    if (p.feature != S.feature) { ov_flush(S, sdec, rgba, o); S.feature = p.feature; S.rgba = p.rgba; S.cov = 0.0f; }
-                    S.cov = fmaxf(S.cov, ov_cover(p, qx, qy));
+                    if (p.feature != S.feature) {
+                        pg_fill_cover(S);
+                        ov_flush(S, sdec, rgba, o);
+                        S.feature = p.feature; S.rgba = p.rgba; S.cov = 0.0f; S.fill = false;
+                    }
+                    if (p.kind <= kOvSegment) S.cov = fmaxf(S.cov, ov_cover(p, qx, qy));
+                    else if (p.kind == kOvFillEdge) {
+                        const float ymin = __uint_as_float(p.rgba), ymax = __uint_as_float(p.pad);
+                        if (ymin <= qy && qy < ymax) {
+                            const float xc = pg_xc(p, qy);
+                            S.par ^= (qx < xc && xc < rb) ? 1u : 0u;
+                        }
+                        const float dx = qx - p.g.x, dy = qy - p.g.y;
+                        const float t = fminf(fmaxf((dx * p.g.z + dy * p.g.w) * p.h.x, 0.0f), 1.0f);
+                        const float rx = dx - t * p.g.z, ry = dy - t * p.g.w;
+                        S.d2 = fminf(S.d2, rx * rx + ry * ry);
+                    } else {                                            // fill header: the pixel's row of the mask, nothing near yet
+                        S.par = (__float_as_uint(p.g.w) >> (tid / kOvBin)) & 1u;
+                        S.d2 = INFINITY;
+                        S.fill = px >= __float_as_uint(p.h.x) && py >= __float_as_uint(p.h.y) && px <= __float_as_uint(p.h.z) && py <= __float_as_uint(p.h.w);
+                    }
                 }
         }
     };
@@ -330,6 +581,7 @@ __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, ui
         }
     }
     if (on) {
+        pg_fill_cover(S);
         ov_flush(S, sdec, rgba, o);
         if (S.touched)
             rgba[o] = srgb_encode(S.c[0], sthr) | (srgb_encode(S.c[1], sthr) << 8) | (srgb_encode(S.c[2], sthr) << 16) | 0xFF000000u;

@@ -457,6 +457,20 @@ public:
                                    (uint32_t)(offsets.shape(0) - 1), width, static_cast<const uint8_t *>(col.data()), cp, drape ? 1 : 0, &id));
         return id;
     }
+    uint32_t add_polygons(py::object polygons, py::object fill_rgba, py::object line_rgba, py::object line_width_px, bool drape)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("polygon_args")(polygons, fill_rgba, line_rgba, line_width_px);
+        py::array coords = a[0].cast<py::array>(), rings = a[1].cast<py::array>(), feats = a[2].cast<py::array>();
+        py::object dfill = a[3], fills = a[4], line = a[5];
+        const float width = a[6].cast<float>();
+        auto bytes = [](py::object o) { return o.is_none() ? nullptr : static_cast<const uint8_t *>(o.cast<py::array>().data()); };
+        Borrow b(busy);
+        uint32_t id = 0;
+        check(vf_terrain_add_polygons(t, static_cast<const float *>(coords.data()), static_cast<const uint32_t *>(rings.data()),
+                                      (uint32_t)(rings.shape(0) - 1), static_cast<const uint32_t *>(feats.data()), (uint32_t)(feats.shape(0) - 1),
+                                      bytes(fills), bytes(dfill), bytes(line), width, drape ? 1 : 0, &id));
+        return id;
+    }
     void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
 
     // src/terrain/mod.rs:537-546
@@ -756,6 +770,8 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("shape") = "circle", py::arg("drape") = false)
         .def("add_lines", &T::add_lines, py::arg("paths"), py::kw_only(), py::arg("width_px") = 2.0f,
              py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("cap") = "round", py::arg("drape") = false)
+        .def("add_polygons", &T::add_polygons, py::arg("polygons"), py::kw_only(), py::arg("fill_rgba") = py::make_tuple(255, 255, 255, 255),
+             py::arg("line_rgba") = py::none(), py::arg("line_width_px") = 1.0f, py::arg("drape") = false)
         .def("clear_overlays", &T::clear_overlays);
 }
 
