@@ -254,6 +254,15 @@ int vf_terrain_clear_overlays(vf_terrain *t);
 int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *ring_offsets, uint32_t nrings, const uint32_t *feature_offsets,
                             uint32_t nfeatures, const uint8_t *fill_rgba, const uint8_t default_fill[4], const uint8_t line_rgba[4],
                             float line_width_px, int drape, uint32_t *layer_id);
+/* Occlusion of a point or line layer by the terrain (new; opt-in, per layer; DESIGN.md 4d has the conventions bit for bit).  With
+ * occlude != 0 the layer's points and segments are not drawn at pixels where the rendered terrain is in front of them: hidden where
+ * the terrain's interpolated 1/w exceeds the primitive's 1/w times kb = 1 + depth_bias (depth_bias >= 0, finite; the library's
+ * default is VF_OCCLUSION_DEPTH_BIAS).  occlude == 0 restores the layer's plain compositing.  Updates the layer's records in place
+ * (no upload).  A handle with an occluding layer draws its frames with the visibility store on and holds one W x H id buffer.
+ * VF_ERR_INVALID for an unknown layer, a polygon layer (polygon fills have no depth), a negative or non-finite depth_bias, and a
+ * sharded handle. */
+#define VF_OCCLUSION_DEPTH_BIAS 1e-2f
+int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude, float depth_bias);
 
 /* copy_texture_to_buffer + map + un-pad (src/terrain/mod.rs:439-485): local rows [y0, y0+rows)
  * into dst (rows*W*4 bytes).  Waits for the last render and for the copy (work the library queues behind the copy for the

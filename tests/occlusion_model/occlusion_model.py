@@ -1,0 +1,137 @@
+"""ctypes loader of the occlusion CPU model (occlusion_model.c): the polygon model's layers, with point and line layers that can be
+hidden behind the terrain.
+
+    import occlusion_model as ocm
+    layers = ocm.Layers(); layers.points(xyz, size_px=4, drape=True, occlude=True); layers.lines(paths, occlude=True, depth_bias=0.01)
+    out = ocm.composite(frame_rgba, vis, uniforms, height, grid, layers)
+
+`vis` is the frame's visibility (H, W) uint32, primitive id + 1, 0 = background (oracle.render_terrain(..., want_vis=True)).  An
+occluding layer's records carry flag 32 and pad[0] = the bits of kb = float32(1) + float32(depth_bias), as
+vf_terrain_set_layer_occlusion writes them.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "polygon_model"))
+import polygon_model as pm  # noqa: E402
+om = pm.om
+
+OCCLUDE = 32
+DEPTH_BIAS = 1e-2                                             # the library's default (include/vf_hip.h VF_OCCLUSION_DEPTH_BIAS)
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        src = os.path.join(HERE, "occlusion_model.c")
+        deps = [src, os.path.join(os.path.dirname(HERE), "polygon_model", "polygon_model.c"),
+                os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")]
+        out = os.path.join(ROOT, "build", "libocmodel.so")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+            tmp = out + f".{os.getpid()}.tmp"
+            subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
+            os.replace(tmp, out)
+        L = C.CDLL(out)
+        vp, u32, i = C.c_void_p, C.c_uint32, C.c_int
+        L.ocm_composite.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
+        L.ocm_composite.restype = i
+        L.ocm_terrain_q.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32]
+        L.ocm_terrain_q.restype = i
+        _lib = L
+    return _lib
+
+
+def kb_bits(depth_bias):
+    return int((np.float32(1.0) + np.float32(depth_bias)).view(np.uint32))
+
+
+class Layers(pm.Layers):
+    """Records of point, line and polygon layers in feature order; points and lines may occlude."""
+
+    def __init__(self):
+        super().__init__()
+        self.ranges = []                                       # per point / line layer: (first, last + 1) into self.recs
+
+    def _occlude(self, first, occlude, depth_bias):
+        self.ranges.append((first, len(self.recs)))
+        if occlude:
+            self.set_occlusion(len(self.ranges) - 1, True, depth_bias)
+        return self
+
+    def set_occlusion(self, layer, occlude, depth_bias=DEPTH_BIAS):
+        """layer: the index of a point / line layer among those added here (polygon layers are not counted)"""
+        a, b = self.ranges[layer]
+        for r in self.recs[a:b]:
+            if occlude:
+                r["flags"] |= OCCLUDE
+                r["pad"][:, 0] = kb_bits(depth_bias)
+            else:
+                r["flags"] &= ~np.uint32(OCCLUDE)
+                r["pad"][:, 0] = 0
+        return self
+
+    def points(self, xyz, size_px=5.0, rgba=(255, 255, 255, 255), shape="circle", drape=False, occlude=False, depth_bias=DEPTH_BIAS):
+        first = len(self.recs)
+        super().points(xyz, size_px=size_px, rgba=rgba, shape=shape, drape=drape)
+        return self._occlude(first, occlude, depth_bias)
+
+    def lines(self, paths, width_px=2.0, rgba=(255, 255, 255, 255), cap="round", drape=False, occlude=False, depth_bias=DEPTH_BIAS):
+        first = len(self.recs)
+        super().lines(paths, width_px=width_px, rgba=rgba, cap=cap, drape=drape)
+        return self._occlude(first, occlude, depth_bias)
+
+    def polygons(self, polygons, fill_rgba=(255, 255, 255, 255), line_rgba=None, line_width_px=1.0, drape=False):
+        n = len(self.ranges)
+        super().polygons(polygons, fill_rgba=fill_rgba, line_rgba=line_rgba, line_width_px=line_width_px, drape=drape)
+        del self.ranges[n:]                                    # (its outlines went through lines(): not a point / line layer)
+        return self
+
+
+def composite(frame, vis, uniforms, height, grid, layers):
+    """frame (H, W, 4) uint8, vis (H, W) uint32 -> a new frame with the layers composited over it (the contract, on the CPU)."""
+    out = np.array(frame, np.uint8, copy=True, order="C")
+    H, W = out.shape[:2]
+    vis = np.ascontiguousarray(vis, np.uint32)
+    assert vis.shape == (H, W)
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    recs = np.ascontiguousarray(layers.array())
+    fills = getattr(layers, "fills", [])
+    feat = np.array([f[0] for f in fills], np.uint32)
+    cols = np.array([f[1] for f in fills], np.uint32)
+    drape = np.array([f[2] for f in fills], np.uint8)
+    rings = [r for f in fills for r in f[3]]
+    fr = np.zeros(len(fills) + 1, np.uint32)
+    fr[1:] = np.cumsum([len(f[3]) for f in fills])
+    offs, xyz = pm._pack(rings)
+    rc = lib().ocm_composite(out.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
+                             recs.ctypes.data, len(recs), len(fills), feat.ctypes.data, cols.ctypes.data, drape.ctypes.data,
+                             fr.ctypes.data, offs.ctypes.data, xyz.ctypes.data)
+    assert rc == 0
+    return out
+
+
+def terrain_q(vis, uniforms, height, grid):
+    """-> (Q (H, W) float32: the terrain's interpolated 1/w at each pixel centre, 0 on background; clipped (H, W) bool: the pixel's
+    primitive has a vertex outside 0 <= z <= w, so it took the generic path)"""
+    vis = np.ascontiguousarray(vis, np.uint32)
+    H, W = vis.shape
+    Q = np.zeros((H, W), np.float32)
+    clipped = np.zeros((H, W), np.uint8)
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    rc = lib().ocm_terrain_q(Q.ctypes.data, clipped.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1],
+                             tex.shape[0], grid)
+    assert rc == 0
+    return Q, clipped.astype(bool)

@@ -1,4 +1,5 @@
-"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines / .add_polygons), pack_lines and pack_polygons.
+"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines / .add_polygons / .set_layer_occlusion), pack_lines
+and pack_polygons.
 
 The extension calls these before it hands the arrays to the C-ABI (include/vf_hip.h, overlays); they need numpy only, no device.
 """
@@ -74,6 +75,18 @@ def point_args(xyz, size_px, rgba, shape):
     dsize, sizes = _size(size_px, n, "size_px")
     dcol, cols = _colour(rgba, n, True)
     return pts, dsize, sizes, dcol, cols, SHAPES[shape]
+
+
+def occlusion_args(occlude, depth_bias):
+    """-> (occlude, depth_bias as a float) for add_points / add_lines / set_layer_occlusion"""
+    if not isinstance(occlude, (bool, np.bool_)):
+        raise TypeError(f"occlude must be a bool, got {type(occlude).__name__}")
+    if isinstance(depth_bias, bool) or not isinstance(depth_bias, numbers.Real):
+        raise TypeError(f"depth_bias must be a number, got {type(depth_bias).__name__}")
+    b = float(depth_bias)
+    if not np.isfinite(b) or b < 0.0 or b > float(np.finfo(np.float32).max):
+        raise ValueError(f"depth_bias must be a finite number >= 0, got {b}")
+    return bool(occlude), b
 
 
 def pack_lines(paths):

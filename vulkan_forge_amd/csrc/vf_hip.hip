@@ -313,7 +313,7 @@ struct vf_terrain {
     uint32_t precision = VF_PRECISION_FAST, precision_frame = VF_PRECISION_FAST;   // fragment arithmetic (of the frame vf_terrain_render drew last)
     uint32_t local_tiles = 0;            // tiles this handle renders (= ntx * local tile rows unless tile-sharded)
     uint32_t *d_rgba = nullptr;
-    uint32_t *d_vis = nullptr;           // only allocated for vf_terrain_read_visibility
+    uint32_t *d_vis = nullptr;           // only allocated for vf_terrain_read_visibility and for occluding overlay layers
     uint32_t *d_stats = nullptr;         // [0] (tile, block) pairs rasterised
     // timing: a ring of (start, after block boxes, after plan, after tile) events, one set per rendered frame
     static constexpr int kTimingRing = 64;
@@ -368,6 +368,11 @@ struct vf_terrain {
         unsigned long long *d_pg_total = nullptr;   // the frame's mask words (zero between frames)
         uint32_t *d_mask = nullptr;          // (feature, bin) backdrop masks, bit r: parity of row r's crossings right of the bin
         size_t mask_cap = 0;
+        // occlusion (vf_terrain_set_layer_occlusion)
+        struct Layer { uint32_t lo, hi; bool polygon, occlude; };
+        std::vector<Layer> layer;            // [layers] each layer's record range
+        uint32_t occluding = 0;              // layers with occlusion on: the frame stores its visibility and composites with depth
+        float4 *d_dep = nullptr;             // [cap] per primitive (rw_a, rw_b - rw_a, kb, 0) of occluding primitives (k_ov_setup)
     } ov;
 };
 
@@ -580,7 +585,7 @@ static int refresh_tables(vf_terrain *t, hipStream_t s)
 static void ov_release(vf_terrain *t)
 {
     vf_terrain::Overlays &O = t->ov;
-    void *ptrs[] = { O.d_in, O.d_prim, O.d_box, O.d_cnt, O.d_start, O.d_decode, O.d_list, O.d_pg_hdr, O.d_pg_fbox, O.d_pg_fbin, O.d_pg_total, O.d_mask };
+    void *ptrs[] = { O.d_in, O.d_prim, O.d_box, O.d_cnt, O.d_start, O.d_decode, O.d_list, O.d_pg_hdr, O.d_pg_fbox, O.d_pg_fbin, O.d_pg_total, O.d_mask, O.d_dep };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (O.h_total) (void)hipHostFree(O.h_total);
     if (O.counted) (void)hipEventDestroy(O.counted);
@@ -1240,12 +1245,15 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
 
 // The overlay pass of a frame (vf_overlay.h), on the draw stream behind the tile kernels.  The pair list is sized by the frame's pair
 // count, which the host reads back between the scan and the scatter: a handle with overlays waits once per frame for that word.
-static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P)
+// With an occluding layer the tile kernels have stored the frame's visibility in d_vis (draw_frame), and the composite reads it.
+static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V)
 {
     vf_terrain::Overlays &O = t->ov;
     const uint32_t nbx = (t->W + kOvBin - 1u) / kOvBin, nby = (t->H + kOvBin - 1u) / kOvBin, nbins = nbx * nby;
     const dim3 per_prim((O.nprims + 255u) / 256u), threads(256);
-    hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx);
+    const bool occlude = O.occluding != 0u;
+    hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx,
+                       occlude ? O.d_dep : nullptr);
     const dim3 per_slot((O.pg_hi - O.pg_lo + 255u) / 256u);
     if (O.nfill) {                                          // fill edges and headers: binned with the rest
         hipLaunchKernelGGL(k_pg_setup, per_slot, threads, 0, s, P, axis(t), O.pg_lo, O.pg_hi, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx, O.d_pg_fbox);
@@ -1296,15 +1304,22 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P)
         O.list_cap = want;
     }
     hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.d_box, nbx, O.d_start, O.d_cnt, O.d_list);
-    hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
-                       t->ctx->d_thresh, O.d_mask, t->d_rgba);
+    if (occlude)
+        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
+                           t->ctx->d_thresh, O.d_mask, t->d_rgba, P, V, t->d_vis, O.d_dep);
+    else
+        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
+                           t->ctx->d_thresh, O.d_mask, t->d_rgba);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
 }
 
-static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool write_vis)
+// diag: a visibility / diagnostics frame (render_visibility): stores its visibility, composites no overlays.  A frame of a handle with an
+// occluding overlay layer stores its visibility too, for the overlay pass.
+static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
     const FrameParams &P = K.P;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims);
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     const bool motion_starts = K.motion_starts, solo = K.solo;
@@ -1322,7 +1337,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool wri
     VF_HIP_TRY(hipStreamWaitEvent(s, S.set_up, 0));
     // The previous frame may have been drawn on another stream of the caller's: this frame waits for it (same output / statistics
     // buffers; and when it went to another output buffer, letting the two tile kernels overlap costs more than it gains -- the
-    // experiment behind VF_OVERLAP_FRAMES, tools/exp_overlap.py).
+    // experiment behind VF_OVERLAP_FRAMES, tools/exp_overlap.py).  Frames that store their visibility -- diagnostics, and every frame of
+    // a handle with an occluding layer -- always wait: d_vis is one buffer per handle.
 #ifdef VF_EXPERIMENTS
     static const bool overlap_frames = std::getenv("VF_OVERLAP_FRAMES") != nullptr;
 #else
@@ -1418,7 +1434,11 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool wri
     }
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev[3], s)); t->timed_frames++; }
-    if (t->ov.nprims && !write_vis) { const int orc = overlay_pass(t, s, P); if (orc != VF_OK) return orc; }   // (visibility / diagnostics frames: none)
+    if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
+        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
+        const int orc = overlay_pass(t, s, P, V);
+        if (orc != VF_OK) return orc;
+    }
     VF_HIP_TRY(hipEventRecord(S.drawn, s));
     VF_HIP_TRY(hipGetLastError());
     std::memcpy(S.u_used, t->u, sizeof S.u_used);           // the camera this set's tile times (being measured now) belong to
@@ -1624,7 +1644,7 @@ int vf_terrain_sync(vf_terrain *t)
 static float ov_clamp_px(float v) { return std::fmin(std::fmax(v, 1.0f), 64.0f); }
 
 // append primitives (feature order) to the handle's overlay array; the first call makes the overlay state
-static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *layer_id)
+static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *layer_id, bool polygon = false)
 {
     vf_terrain::Overlays &O = t->ov;
     if ((uint64_t)O.nprims + add.size() > kOvMaxPrims)
@@ -1654,10 +1674,22 @@ static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *laye
             for (void *p : { (void *)in, (void *)pr, (void *)bx }) if (p) (void)hipFree(p);
             return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
         }
+        if (O.d_dep) {                                        // (per-frame values: made again by the next k_ov_setup)
+            float4 *dp = nullptr;
+            e = hipMalloc(&dp, (size_t)cap * sizeof(float4));
+            if (e == hipSuccess) e = hipMemset(dp, 0, (size_t)cap * sizeof(float4));
+            if (e != hipSuccess) {
+                for (void *p : { (void *)in, (void *)pr, (void *)bx, (void *)dp }) if (p) (void)hipFree(p);
+                return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
+            }
+            (void)hipFree(O.d_dep);
+            O.d_dep = dp;
+        }
         for (void *p : { (void *)O.d_in, (void *)O.d_prim, (void *)O.d_box }) if (p) (void)hipFree(p);
         O.d_in = in; O.d_prim = pr; O.d_box = bx; O.cap = cap;
     }
     if (!add.empty()) VF_HIP_TRY(hipMemcpy(O.d_in + O.nprims, add.data(), add.size() * sizeof(OvIn), hipMemcpyHostToDevice));
+    O.layer.push_back({ O.nprims, need, polygon, false });
     O.nprims = need;
     if (layer_id) *layer_id = O.layers;
     O.layers++;
@@ -1855,7 +1887,7 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
         VF_HIP_TRY(hipMemcpy(O.d_pg_hdr + O.nfill, hdr.data(), hdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     const uint32_t at = O.nprims;
-    const int rc = ov_append(t, add, layer_id);
+    const int rc = ov_append(t, add, layer_id, true);
     if (rc != VF_OK) return rc;
     O.features = feature;
     if (!hdr.empty()) {
@@ -1864,6 +1896,38 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
         O.pg_hi = at + nfillrec;
         O.nfill += (uint32_t)hdr.size();
     }
+    return VF_OK;
+}
+
+int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude, float depth_bias)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "occlusion needs a whole-frame handle: sharded handles have no overlays");
+    if (!std::isfinite(depth_bias) || depth_bias < 0.0f) return fail(VF_ERR_INVALID, "depth_bias must be a finite number >= 0");
+    vf_terrain::Overlays &O = t->ov;
+    if (layer_id >= O.layer.size()) return fail(VF_ERR_INVALID, "no overlay layer with that id");
+    vf_terrain::Overlays::Layer &L = O.layer[layer_id];
+    if (L.polygon) return fail(VF_ERR_INVALID, "a polygon layer cannot occlude: polygon fills have no depth");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));   // (a frame in flight reads the records)
+    if (occlude) {
+        if (!t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
+        if (!O.d_dep) {
+            VF_HIP_TRY(hipMalloc(&O.d_dep, (size_t)O.cap * sizeof(float4)));
+            VF_HIP_TRY(hipMemset(O.d_dep, 0, (size_t)O.cap * sizeof(float4)));
+        }
+    }
+    const float kb = 1.0f + depth_bias;                       // the layer's depth factor, rounded once (binary32)
+    uint32_t kb_bits;
+    std::memcpy(&kb_bits, &kb, sizeof kb_bits);
+    if (L.hi > L.lo) {
+        hipLaunchKernelGGL(k_ov_occlude, dim3((L.hi - L.lo + 255u) / 256u), dim3(256), 0, t->ctx->stream, L.lo, L.hi, O.d_in,
+                           occlude ? 1u : 0u, kb_bits);
+        VF_HIP_TRY(hipGetLastError());
+        VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    }
+    if (L.occlude != (occlude != 0)) O.occluding += occlude ? 1u : (uint32_t)-1;
+    L.occlude = occlude != 0;
     return VF_OK;
 }
 

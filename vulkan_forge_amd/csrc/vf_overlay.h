@@ -21,10 +21,14 @@
 //   k_pg_prefix     one wave per fill feature: right-to-left prefix XOR along each bin row of its box
 // k_ov_composite walks a fill feature as its header (the mask bit of the pixel's row: crossings right of the bin) and its edges in
 // the bin (crossings between the pixel and the bin's right edge, and the nearest-edge distance).
+// Occlusion: a handle with an occluding point or line layer draws its terrain with the visibility store on, k_ov_setup
+// keeps the 1/w of those layers' primitives in a side array, and k_ov_composite_occlude forms the terrain's 1/w of each pixel of a bin
+// that holds primitives (terrain_rw, vf_kernels.h) and drops an occluding primitive's coverage where the terrain is in front of it.
 // All arithmetic is binary32 in the order DESIGN.md states (compiled with -ffp-contract=off); tests/overlay_model/overlay_model.c
 // and tests/polygon_model/polygon_model.c are the same contract on the CPU and the GPU frames equal it bit for bit.
 #pragma once
 #include "vf_device.h"
+#include "vf_kernels.h"
 
 namespace vf {
 
@@ -33,6 +37,7 @@ constexpr uint32_t kOvSortCap = 4096;           // indices a bin sorts in LDS at
 constexpr uint32_t kOvMaxPrims = 1u << 24;      // primitive budget of a handle (all layers)
 constexpr uint32_t kOvCircle = 0u, kOvSquare = 1u, kOvSegment = 2u;
 constexpr uint32_t kOvKindMask = 3u, kOvDrape = 4u, kOvExt0 = 8u, kOvExt1 = 16u;
+constexpr uint32_t kOvOcclude = 32u;            // point / segment of an occluding layer: hidden behind the terrain (pad[0] = bits of kb)
 // polygon fill records (OvIn kind kOvPoly): kPgHeader marks a feature's header, kPgClose an edge's closing-segment slot
 constexpr uint32_t kOvPoly = 3u, kPgHeader = kOvExt0, kPgClose = kOvExt1;
 constexpr uint32_t kOvFillHdr = 3u, kOvFillEdge = 4u, kOvNone = 7u;  // OvPrim kinds of fill records (kOvNone: nothing this frame)
@@ -46,7 +51,8 @@ struct OvIn {
     uint32_t flags;        // kind | kOvDrape | kOvExt0 / kOvExt1 (square cap: the segment reaches hw past its path's first / last vertex)
     uint32_t rgba;         // sRGB8 bytes, r | g << 8 | b << 16 | alpha << 24
     uint32_t feature;      // feature number (ascending with the primitive index; equal for the primitives of one polyline)
-    uint32_t pad[2];       // polygon edge slot: the record index of its ring's first slot, the ring's vertex count
+    uint32_t pad[2];       // polygon edge slot: the record index of its ring's first slot, the ring's vertex count;
+                           // point / segment with kOvOcclude: pad[0] = bits of kb = 1 + depth_bias (the layer's depth factor)
 };
 // A polygon fill feature is one header record (rgba = its fill colour) followed by two slots per ring edge (v_e -> v_e+1, ring order):
 // the kept part (flags without kPgClose) and the closing segment (kPgClose).  p0 / p1 = v_e / v_e+1; size holds the bits of the
@@ -107,8 +113,11 @@ __device__ __forceinline__ void ov_span(float a, float b, uint32_t n, int &lo, i
     hi = min(hi, (int)n - 1);
 }
 
+// dep (a handle with an occluding layer; else nullptr): per primitive (rw_a, rw_b - rw_a, kb, 0) of an occluding point (rw_b = rw_a)
+// or segment (its ends after clipping), zero for every other primitive
 __global__ __launch_bounds__(256) void k_ov_setup(FrameParams P, AxisTables A, uint32_t nprims, const OvIn *__restrict__ in,
-                                                  OvPrim *__restrict__ out, uint2 *__restrict__ box, uint32_t *__restrict__ cnt, uint32_t nbx)
+                                                  OvPrim *__restrict__ out, uint2 *__restrict__ box, uint32_t *__restrict__ cnt, uint32_t nbx,
+                                                  float4 *__restrict__ dep)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nprims) return;
@@ -120,6 +129,9 @@ __global__ __launch_bounds__(256) void k_ov_setup(FrameParams P, AxisTables A, u
     o.g = make_float4(0.0f, 0.0f, 0.0f, 0.0f); o.h = o.g;
     o.kind = kind; o.rgba = q.rgba; o.feature = q.feature; o.pad = 0u;
     float x0 = 0.0f, x1 = -1.0f, y0 = 0.0f, y1 = -1.0f;                // conservative screen extent (empty by default)
+    const bool occl = (q.flags & kOvOcclude) != 0u;
+    const float kb = __uint_as_float(q.pad[0]);
+    float4 d = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     float a[4];
     ov_clip(P, A, q.p0, drape, a);
     if (kind != kOvSegment) {
@@ -129,6 +141,7 @@ __global__ __launch_bounds__(256) void k_ov_setup(FrameParams P, AxisTables A, u
             if (isfinite(sx) && isfinite(sy)) {
                 const float r = q.size, R = r + 1.0f;
                 o.g = make_float4(sx, sy, r, 0.0f);
+                if (occl) d = make_float4(rw, 0.0f, kb, 0.0f);
                 x0 = sx - R; x1 = sx + R; y0 = sy - R; y1 = sy + R;
             }
         }
@@ -161,12 +174,14 @@ __global__ __launch_bounds__(256) void k_ov_setup(FrameParams P, AxisTables A, u
                 const float hw = q.size, e0 = ext0 ? hw : 0.0f, e1 = ext1 ? hw : 0.0f;
                 o.g = make_float4(ax, ay, ex / L, ey / L);
                 o.h = make_float4(L, hw, e0, e1);
+                if (occl) d = make_float4(rwa, rwb - rwa, kb, 0.0f);
                 const float R = hw + fmaxf(e0, e1) + 1.0f;
                 x0 = fminf(ax, bx) - R; x1 = fmaxf(ax, bx) + R; y0 = fminf(ay, by) - R; y1 = fmaxf(ay, by) + R;
             }
         }
     }
     out[i] = o;
+    if (dep) dep[i] = d;
     int px0 = 1, px1 = 0, py0 = 1, py1 = 0;
     if (x0 <= x1) { ov_span(x0, x1, P.W, px0, px1); ov_span(y0, y1, P.H, py0, py1); }
     if (px0 > px1 || py0 > py1) { box[i] = make_uint2(1u, 0u); return; }   // (bin x0 = 1 > x1 = 0: nothing)
@@ -481,16 +496,18 @@ __device__ __forceinline__ uint32_t ov_pow2(uint32_t n)
     return m;
 }
 
-__global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
-                                                      uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
-                                                      const uint32_t *__restrict__ list, const float *__restrict__ decode,
-                                                      const float *__restrict__ thresh, const uint32_t *__restrict__ mask,
-                                                      uint32_t *__restrict__ rgba)
+// The compositing workgroup of one bin (k_ov_composite, k_ov_composite_occlude; the LDS arrays are the kernel's).  OCCLUDE (a handle
+// with an occluding layer): P, V and vis give each pixel the terrain's 1/w, dep / sdep each occluding primitive its own;
+// the other instantiation does not read them.
+template <bool OCCLUDE>
+__device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
+                                             uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
+                                             const uint32_t *__restrict__ list, const float *__restrict__ decode,
+                                             const float *__restrict__ thresh, const uint32_t *__restrict__ mask,
+                                             uint32_t *__restrict__ rgba, const FrameParams *P, const SetupView *V,
+                                             const uint32_t *__restrict__ vis, const float4 *__restrict__ dep,
+                                             uint32_t *keys, OvPrim *recs, float4 *sdep, float *sdec, float *sthr, uint32_t &s_n, uint32_t &s_next)
 {
-    __shared__ uint32_t keys[kOvSortCap];
-    __shared__ OvPrim recs[256];
-    __shared__ float sdec[256], sthr[256];
-    __shared__ uint32_t s_n, s_next;
     // (built without the tuning switches this kernel takes exactly v0..v39 and a 64-bit shift by v39: the form isa_lint refuses, vf_device.h)
     VF_RESERVE_VGPR(40);
     const uint32_t bin = blockIdx.x, tid = threadIdx.x;
@@ -503,6 +520,13 @@ __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, ui
     const size_t o = (size_t)py * W + px;
     const float qx = (float)px + 0.5f, qy = (float)py + 0.5f;
     const float rb = (float)((bin % nbx + 1u) * kOvBin);                // the bin's right edge (fill crossings beyond it: the mask)
+    float Q = 0.0f;                                                     // the terrain's 1/w here (background: 0, hides nothing)
+    if constexpr (OCCLUDE) {
+        if (on) {
+            const uint32_t id = vis[o];
+            if (id) Q = terrain_rw(*P, *V, id - 1u, (int32_t)px, (int32_t)py);
+        }
+    }
     OvPixel S;
     S.c[0] = S.c[1] = S.c[2] = 0.0f; S.touched = false; S.feature = 0xFFFFFFFFu; S.rgba = 0u; S.cov = 0.0f;
     S.fill = false; S.par = 0u; S.d2 = 0.0f;
@@ -513,6 +537,7 @@ __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, ui
             __syncthreads();
             if (k0 + tid < m) {
                 recs[tid] = prims[keys[k0 + tid]];
+                if constexpr (OCCLUDE) sdep[tid] = dep[keys[k0 + tid]];
                 OvPrim &r = recs[tid];
                 if (r.kind == kOvFillHdr) {                             // this bin's word of the feature's backdrop mask
                     const uint32_t b0 = __float_as_uint(r.g.y), fw = __float_as_uint(r.g.z);
@@ -530,7 +555,21 @@ __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, ui
                         ov_flush(S, sdec, rgba, o);
                         S.feature = p.feature; S.rgba = p.rgba; S.cov = 0.0f; S.fill = false;
                     }
-                    if (p.kind <= kOvSegment) S.cov = fmaxf(S.cov, ov_cover(p, qx, qy));
+                    if (p.kind <= kOvSegment) {
+                        float c = ov_cover(p, qx, qy);
+                        if constexpr (OCCLUDE) {
+                            const float4 d = sdep[k];
+                            if (d.z > 0.0f && c > 0.0f) {                // an occluding primitive: its 1/w here against the terrain's
+                                float rw = d.x;
+                                if (p.kind == kOvSegment) {
+                                    const float u = (qx - p.g.x) * p.g.z + (qy - p.g.y) * p.g.w;
+                                    rw = fmaf(fminf(fmaxf(u / p.h.x, 0.0f), 1.0f), d.y, d.x);
+                                }
+                                if (Q > rw * d.z) c = 0.0f;
+                            }
+                        }
+                        S.cov = fmaxf(S.cov, c);
+                    }
                     else if (p.kind == kOvFillEdge) {
                         const float ymin = __uint_as_float(p.rgba), ymax = __uint_as_float(p.pad);
                         if (ymin <= qy && qy < ymax) {
@@ -588,6 +627,49 @@ __global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, ui
     }
     __syncthreads();
     if (tid == 0) cnt[bin] = 0u;                         // (the next frame's k_ov_setup counts from zero)
+}
+
+// vf_terrain_set_layer_occlusion: a point / line layer's records [lo, hi) gain or lose kOvOcclude and kb, in place
+__global__ __launch_bounds__(256) void k_ov_occlude(uint32_t lo, uint32_t hi, OvIn *__restrict__ in, uint32_t on, uint32_t kb_bits)
+{
+    const uint32_t i = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hi) return;
+    OvIn &q = in[i];
+    if ((q.flags & kOvKindMask) == kOvPoly) return;
+    q.flags = on ? (q.flags | kOvOcclude) : (q.flags & ~kOvOcclude);
+    q.pad[0] = on ? kb_bits : 0u;
+}
+
+// The composite of a handle with an occluding layer (reads the frame's visibility, vis, and the set-up's vertex records, V).
+__global__ __launch_bounds__(256) void k_ov_composite_occlude(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
+                                                              uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
+                                                              const uint32_t *__restrict__ list, const float *__restrict__ decode,
+                                                              const float *__restrict__ thresh, const uint32_t *__restrict__ mask,
+                                                              uint32_t *__restrict__ rgba, FrameParams P, SetupView V,
+                                                              const uint32_t *__restrict__ vis, const float4 *__restrict__ dep)
+{
+    __shared__ uint32_t keys[kOvSortCap];
+    __shared__ OvPrim recs[256];
+    __shared__ float4 sdep[256];
+    __shared__ float sdec[256], sthr[256];
+    __shared__ uint32_t s_n, s_next;
+    ov_composite<true>(W, H, nbx, prims, cnt, start, list, decode, thresh, mask, rgba, &P, &V, vis, dep, keys, recs, sdep, sdec, sthr, s_n, s_next);
+}
+
+// The composite of every other handle with overlays.  (Kept the last plain kernel of the library, and as it was before occlusion
+// existed: the code after it -- the generic raster path the tile kernels call -- keeps its place, so their calls stay bit-identical.)
+__global__ __launch_bounds__(256) void k_ov_composite(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
+                                                      uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
+                                                      const uint32_t *__restrict__ list, const float *__restrict__ decode,
+                                                      const float *__restrict__ thresh, const uint32_t *__restrict__ mask,
+                                                      uint32_t *__restrict__ rgba)
+{
+    __shared__ uint32_t keys[kOvSortCap];
+    __shared__ OvPrim recs[256];
+    __shared__ float sdec[256], sthr[256];
+    __shared__ uint32_t s_n, s_next;
+    ov_composite<false>(W, H, nbx, prims, cnt, start, list, decode, thresh, mask, rgba, nullptr, nullptr, nullptr, nullptr, keys, recs, nullptr,
+                        sdec, sthr, s_n, s_next);
 }
 
 } // namespace vf

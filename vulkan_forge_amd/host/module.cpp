@@ -430,9 +430,10 @@ public:
     void enable_timing(bool on) { Borrow b(busy); check(vf_terrain_enable_timing(t, on ? 1 : 0)); }
 
     // extension: overlays over the terrain frame (include/vf_hip.h; argument rules: vulkan_forge_amd/_overlays.py)
-    uint32_t add_points(py::object xyz, py::object size_px, py::object rgba, py::object shape, bool drape)
+    uint32_t add_points(py::object xyz, py::object size_px, py::object rgba, py::object shape, bool drape, py::object occlude, py::object depth_bias)
     {
         py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("point_args")(xyz, size_px, rgba, shape);
+        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
         py::array pts = a[0].cast<py::array>(), dcol = a[3].cast<py::array>();
         const float dsize = a[1].cast<float>();
         py::object sizes = a[2], cols = a[4];
@@ -443,11 +444,13 @@ public:
         uint32_t id = 0;
         check(vf_terrain_add_points(t, static_cast<const float *>(pts.data()), (uint32_t)pts.shape(0), sz, cl, dsize,
                                     static_cast<const uint8_t *>(dcol.data()), shp, drape ? 1 : 0, &id));
+        if (oc[0].cast<bool>()) check(vf_terrain_set_layer_occlusion(t, id, 1, oc[1].cast<float>()));
         return id;
     }
-    uint32_t add_lines(py::object paths, py::object width_px, py::object rgba, py::object cap, bool drape)
+    uint32_t add_lines(py::object paths, py::object width_px, py::object rgba, py::object cap, bool drape, py::object occlude, py::object depth_bias)
     {
         py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("line_args")(paths, width_px, rgba, cap);
+        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
         py::array coords = a[0].cast<py::array>(), offsets = a[1].cast<py::array>(), col = a[3].cast<py::array>();
         const float width = a[2].cast<float>();
         const int cp = a[4].cast<int>();
@@ -455,6 +458,7 @@ public:
         uint32_t id = 0;
         check(vf_terrain_add_lines(t, static_cast<const float *>(coords.data()), static_cast<const uint32_t *>(offsets.data()),
                                    (uint32_t)(offsets.shape(0) - 1), width, static_cast<const uint8_t *>(col.data()), cp, drape ? 1 : 0, &id));
+        if (oc[0].cast<bool>()) check(vf_terrain_set_layer_occlusion(t, id, 1, oc[1].cast<float>()));
         return id;
     }
     uint32_t add_polygons(py::object polygons, py::object fill_rgba, py::object line_rgba, py::object line_width_px, bool drape)
@@ -470,6 +474,13 @@ public:
                                       (uint32_t)(rings.shape(0) - 1), static_cast<const uint32_t *>(feats.data()), (uint32_t)(feats.shape(0) - 1),
                                       bytes(fills), bytes(dfill), bytes(line), width, drape ? 1 : 0, &id));
         return id;
+    }
+    // occlusion of a point / line layer by the terrain
+    void set_layer_occlusion(uint32_t layer, py::object occlude, py::object depth_bias)
+    {
+        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
+        Borrow b(busy);
+        check(vf_terrain_set_layer_occlusion(t, layer, oc[0].cast<bool>() ? 1 : 0, oc[1].cast<float>()));
     }
     void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
 
@@ -767,9 +778,13 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
         .def("enable_timing", &T::enable_timing, py::arg("on") = true)
         .def("last_timings", &T::last_timings)
         .def("add_points", &T::add_points, py::arg("xyz"), py::kw_only(), py::arg("size_px") = 5.0f,
-             py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("shape") = "circle", py::arg("drape") = false)
+             py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("shape") = "circle", py::arg("drape") = false,
+             py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
         .def("add_lines", &T::add_lines, py::arg("paths"), py::kw_only(), py::arg("width_px") = 2.0f,
-             py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("cap") = "round", py::arg("drape") = false)
+             py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("cap") = "round", py::arg("drape") = false,
+             py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
+        .def("set_layer_occlusion", &T::set_layer_occlusion, py::arg("layer"), py::arg("occlude"),
+             py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
         .def("add_polygons", &T::add_polygons, py::arg("polygons"), py::kw_only(), py::arg("fill_rgba") = py::make_tuple(255, 255, 255, 255),
              py::arg("line_rgba") = py::none(), py::arg("line_width_px") = 1.0f, py::arg("drape") = false)
         .def("clear_overlays", &T::clear_overlays);
