@@ -13,13 +13,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "polygon_model"))
 import polygon_model as pm  # noqa: E402
 om = pm.om
@@ -33,16 +31,9 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        src = os.path.join(HERE, "occlusion_model.c")
-        deps = [src, os.path.join(os.path.dirname(HERE), "polygon_model", "polygon_model.c"),
-                os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")]
-        out = os.path.join(ROOT, "build", "libocmodel.so")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
-            tmp = out + f".{os.getpid()}.tmp"
-            subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
-            os.replace(tmp, out)
-        L = C.CDLL(out)
+        L = om.build_model("libocmodel.so", os.path.join(HERE, "occlusion_model.c"),
+                           [os.path.join(os.path.dirname(HERE), "polygon_model", "polygon_model.c"),
+                            os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")])
         vp, u32, i = C.c_void_p, C.c_uint32, C.c_int
         L.ocm_composite.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
         L.ocm_composite.restype = i

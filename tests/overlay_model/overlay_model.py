@@ -29,17 +29,22 @@ CAPS = ("butt", "square", "round")
 _lib = None
 
 
+def build_model(out_name, src, deps=()):
+    """-> the CPU model `src` (C) loaded from build/`out_name`, compiled again when that is older than `src` or any of `deps` (the
+    model sources it includes)"""
+    out = os.path.join(ROOT, "build", out_name)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in (src, *deps)):
+        tmp = out + f".{os.getpid()}.tmp"
+        subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
+        os.replace(tmp, out)
+    return C.CDLL(out)
+
+
 def lib():
     global _lib
     if _lib is None:
-        src = os.path.join(HERE, "overlay_model.c")
-        out = os.path.join(ROOT, "build", "libovmodel.so")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
-            tmp = out + f".{os.getpid()}.tmp"
-            subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
-            os.replace(tmp, out)
-        L = C.CDLL(out)
+        L = build_model("libovmodel.so", os.path.join(HERE, "overlay_model.c"))
         vp, u32, f = C.c_void_p, C.c_uint32, C.c_float
         L.ovm_composite.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32]
         L.ovm_composite.restype = C.c_int

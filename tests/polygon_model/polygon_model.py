@@ -12,13 +12,11 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
 import overlay_model as om  # noqa: E402
 
@@ -28,15 +26,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        src = os.path.join(HERE, "polygon_model.c")
-        dep = os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")
-        out = os.path.join(ROOT, "build", "libpgmodel.so")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(dep)):
-            tmp = out + f".{os.getpid()}.tmp"
-            subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
-            os.replace(tmp, out)
-        L = C.CDLL(out)
+        L = om.build_model("libpgmodel.so", os.path.join(HERE, "polygon_model.c"),
+                           [os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")])
         vp, u32, i = C.c_void_p, C.c_uint32, C.c_int
         L.pgm_composite.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
         L.pgm_composite.restype = i

@@ -11,16 +11,12 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(HERE, "overlay_model"))
 sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
 import occlusion_model as ocm  # noqa: E402
+from overlay_scenes import GRID, apply, heights, scene  # noqa: E402
 
-GRID = 1024
-CAMERAS = {
-    "default": ((3.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 45.0, 0.1, 100.0),
-    "fill": ((0.0, 2.2, 0.01), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 60.0, 0.1, 100.0),
-    "near": ((0.2, 0.6, 0.1), (1.5, 0.2, 1.2), (0.0, 1.0, 0.0), 70.0, 0.5, 100.0),
-    "ridge": ((0.0, 1.0, 3.0), (0.0, 0.3, 0.0), (0.0, 1.0, 0.0), 50.0, 0.1, 100.0),
-}
+RIDGE = ((0.0, 1.0, 3.0), (0.0, 0.3, 0.0), (0.0, 1.0, 0.0), 50.0, 0.1, 100.0)     # from in front of ridge(), over its crest
 
 
 @pytest.fixture(scope="module")
@@ -29,23 +25,9 @@ def vf():
     return vulkan_forge
 
 
-def heights(seed=7, shape=(257, 311)):
-    rng = np.random.default_rng(seed)
-    return (rng.random(shape, dtype=np.float32) * 0.6 - 0.3).astype(np.float32)
-
-
 def ridge(shape=(64, 64)):
     z = np.linspace(-1.5, 1.5, shape[0])
     return np.broadcast_to((1.5 * np.exp(-(z / 0.25) ** 2))[:, None], shape).astype(np.float32)
-
-
-def scene(vf, W, H, h, cam="default", precision=None):
-    s = vf.Scene(W, H, grid=GRID)
-    s.set_height_from_r32f(h)
-    if precision is not None:
-        s.set_shade_precision(precision)
-    s.set_camera_look_at(*CAMERAS[cam])
-    return s
 
 
 def oracle_vis(u, W, H, h):
@@ -81,22 +63,6 @@ def workload(seed=11, npts=8000, npaths=1200):
     return calls
 
 
-def apply(vf, s, calls):
-    L = ocm.Layers()
-    for meth, args, kw in calls:
-        getattr(s, meth)(*args, **kw)
-        if meth == "add_points":
-            L.points(args[0], **kw)
-        elif meth == "add_lines":
-            coords, offs = vf.pack_lines(args[0])
-            L.lines([coords[offs[p]:offs[p + 1]] for p in range(len(offs) - 1)], **kw)
-        else:
-            coords, rings, feats = vf.pack_polygons(args[0])
-            polys = [[coords[rings[r]:rings[r + 1]] for r in range(feats[f], feats[f + 1])] for f in range(len(feats) - 1)]
-            L.polygons(polys, **kw)
-    return L
-
-
 @pytest.mark.parametrize("precision", ["fast", "exact"])
 @pytest.mark.parametrize("size", [(1920, 1080), (257, 131)])
 @pytest.mark.parametrize("cam", ["default", "fill", "near"])
@@ -107,7 +73,7 @@ def test_frames_equal_the_model(vf, size, cam, precision):
     base = s.render_rgba()
     u = s.debug_uniforms_f32()
     vis = oracle_vis(u, W, H, h)
-    L = apply(vf, s, workload())
+    L = apply(vf, s, workload(), ocm.Layers())
     got = s.render_rgba()
     want = ocm.composite(base, vis, u, h, GRID, L)
     assert not np.array_equal(want, ocm.pm.composite(base, u, h, GRID, L))    # (occlusion changes the frame)
@@ -119,7 +85,8 @@ def test_frames_equal_the_model(vf, size, cam, precision):
 def test_the_ridge_hides_what_lies_behind_it(vf):
     W, H = 640, 400
     h = ridge()
-    s = scene(vf, W, H, h, "ridge")
+    s = scene(vf, W, H, h)
+    s.set_camera_look_at(*RIDGE)
     base = s.render_rgba()
     xs = np.linspace(-1.2, 1.2, 25, dtype=np.float32)
     behind = np.column_stack([xs, np.full(25, 0.02, np.float32), np.full(25, -0.9, np.float32)])
@@ -143,7 +110,7 @@ def test_png_batch_streaming_and_toggling_equal_the_model(vf, tmp_path):
         bases.append(s.render_rgba())
         us.append(s.debug_uniforms_f32())
         viss.append(oracle_vis(us[-1], W, H, h))
-    L = apply(vf, s, workload(3, 4000, 600))
+    L = apply(vf, s, workload(3, 4000, 600), ocm.Layers())
     frames = s.render_batch(poses)                            # per-pose visibility
     for k in range(len(poses)):
         assert np.array_equal(frames[k], ocm.composite(bases[k], viss[k], us[k], h, GRID, L)), f"pose {k}"
@@ -166,7 +133,7 @@ def test_clear_overlays_restores_a_plain_handle(vf):
     h = heights(4)
     plain = scene(vf, W, H, h).render_rgba()
     s = scene(vf, W, H, h)
-    apply(vf, s, workload(1, 2000, 300))
+    apply(vf, s, workload(1, 2000, 300), ocm.Layers())
     assert not np.array_equal(s.render_rgba(), plain)
     s.clear_overlays()
     assert np.array_equal(s.render_rgba(), plain)
@@ -180,7 +147,7 @@ def test_visibility_read_back_is_unchanged_by_occlusion(vf):
     plain.render_rgba()
     vis = plain.debug_visibility()
     s = scene(vf, W, H, h)
-    apply(vf, s, workload(2, 500, 90))
+    apply(vf, s, workload(2, 500, 90), ocm.Layers())
     s.render_rgba()
     assert np.array_equal(s.debug_visibility(), vis)
 

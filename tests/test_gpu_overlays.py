@@ -11,31 +11,13 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "overlay_model"))
 import overlay_model as om  # noqa: E402
-
-GRID = 1024
-CAMERAS = {
-    "default": ((3.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 45.0, 0.1, 100.0),
-    "fill": ((0.0, 2.2, 0.01), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 60.0, 0.1, 100.0),
-    "near": ((0.2, 0.6, 0.1), (1.5, 0.2, 1.2), (0.0, 1.0, 0.0), 70.0, 0.5, 100.0),   # lines pass beside and behind the eye
-}
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def vf():
     import vulkan_forge
     return vulkan_forge
-
-
-def heights(seed=7, shape=(257, 311)):
-    rng = np.random.default_rng(seed)
-    return (rng.random(shape, dtype=np.float32) * 0.6 - 0.3).astype(np.float32)
-
-
-def scene(vf, W, H, h, cam="default"):
-    s = vf.Scene(W, H, grid=GRID)
-    s.set_height_from_r32f(h)
-    s.set_camera_look_at(*CAMERAS[cam])
-    return s
 
 
 def workload(seed=11, npts=10_000, npaths=2_000):
@@ -65,18 +47,6 @@ def workload(seed=11, npts=10_000, npaths=2_000):
     return calls
 
 
-def apply(vf, s, calls):
-    L = om.Layers()
-    for meth, args, kw in calls:
-        getattr(s, meth)(*args, **kw)
-        if meth == "add_points":
-            L.points(args[0], **kw)
-        else:
-            coords, offs = vf.pack_lines(args[0])
-            L.lines([coords[offs[p]:offs[p + 1]] for p in range(len(offs) - 1)], **kw)
-    return L
-
-
 @pytest.mark.parametrize("size", [(1920, 1080), (257, 131)])
 @pytest.mark.parametrize("cam", list(CAMERAS))
 def test_frames_equal_the_model(vf, size, cam):
@@ -85,7 +55,7 @@ def test_frames_equal_the_model(vf, size, cam):
     s = scene(vf, W, H, h, cam)
     base = s.render_rgba()
     u = s.debug_uniforms_f32()
-    L = apply(vf, s, workload())
+    L = apply(vf, s, workload(), om.Layers())
     got = s.render_rgba()
     want = om.composite(base, u, h, GRID, L)
     assert not np.array_equal(want, base)
@@ -105,7 +75,7 @@ def test_png_and_batch_equal_the_model(vf, tmp_path):
         s.set_camera_look_at(*p)
         bases.append(s.render_rgba())
         us.append(s.debug_uniforms_f32())
-    L = apply(vf, s, workload(3, 4000, 800))
+    L = apply(vf, s, workload(3, 4000, 800), om.Layers())
     frames = s.render_batch(poses)
     for k, p in enumerate(poses):
         want = om.composite(bases[k], us[k], h, GRID, L)
@@ -148,7 +118,7 @@ def test_clear_overlays_restores_a_plain_handle(vf):
     h = heights(4)
     plain = scene(vf, W, H, h).render_rgba()
     s = scene(vf, W, H, h)
-    apply(vf, s, workload(1, 2000, 300))
+    apply(vf, s, workload(1, 2000, 300), om.Layers())
     assert not np.array_equal(s.render_rgba(), plain)
     s.clear_overlays()
     assert np.array_equal(s.render_rgba(), plain)
@@ -163,7 +133,7 @@ def test_visibility_read_back_ignores_overlays(vf):
     plain.render_rgba()
     vis = plain.debug_visibility()
     s = scene(vf, W, H, h)
-    apply(vf, s, workload(2, 500, 100))
+    apply(vf, s, workload(2, 500, 100), om.Layers())
     s.render_rgba()
     assert np.array_equal(s.debug_visibility(), vis)
 

@@ -9,33 +9,17 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "polygon_model"))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "overlay_model"))
+sys.path.insert(0, os.path.join(HERE, "polygon_model"))
 import polygon_model as pm  # noqa: E402
-
-GRID = 1024
-CAMERAS = {
-    "default": ((3.0, 2.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 45.0, 0.1, 100.0),
-    "fill": ((0.0, 2.2, 0.01), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 60.0, 0.1, 100.0),
-    "near": ((0.2, 0.6, 0.1), (1.5, 0.2, 1.2), (0.0, 1.0, 0.0), 70.0, 0.5, 100.0),   # rings pass beside and behind the eye
-}
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def vf():
     import vulkan_forge
     return vulkan_forge
-
-
-def heights(seed=7, shape=(257, 311)):
-    rng = np.random.default_rng(seed)
-    return (rng.random(shape, dtype=np.float32) * 0.6 - 0.3).astype(np.float32)
-
-
-def scene(vf, W, H, h, cam="default"):
-    s = vf.Scene(W, H, grid=GRID)
-    s.set_height_from_r32f(h)
-    s.set_camera_look_at(*CAMERAS[cam])
-    return s
 
 
 def blob(rng, c, r, n, y):
@@ -86,22 +70,6 @@ def workload(seed=11, npoly=240, npts=3000, npaths=600):
     return calls
 
 
-def apply(vf, s, calls, L=None):
-    L = pm.Layers() if L is None else L
-    for meth, args, kw in calls:
-        getattr(s, meth)(*args, **kw)
-        if meth == "add_points":
-            L.points(args[0], **kw)
-        elif meth == "add_lines":
-            coords, offs = vf.pack_lines(args[0])
-            L.lines([coords[offs[p]:offs[p + 1]] for p in range(len(offs) - 1)], **kw)
-        else:
-            coords, rings, feats = vf.pack_polygons(args[0])
-            polys = [[coords[rings[r]:rings[r + 1]] for r in range(feats[f], feats[f + 1])] for f in range(len(feats) - 1)]
-            L.polygons(polys, **kw)
-    return L
-
-
 def check(got, want, base):
     assert not np.array_equal(want, base)
     diff = (got != want).any(axis=2)
@@ -116,7 +84,7 @@ def test_frames_equal_the_model(vf, size, cam):
     s = scene(vf, W, H, h, cam)
     base = s.render_rgba()
     u = s.debug_uniforms_f32()
-    L = apply(vf, s, workload())
+    L = apply(vf, s, workload(), pm.Layers())
     got = s.render_rgba()
     check(got, pm.composite(base, u, h, GRID, L), base)
     assert np.array_equal(s.render_rgba(), got)               # (again: the pass leaves its counters and boxes as it found them)
@@ -133,7 +101,7 @@ def test_png_and_batch_equal_the_model(vf, tmp_path):
         s.set_camera_look_at(*p)
         bases.append(s.render_rgba())
         us.append(s.debug_uniforms_f32())
-    L = apply(vf, s, workload(3, 120, 800, 200))
+    L = apply(vf, s, workload(3, 120, 800, 200), pm.Layers())
     frames = s.render_batch(poses)
     for k, p in enumerate(poses):
         assert np.array_equal(frames[k], pm.composite(bases[k], us[k], h, GRID, L)), f"pose {k}"
@@ -158,7 +126,7 @@ def test_screen_covering_fill_and_rings_off_every_edge(vf, cam):
               np.array([[-0.3, 0.2, -6], [-0.1, 0.1, 6], [0.2, 0.2, 6], [0.1, 0.3, -6]], np.float32)]      # off the top and bottom edges
     calls = [("add_polygons", ([cover],), dict(fill_rgba=(20, 200, 90, 120))),
              ("add_polygons", (across,), dict(fill_rgba=(250, 90, 20, 200), line_rgba=(0, 0, 0, 255), line_width_px=2.0))]
-    L = apply(vf, s, calls)
+    L = apply(vf, s, calls, pm.Layers())
     check(s.render_rgba(), pm.composite(base, u, h, GRID, L), base)
 
 
@@ -205,7 +173,7 @@ def test_a_200k_vertex_ring(vf):
     a = np.linspace(0, 2 * np.pi, n, endpoint=False)
     r = 1.35 + 0.12 * np.sin(37 * a) + 0.05 * np.sin(1013 * a)
     ring = np.column_stack([r * np.cos(a), np.full(n, 0.2), r * np.sin(a)]).astype(np.float32)
-    L = apply(vf, s, [("add_polygons", ([ring],), dict(fill_rgba=(60, 60, 255, 170), line_rgba=(255, 255, 255, 255)))])
+    L = apply(vf, s, [("add_polygons", ([ring],), dict(fill_rgba=(60, 60, 255, 170), line_rgba=(255, 255, 255, 255)))], pm.Layers())
     check(s.render_rgba(), pm.composite(base, u, h, GRID, L), base)
 
 
@@ -227,7 +195,7 @@ def test_more_than_4096_primitives_in_one_bin(vf):
         polys.append((p[:, :3] / p[:, 3:4]).astype(np.float32))
     cols = rng.integers(0, 256, (1500, 4), dtype=np.uint8)
     cols[:, 3] = rng.integers(40, 256, 1500)
-    L = apply(vf, s, [("add_polygons", (polys,), dict(fill_rgba=cols))])
+    L = apply(vf, s, [("add_polygons", (polys,), dict(fill_rgba=cols))], pm.Layers())
     check(s.render_rgba(), pm.composite(base, u, h, GRID, L), base)
 
 
@@ -250,7 +218,7 @@ def test_clear_overlays_restores_a_plain_handle_and_shards_refuse(vf):
     h = heights(4)
     plain = scene(vf, W, H, h).render_rgba()
     s = scene(vf, W, H, h)
-    apply(vf, s, workload(1, 60, 300, 80))
+    apply(vf, s, workload(1, 60, 300, 80), pm.Layers())
     assert not np.array_equal(s.render_rgba(), plain)
     s.clear_overlays()
     assert np.array_equal(s.render_rgba(), plain)

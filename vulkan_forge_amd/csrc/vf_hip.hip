@@ -196,6 +196,34 @@ struct FramePlan {
     uint32_t *rc_lo = nullptr, *rc_hi = nullptr, *seg_count = nullptr;
 };
 
+// A device array that grows (the overlay state).  reserve: when need > cap, a new allocation of new_cap elements, zero-filled on request,
+// with the first `keep` elements copied over; the old one is freed only when all of that has succeeded -- a failure frees the new one and
+// leaves the array as it was.
+template <typename T> struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    hipError_t reserve(size_t need, size_t new_cap, size_t keep = 0, bool zero = false)
+    {
+        if (need <= cap) return hipSuccess;
+        T *q = nullptr;
+        hipError_t e = hipMalloc(&q, new_cap * sizeof(T));
+        if (e == hipSuccess && zero) e = hipMemset(q, 0, new_cap * sizeof(T));
+        if (e == hipSuccess && keep) e = hipMemcpy(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            if (q) (void)hipFree(q);
+            return e;
+        }
+        release();
+        p = q; cap = new_cap;
+        return hipSuccess;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+
 struct vf_terrain {
     vf_ctx *ctx = nullptr;
     uint32_t W = 0, H = 0, n = 0;
@@ -347,32 +375,29 @@ struct vf_terrain {
     // Overlays (vf_terrain_add_points / _add_lines, vf_overlay.h): made by the first add, freed by vf_terrain_clear_overlays -- a handle
     // without overlays holds none of it and launches nothing for them.
     struct Overlays {
-        uint32_t nprims = 0, cap = 0, features = 0, layers = 0;
-        OvIn *d_in = nullptr;                // [cap] primitives as added, in feature order
-        OvPrim *d_prim = nullptr;            // [cap] ... as the frame sees them (k_ov_setup)
-        uint2 *d_box = nullptr;              // [cap] bin rectangle
+        uint32_t nprims = 0, features = 0;
+        DevBuf<OvIn> in;                     // [nprims] primitives as added, in feature order
+        DevBuf<OvPrim> prim;                 // [nprims] ... as the frame sees them (k_ov_setup)
+        DevBuf<uint2> box;                   // [nprims] bin rectangle
         uint32_t *d_cnt = nullptr;           // [nbins] pairs per bin (zero between frames)
         uint32_t *d_start = nullptr;         // [nbins + 1] each bin's slice of the pair list; [nbins] = pairs in all
         float *d_decode = nullptr;           // 256 sRGB8 -> linear (SrgbTables::decode)
-        uint32_t *d_list = nullptr;          // pair list (primitive indices)
-        size_t list_cap = 0;
+        DevBuf<uint32_t> list;               // pair list (primitive indices)
         uint32_t *h_total = nullptr;         // pinned: the frame's pair count (the list is sized by it); [2..3] the mask words (fills)
         hipEvent_t counted = nullptr;
         // polygon fills (vf_terrain_add_polygons): made by the first polygon layer
-        uint32_t nfill = 0, fill_cap = 0;    // fill features (each: one header record and two slots per ring edge)
+        uint32_t nfill = 0;                  // fill features (each: one header record and two slots per ring edge)
         uint32_t pg_lo = 0, pg_hi = 0;       // record index range that holds every fill record
-        std::vector<uint32_t> hdr;           // [nfill] each fill feature's header record index (host copy of d_pg_hdr)
-        uint32_t *d_pg_hdr = nullptr;        // [fill_cap]
-        uint4 *d_pg_fbox = nullptr;          // [fill_cap] folded feature box (zero between frames)
-        uint4 *d_pg_fbin = nullptr;          // [fill_cap] the frame's mask base and bin box of each fill feature
-        unsigned long long *d_pg_total = nullptr;   // the frame's mask words (zero between frames)
-        uint32_t *d_mask = nullptr;          // (feature, bin) backdrop masks, bit r: parity of row r's crossings right of the bin
-        size_t mask_cap = 0;
+        DevBuf<uint32_t> pg_hdr;             // [nfill] each fill feature's header record index
+        DevBuf<uint4> pg_fbox;               // [nfill] folded feature box (zero between frames)
+        DevBuf<uint4> pg_fbin;               // [nfill] the frame's mask base and bin box of each fill feature
+        DevBuf<unsigned long long> pg_total; // [1] the frame's mask words (zero between frames)
+        DevBuf<uint32_t> mask;               // (feature, bin) backdrop masks, bit r: parity of row r's crossings right of the bin
         // occlusion (vf_terrain_set_layer_occlusion)
         struct Layer { uint32_t lo, hi; bool polygon, occlude; };
-        std::vector<Layer> layer;            // [layers] each layer's record range
+        std::vector<Layer> layer;            // each layer's record range; a layer's id is its index
         uint32_t occluding = 0;              // layers with occlusion on: the frame stores its visibility and composites with depth
-        float4 *d_dep = nullptr;             // [cap] per primitive (rw_a, rw_b - rw_a, kb, 0) of occluding primitives (k_ov_setup)
+        DevBuf<float4> dep;                  // [nprims] per primitive (rw_a, rw_b - rw_a, kb, 0) of occluding primitives (k_ov_setup)
     } ov;
 };
 
@@ -515,6 +540,13 @@ static hipError_t sync_sides(const vf_terrain *t)            // (the side stream
     return e;
 }
 
+// the frame in flight (on the caller's stream, else the handle's own) has finished: what it reads may change now
+static hipError_t wait_frame(const vf_terrain *t)
+{
+    const hipError_t e = hipSetDevice(t->ctx->device);
+    return e != hipSuccess ? e : hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream);
+}
+
 // A plan queued ahead of its frame (vf_terrain::pre) is thrown away: back to where the handle stood before it, and that set's segment list
 // starts empty again (the stale k_block_boxes filled it; its k_clear, which would have emptied it, never runs).
 static hipError_t drop_preplan(vf_terrain *t, hipStream_t next_plan_on = nullptr)
@@ -585,8 +617,10 @@ static int refresh_tables(vf_terrain *t, hipStream_t s)
 static void ov_release(vf_terrain *t)
 {
     vf_terrain::Overlays &O = t->ov;
-    void *ptrs[] = { O.d_in, O.d_prim, O.d_box, O.d_cnt, O.d_start, O.d_decode, O.d_list, O.d_pg_hdr, O.d_pg_fbox, O.d_pg_fbin, O.d_pg_total, O.d_mask, O.d_dep };
+    void *ptrs[] = { O.d_cnt, O.d_start, O.d_decode };
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    O.in.release(); O.prim.release(); O.box.release(); O.list.release(); O.dep.release();
+    O.pg_hdr.release(); O.pg_fbox.release(); O.pg_fbin.release(); O.pg_total.release(); O.mask.release();
     if (O.h_total) (void)hipHostFree(O.h_total);
     if (O.counted) (void)hipEventDestroy(O.counted);
     O = vf_terrain::Overlays();
@@ -716,8 +750,7 @@ int vf_terrain_set_height(vf_terrain *t, const float *host_height, uint32_t tw, 
 {
     if (!t || !host_height) return fail(VF_ERR_INVALID, "NULL argument");
     if (tw == 0 || th == 0 || tw > 32768 || th > 32768) return fail(VF_ERR_INVALID, "height texture size must be in 1..32768");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    VF_HIP_TRY(wait_frame(t));
     VF_HIP_TRY(sync_sides(t));
     size_t bytes = (size_t)tw * th * sizeof(float);
     if ((size_t)t->tw * t->th != (size_t)tw * th || t->d_height != t->d_height_own) {
@@ -746,10 +779,9 @@ int vf_terrain_set_height_device(vf_terrain *t, const float *dev_height, uint32_
 {
     if (!t || !dev_height) return fail(VF_ERR_INVALID, "NULL argument");
     if (tw == 0 || th == 0 || tw > 32768 || th > 32768) return fail(VF_ERR_INVALID, "height texture size must be in 1..32768");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
     // a frame still in flight (caller's stream, or the plan / height-cache kernels on the side stream) reads the axis tables
     // and the old texture: let it finish before either changes
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    VF_HIP_TRY(wait_frame(t));
     VF_HIP_TRY(sync_sides(t));
     t->d_height = dev_height;
     int rc = set_height_common(t, tw, th);
@@ -798,9 +830,8 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!is_pow2(band_h) || band_h < (uint32_t)kTileH) return fail(VF_ERR_INVALID, "band_h must be a power of two >= 64 (the tile height)");
-    if (t->ov.layers) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
+    VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     VF_HIP_TRY(drop_preplan(t));
     t->rank = rank; t->nranks = nranks; t->band_h = band_h;
@@ -930,9 +961,8 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!layout_valid(skew)) return fail(VF_ERR_INVALID, "layout word is neither VF_TILE_LAYOUT(skew < 65536, stripe_log2 <= 15) nor a registered stripe map");
-    if (t->ov.layers) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
+    VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
     int rc = vf_tile_layout(t->W, t->H, rank, nranks, skew, map.data(), (uint32_t)map.size(), &n);
@@ -1252,64 +1282,46 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
     const uint32_t nbx = (t->W + kOvBin - 1u) / kOvBin, nby = (t->H + kOvBin - 1u) / kOvBin, nbins = nbx * nby;
     const dim3 per_prim((O.nprims + 255u) / 256u), threads(256);
     const bool occlude = O.occluding != 0u;
-    hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx,
-                       occlude ? O.d_dep : nullptr);
+    hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.in.p, O.prim.p, O.box.p, O.d_cnt, nbx,
+                       occlude ? O.dep.p : nullptr);
     const dim3 per_slot((O.pg_hi - O.pg_lo + 255u) / 256u);
     if (O.nfill) {                                          // fill edges and headers: binned with the rest
-        hipLaunchKernelGGL(k_pg_setup, per_slot, threads, 0, s, P, axis(t), O.pg_lo, O.pg_hi, O.d_in, O.d_prim, O.d_box, O.d_cnt, nbx, O.d_pg_fbox);
-        hipLaunchKernelGGL(k_pg_header, dim3((O.nfill + 255u) / 256u), threads, 0, s, P, O.nfill, O.d_pg_hdr, O.d_in, O.d_pg_fbox, O.d_pg_fbin,
-                           O.d_prim, O.d_box, O.d_cnt, nbx, O.d_pg_total);
+        hipLaunchKernelGGL(k_pg_setup, per_slot, threads, 0, s, P, axis(t), O.pg_lo, O.pg_hi, O.in.p, O.prim.p, O.box.p, O.d_cnt, nbx, O.pg_fbox.p);
+        hipLaunchKernelGGL(k_pg_header, dim3((O.nfill + 255u) / 256u), threads, 0, s, P, O.nfill, O.pg_hdr.p, O.in.p, O.pg_fbox.p, O.pg_fbin.p,
+                           O.prim.p, O.box.p, O.d_cnt, nbx, O.pg_total.p);
     }
     hipLaunchKernelGGL(k_ov_scan, dim3(1), dim3(1024), 0, s, nbins, O.d_cnt, O.d_start);
     VF_HIP_TRY(hipGetLastError());
     VF_HIP_TRY(hipMemcpyAsync(O.h_total, O.d_start + nbins, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (O.nfill) {
-        VF_HIP_TRY(hipMemcpyAsync(O.h_total + 2, O.d_pg_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-        VF_HIP_TRY(hipMemsetAsync(O.d_pg_total, 0, sizeof(unsigned long long), s));
+        VF_HIP_TRY(hipMemcpyAsync(O.h_total + 2, O.pg_total.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        VF_HIP_TRY(hipMemsetAsync(O.pg_total.p, 0, sizeof(unsigned long long), s));
     }
     VF_HIP_TRY(hipEventRecord(O.counted, s));
     VF_HIP_TRY(hipEventSynchronize(O.counted));
     const uint32_t total = *O.h_total;
     unsigned long long words = 0;
     if (O.nfill) std::memcpy(&words, O.h_total + 2, sizeof words);
-    if (total == 0u) return VF_OK;                          // (nothing on screen: the counts are zero again, the frame stays as drawn)
+    // (k_ov_scan has zeroed the counts: a frame that stops here leaves them as the next one needs them, and stays as drawn)
+    if (total == 0u) return VF_OK;                          // (nothing on screen)
     if (total == 0xFFFFFFFFu) return fail(VF_ERR_NOMEM, "overlays: more than 2^32 - 2 (primitive, screen bin) pairs in one frame");
-    if (words > 0xFFFFFFFFull) {
-        (void)hipMemsetAsync(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t), s);
-        return fail(VF_ERR_NOMEM, "overlays: polygon fills reach more than 2^32 - 1 (feature, screen bin) pairs in one frame");
-    }
-    if (words > O.mask_cap) {
-        if (O.d_mask) { (void)hipFree(O.d_mask); O.d_mask = nullptr; O.mask_cap = 0; }
-        const size_t want = (size_t)words + (size_t)words / 2u + 4096u;
-        const hipError_t e = hipMalloc(&O.d_mask, want * sizeof(uint32_t));
-        if (e != hipSuccess) {
-            (void)hipMemsetAsync(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t), s);
-            return fail(VF_ERR_NOMEM, std::string("polygon mask allocation failed: ") + hipGetErrorString(e));
-        }
-        O.mask_cap = want;
-    }
+    if (words > 0xFFFFFFFFull) return fail(VF_ERR_NOMEM, "overlays: polygon fills reach more than 2^32 - 1 (feature, screen bin) pairs in one frame");
+    hipError_t e = O.mask.reserve(words, words + words / 2u + 4096u);
+    if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("polygon mask allocation failed: ") + hipGetErrorString(e));
     if (words) {                                            // the backdrop: row crossings right of each bin, per fill feature
-        VF_HIP_TRY(hipMemsetAsync(O.d_mask, 0, (size_t)words * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_pg_backdrop, per_slot, threads, 0, s, t->H, O.pg_lo, O.pg_hi, O.d_in, O.d_prim, O.d_pg_fbin, O.d_mask);
-        hipLaunchKernelGGL(k_pg_prefix, dim3((O.nfill + 3u) / 4u), threads, 0, s, O.nfill, O.d_pg_fbin, O.d_mask);
+        VF_HIP_TRY(hipMemsetAsync(O.mask.p, 0, (size_t)words * sizeof(uint32_t), s));
+        hipLaunchKernelGGL(k_pg_backdrop, per_slot, threads, 0, s, t->H, O.pg_lo, O.pg_hi, O.in.p, O.prim.p, O.pg_fbin.p, O.mask.p);
+        hipLaunchKernelGGL(k_pg_prefix, dim3((O.nfill + 3u) / 4u), threads, 0, s, O.nfill, O.pg_fbin.p, O.mask.p);
     }
-    if (total > O.list_cap) {
-        if (O.d_list) { (void)hipFree(O.d_list); O.d_list = nullptr; O.list_cap = 0; }
-        const size_t want = (size_t)total + total / 2u + 4096u;
-        const hipError_t e = hipMalloc(&O.d_list, want * sizeof(uint32_t));
-        if (e != hipSuccess) {
-            (void)hipMemsetAsync(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t), s);
-            return fail(VF_ERR_NOMEM, std::string("overlay pair list allocation failed: ") + hipGetErrorString(e));
-        }
-        O.list_cap = want;
-    }
-    hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.d_box, nbx, O.d_start, O.d_cnt, O.d_list);
+    e = O.list.reserve(total, (size_t)total + total / 2u + 4096u);
+    if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay pair list allocation failed: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.box.p, nbx, O.d_start, O.d_cnt, O.list.p);
     if (occlude)
-        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
-                           t->ctx->d_thresh, O.d_mask, t->d_rgba, P, V, t->d_vis, O.d_dep);
+        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, O.d_decode,
+                           t->ctx->d_thresh, O.mask.p, t->d_rgba, P, V, t->d_vis, O.dep.p);
     else
-        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.d_prim, O.d_cnt, O.d_start, O.d_list, O.d_decode,
-                           t->ctx->d_thresh, O.d_mask, t->d_rgba);
+        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, O.d_decode,
+                           t->ctx->d_thresh, O.mask.p, t->d_rgba);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
 }
@@ -1634,8 +1646,7 @@ static int render_visibility(vf_terrain *t)
 int vf_terrain_sync(vf_terrain *t)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    VF_HIP_TRY(wait_frame(t));
     return VF_OK;
 }
 
@@ -1643,14 +1654,33 @@ int vf_terrain_sync(vf_terrain *t)
 
 static float ov_clamp_px(float v) { return std::fmin(std::fmax(v, 1.0f), 64.0f); }
 
-// append primitives (feature order) to the handle's overlay array; the first call makes the overlay state
-static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *layer_id, bool polygon = false)
+static uint32_t ov_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
+
+static int ov_usable(const vf_terrain *t)
+{
+    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "overlays need a whole-frame handle: sharded compositing is not supported");
+    return VF_OK;
+}
+
+// the primitive budget of a handle (all layers): `more` records on top of `have` (checked as records are built, and by ov_append)
+static int ov_budget(uint64_t have, uint64_t more)
+{
+    if (have + more > kOvMaxPrims)
+        return fail(VF_ERR_INVALID, "overlays: more than 2^24 primitives on one handle (a point is one, a polyline of m vertices up to 2m, "
+                                    "a polygon fill 1 + 2 per ring edge)");
+    return VF_OK;
+}
+
+// One layer, appended as a whole: its records `add` (feature order), for a polygon layer with fills the header record index of each
+// fill feature (`hdr`) and the number of fill records at the start of `add`, and the handle's feature count after the layer.  The first
+// layer makes the overlay state.  Nothing is committed before every allocation and upload has succeeded: a failure leaves the layers as
+// they were.
+static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, const std::vector<uint32_t> &hdr, uint32_t nfillrec, bool polygon,
+                     uint32_t features, uint32_t *layer_id)
 {
     vf_terrain::Overlays &O = t->ov;
-    if ((uint64_t)O.nprims + add.size() > kOvMaxPrims)
-        return fail(VF_ERR_INVALID, "overlays: more than 2^24 primitives on one handle (a point is one, a polyline of m vertices up to 2m)");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));   // (a frame in flight reads the arrays)
+    if (int rc = ov_budget(O.nprims, add.size())) return rc;
+    VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the arrays)
     if (!O.d_cnt) {
         const uint32_t nbins = ((t->W + kOvBin - 1u) / kOvBin) * ((t->H + kOvBin - 1u) / kOvBin);
         hipError_t e = hipMalloc(&O.d_cnt, (size_t)nbins * sizeof(uint32_t));
@@ -1662,45 +1692,36 @@ static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, uint32_t *laye
         if (e == hipSuccess) e = hipEventCreateWithFlags(&O.counted, hipEventDisableTiming);
         if (e != hipSuccess) { ov_release(t); return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e)); }
     }
-    const uint32_t need = O.nprims + (uint32_t)add.size();
-    if (need > O.cap) {
-        const uint32_t cap = std::min<uint32_t>(kOvMaxPrims, std::max<uint32_t>({ need, 2u * O.cap, 1024u }));
-        OvIn *in = nullptr; OvPrim *pr = nullptr; uint2 *bx = nullptr;
-        hipError_t e = hipMalloc(&in, (size_t)cap * sizeof(OvIn));
-        if (e == hipSuccess) e = hipMalloc(&pr, (size_t)cap * sizeof(OvPrim));
-        if (e == hipSuccess) e = hipMalloc(&bx, (size_t)cap * sizeof(uint2));
-        if (e == hipSuccess && O.nprims) e = hipMemcpy(in, O.d_in, (size_t)O.nprims * sizeof(OvIn), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            for (void *p : { (void *)in, (void *)pr, (void *)bx }) if (p) (void)hipFree(p);
-            return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
-        }
-        if (O.d_dep) {                                        // (per-frame values: made again by the next k_ov_setup)
-            float4 *dp = nullptr;
-            e = hipMalloc(&dp, (size_t)cap * sizeof(float4));
-            if (e == hipSuccess) e = hipMemset(dp, 0, (size_t)cap * sizeof(float4));
-            if (e != hipSuccess) {
-                for (void *p : { (void *)in, (void *)pr, (void *)bx, (void *)dp }) if (p) (void)hipFree(p);
-                return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
-            }
-            (void)hipFree(O.d_dep);
-            O.d_dep = dp;
-        }
-        for (void *p : { (void *)O.d_in, (void *)O.d_prim, (void *)O.d_box }) if (p) (void)hipFree(p);
-        O.d_in = in; O.d_prim = pr; O.d_box = bx; O.cap = cap;
+    // Growth: each array of a group to the group's new capacity.  When a group only partly grows, the arrays that did are larger than
+    // they need to be; no counter has moved, so that is harmless.  dep (per-frame values, made again by the next k_ov_setup) is made
+    // when a layer is first set to occlude -- by this growth instead if the handle had no room for records then -- and grows with the
+    // primitives from then on.
+    const uint32_t need = O.nprims + (uint32_t)add.size(), nfill = O.nfill + (uint32_t)hdr.size();
+    const size_t cap = std::min<size_t>(kOvMaxPrims, std::max<size_t>({ need, 2u * O.in.cap, 1024u }));
+    hipError_t e = O.in.reserve(need, cap, O.nprims);
+    if (e == hipSuccess) e = O.prim.reserve(need, cap);
+    if (e == hipSuccess) e = O.box.reserve(need, cap);
+    if (e == hipSuccess && (O.dep.p || O.occluding)) e = O.dep.reserve(need, cap, 0, true);
+    if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
+    if (!hdr.empty()) {
+        const size_t fill_cap = std::max<size_t>({ nfill, 2u * O.pg_hdr.cap, 256u });
+        e = O.pg_total.reserve(1, 1, 0, true);
+        if (e == hipSuccess) e = O.pg_hdr.reserve(nfill, fill_cap, O.nfill);
+        if (e == hipSuccess) e = O.pg_fbox.reserve(nfill, fill_cap, 0, true);
+        if (e == hipSuccess) e = O.pg_fbin.reserve(nfill, fill_cap);
+        if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("polygon overlay allocation failed: ") + hipGetErrorString(e));
+        VF_HIP_TRY(hipMemcpy(O.pg_hdr.p + O.nfill, hdr.data(), hdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    if (!add.empty()) VF_HIP_TRY(hipMemcpy(O.d_in + O.nprims, add.data(), add.size() * sizeof(OvIn), hipMemcpyHostToDevice));
+    if (!add.empty()) VF_HIP_TRY(hipMemcpy(O.in.p + O.nprims, add.data(), add.size() * sizeof(OvIn), hipMemcpyHostToDevice));
+    if (!hdr.empty()) {
+        if (!O.nfill) O.pg_lo = O.nprims;
+        O.pg_hi = O.nprims + nfillrec;
+        O.nfill = nfill;
+    }
+    if (layer_id) *layer_id = (uint32_t)O.layer.size();
     O.layer.push_back({ O.nprims, need, polygon, false });
     O.nprims = need;
-    if (layer_id) *layer_id = O.layers;
-    O.layers++;
-    return VF_OK;
-}
-
-static uint32_t ov_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
-
-static int ov_usable(const vf_terrain *t)
-{
-    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "overlays need a whole-frame handle: sharded compositing is not supported");
+    O.features = features;
     return VF_OK;
 }
 
@@ -1727,27 +1748,27 @@ int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const flo
         q.feature = feature++;
         add.push_back(q);
     }
-    const int rc = ov_append(t, add, layer_id);
-    if (rc == VF_OK) t->ov.features = feature;
-    return rc;
+    return ov_append(t, add, {}, 0, false, feature, layer_id);
 }
 
-// the primitives of one polyline (its vertices in path order): butt segments, discs at interior vertices (round joins) and, for round
-// caps, at both ends; square caps extend the path's first / last segment
-static void ov_path(const std::vector<const float *> &path, float hw, uint32_t rgba, int cap, uint32_t base, uint32_t feature, std::vector<OvIn> &add)
+// the primitives of one polyline (vertices v0 .. v1 - 1 of xyz; a closed ring ends at its first vertex again): butt segments, discs at
+// interior vertices (round joins) and, for round caps, at both ends; square caps extend the path's first / last segment
+static void ov_path(const float *xyz, uint32_t v0, uint32_t v1, bool closed, float hw, uint32_t rgba, int cap, uint32_t base, uint32_t feature,
+                    std::vector<OvIn> &add)
 {
-    const size_t m = path.size();
-    for (size_t v = 0; v < m; ++v) {
+    const uint32_t n = v1 - v0, m = n + (closed ? 1u : 0u);
+    auto at = [&](uint32_t v) { return xyz + 3u * (v0 + (v < n ? v : 0u)); };
+    for (uint32_t v = 0; v < m; ++v) {
         const bool end = v == 0 || v + 1u == m;
         if (!end || cap == VF_CAP_ROUND) {                    // disc: round join / round cap
             OvIn q{};
-            for (int c = 0; c < 3; ++c) { q.p0[c] = path[v][c]; q.p1[c] = q.p0[c]; }
+            for (int c = 0; c < 3; ++c) { q.p0[c] = at(v)[c]; q.p1[c] = q.p0[c]; }
             q.size = hw; q.flags = kOvCircle | base; q.rgba = rgba; q.feature = feature;
             add.push_back(q);
         }
         if (v + 1u < m) {                                     // butt segment v -> v + 1 (square caps extend the path's first / last one)
             OvIn q{};
-            for (int c = 0; c < 3; ++c) { q.p0[c] = path[v][c]; q.p1[c] = path[v + 1u][c]; }
+            for (int c = 0; c < 3; ++c) { q.p0[c] = at(v)[c]; q.p1[c] = at(v + 1u)[c]; }
             q.size = hw; q.rgba = rgba; q.feature = feature;
             q.flags = kOvSegment | base | (cap == VF_CAP_SQUARE && v == 0 ? kOvExt0 : 0u) | (cap == VF_CAP_SQUARE && v + 2u == m ? kOvExt1 : 0u);
             add.push_back(q);
@@ -1773,45 +1794,10 @@ int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_o
         for (uint32_t v = v0; v < v1; ++v)
             for (int c = 0; c < 3; ++c)
                 if (!std::isfinite(xyz[3u * v + c])) return fail(VF_ERR_INVALID, "a line vertex is not finite");
-        if ((uint64_t)add.size() + 2ull * (v1 - v0) > kOvMaxPrims)
-            return fail(VF_ERR_INVALID, "overlays: more than 2^24 primitives on one handle (a point is one, a polyline of m vertices up to 2m)");
-        std::vector<const float *> path;
-        for (uint32_t v = v0; v < v1; ++v) path.push_back(xyz + 3u * v);
-        ov_path(path, hw, ov_rgba(rgba), cap, base, feature, add);
-        feature++;
+        if (int rc = ov_budget(t->ov.nprims + add.size(), 2ull * (v1 - v0))) return rc;
+        ov_path(xyz, v0, v1, false, hw, ov_rgba(rgba), cap, base, feature++, add);
     }
-    const int rc = ov_append(t, add, layer_id);
-    if (rc == VF_OK) t->ov.features = feature;
-    return rc;
-}
-
-// room for `more` fill features in the per-feature arrays of the polygon pass (the caller has synchronised)
-static int pg_reserve(vf_terrain *t, uint32_t more)
-{
-    vf_terrain::Overlays &O = t->ov;
-    const uint32_t need = O.nfill + more;
-    hipError_t e = hipSuccess;
-    if (!O.d_pg_total) {
-        e = hipMalloc(&O.d_pg_total, sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMemset(O.d_pg_total, 0, sizeof(unsigned long long));
-    }
-    if (e == hipSuccess && need > O.fill_cap) {
-        const uint32_t cap = std::max<uint32_t>({ need, 2u * O.fill_cap, 256u });
-        uint32_t *hdr = nullptr; uint4 *fbox = nullptr, *fbin = nullptr;
-        e = hipMalloc(&hdr, (size_t)cap * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&fbox, (size_t)cap * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc(&fbin, (size_t)cap * sizeof(uint4));
-        if (e == hipSuccess) e = hipMemset(fbox, 0, (size_t)cap * sizeof(uint4));
-        if (e == hipSuccess && O.nfill) e = hipMemcpy(hdr, O.hdr.data(), (size_t)O.nfill * sizeof(uint32_t), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            for (void *p : { (void *)hdr, (void *)fbox, (void *)fbin }) if (p) (void)hipFree(p);
-        } else {
-            for (void *p : { (void *)O.d_pg_hdr, (void *)O.d_pg_fbox, (void *)O.d_pg_fbin }) if (p) (void)hipFree(p);
-            O.d_pg_hdr = hdr; O.d_pg_fbox = fbox; O.d_pg_fbin = fbin; O.fill_cap = cap;
-        }
-    }
-    if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("polygon overlay allocation failed: ") + hipGetErrorString(e));
-    return VF_OK;
+    return ov_append(t, add, {}, 0, false, feature, layer_id);
 }
 
 int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *ring_offsets, uint32_t nrings, const uint32_t *feature_offsets,
@@ -1835,8 +1821,7 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
                     if (!std::isfinite(xyz[3u * v + c])) return fail(VF_ERR_INVALID, "a polygon vertex is not finite");
         }
     }
-    const char *too_many = "overlays: more than 2^24 primitives on one handle (a polygon fill is 1 + 2 per ring edge, its outline up to 2 per ring vertex + 1)";
-    vf_terrain::Overlays &O = t->ov;
+    const vf_terrain::Overlays &O = t->ov;
     std::vector<OvIn> add;
     std::vector<uint32_t> hdr;
     uint32_t feature = O.features;
@@ -1848,7 +1833,7 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
             std::memcpy(&kbits, &k, sizeof kbits);
             uint64_t n = 1;
             for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) n += 2ull * (ring_offsets[r + 1] - ring_offsets[r]);
-            if ((uint64_t)O.nprims + add.size() + n > kOvMaxPrims) return fail(VF_ERR_INVALID, too_many);
+            if (int rc = ov_budget(O.nprims + add.size(), n)) return rc;
             hdr.push_back(O.nprims + (uint32_t)add.size());
             OvIn h{};
             h.size = kbits; h.flags = kOvPoly | kPgHeader; h.rgba = ov_rgba(fill_rgba ? fill_rgba + 4u * f : default_fill); h.feature = feature;
@@ -1872,56 +1857,32 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
         for (uint32_t f = 0; f < nfeatures; ++f)
             for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) {
                 const uint32_t v0 = ring_offsets[r], v1 = ring_offsets[r + 1];
-                if ((uint64_t)O.nprims + add.size() + 2ull * (v1 - v0) + 1u > kOvMaxPrims) return fail(VF_ERR_INVALID, too_many);
-                std::vector<const float *> path;
-                for (uint32_t v = v0; v < v1; ++v) path.push_back(xyz + 3u * v);
-                path.push_back(xyz + 3u * v0);
-                ov_path(path, hw, ov_rgba(line_rgba), VF_CAP_ROUND, base, feature, add);
-                feature++;
+                if (int rc = ov_budget(O.nprims + add.size(), 2ull * (v1 - v0) + 1u)) return rc;
+                ov_path(xyz, v0, v1, true, hw, ov_rgba(line_rgba), VF_CAP_ROUND, base, feature++, add);
             }
     }
-    if (!hdr.empty()) {                                       // (before ov_append: a failure here leaves the handle as it was)
-        VF_HIP_TRY(hipSetDevice(t->ctx->device));
-        VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
-        if (int rc = pg_reserve(t, (uint32_t)hdr.size())) return rc;
-        VF_HIP_TRY(hipMemcpy(O.d_pg_hdr + O.nfill, hdr.data(), hdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    const uint32_t at = O.nprims;
-    const int rc = ov_append(t, add, layer_id, true);
-    if (rc != VF_OK) return rc;
-    O.features = feature;
-    if (!hdr.empty()) {
-        O.hdr.insert(O.hdr.end(), hdr.begin(), hdr.end());
-        if (!O.nfill) O.pg_lo = at;
-        O.pg_hi = at + nfillrec;
-        O.nfill += (uint32_t)hdr.size();
-    }
-    return VF_OK;
+    return ov_append(t, add, hdr, nfillrec, true, feature, layer_id);
 }
 
 int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude, float depth_bias)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "occlusion needs a whole-frame handle: sharded handles have no overlays");
+    if (int rc = ov_usable(t)) return rc;
     if (!std::isfinite(depth_bias) || depth_bias < 0.0f) return fail(VF_ERR_INVALID, "depth_bias must be a finite number >= 0");
     vf_terrain::Overlays &O = t->ov;
     if (layer_id >= O.layer.size()) return fail(VF_ERR_INVALID, "no overlay layer with that id");
     vf_terrain::Overlays::Layer &L = O.layer[layer_id];
     if (L.polygon) return fail(VF_ERR_INVALID, "a polygon layer cannot occlude: polygon fills have no depth");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));   // (a frame in flight reads the records)
+    VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the records)
     if (occlude) {
         if (!t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
-        if (!O.d_dep) {
-            VF_HIP_TRY(hipMalloc(&O.d_dep, (size_t)O.cap * sizeof(float4)));
-            VF_HIP_TRY(hipMemset(O.d_dep, 0, (size_t)O.cap * sizeof(float4)));
-        }
+        VF_HIP_TRY(O.dep.reserve(O.in.cap, O.in.cap, 0, true));
     }
     const float kb = 1.0f + depth_bias;                       // the layer's depth factor, rounded once (binary32)
     uint32_t kb_bits;
     std::memcpy(&kb_bits, &kb, sizeof kb_bits);
     if (L.hi > L.lo) {
-        hipLaunchKernelGGL(k_ov_occlude, dim3((L.hi - L.lo + 255u) / 256u), dim3(256), 0, t->ctx->stream, L.lo, L.hi, O.d_in,
+        hipLaunchKernelGGL(k_ov_occlude, dim3((L.hi - L.lo + 255u) / 256u), dim3(256), 0, t->ctx->stream, L.lo, L.hi, O.in.p,
                            occlude ? 1u : 0u, kb_bits);
         VF_HIP_TRY(hipGetLastError());
         VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
@@ -1934,8 +1895,7 @@ int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude
 int vf_terrain_clear_overlays(vf_terrain *t)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(hipStreamSynchronize(t->last_stream ? t->last_stream : t->ctx->stream));
+    VF_HIP_TRY(wait_frame(t));
     ov_release(t);
     return VF_OK;
 }
