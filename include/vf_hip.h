@@ -263,6 +263,30 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
  * sharded handle. */
 #define VF_OCCLUSION_DEPTH_BIAS 1e-2f
 int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude, float depth_bias);
+/* Contour lines (new; isolines of the rendered surface, DESIGN.md 4e has the contract bit for bit).  The lines are extracted on the
+ * device from the surface the handle draws -- the displaced height h of every grid vertex on the renderer's own triangulation, not the
+ * uploaded texture -- and appended as one layer of draped line records, which every later frame draws like a line layer's.
+ *   levels[nlevels]: finite, strictly ascending, 1 <= nlevels <= 65536, in units of h before exaggeration (what the colormap sees; world
+ *     y = h * exaggeration).  width_px clamped to [1, 64]; one colour; lift: world-space offset above the surface (finite).
+ *   join VF_JOIN_ROUND: a disc at the start of every segment (2 primitives per segment; every joint of a chain is closed);
+ *     VF_JOIN_NONE: segments only (1 primitive per segment; for dense layers).
+ *   occlude / depth_bias: as vf_terrain_add_lines followed by vf_terrain_set_layer_occlusion, which also works on the layer afterwards.
+ *   The layer is one feature: its coverage is folded with max over the whole layer, so a translucent contour does not darken at
+ *     joints or where two contours touch.
+ *   Snapshot: the layer is made from the heights and the grid spacing the handle holds when the call is made (a height texture handed
+ *     over in device memory must be complete by then).  It follows a later change of exaggeration (draped records); it does not follow
+ *     a later height upload: vf_terrain_clear_overlays and add again.
+ *   *nsegments (may be NULL): the number of segments found.  Zero segments is not an error: an empty layer with its id.
+ *   VF_ERR_INVALID, nothing added: bad levels / width / lift / join / depth_bias, a sharded handle, and a layer that would exceed the
+ *     handle's 2^24 primitives (the message names the number of segments found).
+ * vf_terrain_height_bounds: min / max of h over the grid's vertices, non-finite heights left out (lo = inf, hi = -inf when there is
+ *   none).  vf_terrain_layer_primitive_count: the primitive records of a layer (any kind).  Both wait for the frame in flight. */
+#define VF_JOIN_ROUND 0
+#define VF_JOIN_NONE 1
+int vf_terrain_add_contours(vf_terrain *t, const float *levels, uint32_t nlevels, float width_px, const uint8_t rgba[4], float lift, int join,
+                            int occlude, float depth_bias, uint32_t *layer_id, uint32_t *nsegments);
+int vf_terrain_height_bounds(vf_terrain *t, float *lo, float *hi);
+int vf_terrain_layer_primitive_count(vf_terrain *t, uint32_t layer_id, uint32_t *count);
 
 /* copy_texture_to_buffer + map + un-pad (src/terrain/mod.rs:439-485): local rows [y0, y0+rows)
  * into dst (rows*W*4 bytes).  Waits for the last render and for the copy (work the library queues behind the copy for the

@@ -1,5 +1,5 @@
-"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines / .add_polygons / .set_layer_occlusion), pack_lines
-and pack_polygons.
+"""Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines / .add_polygons / .add_contours /
+.set_layer_occlusion), pack_lines and pack_polygons.
 
 The extension calls these before it hands the arrays to the C-ABI (include/vf_hip.h, overlays); they need numpy only, no device.
 """
@@ -11,6 +11,8 @@ import numpy as np
 
 SHAPES = {"circle": 0, "square": 1}
 CAPS = {"butt": 0, "square": 1, "round": 2}
+JOINS = {"round": 0, "none": 1}
+MAX_CONTOUR_LEVELS = 65536                                    # include/vf_hip.h, vf_terrain_add_contours
 
 
 def _float_array(obj, what):
@@ -178,3 +180,64 @@ def polygon_args(polygons, fill_rgba, line_rgba, line_width_px):
     if line_rgba is not None:
         line, _ = _colour(line_rgba, 0, False)
     return coords, rings, feats, dfill, fills, line, width
+
+
+def contour_args(levels, interval, base, width_px, rgba, lift, join, bounds=None):
+    """-> (levels (K,) f32 ascending, width, rgba (4,) u8, lift, join code) for add_contours.
+
+    Exactly one of `levels` (a 1-D float array, finite, strictly ascending, 1 .. 65536 values) and `interval` (> 0).  With `interval`
+    the levels are float32(base + k * interval) for every integer k whose level lies within `bounds` = (lo, hi), the handle's
+    height_bounds(): formed in float64 and rounded once."""
+    if (levels is None) == (interval is None):
+        raise ValueError("add_contours needs exactly one of levels and interval")
+    if join not in JOINS:
+        raise ValueError(f"join must be one of {sorted(JOINS)}, got {join!r}")
+    if isinstance(width_px, bool) or not isinstance(width_px, numbers.Real):
+        raise TypeError(f"width_px must be a number, got {type(width_px).__name__}")
+    width, _ = _size(width_px, 0, "width_px")
+    col, _ = _colour(rgba, 0, False)
+    if isinstance(lift, bool) or not isinstance(lift, numbers.Real):
+        raise TypeError(f"lift must be a number, got {type(lift).__name__}")
+    lift = float(lift)
+    if not np.isfinite(lift) or abs(lift) > float(np.finfo(np.float32).max):
+        raise ValueError(f"lift must be a finite number, got {lift}")
+    if levels is not None:
+        lv = _float_array(levels, "levels")
+        if lv.ndim != 1:
+            raise ValueError(f"levels must be a 1-D array, got shape {lv.shape}")
+        if not 1 <= lv.size <= MAX_CONTOUR_LEVELS:
+            raise ValueError(f"levels must hold 1 .. {MAX_CONTOUR_LEVELS} values, got {lv.size}")
+        if not np.isfinite(lv).all():
+            raise ValueError("levels must be finite")
+        with np.errstate(over="ignore"):
+            lv = np.ascontiguousarray(lv, dtype=np.float32)
+        if not np.isfinite(lv).all():
+            raise ValueError("levels must be finite as float32")
+        if not (lv[1:] > lv[:-1]).all():
+            raise ValueError("levels must be strictly ascending (as float32)")
+        return lv, width, col, lift, JOINS[join]
+    for name, v in (("interval", interval), ("base", base)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real):
+            raise TypeError(f"{name} must be a number, got {type(v).__name__}")
+    interval, base = float(interval), float(base)
+    if not np.isfinite(interval) or interval <= 0.0:
+        raise ValueError(f"interval must be a positive finite number, got {interval}")
+    if not np.isfinite(base):
+        raise ValueError(f"base must be a finite number, got {base}")
+    if bounds is None:
+        raise ValueError("interval needs the height bounds of the surface")
+    lo, hi = float(bounds[0]), float(bounds[1])
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+        raise ValueError("the surface has no finite height: no contour levels")
+    k0, k1 = np.ceil((lo - base) / interval) - 1.0, np.floor((hi - base) / interval) + 1.0
+    if k1 - k0 + 1.0 > MAX_CONTOUR_LEVELS + 2:
+        raise ValueError(f"interval {interval} gives more than {MAX_CONTOUR_LEVELS} levels over the height bounds [{lo}, {hi}]")
+    lv = (base + np.arange(int(k0), int(k1) + 1, dtype=np.float64) * interval).astype(np.float32)
+    lv = lv[(lv >= np.float32(lo)) & (lv <= np.float32(hi))]
+    if lv.size > MAX_CONTOUR_LEVELS:
+        raise ValueError(f"interval {interval} gives more than {MAX_CONTOUR_LEVELS} levels over the height bounds [{lo}, {hi}]")
+    if lv.size == 0:
+        raise ValueError(f"no level base + k * interval lies within the height bounds [{lo}, {hi}]")
+    if not (lv[1:] > lv[:-1]).all():
+        raise ValueError(f"interval {interval} is too small: consecutive levels round to the same float32")
+    return np.ascontiguousarray(lv), width, col, lift, JOINS[join]

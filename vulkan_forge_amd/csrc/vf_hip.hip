@@ -2,7 +2,7 @@
 // Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -shared -fPIC + the -mllvm code-generation switches of HIPCC_TUNING
 #include "../../include/vf_hip.h"
 #include "vf_kernels.h"
-#include "vf_overlay.h"
+#include "vf_overlay.h"     // (brings vf_contour.h)
 
 #include <algorithm>
 #include <cmath>
@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <functional>
 #include <new>
 #include <string>
 #include <atomic>
@@ -399,6 +400,14 @@ struct vf_terrain {
         uint32_t occluding = 0;              // layers with occlusion on: the frame stores its visibility and composites with depth
         DevBuf<float4> dep;                  // [nprims] per primitive (rw_a, rw_b - rw_a, kb, 0) of occluding primitives (k_ov_setup)
     } ov;
+    // Contour extraction (vf_terrain_add_contours / vf_terrain_height_bounds, vf_contour.h): made by the first such call, freed with the
+    // overlays -- a handle that never asks for contours holds none of it and launches nothing for them.
+    struct Contours {
+        DevBuf<float> levels;                // the call's level list
+        DevBuf<uint32_t> count;              // [nblocks] segments per block, then their exclusive offsets
+        DevBuf<unsigned long long> total;    // [1] segments in all
+        DevBuf<float2> bounds;               // [1] vf_terrain_height_bounds
+    } ct;
 };
 
 extern "C" {
@@ -624,6 +633,7 @@ static void ov_release(vf_terrain *t)
     if (O.h_total) (void)hipHostFree(O.h_total);
     if (O.counted) (void)hipEventDestroy(O.counted);
     O = vf_terrain::Overlays();
+    t->ct.levels.release(); t->ct.count.release(); t->ct.total.release(); t->ct.bounds.release();
 }
 
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
@@ -1671,16 +1681,20 @@ static int ov_budget(uint64_t have, uint64_t more)
     return VF_OK;
 }
 
-// One layer, appended as a whole: its records `add` (feature order), for a polygon layer with fills the header record index of each
-// fill feature (`hdr`) and the number of fill records at the start of `add`, and the handle's feature count after the layer.  The first
-// layer makes the overlay state.  Nothing is committed before every allocation and upload has succeeded: a failure leaves the layers as
-// they were.
-static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, const std::vector<uint32_t> &hdr, uint32_t nfillrec, bool polygon,
-                     uint32_t features, uint32_t *layer_id)
+// One layer, appended as a whole: its `nadd` records (feature order), which `produce` writes to the device array it is handed (the
+// layer's first record) -- an upload of records built on the host, or a kernel that makes them where they are; for a polygon layer with
+// fills the header record index of each fill feature (`hdr`) and the number of fill records at the start of the layer; the handle's
+// feature count after the layer; `occlude`: the layer's records are made with kOvOcclude set (vf_terrain_set_layer_occlusion's state
+// is brought about here).  The first layer makes the overlay state.  Nothing is committed before every allocation and the producer
+// have succeeded: a failure leaves the layers as they were.
+using OvProducer = std::function<int(OvIn *dst)>;
+static int ov_append(vf_terrain *t, size_t nadd, const OvProducer &produce, const std::vector<uint32_t> &hdr, uint32_t nfillrec, bool polygon,
+                     uint32_t features, uint32_t *layer_id, bool occlude = false)
 {
     vf_terrain::Overlays &O = t->ov;
-    if (int rc = ov_budget(O.nprims, add.size())) return rc;
+    if (int rc = ov_budget(O.nprims, nadd)) return rc;
     VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the arrays)
+    if (occlude && !t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
     if (!O.d_cnt) {
         const uint32_t nbins = ((t->W + kOvBin - 1u) / kOvBin) * ((t->H + kOvBin - 1u) / kOvBin);
         hipError_t e = hipMalloc(&O.d_cnt, (size_t)nbins * sizeof(uint32_t));
@@ -1696,12 +1710,12 @@ static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, const std::vec
     // they need to be; no counter has moved, so that is harmless.  dep (per-frame values, made again by the next k_ov_setup) is made
     // when a layer is first set to occlude -- by this growth instead if the handle had no room for records then -- and grows with the
     // primitives from then on.
-    const uint32_t need = O.nprims + (uint32_t)add.size(), nfill = O.nfill + (uint32_t)hdr.size();
+    const uint32_t need = O.nprims + (uint32_t)nadd, nfill = O.nfill + (uint32_t)hdr.size();
     const size_t cap = std::min<size_t>(kOvMaxPrims, std::max<size_t>({ need, 2u * O.in.cap, 1024u }));
     hipError_t e = O.in.reserve(need, cap, O.nprims);
     if (e == hipSuccess) e = O.prim.reserve(need, cap);
     if (e == hipSuccess) e = O.box.reserve(need, cap);
-    if (e == hipSuccess && (O.dep.p || O.occluding)) e = O.dep.reserve(need, cap, 0, true);
+    if (e == hipSuccess && (O.dep.p || O.occluding || occlude)) e = O.dep.reserve(need, cap, 0, true);
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
     if (!hdr.empty()) {
         const size_t fill_cap = std::max<size_t>({ nfill, 2u * O.pg_hdr.cap, 256u });
@@ -1712,17 +1726,29 @@ static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, const std::vec
         if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("polygon overlay allocation failed: ") + hipGetErrorString(e));
         VF_HIP_TRY(hipMemcpy(O.pg_hdr.p + O.nfill, hdr.data(), hdr.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
-    if (!add.empty()) VF_HIP_TRY(hipMemcpy(O.in.p + O.nprims, add.data(), add.size() * sizeof(OvIn), hipMemcpyHostToDevice));
+    if (nadd)
+        if (int rc = produce(O.in.p + O.nprims)) return rc;
     if (!hdr.empty()) {
         if (!O.nfill) O.pg_lo = O.nprims;
         O.pg_hi = O.nprims + nfillrec;
         O.nfill = nfill;
     }
     if (layer_id) *layer_id = (uint32_t)O.layer.size();
-    O.layer.push_back({ O.nprims, need, polygon, false });
+    O.layer.push_back({ O.nprims, need, polygon, occlude });
+    if (occlude) O.occluding++;
     O.nprims = need;
     O.features = features;
     return VF_OK;
+}
+
+// ... of records built on the host
+static int ov_append(vf_terrain *t, const std::vector<OvIn> &add, const std::vector<uint32_t> &hdr, uint32_t nfillrec, bool polygon,
+                     uint32_t features, uint32_t *layer_id)
+{
+    return ov_append(t, add.size(), [&](OvIn *dst) -> int {
+        VF_HIP_TRY(hipMemcpy(dst, add.data(), add.size() * sizeof(OvIn), hipMemcpyHostToDevice));
+        return VF_OK;
+    }, hdr, nfillrec, polygon, features, layer_id);
 }
 
 int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const float *size_px, const uint8_t *rgba, float default_size,
@@ -1890,6 +1916,93 @@ int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude
     if (L.occlude != (occlude != 0)) O.occluding += occlude ? 1u : (uint32_t)-1;
     L.occlude = occlude != 0;
     return VF_OK;
+}
+
+// ---- contour lines (vf_contour.h) ----------------------------------------------------
+
+// the displaced-height cache and the per-block bounds hold the handle's current heights (no frame in flight afterwards)
+static int ct_heights_current(vf_terrain *t)
+{
+    VF_HIP_TRY(wait_frame(t));
+    VF_HIP_TRY(sync_sides(t));
+    if (t->bounds_dirty) {
+        hipLaunchKernelGGL(k_height_blocks, dim3(t->nblocks), dim3(64), 0, t->ctx->stream, t->n, t->nb, t->tw, axis(t), t->d_height, t->d_hblk, t->d_bounds);
+        VF_HIP_TRY(hipGetLastError());
+        t->bounds_dirty = false;
+    }
+    return VF_OK;
+}
+
+int vf_terrain_height_bounds(vf_terrain *t, float *lo, float *hi)
+{
+    if (!t || !lo || !hi) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = ct_heights_current(t)) return rc;
+    if (t->ct.bounds.reserve(1, 1) != hipSuccess) return fail(VF_ERR_NOMEM, "height bounds allocation failed");
+    hipLaunchKernelGGL(k_ct_bounds, dim3(1), dim3(1024), 0, t->ctx->stream, t->n, t->nb, t->d_bounds, t->d_hblk, t->ct.bounds.p);
+    VF_HIP_TRY(hipGetLastError());
+    float2 b;
+    VF_HIP_TRY(hipMemcpyAsync(&b, t->ct.bounds.p, sizeof b, hipMemcpyDeviceToHost, t->ctx->stream));
+    VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    *lo = b.x; *hi = b.y;
+    return VF_OK;
+}
+
+int vf_terrain_layer_primitive_count(vf_terrain *t, uint32_t layer_id, uint32_t *count)
+{
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    if (layer_id >= t->ov.layer.size()) return fail(VF_ERR_INVALID, "no overlay layer with that id");
+    *count = t->ov.layer[layer_id].hi - t->ov.layer[layer_id].lo;
+    return VF_OK;
+}
+
+int vf_terrain_add_contours(vf_terrain *t, const float *levels, uint32_t nlevels, float width_px, const uint8_t rgba[4], float lift, int join,
+                            int occlude, float depth_bias, uint32_t *layer_id, uint32_t *nsegments)
+{
+    if (!t || !levels || !rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    if (join != VF_JOIN_ROUND && join != VF_JOIN_NONE) return fail(VF_ERR_INVALID, "join must be VF_JOIN_ROUND or VF_JOIN_NONE");
+    if (!std::isfinite(width_px)) return fail(VF_ERR_INVALID, "width_px must be finite");
+    if (!std::isfinite(lift)) return fail(VF_ERR_INVALID, "lift must be finite");
+    if (occlude && (!std::isfinite(depth_bias) || depth_bias < 0.0f)) return fail(VF_ERR_INVALID, "depth_bias must be a finite number >= 0");
+    if (nlevels < 1u || nlevels > kCtMaxLevels) return fail(VF_ERR_INVALID, "a contour layer needs 1 .. 65536 levels");
+    for (uint32_t k = 0; k < nlevels; ++k)
+        if (!std::isfinite(levels[k]) || (k && !(levels[k] > levels[k - 1])))
+            return fail(VF_ERR_INVALID, "contour levels must be finite and strictly ascending");
+    if (int rc = ov_usable(t)) return rc;
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");     // (the grid spacing)
+    if (int rc = ct_heights_current(t)) return rc;
+    vf_terrain::Contours &C = t->ct;
+    hipStream_t s = t->ctx->stream;
+    hipError_t e = C.levels.reserve(nlevels, nlevels);
+    if (e == hipSuccess) e = C.count.reserve(t->nblocks, t->nblocks);
+    if (e == hipSuccess) e = C.total.reserve(1, 1);
+    if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("contour allocation failed: ") + hipGetErrorString(e));
+    VF_HIP_TRY(hipMemcpyAsync(C.levels.p, levels, nlevels * sizeof(float), hipMemcpyHostToDevice, s));
+    const CtGrid G = { t->n - 1u, t->nb, (2.0f * 1.5f) / ((float)t->n - 1.0f), std::fmax(t->u[36], 1e-8f), t->d_hblk, t->d_bounds, C.levels.p, nlevels };
+    hipLaunchKernelGGL(k_ct_count, dim3(t->nblocks), dim3(64), 0, s, G, C.count.p);
+    VF_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ct_scan, dim3(1), dim3(1024), 0, s, t->nblocks, C.count.p, C.total.p);
+    VF_HIP_TRY(hipGetLastError());
+    unsigned long long nseg = 0;
+    VF_HIP_TRY(hipMemcpyAsync(&nseg, C.total.p, sizeof nseg, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));                      // (the level list is only borrowed; the count sizes the layer)
+    const bool round = join == VF_JOIN_ROUND;
+    const unsigned long long nrec = nseg * (round ? 2ull : 1ull);
+    if (t->ov.nprims + nrec > kOvMaxPrims)
+        return fail(VF_ERR_INVALID, "contours: " + std::to_string(nseg) + " segments (" + std::to_string(nrec) + " primitives) on top of the handle's " +
+                                    std::to_string(t->ov.nprims) + " exceed the 2^24 primitive budget: fewer levels, VF_JOIN_NONE or a coarser grid");
+    const float kb = 1.0f + depth_bias;                       // as vf_terrain_set_layer_occlusion forms it
+    CtStyle S = {};
+    S.hw = ov_clamp_px(width_px) * 0.5f; S.lift = lift; S.rgba = ov_rgba(rgba); S.feature = t->ov.features;
+    S.base = kOvDrape | (occlude ? kOvOcclude : 0u); S.round = round ? 1u : 0u;
+    if (occlude) std::memcpy(&S.kb_bits, &kb, sizeof kb);
+    const int rc = ov_append(t, (size_t)nrec, [&](OvIn *dst) -> int {
+        hipLaunchKernelGGL(k_ct_emit, dim3(t->nblocks), dim3(64), 0, s, G, S, C.count.p, dst);
+        VF_HIP_TRY(hipGetLastError());
+        VF_HIP_TRY(hipStreamSynchronize(s));
+        return VF_OK;
+    }, {}, 0, false, t->ov.features + 1u, layer_id, occlude != 0);
+    if (rc == VF_OK && nsegments) *nsegments = (uint32_t)nseg;
+    return rc;
 }
 
 int vf_terrain_clear_overlays(vf_terrain *t)

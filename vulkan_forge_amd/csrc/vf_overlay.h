@@ -629,6 +629,10 @@ __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nb
     if (tid == 0) cnt[bin] = 0u;                         // (the next frame's k_ov_setup counts from zero)
 }
 
+} // namespace vf
+#include "vf_contour.h"     // the contour kernels, here: k_ov_composite stays the library's last non-template kernel (4d)
+namespace vf {
+
 // vf_terrain_set_layer_occlusion: a point / line layer's records [lo, hi) gain or lose kOvOcclude and kb, in place
 __global__ __launch_bounds__(256) void k_ov_occlude(uint32_t lo, uint32_t hi, OvIn *__restrict__ in, uint32_t on, uint32_t kb_bits)
 {

@@ -482,6 +482,36 @@ public:
         Borrow b(busy);
         check(vf_terrain_set_layer_occlusion(t, layer, oc[0].cast<bool>() ? 1 : 0, oc[1].cast<float>()));
     }
+    // contour lines of the rendered surface, extracted on the device
+    py::tuple height_bounds()
+    {
+        Borrow b(busy);
+        float lo = 0.0f, hi = 0.0f;
+        check(vf_terrain_height_bounds(t, &lo, &hi));
+        return py::make_tuple(lo, hi);
+    }
+    uint32_t layer_primitive_count(uint32_t layer)
+    {
+        Borrow b(busy);
+        uint32_t n = 0;
+        check(vf_terrain_layer_primitive_count(t, layer, &n));
+        return n;
+    }
+    uint32_t add_contours(py::object levels, py::object interval, py::object base, py::object width_px, py::object rgba, py::object lift,
+                          py::object join, py::object occlude, py::object depth_bias)
+    {
+        py::object bounds = py::none();
+        if (levels.is_none() && !interval.is_none()) bounds = height_bounds();
+        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("contour_args")(levels, interval, base, width_px, rgba, lift, join, bounds);
+        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
+        py::array lv = a[0].cast<py::array>(), col = a[2].cast<py::array>();
+        Borrow b(busy);
+        uint32_t id = 0;
+        check(vf_terrain_add_contours(t, static_cast<const float *>(lv.data()), (uint32_t)lv.shape(0), a[1].cast<float>(),
+                                      static_cast<const uint8_t *>(col.data()), a[3].cast<float>(), a[4].cast<int>(), oc[0].cast<bool>() ? 1 : 0,
+                                      oc[1].cast<float>(), &id, nullptr));
+        return id;
+    }
     void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
 
     // src/terrain/mod.rs:537-546
@@ -787,6 +817,11 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
         .def("add_polygons", &T::add_polygons, py::arg("polygons"), py::kw_only(), py::arg("fill_rgba") = py::make_tuple(255, 255, 255, 255),
              py::arg("line_rgba") = py::none(), py::arg("line_width_px") = 1.0f, py::arg("drape") = false)
+        .def("add_contours", &T::add_contours, py::arg("levels") = py::none(), py::kw_only(), py::arg("interval") = py::none(),
+             py::arg("base") = 0.0, py::arg("width_px") = 1.0f, py::arg("rgba") = py::make_tuple(0, 0, 0, 255), py::arg("lift") = 0.0f,
+             py::arg("join") = "round", py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
+        .def("height_bounds", &T::height_bounds)
+        .def("layer_primitive_count", &T::layer_primitive_count, py::arg("layer"))
         .def("clear_overlays", &T::clear_overlays);
 }
 
