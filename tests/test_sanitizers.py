@@ -33,3 +33,11 @@ def test_the_span_solver_under_asan_and_ubsan(tmp_path):
     run(["g++", "-std=c++17", *SAN, "-ffp-contract=off", os.path.join(ROOT, "tests", "cpp", "raster_fuzz.cpp"), "-o", exe])
     out = run([exe, "20000", "20250816"])
     assert "failures 0" in [l for l in out.splitlines() if l.startswith("triangles")][0]
+
+
+def test_the_line_loop_chooser_under_asan_and_ubsan(tmp_path):
+    """The decision behind the tile kernel's two line loops (vf_line_loop.h): settle, ABBA probe window, 3 % rule, periodic looks, no
+    probes for empty shards or forced modes, for both default variants."""
+    exe = str(tmp_path / "line_loop_san")
+    run(["g++", "-std=c++17", *SAN, os.path.join(ROOT, "tests", "cpp", "line_loop_main.cpp"), "-o", exe])
+    assert "line-loop chooser under ASan + UBSan: ok" in run([exe])

@@ -1,5 +1,6 @@
 """C5 (64-pose orbit, 1920x1080, grid 2048) through vf_terrain_render_batch: ms per pose over three laps, the tile kernel's share.
-VF_HIP_LIB selects the library (tools/build_variant.sh); with a -DVF_EXPERIMENTS library VF_NO_MOTION_MAP=1 gives round 4's waiting plan."""
+VF_HIP_LIB selects the library (tools/build_variant.sh); with a -DVF_EXPERIMENTS library built from
+sources with tools/experiments/frame_path_hooks.patch applied, VF_NO_MOTION_MAP=1 gives round 4's waiting plan."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,5 +1,6 @@
 """First frames of a fresh handle (the reference's one-shot usage): wall time of three synchronous frames, how frame 0 was cut.
-VF_NO_STATIC_PLAN=1 switches the static first-frame estimate off (the round-2 behaviour).  usage: exp_cold.py [default|fill] [N:rank]"""
+VF_NO_STATIC_PLAN=1 switches the static first-frame estimate off (the round-2 behaviour) in a -DVF_EXPERIMENTS library built from
+sources with tools/experiments/frame_path_hooks.patch applied.  usage: exp_cold.py [default|fill] [N:rank]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np

@@ -1,5 +1,7 @@
 """Consecutive frames on alternating streams and output buffers (their tile kernels may overlap: frame f + 1's persistent workgroups take
 the CUs frame f's tail leaves idle) against the same frames on one stream: steady-state frame period at C4, one GPU and one rank of N.
+The frames overlap only in a -DVF_EXPERIMENTS library built from sources with tools/experiments/frame_path_hooks.patch applied, run with
+VF_OVERLAP_FRAMES=1 (three streams: -DVF_PLAN_STATES=3 as well); the shipped library makes each frame wait for the one before it.
 usage: exp_overlap.py [camera] [rank n]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -3,6 +3,7 @@
 #include "../../include/vf_hip.h"
 #include "vf_kernels.h"
 #include "vf_overlay.h"     // (brings vf_contour.h)
+#include "vf_line_loop.h"
 
 #include <algorithm>
 #include <cmath>
@@ -192,7 +193,7 @@ static hipError_t ctx_copy_stream(vf_ctx *c, hipStream_t *copy)
 struct FramePlan {
     FrameParams P;
     uint32_t set = 0, ntiles = 0;
-    bool solo = false, motion_starts = false;
+    bool motion_starts = false;
     bool sampled = true;                                         // timing level 3: this frame is one of those that carry events
     uint32_t *rc_lo = nullptr, *rc_hi = nullptr, *seg_count = nullptr;
 };
@@ -225,6 +226,96 @@ template <typename T> struct DevBuf {
     }
 };
 
+// What plan_frame advances from frame to frame.  A plan queued ahead of its call and then thrown away puts the handle back by
+// assigning a saved copy (vf_terrain::PrePlan, drop_preplan); so does the diagnostic frame of render_visibility for the motion part.
+struct PlanCursor {
+    uint32_t cur_set = 0;                // the plan state the next frame takes
+    uint32_t frame_no = 0;
+    uint32_t frames_since_reset = 0;     // frames planned since create / set_shard (the feedback arrays were cleared then)
+    bool have_drawn = false, camera_moving = false, was_moving = false;
+    float u_drawn[32] = {};              // view + proj of the frame planned last (is the camera moving?)
+};
+
+// What the caller sets and a frame is drawn from
+struct FrameInputs {
+    float u[44] = {};                    // the uniform block
+    uint32_t shade_mode = 0;             // VF_SHADE_REFERENCE / VF_SHADE_SPEC_T32
+    uint32_t precision = VF_PRECISION_FAST;   // fragment arithmetic
+};
+
+// Which instantiation of the tile kernel draws the frames -- with or without line groups in the raster's line loop (vf_kernels.h,
+// raster_fast) -- is measured, like the frame plan: which one is faster depends on what the camera shows and on how the frame is
+// cut (C4: groups -7 % on the top-down camera at any rank count, -1.5 % on one GPU at the default camera, +5 % on a rank of eight,
+// whose items are narrow strips).  Never a difference in the picture.  The schedule and the decision: vf_line_loop.h.
+struct LineLoop {
+    int mode = -1;                       // -1 measure and choose, 0 / 1 fixed (vf_terrain_set_raster_groups)
+    // A probe = two events around a frame's kernels on the draw stream (k_clear + the tile launches); a sample = the time between them.
+    // (Round 4 sampled the frame PERIOD between two consecutive frames of one variant, in runs AAABBB: right for a camera at rest, but a
+    //  moving camera's frames differ in cost by +-20 % from pose to pose and a run of three A's sat on other poses than the B's -- on the
+    //  C5 orbit the handle kept the slower variant in the bench, 0.326 instead of 0.305 ms per pose.  Round 5: every probed frame is a
+    //  sample of its own, the variants alternate ABBA ABBA ..., so any linear drift of the cost over the window cancels exactly.)
+    struct Probe { hipEvent_t a = nullptr, b = nullptr; int variant = 0; uint32_t epoch = 0; bool pending = false; } probes[16];
+    uint32_t head = 0, epoch_id = 0;
+    float ms[2] = { 0.0f, 0.0f };        // frame period with each variant in this epoch (mean of the samples taken)
+    uint32_t n[2] = { 0u, 0u };
+    uint32_t epoch_frames = 0;           // frames since the epoch began (shard change, height upload, camera jump)
+    int now = 1;                         // the variant of the frame rendered last
+
+    // A new epoch: what was measured belongs to other heights, another layout or mode, or to the view before the camera started to
+    // move.  (Samples of probes still in flight carry the old epoch's number and are dropped when they complete.)
+    void reset()
+    {
+        epoch_frames = 0; epoch_id++;
+        n[0] = n[1] = 0; ms[0] = ms[1] = 0.0f;
+    }
+    // probes that have completed (frames behind us: never a wait): every probed frame is a sample -- the time its kernels took on
+    // the draw stream.  (hipEventQuery's "not ready" is cleared here: the plan launches' errors were collected by plan_frame.)
+    void harvest()
+    {
+        for (Probe &g : probes)
+            if (g.pending && hipEventQuery(g.b) == hipSuccess) {
+                g.pending = false;
+                float t = 0.0f;
+                if (g.epoch == epoch_id && hipEventElapsedTime(&t, g.a, g.b) == hipSuccess && t > 0.0f) {
+                    // the probe window's samples count alike; a later look weighs as much as all before it (the view may have drifted)
+                    const uint32_t k = ++n[g.variant];
+                    ms[g.variant] += (t - ms[g.variant]) / (float)(k <= 8u ? k : 2u);
+                }
+            }
+        (void)hipGetLastError();
+    }
+    // The variant of this frame and whether it is probed.  guess: the variant by default; restart: what was measured describes another
+    // layout or the view before the camera started to move (a camera that keeps moving keeps its choice and is looked at again).
+    LoopPick choose(int guess, bool restart, bool has_tiles)
+    {
+        uint32_t e = 0;
+        if (mode < 0) {
+            harvest();
+            if (restart) reset();
+            e = epoch_frames++;
+        }
+        const LoopPick pick = line_loop_pick(mode, e, guess, ms, n, has_tiles);
+        now = pick.variant;
+        return pick;
+    }
+    // the first event of a probed frame, in front of its kernels on `s`; nullptr: the frame goes unmeasured (ring full, no events)
+    Probe *arm(hipStream_t s)
+    {
+        Probe *g = &probes[head++ % 16];
+        if (g->pending) return nullptr;
+        if (!g->b && (hipEventCreate(&g->a) != hipSuccess || hipEventCreate(&g->b) != hipSuccess)) return nullptr;   // (made on first use: a one-shot handle never probes)
+        if (!g->a || !g->b) return nullptr;
+        (void)hipEventRecord(g->a, s);
+        return g;
+    }
+    // ... and the second one, behind them
+    void close(Probe *g, hipStream_t s)
+    {
+        (void)hipEventRecord(g->b, s);
+        g->variant = now; g->epoch = epoch_id; g->pending = true;
+    }
+};
+
 struct vf_terrain {
     vf_ctx *ctx = nullptr;
     uint32_t W = 0, H = 0, n = 0;
@@ -232,42 +323,47 @@ struct vf_terrain {
     uint32_t ntx = 0, nty = 0;           // 64x64 screen tiles
     // shard
     uint32_t rank = 0, nranks = 1, band_h = kTileH, local_rows = 0, skew = 0;
-    // uniforms
-    float u[44];
+    uint32_t local_tiles = 0;            // tiles this handle renders (= ntx * local tile rows unless tile-sharded)
+    uint32_t *d_tile_map = nullptr;      // tile shards: local tile -> tx | ty << 16
+    uint8_t *d_stripe_owner = nullptr;   // tile shards with a registered stripe map: owner per column stripe (kMaxStripes bytes)
+    bool use_map = false;
+    bool shard_tiles = false;
+    // inputs: the live ones, and those of the frame vf_terrain_render drew last (visibility, fragment diagnostics)
+    FrameInputs inputs, drawn_inputs;
     bool have_uniforms = false;
-    float u_frame[44] = {};              // uniforms / shade mode of the frame vf_terrain_render drew last (visibility, fragment diagnostics)
-    uint32_t shade_mode_frame = 0;
-    bool have_frame = false;             // u_frame is valid: set by vf_terrain_render only, cleared when the shard layout changes
+    bool have_frame = false;             // drawn_inputs is valid: set by vf_terrain_render only, cleared when the shard layout changes
     uint32_t *d_rgba_scratch = nullptr;  // output of those diagnostic re-renders: the caller's frame is never overwritten
     uint32_t *d_diag = nullptr;          // [0] covered pixels (fragment-stage diagnostics)
-    float u_drawn[32];                   // view + proj of the frame rendered last (is the camera moving?)
-    bool have_drawn = false, camera_moving = false, was_moving = false;
-    uint32_t frames_since_reset = 0;     // frames planned since create / set_shard (the feedback arrays were cleared then)
     // device state
     float *d_xs = nullptr, *d_sinx = nullptr, *d_cosz = nullptr;
     int32_t *d_txi = nullptr, *d_tyj = nullptr;
     float *d_height_own = nullptr;       // Scene::set_height_from_r32f's copy (its own allocation: it is replaced when the size changes)
     float *d_height_dummy = nullptr;     // the 1x1 zero texture of TerrainSpike (in the slab)
     const float *d_height = nullptr;
-    // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
-    static constexpr uint32_t kBatchRing = 3;
-    uint32_t *d_batch[kBatchRing] = { nullptr, nullptr, nullptr };
-    hipEvent_t batch_drawn[kBatchRing] = { nullptr, nullptr, nullptr }, batch_copied[kBatchRing] = { nullptr, nullptr, nullptr };
-    hipStream_t copy_stream = nullptr;
     uint8_t *slab = nullptr;             // ONE device allocation behind every fixed-size buffer of the handle (round 5: construction was ~40 hipMallocs)
     uint32_t tw = 1, th = 1;
     bool bounds_dirty = true;
     float2 *d_bounds = nullptr;          // per block: min/max displaced height
     float *d_hblk = nullptr;             // displaced-height cache: 81 floats per block
+    float *d_lut = nullptr;              // 256*3 linear floats
+    uint32_t *d_rgba_own = nullptr;
+    uint32_t *d_rgba = nullptr;
+    uint32_t *d_vis = nullptr;           // only allocated for vf_terrain_read_visibility and for occluding overlay layers (DESIGN.md 4d)
+    uint32_t *d_stats = nullptr;         // [0] (tile, block) pairs rasterised (stats_layout)
+    // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
+    static constexpr uint32_t kBatchRing = 3;
+    uint32_t *d_batch[kBatchRing] = { nullptr, nullptr, nullptr };
+    hipEvent_t batch_drawn[kBatchRing] = { nullptr, nullptr, nullptr }, batch_copied[kBatchRing] = { nullptr, nullptr, nullptr };
+    hipStream_t copy_stream = nullptr;
+    // read-backs
+    uint8_t *d_png = nullptr, *h_png = nullptr;   // PNG scanlines of the last frame: device, pinned host
+    uint8_t *h_stage = nullptr;                   // kStageSlots x kStageChunk pinned bytes: device -> pageable host copies go through here
+    hipEvent_t stage_ev[4] = { nullptr, nullptr, nullptr, nullptr };
     // Per-frame plan state, kPlanStates times: frame f uses set f % kPlanStates.  The plan kernels of a frame run on `side` and touch
     // nothing else, so they overlap the previous frames' tile kernels (which still read the other sets) instead of waiting for them.
-    // (VF_PLAN_STATES 3 and VF_OVERLAP_FRAMES=1 are round 4's experiment with consecutive frames on alternating streams and output
-    //  buffers, whose tile kernels then overlap -- frame f + 1's persistent workgroups take the CUs frame f's tail leaves idle:
-    //  measured +8 % on one GPU and +6 % on a rank of eight with two streams, -1 % on the rank with three; tools/exp_overlap.py.)
-#ifndef VF_PLAN_STATES
-#define VF_PLAN_STATES 2
-#endif
-    static constexpr uint32_t kPlanStates = VF_PLAN_STATES;
+    // (Round 4's experiment with three states and consecutive frames on alternating streams and output buffers, whose tile kernels
+    //  then overlap, was not kept -- EXPERIMENTS.md; tools/experiments/frame_path_hooks.patch brings its switches back.)
+    static constexpr uint32_t kPlanStates = 2;
     struct PlanState {
         PixelBox *ranges = nullptr;      // per block: conservative pixel rectangle (from the block's height bounds)
         VertexRec *vtx = nullptr;        // per block 81 x {X, Y, 1/w, h} (k_block_setup)
@@ -293,16 +389,13 @@ struct vf_terrain {
         float u_used[32] = {};           // view + proj of the frame whose tile times sit in `feedback` (the plan looks them up through the camera motion)
         bool have_u_used = false;
     } ps[kPlanStates];
-    uint32_t cur_set = 0, last_set = 0;  // the set the next frame takes; the set of the frame rendered last
-    const uint32_t *last_out = nullptr;  // output buffer of the frame rendered last
+    PlanCursor cursor;
+    uint32_t last_set = 0;               // the set of the frame rendered last
     hipStream_t side = nullptr;          // k_block_boxes -> k_plan -> k_plan_sort
     hipStream_t side2 = nullptr;         // k_block_setup (needs the block boxes only): beside the plan chain, both under the previous frame
-    uint32_t frame_no = 0;
-    float *d_lut = nullptr;              // 256*3 linear floats
-    uint32_t *d_rgba_own = nullptr;
-    uint8_t *d_png = nullptr, *h_png = nullptr;   // PNG scanlines of the last frame: device, pinned host
-    uint8_t *h_stage = nullptr;                   // kStageSlots x kStageChunk pinned bytes: device -> pageable host copies go through here
-    hipEvent_t stage_ev[4] = { nullptr, nullptr, nullptr, nullptr };
+    hipEvent_t entry = nullptr;          // caller's stream at render entry (orders a height-cache rebuild after the caller's work)
+    hipStream_t last_stream = nullptr;
+    bool rendered = false;
     // THE NEXT FRAME'S PLAN, QUEUED AHEAD (round 5).  A camera at rest draws the same plan again and again, and a caller that waits for
     // each frame (render_png, render_rgba: every call of the reference's API) used to pay the plan chain -- block boxes, set-up pass,
     // plan, sort: 0.2 ms at C4 -- in front of every tile kernel, because nothing is left to hide it under once the caller has waited.
@@ -315,10 +408,7 @@ struct vf_terrain {
         bool valid = false;
         FramePlan K;
         uint64_t gen = 0;
-        // what plan_frame advanced (restored when the plan is thrown away)
-        uint32_t cur_set = 0, frame_no = 0, frames_since_reset = 0;
-        bool camera_moving = false, was_moving = false, have_drawn = false;
-        float u_drawn[32] = {};
+        PlanCursor before;               // where the handle stood before plan_frame advanced it (restored when the plan is thrown away)
     } pre;
     uint64_t last_drawn_gen = 0;         // inputs_gen of the frame drawn last (two frames of one generation: the camera is at rest)
     bool replan_fresh = false;           // a plan queued ahead was thrown away: the next plan takes the previous frame's tile times (drop_preplan)
@@ -334,42 +424,14 @@ struct vf_terrain {
     uint32_t tight_calls = 0;
     bool want_plan_streams = false;
     hipEvent_t copied = nullptr;         // behind a read-back's copy: the host waits for this, not for the stream (the plan made ahead follows it)
-    uint32_t *d_tile_map = nullptr;      // tile shards: local tile -> tx | ty << 16
-    uint8_t *d_stripe_owner = nullptr;   // tile shards with a registered stripe map: owner per column stripe (kMaxStripes bytes)
-    bool use_map = false;
-    bool shard_tiles = false;
-    uint32_t shade_mode = 0;             // VF_SHADE_REFERENCE / VF_SHADE_SPEC_T32
-    uint32_t precision = VF_PRECISION_FAST, precision_frame = VF_PRECISION_FAST;   // fragment arithmetic (of the frame vf_terrain_render drew last)
-    uint32_t local_tiles = 0;            // tiles this handle renders (= ntx * local tile rows unless tile-sharded)
-    uint32_t *d_rgba = nullptr;
-    uint32_t *d_vis = nullptr;           // only allocated for vf_terrain_read_visibility and for occluding overlay layers (DESIGN.md 4d)
-    uint32_t *d_stats = nullptr;         // [0] (tile, block) pairs rasterised
-    // timing: a ring of (start, after block boxes, after plan, after tile) events, one set per rendered frame
+    // timing: a ring of events on the draw stream, one pair per timed frame (the plan's events live with its plan state: pev)
     static constexpr int kTimingRing = 64;
     bool timing = false;
     bool stats_on = false;               // per-item statistics as well (vf_terrain_enable_timing(t, 1)); 2 = device times only
     uint32_t timing_every = 1;           // 3 = device times of every 4th frame only: two event records on the draw stream cost a frame 2 % (tools/exp_timing_cost.py)
-    hipEvent_t ev[kTimingRing][5] = {};   // [3] after the tile kernels, [4] before the clear (caller's stream); [0..2] unused since round 6: the plan's events live with its plan state (pev)
-    hipEvent_t entry = nullptr;          // caller's stream at render entry (orders a height-cache rebuild after the caller's work)
+    struct FrameEvents { hipEvent_t begin = nullptr, end = nullptr; } ev[kTimingRing];   // before the clear, after the tile kernels (caller's stream)
     uint32_t timed_frames = 0;           // frames recorded since timing was enabled
-    hipStream_t last_stream = nullptr;
-    bool rendered = false;
-    // Which instantiation of the tile kernel draws the frames -- with or without line groups in the raster's line loop (vf_kernels.h,
-    // raster_fast) -- is measured, like the frame plan: which one is faster depends on what the camera shows and on how the frame is
-    // cut (C4: groups -7 % on the top-down camera at any rank count, -1.5 % on one GPU at the default camera, +5 % on a rank of eight,
-    // whose items are narrow strips).  Never a difference in the picture.  groups_mode: -1 measure and choose, 0 / 1 fixed.
-    int groups_mode = -1;
-    // A probe = two events around a frame's kernels on the draw stream (k_clear + the tile launches); a sample = the time between them.
-    // (Round 4 sampled the frame PERIOD between two consecutive frames of one variant, in runs AAABBB: right for a camera at rest, but a
-    //  moving camera's frames differ in cost by +-20 % from pose to pose and a run of three A's sat on other poses than the B's -- on the
-    //  C5 orbit the handle kept the slower variant in the bench, 0.326 instead of 0.305 ms per pose.  Round 5: every probed frame is a
-    //  sample of its own, the variants alternate ABBA ABBA ..., so any linear drift of the cost over the window cancels exactly.)
-    struct GroupProbe { hipEvent_t a = nullptr, b = nullptr; int variant = 0; uint32_t seq = 0, epoch = 0; bool pending = false, valid = false; } gprobe[16];
-    uint32_t gprobe_head = 0, g_epoch_id = 0;
-    float g_ms[2] = { 0.0f, 0.0f };      // frame period with each variant in this epoch (mean of the samples taken)
-    uint32_t g_n[2] = { 0u, 0u };
-    uint32_t g_epoch_frames = 0;         // frames since the epoch began (shard change, height upload, camera jump)
-    int groups_now = 1;                  // the variant of the frame rendered last
+    LineLoop loop;
     // vf_dist_exchange_bands: the chunks this rank receives in the all-to-all ([nranks][chunk_tiles] tile slots) and the band it stitches from them
     uint8_t *d_xrecv = nullptr, *d_xband = nullptr;
     size_t xrecv_bytes = 0, xband_bytes = 0;
@@ -409,6 +471,19 @@ struct vf_terrain {
         DevBuf<float2> bounds;               // [1] vf_terrain_height_bounds
     } ct;
 };
+
+// Sizes that more than one place must agree on, in 32-bit words.
+// d_stats: four counters, four words per possible work item, the phase cycle counts (64-bit), one bit per block (drawn this frame?)
+struct StatsLayout { size_t phases, block_bits, words; };
+static StatsLayout stats_layout(const vf_terrain *t)
+{
+    const size_t phases = 4 + 4 * ((size_t)t->ntx * t->nty + kSplitBudget), block_bits = phases + 2 * kPhaseSlots;
+    return { phases, block_bits, block_bits + (t->nblocks + 31) / 32 };
+}
+// a plan state's tile times: one word per tile, the split quantum, 64 words per tile for its pieces
+static size_t feedback_words(const vf_terrain *t) { return (size_t)t->ntx * t->nty * 65 + 1; }
+// 16-block segments of the grid's block rows
+static uint32_t grid_segments(const vf_terrain *t) { return t->nb * ((t->nb + kSegBlocks - 1) / kSegBlocks); }
 
 extern "C" {
 
@@ -564,9 +639,7 @@ static hipError_t drop_preplan(vf_terrain *t, hipStream_t next_plan_on = nullptr
     if (!t->pre.valid) return hipSuccess;
     const vf_terrain::PrePlan &R = t->pre;
     t->pre.valid = false;
-    t->cur_set = R.cur_set; t->frame_no = R.frame_no; t->frames_since_reset = R.frames_since_reset;
-    t->camera_moving = R.camera_moving; t->was_moving = R.was_moving; t->have_drawn = R.have_drawn;
-    std::memcpy(t->u_drawn, R.u_drawn, sizeof t->u_drawn);
+    t->cursor = R.before;
     // The stale plan's k_plan_sort has already zeroed this set's tile times and replaced its flag words: the frame that is planned in
     // its place reads the PREVIOUS frame's (complete: the caller was idle when the plan went out) -- plan_frame's `fresh` mode.
     t->replan_fresh = true;
@@ -586,10 +659,9 @@ static hipError_t ensure_plan_state(vf_terrain *t, uint32_t k, hipStream_t zero_
     vf_terrain::PlanState &S = t->ps[k];
     if (S.slab) return hipSuccess;
     const size_t all_tiles = (size_t)t->ntx * t->nty;
-    const size_t nsegs = (size_t)t->nb * ((t->nb + kSegBlocks - 1) / kSegBlocks);
     Carver C;
-    C.add((void **)&S.seg_list, (nsegs + 1) * sizeof(uint32_t), true);
-    C.add((void **)&S.feedback, (all_tiles * 65 + 1) * sizeof(uint32_t), true);
+    C.add((void **)&S.seg_list, ((size_t)grid_segments(t) + 1) * sizeof(uint32_t), true);
+    C.add((void **)&S.feedback, feedback_words(t) * sizeof(uint32_t), true);
     C.add((void **)&S.background, all_tiles * sizeof(uint32_t), true);
     C.add((void **)&S.ranges, t->nblocks * sizeof(PixelBox));
     C.add((void **)&S.vtx, (size_t)t->nblocks * kBlockStride * sizeof(VertexRec));
@@ -654,7 +726,6 @@ int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t gri
     t->nty = (height + kTileH - 1) / kTileH;
     t->local_rows = height;
     t->local_tiles = t->ntx * t->nty;
-    std::memset(t->u, 0, sizeof t->u);
 
     // linear LUT as the kernels stage it: 257 x {r, g, b, 0}, entry 256 = entry 255
     float lut[kLutFloats];
@@ -670,7 +741,7 @@ int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t gri
     const size_t all_tiles = (size_t)t->ntx * t->nty;
     Carver C;
     C.add((void **)&t->d_height_dummy, sizeof(float), true);      // 1x1 zero texture, src/terrain/mod.rs:342-378
-    C.add((void **)&t->d_stats, (4 + 4 * (all_tiles + kSplitBudget) + 2 * kPhaseSlots + (t->nblocks + 31) / 32) * sizeof(uint32_t), true);   // (only [0..4) must be zero) + one bit per block: drawn this frame?
+    C.add((void **)&t->d_stats, stats_layout(t).words * sizeof(uint32_t), true);   // (only [0..4) must be zero)
     C.add((void **)&t->d_xs, n * sizeof(float));
     C.add((void **)&t->d_sinx, n * sizeof(float));
     C.add((void **)&t->d_cosz, n * sizeof(float));
@@ -727,10 +798,10 @@ void vf_terrain_destroy(vf_terrain *t)
     for (auto &e : t->stage_ev) if (e) (void)hipEventDestroy(e);
     if (t->d_png) (void)hipFree(t->d_png);
     pinned_free(t->h_png);
-    for (auto &f : t->ev) for (auto &e : f) if (e) (void)hipEventDestroy(e);
+    for (auto &f : t->ev) { if (f.begin) (void)hipEventDestroy(f.begin); if (f.end) (void)hipEventDestroy(f.end); }
     if (t->entry) (void)hipEventDestroy(t->entry);
     if (t->copied) (void)hipEventDestroy(t->copied);
-    for (auto &g : t->gprobe) { if (g.a) (void)hipEventDestroy(g.a); if (g.b) (void)hipEventDestroy(g.b); }
+    for (auto &g : t->loop.probes) { if (g.a) (void)hipEventDestroy(g.a); if (g.b) (void)hipEventDestroy(g.b); }
     ov_release(t);
     delete t;
 }
@@ -738,8 +809,8 @@ void vf_terrain_destroy(vf_terrain *t)
 int vf_terrain_set_uniforms(vf_terrain *t, const float uniforms[44])
 {
     if (!t || !uniforms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->have_uniforms || std::memcmp(t->u, uniforms, sizeof t->u) != 0) t->inputs_gen++;     // (a plan made ahead was made for the old block)
-    std::memcpy(t->u, uniforms, sizeof t->u);
+    if (!t->have_uniforms || std::memcmp(t->inputs.u, uniforms, sizeof t->inputs.u) != 0) t->inputs_gen++;     // (a plan made ahead was made for the old block)
+    std::memcpy(t->inputs.u, uniforms, sizeof t->inputs.u);
     t->have_uniforms = true;
     return VF_OK;
 }
@@ -748,7 +819,7 @@ static int set_height_common(vf_terrain *t, uint32_t tw, uint32_t th)
 {
     t->inputs_gen++;
     VF_HIP_TRY(drop_preplan(t));
-    t->g_epoch_frames = 0; t->g_epoch_id++; t->g_n[0] = t->g_n[1] = 0;     // other heights: which line loop is faster is measured again
+    t->loop.reset();                                       // other heights: which line loop is faster is measured again
     bool resized = tw != t->tw || th != t->th;
     t->tw = tw; t->th = th;
     if (resized) return refresh_tables(t, t->ctx->stream);
@@ -804,8 +875,8 @@ int vf_terrain_set_shade_mode(vf_terrain *t, int mode)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (mode != VF_SHADE_REFERENCE && mode != VF_SHADE_SPEC_T32) return fail(VF_ERR_INVALID, "unknown shade mode");
-    if (t->shade_mode != (uint32_t)mode) t->inputs_gen++;
-    t->shade_mode = (uint32_t)mode;
+    if (t->inputs.shade_mode != (uint32_t)mode) t->inputs_gen++;
+    t->inputs.shade_mode = (uint32_t)mode;
     return VF_OK;
 }
 
@@ -813,8 +884,8 @@ int vf_terrain_set_shade_precision(vf_terrain *t, int precision)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (precision != VF_PRECISION_EXACT && precision != VF_PRECISION_FAST) return fail(VF_ERR_INVALID, "unknown shade precision");
-    if (t->precision != (uint32_t)precision) t->inputs_gen++;
-    t->precision = (uint32_t)precision;
+    if (t->inputs.precision != (uint32_t)precision) t->inputs_gen++;
+    t->inputs.precision = (uint32_t)precision;
     return VF_OK;
 }
 
@@ -822,16 +893,32 @@ int vf_terrain_set_raster_groups(vf_terrain *t, int mode)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (mode < -1 || mode > 1) return fail(VF_ERR_INVALID, "mode must be -1 (measure and choose), 0 or 1");
-    t->groups_mode = mode;
-    t->g_epoch_frames = 0; t->g_epoch_id++; t->g_n[0] = t->g_n[1] = 0; t->g_ms[0] = t->g_ms[1] = 0.0f;
+    t->loop.mode = mode;
+    t->loop.reset();
     return VF_OK;
 }
 
 int vf_terrain_raster_groups(const vf_terrain *t, int *in_use, float ms[2])
 {
     if (!t || !in_use) return fail(VF_ERR_INVALID, "NULL argument");
-    *in_use = t->groups_now;
-    if (ms) { ms[0] = t->g_n[0] ? t->g_ms[0] : 0.0f; ms[1] = t->g_n[1] ? t->g_ms[1] : 0.0f; }
+    *in_use = t->loop.now;
+    if (ms) { ms[0] = t->loop.n[0] ? t->loop.ms[0] : 0.0f; ms[1] = t->loop.n[1] ? t->loop.ms[1] : 0.0f; }
+    return VF_OK;
+}
+
+// The shard layout has changed (the caller has waited for the frame in flight): nothing rendered under the new one yet, and the tile
+// numbering is another -- forget the scheduling feedback of the previous layout
+static int reset_layout_feedback(vf_terrain *t)
+{
+    t->rendered = false; t->have_frame = false;
+    t->cursor.frames_since_reset = 0;
+    VF_HIP_TRY(sync_sides(t));
+    for (auto &S : t->ps) {
+        if (!S.slab) continue;                             // (a state not used yet starts at zero when it is made)
+        VF_HIP_TRY(hipMemset(S.feedback, 0, feedback_words(t) * sizeof(uint32_t)));
+        VF_HIP_TRY(hipMemset(S.background, 0, (size_t)t->ntx * t->nty * sizeof(uint32_t)));
+        S.have_u_used = false;
+    }
     return VF_OK;
 }
 
@@ -848,17 +935,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     t->shard_tiles = false; t->use_map = false;
     t->local_rows = compute_local_rows(t->H, rank, nranks, band_h);
     t->local_tiles = t->ntx * ((t->local_rows + kTileH - 1) / kTileH);
-    t->rendered = false; t->have_frame = false;
-    t->frames_since_reset = 0;
-    // tile numbering changed: forget the scheduling feedback of the previous layout
-    VF_HIP_TRY(sync_sides(t));
-    for (auto &S : t->ps) {
-        if (!S.slab) continue;                             // (a state not used yet starts at zero when it is made)
-        VF_HIP_TRY(hipMemset(S.feedback, 0, ((size_t)t->ntx * t->nty * 65 + 1) * sizeof(uint32_t)));
-        VF_HIP_TRY(hipMemset(S.background, 0, (size_t)t->ntx * t->nty * sizeof(uint32_t)));
-        S.have_u_used = false;
-    }
-    return VF_OK;
+    return reset_layout_feedback(t);
 }
 
 int vf_tile_layout(uint32_t width, uint32_t height, uint32_t rank, uint32_t nranks, uint32_t skew, uint32_t *tiles, uint32_t capacity,
@@ -987,16 +1064,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     t->shard_tiles = true; t->local_tiles = n;
     t->rank = rank; t->nranks = nranks; t->skew = skew;
     t->local_rows = 0;                                   // row-oriented accessors do not apply to a tile-major buffer
-    t->rendered = false; t->have_frame = false;
-    t->frames_since_reset = 0;
-    VF_HIP_TRY(sync_sides(t));
-    for (auto &S : t->ps) {
-        if (!S.slab) continue;                             // (a state not used yet starts at zero when it is made)
-        VF_HIP_TRY(hipMemset(S.feedback, 0, ((size_t)t->ntx * t->nty * 65 + 1) * sizeof(uint32_t)));
-        VF_HIP_TRY(hipMemset(S.background, 0, (size_t)t->ntx * t->nty * sizeof(uint32_t)));
-        S.have_u_used = false;
-    }
-    return VF_OK;
+    return reset_layout_feedback(t);
 }
 
 int vf_terrain_local_tiles(const vf_terrain *t, uint32_t *tiles)
@@ -1040,9 +1108,9 @@ int vf_terrain_rgba_device(const vf_terrain *t, void **dev_rgba)
     return VF_OK;
 }
 
-static void build_params(const vf_terrain *t, FrameParams &P)
+static void build_params(const vf_terrain *t, const FrameInputs &in, FrameParams &P)
 {
-    const float *u = t->u;
+    const float *u = in.u;
     std::memcpy(P.view, u, 64);
     std::memcpy(P.proj, u + 16, 64);
     P.spacing = std::fmax(u[36], 1e-8f);       // terrain.wgsl:46
@@ -1062,7 +1130,7 @@ static void build_params(const vf_terrain *t, FrameParams &P)
     P.local_rows = t->local_rows;
     P.shard_tiles = t->shard_tiles ? 1u : 0u; P.tile_map = t->d_tile_map; P.skew = layout_skew(t->skew); P.stripe_shift = layout_shift(t->skew);
     P.stripe_owner = t->shard_tiles && t->use_map ? t->d_stripe_owner : nullptr;
-    P.shade_mode = t->shade_mode; P.tex = t->d_height;
+    P.shade_mode = in.shade_mode; P.tex = t->d_height;
     P.inv2hr = 1.0f / (2.0f * P.h_range);
     {   // cell / nm1 as mulhi(cell, m) >> s, exact for cell < 2^26 (nm1 < 2^13): s = 31 + ceil(log2 nm1) - 32, m = ceil(2^(s + 32) / nm1)
         const uint32_t d = P.nm1;
@@ -1082,7 +1150,7 @@ static void build_params(const vf_terrain *t, FrameParams &P)
 // other content.  A corner behind either camera counts as "moved".
 static float camera_shift_px(const vf_terrain *t, const float *a, const float *b)
 {
-    const float ext = 1.5f * std::fmax(t->u[36], 1e-8f);
+    const float ext = 1.5f * std::fmax(t->inputs.u[36], 1e-8f);
     float worst = 0.0f;
     for (int c = 0; c < 4; ++c) {
         const float p[4] = { (c & 1) ? ext : -ext, 0.0f, (c & 2) ? ext : -ext, 1.0f };
@@ -1144,27 +1212,29 @@ constexpr float kFreshFeedbackPx = 24.0f;   // from here on (3/8 of a tile per f
 #define VF_GROUPS_MAX_RANKS 8    // handles sharded over this many ranks or more take the tile kernel without line groups
 #endif
 // the fast fragment path exists for fs_main as coded; the documented-only SPEC_T32 stage always takes the exact arithmetic
-static bool fast_shading(const vf_terrain *t) { return t->precision == VF_PRECISION_FAST && t->shade_mode == VF_SHADE_REFERENCE; }
+static bool fast_shading(const FrameInputs &in) { return in.precision == VF_PRECISION_FAST && in.shade_mode == VF_SHADE_REFERENCE; }
 
 // A frame in two halves (round 5).  plan_frame: everything up to the plan's last kernel -- block boxes, set-up pass, plan, sort -- on the
 // side streams (a handle's first frame: on `s`); it touches plan state only.  draw_frame: the kernels on the caller's stream.  What the
 // second half needs of the first travels in a FramePlan, so that the first half of the NEXT frame can be queued ahead of its call
 // (vf_terrain::pre, render_impl).
-static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = false, bool streaming = false)
+static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming = false)
 {
     FrameParams &P = K.P;
-    build_params(t, P);
+    PlanCursor &C = t->cursor;
+    const float *u = t->inputs.u;
+    build_params(t, t->inputs, P);
     AxisTables A = axis(t);
     const uint32_t ntiles = t->local_tiles;
-    const uint32_t set = t->cur_set;
-    t->cur_set = (set + 1u) % vf_terrain::kPlanStates;
-    t->frame_no++;
+    const uint32_t set = C.cur_set;
+    C.cur_set = (set + 1u) % vf_terrain::kPlanStates;
+    C.frame_no++;
     // A handle's FIRST frame runs on the caller's stream alone, plan and set-up included: its chain is serial anyway (the static plan
     // estimate reads the set-up pass's records) and there is no earlier frame to hide anything under.  The side streams and the second
     // plan chain's events come into play with the second frame.
     // ... and so do the frames of a caller that waits for each of them (round 6): the plan streams are made for the caller that
     // streams -- a frame arriving while the previous one is in flight -- or borrowed when the context already has them.
-    if (!t->side && t->frame_no > 1u) {
+    if (!t->side && C.frame_no > 1u) {
         bool have = false;
         { std::lock_guard<std::mutex> lk(t->ctx->lazy_mu); have = t->ctx->side && t->ctx->side2; }
         if (have || streaming || t->want_plan_streams) VF_HIP_TRY(ctx_side_streams(t->ctx, &t->side, &t->side2));   // (the context's: made once per process)
@@ -1177,10 +1247,10 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
     // the plan then costs its own time (k_plan + k_plan_sort after the tile kernel), stale feedback costs more (64-pose orbit
     // at 1920x1080, grid 2048: 0.80 -> 0.61 ms per pose together with the dilated weights in k_plan; tools/exp_orbit.py).
     float shift = 0.0f;
-    if (t->have_drawn) {
-        shift = camera_shift_px(t, t->u_drawn, t->u);
-        if (shift > kFreshFeedbackPx) t->camera_moving = true;                 // hysteresis: frames that alternate between the two
-        else if (shift < 0.5f * kFreshFeedbackPx) t->camera_moving = false;    // modes get the worst of both
+    if (C.have_drawn) {
+        shift = camera_shift_px(t, C.u_drawn, u);
+        if (shift > kFreshFeedbackPx) C.camera_moving = true;                  // hysteresis: frames that alternate between the two
+        else if (shift < 0.5f * kFreshFeedbackPx) C.camera_moving = false;     // modes get the worst of both
     }
     // (one more frame after the motion stops: the frame before last still shows the old view, the last one the new)
     // ... and the second frame of a handle: its own plan state has no times yet, the first frame's has
@@ -1189,35 +1259,27 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
     // MotionMap): the homography of the ground plane between this frame's screen and the screen of the frame before last.  What is
     // left of the waiting mode: a handle's second frame, sharded handles (their feedback is per local tile), a jump cut (the view of
     // two frames ago shares little with this one: the previous frame's times, dilated, are the better guess), an edge-on plane.
-    const bool young = t->frames_since_reset >= 1 && t->frames_since_reset < vf_terrain::kPlanStates;
+    const bool young = C.frames_since_reset >= 1 && C.frames_since_reset < vf_terrain::kPlanStates;
     MotionMap M;
     std::memset(&M, 0, sizeof M);
-    if ((t->camera_moving || t->was_moving) && !young && t->frames_since_reset >= vf_terrain::kPlanStates && S.have_u_used && t->nranks == 1u && !t->shard_tiles &&
-        camera_shift_px(t, S.u_used, t->u) < 0.4f * (float)std::max(t->W, t->H))
-        (void)motion_map(t, S.u_used, t->u, M);
-#ifdef VF_EXPERIMENTS
-    if (std::getenv("VF_NO_MOTION_MAP")) M.on = 0u;
-#endif
-    const bool after_drop = t->replan_fresh && t->frames_since_reset >= vf_terrain::kPlanStates;   // (a handle's first frames have their own rules)
+    if ((C.camera_moving || C.was_moving) && !young && C.frames_since_reset >= vf_terrain::kPlanStates && S.have_u_used && t->nranks == 1u && !t->shard_tiles &&
+        camera_shift_px(t, S.u_used, u) < 0.4f * (float)std::max(t->W, t->H))
+        (void)motion_map(t, S.u_used, u, M);
+    const bool after_drop = t->replan_fresh && C.frames_since_reset >= vf_terrain::kPlanStates;   // (a handle's first frames have their own rules)
     t->replan_fresh = false;
     if (after_drop) M.on = 0u;                              // (the motion map reads this set's times too)
-    const bool fresh = young || after_drop || ((t->camera_moving || t->was_moving) && !M.on);
-#ifdef VF_EXPERIMENTS
-    const bool first = t->frames_since_reset == 0 && !std::getenv("VF_NO_STATIC_PLAN");
-#else
-    const bool first = t->frames_since_reset == 0;
-#endif   // no tile times at all yet: a static estimate stands in (k_plan_estimate)
-    t->frames_since_reset++;
-    const bool motion_starts = t->camera_moving && !t->was_moving;
-    t->was_moving = t->camera_moving;
+    const bool fresh = young || after_drop || ((C.camera_moving || C.was_moving) && !M.on);
+    const bool first = C.frames_since_reset == 0;           // no tile times at all yet: a static estimate stands in (k_plan_estimate)
+    C.frames_since_reset++;
+    const bool motion_starts = C.camera_moving && !C.was_moving;
+    C.was_moving = C.camera_moving;
     const bool dilate = fresh || shift > 0.5f * kFreshFeedbackPx;     // slower motion: still overlapped, but the tile weights spread to the neighbours
-    std::memcpy(t->u_drawn, t->u, sizeof t->u_drawn);
-    t->have_drawn = true;
+    std::memcpy(C.u_drawn, u, sizeof C.u_drawn);
+    C.have_drawn = true;
     hipStream_t side = solo ? s : t->side, side2 = solo ? s : t->side2;
     // (the plan's three timing events belong to its plan state, not to a slot of the frame ring: a plan queued ahead of its call has no
     //  place in the ring yet -- advisor, round 5 -- and the ring's events sit on the draw stream, where every record costs the frame)
-    K.sampled = t->timing_every <= 1u || t->frame_no % t->timing_every == 0u;
-    (void)ahead;
+    K.sampled = t->timing_every <= 1u || C.frame_no % t->timing_every == 0u;
     // (not at timing level 3: an event record between two kernels of the plan chain delays the chain, and a plan that is late holds its frame's
     //  tile kernel back -- three records per plan cost a C4 frame 2.5 %, on the plan streams as on the draw stream)
     const bool timed = t->timing && t->timing_every <= 1u && S.pev[0] != nullptr;
@@ -1239,7 +1301,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
     // the split quantum comes from the same tile times the plan will read: summed by an extra workgroup of k_block_boxes, or --
     // when those times belong to the frame still being drawn -- by a kernel of its own after the wait below
     uint32_t *quantum = S.feedback + (size_t)t->ntx * t->nty;
-    const uint32_t nsegs_all = t->nb * ((t->nb + kSegBlocks - 1) / kSegBlocks);
+    const uint32_t nsegs_all = grid_segments(t);
     uint32_t *seg_count = S.seg_list + nsegs_all;
     hipLaunchKernelGGL(k_block_boxes, dim3(t->nb + 1), dim3(t->nb > 256 ? 512 : 256), 0, side, P, t->d_bounds, S.ranges, S.row_ranges, S.cap_seg, S.cap_rad, rc_lo, rc_hi,
                        fresh || first ? (const uint32_t *)nullptr : S.feedback, t->ntx * t->nty, quantum, S.work_count, S.recs, S.seg_list, seg_count);
@@ -1249,14 +1311,6 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
     VF_HIP_TRY(hipStreamWaitEvent(side2, S.boxed, 0));                  // (orders it after S.drawn and the height cache too)
     // (one short-lived workgroup per possible segment -- those beyond the list's length leave at once: workgroups that come and go
     //  share the CUs with the previous frame's tile kernel more smoothly than a few long-lived ones)
-    // (experiments only, VF_DBG_NO_SETUP=1: a camera at rest re-creates the same records in the same buffers, so after the first frames
-    //  the pass can be left out to see what the frame costs without it -- the picture stays right, the time is a lower bound)
-#ifdef VF_EXPERIMENTS
-    static const bool dbg_no_setup = std::getenv("VF_DBG_NO_SETUP") != nullptr;
-#else
-    constexpr bool dbg_no_setup = false;
-#endif
-    if (!(dbg_no_setup && t->frames_since_reset > 6))
     hipLaunchKernelGGL(k_block_setup, dim3(nsegs_all), dim3(kSetupThreads), 0, side2,
                        P, t->d_hblk, S.ranges, S.vtx, S.recs, S.gen, S.seg_list, seg_count);
     VF_HIP_TRY(hipEventRecord(S.set_up, side2));
@@ -1279,7 +1333,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool ahead = f
     VF_HIP_TRY(hipGetLastError());                              // a failed plan launch is reported here: the probe block below clears hipEventQuery's "not ready"
     if (timed) VF_HIP_TRY(hipEventRecord(ev[2], side));
     VF_HIP_TRY(hipEventRecord(S.planned, side));
-    K.set = set; K.ntiles = ntiles; K.solo = solo; K.motion_starts = motion_starts; K.rc_lo = rc_lo; K.rc_hi = rc_hi; K.seg_count = seg_count;
+    K.set = set; K.ntiles = ntiles; K.motion_starts = motion_starts; K.rc_lo = rc_lo; K.rc_hi = rc_hi; K.seg_count = seg_count;
     return VF_OK;
 }
 
@@ -1344,89 +1398,28 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool write_vis = diag || (t->ov.occluding && t->ov.nprims);
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
-    const bool motion_starts = K.motion_starts, solo = K.solo;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
-    // (a plan queued ahead of its call may have been made before timing was switched on, or for another position of the ring: its three
-    //  events are then recorded here -- valid, if not telling -- so that the frame's entry in the ring is complete)
-    const uint32_t slot_now = t->timed_frames % (uint32_t)vf_terrain::kTimingRing;
-    hipEvent_t *ev = t->ev[slot_now];
+    vf_terrain::FrameEvents &ev = t->ev[t->timed_frames % (uint32_t)vf_terrain::kTimingRing];
     const bool timing_now = t->timing && K.sampled;
-    (void)solo;
     // ---- draw, on the caller's stream: everything that touches the output buffers ----
     uint32_t *stats = t->timing && t->stats_on ? t->d_stats : nullptr;
-    const uint32_t nstats = (uint32_t)(4 + 4 * ((size_t)t->ntx * t->nty + kSplitBudget) + 2 * kPhaseSlots + (t->nblocks + 31) / 32);   // zeroed by k_clear (no memset dispatch)
+    const uint32_t nstats = (uint32_t)stats_layout(t).words;     // zeroed by k_clear (no memset dispatch)
     VF_HIP_TRY(hipStreamWaitEvent(s, S.planned, 0));
     VF_HIP_TRY(hipStreamWaitEvent(s, S.set_up, 0));
     // The previous frame may have been drawn on another stream of the caller's: this frame waits for it (same output / statistics
-    // buffers; and when it went to another output buffer, letting the two tile kernels overlap costs more than it gains -- the
-    // experiment behind VF_OVERLAP_FRAMES, tools/exp_overlap.py).  Frames that store their visibility -- diagnostics, and every frame of
-    // a handle with an occluding layer -- always wait: d_vis is one buffer per handle.
-#ifdef VF_EXPERIMENTS
-    static const bool overlap_frames = std::getenv("VF_OVERLAP_FRAMES") != nullptr;
-#else
-    constexpr bool overlap_frames = false;
-#endif
-    if (t->last_stream && t->last_stream != s && t->rendered && (!overlap_frames || t->last_out == t->d_rgba || stats || write_vis || !t->last_out))
+    // buffers; and when it went to another output buffer, letting the two tile kernels overlap costs more than it gains --
+    // tools/exp_overlap.py; d_vis is one buffer per handle anyway).
+    if (t->last_stream && t->last_stream != s && t->rendered)
         VF_HIP_TRY(hipStreamWaitEvent(s, t->ps[t->last_set].drawn, 0));
-    if (timing_now) VF_HIP_TRY(hipEventRecord(ev[4], s));
+    if (timing_now) VF_HIP_TRY(hipEventRecord(ev.begin, s));
     // line groups in the raster's line loop (vf_kernels.h, raster_fast): whole frames and shards of few ranks -- wide items, triangles
     // with many lines -- gain from them (C4: one GPU -2 %, top-down camera -7 %); a rank of many mostly draws narrow strips, whose
-    // triangles have a handful of lines, and is better off with the leaner kernel (VF_GROUPS=0 / 1 overrides)
-#ifdef VF_EXPERIMENTS
-    static const int groups_env = std::getenv("VF_GROUPS") ? std::atoi(std::getenv("VF_GROUPS")) : -1;
-#else
-    constexpr int groups_env = -1;
-#endif
-    const int forced = groups_env >= 0 ? groups_env : t->groups_mode;
-    // the variant by default: groups for whole frames and shards of few ranks, none for a rank of many (mostly narrow strips)
+    // triangles have a handful of lines, and is better off with the leaner kernel.  That is the variant by default; the handle
+    // measures (LineLoop), and starts again when the layout is new or the camera starts to move.
     const int guess = t->nranks < (uint32_t)VF_GROUPS_MAX_RANKS ? 1 : 0;
-    int pick = guess;
-    if (forced >= 0) pick = forced != 0;
-    else {
-        // probes that have completed (frames behind us: never a wait): every probed frame is a sample -- the time its kernels took on
-        // the draw stream.  (hipEventQuery's "not ready" is cleared below: the plan launches' errors were collected above.)
-        for (auto &g : t->gprobe)
-            if (g.pending && hipEventQuery(g.b) == hipSuccess) {
-                g.pending = false;
-                float ms = 0.0f;
-                if (g.epoch == t->g_epoch_id && hipEventElapsedTime(&ms, g.a, g.b) == hipSuccess && ms > 0.0f) {
-                    // the probe window's samples count alike; a later look weighs as much as all before it (the view may have drifted)
-                    const uint32_t n = ++t->g_n[g.variant];
-                    t->g_ms[g.variant] += (ms - t->g_ms[g.variant]) / (float)(n <= 8u ? n : 2u);
-                }
-            }
-        (void)hipGetLastError();
-        // what was measured belongs to another layout, or to the view before the camera started to move (a camera that keeps moving
-        // keeps its choice and is looked at again every kAgain frames)
-        if (t->frames_since_reset <= 1 || motion_starts) { t->g_epoch_frames = 0; t->g_epoch_id++; t->g_n[0] = t->g_n[1] = 0; t->g_ms[0] = t->g_ms[1] = 0.0f; }
-        // the plan settles for four frames on the default variant; then sixteen frames ABBA ABBA ABBA ABBA (both variants see the same
-        // mean position in the window: a drift of the frame cost -- the plan still settling, a camera under way -- cancels); then the
-        // faster one, looked at again now and then (four frames, ABBA)
-        const uint32_t e = t->g_epoch_frames++;
-        constexpr uint32_t kSettle = 4, kProbe = 16, kAgain = 128;
-        auto abba = [](uint32_t k) -> int { return (int)(((k & 3u) == 1u || (k & 3u) == 2u) ? 1u : 0u); };
-        if (e < kSettle) pick = guess;
-        else if (e < kSettle + kProbe) pick = guess ^ abba(e - kSettle);
-        else if (t->g_n[0] && t->g_n[1]) {
-            // (round 6: the default variant stays unless the other one measured CLEARLY faster, 3 %.  Where the choice matters the two are
-            //  5-17 % apart -- profiles/r06_line_loops.log -- but a probed frame carries two event records and reads 10 % high, and two
-            //  noisy means 0.01 % apart once made a C4 handle draw with the strip variant: 0.787 ms instead of 0.723)
-            pick = t->g_ms[guess ^ 1] < 0.97f * t->g_ms[guess] ? (guess ^ 1) : guess;
-            if (e % kAgain >= kAgain - 4u) pick ^= abba(e % kAgain - (kAgain - 4u)) ^ 1;      // B A A B seen from the variant in use: two frames of the other one
-        }
-        // (no samples yet -- a host that queues frames faster than the GPU draws them is past the window before its first probe
-        //  completes: the default stays until they arrive; they are taken whenever they complete)
-    }
-    t->groups_now = pick;
-    const bool groups = pick != 0;
-    // timed: the frames of the probe window (from the last settle frame on), and now and then two frames of each variant (one event each)
-    const uint32_t e_now = t->g_epoch_frames ? t->g_epoch_frames - 1u : 0u;
-    const bool probe = ntiles && forced < 0 && ((e_now >= 4u && e_now < 20u) || (e_now >= 20u && e_now % 128u >= 124u));
-    vf_terrain::GroupProbe *gp = nullptr;
-    if (probe) { gp = &t->gprobe[t->gprobe_head++ % 16]; if (gp->pending) gp = nullptr; }    // (ring full: the frame goes unmeasured)
-    if (gp && !gp->b && (hipEventCreate(&gp->a) != hipSuccess || hipEventCreate(&gp->b) != hipSuccess)) gp = nullptr;   // (made on first use: a one-shot handle never probes)
-    if (gp && (!gp->a || !gp->b)) gp = nullptr;
-    if (gp) (void)hipEventRecord(gp->a, s);
+    const LoopPick pick = t->loop.choose(guess, t->cursor.frames_since_reset <= 1 || K.motion_starts, ntiles != 0u);
+    const bool groups = pick.variant != 0;
+    LineLoop::Probe *gp = pick.probe ? t->loop.arm(s) : nullptr;
     if (ntiles) {
         uint32_t *vis = write_vis ? t->d_vis : nullptr;
         hipLaunchKernelGGL(k_clear, dim3(ntiles), dim3(256), 0, s, P, S.background, t->d_rgba, vis, stats, nstats, seg_count);
@@ -1438,14 +1431,13 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
 #define VF_TILE_ARGS P, V, S.row_ranges, S.cap_seg, S.cap_rad, t->d_lut, t->ctx->d_thresh, S.work_sorted, S.work_count, \
                      rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo
-        const bool fast = fast_shading(t);
+        const bool fast = fast_shading(t->inputs);
         // (the complete variant redraws the rare items that met a clipped primitive: always the plain loop)
 #define VF_TILE_LAUNCH(WV, FS)                                                                                         \
         do {                                                                                                           \
             if (groups) hipLaunchKernelGGL((k_tile<WV, false, FS, true>), per_cu, threads, 0, s, VF_TILE_ARGS);        \
             else hipLaunchKernelGGL((k_tile<WV, false, FS, false>), per_cu, threads, 0, s, VF_TILE_ARGS);              \
             hipLaunchKernelGGL((k_tile<WV, true, FS, false>), few, threads, 0, s, VF_TILE_ARGS);                       \
-            if (gp) { (void)hipEventRecord(gp->b, s); gp->variant = groups ? 1 : 0; gp->seq = e_now; gp->epoch = t->g_epoch_id; gp->pending = true; gp->valid = true; gp = nullptr; } \
         } while (0)
         if (write_vis && fast) VF_TILE_LAUNCH(true, true);
         else if (write_vis) VF_TILE_LAUNCH(true, false);
@@ -1453,9 +1445,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         else VF_TILE_LAUNCH(false, false);
 #undef VF_TILE_LAUNCH
 #undef VF_TILE_ARGS
+        if (gp) t->loop.close(gp, s);
     }
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
-    if (timing_now) { VF_HIP_TRY(hipEventRecord(ev[3], s)); t->timed_frames++; }
+    if (timing_now) { VF_HIP_TRY(hipEventRecord(ev.end, s)); t->timed_frames++; }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
         const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
         const int orc = overlay_pass(t, s, P, V);
@@ -1463,11 +1456,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     }
     VF_HIP_TRY(hipEventRecord(S.drawn, s));
     VF_HIP_TRY(hipGetLastError());
-    std::memcpy(S.u_used, t->u, sizeof S.u_used);           // the camera this set's tile times (being measured now) belong to
+    std::memcpy(S.u_used, t->inputs.u, sizeof S.u_used);           // the camera this set's tile times (being measured now) belong to
     S.have_u_used = true;
     t->last_stream = s;
     t->last_set = set;
-    t->last_out = t->d_rgba;
     t->rendered = true;
     return VF_OK;
 }
@@ -1476,12 +1468,13 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
 static void plan_ahead(vf_terrain *t, hipStream_t s)
 {
     vf_terrain::PrePlan &R = t->pre;
-    R.cur_set = t->cur_set; R.frame_no = t->frame_no; R.frames_since_reset = t->frames_since_reset;
-    R.camera_moving = t->camera_moving; R.was_moving = t->was_moving; R.have_drawn = t->have_drawn;
-    std::memcpy(R.u_drawn, t->u_drawn, sizeof R.u_drawn);
-    if (plan_frame(t, s, R.K, true) == VF_OK) { R.valid = true; R.gen = t->inputs_gen; }
+    R.before = t->cursor;
+    if (plan_frame(t, s, R.K) == VF_OK) { R.valid = true; R.gen = t->inputs_gen; }
     else {                                                  // (a failed launch: the next call plans for itself and reports it)
-        t->cur_set = R.cur_set; t->frame_no = R.frame_no; t->frames_since_reset = R.frames_since_reset;
+        // (the whole cursor goes back, though only cur_set, frame_no and frames_since_reset can have moved: a plan is made ahead for a
+        //  camera at rest only -- neither moving nor was_moving, a frame drawn, u_drawn equal to the live uniforms -- and plan_frame
+        //  leaves the other four fields of such a cursor as they were)
+        t->cursor = R.before;
         (void)hipGetLastError();
     }
 }
@@ -1532,7 +1525,7 @@ static int render_impl(vf_terrain *t, hipStream_t s, bool write_vis)
         }
         else { t->pre.valid = true; VF_HIP_TRY(drop_preplan(t, s)); }     // made for other inputs
     }
-    if (!planned) { const int rc = plan_frame(t, s, K, false, streaming); if (rc != VF_OK) return rc; }
+    if (!planned) { const int rc = plan_frame(t, s, K, streaming); if (rc != VF_OK) return rc; }
     const bool again = t->last_drawn_gen == t->inputs_gen;      // the frame before this one was drawn from the same inputs
     const int rc = draw_frame(t, s, K, write_vis);
     if (rc != VF_OK) return rc;
@@ -1541,11 +1534,19 @@ static int render_impl(vf_terrain *t, hipStream_t s, bool write_vis)
     // the next frame's plan goes out now
     // (round 6: also for a caller that streams frames of a resting camera -- its next plan goes out one call early, which changes nothing while
     //  the frames keep coming and has the plan ready for the first frame after it has waited once)
-    if (again && (idle_at_entry || t->side) && !write_vis && !t->bounds_dirty && !t->camera_moving && !t->was_moving && t->frames_since_reset > vf_terrain::kPlanStates && !(t->timing && t->stats_on)) {
+    if (again && (idle_at_entry || t->side) && !write_vis && !t->bounds_dirty && !t->cursor.camera_moving && !t->cursor.was_moving && t->cursor.frames_since_reset > vf_terrain::kPlanStates && !(t->timing && t->stats_on)) {
         if (t->side) plan_ahead(t, s);                      // on the plan streams, under this frame's tile kernel
         else t->preplan_pending = true;                     // no plan streams (a waiting caller): behind the next read-back's copy, flush_preplan
     }
     return VF_OK;
+}
+
+// a frame for the caller: the inputs it is drawn from are what the diagnostics render again (render_visibility)
+static int render_recorded(vf_terrain *t, hipStream_t s)
+{
+    t->drawn_inputs = t->inputs;
+    t->have_frame = true;
+    return render_impl(t, s, false);
 }
 
 int vf_terrain_render(vf_terrain *t, void *stream)
@@ -1553,10 +1554,7 @@ int vf_terrain_render(vf_terrain *t, void *stream)
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    std::memcpy(t->u_frame, t->u, sizeof t->u_frame);
-    t->shade_mode_frame = t->shade_mode; t->precision_frame = t->precision;
-    t->have_frame = true;
-    return render_impl(t, stream ? (hipStream_t)stream : t->ctx->stream, false);
+    return render_recorded(t, stream ? (hipStream_t)stream : t->ctx->stream);
 }
 
 int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, void *const *dev_rgba, void *stream)
@@ -1566,14 +1564,11 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
         if (dev_rgba && !dev_rgba[k]) return fail(VF_ERR_INVALID, "dev_rgba holds a NULL output buffer");
-        if (!t->have_uniforms || std::memcmp(t->u, uniforms + 44u * k, sizeof t->u) != 0) t->inputs_gen++;
-        std::memcpy(t->u, uniforms + 44u * k, sizeof t->u);
+        if (!t->have_uniforms || std::memcmp(t->inputs.u, uniforms + 44u * k, sizeof t->inputs.u) != 0) t->inputs_gen++;
+        std::memcpy(t->inputs.u, uniforms + 44u * k, sizeof t->inputs.u);
         t->have_uniforms = true;
         if (dev_rgba) t->d_rgba = (uint32_t *)dev_rgba[k];
-        std::memcpy(t->u_frame, t->u, sizeof t->u_frame);
-        t->shade_mode_frame = t->shade_mode; t->precision_frame = t->precision;
-        t->have_frame = true;
-        const int rc = render_impl(t, s, false);
+        const int rc = render_recorded(t, s);
         if (rc != VF_OK) return rc;
     }
     return VF_OK;
@@ -1633,20 +1628,19 @@ static int render_visibility(vf_terrain *t)
     int rc = vf_terrain_sync(t);
     if (rc != VF_OK) return rc;
     VF_HIP_TRY(sync_sides(t));
-    float u_now[44], u_drawn[32];
-    std::memcpy(u_now, t->u, sizeof u_now); std::memcpy(u_drawn, t->u_drawn, sizeof u_drawn);
+    const FrameInputs inputs_now = t->inputs;
+    PlanCursor cursor_now = t->cursor;
     uint32_t *const out_now = t->d_rgba;
     const hipStream_t stream_now = t->last_stream;
-    const bool timing = t->timing, have_drawn = t->have_drawn, moving = t->camera_moving, was_moving = t->was_moving;
-    const uint32_t mode_now = t->shade_mode, prec_now = t->precision, since = t->frames_since_reset;
-    const bool rendered = t->rendered;
-    if (t->have_frame) { std::memcpy(t->u, t->u_frame, sizeof t->u); t->shade_mode = t->shade_mode_frame; t->precision = t->precision_frame; }
+    const bool timing = t->timing, rendered = t->rendered;
+    if (t->have_frame) t->inputs = t->drawn_inputs;
     t->d_rgba = t->d_rgba_scratch; t->timing = false;
     rc = render_impl(t, t->ctx->stream, true);
     hipError_t e = hipStreamSynchronize(t->ctx->stream);
-    std::memcpy(t->u, u_now, sizeof u_now); std::memcpy(t->u_drawn, u_drawn, sizeof u_drawn);
-    t->d_rgba = out_now; t->last_stream = stream_now; t->timing = timing; t->have_drawn = have_drawn;
-    t->camera_moving = moving; t->was_moving = was_moving; t->shade_mode = mode_now; t->precision = prec_now; t->frames_since_reset = since;
+    t->inputs = inputs_now;
+    cursor_now.cur_set = t->cursor.cur_set; cursor_now.frame_no = t->cursor.frame_no;      // (the plan state and the frame number it used stay used, see above)
+    t->cursor = cursor_now;
+    t->d_rgba = out_now; t->last_stream = stream_now; t->timing = timing;
     t->rendered = rendered;                                 // the diagnostic frame went to scratch buffers: the caller's output is as it was
     if (rc != VF_OK) return rc;
     if (e != hipSuccess) return fail(VF_ERR_HIP, std::string("visibility render: ") + hipGetErrorString(e));
@@ -1977,7 +1971,7 @@ int vf_terrain_add_contours(vf_terrain *t, const float *levels, uint32_t nlevels
     if (e == hipSuccess) e = C.total.reserve(1, 1);
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("contour allocation failed: ") + hipGetErrorString(e));
     VF_HIP_TRY(hipMemcpyAsync(C.levels.p, levels, nlevels * sizeof(float), hipMemcpyHostToDevice, s));
-    const CtGrid G = { t->n - 1u, t->nb, (2.0f * 1.5f) / ((float)t->n - 1.0f), std::fmax(t->u[36], 1e-8f), t->d_hblk, t->d_bounds, C.levels.p, nlevels };
+    const CtGrid G = { t->n - 1u, t->nb, (2.0f * 1.5f) / ((float)t->n - 1.0f), std::fmax(t->inputs.u[36], 1e-8f), t->d_hblk, t->d_bounds, C.levels.p, nlevels };
     hipLaunchKernelGGL(k_ct_count, dim3(t->nblocks), dim3(64), 0, s, G, C.count.p);
     VF_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_ct_scan, dim3(1), dim3(1024), 0, s, t->nblocks, C.count.p, C.total.p);
@@ -2171,13 +2165,9 @@ int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment
     uint32_t redo = 0;                                      // did the frame hold clipped / oversized primitives?  (normally not)
     hipError_t err = hipMemcpy(&redo, t->ps[t->last_set].work_count + 3, sizeof redo, hipMemcpyDeviceToHost);
     FrameParams P;
-    float u_now[44];
-    std::memcpy(u_now, t->u, sizeof u_now);
-    const uint32_t mode_now = t->shade_mode, prec_now = t->precision;
-    if (t->have_frame) { std::memcpy(t->u, t->u_frame, sizeof t->u); t->shade_mode = t->shade_mode_frame; t->precision = t->precision_frame; }
-    build_params(t, P);
-    const bool fast = fast_shading(t);
-    std::memcpy(t->u, u_now, sizeof u_now); t->shade_mode = mode_now; t->precision = prec_now;
+    const FrameInputs &in = t->have_frame ? t->drawn_inputs : t->inputs;     // the frame render_visibility has just drawn again
+    build_params(t, in, P);
+    const bool fast = fast_shading(in);
     hipStream_t s = t->ctx->stream;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (err == hipSuccess) err = hipEventCreate(&e0);
@@ -2253,7 +2243,7 @@ int vf_terrain_debug_phase_cycles(vf_terrain *t, uint64_t *dst, uint32_t n)
     int rc = vf_terrain_sync(t);
     if (rc != VF_OK) return rc;
     if (n > kPhaseSlots) n = kPhaseSlots;
-    VF_HIP_TRY(hipMemcpy(dst, t->d_stats + 4 + 4 * ((size_t)t->ntx * t->nty + kSplitBudget), n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    VF_HIP_TRY(hipMemcpy(dst, t->d_stats + stats_layout(t).phases, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return VF_OK;
 #endif
 }
@@ -2261,9 +2251,9 @@ int vf_terrain_debug_phase_cycles(vf_terrain *t, uint64_t *dst, uint32_t n)
 int vf_terrain_enable_timing(vf_terrain *t, int enable)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    if (enable != 0 && !t->ev[0][0]) {                      // the event ring is made when timing is first asked for
+    if (enable != 0 && !t->ev[0].begin) {                   // the event ring is made when timing is first asked for
         VF_HIP_TRY(hipSetDevice(t->ctx->device));
-        for (auto &f : t->ev) for (auto &e : f) VF_HIP_TRY(hipEventCreate(&e));
+        for (auto &f : t->ev) { VF_HIP_TRY(hipEventCreate(&f.begin)); VF_HIP_TRY(hipEventCreate(&f.end)); }
     }
     if (enable != 0) for (auto &S : t->ps) for (auto &e : S.pev) if (!e) VF_HIP_TRY(hipEventCreate(&e));
     if (enable < 0 || enable > 3) return fail(VF_ERR_INVALID, "enable must be 0 .. 3");
@@ -2286,8 +2276,8 @@ int vf_terrain_timings(vf_terrain *t, vf_timings *out)
     uint32_t nplan = 0;
     for (uint32_t f = 0; f < nf; ++f) {
         float c = 0;
-        VF_HIP_TRY(hipEventSynchronize(t->ev[f][3]));
-        VF_HIP_TRY(hipEventElapsedTime(&c, t->ev[f][4], t->ev[f][3]));      // clear + tile kernels, on the caller's stream
+        VF_HIP_TRY(hipEventSynchronize(t->ev[f].end));
+        VF_HIP_TRY(hipEventElapsedTime(&c, t->ev[f].begin, t->ev[f].end));      // clear + tile kernels, on the caller's stream
         tile += c; total += c;
     }
     // the plan chain: the last plan of each plan state (the frames drawn last, or the plan queued ahead of the next call)
@@ -2301,7 +2291,7 @@ int vf_terrain_timings(vf_terrain *t, vf_timings *out)
     }
     if (nf == 1u && t->ps[t->last_set].pev_valid) {         // a single timed frame: plan start -> RGBA8 complete
         float d = 0;
-        if (hipEventElapsedTime(&d, t->ps[t->last_set].pev[0], t->ev[0][3]) == hipSuccess && d > 0.0f) total = d;
+        if (hipEventElapsedTime(&d, t->ps[t->last_set].pev[0], t->ev[0].end) == hipSuccess && d > 0.0f) total = d;
         else (void)hipGetLastError();
     }
     out->ranges_ms = nplan ? (float)(ranges / nplan) : 0.0f; out->plan_ms = nplan ? (float)(plan / nplan) : 0.0f; out->tile_ms = (float)(tile / nf);
@@ -2309,7 +2299,7 @@ int vf_terrain_timings(vf_terrain *t, vf_timings *out)
     if (nf >= 2 && t->timed_frames <= (uint32_t)vf_terrain::kTimingRing) {
         // frames rendered back to back overlap (frame f+1 plans while frame f draws): the frame period is what a frame costs
         float span = 0;
-        VF_HIP_TRY(hipEventElapsedTime(&span, t->ev[0][3], t->ev[nf - 1][3]));
+        VF_HIP_TRY(hipEventElapsedTime(&span, t->ev[0].end, t->ev[nf - 1].end));
         out->total_ms = span / (float)((nf - 1) * t->timing_every);
     }
     out->frames = nf;
@@ -2320,7 +2310,7 @@ int vf_terrain_timings(vf_terrain *t, vf_timings *out)
         VF_HIP_TRY(hipMemcpy(c, t->d_stats, sizeof c, hipMemcpyDeviceToHost));
         out->blocks_rasterised = c[0];   // distinct blocks behind those pairs (last frame): the bitmap behind the per-item statistics
         std::vector<uint32_t> bits((t->nblocks + 31) / 32);
-        VF_HIP_TRY(hipMemcpy(bits.data(), t->d_stats + 4 + 4 * ((size_t)t->ntx * t->nty + kSplitBudget) + 2 * kPhaseSlots, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        VF_HIP_TRY(hipMemcpy(bits.data(), t->d_stats + stats_layout(t).block_bits, bits.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         uint32_t n = 0;
         for (uint32_t w : bits) n += (uint32_t)__builtin_popcount(w);
         out->blocks_distinct = n;
@@ -2338,12 +2328,12 @@ int vf_terrain_frame_times(vf_terrain *t, float *tile_ms, float *period_ms, uint
     const uint32_t nf = std::min(std::min(t->timed_frames, ring), max_frames);
     const uint32_t first = t->timed_frames - nf;            // frame numbers first .. timed_frames - 1 live in ring slot (number % ring)
     for (uint32_t k = 0; k < nf; ++k) {
-        hipEvent_t *e = t->ev[(first + k) % ring];
-        VF_HIP_TRY(hipEventSynchronize(e[3]));
-        if (tile_ms) VF_HIP_TRY(hipEventElapsedTime(&tile_ms[k], e[4], e[3]));
+        const vf_terrain::FrameEvents &e = t->ev[(first + k) % ring];
+        VF_HIP_TRY(hipEventSynchronize(e.end));
+        if (tile_ms) VF_HIP_TRY(hipEventElapsedTime(&tile_ms[k], e.begin, e.end));
         if (period_ms) {
             period_ms[k] = 0.0f;
-            if (k) { VF_HIP_TRY(hipEventElapsedTime(&period_ms[k], t->ev[(first + k - 1u) % ring][3], e[3])); period_ms[k] /= (float)t->timing_every; }
+            if (k) { VF_HIP_TRY(hipEventElapsedTime(&period_ms[k], t->ev[(first + k - 1u) % ring].end, e.end)); period_ms[k] /= (float)t->timing_every; }
         }
     }
     *count = nf;
