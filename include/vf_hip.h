@@ -447,6 +447,36 @@ typedef struct vf_fragment_timing {
 } vf_fragment_timing;
 int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment_timing *out);
 
+/* ---- geometry buffers: per-pixel depth, world position, normal and primitive id of a frame ----------
+ * Four planes, tightly packed, row-major:
+ *   depth      float32 (H, W)      view depth = clip w of the surface at the pixel centre; +inf on background
+ *   position   float32 (H, W, 3)   world (x, y, z) of the surface at the pixel centre; 0 on background
+ *   normal     float32 (H, W, 3)   unit geometric normal of the visible triangle in world space, n.y >= 0; 0 on background
+ *   primitive  uint32  (H, W)      the visibility id: primitive id + 1, 0 = background (what vf_terrain_read_visibility returns)
+ * Overlays never show in them.  The arithmetic is fixed bit for bit and does not follow
+ * vf_terrain_set_shade_precision.  All three calls describe the frame vf_terrain_render drew last (before the first render: the
+ * current uniforms) by drawing it again with the visibility store on, into scratch buffers: the caller's output buffer, the
+ * `rendered` state, timing and plan feedback stay as they were (the rule of vf_terrain_read_visibility).  Whole-frame handles
+ * only (VF_ERR_INVALID on a band- or tile-sharded handle).  A handle that never calls them allocates and launches nothing for them.
+ *
+ * vf_terrain_gbuffer_device: device destinations (e.g. a torch tensor's data_ptr); any may be NULL, at least one not; a NULL plane
+ * is not computed.  The planes are written asynchronously on `stream` (NULL: the context's stream); later calls on the handle are
+ * ordered behind that work by the library.
+ * vf_terrain_read_gbuffer: the same into host memory; returns when the planes are there.
+ * vf_terrain_pick: "what is under these pixels" -- n pixels (x, y) in, n records of eight 32-bit words out:
+ * {depth, x, y, z, nx, ny, nz, id}, the eighth word the id's bits as a uint32_t (not a converted float).  A pixel outside the
+ * frame is VF_ERR_INVALID, and nothing is written. */
+int vf_terrain_gbuffer_device(vf_terrain *t, float *dev_depth, float *dev_position, float *dev_normal, uint32_t *dev_primitive, void *stream);
+int vf_terrain_read_gbuffer(vf_terrain *t, float *depth, float *position, float *normal, uint32_t *primitive);
+int vf_terrain_pick(vf_terrain *t, const int32_t *pixels_xy, uint32_t n, float *out8);
+/* diagnostics: the average time (HIP events, ms) of `repeats` launches of the geometry-buffer kernel for the plane set `planes`
+ * (a combination of the bits below) on the frame rendered last, after one warm-up launch; nothing is read back. */
+#define VF_GBUFFER_DEPTH 1u
+#define VF_GBUFFER_POSITION 2u
+#define VF_GBUFFER_NORMAL 4u
+#define VF_GBUFFER_PRIMITIVE 8u
+int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repeats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

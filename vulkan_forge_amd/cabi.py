@@ -26,6 +26,7 @@ SYMBOLS = [
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
     "vf_terrain_debug_fragment_stage", "vf_host_alloc", "vf_host_free",
+    "vf_terrain_gbuffer_device", "vf_terrain_read_gbuffer", "vf_terrain_pick", "vf_terrain_debug_gbuffer_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -112,6 +113,10 @@ _PROTOS = {
     "vf_dist_gather_bands": (_i, [_vp, _vp, _i, _vp, _vp]),
     "vf_dist_exchange_bands": (_i, [_vp, _vp, _i, _vp, _vp]),
     "vf_terrain_debug_fragment_stage": (_i, [_vp, _u32, C.POINTER(FragmentTiming)]),
+    "vf_terrain_gbuffer_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vf_terrain_read_gbuffer": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "vf_terrain_pick": (_i, [_vp, _vp, _u32, _vp]),
+    "vf_terrain_debug_gbuffer_stage": (_i, [_vp, _u32, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -440,6 +445,35 @@ class Terrain:
         out = np.empty((self.local_rows(), self.W), np.uint32)
         self._check(self.lib.vf_terrain_read_visibility(self.t, out.ctypes.data))
         return out
+
+    def read_gbuffer(self, planes=("depth", "position", "normal", "primitive")):
+        """Geometry buffers of the frame rendered last: dict plane name -> array."""
+        from ._gbuffer import PLANES, plane_args
+        names = plane_args(planes)
+        out = {k: np.empty((self.H, self.W) + PLANES[k][1], PLANES[k][0]) for k in names}
+        ptr = [out[k].ctypes.data if k in out else None for k in PLANES]
+        self._check(self.lib.vf_terrain_read_gbuffer(self.t, *ptr))
+        return out
+
+    def gbuffer_device(self, depth=None, position=None, normal=None, primitive=None, stream=None):
+        """The same into device memory: each argument a device address (a torch tensor's data_ptr()) or None; asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_gbuffer_device(self.t, depth, position, normal, primitive, stream))
+
+    def pick(self, pixels):
+        """What is under the pixels (N, 2) of (x, y) of the frame rendered last: dict depth (N,), position (N, 3), normal (N, 3), primitive (N,)."""
+        from ._gbuffer import pick_result, pixel_args
+        px = pixel_args(pixels, self.W, self.H)
+        out = np.zeros((len(px), 8), np.uint32)
+        self._check(self.lib.vf_terrain_pick(self.t, px.ctypes.data, len(px), out.ctypes.data))
+        return pick_result(out)
+
+    def gbuffer_stage(self, planes=("depth",), repeats=50):
+        """The geometry-buffer kernel as timed launches of its own (diagnostics): average ms of `repeats` launches."""
+        from ._gbuffer import PLANES, plane_args
+        mask = sum(1 << list(PLANES).index(k) for k in plane_args(planes))
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_gbuffer_stage(self.t, mask, int(repeats), C.byref(ms)))
+        return ms.value
 
     def enable_timing(self, on=True, stats=True, sampled=False):
         """stats=False: HIP events only, the kernels run exactly as untimed (no per-item statistics; blocks_* read 0);

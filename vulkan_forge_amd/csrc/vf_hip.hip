@@ -3,6 +3,7 @@
 #include "../../include/vf_hip.h"
 #include "vf_kernels.h"
 #include "vf_overlay.h"     // (brings vf_contour.h)
+#include "vf_gbuffer.h"     // templates only, behind the last non-template kernel
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -350,6 +351,11 @@ struct vf_terrain {
     uint32_t *d_rgba = nullptr;
     uint32_t *d_vis = nullptr;           // only allocated for vf_terrain_read_visibility and for occluding overlay layers
     uint32_t *d_stats = nullptr;         // [0] (tile, block) pairs rasterised (stats_layout)
+    // geometry buffers: made by the first call that needs them, reused, grown when a call asks for more
+    uint8_t *d_gb = nullptr;             // device planes behind vf_terrain_read_gbuffer
+    size_t gb_bytes = 0;
+    uint8_t *d_pick = nullptr;           // vf_terrain_pick: n pixels in, n records out
+    size_t pick_bytes = 0;
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
     uint32_t *d_batch[kBatchRing] = { nullptr, nullptr, nullptr };
@@ -780,7 +786,8 @@ void vf_terrain_destroy(vf_terrain *t)
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
+    void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2],
+                     t->d_gb, t->d_pick };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -2215,6 +2222,162 @@ int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment
     (void)hipFree(d_out);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("fragment-stage diagnostics: ") + hipGetErrorString(err));
     out->resolve_ms = ms / (float)repeats; out->covered_pixels = covered; out->repeats = repeats; out->equal_to_frame = equal;
+    return VF_OK;
+}
+
+// ---- geometry buffers (vf_gbuffer.h) ---------------------------------------------------
+
+// The frame the three calls describe: drawn again with the visibility store on (render_visibility: d_vis and the set-up arrays of
+// t->last_set are complete when it returns), its parameters, and whether it held a clipped / oversized primitive.
+struct GbFrame { FrameParams P; SetupView V; bool clipped; };
+
+static int gb_frame(vf_terrain *t, GbFrame &F)
+{
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "geometry buffers need a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    const int rc = render_visibility(t);
+    if (rc != VF_OK) return rc;
+    uint32_t redo = 0;
+    VF_HIP_TRY(hipMemcpy(&redo, t->ps[t->last_set].work_count + 3, sizeof redo, hipMemcpyDeviceToHost));
+    build_params(t, t->have_frame ? t->drawn_inputs : t->inputs, F.P);
+    const vf_terrain::PlanState &S = t->ps[t->last_set];
+    F.V = { S.vtx, t->d_hblk, S.recs, S.gen };
+    F.clipped = redo != 0;
+    return VF_OK;
+}
+
+// persistent workgroups in a multiple of 8 (one share per XCD), four per CU: k_resolve's launch shape
+static dim3 gb_grid(const vf_terrain *t)
+{
+    const uint32_t cus = (uint32_t)std::max(8, t->ctx->prop.multiProcessorCount) / 8u * 8u;
+    const uint32_t per_cu = std::getenv("VF_GBUFFER_PER_CU") ? (uint32_t)std::max(1, std::atoi(std::getenv("VF_GBUFFER_PER_CU"))) : 4u;
+    return dim3(std::min<uint32_t>((((t->W + 31u) / 32u) * ((t->H + 7u) / 8u) + 7u) / 8u * 8u, cus * per_cu));
+}
+
+static void gb_launch(const vf_terrain *t, const GbFrame &F, const GbPlanes &O, hipStream_t s)
+{
+    if (F.clipped) hipLaunchKernelGGL((k_gbuffer<true>), gb_grid(t), dim3(256), 0, s, F.P, F.V, (const uint32_t *)t->d_vis, O);
+    else hipLaunchKernelGGL((k_gbuffer<false>), gb_grid(t), dim3(256), 0, s, F.P, F.V, (const uint32_t *)t->d_vis, O);
+}
+
+// Work queued on a stream of the caller's reads d_vis and the set-up arrays of t->last_set: that set's `drawn` event is recorded
+// again behind it, so whatever waits for the set before it is reused (plan_frame) or for the frame before (draw_frame on another
+// stream) waits for this too, and the handle's own streams are ordered behind it.
+static hipError_t gb_order_after(vf_terrain *t, hipStream_t s)
+{
+    hipEvent_t ev = t->ps[t->last_set].drawn;
+    hipError_t e = hipEventRecord(ev, s);
+    if (e == hipSuccess && t->last_stream && t->last_stream != s) e = hipStreamWaitEvent(t->last_stream, ev, 0);
+    if (e == hipSuccess && t->ctx->stream != s) e = hipStreamWaitEvent(t->ctx->stream, ev, 0);
+    return e;
+}
+
+int vf_terrain_gbuffer_device(vf_terrain *t, float *dev_depth, float *dev_position, float *dev_normal, uint32_t *dev_primitive, void *stream)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!dev_depth && !dev_position && !dev_normal && !dev_primitive) return fail(VF_ERR_INVALID, "no plane requested");
+    GbFrame F;
+    const int rc = gb_frame(t, F);
+    if (rc != VF_OK) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    gb_launch(t, F, GbPlanes{ dev_depth, dev_position, dev_normal, dev_primitive }, s);
+    VF_HIP_TRY(hipGetLastError());
+    VF_HIP_TRY(gb_order_after(t, s));
+    return VF_OK;
+}
+
+// scratch of the handle, grown to `bytes`
+static int gb_scratch(uint8_t *&buf, size_t &have, size_t bytes)
+{
+    if (have >= bytes) return VF_OK;
+    if (buf) { (void)hipFree(buf); buf = nullptr; have = 0; }
+    if (hipMalloc(&buf, bytes) != hipSuccess) { buf = nullptr; (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "geometry-buffer allocation failed"); }
+    have = bytes;
+    return VF_OK;
+}
+
+int vf_terrain_read_gbuffer(vf_terrain *t, float *depth, float *position, float *normal, uint32_t *primitive)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!depth && !position && !normal && !primitive) return fail(VF_ERR_INVALID, "no plane requested");
+    GbFrame F;
+    int rc = gb_frame(t, F);
+    if (rc != VF_OK) return rc;
+    const size_t npx = (size_t)t->W * t->H;
+    void *const host[4] = { depth, position, normal, primitive };
+    const size_t words[4] = { 1, 3, 3, 1 };
+    size_t off[4], total = 0;
+    for (int k = 0; k < 4; ++k) { off[k] = total; if (host[k]) total += npx * words[k] * 4; }
+    rc = gb_scratch(t->d_gb, t->gb_bytes, total);
+    if (rc != VF_OK) return rc;
+    auto dev = [&](int k) -> void * { return host[k] ? t->d_gb + off[k] : nullptr; };
+    hipStream_t s = t->ctx->stream;
+    gb_launch(t, F, GbPlanes{ (float *)dev(0), (float *)dev(1), (float *)dev(2), (uint32_t *)dev(3) }, s);
+    VF_HIP_TRY(hipGetLastError());
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) VF_HIP_TRY(hipMemcpyAsync(host[k], dev(k), npx * words[k] * 4, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));
+    return VF_OK;
+}
+
+int vf_terrain_pick(vf_terrain *t, const int32_t *pixels_xy, uint32_t n, float *out8)
+{
+    if (!t || (n && (!pixels_xy || !out8))) return fail(VF_ERR_INVALID, "NULL argument");
+    for (uint32_t k = 0; k < n; ++k)
+        if (pixels_xy[2 * k] < 0 || pixels_xy[2 * k + 1] < 0 || (uint32_t)pixels_xy[2 * k] >= t->W || (uint32_t)pixels_xy[2 * k + 1] >= t->H)
+            return fail(VF_ERR_INVALID, "pixel " + std::to_string(k) + " (" + std::to_string(pixels_xy[2 * k]) + ", " + std::to_string(pixels_xy[2 * k + 1]) +
+                                        ") lies outside the " + std::to_string(t->W) + " x " + std::to_string(t->H) + " frame");
+    GbFrame F;
+    int rc = gb_frame(t, F);
+    if (rc != VF_OK || n == 0) return rc;
+    const size_t in_bytes = ((size_t)n * 8 + 31) / 32 * 32, out_bytes = (size_t)n * sizeof(GbPixel);
+    rc = gb_scratch(t->d_pick, t->pick_bytes, in_bytes + out_bytes);
+    if (rc != VF_OK) return rc;
+    hipStream_t s = t->ctx->stream;
+    const int2 *d_in = (const int2 *)t->d_pick;
+    GbPixel *d_out = (GbPixel *)(t->d_pick + in_bytes);
+    VF_HIP_TRY(hipMemcpyAsync(t->d_pick, pixels_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    const dim3 grid((n + 255u) / 256u);
+    if (F.clipped) hipLaunchKernelGGL((k_gbuffer_pick<true>), grid, dim3(256), 0, s, F.P, F.V, (const uint32_t *)t->d_vis, d_in, n, d_out);
+    else hipLaunchKernelGGL((k_gbuffer_pick<false>), grid, dim3(256), 0, s, F.P, F.V, (const uint32_t *)t->d_vis, d_in, n, d_out);
+    VF_HIP_TRY(hipGetLastError());
+    VF_HIP_TRY(hipMemcpyAsync(out8, d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));
+    return VF_OK;
+}
+
+int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!(planes & 15u) || (planes & ~15u)) return fail(VF_ERR_INVALID, "planes: a non-empty combination of VF_GBUFFER_DEPTH / _POSITION / _NORMAL / _PRIMITIVE");
+    if (repeats == 0) repeats = 1;
+    GbFrame F;
+    int rc = gb_frame(t, F);
+    if (rc != VF_OK) return rc;
+    const size_t npx = (size_t)t->W * t->H;
+    const size_t words[4] = { 1, 3, 3, 1 };
+    size_t off[4], total = 0;
+    for (int k = 0; k < 4; ++k) { off[k] = total; if (planes & (1u << k)) total += npx * words[k] * 4; }
+    rc = gb_scratch(t->d_gb, t->gb_bytes, total);
+    if (rc != VF_OK) return rc;
+    auto dev = [&](int k) -> void * { return (planes & (1u << k)) ? t->d_gb + off[k] : nullptr; };
+    const GbPlanes O{ (float *)dev(0), (float *)dev(1), (float *)dev(2), (uint32_t *)dev(3) };
+    hipStream_t s = t->ctx->stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t err = hipEventCreate(&e0);
+    if (err == hipSuccess) err = hipEventCreate(&e1);
+    if (err == hipSuccess) { gb_launch(t, F, O, s); err = hipGetLastError(); }     // warm-up launch
+    if (err == hipSuccess) err = hipEventRecord(e0, s);
+    for (uint32_t k = 0; k < repeats && err == hipSuccess; ++k) { gb_launch(t, F, O, s); err = hipGetLastError(); }
+    if (err == hipSuccess) err = hipEventRecord(e1, s);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float total_ms = 0.0f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&total_ms, e0, e1);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("geometry-buffer diagnostics: ") + hipGetErrorString(err));
+    *ms = total_ms / (float)repeats;
     return VF_OK;
 }
 

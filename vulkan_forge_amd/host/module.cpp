@@ -237,12 +237,14 @@ public:
         uint32_t h = (uint32_t)arr.shape(0), w = (uint32_t)arr.shape(1);
         Borrow b(busy);
         check(vf_terrain_set_height(t, static_cast<const float *>(arr.data()), w, h));
+        frame_current = false;
     }
 
     void render_into(uint8_t *dst, uint32_t rows)          // caller holds the borrow
     {
         py::gil_scoped_release nogil;
         int rc = vf_terrain_render(t, nullptr);
+        frame_current = rc == VF_OK;
         if (rc == VF_OK) rc = vf_terrain_read_rgba(t, dst, 0, rows);
         if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
     }
@@ -272,6 +274,7 @@ public:
         const uint8_t *scan = nullptr;
         size_t nbytes = 0;
         int rc = vf_terrain_render(t, nullptr);
+        frame_current = rc == VF_OK;
         if (rc == VF_OK) rc = vf_terrain_read_png_scanlines(t, &scan, &nbytes);
         if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
         write_png_scanlines(path, scan, W, H);
@@ -399,7 +402,7 @@ public:
         return a;
     }
     // extension: multi-GPU band ownership (DESIGN.md "Sharding")
-    void set_shard(uint32_t rank, uint32_t nranks, uint32_t band_h) { Borrow b(busy); check(vf_terrain_set_shard(t, rank, nranks, band_h)); }
+    void set_shard(uint32_t rank, uint32_t nranks, uint32_t band_h) { Borrow b(busy); check(vf_terrain_set_shard(t, rank, nranks, band_h)); frame_current = false; }
     // extension: "reference" = fs_main as coded; "spec_t32" = the documented-only stage (forward-difference normals + Reinhard)
     void set_shade_mode(const std::string &mode)
     {
@@ -514,6 +517,61 @@ public:
     }
     void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
 
+    // extension: geometry buffers -- per-pixel depth, world position, normal and primitive id (argument rules:
+    // vulkan_forge_amd/_gbuffer.py).  Like render_rgba they describe the frame for the current uniforms: it is drawn first unless the
+    // frame this object drew last already is that frame.
+    py::dict render_gbuffer(py::object planes)
+    {
+        py::tuple names = py::module_::import("vulkan_forge_amd._gbuffer").attr("plane_args")(planes);
+        Borrow b(busy);
+        py::dict out;
+        float *f[3] = { nullptr, nullptr, nullptr };
+        uint32_t *prim = nullptr;
+        for (py::handle h : names) {
+            const std::string k = h.cast<std::string>();
+            if (k == "primitive") { py::array_t<uint32_t> a({ (py::ssize_t)H, (py::ssize_t)W }); prim = a.mutable_data(); out[h] = a; continue; }
+            const int slot = k == "depth" ? 0 : (k == "position" ? 1 : 2);
+            py::array_t<float> a = slot == 0 ? py::array_t<float>({ (py::ssize_t)H, (py::ssize_t)W })
+                                             : py::array_t<float>({ (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)3 });
+            f[slot] = a.mutable_data(); out[h] = a;
+        }
+        {
+            py::gil_scoped_release nogil;
+            int rc = draw_current();
+            if (rc == VF_OK) rc = vf_terrain_read_gbuffer(t, f[0], f[1], f[2], prim);
+            if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        }
+        return out;
+    }
+    py::array_t<float> render_depth()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)H, (py::ssize_t)W });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        int rc = draw_current();
+        if (rc == VF_OK) rc = vf_terrain_read_gbuffer(t, dst, nullptr, nullptr, nullptr);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::dict pick(py::object pixels)
+    {
+        py::module_ rules = py::module_::import("vulkan_forge_amd._gbuffer");
+        py::array px = rules.attr("pixel_args")(pixels, W, H).cast<py::array>();
+        const uint32_t count = (uint32_t)px.shape(0);
+        Borrow b(busy);
+        py::array_t<uint32_t> words({ (py::ssize_t)count, (py::ssize_t)8 });
+        {
+            const int32_t *src = static_cast<const int32_t *>(px.data());
+            float *dst = reinterpret_cast<float *>(words.mutable_data());
+            py::gil_scoped_release nogil;
+            int rc = draw_current();
+            if (rc == VF_OK) rc = vf_terrain_pick(t, src, count, dst);
+            if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        }
+        return rules.attr("pick_result")(words).cast<py::dict>();
+    }
+
     // src/terrain/mod.rs:537-546
     py::array_t<float> debug_uniforms_f32() const
     {
@@ -529,7 +587,16 @@ private:
     {
         last = to_uniforms(globals, view, proj);
         check(vf_terrain_set_uniforms(t, last.data()));
+        frame_current = false;
     }
+    int draw_current()                                      // caller holds the borrow
+    {
+        if (frame_current) return VF_OK;
+        const int rc = vf_terrain_render(t, nullptr);
+        frame_current = rc == VF_OK;
+        return rc;
+    }
+    bool frame_current = false;                             // the frame vf_terrain_render drew last was drawn from the current uniforms and heights
     uint32_t W, H, n = 128;
     vf_terrain *t = nullptr;
     Globals globals;
@@ -822,7 +889,10 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              py::arg("join") = "round", py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
         .def("height_bounds", &T::height_bounds)
         .def("layer_primitive_count", &T::layer_primitive_count, py::arg("layer"))
-        .def("clear_overlays", &T::clear_overlays);
+        .def("clear_overlays", &T::clear_overlays)
+        .def("render_gbuffer", &T::render_gbuffer, py::arg("planes") = py::make_tuple("depth", "position", "normal", "primitive"))
+        .def("render_depth", &T::render_depth)
+        .def("pick", &T::pick, py::arg("pixels"));
 }
 
 } // namespace
