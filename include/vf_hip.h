@@ -477,6 +477,38 @@ int vf_terrain_pick(vf_terrain *t, const int32_t *pixels_xy, uint32_t n, float *
 #define VF_GBUFFER_PRIMITIVE 8u
 int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repeats, float *ms);
 
+/* ---- cast sun shadows on the terrain -----------------------------------------------------------------
+ * The shadow field is one float32 per grid vertex, (grid, grid) row-major (row j = z index, column i = x index): lit in [0, 1],
+ * 1 = the sun reaches the vertex, 1 - strength = fully shadowed.  It comes from the displaced heights the renderer draws and the
+ * sun of the uniforms (u[32..34]) by a horizon scan along sheared grid lines; `bias` (the excess of the horizon over the vertex
+ * that is still lit) and `softness` (the excess over which lit falls to 1 - strength) are in world height units.  The arithmetic
+ * is fixed bit for bit.  The field is computed by the first shadowed frame or field call that needs it and again
+ * only after the heights, the sun, spacing, exaggeration or these parameters have changed.
+ *
+ * vf_terrain_set_shadows: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then writes
+ * again every covered pixel whose interpolated lit is below 1: fs_main with lambert * lit, always in the exact arithmetic, whatever
+ * vf_terrain_set_shade_precision says (both shade modes).  Other pixels keep the frame's bytes.  Overlays composite afterwards
+ * and are not shadowed; geometry buffers and the diagnostics frames are unaffected.  strength in [0, 1], softness > 0, bias >= 0,
+ * all finite, else VF_ERR_INVALID and nothing changes.  Whole-frame handles only: enabling on a band- or tile-sharded handle,
+ * sharding a handle with shadows enabled, and vf_terrain_render_batch / _batch_host on a handle with shadows enabled are
+ * VF_ERR_INVALID and change nothing.  The parameters are stored also with enable == 0 (the field calls below use them).
+ * A handle that never calls any of these allocates and launches nothing for them.
+ * vf_terrain_read_shadow_field: the field for the current heights, uniforms and parameters into host memory (grid * grid
+ * floats), whether or not shadows are enabled for drawing.
+ * vf_terrain_shadow_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream);
+ * later calls on the handle are ordered behind the copy by the library. */
+#define VF_SHADOW_STRENGTH 0.7f
+#define VF_SHADOW_SOFTNESS 0.02f
+#define VF_SHADOW_BIAS 0.002f
+int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float softness, float bias);
+int vf_terrain_read_shadow_field(vf_terrain *t, float *lit);
+int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream);
+/* diagnostics: ms[0] the average time (HIP events) of `repeats` computations of the field, ms[1] of `repeats` shade passes, for the
+ * frame rendered last (drawn again into scratch buffers), each after one warm-up; and how many times the handle has computed its
+ * field so far (the diagnostic launches are not counted). */
+int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
+int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,8 @@ SYMBOLS = [
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
     "vf_terrain_debug_fragment_stage", "vf_host_alloc", "vf_host_free",
     "vf_terrain_gbuffer_device", "vf_terrain_read_gbuffer", "vf_terrain_pick", "vf_terrain_debug_gbuffer_stage",
+    "vf_terrain_set_shadows", "vf_terrain_read_shadow_field", "vf_terrain_shadow_field_device", "vf_terrain_debug_shadow_stage",
+    "vf_terrain_debug_shadow_scans",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -117,6 +119,11 @@ _PROTOS = {
     "vf_terrain_read_gbuffer": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "vf_terrain_pick": (_i, [_vp, _vp, _u32, _vp]),
     "vf_terrain_debug_gbuffer_stage": (_i, [_vp, _u32, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_shadows": (_i, [_vp, _i, _f, _f, _f]),
+    "vf_terrain_read_shadow_field": (_i, [_vp, _vp]),
+    "vf_terrain_shadow_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_debug_shadow_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_debug_shadow_scans": (_i, [_vp, C.POINTER(_u32)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -474,6 +481,35 @@ class Terrain:
         ms = _f()
         self._check(self.lib.vf_terrain_debug_gbuffer_stage(self.t, mask, int(repeats), C.byref(ms)))
         return ms.value
+
+    def set_shadows(self, enabled=True, *, strength=0.7, softness=0.02, bias=0.002):
+        """Cast sun shadows on the terrain.  The three parameters are stored by every call, also one that disables, and
+        steer shadow_field() too: set_shadows(False) without them puts the defaults back."""
+        from ._shadows import shadow_args
+        self._check(self.lib.vf_terrain_set_shadows(self.t, *shadow_args(enabled, strength, softness, bias)))
+
+    def shadow_field(self):
+        """The shadow field for the current heights, uniforms and parameters: (grid, grid) float32, lit in [0, 1]."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_shadow_field(self.t, out.ctypes.data))
+        return out
+
+    def shadow_field_device(self, dev_lit, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_shadow_field_device(self.t, dev_lit, stream))
+
+    def shadow_stage(self, repeats=20):
+        """(scan ms, shade-pass ms) of the frame rendered last, as timed launches of their own (diagnostics)."""
+        ms = (_f * 2)()
+        self._check(self.lib.vf_terrain_debug_shadow_stage(self.t, int(repeats), ms))
+        return ms[0], ms[1]
+
+    def shadow_scans(self):
+        """How many times the handle has computed its shadow field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_shadow_scans(self.t, C.byref(n)))
+        return n.value
 
     def enable_timing(self, on=True, stats=True, sampled=False):
         """stats=False: HIP events only, the kernels run exactly as untimed (no per-item statistics; blocks_* read 0);

@@ -4,6 +4,7 @@
 #include "vf_kernels.h"
 #include "vf_overlay.h"     // (brings vf_contour.h)
 #include "vf_gbuffer.h"     // templates only, behind the last non-template kernel
+#include "vf_shadow.h"      // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -356,6 +357,20 @@ struct vf_terrain {
     size_t gb_bytes = 0;
     uint8_t *d_pick = nullptr;           // vf_terrain_pick: n pixels in, n records out
     size_t pick_bytes = 0;
+    // cast shadows: buffers made by the first shadowed frame or field read; the field is computed again only when
+    // what it was made from has changed
+    struct Shadows {
+        bool enabled = false;
+        float strength = 0.7f, softness = 0.02f, bias = 0.002f;
+        float *d_lit = nullptr;          // n x n, row-major
+        float *d_cmax = nullptr;         // chunk maxima / carries of the scan: nchunks x nlines
+        size_t cmax_floats = 0;
+        bool valid = false;              // d_lit holds the field of `key` and heights generation `height_gen`
+        uint64_t height_gen = 0;
+        float key[8] = {};               // sun (3), spacing, exaggeration, strength, softness, bias
+        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_shadow_scans)
+    } sh;
+    uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
     uint32_t *d_batch[kBatchRing] = { nullptr, nullptr, nullptr };
@@ -787,7 +802,7 @@ void vf_terrain_destroy(vf_terrain *t)
     (void)hipSetDevice(t->ctx->device);
     (void)hipDeviceSynchronize();
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2],
-                     t->d_gb, t->d_pick };
+                     t->d_gb, t->d_pick, t->sh.d_lit, t->sh.d_cmax };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -825,6 +840,7 @@ int vf_terrain_set_uniforms(vf_terrain *t, const float uniforms[44])
 static int set_height_common(vf_terrain *t, uint32_t tw, uint32_t th)
 {
     t->inputs_gen++;
+    t->height_gen++;
     VF_HIP_TRY(drop_preplan(t));
     t->loop.reset();                                       // other heights: which line loop is faster is measured again
     bool resized = tw != t->tw || th != t->th;
@@ -935,6 +951,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!is_pow2(band_h) || band_h < (uint32_t)kTileH) return fail(VF_ERR_INVALID, "band_h must be a power of two >= 64 (the tile height)");
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
+    if (t->sh.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     VF_HIP_TRY(drop_preplan(t));
@@ -1056,6 +1073,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!layout_valid(skew)) return fail(VF_ERR_INVALID, "layout word is neither VF_TILE_LAYOUT(skew < 65536, stripe_log2 <= 15) nor a registered stripe map");
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
+    if (t->sh.enabled) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1399,10 +1417,13 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 
 // diag: a visibility / diagnostics frame (render_visibility): stores its visibility, composites no overlays.  A frame of a handle with an
 // occluding overlay layer stores its visibility too, for the overlay pass.
+static int shadow_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
     const FrameParams &P = K.P;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims);
+    const bool shadows = t->sh.enabled && !diag;           // (visibility / diagnostics frames: the frame as the tile kernel shades it)
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1456,6 +1477,11 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     }
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev.end, s)); t->timed_frames++; }
+    if (shadows && ntiles) {                               // cast shadows: behind the tile kernels, in front of the overlays
+        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
+        const int src = shadow_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        if (src != VF_OK) return src;
+    }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
         const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
         const int orc = overlay_pass(t, s, P, V);
@@ -1567,6 +1593,7 @@ int vf_terrain_render(vf_terrain *t, void *stream)
 int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, void *const *dev_rgba, void *stream)
 {
     if (!t || (!uniforms && n)) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1585,6 +1612,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
 {
     if (!t || !uniforms || !host_rgba) return fail(VF_ERR_INVALID, "NULL argument");
     if (t->shard_tiles || t->local_rows != t->H) return fail(VF_ERR_INVALID, "batch read-back needs the whole frame on one handle (pose-parallel ranks are replicas)");
+    if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2378,6 +2406,179 @@ int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repe
     if (e1) (void)hipEventDestroy(e1);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("geometry-buffer diagnostics: ") + hipGetErrorString(err));
     *ms = total_ms / (float)repeats;
+    return VF_OK;
+}
+
+// ---- cast shadows (vf_shadow.h) ---------------------------------------------------------
+
+// The frame of reference of the field for the uniforms `u`; false: every vertex is lit.  The ratios come
+// from the sun vector as given, not from the normalised one: they are free of scale, so the lines depend on the azimuth alone.
+static bool shadow_plan(const vf_terrain *t, const float *u, ShadowPlan &S)
+{
+    const vf_terrain::Shadows &H = t->sh;
+    const float sx = u[32], sy = u[33], sz = u[34];
+    const float ax = std::fabs(sx), az = std::fabs(sz);
+    const bool zmajor = az > ax;                              // a tie goes to x
+    const float amaj = zmajor ? az : ax, amin = zmajor ? ax : az;
+    const float smaj = zmajor ? sz : sx, smin = zmajor ? sx : sz;
+    if (!(amaj > 0.0f) || !std::isfinite(amaj) || !(amin <= amaj) || !std::isfinite(sy)) return false;
+    const float spacing = std::fmax(u[36], 1e-8f);
+    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    const float d = sy > 0.0f ? ((step * spacing) * sy) / amaj : 0.0f;
+    if (!std::isfinite(d)) return false;
+    S.n = t->n; S.nb = t->nb;
+    S.zmajor = zmajor ? 1u : 0u;
+    S.from_high = smaj > 0.0f ? 1u : 0u;
+    S.s = smin < 0.0f ? -1 : 1;
+    S.a = amin / amaj;
+    const int32_t R = (int32_t)std::rint((float)(t->n - 1u) * S.a);
+    S.c_lo = S.s > 0 ? 0 : -R;
+    S.nlines = t->n + (uint32_t)R;
+    S.nchunks = (t->n + kShChunk - 1u) / kShChunk;
+    S.d = d; S.exag = u[38]; S.strength = H.strength; S.softness = H.softness; S.bias = H.bias;
+    return true;
+}
+
+// d_lit holds the field of the uniforms `u`, the handle's heights and shadow parameters once the work queued on `s` is done.  The
+// displaced-height cache must be current and ordered before `s` (a frame's plan, ct_heights_current).  force: compute it anyway.
+static int shadow_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false)
+{
+    vf_terrain::Shadows &H = t->sh;
+    const size_t nv = (size_t)t->n * t->n;
+    if (!H.d_lit) {
+        if (hipMalloc(&H.d_lit, nv * sizeof(float)) != hipSuccess) { H.d_lit = nullptr; (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow field allocation failed"); }
+        H.valid = false;
+    }
+    const float key[8] = { u[32], u[33], u[34], std::fmax(u[36], 1e-8f), u[38], H.strength, H.softness, H.bias };
+    if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0) return VF_OK;
+    H.valid = false;
+    ShadowPlan S;
+    if (!shadow_plan(t, u, S)) hipLaunchKernelGGL((k_shadow_fill<0>), dim3((uint32_t)((nv + 255u) / 256u)), dim3(256), 0, s, nv, H.d_lit);
+    else {
+        const size_t need = (size_t)S.nchunks * S.nlines;
+        if (H.cmax_floats < need) {
+            if (H.d_cmax) { (void)hipFree(H.d_cmax); H.d_cmax = nullptr; H.cmax_floats = 0; }
+            const size_t most = (size_t)S.nchunks * 2u * t->n;     // (any sun: at most 2n - 1 lines)
+            if (hipMalloc(&H.d_cmax, most * sizeof(float)) != hipSuccess) { H.d_cmax = nullptr; (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow scan allocation failed"); }
+            H.cmax_floats = most;
+        }
+        const dim3 grid(S.nchunks, (S.nlines + kShLines - 1u) / kShLines), threads(256);
+        if (S.zmajor) hipLaunchKernelGGL((k_shadow_chunk_max<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax);
+        else hipLaunchKernelGGL((k_shadow_chunk_max<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax);
+        hipLaunchKernelGGL((k_shadow_carry<0>), dim3((S.nlines + 255u) / 256u), threads, 0, s, S.nlines, S.nchunks, H.d_cmax);
+        if (S.zmajor) hipLaunchKernelGGL((k_shadow_lit<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax, H.d_lit);
+        else hipLaunchKernelGGL((k_shadow_lit<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax, H.d_lit);
+    }
+    VF_HIP_TRY(hipGetLastError());
+    std::memcpy(H.key, key, sizeof key);
+    H.height_gen = t->height_gen; H.valid = true; H.scans++;
+    return VF_OK;
+}
+
+// k_resolve's launch shape (gb_grid)
+static void shadow_shade_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_shadow_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
+                       (const float *)t->sh.d_lit, redo, rgba);
+    hipLaunchKernelGGL((k_shadow_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
+                       (const float *)t->sh.d_lit, redo, rgba);
+}
+
+// The shadows of a frame, on the draw stream behind its tile kernels (which stored the visibility): the field if it is stale, then
+// the shade pass over the covered pixels.
+static int shadow_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    const int rc = shadow_field(t, t->inputs.u, s);
+    if (rc != VF_OK) return rc;
+    shadow_shade_launch(t, s, P, V, redo, rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float softness, float bias)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!(std::isfinite(strength) && strength >= 0.0f && strength <= 1.0f)) return fail(VF_ERR_INVALID, "strength must be a finite number in [0, 1]");
+    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
+    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "shadows need a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable && !t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
+    vf_terrain::Shadows &H = t->sh;
+    if (H.enabled != (enable != 0) || H.strength != strength || H.softness != softness || H.bias != bias) t->inputs_gen++;
+    H.enabled = enable != 0; H.strength = strength; H.softness = softness; H.bias = bias;
+    return VF_OK;
+}
+
+// the field for the live uniforms, heights and parameters in d_lit, complete when this returns
+static int shadow_field_now(vf_terrain *t)
+{
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (int rc = ct_heights_current(t)) return rc;
+    if (int rc = shadow_field(t, t->inputs.u, t->ctx->stream)) return rc;
+    VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    return VF_OK;
+}
+
+int vf_terrain_read_shadow_field(vf_terrain *t, float *lit)
+{
+    if (!t || !lit) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = shadow_field_now(t)) return rc;
+    VF_HIP_TRY(hipMemcpy(lit, t->sh.d_lit, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToHost));
+    return VF_OK;
+}
+
+int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream)
+{
+    if (!t || !dev_lit) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = shadow_field_now(t)) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    VF_HIP_TRY(hipMemcpyAsync(dev_lit, t->sh.d_lit, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    VF_HIP_TRY(gb_order_after(t, s));                         // (a later field of this handle is computed behind the copy)
+    return VF_OK;
+}
+
+int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count)
+{
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    *count = t->sh.scans;
+    return VF_OK;
+}
+
+int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (repeats == 0) repeats = 1;
+    GbFrame F;                                                // the frame rendered last, drawn again into scratch buffers with its visibility
+    int rc = gb_frame(t, F);
+    if (rc != VF_OK) return rc;
+    const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
+    hipStream_t s = t->ctx->stream;
+    const uint32_t scans = t->sh.scans;
+    rc = shadow_field(t, u, s, true);                         // warm-up (and the field the shade pass reads)
+    if (rc != VF_OK) return rc;
+    const uint32_t *redo = t->ps[t->last_set].work_count + 3;
+    hipEvent_t e[3] = { nullptr, nullptr, nullptr };
+    hipError_t err = hipSuccess;
+    for (auto &ev : e) if (err == hipSuccess) err = hipEventCreate(&ev);
+    if (err == hipSuccess) { shadow_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch); err = hipGetLastError(); }
+    if (err == hipSuccess) err = hipEventRecord(e[0], s);
+    for (uint32_t k = 0; k < repeats && err == hipSuccess && rc == VF_OK; ++k) rc = shadow_field(t, u, s, true);
+    if (err == hipSuccess) err = hipEventRecord(e[1], s);
+    for (uint32_t k = 0; k < repeats && err == hipSuccess; ++k) { shadow_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch); err = hipGetLastError(); }
+    if (err == hipSuccess) err = hipEventRecord(e[2], s);
+    if (err == hipSuccess) err = hipEventSynchronize(e[2]);
+    float a = 0.0f, b = 0.0f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&a, e[0], e[1]);
+    if (err == hipSuccess) err = hipEventElapsedTime(&b, e[1], e[2]);
+    for (auto &ev : e) if (ev) (void)hipEventDestroy(ev);
+    t->sh.scans = scans;                                      // (diagnostic launches are not the handle's)
+    if (rc != VF_OK) return rc;
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("shadow diagnostics: ") + hipGetErrorString(err));
+    ms[0] = a / (float)repeats; ms[1] = b / (float)repeats;
     return VF_OK;
 }
 

@@ -701,8 +701,9 @@ __device__ __forceinline__ bool classify_alive(const TileCtx &T, int32_t X0, int
 constexpr int kLutStride = 4, kLutFloats = 257 * kLutStride;
 struct ShadeTables { const float *lut; const float *thresh; };
 
-// fs_main (terrain.wgsl:69-91) + Rgba8UnormSrgb store
-__device__ __forceinline__ uint32_t fragment_shader(const FrameParams &P, const ShadeTables &S, const float attr[3])
+// fs_main (terrain.wgsl:69-91) + Rgba8UnormSrgb store, with the Lambert term scaled by `lit` (cast shadows, DESIGN.md 4g;
+// fragment_shader below is the frame's own: lit = 1, and lambert * 1 is lambert)
+__device__ __forceinline__ uint32_t fragment_shader_lit(const FrameParams &P, const ShadeTables &S, const float attr[3], float lit)
 {
     const float height = attr[0], x = attr[1], z = attr[2];
     float t = 0.5f + height / (2.0f * P.h_range);
@@ -737,7 +738,7 @@ __device__ __forceinline__ uint32_t fragment_shader(const FrameParams &P, const 
         nx = vx * inv; ny = vy * inv; nz = vz * inv;
     }
     float ndl = fmaf(nz, P.Lz, fmaf(ny, P.Ly, nx * P.Lx));
-    float lambert = fminf(fmaxf(ndl, 0.0f), 1.0f);
+    float lambert = fminf(fmaxf(ndl, 0.0f), 1.0f) * lit;
     float shade = 0.15f * (1.0f - lambert) + lambert;
     uint32_t out = 0xFF000000u;
 #pragma unroll
@@ -749,6 +750,10 @@ __device__ __forceinline__ uint32_t fragment_shader(const FrameParams &P, const 
         out |= srgb_encode(v, S.thresh) << (8 * ch);
     }
     return out;
+}
+__device__ __forceinline__ uint32_t fragment_shader(const FrameParams &P, const ShadeTables &S, const float attr[3])
+{
+    return fragment_shader_lit(P, S, attr, 1.0f);
 }
 
 // ---- the fast fragment path (vf_terrain_set_shade_precision(VF_PRECISION_FAST), the default) -------------------------------

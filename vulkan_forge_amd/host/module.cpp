@@ -572,6 +572,49 @@ public:
         return rules.attr("pick_result")(words).cast<py::dict>();
     }
 
+    // extension: cast sun shadows (argument rules: vulkan_forge_amd/_shadows.py)
+    void set_shadows(bool enabled, float strength, float softness, float bias)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._shadows").attr("shadow_args")(enabled, strength, softness, bias);
+        Borrow b(busy);
+        check(vf_terrain_set_shadows(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<float>(), a[3].cast<float>()));
+        frame_current = false;
+    }
+    py::array_t<float> shadow_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_shadow_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    uint32_t debug_shadow_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_shadow_scans(t, &count));
+        return count;
+    }
+    // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
+    void set_sun(float elevation_deg, float azimuth_deg)
+    {
+        if (!std::isfinite(elevation_deg) || !std::isfinite(azimuth_deg)) throw py::value_error("angles must be finite");
+        const float k = 3.14159265358979323846f / 180.0f;
+        const float el = elevation_deg * k, az = azimuth_deg * k;
+        Borrow b(busy);
+        globals.sun_dir = normalize_or_zero({ std::cos(el) * std::cos(az), std::sin(el), std::cos(el) * std::sin(az) });
+        push_uniforms();
+    }
+    void set_exposure(float exposure)
+    {
+        if (!std::isfinite(exposure) || exposure <= 0.0f) throw py::value_error("exposure must be > 0");
+        Borrow b(busy);
+        globals.exposure = exposure;
+        push_uniforms();
+    }
+
     // src/terrain/mod.rs:537-546
     py::array_t<float> debug_uniforms_f32() const
     {
@@ -892,7 +935,15 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
         .def("clear_overlays", &T::clear_overlays)
         .def("render_gbuffer", &T::render_gbuffer, py::arg("planes") = py::make_tuple("depth", "position", "normal", "primitive"))
         .def("render_depth", &T::render_depth)
-        .def("pick", &T::pick, py::arg("pixels"));
+        .def("pick", &T::pick, py::arg("pixels"))
+        .def("set_shadows", &T::set_shadows, py::arg("enabled") = true, py::kw_only(), py::arg("strength") = VF_SHADOW_STRENGTH,
+             py::arg("softness") = VF_SHADOW_SOFTNESS, py::arg("bias") = VF_SHADOW_BIAS,
+             "Cast sun shadows on the terrain (DESIGN.md 4g).  The three parameters are stored by every call, also one that disables, and\n"
+             "steer shadow_field() too: set_shadows(False) without them puts the defaults back.")
+        .def("shadow_field", &T::shadow_field)
+        .def("debug_shadow_scans", &T::debug_shadow_scans)
+        .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
+        .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
 
 } // namespace
