@@ -1,5 +1,5 @@
 /* occlusion_model.c -- CPU model of overlay occlusion, the contract the gfx950 kernels of
- * vulkan_forge_amd/csrc/vf_overlay.h (k_ov_setup's depth values, k_ov_composite_occlude) and terrain_rw (vf_kernels.h) are held to
+ * vulkan_forge_amd/csrc/vf_overlay.h (k_ov_setup's depth values, k_ov_composite_occlude) and terrain_rw (vf_visible.h) are held to
  * bit for bit.  Written from the contract: the terrain's 1/w at every pixel comes from the visibility ids and a restatement of the
  * vertex stage (vertex_shader, snap_vertex), the clipper and the coverage rule; every primitive takes the generic path (clip, fan,
  * last covering piece), which for an unclipped primitive is the same arithmetic as the kernels' vertex-record path.  Points, lines

@@ -228,6 +228,26 @@ template <typename T> struct DevBuf {
     }
 };
 
+// Diagnostics: the mean time in ms of `repeats` back-to-back launches on `s`, between two events behind one warm-up launch.
+// launch(warm) queues one launch and returns its error; the first error ends the measurement and is returned.
+template <typename F> static hipError_t time_launches(hipStream_t s, uint32_t repeats, float &ms, F &&launch)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t err = hipEventCreate(&e0);
+    if (err == hipSuccess) err = hipEventCreate(&e1);
+    if (err == hipSuccess) err = launch(true);
+    if (err == hipSuccess) err = hipEventRecord(e0, s);
+    for (uint32_t k = 0; k < repeats && err == hipSuccess; ++k) err = launch(false);
+    if (err == hipSuccess) err = hipEventRecord(e1, s);
+    if (err == hipSuccess) err = hipEventSynchronize(e1);
+    float total = 0.0f;
+    if (err == hipSuccess) err = hipEventElapsedTime(&total, e0, e1);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    ms = total / (float)repeats;
+    return err;
+}
+
 // What plan_frame advances from frame to frame.  A plan queued ahead of its call and then thrown away puts the handle back by
 // assigning a saved copy (vf_terrain::PrePlan, drop_preplan); so does the diagnostic frame of render_visibility for the motion part.
 struct PlanCursor {
@@ -353,18 +373,15 @@ struct vf_terrain {
     uint32_t *d_vis = nullptr;           // only allocated for vf_terrain_read_visibility and for occluding overlay layers
     uint32_t *d_stats = nullptr;         // [0] (tile, block) pairs rasterised (stats_layout)
     // geometry buffers: made by the first call that needs them, reused, grown when a call asks for more
-    uint8_t *d_gb = nullptr;             // device planes behind vf_terrain_read_gbuffer
-    size_t gb_bytes = 0;
-    uint8_t *d_pick = nullptr;           // vf_terrain_pick: n pixels in, n records out
-    size_t pick_bytes = 0;
+    DevBuf<uint8_t> d_gb;                // device planes behind vf_terrain_read_gbuffer
+    DevBuf<uint8_t> d_pick;              // vf_terrain_pick: n pixels in, n records out
     // cast shadows: buffers made by the first shadowed frame or field read; the field is computed again only when
     // what it was made from has changed
     struct Shadows {
         bool enabled = false;
         float strength = 0.7f, softness = 0.02f, bias = 0.002f;
-        float *d_lit = nullptr;          // n x n, row-major
-        float *d_cmax = nullptr;         // chunk maxima / carries of the scan: nchunks x nlines
-        size_t cmax_floats = 0;
+        DevBuf<float> d_lit;             // n x n, row-major
+        DevBuf<float> d_cmax;            // chunk maxima / carries of the scan: nchunks x nlines
         bool valid = false;              // d_lit holds the field of `key` and heights generation `height_gen`
         uint64_t height_gen = 0;
         float key[8] = {};               // sun (3), spacing, exaggeration, strength, softness, bias
@@ -801,9 +818,9 @@ void vf_terrain_destroy(vf_terrain *t)
     if (!t) return;
     (void)hipSetDevice(t->ctx->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2],
-                     t->d_gb, t->d_pick, t->sh.d_lit, t->sh.d_cmax };
+    void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
+    t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release();
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
 
@@ -1650,6 +1667,15 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     return VF_OK;
 }
 
+// The handle's visibility buffer, one id per pixel of its whole tiles: made by the first caller that needs a stored visibility (a
+// visibility or diagnostics frame, an occluding overlay layer, shadows)
+static int ensure_vis(vf_terrain *t)
+{
+    const size_t npx = (size_t)t->ntx * t->nty * kTileW * kTileH;
+    if (!t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, npx * sizeof(uint32_t)));
+    return VF_OK;
+}
+
 // Re-render the frame vf_terrain_render drew last with the visibility store enabled, into scratch buffers: uniforms set since,
 // the output buffer (also a caller's, vf_terrain_set_output_device), the stream later calls synchronise with, the timing ring
 // and the camera-motion state are as before afterwards.  What the extra frame does leave behind: it uses one of the two plan
@@ -1658,7 +1684,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
 static int render_visibility(vf_terrain *t)
 {
     const size_t npx = (size_t)t->ntx * t->nty * kTileW * kTileH;
-    if (!t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, npx * sizeof(uint32_t)));
+    if (int rc = ensure_vis(t)) return rc;
     if (!t->d_rgba_scratch) VF_HIP_TRY(hipMalloc(&t->d_rgba_scratch, npx * sizeof(uint32_t)));
     int rc = vf_terrain_sync(t);
     if (rc != VF_OK) return rc;
@@ -1723,7 +1749,7 @@ static int ov_append(vf_terrain *t, size_t nadd, const OvProducer &produce, cons
     vf_terrain::Overlays &O = t->ov;
     if (int rc = ov_budget(O.nprims, nadd)) return rc;
     VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the arrays)
-    if (occlude && !t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
+    if (occlude) { if (int rc = ensure_vis(t)) return rc; }
     if (!O.d_cnt) {
         const uint32_t nbins = ((t->W + kOvBin - 1u) / kOvBin) * ((t->H + kOvBin - 1u) / kOvBin);
         hipError_t e = hipMalloc(&O.d_cnt, (size_t)nbins * sizeof(uint32_t));
@@ -1930,7 +1956,7 @@ int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude
     if (L.polygon) return fail(VF_ERR_INVALID, "a polygon layer cannot occlude: polygon fills have no depth");
     VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the records)
     if (occlude) {
-        if (!t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
+        if (int rc = ensure_vis(t)) return rc;
         VF_HIP_TRY(O.dep.reserve(O.in.cap, O.in.cap, 0, true));
     }
     const float kb = 1.0f + depth_bias;                       // the layer's depth factor, rounded once (binary32)
@@ -2184,6 +2210,16 @@ int vf_terrain_read_visibility(vf_terrain *t, uint32_t *dst)
     return VF_OK;
 }
 
+// Persistent workgroups for `regions` regions of a pass over the stored visibility (RegionWalk): a multiple of 8 of them (one share
+// per XCD), at most per_cu per CU; the environment variable `env`, when set, gives per_cu.  FEW per CU on purpose: the record gathers
+// of more waves than these evict each other's lines from the 32 KB L1 (C4 fill camera, k_resolve4: 3 per CU 0.130 ms, 4: 0.144, 8: 0.148)
+static dim3 region_grid(const vf_terrain *t, uint32_t regions, const char *env, uint32_t per_cu)
+{
+    if (const char *v = std::getenv(env)) per_cu = (uint32_t)std::max(1, std::atoi(v));
+    const uint32_t cus = (uint32_t)std::max(8, t->ctx->prop.multiProcessorCount) / 8u * 8u;
+    return dim3(std::min<uint32_t>((regions + 7u) / 8u * 8u, cus * per_cu));
+}
+
 int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment_timing *out)
 {
     if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
@@ -2204,21 +2240,13 @@ int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment
     build_params(t, in, P);
     const bool fast = fast_shading(in);
     hipStream_t s = t->ctx->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (err == hipSuccess) err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
-    // 16-byte HBM accesses when the rows allow them and the frame holds no clipped primitive (VF_RESOLVE_PER_PIXEL=1: the per-pixel form)
+    // 16-byte HBM accesses, four pixels per lane, when the rows allow them and the frame holds no clipped primitive (VF_RESOLVE_PER_PIXEL=1: the per-pixel form)
     const bool quads = !redo && t->W % 4u == 0 && !std::getenv("VF_RESOLVE_PER_PIXEL");
-    // Persistent workgroups, a multiple of 8 of them (one share per XCD).  FEW per CU on purpose: the record gathers of more waves
-    // than these evict each other's lines from the 32 KB L1 (C4 fill camera, k_resolve4: 3 per CU 0.130 ms, 4: 0.144, 8: 0.148)
-    const uint32_t per_cu = std::getenv("VF_RESOLVE_PER_CU") ? (uint32_t)std::max(1, std::atoi(std::getenv("VF_RESOLVE_PER_CU"))) : (quads ? 3u : 4u);
-    const uint32_t cus = (uint32_t)std::max(8, t->ctx->prop.multiProcessorCount) / 8u * 8u;
-    const dim3 grid(std::min<uint32_t>((((t->W + 31u) / 32u) * ((t->H + 7u) / 8u) + 7u) / 8u * 8u, cus * per_cu)), threads(256);   // 32 x 8 pixel regions
+    const dim3 grid = region_grid(t, ((t->W + 31u) / 32u) * ((t->H + 7u) / 8u), "VF_RESOLVE_PER_CU", 4u), threads(256);   // 32 x 8 pixel regions
     const vf_terrain::PlanState &S = t->ps[t->last_set];     // the set-up of the frame just rendered
     const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
-    // four pixels per lane when the rows allow 16-byte accesses and the frame holds no clipped primitive (VF_RESOLVE_PER_PIXEL=1: the per-pixel form)
     constexpr uint32_t RQ = 8u, RY = 32u;                  // k_resolve4's region: 8 quads x 32 rows
-    const dim3 grid4(std::min<uint32_t>((((t->W / 4u + RQ - 1u) / RQ) * ((t->H + RY - 1u) / RY) + 7u) / 8u * 8u, cus * per_cu));
+    const dim3 grid4 = region_grid(t, ((t->W / 4u + RQ - 1u) / RQ) * ((t->H + RY - 1u) / RY), "VF_RESOLVE_PER_CU", 3u);
     auto launch = [&](uint32_t *covered) {
         if (quads && fast) hipLaunchKernelGGL((k_resolve4<true>), grid4, threads, 0, s, P, V, t->d_lut, t->ctx->d_thresh, (const uint4 *)t->d_vis, (uint4 *)d_out, covered);
         else if (quads) hipLaunchKernelGGL((k_resolve4<false>), grid4, threads, 0, s, P, V, t->d_lut, t->ctx->d_thresh, (const uint4 *)t->d_vis, (uint4 *)d_out, covered);
@@ -2228,13 +2256,8 @@ int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment
         else hipLaunchKernelGGL((k_resolve<false, false>), grid, threads, 0, s, P, V, t->d_lut, t->ctx->d_thresh, t->d_vis, d_out, covered);
     };
     if (err == hipSuccess) err = hipMemsetAsync(t->d_diag, 0, 4 * sizeof(uint32_t), s);
-    if (err == hipSuccess) { launch(t->d_diag); err = hipGetLastError(); }       // warm-up launch, counts the covered pixels
-    if (err == hipSuccess) err = hipEventRecord(e0, s);
-    for (uint32_t k = 0; k < repeats && err == hipSuccess; ++k) { launch(nullptr); err = hipGetLastError(); }
-    if (err == hipSuccess) err = hipEventRecord(e1, s);
-    if (err == hipSuccess) err = hipEventSynchronize(e1);
     float ms = 0.0f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
+    if (err == hipSuccess) err = time_launches(s, repeats, ms, [&](bool warm) { launch(warm ? t->d_diag : nullptr); return hipGetLastError(); });   // the warm-up launch counts the covered pixels
     uint32_t covered = 0;
     if (err == hipSuccess) err = hipMemcpy(&covered, t->d_diag, sizeof covered, hipMemcpyDeviceToHost);
     // the resolved frame against the one the tile kernel produced (row-major whole frame in both buffers)
@@ -2245,11 +2268,9 @@ int vf_terrain_debug_fragment_stage(vf_terrain *t, uint32_t repeats, vf_fragment
         if (err == hipSuccess) err = hipMemcpy(b.data(), t->d_rgba_scratch, npx * 4, hipMemcpyDeviceToHost);
         if (err == hipSuccess) equal = std::memcmp(a.data(), b.data(), npx * 4) == 0 ? 1u : 0u;
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
     (void)hipFree(d_out);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("fragment-stage diagnostics: ") + hipGetErrorString(err));
-    out->resolve_ms = ms / (float)repeats; out->covered_pixels = covered; out->repeats = repeats; out->equal_to_frame = equal;
+    out->resolve_ms = ms; out->covered_pixels = covered; out->repeats = repeats; out->equal_to_frame = equal;
     return VF_OK;
 }
 
@@ -2275,13 +2296,8 @@ static int gb_frame(vf_terrain *t, GbFrame &F)
     return VF_OK;
 }
 
-// persistent workgroups in a multiple of 8 (one share per XCD), four per CU: k_resolve's launch shape
-static dim3 gb_grid(const vf_terrain *t)
-{
-    const uint32_t cus = (uint32_t)std::max(8, t->ctx->prop.multiProcessorCount) / 8u * 8u;
-    const uint32_t per_cu = std::getenv("VF_GBUFFER_PER_CU") ? (uint32_t)std::max(1, std::atoi(std::getenv("VF_GBUFFER_PER_CU"))) : 4u;
-    return dim3(std::min<uint32_t>((((t->W + 31u) / 32u) * ((t->H + 7u) / 8u) + 7u) / 8u * 8u, cus * per_cu));
-}
+// the launch shape of for_each_visible (vf_visible.h): 32 x 8 pixel regions, four workgroups per CU, as k_resolve
+static dim3 gb_grid(const vf_terrain *t) { return region_grid(t, ((t->W + 31u) / 32u) * ((t->H + 7u) / 8u), "VF_GBUFFER_PER_CU", 4u); }
 
 static void gb_launch(const vf_terrain *t, const GbFrame &F, const GbPlanes &O, hipStream_t s)
 {
@@ -2315,13 +2331,21 @@ int vf_terrain_gbuffer_device(vf_terrain *t, float *dev_depth, float *dev_positi
     return VF_OK;
 }
 
-// scratch of the handle, grown to `bytes`
-static int gb_scratch(uint8_t *&buf, size_t &have, size_t bytes)
+// The planes of `mask` (bit k: depth, position, normal, primitive) packed one behind the other in the handle's d_gb, grown to hold them
+struct GbLayout {
+    size_t bytes[4] = {};                // of plane k (0: not asked for)
+    GbPlanes dev = {};
+    void *plane(int k) const { void *const p[4] = { dev.depth, dev.position, dev.normal, dev.primitive }; return p[k]; }
+};
+
+static int gb_planes(vf_terrain *t, uint32_t mask, GbLayout &L)
 {
-    if (have >= bytes) return VF_OK;
-    if (buf) { (void)hipFree(buf); buf = nullptr; have = 0; }
-    if (hipMalloc(&buf, bytes) != hipSuccess) { buf = nullptr; (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "geometry-buffer allocation failed"); }
-    have = bytes;
+    const size_t npx = (size_t)t->W * t->H, words[4] = { 1, 3, 3, 1 };
+    size_t off[4], total = 0;
+    for (int k = 0; k < 4; ++k) { off[k] = total; L.bytes[k] = (mask & (1u << k)) ? npx * words[k] * 4 : 0; total += L.bytes[k]; }
+    if (t->d_gb.reserve(total, total) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "geometry-buffer allocation failed"); }
+    auto dev = [&](int k) -> void * { return L.bytes[k] ? t->d_gb.p + off[k] : nullptr; };
+    L.dev = GbPlanes{ (float *)dev(0), (float *)dev(1), (float *)dev(2), (uint32_t *)dev(3) };
     return VF_OK;
 }
 
@@ -2332,19 +2356,15 @@ int vf_terrain_read_gbuffer(vf_terrain *t, float *depth, float *position, float 
     GbFrame F;
     int rc = gb_frame(t, F);
     if (rc != VF_OK) return rc;
-    const size_t npx = (size_t)t->W * t->H;
     void *const host[4] = { depth, position, normal, primitive };
-    const size_t words[4] = { 1, 3, 3, 1 };
-    size_t off[4], total = 0;
-    for (int k = 0; k < 4; ++k) { off[k] = total; if (host[k]) total += npx * words[k] * 4; }
-    rc = gb_scratch(t->d_gb, t->gb_bytes, total);
+    GbLayout L;
+    rc = gb_planes(t, (depth ? 1u : 0u) | (position ? 2u : 0u) | (normal ? 4u : 0u) | (primitive ? 8u : 0u), L);
     if (rc != VF_OK) return rc;
-    auto dev = [&](int k) -> void * { return host[k] ? t->d_gb + off[k] : nullptr; };
     hipStream_t s = t->ctx->stream;
-    gb_launch(t, F, GbPlanes{ (float *)dev(0), (float *)dev(1), (float *)dev(2), (uint32_t *)dev(3) }, s);
+    gb_launch(t, F, L.dev, s);
     VF_HIP_TRY(hipGetLastError());
     for (int k = 0; k < 4; ++k)
-        if (host[k]) VF_HIP_TRY(hipMemcpyAsync(host[k], dev(k), npx * words[k] * 4, hipMemcpyDeviceToHost, s));
+        if (host[k]) VF_HIP_TRY(hipMemcpyAsync(host[k], L.plane(k), L.bytes[k], hipMemcpyDeviceToHost, s));
     VF_HIP_TRY(hipStreamSynchronize(s));
     return VF_OK;
 }
@@ -2360,12 +2380,11 @@ int vf_terrain_pick(vf_terrain *t, const int32_t *pixels_xy, uint32_t n, float *
     int rc = gb_frame(t, F);
     if (rc != VF_OK || n == 0) return rc;
     const size_t in_bytes = ((size_t)n * 8 + 31) / 32 * 32, out_bytes = (size_t)n * sizeof(GbPixel);
-    rc = gb_scratch(t->d_pick, t->pick_bytes, in_bytes + out_bytes);
-    if (rc != VF_OK) return rc;
+    if (t->d_pick.reserve(in_bytes + out_bytes, in_bytes + out_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "geometry-buffer allocation failed"); }
     hipStream_t s = t->ctx->stream;
-    const int2 *d_in = (const int2 *)t->d_pick;
-    GbPixel *d_out = (GbPixel *)(t->d_pick + in_bytes);
-    VF_HIP_TRY(hipMemcpyAsync(t->d_pick, pixels_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    const int2 *d_in = (const int2 *)t->d_pick.p;
+    GbPixel *d_out = (GbPixel *)(t->d_pick.p + in_bytes);
+    VF_HIP_TRY(hipMemcpyAsync(t->d_pick.p, pixels_xy, (size_t)n * 8, hipMemcpyHostToDevice, s));
     const dim3 grid((n + 255u) / 256u);
     if (F.clipped) hipLaunchKernelGGL((k_gbuffer_pick<true>), grid, dim3(256), 0, s, F.P, F.V, (const uint32_t *)t->d_vis, d_in, n, d_out);
     else hipLaunchKernelGGL((k_gbuffer_pick<false>), grid, dim3(256), 0, s, F.P, F.V, (const uint32_t *)t->d_vis, d_in, n, d_out);
@@ -2383,29 +2402,14 @@ int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repe
     GbFrame F;
     int rc = gb_frame(t, F);
     if (rc != VF_OK) return rc;
-    const size_t npx = (size_t)t->W * t->H;
-    const size_t words[4] = { 1, 3, 3, 1 };
-    size_t off[4], total = 0;
-    for (int k = 0; k < 4; ++k) { off[k] = total; if (planes & (1u << k)) total += npx * words[k] * 4; }
-    rc = gb_scratch(t->d_gb, t->gb_bytes, total);
+    GbLayout L;
+    rc = gb_planes(t, planes, L);
     if (rc != VF_OK) return rc;
-    auto dev = [&](int k) -> void * { return (planes & (1u << k)) ? t->d_gb + off[k] : nullptr; };
-    const GbPlanes O{ (float *)dev(0), (float *)dev(1), (float *)dev(2), (uint32_t *)dev(3) };
     hipStream_t s = t->ctx->stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t err = hipEventCreate(&e0);
-    if (err == hipSuccess) err = hipEventCreate(&e1);
-    if (err == hipSuccess) { gb_launch(t, F, O, s); err = hipGetLastError(); }     // warm-up launch
-    if (err == hipSuccess) err = hipEventRecord(e0, s);
-    for (uint32_t k = 0; k < repeats && err == hipSuccess; ++k) { gb_launch(t, F, O, s); err = hipGetLastError(); }
-    if (err == hipSuccess) err = hipEventRecord(e1, s);
-    if (err == hipSuccess) err = hipEventSynchronize(e1);
-    float total_ms = 0.0f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&total_ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    float mean = 0.0f;
+    const hipError_t err = time_launches(s, repeats, mean, [&](bool) { gb_launch(t, F, L.dev, s); return hipGetLastError(); });
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("geometry-buffer diagnostics: ") + hipGetErrorString(err));
-    *ms = total_ms / (float)repeats;
+    *ms = mean;
     return VF_OK;
 }
 
@@ -2445,29 +2449,24 @@ static int shadow_field(vf_terrain *t, const float *u, hipStream_t s, bool force
 {
     vf_terrain::Shadows &H = t->sh;
     const size_t nv = (size_t)t->n * t->n;
-    if (!H.d_lit) {
-        if (hipMalloc(&H.d_lit, nv * sizeof(float)) != hipSuccess) { H.d_lit = nullptr; (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow field allocation failed"); }
+    if (!H.d_lit.p) {
+        if (H.d_lit.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow field allocation failed"); }
         H.valid = false;
     }
     const float key[8] = { u[32], u[33], u[34], std::fmax(u[36], 1e-8f), u[38], H.strength, H.softness, H.bias };
     if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0) return VF_OK;
     H.valid = false;
     ShadowPlan S;
-    if (!shadow_plan(t, u, S)) hipLaunchKernelGGL((k_shadow_fill<0>), dim3((uint32_t)((nv + 255u) / 256u)), dim3(256), 0, s, nv, H.d_lit);
+    if (!shadow_plan(t, u, S)) hipLaunchKernelGGL((k_shadow_fill<0>), dim3((uint32_t)((nv + 255u) / 256u)), dim3(256), 0, s, nv, H.d_lit.p);
     else {
-        const size_t need = (size_t)S.nchunks * S.nlines;
-        if (H.cmax_floats < need) {
-            if (H.d_cmax) { (void)hipFree(H.d_cmax); H.d_cmax = nullptr; H.cmax_floats = 0; }
-            const size_t most = (size_t)S.nchunks * 2u * t->n;     // (any sun: at most 2n - 1 lines)
-            if (hipMalloc(&H.d_cmax, most * sizeof(float)) != hipSuccess) { H.d_cmax = nullptr; (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow scan allocation failed"); }
-            H.cmax_floats = most;
-        }
+        // (grown once, to what any sun needs: at most 2n - 1 lines)
+        if (H.d_cmax.reserve((size_t)S.nchunks * S.nlines, (size_t)S.nchunks * 2u * t->n) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow scan allocation failed"); }
         const dim3 grid(S.nchunks, (S.nlines + kShLines - 1u) / kShLines), threads(256);
-        if (S.zmajor) hipLaunchKernelGGL((k_shadow_chunk_max<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax);
-        else hipLaunchKernelGGL((k_shadow_chunk_max<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax);
-        hipLaunchKernelGGL((k_shadow_carry<0>), dim3((S.nlines + 255u) / 256u), threads, 0, s, S.nlines, S.nchunks, H.d_cmax);
-        if (S.zmajor) hipLaunchKernelGGL((k_shadow_lit<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax, H.d_lit);
-        else hipLaunchKernelGGL((k_shadow_lit<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax, H.d_lit);
+        if (S.zmajor) hipLaunchKernelGGL((k_shadow_chunk_max<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
+        else hipLaunchKernelGGL((k_shadow_chunk_max<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
+        hipLaunchKernelGGL((k_shadow_carry<0>), dim3((S.nlines + 255u) / 256u), threads, 0, s, S.nlines, S.nchunks, H.d_cmax.p);
+        if (S.zmajor) hipLaunchKernelGGL((k_shadow_lit<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_lit.p);
+        else hipLaunchKernelGGL((k_shadow_lit<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_lit.p);
     }
     VF_HIP_TRY(hipGetLastError());
     std::memcpy(H.key, key, sizeof key);
@@ -2480,9 +2479,9 @@ static void shadow_shade_launch(const vf_terrain *t, hipStream_t s, const FrameP
 {
     const dim3 grid = gb_grid(t), threads(256);
     hipLaunchKernelGGL((k_shadow_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
-                       (const float *)t->sh.d_lit, redo, rgba);
+                       (const float *)t->sh.d_lit.p, redo, rgba);
     hipLaunchKernelGGL((k_shadow_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
-                       (const float *)t->sh.d_lit, redo, rgba);
+                       (const float *)t->sh.d_lit.p, redo, rgba);
 }
 
 // The shadows of a frame, on the draw stream behind its tile kernels (which stored the visibility): the field if it is stale, then
@@ -2505,7 +2504,7 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
     if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "shadows need a whole-frame handle: sharded handles are not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     VF_HIP_TRY(wait_frame(t));
-    if (enable && !t->d_vis) VF_HIP_TRY(hipMalloc(&t->d_vis, (size_t)t->ntx * t->nty * kTileW * kTileH * sizeof(uint32_t)));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
     vf_terrain::Shadows &H = t->sh;
     if (H.enabled != (enable != 0) || H.strength != strength || H.softness != softness || H.bias != bias) t->inputs_gen++;
     H.enabled = enable != 0; H.strength = strength; H.softness = softness; H.bias = bias;
@@ -2527,7 +2526,7 @@ int vf_terrain_read_shadow_field(vf_terrain *t, float *lit)
 {
     if (!t || !lit) return fail(VF_ERR_INVALID, "NULL argument");
     if (int rc = shadow_field_now(t)) return rc;
-    VF_HIP_TRY(hipMemcpy(lit, t->sh.d_lit, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToHost));
+    VF_HIP_TRY(hipMemcpy(lit, t->sh.d_lit.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToHost));
     return VF_OK;
 }
 
@@ -2536,7 +2535,7 @@ int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream)
     if (!t || !dev_lit) return fail(VF_ERR_INVALID, "NULL argument");
     if (int rc = shadow_field_now(t)) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
-    VF_HIP_TRY(hipMemcpyAsync(dev_lit, t->sh.d_lit, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    VF_HIP_TRY(hipMemcpyAsync(dev_lit, t->sh.d_lit.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToDevice, s));
     VF_HIP_TRY(gb_order_after(t, s));                         // (a later field of this handle is computed behind the copy)
     return VF_OK;
 }
@@ -2558,27 +2557,15 @@ int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
     const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
     hipStream_t s = t->ctx->stream;
     const uint32_t scans = t->sh.scans;
-    rc = shadow_field(t, u, s, true);                         // warm-up (and the field the shade pass reads)
-    if (rc != VF_OK) return rc;
     const uint32_t *redo = t->ps[t->last_set].work_count + 3;
-    hipEvent_t e[3] = { nullptr, nullptr, nullptr };
-    hipError_t err = hipSuccess;
-    for (auto &ev : e) if (err == hipSuccess) err = hipEventCreate(&ev);
-    if (err == hipSuccess) { shadow_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch); err = hipGetLastError(); }
-    if (err == hipSuccess) err = hipEventRecord(e[0], s);
-    for (uint32_t k = 0; k < repeats && err == hipSuccess && rc == VF_OK; ++k) rc = shadow_field(t, u, s, true);
-    if (err == hipSuccess) err = hipEventRecord(e[1], s);
-    for (uint32_t k = 0; k < repeats && err == hipSuccess; ++k) { shadow_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch); err = hipGetLastError(); }
-    if (err == hipSuccess) err = hipEventRecord(e[2], s);
-    if (err == hipSuccess) err = hipEventSynchronize(e[2]);
     float a = 0.0f, b = 0.0f;
-    if (err == hipSuccess) err = hipEventElapsedTime(&a, e[0], e[1]);
-    if (err == hipSuccess) err = hipEventElapsedTime(&b, e[1], e[2]);
-    for (auto &ev : e) if (ev) (void)hipEventDestroy(ev);
+    // the field first (its last launch leaves what the shade pass reads); one that fails has stated its own error: rc
+    hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = shadow_field(t, u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    if (err == hipSuccess) err = time_launches(s, repeats, b, [&](bool) { shadow_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch); return hipGetLastError(); });
     t->sh.scans = scans;                                      // (diagnostic launches are not the handle's)
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("shadow diagnostics: ") + hipGetErrorString(err));
-    ms[0] = a / (float)repeats; ms[1] = b / (float)repeats;
+    ms[0] = a; ms[1] = b;
     return VF_OK;
 }
 

@@ -823,6 +823,13 @@ struct SetupView {
 // stage ran once per frame -- so this is loads, three exact edge functions (FP64: operands are integers < 2^25, every product and
 // sum stays below 2^53) and the perspective-correct interpolation of (height, x, z).
 // fs_main's inputs from the three vertex records of the visible primitive: exact edge weights, perspective-correct varyings.
+//
+// The twin of this text is vf_visible.h (visible_site, record_weights, clipped_weights, for_each_visible): the one statement of the
+// same lookup and weights for the passes behind the frame -- overlay occlusion, the geometry buffers, the shadow shade pass.  The
+// fused fragment stage (this function, shade_from_records_fast, shade_pixel, clipped_attributes, k_resolve*) keeps its own on
+// purpose: calling shared __forceinline__ helpers from here, identical arithmetic and nothing else changed, gave every k_tile
+// instantiation, k_resolve<false, .> and both k_resolve4 other instructions (tools/isa_hash.py, counts moved by 0 to 2), and k_tile
+// sits at its 96-register cap.  A change to the vertex-record layout, the generic bitmask or the weight order is made in both.
 __device__ __forceinline__ uint32_t shade_from_records(const FrameParams &P, const ShadeTables &S, uint32_t i, uint32_t j, uint32_t odd,
                                                        const VertexRec &r0, const VertexRec &r1, const VertexRec &r2, int32_t px, int32_t py)
 {
@@ -2607,60 +2614,6 @@ __global__ __launch_bounds__(256) void k_stitch_tiles(const uint32_t *__restrict
             }
         }
     }
-}
-
-// ---- terrain depth at a pixel, for overlay occlusion ---------------------------------------------------------------
-// Q = the visible primitive's perspective weights summed, q_i = lambda_i rw_i, Q = (q0 + q1) + q2: its interpolated 1/w at the pixel
-// centre.  The weights are exactly those of shade_from_records (ordinary primitives) and of interpolate() on the sub-triangle
-// clipped_attributes picks (generic ones); always the exact arithmetic, whatever the shade precision.  Separate functions, so the
-// fragment stage's own code is not touched.
-__device__ __forceinline__ float clipped_rw(const GVert v[3], float hw, float hh, uint32_t W, uint32_t H, int32_t px, int32_t py)
-{
-    GVert poly[8];
-    const int np = clip_primitive(v, poly);
-    float Q = 0.0f;                         // (no piece covers the pixel: unreachable when the visibility is consistent; hides nothing)
-    for (int f = 1; f + 1 < np; ++f) {      // the last covering piece wins, as in clipped_attributes
-        TriSetup T;
-        int64_t e[3];
-        if (setup_triangle(poly[0], poly[f], poly[f + 1], hw, hh, W, H, T) && covers(T, px, py, e)) {
-            const float fA = (float)(-T.area2);
-            const float l0 = (float)e[0] / fA, l1 = (float)e[1] / fA, l2 = (float)e[2] / fA;
-            const float q0 = l0 * T.s[0].rw, q1 = l1 * T.s[1].rw, q2 = l2 * T.s[2].rw;
-            Q = (q0 + q1) + q2;
-        }
-    }
-    return Q;
-}
-
-__device__ inline float terrain_rw(const FrameParams &P, const SetupView &V, uint32_t prim, int32_t px, int32_t py)
-{
-    const uint32_t cell = prim >> 1, odd = prim & 1u;
-    const uint32_t j = cell_row(P, cell), i = cell - j * P.nm1;
-    const uint32_t li = i & 7u, lj = j & 7u;
-    const size_t b = (size_t)(j >> 3) * P.nb + (i >> 3);
-    if (V.recs[b].flags & kRecGeneric) {
-        const ulonglong2 g = V.gen[b];
-        if (((odd ? g.y : g.x) >> (lj * 8u + li)) & 1ull) {
-            GVert v[3];
-            load_prim(P, V.hblk, prim, v[0], v[1], v[2]);
-            return clipped_rw(v, P.hw, P.hh, P.W, P.H, px, py);
-        }
-    }
-    const uint32_t va = lj * kBlockVerts + li;
-    const uint32_t l0 = odd ? va + 1u : va, l1 = va + kBlockVerts, l2 = odd ? va + kBlockVerts + 1u : va + 1u;
-    const size_t base = b * kBlockStride;
-    const VertexRec r0 = V.vtx[base + l0], r1 = V.vtx[base + l1], r2 = V.vtx[base + l2];
-    // shade_from_records' edge weights (FP64, exact) and barycentrics
-    const double Px = (double)(px * 256 + 128), Py = (double)(py * 256 + 128);
-    const double X0 = r0.X, Y0 = r0.Y, X1 = r1.X, Y1 = r1.Y, X2 = r2.X, Y2 = r2.Y;
-    const double e0 = -fma(X2 - X1, Py - Y1, -((Y2 - Y1) * (Px - X1)));
-    const double e1 = -fma(X0 - X2, Py - Y2, -((Y0 - Y2) * (Px - X2)));
-    const double e2 = -fma(X1 - X0, Py - Y0, -((Y1 - Y0) * (Px - X0)));
-    const double area2 = fma(X1 - X0, Y2 - Y0, -((Y1 - Y0) * (X2 - X0)));
-    const float fA = (float)(-area2);
-    const float la0 = (float)e0 / fA, la1 = (float)e1 / fA, la2 = (float)e2 / fA;
-    const float q0 = la0 * r0.rw, q1 = la1 * r1.rw, q2 = la2 * r2.rw;
-    return (q0 + q1) + q2;
 }
 
 } // namespace vf

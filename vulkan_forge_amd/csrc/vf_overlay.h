@@ -23,12 +23,13 @@
 // the bin (crossings between the pixel and the bin's right edge, and the nearest-edge distance).
 // Occlusion: a handle with an occluding point or line layer draws its terrain with the visibility store on, k_ov_setup
 // keeps the 1/w of those layers' primitives in a side array, and k_ov_composite_occlude forms the terrain's 1/w of each pixel of a bin
-// that holds primitives (terrain_rw, vf_kernels.h) and drops an occluding primitive's coverage where the terrain is in front of it.
+// that holds primitives (terrain_rw, vf_visible.h) and drops an occluding primitive's coverage where the terrain is in front of it.
 // All arithmetic is binary32 in the order DESIGN.md states (compiled with -ffp-contract=off); tests/overlay_model/overlay_model.c
 // and tests/polygon_model/polygon_model.c are the same contract on the CPU and the GPU frames equal it bit for bit.
 #pragma once
 #include "vf_device.h"
 #include "vf_kernels.h"
+#include "vf_visible.h"     // inline functions and templates only: the kernels keep their places
 
 namespace vf {
 

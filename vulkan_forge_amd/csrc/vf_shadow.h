@@ -4,15 +4,16 @@
 //                      sheared grid lines, as a decoupled scan -- k_shadow_chunk_max (the maximum of every 64-step chunk of every
 //                      line), k_shadow_carry (their exclusive running maximum along each line), k_shadow_lit (the scan inside a chunk
 //                      by DPP, seeded with the chunk's carry, and the horizon test)
-//   the shade pass     k_shadow_shade walks the frame's stored visibility in k_resolve's shape and writes again, through the exact
-//                      fragment function, the pixels whose interpolated lit is below 1
+//   the shade pass     k_shadow_shade walks the frame's stored visibility (for_each_visible, vf_visible.h) and writes again, through
+//                      the exact fragment function, the pixels whose interpolated lit is below 1 (the lookup, the weights and the
+//                      clipped walk are that header's)
 //
 // Launched only for a handle that asked for shadows or for the field: the frame path is not touched.  The arithmetic is the
 // contract's, bit for bit (tests/shadow_model/shadow_model.c is its CPU statement): max is exact and associative, so the scan gives
 // the sequential walk's bits however a line is cut; every term is formed from its step number alone.  All kernels are templates:
 // the library's non-template kernels keep their places.
 #pragma once
-#include "vf_gbuffer.h"
+#include "vf_visible.h"
 
 namespace vf {
 
@@ -166,41 +167,32 @@ __global__ __launch_bounds__(256) void k_shadow_fill(size_t count, float *__rest
 // Pixel (px, py) with visibility id `id`: its interpolated lit; when that is below 1, its colour again with lambert * lit.
 // A primitive whose three vertex values are all 1 is lit without interpolation (x * (1 / x) need not round to 1).
 template <bool CLIPPED>
-__device__ inline bool sh_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *__restrict__ lit, uint32_t id,
+__device__ __forceinline__ bool sh_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *__restrict__ lit, uint32_t id,
                                 int32_t px, int32_t py, uint32_t &rgba)
 {
-    const uint32_t prim = id - 1u, cell = prim >> 1, odd = prim & 1u;
-    const uint32_t j = cell_row(P, cell), i = cell - j * P.nm1;
+    const uint32_t prim = id - 1u;
+    const VisibleSite s = visible_site<CLIPPED>(P, V, prim);
+    const uint32_t i = s.i, j = s.j, odd = s.odd;
     // vertex 0 = (i + odd, j), vertex 1 = (i, j + 1), vertex 2 = (i + 1, j + odd)
     const float l0 = lit[(size_t)j * P.n + i + odd], l1 = lit[(size_t)(j + 1u) * P.n + i], l2 = lit[(size_t)(j + odd) * P.n + i + 1u];
     if (l0 == 1.0f && l1 == 1.0f && l2 == 1.0f) return false;
-    const uint32_t li = i & 7u, lj = j & 7u;
-    const size_t b = (size_t)(j >> 3) * P.nb + (i >> 3);
     float attr[3] = { 0.0f, 0.0f, 0.0f }, v = 1.0f;
-    bool generic = false;
     if constexpr (CLIPPED) {
-        if (V.recs[b].flags & kRecGeneric) {
-            const ulonglong2 gen = V.gen[b];
-            generic = ((odd ? gen.y : gen.x) >> (lj * 8u + li)) & 1ull;
-        }
-        if (generic) {
+        if (s.generic) {
             GVert g[3];
             load_prim(P, V.hblk, prim, g[0], g[1], g[2]);
-            (void)gb_clipped(g, P.hw, P.hh, P.W, P.H, px, py, attr);
+            (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, attr);
             // lit rides through the clipper in the place of the height varying: the same crossings, the same piece
             g[0].a[0] = l0; g[1].a[0] = l1; g[2].a[0] = l2;
             float la[3];
-            (void)gb_clipped(g, P.hw, P.hh, P.W, P.H, px, py, la);
+            (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, la);
             v = la[0];
         }
     }
-    if (!generic) {
-        const uint32_t va = lj * kBlockVerts + li;
-        const uint32_t a0 = odd ? va + 1u : va, a1 = va + kBlockVerts, a2 = odd ? va + kBlockVerts + 1u : va + 1u;
-        const size_t base = b * kBlockStride;
-        const VertexRec r0 = V.vtx[base + a0], r1 = V.vtx[base + a1], r2 = V.vtx[base + a2];
+    if (!s.generic) {
+        const VertexRec r0 = V.vtx[s.r0], r1 = V.vtx[s.r1], r2 = V.vtx[s.r2];
         float q0, q1, q2;
-        gb_record_weights(r0, r1, r2, px, py, q0, q1, q2);
+        record_weights(r0, r1, r2, px, py, q0, q1, q2);
         const float rQ = 1.0f / ((q0 + q1) + q2);
         v = fmaf(q2, l2, fmaf(q1, l1, q0 * l0)) * rQ;
         if (!(v < 1.0f)) return false;
@@ -215,9 +207,9 @@ __device__ inline bool sh_pixel(const FrameParams &P, const SetupView &V, const 
     return true;
 }
 
-// The frame's visibility (H, W) -> the shadowed pixels of its colour buffer, in k_resolve's shape (vf_kernels.h).  `redo` is the
-// frame's count of work items that met a clipped or oversized primitive: both instantiations are launched behind a frame and the
-// one the frame does not call for leaves at once (no host round trip between the frame and its shadows).
+// The frame's visibility (H, W) -> the shadowed pixels of its colour buffer, in the walk of for_each_visible (vf_visible.h).  `redo`
+// is the frame's count of work items that met a clipped or oversized primitive: both instantiations are launched behind a frame and
+// the one the frame does not call for leaves at once (no host round trip between the frame and its shadows).
 template <bool CLIPPED>
 __global__ __launch_bounds__(256) void k_shadow_shade(FrameParams P, SetupView V, const float *__restrict__ lut_linear, const float *__restrict__ thresh,
                                                       const uint32_t *__restrict__ vis, const float *__restrict__ lit, const uint32_t *__restrict__ redo,
@@ -230,27 +222,10 @@ __global__ __launch_bounds__(256) void k_shadow_shade(FrameParams P, SetupView V
     s_thr[threadIdx.x] = thresh[threadIdx.x];
     __syncthreads();
     const ShadeTables T = { s_lut, s_thr };
-    const uint32_t lx = (threadIdx.x >> 6) * 8u + (threadIdx.x & 7u), ly = (threadIdx.x >> 3) & 7u;
-    RegionWalk R;
-    R.init((P.W + 31u) / 32u, (P.H + 7u) / 8u);
-    auto fetch = [&](uint32_t kk) -> uint32_t {
-        uint32_t rx, ry;
-        R.at(kk, rx, ry);
-        const uint32_t px = rx * 32u + lx, py = ry * 8u + ly;
-        return px < P.W && py < P.H ? vis[(size_t)py * P.W + px] : 0u;
-    };
-    uint32_t id_next = R.valid() ? fetch(R.k) : 0u;
-    while (R.valid()) {
-        const uint32_t id = id_next;
-        const uint32_t kn = R.k + R.stride;
-        if (kn < R.total) id_next = fetch(kn);
-        uint32_t rx, ry;
-        R.at(R.k, rx, ry);
-        const uint32_t px = rx * 32u + lx, py = ry * 8u + ly;
+    for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
         uint32_t c;
-        if (id != 0u && px < P.W && py < P.H && sh_pixel<CLIPPED>(P, V, T, lit, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
-        R.k = kn;
-    }
+        if (id != 0u && sh_pixel<CLIPPED>(P, V, T, lit, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
+    });
 }
 
 } // namespace vf
