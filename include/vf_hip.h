@@ -509,6 +509,42 @@ int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream);
 int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
 int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count);
 
+/* ---- ambient occlusion from a sky-view scan of the height field ------------------------------------
+ * The sky-view field is one float32 per grid vertex, (grid, grid) row-major (row j = z index, column i = x index): sky in [0, 1],
+ * 1 = open sky.  It comes from the displaced heights the renderer draws and `ndirs` horizontal directions (ux, uz): along the
+ * sheared grid line of each direction (the lines of the cast shadows) a vertex looks back `reach` grid cells of Euclidean distance
+ * for its horizon slope T; the direction is occluded by 1 - 1 / (1 + T^2), and sky is 1 minus the mean over the directions.  The
+ * arithmetic is fixed bit for bit.  The field is computed by the first frame or field call that needs it and again
+ * only after the heights, spacing, exaggeration, `reach` or the directions have changed -- not for the sun, the camera or `strength`.
+ *
+ * vf_terrain_set_ambient: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then writes
+ * again every covered pixel whose interpolated amb = 1 - strength (1 - sky), or whose lit when cast shadows are on as well, is below
+ * 1: fs_main with lambert * lit and its shade times amb, always in the exact arithmetic (both shade modes).  Other pixels keep the
+ * frame's bytes; with ambient occlusion off nothing changes.  Overlays composite afterwards and are not darkened; geometry buffers
+ * and the diagnostics frames are unaffected.  dirs_xz: ndirs pairs (ux, uz), used as given (only the ratio matters), or NULL for
+ * the default set, azimuth 360 t / ndirs degrees.  strength in [0, 1], reach in [1, 1024], ndirs in [1, 64], all finite, every
+ * direction finite and not (0, 0), else VF_ERR_INVALID and nothing changes.  Whole-frame handles only: enabling on a band- or
+ * tile-sharded handle, sharding a handle with it enabled, and vf_terrain_render_batch / _batch_host with it enabled are
+ * VF_ERR_INVALID and change nothing.  The parameters are stored also with enable == 0 (the field calls below use them).
+ * A handle that never calls any of these allocates and launches nothing for them.
+ * vf_terrain_read_sky_view_field: the field for the current heights, uniforms and parameters into host memory (grid * grid floats),
+ * whether or not ambient occlusion is enabled for drawing.
+ * vf_terrain_sky_view_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream);
+ * later calls on the handle are ordered behind the copy by the library. */
+#define VF_AMBIENT_STRENGTH 0.6f
+#define VF_AMBIENT_REACH 64.0f
+#define VF_AMBIENT_DIRECTIONS 16
+#define VF_AMBIENT_REACH_MAX 1024
+#define VF_AMBIENT_DIRECTIONS_MAX 64
+int vf_terrain_set_ambient(vf_terrain *t, int enable, float strength, float reach, uint32_t ndirs, const float *dirs_xz);
+int vf_terrain_read_sky_view_field(vf_terrain *t, float *sky);
+int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream);
+/* diagnostics: ms[0] the average time (HIP events) of `repeats` computations of the field, ms[1] of `repeats` shade passes (with
+ * the cast shadows when they are on), for the frame rendered last (drawn again into scratch buffers), each after one warm-up; and
+ * how many times the handle has computed its field so far (the diagnostic launches are not counted). */
+int vf_terrain_debug_ambient_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
+int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

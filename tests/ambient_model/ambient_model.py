@@ -1,0 +1,100 @@
+"""ctypes loader of the ambient-occlusion CPU model (ambient_model.c).
+
+    import ambient_model as abm
+    sky = abm.field_heights(h, dirs, spacing=1.0, exag=1.0, reach=64.0)          # h: (n, n) vertex heights, dirs: (D, 2) float32
+    sky = abm.field(uniforms, height, grid, dirs, reach=...)                     # the renderer's own surface
+    frame, rewritten = abm.frame(rgba, vis, uniforms, height, grid, lut_rgba8, sky, strength, lit=None, shade_mode=0)
+
+`rgba` is the plain frame (H, W, 4) and `vis` its visibility (H, W) uint32 (oracle.render_terrain); `lit` the shadow field when cast
+shadows are on as well; `rewritten` marks the pixels whose interpolated lit or amb is below 1 (the ones the shade pass writes again).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "shadow_model"))
+import shadow_model as shm  # noqa: E402
+om = shm.om
+
+# The GPU field tests: (grid, exaggeration, reach, D) on overlay_scenes.heights(4, (97, 131)) -- a grid that is no multiple of 8 or 64,
+# a reach that crosses one tile boundary, one that crosses two, many chunks plus one, and a single direction.
+FIELD_CASES = [(203, 0.6, 16.0, 16), (130, 0.6, 70.0, 16), (520, 0.6, 130.0, 16), (1025, 0.6, 20.0, 16), (203, 0.6, 16.0, 1)]
+# an exact diagonal, both axes, a nearly-axis direction in each major axis, general ones in other quadrants, none normalised
+IRREGULAR = np.array([(1, 1), (1, 0), (0, -1), (1, 1e-3), (-2e-3, 1), (-0.9, 0.31), (0.31, -0.9), (-3, -3), (0, 2)], np.float32)
+# The GPU frame tests' scene: overlay_scenes' white noise at a hundredth of its height, so that the analytic surface under it shows.
+# Every slope of a rough or smooth surface is seen from somewhere, so an all-round direction set leaves no vertex with an open sky and
+# every pixel would be written again; these three directions look one way, down the analytic surface over most of the grid, and
+# between 10 % and 90 % of the covered pixels of every test camera are written again while more than 10 % of the vertices have a
+# sky view in (0.1, 0.9) (test_ambient_model.py asserts both).
+SCENE_PARAMS = dict(strength=0.8, reach=2.0)
+SCENE_SUN_DEG = (8.0, 30.0)                                # elevation, azimuth: low enough for the analytic surface to cast shadows
+SCENE_SHADOWS = dict(strength=0.7, softness=0.02, bias=0.001)
+
+
+def scene_directions():
+    return np.array([(-1, 0), (-0.9, 0.31), (-0.9, -0.31)], np.float32)
+
+
+def scene_heights(seed=7):
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
+    from overlay_scenes import heights
+    return (heights(seed) * np.float32(0.01)).astype(np.float32)
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        T = os.path.dirname(HERE)
+        L = om.build_model("libabmodel.so", os.path.join(HERE, "ambient_model.c"),
+                           [os.path.join(T, "shadow_model", "shadow_model.c"), os.path.join(T, "gbuffer_model", "gbuffer_model.c"),
+                            os.path.join(T, "occlusion_model", "occlusion_model.c"), os.path.join(T, "polygon_model", "polygon_model.c"),
+                            os.path.join(T, "overlay_model", "overlay_model.c")])
+        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
+        L.abm_field_heights.argtypes = [vp, vp, u32, vp, u32, f, f, f]
+        L.abm_field_heights.restype = i
+        L.abm_frame.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp, vp, f]
+        L.abm_frame.restype = i
+        _lib = L
+    return _lib
+
+
+def field_heights(h, dirs, spacing=1.0, exag=1.0, reach=64.0):
+    """h (n, n) float32 vertex heights (row = z index, column = x index), dirs (D, 2) float32 -> sky (n, n) float32"""
+    h = np.ascontiguousarray(h, np.float32)
+    assert h.ndim == 2 and h.shape[0] == h.shape[1]
+    dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 2)
+    sky = np.empty_like(h)
+    rc = lib().abm_field_heights(sky.ctypes.data, h.ctypes.data, h.shape[0], dirs.ctypes.data, len(dirs), spacing, exag, reach)
+    if rc != 0:
+        raise ValueError("a direction without a horizontal part, or a non-finite one")
+    return sky
+
+
+def field(uniforms, height, grid, dirs, reach=64.0):
+    """the field of the renderer's surface for the uniforms' spacing (u[36], at least 1e-8) and exaggeration (u[38])"""
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    return field_heights(shm.heights(u, height, grid), dirs, float(max(u[36], np.float32(1e-8))), float(u[38]), reach)
+
+
+def frame(rgba, vis, uniforms, height, grid, lut_rgba8, sky, strength, lit=None, shade_mode=0):
+    """-> (the frame with ambient occlusion (H, W, 4) uint8, rewritten (H, W) bool)"""
+    vis = np.ascontiguousarray(vis, np.uint32)
+    H, W = vis.shape
+    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
+    sky = np.ascontiguousarray(sky, np.float32)
+    lit = None if lit is None else np.ascontiguousarray(lit, np.float32)
+    mask = np.empty((H, W), np.uint8)
+    assert lib().abm_frame(out.ctypes.data, mask.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0],
+                           grid, lut.ctypes.data, int(shade_mode), None if lit is None else lit.ctypes.data, sky.ctypes.data, strength) == 0
+    return out, mask.astype(bool)

@@ -29,6 +29,8 @@ SYMBOLS = [
     "vf_terrain_gbuffer_device", "vf_terrain_read_gbuffer", "vf_terrain_pick", "vf_terrain_debug_gbuffer_stage",
     "vf_terrain_set_shadows", "vf_terrain_read_shadow_field", "vf_terrain_shadow_field_device", "vf_terrain_debug_shadow_stage",
     "vf_terrain_debug_shadow_scans",
+    "vf_terrain_set_ambient", "vf_terrain_read_sky_view_field", "vf_terrain_sky_view_field_device", "vf_terrain_debug_ambient_stage",
+    "vf_terrain_debug_ambient_scans",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -124,6 +126,11 @@ _PROTOS = {
     "vf_terrain_shadow_field_device": (_i, [_vp, _vp, _vp]),
     "vf_terrain_debug_shadow_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_terrain_debug_shadow_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_set_ambient": (_i, [_vp, _i, _f, _f, _u32, _vp]),
+    "vf_terrain_read_sky_view_field": (_i, [_vp, _vp]),
+    "vf_terrain_sky_view_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_debug_ambient_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_debug_ambient_scans": (_i, [_vp, C.POINTER(_u32)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -509,6 +516,37 @@ class Terrain:
         """How many times the handle has computed its shadow field."""
         n = _u32()
         self._check(self.lib.vf_terrain_debug_shadow_scans(self.t, C.byref(n)))
+        return n.value
+
+    def set_ambient_occlusion(self, enabled=True, *, strength=0.6, reach=64.0, directions=16):
+        """Ambient occlusion from a sky-view scan of the height field.  `directions`: how many of the default set, or
+        a (D, 2) array of (ux, uz).  The parameters are stored by every call, also one that disables, and steer sky_view_field()
+        too: set_ambient_occlusion(False) without them puts the defaults back."""
+        from ._ambient import ambient_args
+        enable, strength, reach, D, dirs = ambient_args(enabled, strength, reach, directions)
+        self._check(self.lib.vf_terrain_set_ambient(self.t, enable, strength, reach, D, dirs.ctypes.data))
+
+    def sky_view_field(self):
+        """The sky-view field for the current heights, uniforms and parameters: (grid, grid) float32, sky in [0, 1], 1 = open sky."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_sky_view_field(self.t, out.ctypes.data))
+        return out
+
+    def sky_view_field_device(self, dev_sky, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_sky_view_field_device(self.t, dev_sky, stream))
+
+    def ambient_stage(self, repeats=20):
+        """(field ms, shade-pass ms) of the frame rendered last, as timed launches of their own (diagnostics)."""
+        ms = (_f * 2)()
+        self._check(self.lib.vf_terrain_debug_ambient_stage(self.t, int(repeats), ms))
+        return ms[0], ms[1]
+
+    def ambient_scans(self):
+        """How many times the handle has computed its sky-view field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_ambient_scans(self.t, C.byref(n)))
         return n.value
 
     def enable_timing(self, on=True, stats=True, sampled=False):

@@ -5,6 +5,7 @@
 #include "vf_overlay.h"     // (brings vf_contour.h)
 #include "vf_gbuffer.h"     // templates only, behind the last non-template kernel
 #include "vf_shadow.h"      // templates only
+#include "vf_ambient.h"     // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -387,6 +388,20 @@ struct vf_terrain {
         float key[8] = {};               // sun (3), spacing, exaggeration, strength, softness, bias
         uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_shadow_scans)
     } sh;
+    // ambient occlusion: the same rules; the sun, the camera and `strength` are not part of the field
+    struct Ambient {
+        bool enabled = false;
+        float strength = VF_AMBIENT_STRENGTH, reach = VF_AMBIENT_REACH;
+        uint32_t ndirs = VF_AMBIENT_DIRECTIONS;
+        bool default_dirs = true;        // dirs holds the default set of ndirs directions (made when first needed)
+        std::vector<float> dirs;         // ndirs x (ux, uz)
+        DevBuf<float> d_sky;             // n x n, row-major
+        bool valid = false;              // d_sky holds the field of `key`, `key_dirs` and heights generation `height_gen`
+        uint64_t height_gen = 0;
+        float key[3] = {};               // spacing, exaggeration, reach
+        std::vector<float> key_dirs;
+        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_ambient_scans)
+    } am;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -820,7 +835,7 @@ void vf_terrain_destroy(vf_terrain *t)
     (void)hipDeviceSynchronize();
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release();
+    t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release(); t->am.d_sky.release();
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
 
@@ -969,6 +984,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (!is_pow2(band_h) || band_h < (uint32_t)kTileH) return fail(VF_ERR_INVALID, "band_h must be a power of two >= 64 (the tile height)");
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
     if (t->sh.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
+    if (t->am.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     VF_HIP_TRY(drop_preplan(t));
@@ -1091,6 +1107,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (!layout_valid(skew)) return fail(VF_ERR_INVALID, "layout word is neither VF_TILE_LAYOUT(skew < 65536, stripe_log2 <= 15) nor a registered stripe map");
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
+    if (t->am.enabled) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1435,12 +1452,14 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 // diag: a visibility / diagnostics frame (render_visibility): stores its visibility, composites no overlays.  A frame of a handle with an
 // occluding overlay layer stores its visibility too, for the overlay pass.
 static int shadow_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int ambient_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows);
 
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
     const FrameParams &P = K.P;
     const bool shadows = t->sh.enabled && !diag;           // (visibility / diagnostics frames: the frame as the tile kernel shades it)
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows;
+    const bool ambient = t->am.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1494,9 +1513,9 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     }
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev.end, s)); t->timed_frames++; }
-    if (shadows && ntiles) {                               // cast shadows: behind the tile kernels, in front of the overlays
+    if ((shadows || ambient) && ntiles) {                  // cast shadows and ambient occlusion: behind the tile kernels, in front of the overlays
         const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
-        const int src = shadow_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        const int src = ambient ? ambient_pass(t, s, P, V, S.work_count + 3, t->d_rgba, shadows) : shadow_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
         if (src != VF_OK) return src;
     }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
@@ -1611,6 +1630,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
 {
     if (!t || (!uniforms && n)) return fail(VF_ERR_INVALID, "NULL argument");
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
+    if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1630,6 +1650,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (!t || !uniforms || !host_rgba) return fail(VF_ERR_INVALID, "NULL argument");
     if (t->shard_tiles || t->local_rows != t->H) return fail(VF_ERR_INVALID, "batch read-back needs the whole frame on one handle (pose-parallel ranks are replicas)");
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
+    if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2565,6 +2586,181 @@ int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
     t->sh.scans = scans;                                      // (diagnostic launches are not the handle's)
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("shadow diagnostics: ") + hipGetErrorString(err));
+    ms[0] = a; ms[1] = b;
+    return VF_OK;
+}
+
+// ---- ambient occlusion (vf_ambient.h) ---------------------------------------------------
+
+// The default set of D directions: azimuth 360 t / D degrees in binary64, rounded; whole octants are the exact axes and (+-1, +-1)
+// (vulkan_forge_amd/_ambient.py: directions states the same rule).
+static void ambient_default_dirs(uint32_t D, std::vector<float> &dirs)
+{
+    static const float oct[8][2] = { { 1, 0 }, { 1, 1 }, { 0, 1 }, { -1, 1 }, { -1, 0 }, { -1, -1 }, { 0, -1 }, { 1, -1 } };
+    dirs.resize(2u * D);
+    for (uint32_t k = 0; k < D; ++k) {
+        if ((8u * k) % D == 0u) { dirs[2u * k] = oct[8u * k / D][0]; dirs[2u * k + 1u] = oct[8u * k / D][1]; continue; }
+        const double az = 2.0 * 3.14159265358979323846 * (double)k / (double)D;
+        dirs[2u * k] = (float)std::cos(az); dirs[2u * k + 1u] = (float)std::sin(az);
+    }
+}
+
+// The frame of reference of direction (ux, uz) of the field for the uniforms `u`; the lines are
+// shadow_plan's with the sun's horizontal part set to the direction (set_ambient has refused a direction without one).
+static void ambient_plan(const vf_terrain *t, const float *u, float ux, float uz, AmbientPlan &A)
+{
+    ShadowPlan &S = A.S;
+    const float ax = std::fabs(ux), az = std::fabs(uz);
+    const bool zmajor = az > ax;                              // a tie goes to x
+    const float amaj = zmajor ? az : ax, amin = zmajor ? ax : az;
+    const float smaj = zmajor ? uz : ux, smin = zmajor ? ux : uz;
+    S.n = t->n; S.nb = t->nb;
+    S.zmajor = zmajor ? 1u : 0u;
+    S.from_high = smaj > 0.0f ? 1u : 0u;
+    S.s = smin < 0.0f ? -1 : 1;
+    S.a = amin / amaj;
+    const int32_t R = (int32_t)std::rint((float)(t->n - 1u) * S.a);
+    S.c_lo = S.s > 0 ? 0 : -R;
+    S.nlines = t->n + (uint32_t)R;
+    S.nchunks = (t->n + kShChunk - 1u) / kShChunk;
+    S.d = 0.0f; S.exag = u[38]; S.strength = 0.0f; S.softness = 1.0f; S.bias = 0.0f;
+    const float spacing = std::fmax(u[36], 1e-8f);
+    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    const float g = std::sqrt(std::fma(S.a, S.a, 1.0f));
+    A.ell = (step * spacing) * g;
+    const float rf = std::floor(t->am.reach / g);
+    A.R = std::min<uint32_t>(rf >= 1.0f ? (uint32_t)rf : 1u, kAmMaxReach);
+}
+
+// d_sky holds the field of the uniforms `u`, the handle's heights, directions and reach once the work queued on `s` is done (the
+// height cache must be current and ordered before `s`, as for shadow_field).  force: compute it anyway.
+static int ambient_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false)
+{
+    vf_terrain::Ambient &H = t->am;
+    const size_t nv = (size_t)t->n * t->n;
+    if (!H.d_sky.p) {
+        if (H.d_sky.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "sky-view field allocation failed"); }
+        H.valid = false;
+    }
+    if (H.default_dirs && H.dirs.size() != 2u * H.ndirs) ambient_default_dirs(H.ndirs, H.dirs);
+    const float key[3] = { std::fmax(u[36], 1e-8f), u[38], H.reach };
+    if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0 && H.key_dirs.size() == H.dirs.size()
+        && std::memcmp(H.key_dirs.data(), H.dirs.data(), H.dirs.size() * sizeof(float)) == 0) return VF_OK;
+    H.valid = false;
+    for (uint32_t k = 0; k < H.ndirs; ++k) {
+        AmbientPlan A;
+        ambient_plan(t, u, H.dirs[2u * k], H.dirs[2u * k + 1u], A);
+        A.first = k == 0u ? 1u : 0u; A.last = k + 1u == H.ndirs ? 1u : 0u; A.count = (float)H.ndirs;
+        const dim3 grid(A.S.nchunks, (A.S.nlines + kShLines - 1u) / kShLines), threads(256);
+        if (A.S.zmajor) hipLaunchKernelGGL((k_ambient_dir<true>), grid, threads, 0, s, A, (const float *)t->d_hblk, H.d_sky.p);
+        else hipLaunchKernelGGL((k_ambient_dir<false>), grid, threads, 0, s, A, (const float *)t->d_hblk, H.d_sky.p);
+    }
+    VF_HIP_TRY(hipGetLastError());
+    std::memcpy(H.key, key, sizeof key);
+    H.key_dirs = H.dirs;
+    H.height_gen = t->height_gen; H.valid = true; H.scans++;
+    return VF_OK;
+}
+
+// k_resolve's launch shape (gb_grid); lit: the shadow field or NULL
+static void ambient_shade_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, const float *lit)
+{
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_ambient_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
+                       lit, (const float *)t->am.d_sky.p, t->am.strength, redo, rgba);
+    hipLaunchKernelGGL((k_ambient_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
+                       lit, (const float *)t->am.d_sky.p, t->am.strength, redo, rgba);
+}
+
+// Ambient occlusion of a frame, and its cast shadows when they are on as well: the fields that are stale, then one shade pass.
+static int ambient_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows)
+{
+    if (shadows) { if (int rc = shadow_field(t, t->inputs.u, s)) return rc; }
+    if (int rc = ambient_field(t, t->inputs.u, s)) return rc;
+    ambient_shade_launch(t, s, P, V, redo, rgba, shadows ? t->sh.d_lit.p : nullptr);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_ambient(vf_terrain *t, int enable, float strength, float reach, uint32_t ndirs, const float *dirs_xz)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!(std::isfinite(strength) && strength >= 0.0f && strength <= 1.0f)) return fail(VF_ERR_INVALID, "strength must be a finite number in [0, 1]");
+    if (!(std::isfinite(reach) && reach >= 1.0f && reach <= (float)VF_AMBIENT_REACH_MAX)) return fail(VF_ERR_INVALID, "reach must be a finite number in [1, 1024]");
+    if (ndirs < 1u || ndirs > VF_AMBIENT_DIRECTIONS_MAX) return fail(VF_ERR_INVALID, "ndirs must lie in [1, 64]");
+    for (uint32_t k = 0; dirs_xz && k < ndirs; ++k) {
+        const float ux = dirs_xz[2u * k], uz = dirs_xz[2u * k + 1u];
+        if (!std::isfinite(ux) || !std::isfinite(uz) || (ux == 0.0f && uz == 0.0f)) return fail(VF_ERR_INVALID, "a direction must be finite and have a horizontal part");
+    }
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "ambient occlusion needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    vf_terrain::Ambient &H = t->am;
+    std::vector<float> dirs;
+    if (dirs_xz) dirs.assign(dirs_xz, dirs_xz + 2u * ndirs);
+    else ambient_default_dirs(ndirs, dirs);
+    if (H.enabled != (enable != 0) || H.strength != strength || H.reach != reach || H.dirs != dirs) t->inputs_gen++;
+    H.enabled = enable != 0; H.strength = strength; H.reach = reach; H.ndirs = ndirs; H.default_dirs = dirs_xz == nullptr; H.dirs = std::move(dirs);
+    return VF_OK;
+}
+
+// the field for the live uniforms, heights and parameters in d_sky, complete when this returns
+static int ambient_field_now(vf_terrain *t)
+{
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (int rc = ct_heights_current(t)) return rc;
+    if (int rc = ambient_field(t, t->inputs.u, t->ctx->stream)) return rc;
+    VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    return VF_OK;
+}
+
+int vf_terrain_read_sky_view_field(vf_terrain *t, float *sky)
+{
+    if (!t || !sky) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = ambient_field_now(t)) return rc;
+    VF_HIP_TRY(hipMemcpy(sky, t->am.d_sky.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToHost));
+    return VF_OK;
+}
+
+int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream)
+{
+    if (!t || !dev_sky) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = ambient_field_now(t)) return rc;
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    VF_HIP_TRY(hipMemcpyAsync(dev_sky, t->am.d_sky.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    VF_HIP_TRY(gb_order_after(t, s));                         // (a later field of this handle is computed behind the copy)
+    return VF_OK;
+}
+
+int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count)
+{
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    *count = t->am.scans;
+    return VF_OK;
+}
+
+int vf_terrain_debug_ambient_stage(vf_terrain *t, uint32_t repeats, float ms[2])
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (repeats == 0) repeats = 1;
+    GbFrame F;                                                // the frame rendered last, drawn again into scratch buffers with its visibility
+    int rc = gb_frame(t, F);
+    if (rc != VF_OK) return rc;
+    const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
+    hipStream_t s = t->ctx->stream;
+    const uint32_t scans = t->am.scans, shadow_scans = t->sh.scans;
+    const uint32_t *redo = t->ps[t->last_set].work_count + 3;
+    if (t->sh.enabled) rc = shadow_field(t, u, s);            // (the shade pass below reads it)
+    float a = 0.0f, b = 0.0f;
+    hipError_t err = hipSuccess;
+    if (rc == VF_OK) err = time_launches(s, repeats, a, [&](bool) { rc = ambient_field(t, u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    if (rc == VF_OK && err == hipSuccess)
+        err = time_launches(s, repeats, b, [&](bool) { ambient_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, t->sh.enabled ? t->sh.d_lit.p : nullptr); return hipGetLastError(); });
+    t->am.scans = scans; t->sh.scans = shadow_scans;          // (diagnostic launches are not the handle's)
+    if (rc != VF_OK) return rc;
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("ambient diagnostics: ") + hipGetErrorString(err));
     ms[0] = a; ms[1] = b;
     return VF_OK;
 }

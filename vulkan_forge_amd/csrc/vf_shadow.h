@@ -166,27 +166,46 @@ __global__ __launch_bounds__(256) void k_shadow_fill(size_t count, float *__rest
 
 // Pixel (px, py) with visibility id `id`: its interpolated lit; when that is below 1, its colour again with lambert * lit.
 // A primitive whose three vertex values are all 1 is lit without interpolation (x * (1 / x) need not round to 1).
-template <bool CLIPPED>
-__device__ __forceinline__ bool sh_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *__restrict__ lit, uint32_t id,
-                                int32_t px, int32_t py, uint32_t &rgba)
+// AMBIENT (k_ambient_shade of vf_ambient.h): amb = 1 - strength (1 - sky) per vertex is interpolated by the same rule
+// and the pixel is written again when lit or amb is below 1, with shade * amb; `lit` may be NULL then (no cast shadows: lit = 1).
+template <bool CLIPPED, bool AMBIENT>
+__device__ __forceinline__ bool sh_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *__restrict__ lit,
+                                         const float *__restrict__ sky, float amb_strength, uint32_t id, int32_t px, int32_t py, uint32_t &rgba)
 {
     const uint32_t prim = id - 1u;
     const VisibleSite s = visible_site<CLIPPED>(P, V, prim);
     const uint32_t i = s.i, j = s.j, odd = s.odd;
     // vertex 0 = (i + odd, j), vertex 1 = (i, j + 1), vertex 2 = (i + 1, j + odd)
-    const float l0 = lit[(size_t)j * P.n + i + odd], l1 = lit[(size_t)(j + 1u) * P.n + i], l2 = lit[(size_t)(j + odd) * P.n + i + 1u];
-    if (l0 == 1.0f && l1 == 1.0f && l2 == 1.0f) return false;
-    float attr[3] = { 0.0f, 0.0f, 0.0f }, v = 1.0f;
+    const bool have_lit = !AMBIENT || lit != nullptr;
+    const float l0 = have_lit ? lit[(size_t)j * P.n + i + odd] : 1.0f, l1 = have_lit ? lit[(size_t)(j + 1u) * P.n + i] : 1.0f, l2 = have_lit ? lit[(size_t)(j + odd) * P.n + i + 1u] : 1.0f;
+    float a0 = 1.0f, a1 = 1.0f, a2 = 1.0f;
+    if constexpr (AMBIENT) {
+        a0 = 1.0f - amb_strength * (1.0f - sky[(size_t)j * P.n + i + odd]);
+        a1 = 1.0f - amb_strength * (1.0f - sky[(size_t)(j + 1u) * P.n + i]);
+        a2 = 1.0f - amb_strength * (1.0f - sky[(size_t)(j + odd) * P.n + i + 1u]);
+    }
+    const bool plain_l = l0 == 1.0f && l1 == 1.0f && l2 == 1.0f, plain_a = a0 == 1.0f && a1 == 1.0f && a2 == 1.0f;
+    if (plain_l && plain_a) return false;
+    float attr[3] = { 0.0f, 0.0f, 0.0f }, v = 1.0f, w = 1.0f;
     if constexpr (CLIPPED) {
         if (s.generic) {
             GVert g[3];
             load_prim(P, V.hblk, prim, g[0], g[1], g[2]);
             (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, attr);
             // lit rides through the clipper in the place of the height varying: the same crossings, the same piece
-            g[0].a[0] = l0; g[1].a[0] = l1; g[2].a[0] = l2;
             float la[3];
-            (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, la);
-            v = la[0];
+            if (!AMBIENT || !plain_l) {
+                g[0].a[0] = l0; g[1].a[0] = l1; g[2].a[0] = l2;
+                (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, la);
+                v = la[0];
+            }
+            if constexpr (AMBIENT) {
+                if (!plain_a) {
+                    g[0].a[0] = a0; g[1].a[0] = a1; g[2].a[0] = a2;
+                    (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, la);
+                    w = la[0];
+                }
+            }
         }
     }
     if (!s.generic) {
@@ -194,16 +213,18 @@ __device__ __forceinline__ bool sh_pixel(const FrameParams &P, const SetupView &
         float q0, q1, q2;
         record_weights(r0, r1, r2, px, py, q0, q1, q2);
         const float rQ = 1.0f / ((q0 + q1) + q2);
-        v = fmaf(q2, l2, fmaf(q1, l1, q0 * l0)) * rQ;
-        if (!(v < 1.0f)) return false;
+        if (!AMBIENT || !plain_l) v = fmaf(q2, l2, fmaf(q1, l1, q0 * l0)) * rQ;
+        if constexpr (AMBIENT) { if (!plain_a) w = fmaf(q2, a2, fmaf(q1, a1, q0 * a0)) * rQ; }
+        if (!(v < 1.0f) && !(AMBIENT && w < 1.0f)) return false;
         const float x0 = grid_coord(P, i + odd), x1 = grid_coord(P, i), x2 = grid_coord(P, i + 1u);
         const float z0 = grid_coord(P, j), z1 = grid_coord(P, j + 1u), z2 = grid_coord(P, j + odd);
         attr[0] = fmaf(q2, r2.h, fmaf(q1, r1.h, q0 * r0.h)) * rQ;
         attr[1] = fmaf(q2, x2, fmaf(q1, x1, q0 * x0)) * rQ;
         attr[2] = fmaf(q2, z2, fmaf(q1, z1, q0 * z0)) * rQ;
     }
-    if (!(v < 1.0f)) return false;
-    rgba = fragment_shader_lit(P, T, attr, v);
+    if (!(v < 1.0f) && !(AMBIENT && w < 1.0f)) return false;
+    // (an interpolated value an ulp above 1 shades as 1; without AMBIENT v is below 1 here)
+    rgba = AMBIENT ? fragment_shader_lit(P, T, attr, fminf(v, 1.0f), fminf(w, 1.0f)) : fragment_shader_lit(P, T, attr, v, 1.0f);
     return true;
 }
 
@@ -224,7 +245,7 @@ __global__ __launch_bounds__(256) void k_shadow_shade(FrameParams P, SetupView V
     const ShadeTables T = { s_lut, s_thr };
     for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
         uint32_t c;
-        if (id != 0u && sh_pixel<CLIPPED>(P, V, T, lit, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
+        if (id != 0u && sh_pixel<CLIPPED, false>(P, V, T, lit, nullptr, 0.0f, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
     });
 }
 

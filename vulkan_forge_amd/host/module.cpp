@@ -597,6 +597,32 @@ public:
         check(vf_terrain_debug_shadow_scans(t, &count));
         return count;
     }
+    // extension: ambient occlusion from a sky-view scan (argument rules: vulkan_forge_amd/_ambient.py)
+    void set_ambient_occlusion(bool enabled, float strength, float reach, py::object directions)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._ambient").attr("ambient_args")(enabled, strength, reach, directions);
+        py::array dirs = a[4].cast<py::array>();             // (D, 2) float32, contiguous
+        Borrow b(busy);
+        check(vf_terrain_set_ambient(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<float>(), a[3].cast<uint32_t>(), static_cast<const float *>(dirs.data())));
+        frame_current = false;
+    }
+    py::array_t<float> sky_view_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_sky_view_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    uint32_t debug_ambient_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_ambient_scans(t, &count));
+        return count;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -942,6 +968,13 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "steer shadow_field() too: set_shadows(False) without them puts the defaults back.")
         .def("shadow_field", &T::shadow_field)
         .def("debug_shadow_scans", &T::debug_shadow_scans)
+        .def("set_ambient_occlusion", &T::set_ambient_occlusion, py::arg("enabled") = true, py::kw_only(), py::arg("strength") = VF_AMBIENT_STRENGTH,
+             py::arg("reach") = VF_AMBIENT_REACH, py::arg("directions") = VF_AMBIENT_DIRECTIONS,
+             "Ambient occlusion from a sky-view scan of the height field (DESIGN.md 4i).  directions: how many of the default set, or a\n"
+             "(D, 2) array of (ux, uz).  The parameters are stored by every call, also one that disables, and steer sky_view_field() too:\n"
+             "set_ambient_occlusion(False) without them puts the defaults back.")
+        .def("sky_view_field", &T::sky_view_field)
+        .def("debug_ambient_scans", &T::debug_ambient_scans)
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
