@@ -340,7 +340,9 @@ __global__ __launch_bounds__(256) void k_pg_setup(FrameParams P, AxisTables A, u
     if (!slot) return;
     out[i] = o;
     int px0 = 1, px1 = 0, py0 = 1, py1 = 0;
-    if (edge) { ov_span(o.h.z - 1.0f, o.h.w + 1.0f, P.W, px0, px1); ov_span(__uint_as_float(o.rgba) - 1.0f, __uint_as_float(o.pad) + 1.0f, P.H, py0, py1); }
+    // x over the whole width of the bins, not the frame's: the last bin column of a frame that is no multiple of the bin width counts
+    // the crossings between the frame's edge and its own right edge itself (k_pg_backdrop gives a bin the crossings beyond it only)
+    if (edge) { ov_span(o.h.z - 1.0f, o.h.w + 1.0f, nbx * kOvBin, px0, px1); ov_span(__uint_as_float(o.rgba) - 1.0f, __uint_as_float(o.pad) + 1.0f, P.H, py0, py1); }
     if (px0 > px1 || py0 > py1) { box[i] = make_uint2(1u, 0u); return; }
     const uint32_t bx0 = (uint32_t)px0 / kOvBin, bx1 = (uint32_t)px1 / kOvBin, by0 = (uint32_t)py0 / kOvBin, by1 = (uint32_t)py1 / kOvBin;
     box[i] = make_uint2(bx0 | (by0 << 16), bx1 | (by1 << 16));
