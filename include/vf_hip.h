@@ -359,9 +359,18 @@ void vf_dem_destroy(vf_dem *d);
 /* add_terrain ingest (src/lib.rs:351-388): heights = (f32)src * exaggeration, row-major h rows x w cols */
 int vf_dem_set_heights_f32(vf_dem *d, const float *host, uint32_t w, uint32_t h, float exaggeration);
 int vf_dem_set_heights_f64(vf_dem *d, const double *host, uint32_t w, uint32_t h, float exaggeration);
-/* terrain_stats -> dem_stats_from_slice (src/lib.rs:905-932): out = {min, max, mean, std} */
+/* terrain_stats -> dem_stats_from_slice (src/lib.rs:905-932): out = {min, max, mean, std}.
+ * min / max: the reference starts both at heights[0] and replaces them by `<` / `>`, so a NaN FIRST sample gives min = max = NaN
+ * (and minmax-normalising that map gives all NaN); a NaN anywhere else is passed over.  The same here.  One difference remains:
+ * among zeros of both signs the reference keeps the first zero it meets, the reduction here orders floats as integers and
+ * reports -0 as min and +0 as max -- equal as numbers (==), not as bits.
+ * mean = (f32)(sum in f64 / n); std = sqrt((f32)(sum in f64 of (f32)((h - mean) * (h - mean)) / n)), h - mean and the square in f32
+ * with the f32 mean, as the reference forms them; the reference adds both sums in f32 in index order. */
 int vf_dem_stats(vf_dem *d, float out[4]);
-/* terrain_stats::min_max(data, clamp=true) (src/terrain_stats.rs:11-35): 1st / 99th percentile, stride-sampled above 65536 */
+/* terrain_stats::min_max(data, clamp=true) (src/terrain_stats.rs:11-35): 1st / 99th percentile, stride-sampled above 65536:
+ * step = n / 65536 (1 up to 65536 samples), the samples h[0], h[step], ... sorted, elements (size_t)((f32)m * 0.01f) and
+ * (size_t)((f32)m * 0.99f) of the m of them.  With a NaN among the samples the result is unspecified, as the reference's own
+ * sort (partial_cmp with Equal for the unordered) is. */
 int vf_dem_percentile_range(vf_dem *d, float *p1, float *p99);
 /* normalize_terrain -> normalize_in_place (src/lib.rs:934-951): mode 0 = minmax to [lo, hi], 1 = zscore */
 int vf_dem_normalize(vf_dem *d, int mode, float lo, float hi, float eps);

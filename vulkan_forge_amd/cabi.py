@@ -590,3 +590,76 @@ class Terrain:
         tm = Timings()
         self._check(self.lib.vf_terrain_timings(self.t, C.byref(tm)))
         return {k: getattr(tm, k) for k, _ in Timings._fields_}
+
+
+class Dem:
+    """Thin RAII wrapper over vf_ctx + vf_dem: the Renderer DEM path (heights resident on the device, statistics, normalisation,
+    the R32F texture round trip) for callers that want the entry points themselves, vf_dem_percentile_range among them."""
+
+    def __init__(self, device=0, lib=None):
+        self.lib = lib or load()
+        self.ctx, self.d = _vp(), _vp()
+        self._check(self.lib.vf_ctx_create(int(device), C.byref(self.ctx)))
+        self._check(self.lib.vf_dem_create(self.ctx, C.byref(self.d)))
+
+    def _check(self, rc):
+        if rc != VF_OK:
+            msg = self.lib.vf_last_error().decode()
+            raise VfError("No suitable GPU adapter" if rc == VF_ERR_NO_DEVICE else msg)
+
+    def close(self):
+        if self.d:
+            self.lib.vf_dem_destroy(self.d)
+            self.d = _vp()
+        if self.ctx:
+            self.lib.vf_ctx_destroy(self.ctx)
+            self.ctx = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def set_heights(self, heights, exaggeration=1.0):
+        """(h, w) float32 or float64, C-contiguous: heights = (f32)src * exaggeration on the device."""
+        a = np.asarray(heights)
+        if a.ndim != 2 or a.dtype not in (np.float32, np.float64) or not a.flags.c_contiguous:
+            raise TypeError("heights must be a C-contiguous 2-D array of float32 or float64")
+        fn = self.lib.vf_dem_set_heights_f32 if a.dtype == np.float32 else self.lib.vf_dem_set_heights_f64
+        self._check(fn(self.d, a.ctypes.data, a.shape[1], a.shape[0], float(exaggeration)))
+
+    def stats(self):
+        """(min, max, mean, std) as float32 scalars."""
+        out = np.zeros(4, np.float32)
+        self._check(self.lib.vf_dem_stats(self.d, out.ctypes.data))
+        return tuple(out)
+
+    def percentile_range(self):
+        """(p1, p99) as float32 scalars."""
+        p1, p99 = _f(), _f()
+        self._check(self.lib.vf_dem_percentile_range(self.d, C.byref(p1), C.byref(p99)))
+        return np.float32(p1.value), np.float32(p99.value)
+
+    def normalize(self, mode, lo=0.0, hi=1.0, eps=1e-8):
+        """mode "minmax" (to [lo, hi]) or "zscore", in place on the device."""
+        self._check(self.lib.vf_dem_normalize(self.d, {"minmax": 0, "zscore": 1}[mode], float(lo), float(hi), float(eps)))
+
+    def upload(self):
+        self._check(self.lib.vf_dem_upload_height(self.d))
+
+    def texture_size(self):
+        w, h = _u32(), _u32()
+        self._check(self.lib.vf_dem_texture_size(self.d, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def read_patch(self, x=0, y=0, w=None, h=None):
+        """(h, w) float32 of the uploaded texture; the whole texture by default."""
+        tw, th = self.texture_size()
+        x, y = int(x), int(y)
+        w, h = (tw - x if w is None else int(w)), (th - y if h is None else int(h))
+        if x < 0 or y < 0 or w <= 0 or h <= 0:
+            raise ValueError(f"patch origin must be >= 0 and patch dimensions > 0 (x={x}, y={y}, w={w}, h={h}; texture {tw} x {th})")
+        out = np.empty((h, w), np.float32)
+        self._check(self.lib.vf_dem_read_patch(self.d, x, y, w, h, out.ctypes.data))
+        return out

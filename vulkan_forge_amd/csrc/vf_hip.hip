@@ -3052,7 +3052,8 @@ static int dem_stats_impl(vf_dem *d, float out[4])
     double var = 0.0;
     for (double v : part) var += v;
     auto unorder = [](uint32_t u) { uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u; float f; std::memcpy(&f, &b, 4); return f; };
-    // an all-NaN map leaves the init pattern; the reference would report its first element (NaN)
+    // a NaN first sample leaves 0 / 0xFFFFFFFF (k_dem_minmaxsum), which unorder to NaNs by themselves: the reference reports its first
+    // element then.  The init pattern survives no map (sample 0 is a number or a NaN); it is mapped to NaN all the same.
     out[0] = mm[0] == 0xFFFFFFFFu ? NAN : unorder(mm[0]);
     out[1] = mm[1] == 0u ? NAN : unorder(mm[1]);
     out[2] = mean;

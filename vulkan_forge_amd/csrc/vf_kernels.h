@@ -2421,10 +2421,14 @@ __global__ __launch_bounds__(256) void k_dem_minmaxsum(const float *__restrict__
     __shared__ uint32_t s_lo[4], s_hi[4];
     uint32_t lo = 0xFFFFFFFFu, hi = 0u;
     double sum = 0.0;
+    // A NaN never wins a `<` / `>` comparison in the reference loop, but that loop STARTS from heights[0]: a NaN there is never
+    // replaced either, and min = max = NaN.  The thread that owns sample 0 says so with the two extremes of the ordered range
+    // (0 = the order of the all-ones NaN, 0xFFFFFFFF = that of 0x7FFFFFFF), which win every min / max below and in `mm`.
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) {
         const float v = h[k];
         const uint32_t o = float_order(v);
-        if (v == v) { lo = min(lo, o); hi = max(hi, o); }     // NaN never wins a `<` / `>` comparison in the reference loop either
+        if (v == v) { lo = min(lo, o); hi = max(hi, o); }
+        else if (k == 0) { lo = 0u; hi = 0xFFFFFFFFu; }
         sum += (double)v;
     }
     for (int o = 32; o > 0; o >>= 1) {
