@@ -11,73 +11,28 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstdint>
-#include <random>
+#include "raster_cases.h"           // the triangle / window stream and the brute-force covered(): shared with tests/hip/raster_device_fuzz.hip
 #include "../../vulkan_forge_amd/csrc/vf_raster.h"
 
 using namespace vf;
-
-static bool covered(const int32_t X[3], const int32_t Y[3], int32_t px, int32_t py)
-{
-    const int64_t Px = (int64_t)px * 256 + 128, Py = (int64_t)py * 256 + 128;
-    for (int i = 0; i < 3; ++i) {
-        const int a = i == 0 ? 1 : (i == 1 ? 2 : 0), b = i == 0 ? 2 : (i == 1 ? 0 : 1);
-        const int64_t A = (int64_t)Y[b] - Y[a], B = -((int64_t)X[b] - X[a]);
-        const int64_t e = A * (Px - X[a]) + B * (Py - Y[a]);
-        const bool tl = A > 0 || (A == 0 && B > 0);
-        if (!(e > 0 || (e == 0 && tl))) return false;
-    }
-    return true;
-}
+using raster_cases::covered;
 
 int main(int argc, char **argv)
 {
     const long cases = argc > 1 ? atol(argv[1]) : 200000;
-    std::mt19937_64 rng(argc > 2 ? (uint64_t)atoll(argv[2]) : 1);
-    auto uni = [&](int64_t lo, int64_t hi) { return (int64_t)(lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1))); };
+    raster_cases::Stream stream(argc > 2 ? (uint64_t)atoll(argv[2]) : 1);
     long lines = 0, nonempty = 0, fallback = 0, irregular_tris = 0, tris = 0, bad = 0;
     long k_tris[10] = {0}, k_irr[10] = {0}, k_lines[10] = {0}, k_fb[10] = {0};
     long group_lines = 0, group_slack = 0;
     for (long c = 0; c < cases && bad < 10; ++c) {
-        int32_t X[3], Y[3];
-        const int kind = (int)uni(0, 9);
-        const int32_t cx = (int32_t)uni(-20000, 1100000), cy = (int32_t)uni(-20000, 1100000);    // 24.8: around a 4096^2 target
-        if (kind <= 4) {                                   // sliver: long, thin, any direction (what a noise terrain is made of)
-            const double ang = (double)uni(0, 6283185) * 1e-6, len = (double)uni(256, 80000), wid = (double)uni(1, 400);
-            const double dx = cos(ang), dy = sin(ang);
-            X[0] = cx; Y[0] = cy;
-            X[1] = cx + (int32_t)(len * dx); Y[1] = cy + (int32_t)(len * dy);
-            X[2] = cx + (int32_t)(0.5 * len * dx - wid * dy); Y[2] = cy + (int32_t)(0.5 * len * dy + wid * dx);
-            if (kind == 0) { X[1] = X[0]; }                // an edge exactly parallel to y
-            if (kind == 1) { Y[1] = Y[0]; }                // ... to x
-        } else if (kind <= 6) {                            // general triangle up to ~300 px
-            for (int k = 0; k < 3; ++k) { X[k] = cx + (int32_t)uni(-40000, 40000); Y[k] = cy + (int32_t)uni(-40000, 40000); }
-        } else if (kind == 7) {                            // vertices and edges through pixel centres (the top-left rule decides)
-            for (int k = 0; k < 3; ++k) { X[k] = ((cx >> 8) + (int32_t)uni(-6, 6)) * 256 + 128; Y[k] = ((cy >> 8) + (int32_t)uni(-6, 6)) * 256 + 128; }
-        } else if (kind == 8) {                            // small, sub-pixel scale
-            for (int k = 0; k < 3; ++k) { X[k] = cx + (int32_t)uni(-600, 600); Y[k] = cy + (int32_t)uni(-600, 600); }
-        } else {                                           // huge: extents just below the fast path's limit (2^24)
-            for (int k = 0; k < 3; ++k) { X[k] = cx + (int32_t)uni(-8000000, 8000000); Y[k] = cy + (int32_t)uni(-8000000, 8000000); }
-        }
-        int64_t area2 = (int64_t)(X[1] - X[0]) * (Y[2] - Y[0]) - (int64_t)(Y[1] - Y[0]) * (X[2] - X[0]);
-        if (area2 == 0) continue;
-        if (area2 > 0) { std::swap(X[1], X[2]); std::swap(Y[1], Y[2]); }     // front-facing = negative area in y-down pixels
-        const int32_t xmin = std::min(X[0], std::min(X[1], X[2])), xmax = std::max(X[0], std::max(X[1], X[2]));
-        const int32_t ymin = std::min(Y[0], std::min(Y[1], Y[2])), ymax = std::max(Y[0], std::max(Y[1], Y[2]));
-        if ((uint32_t)xmax - (uint32_t)xmin >= (1u << 24) || (uint32_t)ymax - (uint32_t)ymin >= (1u << 24)) continue;
-        // a tile (or strip) window that meets the bounding box
-        const int32_t bx0 = (xmin + 127) >> 8, bx1 = (xmax - 128) >> 8, by0 = (ymin + 127) >> 8, by1 = (ymax - 128) >> 8;
-        if (bx0 > bx1 || by0 > by1) continue;
-        const int32_t tw = (int32_t)(1 << uni(2, 6)), th = 64;
-        const int32_t tx_lo = (int32_t)uni(bx0 - tw + 1, bx1), ty_lo = (int32_t)uni(by0 - th + 1, by1);
-        const int32_t tx_hi = tx_lo + tw - 1, ty_hi = ty_lo + (int32_t)uni(0, th - 1);
-        const int32_t px0 = std::max(bx0, tx_lo), px1 = std::min(bx1, tx_hi), py0 = std::max(by0, ty_lo), py1 = std::min(by1, ty_hi);
-        if (px0 > px1 || py0 > py1) continue;
+        raster_cases::Case rc;
+        if (!stream.draw(rc)) continue;
         ++tris;
-        const bool cols = (px1 - px0) <= (py1 - py0);
-        const int32_t U[3] = { cols ? X[0] : Y[0], cols ? X[1] : Y[1], cols ? X[2] : Y[2] };
-        const int32_t V[3] = { cols ? Y[0] : X[0], cols ? Y[1] : X[1], cols ? Y[2] : X[2] };
-        const int32_t n_outer = cols ? px1 - px0 : py1 - py0, n_inner = cols ? py1 - py0 : px1 - px0;
-        const int32_t u0c = (cols ? px0 : py0) * 256 + 128, v0c = (cols ? py0 : px0) * 256 + 128;
+        const raster_cases::SolverArgs sa = raster_cases::solver_args(rc);
+        const int kind = rc.kind;
+        const int32_t *X = rc.X, *Y = rc.Y, *U = sa.U, *V = sa.V;
+        const int32_t px0 = rc.px0, py0 = rc.py0, n_outer = sa.n_outer, n_inner = sa.n_inner, u0c = sa.u0c, v0c = sa.v0c;
+        const bool cols = sa.cols;
         SpanSetup S;
         span_setup(U, V, !cols, u0c, v0c, n_outer, S);
         irregular_tris += S.regular ? 0 : 1;

@@ -1,8 +1,8 @@
 """The span solver of the tile kernel's fast raster path (vulkan_forge_amd/csrc/vf_raster.h: FP32 first, exact FP64 only where FP32
 cannot decide) compiled for the HOST and checked line by line against a brute-force int64 evaluation of the coverage rule
 (pixel centres, top-left rule).  The hardware's reciprocal is a 1-ulp estimate: the harness runs with the
-host reciprocal as is and pushed one ulp up / down.  The GPU parity tests then check the same header as device code against the
-oracle."""
+host reciprocal as is and pushed one ulp up / down.  tests/test_gpu_raster_device.py runs the same case stream
+(tests/cpp/raster_cases.h) through the same header as device code, and the GPU parity tests hold whole frames against the oracle."""
 import os
 import subprocess
 
