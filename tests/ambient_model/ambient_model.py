@@ -18,12 +18,38 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "shadow_model"))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
+import overlay_scenes  # noqa: E402
 import shadow_model as shm  # noqa: E402
 om = shm.om
 
 # The GPU field tests: (grid, exaggeration, reach, D) on overlay_scenes.heights(4, (97, 131)) -- a grid that is no multiple of 8 or 64,
 # a reach that crosses one tile boundary, one that crosses two, many chunks plus one, and a single direction.
 FIELD_CASES = [(203, 0.6, 16.0, 16), (130, 0.6, 70.0, 16), (520, 0.6, 130.0, 16), (1025, 0.6, 20.0, 16), (203, 0.6, 16.0, 1)]
+# The same at the limits the C ABI accepts (tests/test_gpu_limits.py): reach 1024 cells on a grid that does not clip it, along one x-major
+# and one z-major axis direction and along the diagonal (a list of directions in place of a count), and 64 directions.  At reach 1024
+# a vertex's scan looks back over 1024 / 64 = 16 earlier tiles, which is what the kernel's table is sized for.  On limit_heights():
+# over white noise, and over the analytic surface's hill along z, every horizon is a few cells away and the far tiles of the scan
+# decide nothing; in a bowl the rim is the horizon of the vertices that look across it, and the field of reach 1024 differs from
+# the one of reach 512 at 29-51 % of the vertices (test_ambient_model.py asserts more than 10 % on the same surface at a quarter of
+# the grid and of the reach, which costs a sixty-fourth).
+LIMIT_FIELD_CASES = [(1100, 0.6, 1024.0, ((1, 0),)), (1100, 0.6, 1024.0, ((0, -1),)), (1100, 0.6, 1024.0, ((1, 1),)), (203, 0.6, 16.0, 64)]
+
+
+def limit_heights():
+    """the texture of LIMIT_FIELD_CASES: a bowl of depth 2 over the texture's square, and overlay_scenes' noise at a fiftieth of its height"""
+    v, u = np.meshgrid(np.linspace(-1.0, 1.0, 97), np.linspace(-1.0, 1.0, 131), indexing="ij")
+    return (overlay_scenes.heights(4, (97, 131)) * np.float32(0.02) + (u * u + v * v)).astype(np.float32)
+
+
+def case_directions(D):
+    """the (D, 2) float32 directions of a field case: the library's default set of D, or the case's own list"""
+    if isinstance(D, int):
+        from vulkan_forge_amd._ambient import directions
+        return directions(D)
+    return np.array(D, np.float32).reshape(-1, 2)
+
+
 # an exact diagonal, both axes, a nearly-axis direction in each major axis, general ones in other quadrants, none normalised
 IRREGULAR = np.array([(1, 1), (1, 0), (0, -1), (1, 1e-3), (-2e-3, 1), (-0.9, 0.31), (0.31, -0.9), (-3, -3), (0, 2)], np.float32)
 # The GPU frame tests' scene: overlay_scenes' white noise at a hundredth of its height, so that the analytic surface under it shows.
@@ -41,9 +67,7 @@ def scene_directions():
 
 
 def scene_heights(seed=7):
-    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
-    from overlay_scenes import heights
-    return (heights(seed) * np.float32(0.01)).astype(np.float32)
+    return (overlay_scenes.heights(seed) * np.float32(0.01)).astype(np.float32)
 
 
 _lib = None

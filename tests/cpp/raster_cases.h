@@ -1,6 +1,7 @@
 // raster_cases.h -- the case stream of the span-solver checks, stated once: random triangles of ten kinds (24.8 fixed point, around a
-// 4096^2 target) with a tile (or strip) window that meets their bounding box, and the brute-force int64 evaluation of the coverage
-// rule of DESIGN.md section 4 (pixel centres, top-left rule on inside-positive edge functions) they are all held against.
+// 4096^2 target, or around one of another extent up to the frame limit of 16384) with a tile (or strip) window that meets their
+// bounding box, and the brute-force int64 evaluation of the coverage rule of DESIGN.md section 4 (pixel centres, top-left rule on
+// inside-positive edge functions) they are all held against.
 // Users: tests/cpp/raster_fuzz.cpp (vf_raster.h compiled for the host) and tests/hip/raster_device_fuzz.hip (the same header, and the
 // line loop that walks it, as device code).  The same seed gives the same triangles in both.
 #pragma once
@@ -50,7 +51,8 @@ static inline SolverArgs solver_args(const Case &c)
 
 struct Stream {
     std::mt19937_64 rng;
-    explicit Stream(uint64_t seed) : rng(seed) {}
+    int64_t centre_hi;                         // centres run from -20000 to 51424 past the target's far edge (1100000 at the default extent)
+    explicit Stream(uint64_t seed, int64_t extent = 4096) : rng(seed), centre_hi(extent * 256 + 51424) {}
     int64_t uni(int64_t lo, int64_t hi) { return (int64_t)(lo + (int64_t)(rng() % (uint64_t)(hi - lo + 1))); }
 
     // One draw; false: rejected (no area, too large, no pixel centre in the box, window beside the box) -- the draw still counts.
@@ -58,7 +60,7 @@ struct Stream {
     {
         int32_t *X = c.X, *Y = c.Y;
         const int kind = c.kind = (int)uni(0, 9);
-        const int32_t cx = (int32_t)uni(-20000, 1100000), cy = (int32_t)uni(-20000, 1100000);    // 24.8: around a 4096^2 target
+        const int32_t cx = (int32_t)uni(-20000, centre_hi), cy = (int32_t)uni(-20000, centre_hi);    // 24.8: around the target
         if (kind <= 4) {                                   // sliver: long, thin, any direction (what a noise terrain is made of)
             const double ang = (double)uni(0, 6283185) * 1e-6, len = (double)uni(256, 80000), wid = (double)uni(1, 400);
             const double dx = cos(ang), dy = sin(ang);

@@ -1,7 +1,7 @@
 // raster_fuzz.cpp -- host check of vulkan_forge_amd/csrc/vf_raster.h (the span solver of the tile kernel's fast raster path)
 // against a brute-force int64 evaluation of the coverage rule of DESIGN.md section 4 (pixel centres, top-left rule on
 // inside-positive edge functions).  Built and run by tests/test_raster_spans.py:
-//     g++ -O2 -ffp-contract=off [-DVF_RASTER_RCP_ULPS=-1|0|1] tests/cpp/raster_fuzz.cpp -o raster_fuzz && ./raster_fuzz <cases> <seed>
+//     g++ -O2 -ffp-contract=off [-DVF_RASTER_RCP_ULPS=-1|0|1] tests/cpp/raster_fuzz.cpp -o raster_fuzz && ./raster_fuzz <cases> <seed> [target extent]
 // For every random triangle x tile window x line it requires
 //   - stage 1 (span_line) to contain the true span,
 //   - stage 2 (span_confirm), when it accepts, to make the stage-1 span equal to the true span,
@@ -20,7 +20,7 @@ using raster_cases::covered;
 int main(int argc, char **argv)
 {
     const long cases = argc > 1 ? atol(argv[1]) : 200000;
-    raster_cases::Stream stream(argc > 2 ? (uint64_t)atoll(argv[2]) : 1);
+    raster_cases::Stream stream(argc > 2 ? (uint64_t)atoll(argv[2]) : 1, argc > 3 ? atol(argv[3]) : 4096);
     long lines = 0, nonempty = 0, fallback = 0, irregular_tris = 0, tris = 0, bad = 0;
     long k_tris[10] = {0}, k_irr[10] = {0}, k_lines[10] = {0}, k_fb[10] = {0};
     long group_lines = 0, group_slack = 0;

@@ -4,7 +4,7 @@
 // v_cvt_flr_i32_f32, rs_med3 v_med3_f32, span_exact device FP64 division and FMA, all of it under the library's -O3 / -mllvm
 // switches -- and raster_fast exists as device code only.  Built (with __graft_entry__.HIPCC_FLAGS) and run by
 // tests/test_gpu_raster_device.py:
-//     raster_device_fuzz <draws> <seed> <soup cases>
+//     raster_device_fuzz <draws> <seed> <soup cases> [target extent]      (0 soup cases: part 1 alone)
 //
 // Part 1, spans: the case stream of raster_cases.h, one thread per accepted case.  The kernel calls span_setup, span_group for every
 // run of four lines, span_line / span_confirm / span_exact for every line and stores what they return; the host makes the four
@@ -420,8 +420,9 @@ int main(int argc, char **argv)
     const long draws = argc > 1 ? atol(argv[1]) : 250000;
     const uint64_t seed = argc > 2 ? (uint64_t)atoll(argv[2]) : 1;
     const long nsoup = argc > 3 ? atol(argv[3]) : 24000;
+    const long extent = argc > 4 ? atol(argv[4]) : 4096;      // the target the triangles lie around (raster_cases.h)
     const double t0 = now_s();
-    raster_cases::Stream stream(seed);
+    raster_cases::Stream stream(seed, extent);
     std::vector<raster_cases::Case> cs;
     for (long c = 0; c < draws; ++c) {
         raster_cases::Case rc;

@@ -231,6 +231,7 @@ def _amb(reach, dirs, strength=0.6):
 
 
 _FAN = [(-1, 0), (-0.9, 0.31), (-0.9, -0.31)]
+_LONG_FOVY = 2.0 * math.degrees(math.atan(0.5 * 1.5 / 6.0))   # from 6 units above, the long side of a frame sees about 0.6 of the terrain's 3 units
 # Found by this soak (frame_of_one_column), reduced: a fill whose right edge crosses rows 15-18 at x = 19.4 .. 23.5 of a 17-pixel-wide
 # frame -- beyond the frame and inside its last 16-pixel bin column.  k_pg_setup clipped an edge's bins to the frame, the backdrop mask
 # gives a bin only the crossings beyond its right edge, so pixel column 16 lost that crossing and the fill
@@ -261,6 +262,15 @@ _SPECS = [
             more_overlays=[("polygons", dict(polygons=[[GAP_RING]], fill_rgba=(230, 40, 40, 255), line_rgba=None, line_width_px=1.0, drape=False))]),
     _corner(16, "frame_of_one_column", W=1, H=70, grid=17, ambient=_amb(16.0, _FAN)),
     _corner(17, "frame_of_one_row_far_plane_cuts", W=130, H=1, grid=16, zfar=4.8, znear=4.5, ambient=_amb(1.5, _round(3))),
+    # the frame limit of the C ABI in either axis: 256 tile columns / rows, 1024 overlay bins, pixel boxes at the end of int16.  A camera
+    # looking steeply down (up stays +y, so x runs along the width and z down the height) whose narrow field of view lets the terrain
+    # overfill the long side; a line on the world axis that projects to the frame's centre row / column carries an overlay into the last bin (tests/test_feature_soak_cases.py asserts it)
+    _corner(19, "frame16384x24", W=16384, H=24, grid=257, eye=(0.0, 6.0, 0.6), fovy=_LONG_FOVY / (16384 / 24), znear=0.1, zfar=100.0, ambient=_amb(8.0, _FAN),
+            more_overlays=[("lines", dict(paths=[np.array([[-1.6, 0.0, 0.0], [1.6, 0.0, 0.0]], f32)], width_px=3.0, rgba=(250, 220, 30, 255), cap="butt",
+                                          drape=False, occlude=False, depth_bias=0.0))]),
+    _corner(20, "frame24x16384", W=24, H=16384, grid=257, eye=(0.0, 6.0, 0.6), fovy=_LONG_FOVY, znear=0.1, zfar=100.0, ambient=_amb(16.0, _FAN),
+            more_overlays=[("lines", dict(paths=[np.array([[0.0, 0.0, -1.6], [0.0, 0.0, 1.6]], f32)], width_px=3.0, rgba=(250, 220, 30, 255), cap="butt",
+                                          drape=False, occlude=False, depth_bias=0.0))]),
 ]
 
 

@@ -181,16 +181,24 @@ def test_the_reach_is_isotropic():
         assert dist.max() <= reach + 0.5 and dist.max() > reach - g - 0.5, (d, dist.max())
 
 
-@pytest.mark.parametrize("grid,exag,reach,D", abm.FIELD_CASES)
+@pytest.mark.parametrize("grid,exag,reach,D", abm.FIELD_CASES + abm.LIMIT_FIELD_CASES)
 def test_the_gpu_tests_fields_are_partly_occluded(grid, exag, reach, D):
     import oracle
-    from vulkan_forge_amd._ambient import directions
-    h = heights(4, (97, 131))
+    limit = (grid, exag, reach, D) in abm.LIMIT_FIELD_CASES
+    h = abm.limit_heights() if limit else heights(4, (97, 131))
     u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, 64, 64, *CAMERAS["default"]), f32).reshape(44)
     u[38] = exag
-    sky = abm.field(u, h, grid, directions(D), reach)
-    assert ((sky > 0.1) & (sky < 0.9)).mean() >= 0.1
+    sky = abm.field(u, h, grid, abm.case_directions(D), reach)
+    assert ((sky > 0.1) & (sky < 0.9)).mean() > 0.1
     assert (sky >= 0).all() and (sky <= 1).all()
+    if limit and reach == 1024.0:
+        # the far half of the reach decides horizons: a scan that stops short differs.  Shown at a quarter of the grid and of the
+        # reach: the bowl and the noise are stated in world units, so the same horizons lie a quarter as many steps away, and the
+        # two fields cost a sixty-fourth of a second field at full size
+        assert grid > reach
+        g4, dirs = (grid + 3) // 4, abm.case_directions(D)
+        assert g4 > reach / 4
+        assert (abm.field(u, h, g4, dirs, reach / 4) != abm.field(u, h, g4, dirs, reach / 8)).mean() > 0.1
 
 
 @pytest.mark.parametrize("size", [(96, 64), (256, 256)])

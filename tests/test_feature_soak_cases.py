@@ -57,7 +57,7 @@ def test_every_mutation_occurs_and_every_corner_runs_the_chain(oracle):
 def test_the_corners_hold_the_edges_they_are_named_for(oracle):
     by = {c["name"]: c for c in sf.CORNERS}
     assert {c["grid"] for c in sf.CORNERS} >= {2, 3, 9, 10, 63, 64, 65, 129}
-    assert {(c["W"], c["H"]) for c in sf.CORNERS} >= {(1, 1), (15, 17), (16, 16), (17, 15), (64, 64), (65, 63)}
+    assert {(c["W"], c["H"]) for c in sf.CORNERS} >= {(1, 1), (15, 17), (16, 16), (17, 15), (64, 64), (65, 63), (16384, 24), (24, 16384)}
     assert {len(c["ambient"]["directions"]) for c in sf.CORNERS} >= {1, 64}
     assert {(c["grid"], c["ambient"]["reach"]) for c in sf.CORNERS} >= {(5, 1.0), (5, 1024.0)}
     assert {c["exaggeration"] for c in sf.CORNERS} >= {0.0, -2.0} and {c["spacing"] for c in sf.CORNERS} >= {0.3, 2.5}
@@ -88,6 +88,25 @@ def test_the_odd_frames_draw_overlays_in_their_partial_last_bins(oracle, name):
     W, H = c["W"], c["H"]
     assert W % 16 and H % 16
     assert drawn[:, 16 * (W // 16):].any() and drawn[16 * (H // 16):, :].any()
+
+
+@pytest.mark.parametrize("name", ["frame16384x24", "frame24x16384"])
+def test_the_frame_limit_corners_reach_the_last_bin_and_both_outer_tiles(oracle, name):
+    """the corners at the C ABI's frame limit, from the models alone: the terrain covers the first and the last tile column (wide) or
+    row (tall), the overlays change pixels in the last 16-pixel bin column or row, and the shade pass writes part of the covered
+    pixels again, not all and not none; everything is on, and pick asks for the pixels at the four corners (soak_features.run_case)"""
+    c = sf.CORNERS.named(name)
+    W, H = c["W"], c["H"]
+    assert max(W, H) == 16384 and c["grid"] >= 129 and c["features"] == "both" and len(c["ambient"]["directions"]) == len(sf._FAN)
+    assert {k for k, _ in c["overlays"]} == {"points", "lines", "polygons", "contours"}
+    e = sf.expected(c, sf.featured(c, sf.initial_state(c), overlays=True))
+    covered = e["vis"] != 0
+    drawn = (e["frame"] != e["shaded"]).any(axis=2)
+    if W > H:
+        covered, drawn = covered.T, drawn.T                   # (the long side first)
+    assert covered[:64].any() and covered[-64:].any()
+    assert drawn[-16:].any()
+    assert 0.1 < e["mask"].sum() / covered.sum() < 0.9
 
 
 def test_expected_is_deterministic(oracle):

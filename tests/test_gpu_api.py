@@ -60,10 +60,12 @@ def test_png_scanlines_are_filtered_on_the_gpu_like_the_host_encoder(tmp_path, l
     from test_host_api import _png_scanlines
     from vulkan_forge_amd import cabi
     import oracle as O
-    for W, H, G in ((200, 120, 32), (1, 1, 2), (257, 65, 16), (1920, 1080, 256)):
+    import limit_cases as lc
+    for W, H, G in ((200, 120, 32), (1, 1, 2), (257, 65, 16), (1920, 1080, 256), (16384, 3, 257), (3, 16384, 257)):
         t = cabi.Terrain(W, H, G, luts["terrain"])
         try:
-            t.set_uniforms(O.default_uniforms(1, W, H))
+            # (at the frame limit the default camera would show a sliver of the terrain: a camera under which it overfills the long side)
+            t.set_uniforms(O.default_uniforms(1, W, H) if max(W, H) < 16384 else O.look_at_uniforms(1, W, H, *lc.top_down(W, H)))
             t.set_height(np.random.default_rng(W).random((G, G), dtype=np.float32) * np.float32(0.5) - np.float32(0.25))
             t.render()
             rgba, scan = t.read_rgba(), t.read_png_scanlines()
@@ -200,7 +202,7 @@ def test_cabi_misuse_reports_errors(luts):
     assert lib.vf_ctx_create(0, C.byref(ctx)) == cabi.VF_OK
     t = C.c_void_p()
     lut = np.ascontiguousarray(luts["viridis"], np.uint8).reshape(1024)
-    for w, h, g in ((0, 10, 8), (10, 0, 8), (20000, 10, 8), (10, 10, 9000)):      # (grid < 2 is raised to 2 like src/terrain/mod.rs:260)
+    for w, h, g in ((0, 10, 8), (10, 0, 8), (20000, 10, 8), (16385, 10, 8), (10, 16385, 8), (10, 10, 9000)):      # (grid < 2 is raised to 2 like src/terrain/mod.rs:260)
         assert lib.vf_terrain_create(ctx, w, h, g, lut.ctypes.data, 1, C.byref(t)) == cabi.VF_ERR_INVALID, (w, h, g)
         assert lib.vf_last_error()
     assert lib.vf_terrain_create(ctx, 64, 48, 8, None, 1, C.byref(t)) == cabi.VF_ERR_INVALID

@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
 
 SRC = os.path.join(ROOT, "tests", "hip", "raster_device_fuzz.hip")
 DRAWS, SEED, SOUP = 250000, 20250816, 24000           # draws and seed of tests/test_raster_spans.py (ulps 0)
+LIMIT_EXTENT, LIMIT_SEED = 16384, 20261018            # extent and seed of tests/test_raster_spans.py's run around the largest frame
 _RUN = {}                                              # the child's outcome: it runs once, whatever becomes of it
 
 
@@ -48,7 +49,7 @@ def _build(exe):
 
 def _child(tmp_path_factory):
     if not _RUN:
-        exe = str(tmp_path_factory.mktemp("raster_device") / "raster_device_fuzz")
+        exe = _RUN["exe"] = str(tmp_path_factory.mktemp("raster_device") / "raster_device_fuzz")
         _RUN["rc"], _RUN["out"] = None, ""
         _build(exe)
         try:
@@ -84,6 +85,18 @@ def test_span_solver_as_device_code_against_brute_force(fuzz_output):
         # bounds of the host test carry over (eps, and with it the fallback decision, is computed from the inputs alone)
         if k in (2, 3, 4, 5, 6, 8):
             assert irregular < 0.2 and fallback < 0.1, (k, kinds[k])
+
+
+def test_span_solver_as_device_code_around_a_16384_target(fuzz_output):
+    """The span part alone (no soup) on the stream around the largest frame the C ABI accepts: centres up to 16384 * 256 + 51424.
+    The solver works in window-relative coordinates, so the bounds of the run above carry over.  (`fuzz_output`: the program is
+    built once, and after a first run that did not finish this one is not started.)"""
+    r = subprocess.run([_RUN["exe"], str(DRAWS), str(LIMIT_SEED), "0", str(LIMIT_EXTENT)], capture_output=True, text=True, timeout=120)
+    out = r.stdout + r.stderr
+    print(out)
+    assert r.returncode in (0, 1), f"raster_device_fuzz did not finish (exit {r.returncode}):\n{out[-3000:]}"
+    test_span_solver_as_device_code_against_brute_force(out)
+    assert not any(l.startswith("soup") for l in out.splitlines())
 
 
 def test_raster_fast_on_triangle_soup_against_brute_force(fuzz_output):
