@@ -554,6 +554,38 @@ int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream
 int vf_terrain_debug_ambient_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
 int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count);
 
+/* ---- a draped image layer: an RGBA raster as the terrain's albedo ----------------------------------
+ * One image per handle: (ih, iw) texels of sRGB bytes with straight alpha, row-major, row 0 at the extent's z0 and column 0 at its
+ * x0 (as the height array: row = z index, column = x index).  extent = (x0, z0, x1, z1) in the world plane of the grid, whose
+ * vertices lie at -1.5 ... 1.5 in x and z; NULL: the whole grid.  It may reach outside the grid or cover a part of it.
+ *
+ * vf_terrain_set_drape: the handle keeps a device copy made at the call (a snapshot; a second call replaces it).  channels 3: RGB,
+ * alpha 255.  From then on vf_terrain_render draws the frame as before, with the visibility store on, then writes again every
+ * covered pixel the image reaches with a sample that is not transparent: fs_main with the colormap value of each channel replaced
+ * by opacity * sample + (1 - opacity * alpha) * colormap, the sample filtered on premultiplied linear values, always in the exact
+ * arithmetic (both shade modes), with cast shadows and ambient occlusion as their passes apply them.  Other pixels keep the frame's
+ * bytes.  Overlays composite afterwards; geometry buffers and the diagnostics frames are unaffected.
+ * 1 <= iw, ih <= VF_DRAPE_SIZE_MAX; extent finite with x1 > x0 and z1 > z0; opacity in [0, 1]; filter VF_DRAPE_NEAREST or
+ * VF_DRAPE_LINEAR.  Anything else, a sharded handle (and sharding a handle that holds a drape), and vf_terrain_render_batch /
+ * _render_batch_host on a handle that holds a drape are refused with VF_ERR_INVALID and change nothing.
+ * vf_terrain_set_drape_device: the same from device memory (iw * ih * 4 bytes, RGBA), copied device to device on `stream` (NULL:
+ * the context's stream); later frames of the handle are ordered behind the copy by the library.
+ * vf_terrain_clear_drape: frees the copy; the handle draws as before.  A handle that never sets a drape allocates and launches
+ * nothing for it.
+ * vf_terrain_drape_info: the drape as set; *iw = 0: none (the other outputs are not written then).  Any output may be NULL. */
+#define VF_DRAPE_SIZE_MAX 16384
+#define VF_DRAPE_NEAREST 0
+#define VF_DRAPE_LINEAR 1
+int vf_terrain_set_drape(vf_terrain *t, const uint8_t *rgba, uint32_t iw, uint32_t ih, uint32_t channels /* 3 | 4 */,
+                         const float extent[4], float opacity, int filter);
+int vf_terrain_set_drape_device(vf_terrain *t, const void *dev_rgba /* iw*ih*4 bytes */, uint32_t iw, uint32_t ih,
+                                const float extent[4], float opacity, int filter, void *stream);
+int vf_terrain_clear_drape(vf_terrain *t);
+int vf_terrain_drape_info(const vf_terrain *t, uint32_t *iw, uint32_t *ih, float extent[4], float *opacity, int *filter);  /* iw = 0: none */
+/* Diagnostics: mean time in ms of `repeats` back-to-back launches of the drape shade pass alone (with the cast shadows and the
+ * ambient occlusion that are on), for the frame rendered last (drawn again into scratch buffers), after one warm-up. */
+int vf_terrain_debug_drape_stage(vf_terrain *t, uint32_t repeats, float *ms);   /* the shade pass alone, like the shadow one */
+
 #ifdef __cplusplus
 }
 #endif

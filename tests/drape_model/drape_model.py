@@ -1,0 +1,100 @@
+"""ctypes loader of the draped-image CPU model (drape_model.c), and the image the drape tests share.
+
+    import drape_model as drm
+    frame, rewritten = drm.frame(rgba, vis, uniforms, height, grid, lut_rgba8, image, extent=None, opacity=1.0, filter="linear",
+                                 lit=None, sky=None, strength=0.0, shade_mode=0)
+    frame, rewritten, sample = drm.frame(..., want_sample=True)
+
+`rgba` is the plain frame (H, W, 4) and `vis` its visibility (H, W) uint32 (oracle.render_terrain); `image` (ih, iw, 4) or (ih, iw, 3)
+uint8; `lit` / `sky` the shadow and sky-view fields when those features are on; `rewritten` marks the pixels the shade pass writes
+again and `sample` (H, W, 6) float32 holds their filtered premultiplied (r, g, b, a) and the lit and amb they were shaded with.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "ambient_model"))
+import ambient_model as abm  # noqa: E402
+shm = abm.shm
+om = abm.om
+
+FULL_EXTENT = (-1.5, -1.5, 1.5, 1.5)
+# The tests' image and where it lies: 37 x 53 texels (iw x ih) over a part of the grid and beyond its z edge (the grid ends at 1.5).
+IMAGE_SIZE = (37, 53)
+EXTENT = (-1.1, -0.9, 1.3, 1.6)
+# the same per camera (test_drape_model.py asserts that between 10 % and 90 % of each camera's covered pixels are written again)
+SCENE_EXTENT = {"default": EXTENT, "fill": EXTENT, "near": EXTENT}
+
+
+def image(seed=11, size=IMAGE_SIZE):
+    """(ih, iw, 4) uint8 from a seeded generator: alpha 0 where (ix // 6 + iy // 6) % 3 == 0, elsewhere a random value in 1 ... 255"""
+    iw, ih = size
+    rng = np.random.default_rng(seed)
+    img = rng.integers(0, 256, (ih, iw, 4), dtype=np.uint8)
+    img[..., 3] = rng.integers(1, 256, (ih, iw), dtype=np.uint8)
+    iy, ix = np.meshgrid(np.arange(ih), np.arange(iw), indexing="ij")
+    img[(ix // 6 + iy // 6) % 3 == 0, 3] = 0
+    return img
+
+
+def opaque_image(size, seed=3):
+    """(ih, iw, 4) uint8, random colours, alpha 255"""
+    iw, ih = size
+    img = np.random.default_rng(seed).integers(0, 256, (ih, iw, 4), dtype=np.uint8)
+    img[..., 3] = 255
+    return img
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        T = os.path.dirname(HERE)
+        L = om.build_model("libdrmodel.so", os.path.join(HERE, "drape_model.c"),
+                           [os.path.join(T, "ambient_model", "ambient_model.c"), os.path.join(T, "shadow_model", "shadow_model.c"),
+                            os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
+                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
+        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
+        L.drm_frame.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp, u32, u32, vp, f, i, vp, vp, f]
+        L.drm_frame.restype = i
+        _lib = L
+    return _lib
+
+
+def rgba8(img):
+    """(ih, iw, 3 | 4) uint8 -> contiguous (ih, iw, 4): RGB gets alpha 255"""
+    img = np.asarray(img, np.uint8)
+    assert img.ndim == 3 and img.shape[2] in (3, 4)
+    if img.shape[2] == 3:
+        img = np.concatenate([img, np.full(img.shape[:2] + (1,), 255, np.uint8)], axis=2)
+    return np.ascontiguousarray(img)
+
+
+def frame(rgba, vis, uniforms, height, grid, lut_rgba8, image, extent=None, opacity=1.0, filter="linear", lit=None, sky=None, strength=0.0,
+          shade_mode=0, want_sample=False):
+    """-> (the draped frame (H, W, 4) uint8, rewritten (H, W) bool[, sample (H, W, 6) float32])"""
+    vis = np.ascontiguousarray(vis, np.uint32)
+    H, W = vis.shape
+    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
+    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    tex = np.ascontiguousarray(height, np.float32)
+    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
+    img = rgba8(image)
+    ext = np.ascontiguousarray(FULL_EXTENT if extent is None else extent, np.float32).reshape(4)
+    lit = None if lit is None else np.ascontiguousarray(lit, np.float32)
+    sky = None if sky is None else np.ascontiguousarray(sky, np.float32)
+    mask = np.empty((H, W), np.uint8)
+    sample = np.empty((H, W, 6), np.float32) if want_sample else None
+    assert filter in ("linear", "nearest")
+    assert lib().drm_frame(out.ctypes.data, mask.ctypes.data, None if sample is None else sample.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data,
+                           tex.ctypes.data, tex.shape[1], tex.shape[0], grid, lut.ctypes.data, int(shade_mode), img.ctypes.data, img.shape[1],
+                           img.shape[0], ext.ctypes.data, float(opacity), 1 if filter == "linear" else 0,
+                           None if lit is None else lit.ctypes.data, None if sky is None else sky.ctypes.data, float(strength)) == 0
+    return (out, mask.astype(bool), sample) if want_sample else (out, mask.astype(bool))

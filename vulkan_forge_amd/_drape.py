@@ -1,0 +1,77 @@
+"""Argument rules of the draped-image methods (Scene / TerrainSpike .set_drape / .clear_drape / .drape_info).
+
+The extension and cabi.Terrain call these before they hand the values to the C-ABI (include/vf_hip.h, a draped image layer); they
+need no device.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ._shadows import _number
+
+SIZE_MAX = 16384                                          # VF_DRAPE_SIZE_MAX
+NEAREST, LINEAR = 0, 1                                    # VF_DRAPE_NEAREST, VF_DRAPE_LINEAR
+FILTERS = {"nearest": NEAREST, "linear": LINEAR}
+FULL_EXTENT = (-1.5, -1.5, 1.5, 1.5)                      # the grid's vertices lie at -1.5 ... 1.5 in x and z
+DEFAULTS = {"extent": None, "opacity": 1.0, "filter": "linear"}
+
+
+def drape_params(extent, opacity, filter):
+    """-> ((4,) float32 extent (x0, z0, x1, z1), opacity, filter code) as the C calls take them"""
+    if extent is None:
+        extent = FULL_EXTENT
+    try:
+        ext = np.ascontiguousarray(extent, np.float32)
+    except (TypeError, ValueError):
+        raise TypeError(f"extent must be four numbers (x0, z0, x1, z1), got {type(extent).__name__}") from None
+    if ext.shape != (4,):
+        raise ValueError(f"extent must be four numbers (x0, z0, x1, z1), got shape {ext.shape}")
+    if not np.isfinite(ext).all():
+        raise ValueError("extent must be finite")
+    if not (ext[2] > ext[0] and ext[3] > ext[1]):
+        raise ValueError(f"extent (x0, z0, x1, z1) needs x1 > x0 and z1 > z0, got {tuple(float(v) for v in ext)}")
+    opacity = _number("opacity", opacity)
+    if not 0.0 <= opacity <= 1.0:
+        raise ValueError(f"opacity must lie in [0, 1], got {opacity}")
+    if not isinstance(filter, str):
+        raise TypeError(f"filter must be 'linear' or 'nearest', got {type(filter).__name__}")
+    if filter not in FILTERS:
+        raise ValueError(f"filter must be 'linear' or 'nearest', got {filter!r}")
+    return ext, opacity, FILTERS[filter]
+
+
+def drape_args(image, extent=None, opacity=1.0, filter="linear"):
+    """-> (contiguous (ih, iw, channels) uint8 array, iw, ih, channels, (4,) float32 extent, opacity, filter code)"""
+    if image is None or isinstance(image, (str, bytes)):
+        raise TypeError(f"image must be an (ih, iw, 4) or (ih, iw, 3) uint8 array, got {type(image).__name__}")
+    try:
+        img = np.asarray(image)
+    except (TypeError, ValueError):
+        raise TypeError(f"image must be an (ih, iw, 4) or (ih, iw, 3) uint8 array, got {type(image).__name__}") from None
+    if img.dtype != np.uint8:
+        raise TypeError(f"image must be uint8 (sRGB bytes, straight alpha), got {img.dtype}")
+    if img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError(f"image must be (ih, iw, 4) or (ih, iw, 3), got shape {img.shape}")
+    ih, iw, ch = img.shape
+    if not (1 <= iw <= SIZE_MAX and 1 <= ih <= SIZE_MAX):
+        raise ValueError(f"image width and height must lie in [1, {SIZE_MAX}], got {iw} x {ih}")
+    ext, opacity, code = drape_params(extent, opacity, filter)
+    return np.ascontiguousarray(img), int(iw), int(ih), int(ch), ext, opacity, code
+
+
+def drape_size(iw, ih):
+    """the size rule alone (set_drape_device: the image is in device memory)"""
+    for name, v in (("width", iw), ("height", ih)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"image {name} must be an int, got {type(v).__name__}")
+    if not (1 <= iw <= SIZE_MAX and 1 <= ih <= SIZE_MAX):
+        raise ValueError(f"image width and height must lie in [1, {SIZE_MAX}], got {iw} x {ih}")
+    return int(iw), int(ih)
+
+
+def drape_info(iw, ih, extent, opacity, code):
+    """what drape_info() returns: None without a drape"""
+    if not iw:
+        return None
+    return {"width": int(iw), "height": int(ih), "extent": tuple(float(v) for v in extent), "opacity": float(opacity),
+            "filter": "linear" if code == LINEAR else "nearest"}

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.environ.get("VF_HIP_LIB") or os.path.join(_HERE, "libvf_hip.so")     # override: kernel experiments only
 
 VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -3, -4
+VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
 
 # every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py)
 SYMBOLS = [
@@ -31,6 +32,7 @@ SYMBOLS = [
     "vf_terrain_debug_shadow_scans",
     "vf_terrain_set_ambient", "vf_terrain_read_sky_view_field", "vf_terrain_sky_view_field_device", "vf_terrain_debug_ambient_stage",
     "vf_terrain_debug_ambient_scans",
+    "vf_terrain_set_drape", "vf_terrain_set_drape_device", "vf_terrain_clear_drape", "vf_terrain_drape_info", "vf_terrain_debug_drape_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -131,6 +133,11 @@ _PROTOS = {
     "vf_terrain_sky_view_field_device": (_i, [_vp, _vp, _vp]),
     "vf_terrain_debug_ambient_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_terrain_debug_ambient_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_set_drape": (_i, [_vp, _vp, _u32, _u32, _u32, C.POINTER(_f), _f, _i]),
+    "vf_terrain_set_drape_device": (_i, [_vp, _vp, _u32, _u32, C.POINTER(_f), _f, _i, _vp]),
+    "vf_terrain_clear_drape": (_i, [_vp]),
+    "vf_terrain_drape_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "vf_terrain_debug_drape_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -548,6 +555,39 @@ class Terrain:
         n = _u32()
         self._check(self.lib.vf_terrain_debug_ambient_scans(self.t, C.byref(n)))
         return n.value
+
+    def set_drape(self, image, *, extent=None, opacity=1.0, filter="linear"):
+        """Drape an image on the terrain as its albedo.  image: (ih, iw, 4) or (ih, iw, 3) uint8, sRGB bytes with
+        straight alpha, row 0 at the extent's z0 and column 0 at its x0; extent: (x0, z0, x1, z1) in the world plane of the grid
+        (vertices at -1.5 ... 1.5), None: the whole grid.  The handle keeps a copy made at the call; a second call replaces it."""
+        from ._drape import drape_args
+        img, iw, ih, ch, ext, opacity, code = drape_args(image, extent, opacity, filter)
+        self._check(self.lib.vf_terrain_set_drape(self.t, img.ctypes.data, iw, ih, ch, ext.ctypes.data_as(C.POINTER(_f)), opacity, code))
+
+    def set_drape_device(self, dev_rgba, width, height, *, extent=None, opacity=1.0, filter="linear", stream=None):
+        """The same from device memory (a torch tensor's data_ptr(): width * height * 4 bytes, RGBA); the copy is device to device and
+        asynchronous on `stream`, and later frames of the handle are ordered behind it."""
+        from ._drape import drape_params, drape_size
+        iw, ih = drape_size(width, height)
+        ext, opacity, code = drape_params(extent, opacity, filter)
+        self._check(self.lib.vf_terrain_set_drape_device(self.t, dev_rgba, iw, ih, ext.ctypes.data_as(C.POINTER(_f)), opacity, code, stream))
+
+    def clear_drape(self):
+        """Drop the draped image and free its copy: the handle draws as before."""
+        self._check(self.lib.vf_terrain_clear_drape(self.t))
+
+    def drape_info(self):
+        """None, or dict(width, height, extent, opacity, filter) of the drape as set."""
+        from ._drape import drape_info
+        iw, ih, op, code, ext = _u32(), _u32(), _f(), _i(), (_f * 4)()
+        self._check(self.lib.vf_terrain_drape_info(self.t, C.byref(iw), C.byref(ih), ext, C.byref(op), C.byref(code)))
+        return drape_info(iw.value, ih.value, tuple(ext), op.value, code.value)
+
+    def drape_stage(self, repeats=20):
+        """Shade-pass ms of the drape for the frame rendered last, as timed launches of their own (diagnostics)."""
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_drape_stage(self.t, int(repeats), C.byref(ms)))
+        return ms.value
 
     def enable_timing(self, on=True, stats=True, sampled=False):
         """stats=False: HIP events only, the kernels run exactly as untimed (no per-item statistics; blocks_* read 0);

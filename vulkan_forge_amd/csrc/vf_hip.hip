@@ -6,6 +6,7 @@
 #include "vf_gbuffer.h"     // templates only, behind the last non-template kernel
 #include "vf_shadow.h"      // templates only
 #include "vf_ambient.h"     // templates only
+#include "vf_drape.h"       // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -402,6 +403,15 @@ struct vf_terrain {
         std::vector<float> key_dirs;
         uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_ambient_scans)
     } am;
+    // the draped image: everything is made by set_drape and freed by clear_drape; iw = 0: none
+    struct Drape {
+        uint32_t iw = 0, ih = 0;
+        float extent[4] = { -1.5f, -1.5f, 1.5f, 1.5f }, opacity = 1.0f;
+        int filter = VF_DRAPE_LINEAR;
+        DevBuf<uint32_t> d_img;          // iw x ih RGBA8 words, row-major
+        DevBuf<float> d_decode;          // 256 sRGB8 -> linear (SrgbTables::decode)
+        hipEvent_t copied = nullptr;     // behind set_drape_device's copy on the caller's stream: the frames' shade passes wait for it
+    } dr;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -761,6 +771,15 @@ static void ov_release(vf_terrain *t)
     t->ct.levels.release(); t->ct.count.release(); t->ct.total.release(); t->ct.bounds.release();
 }
 
+// the draped image: gone, as if the handle never had one (the caller has synchronised)
+static void drape_release(vf_terrain *t)
+{
+    vf_terrain::Drape &D = t->dr;
+    D.d_img.release(); D.d_decode.release();
+    if (D.copied) (void)hipEventDestroy(D.copied);
+    D = vf_terrain::Drape();
+}
+
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
@@ -836,6 +855,7 @@ void vf_terrain_destroy(vf_terrain *t)
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release(); t->am.d_sky.release();
+    drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
 
@@ -985,6 +1005,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
     if (t->sh.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
     if (t->am.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
+    if (t->dr.iw && nranks != 1) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     VF_HIP_TRY(drop_preplan(t));
@@ -1108,6 +1129,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
     if (t->am.enabled) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
+    if (t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1453,13 +1475,15 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 // occluding overlay layer stores its visibility too, for the overlay pass.
 static int shadow_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int ambient_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows);
+static int drape_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows, bool ambient);
 
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
     const FrameParams &P = K.P;
     const bool shadows = t->sh.enabled && !diag;           // (visibility / diagnostics frames: the frame as the tile kernel shades it)
     const bool ambient = t->am.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient;
+    const bool drape = t->dr.iw != 0u && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1517,6 +1541,11 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
         const int src = ambient ? ambient_pass(t, s, P, V, S.work_count + 3, t->d_rgba, shadows) : shadow_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
         if (src != VF_OK) return src;
+    }
+    if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
+        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
+        const int drc = drape_pass(t, s, P, V, S.work_count + 3, t->d_rgba, shadows, ambient);
+        if (drc != VF_OK) return drc;
     }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
         const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
@@ -1631,6 +1660,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (!t || (!uniforms && n)) return fail(VF_ERR_INVALID, "NULL argument");
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
     if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
+    if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1651,6 +1681,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->shard_tiles || t->local_rows != t->H) return fail(VF_ERR_INVALID, "batch read-back needs the whole frame on one handle (pose-parallel ranks are replicas)");
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
     if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
+    if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2762,6 +2793,171 @@ int vf_terrain_debug_ambient_stage(vf_terrain *t, uint32_t repeats, float ms[2])
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("ambient diagnostics: ") + hipGetErrorString(err));
     ms[0] = a; ms[1] = b;
+    return VF_OK;
+}
+
+// ---- the draped image (vf_drape.h) ------------------------------------------------------
+
+static void drape_shade_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba,
+                               const float *lit, const float *sky)
+{
+    const vf_terrain::Drape &H = t->dr;
+    DrapeParams D;
+    D.x0 = H.extent[0]; D.z0 = H.extent[1];
+    D.sx = (float)H.iw / (H.extent[2] - H.extent[0]); D.sz = (float)H.ih / (H.extent[3] - H.extent[1]);
+    D.iw = H.iw; D.ih = H.ih; D.opacity = H.opacity; D.linear = H.filter == VF_DRAPE_LINEAR ? 1u : 0u;
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_drape_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const float *)H.d_decode.p,
+                       (const uint32_t *)t->d_vis, D, (const uint32_t *)H.d_img.p, lit, sky, t->am.strength, redo, rgba);
+    hipLaunchKernelGGL((k_drape_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const float *)H.d_decode.p,
+                       (const uint32_t *)t->d_vis, D, (const uint32_t *)H.d_img.p, lit, sky, t->am.strength, redo, rgba);
+}
+
+// The drape of a frame, on the draw stream behind its shadow / ambient pass (which has brought the fields it reads up to date; they
+// are checked again here, at no cost when they are current), then one shade pass.
+static int drape_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows, bool ambient)
+{
+    if (shadows) { if (int rc = shadow_field(t, t->inputs.u, s)) return rc; }
+    if (ambient) { if (int rc = ambient_field(t, t->inputs.u, s)) return rc; }
+    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    drape_shade_launch(t, s, P, V, redo, rgba, shadows ? t->sh.d_lit.p : nullptr, ambient ? t->am.d_sky.p : nullptr);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+// the argument rules of both setters (vulkan_forge_amd/_drape.py states the same); ext: the extent to keep
+static int drape_check(const vf_terrain *t, const void *image, uint32_t iw, uint32_t ih, const float *extent, float opacity, int filter, float ext[4])
+{
+    if (!t || !image) return fail(VF_ERR_INVALID, "NULL argument");
+    if (iw < 1u || ih < 1u || iw > VF_DRAPE_SIZE_MAX || ih > VF_DRAPE_SIZE_MAX) return fail(VF_ERR_INVALID, "image width and height must lie in [1, 16384]");
+    const float whole[4] = { -1.5f, -1.5f, 1.5f, 1.5f };
+    std::memcpy(ext, extent ? extent : whole, sizeof whole);
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(ext[k])) return fail(VF_ERR_INVALID, "extent must be finite");
+    if (!(ext[2] > ext[0]) || !(ext[3] > ext[1])) return fail(VF_ERR_INVALID, "extent (x0, z0, x1, z1) needs x1 > x0 and z1 > z0");
+    if (!(std::isfinite(opacity) && opacity >= 0.0f && opacity <= 1.0f)) return fail(VF_ERR_INVALID, "opacity must be a finite number in [0, 1]");
+    if (filter != VF_DRAPE_NEAREST && filter != VF_DRAPE_LINEAR) return fail(VF_ERR_INVALID, "filter must be VF_DRAPE_NEAREST or VF_DRAPE_LINEAR");
+    if (t->shard_tiles || t->nranks != 1) return fail(VF_ERR_INVALID, "a draped image needs a whole-frame handle: sharded handles are not supported");
+    return VF_OK;
+}
+
+// what a drape needs beside its image (nothing is changed when this fails); the caller has waited for the frame in flight
+static int drape_buffers(vf_terrain *t, size_t texels)
+{
+    if (int rc = ensure_vis(t)) return rc;
+    vf_terrain::Drape &H = t->dr;
+    if (!H.d_decode.p) {
+        if (H.d_decode.reserve(256, 256) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "drape allocation failed"); }
+        VF_HIP_TRY(hipMemcpy(H.d_decode.p, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (H.d_img.reserve(texels, texels) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "drape image allocation failed"); }
+    return VF_OK;
+}
+
+static void drape_commit(vf_terrain *t, uint32_t iw, uint32_t ih, const float ext[4], float opacity, int filter)
+{
+    vf_terrain::Drape &H = t->dr;
+    H.iw = iw; H.ih = ih; H.opacity = opacity; H.filter = filter;
+    std::memcpy(H.extent, ext, sizeof H.extent);
+    t->inputs_gen++;
+}
+
+int vf_terrain_set_drape(vf_terrain *t, const uint8_t *rgba, uint32_t iw, uint32_t ih, uint32_t channels, const float extent[4], float opacity, int filter)
+{
+    float ext[4];
+    if (int rc = drape_check(t, rgba, iw, ih, extent, opacity, filter, ext)) return rc;
+    if (channels != 3u && channels != 4u) return fail(VF_ERR_INVALID, "channels must be 3 or 4");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));                                // (the frame in flight reads the image this call replaces)
+    if (t->dr.copied) VF_HIP_TRY(hipEventSynchronize(t->dr.copied));   // (and so does an earlier device copy, on a stream of the caller's)
+    const size_t texels = (size_t)iw * ih;
+    DevBuf<uint8_t> rgb;                                      // an RGB upload's bytes: expanded on the device, then freed
+    if (channels == 3u && rgb.reserve(texels * 3u, texels * 3u) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "drape upload allocation failed"); }
+    if (int rc = drape_buffers(t, texels)) { rgb.release(); return rc; }
+    hipStream_t s = t->ctx->stream;
+    hipError_t err;
+    if (channels == 3u) {
+        err = hipMemcpyAsync(rgb.p, rgba, texels * 3u, hipMemcpyHostToDevice, s);
+        if (err == hipSuccess) {
+            hipLaunchKernelGGL((k_drape_expand<0>), dim3((uint32_t)((texels + 255u) / 256u)), dim3(256), 0, s, texels, (const uint8_t *)rgb.p, t->dr.d_img.p);
+            err = hipGetLastError();
+        }
+    }
+    else err = hipMemcpyAsync(t->dr.d_img.p, rgba, texels * 4u, hipMemcpyHostToDevice, s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);     // (a snapshot: the caller's array is free when this returns)
+    rgb.release();
+    if (err != hipSuccess) { drape_release(t); return fail(VF_ERR_HIP, std::string("drape upload: ") + hipGetErrorString(err)); }
+    if (t->dr.copied) { (void)hipEventDestroy(t->dr.copied); t->dr.copied = nullptr; }
+    drape_commit(t, iw, ih, ext, opacity, filter);
+    return VF_OK;
+}
+
+int vf_terrain_set_drape_device(vf_terrain *t, const void *dev_rgba, uint32_t iw, uint32_t ih, const float extent[4], float opacity, int filter, void *stream)
+{
+    float ext[4];
+    if (int rc = drape_check(t, dev_rgba, iw, ih, extent, opacity, filter, ext)) return rc;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (t->dr.copied) VF_HIP_TRY(hipEventSynchronize(t->dr.copied));
+    const size_t texels = (size_t)iw * ih;
+    if (int rc = drape_buffers(t, texels)) return rc;
+    if (!t->dr.copied) VF_HIP_TRY(hipEventCreateWithFlags(&t->dr.copied, hipEventDisableTiming));
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    hipError_t err = hipMemcpyAsync(t->dr.d_img.p, dev_rgba, texels * 4u, hipMemcpyDeviceToDevice, s);
+    if (err == hipSuccess) err = hipEventRecord(t->dr.copied, s);
+    if (err != hipSuccess) { drape_release(t); return fail(VF_ERR_HIP, std::string("drape copy: ") + hipGetErrorString(err)); }
+    drape_commit(t, iw, ih, ext, opacity, filter);
+    return VF_OK;
+}
+
+int vf_terrain_clear_drape(vf_terrain *t)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->dr.iw && !t->dr.d_img.p) return VF_OK;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (t->dr.copied) VF_HIP_TRY(hipEventSynchronize(t->dr.copied));
+    drape_release(t);
+    t->inputs_gen++;
+    return VF_OK;
+}
+
+int vf_terrain_drape_info(const vf_terrain *t, uint32_t *iw, uint32_t *ih, float extent[4], float *opacity, int *filter)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::Drape &H = t->dr;
+    if (iw) *iw = H.iw;
+    if (!H.iw) return VF_OK;
+    if (ih) *ih = H.ih;
+    if (extent) std::memcpy(extent, H.extent, sizeof H.extent);
+    if (opacity) *opacity = H.opacity;
+    if (filter) *filter = H.filter;
+    return VF_OK;
+}
+
+int vf_terrain_debug_drape_stage(vf_terrain *t, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds no draped image");
+    if (repeats == 0) repeats = 1;
+    GbFrame F;                                                // the frame rendered last, drawn again into scratch buffers with its visibility
+    int rc = gb_frame(t, F);
+    if (rc != VF_OK) return rc;
+    const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
+    hipStream_t s = t->ctx->stream;
+    const uint32_t scans = t->am.scans, shadow_scans = t->sh.scans;
+    const uint32_t *redo = t->ps[t->last_set].work_count + 3;
+    if (t->sh.enabled) rc = shadow_field(t, u, s);            // (the shade pass below reads them)
+    if (rc == VF_OK && t->am.enabled) rc = ambient_field(t, u, s);
+    t->am.scans = scans; t->sh.scans = shadow_scans;          // (diagnostic launches are not the handle's)
+    if (rc != VF_OK) return rc;
+    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    float mean = 0.0f;
+    const hipError_t err = time_launches(s, repeats, mean, [&](bool) {
+        drape_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, t->sh.enabled ? t->sh.d_lit.p : nullptr, t->am.enabled ? t->am.d_sky.p : nullptr);
+        return hipGetLastError();
+    });
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("drape diagnostics: ") + hipGetErrorString(err));
+    *ms = mean;
     return VF_OK;
 }
 

@@ -623,6 +623,41 @@ public:
         check(vf_terrain_debug_ambient_scans(t, &count));
         return count;
     }
+    // extension: a draped image layer (argument rules: vulkan_forge_amd/_drape.py)
+    void set_drape(py::object image, py::object extent, py::object opacity, py::object filter)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._drape").attr("drape_args")(image, extent, opacity, filter);
+        py::array img = a[0].cast<py::array>();              // (ih, iw, channels) uint8, contiguous
+        py::array ext = a[4].cast<py::array>();              // (4,) float32
+        const uint32_t iw = a[1].cast<uint32_t>(), ih = a[2].cast<uint32_t>(), channels = a[3].cast<uint32_t>();
+        const float op = a[5].cast<float>();
+        const int code = a[6].cast<int>();
+        Borrow b(busy);
+        const uint8_t *src = static_cast<const uint8_t *>(img.data());
+        const float *e = static_cast<const float *>(ext.data());
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = vf_terrain_set_drape(t, src, iw, ih, channels, e, op, code);
+        }
+        check(rc);
+        frame_current = false;
+    }
+    void clear_drape()
+    {
+        Borrow b(busy);
+        check(vf_terrain_clear_drape(t));
+        frame_current = false;
+    }
+    py::object drape_info()
+    {
+        Borrow b(busy);
+        uint32_t iw = 0, ih = 0;
+        float ext[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, op = 0.0f;
+        int code = 0;
+        check(vf_terrain_drape_info(t, &iw, &ih, ext, &op, &code));
+        return py::module_::import("vulkan_forge_amd._drape").attr("drape_info")(iw, ih, py::make_tuple(ext[0], ext[1], ext[2], ext[3]), op, code);
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -975,6 +1010,14 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "set_ambient_occlusion(False) without them puts the defaults back.")
         .def("sky_view_field", &T::sky_view_field)
         .def("debug_ambient_scans", &T::debug_ambient_scans)
+        .def("set_drape", &T::set_drape, py::arg("image"), py::kw_only(), py::arg("extent") = py::none(), py::arg("opacity") = 1.0,
+             py::arg("filter") = "linear",
+             "Drape an image on the terrain as its albedo (DESIGN.md 4j).  image: (ih, iw, 4) or (ih, iw, 3) uint8, sRGB bytes with\n"
+             "straight alpha; row 0 lies at the extent's z0 and column 0 at its x0, as in the height array.  extent: (x0, z0, x1, z1)\n"
+             "in the world plane of the grid (vertices at -1.5 ... 1.5), None: the whole grid.  The handle keeps a copy made at the\n"
+             "call; a second call replaces it.  The image is lit and shadowed as the surface is; overlays composite on top.")
+        .def("clear_drape", &T::clear_drape, "Drop the draped image and free its copy: the handle draws as before.")
+        .def("drape_info", &T::drape_info, "None, or dict(width, height, extent, opacity, filter) of the drape as set.")
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
