@@ -329,6 +329,26 @@ int vf_terrain_frame_times(vf_terrain *t, float *tile_ms, float *period_ms, uint
  * launch order, 4 words: item code (local tile | strip << 20 | log2(strips) << 24 | depth slice << 27 | log2(slices) << 29), candidate blocks processed,
  * raster-phase time, raster+fragment time (10 ns ticks of the constant 100 MHz clock).  *count = items written. */
 int vf_terrain_debug_item_stats(vf_terrain *t, uint32_t *dst, uint32_t max_items, uint32_t *count);
+/* debug/tests: set the scheduling feedback the NEXT frame's plan reads, instead of whatever the machine measured.
+ * Per local tile (storage order, ntiles = vf_terrain_local_tiles): tile_ticks[k] the tile's time in 10 ns ticks, strips_log2[k] the
+ * log2 (0 .. 4) of the strips that time was "recorded" with, piece_ticks[64 k + p] the time of its piece p (NULL: all zero).
+ * The call waits for the handle's queued work, throws away a plan queued ahead of its frame (the next plan then takes the previous
+ * frame's times, as after any such drop) and writes the words into BOTH plan states -- tile words, piece words, bits 8.. of the
+ * per-tile flag words (bit 0, background, stays) -- so that the next plan reads them whichever state it takes them from.  The split
+ * quantum is not set: the next plan derives it from the tile words as always.  Nothing else moves: which mode the next frame is
+ * planned in follows from the calls made, as without this one.  vf_terrain_tile_times reports the injected words until the next frame.
+ * VF_ERR_INVALID, and nothing is changed: a NULL pointer, ntiles != local tiles, strips_log2 > 4, or a handle on its first two frames
+ * since create / set_shard / set_tile_shard (those are planned from a static estimate that overwrites the words).
+ * Scheduling only: no frame may differ by a pixel for anything passed here. */
+int vf_terrain_debug_set_plan_feedback(vf_terrain *t, const uint32_t *tile_ticks, const uint8_t *strips_log2, const uint32_t *piece_ticks,
+                                       uint32_t ntiles);
+/* debug/tests: how the frame vf_terrain_render drew last was planned, VF_PLAN_* bits.  VF_ERR_INVALID before the first frame. */
+#define VF_PLAN_FIRST        1u   /* no tile times yet: the static estimate */
+#define VF_PLAN_FRESH        2u   /* tile times of the frame before it (the plan waited for that frame) */
+#define VF_PLAN_MOTION_MAP   4u   /* tile times looked up through the camera motion */
+#define VF_PLAN_DILATE       8u   /* every tile takes the heaviest time of its neighbourhood */
+#define VF_PLAN_QUEUED_AHEAD 16u  /* the plan was queued ahead of the call, behind the frame before it */
+int vf_terrain_debug_plan_mode(const vf_terrain *t, uint32_t *mode);
 /* diagnostics, only in libraries built with -DVF_PHASE_PROF (VF_ERR_INVALID otherwise): shader-clock cycles summed over
  * all waves of the last frame's tile kernel, per phase (set-up, pull/cull, vertex stage, classification, span raster,
  * completion/rescan, end-of-chunk wait, fragment stage), then 8 event counts, then up to 8 parts of the set-up phase; n <= 32 */

@@ -14,6 +14,7 @@ DEFAULT_LIB = os.environ.get("VF_HIP_LIB") or os.path.join(_HERE, "libvf_hip.so"
 
 VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -3, -4
 VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
+VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED_AHEAD = 1, 2, 4, 8, 16   # vf_terrain_debug_plan_mode
 
 # every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py)
 SYMBOLS = [
@@ -23,7 +24,7 @@ SYMBOLS = [
     "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
     "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
     "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_set_layer_occlusion", "vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
-    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
+    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
     "vf_terrain_debug_fragment_stage", "vf_host_alloc", "vf_host_free",
@@ -99,6 +100,8 @@ _PROTOS = {
     "vf_terrain_timings": (_i, [_vp, C.POINTER(Timings)]),
     "vf_terrain_frame_times": (_i, [_vp, _vp, _vp, _u32, C.POINTER(_u32)]),
     "vf_terrain_debug_item_stats": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
+    "vf_terrain_debug_set_plan_feedback": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "vf_terrain_debug_plan_mode": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_debug_phase_cycles": (_i, [_vp, _vp, _u32]),
     "vf_terrain_tile_times": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "vf_balance_stripes": (_i, [_vp, _u32, _u32, _vp]),
@@ -602,6 +605,22 @@ class Terrain:
         n = _u32()
         self._check(self.lib.vf_terrain_debug_item_stats(self.t, out.ctypes.data, cap, C.byref(n)))
         return out[:n.value]
+
+    def set_plan_feedback(self, tile_ticks, strips_log2=None, piece_ticks=None):
+        """Debug / tests: the scheduling feedback the next frame's plan reads.  Per local tile: tile_ticks (n,) u32,
+        strips_log2 (n,) 0 .. 4 (None: 0), piece_ticks (n, 64) u32 (None: 0).  Refused on a handle's first two frames."""
+        ticks = np.ascontiguousarray(tile_ticks, dtype=np.uint32).reshape(-1)
+        n = len(ticks)
+        lg = np.zeros(n, np.uint8) if strips_log2 is None else np.ascontiguousarray(strips_log2, dtype=np.uint8).reshape(n)
+        pieces = None if piece_ticks is None else np.ascontiguousarray(piece_ticks, dtype=np.uint32).reshape(n, 64)
+        self._check(self.lib.vf_terrain_debug_set_plan_feedback(self.t, ticks.ctypes.data, lg.ctypes.data,
+                                                                None if pieces is None else pieces.ctypes.data, n))
+
+    def plan_mode(self):
+        """VF_PLAN_* bits: how the frame rendered last was planned."""
+        m = _u32()
+        self._check(self.lib.vf_terrain_debug_plan_mode(self.t, C.byref(m)))
+        return m.value
 
     def tile_stats(self):
         """(ntiles, 3) u32 per local tile: candidate blocks (sum over strips), raster ticks, raster+fragment ticks (max)."""

@@ -197,6 +197,7 @@ static hipError_t ctx_copy_stream(vf_ctx *c, hipStream_t *copy)
 struct FramePlan {
     FrameParams P;
     uint32_t set = 0, ntiles = 0;
+    uint32_t mode = 0;                                           // VF_PLAN_* bits: how plan_frame planned it (vf_terrain_debug_plan_mode)
     bool motion_starts = false;
     bool sampled = true;                                         // timing level 3: this frame is one of those that carry events
     uint32_t *rc_lo = nullptr, *rc_hi = nullptr, *seg_count = nullptr;
@@ -454,6 +455,7 @@ struct vf_terrain {
     } ps[kPlanStates];
     PlanCursor cursor;
     uint32_t last_set = 0;               // the set of the frame rendered last
+    uint32_t last_plan_mode = 0;         // VF_PLAN_* bits of the frame rendered last (vf_terrain_debug_plan_mode)
     hipStream_t side = nullptr;          // k_block_boxes -> k_plan -> k_plan_sort
     hipStream_t side2 = nullptr;         // k_block_setup (needs the block boxes only): beside the plan chain, both under the previous frame
     hipEvent_t entry = nullptr;          // caller's stream at render entry (orders a height-cache rebuild after the caller's work)
@@ -1414,6 +1416,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
     VF_HIP_TRY(hipGetLastError());                              // a failed plan launch is reported here: the probe block below clears hipEventQuery's "not ready"
     if (timed) VF_HIP_TRY(hipEventRecord(ev[2], side));
     VF_HIP_TRY(hipEventRecord(S.planned, side));
+    K.mode = (first ? VF_PLAN_FIRST : 0u) | (fresh ? VF_PLAN_FRESH : 0u) | (M.on ? VF_PLAN_MOTION_MAP : 0u) | (dilate ? VF_PLAN_DILATE : 0u);
     K.set = set; K.ntiles = ntiles; K.motion_starts = motion_starts; K.rc_lo = rc_lo; K.rc_hi = rc_hi; K.seg_count = seg_count;
     return VF_OK;
 }
@@ -1627,6 +1630,7 @@ static int render_impl(vf_terrain *t, hipStream_t s, bool write_vis)
     const bool again = t->last_drawn_gen == t->inputs_gen;      // the frame before this one was drawn from the same inputs
     const int rc = draw_frame(t, s, K, write_vis);
     if (rc != VF_OK) return rc;
+    t->last_plan_mode = K.mode | (planned ? VF_PLAN_QUEUED_AHEAD : 0u);
     t->last_drawn_gen = t->inputs_gen;
     // the camera is at rest (two frames from one set of inputs), the handle is past its first frames, nothing diagnostic is going on:
     // the next frame's plan goes out now
@@ -1746,6 +1750,7 @@ static int render_visibility(vf_terrain *t)
     uint32_t *const out_now = t->d_rgba;
     const hipStream_t stream_now = t->last_stream;
     const bool timing = t->timing, rendered = t->rendered;
+    const uint32_t plan_mode_now = t->last_plan_mode;
     if (t->have_frame) t->inputs = t->drawn_inputs;
     t->d_rgba = t->d_rgba_scratch; t->timing = false;
     rc = render_impl(t, t->ctx->stream, true);
@@ -1755,6 +1760,7 @@ static int render_visibility(vf_terrain *t)
     t->cursor = cursor_now;
     t->d_rgba = out_now; t->last_stream = stream_now; t->timing = timing;
     t->rendered = rendered;                                 // the diagnostic frame went to scratch buffers: the caller's output is as it was
+    t->last_plan_mode = plan_mode_now;
     if (rc != VF_OK) return rc;
     if (e != hipSuccess) return fail(VF_ERR_HIP, std::string("visibility render: ") + hipGetErrorString(e));
     return VF_OK;
@@ -2972,6 +2978,45 @@ int vf_terrain_debug_item_stats(vf_terrain *t, uint32_t *dst, uint32_t max_items
     if (n > max_items) n = max_items;
     if (n) VF_HIP_TRY(hipMemcpy(dst, t->d_stats + 4, 4 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *count = n;
+    return VF_OK;
+}
+
+// The words the next plan reads, written into both plan states (include/vf_hip.h).  Host copies behind a full wait: nothing of this
+// is on a frame's path.
+int vf_terrain_debug_set_plan_feedback(vf_terrain *t, const uint32_t *tile_ticks, const uint8_t *strips_log2, const uint32_t *piece_ticks,
+                                       uint32_t ntiles)
+{
+    if (!t || !tile_ticks || !strips_log2) return fail(VF_ERR_INVALID, "NULL argument");
+    if (ntiles != t->local_tiles) return fail(VF_ERR_INVALID, "ntiles must be the handle's local tiles");
+    for (uint32_t k = 0; k < ntiles; ++k) if (strips_log2[k] > 4u) return fail(VF_ERR_INVALID, "strips_log2 must be 0 .. 4");
+    if (t->cursor.frames_since_reset < vf_terrain::kPlanStates)
+        return fail(VF_ERR_INVALID, "the handle's first frames are planned from the static estimate: render two frames first");
+    for (const auto &S : t->ps) if (!S.slab) return fail(VF_ERR_INVALID, "a plan state has not been used yet: render two frames first");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    VF_HIP_TRY(sync_sides(t));
+    VF_HIP_TRY(drop_preplan(t));                            // (its waits and its memset are queued on one of the streams waited for next)
+    VF_HIP_TRY(wait_frame(t));
+    VF_HIP_TRY(sync_sides(t));
+    if (!ntiles) return VF_OK;                              // (a shard without tiles)
+    const size_t all_tiles = (size_t)t->ntx * t->nty;
+    std::vector<uint32_t> pieces((size_t)ntiles * 64u, 0u), flags(ntiles);
+    if (piece_ticks) std::memcpy(pieces.data(), piece_ticks, pieces.size() * sizeof(uint32_t));
+    for (auto &S : t->ps) {
+        VF_HIP_TRY(hipMemcpy(S.feedback, tile_ticks, (size_t)ntiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        VF_HIP_TRY(hipMemcpy(S.feedback + all_tiles + 1u, pieces.data(), pieces.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        VF_HIP_TRY(hipMemcpy(flags.data(), S.background, (size_t)ntiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < ntiles; ++k) flags[k] = (flags[k] & 0xFFu) | ((uint32_t)strips_log2[k] << 8);
+        VF_HIP_TRY(hipMemcpy(S.background, flags.data(), (size_t)ntiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    return VF_OK;
+}
+
+int vf_terrain_debug_plan_mode(const vf_terrain *t, uint32_t *mode)
+{
+    if (!t || !mode) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
+    *mode = t->last_plan_mode;
     return VF_OK;
 }
 
