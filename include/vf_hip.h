@@ -577,7 +577,8 @@ int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count);
 /* ---- a draped image layer: an RGBA raster as the terrain's albedo ----------------------------------
  * One image per handle: (ih, iw) texels of sRGB bytes with straight alpha, row-major, row 0 at the extent's z0 and column 0 at its
  * x0 (as the height array: row = z index, column = x index).  extent = (x0, z0, x1, z1) in the world plane of the grid, whose
- * vertices lie at -1.5 ... 1.5 in x and z; NULL: the whole grid.  It may reach outside the grid or cover a part of it.
+ * vertices lie at -1.5 ... 1.5 in x and z; NULL: the whole grid.  It may reach outside the grid or cover a part of it.  The extent
+ * is in grid coordinates and is not multiplied by the grid spacing, unlike overlay coordinates, which are in the spaced world.
  *
  * vf_terrain_set_drape: the handle keeps a device copy made at the call (a snapshot; a second call replaces it).  channels 3: RGB,
  * alpha 255.  From then on vf_terrain_render draws the frame as before, with the visibility store on, then writes again every

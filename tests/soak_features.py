@@ -1,6 +1,6 @@
 """Feature soak on the GPU box: seeded random scenes through every pass that runs after the tile kernel -- geometry buffers and pick,
-the shadow field and the sky-view field, their shade passes, point / line / polygon / contour overlays with occlusion -- on one handle
-per case, followed by one mutation of the handle (a height upload, a new sun, ...), each step compared with the CPU models
+the shadow field and the sky-view field, their shade passes, the draped image, point / line / polygon / contour overlays with occlusion
+-- on one handle per case, followed by one mutation of the handle (a height upload, a new sun, another image, ...), each step compared with the CPU models
 (tests/*_model) run on the oracle's frame.  Every comparison is equality; the one exception is the FAST frame's stated 1 LSB
 (include/vf_hip.h).  A sibling of tests/soak_parity.py: test infrastructure, nothing of it is shipped.  A script, and the library of
 tests/test_gpu_feature_soak.py (the GPU slice) and tests/test_feature_soak_cases.py (the slice is not vacuous; CPU only).
@@ -8,24 +8,27 @@ tests/test_gpu_feature_soak.py (the GPU slice) and tests/test_feature_soak_cases
     case(seed)              a case description: pure numpy and the models' surface sampling, no GPU, no oracle
     CORNERS                 hand-written case descriptions: the edges that must not be left to the draw
     expected(case, state)   the reference frame and planes of a handle state, composed from the models in the library's order:
-                            oracle frame -> ambient / shadow shade pass -> overlays
+                            oracle frame -> ambient / shadow shade pass -> draped image -> overlays
     run(first, cases, ...)  the GPU side, case by case
 
 usage: soak_features.py [first_seed] [cases] [time_budget_s]"""
 import math, os, sys, time, zlib
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model", "shadow_model", "ambient_model"):
+for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model", "shadow_model", "ambient_model", "drape_model"):
     sys.path.insert(0, os.path.join(HERE, _m))
 import numpy as np
 import ambient_model as abm  # noqa: E402
 import contour_model as cm  # noqa: E402
+import drape_model as drm  # noqa: E402
 import gbuffer_model as gbm  # noqa: E402
 import shadow_model as shm  # noqa: E402
 
 ocm = cm.ocm
 f32 = np.float32
-MUTATIONS = ("heights", "sun", "exaggeration", "clear_overlays", "layer_occlusion", "shadows_off", "reach")
+MUTATIONS = ("heights", "sun", "exaggeration", "clear_overlays", "layer_occlusion", "shadows_off", "reach", "drape_replace", "drape_opacity_zero",
+             "drape_clear")
+DRAPE_MUTATIONS = MUTATIONS[7:]
 GRIDS = (2, 3, 5, 9, 16, 17, 33, 63, 64, 65, 96, 130)
 CAPS = ("butt", "square", "round")
 SHAPES = ("circle", "square")
@@ -34,6 +37,12 @@ SIZES = (0.3, 1.0, 3.0, 9.0, 30.0, 64.0, 100.0)               # clamped to [1, 6
 # which fields vf_hip.h says a mutation makes stale (when the field's feature is on)
 STALE_SHADOW = ("heights", "sun", "exaggeration")
 STALE_AMBIENT = ("heights", "exaggeration", "reach")
+# the draped image: widths and heights drawn independently -- one texel, Nx1 and 1xN, texel counts that are and are not
+# multiples of k_drape_expand's 256 threads
+DRAPE_SIZES = (1, 2, 3, 7, 37, 64, 255, 256, 257, 300)
+DRAPE_EXTENTS = ("whole", "interior", "overhanging", "one_side", "off_grid")
+DRAPE_FILTERS = ("linear", "nearest")
+DRAPE_STREAM = 0xD4A9E                                        # the drape's own generator is default_rng([seed, DRAPE_STREAM])
 
 
 def _heights(rng, shape, amp, smooth):
@@ -133,8 +142,78 @@ def _overlays(rng, c, surf):
     return [calls[k] for k in rng.permutation(len(calls))]
 
 
-def _make(rng, name, fix):
-    """A case description; `fix` overrides what the draw would choose (CORNERS)."""
+def drape_image(rng, iw, ih, channels):
+    """(ih, iw, channels) uint8.  RGBA in the pattern of drape_model.image: random colours, alpha 0 in every third cell of 6 x 6 texels
+    (of a third of the width or height in an image smaller than 18 texels, so that the linear filter leaves holes in it too) and a
+    random value in 1 ... 255 elsewhere -- everywhere, where that would leave no texel to see; RGB: random colours"""
+    img = rng.integers(0, 256, (ih, iw, channels), dtype=np.uint8)
+    if channels == 4:
+        img[..., 3] = rng.integers(1, 256, (ih, iw), dtype=np.uint8)
+        cx, cy = max(1, min(6, iw // 3)), max(1, min(6, ih // 3))
+        iy, ix = np.meshgrid(np.arange(ih), np.arange(iw), indexing="ij")
+        hole = (ix // cx + iy // cy) % 3 == 0
+        if not hole.all():
+            img[hole, 3] = 0
+    return img
+
+
+def distinct_image(iw, ih):
+    """(ih, iw, 4) uint8, opaque, every texel another colour (iw, ih <= 256): a sample names its texel"""
+    iy, ix = np.meshgrid(np.arange(ih), np.arange(iw), indexing="ij")
+    return np.stack([ix, iy, (ix * 7 + iy * 3) % 256, np.full_like(ix, 255)], axis=2).astype(np.uint8)
+
+
+def _drape_extent(rng, kind):
+    """(x0, z0, x1, z1) in the grid's own plane (vertices at -1.5 ... 1.5, whatever the spacing), or None for the whole grid"""
+    def inner():
+        a = float(rng.uniform(-1.4, -0.5))
+        return a, min(a + float(rng.uniform(1.2, 2.4)), 1.4)
+
+    def over():                                               # beyond the grid at one end, as drape_model.EXTENT is in z
+        a, b = inner()
+        return (-float(rng.uniform(1.6, 2.5)), b) if rng.random() < 0.5 else (a, float(rng.uniform(1.6, 2.5)))
+
+    if kind == "whole":
+        return None
+    if kind == "interior":
+        (x0, x1), (z0, z1) = inner(), inner()
+    elif kind == "overhanging":                               # over a corner of the grid: beyond it in x and in z
+        (x0, x1), (z0, z1) = over(), over()
+    elif kind == "one_side":
+        (x0, x1), (z0, z1) = inner(), inner()
+        side = int(rng.integers(0, 4))
+        beyond = float(rng.uniform(1.6, 2.5))
+        x0, z0, x1, z1 = [(-beyond, z0, x1, z1), (x0, -beyond, x1, z1), (x0, z0, beyond, z1), (x0, z0, x1, beyond)][side]
+    else:
+        (x0, x1), (z0, z1) = inner(), inner()
+        w, off = x1 - x0, float(rng.uniform(1.6, 2.6))
+        side = int(rng.integers(0, 4))
+        x0, z0, x1, z1 = [(off, z0, off + w, z1), (-off - w, z0, -off, z1), (x0, off, x1, off + w), (x0, -off - w, x1, -off)][side]
+    return tuple(float(f32(v)) for v in (x0, z0, x1, z1))
+
+
+def _drape(rng, must):
+    """The drape entry of a case from the drape's own generator: None for about one case in five (never when `must`: the case's
+    mutation is one of DRAPE_MUTATIONS), else image, extent, opacity, filter and `replace`, the payload of drape_replace: another
+    size, the other channel count, another extent kind and the other filter."""
+    absent = rng.random() < 0.2
+    iw, ih = (int(v) for v in rng.choice(DRAPE_SIZES, 2))
+    channels = int(rng.choice([4, 4, 3]))
+    kind = str(rng.choice(DRAPE_EXTENTS, p=[0.06, 0.3, 0.32, 0.27, 0.05]))
+    d = dict(image=drape_image(rng, iw, ih, channels), extent=_drape_extent(rng, kind), extent_kind=kind,
+             opacity=float(rng.choice([1.0, 0.37, 0.0], p=[0.5, 0.42, 0.08])), filter=str(rng.choice(DRAPE_FILTERS)))
+    iw2, ih2 = (int(v) for v in rng.choice(DRAPE_SIZES, 2))
+    if (iw2, ih2) == (iw, ih):
+        iw2 = DRAPE_SIZES[(DRAPE_SIZES.index(iw) + 1) % len(DRAPE_SIZES)]
+    kind2 = str(rng.choice([k for k in DRAPE_EXTENTS if k not in (kind, "off_grid")]))
+    d["replace"] = dict(image=drape_image(rng, iw2, ih2, 7 - channels), extent=_drape_extent(rng, kind2), extent_kind=kind2,
+                        opacity=float(rng.choice([1.0, 0.37])), filter=DRAPE_FILTERS[1 - DRAPE_FILTERS.index(d["filter"])])
+    return None if absent and not must else d
+
+
+def _make(rng, name, fix, drape_rng, draped=False):
+    """A case description; `fix` overrides what the draw would choose (CORNERS).  The drape comes from `drape_rng`, a generator of
+    its own: what `rng` gives a seed or a corner does not depend on it; `draped`: never without one (every corner)."""
     c = {"name": name}
 
     def put(key, draw):
@@ -170,7 +249,7 @@ def _make(rng, name, fix):
     put("sun", tuple(float(v) for v in (special[int(rng.integers(0, len(special)))] if rng.random() < 0.15 else sun)))
     put("cmap", str(rng.choice(["viridis", "magma", "terrain"])))
     put("mode", int(rng.random() < 0.2))
-    mutation = put("mutation", MUTATIONS[int(rng.integers(0, len(MUTATIONS)))])
+    mutation = put("mutation", MUTATIONS[int(rng.integers(0, 7))])   # (every caller fixes the mutation; the draw keeps its place in the stream)
     features = put("features", str(rng.choice(["shadows", "ambient", "both"], p=[0.45, 0.3, 0.25])))
     if mutation == "shadows_off" and features == "ambient":
         features = c["features"] = "both"
@@ -198,13 +277,17 @@ def _make(rng, name, fix):
         "depth_bias": float(rng.choice([0.0, 0.05])),
         "reach": float(rng.choice([v for v in (1.0, 3.0, 40.0, 1024.0) if v != c["ambient"]["reach"]])),
     }, **fix.get("mutation_args", {}))
+    # the draped image: drawn whole, then a corner's own fields laid over it (its "replace" replaces the payload whole)
+    d = _drape(drape_rng, draped or mutation in DRAPE_MUTATIONS)
+    c["drape"] = None if d is None else dict(d, **fix.get("drape", {}))
     return c
 
 
 def case(seed):
     """The case of a seed: frame, grid, texture, camera and uniforms drawn as test_random_scenes_fuzz draws them, a sun, colormap,
-    shade mode, shadow and ambient parameters, which of them are on, the overlay calls and one mutation."""
-    return _make(np.random.default_rng(seed), f"seed{seed}", {"mutation": MUTATIONS[seed % len(MUTATIONS)]})
+    shade mode, shadow and ambient parameters, which of them are on, the overlay calls, one mutation and (from a generator of its
+    own) a draped image or none."""
+    return _make(np.random.default_rng(seed), f"seed{seed}", {"mutation": MUTATIONS[seed % len(MUTATIONS)]}, np.random.default_rng([seed, DRAPE_STREAM]))
 
 
 _CAMERA = dict(eye=(3.0, 2.0, 3.0), target=(0.0, 0.0, 0.0), fovy=45.0, znear=0.1, zfar=100.0)
@@ -218,12 +301,12 @@ def _corner(k, name, **fix):
 def _build(k, name, fix):
     """a corner: a well-behaved camera over long waves of amplitude 1, everything on, whatever `fix` does not say drawn from seed k"""
     base = dict(_CAMERA, W=96, H=64, grid=33, tex=(23, 31), amp=1.0, smooth=True, nan_texel=False, exaggeration=1.0, spacing=1.0,
-                features="both", mutation=MUTATIONS[k % len(MUTATIONS)], cmap="viridis", mode=0,
+                features="both", mutation=MUTATIONS[k % 7], cmap="viridis", mode=0,     # (the seven mutations older than the drape's: a corner that names none keeps its own)
                 shadows=dict(strength=0.7, softness=0.1, bias=0.02))
     base.update(fix)
     if "spacing" in fix and "eye" not in fix:                 # keep the terrain in view
         base["eye"] = tuple(v * fix["spacing"] for v in _CAMERA["eye"])
-    return _make(np.random.default_rng(90000 + k), name, base)
+    return _make(np.random.default_rng(90000 + k), name, base, np.random.default_rng([90000 + k, DRAPE_STREAM]), draped=True)
 
 
 def _amb(reach, dirs, strength=0.6):
@@ -271,6 +354,32 @@ _SPECS = [
     _corner(20, "frame24x16384", W=24, H=16384, grid=257, eye=(0.0, 6.0, 0.6), fovy=_LONG_FOVY, znear=0.1, zfar=100.0, ambient=_amb(16.0, _FAN),
             more_overlays=[("lines", dict(paths=[np.array([[0.0, 0.0, -1.6], [0.0, 0.0, 1.6]], f32)], width_px=3.0, rgba=(250, 220, 30, 255), cap="butt",
                                           drape=False, occlude=False, depth_bias=0.0))]),
+    # the draped image's own edges (tests/test_feature_soak_cases.py asserts what each is named for)
+    # one texel under the linear filter: all four taps clamp to it; a border pixel whose interpolated x rounds beyond +-1.5 is not written
+    _corner(21, "drape_1x1_linear_full_extent", mutation="drape_opacity_zero", ambient=_amb(16.0, _FAN, strength=0.0),
+            drape=dict(image=np.array([[(200, 90, 33, 180)]], np.uint8), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
+    # x1 - x0 is inf in binary32 and sx = 0: every covered pixel takes texel (0, 0)
+    _corner(22, "drape_extent_overflows", mutation="drape_replace", ambient=_amb(16.0, _FAN),
+            drape=dict(image=distinct_image(7, 5), extent=(-3e38, -3e38, 3e38, 3e38), extent_kind="overflows", opacity=1.0, filter="linear")),
+    _corner(23, "drape_extent_off_the_grid", mutation="heights", ambient=_amb(16.0, _FAN),
+            drape=dict(image=distinct_image(37, 64), extent=(1.6, -1.0, 2.9, 1.0), extent_kind="off_grid", opacity=1.0, filter="linear")),
+    _corner(24, "drape_transparent_image", mutation="drape_replace", ambient=_amb(16.0, _FAN),
+            drape=dict(image=distinct_image(37, 7) * np.array([1, 1, 1, 0], np.uint8), extent=None, extent_kind="whole", opacity=1.0, filter="linear",
+                       replace=dict(image=distinct_image(64, 3)[..., :3].copy(), extent=None, extent_kind="whole", opacity=1.0, filter="nearest"))),
+    # the eye low over the middle of a coarse grid: the near plane cuts triangles the image covers, so k_drape_shade<true> sends lit
+    # and amb through the clipper in the place of the height, under a low sun and an ambient fan that leave neither at 1;
+    # then the shadows go while the drape stays
+    _corner(25, "drape_near_plane_through_the_terrain", grid=9, eye=(0.9, 0.7, 0.8), target=(-0.4, -0.2, -0.3), znear=0.4, fovy=60.0,
+            sun=tuple(float(v) for v in shm.sun_vector(15.0, 200.0)), shadows=dict(strength=0.7, softness=0.1, bias=0.02),
+            ambient=_amb(16.0, _FAN, strength=0.6), mutation="shadows_off",
+            drape=dict(image=distinct_image(37, 64), extent=(-0.9, -1.0, 0.6, 0.7), extent_kind="interior", opacity=0.37, filter="linear")),
+    # the extent lies in the grid's own plane, whatever the spacing: an interior box, the nearest filter, every texel distinct
+    _corner(26, "drape_under_spacing_2p5_exaggeration_minus2", spacing=2.5, exaggeration=-2.0, amp=0.2, mutation="exaggeration", ambient=_amb(16.0, _FAN, strength=0.0),
+            drape=dict(image=distinct_image(37, 64), extent=(-0.7, -0.5, 0.9, 0.8), extent_kind="interior", opacity=1.0, filter="nearest")),
+    _corner(27, "drape_under_spacing_0p3", spacing=0.3, exaggeration=0.3, eye=(0.5, 0.9, 0.5), mutation="sun", ambient=_amb(16.0, _FAN),
+            drape=dict(image=distinct_image(64, 37), extent=(-0.7, -0.5, 0.9, 0.8), extent_kind="interior", opacity=1.0, filter="nearest")),
+    _corner(28, "drape_denser_than_the_frame", W=15, H=17, mutation="drape_clear", ambient=_amb(16.0, _FAN),
+            drape=dict(image=drape_image(np.random.default_rng(28), 300, 300, 4), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
 ]
 
 
@@ -325,11 +434,18 @@ def uniforms(c, sun=None, exaggeration=None):
 def initial_state(c):
     """the handle's state before any feature is on: what `expected` and `run` step through"""
     return dict(heights=c["heights"], u=uniforms(c), shadows=False, ambient=False, shadow_params=dict(c["shadows"]), ambient_params=dict(c["ambient"]),
-                overlays=False, occlusion={})
+                overlays=False, occlusion={}, drape=None)
 
 
-def featured(c, state, overlays=False):
-    return dict(state, shadows=c["features"] in ("shadows", "both"), ambient=c["features"] in ("ambient", "both"), overlays=overlays)
+def the_drape(d):
+    """what a handle state holds of a drape entry: the arguments of set_drape"""
+    return None if d is None else {k: d[k] for k in ("image", "extent", "opacity", "filter")}
+
+
+def featured(c, state, overlays=False, drape=True):
+    """the state with the case's shade features on and, unless `drape` is false, its draped image set"""
+    return dict(state, shadows=c["features"] in ("shadows", "both"), ambient=c["features"] in ("ambient", "both"), overlays=overlays,
+                drape=the_drape(c["drape"]) if drape else state["drape"])
 
 
 def mutated(c, state):
@@ -351,6 +467,12 @@ def mutated(c, state):
         s["shadows"] = False
     elif kind == "reach":
         s["ambient_params"] = dict(state["ambient_params"], reach=a["reach"])
+    elif kind == "drape_replace":
+        s["drape"] = the_drape(c["drape"]["replace"])
+    elif kind == "drape_opacity_zero":                        # (the same image set again; on a handle without one, the case's)
+        s["drape"] = dict(state["drape"] or the_drape(c["drape"]), opacity=0.0)
+    elif kind == "drape_clear":
+        s["drape"] = None
     return s
 
 
@@ -388,15 +510,18 @@ def layers(c, state):
 def expected(c, state, cache=None):
     """The reference of a handle state, in the order the library documents: the oracle's frame and visibility; the shade pass
     (ambient_model.frame with the shadow field when both are on, shadow_model.frame for shadows alone); the overlays
-    (occlusion_model.composite of the contour model's layers).  `cache` (a dict of one case) keeps the oracle's frames and the
-    results, for a caller that asks for a state twice.  -> dict rgba (the oracle's frame), vis, shaded, mask (the pixels the
-    shade pass writes again), frame (what the handle must show), layers (or None)."""
+    the draped image over that frame (drape_model.frame, with the state's shadow and sky-view fields and strength when those
+    features are on); the overlays (occlusion_model.composite of the contour model's layers).  `cache` (a dict of one case) keeps
+    the oracle's frames and the results, for a caller that asks for a state twice.  -> dict rgba (the oracle's frame), vis, shaded,
+    mask (the pixels the shade pass writes again), draped (the frame behind the drape pass: `shaded` without a drape), drape_mask
+    (the pixels the drape writes again), frame (what the handle must show), layers (or None)."""
     import oracle
     W, H, G, h, u = c["W"], c["H"], c["grid"], state["heights"], state["u"]
     key = (u.tobytes(), h.tobytes(), h.shape)
-    A = state["ambient_params"]
+    A, D = state["ambient_params"], state["drape"]
     whole = (key, state["shadows"], state["ambient"], state["overlays"], tuple(sorted(state["shadow_params"].items())),
-             A["strength"], A["reach"], A["directions"].tobytes(), tuple(sorted(state["occlusion"].items())))
+             A["strength"], A["reach"], A["directions"].tobytes(), tuple(sorted(state["occlusion"].items())),
+             None if D is None else (D["image"].tobytes(), D["image"].shape, D["extent"], D["opacity"], D["filter"]))
     if cache is not None and whole in cache:
         return cache[whole]
     if cache is not None and key in cache:
@@ -407,17 +532,28 @@ def expected(c, state, cache=None):
         if cache is not None:
             cache[key] = (rgba, vis)
     out = {"rgba": rgba, "vis": vis, "shaded": rgba, "mask": np.zeros((H, W), bool), "layers": None}
-    lit = shm.field(u, h, G, **state["shadow_params"]) if state["shadows"] else None
-    if state["ambient"]:
-        P = state["ambient_params"]
-        sky = abm.field(u, h, G, P["directions"], P["reach"])
-        out["shaded"], out["mask"] = abm.frame(rgba, vis, u, h, G, lut(c["cmap"]), sky, P["strength"], lit=lit, shade_mode=c["mode"])
-    elif state["shadows"]:
-        out["shaded"], out["mask"] = shm.frame(rgba, vis, u, h, G, lut(c["cmap"]), lit, shade_mode=c["mode"])
-    out["frame"] = out["shaded"]
+    shade = ("shade",) + whole[:3] + whole[4:8]               # the fields and the shade pass: the same under any drape and any overlays
+    if cache is not None and shade in cache:
+        lit, sky, out["shaded"], out["mask"] = cache[shade]
+    else:
+        lit = shm.field(u, h, G, **state["shadow_params"]) if state["shadows"] else None
+        sky = None
+        if state["ambient"]:
+            sky = abm.field(u, h, G, A["directions"], A["reach"])
+            out["shaded"], out["mask"] = abm.frame(rgba, vis, u, h, G, lut(c["cmap"]), sky, A["strength"], lit=lit, shade_mode=c["mode"])
+        elif state["shadows"]:
+            out["shaded"], out["mask"] = shm.frame(rgba, vis, u, h, G, lut(c["cmap"]), lit, shade_mode=c["mode"])
+        if cache is not None:
+            cache[shade] = (lit, sky, out["shaded"], out["mask"])
+    out["draped"], out["drape_mask"] = out["shaded"], np.zeros((H, W), bool)
+    if D is not None:
+        out["draped"], out["drape_mask"] = drm.frame(out["shaded"], vis, u, h, G, lut(c["cmap"]), D["image"], extent=D["extent"], opacity=D["opacity"],
+                                                     filter=D["filter"], lit=lit, sky=sky, strength=A["strength"],
+                                                     shade_mode=c["mode"])
+    out["frame"] = out["draped"]
     if state["overlays"]:
         out["layers"] = layers(c, state)
-        out["frame"] = ocm.composite(out["shaded"], vis, u, h, G, out["layers"])
+        out["frame"] = ocm.composite(out["draped"], vis, u, h, G, out["layers"])
     if cache is not None:
         cache[whole] = out
     return out
@@ -430,12 +566,17 @@ def planes(c, state, vis):
 
 def shares(c, cache=None):
     """what the reference alone says about a case (tests/test_feature_soak_cases.py): the share of covered pixels, the share of the
-    covered pixels the shade pass writes again, whether the overlays change a pixel"""
+    covered pixels the shade pass writes again, the share the drape writes again (None without a drape or without a covered pixel),
+    whether the drape's pixels and the shade pass's overlap with each having pixels the other lacks, whether the overlays change a
+    pixel"""
     s0 = initial_state(c)
     e = expected(c, featured(c, s0, overlays=True), cache)
     covered = int((e["vis"] != 0).sum())
-    return dict(covered=covered / e["vis"].size, rewritten=(int(e["mask"].sum()) / covered) if covered else None,
-                overlays_show=bool((e["frame"] != e["shaded"]).any()))
+    m, d = e["mask"], e["drape_mask"]
+    return dict(covered=covered / e["vis"].size, rewritten=(int(m.sum()) / covered) if covered else None,
+                draped=(int(d.sum()) / covered) if covered and c["drape"] is not None else None,
+                masks_cross=bool((m & d).any() and (m & ~d).any() and (d & ~m).any()),
+                overlays_show=bool((e["frame"] != e["draped"]).any()))
 
 
 # ---- the GPU side ----------------------------------------------------------------------------------------------------
@@ -476,6 +617,17 @@ def _set_features(t, state):
     P = state["ambient_params"]
     t.set_shadows(state["shadows"], **state["shadow_params"])
     t.set_ambient_occlusion(state["ambient"], strength=P["strength"], reach=P["reach"], directions=P["directions"])
+
+
+def _set_drape(t, D):
+    """the state's drape on the handle -> what drape_info() must say then"""
+    if D is None:
+        t.clear_drape()
+        return None
+    t.set_drape(D["image"], extent=D["extent"], opacity=D["opacity"], filter=D["filter"])
+    ih, iw = D["image"].shape[:2]
+    return dict(width=iw, height=ih, extent=tuple(float(f32(v)) for v in (drm.FULL_EXTENT if D["extent"] is None else D["extent"])),
+                opacity=float(f32(D["opacity"])), filter=D["filter"])
 
 
 def run_case(c, seed=None, cache=None):
@@ -527,13 +679,26 @@ def run_case(c, seed=None, cache=None):
         t.set_shade_precision(1)
         plain = frame(t).copy()
         differ(3, "fast frame more than 1 LSB from the oracle", (np.abs(plain.astype(np.int16) - e["rgba"].astype(np.int16)) > 1).any(axis=2))
-        state = featured(c, state)
+        state = featured(c, state, drape=False)
         _set_features(t, state)
         e = expected(c, state, cache)
         got = frame(t)
         differ(3, "rewritten pixels", (got != e["shaded"]).any(axis=2) & e["mask"])
         differ(3, "other pixels against the frame before", (got != plain).any(axis=2) & ~e["mask"])
         differ(3, "other pixels more than 1 LSB from the oracle", (np.abs(got.astype(np.int16) - e["rgba"].astype(np.int16)) > 1).any(axis=2) & ~e["mask"])
+        if t.drape_info() is not None:
+            bad.append((seed, 3, "drape_info() of a handle that never had a drape is not None", 1, []))
+        if c["drape"] is not None:                            # the draped image, still in fast precision; the second frame is the one planned ahead
+            state = featured(c, state)
+            info = _set_drape(t, state["drape"])
+            if t.drape_info() != info:
+                bad.append((seed, 3, f"drape_info() {t.drape_info()} against {info}", 1, []))
+            e = expected(c, state, cache)
+            for again in ("", " drawn again"):
+                got = frame(t)
+                differ(3, "draped pixels" + again, (got != e["draped"]).any(axis=2) & e["drape_mask"])
+                differ(3, "rewritten pixels outside the drape" + again, (got != e["shaded"]).any(axis=2) & e["mask"] & ~e["drape_mask"])
+                differ(3, "other pixels against the frame before" + again, (got != plain).any(axis=2) & ~e["mask"] & ~e["drape_mask"])
         # 4. exact precision, the overlays
         t.set_shade_precision(0)
         ids, nseg = _add_overlays(t, c)
@@ -549,7 +714,8 @@ def run_case(c, seed=None, cache=None):
                 bad.append((seed, 4, f"layer {k}: {n} primitives against {L.counts[k]}", 1, []))
         differ(4, "frame", (frame(t) != e["frame"]).any(axis=2))
         differ(4, "frame drawn again", (frame(t) != e["frame"]).any(axis=2))
-        compare_planes(4, state, e["vis"])
+        compare_planes(4, state, e["vis"])                    # (the planes and the visibility know nothing of the drape)
+        differ(4, "visibility", t.read_visibility() != e["vis"])
         # 5. the mutation
         kind, a = c["mutation"], c["mutation_args"]
         scans = (t.shadow_scans(), t.ambient_scans())
@@ -562,14 +728,27 @@ def run_case(c, seed=None, cache=None):
             t.clear_overlays()
         elif kind == "layer_occlusion":
             t.set_layer_occlusion(ids[a["layer"]], *state["occlusion"][a["layer"]])
+        elif kind in DRAPE_MUTATIONS:
+            info = _set_drape(t, state["drape"])
+            if t.drape_info() != info:
+                bad.append((seed, 5, f"drape_info() {t.drape_info()} against {info} after {kind}", 1, []))
         else:
             _set_features(t, state)
         e = expected(c, state, cache)
         differ(5, f"frame after {kind}", (frame(t) != e["frame"]).any(axis=2))
+        if kind == "drape_opacity_zero":                      # nothing is written by the drape: the frame of the state without one
+            differ(5, "frame at opacity 0 against the state without a drape", (frame(t) != expected(c, dict(state, drape=None), cache)["frame"]).any(axis=2))
         rose = (t.shadow_scans() - scans[0], t.ambient_scans() - scans[1])
         must = (int(state["shadows"] and kind in STALE_SHADOW), int(state["ambient"] and kind in STALE_AMBIENT))
         if rose != must:
             bad.append((seed, 5, f"after {kind} the shadow / sky-view field was computed {rose} times, the contract says {must}", 1, []))
+        # 6. the drape cleared: the frame of the same state without one
+        if state["drape"] is not None:
+            state = dict(state, drape=None)
+            _set_drape(t, None)
+            differ(6, "frame after clear_drape", (frame(t) != expected(c, state, cache)["frame"]).any(axis=2))
+        if t.drape_info() is not None:
+            bad.append((seed, 6, f"drape_info() {t.drape_info()} after clear_drape", 1, []))
     finally:
         t.close()
     return bad
@@ -626,8 +805,12 @@ def describe(stat):
     n = max(len(stat), 1)
     shaded = [s["rewritten"] for s in stat if s["rewritten"] is not None]
     partial = sum(0.1 < r < 0.9 for r in shaded)
+    draped = [s for s in stat if s["draped"] is not None]
     return (f"{100.0 * sum(s['covered'] > 0.05 for s in stat) / n:.0f} % of the cases with more than 5 % of the pixels covered, "
             f"{100.0 * partial / max(len(shaded), 1):.0f} % of the covered ones rewrite 10-90 % of the covered pixels, "
+            f"{len(draped)} draped and covered cases of which the drape rewrites 10-90 % of the covered pixels in "
+            f"{100.0 * sum(0.1 < s['draped'] < 0.9 for s in draped) / max(len(draped), 1):.0f} % and crosses the shade pass's pixels in "
+            f"{100.0 * sum(s['masks_cross'] for s in draped) / max(len(draped), 1):.0f} %, "
             f"overlays change a pixel in {100.0 * sum(s['overlays_show'] for s in stat) / n:.0f} %")
 
 

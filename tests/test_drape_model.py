@@ -111,6 +111,47 @@ def test_the_nearest_filter_takes_the_texel_the_position_falls_in():
     assert np.array_equal(frame[~again], rgba[~again]) and (frame[again] != rgba[again]).any()
 
 
+@pytest.mark.parametrize("spacing", [2.0, 0.25])
+def test_the_extent_is_in_grid_coordinates_whatever_the_spacing(spacing):
+    """The twin of the test above at a spacing that is not 1 (a power of two: position.x / spacing is exact) and exaggeration -2.
+    include/vf_hip.h: the extent is in the plane in which the grid's vertices lie at -1.5 ... 1.5 and is not multiplied by the
+    spacing, unlike overlay coordinates -- the texel is the one that position / spacing falls in."""
+    import oracle
+    W, H = 257, 131
+    iw, ih = 7, 5
+    ext = np.array((-0.7, -0.5, 0.9, 0.8), f32)
+    h = heights()
+    # the top-down camera on its own line of sight, further out with the terrain's width and lifted over the exaggerated relief
+    k = spacing + 1.0
+    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, (0.0, 2.2 * k, 0.01 * k), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 60.0, 0.1, 100.0), f32).reshape(44)
+    u[36], u[38] = spacing, -2.0
+    rgba, vis = oracle.render_terrain(u, W, H, GRID, h, VIRIDIS, want_vis=True, nthreads=8, shade_mode=oracle.SHADE_REFERENCE)
+    rgba = rgba.reshape(H, W, 4)
+    iy, ix = np.meshgrid(np.arange(ih), np.arange(iw), indexing="ij")
+    img = np.stack([ix, iy, (ix * 7 + iy * 3) % 256, np.full_like(ix, 255)], axis=2).astype(np.uint8)
+    frame, again, sample = drm.frame(rgba, vis, u, h, GRID, VIRIDIS, img, extent=ext, filter="nearest", want_sample=True)
+    _, pos, _ = gbm.planes(vis, u, h, GRID)
+    x, z = pos[..., 0] / f32(spacing), pos[..., 2] / f32(spacing)              # exact: back in the grid's plane
+    sx, sz = f32(iw) / (ext[2] - ext[0]), f32(ih) / (ext[3] - ext[1])
+    fu, fv = (x - ext[0]) * sx, (z - ext[1]) * sz
+    inside = (vis != 0) & (fu >= 0) & (fu <= f32(iw)) & (fv >= 0) & (fv <= f32(ih))
+    assert np.array_equal(again, inside)
+    cx = np.minimum(np.floor(fu[inside]).astype(np.int64), iw - 1)
+    cy = np.minimum(np.floor(fv[inside]).astype(np.int64), ih - 1)
+    decode = oracle.srgb_tables()[0]
+    got = sample[inside]
+    assert np.array_equal(got[:, 0], decode[cx]) and np.array_equal(got[:, 1], decode[cy]) and (got[:, 3] == 1.0).all()
+    assert set(cx.tolist()) == set(range(iw)) and set(cy.tolist()) == set(range(ih))
+    # the frame shows the extent's four edges; read in the spaced world, the same box would lie elsewhere
+    covered = vis != 0
+    assert (covered & ~inside & (fu < 0)).any() and (covered & ~inside & (fu > iw)).any()
+    assert (covered & ~inside & (fv < 0)).any() and (covered & ~inside & (fv > ih)).any()
+    wu, wv = (pos[..., 0] - ext[0]) * sx, (pos[..., 2] - ext[1]) * sz
+    spaced = covered & (wu >= 0) & (wu <= f32(iw)) & (wv >= 0) & (wv <= f32(ih))
+    assert (spaced != inside).sum() > 0.2 * inside.sum()
+    assert np.array_equal(frame[~again], rgba[~again]) and (frame[again] != rgba[again]).any()
+
+
 def test_filtering_is_premultiplied():
     W, H = 96, 64
     u, rgba, vis = plain(W, H, "fill")

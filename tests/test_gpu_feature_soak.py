@@ -1,7 +1,7 @@
 """A bounded slice of the feature soak (tests/soak_features.py) inside the suite: the hand-written corners, one test each, and six
 blocks of eight seeded random cases.  Every pass that runs after the tile kernel -- geometry buffers and pick, the shadow and
-sky-view fields and their shade passes, point / line / polygon / contour overlays with occlusion -- equals its CPU model on the
-oracle's frame, before and after one mutation of the handle.  Fixed seeds (a failure reproduces from the commit alone);
+sky-view fields and their shade passes, the draped image, point / line / polygon / contour overlays with occlusion -- equals its
+CPU model on the oracle's frame, before and after one mutation of the handle and after the drape is cleared.  Fixed seeds (a failure reproduces from the commit alone);
 VF_FEATURE_SOAK_FIRST_SEED moves the window.  tests/test_feature_soak_cases.py asserts, without a GPU, that these very cases
 are not vacuous."""
 import os
