@@ -1,5 +1,5 @@
 /* ambient_model.c -- CPU model of ambient occlusion from a sky-view scan, the contract the gfx950 kernels of
- * vulkan_forge_amd/csrc/vf_ambient.h (k_ambient_dir, k_ambient_shade) are held to bit for bit.  Written from the contract: the field
+ * vulkan_forge_amd/csrc/vf_ambient.h (k_ambient_dir) and vf_relight.h (k_relight<., kAmbient>) are held to bit for bit.  Written from the contract: the field
  * is the plain walk over every direction, every sheared line of it (the lines of DESIGN.md 4g) and every vertex's R_t predecessors,
  * with no tiles and no table; the frame takes a frame and its visibility ids, interpolates lit and amb of every covered pixel as the
  * shadow model interpolates lit (included below) and shades the pixels where either is below 1 again with a restatement of fs_main

@@ -1,5 +1,5 @@
 /* drape_model.c -- CPU model of the draped image layer, the contract the gfx950 kernel of
- * vulkan_forge_amd/csrc/vf_drape.h (k_drape_shade) is held to bit for bit.  Written from the contract: the frame takes a frame and
+ * vulkan_forge_amd/csrc/vf_drape.h and vf_relight.h (k_relight<., kDrape>) is held to bit for bit.  Written from the contract: the frame takes a frame and
  * its visibility ids, forms the varyings (h, x, z) of every covered pixel as the shadow and ambient models do (included below: clip,
  * fan, last covering piece), samples the image at (x, z) and shades the pixels whose sample is not transparent again with a
  * restatement of fs_main in which the colormap value is mixed with the sample; lit and amb are formed by the rules of 4g and 4i.

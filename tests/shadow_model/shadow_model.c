@@ -1,5 +1,5 @@
 /* shadow_model.c -- CPU model of cast sun shadows, the contract the gfx950 kernels of
- * vulkan_forge_amd/csrc/vf_shadow.h (k_shadow_chunk_max / _carry / _lit, k_shadow_shade) are held to bit for bit.  Written from the
+ * vulkan_forge_amd/csrc/vf_shadow.h (k_shadow_chunk_max / _carry / _lit) and vf_relight.h (k_relight) are held to bit for bit.  Written from the
  * contract: the field is the plain sequential walk along every sheared line, with no scan; the shadowed frame takes a frame and its
  * visibility ids, interpolates the three vertex values of every covered pixel with the geometry-buffer model's weights (included
  * below: clip, fan, last covering piece) and shades the pixels below 1 again with a restatement of fs_main and the sRGB store

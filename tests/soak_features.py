@@ -366,7 +366,7 @@ _SPECS = [
     _corner(24, "drape_transparent_image", mutation="drape_replace", ambient=_amb(16.0, _FAN),
             drape=dict(image=distinct_image(37, 7) * np.array([1, 1, 1, 0], np.uint8), extent=None, extent_kind="whole", opacity=1.0, filter="linear",
                        replace=dict(image=distinct_image(64, 3)[..., :3].copy(), extent=None, extent_kind="whole", opacity=1.0, filter="nearest"))),
-    # the eye low over the middle of a coarse grid: the near plane cuts triangles the image covers, so k_drape_shade<true> sends lit
+    # the eye low over the middle of a coarse grid: the near plane cuts triangles the image covers, so k_relight<true, kDrape> sends lit
     # and amb through the clipper in the place of the height, under a low sun and an ambient fan that leave neither at 1;
     # then the shadows go while the drape stays
     _corner(25, "drape_near_plane_through_the_terrain", grid=9, eye=(0.9, 0.7, 0.8), target=(-0.4, -0.2, -0.3), znear=0.4, fovy=60.0,

@@ -301,6 +301,34 @@ def test_refusals_change_nothing(vf):
     assert s.drape_info()["opacity"] == 1.0
 
 
+def test_the_stage_calls_hand_the_scan_counters_back():
+    """drape_stage brings the shadow and sky-view fields up to date itself, ambient_stage the shadow field: diagnostic launches are
+    not the handle's, whichever call makes them"""
+    from vulkan_forge_amd import cabi
+    import oracle
+    W, H = 257, 131
+    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    u[32:35] = shm.sun_vector(*abm.SCENE_SUN_DEG)
+    t = cabi.Terrain(W, H, 32, viridis())
+    t.set_height(heights(2, (32, 32)))
+    t.set_uniforms(u)
+    t.set_shadows(True, **abm.SCENE_SHADOWS)
+    t.set_ambient_occlusion(True, strength=abm.SCENE_PARAMS["strength"], reach=abm.SCENE_PARAMS["reach"], directions=abm.scene_directions())
+    t.set_drape(drm.image(), extent=drm.EXTENT, opacity=0.37, filter="linear")
+    t.render()
+    frame = t.read_rgba().copy()
+    info, scans = t.drape_info(), (t.shadow_scans(), t.ambient_scans())
+    assert scans == (1, 1) and info["width"] == 37 and info["height"] == 53
+    ms = (t.drape_stage(2), *t.ambient_stage(2), *t.shadow_stage(2))
+    print("drape, ambient field, ambient shade, shadow field, shadow shade ms:", ms)
+    assert all(v > 0 for v in ms)
+    assert (t.shadow_scans(), t.ambient_scans()) == scans
+    t.render()
+    assert np.array_equal(t.read_rgba(), frame) and t.drape_info() == info
+    assert (t.shadow_scans(), t.ambient_scans()) == scans
+    t.close()
+
+
 def test_the_image_from_device_memory_on_a_stream_of_the_callers():
     r = subprocess.run([sys.executable, os.path.join(HERE, "drape_torch_check.py")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "DRAPE TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])

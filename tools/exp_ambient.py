@@ -2,8 +2,8 @@
 """Cost of ambient occlusion (include/vf_hip.h vf_terrain_set_ambient / _read_sky_view_field) at C4 (4096 x 4096, grid 4096).
 
 The field (k_ambient_dir, one launch per direction) for reach 16, 64 and 256 and one direction of each class -- on an axis, a general
-x-major and z-major one, 45 degrees -- and for the default sixteen; the shade pass (k_ambient_shade) next to the cast-shadow shade
-pass (k_shadow_shade) of the same frame under the default and the fill camera; and the whole frame with ambient occlusion against
+x-major and z-major one, 45 degrees -- and for the default sixteen; the shade pass (k_relight<., kAmbient>) next to the cast-shadow shade
+pass (k_relight<., kShadow>) of the same frame under the default and the fill camera; and the whole frame with ambient occlusion against
 the plain one.  Kernel times are HIP events around `--launches` back-to-back launches after a warm-up
 (vf_terrain_debug_ambient_stage / _shadow_stage); the variants alternate within the process, `--reps` rounds, and the median is
 reported with the spread (max - min) of the rounds.  Slope evaluations of a field: the (vertex, predecessor) pairs the contract asks

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Cost of the draped image layer (include/vf_hip.h vf_terrain_set_drape) at C4 (4096 x 4096, grid 4096).
 
-The drape shade pass (k_drape_shade, vf_terrain_debug_drape_stage) under the default and the fill camera, for opaque full-extent
-images of 4096^2 and 16384^2 texels and both filters, next to the shadow shade pass (k_shadow_shade: the same walk and weights plus
-three field gathers, the yardstick) and the exact resolve pass of the same frame in the same session; and the whole draped frame
+The drape shade pass (k_relight<., kDrape>, vf_terrain_debug_drape_stage) under the default and the fill camera, for opaque full-extent
+images of 4096^2 and 16384^2 texels and both filters, next to the shadow shade pass (k_relight<., kShadow>: the same walk and weights
+plus three field gathers, the yardstick) and the exact resolve pass of the same frame in the same session; and the whole draped frame
 against the plain one.  Kernel times are HIP events around `--launches` back-to-back launches after a warm-up; the variants alternate
 within the process, `--reps` rounds, and the median is reported with the spread (max - min) of the rounds.  Run it twice.
 

@@ -2,7 +2,7 @@
 """Cost of cast shadows (include/vf_hip.h vf_terrain_set_shadows / _read_shadow_field) at C4 (4096 x 4096, grid 4096).
 
 The scan (k_shadow_chunk_max, k_shadow_carry, k_shadow_lit) for suns on the x axis, on the z axis, at 45 degrees and at a general
-azimuth in each major axis; the shade pass (k_shadow_shade) under the default and the fill camera next to the exact resolve pass of the
+azimuth in each major axis; the shade pass (k_relight<., kShadow>) under the default and the fill camera next to the exact resolve pass of the
 same frame (vf_terrain_debug_fragment_stage); and the whole shadowed frame against the unshadowed one.  Kernel times are HIP events
 around `--launches` back-to-back launches after a warm-up (vf_terrain_debug_shadow_stage); the variants alternate within the process,
 `--reps` rounds, and the median is reported with the spread (max - min) of the rounds.  Algorithmic bytes of a scan: 4 n^2 of heights

@@ -24,14 +24,16 @@ def collect():
     out.append("")
     out.append(f"{'kernel':34s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'LDS B':>7s} {'scratch B':>9s} {'waves/SIMD':>10s} {'code B':>7s} {'scratch ld/st':>13s}")
     def demangle(n):
-        """vf::k_tile<false, false, true> from the mangled name, without a demangler: the template arguments are the Lb0E / Lb1E runs"""
+        """vf::k_tile<false, false, true> from the mangled name, without a demangler: the template arguments are the Lb0E / Lb1E runs
+        (and Li2E / LNS_7RelightE2E, an int or an enumerator of the namespace: its number)"""
         m = re.match(r"_ZN2vf(\d+)", n)
         if not m:
             return n
         ln = int(m.group(1)); base = n[len(m.group(0)):len(m.group(0)) + ln]; rest = n[len(m.group(0)) + ln:]
-        t = re.match(r"I((?:Lb[01]E)+)E", rest)
+        arg = r"L(b|i|NS_\d+[A-Za-z_]+E)(\d+)E"
+        t = re.match(rf"I((?:{arg})+)E", rest)
         if t:
-            return base + "<" + ", ".join("true" if b == "1" else "false" for b in re.findall(r"Lb([01])E", t.group(1))) + ">"
+            return base + "<" + ", ".join(("true" if v == "1" else "false") if k == "b" else v for k, v in re.findall(arg, t.group(1))) + ">"
         t = re.match(r"I([fd])E", rest)
         return base + ("<float>" if t and t.group(1) == "f" else "<double>" if t else "")
     # one linear pass: a kernel's text runs from its label to .Lfunc_end; its notes ("; NumVgprs: ..") follow under "; Kernel info:"

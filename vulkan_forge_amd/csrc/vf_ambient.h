@@ -4,8 +4,8 @@
 //                       directions: k_ambient_dir, one launch per direction over the sheared lines of the shadow scan (ShadowPlan,
 //                       sh_vertex), forms every vertex's horizon slope over its R predecessors on its line and adds the occlusion
 //                       to the field; the last launch turns the sum into sky
-//   the shade pass      k_ambient_shade is k_shadow_shade with sh_pixel<., AMBIENT = true>: one pass serves cast shadows and
-//                       ambient occlusion together
+//   the shade pass      k_relight<., kAmbient> (vf_relight.h): one pass serves cast shadows and ambient occlusion
+//                       together
 //
 // Launched only for a handle that asked for ambient occlusion or for the field.  The arithmetic is the contract's, bit for bit
 // (tests/ambient_model/ambient_model.c is its CPU statement): the horizon is a maximum, exact in any order, of terms formed from the
@@ -110,28 +110,6 @@ __global__ __launch_bounds__(256) void k_ambient_dir(AmbientPlan A, const float 
             if (sh_vertex(S, l0 + wave + 4u * gi, k0 + lane, i, j)) am_store(A, sky, (size_t)j * S.n + i, y[gi], T[gi]);
         }
     }
-}
-
-// ---- the shade pass ---------------------------------------------------------------------------------------------------------
-
-// k_shadow_shade (vf_shadow.h) with ambient occlusion: the frame's visibility -> the pixels whose interpolated lit or amb is below
-// 1, written again with lambert * lit and shade * amb.  lit: the shadow field, NULL when cast shadows are off.
-template <bool CLIPPED>
-__global__ __launch_bounds__(256) void k_ambient_shade(FrameParams P, SetupView V, const float *__restrict__ lut_linear, const float *__restrict__ thresh,
-                                                       const uint32_t *__restrict__ vis, const float *__restrict__ lit, const float *__restrict__ sky,
-                                                       float strength, const uint32_t *__restrict__ redo, uint32_t *__restrict__ rgba)
-{
-    if ((*redo != 0u) != CLIPPED) return;
-    __shared__ __attribute__((aligned(16))) float s_lut[kLutFloats];
-    __shared__ float s_thr[256];
-    for (int k = threadIdx.x; k < kLutFloats; k += 256) s_lut[k] = lut_linear[k];
-    s_thr[threadIdx.x] = thresh[threadIdx.x];
-    __syncthreads();
-    const ShadeTables T = { s_lut, s_thr };
-    for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
-        uint32_t c;
-        if (id != 0u && sh_pixel<CLIPPED, true>(P, V, T, lit, sky, strength, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
-    });
 }
 
 } // namespace vf

@@ -7,6 +7,7 @@
 #include "vf_shadow.h"      // templates only
 #include "vf_ambient.h"     // templates only
 #include "vf_drape.h"       // templates only
+#include "vf_relight.h"     // templates only: the shade pass of the three
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -1476,9 +1477,8 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 
 // diag: a visibility / diagnostics frame (render_visibility): stores its visibility, composites no overlays.  A frame of a handle with an
 // occluding overlay layer stores its visibility too, for the overlay pass.
-static int shadow_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-static int ambient_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows);
-static int drape_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows, bool ambient);
+static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
+                        bool shadows, bool ambient);
 
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
@@ -1492,6 +1492,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
     vf_terrain::FrameEvents &ev = t->ev[t->timed_frames % (uint32_t)vf_terrain::kTimingRing];
     const bool timing_now = t->timing && K.sampled;
+    const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
     // ---- draw, on the caller's stream: everything that touches the output buffers ----
     uint32_t *stats = t->timing && t->stats_on ? t->d_stats : nullptr;
     const uint32_t nstats = (uint32_t)stats_layout(t).words;     // zeroed by k_clear (no memset dispatch)
@@ -1519,7 +1520,6 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         // oversized primitive (normally none)
         const dim3 per_cu(std::min<uint32_t>((uint32_t)std::max(1, t->ctx->prop.multiProcessorCount) * (1024u / (uint32_t)kTileThreads), ntiles + kSplitBudget)),
                    few(std::min<uint32_t>(64u, ntiles + kSplitBudget)), threads(kTileThreads);
-        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
 #define VF_TILE_ARGS P, V, S.row_ranges, S.cap_seg, S.cap_rad, t->d_lut, t->ctx->d_thresh, S.work_sorted, S.work_count, \
                      rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo
         const bool fast = fast_shading(t->inputs);
@@ -1541,17 +1541,14 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev.end, s)); t->timed_frames++; }
     if ((shadows || ambient) && ntiles) {                  // cast shadows and ambient occlusion: behind the tile kernels, in front of the overlays
-        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
-        const int src = ambient ? ambient_pass(t, s, P, V, S.work_count + 3, t->d_rgba, shadows) : shadow_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        const int src = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, ambient ? kAmbient : kShadow, shadows, ambient);
         if (src != VF_OK) return src;
     }
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
-        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
-        const int drc = drape_pass(t, s, P, V, S.work_count + 3, t->d_rgba, shadows, ambient);
+        const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, kDrape, shadows, ambient);
         if (drc != VF_OK) return drc;
     }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
-        const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
         const int orc = overlay_pass(t, s, P, V);
         if (orc != VF_OK) return orc;
     }
@@ -2473,21 +2470,17 @@ int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repe
 
 // ---- cast shadows (vf_shadow.h) ---------------------------------------------------------
 
-// The frame of reference of the field for the uniforms `u`; false: every vertex is lit.  The ratios come
-// from the sun vector as given, not from the normalised one: they are free of scale, so the lines depend on the azimuth alone.
-static bool shadow_plan(const vf_terrain *t, const float *u, ShadowPlan &S)
+// The sheared grid lines that run along the horizontal direction (hx, hz): S.n ... S.nchunks, and the
+// magnitude of the direction's major component; false when it has no usable horizontal part.  The ratio comes from the vector as
+// given, not from a normalised one: it is free of scale, so the lines depend on the azimuth alone.
+static bool line_geometry(const vf_terrain *t, float hx, float hz, ShadowPlan &S, float &amaj)
 {
-    const vf_terrain::Shadows &H = t->sh;
-    const float sx = u[32], sy = u[33], sz = u[34];
-    const float ax = std::fabs(sx), az = std::fabs(sz);
+    const float ax = std::fabs(hx), az = std::fabs(hz);
     const bool zmajor = az > ax;                              // a tie goes to x
-    const float amaj = zmajor ? az : ax, amin = zmajor ? ax : az;
-    const float smaj = zmajor ? sz : sx, smin = zmajor ? sx : sz;
-    if (!(amaj > 0.0f) || !std::isfinite(amaj) || !(amin <= amaj) || !std::isfinite(sy)) return false;
-    const float spacing = std::fmax(u[36], 1e-8f);
-    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
-    const float d = sy > 0.0f ? ((step * spacing) * sy) / amaj : 0.0f;
-    if (!std::isfinite(d)) return false;
+    amaj = zmajor ? az : ax;
+    const float amin = zmajor ? ax : az;
+    const float smaj = zmajor ? hz : hx, smin = zmajor ? hx : hz;
+    if (!(amaj > 0.0f) || !std::isfinite(amaj) || !(amin <= amaj)) return false;
     S.n = t->n; S.nb = t->nb;
     S.zmajor = zmajor ? 1u : 0u;
     S.from_high = smaj > 0.0f ? 1u : 0u;
@@ -2497,6 +2490,20 @@ static bool shadow_plan(const vf_terrain *t, const float *u, ShadowPlan &S)
     S.c_lo = S.s > 0 ? 0 : -R;
     S.nlines = t->n + (uint32_t)R;
     S.nchunks = (t->n + kShChunk - 1u) / kShChunk;
+    return true;
+}
+
+// The frame of reference of the field for the uniforms `u`; false: every vertex is lit.
+static bool shadow_plan(const vf_terrain *t, const float *u, ShadowPlan &S)
+{
+    const vf_terrain::Shadows &H = t->sh;
+    const float sy = u[33];
+    float amaj;
+    if (!line_geometry(t, u[32], u[34], S, amaj) || !std::isfinite(sy)) return false;
+    const float spacing = std::fmax(u[36], 1e-8f);
+    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    const float d = sy > 0.0f ? ((step * spacing) * sy) / amaj : 0.0f;
+    if (!std::isfinite(d)) return false;
     S.d = d; S.exag = u[38]; S.strength = H.strength; S.softness = H.softness; S.bias = H.bias;
     return true;
 }
@@ -2532,23 +2539,52 @@ static int shadow_field(vf_terrain *t, const float *u, hipStream_t s, bool force
     return VF_OK;
 }
 
-// k_resolve's launch shape (gb_grid)
-static void shadow_shade_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+static int ambient_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
+
+// The fields a pass reads hold the values of the uniforms `u` once the work queued on `s` is done: the shadow field
+// if asked, the sky-view field if asked; at no cost when they are current.  force: compute them anyway.
+static int relight_fields(vf_terrain *t, const float *u, hipStream_t s, bool shadows, bool ambient, bool force = false)
 {
-    const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_shadow_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
-                       (const float *)t->sh.d_lit.p, redo, rgba);
-    hipLaunchKernelGGL((k_shadow_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
-                       (const float *)t->sh.d_lit.p, redo, rgba);
+    if (shadows) { if (int rc = shadow_field(t, u, s, force)) return rc; }
+    if (ambient) { if (int rc = ambient_field(t, u, s, force)) return rc; }
+    return VF_OK;
 }
 
-// The shadows of a frame, on the draw stream behind its tile kernels (which stored the visibility): the field if it is stale, then
-// the shade pass over the covered pixels.
-static int shadow_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+// Both instantiations of a pass of the relight kernel (vf_relight.h), in k_resolve's launch shape (gb_grid).  shadows / ambient:
+// the pass reads that field (kShadow reads the shadow field, kAmbient the sky-view field, whatever they say).
+static void relight_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
+                           bool shadows, bool ambient)
 {
-    const int rc = shadow_field(t, t->inputs.u, s);
-    if (rc != VF_OK) return rc;
-    shadow_shade_launch(t, s, P, V, redo, rgba);
+    RelightParams R = {};
+    R.lit = shadows || pass == kShadow ? t->sh.d_lit.p : nullptr;
+    R.sky = ambient || pass == kAmbient ? t->am.d_sky.p : nullptr;
+    R.amb_strength = t->am.strength;
+    const dim3 grid = gb_grid(t), threads(256);
+#define VF_RELIGHT(CLIPPED, PASS) hipLaunchKernelGGL((k_relight<CLIPPED, PASS>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, \
+                                                     (const uint32_t *)t->d_vis, R, redo, rgba)
+    if (pass == kShadow) { VF_RELIGHT(false, kShadow); VF_RELIGHT(true, kShadow); }
+    else if (pass == kAmbient) { VF_RELIGHT(false, kAmbient); VF_RELIGHT(true, kAmbient); }
+    else {
+        const vf_terrain::Drape &H = t->dr;
+        R.decode = H.d_decode.p; R.img = H.d_img.p;
+        DrapeParams &D = R.D;
+        D.x0 = H.extent[0]; D.z0 = H.extent[1];
+        D.sx = (float)H.iw / (H.extent[2] - H.extent[0]); D.sz = (float)H.ih / (H.extent[3] - H.extent[1]);
+        D.iw = H.iw; D.ih = H.ih; D.opacity = H.opacity; D.linear = H.filter == VF_DRAPE_LINEAR ? 1u : 0u;
+        VF_RELIGHT(false, kDrape); VF_RELIGHT(true, kDrape);
+    }
+#undef VF_RELIGHT
+}
+
+// A relight pass of a frame, on the draw stream behind its tile kernels (which stored the visibility) and the pass before: the
+// fields it reads if they are stale, then the shade pass over the covered pixels.  The drape comes behind the shadow / ambient pass,
+// which has brought the fields up to date; they are checked again here, at no cost when they are current.
+static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
+                        bool shadows, bool ambient)
+{
+    if (int rc = relight_fields(t, t->inputs.u, s, shadows, ambient)) return rc;
+    if (pass == kDrape && t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    relight_launch(t, s, P, V, redo, rgba, pass, shadows, ambient);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
 }
@@ -2569,33 +2605,34 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
     return VF_OK;
 }
 
-// the field for the live uniforms, heights and parameters in d_lit, complete when this returns
-static int shadow_field_now(vf_terrain *t)
+// The shadow field (sky = false) or the sky-view field for the live uniforms, heights and parameters, complete in d_lit / d_sky; then
+// to `host`, or to `dev` behind the work on `stream` (NULL: the handle's)
+static int field_out(vf_terrain *t, bool sky, float *host, float *dev, void *stream)
 {
     if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     if (int rc = ct_heights_current(t)) return rc;
-    if (int rc = shadow_field(t, t->inputs.u, t->ctx->stream)) return rc;
+    if (int rc = relight_fields(t, t->inputs.u, t->ctx->stream, !sky, sky)) return rc;
     VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    const float *field = sky ? t->am.d_sky.p : t->sh.d_lit.p;
+    const size_t bytes = (size_t)t->n * t->n * sizeof(float);
+    if (host) { VF_HIP_TRY(hipMemcpy(host, field, bytes, hipMemcpyDeviceToHost)); return VF_OK; }
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    VF_HIP_TRY(hipMemcpyAsync(dev, field, bytes, hipMemcpyDeviceToDevice, s));
+    VF_HIP_TRY(gb_order_after(t, s));                         // (a later field of this handle is computed behind the copy)
     return VF_OK;
 }
 
 int vf_terrain_read_shadow_field(vf_terrain *t, float *lit)
 {
     if (!t || !lit) return fail(VF_ERR_INVALID, "NULL argument");
-    if (int rc = shadow_field_now(t)) return rc;
-    VF_HIP_TRY(hipMemcpy(lit, t->sh.d_lit.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToHost));
-    return VF_OK;
+    return field_out(t, false, lit, nullptr, nullptr);
 }
 
 int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream)
 {
     if (!t || !dev_lit) return fail(VF_ERR_INVALID, "NULL argument");
-    if (int rc = shadow_field_now(t)) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
-    VF_HIP_TRY(hipMemcpyAsync(dev_lit, t->sh.d_lit.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    VF_HIP_TRY(gb_order_after(t, s));                         // (a later field of this handle is computed behind the copy)
-    return VF_OK;
+    return field_out(t, false, nullptr, dev_lit, stream);
 }
 
 int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count)
@@ -2605,22 +2642,50 @@ int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count)
     return VF_OK;
 }
 
+// What the three stage calls below start from: the frame rendered last, drawn again into scratch buffers with its visibility
+// (gb_frame), the uniforms it was drawn with and its `redo` word.  Their launches are diagnostic, not the handle's: the scan
+// counters are handed back as open() found them, whichever way the call returns.
+struct RelightStage {
+    GbFrame F;
+    const float *u = nullptr;
+    const uint32_t *redo = nullptr;
+    hipStream_t s = nullptr;
+    vf_terrain *t = nullptr;
+    uint32_t shadow_scans = 0, ambient_scans = 0;
+    int open(vf_terrain *handle)
+    {
+        if (int rc = gb_frame(handle, F)) return rc;
+        t = handle;
+        u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
+        redo = t->ps[t->last_set].work_count + 3;
+        s = t->ctx->stream;
+        shadow_scans = t->sh.scans; ambient_scans = t->am.scans;
+        return VF_OK;
+    }
+    // the shade pass into the scratch frame, timed; the fields it reads are current
+    hipError_t time_shade(uint32_t repeats, float &ms, Relight pass) const
+    {
+        return time_launches(s, repeats, ms, [&](bool) { relight_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, pass, t->sh.enabled, t->am.enabled); return hipGetLastError(); });
+    }
+    // a field computed anyway, timed; one that fails has stated its own error: rc
+    hipError_t time_field(uint32_t repeats, float &ms, bool sky, int &rc) const
+    {
+        return time_launches(s, repeats, ms, [&](bool) { rc = relight_fields(t, u, s, !sky, sky, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    }
+    ~RelightStage() { if (t) { t->sh.scans = shadow_scans; t->am.scans = ambient_scans; } }
+};
+
 int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
 {
     if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
     if (repeats == 0) repeats = 1;
-    GbFrame F;                                                // the frame rendered last, drawn again into scratch buffers with its visibility
-    int rc = gb_frame(t, F);
+    RelightStage G;
+    int rc = G.open(t);
     if (rc != VF_OK) return rc;
-    const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
-    hipStream_t s = t->ctx->stream;
-    const uint32_t scans = t->sh.scans;
-    const uint32_t *redo = t->ps[t->last_set].work_count + 3;
     float a = 0.0f, b = 0.0f;
-    // the field first (its last launch leaves what the shade pass reads); one that fails has stated its own error: rc
-    hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = shadow_field(t, u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
-    if (err == hipSuccess) err = time_launches(s, repeats, b, [&](bool) { shadow_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch); return hipGetLastError(); });
-    t->sh.scans = scans;                                      // (diagnostic launches are not the handle's)
+    // the field first (its last launch leaves what the shade pass reads)
+    hipError_t err = G.time_field(repeats, a, false, rc);
+    if (err == hipSuccess) err = G.time_shade(repeats, b, kShadow);
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("shadow diagnostics: ") + hipGetErrorString(err));
     ms[0] = a; ms[1] = b;
@@ -2642,24 +2707,13 @@ static void ambient_default_dirs(uint32_t D, std::vector<float> &dirs)
     }
 }
 
-// The frame of reference of direction (ux, uz) of the field for the uniforms `u`; the lines are
-// shadow_plan's with the sun's horizontal part set to the direction (set_ambient has refused a direction without one).
+// The frame of reference of direction (ux, uz) of the field for the uniforms `u`: the lines are
+// line_geometry's (set_ambient has refused a direction without a horizontal part).
 static void ambient_plan(const vf_terrain *t, const float *u, float ux, float uz, AmbientPlan &A)
 {
     ShadowPlan &S = A.S;
-    const float ax = std::fabs(ux), az = std::fabs(uz);
-    const bool zmajor = az > ax;                              // a tie goes to x
-    const float amaj = zmajor ? az : ax, amin = zmajor ? ax : az;
-    const float smaj = zmajor ? uz : ux, smin = zmajor ? ux : uz;
-    S.n = t->n; S.nb = t->nb;
-    S.zmajor = zmajor ? 1u : 0u;
-    S.from_high = smaj > 0.0f ? 1u : 0u;
-    S.s = smin < 0.0f ? -1 : 1;
-    S.a = amin / amaj;
-    const int32_t R = (int32_t)std::rint((float)(t->n - 1u) * S.a);
-    S.c_lo = S.s > 0 ? 0 : -R;
-    S.nlines = t->n + (uint32_t)R;
-    S.nchunks = (t->n + kShChunk - 1u) / kShChunk;
+    float amaj;
+    (void)line_geometry(t, ux, uz, S, amaj);
     S.d = 0.0f; S.exag = u[38]; S.strength = 0.0f; S.softness = 1.0f; S.bias = 0.0f;
     const float spacing = std::fmax(u[36], 1e-8f);
     const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
@@ -2671,7 +2725,7 @@ static void ambient_plan(const vf_terrain *t, const float *u, float ux, float uz
 
 // d_sky holds the field of the uniforms `u`, the handle's heights, directions and reach once the work queued on `s` is done (the
 // height cache must be current and ordered before `s`, as for shadow_field).  force: compute it anyway.
-static int ambient_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false)
+static int ambient_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::Ambient &H = t->am;
     const size_t nv = (size_t)t->n * t->n;
@@ -2699,26 +2753,6 @@ static int ambient_field(vf_terrain *t, const float *u, hipStream_t s, bool forc
     return VF_OK;
 }
 
-// k_resolve's launch shape (gb_grid); lit: the shadow field or NULL
-static void ambient_shade_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, const float *lit)
-{
-    const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_ambient_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
-                       lit, (const float *)t->am.d_sky.p, t->am.strength, redo, rgba);
-    hipLaunchKernelGGL((k_ambient_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis,
-                       lit, (const float *)t->am.d_sky.p, t->am.strength, redo, rgba);
-}
-
-// Ambient occlusion of a frame, and its cast shadows when they are on as well: the fields that are stale, then one shade pass.
-static int ambient_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows)
-{
-    if (shadows) { if (int rc = shadow_field(t, t->inputs.u, s)) return rc; }
-    if (int rc = ambient_field(t, t->inputs.u, s)) return rc;
-    ambient_shade_launch(t, s, P, V, redo, rgba, shadows ? t->sh.d_lit.p : nullptr);
-    VF_HIP_TRY(hipGetLastError());
-    return VF_OK;
-}
-
 int vf_terrain_set_ambient(vf_terrain *t, int enable, float strength, float reach, uint32_t ndirs, const float *dirs_xz)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
@@ -2742,33 +2776,16 @@ int vf_terrain_set_ambient(vf_terrain *t, int enable, float strength, float reac
     return VF_OK;
 }
 
-// the field for the live uniforms, heights and parameters in d_sky, complete when this returns
-static int ambient_field_now(vf_terrain *t)
-{
-    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    if (int rc = ct_heights_current(t)) return rc;
-    if (int rc = ambient_field(t, t->inputs.u, t->ctx->stream)) return rc;
-    VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    return VF_OK;
-}
-
 int vf_terrain_read_sky_view_field(vf_terrain *t, float *sky)
 {
     if (!t || !sky) return fail(VF_ERR_INVALID, "NULL argument");
-    if (int rc = ambient_field_now(t)) return rc;
-    VF_HIP_TRY(hipMemcpy(sky, t->am.d_sky.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToHost));
-    return VF_OK;
+    return field_out(t, true, sky, nullptr, nullptr);
 }
 
 int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream)
 {
     if (!t || !dev_sky) return fail(VF_ERR_INVALID, "NULL argument");
-    if (int rc = ambient_field_now(t)) return rc;
-    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
-    VF_HIP_TRY(hipMemcpyAsync(dev_sky, t->am.d_sky.p, (size_t)t->n * t->n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    VF_HIP_TRY(gb_order_after(t, s));                         // (a later field of this handle is computed behind the copy)
-    return VF_OK;
+    return field_out(t, true, nullptr, dev_sky, stream);
 }
 
 int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count)
@@ -2782,54 +2799,21 @@ int vf_terrain_debug_ambient_stage(vf_terrain *t, uint32_t repeats, float ms[2])
 {
     if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
     if (repeats == 0) repeats = 1;
-    GbFrame F;                                                // the frame rendered last, drawn again into scratch buffers with its visibility
-    int rc = gb_frame(t, F);
+    RelightStage G;
+    int rc = G.open(t);
     if (rc != VF_OK) return rc;
-    const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
-    hipStream_t s = t->ctx->stream;
-    const uint32_t scans = t->am.scans, shadow_scans = t->sh.scans;
-    const uint32_t *redo = t->ps[t->last_set].work_count + 3;
-    if (t->sh.enabled) rc = shadow_field(t, u, s);            // (the shade pass below reads it)
+    rc = relight_fields(t, G.u, G.s, t->sh.enabled, false);  // (the shade pass below reads it)
+    if (rc != VF_OK) return rc;
     float a = 0.0f, b = 0.0f;
-    hipError_t err = hipSuccess;
-    if (rc == VF_OK) err = time_launches(s, repeats, a, [&](bool) { rc = ambient_field(t, u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
-    if (rc == VF_OK && err == hipSuccess)
-        err = time_launches(s, repeats, b, [&](bool) { ambient_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, t->sh.enabled ? t->sh.d_lit.p : nullptr); return hipGetLastError(); });
-    t->am.scans = scans; t->sh.scans = shadow_scans;          // (diagnostic launches are not the handle's)
+    hipError_t err = G.time_field(repeats, a, true, rc);
     if (rc != VF_OK) return rc;
+    if (err == hipSuccess) err = G.time_shade(repeats, b, kAmbient);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("ambient diagnostics: ") + hipGetErrorString(err));
     ms[0] = a; ms[1] = b;
     return VF_OK;
 }
 
 // ---- the draped image (vf_drape.h) ------------------------------------------------------
-
-static void drape_shade_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba,
-                               const float *lit, const float *sky)
-{
-    const vf_terrain::Drape &H = t->dr;
-    DrapeParams D;
-    D.x0 = H.extent[0]; D.z0 = H.extent[1];
-    D.sx = (float)H.iw / (H.extent[2] - H.extent[0]); D.sz = (float)H.ih / (H.extent[3] - H.extent[1]);
-    D.iw = H.iw; D.ih = H.ih; D.opacity = H.opacity; D.linear = H.filter == VF_DRAPE_LINEAR ? 1u : 0u;
-    const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_drape_shade<false>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const float *)H.d_decode.p,
-                       (const uint32_t *)t->d_vis, D, (const uint32_t *)H.d_img.p, lit, sky, t->am.strength, redo, rgba);
-    hipLaunchKernelGGL((k_drape_shade<true>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, (const float *)H.d_decode.p,
-                       (const uint32_t *)t->d_vis, D, (const uint32_t *)H.d_img.p, lit, sky, t->am.strength, redo, rgba);
-}
-
-// The drape of a frame, on the draw stream behind its shadow / ambient pass (which has brought the fields it reads up to date; they
-// are checked again here, at no cost when they are current), then one shade pass.
-static int drape_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, bool shadows, bool ambient)
-{
-    if (shadows) { if (int rc = shadow_field(t, t->inputs.u, s)) return rc; }
-    if (ambient) { if (int rc = ambient_field(t, t->inputs.u, s)) return rc; }
-    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
-    drape_shade_launch(t, s, P, V, redo, rgba, shadows ? t->sh.d_lit.p : nullptr, ambient ? t->am.d_sky.p : nullptr);
-    VF_HIP_TRY(hipGetLastError());
-    return VF_OK;
-}
 
 // the argument rules of both setters (vulkan_forge_amd/_drape.py states the same); ext: the extent to keep
 static int drape_check(const vf_terrain *t, const void *image, uint32_t iw, uint32_t ih, const float *extent, float opacity, int filter, float ext[4])
@@ -2945,23 +2929,12 @@ int vf_terrain_debug_drape_stage(vf_terrain *t, uint32_t repeats, float *ms)
     if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
     if (!t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds no draped image");
     if (repeats == 0) repeats = 1;
-    GbFrame F;                                                // the frame rendered last, drawn again into scratch buffers with its visibility
-    int rc = gb_frame(t, F);
-    if (rc != VF_OK) return rc;
-    const float *u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
-    hipStream_t s = t->ctx->stream;
-    const uint32_t scans = t->am.scans, shadow_scans = t->sh.scans;
-    const uint32_t *redo = t->ps[t->last_set].work_count + 3;
-    if (t->sh.enabled) rc = shadow_field(t, u, s);            // (the shade pass below reads them)
-    if (rc == VF_OK && t->am.enabled) rc = ambient_field(t, u, s);
-    t->am.scans = scans; t->sh.scans = shadow_scans;          // (diagnostic launches are not the handle's)
-    if (rc != VF_OK) return rc;
-    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    RelightStage G;
+    if (int rc = G.open(t)) return rc;
+    if (int rc = relight_fields(t, G.u, G.s, t->sh.enabled, t->am.enabled)) return rc;   // (the shade pass below reads them)
+    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(G.s, t->dr.copied, 0));
     float mean = 0.0f;
-    const hipError_t err = time_launches(s, repeats, mean, [&](bool) {
-        drape_shade_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, t->sh.enabled ? t->sh.d_lit.p : nullptr, t->am.enabled ? t->am.d_sky.p : nullptr);
-        return hipGetLastError();
-    });
+    const hipError_t err = G.time_shade(repeats, mean, kDrape);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("drape diagnostics: ") + hipGetErrorString(err));
     *ms = mean;
     return VF_OK;

@@ -702,8 +702,12 @@ constexpr int kLutStride = 4, kLutFloats = 257 * kLutStride;
 struct ShadeTables { const float *lut; const float *thresh; };
 
 // fs_main (terrain.wgsl:69-91) + Rgba8UnormSrgb store, with the Lambert term scaled by `lit` (cast shadows) and the
-// shade by `amb` (ambient occlusion); fragment_shader below is the frame's own: both 1, and x * 1 is x
-__device__ __forceinline__ uint32_t fragment_shader_lit(const FrameParams &P, const ShadeTables &S, const float attr[3], float lit, float amb)
+// shade by `amb` (ambient occlusion); fragment_shader below is the frame's own: both 1, and x * 1 is x.
+// ALBEDO (the draped image): the colormap value lc of every channel gives way to fmaf(opacity, val, keep * lc),
+// val the image's premultiplied sample and keep = 1 - val_a * opacity.
+template <bool ALBEDO>
+__device__ __forceinline__ uint32_t fragment_shader_albedo(const FrameParams &P, const ShadeTables &S, const float attr[3], float lit, float amb,
+                                                           const float *val, float opacity, float keep)
 {
     const float height = attr[0], x = attr[1], z = attr[2];
     float t = 0.5f + height / (2.0f * P.h_range);
@@ -745,11 +749,16 @@ __device__ __forceinline__ uint32_t fragment_shader_lit(const FrameParams &P, co
     for (int ch = 0; ch < 3; ++ch) {
         float l0 = S.lut[i0 * kLutStride + ch], l1 = S.lut[i1 * kLutStride + ch];
         float lc = fmaf(f, l1 - l0, l0);
+        if constexpr (ALBEDO) lc = fmaf(opacity, val[ch], keep * lc);
         float v = lc * P.exposure * shade;
         if (P.shade_mode != 0u) v = v / (1.0f + v);          // Reinhard (tests/test_tonemap.py:7-8), before the sRGB store
         out |= srgb_encode(v, S.thresh) << (8 * ch);
     }
     return out;
+}
+__device__ __forceinline__ uint32_t fragment_shader_lit(const FrameParams &P, const ShadeTables &S, const float attr[3], float lit, float amb)
+{
+    return fragment_shader_albedo<false>(P, S, attr, lit, amb, nullptr, 0.0f, 0.0f);
 }
 __device__ __forceinline__ uint32_t fragment_shader(const FrameParams &P, const ShadeTables &S, const float attr[3])
 {

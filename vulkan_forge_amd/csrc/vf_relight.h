@@ -1,0 +1,125 @@
+// vf_relight.h -- the relight pass: one walk over a frame's stored visibility that writes pixels again through the
+// exact fragment function, for the three features that rewrite a frame behind the tile kernel.
+//
+//   kShadow    cast shadows (4g): the pixels whose interpolated lit is below 1, with lambert * lit
+//   kAmbient   ambient occlusion, and cast shadows when they are on as well (4i): the pixels whose lit or amb is below 1, with
+//              lambert * lit and shade * amb; amb = 1 - strength (1 - sky) per vertex
+//   kDrape     the draped image (4j): the pixels where the image's sample at (x, z) is not transparent, with the colormap value
+//              mixed with the sample; lit and amb are formed by the same rules, so the result does not depend on what the pass
+//              before wrote
+//
+// The surface point, its varyings and the interpolation of a per-vertex scalar are vf_visible.h's.  The arithmetic is the
+// contract's, bit for bit (tests/shadow_model, ambient_model and drape_model are its CPU statements).  All kernels are templates
+// (DESIGN.md 4d).
+#pragma once
+#include "vf_drape.h"
+
+namespace vf {
+
+enum Relight : int { kShadow = 0, kAmbient = 1, kDrape = 2 };
+
+// What a pass reads beside the frame.  lit / sky: the shadow and sky-view fields; kShadow reads lit alone, kAmbient takes sky for
+// granted, and a field that is NULL otherwise belongs to a feature that is off (its value is 1).  The rest is the drape's.
+struct RelightParams {
+    const float *lit, *sky;
+    float amb_strength;
+    const float *decode;        // 256 sRGB8 -> linear
+    const uint32_t *img;
+    DrapeParams D;
+};
+
+// lit and amb of a pixel.  At the three vertices first: a primitive whose three values are all 1 is `plain` and gives 1 without
+// interpolation (x * (1 / x) need not round to 1).
+struct LightTerms {
+    float l[3], a[3];
+    bool plain_l, plain_a;
+};
+
+template <Relight PASS>
+__device__ __forceinline__ LightTerms vertex_light(const FrameParams &P, const VisibleSite &s, const RelightParams &R)
+{
+    const float *lit = R.lit, *sky = R.sky;
+    const bool have_lit = PASS == kShadow || lit != nullptr, have_sky = PASS == kAmbient || (PASS == kDrape && sky != nullptr);
+    LightTerms L;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) L.l[k] = have_lit ? lit[site_vertex(P, s, k)] : 1.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) L.a[k] = have_sky ? 1.0f - R.amb_strength * (1.0f - sky[site_vertex(P, s, k)]) : 1.0f;
+    L.plain_l = L.l[0] == 1.0f && L.l[1] == 1.0f && L.l[2] == 1.0f;
+    L.plain_a = L.a[0] == 1.0f && L.a[1] == 1.0f && L.a[2] == 1.0f;
+    return L;
+}
+
+// ... then at the point (vf_visible.h).  kShadow hands lit on as it is (the pass leaves unless it is below 1); the others shade
+// an interpolated value an ulp above 1 as 1.
+template <bool CLIPPED, Relight PASS>
+__device__ __forceinline__ void point_light(const FrameParams &P, const VisiblePoint<CLIPPED> &p, int32_t px, int32_t py, const LightTerms &L,
+                                            float &lit, float &amb)
+{
+    lit = L.plain_l ? 1.0f : point_scalar(P, p, px, py, L.l[0], L.l[1], L.l[2]);
+    amb = L.plain_a ? 1.0f : point_scalar(P, p, px, py, L.a[0], L.a[1], L.a[2]);
+    if constexpr (PASS != kShadow) { lit = fminf(lit, 1.0f); amb = fminf(amb, 1.0f); }
+}
+
+// Pixel (px, py) with visibility id `id`: false when the pass leaves it as the frame drew it, else its colour again.  Each pass
+// leaves before it computes what it does not need: kShadow and kAmbient on the vertex values alone, then on the interpolated ones,
+// and form the varyings last; kDrape needs (x, z) for its sample and touches the fields only where the image shows.
+template <bool CLIPPED, Relight PASS>
+__device__ __forceinline__ bool relight_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *dec, const RelightParams &R,
+                                              uint32_t id, int32_t px, int32_t py, uint32_t &rgba)
+{
+    const uint32_t prim = id - 1u;
+    const VisibleSite s = visible_site<CLIPPED>(P, V, prim);
+    LightTerms L;
+    if constexpr (PASS != kDrape) {
+        L = vertex_light<PASS>(P, s, R);
+        if (L.plain_l && L.plain_a) return false;
+    }
+    const VisiblePoint<CLIPPED> p = visible_point<CLIPPED>(P, V, s, prim, px, py);
+    float attr[3], lit, amb;
+    if constexpr (PASS == kDrape) {
+        point_varyings(P, p, px, py, attr);
+        float val[4];
+        if (!dr_sample(R.D, R.img, dec, attr[1], attr[2], val)) return false;
+        const float Aop = val[3] * R.D.opacity;
+        if (!(Aop > 0.0f)) return false;
+        L = vertex_light<PASS>(P, s, R);
+        point_light<CLIPPED, PASS>(P, p, px, py, L, lit, amb);
+        rgba = fragment_shader_albedo<true>(P, T, attr, lit, amb, val, R.D.opacity, 1.0f - Aop);
+    } else {
+        point_light<CLIPPED, PASS>(P, p, px, py, L, lit, amb);
+        if (!(lit < 1.0f) && !(amb < 1.0f)) return false;
+        point_varyings(P, p, px, py, attr);
+        rgba = fragment_shader_lit(P, T, attr, lit, PASS == kShadow ? 1.0f : amb);
+    }
+    return true;
+}
+
+// The frame's visibility (H, W) -> the pixels of its colour buffer the pass writes again, in the walk of for_each_visible
+// (vf_visible.h).  `redo` is the frame's count of work items that met a clipped or oversized primitive: both instantiations are
+// launched behind a frame and the one the frame does not call for leaves at once (no host round trip between the frame and the pass).
+template <bool CLIPPED, Relight PASS>
+__global__ __launch_bounds__(256) void k_relight(FrameParams P, SetupView V, const float *__restrict__ lut_linear, const float *__restrict__ thresh,
+                                                 const uint32_t *__restrict__ vis, RelightParams R, const uint32_t *__restrict__ redo,
+                                                 uint32_t *__restrict__ rgba)
+{
+    if ((*redo != 0u) != CLIPPED) return;
+    __shared__ __attribute__((aligned(16))) float s_lut[kLutFloats];
+    __shared__ float s_thr[256];
+    for (int k = threadIdx.x; k < kLutFloats; k += 256) s_lut[k] = lut_linear[k];
+    s_thr[threadIdx.x] = thresh[threadIdx.x];
+    const float *dec = nullptr;
+    if constexpr (PASS == kDrape) {
+        __shared__ float s_dec[256];
+        s_dec[threadIdx.x] = R.decode[threadIdx.x];
+        dec = s_dec;
+    }
+    __syncthreads();
+    const ShadeTables T = { s_lut, s_thr };
+    for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
+        uint32_t c;
+        if (id != 0u && relight_pixel<CLIPPED, PASS>(P, V, T, dec, R, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
+    });
+}
+
+} // namespace vf

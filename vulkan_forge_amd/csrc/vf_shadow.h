@@ -4,9 +4,8 @@
 //                      sheared grid lines, as a decoupled scan -- k_shadow_chunk_max (the maximum of every 64-step chunk of every
 //                      line), k_shadow_carry (their exclusive running maximum along each line), k_shadow_lit (the scan inside a chunk
 //                      by DPP, seeded with the chunk's carry, and the horizon test)
-//   the shade pass     k_shadow_shade walks the frame's stored visibility (for_each_visible, vf_visible.h) and writes again, through
-//                      the exact fragment function, the pixels whose interpolated lit is below 1 (the lookup, the weights and the
-//                      clipped walk are that header's)
+//   the shade pass     k_relight<., kShadow> (vf_relight.h) writes again, through the exact fragment function, the
+//                      pixels whose interpolated lit is below 1
 //
 // Launched only for a handle that asked for shadows or for the field: the frame path is not touched.  The arithmetic is the
 // contract's, bit for bit (tests/shadow_model/shadow_model.c is its CPU statement): max is exact and associative, so the scan gives
@@ -160,93 +159,6 @@ __global__ __launch_bounds__(256) void k_shadow_fill(size_t count, float *__rest
 {
     const size_t k = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (k < count) lit[k] = 1.0f;
-}
-
-// ---- the shade pass ---------------------------------------------------------------------------------------------------------
-
-// Pixel (px, py) with visibility id `id`: its interpolated lit; when that is below 1, its colour again with lambert * lit.
-// A primitive whose three vertex values are all 1 is lit without interpolation (x * (1 / x) need not round to 1).
-// AMBIENT (k_ambient_shade of vf_ambient.h): amb = 1 - strength (1 - sky) per vertex is interpolated by the same rule
-// and the pixel is written again when lit or amb is below 1, with shade * amb; `lit` may be NULL then (no cast shadows: lit = 1).
-template <bool CLIPPED, bool AMBIENT>
-__device__ __forceinline__ bool sh_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *__restrict__ lit,
-                                         const float *__restrict__ sky, float amb_strength, uint32_t id, int32_t px, int32_t py, uint32_t &rgba)
-{
-    const uint32_t prim = id - 1u;
-    const VisibleSite s = visible_site<CLIPPED>(P, V, prim);
-    const uint32_t i = s.i, j = s.j, odd = s.odd;
-    // vertex 0 = (i + odd, j), vertex 1 = (i, j + 1), vertex 2 = (i + 1, j + odd)
-    const bool have_lit = !AMBIENT || lit != nullptr;
-    const float l0 = have_lit ? lit[(size_t)j * P.n + i + odd] : 1.0f, l1 = have_lit ? lit[(size_t)(j + 1u) * P.n + i] : 1.0f, l2 = have_lit ? lit[(size_t)(j + odd) * P.n + i + 1u] : 1.0f;
-    float a0 = 1.0f, a1 = 1.0f, a2 = 1.0f;
-    if constexpr (AMBIENT) {
-        a0 = 1.0f - amb_strength * (1.0f - sky[(size_t)j * P.n + i + odd]);
-        a1 = 1.0f - amb_strength * (1.0f - sky[(size_t)(j + 1u) * P.n + i]);
-        a2 = 1.0f - amb_strength * (1.0f - sky[(size_t)(j + odd) * P.n + i + 1u]);
-    }
-    const bool plain_l = l0 == 1.0f && l1 == 1.0f && l2 == 1.0f, plain_a = a0 == 1.0f && a1 == 1.0f && a2 == 1.0f;
-    if (plain_l && plain_a) return false;
-    float attr[3] = { 0.0f, 0.0f, 0.0f }, v = 1.0f, w = 1.0f;
-    if constexpr (CLIPPED) {
-        if (s.generic) {
-            GVert g[3];
-            load_prim(P, V.hblk, prim, g[0], g[1], g[2]);
-            (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, attr);
-            // lit rides through the clipper in the place of the height varying: the same crossings, the same piece
-            float la[3];
-            if (!AMBIENT || !plain_l) {
-                g[0].a[0] = l0; g[1].a[0] = l1; g[2].a[0] = l2;
-                (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, la);
-                v = la[0];
-            }
-            if constexpr (AMBIENT) {
-                if (!plain_a) {
-                    g[0].a[0] = a0; g[1].a[0] = a1; g[2].a[0] = a2;
-                    (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, la);
-                    w = la[0];
-                }
-            }
-        }
-    }
-    if (!s.generic) {
-        const VertexRec r0 = V.vtx[s.r0], r1 = V.vtx[s.r1], r2 = V.vtx[s.r2];
-        float q0, q1, q2;
-        record_weights(r0, r1, r2, px, py, q0, q1, q2);
-        const float rQ = 1.0f / ((q0 + q1) + q2);
-        if (!AMBIENT || !plain_l) v = fmaf(q2, l2, fmaf(q1, l1, q0 * l0)) * rQ;
-        if constexpr (AMBIENT) { if (!plain_a) w = fmaf(q2, a2, fmaf(q1, a1, q0 * a0)) * rQ; }
-        if (!(v < 1.0f) && !(AMBIENT && w < 1.0f)) return false;
-        const float x0 = grid_coord(P, i + odd), x1 = grid_coord(P, i), x2 = grid_coord(P, i + 1u);
-        const float z0 = grid_coord(P, j), z1 = grid_coord(P, j + 1u), z2 = grid_coord(P, j + odd);
-        attr[0] = fmaf(q2, r2.h, fmaf(q1, r1.h, q0 * r0.h)) * rQ;
-        attr[1] = fmaf(q2, x2, fmaf(q1, x1, q0 * x0)) * rQ;
-        attr[2] = fmaf(q2, z2, fmaf(q1, z1, q0 * z0)) * rQ;
-    }
-    if (!(v < 1.0f) && !(AMBIENT && w < 1.0f)) return false;
-    // (an interpolated value an ulp above 1 shades as 1; without AMBIENT v is below 1 here)
-    rgba = AMBIENT ? fragment_shader_lit(P, T, attr, fminf(v, 1.0f), fminf(w, 1.0f)) : fragment_shader_lit(P, T, attr, v, 1.0f);
-    return true;
-}
-
-// The frame's visibility (H, W) -> the shadowed pixels of its colour buffer, in the walk of for_each_visible (vf_visible.h).  `redo`
-// is the frame's count of work items that met a clipped or oversized primitive: both instantiations are launched behind a frame and
-// the one the frame does not call for leaves at once (no host round trip between the frame and its shadows).
-template <bool CLIPPED>
-__global__ __launch_bounds__(256) void k_shadow_shade(FrameParams P, SetupView V, const float *__restrict__ lut_linear, const float *__restrict__ thresh,
-                                                      const uint32_t *__restrict__ vis, const float *__restrict__ lit, const uint32_t *__restrict__ redo,
-                                                      uint32_t *__restrict__ rgba)
-{
-    if ((*redo != 0u) != CLIPPED) return;
-    __shared__ __attribute__((aligned(16))) float s_lut[kLutFloats];
-    __shared__ float s_thr[256];
-    for (int k = threadIdx.x; k < kLutFloats; k += 256) s_lut[k] = lut_linear[k];
-    s_thr[threadIdx.x] = thresh[threadIdx.x];
-    __syncthreads();
-    const ShadeTables T = { s_lut, s_thr };
-    for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
-        uint32_t c;
-        if (id != 0u && sh_pixel<CLIPPED, false>(P, V, T, lit, nullptr, 0.0f, id, (int32_t)px, (int32_t)py, c)) rgba[(size_t)py * P.W + px] = c;
-    });
 }
 
 } // namespace vf

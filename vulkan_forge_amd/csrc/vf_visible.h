@@ -1,7 +1,7 @@
 // vf_visible.h -- from a stored visibility id back to the surface at the pixel centre: which primitive, which three vertex records,
 // which perspective weights.  The one statement of that lookup for every pass that reads a frame's stored visibility (H, W) u32
-// behind the frame: overlay occlusion (terrain_rw), the geometry buffers (vf_gbuffer.h, 4f) and the shadow shade pass
-// (vf_shadow.h, 4g).  The fused fragment stage (shade_pixel / shade_from_records / clipped_attributes / k_resolve*, vf_kernels.h)
+// behind the frame: overlay occlusion (terrain_rw), the geometry buffers (vf_gbuffer.h, 4f) and the relight pass
+// (vf_relight.h, 4h).  The fused fragment stage (shade_pixel / shade_from_records / clipped_attributes / k_resolve*, vf_kernels.h)
 // keeps its own text of the same arithmetic, for the reason given above shade_from_records.
 //
 // The arithmetic is the contract's, bit for bit (the CPU models under tests/*_model restate it): always the exact path, whatever
@@ -82,6 +82,69 @@ __device__ __forceinline__ float clipped_weights(const GVert v[3], float hw, flo
         }
     }
     return Q;
+}
+
+// The three field indices of a site: where a per-vertex field (n x n, row-major) holds vertex k = 0, 1, 2 of its primitive
+__device__ __forceinline__ size_t site_vertex(const FrameParams &P, const VisibleSite &s, int k)
+{
+    const uint32_t dj = k == 1 ? 1u : k == 2 ? s.odd : 0u, di = k == 0 ? s.odd : k == 2 ? 1u : 0u;
+    return (size_t)(s.j + dj) * P.n + s.i + di;
+}
+
+// The surface point of a visible pixel: what is loaded once per pixel, for point_varyings and point_scalar below.
+// A pass that can leave on its site alone (site_vertex) does so before it asks for the point.
+template <bool CLIPPED>
+struct VisiblePoint {
+    VisibleSite s;
+    VertexRec r0, r1, r2;       // the record path: the three records, q_i = lambda_i rw_i and 1 / Q
+    float q0, q1, q2, rQ;
+    GVert g[CLIPPED ? 3 : 1];   // the generic path (CLIPPED only): the primitive as load_prim gives it
+};
+
+template <bool CLIPPED>
+__device__ __forceinline__ VisiblePoint<CLIPPED> visible_point(const FrameParams &P, const SetupView &V, const VisibleSite &s, uint32_t prim,
+                                                               int32_t px, int32_t py)
+{
+    VisiblePoint<CLIPPED> p;
+    p.s = s;
+    p.q0 = p.q1 = p.q2 = p.rQ = 0.0f;
+    if constexpr (CLIPPED) {
+        if (s.generic) { load_prim(P, V.hblk, prim, p.g[0], p.g[1], p.g[2]); return p; }
+    }
+    p.r0 = V.vtx[s.r0]; p.r1 = V.vtx[s.r1]; p.r2 = V.vtx[s.r2];
+    record_weights(p.r0, p.r1, p.r2, px, py, p.q0, p.q1, p.q2);
+    p.rQ = 1.0f / ((p.q0 + p.q1) + p.q2);
+    return p;
+}
+
+// One per-vertex scalar (f0, f1, f2 at vertex 0, 1, 2) interpolated at the point.  On the generic path it rides through the clipper
+// in the place of the height varying: the same crossings, the same piece.
+template <bool CLIPPED>
+__device__ __forceinline__ float point_scalar(const FrameParams &P, const VisiblePoint<CLIPPED> &p, int32_t px, int32_t py, float f0, float f1, float f2)
+{
+    if constexpr (CLIPPED) {
+        if (p.s.generic) {
+            GVert g[3] = { p.g[0], p.g[1], p.g[2] };
+            g[0].a[0] = f0; g[1].a[0] = f1; g[2].a[0] = f2;
+            float attr[3];
+            (void)clipped_weights(g, P.hw, P.hh, P.W, P.H, px, py, attr);
+            return attr[0];
+        }
+    }
+    return fmaf(p.q2, f2, fmaf(p.q1, f1, p.q0 * f0)) * p.rQ;
+}
+
+// The varyings (h, x, z) at the point: vertex 0 = (i + odd, j), vertex 1 = (i, j + 1), vertex 2 = (i + 1, j + odd)
+template <bool CLIPPED>
+__device__ __forceinline__ void point_varyings(const FrameParams &P, const VisiblePoint<CLIPPED> &p, int32_t px, int32_t py, float attr[3])
+{
+    if constexpr (CLIPPED) {
+        if (p.s.generic) { (void)clipped_weights(p.g, P.hw, P.hh, P.W, P.H, px, py, attr); return; }
+    }
+    const uint32_t i = p.s.i, j = p.s.j, odd = p.s.odd;
+    attr[0] = point_scalar(P, p, px, py, p.r0.h, p.r1.h, p.r2.h);
+    attr[1] = point_scalar(P, p, px, py, grid_coord(P, i + odd), grid_coord(P, i), grid_coord(P, i + 1u));
+    attr[2] = point_scalar(P, p, px, py, grid_coord(P, j), grid_coord(P, j + 1u), grid_coord(P, j + odd));
 }
 
 // Terrain depth at a pixel, for overlay occlusion: Q of the visible primitive `prim`, its interpolated 1/w at the pixel centre
