@@ -607,6 +607,32 @@ int vf_terrain_drape_info(const vf_terrain *t, uint32_t *iw, uint32_t *ih, float
  * ambient occlusion that are on), for the frame rendered last (drawn again into scratch buffers), after one warm-up. */
 int vf_terrain_debug_drape_stage(vf_terrain *t, uint32_t repeats, float *ms);   /* the shade pass alone, like the shadow one */
 
+/* ---- a mip pyramid under the draped image, and trilinear filtering ----------------------------------
+ * A sampling state of the handle, off by default; like the shadow settings it survives vf_terrain_set_drape and _clear_drape.
+ * With it on, a drape is sampled at the level of detail of each pixel's footprint on the image (measured on the surface, from the
+ * same primitive one pixel to the right and one below), so an image denser than the frame no longer aliases: `linear` blends the
+ * bilinear samples of two levels, `nearest` takes the nearest texel of the nearest level.  Where the image is magnified the sample
+ * is the unmipped one, bit for bit.  The footprint is isotropic (the larger of the two axes): at grazing angles it blurs.
+ * The pyramid: level 0 is the image; level k >= 1 is max(1, (w + 1) >> 1) x max(1, (h + 1) >> 1) of the level above it, premultiplied
+ * linear (r, g, b, a) as four binary16 values per texel, each the mean of the 4, 2 or 1 parents that exist.  It exists only while
+ * a drape is held and mipmaps are on, is built on the draw stream by the first frame (or read) after a new image or after enabling,
+ * and is not built again while the image rests.  Memory: a third of the image's texel count at 8 bytes each -- 716 MB beside the
+ * 1 GiB image at 16384 x 16384.  If that allocation fails the frame is refused with VF_ERR_NOMEM (mipmaps stay on; nothing is
+ * drawn unfiltered in its place).
+ * vf_terrain_set_drape_mips: bias is added to the level of detail, a finite number in [-16, 16]; anything else is refused with
+ *     VF_ERR_INVALID and changes nothing.  Disabling frees the pyramid.  Sharded handles and render_batch stay refused as for the drape.
+ * vf_terrain_drape_mip_info: *enabled; *levels (0 without a drape) and *bytes of the pyramid as it is or will be built; *builds
+ *     counts the pyramid builds over the handle's life.  Any output may be NULL.
+ * vf_terrain_read_drape_level: level 1 <= level < levels as (h, w, 4) binary16 values, after bringing the pyramid up to date; `out`
+ *     NULL: the size alone.  Level 0 is the uploaded bytes and has no binary16 form. */
+#define VF_DRAPE_MIP_BIAS_MAX 16.0f
+#define VF_DRAPE_MIP_LEVELS_MAX 15
+int vf_terrain_set_drape_mips(vf_terrain *t, int enabled, float bias);
+int vf_terrain_drape_mip_info(const vf_terrain *t, int *enabled, uint32_t *levels, float *bias, uint64_t *bytes, uint32_t *builds);
+int vf_terrain_read_drape_level(vf_terrain *t, uint32_t level, uint16_t *out /* h * w * 4, or NULL */, uint32_t *w, uint32_t *h);
+/* Diagnostics: mean time in ms of `repeats` back-to-back builds of the whole pyramid, after one warm-up. */
+int vf_terrain_debug_drape_mip_build(vf_terrain *t, uint32_t repeats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

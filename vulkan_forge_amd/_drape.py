@@ -75,3 +75,47 @@ def drape_info(iw, ih, extent, opacity, code):
         return None
     return {"width": int(iw), "height": int(ih), "extent": tuple(float(v) for v in extent), "opacity": float(opacity),
             "filter": "linear" if code == LINEAR else "nearest"}
+
+
+# ---- the mip pyramid (set_drape_mipmaps / drape_mip_info / read_drape_level) ----
+
+MIP_BIAS_MAX = 16.0                                       # VF_DRAPE_MIP_BIAS_MAX
+MIP_LEVELS_MAX = 15                                       # VF_DRAPE_MIP_LEVELS_MAX
+MIP_DEFAULTS = {"enabled": True, "bias": 0.0}
+
+
+def mip_params(enabled=True, bias=0.0):
+    """-> (enabled as 0 | 1, bias) as vf_terrain_set_drape_mips takes them"""
+    if isinstance(enabled, (str, bytes)) or not isinstance(enabled, (bool, int, np.bool_, np.integer)):
+        raise TypeError(f"enabled must be a bool, got {type(enabled).__name__}")
+    bias = _number("bias", bias)
+    if not -MIP_BIAS_MAX <= bias <= MIP_BIAS_MAX:
+        raise ValueError(f"bias must lie in [-16, 16], got {bias}")
+    return int(bool(enabled)), bias
+
+
+def mip_sizes(iw, ih):
+    """[(w, h)] of levels 0, 1, ...: each max(1, (size + 1) >> 1) of the level above, down to 1 x 1"""
+    sizes = [(int(iw), int(ih))]
+    while sizes[-1] != (1, 1):
+        w, h = sizes[-1]
+        sizes.append((max(1, (w + 1) >> 1), max(1, (h + 1) >> 1)))
+    return sizes
+
+
+def mip_level(level, levels):
+    """the level rule of read_drape_level: 1 <= level < levels (level 0 is the uploaded bytes)"""
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)):
+        raise TypeError(f"level must be an int, got {type(level).__name__}")
+    if not 1 <= level < levels:
+        raise ValueError(f"level must lie in [1, {levels}), got {level}" if levels > 1 else f"the pyramid has no level to read (levels = {levels})")
+    return int(level)
+
+
+def mip_info(enabled, levels, bias, nbytes, builds, iw, ih):
+    """what drape_mip_info() returns: None while mipmaps are off; levels 0 and no sizes while they are on without a drape"""
+    if not enabled:
+        return None
+    sizes = mip_sizes(iw, ih) if levels else []
+    assert len(sizes) == levels
+    return {"levels": int(levels), "sizes": sizes, "bias": float(bias), "bytes": int(nbytes), "builds": int(builds)}

@@ -14,6 +14,7 @@ DEFAULT_LIB = os.environ.get("VF_HIP_LIB") or os.path.join(_HERE, "libvf_hip.so"
 
 VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -3, -4
 VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
+VF_DRAPE_MIP_BIAS_MAX, VF_DRAPE_MIP_LEVELS_MAX = 16.0, 15                                # its mip pyramid
 VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED_AHEAD = 1, 2, 4, 8, 16   # vf_terrain_debug_plan_mode
 
 # every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py)
@@ -34,6 +35,7 @@ SYMBOLS = [
     "vf_terrain_set_ambient", "vf_terrain_read_sky_view_field", "vf_terrain_sky_view_field_device", "vf_terrain_debug_ambient_stage",
     "vf_terrain_debug_ambient_scans",
     "vf_terrain_set_drape", "vf_terrain_set_drape_device", "vf_terrain_clear_drape", "vf_terrain_drape_info", "vf_terrain_debug_drape_stage",
+    "vf_terrain_set_drape_mips", "vf_terrain_drape_mip_info", "vf_terrain_read_drape_level", "vf_terrain_debug_drape_mip_build",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -141,6 +143,10 @@ _PROTOS = {
     "vf_terrain_clear_drape": (_i, [_vp]),
     "vf_terrain_drape_info": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "vf_terrain_debug_drape_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_drape_mips": (_i, [_vp, _i, _f]),
+    "vf_terrain_drape_mip_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32), C.POINTER(_f), C.POINTER(C.c_uint64), C.POINTER(_u32)]),
+    "vf_terrain_read_drape_level": (_i, [_vp, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "vf_terrain_debug_drape_mip_build": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -590,6 +596,39 @@ class Terrain:
         """Shade-pass ms of the drape for the frame rendered last, as timed launches of their own (diagnostics)."""
         ms = _f()
         self._check(self.lib.vf_terrain_debug_drape_stage(self.t, int(repeats), C.byref(ms)))
+        return ms.value
+
+    def set_drape_mipmaps(self, enabled=True, *, bias=0.0):
+        """Sample the draped image through a mip pyramid at the level of detail of each pixel's footprint.  bias is
+        added to the level, a finite number in [-16, 16].  A setting of the handle, off by default, that survives set_drape and
+        clear_drape; the pyramid exists while a drape is held and mipmaps are on."""
+        from ._drape import mip_params
+        on, bias = mip_params(enabled, bias)
+        self._check(self.lib.vf_terrain_set_drape_mips(self.t, on, bias))
+
+    def drape_mip_info(self):
+        """None while mipmaps are off, else dict(levels, sizes=[(w, h), ...], bias, bytes, builds); levels 0 without a drape."""
+        from ._drape import mip_info
+        on, levels, bias, nbytes, builds, iw, ih = _i(), _u32(), _f(), C.c_uint64(), _u32(), _u32(), _u32()
+        self._check(self.lib.vf_terrain_drape_mip_info(self.t, C.byref(on), C.byref(levels), C.byref(bias), C.byref(nbytes), C.byref(builds)))
+        self._check(self.lib.vf_terrain_drape_info(self.t, C.byref(iw), C.byref(ih), None, None, None))
+        return mip_info(on.value != 0, levels.value, bias.value, nbytes.value, builds.value, iw.value, ih.value)
+
+    def read_drape_level(self, level):
+        """Level 1 <= level < levels of the pyramid as (h, w, 4) float16: premultiplied linear (r, g, b, a).  Builds it if stale."""
+        from ._drape import mip_level
+        levels, w, h = _u32(), _u32(), _u32()
+        self._check(self.lib.vf_terrain_drape_mip_info(self.t, None, C.byref(levels), None, None, None))
+        k = mip_level(level, levels.value)
+        self._check(self.lib.vf_terrain_read_drape_level(self.t, k, None, C.byref(w), C.byref(h)))
+        out = np.empty((h.value, w.value, 4), np.float16)
+        self._check(self.lib.vf_terrain_read_drape_level(self.t, k, out.ctypes.data, None, None))
+        return out
+
+    def drape_mip_build_stage(self, repeats=20):
+        """Build ms of the whole mip pyramid of the drape held, as timed launches of their own (diagnostics)."""
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_drape_mip_build(self.t, int(repeats), C.byref(ms)))
         return ms.value
 
     def enable_timing(self, on=True, stats=True, sampled=False):

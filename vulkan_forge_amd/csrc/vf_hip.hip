@@ -414,6 +414,15 @@ struct vf_terrain {
         DevBuf<float> d_decode;          // 256 sRGB8 -> linear (SrgbTables::decode)
         hipEvent_t copied = nullptr;     // behind set_drape_device's copy on the caller's stream: the frames' shade passes wait for it
     } dr;
+    // its mip pyramid: enabled and bias are the handle's and survive set_drape / clear_drape; the rest belongs to the
+    // image held and exists only while a drape is held and mipmaps are on
+    struct DrapeMipState {
+        bool enabled = false;
+        float bias = 0.0f;
+        DevBuf<uint2> d_pyr;             // levels 1 ... levels - 1, one after the other, each from an even texel index (16-byte aligned)
+        bool stale = true;               // d_pyr does not hold the pyramid of the image held
+        uint32_t builds = 0;             // times a pyramid was built (vf_terrain_drape_mip_info)
+    } dm;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -781,6 +790,7 @@ static void drape_release(vf_terrain *t)
     D.d_img.release(); D.d_decode.release();
     if (D.copied) (void)hipEventDestroy(D.copied);
     D = vf_terrain::Drape();
+    t->dm.d_pyr.release(); t->dm.stale = true;              // (the pyramid goes with its image; the setting stays)
 }
 
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
@@ -1486,6 +1496,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool shadows = t->sh.enabled && !diag;           // (visibility / diagnostics frames: the frame as the tile kernel shades it)
     const bool ambient = t->am.enabled && !diag;
     const bool drape = t->dr.iw != 0u && !diag;
+    const Relight drape_pass = t->dm.enabled ? kDrapeMip : kDrape;   // (through the mip pyramid when mipmaps are on)
     const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
@@ -1545,7 +1556,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         if (src != VF_OK) return src;
     }
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
-        const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, kDrape, shadows, ambient);
+        const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, drape_pass, shadows, ambient);
         if (drc != VF_OK) return drc;
     }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
@@ -2550,6 +2561,64 @@ static int relight_fields(vf_terrain *t, const float *u, hipStream_t s, bool sha
     return VF_OK;
 }
 
+// Where the levels of a drape's mip pyramid lie: level k is w[k] x h[k] texels, halved rounding up; levels 1 ... in
+// one buffer at texel offsets off[k], each even (16-byte aligned rows for the build kernel's vector accesses); texels: its length
+struct MipLayout {
+    uint32_t levels;
+    uint32_t w[kMipLevelsMax], h[kMipLevelsMax];
+    size_t off[kMipLevelsMax], texels;
+};
+
+static MipLayout mip_layout(uint32_t iw, uint32_t ih)
+{
+    MipLayout L = {};
+    L.w[0] = iw; L.h[0] = ih; L.levels = 1;
+    while ((L.w[L.levels - 1u] > 1u || L.h[L.levels - 1u] > 1u) && L.levels < (uint32_t)kMipLevelsMax) {
+        const uint32_t k = L.levels++;
+        L.w[k] = std::max(1u, (L.w[k - 1u] + 1u) >> 1); L.h[k] = std::max(1u, (L.h[k - 1u] + 1u) >> 1);
+        L.off[k] = L.texels;
+        L.texels += ((size_t)L.w[k] * L.h[k] + 1u) & ~(size_t)1u;
+    }
+    return L;
+}
+
+// The build alone: the launches that make the pyramid of layout L in d_pyr (which holds L.texels texels) from the image held, on
+// `s`.  Three levels per launch (vf_drape_mips.h): the first reads the image, the later ones binary16 texels.  Touches no state.
+static void mips_launch(const vf_terrain *t, hipStream_t s, const MipLayout &L)
+{
+    const vf_terrain::DrapeMipState &M = t->dm;
+    for (uint32_t k = 0; k + 1u < L.levels; k += 3u) {
+        const uint32_t nout = std::min(3u, L.levels - 1u - k);
+        uint2 *d[3];
+        for (uint32_t q = 0; q < 3u; ++q) d[q] = q < nout ? M.d_pyr.p + L.off[k + 1u + q] : nullptr;
+        const dim3 grid((L.w[k] + 63u) / 64u, (L.h[k] + 31u) / 32u), threads(256);
+        if (k == 0u) hipLaunchKernelGGL((k_drape_mips<true>), grid, threads, 0, s, (const void *)t->dr.d_img.p, (const float *)t->dr.d_decode.p, L.w[k], L.h[k], nout, d[0], d[1], d[2]);
+        else hipLaunchKernelGGL((k_drape_mips<false>), grid, threads, 0, s, (const void *)(M.d_pyr.p + L.off[k]), (const float *)nullptr, L.w[k], L.h[k], nout, d[0], d[1], d[2]);
+    }
+}
+
+// The pyramid of the image held is complete in d_pyr once the work queued on `s` is done (which is ordered behind the image's
+// upload): built when stale -- after a new image or after enabling -- and at no cost otherwise.  The buffer is allocated when first
+// needed and kept from image to image while the layout's texel count stays (an image update of the same size frees and allocates
+// nothing); the caller of whatever made it stale has waited for the frames that read the old one.
+static int mips_current(vf_terrain *t, hipStream_t s)
+{
+    vf_terrain::DrapeMipState &M = t->dm;
+    if (!M.enabled || !t->dr.iw) return VF_OK;
+    const MipLayout L = mip_layout(t->dr.iw, t->dr.ih);
+    if (L.levels < 2u) { M.d_pyr.release(); M.stale = false; return VF_OK; }   // (a 1 x 1 image is its own pyramid)
+    if (M.d_pyr.cap != L.texels) {
+        M.d_pyr.release();
+        M.stale = true;
+        if (M.d_pyr.reserve(L.texels, L.texels) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "drape mip pyramid allocation failed"); }
+    }
+    if (!M.stale) return VF_OK;
+    mips_launch(t, s, L);
+    VF_HIP_TRY(hipGetLastError());
+    M.stale = false; M.builds++;
+    return VF_OK;
+}
+
 // Both instantiations of a pass of the relight kernel (vf_relight.h), in k_resolve's launch shape (gb_grid).  shadows / ambient:
 // the pass reads that field (kShadow reads the shadow field, kAmbient the sky-view field, whatever they say).
 static void relight_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
@@ -2571,7 +2640,18 @@ static void relight_launch(const vf_terrain *t, hipStream_t s, const FrameParams
         D.x0 = H.extent[0]; D.z0 = H.extent[1];
         D.sx = (float)H.iw / (H.extent[2] - H.extent[0]); D.sz = (float)H.ih / (H.extent[3] - H.extent[1]);
         D.iw = H.iw; D.ih = H.ih; D.opacity = H.opacity; D.linear = H.filter == VF_DRAPE_LINEAR ? 1u : 0u;
-        VF_RELIGHT(false, kDrape); VF_RELIGHT(true, kDrape);
+        if (pass == kDrape) { VF_RELIGHT(false, kDrape); VF_RELIGHT(true, kDrape); }
+        else {                                                 // kDrapeMip: the pyramid beside it (current: mips_current)
+            RelightMipParams RM = {};
+            static_cast<RelightParams &>(RM) = R;
+            const MipLayout L = mip_layout(H.iw, H.ih);
+            RM.M.levels = L.levels; RM.M.bias = t->dm.bias;
+            for (uint32_t k = 0; k < L.levels; ++k) { RM.M.w[k] = (uint16_t)L.w[k]; RM.M.h[k] = (uint16_t)L.h[k]; RM.M.lvl[k] = k ? t->dm.d_pyr.p + L.off[k] : nullptr; }
+            hipLaunchKernelGGL((k_relight<false, kDrapeMip>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
+                               (const uint32_t *)t->d_vis, RM, redo, rgba);
+            hipLaunchKernelGGL((k_relight<true, kDrapeMip>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
+                               (const uint32_t *)t->d_vis, RM, redo, rgba);
+        }
     }
 #undef VF_RELIGHT
 }
@@ -2583,7 +2663,8 @@ static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
                         bool shadows, bool ambient)
 {
     if (int rc = relight_fields(t, t->inputs.u, s, shadows, ambient)) return rc;
-    if (pass == kDrape && t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    if (relight_drapes(pass) && t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    if (pass == kDrapeMip) { if (int rc = mips_current(t, s)) return rc; }
     relight_launch(t, s, P, V, redo, rgba, pass, shadows, ambient);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
@@ -2848,6 +2929,7 @@ static void drape_commit(vf_terrain *t, uint32_t iw, uint32_t ih, const float ex
     vf_terrain::Drape &H = t->dr;
     H.iw = iw; H.ih = ih; H.opacity = opacity; H.filter = filter;
     std::memcpy(H.extent, ext, sizeof H.extent);
+    t->dm.stale = true;                                      // (a new image: its pyramid is built by the first frame that wants it, into the buffer held if the size is the old one)
     t->inputs_gen++;
 }
 
@@ -2933,9 +3015,80 @@ int vf_terrain_debug_drape_stage(vf_terrain *t, uint32_t repeats, float *ms)
     if (int rc = G.open(t)) return rc;
     if (int rc = relight_fields(t, G.u, G.s, t->sh.enabled, t->am.enabled)) return rc;   // (the shade pass below reads them)
     if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(G.s, t->dr.copied, 0));
+    if (int rc = mips_current(t, G.s)) return rc;            // (whichever drape pass the handle would run)
     float mean = 0.0f;
-    const hipError_t err = G.time_shade(repeats, mean, kDrape);
+    const hipError_t err = G.time_shade(repeats, mean, t->dm.enabled ? kDrapeMip : kDrape);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("drape diagnostics: ") + hipGetErrorString(err));
+    *ms = mean;
+    return VF_OK;
+}
+
+// ---- its mip pyramid (vf_drape_mips.h) ---------------------------------------------------
+
+int vf_terrain_set_drape_mips(vf_terrain *t, int enabled, float bias)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!(std::isfinite(bias) && bias >= -VF_DRAPE_MIP_BIAS_MAX && bias <= VF_DRAPE_MIP_BIAS_MAX)) return fail(VF_ERR_INVALID, "bias must be a finite number in [-16, 16]");
+    vf_terrain::DrapeMipState &M = t->dm;
+    if (M.enabled == (enabled != 0) && M.bias == bias) return VF_OK;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));                                // (the frame in flight reads the pyramid this call may free)
+    if (!enabled) { M.d_pyr.release(); M.stale = true; }
+    M.enabled = enabled != 0; M.bias = bias;
+    t->inputs_gen++;
+    return VF_OK;
+}
+
+int vf_terrain_drape_mip_info(const vf_terrain *t, int *enabled, uint32_t *levels, float *bias, uint64_t *bytes, uint32_t *builds)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::DrapeMipState &M = t->dm;
+    const bool held = M.enabled && t->dr.iw != 0u;
+    const MipLayout L = held ? mip_layout(t->dr.iw, t->dr.ih) : MipLayout();
+    if (enabled) *enabled = M.enabled ? 1 : 0;
+    if (levels) *levels = held ? L.levels : 0u;
+    if (bias) *bias = M.bias;
+    if (bytes) *bytes = (uint64_t)L.texels * sizeof(uint2);
+    if (builds) *builds = M.builds;
+    return VF_OK;
+}
+
+int vf_terrain_read_drape_level(vf_terrain *t, uint32_t level, uint16_t *out, uint32_t *w, uint32_t *h)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->dm.enabled || !t->dr.iw) return fail(VF_ERR_INVALID, "no mip pyramid: it needs a draped image and mipmaps enabled");
+    const MipLayout L = mip_layout(t->dr.iw, t->dr.ih);
+    if (level < 1u || level >= L.levels) return fail(VF_ERR_INVALID, "level must lie in [1, levels)");
+    if (w) *w = L.w[level];
+    if (h) *h = L.h[level];
+    if (!out) return VF_OK;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    // The frame in flight may have been drawn on a stream of the caller's, and the build with it: the copy below, on the context's
+    // stream, is ordered against neither by itself.  So the frame is waited for first, always: the copy then reads a complete
+    // pyramid, and a build queued here does not overtake a frame that still reads the image.
+    VF_HIP_TRY(wait_frame(t));
+    hipStream_t s = t->ctx->stream;
+    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    if (int rc = mips_current(t, s)) return rc;
+    VF_HIP_TRY(hipMemcpyAsync(out, t->dm.d_pyr.p + L.off[level], (size_t)L.w[level] * L.h[level] * sizeof(uint2), hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));
+    return VF_OK;
+}
+
+int vf_terrain_debug_drape_mip_build(vf_terrain *t, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->dm.enabled || !t->dr.iw) return fail(VF_ERR_INVALID, "no mip pyramid: it needs a draped image and mipmaps enabled");
+    if (repeats == 0) repeats = 1;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    hipStream_t s = t->ctx->stream;
+    if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
+    if (int rc = mips_current(t, s)) return rc;              // (the handle's own build, if it was due; the timed ones below touch no state)
+    const MipLayout L = mip_layout(t->dr.iw, t->dr.ih);
+    float mean = 0.0f;
+    const hipError_t err = L.levels < 2u ? hipSuccess : time_launches(s, repeats, mean, [&](bool) { mips_launch(t, s, L); return hipGetLastError(); });
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("drape mip diagnostics: ") + hipGetErrorString(err));
     *ms = mean;
     return VF_OK;
 }

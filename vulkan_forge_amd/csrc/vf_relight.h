@@ -1,5 +1,5 @@
 // vf_relight.h -- the relight pass: one walk over a frame's stored visibility that writes pixels again through the
-// exact fragment function, for the three features that rewrite a frame behind the tile kernel.
+// exact fragment function, for the features that rewrite a frame behind the tile kernel.
 //
 //   kShadow    cast shadows (4g): the pixels whose interpolated lit is below 1, with lambert * lit
 //   kAmbient   ambient occlusion, and cast shadows when they are on as well (4i): the pixels whose lit or amb is below 1, with
@@ -7,16 +7,20 @@
 //   kDrape     the draped image (4j): the pixels where the image's sample at (x, z) is not transparent, with the colormap value
 //              mixed with the sample; lit and amb are formed by the same rules, so the result does not depend on what the pass
 //              before wrote
+//   kDrapeMip  the draped image through its mip pyramid (4k): kDrape with the level of detail of the pixel's footprint on the image,
+//              from the varyings of the same primitive one pixel to the right and one below
 //
 // The surface point, its varyings and the interpolation of a per-vertex scalar are vf_visible.h's.  The arithmetic is the
-// contract's, bit for bit (tests/shadow_model, ambient_model and drape_model are its CPU statements).  All kernels are templates
+// contract's, bit for bit (tests/shadow_model, ambient_model, drape_model and drape_mip_model are its CPU statements).  All kernels are templates
 // (DESIGN.md 4d).
 #pragma once
-#include "vf_drape.h"
+#include <type_traits>
+#include "vf_drape_mips.h"
 
 namespace vf {
 
-enum Relight : int { kShadow = 0, kAmbient = 1, kDrape = 2 };
+enum Relight : int { kShadow = 0, kAmbient = 1, kDrape = 2, kDrapeMip = 3 };
+constexpr bool relight_drapes(Relight pass) { return pass == kDrape || pass == kDrapeMip; }
 
 // What a pass reads beside the frame.  lit / sky: the shadow and sky-view fields; kShadow reads lit alone, kAmbient takes sky for
 // granted, and a field that is NULL otherwise belongs to a feature that is off (its value is 1).  The rest is the drape's.
@@ -27,6 +31,9 @@ struct RelightParams {
     const uint32_t *img;
     DrapeParams D;
 };
+// ... and kDrapeMip the pyramid beside it: the other passes keep their kernel arguments as they are
+struct RelightMipParams : RelightParams { DrapeMips M; };
+template <Relight PASS> using RelightArg = std::conditional_t<PASS == kDrapeMip, RelightMipParams, RelightParams>;
 
 // lit and amb of a pixel.  At the three vertices first: a primitive whose three values are all 1 is `plain` and gives 1 without
 // interpolation (x * (1 / x) need not round to 1).
@@ -39,7 +46,7 @@ template <Relight PASS>
 __device__ __forceinline__ LightTerms vertex_light(const FrameParams &P, const VisibleSite &s, const RelightParams &R)
 {
     const float *lit = R.lit, *sky = R.sky;
-    const bool have_lit = PASS == kShadow || lit != nullptr, have_sky = PASS == kAmbient || (PASS == kDrape && sky != nullptr);
+    const bool have_lit = PASS == kShadow || lit != nullptr, have_sky = PASS == kAmbient || (relight_drapes(PASS) && sky != nullptr);
     LightTerms L;
 #pragma unroll
     for (int k = 0; k < 3; ++k) L.l[k] = have_lit ? lit[site_vertex(P, s, k)] : 1.0f;
@@ -63,24 +70,34 @@ __device__ __forceinline__ void point_light(const FrameParams &P, const VisibleP
 
 // Pixel (px, py) with visibility id `id`: false when the pass leaves it as the frame drew it, else its colour again.  Each pass
 // leaves before it computes what it does not need: kShadow and kAmbient on the vertex values alone, then on the interpolated ones,
-// and form the varyings last; kDrape needs (x, z) for its sample and touches the fields only where the image shows.
+// and form the varyings last; kDrape needs (x, z) for its sample and touches the fields only where the image shows; kDrapeMip
+// evaluates the neighbouring centres only for a pixel inside the image's extent.
 template <bool CLIPPED, Relight PASS>
-__device__ __forceinline__ bool relight_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *dec, const RelightParams &R,
+__device__ __forceinline__ bool relight_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *dec, const RelightArg<PASS> &R,
                                               uint32_t id, int32_t px, int32_t py, uint32_t &rgba)
 {
     const uint32_t prim = id - 1u;
     const VisibleSite s = visible_site<CLIPPED>(P, V, prim);
     LightTerms L;
-    if constexpr (PASS != kDrape) {
+    if constexpr (!relight_drapes(PASS)) {
         L = vertex_light<PASS>(P, s, R);
         if (L.plain_l && L.plain_a) return false;
     }
     const VisiblePoint<CLIPPED> p = visible_point<CLIPPED>(P, V, s, prim, px, py);
     float attr[3], lit, amb;
-    if constexpr (PASS == kDrape) {
+    if constexpr (relight_drapes(PASS)) {
         point_varyings(P, p, px, py, attr);
         float val[4];
-        if (!dr_sample(R.D, R.img, dec, attr[1], attr[2], val)) return false;
+        if constexpr (PASS == kDrapeMip) {
+            const float fu = (attr[1] - R.D.x0) * R.D.sx, fv = (attr[2] - R.D.z0) * R.D.sz;
+            if (!(fu >= 0.0f && fu <= (float)R.D.iw && fv >= 0.0f && fv <= (float)R.D.ih)) return false;
+            float right[3], down[3];
+            point_neighbours(P, p, px, py, right, down);
+            const float lod = mip_lod(R.D, R.M.bias, attr[1], attr[2], right[1], right[2], down[1], down[2]);
+            if (!mip_sample(R.D, R.M, R.img, dec, attr[1], attr[2], lod, val)) return false;
+        } else {
+            if (!dr_sample(R.D, R.img, dec, attr[1], attr[2], val)) return false;
+        }
         const float Aop = val[3] * R.D.opacity;
         if (!(Aop > 0.0f)) return false;
         L = vertex_light<PASS>(P, s, R);
@@ -100,7 +117,7 @@ __device__ __forceinline__ bool relight_pixel(const FrameParams &P, const SetupV
 // launched behind a frame and the one the frame does not call for leaves at once (no host round trip between the frame and the pass).
 template <bool CLIPPED, Relight PASS>
 __global__ __launch_bounds__(256) void k_relight(FrameParams P, SetupView V, const float *__restrict__ lut_linear, const float *__restrict__ thresh,
-                                                 const uint32_t *__restrict__ vis, RelightParams R, const uint32_t *__restrict__ redo,
+                                                 const uint32_t *__restrict__ vis, RelightArg<PASS> R, const uint32_t *__restrict__ redo,
                                                  uint32_t *__restrict__ rgba)
 {
     if ((*redo != 0u) != CLIPPED) return;
@@ -109,7 +126,7 @@ __global__ __launch_bounds__(256) void k_relight(FrameParams P, SetupView V, con
     for (int k = threadIdx.x; k < kLutFloats; k += 256) s_lut[k] = lut_linear[k];
     s_thr[threadIdx.x] = thresh[threadIdx.x];
     const float *dec = nullptr;
-    if constexpr (PASS == kDrape) {
+    if constexpr (relight_drapes(PASS)) {
         __shared__ float s_dec[256];
         s_dec[threadIdx.x] = R.decode[threadIdx.x];
         dec = s_dec;

@@ -147,6 +147,43 @@ __device__ __forceinline__ void point_varyings(const FrameParams &P, const Visib
     attr[2] = point_scalar(P, p, px, py, grid_coord(P, j), grid_coord(P, j + 1u), grid_coord(P, j + odd));
 }
 
+// The generic path of point_neighbours below: the piece of the clipped fan that covers (px, py) -- the last one, as in
+// clipped_weights -- evaluated at the centres of (px + 1, py) and (px, py + 1) as well: its edge values there through the same int64
+// edge function, with no cover test (the piece's plane goes on outside the piece and outside the frame).  Zero varyings when no piece
+// covers (px, py).
+__device__ __forceinline__ void clipped_neighbours(const GVert v[3], float hw, float hh, uint32_t W, uint32_t H, int32_t px, int32_t py,
+                                                   float right[3], float down[3])
+{
+    GVert poly[8];
+    const int np = clip_primitive(v, poly);
+    right[0] = right[1] = right[2] = down[0] = down[1] = down[2] = 0.0f;
+    for (int f = 1; f + 1 < np; ++f) {
+        TriSetup T;
+        int64_t e[3];
+        if (setup_triangle(poly[0], poly[f], poly[f + 1], hw, hh, W, H, T) && covers(T, px, py, e)) {
+            (void)covers(T, px + 1, py, e); interpolate(T, e, right);
+            (void)covers(T, px, py + 1, e); interpolate(T, e, down);
+        }
+    }
+}
+
+// The varyings (h, x, z) of the point's primitive at the centres of the pixel to the right and the pixel below: the
+// same records and edge functions one pixel on, wherever that centre lies.  What a footprint on the surface is measured from.
+template <bool CLIPPED>
+__device__ __forceinline__ void point_neighbours(const FrameParams &P, const VisiblePoint<CLIPPED> &p, int32_t px, int32_t py, float right[3], float down[3])
+{
+    if constexpr (CLIPPED) {
+        if (p.s.generic) { clipped_neighbours(p.g, P.hw, P.hh, P.W, P.H, px, py, right, down); return; }
+    }
+    VisiblePoint<CLIPPED> n = p;
+    record_weights(p.r0, p.r1, p.r2, px + 1, py, n.q0, n.q1, n.q2);
+    n.rQ = 1.0f / ((n.q0 + n.q1) + n.q2);
+    point_varyings(P, n, px + 1, py, right);
+    record_weights(p.r0, p.r1, p.r2, px, py + 1, n.q0, n.q1, n.q2);
+    n.rQ = 1.0f / ((n.q0 + n.q1) + n.q2);
+    point_varyings(P, n, px, py + 1, down);
+}
+
 // Terrain depth at a pixel, for overlay occlusion: Q of the visible primitive `prim`, its interpolated 1/w at the pixel centre
 __device__ inline float terrain_rw(const FrameParams &P, const SetupView &V, uint32_t prim, int32_t px, int32_t py)
 {

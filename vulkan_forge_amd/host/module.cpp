@@ -658,6 +658,42 @@ public:
         check(vf_terrain_drape_info(t, &iw, &ih, ext, &op, &code));
         return py::module_::import("vulkan_forge_amd._drape").attr("drape_info")(iw, ih, py::make_tuple(ext[0], ext[1], ext[2], ext[3]), op, code);
     }
+    // extension: a mip pyramid under the draped image (argument rules: vulkan_forge_amd/_drape.py)
+    void set_drape_mipmaps(py::object enabled, py::object bias)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._drape").attr("mip_params")(enabled, bias);
+        Borrow b(busy);
+        check(vf_terrain_set_drape_mips(t, a[0].cast<int>(), a[1].cast<float>()));
+        frame_current = false;
+    }
+    py::object drape_mip_info()
+    {
+        Borrow b(busy);
+        int enabled = 0;
+        uint32_t levels = 0, builds = 0, iw = 0, ih = 0;
+        float bias = 0.0f;
+        uint64_t bytes = 0;
+        check(vf_terrain_drape_mip_info(t, &enabled, &levels, &bias, &bytes, &builds));
+        check(vf_terrain_drape_info(t, &iw, &ih, nullptr, nullptr, nullptr));
+        return py::module_::import("vulkan_forge_amd._drape").attr("mip_info")(enabled != 0, levels, bias, bytes, builds, iw, ih);
+    }
+    py::array read_drape_level(py::object level)
+    {
+        Borrow b(busy);
+        uint32_t levels = 0, w = 0, h = 0;
+        check(vf_terrain_drape_mip_info(t, nullptr, &levels, nullptr, nullptr, nullptr));
+        const uint32_t k = py::module_::import("vulkan_forge_amd._drape").attr("mip_level")(level, levels).cast<uint32_t>();
+        check(vf_terrain_read_drape_level(t, k, nullptr, &w, &h));
+        py::array out(py::dtype("float16"), std::vector<py::ssize_t>{ (py::ssize_t)h, (py::ssize_t)w, 4 });
+        uint16_t *dst = static_cast<uint16_t *>(out.mutable_data());
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = vf_terrain_read_drape_level(t, k, dst, nullptr, nullptr);
+        }
+        check(rc);
+        return out;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1018,6 +1054,15 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "call; a second call replaces it.  The image is lit and shadowed as the surface is; overlays composite on top.")
         .def("clear_drape", &T::clear_drape, "Drop the draped image and free its copy: the handle draws as before.")
         .def("drape_info", &T::drape_info, "None, or dict(width, height, extent, opacity, filter) of the drape as set.")
+        .def("set_drape_mipmaps", &T::set_drape_mipmaps, py::arg("enabled") = true, py::kw_only(), py::arg("bias") = 0.0,
+             "Sample the draped image through a mip pyramid at the level of detail of each pixel's footprint (DESIGN.md 4k): an image\n"
+             "denser than the frame no longer aliases.  bias is added to the level, a finite number in [-16, 16].  A setting of the\n"
+             "handle, off by default, that survives set_drape and clear_drape; the pyramid (a third of the image's texels at 8 bytes)\n"
+             "exists while a drape is held and mipmaps are on.  Where the image is magnified the frame is the unmipped one.")
+        .def("drape_mip_info", &T::drape_mip_info,
+             "None while mipmaps are off, else dict(levels, sizes=[(w, h), ...], bias, bytes, builds); levels 0 without a drape.")
+        .def("read_drape_level", &T::read_drape_level, py::arg("level"),
+             "Level 1 <= level < levels of the pyramid as (h, w, 4) float16: premultiplied linear (r, g, b, a).  Builds it if stale.")
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
