@@ -348,6 +348,7 @@ int vf_terrain_debug_set_plan_feedback(vf_terrain *t, const uint32_t *tile_ticks
 #define VF_PLAN_MOTION_MAP   4u   /* tile times looked up through the camera motion */
 #define VF_PLAN_DILATE       8u   /* every tile takes the heaviest time of its neighbourhood */
 #define VF_PLAN_QUEUED_AHEAD 16u  /* the plan was queued ahead of the call, behind the frame before it */
+#define VF_PLAN_GEOMETRY_REUSED 32u /* block boxes and set-up records of this plan state were built from the same geometry inputs: not rebuilt */
 int vf_terrain_debug_plan_mode(const vf_terrain *t, uint32_t *mode);
 /* diagnostics, only in libraries built with -DVF_PHASE_PROF (VF_ERR_INVALID otherwise): shader-clock cycles summed over
  * all waves of the last frame's tile kernel, per phase (set-up, pull/cull, vertex stage, classification, span raster,

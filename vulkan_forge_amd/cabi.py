@@ -16,6 +16,7 @@ VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -
 VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
 VF_DRAPE_MIP_BIAS_MAX, VF_DRAPE_MIP_LEVELS_MAX = 16.0, 15                                # its mip pyramid
 VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED_AHEAD = 1, 2, 4, 8, 16   # vf_terrain_debug_plan_mode
+VF_PLAN_GEOMETRY_REUSED = 32   # ... its bit for "the block boxes and set-up records were not rebuilt" (DESIGN.md 3): Terrain.geometry_reused()
 
 # every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py)
 SYMBOLS = [
@@ -655,11 +656,16 @@ class Terrain:
         self._check(self.lib.vf_terrain_debug_set_plan_feedback(self.t, ticks.ctypes.data, lg.ctypes.data,
                                                                 None if pieces is None else pieces.ctypes.data, n))
 
-    def plan_mode(self):
-        """VF_PLAN_* bits: how the frame rendered last was planned."""
+    def plan_mode(self, geometry=False):
+        """VF_PLAN_* bits: how the frame rendered last was planned.  Whether the plan state's geometry was rebuilt or reused changes nothing
+        in the plan, so VF_PLAN_GEOMETRY_REUSED is reported only on request (geometry=True: the word as the library gives it)."""
         m = _u32()
         self._check(self.lib.vf_terrain_debug_plan_mode(self.t, C.byref(m)))
-        return m.value
+        return m.value if geometry else m.value & ~VF_PLAN_GEOMETRY_REUSED
+
+    def geometry_reused(self):
+        """Did the frame rendered last reuse its plan state's block boxes and set-up records (VF_PLAN_GEOMETRY_REUSED)?"""
+        return bool(self.plan_mode(geometry=True) & VF_PLAN_GEOMETRY_REUSED)
 
     def tile_stats(self):
         """(ntiles, 3) u32 per local tile: candidate blocks (sum over strips), raster ticks, raster+fragment ticks (max)."""

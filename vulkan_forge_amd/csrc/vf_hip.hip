@@ -462,6 +462,9 @@ struct vf_terrain {
         uint8_t *slab = nullptr;         // one allocation per plan state
         float u_used[32] = {};           // view + proj of the frame whose tile times sit in `feedback` (the plan looks them up through the camera motion)
         bool have_u_used = false;
+        // the stamp: geom_gen / height_gen the boxes, ranges, segment list, records, masks and vertex records were built from (0: none --
+        // never filled, or left half-written).  While both equal the live generations the plan reuses them (plan_frame).
+        uint64_t geom_stamp = 0, height_stamp = 0;
     } ps[kPlanStates];
     PlanCursor cursor;
     uint32_t last_set = 0;               // the set of the frame rendered last
@@ -469,23 +472,36 @@ struct vf_terrain {
     hipStream_t side = nullptr;          // k_block_boxes -> k_plan -> k_plan_sort
     hipStream_t side2 = nullptr;         // k_block_setup (needs the block boxes only): beside the plan chain, both under the previous frame
     hipEvent_t entry = nullptr;          // caller's stream at render entry (orders a height-cache rebuild after the caller's work)
+    // behind the last height-cache rebuild, on the stream `cached_on`: a plan chain that starts on another stream waits for it first.
+    // (A handle's first frame builds the cache on the caller's stream; the second frame's chain, on the plan streams, has no event of
+    //  its plan state to wait for yet and used to read the bounds and the cache while they were being written -- a wrong second frame
+    //  that the fourth frame used to paint over, and that reuse would keep.)
+    hipEvent_t cached = nullptr;
+    hipStream_t cached_on = nullptr;
     hipStream_t last_stream = nullptr;
     bool rendered = false;
     // THE NEXT FRAME'S PLAN, QUEUED AHEAD (round 5).  A camera at rest draws the same plan again and again, and a caller that waits for
     // each frame (render_png, render_rgba: every call of the reference's API) used to pay the plan chain -- block boxes, set-up pass,
     // plan, sort: 0.2 ms at C4 -- in front of every tile kernel, because nothing is left to hide it under once the caller has waited.
     // So when a frame was drawn with the very inputs of the frame before it, the first half of the NEXT frame (plan_frame) is queued
-    // right behind it: by the time the caller comes back the plan is there.  `inputs_gen` counts everything a plan depends on (uniforms,
-    // heights, shard, shade mode, timing); a plan made ahead is used only for the generation it was made for, and otherwise thrown
-    // away: the bookkeeping it advanced is rolled back and the frame is planned again (its kernels queue behind the stale ones).
+    // right behind it: by the time the caller comes back the plan is there.  `inputs_gen` counts everything a picture depends on (uniforms,
+    // heights, shard, shade mode, features), `geom_gen` below what a plan depends on; a plan made ahead is used only for the geometry
+    // generation it was made for, and otherwise thrown away: the bookkeeping it advanced is rolled back and the frame is planned again (its kernels queue behind the stale ones).
     uint64_t inputs_gen = 1;
+    // Two generations.  `inputs_gen` means "the same picture"; `geom_gen` means "the same geometry": it counts the changes of what
+    // k_block_boxes and k_block_setup read -- view, projection, spacing (u[36]) and exaggeration (u[38]) of the uniform block, compared
+    // bit for bit; the heights; the shard layout (the frame and grid sizes are the handle's for life).  The sun, exposure, height range,
+    // shade mode, precision, shadows, ambient occlusion, drape and overlays move inputs_gen alone.  A counter, not a hash: camera
+    // A -> B -> A is two changes.  A plan state's boxes and records (PlanState::geom_stamp) and a plan made ahead (PrePlan::geom) hold
+    // for one geometry generation; a plan made ahead that meets new shading inputs has the shading fields of its K.P refreshed.
+    uint64_t geom_gen = 1;
     struct PrePlan {
         bool valid = false;
         FramePlan K;
-        uint64_t gen = 0;
+        uint64_t gen = 0, geom = 0;      // inputs_gen / geom_gen it was made for
         PlanCursor before;               // where the handle stood before plan_frame advanced it (restored when the plan is thrown away)
     } pre;
-    uint64_t last_drawn_gen = 0;         // inputs_gen of the frame drawn last (two frames of one generation: the camera is at rest)
+    uint64_t last_drawn_geom = 0;        // geom_gen of the frame drawn last (SAME GEOMETRY: two frames of one generation -- the camera is at rest, whatever the light does)
     bool replan_fresh = false;           // a plan queued ahead was thrown away: the next plan takes the previous frame's tile times (drop_preplan)
     // Round 6: a caller that WAITS for every frame (every call of the reference's API) never makes the context's two plan streams (17-20 ms
     // once per process, which its second call used to pay): its plans run on its own stream, and the plan made ahead for a camera at
@@ -752,6 +768,7 @@ static hipError_t ensure_plan_state(vf_terrain *t, uint32_t k, hipStream_t zero_
     C.add((void **)&S.flags_new, all_tiles * sizeof(uint32_t));
     hipError_t err = C.commit(&S.slab, zero_on);          // (the stream of the state's first user: the plan chain)
     if (err != hipSuccess) { S.slab = nullptr; return err; }
+    S.geom_stamp = S.height_stamp = 0;                     // a fresh slab holds no geometry
     S.work_sorted = S.work + (all_tiles + kSplitBudget + 16);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&S.planned, hipEventDisableTiming);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&S.drawn, hipEventDisableTiming);
@@ -843,6 +860,7 @@ int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t gri
     //  handle's first frame -- the only one of the reference's construct / render_png once usage -- has nothing to overlap with)
     if (err == hipSuccess) err = hipMemcpyAsync(t->d_lut, lut, sizeof lut, hipMemcpyHostToDevice, ctx->stream);   // (pageable source: returns when the copy is staged)
     if (err == hipSuccess) err = hipEventCreateWithFlags(&t->entry, hipEventDisableTiming);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&t->cached, hipEventDisableTiming);
     // (both plan states now: a device allocation costs 0.03 ms whatever its size -- measured, round 5 -- while making the second one
     //  inside the handle's second frame cost that frame 0.7 ms)
     for (uint32_t k = 0; k < vf_terrain::kPlanStates && err == hipSuccess; ++k) err = ensure_plan_state(t, k, ctx->stream);
@@ -887,24 +905,42 @@ void vf_terrain_destroy(vf_terrain *t)
     pinned_free(t->h_png);
     for (auto &f : t->ev) { if (f.begin) (void)hipEventDestroy(f.begin); if (f.end) (void)hipEventDestroy(f.end); }
     if (t->entry) (void)hipEventDestroy(t->entry);
+    if (t->cached) (void)hipEventDestroy(t->cached);
     if (t->copied) (void)hipEventDestroy(t->copied);
     for (auto &g : t->loop.probes) { if (g.a) (void)hipEventDestroy(g.a); if (g.b) (void)hipEventDestroy(g.b); }
     ov_release(t);
     delete t;
 }
 
+// The geometry fields of a uniform block: what k_block_boxes, k_block_setup, vertex_shader and grid_coord read of the FrameParams that
+// build_params makes from it -- view (u[0..16)), proj (u[16..32)), spacing (u[36]) and exag (u[38]); hw, hh, step, n, nm1, nb, W, H and
+// ntx come from the handle's sizes, the shard fields from the layout.  The sun u[32..35), exposure u[35] and the height range u[37]
+// (Lx..Lz, exposure, h_range / inv2hr) are shading.  Bits are compared, not values: -0 is not +0 and a NaN equals itself.
+static bool same_geometry(const float *a, const float *b)
+{
+    return std::memcmp(a, b, 32 * sizeof(float)) == 0 && std::memcmp(a + 36, b + 36, sizeof(float)) == 0 && std::memcmp(a + 38, b + 38, sizeof(float)) == 0;
+}
+
+// a new uniform block becomes the live one (vf_terrain_set_uniforms and the batch entry point): which generations move
+static void take_uniforms(vf_terrain *t, const float *uniforms)
+{
+    if (!t->have_uniforms || std::memcmp(t->inputs.u, uniforms, sizeof t->inputs.u) != 0) t->inputs_gen++;     // another picture
+    if (!t->have_uniforms || !same_geometry(t->inputs.u, uniforms)) t->geom_gen++;                             // ... of other geometry
+    std::memcpy(t->inputs.u, uniforms, sizeof t->inputs.u);
+    t->have_uniforms = true;
+}
+
 int vf_terrain_set_uniforms(vf_terrain *t, const float uniforms[44])
 {
     if (!t || !uniforms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->have_uniforms || std::memcmp(t->inputs.u, uniforms, sizeof t->inputs.u) != 0) t->inputs_gen++;     // (a plan made ahead was made for the old block)
-    std::memcpy(t->inputs.u, uniforms, sizeof t->inputs.u);
-    t->have_uniforms = true;
+    take_uniforms(t, uniforms);
     return VF_OK;
 }
 
 static int set_height_common(vf_terrain *t, uint32_t tw, uint32_t th)
 {
     t->inputs_gen++;
+    t->geom_gen++;                                         // (the height cache and the block bounds are geometry inputs; so are tw / th through the axis tables)
     t->height_gen++;
     VF_HIP_TRY(drop_preplan(t));
     t->loop.reset();                                       // other heights: which line loop is faster is measured again
@@ -1007,6 +1043,7 @@ static int reset_layout_feedback(vf_terrain *t)
         VF_HIP_TRY(hipMemset(S.background, 0, (size_t)t->ntx * t->nty * sizeof(uint32_t)));
         S.have_u_used = false;
     }
+    for (auto &S : t->ps) S.geom_stamp = S.height_stamp = 0;   // (k_block_boxes dropped the blocks of the other layout's tiles)
     return VF_OK;
 }
 
@@ -1021,6 +1058,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->dr.iw && nranks != 1) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
+    t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
     VF_HIP_TRY(drop_preplan(t));
     t->rank = rank; t->nranks = nranks; t->band_h = band_h;
     t->shard_tiles = false; t->use_map = false;
@@ -1150,6 +1188,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (rc != VF_OK) return rc;
     VF_HIP_TRY(sync_sides(t));                                // (k_block_boxes of a frame in flight reads the owner table)
     const StripeMap *sm = layout_map(skew);
+    t->geom_gen++;                                            // before the first byte of the owner table changes: k_block_boxes reads the table, the stripe width, the skew and the rank
     if (sm) VF_HIP_TRY(hipMemcpy(t->d_stripe_owner, sm->owner.data(), sm->owner.size(), hipMemcpyHostToDevice));
     t->use_map = sm != nullptr;
     if (n) VF_HIP_TRY(hipMemcpy(t->d_tile_map, map.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -1343,7 +1382,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
     float shift = 0.0f;
     if (C.have_drawn) {
         shift = camera_shift_px(t, C.u_drawn, u);
-        if (shift > kFreshFeedbackPx) C.camera_moving = true;                  // hysteresis: frames that alternate between the two
+        if (shift > kFreshFeedbackPx) C.camera_moving = true;                  // (SAME GEOMETRY by construction: view and projection alone) hysteresis: frames that alternate between the two
         else if (shift < 0.5f * kFreshFeedbackPx) C.camera_moving = false;     // modes get the worst of both
     }
     // (one more frame after the motion stops: the frame before last still shows the old view, the last one the new)
@@ -1387,8 +1426,19 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
         VF_HIP_TRY(hipStreamWaitEvent(side, t->entry, 0));
         hipLaunchKernelGGL(k_height_blocks, dim3(t->nblocks), dim3(64), 0, side, t->n, t->nb, t->tw, A, t->d_height, t->d_hblk, t->d_bounds);
         VF_HIP_TRY(hipGetLastError());
+        VF_HIP_TRY(hipEventRecord(t->cached, side));
+        t->cached_on = side;
         t->bounds_dirty = false;
+        for (auto &X : t->ps) X.geom_stamp = X.height_stamp = 0;       // (whatever the generations say: nothing was built from this cache)
     }
+    if (t->cached_on && t->cached_on != side) {             // the cache was last rebuilt on another stream: this chain (and, through S.boxed and S.planned, the set-up pass and the draw) comes after it
+        VF_HIP_TRY(hipStreamWaitEvent(side, t->cached, 0));
+        t->cached_on = side;
+    }
+    // This set's boxes, ranges, segment list, records, masks and vertex records are a pure function of the geometry inputs: when they
+    // were built from the live generations they are left as they are (S.boxed and S.set_up keep their last record: completed long ago).
+    // After a geometry change each of the two sets pays the full pass once.
+    const bool reuse = S.geom_stamp != 0 && S.geom_stamp == t->geom_gen && S.height_stamp == t->height_gen;
     if (timed) VF_HIP_TRY(hipEventRecord(ev[0], side));
     const size_t rc_n = (size_t)t->nb * t->ntx;
     uint32_t *rc_lo = S.rc, *rc_hi = S.rc + rc_n;
@@ -1397,17 +1447,27 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
     uint32_t *quantum = S.feedback + (size_t)t->ntx * t->nty;
     const uint32_t nsegs_all = grid_segments(t);
     uint32_t *seg_count = S.seg_list + nsegs_all;
-    hipLaunchKernelGGL(k_block_boxes, dim3(t->nb + 1), dim3(t->nb > 256 ? 512 : 256), 0, side, P, t->d_bounds, S.ranges, S.row_ranges, S.cap_seg, S.cap_rad, rc_lo, rc_hi,
-                       fresh || first ? (const uint32_t *)nullptr : S.feedback, t->ntx * t->nty, quantum, S.work_count, S.recs, S.seg_list, seg_count);
-    // vertex stage + tile-independent culling, once per frame (streams ~1.3 KB per block into this frame's plan state): needs the
-    // block boxes only, so it runs on a second stream beside k_plan / k_plan_sort -- all of them under the previous frame's tile kernel
-    VF_HIP_TRY(hipEventRecord(S.boxed, side));
-    VF_HIP_TRY(hipStreamWaitEvent(side2, S.boxed, 0));                  // (orders it after S.drawn and the height cache too)
-    // (one short-lived workgroup per possible segment -- those beyond the list's length leave at once: workgroups that come and go
-    //  share the CUs with the previous frame's tile kernel more smoothly than a few long-lived ones)
-    hipLaunchKernelGGL(k_block_setup, dim3(nsegs_all), dim3(kSetupThreads), 0, side2,
-                       P, t->d_hblk, S.ranges, S.vtx, S.recs, S.gen, S.seg_list, seg_count);
-    VF_HIP_TRY(hipEventRecord(S.set_up, side2));
+    const uint32_t *const quantum_from = fresh || first ? (const uint32_t *)nullptr : S.feedback;
+    if (reuse) {
+        // the work of k_block_boxes' extra workgroup alone: this frame's queue words and split quantum, in front of k_plan.  The segment
+        // counter stays at the zero k_clear left it at, and nothing is launched against it.
+        hipLaunchKernelGGL(k_plan_begin, dim3(1), dim3(512), 0, side, quantum_from, t->ntx * t->nty, quantum, S.work_count);
+    } else {
+        S.geom_stamp = S.height_stamp = 0;                                  // half-written from here until both kernels are on their way
+        hipLaunchKernelGGL(k_block_boxes, dim3(t->nb + 1), dim3(t->nb > 256 ? 512 : 256), 0, side, P, t->d_bounds, S.ranges, S.row_ranges, S.cap_seg, S.cap_rad, rc_lo, rc_hi,
+                           quantum_from, t->ntx * t->nty, quantum, S.work_count, S.recs, S.seg_list, seg_count);
+        // vertex stage + tile-independent culling, once per geometry (streams ~1.3 KB per block into this frame's plan state): needs the
+        // block boxes only, so it runs on a second stream beside k_plan / k_plan_sort -- all of them under the previous frame's tile kernel
+        VF_HIP_TRY(hipEventRecord(S.boxed, side));
+        VF_HIP_TRY(hipStreamWaitEvent(side2, S.boxed, 0));                  // (orders it after S.drawn and the height cache too)
+        // (one short-lived workgroup per possible segment -- those beyond the list's length leave at once: workgroups that come and go
+        //  share the CUs with the previous frame's tile kernel more smoothly than a few long-lived ones)
+        hipLaunchKernelGGL(k_block_setup, dim3(nsegs_all), dim3(kSetupThreads), 0, side2,
+                           P, t->d_hblk, S.ranges, S.vtx, S.recs, S.gen, S.seg_list, seg_count);
+        VF_HIP_TRY(hipEventRecord(S.set_up, side2));
+        VF_HIP_TRY(hipGetLastError());                                      // both launched without error: the stamp
+        S.geom_stamp = t->geom_gen; S.height_stamp = t->height_gen;
+    }
     if (timed) VF_HIP_TRY(hipEventRecord(ev[1], side));
     if (ntiles) {
         if (fresh) {
@@ -1427,7 +1487,8 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
     VF_HIP_TRY(hipGetLastError());                              // a failed plan launch is reported here: the probe block below clears hipEventQuery's "not ready"
     if (timed) VF_HIP_TRY(hipEventRecord(ev[2], side));
     VF_HIP_TRY(hipEventRecord(S.planned, side));
-    K.mode = (first ? VF_PLAN_FIRST : 0u) | (fresh ? VF_PLAN_FRESH : 0u) | (M.on ? VF_PLAN_MOTION_MAP : 0u) | (dilate ? VF_PLAN_DILATE : 0u);
+    K.mode = (first ? VF_PLAN_FIRST : 0u) | (fresh ? VF_PLAN_FRESH : 0u) | (M.on ? VF_PLAN_MOTION_MAP : 0u) | (dilate ? VF_PLAN_DILATE : 0u) |
+             (reuse ? VF_PLAN_GEOMETRY_REUSED : 0u);
     K.set = set; K.ntiles = ntiles; K.motion_starts = motion_starts; K.rc_lo = rc_lo; K.rc_hi = rc_hi; K.seg_count = seg_count;
     return VF_OK;
 }
@@ -1520,6 +1581,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     // triangles have a handful of lines, and is better off with the leaner kernel.  That is the variant by default; the handle
     // measures (LineLoop), and starts again when the layout is new or the camera starts to move.
     const int guess = t->nranks < (uint32_t)VF_GROUPS_MAX_RANKS ? 1 : 0;
+    // (the probe's reset is about geometry -- a new layout, a camera that starts to move, other heights (set_height_common) -- never about the light)
     const LoopPick pick = t->loop.choose(guess, t->cursor.frames_since_reset <= 1 || K.motion_starts, ntiles != 0u);
     const bool groups = pick.variant != 0;
     LineLoop::Probe *gp = pick.probe ? t->loop.arm(s) : nullptr;
@@ -1578,7 +1640,7 @@ static void plan_ahead(vf_terrain *t, hipStream_t s)
 {
     vf_terrain::PrePlan &R = t->pre;
     R.before = t->cursor;
-    if (plan_frame(t, s, R.K) == VF_OK) { R.valid = true; R.gen = t->inputs_gen; }
+    if (plan_frame(t, s, R.K) == VF_OK) { R.valid = true; R.gen = t->inputs_gen; R.geom = t->geom_gen; }
     else {                                                  // (a failed launch: the next call plans for itself and reports it)
         // (the whole cursor goes back, though only cur_set, frame_no and frames_since_reset can have moved: a plan is made ahead for a
         //  camera at rest only -- neither moving nor was_moving, a frame drawn, u_drawn equal to the live uniforms -- and plan_frame
@@ -1589,12 +1651,13 @@ static void plan_ahead(vf_terrain *t, hipStream_t s)
 }
 
 // A read-back has queued its copy on `s`: the plan a waiting caller's next frame will want goes out now, behind the copy (the caller
-// waits for the copy's event, not for the stream), if the frame was drawn from inputs that still stand.
+// waits for the copy's event, not for the stream), if the frame was drawn from geometry inputs that still stand (SAME GEOMETRY: a plan
+// made ahead survives a change of the shading inputs, render_impl).
 static void flush_preplan(vf_terrain *t, hipStream_t s)
 {
     if (!t->preplan_pending) return;
     t->preplan_pending = false;
-    if (t->pre.valid || t->side || t->last_drawn_gen != t->inputs_gen || t->bounds_dirty || s != t->last_stream) return;
+    if (t->pre.valid || t->side || t->last_drawn_geom != t->geom_gen || t->bounds_dirty || s != t->last_stream) return;
     plan_ahead(t, s);
 }
 
@@ -1623,8 +1686,14 @@ static int render_impl(vf_terrain *t, hipStream_t s, bool write_vis)
     t->preplan_pending = false;                             // (no read-back came in between: this call plans for itself)
     if (t->pre.valid) {
         t->pre.valid = false;
-        if (t->pre.gen == t->inputs_gen && !write_vis) {
+        // SAME GEOMETRY, not "same picture": the plan holds for the geometry generation and the feedback it read (whoever changes the
+        // feedback or the layout drops it: vf_terrain_debug_set_plan_feedback, the shard setters).  When only shading inputs moved --
+        // sun, exposure, height range, shade mode, precision -- the plan stays and K.P is made again from the live inputs: its geometry
+        // fields come out bit for bit as the plan's kernels saw them, its shading fields are the new ones.  What the plan chose (set,
+        // mode, ranges, sampling) is not in K.P.
+        if (t->pre.geom == t->geom_gen && !write_vis) {
             K = t->pre.K; planned = true;
+            if (t->pre.gen != t->inputs_gen) build_params(t, t->inputs, K.P);
             if (!t->side) {                                 // a waiting caller's plan, queued behind its last read-back: done by now?
                 const bool ready = hipEventQuery(t->ps[K.set].planned) == hipSuccess;
                 (void)hipGetLastError();
@@ -1632,15 +1701,15 @@ static int render_impl(vf_terrain *t, hipStream_t s, bool write_vis)
                 if (t->tight_calls >= 3u) t->want_plan_streams = true;
             }
         }
-        else { t->pre.valid = true; VF_HIP_TRY(drop_preplan(t, s)); }     // made for other inputs
+        else { t->pre.valid = true; VF_HIP_TRY(drop_preplan(t, s)); }     // made for other geometry
     }
     if (!planned) { const int rc = plan_frame(t, s, K, streaming); if (rc != VF_OK) return rc; }
-    const bool again = t->last_drawn_gen == t->inputs_gen;      // the frame before this one was drawn from the same inputs
+    const bool again = t->last_drawn_geom == t->geom_gen;       // SAME GEOMETRY: the frame before this one was drawn from the same geometry inputs (its light may differ)
     const int rc = draw_frame(t, s, K, write_vis);
     if (rc != VF_OK) return rc;
     t->last_plan_mode = K.mode | (planned ? VF_PLAN_QUEUED_AHEAD : 0u);
-    t->last_drawn_gen = t->inputs_gen;
-    // the camera is at rest (two frames from one set of inputs), the handle is past its first frames, nothing diagnostic is going on:
+    t->last_drawn_geom = t->geom_gen;
+    // the camera is at rest (two frames from one set of geometry inputs), the handle is past its first frames, nothing diagnostic is going on:
     // the next frame's plan goes out now
     // (round 6: also for a caller that streams frames of a resting camera -- its next plan goes out one call early, which changes nothing while
     //  the frames keep coming and has the plan ready for the first frame after it has waited once)
@@ -1677,9 +1746,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
         if (dev_rgba && !dev_rgba[k]) return fail(VF_ERR_INVALID, "dev_rgba holds a NULL output buffer");
-        if (!t->have_uniforms || std::memcmp(t->inputs.u, uniforms + 44u * k, sizeof t->inputs.u) != 0) t->inputs_gen++;
-        std::memcpy(t->inputs.u, uniforms + 44u * k, sizeof t->inputs.u);
-        t->have_uniforms = true;
+        take_uniforms(t, uniforms + 44u * k);
         if (dev_rgba) t->d_rgba = (uint32_t *)dev_rgba[k];
         const int rc = render_recorded(t, s);
         if (rc != VF_OK) return rc;
@@ -1759,11 +1826,16 @@ static int render_visibility(vf_terrain *t)
     const hipStream_t stream_now = t->last_stream;
     const bool timing = t->timing, rendered = t->rendered;
     const uint32_t plan_mode_now = t->last_plan_mode;
+    // uniforms set since the frame was drawn may describe other geometry: the diagnostic frame then gets a geometry generation of its own,
+    // and so does the live block when it comes back -- the plan state the frame filled is not taken for the live inputs' (nor the other way)
+    const bool other_geometry = t->have_frame && !same_geometry(t->drawn_inputs.u, t->inputs.u);
     if (t->have_frame) t->inputs = t->drawn_inputs;
+    if (other_geometry) t->geom_gen++;
     t->d_rgba = t->d_rgba_scratch; t->timing = false;
     rc = render_impl(t, t->ctx->stream, true);
     hipError_t e = hipStreamSynchronize(t->ctx->stream);
     t->inputs = inputs_now;
+    if (other_geometry) t->geom_gen++;
     cursor_now.cur_set = t->cursor.cur_set; cursor_now.frame_no = t->cursor.frame_no;      // (the plan state and the frame number it used stay used, see above)
     t->cursor = cursor_now;
     t->d_rgba = out_now; t->last_stream = stream_now; t->timing = timing;
@@ -2049,6 +2121,8 @@ static int ct_heights_current(vf_terrain *t)
     if (t->bounds_dirty) {
         hipLaunchKernelGGL(k_height_blocks, dim3(t->nblocks), dim3(64), 0, t->ctx->stream, t->n, t->nb, t->tw, axis(t), t->d_height, t->d_hblk, t->d_bounds);
         VF_HIP_TRY(hipGetLastError());
+        VF_HIP_TRY(hipEventRecord(t->cached, t->ctx->stream));
+        t->cached_on = t->ctx->stream;
         t->bounds_dirty = false;
     }
     return VF_OK;

@@ -7,6 +7,8 @@
 //                     shard: drops the blocks that reach none of the rank's tiles, lists the 16-block segments still needed
 //   k_block_setup     vs_main + the tile-independent part of primitive assembly / culling, once per block: 81 vertex records
 //                     {X, Y, 1/w, h} and a block record (exact pixel box, alive masks) per block
+//                     (both only when the geometry inputs differ from those the plan state was filled from; otherwise
+//                     k_plan_begin: the queue words and the split quantum, one workgroup)
 //   k_plan, k_plan_sort   busy tiles -> work items weighted by last frame's measured times, heavy tiles cut into column
 //                     strips, heaviest first
 //   per frame, on the caller's stream:
@@ -119,6 +121,16 @@ __device__ __forceinline__ void publish_quantum(const uint32_t *__restrict__ fee
 __global__ __launch_bounds__(512) void k_quantum(const uint32_t *__restrict__ feedback, uint32_t ntiles, uint32_t *__restrict__ quantum)
 {
     publish_quantum(feedback, ntiles, quantum);
+}
+
+// What k_block_boxes' extra workgroup does, as a kernel of one workgroup: the frame's queue words to zero and its split quantum from
+// `feedback` when given.  It opens the plan chain of a frame whose block boxes and set-up records are reused (plan_frame: the geometry
+// inputs are those the plan state was filled from), in front of k_plan on the same stream.
+__global__ __launch_bounds__(512) void k_plan_begin(const uint32_t *__restrict__ feedback, uint32_t ntiles_all, uint32_t *__restrict__ quantum,
+                                                    uint32_t *__restrict__ work_count)
+{
+    if (threadIdx.x < 4u) work_count[threadIdx.x] = 0u;
+    if (feedback) publish_quantum(feedback, ntiles_all, quantum);
 }
 
 // One workgroup per block row, plus one (index nb) that publishes the frame's split quantum when `feedback` is given.
