@@ -634,6 +634,61 @@ int vf_terrain_read_drape_level(vf_terrain *t, uint32_t level, uint16_t *out /* 
 /* Diagnostics: mean time in ms of `repeats` back-to-back builds of the whole pyramid, after one warm-up. */
 int vf_terrain_debug_drape_mip_build(vf_terrain *t, uint32_t repeats, float *ms);
 
+/* ---- viewshed analysis: a line-of-sight field from an observer, and a tint of the frame ------------
+ * The viewshed field is one float32 per grid vertex, (grid, grid) row-major (row j = z index, column i = x index): seen in [0, 1],
+ * 1 = the observer sees the vertex, 0 = the terrain hides it.  One observer per handle: observer_xz = (x, z) in the overlays' world
+ * frame (the one vf_terrain_add_points takes: grid coordinates times the spacing), snapped to the nearest grid vertex; the eye stands
+ * eye_height above the surface there, a target target_height above its vertex, both in the units of y = h * exag.  The field comes
+ * from the displaced heights the renderer draws by a horizon scan along lines that fan out from the observer's vertex (Franklin's R2
+ * rule with true distances); `bias` (the height by which a target may lie below the horizon and still be seen) and `softness` (the
+ * height over which seen falls to 0) are in the same units.  The arithmetic is fixed bit for bit.  The field is
+ * computed by the first tinted frame or field call that needs it and again only after the heights, exaggeration, the observer's
+ * vertex, eye_height, target_height, softness or bias have changed -- not for the colours, the radius, the camera or the sun.
+ *
+ * vf_terrain_set_viewshed: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then (behind
+ * the shadow, ambient and drape passes) blends over every covered pixel the hidden colour with coverage 1 - s and the visible colour
+ * with coverage s, s the interpolated seen value, each as an overlay feature blends (alpha8 / 255 times the coverage, on linear
+ * values, the exact sRGB encoder); a colour with alpha 0 blends nothing, and a pixel neither colour touches keeps the frame's bytes.
+ * radius > 0: only pixels whose surface point lies within `radius` (world units, horizontal) of the observer's vertex; 0: all.
+ * The tint is flat, neither lit nor shadowed; background pixels are never touched.  Overlays composite afterwards; geometry buffers
+ * and the diagnostics frames are unaffected.  The colours are {r, g, b, a} bytes.  observer finite, eye_height >= 0,
+ * target_height >= 0, radius >= 0, softness > 0, bias >= 0, all finite, else VF_ERR_INVALID and nothing changes.  Whole-frame handles
+ * only: enabling on a band- or tile-sharded handle, sharding a handle with a viewshed enabled, and vf_terrain_render_batch /
+ * _batch_host on a handle with a viewshed enabled are VF_ERR_INVALID and change nothing.  The parameters are stored also with
+ * enable == 0 (the field calls below use them).  observer_xz == NULL (with enable == 0): the observer is forgotten, the defaults are
+ * back and everything made for the viewshed is freed.  The setting survives height uploads.  A handle that never calls any of these
+ * allocates and launches nothing for them.
+ * vf_terrain_read_viewshed_field: the field for the current heights, uniforms, observer and parameters into host memory (grid * grid
+ * floats), whether or not the viewshed is enabled for drawing; VF_ERR_INVALID before an observer is set.
+ * vf_terrain_viewshed_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream);
+ * later calls on the handle are ordered behind the copy by the library.
+ * vf_terrain_viewshed_info: the setting; with an observer (and uniforms) also its vertex (i, j), the vertex's world position
+ * (x, y, z) -- where a marker goes -- and the eye's y. */
+#define VF_VIEWSHED_EYE_HEIGHT 0.05f
+#define VF_VIEWSHED_TARGET_HEIGHT 0.0f
+#define VF_VIEWSHED_SOFTNESS 0.02f
+#define VF_VIEWSHED_BIAS 0.002f
+#define VF_VIEWSHED_VISIBLE_RGBA 0x6060FF40u   /* (64, 255, 96, 96) as r | g << 8 | b << 16 | a << 24 */
+#define VF_VIEWSHED_HIDDEN_RGBA 0x00000000u    /* (0, 0, 0, 0): hidden ground keeps the frame's colour */
+typedef struct vf_viewshed_info {
+    int32_t enabled, has_observer;
+    uint32_t vertex[2];       /* (i, j); this and the next two only with an observer */
+    float observer_xyz[3];    /* world position of the observer's vertex */
+    float eye_y;              /* observer_xyz[1] + eye_height */
+    float eye_height, target_height, radius /* 0: none */, softness, bias;
+    uint8_t visible_rgba[4], hidden_rgba[4];
+} vf_viewshed_info;
+int vf_terrain_set_viewshed(vf_terrain *t, int enable, const float observer_xz[2], float eye_height, float target_height, float radius,
+                            const uint8_t visible_rgba[4], const uint8_t hidden_rgba[4], float softness, float bias);
+int vf_terrain_read_viewshed_field(vf_terrain *t, float *seen);
+int vf_terrain_viewshed_field_device(vf_terrain *t, float *dev_seen, void *stream);
+int vf_terrain_viewshed_info(vf_terrain *t, vf_viewshed_info *out);
+/* diagnostics: ms[0] the average time (HIP events) of `repeats` computations of the field, ms[1] of `repeats` tint passes, for the
+ * frame rendered last (drawn again into scratch buffers), each after one warm-up; and how many times the handle has computed its
+ * field so far (the diagnostic launches are not counted). */
+int vf_terrain_debug_viewshed_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
+int vf_terrain_debug_viewshed_scans(vf_terrain *t, uint32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@ SYMBOLS = [
     "vf_terrain_debug_ambient_scans",
     "vf_terrain_set_drape", "vf_terrain_set_drape_device", "vf_terrain_clear_drape", "vf_terrain_drape_info", "vf_terrain_debug_drape_stage",
     "vf_terrain_set_drape_mips", "vf_terrain_drape_mip_info", "vf_terrain_read_drape_level", "vf_terrain_debug_drape_mip_build",
+    "vf_terrain_set_viewshed", "vf_terrain_read_viewshed_field", "vf_terrain_viewshed_field_device", "vf_terrain_viewshed_info",
+    "vf_terrain_debug_viewshed_stage", "vf_terrain_debug_viewshed_scans",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -55,6 +57,12 @@ class Timings(C.Structure):
 
 class FragmentTiming(C.Structure):
     _fields_ = [("resolve_ms", C.c_float), ("covered_pixels", C.c_uint32), ("repeats", C.c_uint32), ("equal_to_frame", C.c_uint32)]
+
+
+class ViewshedInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("has_observer", C.c_int32), ("vertex", C.c_uint32 * 2), ("observer_xyz", C.c_float * 3), ("eye_y", C.c_float),
+                ("eye_height", C.c_float), ("target_height", C.c_float), ("radius", C.c_float), ("softness", C.c_float), ("bias", C.c_float),
+                ("visible_rgba", C.c_uint8 * 4), ("hidden_rgba", C.c_uint8 * 4)]
 
 
 DIST_UNIQUE_ID_BYTES = 128
@@ -148,6 +156,12 @@ _PROTOS = {
     "vf_terrain_drape_mip_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32), C.POINTER(_f), C.POINTER(C.c_uint64), C.POINTER(_u32)]),
     "vf_terrain_read_drape_level": (_i, [_vp, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "vf_terrain_debug_drape_mip_build": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_viewshed": (_i, [_vp, _i, C.POINTER(_f), _f, _f, _f, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _f, _f]),
+    "vf_terrain_read_viewshed_field": (_i, [_vp, _vp]),
+    "vf_terrain_viewshed_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_viewshed_info": (_i, [_vp, C.POINTER(ViewshedInfo)]),
+    "vf_terrain_debug_viewshed_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_debug_viewshed_scans": (_i, [_vp, C.POINTER(_u32)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -564,6 +578,50 @@ class Terrain:
         """How many times the handle has computed its sky-view field."""
         n = _u32()
         self._check(self.lib.vf_terrain_debug_ambient_scans(self.t, C.byref(n)))
+        return n.value
+
+    def set_viewshed(self, observer, *, enabled=True, eye_height=0.05, target_height=0.0, radius=None, visible_rgba=(64, 255, 96, 96),
+                     hidden_rgba=(0, 0, 0, 0), softness=0.02, bias=0.002):
+        """Viewshed analysis: what the observer at (x, z) of the overlays' world frame sees, as a tint of the frame.
+        Every parameter is stored by every call, also one that disables, and steers viewshed_field() too."""
+        from ._viewshed import viewshed_args
+        en, x, z, eye, tgt, rad, vis, hid, soft, bias = viewshed_args(observer, enabled, eye_height, target_height, radius, visible_rgba, hidden_rgba,
+                                                                      softness, bias)
+        self._check(self.lib.vf_terrain_set_viewshed(self.t, en, (_f * 2)(x, z), eye, tgt, rad, (C.c_uint8 * 4)(*vis), (C.c_uint8 * 4)(*hid), soft, bias))
+
+    def clear_viewshed(self):
+        """Forget the observer: the viewshed is off, its parameters are the defaults again and its buffers are freed."""
+        self._check(self.lib.vf_terrain_set_viewshed(self.t, 0, None, 0.0, 0.0, 0.0, None, None, 1.0, 0.0))
+
+    def viewshed_field(self):
+        """The viewshed field for the current heights, uniforms, observer and parameters: (grid, grid) float32, 1 = seen, 0 = hidden."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_viewshed_field(self.t, out.ctypes.data))
+        return out
+
+    def viewshed_field_device(self, dev_seen, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_viewshed_field_device(self.t, dev_seen, stream))
+
+    def viewshed_info(self):
+        """dict: enabled, vertex (i, j), observer_xyz (world), eye_y, and the parameters."""
+        from ._viewshed import viewshed_info
+        v = ViewshedInfo()
+        self._check(self.lib.vf_terrain_viewshed_info(self.t, C.byref(v)))
+        return viewshed_info(v.enabled, v.has_observer, tuple(v.vertex), tuple(v.observer_xyz), v.eye_y, v.eye_height, v.target_height, v.radius,
+                             v.softness, v.bias, tuple(v.visible_rgba), tuple(v.hidden_rgba))
+
+    def viewshed_stage(self, repeats=20):
+        """(scan ms, tint-pass ms) of the frame rendered last, as timed launches of their own (diagnostics)."""
+        ms = (_f * 2)()
+        self._check(self.lib.vf_terrain_debug_viewshed_stage(self.t, int(repeats), ms))
+        return ms[0], ms[1]
+
+    def viewshed_scans(self):
+        """How many times the handle has computed its viewshed field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_viewshed_scans(self.t, C.byref(n)))
         return n.value
 
     def set_drape(self, image, *, extent=None, opacity=1.0, filter="linear"):

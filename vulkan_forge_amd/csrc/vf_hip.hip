@@ -8,6 +8,7 @@
 #include "vf_ambient.h"     // templates only
 #include "vf_drape.h"       // templates only
 #include "vf_relight.h"     // templates only: the shade pass of the three
+#include "vf_viewshed.h"    // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -423,6 +424,23 @@ struct vf_terrain {
         bool stale = true;               // d_pyr does not hold the pyramid of the image held
         uint32_t builds = 0;             // times a pyramid was built (vf_terrain_drape_mip_info)
     } dm;
+    // viewshed analysis: buffers made by the first tinted frame or field read; the field is computed again only when
+    // what it was made from has changed (not for the colours, the radius or a spacing that leaves the observer's vertex where it was)
+    struct Viewshed {
+        bool enabled = false, have_observer = false;
+        float ox = 0.0f, oz = 0.0f;      // the observer in the overlays' world frame
+        float eye_height = VF_VIEWSHED_EYE_HEIGHT, target_height = VF_VIEWSHED_TARGET_HEIGHT, radius = 0.0f;
+        float softness = VF_VIEWSHED_SOFTNESS, bias = VF_VIEWSHED_BIAS;
+        uint32_t visible_rgba = VF_VIEWSHED_VISIBLE_RGBA, hidden_rgba = VF_VIEWSHED_HIDDEN_RGBA;   // r | g << 8 | b << 16 | a << 24
+        DevBuf<float> d_seen;            // n x n, row-major
+        DevBuf<float> d_cmax;            // chunk maxima / carries of the scan: 4 quadrants x nchunks x nlines
+        DevBuf<float> d_decode;          // 256 sRGB8 -> linear (SrgbTables::decode)
+        bool valid = false;              // d_seen holds the field of `key`, vertex `key_ij` and heights generation `height_gen`
+        uint64_t height_gen = 0;
+        float key[5] = {};               // exaggeration, eye_height, target_height, softness, bias
+        uint32_t key_ij[2] = {};
+        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_viewshed_scans)
+    } vs;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -886,6 +904,7 @@ void vf_terrain_destroy(vf_terrain *t)
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release(); t->am.d_sky.release();
+    t->vs.d_seen.release(); t->vs.d_cmax.release(); t->vs.d_decode.release();
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -1056,6 +1075,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->sh.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
     if (t->am.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     if (t->dr.iw && nranks != 1) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
+    if (t->vs.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1181,6 +1201,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
     if (t->am.enabled) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
+    if (t->vs.enabled) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1551,6 +1572,8 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
                         bool shadows, bool ambient);
 
+static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
     const FrameParams &P = K.P;
@@ -1558,7 +1581,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool ambient = t->am.enabled && !diag;
     const bool drape = t->dr.iw != 0u && !diag;
     const Relight drape_pass = t->dm.enabled ? kDrapeMip : kDrape;   // (through the mip pyramid when mipmaps are on)
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape;
+    const bool viewshed = t->vs.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1620,6 +1644,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
         const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, drape_pass, shadows, ambient);
         if (drc != VF_OK) return drc;
+    }
+    if (viewshed && ntiles) {                              // the viewshed tint: behind the relight passes, in front of the overlays
+        const int vrc = viewshed_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        if (vrc != VF_OK) return vrc;
     }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
         const int orc = overlay_pass(t, s, P, V);
@@ -1742,6 +1770,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
     if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
+    if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1761,6 +1790,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
     if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
+    if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2760,16 +2790,20 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
     return VF_OK;
 }
 
-// The shadow field (sky = false) or the sky-view field for the live uniforms, heights and parameters, complete in d_lit / d_sky; then
+// The shadow field (which = 0), the sky-view field (1) or the viewshed field (2) for the live uniforms, heights and parameters, complete in d_lit / d_sky; then
 // to `host`, or to `dev` behind the work on `stream` (NULL: the handle's)
-static int field_out(vf_terrain *t, bool sky, float *host, float *dev, void *stream)
+static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
+
+static int field_out(vf_terrain *t, int which /* 0 lit, 1 sky, 2 seen */, float *host, float *dev, void *stream)
 {
+    const bool sky = which == 1;
     if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     if (int rc = ct_heights_current(t)) return rc;
-    if (int rc = relight_fields(t, t->inputs.u, t->ctx->stream, !sky, sky)) return rc;
+    if (which == 2) { if (int rc = viewshed_field(t, t->inputs.u, t->ctx->stream)) return rc; }
+    else if (int rc = relight_fields(t, t->inputs.u, t->ctx->stream, !sky, sky)) return rc;
     VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    const float *field = sky ? t->am.d_sky.p : t->sh.d_lit.p;
+    const float *field = which == 2 ? t->vs.d_seen.p : sky ? t->am.d_sky.p : t->sh.d_lit.p;
     const size_t bytes = (size_t)t->n * t->n * sizeof(float);
     if (host) { VF_HIP_TRY(hipMemcpy(host, field, bytes, hipMemcpyDeviceToHost)); return VF_OK; }
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
@@ -2781,13 +2815,13 @@ static int field_out(vf_terrain *t, bool sky, float *host, float *dev, void *str
 int vf_terrain_read_shadow_field(vf_terrain *t, float *lit)
 {
     if (!t || !lit) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, false, lit, nullptr, nullptr);
+    return field_out(t, 0, lit, nullptr, nullptr);
 }
 
 int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream)
 {
     if (!t || !dev_lit) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, false, nullptr, dev_lit, stream);
+    return field_out(t, 0, nullptr, dev_lit, stream);
 }
 
 int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count)
@@ -2806,7 +2840,7 @@ struct RelightStage {
     const uint32_t *redo = nullptr;
     hipStream_t s = nullptr;
     vf_terrain *t = nullptr;
-    uint32_t shadow_scans = 0, ambient_scans = 0;
+    uint32_t shadow_scans = 0, ambient_scans = 0, viewshed_scans = 0;
     int open(vf_terrain *handle)
     {
         if (int rc = gb_frame(handle, F)) return rc;
@@ -2814,7 +2848,7 @@ struct RelightStage {
         u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
         redo = t->ps[t->last_set].work_count + 3;
         s = t->ctx->stream;
-        shadow_scans = t->sh.scans; ambient_scans = t->am.scans;
+        shadow_scans = t->sh.scans; ambient_scans = t->am.scans; viewshed_scans = t->vs.scans;
         return VF_OK;
     }
     // the shade pass into the scratch frame, timed; the fields it reads are current
@@ -2827,7 +2861,7 @@ struct RelightStage {
     {
         return time_launches(s, repeats, ms, [&](bool) { rc = relight_fields(t, u, s, !sky, sky, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
     }
-    ~RelightStage() { if (t) { t->sh.scans = shadow_scans; t->am.scans = ambient_scans; } }
+    ~RelightStage() { if (t) { t->sh.scans = shadow_scans; t->am.scans = ambient_scans; t->vs.scans = viewshed_scans; } }
 };
 
 int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
@@ -2934,13 +2968,13 @@ int vf_terrain_set_ambient(vf_terrain *t, int enable, float strength, float reac
 int vf_terrain_read_sky_view_field(vf_terrain *t, float *sky)
 {
     if (!t || !sky) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, true, sky, nullptr, nullptr);
+    return field_out(t, 1, sky, nullptr, nullptr);
 }
 
 int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream)
 {
     if (!t || !dev_sky) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, true, nullptr, dev_sky, stream);
+    return field_out(t, 1, nullptr, dev_sky, stream);
 }
 
 int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count)
@@ -3164,6 +3198,204 @@ int vf_terrain_debug_drape_mip_build(vf_terrain *t, uint32_t repeats, float *ms)
     const hipError_t err = L.levels < 2u ? hipSuccess : time_launches(s, repeats, mean, [&](bool) { mips_launch(t, s, L); return hipGetLastError(); });
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("drape mip diagnostics: ") + hipGetErrorString(err));
     *ms = mean;
+    return VF_OK;
+}
+
+// ---- viewshed analysis (vf_viewshed.h) --------------------------------------------------
+
+// The observer's vertex on one axis from its world coordinate: the drape's grid coordinate (4b step 1), rounded
+static uint32_t viewshed_index(const vf_terrain *t, float x, float spacing)
+{
+    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    float mx = x / spacing;
+    mx = std::fmin(std::fmax(mx, -1.5f), 1.5f);
+    const float gx = (mx + 1.5f) / step;
+    return std::min((uint32_t)std::rint(gx), t->n - 1u);
+}
+
+// The frame of reference of the field for the uniforms `u`
+static void viewshed_plan(const vf_terrain *t, const float *u, ViewshedPlan &S)
+{
+    const vf_terrain::Viewshed &H = t->vs;
+    const float spacing = std::fmax(u[36], 1e-8f);
+    S.n = t->n; S.nb = t->nb;
+    S.io = viewshed_index(t, H.ox, spacing); S.jo = viewshed_index(t, H.oz, spacing);
+    S.L = t->n - 1u;
+    S.nlines = 2u * S.L + 1u; S.nchunks = (S.L + kShChunk - 1u) / kShChunk;
+    S.steps[0] = t->n - 1u - S.io; S.steps[1] = S.io; S.steps[2] = t->n - 1u - S.jo; S.steps[3] = S.jo;
+    S.exag = u[38]; S.eye_height = H.eye_height; S.target_height = H.target_height; S.softness = H.softness; S.bias = H.bias;
+}
+
+// d_seen holds the field of the uniforms `u`, the handle's heights, observer and scan parameters once the work queued on `s` is done
+// (the height cache must be current and ordered before `s`, as for shadow_field).  force: compute it anyway.
+static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
+{
+    vf_terrain::Viewshed &H = t->vs;
+    if (!H.have_observer) return fail(VF_ERR_INVALID, "no observer set (vf_terrain_set_viewshed)");
+    const size_t nv = (size_t)t->n * t->n;
+    if (!H.d_seen.p) {
+        if (H.d_seen.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "viewshed field allocation failed"); }
+        H.valid = false;
+    }
+    ViewshedPlan S;
+    viewshed_plan(t, u, S);
+    const float key[5] = { S.exag, S.eye_height, S.target_height, S.softness, S.bias };
+    if (!force && H.valid && H.height_gen == t->height_gen && H.key_ij[0] == S.io && H.key_ij[1] == S.jo && std::memcmp(key, H.key, sizeof key) == 0) return VF_OK;
+    H.valid = false;
+    const size_t ncmax = (size_t)4u * S.nchunks * S.nlines;
+    if (H.d_cmax.reserve(ncmax, ncmax) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "viewshed scan allocation failed"); }
+    // (the x-major quadrants in one launch, the z-major ones in another: a quadrant's chunks beyond its steps leave at once)
+    const uint32_t cx = (std::max(S.steps[0], S.steps[1]) + kShChunk - 1u) / kShChunk, cz = (std::max(S.steps[2], S.steps[3]) + kShChunk - 1u) / kShChunk;
+    const uint32_t groups = (S.nlines + kShLines - 1u) / kShLines;
+    const dim3 gx(cx, groups, 2), gz(cz, groups, 2), threads(256);
+    hipLaunchKernelGGL((k_viewshed_chunk_max<false>), gx, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
+    hipLaunchKernelGGL((k_viewshed_chunk_max<true>), gz, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
+    hipLaunchKernelGGL((k_viewshed_carry<0>), dim3((S.nlines + 255u) / 256u, 4), threads, 0, s, S, H.d_cmax.p);
+    hipLaunchKernelGGL((k_viewshed_seen<false>), gx, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_seen.p);
+    hipLaunchKernelGGL((k_viewshed_seen<true>), gz, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_seen.p);
+    VF_HIP_TRY(hipGetLastError());
+    std::memcpy(H.key, key, sizeof key);
+    H.key_ij[0] = S.io; H.key_ij[1] = S.jo;
+    H.height_gen = t->height_gen; H.valid = true; H.scans++;
+    return VF_OK;
+}
+
+// Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
+static void viewshed_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    const vf_terrain::Viewshed &H = t->vs;
+    ViewshedTint T = {};
+    T.seen = H.d_seen.p; T.decode = H.d_decode.p;
+    T.visible_rgba = H.visible_rgba; T.hidden_rgba = H.hidden_rgba;
+    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);   // (P.step, as the vertex stage forms the grid coordinates)
+    T.xo = -1.5f + (float)viewshed_index(t, H.ox, P.spacing) * step; T.zo = -1.5f + (float)viewshed_index(t, H.oz, P.spacing) * step;
+    const float R = H.radius / P.spacing;
+    T.RR = R * R; T.radius_on = H.radius > 0.0f ? 1u : 0u;
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_viewshed_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    hipLaunchKernelGGL((k_viewshed_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+}
+
+// The tint of a frame, on the draw stream behind its tile kernels (which stored the visibility) and the relight passes: the field
+// if it is stale, then the tint pass over the covered pixels
+static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    if (int rc = viewshed_field(t, t->inputs.u, s)) return rc;
+    viewshed_launch(t, s, P, V, redo, rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+static uint32_t pack_rgba8(const uint8_t c[4]) { return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24; }
+
+int vf_terrain_set_viewshed(vf_terrain *t, int enable, const float observer_xz[2], float eye_height, float target_height, float radius,
+                            const uint8_t visible_rgba[4], const uint8_t hidden_rgba[4], float softness, float bias)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    vf_terrain::Viewshed &H = t->vs;
+    if (!observer_xz) {                                        // forget the observer: off, and everything made for it is freed
+        if (enable) return fail(VF_ERR_INVALID, "a viewshed needs an observer");
+        VF_HIP_TRY(hipSetDevice(t->ctx->device));
+        VF_HIP_TRY(wait_frame(t));
+        if (H.enabled) t->inputs_gen++;
+        H.d_seen.release(); H.d_cmax.release(); H.d_decode.release();
+        const uint32_t scans = H.scans;
+        H = vf_terrain::Viewshed();
+        H.scans = scans;
+        return VF_OK;
+    }
+    if (!visible_rgba || !hidden_rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!(std::isfinite(observer_xz[0]) && std::isfinite(observer_xz[1]))) return fail(VF_ERR_INVALID, "the observer must be finite");
+    if (!(std::isfinite(eye_height) && eye_height >= 0.0f)) return fail(VF_ERR_INVALID, "eye_height must be a finite number >= 0");
+    if (!(std::isfinite(target_height) && target_height >= 0.0f)) return fail(VF_ERR_INVALID, "target_height must be a finite number >= 0");
+    if (!(std::isfinite(radius) && radius >= 0.0f)) return fail(VF_ERR_INVALID, "radius must be a finite number > 0, or 0 for none");
+    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
+    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "a viewshed needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) {
+        if (int rc = ensure_vis(t)) return rc;
+        if (!H.d_decode.p) {
+            if (H.d_decode.reserve(256, 256) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "viewshed allocation failed"); }
+            VF_HIP_TRY(hipMemcpy(H.d_decode.p, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    const uint32_t vis = pack_rgba8(visible_rgba), hid = pack_rgba8(hidden_rgba);
+    if (H.enabled != (enable != 0) || !H.have_observer || H.ox != observer_xz[0] || H.oz != observer_xz[1] || H.eye_height != eye_height
+        || H.target_height != target_height || H.radius != radius || H.softness != softness || H.bias != bias || H.visible_rgba != vis || H.hidden_rgba != hid)
+        t->inputs_gen++;
+    H.enabled = enable != 0; H.have_observer = true;
+    H.ox = observer_xz[0]; H.oz = observer_xz[1];
+    H.eye_height = eye_height; H.target_height = target_height; H.radius = radius; H.softness = softness; H.bias = bias;
+    H.visible_rgba = vis; H.hidden_rgba = hid;
+    return VF_OK;
+}
+
+int vf_terrain_read_viewshed_field(vf_terrain *t, float *seen)
+{
+    if (!t || !seen) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->vs.have_observer) return fail(VF_ERR_INVALID, "no observer set (vf_terrain_set_viewshed)");
+    return field_out(t, 2, seen, nullptr, nullptr);
+}
+
+int vf_terrain_viewshed_field_device(vf_terrain *t, float *dev_seen, void *stream)
+{
+    if (!t || !dev_seen) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->vs.have_observer) return fail(VF_ERR_INVALID, "no observer set (vf_terrain_set_viewshed)");
+    return field_out(t, 2, nullptr, dev_seen, stream);
+}
+
+int vf_terrain_viewshed_info(vf_terrain *t, vf_viewshed_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::Viewshed &H = t->vs;
+    *out = vf_viewshed_info();
+    out->enabled = H.enabled ? 1 : 0; out->has_observer = H.have_observer ? 1 : 0;
+    out->eye_height = H.eye_height; out->target_height = H.target_height; out->radius = H.radius; out->softness = H.softness; out->bias = H.bias;
+    for (int k = 0; k < 4; ++k) { out->visible_rgba[k] = (uint8_t)(H.visible_rgba >> (8 * k)); out->hidden_rgba[k] = (uint8_t)(H.hidden_rgba >> (8 * k)); }
+    if (!H.have_observer) return VF_OK;
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (int rc = ct_heights_current(t)) return rc;
+    ViewshedPlan S;
+    viewshed_plan(t, t->inputs.u, S);
+    const uint32_t bx = std::min(S.io >> 3, t->nb - 1u), by = std::min(S.jo >> 3, t->nb - 1u);   // (cached_height's place)
+    float h = 0.0f;
+    VF_HIP_TRY(hipMemcpyAsync(&h, t->d_hblk + (size_t)(by * t->nb + bx) * kBlockStride + (S.jo - 8u * by) * 9u + (S.io - 8u * bx), sizeof h,
+                              hipMemcpyDeviceToHost, t->ctx->stream));
+    VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    const float spacing = std::fmax(t->inputs.u[36], 1e-8f), step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    out->vertex[0] = S.io; out->vertex[1] = S.jo;
+    out->observer_xyz[0] = (-1.5f + (float)S.io * step) * spacing;
+    out->observer_xyz[1] = h * S.exag;
+    out->observer_xyz[2] = (-1.5f + (float)S.jo * step) * spacing;
+    out->eye_y = out->observer_xyz[1] + H.eye_height;
+    return VF_OK;
+}
+
+int vf_terrain_debug_viewshed_scans(vf_terrain *t, uint32_t *count)
+{
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    *count = t->vs.scans;
+    return VF_OK;
+}
+
+int vf_terrain_debug_viewshed_stage(vf_terrain *t, uint32_t repeats, float ms[2])
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->vs.have_observer || !t->vs.d_decode.p) return fail(VF_ERR_INVALID, "no viewshed: it needs an observer, and to have been enabled once");
+    if (repeats == 0) repeats = 1;
+    RelightStage G;
+    int rc = G.open(t);
+    if (rc != VF_OK) return rc;
+    float a = 0.0f, b = 0.0f;
+    // the field first (its last launch leaves what the tint pass reads)
+    hipError_t err = time_launches(G.s, repeats, a, [&](bool) { rc = viewshed_field(t, G.u, G.s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    if (err == hipSuccess) err = time_launches(G.s, repeats, b, [&](bool) { viewshed_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); return hipGetLastError(); });
+    if (rc != VF_OK) return rc;
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("viewshed diagnostics: ") + hipGetErrorString(err));
+    ms[0] = a; ms[1] = b;
     return VF_OK;
 }
 

@@ -694,6 +694,55 @@ public:
         check(rc);
         return out;
     }
+    // extension: viewshed analysis (argument rules: vulkan_forge_amd/_viewshed.py)
+    void set_viewshed(py::object observer, py::object enabled, py::object eye_height, py::object target_height, py::object radius,
+                      py::object visible_rgba, py::object hidden_rgba, py::object softness, py::object bias)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._viewshed").attr("viewshed_args")(observer, enabled, eye_height, target_height, radius,
+                                                                                           visible_rgba, hidden_rgba, softness, bias);
+        const float xz[2] = { a[1].cast<float>(), a[2].cast<float>() };
+        uint8_t vis[4], hid[4];
+        py::tuple tv = a[6].cast<py::tuple>(), th = a[7].cast<py::tuple>();
+        for (int k = 0; k < 4; ++k) { vis[k] = tv[k].cast<uint8_t>(); hid[k] = th[k].cast<uint8_t>(); }
+        Borrow b(busy);
+        check(vf_terrain_set_viewshed(t, a[0].cast<int>(), xz, a[3].cast<float>(), a[4].cast<float>(), a[5].cast<float>(), vis, hid,
+                                      a[8].cast<float>(), a[9].cast<float>()));
+        frame_current = false;
+    }
+    void clear_viewshed()
+    {
+        Borrow b(busy);
+        check(vf_terrain_set_viewshed(t, 0, nullptr, 0.0f, 0.0f, 0.0f, nullptr, nullptr, 1.0f, 0.0f));
+        frame_current = false;
+    }
+    py::array_t<float> viewshed_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_viewshed_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::object viewshed_info()
+    {
+        Borrow b(busy);
+        vf_viewshed_info v;
+        check(vf_terrain_viewshed_info(t, &v));
+        return py::module_::import("vulkan_forge_amd._viewshed").attr("viewshed_info")(
+            v.enabled, v.has_observer, py::make_tuple(v.vertex[0], v.vertex[1]), py::make_tuple(v.observer_xyz[0], v.observer_xyz[1], v.observer_xyz[2]),
+            v.eye_y, v.eye_height, v.target_height, v.radius, v.softness, v.bias,
+            py::make_tuple(v.visible_rgba[0], v.visible_rgba[1], v.visible_rgba[2], v.visible_rgba[3]),
+            py::make_tuple(v.hidden_rgba[0], v.hidden_rgba[1], v.hidden_rgba[2], v.hidden_rgba[3]));
+    }
+    uint32_t debug_viewshed_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_viewshed_scans(t, &count));
+        return count;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1063,6 +1112,20 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "None while mipmaps are off, else dict(levels, sizes=[(w, h), ...], bias, bytes, builds); levels 0 without a drape.")
         .def("read_drape_level", &T::read_drape_level, py::arg("level"),
              "Level 1 <= level < levels of the pyramid as (h, w, 4) float16: premultiplied linear (r, g, b, a).  Builds it if stale.")
+        .def("set_viewshed", &T::set_viewshed, py::arg("observer"), py::kw_only(), py::arg("enabled") = true, py::arg("eye_height") = VF_VIEWSHED_EYE_HEIGHT,
+             py::arg("target_height") = VF_VIEWSHED_TARGET_HEIGHT, py::arg("radius") = py::none(), py::arg("visible_rgba") = py::make_tuple(64, 255, 96, 96),
+             py::arg("hidden_rgba") = py::make_tuple(0, 0, 0, 0), py::arg("softness") = VF_VIEWSHED_SOFTNESS, py::arg("bias") = VF_VIEWSHED_BIAS,
+             "Viewshed analysis (DESIGN.md 4l): tint the frame by what an observer sees.  observer = (x, z) in the overlays' world frame\n"
+             "(the one add_points takes), snapped to the nearest grid vertex; eye_height and target_height are in the units of\n"
+             "y = h * exag; radius (world units) limits the tint to a disc around the observer, None: everywhere.  The tint is flat:\n"
+             "hidden_rgba over hidden ground, visible_rgba over seen ground, each with its alpha.  Every parameter is stored by every\n"
+             "call, also one that disables, and steers viewshed_field() too.")
+        .def("clear_viewshed", &T::clear_viewshed, "Forget the observer: the viewshed is off, its parameters are the defaults again, its buffers are freed.")
+        .def("viewshed_field", &T::viewshed_field, "(grid, grid) float32, row j = z index, column i = x index: 1 = seen from the observer, 0 = hidden.")
+        .def("viewshed_info", &T::viewshed_info,
+             "dict(enabled, vertex (i, j), observer_xyz (world), eye_y, eye_height, target_height, radius, visible_rgba, hidden_rgba,\n"
+             "softness, bias); vertex, observer_xyz and eye_y are None before an observer is set.")
+        .def("debug_viewshed_scans", &T::debug_viewshed_scans)
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
