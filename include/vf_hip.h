@@ -689,6 +689,58 @@ int vf_terrain_viewshed_info(vf_terrain *t, vf_viewshed_info *out);
 int vf_terrain_debug_viewshed_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
 int vf_terrain_debug_viewshed_scans(vf_terrain *t, uint32_t *count);
 
+/* ---- cumulative viewsheds: how many of N observers see each vertex, and a tint of the frame ---------
+ * The count field is one float32 per grid vertex, (grid, grid) row-major as the viewshed field: count in [0, N], the sum over the
+ * observers of each one's seen value.  Many observers per handle: observers_xz = count pairs (x, z) in the overlays' world frame, each
+ * snapped to a grid vertex as vf_terrain_set_viewshed snaps its one; two observers on one vertex both count.  eye_height,
+ * target_height, softness and bias are shared by all observers and mean what they mean there.  Each observer's field is the viewshed
+ * field of that observer, bit for bit; it enters the sum as q = rint(seen * 65536), an unsigned 32-bit integer, so the sum does not
+ * depend on the order of the observers or on how they are batched, and count = (float)sum / 65536.  radius > 0 (world units): an
+ * observer counts only for the vertices within the radius of its own vertex, and no line is walked further than that; 0: no limit.
+ * The arithmetic is fixed bit for bit.  The field is computed by the first tinted frame or field call that needs it and
+ * again only after the heights, the exaggeration, the observers' vertices, eye_height, target_height, softness, bias or (with a
+ * radius) the radius in cells have changed -- not for the colours, the camera or the sun.
+ *
+ * vf_terrain_set_cumulative_viewshed: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then
+ * (behind the shadow, ambient and drape passes, and behind the single observer's tint if that is on too) blends over every covered
+ * pixel low_rgba with coverage 1 - s and high_rgba with coverage s, s the interpolated count / N, as vf_terrain_set_viewshed blends
+ * its hidden and visible colours.  Overlays composite afterwards; geometry buffers and the diagnostics frames are unaffected.
+ * 1 <= count <= 65535, observers finite, eye_height >= 0, target_height >= 0, radius >= 0, softness > 0, bias >= 0, all finite, else
+ * VF_ERR_INVALID and nothing changes.  Whole-frame handles only: enabling on a band- or tile-sharded handle, sharding a handle with a
+ * cumulative viewshed enabled, and vf_terrain_render_batch / _batch_host on such a handle are VF_ERR_INVALID and change nothing.  The
+ * parameters are stored also with enable == 0 (the field calls below use them).  observers_xz == NULL (with enable == 0): the
+ * observers are forgotten, the defaults are back and everything made for them is freed.  The setting survives height uploads.  A
+ * handle that never calls any of these allocates and launches nothing for them.
+ * vf_terrain_read_cumulative_viewshed_field: the count field for the current heights, uniforms, observers and parameters into host
+ * memory (grid * grid floats), whether or not the cumulative viewshed is enabled for drawing; VF_ERR_INVALID before observers are set.
+ * vf_terrain_cumulative_viewshed_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's
+ * stream); later calls on the handle are ordered behind the copy by the library.
+ * vf_terrain_cumulative_viewshed_info: the setting, N, and the number of observers a launch took in the last computation (0 before it).
+ * vf_terrain_read_cumulative_viewshed_vertices: the observers' vertices (i, j) for the current uniforms, count pairs of uint32. */
+#define VF_CUMULATIVE_VIEWSHED_MAX_OBSERVERS 65535u
+#define VF_CUMULATIVE_VIEWSHED_HIGH_RGBA 0xA060FF40u   /* (64, 255, 96, 160) as r | g << 8 | b << 16 | a << 24 */
+#define VF_CUMULATIVE_VIEWSHED_LOW_RGBA 0x00000000u    /* (0, 0, 0, 0): ground that nobody sees keeps the frame's colour */
+typedef struct vf_cumulative_viewshed_info {
+    int32_t enabled;
+    uint32_t count;           /* N; 0: no observers set */
+    uint32_t batch;           /* observers per launch in the last computation */
+    float eye_height, target_height, radius /* 0: none */, softness, bias;
+    uint8_t high_rgba[4], low_rgba[4];
+} vf_cumulative_viewshed_info;
+int vf_terrain_set_cumulative_viewshed(vf_terrain *t, int enable, const float *observers_xz /* count x 2 */, uint32_t count, float eye_height,
+                                       float target_height, float radius, const uint8_t high_rgba[4], const uint8_t low_rgba[4], float softness,
+                                       float bias);
+int vf_terrain_read_cumulative_viewshed_field(vf_terrain *t, float *count);
+int vf_terrain_cumulative_viewshed_field_device(vf_terrain *t, float *dev_count, void *stream);
+int vf_terrain_cumulative_viewshed_info(vf_terrain *t, vf_cumulative_viewshed_info *out);
+int vf_terrain_read_cumulative_viewshed_vertices(vf_terrain *t, uint32_t *vertices /* count x 2 */);
+/* diagnostics: the number of observers a launch takes (0: as many as the memory budget for the carries holds; the next call computes
+ * the field again); how many times the handle has computed its field so far (the diagnostic launches are not counted); and the
+ * average time (HIP events) of `repeats` computations of the field, after one warm-up. */
+int vf_terrain_debug_cumulative_viewshed_batch(vf_terrain *t, uint32_t batch);
+int vf_terrain_debug_cumulative_viewshed_scans(vf_terrain *t, uint32_t *count);
+int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

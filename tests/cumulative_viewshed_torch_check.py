@@ -1,0 +1,52 @@
+"""vf_terrain_cumulative_viewshed_field_device into a torch tensor on a stream of the caller's equals
+vf_terrain_read_cumulative_viewshed_field and the CPU model (run by tests/test_gpu_cumulative_viewshed.py in a process of its own)."""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(HERE, "overlay_model"))
+sys.path.insert(0, os.path.join(HERE, "cumulative_viewshed_model"))
+
+
+def main():
+    import torch                                           # before the library: one HIP runtime per process
+    import oracle
+    import cumulative_viewshed_model as cvm
+    from overlay_scenes import CAMERAS, heights
+    from vulkan_forge_amd import cabi
+    W, H, grid = 320, 200, 257
+    h = heights(3)
+    t = cabi.Terrain(W, H, grid, np.zeros(1024, np.uint8))
+    t.set_height(h)
+    params = dict(eye_height=0.4, target_height=0.02, softness=0.05, bias=0.01)
+    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    t.set_uniforms(u)
+    dev = torch.device("cuda")
+    stream = torch.cuda.Stream()
+    # a corner, an edge, an inner vertex, a position outside the grid, and ten more
+    observers = np.concatenate([np.array([(-1.5, 1.5), (0.3, -1.5), (0.41, -0.87), (-4.0, 9.0)], np.float32),
+                                np.random.default_rng(2).uniform(-1.5, 1.5, (10, 2)).astype(np.float32)])
+    for radius, batch in ((None, 0), (0.9, 3)):
+        t.cumulative_viewshed_batch(batch)
+        t.set_cumulative_viewshed(observers, enabled=False, radius=radius, **params)
+        count = torch.full((grid, grid), -1.0, dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(stream):
+            t.cumulative_viewshed_field_device(count.data_ptr(), stream.cuda_stream)
+            highest = count.max()                          # consumed on the device, behind the copy
+        stream.synchronize()
+        got = count.cpu().numpy()
+        want = cvm.field(u, h, grid, observers, radius=radius, **params)[0]
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), radius
+        assert np.array_equal(t.cumulative_viewshed_field().view(np.uint32), want.view(np.uint32)), radius
+        assert float(highest) == float(want.max()) and (want < len(observers)).any() and (want > 0).any()
+    assert t.lib.vf_terrain_cumulative_viewshed_field_device(t.t, None, None) == cabi.VF_ERR_INVALID
+    t.close()
+    print("CUMULATIVE VIEWSHED TORCH OK")
+
+
+if __name__ == "__main__":
+    main()

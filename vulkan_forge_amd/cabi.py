@@ -39,6 +39,9 @@ SYMBOLS = [
     "vf_terrain_set_drape_mips", "vf_terrain_drape_mip_info", "vf_terrain_read_drape_level", "vf_terrain_debug_drape_mip_build",
     "vf_terrain_set_viewshed", "vf_terrain_read_viewshed_field", "vf_terrain_viewshed_field_device", "vf_terrain_viewshed_info",
     "vf_terrain_debug_viewshed_stage", "vf_terrain_debug_viewshed_scans",
+    "vf_terrain_set_cumulative_viewshed", "vf_terrain_read_cumulative_viewshed_field", "vf_terrain_cumulative_viewshed_field_device",
+    "vf_terrain_cumulative_viewshed_info", "vf_terrain_read_cumulative_viewshed_vertices", "vf_terrain_debug_cumulative_viewshed_batch",
+    "vf_terrain_debug_cumulative_viewshed_scans", "vf_terrain_debug_cumulative_viewshed_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -63,6 +66,11 @@ class ViewshedInfo(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("has_observer", C.c_int32), ("vertex", C.c_uint32 * 2), ("observer_xyz", C.c_float * 3), ("eye_y", C.c_float),
                 ("eye_height", C.c_float), ("target_height", C.c_float), ("radius", C.c_float), ("softness", C.c_float), ("bias", C.c_float),
                 ("visible_rgba", C.c_uint8 * 4), ("hidden_rgba", C.c_uint8 * 4)]
+
+
+class CumulativeViewshedInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("count", C.c_uint32), ("batch", C.c_uint32), ("eye_height", C.c_float), ("target_height", C.c_float),
+                ("radius", C.c_float), ("softness", C.c_float), ("bias", C.c_float), ("high_rgba", C.c_uint8 * 4), ("low_rgba", C.c_uint8 * 4)]
 
 
 DIST_UNIQUE_ID_BYTES = 128
@@ -162,6 +170,14 @@ _PROTOS = {
     "vf_terrain_viewshed_info": (_i, [_vp, C.POINTER(ViewshedInfo)]),
     "vf_terrain_debug_viewshed_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_terrain_debug_viewshed_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_set_cumulative_viewshed": (_i, [_vp, _i, _vp, _u32, _f, _f, _f, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _f, _f]),
+    "vf_terrain_read_cumulative_viewshed_field": (_i, [_vp, _vp]),
+    "vf_terrain_cumulative_viewshed_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_cumulative_viewshed_info": (_i, [_vp, C.POINTER(CumulativeViewshedInfo)]),
+    "vf_terrain_read_cumulative_viewshed_vertices": (_i, [_vp, _vp]),
+    "vf_terrain_debug_cumulative_viewshed_batch": (_i, [_vp, _u32]),
+    "vf_terrain_debug_cumulative_viewshed_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_debug_cumulative_viewshed_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -623,6 +639,61 @@ class Terrain:
         n = _u32()
         self._check(self.lib.vf_terrain_debug_viewshed_scans(self.t, C.byref(n)))
         return n.value
+
+    def set_cumulative_viewshed(self, observers, *, enabled=True, eye_height=0.05, target_height=0.0, radius=None, high_rgba=(64, 255, 96, 160),
+                                low_rgba=(0, 0, 0, 0), softness=0.02, bias=0.002):
+        """Cumulative viewshed: how many of the observers, (N, 2) points (x, z) of the overlays' world frame, see each
+        vertex, as a tint of the frame.  Every parameter is stored by every call, also one that disables, and steers
+        cumulative_viewshed_field() too."""
+        from ._cumulative_viewshed import cumulative_viewshed_args
+        en, obs, eye, tgt, rad, high, low, soft, bias = cumulative_viewshed_args(observers, enabled, eye_height, target_height, radius, high_rgba,
+                                                                                 low_rgba, softness, bias)
+        self._check(self.lib.vf_terrain_set_cumulative_viewshed(self.t, en, obs.ctypes.data, obs.shape[0], eye, tgt, rad, (C.c_uint8 * 4)(*high),
+                                                                (C.c_uint8 * 4)(*low), soft, bias))
+
+    def clear_cumulative_viewshed(self):
+        """Forget the observers: the cumulative viewshed is off, its parameters are the defaults again and its buffers are freed."""
+        self._check(self.lib.vf_terrain_set_cumulative_viewshed(self.t, 0, None, 0, 0.0, 0.0, 0.0, None, None, 1.0, 0.0))
+
+    def cumulative_viewshed_field(self):
+        """The count field for the current heights, uniforms, observers and parameters: (grid, grid) float32 in [0, N]."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_cumulative_viewshed_field(self.t, out.ctypes.data))
+        return out
+
+    def cumulative_viewshed_field_device(self, dev_count, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_cumulative_viewshed_field_device(self.t, dev_count, stream))
+
+    def cumulative_viewshed_info(self):
+        """dict: enabled, observers (N), batch, vertices ((N, 2) uint32, None before observers and uniforms are set), and the parameters."""
+        from ._cumulative_viewshed import cumulative_viewshed_info
+        v = CumulativeViewshedInfo()
+        self._check(self.lib.vf_terrain_cumulative_viewshed_info(self.t, C.byref(v)))
+        vertices = None
+        if v.count:
+            vertices = np.empty((v.count, 2), np.uint32)
+            if self.lib.vf_terrain_read_cumulative_viewshed_vertices(self.t, vertices.ctypes.data) != VF_OK:
+                vertices = None                                # (uniforms not set yet)
+        return cumulative_viewshed_info(v.enabled, v.count, v.batch, vertices, v.eye_height, v.target_height, v.radius, v.softness, v.bias,
+                                        tuple(v.high_rgba), tuple(v.low_rgba))
+
+    def cumulative_viewshed_batch(self, batch=0):
+        """Force the number of observers a launch takes (diagnostics); 0: from the memory budget again."""
+        self._check(self.lib.vf_terrain_debug_cumulative_viewshed_batch(self.t, int(batch)))
+
+    def cumulative_viewshed_scans(self):
+        """How many times the handle has computed its cumulative viewshed field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_cumulative_viewshed_scans(self.t, C.byref(n)))
+        return n.value
+
+    def cumulative_viewshed_stage(self, repeats=5):
+        """ms of one computation of the field, as timed launches of their own (diagnostics)."""
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_cumulative_viewshed_stage(self.t, int(repeats), C.byref(ms)))
+        return ms.value
 
     def set_drape(self, image, *, extent=None, opacity=1.0, filter="linear"):
         """Drape an image on the terrain as its albedo.  image: (ih, iw, 4) or (ih, iw, 3) uint8, sRGB bytes with

@@ -9,6 +9,7 @@
 #include "vf_drape.h"       // templates only
 #include "vf_relight.h"     // templates only: the shade pass of the three
 #include "vf_viewshed.h"    // templates only
+#include "vf_cumulative_viewshed.h"   // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -441,6 +442,28 @@ struct vf_terrain {
         uint32_t key_ij[2] = {};
         uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_viewshed_scans)
     } vs;
+    // cumulative viewsheds: buffers made by the first tinted frame or field read; the sums are formed again only when
+    // what they were made from has changed (not for the colours, the camera or the sun)
+    struct CumulativeViewshed {
+        bool enabled = false;
+        std::vector<float> xz;           // the observers in the overlays' world frame, (x, z) each; empty: none set
+        float eye_height = VF_VIEWSHED_EYE_HEIGHT, target_height = VF_VIEWSHED_TARGET_HEIGHT, radius = 0.0f;
+        float softness = VF_VIEWSHED_SOFTNESS, bias = VF_VIEWSHED_BIAS;
+        uint32_t high_rgba = VF_CUMULATIVE_VIEWSHED_HIGH_RGBA, low_rgba = VF_CUMULATIVE_VIEWSHED_LOW_RGBA;
+        uint32_t forced_batch = 0;       // vf_terrain_debug_cumulative_viewshed_batch; 0: from the memory budget
+        DevBuf<uint32_t> d_sum;          // n x n sums of q
+        DevBuf<float> d_count, d_frac;   // n x n: sum / 65536, and that over N
+        DevBuf<float> d_cmax;            // carries of a batch: B x 4 quadrants x nchunks x nlines
+        DevBuf<ViewshedPlan> d_plans;    // one per observer
+        DevBuf<float> d_decode;          // 256 sRGB8 -> linear
+        std::vector<ViewshedPlan> plans; // the host's copy of d_plans (the source of its upload)
+        bool valid = false;              // d_count / d_frac hold the field of `key`, `key_ij` and heights generation `height_gen`
+        uint64_t height_gen = 0;
+        float key[6] = {};               // exaggeration, eye_height, target_height, softness, bias, Rc (0: no radius)
+        std::vector<uint32_t> key_ij;    // the observers' vertices, (i, j) each
+        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_cumulative_viewshed_scans)
+        uint32_t batch = 0;              // the batch size of the last computation
+    } cv;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -828,6 +851,16 @@ static void drape_release(vf_terrain *t)
     t->dm.d_pyr.release(); t->dm.stale = true;              // (the pyramid goes with its image; the setting stays)
 }
 
+// the cumulative viewshed: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced batch size stay
+static void cumulative_release(vf_terrain *t)
+{
+    vf_terrain::CumulativeViewshed &H = t->cv;
+    H.d_sum.release(); H.d_count.release(); H.d_frac.release(); H.d_cmax.release(); H.d_plans.release(); H.d_decode.release();
+    const uint32_t scans = H.scans, forced = H.forced_batch;
+    H = vf_terrain::CumulativeViewshed();
+    H.scans = scans; H.forced_batch = forced;
+}
+
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
@@ -905,6 +938,7 @@ void vf_terrain_destroy(vf_terrain *t)
     for (void *p : ptrs) if (p) (void)hipFree(p);
     t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release(); t->am.d_sky.release();
     t->vs.d_seen.release(); t->vs.d_cmax.release(); t->vs.d_decode.release();
+    cumulative_release(t);
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -1076,6 +1110,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->am.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     if (t->dr.iw && nranks != 1) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     if (t->vs.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
+    if (t->cv.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1202,6 +1237,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->am.enabled) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
+    if (t->cv.enabled) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1573,6 +1609,7 @@ static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
                         bool shadows, bool ambient);
 
 static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
@@ -1582,7 +1619,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool drape = t->dr.iw != 0u && !diag;
     const Relight drape_pass = t->dm.enabled ? kDrapeMip : kDrape;   // (through the mip pyramid when mipmaps are on)
     const bool viewshed = t->vs.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed;
+    const bool cumulative = t->cv.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1644,6 +1682,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
         const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, drape_pass, shadows, ambient);
         if (drc != VF_OK) return drc;
+    }
+    if (cumulative && ntiles) {                            // the cumulative viewshed's tint: behind the single observer's
+        const int crc = cumulative_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        if (crc != VF_OK) return crc;
     }
     if (viewshed && ntiles) {                              // the viewshed tint: behind the relight passes, in front of the overlays
         const int vrc = viewshed_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
@@ -1771,6 +1813,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
+    if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1791,6 +1834,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
+    if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2794,16 +2838,19 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
 // to `host`, or to `dev` behind the work on `stream` (NULL: the handle's)
 static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 
-static int field_out(vf_terrain *t, int which /* 0 lit, 1 sky, 2 seen */, float *host, float *dev, void *stream)
+static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
+
+static int field_out(vf_terrain *t, int which /* 0 lit, 1 sky, 2 seen, 3 count */, float *host, float *dev, void *stream)
 {
     const bool sky = which == 1;
     if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     if (int rc = ct_heights_current(t)) return rc;
     if (which == 2) { if (int rc = viewshed_field(t, t->inputs.u, t->ctx->stream)) return rc; }
+    else if (which == 3) { if (int rc = cumulative_field(t, t->inputs.u, t->ctx->stream)) return rc; }
     else if (int rc = relight_fields(t, t->inputs.u, t->ctx->stream, !sky, sky)) return rc;
     VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    const float *field = which == 2 ? t->vs.d_seen.p : sky ? t->am.d_sky.p : t->sh.d_lit.p;
+    const float *field = which == 3 ? t->cv.d_count.p : which == 2 ? t->vs.d_seen.p : sky ? t->am.d_sky.p : t->sh.d_lit.p;
     const size_t bytes = (size_t)t->n * t->n * sizeof(float);
     if (host) { VF_HIP_TRY(hipMemcpy(host, field, bytes, hipMemcpyDeviceToHost)); return VF_OK; }
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
@@ -3261,6 +3308,13 @@ static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool for
 }
 
 // Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
+static void tint_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, const ViewshedTint &T)
+{
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_viewshed_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    hipLaunchKernelGGL((k_viewshed_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+}
+
 static void viewshed_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
     const vf_terrain::Viewshed &H = t->vs;
@@ -3271,9 +3325,7 @@ static void viewshed_launch(const vf_terrain *t, hipStream_t s, const FrameParam
     T.xo = -1.5f + (float)viewshed_index(t, H.ox, P.spacing) * step; T.zo = -1.5f + (float)viewshed_index(t, H.oz, P.spacing) * step;
     const float R = H.radius / P.spacing;
     T.RR = R * R; T.radius_on = H.radius > 0.0f ? 1u : 0u;
-    const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_viewshed_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
-    hipLaunchKernelGGL((k_viewshed_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    tint_launch(t, s, P, V, redo, rgba, T);
 }
 
 // The tint of a frame, on the draw stream behind its tile kernels (which stored the visibility) and the relight passes: the field
@@ -3396,6 +3448,244 @@ int vf_terrain_debug_viewshed_stage(vf_terrain *t, uint32_t repeats, float ms[2]
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("viewshed diagnostics: ") + hipGetErrorString(err));
     ms[0] = a; ms[1] = b;
+    return VF_OK;
+}
+
+// ---- cumulative viewsheds (vf_cumulative_viewshed.h) ------------------------------------
+
+// The carries of a batch may take this many floats (32 MiB).  Not more: every observer of a batch reads the one height cache, and
+// at grid 4096 carries of 134 MB and more push it out of the last-level cache between the stages (4 observers per
+// launch there take 28 ms for 64 observers, 32 take 38 ms); at smaller grids the batch is still 64 observers and more.
+constexpr size_t kCvCarryFloats = (size_t)8u << 20;
+constexpr uint32_t kCvMaxBatch = 4096;                        // (the carry stage's grid holds four blocks rows per observer: 4 B <= 65535)
+
+// Rc = radius / (spacing step) of the uniforms `u`; only with a radius
+static float cumulative_rc(const vf_terrain *t, const float *u)
+{
+    const float spacing = std::fmax(u[36], 1e-8f), step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    return t->cv.radius / (spacing * step);
+}
+
+// the steps of a line that can lie within Rc: min(L, ceil(Rc)), at least 1
+static uint32_t cumulative_reach(const vf_terrain *t, float Rc)
+{
+    const uint32_t L = t->n - 1u;
+    if (!(Rc < (float)L)) return L;
+    return std::max(1u, (uint32_t)std::ceil(Rc));
+}
+
+// observers per launch: as many as the budget for the carries holds
+static uint32_t cumulative_batch(const vf_terrain *t, uint32_t N, uint32_t nchunks)
+{
+    const size_t per = (size_t)4u * nchunks * (2u * (t->n - 1u) + 1u);
+    const size_t B = t->cv.forced_batch ? t->cv.forced_batch : std::max<size_t>(kCvCarryFloats / per, 1u);
+    return (uint32_t)std::min<size_t>(std::min<size_t>(B, kCvMaxBatch), N);
+}
+
+// d_count and d_frac hold the field of the uniforms `u`, the handle's heights, observers and scan parameters once the work queued on
+// `s` is done (the height cache must be current and ordered before `s`).  force: compute it anyway.
+static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
+{
+    vf_terrain::CumulativeViewshed &H = t->cv;
+    const uint32_t N = (uint32_t)(H.xz.size() / 2u);
+    if (!N) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
+    const size_t nv = (size_t)t->n * t->n;
+    if (!H.d_sum.p || !H.d_count.p || !H.d_frac.p) {
+        if (H.d_sum.reserve(nv, nv) != hipSuccess || H.d_count.reserve(nv, nv) != hipSuccess || H.d_frac.reserve(nv, nv) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(VF_ERR_NOMEM, "cumulative viewshed field allocation failed");
+        }
+        H.valid = false;
+    }
+    const float spacing = std::fmax(u[36], 1e-8f);
+    const bool ranged = H.radius > 0.0f;
+    const float Rc = ranged ? cumulative_rc(t, u) : 0.0f;
+    const uint32_t L = t->n - 1u, reach = ranged ? cumulative_reach(t, Rc) : L;
+    std::vector<uint32_t> ij((size_t)2u * N);
+    for (uint32_t o = 0; o < N; ++o) {
+        ij[2u * o] = viewshed_index(t, H.xz[2u * o], spacing);
+        ij[2u * o + 1u] = viewshed_index(t, H.xz[2u * o + 1u], spacing);
+    }
+    const float key[6] = { u[38], H.eye_height, H.target_height, H.softness, H.bias, ranged ? Rc : -1.0f };
+    if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0 && ij == H.key_ij) return VF_OK;
+    H.valid = false;
+    const uint32_t nlines = 2u * L + 1u, nchunks = (reach + kShChunk - 1u) / kShChunk;
+    const uint32_t B = cumulative_batch(t, N, nchunks);
+    const size_t ncmax = (size_t)B * 4u * nchunks * nlines;
+    if (H.d_cmax.reserve(ncmax, ncmax) != hipSuccess || H.d_plans.reserve(N, N) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VF_ERR_NOMEM, "cumulative viewshed scan allocation failed");
+    }
+    H.plans.resize(N);
+    for (uint32_t o = 0; o < N; ++o) {                         // viewshed_plan's frame of reference, cut at the range
+        ViewshedPlan &S = H.plans[o];
+        S.n = t->n; S.nb = t->nb;
+        S.io = ij[2u * o]; S.jo = ij[2u * o + 1u];
+        S.L = L; S.nlines = nlines; S.nchunks = nchunks;
+        S.steps[0] = std::min(L - S.io, reach); S.steps[1] = std::min(S.io, reach);
+        S.steps[2] = std::min(L - S.jo, reach); S.steps[3] = std::min(S.jo, reach);
+        S.exag = u[38]; S.eye_height = H.eye_height; S.target_height = H.target_height; S.softness = H.softness; S.bias = H.bias;
+    }
+    VF_HIP_TRY(hipMemcpyAsync(H.d_plans.p, H.plans.data(), (size_t)N * sizeof(ViewshedPlan), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
+    VF_HIP_TRY(hipMemsetAsync(H.d_sum.p, 0, nv * sizeof(uint32_t), s));
+    const float RR = Rc * Rc;
+    const uint32_t groups = (nlines + kShLines - 1u) / kShLines;
+    const dim3 threads(256);
+    for (uint32_t b0 = 0; b0 < N; b0 += B) {                   // five launches per batch; the batches share the carries, in stream order
+        const uint32_t nb = std::min(B, N - b0);
+        uint32_t sx = 0, sz = 0;
+        for (uint32_t o = b0; o < b0 + nb; ++o) {
+            sx = std::max(sx, std::max(H.plans[o].steps[0], H.plans[o].steps[1]));
+            sz = std::max(sz, std::max(H.plans[o].steps[2], H.plans[o].steps[3]));
+        }
+        // (a quadrant's chunks beyond its steps leave at once)
+        const dim3 gx((sx + kShChunk - 1u) / kShChunk, groups, 2u * nb), gz((sz + kShChunk - 1u) / kShChunk, groups, 2u * nb);
+        const ViewshedPlan *plans = H.d_plans.p + b0;
+        if (gx.x) hipLaunchKernelGGL((k_cumulative_chunk_max<false>), gx, threads, 0, s, plans, (const float *)t->d_hblk, H.d_cmax.p);
+        if (gz.x) hipLaunchKernelGGL((k_cumulative_chunk_max<true>), gz, threads, 0, s, plans, (const float *)t->d_hblk, H.d_cmax.p);
+        hipLaunchKernelGGL((k_cumulative_carry<0>), dim3((nlines + 255u) / 256u, 4u * nb), threads, 0, s, plans, H.d_cmax.p);
+        // (with no x-major chunk the observer's own vertex would go without its 1: n >= 2 gives every observer a step on both axes)
+        if (gx.x) hipLaunchKernelGGL((k_cumulative_seen<false>), gx, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.d_sum.p);
+        if (gz.x) hipLaunchKernelGGL((k_cumulative_seen<true>), gz, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.d_sum.p);
+    }
+    hipLaunchKernelGGL((k_cumulative_finish<0>), dim3((uint32_t)((nv + 255u) / 256u)), threads, 0, s, (const uint32_t *)H.d_sum.p, (uint32_t)nv, (float)N, H.d_count.p, H.d_frac.p);
+    VF_HIP_TRY(hipGetLastError());
+    std::memcpy(H.key, key, sizeof key);
+    H.key_ij.swap(ij);
+    H.height_gen = t->height_gen; H.valid = true; H.scans++; H.batch = B;
+    return VF_OK;
+}
+
+static void cumulative_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    const vf_terrain::CumulativeViewshed &H = t->cv;
+    ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
+    T.seen = H.d_frac.p; T.decode = H.d_decode.p;
+    T.visible_rgba = H.high_rgba; T.hidden_rgba = H.low_rgba;
+    tint_launch(t, s, P, V, redo, rgba, T);
+}
+
+// The cumulative viewshed's tint of a frame: the field if it is stale, then k_viewshed_tint on f = count / N
+static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    if (int rc = cumulative_field(t, t->inputs.u, s)) return rc;
+    cumulative_launch(t, s, P, V, redo, rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_cumulative_viewshed(vf_terrain *t, int enable, const float *observers_xz, uint32_t count, float eye_height, float target_height,
+                                       float radius, const uint8_t high_rgba[4], const uint8_t low_rgba[4], float softness, float bias)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    vf_terrain::CumulativeViewshed &H = t->cv;
+    if (!observers_xz) {                                       // forget the observers: off, and everything made for them is freed
+        if (enable) return fail(VF_ERR_INVALID, "a cumulative viewshed needs observers");
+        VF_HIP_TRY(hipSetDevice(t->ctx->device));
+        VF_HIP_TRY(wait_frame(t));
+        if (H.enabled) t->inputs_gen++;
+        cumulative_release(t);
+        return VF_OK;
+    }
+    if (!high_rgba || !low_rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    if (count < 1u || count > VF_CUMULATIVE_VIEWSHED_MAX_OBSERVERS) return fail(VF_ERR_INVALID, "a cumulative viewshed takes 1 to 65535 observers");
+    for (size_t k = 0; k < (size_t)2u * count; ++k)
+        if (!std::isfinite(observers_xz[k])) return fail(VF_ERR_INVALID, "the observers must be finite");
+    if (!(std::isfinite(eye_height) && eye_height >= 0.0f)) return fail(VF_ERR_INVALID, "eye_height must be a finite number >= 0");
+    if (!(std::isfinite(target_height) && target_height >= 0.0f)) return fail(VF_ERR_INVALID, "target_height must be a finite number >= 0");
+    if (!(std::isfinite(radius) && radius >= 0.0f)) return fail(VF_ERR_INVALID, "radius must be a finite number > 0, or 0 for none");
+    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
+    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "a cumulative viewshed needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) {
+        if (int rc = ensure_vis(t)) return rc;
+        if (!H.d_decode.p) {
+            if (H.d_decode.reserve(256, 256) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "cumulative viewshed allocation failed"); }
+            VF_HIP_TRY(hipMemcpy(H.d_decode.p, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    const uint32_t hi = pack_rgba8(high_rgba), lo = pack_rgba8(low_rgba);
+    std::vector<float> xz(observers_xz, observers_xz + (size_t)2u * count);
+    if (H.enabled != (enable != 0) || H.xz != xz || H.eye_height != eye_height || H.target_height != target_height || H.radius != radius
+        || H.softness != softness || H.bias != bias || H.high_rgba != hi || H.low_rgba != lo)
+        t->inputs_gen++;
+    H.enabled = enable != 0;
+    H.xz.swap(xz);
+    H.eye_height = eye_height; H.target_height = target_height; H.radius = radius; H.softness = softness; H.bias = bias;
+    H.high_rgba = hi; H.low_rgba = lo;
+    return VF_OK;
+}
+
+int vf_terrain_read_cumulative_viewshed_field(vf_terrain *t, float *count)
+{
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->cv.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
+    return field_out(t, 3, count, nullptr, nullptr);
+}
+
+int vf_terrain_cumulative_viewshed_field_device(vf_terrain *t, float *dev_count, void *stream)
+{
+    if (!t || !dev_count) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->cv.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
+    return field_out(t, 3, nullptr, dev_count, stream);
+}
+
+int vf_terrain_cumulative_viewshed_info(vf_terrain *t, vf_cumulative_viewshed_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::CumulativeViewshed &H = t->cv;
+    *out = vf_cumulative_viewshed_info();
+    out->enabled = H.enabled ? 1 : 0; out->count = (uint32_t)(H.xz.size() / 2u); out->batch = H.batch;
+    out->eye_height = H.eye_height; out->target_height = H.target_height; out->radius = H.radius; out->softness = H.softness; out->bias = H.bias;
+    for (int k = 0; k < 4; ++k) { out->high_rgba[k] = (uint8_t)(H.high_rgba >> (8 * k)); out->low_rgba[k] = (uint8_t)(H.low_rgba >> (8 * k)); }
+    return VF_OK;
+}
+
+int vf_terrain_read_cumulative_viewshed_vertices(vf_terrain *t, uint32_t *vertices)
+{
+    if (!t || !vertices) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::CumulativeViewshed &H = t->cv;
+    if (H.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    const float spacing = std::fmax(t->inputs.u[36], 1e-8f);
+    for (size_t k = 0; k < H.xz.size(); ++k) vertices[k] = viewshed_index(t, H.xz[k], spacing);
+    return VF_OK;
+}
+
+int vf_terrain_debug_cumulative_viewshed_batch(vf_terrain *t, uint32_t batch)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->cv.forced_batch != batch) t->cv.valid = false;      // (the next call computes the field again, with this batch size)
+    t->cv.forced_batch = batch;
+    return VF_OK;
+}
+
+int vf_terrain_debug_cumulative_viewshed_scans(vf_terrain *t, uint32_t *count)
+{
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    *count = t->cv.scans;
+    return VF_OK;
+}
+
+int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->cv.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    if (repeats == 0) repeats = 1;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (int rc = ct_heights_current(t)) return rc;
+    hipStream_t s = t->ctx->stream;
+    const uint32_t scans = t->cv.scans;
+    int rc = VF_OK;
+    float a = 0.0f;
+    const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = cumulative_field(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    t->cv.scans = scans;
+    if (rc != VF_OK) return rc;
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("cumulative viewshed diagnostics: ") + hipGetErrorString(err));
+    *ms = a;
     return VF_OK;
 }
 

@@ -743,6 +743,64 @@ public:
         check(vf_terrain_debug_viewshed_scans(t, &count));
         return count;
     }
+    // extension: cumulative viewsheds (argument rules: vulkan_forge_amd/_cumulative_viewshed.py)
+    void set_cumulative_viewshed(py::object observers, py::object enabled, py::object eye_height, py::object target_height, py::object radius,
+                                 py::object high_rgba, py::object low_rgba, py::object softness, py::object bias)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._cumulative_viewshed").attr("cumulative_viewshed_args")(
+            observers, enabled, eye_height, target_height, radius, high_rgba, low_rgba, softness, bias);
+        auto obs = a[1].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+        uint8_t high[4], low[4];
+        py::tuple th = a[5].cast<py::tuple>(), tl = a[6].cast<py::tuple>();
+        for (int k = 0; k < 4; ++k) { high[k] = th[k].cast<uint8_t>(); low[k] = tl[k].cast<uint8_t>(); }
+        Borrow b(busy);
+        check(vf_terrain_set_cumulative_viewshed(t, a[0].cast<int>(), obs.data(), (uint32_t)obs.shape(0), a[2].cast<float>(), a[3].cast<float>(),
+                                                 a[4].cast<float>(), high, low, a[7].cast<float>(), a[8].cast<float>()));
+        frame_current = false;
+    }
+    void clear_cumulative_viewshed()
+    {
+        Borrow b(busy);
+        check(vf_terrain_set_cumulative_viewshed(t, 0, nullptr, 0, 0.0f, 0.0f, 0.0f, nullptr, nullptr, 1.0f, 0.0f));
+        frame_current = false;
+    }
+    py::array_t<float> cumulative_viewshed_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_cumulative_viewshed_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::object cumulative_viewshed_info()
+    {
+        Borrow b(busy);
+        vf_cumulative_viewshed_info v;
+        check(vf_terrain_cumulative_viewshed_info(t, &v));
+        py::object vertices = py::none();
+        if (v.count) {
+            py::array_t<uint32_t> a({ (py::ssize_t)v.count, (py::ssize_t)2 });
+            if (vf_terrain_read_cumulative_viewshed_vertices(t, a.mutable_data()) == VF_OK) vertices = a;   // (else: uniforms not set yet)
+        }
+        return py::module_::import("vulkan_forge_amd._cumulative_viewshed").attr("cumulative_viewshed_info")(
+            v.enabled, v.count, v.batch, vertices, v.eye_height, v.target_height, v.radius, v.softness, v.bias,
+            py::make_tuple(v.high_rgba[0], v.high_rgba[1], v.high_rgba[2], v.high_rgba[3]),
+            py::make_tuple(v.low_rgba[0], v.low_rgba[1], v.low_rgba[2], v.low_rgba[3]));
+    }
+    void debug_cumulative_viewshed_batch(uint32_t batch)
+    {
+        Borrow b(busy);
+        check(vf_terrain_debug_cumulative_viewshed_batch(t, batch));
+    }
+    uint32_t debug_cumulative_viewshed_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_cumulative_viewshed_scans(t, &count));
+        return count;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1126,6 +1184,25 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "dict(enabled, vertex (i, j), observer_xyz (world), eye_y, eye_height, target_height, radius, visible_rgba, hidden_rgba,\n"
              "softness, bias); vertex, observer_xyz and eye_y are None before an observer is set.")
         .def("debug_viewshed_scans", &T::debug_viewshed_scans)
+        .def("set_cumulative_viewshed", &T::set_cumulative_viewshed, py::arg("observers"), py::kw_only(), py::arg("enabled") = true,
+             py::arg("eye_height") = VF_VIEWSHED_EYE_HEIGHT, py::arg("target_height") = VF_VIEWSHED_TARGET_HEIGHT, py::arg("radius") = py::none(),
+             py::arg("high_rgba") = py::make_tuple(64, 255, 96, 160), py::arg("low_rgba") = py::make_tuple(0, 0, 0, 0),
+             py::arg("softness") = VF_VIEWSHED_SOFTNESS, py::arg("bias") = VF_VIEWSHED_BIAS,
+             "Cumulative viewshed (DESIGN.md 4m): tint the frame by how many of N observers see the ground.  observers = (N, 2) points\n"
+             "(x, z) in the overlays' world frame, 1 <= N <= 65535, each snapped to the nearest grid vertex; eye_height, target_height,\n"
+             "softness and bias are shared by all of them and mean what they mean for set_viewshed; radius (world units): an observer\n"
+             "counts only for the ground within it, None: everywhere.  The tint is flat: low_rgba where nobody sees the ground, high_rgba\n"
+             "where everybody does, blended by count / N in between.  Every parameter is stored by every call, also one that disables,\n"
+             "and steers cumulative_viewshed_field() too.")
+        .def("clear_cumulative_viewshed", &T::clear_cumulative_viewshed,
+             "Forget the observers: the cumulative viewshed is off, its parameters are the defaults again, its buffers are freed.")
+        .def("cumulative_viewshed_field", &T::cumulative_viewshed_field,
+             "(grid, grid) float32, row j = z index, column i = x index: the sum of the observers' seen values, in [0, N].")
+        .def("cumulative_viewshed_info", &T::cumulative_viewshed_info,
+             "dict(enabled, observers (N), batch, vertices ((N, 2) uint32 (i, j)), eye_height, target_height, radius, high_rgba, low_rgba,\n"
+             "softness, bias); vertices is None before observers are set.")
+        .def("debug_cumulative_viewshed_batch", &T::debug_cumulative_viewshed_batch, py::arg("batch") = 0)
+        .def("debug_cumulative_viewshed_scans", &T::debug_cumulative_viewshed_scans)
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
