@@ -329,6 +329,15 @@ int vf_terrain_frame_times(vf_terrain *t, float *tile_ms, float *period_ms, uint
  * launch order, 4 words: item code (local tile | strip << 20 | log2(strips) << 24 | depth slice << 27 | log2(slices) << 29), candidate blocks processed,
  * raster-phase time, raster+fragment time (10 ns ticks of the constant 100 MHz clock).  *count = items written. */
 int vf_terrain_debug_item_stats(vf_terrain *t, uint32_t *dst, uint32_t max_items, uint32_t *count);
+/* debug/tests (band masks): what the set-up pass left in the plan state the frame rendered last was drawn from, copied
+ * after a full wait.  Per block of the grid, row-major (by * blocks_per_side + bx): recs 8 words -- the pixel box as four int16
+ * {x0, y0, x1, y1} (x0 > x1: nothing to draw), flags, count, alive_even and alive_odd (64 bits each, low word first); masks
+ * VF_BAND_SLOTS x {even, odd} 64-bit words -- slot s: the alive primitives that reach a row of tiles r with r % VF_BAND_SLOTS == s;
+ * xy 81 x {X, Y} int32, the block's 9 x 9 snapped vertices (24.8 fixed point).  Any of the three may be NULL.  Blocks the frame's
+ * set-up pass did not visit (nothing of them can reach this shard's pixels: count 0, an empty box) keep whatever an earlier frame left.
+ * *count = blocks of the grid; VF_ERR_INVALID when max_blocks is smaller or nothing was rendered.  Host copies only. */
+#define VF_BAND_SLOTS 8u
+int vf_terrain_debug_band_masks(vf_terrain *t, uint32_t *recs, uint64_t *masks, int32_t *xy, uint32_t max_blocks, uint32_t *count);
 /* debug/tests: set the scheduling feedback the NEXT frame's plan reads, instead of whatever the machine measured.
  * Per local tile (storage order, ntiles = vf_terrain_local_tiles): tile_ticks[k] the tile's time in 10 ns ticks, strips_log2[k] the
  * log2 (0 .. 4) of the strips that time was "recorded" with, piece_ticks[64 k + p] the time of its piece p (NULL: all zero).

@@ -28,6 +28,7 @@ for cam in (("pose8", "pose0") if os.environ.get("VF_C5") else ("default", "fill
     div = lambda x, y: x / y if y else float("nan")
     print(f"   LANES busy per wave-level execution: pass A (classification) {div(lanes[1], lanes[2]):.1f} of 64;  pass B set-up (lanes with a triangle) {div(lanes[3], cnt[1]):.1f};  "
           f"line loop: {'group tests' if use else 'line trips'} {div(lanes[0], wv[0]):.1f}, stage 1 {div(cnt[6], wv[1]):.1f}, stage 2 {div(cnt[4], wv[2]):.1f}, paint {div(cnt[5], wv[3]):.1f};  occlusion loop of the classification {div(wv[5], wv[4]):.1f} (triangles per iteration)")
+    print(f"   BAND MASKS: alive primitives per pair (the tile row's slot of the block's masks) {div(lanes[1], live):.1f};  pass-A executions per pair {div(lanes[2], live):.3f}")
     for n, c in zip(["row list", "candidate tests", "wait for slowest wave", "scan + list fill", "hand-over + pull", "item record + tile state", "row mask", "-"], sub):
         print(f"      set-up: {n:22s} {100*c/tot:6.2f} %")
     print(f"      vertex: record wait {100*vsub[0]/tot:.2f} %  (one empty time stamp: {100*vsub[1]/tot:.2f} % = {vsub[1]/live:.0f} cycles per pair; every phase above holds one per boundary)  wait for the vertex records {100*vsub2[0]/tot:.2f} % = {vsub2[0]/live:.0f} cycles per pair  LDS staging {100*vsub2[1]/tot:.2f} %  alive-list compaction {100*(ph[2]-vsub.sum()-vsub2.sum())/tot:.2f} %")

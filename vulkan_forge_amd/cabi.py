@@ -26,7 +26,7 @@ SYMBOLS = [
     "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
     "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
     "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_set_layer_occlusion", "vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
-    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
+    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_band_masks", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
     "vf_terrain_debug_fragment_stage", "vf_host_alloc", "vf_host_free",
@@ -119,6 +119,7 @@ _PROTOS = {
     "vf_terrain_timings": (_i, [_vp, C.POINTER(Timings)]),
     "vf_terrain_frame_times": (_i, [_vp, _vp, _vp, _u32, C.POINTER(_u32)]),
     "vf_terrain_debug_item_stats": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
+    "vf_terrain_debug_band_masks": (_i, [_vp, _vp, _vp, _vp, _u32, C.POINTER(_u32)]),
     "vf_terrain_debug_set_plan_feedback": (_i, [_vp, _vp, _vp, _vp, _u32]),
     "vf_terrain_debug_plan_mode": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_debug_phase_cycles": (_i, [_vp, _vp, _u32]),
@@ -774,6 +775,20 @@ class Terrain:
         n = _u32()
         self._check(self.lib.vf_terrain_debug_item_stats(self.t, out.ctypes.data, cap, C.byref(n)))
         return out[:n.value]
+
+    def band_masks(self):
+        """Debug / tests (band masks): the set-up pass's output in the plan state the last frame was drawn from, per block
+        of the grid (row-major): dict(box (n, 4) int16 {x0, y0, x1, y1}, flags (n,), count (n,), alive_even (n,) u64, alive_odd (n,) u64,
+        masks (n, 8, 2) u64 [block, slot, even / odd], xy (n, 81, 2) int32 snapped vertices)."""
+        nb = (self.grid - 1 + 7) // 8
+        n = nb * nb
+        recs, masks, xy = np.zeros((n, 8), np.uint32), np.zeros((n, 8, 2), np.uint64), np.zeros((n, 81, 2), np.int32)
+        got = _u32()
+        self._check(self.lib.vf_terrain_debug_band_masks(self.t, recs.ctypes.data, masks.ctypes.data, xy.ctypes.data, n, C.byref(got)))
+        assert got.value == n
+        wide = recs[:, 4:8].copy().view(np.uint64)
+        return dict(box=recs[:, 0:2].copy().view(np.int16), flags=recs[:, 2].copy(), count=recs[:, 3].copy(),
+                    alive_even=wide[:, 0].copy(), alive_odd=wide[:, 1].copy(), masks=masks, xy=xy)
 
     def set_plan_feedback(self, tile_ticks, strips_log2=None, piece_ticks=None):
         """Debug / tests: the scheduling feedback the next frame's plan reads.  Per local tile: tile_ticks (n,) u32,

@@ -97,6 +97,16 @@ struct BlockRec {
 constexpr uint32_t kRecGeneric = 1u;
 static_assert(sizeof(BlockRec) == 32, "BlockRec is read with wide loads");
 
+// BAND MASKS.  Beside its record a block has kBandSlots pairs {even, odd} of 64-bit masks (ulonglong2, 128 bytes per block), written by
+// k_block_setup with the record: slot s holds the alive primitives whose pixel-centre rows py0 .. py1 (clamped to the target) reach a
+// row of tiles r -- pixel rows 64 r .. 64 r + 63 -- with r % kBandSlots == s.  A primitive that spans kBandSlots tile rows or more is in
+// every slot; the OR of a block's slots is alive_even / alive_odd.  The tile kernel reads the slot of its own tile row instead of the
+// record's masks: a superset of the primitives whose box holds a pixel centre of the tile, so its classification and raster, which test
+// every primitive against the tile themselves, see the same survivors in the same order and skip the others.
+// Eight slots: a block rarely spans more tile rows (C4: 8.6 on average at the default camera), and the fold then costs next to nothing.
+constexpr int kBandSlots = 8;
+static_assert((kBandSlots & (kBandSlots - 1)) == 0 && kBandSlots <= 8, "a power of two: the slot is the tile row's low bits; the set-up pass folds into a byte");
+
 // ---- deterministic sin / cos ---------------------------------------------------------------
 __device__ __forceinline__ float sin_poly(float r)
 {

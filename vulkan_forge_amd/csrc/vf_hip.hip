@@ -484,6 +484,7 @@ struct vf_terrain {
         VertexRec *vtx = nullptr;        // per block 81 x {X, Y, 1/w, h} (k_block_setup)
         BlockRec *recs = nullptr;        // per block: alive masks, exact pixel box
         ulonglong2 *gen = nullptr;       // per block: primitives that need the generic path (valid where the record says so)
+        ulonglong2 *band = nullptr;      // per block kBandSlots x {even, odd}: the alive masks per row of tiles (k_block_setup, with the records)
         uint32_t *seg_list = nullptr;    // 16-block segments with a block that reaches this shard's pixels (+ [nsegs] = their number)
         PixelBox *row_ranges = nullptr;  // per block row
         float4 *cap_seg = nullptr;       // per block: capsule axis (screen space)
@@ -503,7 +504,7 @@ struct vf_terrain {
         uint8_t *slab = nullptr;         // one allocation per plan state
         float u_used[32] = {};           // view + proj of the frame whose tile times sit in `feedback` (the plan looks them up through the camera motion)
         bool have_u_used = false;
-        // the stamp: geom_gen / height_gen the boxes, ranges, segment list, records, masks and vertex records were built from (0: none --
+        // the stamp: geom_gen / height_gen the boxes, ranges, segment list, records, masks, band masks and vertex records were built from (0: none --
         // never filled, or left half-written).  While both equal the live generations the plan reuses them (plan_frame).
         uint64_t geom_stamp = 0, height_stamp = 0;
     } ps[kPlanStates];
@@ -798,6 +799,7 @@ static hipError_t ensure_plan_state(vf_terrain *t, uint32_t k, hipStream_t zero_
     C.add((void **)&S.ranges, t->nblocks * sizeof(PixelBox));
     C.add((void **)&S.vtx, (size_t)t->nblocks * kBlockStride * sizeof(VertexRec));
     C.add((void **)&S.recs, (size_t)t->nblocks * sizeof(BlockRec));
+    C.add((void **)&S.band, (size_t)t->nblocks * kBandSlots * sizeof(ulonglong2));
     C.add((void **)&S.gen, (size_t)t->nblocks * sizeof(ulonglong2));
     C.add((void **)&S.row_ranges, t->nb * sizeof(PixelBox));
     C.add((void **)&S.cap_seg, t->nblocks * sizeof(float4));
@@ -1520,7 +1522,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
         // (one short-lived workgroup per possible segment -- those beyond the list's length leave at once: workgroups that come and go
         //  share the CUs with the previous frame's tile kernel more smoothly than a few long-lived ones)
         hipLaunchKernelGGL(k_block_setup, dim3(nsegs_all), dim3(kSetupThreads), 0, side2,
-                           P, t->d_hblk, S.ranges, S.vtx, S.recs, S.gen, S.seg_list, seg_count);
+                           P, t->d_hblk, S.ranges, S.vtx, S.recs, S.gen, S.seg_list, seg_count, S.band);
         VF_HIP_TRY(hipEventRecord(S.set_up, side2));
         VF_HIP_TRY(hipGetLastError());                                      // both launched without error: the stamp
         S.geom_stamp = t->geom_gen; S.height_stamp = t->height_gen;
@@ -1656,7 +1658,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         const dim3 per_cu(std::min<uint32_t>((uint32_t)std::max(1, t->ctx->prop.multiProcessorCount) * (1024u / (uint32_t)kTileThreads), ntiles + kSplitBudget)),
                    few(std::min<uint32_t>(64u, ntiles + kSplitBudget)), threads(kTileThreads);
 #define VF_TILE_ARGS P, V, S.row_ranges, S.cap_seg, S.cap_rad, t->d_lut, t->ctx->d_thresh, S.work_sorted, S.work_count, \
-                     rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo
+                     rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo, S.band
         const bool fast = fast_shading(t->inputs);
         // (the complete variant redraws the rare items that met a clipped primitive: always the plain loop)
 #define VF_TILE_LAUNCH(WV, FS)                                                                                         \
@@ -3700,6 +3702,30 @@ int vf_terrain_debug_item_stats(vf_terrain *t, uint32_t *dst, uint32_t max_items
     if (n > max_items) n = max_items;
     if (n) VF_HIP_TRY(hipMemcpy(dst, t->d_stats + 4, 4 * (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *count = n;
+    return VF_OK;
+}
+
+// The set-up pass's output of the plan state the last frame was drawn from (include/vf_hip.h).  Host copies behind a full wait:
+// nothing of this is on a frame's path.
+int vf_terrain_debug_band_masks(vf_terrain *t, uint32_t *recs, uint64_t *masks, int32_t *xy, uint32_t max_blocks, uint32_t *count)
+{
+    static_assert(VF_BAND_SLOTS == (uint32_t)kBandSlots, "the header's slot count is the kernels'");
+    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered");
+    if (max_blocks < t->nblocks) return fail(VF_ERR_INVALID, "max_blocks is smaller than the grid's blocks");
+    const vf_terrain::PlanState &S = t->ps[t->last_set];
+    if (!S.slab) return fail(VF_ERR_INVALID, "nothing rendered");
+    VF_HIP_TRY(wait_frame(t));
+    VF_HIP_TRY(sync_sides(t));
+    const size_t nb = t->nblocks;
+    if (recs) VF_HIP_TRY(hipMemcpy(recs, S.recs, nb * sizeof(BlockRec), hipMemcpyDeviceToHost));
+    if (masks) VF_HIP_TRY(hipMemcpy(masks, S.band, nb * kBandSlots * sizeof(ulonglong2), hipMemcpyDeviceToHost));
+    if (xy) {
+        std::vector<VertexRec> v(nb * kBlockStride);
+        VF_HIP_TRY(hipMemcpy(v.data(), S.vtx, v.size() * sizeof(VertexRec), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < v.size(); ++k) { xy[2 * k] = v[k].X; xy[2 * k + 1] = v[k].Y; }
+    }
+    *count = (uint32_t)nb;
     return VF_OK;
 }
 

@@ -287,9 +287,10 @@ __global__ __launch_bounds__(512) void k_block_boxes(FrameParams P, const float2
 //      -> clip coordinates -> 24.8 snapped X, Y, 1/w and clip flags, kept in LDS;
 //   2. one wave per block, lane = cell: both primitives are classified -- dead (non-finite, outside near/far, not projectable,
 //      bounding box without a pixel centre of the target, back-facing or degenerate), generic (needs clipping / oversized) or alive;
-//      alive masks by ballot, exact union of the alive primitives' pixel boxes by wave reduction -> BlockRec;
+//      alive masks by ballot, exact union of the alive primitives' pixel boxes by wave reduction -> BlockRec; the alive masks
+//      again per row of tiles, folded into kBandSlots slots (vf_device.h) -> 128 B of band masks;
 //   3. the block's 81 vertices as {X, Y, 1/w, h} records (1296 B, coalesced) for the tile kernel's raster and fragment stages.
-// Streaming: 324 B read, ~1.3 KB written per block.  The tile kernel then loads instead of recomputing -- each block is looked at by
+// Streaming: 324 B read, ~1.45 KB written per block.  The tile kernel then loads instead of recomputing -- each block is looked at by
 // 1.9 tiles on average, by up to 16 strips of a heavy tile on a multi-GPU rank -- and never touches a block without alive primitives.
 // It needs at most 64 vector registers and 21 KB of LDS: workgroups of the NEXT frame's set-up (side stream) fit on a CU beside the
 // tile kernel's workgroup and run in the issue slots it leaves idle.
@@ -355,7 +356,8 @@ __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v)
 __global__ __launch_bounds__(kSetupThreads) void k_block_setup(FrameParams P, const float *__restrict__ hblk,
                                                                const PixelBox *__restrict__ cons_boxes, VertexRec *__restrict__ vtx,
                                                                BlockRec *__restrict__ recs, ulonglong2 *__restrict__ gen,
-                                                               const uint32_t *__restrict__ seg_list, const uint32_t *__restrict__ seg_count)
+                                                               const uint32_t *__restrict__ seg_list, const uint32_t *__restrict__ seg_count,
+                                                               ulonglong2 *__restrict__ band)
 {
     __shared__ int2 sXY[kBlockVerts][kSegStride];
     __shared__ uint8_t sF[kBlockVerts][kSegStride];
@@ -415,6 +417,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_block_setup(FrameParams P, co
         }
         const uint32_t lj = lane >> 3, li = lane & 7u;
         int c0 = 0, c1 = 0;                                // 0 dead, 1 alive, 2 generic
+        uint32_t lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;       // the two primitives' own boxes, packed like lo / hi (meaningful where alive)
         uint32_t lo = 0x7FFF7FFFu, hi = 0x80008000u;       // packed (x, y) int16: running min of (px0, py0), max of (px1, py1)
         if (i0 + cbase + li < P.nm1 && j0 + lj < P.nm1) {
             const int2 pa = sXY[lj][cbase + li], pb = sXY[lj][cbase + li + 1u], pc = sXY[lj + 1u][cbase + li], pd = sXY[lj + 1u][cbase + li + 1u];
@@ -422,7 +425,7 @@ __global__ __launch_bounds__(kSetupThreads) void k_block_setup(FrameParams P, co
             if (any_flag) { fa = sF[lj][cbase + li]; fb = sF[lj][cbase + li + 1u]; fc = sF[lj + 1u][cbase + li]; fd = sF[lj + 1u][cbase + li + 1u]; }
             // Straight-line on purpose: nearly every primitive reaches the facing test, so early exits would only add divergent
             // branches (scalar instructions cost twice a vector one here); the flag tests are skipped as a whole in ordinary views.
-            auto classify = [&](uint32_t f0, uint32_t f1, uint32_t f2, int2 q0, int2 q1, int2 q2) -> int {
+            auto classify = [&](uint32_t f0, uint32_t f1, uint32_t f2, int2 q0, int2 q1, int2 q2, uint32_t &box_lo, uint32_t &box_hi) -> int {
                 int forced = -1;                                       // a verdict from the clip flags, if any
                 if (any_flag) {
                     const uint32_t any = f0 | f1 | f2, all = f0 & f1 & f2;
@@ -444,10 +447,11 @@ __global__ __launch_bounds__(kSetupThreads) void k_block_setup(FrameParams P, co
                 const uint32_t plo = (uint32_t)px0 | ((uint32_t)py0 << 16), phi = (uint32_t)px1 | ((uint32_t)py1 << 16);
                 lo = alive ? pk_min_i16(lo, plo) : lo;
                 hi = alive ? pk_max_i16(hi, phi) : hi;
+                box_lo = plo; box_hi = phi;                             // (the band masks below: the rows of an alive primitive)
                 return forced >= 0 ? forced : (oversized ? 2 : (alive ? 1 : 0));
             };
-            c0 = classify(fa, fc, fb, pa, pc, pb);        // (a, c, b)
-            c1 = classify(fb, fc, fd, pb, pc, pd);        // (b, c, d)
+            c0 = classify(fa, fc, fb, pa, pc, pb, lo0, hi0);   // (a, c, b)
+            c1 = classify(fb, fc, fd, pb, pc, pd, lo1, hi1);   // (b, c, d)
         }
         const unsigned long long a0 = __ballot(c0 == 1), a1 = __ballot(c1 == 1), g0 = __ballot(c0 == 2), g1 = __ballot(c1 == 2);
         lo = wave_reduce_pk_i16<false>(lo);                // (valid in lane 63, which writes the record)
@@ -459,6 +463,32 @@ __global__ __launch_bounds__(kSetupThreads) void k_block_setup(FrameParams P, co
         if (lane == 63u) {
             recs[b] = rec;
             if (g0 | g1) gen[b] = make_ulonglong2(g0, g1);
+        }
+        // the alive masks once more, per tile row: slot s holds the alive primitives whose pixel-centre rows py0 .. py1 reach a row of
+        // tiles r with r % kBandSlots == s (a tile of row r then classifies those only; their OR over the slots is alive_even / alive_odd).
+        // The union box has the tile rows the block reaches.  One row -- most blocks of a far field, and the set-up pass of an orbit runs
+        // every pose -- and the alive masks ARE its slot.  Otherwise two ballots per row, rows kBandSlots apart sharing a slot.  Lane s
+        // keeps slot s, the slots of rows out of reach are zero: one 128-byte store per block.
+        // (A block without an alive primitive gets zeros: with generic primitives its box is not empty, and a tile that pulls it reads its slot.)
+        {
+            unsigned long long be = 0ull, bo = 0ull;
+            const uint32_t row0 = ((uint32_t)__builtin_amdgcn_readlane((int)lo, 63) >> 16) >> 6;
+            const uint32_t row1 = ((uint32_t)__builtin_amdgcn_readlane((int)hi, 63) >> 16) >> 6;
+            if (!rec.count) {                              // (uniform)
+            } else if (row0 == row1) {
+                const bool mine = lane == (row0 & ((uint32_t)kBandSlots - 1u));
+                be = mine ? a0 : 0ull; bo = mine ? a1 : 0ull;
+            } else {
+                const uint32_t e0 = lo0 >> 22, e1 = hi0 >> 22, o0 = lo1 >> 22, o1 = hi1 >> 22;       // py0 >> 6, py1 >> 6 of the two primitives
+                const uint32_t nslots = min(row1 - row0 + 1u, (uint32_t)kBandSlots);
+                for (uint32_t j = 0; j < nslots; ++j) {
+                    unsigned long long e = 0ull, o = 0ull;
+                    for (uint32_t r = row0 + j; r <= row1; r += (uint32_t)kBandSlots) { e |= __ballot(e0 <= r && r <= e1); o |= __ballot(o0 <= r && r <= o1); }
+                    const bool mine = lane == ((row0 + j) & ((uint32_t)kBandSlots - 1u));
+                    be = mine ? (e & a0) : be; bo = mine ? (o & a1) : bo;
+                }
+            }
+            if (lane < (uint32_t)kBandSlots) band[(size_t)b * kBandSlots + lane] = make_ulonglong2(be, bo);
         }
     }
     }
@@ -1796,7 +1826,8 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                                                        const uint2 *__restrict__ work, uint32_t *__restrict__ work_count,
                                                        const uint32_t *__restrict__ rc_lo, const uint32_t *__restrict__ rc_hi,
                                                        uint32_t *__restrict__ rgba, uint32_t *__restrict__ vis_out, uint32_t *stats,
-                                                       uint32_t *__restrict__ last_blocks, uint32_t *__restrict__ redo)
+                                                       uint32_t *__restrict__ last_blocks, uint32_t *__restrict__ redo,
+                                                       const ulonglong2 *__restrict__ band)
 {
     using namespace tile;
     uint32_t *const redo_count = work_count + 3;           // items handed to the complete variant
@@ -1861,7 +1892,10 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
     T.vis = s_vis; T.colfin = s_colfin; T.rowfin = s_rowfin; T.colfin4 = s_colfin4; T.rowfin4 = s_rowfin4;
     const TilePlace tp = tile_rect(P, tile, T.px_lo, T.px_hi, T.py_lo, T.py_hi);
     const uint32_t tcol = tp.tx;
-    const int32_t tile_x0 = T.px_lo;                       // the tile's left edge (T.px_lo becomes the strip's below)
+    // which of a block's band masks this item reads (vf_device.h): its row of tiles, folded (py_lo is a multiple of kTileH in both layouts)
+    static_assert(kTileH == 64, "the set-up pass folds rows of 64 pixels");
+    const uint32_t band_slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(((uint32_t)T.py_lo >> 6) & ((uint32_t)kBandSlots - 1u)));
+    const int32_t tile_x0 = T.px_lo;                      // the tile's left edge (T.px_lo becomes the strip's below)
     work_strip(item, T.px_lo, T.px_hi);                    // heavy tiles arrive as 2..16 column strips
     const uint32_t tile_pixels = (uint32_t)(T.px_hi - T.px_lo + 1) * (uint32_t)(T.py_hi - T.py_lo + 1);
     const uint64_t row_full = ~0ull >> (63 - (T.px_hi - T.px_lo));   // row mask of a fully final row of this tile / strip
@@ -1935,9 +1969,15 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
             // were rewritten WHILE this launch runs -- and the plan state this launch reads is not written again before its `drawn`
             // event (render_impl: the next user of the set waits for it).  tests/test_gpu_parity.py::
             // test_records_rewritten_every_frame_are_never_read_stale rewrites both sets with different records 20 frames in a row.
-            typedef uint32_t __attribute__((ext_vector_type(8))) rec_words;
+            // The BAND MASKS (vf_device.h) are read the same way and the argument covers them word for word: k_block_setup writes them
+            // with vector stores in the launch that writes the records, into the same plan state, which is not rewritten while a tile
+            // kernel reads it.  Their address needs nothing from the record -- the block index and the item's slot -- so the load goes
+            // out with the record's and the vertices', and its 16 bytes take the place of the record's second half (alive_even,
+            // alive_odd: what every tile of every row would have to classify).
+            typedef uint32_t __attribute__((ext_vector_type(4))) rec_words;
             const rec_words rw = *(const __attribute__((address_space(4))) rec_words *)(uintptr_t)(V.recs + bidx);
-            const uint4 r_lo = make_uint4(rw[0], rw[1], rw[2], rw[3]), r_hi = make_uint4(rw[4], rw[5], rw[6], rw[7]);   // box (2 words), flags, count | alive_even, alive_odd
+            const rec_words bw = *(const __attribute__((address_space(4))) rec_words *)(uintptr_t)(band + (size_t)bidx * kBandSlots + band_slot);
+            const uint4 r_lo = make_uint4(rw[0], rw[1], rw[2], rw[3]), r_hi = make_uint4(bw[0], bw[1], bw[2], bw[3]);   // box (2 words), flags, count | this tile row's alive_even, alive_odd
             const uint4 *vsrc = reinterpret_cast<const uint4 *>(V.vtx + (size_t)bidx * kBlockStride);
             const uint4 va4 = vsrc[lane];
             uint4 vb4 = make_uint4(0u, 0u, 0u, 0u);
