@@ -16,7 +16,7 @@ for cam in (("pose8", "pose0") if os.environ.get("VF_C5") else ("default", "fill
     t.set_uniforms(b.orbit_uniforms(int(cam[4:]), W, H) if cam.startswith("pose") else b.camera_uniforms(cam, W, H))
     for _ in range(24): t.render()
     t.enable_timing(True); t.render(); tm = t.timings(); ph = t.phase_cycles().astype(float); it = t.item_stats(); t.enable_timing(False)
-    lanes = ph[34:38]; vsub2 = ph[32:34]; vsub = ph[30:32]; wv = ph[24:30]; sub = ph[16:24]; cnt = ph[8:16]; ph = ph[:8]; ph[0] += sub.sum(); ph[2] += vsub.sum() + vsub2.sum()
+    og = ph[38:40]; lanes = ph[34:38]; vsub2 = ph[32:34]; vsub = ph[30:32]; wv = ph[24:30]; sub = ph[16:24]; cnt = ph[8:16]; ph = ph[:8]; ph[0] += sub.sum(); ph[2] += vsub.sum() + vsub2.sum()
     tot = ph.sum()
     live = max(cnt[7], 1)
     print(f"{cam}: tile_ms={tm['tile_ms']:.3f} pairs={tm['blocks_rasterised']} wave-cycles total={tot:.3e} (= {tot/16/2.4e6:.1f} ms of workgroup time at 2.4 GHz)")
@@ -28,6 +28,9 @@ for cam in (("pose8", "pose0") if os.environ.get("VF_C5") else ("default", "fill
     div = lambda x, y: x / y if y else float("nan")
     print(f"   LANES busy per wave-level execution: pass A (classification) {div(lanes[1], lanes[2]):.1f} of 64;  pass B set-up (lanes with a triangle) {div(lanes[3], cnt[1]):.1f};  "
           f"line loop: {'group tests' if use else 'line trips'} {div(lanes[0], wv[0]):.1f}, stage 1 {div(cnt[6], wv[1]):.1f}, stage 2 {div(cnt[4], wv[2]):.1f}, paint {div(cnt[5], wv[3]):.1f};  occlusion loop of the classification {div(wv[5], wv[4]):.1f} (triangles per iteration)")
+    if use:
+        print(f"   OPEN GROUPS: four-line groups entering stage 0 per pair {div(lanes[0], live):.1f};  with an open pixel in their triangle's box {div(og[0], live):.1f} (open share {div(og[0], lanes[0]):.3f});  "
+              f"span_group executions per pair (wave-level) {div(og[1], live):.2f}, lanes per execution {div(lanes[0], og[1]):.1f}")
     print(f"   BAND MASKS: alive primitives per pair (the tile row's slot of the block's masks) {div(lanes[1], live):.1f};  pass-A executions per pair {div(lanes[2], live):.3f}")
     for n, c in zip(["row list", "candidate tests", "wait for slowest wave", "scan + list fill", "hand-over + pull", "item record + tile state", "row mask", "-"], sub):
         print(f"      set-up: {n:22s} {100*c/tot:6.2f} %")

@@ -526,7 +526,7 @@ __device__ __forceinline__ uint64_t bit_range(int32_t lo, int32_t hi)   // bits 
 // (owned by a higher block row) are skipped unsolved, and only non-final pixels are touched.
 // `sub` / `nsub`: the lines of one triangle are dealt round-robin to nsub cooperating lanes (all of them run the set-up).
 #ifdef VF_PHASE_PROF
-struct RasterCounts { uint32_t tris, lines, solved, painted, paint_lines, trips, w_iter, w_s1, w_s2, w_paint, w_cls, c_reach, l_iter, nsurv, iters, live, empty, alive, apass, act; };   // w_*: wave-level executions, the others lane-level: their ratio is the lanes a wave keeps busy there
+struct RasterCounts { uint32_t tris, lines, solved, painted, paint_lines, trips, w_iter, w_s1, w_s2, w_paint, w_cls, c_reach, l_iter, nsurv, iters, live, empty, alive, apass, act, g_open, w_sg; };   // g_open: four-line groups with an open pixel in their triangle's box (lane-level), w_sg: wave-level executions of the group's span bound; w_*: wave-level executions, the others lane-level: their ratio is the lanes a wave keeps busy there
 #define VF_RC_ARG , RasterCounts &RC
 #define VF_RC(...) __VA_ARGS__
 #else
@@ -549,28 +549,45 @@ __device__ __forceinline__ int32_t floor_to_int(float x)
 // travel between the triangle's lanes by ballot, and only the lines of the groups that are left are dealt to the lanes and solved as
 // before.  The pixels painted are the same by construction (a dropped line would have failed its own stage-1 test).
 // `first`: the wave's first lane working on this triangle (lanes first .. first + nsub - 1 do, all of them active here).
-template <bool GROUPS>
-__device__ __forceinline__ void raster_fast(const TileCtx &T, uint32_t word, const int2 *vb, uint32_t vcode, int32_t sub, int32_t nsub, uint32_t first VF_RC_ARG)
+// BOXED / `box`: the triangle's box inside the tile as k_tile's pass A packed it (classify_alive<true>) -- every survivor of the kernel
+// instantiation with line groups has been classified against this very tile or strip, so its box is not empty and is the one the
+// vertices would give again: the min / max, snap and clamp of six coordinates become four bit-field extracts.  The vertices are
+// still loaded, for span_setup.  (Not BOXED -- the strip instantiation, whose survivors may be unclassified -- the box is worked out here.)
+template <bool GROUPS, bool BOXED = false>
+__device__ __forceinline__ void raster_fast(const TileCtx &T, uint32_t word, const int2 *vb, uint32_t vcode, int32_t sub, int32_t nsub, uint32_t first VF_RC_ARG, uint32_t box = 0u)
 {
     VF_RC(RC.tris++;)
-    int32_t px0, py0, n_outer, n_inner, o_base, i_base;
+    int32_t px0 = 0, py0 = 0, n_outer, n_inner, o_base, i_base;   // o_base / i_base: tile-local index of outer line 0 / of inner offset 0
     bool cols;
     SpanSetup S;
+    // sub-pixel coordinates of the centre of (outer line 0, inner offset 0), for the set-up and the exact solver
+    auto centre0 = [&](int32_t &u0c, int32_t &v0c) {
+        if constexpr (BOXED) { u0c = (o_base + (cols ? T.px_lo : T.py_lo)) * 256 + 128; v0c = (i_base + (cols ? T.py_lo : T.px_lo)) * 256 + 128; }
+        else { u0c = (cols ? px0 : py0) * 256 + 128; v0c = (cols ? py0 : px0) * 256 + 128; }
+    };
     {
         const int2 q0 = vb[vcode & 0xFFu], q1 = vb[(vcode >> 8) & 0xFFu], q2 = vb[vcode >> 16];
-        const int32_t xmin = min(q0.x, min(q1.x, q2.x)), xmax = max(q0.x, max(q1.x, q2.x));
-        const int32_t ymin = min(q0.y, min(q1.y, q2.y)), ymax = max(q0.y, max(q1.y, q2.y));
-        px0 = max((xmin + 127) >> 8, T.px_lo); py0 = max((ymin + 127) >> 8, T.py_lo);
-        const int32_t px1 = min((xmax - 128) >> 8, T.px_hi), py1 = min((ymax - 128) >> 8, T.py_hi);
-        if (px0 > px1 || py0 > py1) return;
-        cols = (px1 - px0) <= (py1 - py0);                 // iterate the short axis, solve spans along the long one
+        if constexpr (BOXED) {
+            cols = (box & 1u) != 0u;
+            o_base = (int32_t)((box >> 1) & 63u); n_outer = (int32_t)((box >> 7) & 63u);
+            i_base = (int32_t)((box >> 13) & 63u); n_inner = (int32_t)(box >> 19);
+        } else {
+            const int32_t xmin = min(q0.x, min(q1.x, q2.x)), xmax = max(q0.x, max(q1.x, q2.x));
+            const int32_t ymin = min(q0.y, min(q1.y, q2.y)), ymax = max(q0.y, max(q1.y, q2.y));
+            px0 = max((xmin + 127) >> 8, T.px_lo); py0 = max((ymin + 127) >> 8, T.py_lo);
+            const int32_t px1 = min((xmax - 128) >> 8, T.px_hi), py1 = min((ymax - 128) >> 8, T.py_hi);
+            if (px0 > px1 || py0 > py1) return;
+            cols = (px1 - px0) <= (py1 - py0);             // iterate the short axis, solve spans along the long one
+            n_outer = cols ? px1 - px0 : py1 - py0; n_inner = cols ? py1 - py0 : px1 - px0;
+            o_base = cols ? px0 - T.px_lo : py0 - T.py_lo;
+            i_base = cols ? py0 - T.py_lo : px0 - T.px_lo;
+        }
         const int32_t U[3] = { cols ? q0.x : q0.y, cols ? q1.x : q1.y, cols ? q2.x : q2.y };     // outer / inner coordinates of the vertices
         const int32_t V[3] = { cols ? q0.y : q0.x, cols ? q1.y : q1.x, cols ? q2.y : q2.x };
-        n_outer = cols ? px1 - px0 : py1 - py0; n_inner = cols ? py1 - py0 : px1 - px0;
-        span_setup(U, V, !cols, (cols ? px0 : py0) * 256 + 128, (cols ? py0 : px0) * 256 + 128, n_outer, S);
+        int32_t u0c, v0c;
+        centre0(u0c, v0c);
+        span_setup(U, V, !cols, u0c, v0c, n_outer, S);
     }
-    o_base = cols ? px0 - T.px_lo : py0 - T.py_lo;         // tile-local index of outer line 0
-    i_base = cols ? py0 - T.py_lo : px0 - T.px_lo;         // tile-local index of inner offset 0
     const uint32_t *fin = cols ? T.colfin : T.rowfin;
     // (one loop header or the other: the body below is shared)
     uint32_t gmask = 0, gleft = 0;
@@ -584,6 +601,9 @@ __device__ __forceinline__ void raster_fast(const TileCtx &T, uint32_t word, con
     const uint32_t *fin4 = cols ? T.colfin4 : T.rowfin4;
     // (round 4 let a triangle with no more than one line per lane skip the test, its groups all counting as open; since a group's test is
     //  one LDS word -- round 5 -- every triangle is tested: C4 -0.4 %)
+    // (a cheaper test in front of span_group -- the group's mask against the box's inner range alone, the occlusion test of
+    //  classify_alive, the span bound only for the groups it leaves -- would leave most of them: 48.6 of the 63.6 groups a pair brings here
+    //  hold an open pixel in their box at C4's default camera, 159.6 of 223.5 top-down: measured, not built; EXPERIMENTS.md)
     const bool test_groups = n_outer + 1 > 0;
     gmask = test_groups ? 0u : (1u << ng) - 1u;
     const uint32_t lanes_mask = nsub >= 32 ? 0xFFFFFFFFu : (1u << nsub) - 1u;
@@ -597,9 +617,9 @@ __device__ __forceinline__ void raster_fast(const TileCtx &T, uint32_t word, con
             span_group(S, oa, ob, n_inner, glo, ghi);
             if (!S.regular) { glo = 0; ghi = n_inner; }
             open = glo <= ghi && (bit_range(i_base + min(glo, n_inner), i_base + max(ghi, 0)) & ~done4) != 0ull;
-            VF_RC(RC.lines += (uint32_t)(ob - oa + 1); RC.l_iter++;)
+            VF_RC(RC.lines += (uint32_t)(ob - oa + 1); RC.l_iter++; RC.g_open += (~done4 & bit_range(i_base, i_base + n_inner)) != 0ull ? 1u : 0u;)
         }
-        VF_RC(if ((int)(threadIdx.x & 63u) == __builtin_ctzll(__ballot(1))) RC.w_iter++;)
+        VF_RC(if ((int)(threadIdx.x & 63u) == __builtin_ctzll(__ballot(1))) { RC.w_iter++; RC.w_sg++; })
         const unsigned long long votes = __ballot(open);
         gmask |= ((uint32_t)(votes >> first) & lanes_mask) << kb;     // (groups beyond ng voted no; other triangles' lanes are masked out)
     }
@@ -633,7 +653,9 @@ __device__ __forceinline__ void raster_fast(const TileCtx &T, uint32_t word, con
             const int2 q0 = vb[vcode & 0xFFu], q1 = vb[(vcode >> 8) & 0xFFu], q2 = vb[vcode >> 16];
             const int32_t U[3] = { cols ? q0.x : q0.y, cols ? q1.x : q1.y, cols ? q2.x : q2.y };
             const int32_t V[3] = { cols ? q0.y : q0.x, cols ? q1.y : q1.x, cols ? q2.y : q2.x };
-            span_exact(U, V, !cols, (cols ? px0 : py0) * 256 + 128, (cols ? py0 : px0) * 256 + 128, o, n_inner, lo, hi);
+            int32_t u0c, v0c;
+            centre0(u0c, v0c);
+            span_exact(U, V, !cols, u0c, v0c, o, n_inner, lo, hi);
             if (lo > hi) continue;
             bits = bit_range(i_base + lo, i_base + hi) & ~done;
         }
@@ -698,8 +720,11 @@ __device__ __noinline__ void raster_generic(const GVert v[3], float hw, float hh
 // Tile-dependent part of the classification of a primitive k_block_setup found alive (no clipping needed, front-facing, a pixel
 // centre of the target inside its bounding box): does it hold a pixel centre of this tile that is still open?
 // `lines`: how many lines raster_fast will walk for it (the shorter side of its box inside the tile).
+// `box` (FOUR only): that box the way raster_fast walks it, tile-local -- cols | first outer line << 1 | outer lines - 1 << 7 | first inner
+// offset << 13 | inner length - 1 << 19 (25 bits): what raster_fast would otherwise work out again from the three vertices (the
+// hand-over in k_tile's pass A).
 template <bool FOUR>      // FOUR: the occlusion loop reads the four-line masks (the kernel instantiation for wide items; narrow strips keep their lines' own)
-__device__ __forceinline__ bool classify_alive(const TileCtx &T, int32_t X0, int32_t Y0, int32_t X1, int32_t Y1, int32_t X2, int32_t Y2, uint32_t &lines VF_RC_ARG)
+__device__ __forceinline__ bool classify_alive(const TileCtx &T, int32_t X0, int32_t Y0, int32_t X1, int32_t Y1, int32_t X2, int32_t Y2, uint32_t &lines, uint32_t &box VF_RC_ARG)
 {
     const int32_t xmin = min(X0, min(X1, X2)), xmax = max(X0, max(X1, X2));
     const int32_t ymin = min(Y0, min(Y1, Y2)), ymax = max(Y0, max(Y1, Y2));
@@ -708,10 +733,14 @@ __device__ __forceinline__ bool classify_alive(const TileCtx &T, int32_t X0, int
     if (px0 > px1 || py0 > py1) return false;             // no pixel centre of the tile inside the bbox
     // occlusion: every candidate pixel already final
     const bool cols = (px1 - px0) <= (py1 - py0);
-    lines = (uint32_t)(min(px1 - px0, py1 - py0) + 1);
+    if constexpr (!FOUR) lines = (uint32_t)(min(px1 - px0, py1 - py0) + 1);      // (FOUR: bits 7..12 of `box` + 1 -- one value kept through the loop below, not two)
     const uint32_t *fin = cols ? T.colfin : T.rowfin;
     const int32_t o0 = cols ? px0 - T.px_lo : py0 - T.py_lo, o1 = cols ? px1 - T.px_lo : py1 - T.py_lo;
     const uint64_t seg = cols ? bit_range(py0 - T.py_lo, py1 - T.py_lo) : bit_range(px0 - T.px_lo, px1 - T.px_lo);
+    if constexpr (FOUR) {
+        const int32_t i0 = cols ? py0 - T.py_lo : px0 - T.px_lo, i1 = cols ? py1 - T.py_lo : px1 - T.px_lo;
+        box = (cols ? 1u : 0u) | ((uint32_t)o0 << 1) | ((uint32_t)(o1 - o0) << 7) | ((uint32_t)i0 << 13) | ((uint32_t)(i1 - i0) << 19);
+    }
     VF_RC(RC.c_reach++;)
     // four lines per step: the loop is a chain of LDS latencies (load, test, branch), not of arithmetic
     constexpr int kClsLines = 4;
@@ -1023,6 +1052,9 @@ __device__ __forceinline__ bool block_is_candidate(const PixelBox &b, const floa
 // also sees up to three lines outside it -- their open pixels can only make the answer "open", the conservative side.
 __device__ __forceinline__ void refresh_fin4(const uint32_t *colfin, const uint32_t *rowfin, uint32_t *colfin4, uint32_t *rowfin4, uint32_t lane)
 {
+    // (the lane's LDS addresses are worked out where they are used: hoisted out of the kernel's loops they sit in a vector register the
+    //  tile kernel does not have -- a spill at kernel entry and a reload per rescan; likewise in fill_work_list)
+    asm volatile("" : "+v"(lane));
     if (lane < 32u) {
         const uint32_t g = lane & 15u;
         const uint32_t *src = lane < 16u ? colfin : rowfin;
@@ -1533,12 +1565,17 @@ constexpr uint32_t kWideLines = 28, kBalGain = 2;          // lane dealing by li
 // from the barrier behind the list fill to the barrier behind the block loop, the private arrays live only between the two.  The
 // kernel's LDS falls from 80.5 to 64 KB: two of its workgroups (this frame's last, the next frame's first) then leave a CU 32 KB for
 // the set-up pass that runs beside them, where they left 2.8 -- C4 -1.4 %, top-down camera -0.9 % (round 5; spent on chunks of 192
-// block rows instead, the 16 KB lose: 0.7189 -> 0.7239 ms).
+// block rows instead, the 16 KB lose: 0.7189 -> 0.7239 ms).  (With the survivors' boxes, below, the overlay is 18.1 KB and the kernel's
+// LDS 66 168 B: still two workgroups and two groups of the set-up pass per CU.  A first form of the hand-over -- a word array beside
+// the three byte arrays, 70 264 B -- put arrays beyond the 64 KB a DS instruction's offset field reaches: longer code in every
+// instantiation and two scratch reloads in the chunk loop.)
 struct WaveLds {
     int2 xy[kWaves][kNV];                                  // per wave: snapped vertices of the current block (from k_block_setup)
-    uint8_t alive[kWaves][kBlockPrims];                    // per wave: the block's alive primitives (cell << 1 | odd), compacted
-    uint8_t surv[kWaves][kBlockPrims];                     // per wave: those of them that survive against this tile
-    uint8_t lines[kWaves][kBlockPrims];                    // per wave: ... and how many lines each of them has inside the tile
+    // per wave: the block's alive primitives (cell << 1 | odd), compacted; pass A compacts those that survive against this tile IN PLACE
+    // (a survivor's slot is never behind the one it was read from, and a wave's LDS operations complete in order) and leaves with each
+    // what pass B needs: cell << 1 | odd (7 bits) | classify_alive's box << 7 with line groups, | lines inside the tile - 1 << 14 without
+    // (the same six bits of the box).  One word per primitive where three byte arrays used to cost three: the box rides for 128 B a wave.
+    uint32_t surv[kWaves][kBlockPrims];
 };
 constexpr size_t kHitBytes = sizeof(unsigned long long) * kMaxSteps * kHitWords;
 constexpr size_t kOverlayBytes = sizeof(WaveLds) > kHitBytes ? sizeof(WaveLds) : kHitBytes;
@@ -1547,7 +1584,7 @@ constexpr size_t kOverlayBytes = sizeof(WaveLds) > kHitBytes ? sizeof(WaveLds) :
 struct Lds {
     uint32_t *vis;                                         // the 64 x 64 visibility tile (rows skewed: vis_index)
     unsigned long long (*hit)[kHitWords];                  // 64-bit ballots per block row of the chunk (list building)
-    int2 (*xy)[kNV]; uint8_t (*alive)[kBlockPrims]; uint8_t (*surv)[kBlockPrims]; uint8_t (*lines)[kBlockPrims];   // WaveLds (block loop)
+    int2 (*xy)[kNV]; uint32_t (*surv)[kBlockPrims];   // WaveLds (block loop)
     uint32_t *list;                                        // bx | by << 10 | step << 20
     uint32_t *cnt;                                         // candidates per step
     uint16_t *words;                                       // per step: first | end << 8 of the 64-block groups its ballots were taken for
@@ -1715,6 +1752,7 @@ __device__ __forceinline__ void fill_work_list(const Lds &L, uint32_t cursor, ui
     static_assert(kMaxSteps % 64 == 0 && kParts >= 1 && kParts <= 4, "the offset scan below works on 64-row parts");
     uint32_t c[kParts], inc[kParts];
     unsigned long long fm[kParts];
+    asm volatile("" : "+v"(lane));                      // (addresses of the lane's counts: not hoisted -- refresh_fin4)
 #pragma unroll
     for (int p = 0; p < kParts; ++p) {
         c[p] = lane + 64u * p < nrowsteps ? L.cnt[lane + 64u * p] : 0u;
@@ -1831,7 +1869,7 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
 {
     using namespace tile;
     uint32_t *const redo_count = work_count + 3;           // items handed to the complete variant
-    // ---- LDS (64 KB): separate arrays, bundled into `L` for the phases (tile::Lds) ----
+    // ---- LDS (64.6 KB): separate arrays, bundled into `L` for the phases (tile::Lds) ----
     __shared__ uint32_t s_vis[kTileW * kTileH];
     __shared__ __attribute__((aligned(16))) unsigned char s_overlay[kOverlayBytes];   // list-building ballots, then the waves' private arrays (WaveLds)
     __shared__ uint32_t s_list[kChunk];
@@ -1852,12 +1890,10 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
     __shared__ uint32_t s_per[65];
     WaveLds &s_wave = *reinterpret_cast<WaveLds *>(s_overlay);
     int2 (&sXY)[kWaves][kNV] = s_wave.xy;
-    uint8_t (&sC)[kWaves][kBlockPrims] = s_wave.alive;
-    uint8_t (&sS)[kWaves][kBlockPrims] = s_wave.surv;
-    uint8_t (&sL)[kWaves][kBlockPrims] = s_wave.lines;
+    uint32_t (&sS)[kWaves][kBlockPrims] = s_wave.surv;
     Lds L;
     L.vis = s_vis; L.hit = reinterpret_cast<unsigned long long (*)[kHitWords]>(s_overlay);
-    L.xy = s_wave.xy; L.alive = s_wave.alive; L.surv = s_wave.surv; L.lines = s_wave.lines;
+    L.xy = s_wave.xy; L.surv = s_wave.surv;
     L.list = s_list; L.cnt = s_cnt; L.words = s_words; L.pending = s_pending; L.firstid = s_firstid; L.allrows = s_allrows; L.rc = s_rc;
     L.colfin = s_colfin; L.rowfin = s_rowfin; L.colfin4 = s_colfin4; L.rowfin4 = s_rowfin4; L.part = s_part; L.rows = s_rows;
     L.next = &s_next; L.lock = &s_lock; L.done = &s_done; L.frontier = &s_frontier; L.published = &s_published; L.blocks = &s_blocks; L.redo = &s_redo;
@@ -2025,8 +2061,8 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                 {
                     const uint32_t pe = __builtin_amdgcn_mbcnt_hi((uint32_t)(alive_e >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)alive_e, 0u));
                     const uint32_t po = __builtin_amdgcn_mbcnt_hi((uint32_t)(alive_o >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)alive_o, 0u));
-                    if ((alive_e >> lane) & 1ull) sC[wave][pe] = (uint8_t)(2u * lane);
-                    if ((alive_o >> lane) & 1ull) sC[wave][n_even + po] = (uint8_t)(2u * lane + 1u);
+                    if ((alive_e >> lane) & 1ull) sS[wave][pe] = 2u * lane;
+                    if ((alive_o >> lane) & 1ull) sS[wave][n_even + po] = 2u * lane + 1u;
                 }
                 __builtin_amdgcn_wave_barrier();   // LDS ops of one wave complete in order; keep the compiler from reordering
                 VF_PH(2)
@@ -2054,26 +2090,26 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                 for (uint32_t k0 = 0; k0 < n_cls; k0 += 64u) {
                     const uint32_t k = k0 + lane;
                     bool keep = false;
-                    uint32_t code = 0, nlines = 0;
+                    uint32_t code = 0, nlines = 0, box = 0;
                     if (k < n_cls) {
-                        code = sC[wave][k];
+                        code = sS[wave][k];
                         const uint32_t cell = code >> 1, odd = code & 1u;
                         const uint32_t va = (cell >> 3) * kBlockVerts + (cell & 7u);
                         const int2 q0 = sXY[wave][odd ? va + 1u : va], q1 = sXY[wave][va + kBlockVerts], q2 = sXY[wave][odd ? va + kBlockVerts + 1u : va + 1u];
-                        keep = classify_alive<GROUPS>(T, q0.x, q0.y, q1.x, q1.y, q2.x, q2.y, nlines VF_RC(, RC));
+                        keep = classify_alive<GROUPS>(T, q0.x, q0.y, q1.x, q1.y, q2.x, q2.y, nlines, box VF_RC(, RC));
+                        if constexpr (GROUPS) nlines = ((box >> 7) & 63u) + 1u;
                     }
                     const unsigned long long m = __ballot(keep);
                     any_wide = any_wide || __ballot(keep && nlines > kWideLines) != 0ull;
                     if (keep) {
                         const uint32_t at = nsurv + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                        sS[wave][at] = (uint8_t)code;
-                        sL[wave][at] = (uint8_t)nlines;
+                        sS[wave][at] = GROUPS ? code | (box << 7) : code | ((nlines - 1u) << 14);   // (in place: at <= k; WaveLds)
                     }
                     nsurv += (uint32_t)__popcll(m);
                 }
                 if constexpr (!GROUPS) if (n_cls < n_alive) {      // (uniform) a few primitives beyond the wave's 64 lanes: straight to the raster, unclassified
                     const uint32_t extra = n_alive - n_cls;
-                    if (lane < extra) { sS[wave][nsurv + lane] = sC[wave][n_cls + lane]; sL[wave][nsurv + lane] = (uint8_t)8; }
+                    if (lane < extra) sS[wave][nsurv + lane] = sS[wave][n_cls + lane] | (7u << 14);     // (eight lines; in place: nsurv <= n_cls)
                     nsurv += extra;
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -2091,9 +2127,9 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                     // lanes are dealt in proportion to the line counts instead: chunks of C = ceil(lines / (64 - survivors)) lines,
                     // survivor k gets ceil(L_k / C) lanes (at most 64 in all), found by a running maximum over the lanes.
                     bool balanced = false;
-                    uint32_t b_mine = 0, b_used = 0;                               // balanced: code | first lane << 8 | lanes << 16 of this lane's survivor
+                    uint32_t b_mine = 0, b_used = 0;                               // balanced: survivor | first lane << 8 | lanes << 16 of this lane's
                     if (any_wide && nsurv > 1u && nsurv <= 56u) {                  // (uniform)
-                        const uint32_t Lk = lane < nsurv ? (uint32_t)sL[wave][lane] : 0u;
+                        const uint32_t Lk = lane < nsurv ? ((sS[wave][lane] >> 14) & 63u) + 1u : 0u;
                         const uint32_t incL = wave_scan_add(Lk), maxL = wave_scan_max(Lk);
                         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incL, 63), widest = (uint32_t)__builtin_amdgcn_readlane((int)maxL, 63);
                         const uint32_t spare = 64u - nsurv;
@@ -2111,12 +2147,13 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                             const uint32_t mk = lane < nsurv ? (uint32_t)(((float)(Lk + C - 1u) + 0.5f) * __builtin_amdgcn_rcpf((float)C)) : 0u;   // lanes for survivor `lane`
                             const uint32_t inc = wave_scan_add(mk), start = inc - mk;
                             // owner of lane l = the last survivor whose first lane is <= l: marks at the first lanes, running maximum
-                            sC[wave][lane] = 0;                                    // (the alive list is done with: its bytes carry the marks)
+                            uint32_t *const marks = &sS[wave][64];                 // (at most 56 survivors here: the list's upper half is free and carries the marks)
+                            marks[lane] = 0;
                             __builtin_amdgcn_wave_barrier();
-                            if (lane < nsurv) sC[wave][start] = (uint8_t)(lane + 1u);
+                            if (lane < nsurv) marks[start] = lane + 1u;
                             __builtin_amdgcn_wave_barrier();
-                            const uint32_t owner = wave_scan_max((uint32_t)sC[wave][lane]) - 1u;
-                            const uint32_t packed = (uint32_t)sS[wave][min(lane, nsurv - 1u)] | (start << 8) | (mk << 16);   // of survivor `lane`
+                            const uint32_t owner = wave_scan_max(marks[lane]) - 1u;
+                            const uint32_t packed = min(lane, nsurv - 1u) | (start << 8) | (mk << 16);   // of survivor `lane`
                             b_mine = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(owner << 2), (int)packed);
                             b_used = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
                         }
@@ -2126,14 +2163,14 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                         const bool act = balanced ? lane < b_used : (q < group && sidx < nsurv);
                         VF_RC({ const uint32_t na = (uint32_t)__popcll(__ballot(act)); if (lane == 0) { RC.iters++; RC.act += na; } })
                         if (act) {
-                            const uint32_t code = balanced ? (b_mine & 0xFFu) : (uint32_t)sS[wave][sidx];
+                            const uint32_t sw = sS[wave][balanced ? (b_mine & 0xFFu) : sidx], code = sw & 0x7Fu;
                             const uint32_t my_sub = balanced ? lane - ((b_mine >> 8) & 0xFFu) : sub, my_n = balanced ? b_mine >> 16 : per;
                             const uint32_t cell = code >> 1, odd = code & 1u;
                             const uint32_t lj = cell >> 3, li = cell & 7u;
                             const uint32_t va = lj * kBlockVerts + li, vb = va + 1, vc = va + kBlockVerts, vd = vc + 1;
                             const uint32_t v0 = odd ? vb : va, v1 = vc, v2 = odd ? vd : vb;
                             const uint32_t prim = 2u * ((j0 + lj) * P.nm1 + (i0 + li)) + odd;
-                            raster_fast<GROUPS>(T, prim + 1u, sXY[wave], v0 | (v1 << 8) | (v2 << 16), (int32_t)my_sub, (int32_t)my_n, lane - my_sub VF_RC(, RC));
+                            raster_fast<GROUPS, GROUPS>(T, prim + 1u, sXY[wave], v0 | (v1 << 8) | (v2 << 16), (int32_t)my_sub, (int32_t)my_n, lane - my_sub VF_RC(, RC), sw >> 7);
                         }
                         if (balanced) break;
                     }
@@ -2228,6 +2265,11 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
             uint32_t li = RC.l_iter;
             for (int o = 32; o > 0; o >>= 1) li += __shfl_xor(li, o);
             if (lane == 0) atomicAdd(&ph[34], (unsigned long long)li);
+        }
+        {   // four-line groups with an open pixel in their box (lanes), executions of the group's span bound (waves)
+            uint32_t go = RC.g_open, ws = RC.w_sg;
+            for (int o = 32; o > 0; o >>= 1) { go += __shfl_xor(go, o); ws += __shfl_xor(ws, o); }
+            if (lane == 0) { atomicAdd(&ph[38], (unsigned long long)go); atomicAdd(&ph[39], (unsigned long long)ws); }
         }
         uint32_t rcs[4] = { RC.lines, RC.solved, RC.painted, RC.trips };   // (paint_lines gave way to: lines with an open pixel in their bounding range)
         for (int c = 0; c < 4; ++c) {
