@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <vector>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -164,7 +165,8 @@ struct vf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipDeviceProp_t prop;
-    float *d_thresh = nullptr;   // 256 sRGB store thresholds
+    float *d_decode = nullptr;   // 256 sRGB8 -> linear (SrgbTables::decode), the head of the one allocation that holds both tables
+    float *d_thresh = nullptr;   // 256 sRGB store thresholds, behind it
     // Streams the handles of this context borrow, made on first need: a stream costs 3-10 ms to create and 2-3 ms to destroy on this
     // runtime (round 5, measured), so they belong to the process-lifetime context, not to every handle.  side / side2: a frame's plan
     // chain and set-up pass (they overlap the previous frame's tile kernel; a handle's first frame needs neither); copy: batch read-back.
@@ -233,6 +235,29 @@ template <typename T> struct DevBuf {
         p = nullptr; cap = 0;
     }
 };
+
+// A per-vertex analysis field of a handle with its cache ("The field cache"): when `valid`, d holds the field of `key`
+// and of the heights generation `height_gen`.  The key: the bit patterns of everything beside the heights that the field is computed
+// from, in an order the feature fixes, the lengths of its lists among them.  Keys compare bit for bit: -0 is not +0, a NaN equals itself.
+struct VertexField {
+    DevBuf<float> d;                     // n x n, row-major
+    bool valid = false;
+    uint64_t height_gen = 0;
+    std::vector<uint32_t> key;
+    uint32_t scans = 0;                  // times the field was computed (the vf_terrain_debug_*_scans calls)
+    // *current: d holds the field of `k` and the handle's heights, and force is not set.  Otherwise d is ready to be computed: allocated
+    // (nomem: the feature's message when that fails) and not valid until computed(), so launches that fail leave no field behind.
+    int prepare(const vf_terrain *t, const std::vector<uint32_t> &k, bool force, const char *nomem, bool *current);
+    void computed(const vf_terrain *t, std::vector<uint32_t> &k);   // the launches are queued: d is the field of `k` (which is taken)
+    void release() { d.release(); valid = false; }                  // the buffer goes, the count stays
+};
+static uint32_t key_bits(float f) { uint32_t w; std::memcpy(&w, &f, sizeof w); return w; }
+static std::vector<uint32_t> key_of(std::initializer_list<float> fs)
+{
+    std::vector<uint32_t> k;
+    for (float f : fs) k.push_back(key_bits(f));
+    return k;
+}
 
 // Diagnostics: the mean time in ms of `repeats` back-to-back launches on `s`, between two events behind one warm-up launch.
 // launch(warm) queues one launch and returns its error; the first error ends the measurement and is returned.
@@ -386,12 +411,8 @@ struct vf_terrain {
     struct Shadows {
         bool enabled = false;
         float strength = 0.7f, softness = 0.02f, bias = 0.002f;
-        DevBuf<float> d_lit;             // n x n, row-major
+        VertexField lit;                 // key: sun (3), spacing, exaggeration, strength, softness, bias
         DevBuf<float> d_cmax;            // chunk maxima / carries of the scan: nchunks x nlines
-        bool valid = false;              // d_lit holds the field of `key` and heights generation `height_gen`
-        uint64_t height_gen = 0;
-        float key[8] = {};               // sun (3), spacing, exaggeration, strength, softness, bias
-        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_shadow_scans)
     } sh;
     // ambient occlusion: the same rules; the sun, the camera and `strength` are not part of the field
     struct Ambient {
@@ -400,12 +421,7 @@ struct vf_terrain {
         uint32_t ndirs = VF_AMBIENT_DIRECTIONS;
         bool default_dirs = true;        // dirs holds the default set of ndirs directions (made when first needed)
         std::vector<float> dirs;         // ndirs x (ux, uz)
-        DevBuf<float> d_sky;             // n x n, row-major
-        bool valid = false;              // d_sky holds the field of `key`, `key_dirs` and heights generation `height_gen`
-        uint64_t height_gen = 0;
-        float key[3] = {};               // spacing, exaggeration, reach
-        std::vector<float> key_dirs;
-        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_ambient_scans)
+        VertexField sky;                 // key: spacing, exaggeration, reach, the length of dirs, dirs
     } am;
     // the draped image: everything is made by set_drape and freed by clear_drape; iw = 0: none
     struct Drape {
@@ -413,7 +429,6 @@ struct vf_terrain {
         float extent[4] = { -1.5f, -1.5f, 1.5f, 1.5f }, opacity = 1.0f;
         int filter = VF_DRAPE_LINEAR;
         DevBuf<uint32_t> d_img;          // iw x ih RGBA8 words, row-major
-        DevBuf<float> d_decode;          // 256 sRGB8 -> linear (SrgbTables::decode)
         hipEvent_t copied = nullptr;     // behind set_drape_device's copy on the caller's stream: the frames' shade passes wait for it
     } dr;
     // its mip pyramid: enabled and bias are the handle's and survive set_drape / clear_drape; the rest belongs to the
@@ -433,14 +448,9 @@ struct vf_terrain {
         float eye_height = VF_VIEWSHED_EYE_HEIGHT, target_height = VF_VIEWSHED_TARGET_HEIGHT, radius = 0.0f;
         float softness = VF_VIEWSHED_SOFTNESS, bias = VF_VIEWSHED_BIAS;
         uint32_t visible_rgba = VF_VIEWSHED_VISIBLE_RGBA, hidden_rgba = VF_VIEWSHED_HIDDEN_RGBA;   // r | g << 8 | b << 16 | a << 24
-        DevBuf<float> d_seen;            // n x n, row-major
+        bool tinted = false;             // enabled once since the observer was set (vf_terrain_debug_viewshed_stage asks for it)
+        VertexField seen;                // key: exaggeration, eye_height, target_height, softness, bias, the observer's vertex (i, j)
         DevBuf<float> d_cmax;            // chunk maxima / carries of the scan: 4 quadrants x nchunks x nlines
-        DevBuf<float> d_decode;          // 256 sRGB8 -> linear (SrgbTables::decode)
-        bool valid = false;              // d_seen holds the field of `key`, vertex `key_ij` and heights generation `height_gen`
-        uint64_t height_gen = 0;
-        float key[5] = {};               // exaggeration, eye_height, target_height, softness, bias
-        uint32_t key_ij[2] = {};
-        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_viewshed_scans)
     } vs;
     // cumulative viewsheds: buffers made by the first tinted frame or field read; the sums are formed again only when
     // what they were made from has changed (not for the colours, the camera or the sun)
@@ -452,16 +462,12 @@ struct vf_terrain {
         uint32_t high_rgba = VF_CUMULATIVE_VIEWSHED_HIGH_RGBA, low_rgba = VF_CUMULATIVE_VIEWSHED_LOW_RGBA;
         uint32_t forced_batch = 0;       // vf_terrain_debug_cumulative_viewshed_batch; 0: from the memory budget
         DevBuf<uint32_t> d_sum;          // n x n sums of q
-        DevBuf<float> d_count, d_frac;   // n x n: sum / 65536, and that over N
+        VertexField count;               // sum / 65536; key: exaggeration, eye_height, target_height, softness, bias, Rc (-1: no radius), the
+                                         // length of the vertex list, the observers' vertices (i, j) each
+        DevBuf<float> d_frac;            // n x n: count / N
         DevBuf<float> d_cmax;            // carries of a batch: B x 4 quadrants x nchunks x nlines
         DevBuf<ViewshedPlan> d_plans;    // one per observer
-        DevBuf<float> d_decode;          // 256 sRGB8 -> linear
         std::vector<ViewshedPlan> plans; // the host's copy of d_plans (the source of its upload)
-        bool valid = false;              // d_count / d_frac hold the field of `key`, `key_ij` and heights generation `height_gen`
-        uint64_t height_gen = 0;
-        float key[6] = {};               // exaggeration, eye_height, target_height, softness, bias, Rc (0: no radius)
-        std::vector<uint32_t> key_ij;    // the observers' vertices, (i, j) each
-        uint32_t scans = 0;              // times the field was computed (vf_terrain_debug_cumulative_viewshed_scans)
         uint32_t batch = 0;              // the batch size of the last computation
     } cv;
     uint64_t height_gen = 1;             // counts height uploads
@@ -577,7 +583,6 @@ struct vf_terrain {
         DevBuf<uint2> box;                   // [nprims] bin rectangle
         uint32_t *d_cnt = nullptr;           // [nbins] pairs per bin (zero between frames)
         uint32_t *d_start = nullptr;         // [nbins + 1] each bin's slice of the pair list; [nbins] = pairs in all
-        float *d_decode = nullptr;           // 256 sRGB8 -> linear (SrgbTables::decode)
         DevBuf<uint32_t> list;               // pair list (primitive indices)
         uint32_t *h_total = nullptr;         // pinned: the frame's pair count (the list is sized by it); [2..3] the mask words (fills)
         hipEvent_t counted = nullptr;
@@ -617,6 +622,27 @@ static StatsLayout stats_layout(const vf_terrain *t)
 static size_t feedback_words(const vf_terrain *t) { return (size_t)t->ntx * t->nty * 65 + 1; }
 // 16-block segments of the grid's block rows
 static uint32_t grid_segments(const vf_terrain *t) { return t->nb * ((t->nb + kSegBlocks - 1) / kSegBlocks); }
+// the pitch of the grid's vertices (FrameParams::step) and the spacing of a uniform block (terrain.wgsl:46)
+static float grid_step(const vf_terrain *t) { return (2.0f * 1.5f) / ((float)t->n - 1.0f); }
+static float spacing_of(const float *u) { return std::fmax(u[36], 1e-8f); }
+
+int VertexField::prepare(const vf_terrain *t, const std::vector<uint32_t> &k, bool force, const char *nomem, bool *current)
+{
+    if (!d.p) {
+        const size_t nv = (size_t)t->n * t->n;
+        if (d.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, nomem); }
+        valid = false;
+    }
+    *current = !force && valid && height_gen == t->height_gen && key == k;
+    if (!*current) valid = false;
+    return VF_OK;
+}
+
+void VertexField::computed(const vf_terrain *t, std::vector<uint32_t> &k)
+{
+    key.swap(k);
+    height_gen = t->height_gen; valid = true; scans++;
+}
 
 extern "C" {
 
@@ -674,8 +700,11 @@ int vf_ctx_create(int device_ordinal, vf_ctx **out)
     hipError_t err = hipSetDevice(device_ordinal);
     if (err == hipSuccess) err = hipGetDeviceProperties(&c->prop, device_ordinal);
     if (err == hipSuccess) err = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipMalloc(&c->d_thresh, 256 * sizeof(float));
-    if (err == hipSuccess) err = hipMemcpy(c->d_thresh, tables().thresh, 256 * sizeof(float), hipMemcpyHostToDevice);
+    static_assert(offsetof(SrgbTables, decode) == 0 && offsetof(SrgbTables, thresh) == 256 * sizeof(float) && sizeof(SrgbTables) == 512 * sizeof(float),
+                  "both tables go up in one copy");
+    if (err == hipSuccess) err = hipMalloc(&c->d_decode, sizeof(SrgbTables));
+    if (err == hipSuccess) err = hipMemcpy(c->d_decode, &tables(), sizeof(SrgbTables), hipMemcpyHostToDevice);
+    if (err == hipSuccess) c->d_thresh = c->d_decode + 256;
     if (err != hipSuccess) {
         std::string m = std::string("context creation failed: ") + hipGetErrorString(err);
         vf_ctx_destroy(c);
@@ -689,7 +718,7 @@ void vf_ctx_destroy(vf_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->d_thresh) (void)hipFree(c->d_thresh);
+    if (c->d_decode) (void)hipFree(c->d_decode);
     if (c->d_maps) (void)hipFree(c->d_maps);
     for (hipStream_t q : { c->side, c->side2, c->copy }) if (q) (void)hipStreamDestroy(q);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -833,7 +862,7 @@ static int refresh_tables(vf_terrain *t, hipStream_t s)
 static void ov_release(vf_terrain *t)
 {
     vf_terrain::Overlays &O = t->ov;
-    void *ptrs[] = { O.d_cnt, O.d_start, O.d_decode };
+    void *ptrs[] = { O.d_cnt, O.d_start };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     O.in.release(); O.prim.release(); O.box.release(); O.list.release(); O.dep.release();
     O.pg_hdr.release(); O.pg_fbox.release(); O.pg_fbin.release(); O.pg_total.release(); O.mask.release();
@@ -847,20 +876,34 @@ static void ov_release(vf_terrain *t)
 static void drape_release(vf_terrain *t)
 {
     vf_terrain::Drape &D = t->dr;
-    D.d_img.release(); D.d_decode.release();
+    D.d_img.release();
     if (D.copied) (void)hipEventDestroy(D.copied);
     D = vf_terrain::Drape();
     t->dm.d_pyr.release(); t->dm.stale = true;              // (the pyramid goes with its image; the setting stays)
+}
+
+// the shadow and sky-view fields with the scan's carries (their settings stay)
+static void shadow_release(vf_terrain *t) { t->sh.lit.release(); t->sh.d_cmax.release(); }
+static void ambient_release(vf_terrain *t) { t->am.sky.release(); }
+
+// the viewshed: gone, as if the handle never had an observer (the caller has synchronised); the scan counter stays
+static void viewshed_release(vf_terrain *t)
+{
+    vf_terrain::Viewshed &H = t->vs;
+    H.seen.release(); H.d_cmax.release();
+    const uint32_t scans = H.seen.scans;
+    H = vf_terrain::Viewshed();
+    H.seen.scans = scans;
 }
 
 // the cumulative viewshed: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced batch size stay
 static void cumulative_release(vf_terrain *t)
 {
     vf_terrain::CumulativeViewshed &H = t->cv;
-    H.d_sum.release(); H.d_count.release(); H.d_frac.release(); H.d_cmax.release(); H.d_plans.release(); H.d_decode.release();
-    const uint32_t scans = H.scans, forced = H.forced_batch;
+    H.d_sum.release(); H.count.release(); H.d_frac.release(); H.d_cmax.release(); H.d_plans.release();
+    const uint32_t scans = H.count.scans, forced = H.forced_batch;
     H = vf_terrain::CumulativeViewshed();
-    H.scans = scans; H.forced_batch = forced;
+    H.count.scans = scans; H.forced_batch = forced;
 }
 
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
@@ -938,9 +981,8 @@ void vf_terrain_destroy(vf_terrain *t)
     (void)hipDeviceSynchronize();
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    t->d_gb.release(); t->d_pick.release(); t->sh.d_lit.release(); t->sh.d_cmax.release(); t->am.d_sky.release();
-    t->vs.d_seen.release(); t->vs.d_cmax.release(); t->vs.d_decode.release();
-    cumulative_release(t);
+    t->d_gb.release(); t->d_pick.release();
+    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t);
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -1305,7 +1347,7 @@ static void build_params(const vf_terrain *t, const FrameInputs &in, FrameParams
     const float *u = in.u;
     std::memcpy(P.view, u, 64);
     std::memcpy(P.proj, u + 16, 64);
-    P.spacing = std::fmax(u[36], 1e-8f);       // terrain.wgsl:46
+    P.spacing = spacing_of(u);       // terrain.wgsl:46
     P.exag = u[38];
     P.h_range = std::fmax(u[37], 1e-8f);       // terrain.wgsl:71
     P.exposure = u[35];
@@ -1315,7 +1357,7 @@ static void build_params(const vf_terrain *t, const FrameInputs &in, FrameParams
         P.Lx = sx * inv; P.Ly = sy * inv; P.Lz = sz * inv;
     }
     P.hw = 0.5f * (float)t->W; P.hh = 0.5f * (float)t->H;
-    P.step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    P.step = grid_step(t);
     P.n = t->n; P.nm1 = t->n - 1; P.nb = t->nb;
     P.W = t->W; P.H = t->H; P.ntx = t->ntx; P.nty = t->nty; P.tw = t->tw; P.th = t->th;
     P.rank = t->rank; P.nranks = t->nranks; P.band_h = t->band_h; P.band_shift = ilog2(t->band_h);
@@ -1342,7 +1384,7 @@ static void build_params(const vf_terrain *t, const FrameInputs &in, FrameParams
 // other content.  A corner behind either camera counts as "moved".
 static float camera_shift_px(const vf_terrain *t, const float *a, const float *b)
 {
-    const float ext = 1.5f * std::fmax(t->inputs.u[36], 1e-8f);
+    const float ext = 1.5f * spacing_of(t->inputs.u);
     float worst = 0.0f;
     for (int c = 0; c < 4; ++c) {
         const float p[4] = { (c & 1) ? ext : -ext, 0.0f, (c & 2) ? ext : -ext, 1.0f };
@@ -1596,10 +1638,10 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay pair list allocation failed: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.box.p, nbx, O.d_start, O.d_cnt, O.list.p);
     if (occlude)
-        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, O.d_decode,
+        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
                            t->ctx->d_thresh, O.mask.p, t->d_rgba, P, V, t->d_vis, O.dep.p);
     else
-        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, O.d_decode,
+        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
                            t->ctx->d_thresh, O.mask.p, t->d_rgba);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
@@ -1933,7 +1975,7 @@ int vf_terrain_sync(vf_terrain *t)
 
 static float ov_clamp_px(float v) { return std::fmin(std::fmax(v, 1.0f), 64.0f); }
 
-static uint32_t ov_rgba(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
+static uint32_t pack_rgba8(const uint8_t c[4]) { return (uint32_t)c[0] | ((uint32_t)c[1] << 8) | ((uint32_t)c[2] << 16) | ((uint32_t)c[3] << 24); }
 
 static int ov_usable(const vf_terrain *t)
 {
@@ -1969,8 +2011,6 @@ static int ov_append(vf_terrain *t, size_t nadd, const OvProducer &produce, cons
         hipError_t e = hipMalloc(&O.d_cnt, (size_t)nbins * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(&O.d_start, ((size_t)nbins + 1u) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&O.d_decode, 256 * sizeof(float));
-        if (e == hipSuccess) e = hipMemcpy(O.d_decode, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipHostMalloc((void **)&O.h_total, 4 * sizeof(uint32_t), hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&O.counted, hipEventDisableTiming);
         if (e != hipSuccess) { ov_release(t); return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e)); }
@@ -2039,7 +2079,7 @@ int vf_terrain_add_points(vf_terrain *t, const float *xyz, uint32_t n, const flo
         for (int c = 0; c < 3; ++c) { q.p0[c] = p[c]; q.p1[c] = p[c]; }
         q.size = ov_clamp_px(sz) * 0.5f;
         q.flags = (shape == VF_SHAPE_SQUARE ? kOvSquare : kOvCircle) | (drape ? kOvDrape : 0u);
-        q.rgba = ov_rgba(rgba ? rgba + 4u * k : default_rgba);
+        q.rgba = pack_rgba8(rgba ? rgba + 4u * k : default_rgba);
         q.feature = feature++;
         add.push_back(q);
     }
@@ -2090,7 +2130,7 @@ int vf_terrain_add_lines(vf_terrain *t, const float *xyz, const uint32_t *path_o
             for (int c = 0; c < 3; ++c)
                 if (!std::isfinite(xyz[3u * v + c])) return fail(VF_ERR_INVALID, "a line vertex is not finite");
         if (int rc = ov_budget(t->ov.nprims + add.size(), 2ull * (v1 - v0))) return rc;
-        ov_path(xyz, v0, v1, false, hw, ov_rgba(rgba), cap, base, feature++, add);
+        ov_path(xyz, v0, v1, false, hw, pack_rgba8(rgba), cap, base, feature++, add);
     }
     return ov_append(t, add, {}, 0, false, feature, layer_id);
 }
@@ -2131,7 +2171,7 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
             if (int rc = ov_budget(O.nprims + add.size(), n)) return rc;
             hdr.push_back(O.nprims + (uint32_t)add.size());
             OvIn h{};
-            h.size = kbits; h.flags = kOvPoly | kPgHeader; h.rgba = ov_rgba(fill_rgba ? fill_rgba + 4u * f : default_fill); h.feature = feature;
+            h.size = kbits; h.flags = kOvPoly | kPgHeader; h.rgba = pack_rgba8(fill_rgba ? fill_rgba + 4u * f : default_fill); h.feature = feature;
             add.push_back(h);
             for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) {
                 const uint32_t v0 = ring_offsets[r], nv = ring_offsets[r + 1] - v0, first = O.nprims + (uint32_t)add.size();
@@ -2153,7 +2193,7 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
             for (uint32_t r = feature_offsets[f]; r < feature_offsets[f + 1]; ++r) {
                 const uint32_t v0 = ring_offsets[r], v1 = ring_offsets[r + 1];
                 if (int rc = ov_budget(O.nprims + add.size(), 2ull * (v1 - v0) + 1u)) return rc;
-                ov_path(xyz, v0, v1, true, hw, ov_rgba(line_rgba), VF_CAP_ROUND, base, feature++, add);
+                ov_path(xyz, v0, v1, true, hw, pack_rgba8(line_rgba), VF_CAP_ROUND, base, feature++, add);
             }
     }
     return ov_append(t, add, hdr, nfillrec, true, feature, layer_id);
@@ -2248,7 +2288,7 @@ int vf_terrain_add_contours(vf_terrain *t, const float *levels, uint32_t nlevels
     if (e == hipSuccess) e = C.total.reserve(1, 1);
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("contour allocation failed: ") + hipGetErrorString(e));
     VF_HIP_TRY(hipMemcpyAsync(C.levels.p, levels, nlevels * sizeof(float), hipMemcpyHostToDevice, s));
-    const CtGrid G = { t->n - 1u, t->nb, (2.0f * 1.5f) / ((float)t->n - 1.0f), std::fmax(t->inputs.u[36], 1e-8f), t->d_hblk, t->d_bounds, C.levels.p, nlevels };
+    const CtGrid G = { t->n - 1u, t->nb, grid_step(t), spacing_of(t->inputs.u), t->d_hblk, t->d_bounds, C.levels.p, nlevels };
     hipLaunchKernelGGL(k_ct_count, dim3(t->nblocks), dim3(64), 0, s, G, C.count.p);
     VF_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_ct_scan, dim3(1), dim3(1024), 0, s, t->nblocks, C.count.p, C.total.p);
@@ -2263,7 +2303,7 @@ int vf_terrain_add_contours(vf_terrain *t, const float *levels, uint32_t nlevels
                                     std::to_string(t->ov.nprims) + " exceed the 2^24 primitive budget: fewer levels, VF_JOIN_NONE or a coarser grid");
     const float kb = 1.0f + depth_bias;                       // as vf_terrain_set_layer_occlusion forms it
     CtStyle S = {};
-    S.hw = ov_clamp_px(width_px) * 0.5f; S.lift = lift; S.rgba = ov_rgba(rgba); S.feature = t->ov.features;
+    S.hw = ov_clamp_px(width_px) * 0.5f; S.lift = lift; S.rgba = pack_rgba8(rgba); S.feature = t->ov.features;
     S.base = kOvDrape | (occlude ? kOvOcclude : 0u); S.round = round ? 1u : 0u;
     if (occlude) std::memcpy(&S.kb_bits, &kb, sizeof kb);
     const int rc = ov_append(t, (size_t)nrec, [&](OvIn *dst) -> int {
@@ -2661,29 +2701,24 @@ static bool shadow_plan(const vf_terrain *t, const float *u, ShadowPlan &S)
     const float sy = u[33];
     float amaj;
     if (!line_geometry(t, u[32], u[34], S, amaj) || !std::isfinite(sy)) return false;
-    const float spacing = std::fmax(u[36], 1e-8f);
-    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
-    const float d = sy > 0.0f ? ((step * spacing) * sy) / amaj : 0.0f;
+    const float d = sy > 0.0f ? ((grid_step(t) * spacing_of(u)) * sy) / amaj : 0.0f;
     if (!std::isfinite(d)) return false;
     S.d = d; S.exag = u[38]; S.strength = H.strength; S.softness = H.softness; S.bias = H.bias;
     return true;
 }
 
-// d_lit holds the field of the uniforms `u`, the handle's heights and shadow parameters once the work queued on `s` is done.  The
+// `lit` holds the field of the uniforms `u`, the handle's heights and shadow parameters once the work queued on `s` is done.  The
 // displaced-height cache must be current and ordered before `s` (a frame's plan, ct_heights_current).  force: compute it anyway.
 static int shadow_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false)
 {
     vf_terrain::Shadows &H = t->sh;
+    std::vector<uint32_t> key = key_of({ u[32], u[33], u[34], spacing_of(u), u[38], H.strength, H.softness, H.bias });
+    bool current;
+    if (int rc = H.lit.prepare(t, key, force, "shadow field allocation failed", &current)) return rc;
+    if (current) return VF_OK;
     const size_t nv = (size_t)t->n * t->n;
-    if (!H.d_lit.p) {
-        if (H.d_lit.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow field allocation failed"); }
-        H.valid = false;
-    }
-    const float key[8] = { u[32], u[33], u[34], std::fmax(u[36], 1e-8f), u[38], H.strength, H.softness, H.bias };
-    if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0) return VF_OK;
-    H.valid = false;
     ShadowPlan S;
-    if (!shadow_plan(t, u, S)) hipLaunchKernelGGL((k_shadow_fill<0>), dim3((uint32_t)((nv + 255u) / 256u)), dim3(256), 0, s, nv, H.d_lit.p);
+    if (!shadow_plan(t, u, S)) hipLaunchKernelGGL((k_shadow_fill<0>), dim3((uint32_t)((nv + 255u) / 256u)), dim3(256), 0, s, nv, H.lit.d.p);
     else {
         // (grown once, to what any sun needs: at most 2n - 1 lines)
         if (H.d_cmax.reserve((size_t)S.nchunks * S.nlines, (size_t)S.nchunks * 2u * t->n) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "shadow scan allocation failed"); }
@@ -2691,12 +2726,11 @@ static int shadow_field(vf_terrain *t, const float *u, hipStream_t s, bool force
         if (S.zmajor) hipLaunchKernelGGL((k_shadow_chunk_max<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
         else hipLaunchKernelGGL((k_shadow_chunk_max<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
         hipLaunchKernelGGL((k_shadow_carry<0>), dim3((S.nlines + 255u) / 256u), threads, 0, s, S.nlines, S.nchunks, H.d_cmax.p);
-        if (S.zmajor) hipLaunchKernelGGL((k_shadow_lit<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_lit.p);
-        else hipLaunchKernelGGL((k_shadow_lit<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_lit.p);
+        if (S.zmajor) hipLaunchKernelGGL((k_shadow_lit<true>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.lit.d.p);
+        else hipLaunchKernelGGL((k_shadow_lit<false>), grid, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.lit.d.p);
     }
     VF_HIP_TRY(hipGetLastError());
-    std::memcpy(H.key, key, sizeof key);
-    H.height_gen = t->height_gen; H.valid = true; H.scans++;
+    H.lit.computed(t, key);
     return VF_OK;
 }
 
@@ -2742,7 +2776,7 @@ static void mips_launch(const vf_terrain *t, hipStream_t s, const MipLayout &L)
         uint2 *d[3];
         for (uint32_t q = 0; q < 3u; ++q) d[q] = q < nout ? M.d_pyr.p + L.off[k + 1u + q] : nullptr;
         const dim3 grid((L.w[k] + 63u) / 64u, (L.h[k] + 31u) / 32u), threads(256);
-        if (k == 0u) hipLaunchKernelGGL((k_drape_mips<true>), grid, threads, 0, s, (const void *)t->dr.d_img.p, (const float *)t->dr.d_decode.p, L.w[k], L.h[k], nout, d[0], d[1], d[2]);
+        if (k == 0u) hipLaunchKernelGGL((k_drape_mips<true>), grid, threads, 0, s, (const void *)t->dr.d_img.p, (const float *)t->ctx->d_decode, L.w[k], L.h[k], nout, d[0], d[1], d[2]);
         else hipLaunchKernelGGL((k_drape_mips<false>), grid, threads, 0, s, (const void *)(M.d_pyr.p + L.off[k]), (const float *)nullptr, L.w[k], L.h[k], nout, d[0], d[1], d[2]);
     }
 }
@@ -2775,8 +2809,8 @@ static void relight_launch(const vf_terrain *t, hipStream_t s, const FrameParams
                            bool shadows, bool ambient)
 {
     RelightParams R = {};
-    R.lit = shadows || pass == kShadow ? t->sh.d_lit.p : nullptr;
-    R.sky = ambient || pass == kAmbient ? t->am.d_sky.p : nullptr;
+    R.lit = shadows || pass == kShadow ? t->sh.lit.d.p : nullptr;
+    R.sky = ambient || pass == kAmbient ? t->am.sky.d.p : nullptr;
     R.amb_strength = t->am.strength;
     const dim3 grid = gb_grid(t), threads(256);
 #define VF_RELIGHT(CLIPPED, PASS) hipLaunchKernelGGL((k_relight<CLIPPED, PASS>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh, \
@@ -2785,7 +2819,7 @@ static void relight_launch(const vf_terrain *t, hipStream_t s, const FrameParams
     else if (pass == kAmbient) { VF_RELIGHT(false, kAmbient); VF_RELIGHT(true, kAmbient); }
     else {
         const vf_terrain::Drape &H = t->dr;
-        R.decode = H.d_decode.p; R.img = H.d_img.p;
+        R.decode = t->ctx->d_decode; R.img = H.d_img.p;
         DrapeParams &D = R.D;
         D.x0 = H.extent[0]; D.z0 = H.extent[1];
         D.sx = (float)H.iw / (H.extent[2] - H.extent[0]); D.sz = (float)H.ih / (H.extent[3] - H.extent[1]);
@@ -2836,23 +2870,38 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
     return VF_OK;
 }
 
-// The shadow field (which = 0), the sky-view field (1) or the viewshed field (2) for the live uniforms, heights and parameters, complete in d_lit / d_sky; then
-// to `host`, or to `dev` behind the work on `stream` (NULL: the handle's)
 static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
-
 static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 
-static int field_out(vf_terrain *t, int which /* 0 lit, 1 sky, 2 seen, 3 count */, float *host, float *dev, void *stream)
+// The per-vertex fields a caller can have.  A new one is a feature struct that holds a VertexField, its *_field function and a row here.
+enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFields };
+struct FieldRow {
+    int (*compute)(vf_terrain *, const float *, hipStream_t, bool);   // its *_field function
+    VertexField &(*cache)(vf_terrain *);                               // its buffer, key and scan counter
+    const char *(*refusal)(const vf_terrain *);                        // why the handle cannot have it now (nullptr: it can); no rule: nullptr
+};
+static const FieldRow kFieldTable[kFields] = {
+    { shadow_field, [](vf_terrain *t) -> VertexField & { return t->sh.lit; }, nullptr },
+    { ambient_field, [](vf_terrain *t) -> VertexField & { return t->am.sky; }, nullptr },
+    { viewshed_field, [](vf_terrain *t) -> VertexField & { return t->vs.seen; },
+      [](const vf_terrain *t) -> const char * { return t->vs.have_observer ? nullptr : "no observer set (vf_terrain_set_viewshed)"; } },
+    { cumulative_field, [](vf_terrain *t) -> VertexField & { return t->cv.count; },
+      [](const vf_terrain *t) -> const char * { return t->cv.xz.empty() ? "no observers set (vf_terrain_set_cumulative_viewshed)" : nullptr; } },
+};
+
+// Field f for the live uniforms, heights and parameters, complete in its buffer; then to `host`, or to `dev` behind the work on
+// `stream` (NULL: the handle's)
+static int field_out(vf_terrain *t, Field f, float *host, float *dev, void *stream)
 {
-    const bool sky = which == 1;
+    if (!t || !(host || dev)) return fail(VF_ERR_INVALID, "NULL argument");
+    const FieldRow &R = kFieldTable[f];
+    if (const char *why = R.refusal ? R.refusal(t) : nullptr) return fail(VF_ERR_INVALID, why);
     if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     if (int rc = ct_heights_current(t)) return rc;
-    if (which == 2) { if (int rc = viewshed_field(t, t->inputs.u, t->ctx->stream)) return rc; }
-    else if (which == 3) { if (int rc = cumulative_field(t, t->inputs.u, t->ctx->stream)) return rc; }
-    else if (int rc = relight_fields(t, t->inputs.u, t->ctx->stream, !sky, sky)) return rc;
+    if (int rc = R.compute(t, t->inputs.u, t->ctx->stream, false)) return rc;
     VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    const float *field = which == 3 ? t->cv.d_count.p : which == 2 ? t->vs.d_seen.p : sky ? t->am.d_sky.p : t->sh.d_lit.p;
+    const float *field = R.cache(t).d.p;
     const size_t bytes = (size_t)t->n * t->n * sizeof(float);
     if (host) { VF_HIP_TRY(hipMemcpy(host, field, bytes, hipMemcpyDeviceToHost)); return VF_OK; }
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
@@ -2861,35 +2910,39 @@ static int field_out(vf_terrain *t, int which /* 0 lit, 1 sky, 2 seen, 3 count *
     return VF_OK;
 }
 
-int vf_terrain_read_shadow_field(vf_terrain *t, float *lit)
-{
-    if (!t || !lit) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, 0, lit, nullptr, nullptr);
-}
-
-int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream)
-{
-    if (!t || !dev_lit) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, 0, nullptr, dev_lit, stream);
-}
-
-int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count)
+static int field_scans(vf_terrain *t, Field f, uint32_t *count)
 {
     if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
-    *count = t->sh.scans;
+    *count = kFieldTable[f].cache(t).scans;
     return VF_OK;
 }
 
-// What the three stage calls below start from: the frame rendered last, drawn again into scratch buffers with its visibility
-// (gb_frame), the uniforms it was drawn with and its `redo` word.  Their launches are diagnostic, not the handle's: the scan
-// counters are handed back as open() found them, whichever way the call returns.
+int vf_terrain_read_shadow_field(vf_terrain *t, float *lit) { return field_out(t, kFieldLit, lit, nullptr, nullptr); }
+int vf_terrain_shadow_field_device(vf_terrain *t, float *dev_lit, void *stream) { return field_out(t, kFieldLit, nullptr, dev_lit, stream); }
+int vf_terrain_debug_shadow_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldLit, count); }
+
+// Diagnostic launches are not the handle's: the scan counters of every field are handed back as hold() found them, whichever way
+// the call returns.
+struct ScansHeld {
+    vf_terrain *t = nullptr;
+    uint32_t scans[kFields] = {};
+    void hold(vf_terrain *handle)
+    {
+        t = handle;
+        for (int f = 0; f < kFields; ++f) scans[f] = kFieldTable[f].cache(t).scans;
+    }
+    ~ScansHeld() { for (int f = 0; t && f < kFields; ++f) kFieldTable[f].cache(t).scans = scans[f]; }
+};
+
+// What the stage calls below start from: the frame rendered last, drawn again into scratch buffers with its visibility (gb_frame),
+// the uniforms it was drawn with and its `redo` word.
 struct RelightStage {
     GbFrame F;
     const float *u = nullptr;
     const uint32_t *redo = nullptr;
     hipStream_t s = nullptr;
     vf_terrain *t = nullptr;
-    uint32_t shadow_scans = 0, ambient_scans = 0, viewshed_scans = 0;
+    ScansHeld held;
     int open(vf_terrain *handle)
     {
         if (int rc = gb_frame(handle, F)) return rc;
@@ -2897,20 +2950,28 @@ struct RelightStage {
         u = (t->have_frame ? t->drawn_inputs : t->inputs).u;
         redo = t->ps[t->last_set].work_count + 3;
         s = t->ctx->stream;
-        shadow_scans = t->sh.scans; ambient_scans = t->am.scans; viewshed_scans = t->vs.scans;
+        held.hold(t);
         return VF_OK;
     }
-    // the shade pass into the scratch frame, timed; the fields it reads are current
+    // the shade pass into the scratch frame (the fields it reads are current), and timed
+    void shade(Relight pass) const { relight_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, pass, t->sh.enabled, t->am.enabled); }
     hipError_t time_shade(uint32_t repeats, float &ms, Relight pass) const
     {
-        return time_launches(s, repeats, ms, [&](bool) { relight_launch(t, s, F.P, F.V, redo, t->d_rgba_scratch, pass, t->sh.enabled, t->am.enabled); return hipGetLastError(); });
+        return time_launches(s, repeats, ms, [&](bool) { shade(pass); return hipGetLastError(); });
     }
-    // a field computed anyway, timed; one that fails has stated its own error: rc
-    hipError_t time_field(uint32_t repeats, float &ms, bool sky, int &rc) const
+    // ms[0]: field() timed, a field computed anyway, which states its own error when it fails; ms[1]: shade() timed, the pass that
+    // reads what the field's last launch left.  label: whose diagnostics these are.
+    int time_pair(uint32_t repeats, float ms[2], const char *label, const std::function<int()> &field, const std::function<void()> &shade) const
     {
-        return time_launches(s, repeats, ms, [&](bool) { rc = relight_fields(t, u, s, !sky, sky, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+        int rc = VF_OK;
+        float a = 0.0f, b = 0.0f;
+        hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = field(); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+        if (err == hipSuccess) err = time_launches(s, repeats, b, [&](bool) { shade(); return hipGetLastError(); });
+        if (rc != VF_OK) return rc;
+        if (err != hipSuccess) return fail(VF_ERR_HIP, std::string(label) + " diagnostics: " + hipGetErrorString(err));
+        ms[0] = a; ms[1] = b;
+        return VF_OK;
     }
-    ~RelightStage() { if (t) { t->sh.scans = shadow_scans; t->am.scans = ambient_scans; t->vs.scans = viewshed_scans; } }
 };
 
 int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
@@ -2918,16 +2979,8 @@ int vf_terrain_debug_shadow_stage(vf_terrain *t, uint32_t repeats, float ms[2])
     if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
     if (repeats == 0) repeats = 1;
     RelightStage G;
-    int rc = G.open(t);
-    if (rc != VF_OK) return rc;
-    float a = 0.0f, b = 0.0f;
-    // the field first (its last launch leaves what the shade pass reads)
-    hipError_t err = G.time_field(repeats, a, false, rc);
-    if (err == hipSuccess) err = G.time_shade(repeats, b, kShadow);
-    if (rc != VF_OK) return rc;
-    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("shadow diagnostics: ") + hipGetErrorString(err));
-    ms[0] = a; ms[1] = b;
-    return VF_OK;
+    if (int rc = G.open(t)) return rc;
+    return G.time_pair(repeats, ms, "shadow", [&] { return shadow_field(t, G.u, G.s, true); }, [&] { G.shade(kShadow); });
 }
 
 // ---- ambient occlusion (vf_ambient.h) ---------------------------------------------------
@@ -2953,41 +3006,34 @@ static void ambient_plan(const vf_terrain *t, const float *u, float ux, float uz
     float amaj;
     (void)line_geometry(t, ux, uz, S, amaj);
     S.d = 0.0f; S.exag = u[38]; S.strength = 0.0f; S.softness = 1.0f; S.bias = 0.0f;
-    const float spacing = std::fmax(u[36], 1e-8f);
-    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
     const float g = std::sqrt(std::fma(S.a, S.a, 1.0f));
-    A.ell = (step * spacing) * g;
+    A.ell = (grid_step(t) * spacing_of(u)) * g;
     const float rf = std::floor(t->am.reach / g);
     A.R = std::min<uint32_t>(rf >= 1.0f ? (uint32_t)rf : 1u, kAmMaxReach);
 }
 
-// d_sky holds the field of the uniforms `u`, the handle's heights, directions and reach once the work queued on `s` is done (the
+// `sky` holds the field of the uniforms `u`, the handle's heights, directions and reach once the work queued on `s` is done (the
 // height cache must be current and ordered before `s`, as for shadow_field).  force: compute it anyway.
 static int ambient_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::Ambient &H = t->am;
-    const size_t nv = (size_t)t->n * t->n;
-    if (!H.d_sky.p) {
-        if (H.d_sky.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "sky-view field allocation failed"); }
-        H.valid = false;
-    }
     if (H.default_dirs && H.dirs.size() != 2u * H.ndirs) ambient_default_dirs(H.ndirs, H.dirs);
-    const float key[3] = { std::fmax(u[36], 1e-8f), u[38], H.reach };
-    if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0 && H.key_dirs.size() == H.dirs.size()
-        && std::memcmp(H.key_dirs.data(), H.dirs.data(), H.dirs.size() * sizeof(float)) == 0) return VF_OK;
-    H.valid = false;
+    std::vector<uint32_t> key = key_of({ spacing_of(u), u[38], H.reach });
+    key.push_back((uint32_t)H.dirs.size());
+    for (float d : H.dirs) key.push_back(key_bits(d));
+    bool current;
+    if (int rc = H.sky.prepare(t, key, force, "sky-view field allocation failed", &current)) return rc;
+    if (current) return VF_OK;
     for (uint32_t k = 0; k < H.ndirs; ++k) {
         AmbientPlan A;
         ambient_plan(t, u, H.dirs[2u * k], H.dirs[2u * k + 1u], A);
         A.first = k == 0u ? 1u : 0u; A.last = k + 1u == H.ndirs ? 1u : 0u; A.count = (float)H.ndirs;
         const dim3 grid(A.S.nchunks, (A.S.nlines + kShLines - 1u) / kShLines), threads(256);
-        if (A.S.zmajor) hipLaunchKernelGGL((k_ambient_dir<true>), grid, threads, 0, s, A, (const float *)t->d_hblk, H.d_sky.p);
-        else hipLaunchKernelGGL((k_ambient_dir<false>), grid, threads, 0, s, A, (const float *)t->d_hblk, H.d_sky.p);
+        if (A.S.zmajor) hipLaunchKernelGGL((k_ambient_dir<true>), grid, threads, 0, s, A, (const float *)t->d_hblk, H.sky.d.p);
+        else hipLaunchKernelGGL((k_ambient_dir<false>), grid, threads, 0, s, A, (const float *)t->d_hblk, H.sky.d.p);
     }
     VF_HIP_TRY(hipGetLastError());
-    std::memcpy(H.key, key, sizeof key);
-    H.key_dirs = H.dirs;
-    H.height_gen = t->height_gen; H.valid = true; H.scans++;
+    H.sky.computed(t, key);
     return VF_OK;
 }
 
@@ -3014,41 +3060,18 @@ int vf_terrain_set_ambient(vf_terrain *t, int enable, float strength, float reac
     return VF_OK;
 }
 
-int vf_terrain_read_sky_view_field(vf_terrain *t, float *sky)
-{
-    if (!t || !sky) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, 1, sky, nullptr, nullptr);
-}
-
-int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream)
-{
-    if (!t || !dev_sky) return fail(VF_ERR_INVALID, "NULL argument");
-    return field_out(t, 1, nullptr, dev_sky, stream);
-}
-
-int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count)
-{
-    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
-    *count = t->am.scans;
-    return VF_OK;
-}
+int vf_terrain_read_sky_view_field(vf_terrain *t, float *sky) { return field_out(t, kFieldSky, sky, nullptr, nullptr); }
+int vf_terrain_sky_view_field_device(vf_terrain *t, float *dev_sky, void *stream) { return field_out(t, kFieldSky, nullptr, dev_sky, stream); }
+int vf_terrain_debug_ambient_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldSky, count); }
 
 int vf_terrain_debug_ambient_stage(vf_terrain *t, uint32_t repeats, float ms[2])
 {
     if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
     if (repeats == 0) repeats = 1;
     RelightStage G;
-    int rc = G.open(t);
-    if (rc != VF_OK) return rc;
-    rc = relight_fields(t, G.u, G.s, t->sh.enabled, false);  // (the shade pass below reads it)
-    if (rc != VF_OK) return rc;
-    float a = 0.0f, b = 0.0f;
-    hipError_t err = G.time_field(repeats, a, true, rc);
-    if (rc != VF_OK) return rc;
-    if (err == hipSuccess) err = G.time_shade(repeats, b, kAmbient);
-    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("ambient diagnostics: ") + hipGetErrorString(err));
-    ms[0] = a; ms[1] = b;
-    return VF_OK;
+    if (int rc = G.open(t)) return rc;
+    if (int rc = relight_fields(t, G.u, G.s, t->sh.enabled, false)) return rc;   // (the shade pass below reads it)
+    return G.time_pair(repeats, ms, "ambient", [&] { return ambient_field(t, G.u, G.s, true); }, [&] { G.shade(kAmbient); });
 }
 
 // ---- the draped image (vf_drape.h) ------------------------------------------------------
@@ -3073,10 +3096,6 @@ static int drape_buffers(vf_terrain *t, size_t texels)
 {
     if (int rc = ensure_vis(t)) return rc;
     vf_terrain::Drape &H = t->dr;
-    if (!H.d_decode.p) {
-        if (H.d_decode.reserve(256, 256) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "drape allocation failed"); }
-        VF_HIP_TRY(hipMemcpy(H.d_decode.p, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice));
-    }
     if (H.d_img.reserve(texels, texels) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "drape image allocation failed"); }
     return VF_OK;
 }
@@ -3255,10 +3274,9 @@ int vf_terrain_debug_drape_mip_build(vf_terrain *t, uint32_t repeats, float *ms)
 // The observer's vertex on one axis from its world coordinate: the drape's grid coordinate (4b step 1), rounded
 static uint32_t viewshed_index(const vf_terrain *t, float x, float spacing)
 {
-    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
     float mx = x / spacing;
     mx = std::fmin(std::fmax(mx, -1.5f), 1.5f);
-    const float gx = (mx + 1.5f) / step;
+    const float gx = (mx + 1.5f) / grid_step(t);
     return std::min((uint32_t)std::rint(gx), t->n - 1u);
 }
 
@@ -3266,7 +3284,7 @@ static uint32_t viewshed_index(const vf_terrain *t, float x, float spacing)
 static void viewshed_plan(const vf_terrain *t, const float *u, ViewshedPlan &S)
 {
     const vf_terrain::Viewshed &H = t->vs;
-    const float spacing = std::fmax(u[36], 1e-8f);
+    const float spacing = spacing_of(u);
     S.n = t->n; S.nb = t->nb;
     S.io = viewshed_index(t, H.ox, spacing); S.jo = viewshed_index(t, H.oz, spacing);
     S.L = t->n - 1u;
@@ -3275,22 +3293,19 @@ static void viewshed_plan(const vf_terrain *t, const float *u, ViewshedPlan &S)
     S.exag = u[38]; S.eye_height = H.eye_height; S.target_height = H.target_height; S.softness = H.softness; S.bias = H.bias;
 }
 
-// d_seen holds the field of the uniforms `u`, the handle's heights, observer and scan parameters once the work queued on `s` is done
+// `seen` holds the field of the uniforms `u`, the handle's heights, observer and scan parameters once the work queued on `s` is done
 // (the height cache must be current and ordered before `s`, as for shadow_field).  force: compute it anyway.
 static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::Viewshed &H = t->vs;
     if (!H.have_observer) return fail(VF_ERR_INVALID, "no observer set (vf_terrain_set_viewshed)");
-    const size_t nv = (size_t)t->n * t->n;
-    if (!H.d_seen.p) {
-        if (H.d_seen.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "viewshed field allocation failed"); }
-        H.valid = false;
-    }
     ViewshedPlan S;
     viewshed_plan(t, u, S);
-    const float key[5] = { S.exag, S.eye_height, S.target_height, S.softness, S.bias };
-    if (!force && H.valid && H.height_gen == t->height_gen && H.key_ij[0] == S.io && H.key_ij[1] == S.jo && std::memcmp(key, H.key, sizeof key) == 0) return VF_OK;
-    H.valid = false;
+    std::vector<uint32_t> key = key_of({ S.exag, S.eye_height, S.target_height, S.softness, S.bias });
+    key.push_back(S.io); key.push_back(S.jo);
+    bool current;
+    if (int rc = H.seen.prepare(t, key, force, "viewshed field allocation failed", &current)) return rc;
+    if (current) return VF_OK;
     const size_t ncmax = (size_t)4u * S.nchunks * S.nlines;
     if (H.d_cmax.reserve(ncmax, ncmax) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "viewshed scan allocation failed"); }
     // (the x-major quadrants in one launch, the z-major ones in another: a quadrant's chunks beyond its steps leave at once)
@@ -3300,12 +3315,10 @@ static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool for
     hipLaunchKernelGGL((k_viewshed_chunk_max<false>), gx, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
     hipLaunchKernelGGL((k_viewshed_chunk_max<true>), gz, threads, 0, s, S, (const float *)t->d_hblk, H.d_cmax.p);
     hipLaunchKernelGGL((k_viewshed_carry<0>), dim3((S.nlines + 255u) / 256u, 4), threads, 0, s, S, H.d_cmax.p);
-    hipLaunchKernelGGL((k_viewshed_seen<false>), gx, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_seen.p);
-    hipLaunchKernelGGL((k_viewshed_seen<true>), gz, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.d_seen.p);
+    hipLaunchKernelGGL((k_viewshed_seen<false>), gx, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.seen.d.p);
+    hipLaunchKernelGGL((k_viewshed_seen<true>), gz, threads, 0, s, S, (const float *)t->d_hblk, (const float *)H.d_cmax.p, H.seen.d.p);
     VF_HIP_TRY(hipGetLastError());
-    std::memcpy(H.key, key, sizeof key);
-    H.key_ij[0] = S.io; H.key_ij[1] = S.jo;
-    H.height_gen = t->height_gen; H.valid = true; H.scans++;
+    H.seen.computed(t, key);
     return VF_OK;
 }
 
@@ -3321,9 +3334,9 @@ static void viewshed_launch(const vf_terrain *t, hipStream_t s, const FrameParam
 {
     const vf_terrain::Viewshed &H = t->vs;
     ViewshedTint T = {};
-    T.seen = H.d_seen.p; T.decode = H.d_decode.p;
+    T.seen = H.seen.d.p; T.decode = t->ctx->d_decode;
     T.visible_rgba = H.visible_rgba; T.hidden_rgba = H.hidden_rgba;
-    const float step = (2.0f * 1.5f) / ((float)t->n - 1.0f);   // (P.step, as the vertex stage forms the grid coordinates)
+    const float step = grid_step(t);   // (P.step, as the vertex stage forms the grid coordinates)
     T.xo = -1.5f + (float)viewshed_index(t, H.ox, P.spacing) * step; T.zo = -1.5f + (float)viewshed_index(t, H.oz, P.spacing) * step;
     const float R = H.radius / P.spacing;
     T.RR = R * R; T.radius_on = H.radius > 0.0f ? 1u : 0u;
@@ -3340,7 +3353,16 @@ static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, con
     return VF_OK;
 }
 
-static uint32_t pack_rgba8(const uint8_t c[4]) { return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24; }
+// the scan parameters of both viewshed setters
+static int viewshed_params_check(float eye_height, float target_height, float radius, float softness, float bias)
+{
+    if (!(std::isfinite(eye_height) && eye_height >= 0.0f)) return fail(VF_ERR_INVALID, "eye_height must be a finite number >= 0");
+    if (!(std::isfinite(target_height) && target_height >= 0.0f)) return fail(VF_ERR_INVALID, "target_height must be a finite number >= 0");
+    if (!(std::isfinite(radius) && radius >= 0.0f)) return fail(VF_ERR_INVALID, "radius must be a finite number > 0, or 0 for none");
+    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
+    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    return VF_OK;
+}
 
 int vf_terrain_set_viewshed(vf_terrain *t, int enable, const float observer_xz[2], float eye_height, float target_height, float radius,
                             const uint8_t visible_rgba[4], const uint8_t hidden_rgba[4], float softness, float bias)
@@ -3352,28 +3374,18 @@ int vf_terrain_set_viewshed(vf_terrain *t, int enable, const float observer_xz[2
         VF_HIP_TRY(hipSetDevice(t->ctx->device));
         VF_HIP_TRY(wait_frame(t));
         if (H.enabled) t->inputs_gen++;
-        H.d_seen.release(); H.d_cmax.release(); H.d_decode.release();
-        const uint32_t scans = H.scans;
-        H = vf_terrain::Viewshed();
-        H.scans = scans;
+        viewshed_release(t);
         return VF_OK;
     }
     if (!visible_rgba || !hidden_rgba) return fail(VF_ERR_INVALID, "NULL argument");
     if (!(std::isfinite(observer_xz[0]) && std::isfinite(observer_xz[1]))) return fail(VF_ERR_INVALID, "the observer must be finite");
-    if (!(std::isfinite(eye_height) && eye_height >= 0.0f)) return fail(VF_ERR_INVALID, "eye_height must be a finite number >= 0");
-    if (!(std::isfinite(target_height) && target_height >= 0.0f)) return fail(VF_ERR_INVALID, "target_height must be a finite number >= 0");
-    if (!(std::isfinite(radius) && radius >= 0.0f)) return fail(VF_ERR_INVALID, "radius must be a finite number > 0, or 0 for none");
-    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
-    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    if (int rc = viewshed_params_check(eye_height, target_height, radius, softness, bias)) return rc;
     if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "a viewshed needs a whole-frame handle: sharded handles are not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     VF_HIP_TRY(wait_frame(t));
     if (enable) {
         if (int rc = ensure_vis(t)) return rc;
-        if (!H.d_decode.p) {
-            if (H.d_decode.reserve(256, 256) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "viewshed allocation failed"); }
-            VF_HIP_TRY(hipMemcpy(H.d_decode.p, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice));
-        }
+        H.tinted = true;
     }
     const uint32_t vis = pack_rgba8(visible_rgba), hid = pack_rgba8(hidden_rgba);
     if (H.enabled != (enable != 0) || !H.have_observer || H.ox != observer_xz[0] || H.oz != observer_xz[1] || H.eye_height != eye_height
@@ -3386,19 +3398,8 @@ int vf_terrain_set_viewshed(vf_terrain *t, int enable, const float observer_xz[2
     return VF_OK;
 }
 
-int vf_terrain_read_viewshed_field(vf_terrain *t, float *seen)
-{
-    if (!t || !seen) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->vs.have_observer) return fail(VF_ERR_INVALID, "no observer set (vf_terrain_set_viewshed)");
-    return field_out(t, 2, seen, nullptr, nullptr);
-}
-
-int vf_terrain_viewshed_field_device(vf_terrain *t, float *dev_seen, void *stream)
-{
-    if (!t || !dev_seen) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->vs.have_observer) return fail(VF_ERR_INVALID, "no observer set (vf_terrain_set_viewshed)");
-    return field_out(t, 2, nullptr, dev_seen, stream);
-}
+int vf_terrain_read_viewshed_field(vf_terrain *t, float *seen) { return field_out(t, kFieldSeen, seen, nullptr, nullptr); }
+int vf_terrain_viewshed_field_device(vf_terrain *t, float *dev_seen, void *stream) { return field_out(t, kFieldSeen, nullptr, dev_seen, stream); }
 
 int vf_terrain_viewshed_info(vf_terrain *t, vf_viewshed_info *out)
 {
@@ -3419,7 +3420,7 @@ int vf_terrain_viewshed_info(vf_terrain *t, vf_viewshed_info *out)
     VF_HIP_TRY(hipMemcpyAsync(&h, t->d_hblk + (size_t)(by * t->nb + bx) * kBlockStride + (S.jo - 8u * by) * 9u + (S.io - 8u * bx), sizeof h,
                               hipMemcpyDeviceToHost, t->ctx->stream));
     VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
-    const float spacing = std::fmax(t->inputs.u[36], 1e-8f), step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    const float spacing = spacing_of(t->inputs.u), step = grid_step(t);
     out->vertex[0] = S.io; out->vertex[1] = S.jo;
     out->observer_xyz[0] = (-1.5f + (float)S.io * step) * spacing;
     out->observer_xyz[1] = h * S.exag;
@@ -3428,29 +3429,17 @@ int vf_terrain_viewshed_info(vf_terrain *t, vf_viewshed_info *out)
     return VF_OK;
 }
 
-int vf_terrain_debug_viewshed_scans(vf_terrain *t, uint32_t *count)
-{
-    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
-    *count = t->vs.scans;
-    return VF_OK;
-}
+int vf_terrain_debug_viewshed_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldSeen, count); }
 
 int vf_terrain_debug_viewshed_stage(vf_terrain *t, uint32_t repeats, float ms[2])
 {
     if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->vs.have_observer || !t->vs.d_decode.p) return fail(VF_ERR_INVALID, "no viewshed: it needs an observer, and to have been enabled once");
+    if (!t->vs.have_observer || !t->vs.tinted) return fail(VF_ERR_INVALID, "no viewshed: it needs an observer, and to have been enabled once");
     if (repeats == 0) repeats = 1;
     RelightStage G;
-    int rc = G.open(t);
-    if (rc != VF_OK) return rc;
-    float a = 0.0f, b = 0.0f;
-    // the field first (its last launch leaves what the tint pass reads)
-    hipError_t err = time_launches(G.s, repeats, a, [&](bool) { rc = viewshed_field(t, G.u, G.s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
-    if (err == hipSuccess) err = time_launches(G.s, repeats, b, [&](bool) { viewshed_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); return hipGetLastError(); });
-    if (rc != VF_OK) return rc;
-    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("viewshed diagnostics: ") + hipGetErrorString(err));
-    ms[0] = a; ms[1] = b;
-    return VF_OK;
+    if (int rc = G.open(t)) return rc;
+    return G.time_pair(repeats, ms, "viewshed", [&] { return viewshed_field(t, G.u, G.s, true); },
+                       [&] { viewshed_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
 }
 
 // ---- cumulative viewsheds (vf_cumulative_viewshed.h) ------------------------------------
@@ -3464,7 +3453,7 @@ constexpr uint32_t kCvMaxBatch = 4096;                        // (the carry stag
 // Rc = radius / (spacing step) of the uniforms `u`; only with a radius
 static float cumulative_rc(const vf_terrain *t, const float *u)
 {
-    const float spacing = std::fmax(u[36], 1e-8f), step = (2.0f * 1.5f) / ((float)t->n - 1.0f);
+    const float spacing = spacing_of(u), step = grid_step(t);
     return t->cv.radius / (spacing * step);
 }
 
@@ -3484,7 +3473,7 @@ static uint32_t cumulative_batch(const vf_terrain *t, uint32_t N, uint32_t nchun
     return (uint32_t)std::min<size_t>(std::min<size_t>(B, kCvMaxBatch), N);
 }
 
-// d_count and d_frac hold the field of the uniforms `u`, the handle's heights, observers and scan parameters once the work queued on
+// `count` and d_frac hold the field of the uniforms `u`, the handle's heights, observers and scan parameters once the work queued on
 // `s` is done (the height cache must be current and ordered before `s`).  force: compute it anyway.
 static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
@@ -3492,14 +3481,9 @@ static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool f
     const uint32_t N = (uint32_t)(H.xz.size() / 2u);
     if (!N) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
     const size_t nv = (size_t)t->n * t->n;
-    if (!H.d_sum.p || !H.d_count.p || !H.d_frac.p) {
-        if (H.d_sum.reserve(nv, nv) != hipSuccess || H.d_count.reserve(nv, nv) != hipSuccess || H.d_frac.reserve(nv, nv) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(VF_ERR_NOMEM, "cumulative viewshed field allocation failed");
-        }
-        H.valid = false;
-    }
-    const float spacing = std::fmax(u[36], 1e-8f);
+    const char *nomem = "cumulative viewshed field allocation failed";
+    if (H.d_sum.reserve(nv, nv) != hipSuccess || H.d_frac.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, nomem); }
+    const float spacing = spacing_of(u);
     const bool ranged = H.radius > 0.0f;
     const float Rc = ranged ? cumulative_rc(t, u) : 0.0f;
     const uint32_t L = t->n - 1u, reach = ranged ? cumulative_reach(t, Rc) : L;
@@ -3508,9 +3492,12 @@ static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool f
         ij[2u * o] = viewshed_index(t, H.xz[2u * o], spacing);
         ij[2u * o + 1u] = viewshed_index(t, H.xz[2u * o + 1u], spacing);
     }
-    const float key[6] = { u[38], H.eye_height, H.target_height, H.softness, H.bias, ranged ? Rc : -1.0f };
-    if (!force && H.valid && H.height_gen == t->height_gen && std::memcmp(key, H.key, sizeof key) == 0 && ij == H.key_ij) return VF_OK;
-    H.valid = false;
+    std::vector<uint32_t> key = key_of({ u[38], H.eye_height, H.target_height, H.softness, H.bias, ranged ? Rc : -1.0f });
+    key.push_back((uint32_t)ij.size());
+    key.insert(key.end(), ij.begin(), ij.end());
+    bool current;
+    if (int rc = H.count.prepare(t, key, force, nomem, &current)) return rc;
+    if (current) return VF_OK;
     const uint32_t nlines = 2u * L + 1u, nchunks = (reach + kShChunk - 1u) / kShChunk;
     const uint32_t B = cumulative_batch(t, N, nchunks);
     const size_t ncmax = (size_t)B * 4u * nchunks * nlines;
@@ -3550,11 +3537,10 @@ static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool f
         if (gx.x) hipLaunchKernelGGL((k_cumulative_seen<false>), gx, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.d_sum.p);
         if (gz.x) hipLaunchKernelGGL((k_cumulative_seen<true>), gz, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.d_sum.p);
     }
-    hipLaunchKernelGGL((k_cumulative_finish<0>), dim3((uint32_t)((nv + 255u) / 256u)), threads, 0, s, (const uint32_t *)H.d_sum.p, (uint32_t)nv, (float)N, H.d_count.p, H.d_frac.p);
+    hipLaunchKernelGGL((k_cumulative_finish<0>), dim3((uint32_t)((nv + 255u) / 256u)), threads, 0, s, (const uint32_t *)H.d_sum.p, (uint32_t)nv, (float)N, H.count.d.p, H.d_frac.p);
     VF_HIP_TRY(hipGetLastError());
-    std::memcpy(H.key, key, sizeof key);
-    H.key_ij.swap(ij);
-    H.height_gen = t->height_gen; H.valid = true; H.scans++; H.batch = B;
+    H.count.computed(t, key);
+    H.batch = B;
     return VF_OK;
 }
 
@@ -3562,7 +3548,7 @@ static void cumulative_launch(const vf_terrain *t, hipStream_t s, const FramePar
 {
     const vf_terrain::CumulativeViewshed &H = t->cv;
     ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
-    T.seen = H.d_frac.p; T.decode = H.d_decode.p;
+    T.seen = H.d_frac.p; T.decode = t->ctx->d_decode;
     T.visible_rgba = H.high_rgba; T.hidden_rgba = H.low_rgba;
     tint_launch(t, s, P, V, redo, rgba, T);
 }
@@ -3593,21 +3579,11 @@ int vf_terrain_set_cumulative_viewshed(vf_terrain *t, int enable, const float *o
     if (count < 1u || count > VF_CUMULATIVE_VIEWSHED_MAX_OBSERVERS) return fail(VF_ERR_INVALID, "a cumulative viewshed takes 1 to 65535 observers");
     for (size_t k = 0; k < (size_t)2u * count; ++k)
         if (!std::isfinite(observers_xz[k])) return fail(VF_ERR_INVALID, "the observers must be finite");
-    if (!(std::isfinite(eye_height) && eye_height >= 0.0f)) return fail(VF_ERR_INVALID, "eye_height must be a finite number >= 0");
-    if (!(std::isfinite(target_height) && target_height >= 0.0f)) return fail(VF_ERR_INVALID, "target_height must be a finite number >= 0");
-    if (!(std::isfinite(radius) && radius >= 0.0f)) return fail(VF_ERR_INVALID, "radius must be a finite number > 0, or 0 for none");
-    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
-    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    if (int rc = viewshed_params_check(eye_height, target_height, radius, softness, bias)) return rc;
     if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "a cumulative viewshed needs a whole-frame handle: sharded handles are not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     VF_HIP_TRY(wait_frame(t));
-    if (enable) {
-        if (int rc = ensure_vis(t)) return rc;
-        if (!H.d_decode.p) {
-            if (H.d_decode.reserve(256, 256) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "cumulative viewshed allocation failed"); }
-            VF_HIP_TRY(hipMemcpy(H.d_decode.p, tables().decode, 256 * sizeof(float), hipMemcpyHostToDevice));
-        }
-    }
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
     const uint32_t hi = pack_rgba8(high_rgba), lo = pack_rgba8(low_rgba);
     std::vector<float> xz(observers_xz, observers_xz + (size_t)2u * count);
     if (H.enabled != (enable != 0) || H.xz != xz || H.eye_height != eye_height || H.target_height != target_height || H.radius != radius
@@ -3620,19 +3596,8 @@ int vf_terrain_set_cumulative_viewshed(vf_terrain *t, int enable, const float *o
     return VF_OK;
 }
 
-int vf_terrain_read_cumulative_viewshed_field(vf_terrain *t, float *count)
-{
-    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->cv.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
-    return field_out(t, 3, count, nullptr, nullptr);
-}
-
-int vf_terrain_cumulative_viewshed_field_device(vf_terrain *t, float *dev_count, void *stream)
-{
-    if (!t || !dev_count) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->cv.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
-    return field_out(t, 3, nullptr, dev_count, stream);
-}
+int vf_terrain_read_cumulative_viewshed_field(vf_terrain *t, float *count) { return field_out(t, kFieldCount, count, nullptr, nullptr); }
+int vf_terrain_cumulative_viewshed_field_device(vf_terrain *t, float *dev_count, void *stream) { return field_out(t, kFieldCount, nullptr, dev_count, stream); }
 
 int vf_terrain_cumulative_viewshed_info(vf_terrain *t, vf_cumulative_viewshed_info *out)
 {
@@ -3651,7 +3616,7 @@ int vf_terrain_read_cumulative_viewshed_vertices(vf_terrain *t, uint32_t *vertic
     const vf_terrain::CumulativeViewshed &H = t->cv;
     if (H.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
     if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
-    const float spacing = std::fmax(t->inputs.u[36], 1e-8f);
+    const float spacing = spacing_of(t->inputs.u);
     for (size_t k = 0; k < H.xz.size(); ++k) vertices[k] = viewshed_index(t, H.xz[k], spacing);
     return VF_OK;
 }
@@ -3659,17 +3624,12 @@ int vf_terrain_read_cumulative_viewshed_vertices(vf_terrain *t, uint32_t *vertic
 int vf_terrain_debug_cumulative_viewshed_batch(vf_terrain *t, uint32_t batch)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->cv.forced_batch != batch) t->cv.valid = false;      // (the next call computes the field again, with this batch size)
+    if (t->cv.forced_batch != batch) t->cv.count.valid = false;      // (the next call computes the field again, with this batch size)
     t->cv.forced_batch = batch;
     return VF_OK;
 }
 
-int vf_terrain_debug_cumulative_viewshed_scans(vf_terrain *t, uint32_t *count)
-{
-    if (!t || !count) return fail(VF_ERR_INVALID, "NULL argument");
-    *count = t->cv.scans;
-    return VF_OK;
-}
+int vf_terrain_debug_cumulative_viewshed_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldCount, count); }
 
 int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, float *ms)
 {
@@ -3680,11 +3640,11 @@ int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, 
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     if (int rc = ct_heights_current(t)) return rc;
     hipStream_t s = t->ctx->stream;
-    const uint32_t scans = t->cv.scans;
+    ScansHeld held;
+    held.hold(t);
     int rc = VF_OK;
     float a = 0.0f;
     const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = cumulative_field(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
-    t->cv.scans = scans;
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("cumulative viewshed diagnostics: ") + hipGetErrorString(err));
     *ms = a;
