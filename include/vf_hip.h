@@ -358,7 +358,22 @@ int vf_terrain_debug_set_plan_feedback(vf_terrain *t, const uint32_t *tile_ticks
 #define VF_PLAN_DILATE       8u   /* every tile takes the heaviest time of its neighbourhood */
 #define VF_PLAN_QUEUED_AHEAD 16u  /* the plan was queued ahead of the call, behind the frame before it */
 #define VF_PLAN_GEOMETRY_REUSED 32u /* block boxes and set-up records of this plan state were built from the same geometry inputs: not rebuilt */
+#define VF_PLAN_TILE_LISTS   64u  /* the tile kernel read this plan state's per-tile candidate lists */
 int vf_terrain_debug_plan_mode(const vf_terrain *t, uint32_t *mode);
+/* debug/tests (candidate lists): while a plan state's set-up records stand, the blocks that can reach each local tile are
+ * listed once, off the frames' chain, and later frames drawn from that state read the lists instead of testing the block ranges.
+ * For the plan state the last frame was drawn from -- built: its lists exist (or are queued) for the live geometry; used: the last
+ * frame read them; tiles_listed / tiles_fallback: local tiles with a list (an empty one counts) / without, because the shared buffer
+ * was full; entries: listed (tile, block) pairs; capacity: the buffer's 16-byte units handed to the builder; units_asked: what all
+ * tiles together asked for (entries + offset words; saturates).  The counts are zero when neither built nor used.  The call waits for
+ * the builder.  VF_NO_TILE_LISTS=1 in the environment when a handle is created: that handle never builds a list.
+ * VF_ERR_INVALID before the first frame. */
+typedef struct vf_tile_list_info { uint32_t built, used, tiles_listed, tiles_fallback, entries, capacity, units_asked, reserved; } vf_tile_list_info;
+int vf_terrain_debug_tile_lists(vf_terrain *t, vf_tile_list_info *out);
+/* debug/tests: the capacity (16-byte units) the NEXT builders get, at most the buffer's own size; UINT32_MAX: the default.  Waits for
+ * the handle's queued work, throws away a plan queued ahead and marks both plan states' lists as not built: each is built again
+ * behind the next frame drawn from it.  0: every tile that a block reaches falls back.  No frame may differ by a pixel. */
+int vf_terrain_debug_set_tile_list_capacity(vf_terrain *t, uint32_t units);
 /* diagnostics, only in libraries built with -DVF_PHASE_PROF (VF_ERR_INVALID otherwise): shader-clock cycles summed over
  * all waves of the last frame's tile kernel, per phase (set-up, pull/cull, vertex stage, classification, span raster,
  * completion/rescan, end-of-chunk wait, fragment stage), then 8 event counts, then up to 8 parts of the set-up phase; n <= 32 */

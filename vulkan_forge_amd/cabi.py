@@ -16,6 +16,7 @@ VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -
 VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
 VF_DRAPE_MIP_BIAS_MAX, VF_DRAPE_MIP_LEVELS_MAX = 16.0, 15                                # its mip pyramid
 VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED_AHEAD = 1, 2, 4, 8, 16   # vf_terrain_debug_plan_mode
+VF_PLAN_TILE_LISTS = 64        # ... and for "the tile kernel read the plan state's per-tile candidate lists" (DESIGN.md 3): Terrain.tile_lists()
 VF_PLAN_GEOMETRY_REUSED = 32   # ... its bit for "the block boxes and set-up records were not rebuilt" (DESIGN.md 3): Terrain.geometry_reused()
 
 # every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py)
@@ -26,7 +27,7 @@ SYMBOLS = [
     "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
     "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
     "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_set_layer_occlusion", "vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
-    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_band_masks", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
+    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_band_masks", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_tile_lists", "vf_terrain_debug_set_tile_list_capacity", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
     "vf_terrain_debug_fragment_stage", "vf_host_alloc", "vf_host_free",
@@ -122,6 +123,8 @@ _PROTOS = {
     "vf_terrain_debug_band_masks": (_i, [_vp, _vp, _vp, _vp, _u32, C.POINTER(_u32)]),
     "vf_terrain_debug_set_plan_feedback": (_i, [_vp, _vp, _vp, _vp, _u32]),
     "vf_terrain_debug_plan_mode": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_debug_tile_lists": (_i, [_vp, _vp]),
+    "vf_terrain_debug_set_tile_list_capacity": (_i, [_vp, _u32]),
     "vf_terrain_debug_phase_cycles": (_i, [_vp, _vp, _u32]),
     "vf_terrain_tile_times": (_i, [_vp, _vp, _u32, C.POINTER(_u32)]),
     "vf_balance_stripes": (_i, [_vp, _u32, _u32, _vp]),
@@ -805,7 +808,21 @@ class Terrain:
         in the plan, so VF_PLAN_GEOMETRY_REUSED is reported only on request (geometry=True: the word as the library gives it)."""
         m = _u32()
         self._check(self.lib.vf_terrain_debug_plan_mode(self.t, C.byref(m)))
-        return m.value if geometry else m.value & ~VF_PLAN_GEOMETRY_REUSED
+        return m.value if geometry else m.value & ~(VF_PLAN_GEOMETRY_REUSED | VF_PLAN_TILE_LISTS)
+
+    def tile_lists(self):
+        """Debug / tests: the per-tile candidate lists of the plan state the last frame was drawn from, as a dict:
+        built, used (bools), tiles_listed, tiles_fallback, entries, capacity, units_asked.  Waits for the builder."""
+        w = (_u32 * 8)()
+        self._check(self.lib.vf_terrain_debug_tile_lists(self.t, C.addressof(w)))
+        names = ("built", "used", "tiles_listed", "tiles_fallback", "entries", "capacity", "units_asked")
+        d = dict(zip(names, (int(v) for v in w)))
+        d["built"], d["used"] = bool(d["built"]), bool(d["used"])
+        return d
+
+    def set_tile_list_capacity(self, units=0xFFFFFFFF):
+        """Debug / tests: the capacity (16-byte units) the next list builders get; both plan states build theirs again."""
+        self._check(self.lib.vf_terrain_debug_set_tile_list_capacity(self.t, units))
 
     def geometry_reused(self):
         """Did the frame rendered last reuse its plan state's block boxes and set-up records (VF_PLAN_GEOMETRY_REUSED)?"""

@@ -206,6 +206,7 @@ struct FramePlan {
     bool motion_starts = false;
     bool sampled = true;                                         // timing level 3: this frame is one of those that carry events
     uint32_t *rc_lo = nullptr, *rc_hi = nullptr, *seg_count = nullptr;
+    bool lists = false;                                          // the tile kernel reads this plan state's per-tile candidate lists (k_tile_lists)
 };
 
 // A device array that grows (the overlay state).  reserve: when need > cap, a new allocation of new_cap elements, zero-filled on request,
@@ -513,7 +514,21 @@ struct vf_terrain {
         // the stamp: geom_gen / height_gen the boxes, ranges, segment list, records, masks, band masks and vertex records were built from (0: none --
         // never filled, or left half-written).  While both equal the live generations the plan reuses them (plan_frame).
         uint64_t geom_stamp = 0, height_stamp = 0;
+        // PER-TILE CANDIDATE LISTS (k_tile_lists): built once from this state's records while they stand, off the frames'
+        // chain.  list_stamp: the geom_stamp of the records they were built from (0: none); whatever rebuilds the records zeroes it.
+        // `listed` is recorded behind the builder: a frame that reads the lists waits for it, and so does a rebuild of the records.
+        uint4 *tl_ent = nullptr, *tl_hdr = nullptr;  // the shared entry buffer (tl_units x 16 B), one header per local tile
+        uint32_t *tl_ctl = nullptr;      // the bump cursor (64 bits), tiles with a list, tiles fallen back, entries listed
+        uint32_t tl_units = 0, tl_cap = 0;           // allocated / handed to the last builder (vf_terrain_debug_set_tile_list_capacity)
+        uint64_t list_stamp = 0;
+        hipEvent_t listed = nullptr;
     } ps[kPlanStates];
+    // ... for a caller that waits for its frames the builder must not stand in front of one: the state drawn last is noted here and its
+    // lists are queued behind the next read-back's copy, as the plan made ahead is (or behind the next frame's kernels).
+    struct ListJob { bool pending = false; uint32_t set = 0; uint64_t geom = 0; FrameParams P; } tl_job;
+    bool tl_off = false;                 // VF_NO_TILE_LISTS=1 at handle creation: never build one
+    uint32_t tl_cap_debug = 0xFFFFFFFFu; // vf_terrain_debug_set_tile_list_capacity (0xFFFFFFFF: the buffer's size)
+    bool tl_failed = false;              // the list buffers could not be allocated: the handle goes without
     PlanCursor cursor;
     uint32_t last_set = 0;               // the set of the frame rendered last
     uint32_t last_plan_mode = 0;         // VF_PLAN_* bits of the frame rendered last (vf_terrain_debug_plan_mode)
@@ -841,6 +856,7 @@ static hipError_t ensure_plan_state(vf_terrain *t, uint32_t k, hipStream_t zero_
     hipError_t err = C.commit(&S.slab, zero_on);          // (the stream of the state's first user: the plan chain)
     if (err != hipSuccess) { S.slab = nullptr; return err; }
     S.geom_stamp = S.height_stamp = 0;                     // a fresh slab holds no geometry
+    S.list_stamp = 0;
     S.work_sorted = S.work + (all_tiles + kSplitBudget + 16);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&S.planned, hipEventDisableTiming);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&S.drawn, hipEventDisableTiming);
@@ -916,6 +932,7 @@ int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t gri
     if (n > 8192) return fail(VF_ERR_INVALID, "grid must be <= 8192");
     VF_HIP_TRY(hipSetDevice(ctx->device));
     vf_terrain *t = new (std::nothrow) vf_terrain;
+    if (t) { const char *e = std::getenv("VF_NO_TILE_LISTS"); t->tl_off = e && *e && std::strcmp(e, "0") != 0; }
     if (!t) return fail(VF_ERR_NOMEM, "out of host memory");
     t->ctx = ctx; t->W = width; t->H = height; t->n = n;
     t->nb = (n - 1 + kBlockCells - 1) / kBlockCells;
@@ -993,6 +1010,9 @@ void vf_terrain_destroy(vf_terrain *t)
         if (S.drawn) (void)hipEventDestroy(S.drawn);
         if (S.boxed) (void)hipEventDestroy(S.boxed);
         if (S.set_up) (void)hipEventDestroy(S.set_up);
+        if (S.listed) (void)hipEventDestroy(S.listed);
+        if (S.tl_ent) (void)hipFree(S.tl_ent);
+        if (S.tl_hdr) (void)hipFree(S.tl_hdr);
         for (auto &e : S.pev) if (e) (void)hipEventDestroy(e);
     }
     // (side / side2 / copy_stream belong to the context)
@@ -1140,7 +1160,7 @@ static int reset_layout_feedback(vf_terrain *t)
         VF_HIP_TRY(hipMemset(S.background, 0, (size_t)t->ntx * t->nty * sizeof(uint32_t)));
         S.have_u_used = false;
     }
-    for (auto &S : t->ps) S.geom_stamp = S.height_stamp = 0;   // (k_block_boxes dropped the blocks of the other layout's tiles)
+    for (auto &S : t->ps) { S.geom_stamp = S.height_stamp = 0; S.list_stamp = 0; }   // (k_block_boxes dropped the blocks of the other layout's tiles)
     return VF_OK;
 }
 
@@ -1448,11 +1468,67 @@ constexpr float kFreshFeedbackPx = 24.0f;   // from here on (3/8 of a tile per f
 // the fast fragment path exists for fs_main as coded; the documented-only SPEC_T32 stage always takes the exact arithmetic
 static bool fast_shading(const FrameInputs &in) { return in.precision == VF_PRECISION_FAST && in.shade_mode == VF_SHADE_REFERENCE; }
 
+// The per-tile candidate lists of plan state S (k_tile_lists, vf_kernels.h), queued on `on`: behind the set-up pass whose records they
+// are read from and behind the last frame that read this state's lists, never in front of a frame.  The buffers are made by the first
+// builder of the state -- a one-shot render and a moving camera never pay for them.  SIZE: the entries are the (tile, block) pairs whose
+// box meets the tile, which only the device knows; the buffer is sized from what the host knows -- two units (16 B) per grid block plus
+// 512 per local tile, at most kTileListMaxUnits (64 MiB) -- and a tile that finds it full goes without (DESIGN.md 3 has the fill).
+constexpr size_t kTileListMaxUnits = (size_t)4 << 20;
+static bool lists_valid(const vf_terrain *t, const vf_terrain::PlanState &S)
+{
+    return S.list_stamp != 0 && S.list_stamp == S.geom_stamp && S.geom_stamp == t->geom_gen && S.height_stamp == t->height_gen;
+}
+static hipError_t queue_tile_lists(vf_terrain *t, vf_terrain::PlanState &S, const FrameParams &P, hipStream_t on)
+{
+    const uint32_t ntiles = t->local_tiles;
+    if (t->tl_off || t->tl_failed || !ntiles || !S.slab || S.geom_stamp == 0) return hipSuccess;
+    if (!S.tl_ent) {
+        const size_t all_tiles = (size_t)t->ntx * t->nty;
+        const size_t units = std::min<size_t>(kTileListMaxUnits, 2 * (size_t)t->nblocks + 512 * (size_t)ntiles);
+        hipError_t e = hipMalloc((void **)&S.tl_ent, units * sizeof(uint4));
+        if (e == hipSuccess) e = hipMalloc((void **)&S.tl_hdr, (all_tiles + 2) * sizeof(uint4));      // (+ 2: the control words behind the headers)
+        if (e == hipSuccess && !S.listed) e = hipEventCreateWithFlags(&S.listed, hipEventDisableTiming);
+        if (e != hipSuccess) {                              // no memory for them: the handle draws as it always has
+            if (S.tl_ent) (void)hipFree(S.tl_ent);
+            if (S.tl_hdr) (void)hipFree(S.tl_hdr);
+            S.tl_ent = S.tl_hdr = nullptr;
+            t->tl_failed = true;
+            (void)hipGetLastError();
+            return hipSuccess;
+        }
+        S.tl_ctl = reinterpret_cast<uint32_t *>(S.tl_hdr + all_tiles);
+        S.tl_units = (uint32_t)units;
+    }
+    const size_t rc_n = (size_t)t->nb * t->ntx;
+    hipError_t e = hipStreamWaitEvent(on, S.set_up, 0);
+    if (e == hipSuccess) e = hipStreamWaitEvent(on, S.drawn, 0);        // (a frame that still reads the lists this builder writes over)
+    if (e == hipSuccess) e = hipMemsetAsync(S.tl_ctl, 0, 8 * sizeof(uint32_t), on);
+    if (e != hipSuccess) return e;
+    S.tl_cap = std::min(S.tl_units, t->tl_cap_debug);
+    hipLaunchKernelGGL(k_tile_lists, dim3(ntiles), dim3(256), 0, on, P, S.row_ranges, S.recs, S.cap_seg, S.cap_rad, S.rc, S.rc + rc_n,
+                       S.tl_ent, S.tl_hdr, S.tl_ctl, S.tl_cap);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(S.listed, on);
+    if (e == hipSuccess) S.list_stamp = S.geom_stamp;
+    return e;
+}
+// ... for the caller that waits for its frames: the job noted by render_impl, behind whatever `s` holds by now
+static void flush_tile_lists(vf_terrain *t, hipStream_t s)
+{
+    if (!t->tl_job.pending) return;
+    t->tl_job.pending = false;
+    vf_terrain::PlanState &S = t->ps[t->tl_job.set];
+    // (the records must still be the ones the frame was drawn from, and the live geometry theirs)
+    if (S.geom_stamp == 0 || S.geom_stamp != t->tl_job.geom || S.geom_stamp != t->geom_gen || S.height_stamp != t->height_gen || t->bounds_dirty) return;
+    if (lists_valid(t, S)) return;
+    if (queue_tile_lists(t, S, t->tl_job.P, s) != hipSuccess) (void)hipGetLastError();
+}
+
 // A frame in two halves (round 5).  plan_frame: everything up to the plan's last kernel -- block boxes, set-up pass, plan, sort -- on the
 // side streams (a handle's first frame: on `s`); it touches plan state only.  draw_frame: the kernels on the caller's stream.  What the
 // second half needs of the first travels in a FramePlan, so that the first half of the NEXT frame can be queued ahead of its call
 // (vf_terrain::pre, render_impl).
-static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming = false)
+static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming = false, bool ahead = false)
 {
     FrameParams &P = K.P;
     PlanCursor &C = t->cursor;
@@ -1530,7 +1606,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
         VF_HIP_TRY(hipEventRecord(t->cached, side));
         t->cached_on = side;
         t->bounds_dirty = false;
-        for (auto &X : t->ps) X.geom_stamp = X.height_stamp = 0;       // (whatever the generations say: nothing was built from this cache)
+        for (auto &X : t->ps) { X.geom_stamp = X.height_stamp = 0; X.list_stamp = 0; }   // (whatever the generations say: nothing was built from this cache)
     }
     if (t->cached_on && t->cached_on != side) {             // the cache was last rebuilt on another stream: this chain (and, through S.boxed and S.planned, the set-up pass and the draw) comes after it
         VF_HIP_TRY(hipStreamWaitEvent(side, t->cached, 0));
@@ -1555,6 +1631,8 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
         hipLaunchKernelGGL(k_plan_begin, dim3(1), dim3(512), 0, side, quantum_from, t->ntx * t->nty, quantum, S.work_count);
     } else {
         S.geom_stamp = S.height_stamp = 0;                                  // half-written from here until both kernels are on their way
+        S.list_stamp = 0;                                                   // (the candidate lists were built from the records that go now)
+        if (S.listed) VF_HIP_TRY(hipStreamWaitEvent(side, S.listed, 0));    // ... and their builder, if it is still on its way, reads those records
         hipLaunchKernelGGL(k_block_boxes, dim3(t->nb + 1), dim3(t->nb > 256 ? 512 : 256), 0, side, P, t->d_bounds, S.ranges, S.row_ranges, S.cap_seg, S.cap_rad, rc_lo, rc_hi,
                            quantum_from, t->ntx * t->nty, quantum, S.work_count, S.recs, S.seg_list, seg_count);
         // vertex stage + tile-independent culling, once per geometry (streams ~1.3 KB per block into this frame's plan state): needs the
@@ -1569,6 +1647,13 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
         VF_HIP_TRY(hipGetLastError());                                      // both launched without error: the stamp
         S.geom_stamp = t->geom_gen; S.height_stamp = t->height_gen;
     }
+    // the candidate lists of a state whose records stand: read by this frame when they are of this generation; built otherwise -- on the
+    // set-up stream, behind S.set_up, beside the plan chain and not on it: this frame does not wait for them and draws without.
+    // Only where a frame in flight hides the builder: a plan made ahead, or a caller that streams.  A caller that waits for this
+    // frame would wait for the builder too (it fills the GPU for 0.1 ms at C4 and the plan chain queues up behind it: +0.09 ms on a
+    // handle's third frame): render_impl notes the job instead, and it goes out behind the frame.
+    K.lists = reuse && ntiles && !t->tl_off && lists_valid(t, S);
+    if (reuse && ntiles && !K.lists && !solo && (ahead || streaming)) VF_HIP_TRY(queue_tile_lists(t, S, P, side2));
     if (timed) VF_HIP_TRY(hipEventRecord(ev[1], side));
     if (ntiles) {
         if (fresh) {
@@ -1589,7 +1674,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
     if (timed) VF_HIP_TRY(hipEventRecord(ev[2], side));
     VF_HIP_TRY(hipEventRecord(S.planned, side));
     K.mode = (first ? VF_PLAN_FIRST : 0u) | (fresh ? VF_PLAN_FRESH : 0u) | (M.on ? VF_PLAN_MOTION_MAP : 0u) | (dilate ? VF_PLAN_DILATE : 0u) |
-             (reuse ? VF_PLAN_GEOMETRY_REUSED : 0u);
+             (reuse ? VF_PLAN_GEOMETRY_REUSED : 0u) | (K.lists ? VF_PLAN_TILE_LISTS : 0u);
     K.set = set; K.ntiles = ntiles; K.motion_starts = motion_starts; K.rc_lo = rc_lo; K.rc_hi = rc_hi; K.seg_count = seg_count;
     return VF_OK;
 }
@@ -1676,6 +1761,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const uint32_t nstats = (uint32_t)stats_layout(t).words;     // zeroed by k_clear (no memset dispatch)
     VF_HIP_TRY(hipStreamWaitEvent(s, S.planned, 0));
     VF_HIP_TRY(hipStreamWaitEvent(s, S.set_up, 0));
+    if (K.lists) VF_HIP_TRY(hipStreamWaitEvent(s, S.listed, 0));
+    const TileLists TL = { K.lists ? S.tl_ent : nullptr, K.lists ? S.tl_hdr : nullptr };
     // The previous frame may have been drawn on another stream of the caller's: this frame waits for it (same output / statistics
     // buffers; and when it went to another output buffer, letting the two tile kernels overlap costs more than it gains --
     // tools/exp_overlap.py; d_vis is one buffer per handle anyway).
@@ -1700,7 +1787,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         const dim3 per_cu(std::min<uint32_t>((uint32_t)std::max(1, t->ctx->prop.multiProcessorCount) * (1024u / (uint32_t)kTileThreads), ntiles + kSplitBudget)),
                    few(std::min<uint32_t>(64u, ntiles + kSplitBudget)), threads(kTileThreads);
 #define VF_TILE_ARGS P, V, S.row_ranges, S.cap_seg, S.cap_rad, t->d_lut, t->ctx->d_thresh, S.work_sorted, S.work_count, \
-                     rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo, S.band
+                     rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo, S.band, TL
         const bool fast = fast_shading(t->inputs);
         // (the complete variant redraws the rare items that met a clipped primitive: always the plain loop)
 #define VF_TILE_LAUNCH(WV, FS)                                                                                         \
@@ -1754,7 +1841,7 @@ static void plan_ahead(vf_terrain *t, hipStream_t s)
 {
     vf_terrain::PrePlan &R = t->pre;
     R.before = t->cursor;
-    if (plan_frame(t, s, R.K) == VF_OK) { R.valid = true; R.gen = t->inputs_gen; R.geom = t->geom_gen; }
+    if (plan_frame(t, s, R.K, false, true) == VF_OK) { R.valid = true; R.gen = t->inputs_gen; R.geom = t->geom_gen; }
     else {                                                  // (a failed launch: the next call plans for itself and reports it)
         // (the whole cursor goes back, though only cur_set, frame_no and frames_since_reset can have moved: a plan is made ahead for a
         //  camera at rest only -- neither moving nor was_moving, a frame drawn, u_drawn equal to the live uniforms -- and plan_frame
@@ -1778,11 +1865,12 @@ static void flush_preplan(vf_terrain *t, hipStream_t s)
 // ... and the wait that goes with it: for the copy's event when a plan was queued behind it, for the stream otherwise
 static hipError_t finish_readback(vf_terrain *t, hipStream_t s)
 {
-    if (!t->preplan_pending) return hipStreamSynchronize(s);
+    if (!t->preplan_pending && !t->tl_job.pending) return hipStreamSynchronize(s);
     hipError_t e = t->copied ? hipSuccess : hipEventCreateWithFlags(&t->copied, hipEventDisableTiming);
-    if (e != hipSuccess) { t->preplan_pending = false; return hipStreamSynchronize(s); }
+    if (e != hipSuccess) { t->preplan_pending = false; t->tl_job.pending = false; return hipStreamSynchronize(s); }
     e = hipEventRecord(t->copied, s);
     if (e != hipSuccess) return e;
+    flush_tile_lists(t, s);
     flush_preplan(t, s);
     return hipEventSynchronize(t->copied);
 }
@@ -1823,6 +1911,13 @@ static int render_impl(vf_terrain *t, hipStream_t s, bool write_vis)
     if (rc != VF_OK) return rc;
     t->last_plan_mode = K.mode | (planned ? VF_PLAN_QUEUED_AHEAD : 0u);
     t->last_drawn_geom = t->geom_gen;
+    // a caller that waits for its frames: the lists of the state drawn before this one go out now, behind this frame's kernels (on the
+    // set-up stream when there is one), if no read-back took them; those of this frame's state wait for the next read-back's copy
+    // (finish_readback) or the next frame
+    flush_tile_lists(t, t->side ? t->side2 : s);
+    if (!write_vis && (K.mode & VF_PLAN_GEOMETRY_REUSED) && !K.lists && !t->tl_off && !t->tl_failed && K.ntiles && !lists_valid(t, t->ps[K.set])) {
+        t->tl_job.pending = true; t->tl_job.set = K.set; t->tl_job.geom = t->ps[K.set].geom_stamp; t->tl_job.P = K.P;
+    }
     // the camera is at rest (two frames from one set of geometry inputs), the handle is past its first frames, nothing diagnostic is going on:
     // the next frame's plan goes out now
     // (round 6: also for a caller that streams frames of a resting camera -- its next plan goes out one call early, which changes nothing while
@@ -2401,7 +2496,7 @@ static int copy_to_host_staged(vf_terrain *t, uint8_t *dst, const uint8_t *src, 
         if (err == hipSuccess) err = hipEventRecord(t->stage_ev[i % kStageSlots], s);
         if (err == hipSuccess) enqueued.store(i + 1, std::memory_order_release);
     }
-    if (err == hipSuccess) flush_preplan(t, s);            // (behind the last chunk's copy: the threads above wait for the chunks' events)
+    if (err == hipSuccess) { flush_tile_lists(t, s); flush_preplan(t, s); }   // (behind the last chunk's copy: the threads above wait for the chunks' events)
     if (err != hipSuccess) failed.store(1);
     for (auto &th : pool) th.join();
     if (err != hipSuccess) return fail(VF_ERR_HIP, hipGetErrorString(err));
@@ -3725,6 +3820,42 @@ int vf_terrain_debug_plan_mode(const vf_terrain *t, uint32_t *mode)
     if (!t || !mode) return fail(VF_ERR_INVALID, "NULL argument");
     if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
     *mode = t->last_plan_mode;
+    return VF_OK;
+}
+
+// The candidate lists of the plan state drawn last (include/vf_hip.h).  Host copies behind a full wait.
+int vf_terrain_debug_tile_lists(vf_terrain *t, vf_tile_list_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    std::memset(out, 0, sizeof *out);
+    const vf_terrain::PlanState &S = t->ps[t->last_set];
+    out->used = (t->last_plan_mode & VF_PLAN_TILE_LISTS) ? 1u : 0u;
+    out->built = lists_valid(t, S) ? 1u : 0u;
+    if (!out->built && !out->used) return VF_OK;
+    VF_HIP_TRY(hipEventSynchronize(S.listed));
+    uint32_t ctl[8];
+    VF_HIP_TRY(hipMemcpy(ctl, S.tl_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+    out->tiles_listed = ctl[2]; out->tiles_fallback = ctl[3]; out->entries = ctl[4];
+    out->capacity = S.tl_cap;
+    const unsigned long long asked = (unsigned long long)ctl[0] | ((unsigned long long)ctl[1] << 32);
+    out->units_asked = asked > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)asked;
+    return VF_OK;
+}
+
+int vf_terrain_debug_set_tile_list_capacity(vf_terrain *t, uint32_t units)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    VF_HIP_TRY(sync_sides(t));
+    VF_HIP_TRY(drop_preplan(t));                            // (a plan made ahead may hold "read the lists": planned again, without)
+    VF_HIP_TRY(wait_frame(t));
+    VF_HIP_TRY(sync_sides(t));
+    t->tl_cap_debug = units;
+    t->tl_job.pending = false;
+    for (auto &S : t->ps) S.list_stamp = 0;                 // both states build theirs again, with the new capacity
     return VF_OK;
 }
 

@@ -1302,6 +1302,114 @@ __global__ __launch_bounds__(256) void k_plan_estimate(FrameParams P, const Pixe
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// PER-TILE CANDIDATE LISTS, built once per geometry generation.  Which blocks can reach a tile is a pure function
+// of the geometry inputs -- row boxes, block ranges, the records' exact boxes, the capsules -- and the tile kernel used to work it out
+// again in every item of every frame: the row mask and row list per item, three strided gathers per (row, 64-block group) and chunk with
+// a handful of lanes on a block that can reach the tile.  While a plan state's records stand (plan_frame, `reuse`) one workgroup per
+// local tile writes that answer down: the blocks whose record box and capsule meet the tile's full rectangle -- the geometry part of
+// block_is_candidate, k_plan_estimate's test -- as 16-byte entries { bx | by << 10, box (2 words), spare }, block rows descending (=
+// descending primitive id), blocks ascending inside a row, in front of them one word per block row of the tile's span hi .. lo: the
+// entries in the rows above it (and the total behind the last), so that a step of the tile kernel stays a block row.  A block whose
+// record has no alive primitive but a non-empty box (generic primitives only) is on the list: the box is the test, as it is today.
+// All tiles of a plan state share one buffer through a bump cursor (16-byte units); a tile whose words no longer fit gets "no list"
+// in its header and the tile kernel tests the ranges itself.  Header per local tile: { first entry, entries (0xFFFFFFFF: no list),
+// hi | lo << 16, first offset word's unit }.  `ctl`: [0..1] the cursor (64 bits), [2] tiles with a list, [3] tiles fallen back,
+// [4] entries listed.  Two passes over the tile column's ranges (count, then write), 32 rows x 8 lanes per trip as k_plan_estimate.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_tile_lists(FrameParams P, const PixelBox *__restrict__ row_boxes, const BlockRec *__restrict__ recs,
+                                                    const float4 *__restrict__ cap_seg, const float *__restrict__ cap_rad,
+                                                    const uint32_t *__restrict__ rc_lo, const uint32_t *__restrict__ rc_hi,
+                                                    uint4 *__restrict__ ent, uint4 *__restrict__ hdr, uint32_t *__restrict__ ctl, uint32_t capacity)
+{
+    __shared__ uint32_t s_cnt[1024];                        // per block row: entries, then (after the scan) entries in the rows above it
+    __shared__ uint32_t s_part[4], s_at, s_hi, s_lo;
+    int32_t px_lo, px_hi, py_lo, py_hi;
+    const TilePlace tp = tile_rect(P, blockIdx.x, px_lo, px_hi, py_lo, py_hi);
+    const uint32_t tid = threadIdx.x, sub = tid & 7u, rsub = tid >> 3, lane = tid & 63u, wv = tid >> 6;
+    for (uint32_t r = tid; r < 1024u; r += 256u) s_cnt[r] = 0u;
+    if (tid == 0) { s_hi = 0u; s_lo = 0xFFFFu; }
+    __syncthreads();
+    // does block bx of row r belong on the list?  (its entry in e when it does)
+    auto test = [&](uint32_t r, uint32_t bx, uint4 &e) -> bool {
+        const uint4 rw = *reinterpret_cast<const uint4 *>(recs + r * P.nb + bx);                  // box (2 words), flags, count
+        const int32_t x0 = (int16_t)(rw.x & 0xFFFFu), y0 = (int16_t)(rw.x >> 16), x1 = (int16_t)(rw.y & 0xFFFFu), y1 = (int16_t)(rw.y >> 16);
+        if (!(x0 <= x1 && x1 >= px_lo && x0 <= px_hi && y1 >= py_lo && y0 <= py_hi)) return false;
+        if (!capsule_hits_rect(cap_seg[r * P.nb + bx], cap_rad[r * P.nb + bx], px_lo, px_hi, py_lo, py_hi)) return false;
+        e = make_uint4(bx | (r << 10), rw.x, rw.y, 0u);
+        return true;
+    };
+    auto row_range = [&](uint32_t r, uint32_t &lo, uint32_t &hi) -> bool {
+        const PixelBox rr = row_boxes[r];
+        lo = rc_lo[tp.tx * P.nb + r]; hi = rc_hi[tp.tx * P.nb + r];
+        return lo < hi && rr.x0 <= rr.x1 && rr.x1 >= px_lo && rr.x0 <= px_hi && rr.y1 >= py_lo && rr.y0 <= py_hi;
+    };
+    // ---- pass 1: entries per row ----
+    for (uint32_t base = 0; base < P.nb; base += 32u) {
+        const uint32_t r = base + rsub;
+        uint32_t c = 0, lo = 1, hi = 0;
+        if (r < P.nb && row_range(r, lo, hi))
+            for (uint32_t bx = lo + sub; bx < hi; bx += 8u) { uint4 e; c += test(r, bx, e) ? 1u : 0u; }
+        c += __shfl_xor(c, 1); c += __shfl_xor(c, 2); c += __shfl_xor(c, 4);             // the row's eight lanes
+        if (sub == 0 && c) { s_cnt[r] = c; atomicMax(&s_hi, r); atomicMin(&s_lo, r); }
+    }
+    __syncthreads();
+    // ---- entries in the rows ABOVE each row (the list runs from the highest row down): a scan over the rows in descending order ----
+    uint32_t mine[4], sum = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { mine[k] = s_cnt[1023u - (tid * 4u + (uint32_t)k)]; sum += mine[k]; }
+    const uint32_t inc = wave_scan_add(sum);
+    if (lane == 63u) s_part[wv] = inc;
+    __syncthreads();
+    uint32_t before = inc - sum;
+    for (uint32_t w = 0; w < wv; ++w) before += s_part[w];
+    const uint32_t total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { s_cnt[1023u - (tid * 4u + (uint32_t)k)] = before; before += mine[k]; }   // (each thread rewrites the four words it read)
+    const uint32_t row_hi = s_hi, row_lo = s_lo;
+    const uint32_t span = total ? row_hi - row_lo + 1u : 0u;
+    const uint32_t noff4 = (span + 1u + 3u) / 4u;           // 16-byte units of the offset words: one per row of the span and the total
+    if (tid == 0) {
+        uint32_t at = 0xFFFFFFFFu;
+        if (total) {
+            const unsigned long long need = (unsigned long long)noff4 + total;
+            const unsigned long long got = atomicAdd(reinterpret_cast<unsigned long long *>(ctl), need);
+            if (got + need <= (unsigned long long)capacity) at = (uint32_t)got;
+            if (at != 0xFFFFFFFFu) { atomicAdd(&ctl[2], 1u); atomicAdd(&ctl[4], total); } else atomicAdd(&ctl[3], 1u);
+            hdr[blockIdx.x] = at != 0xFFFFFFFFu ? make_uint4(at + noff4, total, row_hi | (row_lo << 16), at) : make_uint4(0u, 0xFFFFFFFFu, 0u, 0u);
+        } else {
+            atomicAdd(&ctl[2], 1u);                         // nothing reaches the tile: an empty list is a list
+            hdr[blockIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+        }
+        s_at = at;
+    }
+    __syncthreads();
+    const uint32_t at = s_at;
+    if (at == 0xFFFFFFFFu) return;                          // (uniform) nothing to write, or no room
+    uint32_t *const roff = reinterpret_cast<uint32_t *>(ent + at);
+    for (uint32_t j = tid; j <= span; j += 256u) roff[j] = j < span ? s_cnt[row_hi - j] : total;
+    uint4 *const out = ent + at + noff4;
+    // ---- pass 2: the entries, each row's at its offset, blocks ascending ----
+    for (uint32_t base = 0; base < P.nb; base += 32u) {
+        const uint32_t r = base + rsub;
+        uint32_t lo = 1, hi = 0;
+        const bool on = r < P.nb && row_range(r, lo, hi);
+        // the row's eight lanes take blocks lo + 8 t + sub of trip t: a lane's entry goes behind those of the lower lanes of its trip
+        const uint32_t trips = on ? (hi - lo + 7u) / 8u : 0u;
+        uint32_t tmax = trips, done = 0;
+        tmax = max(tmax, (uint32_t)__shfl_xor((int)tmax, 8)); tmax = max(tmax, (uint32_t)__shfl_xor((int)tmax, 16)); tmax = max(tmax, (uint32_t)__shfl_xor((int)tmax, 32));
+        for (uint32_t t = 0; t < tmax; ++t) {              // (wave-uniform trip count: the ballot below needs every lane)
+            uint4 e = make_uint4(0u, 0u, 0u, 0u);
+            const uint32_t bx = lo + sub + 8u * t;
+            const bool hit = t < trips && bx < hi && test(r, bx, e);
+            const unsigned long long m = __ballot(hit);
+            const uint32_t grp = (uint32_t)((m >> (lane & ~7u)) & 0xFFull);             // this row's eight lanes
+            if (hit) out[s_cnt[r] + done + (uint32_t)__popc(grp & ((1u << sub) - 1u))] = e;
+            done += (uint32_t)__popc(grp);
+        }
+    }
+}
+
 // `flags_out`: this frame's per-tile word (bit 0 background, bits 8.. the cut).  Not the `background` array itself: when the plan is
 // not fresh, `last_flags` IS this plan state's `background` (the frame two back), and other workgroups of this launch still read
 // their neighbours' old entries -- k_plan_sort, which runs after every workgroup of this kernel, moves the new words over.
@@ -1552,6 +1660,8 @@ struct PhaseClock {
 #define VF_PH_PASS
 #endif
 // ---- k_tile's constants, its LDS and its phases --------------------------------------------------------------------------------
+// a plan state's per-tile candidate lists (k_tile_lists); both NULL: none built, or not for the frame in flight
+struct TileLists { const uint4 *ent; const uint4 *hdr; };
 namespace tile {
 constexpr int kWaves = kTileThreads / 64;
 constexpr int kNV = kBlockVerts * kBlockVerts;             // 81
@@ -1789,6 +1899,78 @@ __device__ __forceinline__ void fill_work_list(const Lds &L, uint32_t cursor, ui
     }
 }
 
+// A chunk's work list from the tile's candidate list (k_tile_lists), for an item whose tile has one: `done` of the tile's `span` block
+// rows (hi downwards; a step = a block row, with or without entries) are behind us.  The offset words say how many of the next
+// <= kMaxSteps rows fit the work list (today's rule: <= kChunk listed blocks, whole rows; the rest wait); their entries are read
+// coalesced, 64 per wave trip, each lane tests its entry's box against the item's rectangle -- the strips of a tile filter the same
+// list -- and the masks (block_is_candidate; the capsule, which the builder held against the whole tile, is fetched and held against
+// a STRIP's rectangle for the entries whose box meets it -- at the default camera the far blocks are slanted slivers whose boxes
+// meet several 4-pixel strips and whose capsules meet one: without it a rank of eight pulled that many more blocks, 0.184 -> 0.277
+// ms), and the hits are compacted in order into `list`, with `pending` and `firstid` as fill_work_list leaves them.  The trips' ballots and the entries'
+// block words wait in the `hit` area (free in this phase; 512 B + 16 KB of the overlay's 18.1 KB), not in registers: no scratch in
+// the chunk loop.  One workgroup barrier inside.
+template <bool GROUPS>
+__device__ __forceinline__ void take_listed_rows(const FrameParams &P, const Lds &L, const TileCtx &T, const uint4 *__restrict__ ent,
+                                                 const uint32_t *__restrict__ roff, const float4 *__restrict__ cap_seg, const float *__restrict__ cap_rad,
+                                                 bool strip, uint32_t row_hi, uint32_t done, uint32_t span_all,
+                                                 uint32_t tid, uint32_t lane, uint32_t wave, uint32_t &nsteps, uint32_t &nlist VF_PH_ARG)
+{
+    static_assert(kMaxSteps == 128 && kChunk == 64u * 64u, "two lanes' worth of offset words and one; one ballot per lane in the scan");
+    static_assert(sizeof(unsigned long long) * 64 + sizeof(uint32_t) * kChunk <= kOverlayBytes, "ballots + block words live in the overlay");
+    const uint32_t span = min((uint32_t)kMaxSteps, span_all - done);
+    const uint32_t *const o = roff + done;                  // o[k]: entries in front of step k's (o[span]: behind the last step's)
+    const uint32_t v0 = lane <= span ? o[lane] : 0u, v1 = 64u + lane <= span ? o[64u + lane] : 0u;
+    const uint32_t v2 = span == 128u ? o[128] : 0u;
+    const uint32_t e_first = (uint32_t)__builtin_amdgcn_readfirstlane((int)v0);
+    const unsigned long long fa = __ballot(lane >= 1u && lane <= span && v0 - e_first <= kChunk), fb = __ballot(64u + lane <= span && v1 - e_first <= kChunk);
+    // (the offsets rise with the step: the steps that fit are the first ones; a single row always fits, nb <= 1024 < kChunk)
+    nsteps = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)__popcll(fa) + (uint32_t)__popcll(fb) + (span == 128u && v2 - e_first <= kChunk ? 1u : 0u)));
+    uint32_t e_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)v2);
+    if (nsteps < 64u) e_end = (uint32_t)__builtin_amdgcn_readlane((int)v0, (int)nsteps);
+    else if (nsteps < 128u) e_end = (uint32_t)__builtin_amdgcn_readlane((int)v1, (int)(nsteps - 64u));
+    const uint32_t n_ent = e_end - e_first, ntrips = (n_ent + 63u) / 64u;                   // <= kChunk, <= 64
+    const uint32_t row_top = row_hi - done;                 // the block row of step 0
+    asm volatile("" : "+v"(tid));                           // (the addresses of the thread's two words: not hoisted to kernel entry and spilled -- refresh_fin4)
+    if (tid < nsteps) { L.pending[tid] = 0u; L.firstid[tid] = 2u * ((row_top - tid) * kBlockCells * P.nm1) + 1u; }   // smallest (id + 1) of the row
+    unsigned long long *const hitm = &L.hit[0][0];
+    uint32_t *const stage = reinterpret_cast<uint32_t *>(hitm + 64);
+    const uint4 *const src = ent + e_first;
+    for (uint32_t t = wave; t < ntrips; t += kWaves) {
+        const uint32_t idx = t * 64u + lane;
+        bool hit = false;
+        if (idx < n_ent) {
+            const uint4 e = src[idx];
+            stage[idx] = e.x;
+            const PixelBox box = PixelBox{ (int16_t)(e.y & 0xFFFFu), (int16_t)(e.y >> 16), (int16_t)(e.z & 0xFFFFu), (int16_t)(e.z >> 16) };
+            float4 seg = make_float4(0.f, 0.f, 0.f, 0.f);
+            float rad = INFINITY;                           // (no capsule: it met the tile)
+            if (strip && box.x1 >= T.px_lo && box.x0 <= T.px_hi) {
+                const uint32_t bidx = ((e.x >> 10) & 0x3FFu) * P.nb + (e.x & 0x3FFu);
+                seg = cap_seg[bidx]; rad = cap_rad[bidx];
+            }
+            hit = block_is_candidate<GROUPS>(box, seg, rad, T);
+        }
+        const unsigned long long m = __ballot(hit);
+        if (lane == 0) hitm[t] = m;
+    }
+    VF_PH(9)                                                // candidate tests
+    __syncthreads();
+    VF_PH(10)                                               // ... waiting for the slowest wave
+    // every wave scans the trips' counts for itself (one per lane), so all agree on the positions without another barrier
+    const uint32_t c = lane < ntrips ? (uint32_t)__popcll(hitm[lane]) : 0u;
+    const uint32_t inc = wave_scan_add(c);
+    nlist = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+    for (uint32_t t = wave; t < ntrips; t += kWaves) {
+        const unsigned long long m = hitm[t];
+        const uint32_t pos = (uint32_t)__builtin_amdgcn_readlane((int)inc, (int)t) - (uint32_t)__popcll(m);
+        if ((m >> lane) & 1ull) {
+            const uint32_t e = stage[t * 64u + lane], step = row_top - ((e >> 10) & 0x3FFu);
+            L.list[pos + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = (e & 0xFFFFFu) | (step << 20);
+            atomicAdd(&L.pending[step], 1u);
+        }
+    }
+}
+
 // Every block of the chunk is done: exact masks for the next chunk; returns the number of final pixels.  One workgroup barrier inside.
 template <bool GROUPS>
 __device__ __forceinline__ uint32_t publish_chunk_masks(const Lds &L, uint32_t nsteps, uint32_t lane, uint32_t wave)
@@ -1865,7 +2047,7 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
                                                        const uint32_t *__restrict__ rc_lo, const uint32_t *__restrict__ rc_hi,
                                                        uint32_t *__restrict__ rgba, uint32_t *__restrict__ vis_out, uint32_t *stats,
                                                        uint32_t *__restrict__ last_blocks, uint32_t *__restrict__ redo,
-                                                       const ulonglong2 *__restrict__ band)
+                                                       const ulonglong2 *__restrict__ band, TileLists TL)
 {
     using namespace tile;
     uint32_t *const redo_count = work_count + 3;           // items handed to the complete variant
@@ -1888,6 +2070,7 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
     __shared__ __attribute__((aligned(16))) float s_lut[kLutFloats];
     __shared__ float s_thr[256];
     __shared__ uint32_t s_per[65];
+    __shared__ uint32_t s_tl[4];                           // the tile's candidate-list header (k_tile_lists), or "none" in [1]
     WaveLds &s_wave = *reinterpret_cast<WaveLds *>(s_overlay);
     int2 (&sXY)[kWaves][kNV] = s_wave.xy;
     uint32_t (&sS)[kWaves][kBlockPrims] = s_wave.surv;
@@ -1941,17 +2124,35 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
     for (int k = tid; k < kTileH * 2; k += kTileThreads) s_rowfin[k] = 0u;
     if (tid < kTileW / 4 * 2) { s_colfin4[tid] = 0u; s_rowfin4[tid] = 0u; }
     if (tid < 16) s_rows[tid] = 0ull;
-    if (tid == 0) { s_done = 0; s_blocks = 0; s_redo = 0; }
+    if (tid == 0) {
+        s_done = 0; s_blocks = 0; s_redo = 0;
+        uint4 th = make_uint4(0u, 0xFFFFFFFFu, 0u, 0u);
+        if (TL.hdr) th = TL.hdr[tile];
+        s_tl[0] = th.x; s_tl[1] = th.y; s_tl[2] = th.z; s_tl[3] = th.w;
+    }
     __syncthreads();
     VF_PH(13)                                              // item record, tile state
-    const uint32_t nrows_total = list_block_rows(P, L, T, row_boxes, rc_lo, rc_hi, tcol, tid, lane, wave VF_PH_PASS);
+    // the tile's candidate list, if its plan state holds one for this geometry (workgroup-uniform; the strips of a tile share it): the
+    // row range comes from its header, a step is a block row of that range.  (The header waits in LDS for the chunk loop, which reads
+    // it where it needs it: nothing of it lives in a register across the block loop.)
+    const bool listed = lds_peek(&s_tl[1]) != 0xFFFFFFFFu;
+    uint32_t nrows_total;
+    if (listed) { const uint32_t n = lds_peek(&s_tl[1]), rows = lds_peek(&s_tl[2]); nrows_total = n ? (rows & 0xFFFFu) - (rows >> 16) + 1u : 0u; }
+    else nrows_total = list_block_rows(P, L, T, row_boxes, rc_lo, rc_hi, tcol, tid, lane, wave VF_PH_PASS);
     VF_PH(8)                                                // item start, tile state, row list
     uint32_t dbg_loop = 0;                                 // (VF_DIAG_ITEM=1 only; dead code otherwise)
     const uint32_t hit_words = (P.nb + 63u) / 64u;
     for (uint32_t cursor = 0; cursor < nrows_total;) {     // ---- chunks of <= kMaxSteps block rows, nearest first; uniform: nothing (left) to draw ends the loop ----
         // chunk set-up 1: each wave tests the blocks of its rows (the next <= kMaxSteps of the list) against the tile; the ballots are kept
-        const uint32_t nrowsteps = min((uint32_t)kMaxSteps, nrows_total - cursor);
         if (tid == 0) { s_next = 0; s_lock = 0; s_frontier = 0; s_published = 0; }
+        uint32_t nsteps, nlist;
+        if (lds_peek(&s_tl[1]) != 0xFFFFFFFFu) {
+            const uint32_t e0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_peek(&s_tl[0])), o0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_peek(&s_tl[3]));
+            const uint32_t row_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_peek(&s_tl[2])) & 0xFFFFu;
+            take_listed_rows<GROUPS>(P, L, T, TL.ent + e0, reinterpret_cast<const uint32_t *>(TL.ent + o0), cap_seg, cap_rad, ((item >> 24) & 7u) != 0u, row_hi, cursor, nrows_total,
+                                     tid, lane, wave, nsteps, nlist VF_PH_PASS);
+        } else {
+        const uint32_t nrowsteps = min((uint32_t)kMaxSteps, nrows_total - cursor);
         // (lanes = (row, block) pairs in the kernel instantiation WITHOUT line groups only -- the one a handle ends up with when its items
         //  are narrow strips of far-field tiles, hundreds of rows each: C4, a rank of eight 0.214 -> 0.199 ms; the other instantiation's
         //  wide items have a dozen rows and lose 1 % to the longer code: measured both ways, EXPERIMENTS.md)
@@ -1961,8 +2162,8 @@ __global__ __launch_bounds__(kTileThreads, VF_TILE_MIN_WAVES) void k_tile(FrameP
         __syncthreads();
         VF_PH(10)                                           // ... waiting for the slowest wave
         // chunk set-up 2 + 3: list offsets, the work list
-        uint32_t nsteps, nlist;
         fill_work_list(L, cursor, nrowsteps, lane, wave, nsteps, nlist);
+        }
         cursor += nsteps;
         VF_PH(11)                                           // scan + list fill
         __syncthreads();
