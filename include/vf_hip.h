@@ -765,6 +765,62 @@ int vf_terrain_debug_cumulative_viewshed_batch(vf_terrain *t, uint32_t batch);
 int vf_terrain_debug_cumulative_viewshed_scans(vf_terrain *t, uint32_t *count);
 int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, float *ms);
 
+/* ---- sun exposure: the weighted sum of the shadow fields of N suns, and a tint of the frame ----------
+ * The exposure field is one float32 per grid vertex, (grid, grid) row-major as the shadow field: exposure in [0, sum of weights], the
+ * sum over the suns of lit_o * c_o * w_o.  suns_xyz = count direction vectors (x, y, z) towards the sun, as the uniforms hold the
+ * handle's own; they need not be normalised.  lit_o is the shadow field (vf_terrain_read_shadow_field) of that sun at strength 1 with
+ * the call's softness and bias, bit for bit.  A sun whose y is not > 0 (on or below the horizon, a zero vector) is not counted: it
+ * adds nothing and costs nothing.  weights = count numbers in [0, 1], or NULL: all 1 -- the share of a time step, or the
+ * transmittance, that the caller's ephemeris gives a sun.  incidence != 0: c_o is the cosine between the sun and the surface normal
+ * of the height field (central differences, one-sided on the grid's edges), clamped to [0, 1], 0 where a height involved is not
+ * finite; incidence == 0: c_o = 1.  Each sun's term enters the sum as q = rint(lit * c * w * 65536), an unsigned 32-bit integer, so
+ * the sum does not depend on the order of the suns or on how they are batched, and exposure = (float)sum / 65536.  The arithmetic is
+ * fixed bit for bit.  The field is computed by the first tinted frame or field call that needs it and again only after
+ * the heights, the spacing, the exaggeration, a sun, a weight, incidence, softness or bias have changed -- not for the colours, the
+ * camera or the handle's own sun.
+ *
+ * vf_terrain_set_sun_exposure: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then (behind
+ * the shadow, ambient and drape passes, under both viewshed tints if they are on too) blends over every covered pixel low_rgba with
+ * coverage 1 - s and high_rgba with coverage s, s the interpolated f = min(exposure / W, 1), W the sum of the counted suns' weights
+ * in list order (f = 0 when W is 0), as vf_terrain_set_viewshed blends its hidden and visible colours.  Overlays composite
+ * afterwards; geometry buffers and the diagnostics frames are unaffected.  1 <= count <= 65535, suns and weights finite, weights in
+ * [0, 1], softness > 0, bias >= 0, both finite, else VF_ERR_INVALID and nothing changes.  Whole-frame handles only: enabling on a
+ * band- or tile-sharded handle, sharding a handle with sun exposure enabled, and vf_terrain_render_batch / _batch_host on such a
+ * handle are VF_ERR_INVALID and change nothing.  The parameters are stored also with enable == 0 (the field calls below use them).
+ * The setting survives height uploads.  A handle that never calls any of these allocates and launches nothing for them.
+ * vf_terrain_clear_sun_exposure: the suns are forgotten, the defaults are back and everything made for them is freed.
+ * vf_terrain_read_sun_exposure_field: the exposure field for the current heights, uniforms, suns and parameters into host memory
+ * (grid * grid floats), whether or not sun exposure is enabled for drawing; VF_ERR_INVALID before suns are set.
+ * vf_terrain_sun_exposure_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream);
+ * later calls on the handle are ordered behind the copy by the library.
+ * vf_terrain_sun_exposure_info: the setting, N, the number of counted suns, W, and the number of suns a launch took in the last
+ * computation (0 before it). */
+#define VF_SUN_EXPOSURE_MAX_SUNS 65535u
+#define VF_SUN_EXPOSURE_HIGH_RGBA 0xA040D0FFu   /* (255, 208, 64, 160) as r | g << 8 | b << 16 | a << 24 */
+#define VF_SUN_EXPOSURE_LOW_RGBA 0x00000000u    /* (0, 0, 0, 0): ground that no sun reaches keeps the frame's colour */
+typedef struct vf_sun_exposure_info {
+    int32_t enabled;
+    uint32_t count;           /* N; 0: no suns set */
+    uint32_t counted;         /* suns above the horizon (y > 0) */
+    float weight_total;       /* W: the sum of their weights */
+    int32_t incidence;
+    uint32_t batch;           /* suns per launch in the last computation */
+    float softness, bias;
+    uint8_t high_rgba[4], low_rgba[4];
+} vf_sun_exposure_info;
+int vf_terrain_set_sun_exposure(vf_terrain *t, int enable, const float *suns_xyz /* count x 3 */, const float *weights /* count, or NULL */,
+                                uint32_t count, int incidence, float softness, float bias, const uint8_t high_rgba[4], const uint8_t low_rgba[4]);
+int vf_terrain_clear_sun_exposure(vf_terrain *t);
+int vf_terrain_read_sun_exposure_field(vf_terrain *t, float *exposure);
+int vf_terrain_sun_exposure_field_device(vf_terrain *t, float *dev_exposure, void *stream);
+int vf_terrain_sun_exposure_info(vf_terrain *t, vf_sun_exposure_info *out);
+/* diagnostics: the number of suns a launch takes (0: as many as the memory budget for the carries holds; the next call computes the
+ * field again); how many times the handle has computed its field so far (the diagnostic launches are not counted); and the average
+ * time (HIP events) of `repeats` computations of the field, after one warm-up. */
+int vf_terrain_debug_sun_exposure_batch(vf_terrain *t, uint32_t batch);
+int vf_terrain_debug_sun_exposure_scans(vf_terrain *t, uint32_t *count);
+int vf_terrain_debug_sun_exposure_stage(vf_terrain *t, uint32_t repeats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,9 @@ SYMBOLS = [
     "vf_terrain_set_cumulative_viewshed", "vf_terrain_read_cumulative_viewshed_field", "vf_terrain_cumulative_viewshed_field_device",
     "vf_terrain_cumulative_viewshed_info", "vf_terrain_read_cumulative_viewshed_vertices", "vf_terrain_debug_cumulative_viewshed_batch",
     "vf_terrain_debug_cumulative_viewshed_scans", "vf_terrain_debug_cumulative_viewshed_stage",
+    "vf_terrain_set_sun_exposure", "vf_terrain_clear_sun_exposure", "vf_terrain_read_sun_exposure_field", "vf_terrain_sun_exposure_field_device",
+    "vf_terrain_sun_exposure_info", "vf_terrain_debug_sun_exposure_batch", "vf_terrain_debug_sun_exposure_scans",
+    "vf_terrain_debug_sun_exposure_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -72,6 +75,11 @@ class ViewshedInfo(C.Structure):
 class CumulativeViewshedInfo(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("count", C.c_uint32), ("batch", C.c_uint32), ("eye_height", C.c_float), ("target_height", C.c_float),
                 ("radius", C.c_float), ("softness", C.c_float), ("bias", C.c_float), ("high_rgba", C.c_uint8 * 4), ("low_rgba", C.c_uint8 * 4)]
+
+
+class SunExposureInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("count", C.c_uint32), ("counted", C.c_uint32), ("weight_total", C.c_float), ("incidence", C.c_int32),
+                ("batch", C.c_uint32), ("softness", C.c_float), ("bias", C.c_float), ("high_rgba", C.c_uint8 * 4), ("low_rgba", C.c_uint8 * 4)]
 
 
 DIST_UNIQUE_ID_BYTES = 128
@@ -182,6 +190,14 @@ _PROTOS = {
     "vf_terrain_debug_cumulative_viewshed_batch": (_i, [_vp, _u32]),
     "vf_terrain_debug_cumulative_viewshed_scans": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_debug_cumulative_viewshed_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_sun_exposure": (_i, [_vp, _i, _vp, _vp, _u32, _i, _f, _f, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "vf_terrain_clear_sun_exposure": (_i, [_vp]),
+    "vf_terrain_read_sun_exposure_field": (_i, [_vp, _vp]),
+    "vf_terrain_sun_exposure_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_sun_exposure_info": (_i, [_vp, C.POINTER(SunExposureInfo)]),
+    "vf_terrain_debug_sun_exposure_batch": (_i, [_vp, _u32]),
+    "vf_terrain_debug_sun_exposure_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_debug_sun_exposure_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -697,6 +713,57 @@ class Terrain:
         """ms of one computation of the field, as timed launches of their own (diagnostics)."""
         ms = _f()
         self._check(self.lib.vf_terrain_debug_cumulative_viewshed_stage(self.t, int(repeats), C.byref(ms)))
+        return ms.value
+
+    def set_sun_exposure(self, suns, *, weights=None, incidence=False, enabled=True, softness=0.02, bias=0.002, high_rgba=(255, 208, 64, 160),
+                         low_rgba=(0, 0, 0, 0)):
+        """Sun exposure: the weighted sum of the shadow fields of the suns, (N, 3) direction vectors, as a tint of the
+        frame.  The C call takes vectors: the angle form (N, 2) is the extension's, which shares set_sun's own arithmetic.  Every
+        parameter is stored by every call, also one that disables, and steers sun_exposure_field() too."""
+        from ._sun_exposure import sun_exposure_args
+        en, s, w, inc, soft, bias, high, low = sun_exposure_args(suns, weights, incidence, enabled, softness, bias, high_rgba, low_rgba)
+        if s.shape[1] != 3:
+            raise ValueError("the C ABI takes suns as (N, 3) direction vectors")
+        self._check(self.lib.vf_terrain_set_sun_exposure(self.t, en, s.ctypes.data, w.ctypes.data, s.shape[0], inc, soft, bias, (C.c_uint8 * 4)(*high),
+                                                         (C.c_uint8 * 4)(*low)))
+
+    def clear_sun_exposure(self):
+        """Forget the suns: sun exposure is off, its parameters are the defaults again and its buffers are freed."""
+        self._check(self.lib.vf_terrain_clear_sun_exposure(self.t))
+
+    def sun_exposure_field(self):
+        """The exposure field for the current heights, uniforms, suns and parameters: (grid, grid) float32 in [0, sum of weights]."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_sun_exposure_field(self.t, out.ctypes.data))
+        return out
+
+    def sun_exposure_field_device(self, dev_exposure, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_sun_exposure_field_device(self.t, dev_exposure, stream))
+
+    def sun_exposure_info(self):
+        """dict: enabled, suns (N), counted, weight_total, incidence, batch, softness, bias and the colours."""
+        from ._sun_exposure import sun_exposure_info
+        v = SunExposureInfo()
+        self._check(self.lib.vf_terrain_sun_exposure_info(self.t, C.byref(v)))
+        return sun_exposure_info(v.enabled, v.count, v.counted, v.weight_total, v.incidence, v.batch, v.softness, v.bias, tuple(v.high_rgba),
+                                 tuple(v.low_rgba))
+
+    def sun_exposure_batch(self, batch=0):
+        """Force the number of suns a launch takes (diagnostics); 0: from the memory budget again."""
+        self._check(self.lib.vf_terrain_debug_sun_exposure_batch(self.t, int(batch)))
+
+    def sun_exposure_scans(self):
+        """How many times the handle has computed its sun exposure field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_sun_exposure_scans(self.t, C.byref(n)))
+        return n.value
+
+    def sun_exposure_stage(self, repeats=5):
+        """ms of one computation of the field, as timed launches of their own (diagnostics)."""
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_sun_exposure_stage(self.t, int(repeats), C.byref(ms)))
         return ms.value
 
     def set_drape(self, image, *, extent=None, opacity=1.0, filter="linear"):

@@ -10,6 +10,7 @@
 #include "vf_relight.h"     // templates only: the shade pass of the three
 #include "vf_viewshed.h"    // templates only
 #include "vf_cumulative_viewshed.h"   // templates only
+#include "vf_sun_exposure.h"          // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -471,6 +472,27 @@ struct vf_terrain {
         std::vector<ViewshedPlan> plans; // the host's copy of d_plans (the source of its upload)
         uint32_t batch = 0;              // the batch size of the last computation
     } cv;
+    // sun exposure: buffers made by the first tinted frame or field read; the sums are formed again only when what they
+    // were made from has changed (not for the colours, the camera or the handle's own sun)
+    struct SunExposure {
+        bool enabled = false, incidence = false;
+        std::vector<float> suns;         // the sun vectors as given, (x, y, z) each; empty: none set
+        std::vector<float> weights;      // one per sun
+        uint32_t counted = 0;            // suns with sy > 0
+        float wtot = 0.0f;               // the sum of their weights, in list order
+        float softness = VF_SHADOW_SOFTNESS, bias = VF_SHADOW_BIAS;
+        uint32_t high_rgba = VF_SUN_EXPOSURE_HIGH_RGBA, low_rgba = VF_SUN_EXPOSURE_LOW_RGBA;
+        uint32_t forced_batch = 0;       // vf_terrain_debug_sun_exposure_batch; 0: from the memory budget
+        DevBuf<uint32_t> d_sum;          // n x n sums of q
+        VertexField exposure;            // sum / 65536; key: spacing, exaggeration, softness, bias, incidence, the length of the list, the
+                                         // suns (x, y, z) each, the weights
+        DevBuf<float> d_frac;            // n x n: min(exposure / wtot, 1)
+        DevBuf<float2> d_slope;          // n x n (px, pz); only with incidence
+        DevBuf<float> d_cmax;            // carries of a batch: B x nchunks x (2n - 1)
+        DevBuf<ExposureSun> d_suns;      // the suns that add something: x-major scans, z-major scans, degenerate ones
+        std::vector<ExposureSun> recs;   // the host's copy of d_suns (the source of its upload)
+        uint32_t batch = 0;              // the batch size of the last computation
+    } se;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -922,6 +944,16 @@ static void cumulative_release(vf_terrain *t)
     H.count.scans = scans; H.forced_batch = forced;
 }
 
+// sun exposure: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced batch size stay
+static void exposure_release(vf_terrain *t)
+{
+    vf_terrain::SunExposure &H = t->se;
+    H.d_sum.release(); H.exposure.release(); H.d_frac.release(); H.d_slope.release(); H.d_cmax.release(); H.d_suns.release();
+    const uint32_t scans = H.exposure.scans, forced = H.forced_batch;
+    H = vf_terrain::SunExposure();
+    H.exposure.scans = scans; H.forced_batch = forced;
+}
+
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
@@ -999,7 +1031,7 @@ void vf_terrain_destroy(vf_terrain *t)
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     t->d_gb.release(); t->d_pick.release();
-    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t);
+    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t); exposure_release(t);
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -1175,6 +1207,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->dr.iw && nranks != 1) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     if (t->vs.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
     if (t->cv.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
+    if (t->se.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1302,6 +1335,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
+    if (t->se.enabled) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1739,6 +1773,7 @@ static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 
 static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
@@ -1749,7 +1784,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const Relight drape_pass = t->dm.enabled ? kDrapeMip : kDrape;   // (through the mip pyramid when mipmaps are on)
     const bool viewshed = t->vs.enabled && !diag;
     const bool cumulative = t->cv.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative;
+    const bool exposure = t->se.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1813,6 +1849,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
         const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, drape_pass, shadows, ambient);
         if (drc != VF_OK) return drc;
+    }
+    if (exposure && ntiles) {                              // the sun exposure's tint: behind both viewshed tints
+        const int erc = exposure_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        if (erc != VF_OK) return erc;
     }
     if (cumulative && ntiles) {                            // the cumulative viewshed's tint: behind the single observer's
         const int crc = cumulative_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
@@ -1953,6 +1993,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
+    if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -1974,6 +2015,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
+    if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2790,16 +2832,22 @@ static bool line_geometry(const vf_terrain *t, float hx, float hz, ShadowPlan &S
 }
 
 // The frame of reference of the field for the uniforms `u`; false: every vertex is lit.
+static bool sun_plan(const vf_terrain *t, const float sun[3], float spacing, float exag, float strength, float softness, float bias, ShadowPlan &S)
+{
+    const float sy = sun[1];
+    float amaj;
+    if (!line_geometry(t, sun[0], sun[2], S, amaj) || !std::isfinite(sy)) return false;
+    const float d = sy > 0.0f ? ((grid_step(t) * spacing) * sy) / amaj : 0.0f;
+    if (!std::isfinite(d)) return false;
+    S.d = d; S.exag = exag; S.strength = strength; S.softness = softness; S.bias = bias;
+    return true;
+}
+
+// ... of the handle's own sun and shadow parameters
 static bool shadow_plan(const vf_terrain *t, const float *u, ShadowPlan &S)
 {
     const vf_terrain::Shadows &H = t->sh;
-    const float sy = u[33];
-    float amaj;
-    if (!line_geometry(t, u[32], u[34], S, amaj) || !std::isfinite(sy)) return false;
-    const float d = sy > 0.0f ? ((grid_step(t) * spacing_of(u)) * sy) / amaj : 0.0f;
-    if (!std::isfinite(d)) return false;
-    S.d = d; S.exag = u[38]; S.strength = H.strength; S.softness = H.softness; S.bias = H.bias;
-    return true;
+    return sun_plan(t, u + 32, spacing_of(u), u[38], H.strength, H.softness, H.bias, S);
 }
 
 // `lit` holds the field of the uniforms `u`, the handle's heights and shadow parameters once the work queued on `s` is done.  The
@@ -2967,9 +3015,10 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
 
 static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
+static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 
 // The per-vertex fields a caller can have.  A new one is a feature struct that holds a VertexField, its *_field function and a row here.
-enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFields };
+enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFieldExposure, kFields };
 struct FieldRow {
     int (*compute)(vf_terrain *, const float *, hipStream_t, bool);   // its *_field function
     VertexField &(*cache)(vf_terrain *);                               // its buffer, key and scan counter
@@ -2982,6 +3031,8 @@ static const FieldRow kFieldTable[kFields] = {
       [](const vf_terrain *t) -> const char * { return t->vs.have_observer ? nullptr : "no observer set (vf_terrain_set_viewshed)"; } },
     { cumulative_field, [](vf_terrain *t) -> VertexField & { return t->cv.count; },
       [](const vf_terrain *t) -> const char * { return t->cv.xz.empty() ? "no observers set (vf_terrain_set_cumulative_viewshed)" : nullptr; } },
+    { exposure_field, [](vf_terrain *t) -> VertexField & { return t->se.exposure; },
+      [](const vf_terrain *t) -> const char * { return t->se.suns.empty() ? "no suns set (vf_terrain_set_sun_exposure)" : nullptr; } },
 };
 
 // Field f for the live uniforms, heights and parameters, complete in its buffer; then to `host`, or to `dev` behind the work on
@@ -3742,6 +3793,208 @@ int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, 
     const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = cumulative_field(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("cumulative viewshed diagnostics: ") + hipGetErrorString(err));
+    *ms = a;
+    return VF_OK;
+}
+
+// ---- sun exposure (vf_sun_exposure.h) ---------------------------------------------------
+
+// The carries of a batch may take this many floats (32 MiB), for the reason DESIGN.md 4m measured: every sun of a batch reads the one
+// height cache, and carries that stream through the last-level cache push it out.
+constexpr size_t kSeCarryFloats = (size_t)8u << 20;
+constexpr uint32_t kSeMaxBatch = 4096;                        // (the sun's index rides in grid.z and grid.y: at most 65535)
+
+// suns per launch: as many as the budget for the carries holds, a slot being nchunks x (2n - 1) floats
+static uint32_t exposure_batch(const vf_terrain *t, uint32_t scans, size_t stride)
+{
+    const size_t B = t->se.forced_batch ? t->se.forced_batch : std::max<size_t>(kSeCarryFloats / stride, 1u);
+    return (uint32_t)std::max<size_t>(std::min<size_t>(std::min<size_t>(B, kSeMaxBatch), scans), 1u);
+}
+
+// `exposure` and d_frac hold the field of the uniforms `u`, the handle's heights, suns, weights and scan parameters once the work
+// queued on `s` is done (the height cache must be current and ordered before `s`).  force: compute it anyway.
+static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
+{
+    vf_terrain::SunExposure &H = t->se;
+    const uint32_t N = (uint32_t)H.weights.size();
+    if (!N) return fail(VF_ERR_INVALID, "no suns set (vf_terrain_set_sun_exposure)");
+    const size_t nv = (size_t)t->n * t->n;
+    const char *nomem = "sun exposure field allocation failed";
+    if (H.d_sum.reserve(nv, nv) != hipSuccess || H.d_frac.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, nomem); }
+    const float spacing = spacing_of(u), exag = u[38];
+    std::vector<uint32_t> key = key_of({ spacing, exag, H.softness, H.bias, H.incidence ? 1.0f : 0.0f });
+    key.push_back(N);
+    for (float f : H.suns) key.push_back(key_bits(f));
+    for (float f : H.weights) key.push_back(key_bits(f));
+    bool current;
+    if (int rc = H.exposure.prepare(t, key, force, nomem, &current)) return rc;
+    if (current) return VF_OK;
+    // the suns that add something, in the order of their launches: x-major scans, z-major scans, degenerate suns (every vertex lit)
+    std::vector<ExposureSun> part[3];
+    for (uint32_t o = 0; o < N; ++o) {
+        const float *sun = &H.suns[3u * o];
+        if (!(sun[1] > 0.0f) || H.weights[o] == 0.0f) continue;           // not counted, or q = 0 everywhere
+        ExposureSun E = {};
+        const bool scan = sun_plan(t, sun, spacing, exag, 1.0f, H.softness, H.bias, E.S);
+        E.S.n = t->n; E.S.nb = t->nb;
+        E.sx = sun[0]; E.sy = sun[1]; E.sz = sun[2];
+        E.sl = std::sqrt((sun[0] * sun[0] + sun[1] * sun[1]) + sun[2] * sun[2]);
+        E.w = H.weights[o];
+        part[scan ? (E.S.zmajor ? 1 : 0) : 2].push_back(E);
+    }
+    const uint32_t nx = (uint32_t)part[0].size(), scans = nx + (uint32_t)part[1].size(), nflat = (uint32_t)part[2].size();
+    H.recs.clear();
+    for (const std::vector<ExposureSun> &p : part) H.recs.insert(H.recs.end(), p.begin(), p.end());
+    const uint32_t nchunks = (t->n + kShChunk - 1u) / kShChunk;
+    const size_t stride = (size_t)nchunks * (2u * t->n - 1u);
+    const uint32_t B = exposure_batch(t, scans, stride);
+    if ((scans && H.d_cmax.reserve((size_t)B * stride, (size_t)B * stride) != hipSuccess)
+        || (!H.recs.empty() && H.d_suns.reserve(H.recs.size(), H.recs.size()) != hipSuccess)
+        || (H.incidence && H.d_slope.reserve(nv, nv) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(VF_ERR_NOMEM, "sun exposure scan allocation failed");
+    }
+    if (!H.recs.empty())
+        VF_HIP_TRY(hipMemcpyAsync(H.d_suns.p, H.recs.data(), H.recs.size() * sizeof(ExposureSun), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
+    VF_HIP_TRY(hipMemsetAsync(H.d_sum.p, 0, nv * sizeof(uint32_t), s));
+    const dim3 threads(256);
+    const float *hblk = t->d_hblk;
+    const float2 *slope = H.incidence ? H.d_slope.p : nullptr;
+    if (H.incidence && !H.recs.empty())
+        hipLaunchKernelGGL((k_exposure_slopes<0>), dim3((t->n + 31u) / 32u, (t->n + 7u) / 8u), threads, 0, s, hblk, t->n, t->nb, exag, grid_step(t) * spacing, H.d_slope.p);
+    for (uint32_t b0 = 0; b0 < scans; b0 += B) {               // three launches per major axis and batch; the batches share the carries, in stream order
+        const uint32_t b1 = std::min(b0 + B, scans), mid = std::min(std::max(b0, nx), b1);
+        const uint32_t lo[2] = { b0, mid }, hi[2] = { mid, b1 };
+        uint32_t lines[2] = { 0u, 0u };
+        for (int z = 0; z < 2; ++z)
+            for (uint32_t o = lo[z]; o < hi[z]; ++o) lines[z] = std::max(lines[z], H.recs[o].S.nlines);
+        const ExposureSun *suns = H.d_suns.p + b0;
+        for (int z = 0; z < 2; ++z) {
+            if (lo[z] == hi[z]) continue;
+            const dim3 grid(nchunks, (lines[z] + kShLines - 1u) / kShLines, hi[z] - lo[z]);
+            float *cmax = H.d_cmax.p + (size_t)(lo[z] - b0) * stride;
+            if (z) hipLaunchKernelGGL((k_exposure_chunk_max<true>), grid, threads, 0, s, H.d_suns.p + lo[z], hblk, cmax, stride);
+            else hipLaunchKernelGGL((k_exposure_chunk_max<false>), grid, threads, 0, s, H.d_suns.p + lo[z], hblk, cmax, stride);
+        }
+        hipLaunchKernelGGL((k_exposure_carry<0>), dim3((std::max(lines[0], lines[1]) + 255u) / 256u, b1 - b0), threads, 0, s, suns, H.d_cmax.p, stride);
+        for (int z = 0; z < 2; ++z) {
+            if (lo[z] == hi[z]) continue;
+            const dim3 grid(nchunks, (lines[z] + kShLines - 1u) / kShLines, hi[z] - lo[z]);
+            const float *carry = H.d_cmax.p + (size_t)(lo[z] - b0) * stride;
+            const ExposureSun *ps = H.d_suns.p + lo[z];
+            if (z && H.incidence) hipLaunchKernelGGL((k_exposure_lit<true, true>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
+            else if (z) hipLaunchKernelGGL((k_exposure_lit<true, false>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
+            else if (H.incidence) hipLaunchKernelGGL((k_exposure_lit<false, true>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
+            else hipLaunchKernelGGL((k_exposure_lit<false, false>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
+        }
+    }
+    const dim3 flat((uint32_t)((nv + 255u) / 256u));
+    if (nflat && H.incidence) hipLaunchKernelGGL((k_exposure_flat<true>), flat, threads, 0, s, (const ExposureSun *)H.d_suns.p + scans, nflat, slope, (uint32_t)nv, H.d_sum.p);
+    else if (nflat) hipLaunchKernelGGL((k_exposure_flat<false>), flat, threads, 0, s, (const ExposureSun *)H.d_suns.p + scans, nflat, slope, (uint32_t)nv, H.d_sum.p);
+    hipLaunchKernelGGL((k_exposure_finish<0>), flat, threads, 0, s, (const uint32_t *)H.d_sum.p, (uint32_t)nv, H.wtot, H.exposure.d.p, H.d_frac.p);
+    VF_HIP_TRY(hipGetLastError());
+    H.exposure.computed(t, key);
+    H.batch = B;
+    return VF_OK;
+}
+
+// The sun exposure's tint of a frame: the field if it is stale, then k_viewshed_tint on f = min(exposure / wtot, 1)
+static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    if (int rc = exposure_field(t, t->inputs.u, s)) return rc;
+    const vf_terrain::SunExposure &H = t->se;
+    ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
+    T.seen = H.d_frac.p; T.decode = t->ctx->d_decode;
+    T.visible_rgba = H.high_rgba; T.hidden_rgba = H.low_rgba;
+    tint_launch(t, s, P, V, redo, rgba, T);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_sun_exposure(vf_terrain *t, int enable, const float *suns_xyz, const float *weights, uint32_t count, int incidence, float softness,
+                                float bias, const uint8_t high_rgba[4], const uint8_t low_rgba[4])
+{
+    if (!t || !suns_xyz || !high_rgba || !low_rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    vf_terrain::SunExposure &H = t->se;
+    if (count < 1u || count > VF_SUN_EXPOSURE_MAX_SUNS) return fail(VF_ERR_INVALID, "sun exposure takes 1 to 65535 suns");
+    for (size_t k = 0; k < (size_t)3u * count; ++k)
+        if (!std::isfinite(suns_xyz[k])) return fail(VF_ERR_INVALID, "the suns must be finite");
+    for (size_t k = 0; weights && k < count; ++k)
+        if (!(weights[k] >= 0.0f && weights[k] <= 1.0f)) return fail(VF_ERR_INVALID, "the weights must lie in [0, 1]");
+    if (!(std::isfinite(softness) && softness > 0.0f)) return fail(VF_ERR_INVALID, "softness must be a finite number > 0");
+    if (!(std::isfinite(bias) && bias >= 0.0f)) return fail(VF_ERR_INVALID, "bias must be a finite number >= 0");
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "sun exposure needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    const uint32_t hi = pack_rgba8(high_rgba), lo = pack_rgba8(low_rgba);
+    std::vector<float> suns(suns_xyz, suns_xyz + (size_t)3u * count), w(count, 1.0f);
+    if (weights) w.assign(weights, weights + count);
+    // (compared as bits, as the field's key is: -0 is not +0)
+    const bool same = suns.size() == H.suns.size() && !std::memcmp(suns.data(), H.suns.data(), suns.size() * sizeof(float))
+                      && !std::memcmp(w.data(), H.weights.data(), w.size() * sizeof(float));
+    if (H.enabled != (enable != 0) || !same || H.incidence != (incidence != 0) || H.softness != softness || H.bias != bias || H.high_rgba != hi || H.low_rgba != lo)
+        t->inputs_gen++;
+    H.enabled = enable != 0; H.incidence = incidence != 0;
+    H.suns.swap(suns); H.weights.swap(w);
+    H.counted = 0; H.wtot = 0.0f;
+    for (uint32_t o = 0; o < count; ++o)
+        if (H.suns[3u * o + 1u] > 0.0f) { H.counted++; H.wtot += H.weights[o]; }
+    H.softness = softness; H.bias = bias; H.high_rgba = hi; H.low_rgba = lo;
+    return VF_OK;
+}
+
+int vf_terrain_clear_sun_exposure(vf_terrain *t)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (t->se.enabled) t->inputs_gen++;
+    exposure_release(t);
+    return VF_OK;
+}
+
+int vf_terrain_read_sun_exposure_field(vf_terrain *t, float *exposure) { return field_out(t, kFieldExposure, exposure, nullptr, nullptr); }
+int vf_terrain_sun_exposure_field_device(vf_terrain *t, float *dev_exposure, void *stream) { return field_out(t, kFieldExposure, nullptr, dev_exposure, stream); }
+
+int vf_terrain_sun_exposure_info(vf_terrain *t, vf_sun_exposure_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::SunExposure &H = t->se;
+    *out = vf_sun_exposure_info();
+    out->enabled = H.enabled ? 1 : 0; out->incidence = H.incidence ? 1 : 0;
+    out->count = (uint32_t)H.weights.size(); out->counted = H.counted; out->batch = H.batch;
+    out->weight_total = H.wtot; out->softness = H.softness; out->bias = H.bias;
+    for (int k = 0; k < 4; ++k) { out->high_rgba[k] = (uint8_t)(H.high_rgba >> (8 * k)); out->low_rgba[k] = (uint8_t)(H.low_rgba >> (8 * k)); }
+    return VF_OK;
+}
+
+int vf_terrain_debug_sun_exposure_batch(vf_terrain *t, uint32_t batch)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->se.forced_batch != batch) t->se.exposure.valid = false;   // (the next call computes the field again, with this batch size)
+    t->se.forced_batch = batch;
+    return VF_OK;
+}
+
+int vf_terrain_debug_sun_exposure_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldExposure, count); }
+
+int vf_terrain_debug_sun_exposure_stage(vf_terrain *t, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->se.suns.empty()) return fail(VF_ERR_INVALID, "no suns set (vf_terrain_set_sun_exposure)");
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    if (repeats == 0) repeats = 1;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (int rc = ct_heights_current(t)) return rc;
+    hipStream_t s = t->ctx->stream;
+    ScansHeld held;
+    held.hold(t);
+    int rc = VF_OK;
+    float a = 0.0f;
+    const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = exposure_field(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    if (rc != VF_OK) return rc;
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("sun exposure diagnostics: ") + hipGetErrorString(err));
     *ms = a;
     return VF_OK;
 }

@@ -11,6 +11,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
@@ -167,6 +168,15 @@ private:
 };
 
 Vec3 v3(const std::tuple<float, float, float> &t) { return { std::get<0>(t), std::get<1>(t), std::get<2>(t) }; }
+
+// The sun direction of an elevation and an azimuth in degrees (src/lib.rs:441-462): what set_sun stores and set_sun_exposure's angle
+// form hands on, so one sun given by angles has the bits of the handle's own
+Vec3 sun_from_angles(float elevation_deg, float azimuth_deg)
+{
+    const float k = 3.14159265358979323846f / 180.0f;
+    const float el = elevation_deg * k, az = azimuth_deg * k;
+    return normalize_or_zero({ std::cos(el) * std::cos(az), std::sin(el), std::cos(el) * std::sin(az) });
+}
 
 // mat4_to_numpy, src/camera.rs:94-112: (4,4) float32 C-contiguous in mathematical (row, col) indexing
 py::array_t<float> mat4_to_numpy(const Mat4 &m)
@@ -801,14 +811,76 @@ public:
         check(vf_terrain_debug_cumulative_viewshed_scans(t, &count));
         return count;
     }
+    // extension: sun exposure (argument rules: vulkan_forge_amd/_sun_exposure.py)
+    void set_sun_exposure(py::object suns, py::object weights, py::object incidence, py::object enabled, py::object softness, py::object bias,
+                          py::object high_rgba, py::object low_rgba)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._sun_exposure").attr("sun_exposure_args")(suns, weights, incidence, enabled, softness, bias,
+                                                                                                     high_rgba, low_rgba);
+        auto given = a[1].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+        auto w = a[2].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+        const size_t count = (size_t)given.shape(0);
+        std::vector<float> xyz(3u * count);
+        const float *g = given.data();
+        if (given.shape(1) == 2) {                              // angles: the vectors set_sun would store
+            for (size_t o = 0; o < count; ++o) {
+                const Vec3 v = sun_from_angles(g[2u * o], g[2u * o + 1u]);
+                xyz[3u * o] = v.x; xyz[3u * o + 1u] = v.y; xyz[3u * o + 2u] = v.z;
+            }
+        }
+        else std::copy(g, g + 3u * count, xyz.begin());
+        uint8_t high[4], low[4];
+        py::tuple th = a[6].cast<py::tuple>(), tl = a[7].cast<py::tuple>();
+        for (int k = 0; k < 4; ++k) { high[k] = th[k].cast<uint8_t>(); low[k] = tl[k].cast<uint8_t>(); }
+        Borrow b(busy);
+        check(vf_terrain_set_sun_exposure(t, a[0].cast<int>(), xyz.data(), w.data(), (uint32_t)count, a[3].cast<int>(), a[4].cast<float>(),
+                                          a[5].cast<float>(), high, low));
+        frame_current = false;
+    }
+    void clear_sun_exposure()
+    {
+        Borrow b(busy);
+        check(vf_terrain_clear_sun_exposure(t));
+        frame_current = false;
+    }
+    py::array_t<float> sun_exposure_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_sun_exposure_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::object sun_exposure_info()
+    {
+        Borrow b(busy);
+        vf_sun_exposure_info v;
+        check(vf_terrain_sun_exposure_info(t, &v));
+        return py::module_::import("vulkan_forge_amd._sun_exposure").attr("sun_exposure_info")(
+            v.enabled, v.count, v.counted, v.weight_total, v.incidence, v.batch, v.softness, v.bias,
+            py::make_tuple(v.high_rgba[0], v.high_rgba[1], v.high_rgba[2], v.high_rgba[3]),
+            py::make_tuple(v.low_rgba[0], v.low_rgba[1], v.low_rgba[2], v.low_rgba[3]));
+    }
+    void debug_sun_exposure_batch(uint32_t batch)
+    {
+        Borrow b(busy);
+        check(vf_terrain_debug_sun_exposure_batch(t, batch));
+    }
+    uint32_t debug_sun_exposure_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_sun_exposure_scans(t, &count));
+        return count;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
         if (!std::isfinite(elevation_deg) || !std::isfinite(azimuth_deg)) throw py::value_error("angles must be finite");
-        const float k = 3.14159265358979323846f / 180.0f;
-        const float el = elevation_deg * k, az = azimuth_deg * k;
         Borrow b(busy);
-        globals.sun_dir = normalize_or_zero({ std::cos(el) * std::cos(az), std::sin(el), std::cos(el) * std::sin(az) });
+        globals.sun_dir = sun_from_angles(elevation_deg, azimuth_deg);
         push_uniforms();
     }
     void set_exposure(float exposure)
@@ -935,9 +1007,7 @@ public:
     void set_sun(float elevation_deg, float azimuth_deg)                    // src/lib.rs:441-462
     {
         if (!std::isfinite(elevation_deg) || !std::isfinite(azimuth_deg)) throw py::value_error("angles must be finite");
-        const float k = 3.14159265358979323846f / 180.0f;
-        const float el = elevation_deg * k, az = azimuth_deg * k;
-        globals.sun_dir = normalize_or_zero({ std::cos(el) * std::cos(az), std::sin(el), std::cos(el) * std::sin(az) });
+        globals.sun_dir = sun_from_angles(elevation_deg, azimuth_deg);
     }
     void set_exposure(float exposure)                                       // src/lib.rs:464-473
     {
@@ -1203,6 +1273,22 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "softness, bias); vertices is None before observers are set.")
         .def("debug_cumulative_viewshed_batch", &T::debug_cumulative_viewshed_batch, py::arg("batch") = 0)
         .def("debug_cumulative_viewshed_scans", &T::debug_cumulative_viewshed_scans)
+        .def("set_sun_exposure", &T::set_sun_exposure, py::arg("suns"), py::kw_only(), py::arg("weights") = py::none(), py::arg("incidence") = false,
+             py::arg("enabled") = true, py::arg("softness") = VF_SHADOW_SOFTNESS, py::arg("bias") = VF_SHADOW_BIAS,
+             py::arg("high_rgba") = py::make_tuple(255, 208, 64, 160), py::arg("low_rgba") = py::make_tuple(0, 0, 0, 0),
+             "Sun exposure (DESIGN.md 4n): tint the frame by how much direct sun the ground gets from N suns.  suns = (N, 2) angles\n"
+             "(elevation_deg, azimuth_deg) as set_sun takes them, or (N, 3) direction vectors, 1 <= N <= 65535; a sun on or below the\n"
+             "horizon is not counted.  weights = (N,) numbers in [0, 1] (None: all 1).  Each sun's shadow field (strength 1, the call's\n"
+             "softness and bias) times its weight -- with incidence=True also times the cosine between the sun and the surface normal --\n"
+             "is added up; the tint is low_rgba where the sum is 0, high_rgba where it equals the sum of the counted weights, blended in\n"
+             "between.  Every parameter is stored by every call, also one that disables, and steers sun_exposure_field() too.")
+        .def("clear_sun_exposure", &T::clear_sun_exposure, "Forget the suns: sun exposure is off, its parameters are the defaults again, its buffers are freed.")
+        .def("sun_exposure_field", &T::sun_exposure_field,
+             "(grid, grid) float32, row j = z index, column i = x index: the weighted sum of the suns' lit values, in [0, sum of weights].")
+        .def("sun_exposure_info", &T::sun_exposure_info,
+             "dict(enabled, suns (N), counted, weight_total, incidence, batch, softness, bias, high_rgba, low_rgba).")
+        .def("debug_sun_exposure_batch", &T::debug_sun_exposure_batch, py::arg("batch") = 0)
+        .def("debug_sun_exposure_scans", &T::debug_sun_exposure_scans)
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
