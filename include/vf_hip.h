@@ -821,6 +821,45 @@ int vf_terrain_debug_sun_exposure_batch(vf_terrain *t, uint32_t batch);
 int vf_terrain_debug_sun_exposure_scans(vf_terrain *t, uint32_t *count);
 int vf_terrain_debug_sun_exposure_stage(vf_terrain *t, uint32_t repeats, float *ms);
 
+/* ---- supersampled terrain frames: factor x factor samples per pixel, resolved on the GPU ----------
+ * A handle made with factor f in 1..VF_SUPERSAMPLE_MAX draws its terrain -- set-up, plan, tile kernels, the shadow / ambient / drape
+ * passes and the three tints, in their usual order, with the caller's uniforms -- at the SAMPLE SIZE (f width, f height) into a
+ * sample buffer of its own, on an ordered grid of f x f samples per pixel.  One kernel then resolves the samples into the
+ * width x height frame (the caller's output buffer if one is set, vf_terrain_set_output_device), and the overlays composite onto that
+ * frame at width x height: sizes and widths in pixels, the overlays' anti-aliasing and the layer order mean what they mean on any
+ * handle.  The resolve, per output pixel and colour channel, bit for bit: the f f sample bytes decoded to linear light through the
+ * sRGB8 table, added in binary32 rows outer, columns inner, starting from the first sample; the sum multiplied by the binary32
+ * 1.0f / (f f), no fused multiply-add anywhere; encoded as every frame store encodes.  Alpha is the integer mean of the f f alpha
+ * bytes, half up.  Every output pixel is rewritten by every frame.
+ *
+ * vf_terrain_read_rgba, vf_terrain_read_png_scanlines, vf_terrain_rgba_device and vf_terrain_set_output_device deal in
+ * width x height.  vf_terrain_read_visibility, the geometry buffers and their device variants describe the samples: their planes
+ * are (f height, f width).  vf_terrain_pick takes output pixels and answers for the sample (f x + f / 2, f y + f / 2), integer
+ * division.  vf_terrain_local_rows gives the frame's rows, `height`.  factor 1 is vf_terrain_create in every respect: no sample
+ * buffer, no resolve, the same launches.
+ *
+ * VF_ERR_INVALID, with a message that says why and the handle (if any) left as it was: factor outside 1..VF_SUPERSAMPLE_MAX;
+ * f width or f height above 16384; and on a handle with f > 1: vf_terrain_set_shard with more than one rank,
+ * vf_terrain_set_tile_shard, vf_dist_gather_bands, vf_terrain_render_batch / _batch_host, and any occluding overlay layer
+ * (vf_terrain_set_layer_occlusion(..., 1, ...), vf_terrain_add_contours with occlude != 0): the depth test of an occluding layer reads
+ * the frame's visibility and set-up records at the output pixel's centre, and those of a supersampled frame are the samples'.
+ *
+ * vf_terrain_supersampling: the factor and the sample size (any pointer may be NULL).
+ * vf_terrain_read_samples: the samples the last vf_terrain_render drew, before the resolve -- terrain and passes, no overlays --
+ * into host memory, (f height, f width, 4) bytes row-major.  VF_ERR_INVALID before the first render and on a handle with factor 1,
+ * which keeps no samples apart from its frame.
+ * vf_terrain_samples_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream); later calls
+ * on the handle are ordered behind the copy by the library.
+ * vf_terrain_debug_resolve_stage: diagnostics -- the average time (HIP events, ms) of `repeats` launches of the resolve kernel on the
+ * samples of the frame rendered last, into a scratch frame, after one warm-up launch; the handle's frame stays as it was. */
+#define VF_SUPERSAMPLE_MAX 4
+int vf_terrain_create_supersampled(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
+                                   int lut_is_srgb, uint32_t factor, vf_terrain **out);
+int vf_terrain_supersampling(const vf_terrain *t, uint32_t *factor, uint32_t *sample_width, uint32_t *sample_height);
+int vf_terrain_read_samples(vf_terrain *t, uint8_t *dst);
+int vf_terrain_samples_device(vf_terrain *t, void *dev_dst, void *stream);
+int vf_terrain_debug_resolve_stage(vf_terrain *t, uint32_t repeats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

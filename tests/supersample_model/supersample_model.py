@@ -1,0 +1,153 @@
+"""The CPU model of supersampled terrain frames: numpy over the existing models.
+
+    out = ssm.resolve(samples, f)                  # (f H, f W, 4) uint8 -> (H, W, 4) uint8: the contract of the resolve kernel
+    s, vis = ssm.samples(W, H, f, uniforms, height, grid, lut, **features)         # the existing models at (f W, f H), in the library's order
+    out = ssm.frame(W, H, f, uniforms, height, grid, lut, layers=None, **features) # samples -> resolve -> the overlay models at (W, H)
+    p = ssm.representative(plane, f)               # plane[f // 2::f, f // 2::f]: the sample pick() answers for
+
+The resolve, per output pixel and colour channel: the f f sample bytes decoded through the 256-entry sRGB8 -> linear table; added in
+binary32, rows outer, columns inner, starting from the first sample; times the binary32 1 / (f f); encoded over the threshold table
+(byte = the number of thresholds T[1..255] the value reaches).  Alpha: the integer mean of the f f alpha bytes, half up.  The tables are
+the oracle's (oracle.srgb_tables); tests/test_supersample_model.py holds them to the overlay model's decode / encode, which the tint
+models use, over all 256 bytes.
+
+features (all optional, each as the public setters take them):
+    shade_mode   0 / 1
+    shadows      dict(strength, softness, bias)
+    ambient      dict(directions (D, 2), reach, strength)
+    drape        dict(image, extent, opacity, filter, mips=False, bias=0.0)
+    exposure     dict(suns, weights, incidence, softness, bias, high_rgba, low_rgba)
+    cumulative   dict(observers, radius, eye_height, target_height, softness, bias, high_rgba, low_rgba)
+    viewshed     dict(observer, radius, eye_height, target_height, softness, bias, visible_rgba, hidden_rgba)
+"""
+from __future__ import annotations
+
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TESTS = os.path.dirname(HERE)
+sys.path.insert(0, os.path.dirname(TESTS))
+for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "shadow_model", "ambient_model", "drape_model", "drape_mip_model",
+           "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model"):
+    sys.path.insert(0, os.path.join(TESTS, _m))
+
+F32 = np.float32
+FACTORS = (1, 2, 3, 4)
+_tables = None
+
+
+def tables():
+    """(decode (256,) float32, thresholds (256,) float32): the context's tables"""
+    global _tables
+    if _tables is None:
+        import oracle
+        d, t = oracle.srgb_tables()
+        _tables = (np.ascontiguousarray(d, F32), np.ascontiguousarray(t, F32))
+    return _tables
+
+
+def encode(c):
+    """float32 array -> uint8: the number of k in 1..255 with c >= T[k] (what srgb_encode stores)"""
+    c = np.ascontiguousarray(c, F32)
+    return np.searchsorted(tables()[1][1:], c, side="right").astype(np.uint8)
+
+
+def resolve(samples, f, order=None):
+    """(f H, f W, 4) uint8 -> (H, W, 4) uint8.  `order`: another sequence of the (sy, sx) pairs than the contract's, for the test that
+    pins the order."""
+    s = np.ascontiguousarray(samples, np.uint8)
+    f = int(f)
+    assert f in FACTORS and s.ndim == 3 and s.shape[2] == 4 and s.shape[0] % f == 0 and s.shape[1] % f == 0
+    if f == 1:
+        return s.copy()
+    H, W = s.shape[0] // f, s.shape[1] // f
+    b = s.reshape(H, f, W, f, 4)
+    lin = tables()[0][b[..., :3]]                              # (H, f, W, f, 3) float32
+    pairs = [(sy, sx) for sy in range(f) for sx in range(f)] if order is None else list(order)
+    assert sorted(pairs) == [(sy, sx) for sy in range(f) for sx in range(f)]
+    acc = lin[:, pairs[0][0], :, pairs[0][1], :].astype(F32)
+    for sy, sx in pairs[1:]:
+        acc = (acc + lin[:, sy, :, sx, :]).astype(F32)
+    inv = F32(1.0) / F32(f * f)
+    out = np.empty((H, W, 4), np.uint8)
+    out[..., :3] = encode((acc * inv).astype(F32))
+    a = b[..., 3].astype(np.uint32).sum(axis=(1, 3))
+    out[..., 3] = ((a + (f * f) // 2) // (f * f)).astype(np.uint8)
+    return out
+
+
+def representative(plane, f):
+    f = int(f)
+    return np.asarray(plane)[f // 2::f, f // 2::f]
+
+
+def samples(W, H, f, uniforms, height, grid, lut, shade_mode=0, shadows=None, ambient=None, drape=None, exposure=None, cumulative=None,
+            viewshed=None, nthreads=8):
+    """The terrain and its passes at the sample size (f W, f H), composed from the models in the library's order: the oracle's frame ->
+    the ambient / shadow relight -> the draped image (through its mips if asked) -> the sun-exposure, cumulative and viewshed tints.
+    -> (samples (f H, f W, 4) uint8, vis (f H, f W) uint32)"""
+    import oracle
+    import ambient_model as abm
+    import cumulative_viewshed_model as cvm
+    import drape_mip_model as dmm
+    import drape_model as drm
+    import shadow_model as shm
+    import sun_exposure_model as sem
+    import viewshed_model as vsm
+    sw, sh = int(f) * int(W), int(f) * int(H)
+    u = np.ascontiguousarray(uniforms, F32).reshape(44)
+    h = np.ascontiguousarray(height, F32)
+    rgba, vis = oracle.render_terrain(u, sw, sh, grid, h, lut, want_vis=True, nthreads=min(nthreads, oracle.max_threads()), shade_mode=shade_mode)
+    out = rgba.reshape(sh, sw, 4)
+    lit = shm.field(u, h, grid, **shadows) if shadows is not None else None
+    sky, strength = None, 0.0
+    if ambient is not None:
+        strength = ambient["strength"]
+        sky = abm.field(u, h, grid, ambient["directions"], ambient["reach"])
+        out, _ = abm.frame(out, vis, u, h, grid, lut, sky, strength, lit=lit, shade_mode=shade_mode)
+    elif shadows is not None:
+        out, _ = shm.frame(out, vis, u, h, grid, lut, lit, shade_mode=shade_mode)
+    if drape is not None:
+        kw = dict(extent=drape.get("extent"), opacity=drape.get("opacity", 1.0), filter=drape.get("filter", "linear"), lit=lit, sky=sky,
+                  strength=strength, shade_mode=shade_mode)
+        if drape.get("mips"):
+            out, _ = dmm.frame(out, vis, u, h, grid, lut, drape["image"], bias=drape.get("bias", 0.0), **kw)
+        else:
+            out, _ = drm.frame(out, vis, u, h, grid, lut, drape["image"], **kw)
+    if exposure is not None:
+        field = {k: exposure[k] for k in ("incidence", "softness", "bias") if k in exposure}
+        tint = {k: exposure[k] for k in ("high_rgba", "low_rgba") if k in exposure}
+        e = sem.field(u, h, grid, exposure["suns"], exposure.get("weights"), **field)
+        out, _ = sem.frame(out, vis, u, h, grid, e, sem.weight_total(exposure["suns"], exposure.get("weights")), **tint)
+    if cumulative is not None:
+        field = {k: cumulative[k] for k in ("radius", "eye_height", "target_height", "softness", "bias") if k in cumulative}
+        tint = {k: cumulative[k] for k in ("high_rgba", "low_rgba") if k in cumulative}
+        cnt = cvm.field(u, h, grid, cumulative["observers"], **field)
+        cnt = cnt[0] if isinstance(cnt, tuple) else cnt
+        out, _ = cvm.frame(out, vis, u, h, grid, cnt, len(cumulative["observers"]), **tint)
+    if viewshed is not None:
+        field = {k: viewshed[k] for k in ("eye_height", "target_height", "softness", "bias") if k in viewshed}
+        tint = {k: viewshed[k] for k in ("radius", "visible_rgba", "hidden_rgba") if k in viewshed}
+        seen, v = vsm.field(u, h, grid, viewshed["observer"], **field)
+        out, _ = vsm.frame(out, vis, u, h, grid, seen, v, **tint)
+    return np.ascontiguousarray(out, np.uint8), vis
+
+
+def composite(frame, uniforms, height, grid, layers):
+    """the overlay / polygon / contour models at the output size, over the resolved frame (no layer occludes: the visibility is not read)"""
+    if layers is None:
+        return frame
+    import occlusion_model as ocm
+    H, W = frame.shape[:2]
+    return ocm.composite(frame, np.zeros((H, W), np.uint32), uniforms, height, grid, layers)
+
+
+def frame(W, H, f, uniforms, height, grid, lut, layers=None, **features):
+    """-> dict(samples, vis, resolved, frame): the samples and their visibility at (f H, f W), the resolved frame and the frame under
+    its overlays at (H, W)"""
+    s, vis = samples(W, H, f, uniforms, height, grid, lut, **features)
+    resolved = resolve(s, f)
+    return dict(samples=s, vis=vis, resolved=resolved, frame=composite(resolved, uniforms, height, grid, layers))

@@ -15,6 +15,7 @@ DEFAULT_LIB = os.environ.get("VF_HIP_LIB") or os.path.join(_HERE, "libvf_hip.so"
 VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -3, -4
 VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
 VF_DRAPE_MIP_BIAS_MAX, VF_DRAPE_MIP_LEVELS_MAX = 16.0, 15                                # its mip pyramid
+VF_SUPERSAMPLE_MAX = 4                                                                   # supersampled terrain frames
 VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED_AHEAD = 1, 2, 4, 8, 16   # vf_terrain_debug_plan_mode
 VF_PLAN_TILE_LISTS = 64        # ... and for "the tile kernel read the plan state's per-tile candidate lists" (DESIGN.md 3): Terrain.tile_lists()
 VF_PLAN_GEOMETRY_REUSED = 32   # ... its bit for "the block boxes and set-up records were not rebuilt" (DESIGN.md 3): Terrain.geometry_reused()
@@ -46,6 +47,8 @@ SYMBOLS = [
     "vf_terrain_set_sun_exposure", "vf_terrain_clear_sun_exposure", "vf_terrain_read_sun_exposure_field", "vf_terrain_sun_exposure_field_device",
     "vf_terrain_sun_exposure_info", "vf_terrain_debug_sun_exposure_batch", "vf_terrain_debug_sun_exposure_scans",
     "vf_terrain_debug_sun_exposure_stage",
+    "vf_terrain_create_supersampled", "vf_terrain_supersampling", "vf_terrain_read_samples", "vf_terrain_samples_device",
+    "vf_terrain_debug_resolve_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -198,6 +201,11 @@ _PROTOS = {
     "vf_terrain_debug_sun_exposure_batch": (_i, [_vp, _u32]),
     "vf_terrain_debug_sun_exposure_scans": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_debug_sun_exposure_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_create_supersampled": (_i, [_vp, _u32, _u32, _u32, _vp, _i, _u32, C.POINTER(_vp)]),
+    "vf_terrain_supersampling": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "vf_terrain_read_samples": (_i, [_vp, _vp]),
+    "vf_terrain_samples_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_debug_resolve_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -260,11 +268,15 @@ def register_stripe_map(stripe_owner, stripe_log2, nranks, lib=None):
 class Terrain:
     """Thin RAII wrapper over vf_ctx + vf_terrain for callers that pass raw device pointers / streams."""
 
-    def __init__(self, width, height, grid, lut_rgba8, lut_is_srgb=True, device=0, lib=None, share_ctx=None):
+    def __init__(self, width, height, grid, lut_rgba8, lut_is_srgb=True, device=0, lib=None, share_ctx=None, supersample=None):
         """`share_ctx`: another Terrain whose context (vf_ctx: device, stream, the side streams handles borrow) this one uses too -- what the
-        drop-in module does for every object of a process (one context per process and device); the other Terrain must outlive this one."""
+        drop-in module does for every object of a process (one context per process and device); the other Terrain must outlive this one.
+        `supersample`: None -- vf_terrain_create; a factor -- vf_terrain_create_supersampled, handed to the library as it
+        is (its refusals raise VfError).  W, H stay the frame's size; SW, SH are the sample size, which visibility and geometry buffers have."""
         self.lib = lib or load()
         self.W, self.H, self.grid = int(width), int(height), int(grid)
+        self.ss = 1 if supersample is None else int(supersample)
+        self.SW, self.SH = self.ss * self.W, self.ss * self.H
         self.ctx, self.t = _vp(), _vp()
         self._own_ctx = share_ctx is None
         if share_ctx is None:
@@ -272,8 +284,12 @@ class Terrain:
         else:
             self.ctx = share_ctx.ctx
         lut = np.ascontiguousarray(lut_rgba8, dtype=np.uint8).reshape(1024)
-        self._check(self.lib.vf_terrain_create(self.ctx, self.W, self.H, self.grid, lut.ctypes.data, int(bool(lut_is_srgb)),
-                                               C.byref(self.t)))
+        if supersample is None:
+            self._check(self.lib.vf_terrain_create(self.ctx, self.W, self.H, self.grid, lut.ctypes.data, int(bool(lut_is_srgb)),
+                                                   C.byref(self.t)))
+        else:
+            self._check(self.lib.vf_terrain_create_supersampled(self.ctx, self.W, self.H, self.grid, lut.ctypes.data, int(bool(lut_is_srgb)),
+                                                                self.ss, C.byref(self.t)))
 
     def _check(self, rc):
         if rc != VF_OK:
@@ -523,15 +539,38 @@ class Terrain:
         return np.frombuffer(buf, np.uint8).reshape(self.H, self.W * 4 + 1).copy()
 
     def read_visibility(self):
-        out = np.empty((self.local_rows(), self.W), np.uint32)
+        out = np.empty((self.SH if self.ss > 1 else self.local_rows(), self.SW), np.uint32)      # (a supersampled handle: the samples' ids)
         self._check(self.lib.vf_terrain_read_visibility(self.t, out.ctypes.data))
         return out
+
+    # ---- supersampling (include/vf_hip.h) ----
+    def supersampling(self):
+        """(factor, sample width, sample height) as the library holds them."""
+        f, w, h = _u32(), _u32(), _u32()
+        self._check(self.lib.vf_terrain_supersampling(self.t, C.byref(f), C.byref(w), C.byref(h)))
+        return f.value, w.value, h.value
+
+    def read_samples(self):
+        """The samples of the frame rendered last, before the resolve: (f H, f W, 4) uint8, terrain and passes, no overlays."""
+        out = np.empty((self.SH, self.SW, 4), np.uint8)
+        self._check(self.lib.vf_terrain_read_samples(self.t, out.ctypes.data))
+        return out
+
+    def samples_device(self, dev_dst, stream=None):
+        """The same into device memory (a torch tensor's data_ptr(), f H x f W x 4 bytes); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_samples_device(self.t, dev_dst, stream))
+
+    def resolve_stage(self, repeats=50):
+        """The resolve kernel as timed launches of its own (diagnostics): average ms of `repeats` launches."""
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_resolve_stage(self.t, int(repeats), C.byref(ms)))
+        return ms.value
 
     def read_gbuffer(self, planes=("depth", "position", "normal", "primitive")):
         """Geometry buffers of the frame rendered last: dict plane name -> array."""
         from ._gbuffer import PLANES, plane_args
         names = plane_args(planes)
-        out = {k: np.empty((self.H, self.W) + PLANES[k][1], PLANES[k][0]) for k in names}
+        out = {k: np.empty((self.SH, self.SW) + PLANES[k][1], PLANES[k][0]) for k in names}
         ptr = [out[k].ctypes.data if k in out else None for k in PLANES]
         self._check(self.lib.vf_terrain_read_gbuffer(self.t, *ptr))
         return out

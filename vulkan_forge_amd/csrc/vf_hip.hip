@@ -11,6 +11,7 @@
 #include "vf_viewshed.h"    // templates only
 #include "vf_cumulative_viewshed.h"   // templates only
 #include "vf_sun_exposure.h"          // templates only
+#include "vf_resolve.h"               // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -373,7 +374,12 @@ struct LineLoop {
 
 struct vf_terrain {
     vf_ctx *ctx = nullptr;
-    uint32_t W = 0, H = 0, n = 0;
+    uint32_t W = 0, H = 0, n = 0;        // W, H: the RASTER size -- what the terrain is drawn at, and with it the visibility, the tiles, the plan and every pass over them
+    // Supersampling.  ss = 1: the raster is the frame, oW = W, oH = H, no sample buffer, nothing below is launched.
+    // ss > 1: W = ss oW, H = ss oH; the terrain passes draw into d_samples, k_ss_resolve makes the oW x oH frame in d_rgba from it and the
+    // overlays composite onto that.  d_rgba, its read-backs and the overlay pass deal in oW x oH, everything else in W x H.
+    uint32_t ss = 1, oW = 0, oH = 0;
+    uint32_t *d_samples = nullptr;       // ss > 1 only (in the slab): whole tiles of the raster
     uint32_t nb = 0, nblocks = 0;        // 8x8-cell blocks per side / in total
     uint32_t ntx = 0, nty = 0;           // 64x64 screen tiles
     // shard
@@ -957,9 +963,22 @@ static void exposure_release(vf_terrain *t)
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
+    return vf_terrain_create_supersampled(ctx, width, height, grid, lut_rgba8, lut_is_srgb, 1u, out);
+}
+
+// (width, height: the frame handed out; the handle's W, H are the raster's, `factor` times as large)
+int vf_terrain_create_supersampled(vf_ctx *ctx, uint32_t out_width, uint32_t out_height, uint32_t grid, const uint8_t lut_rgba8[1024],
+                                   int lut_is_srgb, uint32_t factor, vf_terrain **out)
+{
     if (!ctx || !out || !lut_rgba8) return fail(VF_ERR_INVALID, "NULL argument");
     *out = nullptr;
-    if (width == 0 || height == 0 || width > 16384 || height > 16384) return fail(VF_ERR_INVALID, "width/height must be in 1..16384");
+    if (out_width == 0 || out_height == 0 || out_width > 16384 || out_height > 16384) return fail(VF_ERR_INVALID, "width/height must be in 1..16384");
+    if (factor < 1u || factor > (uint32_t)VF_SUPERSAMPLE_MAX)
+        return fail(VF_ERR_INVALID, "supersampling factor " + std::to_string(factor) + " is outside 1.." + std::to_string(VF_SUPERSAMPLE_MAX));
+    if (factor * out_width > 16384u || factor * out_height > 16384u)
+        return fail(VF_ERR_INVALID, "supersampling: " + std::to_string(factor) + " x (" + std::to_string(out_width) + " x " + std::to_string(out_height) +
+                                    ") samples exceed the 16384 x 16384 frame limit");
+    const uint32_t width = factor * out_width, height = factor * out_height;
     uint32_t n = grid < 2 ? 2 : grid;   // `.max(2)`, src/terrain/mod.rs:260
     if (n > 8192) return fail(VF_ERR_INVALID, "grid must be <= 8192");
     VF_HIP_TRY(hipSetDevice(ctx->device));
@@ -967,6 +986,7 @@ int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t gri
     if (t) { const char *e = std::getenv("VF_NO_TILE_LISTS"); t->tl_off = e && *e && std::strcmp(e, "0") != 0; }
     if (!t) return fail(VF_ERR_NOMEM, "out of host memory");
     t->ctx = ctx; t->W = width; t->H = height; t->n = n;
+    t->ss = factor; t->oW = out_width; t->oH = out_height;
     t->nb = (n - 1 + kBlockCells - 1) / kBlockCells;
     t->nblocks = t->nb * t->nb;
     t->ntx = (width + kTileW - 1) / kTileW;
@@ -997,7 +1017,11 @@ int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t gri
     C.add((void **)&t->d_bounds, t->nblocks * sizeof(float2));
     C.add((void **)&t->d_hblk, (size_t)t->nblocks * kBlockStride * sizeof(float));
     C.add((void **)&t->d_lut, sizeof lut);
-    C.add((void **)&t->d_rgba_own, all_tiles * kTileW * kTileH * sizeof(uint32_t));   // whole tiles: tile-major shards need the padding
+    if (factor == 1u) C.add((void **)&t->d_rgba_own, all_tiles * kTileW * kTileH * sizeof(uint32_t));   // whole tiles: tile-major shards need the padding
+    else {                                                        // (the samples take the frame's place under the terrain passes)
+        C.add((void **)&t->d_samples, all_tiles * kTileW * kTileH * sizeof(uint32_t));
+        C.add((void **)&t->d_rgba_own, (size_t)out_width * out_height * sizeof(uint32_t));
+    }
     C.add((void **)&t->d_tile_map, all_tiles * sizeof(uint32_t));
     C.add((void **)&t->d_stripe_owner, kMaxStripes);
     err = C.commit(&t->slab, ctx->stream);
@@ -1208,6 +1232,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->vs.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
     if (t->cv.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     if (t->se.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
+    if (t->ss > 1u && nranks != 1) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1334,6 +1359,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->am.enabled) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
     if (t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
+    if (t->ss > 1u) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
@@ -1378,7 +1404,7 @@ int vf_terrain_read_tiles(vf_terrain *t, uint8_t *dst, uint32_t first, uint32_t 
 int vf_terrain_local_rows(const vf_terrain *t, uint32_t *rows)
 {
     if (!t || !rows) return fail(VF_ERR_INVALID, "NULL argument");
-    *rows = t->local_rows;
+    *rows = t->ss > 1u ? t->oH : t->local_rows;             // rows of the frame handed out (a supersampled handle is a whole-frame handle)
     return VF_OK;
 }
 
@@ -1719,7 +1745,7 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
 static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V)
 {
     vf_terrain::Overlays &O = t->ov;
-    const uint32_t nbx = (t->W + kOvBin - 1u) / kOvBin, nby = (t->H + kOvBin - 1u) / kOvBin, nbins = nbx * nby;
+    const uint32_t nbx = (t->oW + kOvBin - 1u) / kOvBin, nby = (t->oH + kOvBin - 1u) / kOvBin, nbins = nbx * nby;   // (P is the output size's: output_params)
     const dim3 per_prim((O.nprims + 255u) / 256u), threads(256);
     const bool occlude = O.occluding != 0u;
     hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.in.p, O.prim.p, O.box.p, O.d_cnt, nbx,
@@ -1750,17 +1776,17 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("polygon mask allocation failed: ") + hipGetErrorString(e));
     if (words) {                                            // the backdrop: row crossings right of each bin, per fill feature
         VF_HIP_TRY(hipMemsetAsync(O.mask.p, 0, (size_t)words * sizeof(uint32_t), s));
-        hipLaunchKernelGGL(k_pg_backdrop, per_slot, threads, 0, s, t->H, O.pg_lo, O.pg_hi, O.in.p, O.prim.p, O.pg_fbin.p, O.mask.p);
+        hipLaunchKernelGGL(k_pg_backdrop, per_slot, threads, 0, s, t->oH, O.pg_lo, O.pg_hi, O.in.p, O.prim.p, O.pg_fbin.p, O.mask.p);
         hipLaunchKernelGGL(k_pg_prefix, dim3((O.nfill + 3u) / 4u), threads, 0, s, O.nfill, O.pg_fbin.p, O.mask.p);
     }
     e = O.list.reserve(total, (size_t)total + total / 2u + 4096u);
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay pair list allocation failed: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.box.p, nbx, O.d_start, O.d_cnt, O.list.p);
     if (occlude)
-        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
+        hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->oW, t->oH, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
                            t->ctx->d_thresh, O.mask.p, t->d_rgba, P, V, t->d_vis, O.dep.p);
     else
-        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->W, t->H, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
+        hipLaunchKernelGGL(k_ov_composite, dim3(nbins), threads, 0, s, t->oW, t->oH, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
                            t->ctx->d_thresh, O.mask.p, t->d_rgba);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
@@ -1774,6 +1800,21 @@ static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+
+// The resolve of a supersampled handle's samples into its frame (vf_resolve.h).  Defined with the other supersampling calls below: the template is
+// instantiated there, behind the tile kernels and what they call, whose code -- PC-relative call offsets included -- keeps its place
+static void resolve_launch(const vf_terrain *t, hipStream_t s, uint32_t *dst);
+
+// The FrameParams of the overlay pass of a supersampled handle: the caller's camera on a frame of the output size (sizes and widths in
+// pixels mean output pixels).  The overlay kernels read the camera, the grid and hw, hh, W, H of it; the tile and shard fields follow.
+static FrameParams output_params(const vf_terrain *t, const FrameParams &P)
+{
+    FrameParams Q = P;
+    Q.hw = 0.5f * (float)t->oW; Q.hh = 0.5f * (float)t->oH;
+    Q.W = t->oW; Q.H = t->oH; Q.ntx = (t->oW + kTileW - 1) / kTileW; Q.nty = (t->oH + kTileH - 1) / kTileH;
+    Q.local_rows = t->oH;
+    return Q;
+}
 
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
@@ -1792,6 +1833,9 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     vf_terrain::FrameEvents &ev = t->ev[t->timed_frames % (uint32_t)vf_terrain::kTimingRing];
     const bool timing_now = t->timing && K.sampled;
     const SetupView V = { S.vtx, t->d_hblk, S.recs, S.gen };
+    // what the terrain passes draw into: the samples of a supersampled handle, else the frame itself (as a diagnostics frame's scratch buffer is)
+    const bool resolve = t->ss > 1u && !diag;
+    uint32_t *const raster = resolve ? t->d_samples : t->d_rgba;
     // ---- draw, on the caller's stream: everything that touches the output buffers ----
     uint32_t *stats = t->timing && t->stats_on ? t->d_stats : nullptr;
     const uint32_t nstats = (uint32_t)stats_layout(t).words;     // zeroed by k_clear (no memset dispatch)
@@ -1816,14 +1860,14 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     LineLoop::Probe *gp = pick.probe ? t->loop.arm(s) : nullptr;
     if (ntiles) {
         uint32_t *vis = write_vis ? t->d_vis : nullptr;
-        hipLaunchKernelGGL(k_clear, dim3(ntiles), dim3(256), 0, s, P, S.background, t->d_rgba, vis, stats, nstats, seg_count);
+        hipLaunchKernelGGL(k_clear, dim3(ntiles), dim3(256), 0, s, P, S.background, raster, vis, stats, nstats, seg_count);
         // one persistent workgroup per CU (a 1024-thread workgroup with 70 KB of LDS fills one), the fast variant, works through
         // the items; then a handful of persistent workgroups of the complete variant take the items that met a clipped or
         // oversized primitive (normally none)
         const dim3 per_cu(std::min<uint32_t>((uint32_t)std::max(1, t->ctx->prop.multiProcessorCount) * (1024u / (uint32_t)kTileThreads), ntiles + kSplitBudget)),
                    few(std::min<uint32_t>(64u, ntiles + kSplitBudget)), threads(kTileThreads);
 #define VF_TILE_ARGS P, V, S.row_ranges, S.cap_seg, S.cap_rad, t->d_lut, t->ctx->d_thresh, S.work_sorted, S.work_count, \
-                     rc_lo, rc_hi, t->d_rgba, vis, stats, S.feedback, S.redo, S.band, TL
+                     rc_lo, rc_hi, raster, vis, stats, S.feedback, S.redo, S.band, TL
         const bool fast = fast_shading(t->inputs);
         // (the complete variant redraws the rare items that met a clipped primitive: always the plain loop)
 #define VF_TILE_LAUNCH(WV, FS)                                                                                         \
@@ -1843,27 +1887,31 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev.end, s)); t->timed_frames++; }
     if ((shadows || ambient) && ntiles) {                  // cast shadows and ambient occlusion: behind the tile kernels, in front of the overlays
-        const int src = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, ambient ? kAmbient : kShadow, shadows, ambient);
+        const int src = relight_pass(t, s, P, V, S.work_count + 3, raster, ambient ? kAmbient : kShadow, shadows, ambient);
         if (src != VF_OK) return src;
     }
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
-        const int drc = relight_pass(t, s, P, V, S.work_count + 3, t->d_rgba, drape_pass, shadows, ambient);
+        const int drc = relight_pass(t, s, P, V, S.work_count + 3, raster, drape_pass, shadows, ambient);
         if (drc != VF_OK) return drc;
     }
     if (exposure && ntiles) {                              // the sun exposure's tint: behind both viewshed tints
-        const int erc = exposure_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        const int erc = exposure_pass(t, s, P, V, S.work_count + 3, raster);
         if (erc != VF_OK) return erc;
     }
     if (cumulative && ntiles) {                            // the cumulative viewshed's tint: behind the single observer's
-        const int crc = cumulative_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        const int crc = cumulative_pass(t, s, P, V, S.work_count + 3, raster);
         if (crc != VF_OK) return crc;
     }
     if (viewshed && ntiles) {                              // the viewshed tint: behind the relight passes, in front of the overlays
-        const int vrc = viewshed_pass(t, s, P, V, S.work_count + 3, t->d_rgba);
+        const int vrc = viewshed_pass(t, s, P, V, S.work_count + 3, raster);
         if (vrc != VF_OK) return vrc;
     }
+    if (resolve) {                                         // the samples -> the frame: every output pixel is rewritten, whatever the tiles drew
+        resolve_launch(t, s, t->d_rgba);
+        VF_HIP_TRY(hipGetLastError());
+    }
     if (t->ov.nprims && !diag) {                           // (visibility / diagnostics frames: none)
-        const int orc = overlay_pass(t, s, P, V);
+        const int orc = resolve ? overlay_pass(t, s, output_params(t, P), V) : overlay_pass(t, s, P, V);
         if (orc != VF_OK) return orc;
     }
     VF_HIP_TRY(hipEventRecord(S.drawn, s));
@@ -1994,6 +2042,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
+    if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -2016,6 +2065,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
+    if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -2136,15 +2186,18 @@ static int ov_budget(uint64_t have, uint64_t more)
 // is brought about here).  The first layer makes the overlay state.  Nothing is committed before every allocation and the producer
 // have succeeded: a failure leaves the layers as they were.
 using OvProducer = std::function<int(OvIn *dst)>;
+// (the set-up records and the visibility of a supersampled frame are the samples'; the composite's depth test reads them at the pixel centre)
+static const char *const kSsNoOcclusion = "the handle is supersampled: occluding overlay layers are not supported (their depth test reads the frame's visibility per output pixel)";
 static int ov_append(vf_terrain *t, size_t nadd, const OvProducer &produce, const std::vector<uint32_t> &hdr, uint32_t nfillrec, bool polygon,
                      uint32_t features, uint32_t *layer_id, bool occlude = false)
 {
     vf_terrain::Overlays &O = t->ov;
     if (int rc = ov_budget(O.nprims, nadd)) return rc;
+    if (occlude && t->ss > 1u) return fail(VF_ERR_INVALID, kSsNoOcclusion);
     VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the arrays)
     if (occlude) { if (int rc = ensure_vis(t)) return rc; }
     if (!O.d_cnt) {
-        const uint32_t nbins = ((t->W + kOvBin - 1u) / kOvBin) * ((t->H + kOvBin - 1u) / kOvBin);
+        const uint32_t nbins = ((t->oW + kOvBin - 1u) / kOvBin) * ((t->oH + kOvBin - 1u) / kOvBin);
         hipError_t e = hipMalloc(&O.d_cnt, (size_t)nbins * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(O.d_cnt, 0, (size_t)nbins * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(&O.d_start, ((size_t)nbins + 1u) * sizeof(uint32_t));
@@ -2345,6 +2398,7 @@ int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude
     if (layer_id >= O.layer.size()) return fail(VF_ERR_INVALID, "no overlay layer with that id");
     vf_terrain::Overlays::Layer &L = O.layer[layer_id];
     if (L.polygon) return fail(VF_ERR_INVALID, "a polygon layer cannot occlude: polygon fills have no depth");
+    if (occlude && t->ss > 1u) return fail(VF_ERR_INVALID, kSsNoOcclusion);
     VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the records)
     if (occlude) {
         if (int rc = ensure_vis(t)) return rc;
@@ -2551,10 +2605,10 @@ int vf_terrain_read_rgba(vf_terrain *t, uint8_t *dst, uint32_t y0, uint32_t rows
     if (!t || !dst) return fail(VF_ERR_INVALID, "NULL argument");
     if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
     if (t->shard_tiles) return fail(VF_ERR_INVALID, "tile-sharded handle: read with vf_terrain_read_tiles");
-    if ((uint64_t)y0 + rows > t->local_rows) return fail(VF_ERR_INVALID, "row range outside the local rows");
+    if ((uint64_t)y0 + rows > (t->ss > 1u ? t->oH : t->local_rows)) return fail(VF_ERR_INVALID, "row range outside the local rows");   // (supersampled: a whole-frame handle)
     int rc = vf_terrain_sync(t);
     if (rc != VF_OK) return rc;
-    return copy_to_host_staged(t, dst, (const uint8_t *)(t->d_rgba + (size_t)y0 * t->W), (size_t)rows * t->W * 4,
+    return copy_to_host_staged(t, dst, (const uint8_t *)(t->d_rgba + (size_t)y0 * t->oW), (size_t)rows * t->oW * 4,
                                t->last_stream ? t->last_stream : t->ctx->stream);
 }
 
@@ -2574,10 +2628,10 @@ int vf_terrain_read_png_scanlines(vf_terrain *t, const uint8_t **host_scanlines,
     if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
     if (t->shard_tiles || t->local_rows != t->H) return fail(VF_ERR_INVALID, "PNG read-back needs the whole frame on one handle");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    const size_t n = ((size_t)t->W * 4 + 1) * t->H;
+    const size_t n = ((size_t)t->oW * 4 + 1) * t->oH;
     if (!t->d_png) VF_HIP_TRY(hipMalloc(&t->d_png, n));
     hipStream_t s = t->last_stream ? t->last_stream : t->ctx->stream;
-    hipLaunchKernelGGL(k_png_filter, dim3(t->H), dim3(256), 0, s, (const uint32_t *)t->d_rgba, t->W, t->d_png);
+    hipLaunchKernelGGL(k_png_filter, dim3(t->oH), dim3(256), 0, s, (const uint32_t *)t->d_rgba, t->oW, t->d_png);
     VF_HIP_TRY(hipGetLastError());
     // the scanlines land in a page-locked buffer of the handle (pinned_alloc: 2.6 ms to make for a C4 frame, then one DMA per frame):
     // persistent, where the reference allocates per call (:446-451)
@@ -2766,9 +2820,16 @@ int vf_terrain_pick(vf_terrain *t, const int32_t *pixels_xy, uint32_t n, float *
 {
     if (!t || (n && (!pixels_xy || !out8))) return fail(VF_ERR_INVALID, "NULL argument");
     for (uint32_t k = 0; k < n; ++k)
-        if (pixels_xy[2 * k] < 0 || pixels_xy[2 * k + 1] < 0 || (uint32_t)pixels_xy[2 * k] >= t->W || (uint32_t)pixels_xy[2 * k + 1] >= t->H)
+        if (pixels_xy[2 * k] < 0 || pixels_xy[2 * k + 1] < 0 || (uint32_t)pixels_xy[2 * k] >= t->oW || (uint32_t)pixels_xy[2 * k + 1] >= t->oH)
             return fail(VF_ERR_INVALID, "pixel " + std::to_string(k) + " (" + std::to_string(pixels_xy[2 * k]) + ", " + std::to_string(pixels_xy[2 * k + 1]) +
-                                        ") lies outside the " + std::to_string(t->W) + " x " + std::to_string(t->H) + " frame");
+                                        ") lies outside the " + std::to_string(t->oW) + " x " + std::to_string(t->oH) + " frame");
+    // a supersampled handle answers for the pixel's representative sample (ss x + ss / 2, ss y + ss / 2): the kernel sees sample coordinates
+    std::vector<int32_t> mapped;
+    if (t->ss > 1u && n) {
+        mapped.resize(2u * (size_t)n);
+        for (size_t k = 0; k < 2u * (size_t)n; ++k) mapped[k] = (int32_t)(t->ss * (uint32_t)pixels_xy[k] + t->ss / 2u);
+        pixels_xy = mapped.data();
+    }
     GbFrame F;
     int rc = gb_frame(t, F);
     if (rc != VF_OK || n == 0) return rc;
@@ -2802,6 +2863,76 @@ int vf_terrain_debug_gbuffer_stage(vf_terrain *t, uint32_t planes, uint32_t repe
     float mean = 0.0f;
     const hipError_t err = time_launches(s, repeats, mean, [&](bool) { gb_launch(t, F, L.dev, s); return hipGetLastError(); });
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("geometry-buffer diagnostics: ") + hipGetErrorString(err));
+    *ms = mean;
+    return VF_OK;
+}
+
+// ---- supersampling (vf_resolve.h) --------------------------------------------------------
+
+// the resolve launch (declared in front of draw_frame; see there for why it stands here): persistent, a few workgroups per CU
+static void resolve_launch(const vf_terrain *t, hipStream_t s, uint32_t *dst)
+{
+    const uint32_t px = t->ss == 2u ? (uint32_t)SsShape<2>::PX : (t->ss == 3u ? (uint32_t)SsShape<3>::PX : (uint32_t)SsShape<4>::PX);
+    const uint32_t lanes = ((t->oW + px - 1u) / px) * t->oH;
+    const dim3 grid(std::min<uint32_t>((lanes + 255u) / 256u, (uint32_t)std::max(1, t->ctx->prop.multiProcessorCount) * 8u)), threads(256);
+    const float *dec = t->ctx->d_decode, *thr = t->ctx->d_thresh;
+    if (t->ss == 2u) hipLaunchKernelGGL((k_ss_resolve<2>), grid, threads, 0, s, (const uint32_t *)t->d_samples, t->oW, t->oH, dec, thr, dst);
+    else if (t->ss == 3u) hipLaunchKernelGGL((k_ss_resolve<3>), grid, threads, 0, s, (const uint32_t *)t->d_samples, t->oW, t->oH, dec, thr, dst);
+    else hipLaunchKernelGGL((k_ss_resolve<4>), grid, threads, 0, s, (const uint32_t *)t->d_samples, t->oW, t->oH, dec, thr, dst);
+}
+
+int vf_terrain_supersampling(const vf_terrain *t, uint32_t *factor, uint32_t *sample_width, uint32_t *sample_height)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (factor) *factor = t->ss;
+    if (sample_width) *sample_width = t->W;
+    if (sample_height) *sample_height = t->H;
+    return VF_OK;
+}
+
+// the samples of the frame rendered last: what the resolve read (a frame in flight is waited for / ordered in front)
+static int samples_ready(const vf_terrain *t)
+{
+    if (t->ss <= 1u) return fail(VF_ERR_INVALID, "the handle is not supersampled: it keeps no samples apart from its frame (vf_terrain_create_supersampled)");
+    if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
+    return VF_OK;
+}
+
+int vf_terrain_read_samples(vf_terrain *t, uint8_t *dst)
+{
+    if (!t || !dst) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = samples_ready(t)) return rc;
+    int rc = vf_terrain_sync(t);
+    if (rc != VF_OK) return rc;
+    return copy_to_host_staged(t, dst, (const uint8_t *)t->d_samples, (size_t)t->W * t->H * 4, t->last_stream ? t->last_stream : t->ctx->stream);
+}
+
+int vf_terrain_samples_device(vf_terrain *t, void *dev_dst, void *stream)
+{
+    if (!t || !dev_dst) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = samples_ready(t)) return rc;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    if (t->last_stream && t->last_stream != s) VF_HIP_TRY(hipStreamWaitEvent(s, t->ps[t->last_set].drawn, 0));
+    VF_HIP_TRY(hipMemcpyAsync(dev_dst, t->d_samples, (size_t)t->W * t->H * 4, hipMemcpyDeviceToDevice, s));
+    VF_HIP_TRY(gb_order_after(t, s));                       // (the next frame overwrites the samples: it waits for this copy)
+    return VF_OK;
+}
+
+int vf_terrain_debug_resolve_stage(vf_terrain *t, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = samples_ready(t)) return rc;
+    if (repeats == 0) repeats = 1;
+    int rc = vf_terrain_sync(t);
+    if (rc != VF_OK) return rc;
+    uint32_t *d_out = nullptr;                              // (not the frame: it may hold overlays)
+    if (hipMalloc(&d_out, (size_t)t->oW * t->oH * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "resolve diagnostics allocation failed"); }
+    hipStream_t s = t->ctx->stream;
+    float mean = 0.0f;
+    const hipError_t err = time_launches(s, repeats, mean, [&](bool) { resolve_launch(t, s, d_out); return hipGetLastError(); });
+    (void)hipFree(d_out);
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("resolve diagnostics: ") + hipGetErrorString(err));
     *ms = mean;
     return VF_OK;
 }
@@ -4720,6 +4851,7 @@ int vf_dist_gather_bands(vf_terrain *t, void *rccl_comm, int root, void *dev_ima
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     if (t->shard_tiles) return fail(VF_ERR_INVALID, "handle is tile-sharded: gather with vf_dist_gather_tiles");
+    if (t->ss > 1u) return fail(VF_ERR_INVALID, "the handle is supersampled: it is a whole-frame handle, there are no bands to gather");
     if (!t->rendered) return fail(VF_ERR_INVALID, "nothing rendered yet");
     const Rccl &R = resolve_rccl();
     int rc = check_comm(R, t, rccl_comm, root);

@@ -192,8 +192,11 @@ py::array_t<float> mat4_to_numpy(const Mat4 &m)
 class TerrainObject {
 public:
     // kind 0: TerrainSpike::new (src/terrain/mod.rs:259-407); kind 1: Scene::new (src/scene/mod.rs:60-206)
-    TerrainObject(int kind, uint32_t width, uint32_t height, py::object grid, py::object colormap) : W(width), H(height)
+    // supersample: f x f samples per pixel, resolved on the GPU (argument rules: vulkan_forge_amd/_supersample.py)
+    TerrainObject(int kind, uint32_t width, uint32_t height, py::object grid, py::object colormap, py::object supersample) : W(width), H(height)
     {
+        ss = py::module_::import("vulkan_forge_amd._supersample").attr("supersample_args")(width, height, supersample).cast<uint32_t>();
+        SW = ss * W; SH = ss * H;
         uint32_t g = grid.is_none() ? 128u : grid.cast<uint32_t>();
         n = g < 2 ? 2 : g;
         std::string cmap = colormap.is_none() ? "viridis" : colormap.cast<std::string>();
@@ -208,7 +211,7 @@ public:
         if (force_unorm) to_linear_u8_rgba(srgb_bytes, lin);
         lut_format = force_unorm ? "Rgba8Unorm" : "Rgba8UnormSrgb";
 
-        check(vf_terrain_create(global_ctx(), W, H, n, force_unorm ? lin : srgb_bytes, force_unorm ? 0 : 1, &t));
+        check(vf_terrain_create_supersampled(global_ctx(), W, H, n, force_unorm ? lin : srgb_bytes, force_unorm ? 0 : 1, ss, &t));
 
         // build_view_matrices (src/terrain/mod.rs:681-691) / SceneGlobals::default (src/scene/mod.rs:17-23,119)
         view = look_at_rh({ 3.f, 2.f, 3.f }, { 0.f, 0.f, 0.f }, { 0.f, 1.f, 0.f });
@@ -407,7 +410,7 @@ public:
         Borrow b(busy);
         uint32_t rows = 0;
         check(vf_terrain_local_rows(t, &rows));
-        py::array_t<uint32_t> a({ (py::ssize_t)rows, (py::ssize_t)W });
+        py::array_t<uint32_t> a({ (py::ssize_t)(ss > 1u ? SH : rows), (py::ssize_t)SW });   // (a supersampled object: the samples' ids)
         check(vf_terrain_read_visibility(t, a.mutable_data()));
         return a;
     }
@@ -454,6 +457,7 @@ public:
         const float *sz = sizes.is_none() ? nullptr : static_cast<const float *>(sizes.cast<py::array>().data());
         const uint8_t *cl = cols.is_none() ? nullptr : static_cast<const uint8_t *>(cols.cast<py::array>().data());
         Borrow b(busy);
+        if (oc[0].cast<bool>()) refuse_occlusion_if_supersampled();   // (before the layer exists: a refusal leaves the object as it was)
         uint32_t id = 0;
         check(vf_terrain_add_points(t, static_cast<const float *>(pts.data()), (uint32_t)pts.shape(0), sz, cl, dsize,
                                     static_cast<const uint8_t *>(dcol.data()), shp, drape ? 1 : 0, &id));
@@ -468,6 +472,7 @@ public:
         const float width = a[2].cast<float>();
         const int cp = a[4].cast<int>();
         Borrow b(busy);
+        if (oc[0].cast<bool>()) refuse_occlusion_if_supersampled();
         uint32_t id = 0;
         check(vf_terrain_add_lines(t, static_cast<const float *>(coords.data()), static_cast<const uint32_t *>(offsets.data()),
                                    (uint32_t)(offsets.shape(0) - 1), width, static_cast<const uint8_t *>(col.data()), cp, drape ? 1 : 0, &id));
@@ -527,6 +532,23 @@ public:
     }
     void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
 
+    // extension: supersampling
+    uint32_t supersample() const { return ss; }
+    uint32_t samples() const { return ss * ss; }
+    py::tuple sample_size() const { return py::make_tuple(SW, SH); }
+    // the samples of the current frame before the resolve: terrain and passes, no overlays, (f H, f W, 4) uint8
+    py::array_t<uint8_t> render_samples()
+    {
+        Borrow b(busy);
+        py::array_t<uint8_t> a({ (py::ssize_t)SH, (py::ssize_t)SW, (py::ssize_t)4 });
+        uint8_t *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        int rc = draw_current();
+        if (rc == VF_OK) rc = vf_terrain_read_samples(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+
     // extension: geometry buffers -- per-pixel depth, world position, normal and primitive id (argument rules:
     // vulkan_forge_amd/_gbuffer.py).  Like render_rgba they describe the frame for the current uniforms: it is drawn first unless the
     // frame this object drew last already is that frame.
@@ -539,10 +561,11 @@ public:
         uint32_t *prim = nullptr;
         for (py::handle h : names) {
             const std::string k = h.cast<std::string>();
-            if (k == "primitive") { py::array_t<uint32_t> a({ (py::ssize_t)H, (py::ssize_t)W }); prim = a.mutable_data(); out[h] = a; continue; }
+            // (the planes describe what was drawn: the samples of a supersampled object, sample_size)
+            if (k == "primitive") { py::array_t<uint32_t> a({ (py::ssize_t)SH, (py::ssize_t)SW }); prim = a.mutable_data(); out[h] = a; continue; }
             const int slot = k == "depth" ? 0 : (k == "position" ? 1 : 2);
-            py::array_t<float> a = slot == 0 ? py::array_t<float>({ (py::ssize_t)H, (py::ssize_t)W })
-                                             : py::array_t<float>({ (py::ssize_t)H, (py::ssize_t)W, (py::ssize_t)3 });
+            py::array_t<float> a = slot == 0 ? py::array_t<float>({ (py::ssize_t)SH, (py::ssize_t)SW })
+                                             : py::array_t<float>({ (py::ssize_t)SH, (py::ssize_t)SW, (py::ssize_t)3 });
             f[slot] = a.mutable_data(); out[h] = a;
         }
         {
@@ -556,7 +579,7 @@ public:
     py::array_t<float> render_depth()
     {
         Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)H, (py::ssize_t)W });
+        py::array_t<float> a({ (py::ssize_t)SH, (py::ssize_t)SW });
         float *dst = a.mutable_data();
         py::gil_scoped_release nogil;
         int rc = draw_current();
@@ -902,6 +925,12 @@ public:
     std::string debug_lut_format() const { return lut_format; }   // src/terrain/mod.rs:493-496
 
 private:
+    // add_points / add_lines make the layer first and set its occlusion afterwards: on a supersampled object the library would refuse the
+    // second step with the layer already there, so the first is not taken and the library's refusal is raised here, in its words
+    void refuse_occlusion_if_supersampled()
+    {
+        if (ss > 1u) throw std::runtime_error("the handle is supersampled: occluding overlay layers are not supported (their depth test reads the frame's visibility per output pixel)");
+    }
     void push_uniforms()
     {
         last = to_uniforms(globals, view, proj);
@@ -917,6 +946,7 @@ private:
     }
     bool frame_current = false;                             // the frame vf_terrain_render drew last was drawn from the current uniforms and heights
     uint32_t W, H, n = 128;
+    uint32_t ss = 1, SW = 0, SH = 0;                        // supersampling factor and the sample size (ss W, ss H)
     vf_terrain *t = nullptr;
     Globals globals;
     Mat4 view{}, proj{};
@@ -927,11 +957,11 @@ private:
 
 class TerrainSpike : public TerrainObject {
 public:
-    TerrainSpike(uint32_t w, uint32_t h, py::object grid, py::object colormap) : TerrainObject(0, w, h, grid, colormap) {}
+    TerrainSpike(uint32_t w, uint32_t h, py::object grid, py::object colormap, py::object supersample) : TerrainObject(0, w, h, grid, colormap, supersample) {}
 };
 class Scene : public TerrainObject {
 public:
-    Scene(uint32_t w, uint32_t h, py::object grid, py::object colormap) : TerrainObject(1, w, h, grid, colormap) {}
+    Scene(uint32_t w, uint32_t h, py::object grid, py::object colormap, py::object supersample) : TerrainObject(1, w, h, grid, colormap, supersample) {}
 };
 
 // ---- Renderer: the triangle smoke path (src/lib.rs:245-334, 685-721) + the DEM path (:336-682) ---------------------
@@ -1176,8 +1206,13 @@ template <class T>
 py::class_<T> bind_terrain(py::module_ &m, const char *name)
 {
     return py::class_<T>(m, name)
-        .def(py::init<uint32_t, uint32_t, py::object, py::object>(), py::arg("width"), py::arg("height"), py::arg("grid") = 128,
-             py::arg("colormap") = "viridis")
+        .def(py::init<uint32_t, uint32_t, py::object, py::object, py::object>(), py::arg("width"), py::arg("height"), py::arg("grid") = 128,
+             py::arg("colormap") = "viridis", py::kw_only(), py::arg("supersample") = 1)
+        .def_property_readonly("supersample", &T::supersample, "The supersampling factor f per axis (1: none).")
+        .def_property_readonly("samples", &T::samples, "Samples per pixel, f * f.")
+        .def_property_readonly("sample_size", &T::sample_size, "(f * width, f * height): the size the terrain is drawn at.")
+        .def("render_samples", &T::render_samples,
+             "The samples of the current frame before the resolve, (f * height, f * width, 4) uint8: terrain and passes, no overlays.")
         .def("render_png", &T::render_png, py::arg("path"))
         .def("render_rgba", &T::render_rgba)
         .def("render_batch", &T::render_batch, py::arg("poses"), py::arg("paths") = py::none())
