@@ -658,6 +658,20 @@ int vf_terrain_read_drape_level(vf_terrain *t, uint32_t level, uint16_t *out /* 
 /* Diagnostics: mean time in ms of `repeats` back-to-back builds of the whole pyramid, after one warm-up. */
 int vf_terrain_debug_drape_mip_build(vf_terrain *t, uint32_t repeats, float *ms);
 
+/* ---- anisotropic filtering of the mip sampling ----
+ * An oblique view stretches a pixel's footprint on the image along one axis, and the pyramid's one sample at the level of the longer
+ * axis blurs across the shorter.  With a largest anisotropy A > 1 (and mipmaps on) a pixel whose footprint is longer than 1.25 times
+ * its width takes up to A samples along the longer of its two screen-axis derivatives, at the level of detail of the shorter
+ * (raised where the ratio exceeds A), and writes their mean; every other pixel is the mipped one, bit for bit.  A setting of the
+ * handle, 1 by default, that survives set_drape, set_drape_device, clear_drape and mipmaps off / on; with mipmaps off it is kept
+ * and has no effect.  It leaves the pyramid as it is: nothing is built again.
+ * vf_terrain_set_drape_anisotropy: max_anisotropy 1, 2, 4, 8 or 16; anything else is refused with VF_ERR_INVALID and changes nothing.
+ *     1: the frames of vf_terrain_set_drape_mips alone, through the same kernel.
+ * vf_terrain_drape_anisotropy: *max_anisotropy as set. */
+#define VF_DRAPE_ANISOTROPY_MAX 16
+int vf_terrain_set_drape_anisotropy(vf_terrain *t, uint32_t max_anisotropy);
+int vf_terrain_drape_anisotropy(const vf_terrain *t, uint32_t *max_anisotropy);
+
 /* ---- viewshed analysis: a line-of-sight field from an observer, and a tint of the frame ------------
  * The viewshed field is one float32 per grid vertex, (grid, grid) row-major (row j = z index, column i = x index): seen in [0, 1],
  * 1 = the observer sees the vertex, 0 = the terrain hides it.  One observer per handle: observer_xz = (x, z) in the overlays' world

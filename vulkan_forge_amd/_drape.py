@@ -94,6 +94,19 @@ def mip_params(enabled=True, bias=0.0):
     return int(bool(enabled)), bias
 
 
+ANISOTROPY_MAX = 16                                       # VF_DRAPE_ANISOTROPY_MAX
+ANISOTROPIES = (1, 2, 4, 8, 16)
+
+
+def aniso_params(max_anisotropy=1):
+    """-> the largest anisotropy as vf_terrain_set_drape_anisotropy takes it (set_drape_anisotropy)"""
+    if isinstance(max_anisotropy, (bool, np.bool_)) or not isinstance(max_anisotropy, (int, np.integer)):
+        raise TypeError(f"max_anisotropy must be an int, got {type(max_anisotropy).__name__}")
+    if max_anisotropy not in ANISOTROPIES:
+        raise ValueError(f"max_anisotropy must be 1, 2, 4, 8 or 16, got {max_anisotropy}")
+    return int(max_anisotropy)
+
+
 def mip_sizes(iw, ih):
     """[(w, h)] of levels 0, 1, ...: each max(1, (size + 1) >> 1) of the level above, down to 1 x 1"""
     sizes = [(int(iw), int(ih))]

@@ -15,6 +15,7 @@ DEFAULT_LIB = os.environ.get("VF_HIP_LIB") or os.path.join(_HERE, "libvf_hip.so"
 VF_OK, VF_ERR_NO_DEVICE, VF_ERR_HIP, VF_ERR_INVALID, VF_ERR_NOMEM = 0, -1, -2, -3, -4
 VF_DRAPE_SIZE_MAX, VF_DRAPE_NEAREST, VF_DRAPE_LINEAR = 16384, 0, 1                       # a draped image layer
 VF_DRAPE_MIP_BIAS_MAX, VF_DRAPE_MIP_LEVELS_MAX = 16.0, 15                                # its mip pyramid
+VF_DRAPE_ANISOTROPY_MAX = 16                                                             # anisotropic taps through it
 VF_SUPERSAMPLE_MAX = 4                                                                   # supersampled terrain frames
 VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED_AHEAD = 1, 2, 4, 8, 16   # vf_terrain_debug_plan_mode
 VF_PLAN_TILE_LISTS = 64        # ... and for "the tile kernel read the plan state's per-tile candidate lists" (DESIGN.md 3): Terrain.tile_lists()
@@ -39,6 +40,7 @@ SYMBOLS = [
     "vf_terrain_debug_ambient_scans",
     "vf_terrain_set_drape", "vf_terrain_set_drape_device", "vf_terrain_clear_drape", "vf_terrain_drape_info", "vf_terrain_debug_drape_stage",
     "vf_terrain_set_drape_mips", "vf_terrain_drape_mip_info", "vf_terrain_read_drape_level", "vf_terrain_debug_drape_mip_build",
+    "vf_terrain_set_drape_anisotropy", "vf_terrain_drape_anisotropy",
     "vf_terrain_set_viewshed", "vf_terrain_read_viewshed_field", "vf_terrain_viewshed_field_device", "vf_terrain_viewshed_info",
     "vf_terrain_debug_viewshed_stage", "vf_terrain_debug_viewshed_scans",
     "vf_terrain_set_cumulative_viewshed", "vf_terrain_read_cumulative_viewshed_field", "vf_terrain_cumulative_viewshed_field_device",
@@ -179,6 +181,8 @@ _PROTOS = {
     "vf_terrain_drape_mip_info": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32), C.POINTER(_f), C.POINTER(C.c_uint64), C.POINTER(_u32)]),
     "vf_terrain_read_drape_level": (_i, [_vp, _u32, _vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "vf_terrain_debug_drape_mip_build": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_drape_anisotropy": (_i, [_vp, _u32]),
+    "vf_terrain_drape_anisotropy": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_set_viewshed": (_i, [_vp, _i, C.POINTER(_f), _f, _f, _f, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _f, _f]),
     "vf_terrain_read_viewshed_field": (_i, [_vp, _vp]),
     "vf_terrain_viewshed_field_device": (_i, [_vp, _vp, _vp]),
@@ -870,6 +874,19 @@ class Terrain:
         ms = _f()
         self._check(self.lib.vf_terrain_debug_drape_mip_build(self.t, int(repeats), C.byref(ms)))
         return ms.value
+
+    def set_drape_anisotropy(self, max_anisotropy=1):
+        """Anisotropic filtering of the mip sampling: up to max_anisotropy (1, 2, 4, 8 or 16) samples along the longer
+        axis of a pixel's footprint, at the level of detail of the shorter.  A setting of the handle, 1 by default, that survives
+        set_drape, clear_drape and mipmaps off / on; it has no effect while mipmaps are off."""
+        from ._drape import aniso_params
+        self._check(self.lib.vf_terrain_set_drape_anisotropy(self.t, aniso_params(max_anisotropy)))
+
+    def drape_anisotropy(self):
+        """The largest anisotropy as set (1: off)."""
+        a = _u32()
+        self._check(self.lib.vf_terrain_drape_anisotropy(self.t, C.byref(a)))
+        return a.value
 
     def enable_timing(self, on=True, stats=True, sampled=False):
         """stats=False: HIP events only, the kernels run exactly as untimed (no per-item statistics; blocks_* read 0);

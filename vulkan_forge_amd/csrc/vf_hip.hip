@@ -444,7 +444,8 @@ struct vf_terrain {
     struct DrapeMipState {
         bool enabled = false;
         float bias = 0.0f;
-        DevBuf<uint2> d_pyr;             // levels 1 ... levels - 1, one after the other, each from an even texel index (16-byte aligned)
+        uint32_t aniso = 1;              // the largest anisotropy A: the handle's as bias is; 1: 4k's one sample
+        DevBuf<uint2> d_pyr;            // levels 1 ... levels - 1, one after the other, each from an even texel index (16-byte aligned)
         bool stale = true;               // d_pyr does not hold the pyramid of the image held
         uint32_t builds = 0;             // times a pyramid was built (vf_terrain_drape_mip_info)
     } dm;
@@ -1797,6 +1798,10 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
                         bool shadows, bool ambient);
 
+// The drape's shade pass as the handle's settings choose it: through the mip pyramid when mipmaps are on, and with
+// anisotropic taps when the largest anisotropy is above 1 as well (4p); the frames and the drape diagnostics both ask here
+static Relight drape_pass_of(const vf_terrain *t) { return !t->dm.enabled ? kDrape : t->dm.aniso > 1u ? kDrapeAniso : kDrapeMip; }
+
 static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
@@ -1822,7 +1827,7 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool shadows = t->sh.enabled && !diag;           // (visibility / diagnostics frames: the frame as the tile kernel shades it)
     const bool ambient = t->am.enabled && !diag;
     const bool drape = t->dr.iw != 0u && !diag;
-    const Relight drape_pass = t->dm.enabled ? kDrapeMip : kDrape;   // (through the mip pyramid when mipmaps are on)
+    const Relight drape_pass = drape_pass_of(t);
     const bool viewshed = t->vs.enabled && !diag;
     const bool cumulative = t->cv.enabled && !diag;
     const bool exposure = t->se.enabled && !diag;
@@ -3100,15 +3105,24 @@ static void relight_launch(const vf_terrain *t, hipStream_t s, const FrameParams
         D.iw = H.iw; D.ih = H.ih; D.opacity = H.opacity; D.linear = H.filter == VF_DRAPE_LINEAR ? 1u : 0u;
         if (pass == kDrape) { VF_RELIGHT(false, kDrape); VF_RELIGHT(true, kDrape); }
         else {                                                 // kDrapeMip: the pyramid beside it (current: mips_current)
-            RelightMipParams RM = {};
-            static_cast<RelightParams &>(RM) = R;
+            RelightAnisoParams RA = {};
+            static_cast<RelightParams &>(RA) = R;
             const MipLayout L = mip_layout(H.iw, H.ih);
-            RM.M.levels = L.levels; RM.M.bias = t->dm.bias;
-            for (uint32_t k = 0; k < L.levels; ++k) { RM.M.w[k] = (uint16_t)L.w[k]; RM.M.h[k] = (uint16_t)L.h[k]; RM.M.lvl[k] = k ? t->dm.d_pyr.p + L.off[k] : nullptr; }
-            hipLaunchKernelGGL((k_relight<false, kDrapeMip>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
-                               (const uint32_t *)t->d_vis, RM, redo, rgba);
-            hipLaunchKernelGGL((k_relight<true, kDrapeMip>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
-                               (const uint32_t *)t->d_vis, RM, redo, rgba);
+            RA.M.levels = L.levels; RA.M.bias = t->dm.bias;
+            for (uint32_t k = 0; k < L.levels; ++k) { RA.M.w[k] = (uint16_t)L.w[k]; RA.M.h[k] = (uint16_t)L.h[k]; RA.M.lvl[k] = k ? t->dm.d_pyr.p + L.off[k] : nullptr; }
+            if (pass == kDrapeMip) {
+                const RelightMipParams &RM = RA;
+                hipLaunchKernelGGL((k_relight<false, kDrapeMip>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
+                                   (const uint32_t *)t->d_vis, RM, redo, rgba);
+                hipLaunchKernelGGL((k_relight<true, kDrapeMip>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
+                                   (const uint32_t *)t->d_vis, RM, redo, rgba);
+            } else {                                           // kDrapeAniso: the largest anisotropy A and 1 / A^2 behind that
+                RA.max_aniso = t->dm.aniso; RA.inv_a2 = 1.0f / (float)(t->dm.aniso * t->dm.aniso);
+                hipLaunchKernelGGL((k_relight<false, kDrapeAniso>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
+                                   (const uint32_t *)t->d_vis, RA, redo, rgba);
+                hipLaunchKernelGGL((k_relight<true, kDrapeAniso>), grid, threads, 0, s, P, V, (const float *)t->d_lut, (const float *)t->ctx->d_thresh,
+                                   (const uint32_t *)t->d_vis, RA, redo, rgba);
+            }
         }
     }
 #undef VF_RELIGHT
@@ -3122,7 +3136,7 @@ static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
 {
     if (int rc = relight_fields(t, t->inputs.u, s, shadows, ambient)) return rc;
     if (relight_drapes(pass) && t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(s, t->dr.copied, 0));
-    if (pass == kDrapeMip) { if (int rc = mips_current(t, s)) return rc; }
+    if (relight_mips(pass)) { if (int rc = mips_current(t, s)) return rc; }
     relight_launch(t, s, P, V, redo, rgba, pass, shadows, ambient);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
@@ -3470,7 +3484,7 @@ int vf_terrain_debug_drape_stage(vf_terrain *t, uint32_t repeats, float *ms)
     if (t->dr.copied) VF_HIP_TRY(hipStreamWaitEvent(G.s, t->dr.copied, 0));
     if (int rc = mips_current(t, G.s)) return rc;            // (whichever drape pass the handle would run)
     float mean = 0.0f;
-    const hipError_t err = G.time_shade(repeats, mean, t->dm.enabled ? kDrapeMip : kDrape);
+    const hipError_t err = G.time_shade(repeats, mean, drape_pass_of(t));
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("drape diagnostics: ") + hipGetErrorString(err));
     *ms = mean;
     return VF_OK;
@@ -3503,6 +3517,27 @@ int vf_terrain_drape_mip_info(const vf_terrain *t, int *enabled, uint32_t *level
     if (bias) *bias = M.bias;
     if (bytes) *bytes = (uint64_t)L.texels * sizeof(uint2);
     if (builds) *builds = M.builds;
+    return VF_OK;
+}
+
+// ---- and anisotropic taps through it (vf_drape_aniso.h) -----------------------------------
+// The setting reads nothing the frame in flight holds and leaves the pyramid as it is: the next frame is drawn again, that is all.
+
+int vf_terrain_set_drape_anisotropy(vf_terrain *t, uint32_t max_anisotropy)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    const uint32_t a = max_anisotropy;
+    if (!(a == 1u || a == 2u || a == 4u || a == 8u || a == VF_DRAPE_ANISOTROPY_MAX)) return fail(VF_ERR_INVALID, "max_anisotropy must be 1, 2, 4, 8 or 16");
+    if (t->dm.aniso == a) return VF_OK;
+    t->dm.aniso = a;
+    t->inputs_gen++;
+    return VF_OK;
+}
+
+int vf_terrain_drape_anisotropy(const vf_terrain *t, uint32_t *max_anisotropy)
+{
+    if (!t || !max_anisotropy) return fail(VF_ERR_INVALID, "NULL argument");
+    *max_anisotropy = t->dm.aniso;
     return VF_OK;
 }
 

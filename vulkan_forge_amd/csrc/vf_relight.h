@@ -9,18 +9,20 @@
 //              before wrote
 //   kDrapeMip  the draped image through its mip pyramid (4k): kDrape with the level of detail of the pixel's footprint on the image,
 //              from the varyings of the same primitive one pixel to the right and one below
+//   kDrapeAniso  kDrapeMip with up to A taps along the footprint's major axis, at the level of detail of the minor one (4p)
 //
 // The surface point, its varyings and the interpolation of a per-vertex scalar are vf_visible.h's.  The arithmetic is the
-// contract's, bit for bit (tests/shadow_model, ambient_model, drape_model and drape_mip_model are its CPU statements).  All kernels are templates
+// contract's, bit for bit (tests/shadow_model, ambient_model, drape_model, drape_mip_model and drape_aniso_model are its CPU statements).  All kernels are templates
 // (DESIGN.md 4d).
 #pragma once
 #include <type_traits>
-#include "vf_drape_mips.h"
+#include "vf_drape_aniso.h"
 
 namespace vf {
 
-enum Relight : int { kShadow = 0, kAmbient = 1, kDrape = 2, kDrapeMip = 3 };
-constexpr bool relight_drapes(Relight pass) { return pass == kDrape || pass == kDrapeMip; }
+enum Relight : int { kShadow = 0, kAmbient = 1, kDrape = 2, kDrapeMip = 3, kDrapeAniso = 4 };
+constexpr bool relight_mips(Relight pass) { return pass == kDrapeMip || pass == kDrapeAniso; }     // the passes that read the pyramid
+constexpr bool relight_drapes(Relight pass) { return pass == kDrape || relight_mips(pass); }
 
 // What a pass reads beside the frame.  lit / sky: the shadow and sky-view fields; kShadow reads lit alone, kAmbient takes sky for
 // granted, and a field that is NULL otherwise belongs to a feature that is off (its value is 1).  The rest is the drape's.
@@ -33,7 +35,9 @@ struct RelightParams {
 };
 // ... and kDrapeMip the pyramid beside it: the other passes keep their kernel arguments as they are
 struct RelightMipParams : RelightParams { DrapeMips M; };
-template <Relight PASS> using RelightArg = std::conditional_t<PASS == kDrapeMip, RelightMipParams, RelightParams>;
+// ... and kDrapeAniso the largest anisotropy A and 1 / A^2 behind that
+struct RelightAnisoParams : RelightMipParams { uint32_t max_aniso; float inv_a2; };
+template <Relight PASS> using RelightArg = std::conditional_t<PASS == kDrapeAniso, RelightAnisoParams, std::conditional_t<PASS == kDrapeMip, RelightMipParams, RelightParams>>;
 
 // lit and amb of a pixel.  At the three vertices first: a primitive whose three values are all 1 is `plain` and gives 1 without
 // interpolation (x * (1 / x) need not round to 1).
@@ -71,7 +75,8 @@ __device__ __forceinline__ void point_light(const FrameParams &P, const VisibleP
 // Pixel (px, py) with visibility id `id`: false when the pass leaves it as the frame drew it, else its colour again.  Each pass
 // leaves before it computes what it does not need: kShadow and kAmbient on the vertex values alone, then on the interpolated ones,
 // and form the varyings last; kDrape needs (x, z) for its sample and touches the fields only where the image shows; kDrapeMip
-// evaluates the neighbouring centres only for a pixel inside the image's extent.
+// evaluates the neighbouring centres only for a pixel inside the image's extent, and kDrapeAniso follows it with its plan between
+// the neighbours and the sample.
 template <bool CLIPPED, Relight PASS>
 __device__ __forceinline__ bool relight_pixel(const FrameParams &P, const SetupView &V, const ShadeTables &T, const float *dec, const RelightArg<PASS> &R,
                                               uint32_t id, int32_t px, int32_t py, uint32_t &rgba)
@@ -95,6 +100,14 @@ __device__ __forceinline__ bool relight_pixel(const FrameParams &P, const SetupV
             point_neighbours(P, p, px, py, right, down);
             const float lod = mip_lod(R.D, R.M.bias, attr[1], attr[2], right[1], right[2], down[1], down[2]);
             if (!mip_sample(R.D, R.M, R.img, dec, attr[1], attr[2], lod, val)) return false;
+        } else if constexpr (PASS == kDrapeAniso) {
+            const float fu = (attr[1] - R.D.x0) * R.D.sx, fv = (attr[2] - R.D.z0) * R.D.sz;
+            if (!(fu >= 0.0f && fu <= (float)R.D.iw && fv >= 0.0f && fv <= (float)R.D.ih)) return false;
+            float right[3], down[3];
+            point_neighbours(P, p, px, py, right, down);
+            const AnisoPlan a = aniso_plan(R.D, R.M.bias, R.max_aniso, R.inv_a2, attr[1], attr[2], right[1], right[2], down[1], down[2]);
+            if (a.n == 1u) { if (!mip_sample(R.D, R.M, R.img, dec, attr[1], attr[2], a.lod, val)) return false; }
+            else aniso_sample(R.D, R.M, R.img, dec, fu, fv, a, val);
         } else {
             if (!dr_sample(R.D, R.img, dec, attr[1], attr[2], val)) return false;
         }

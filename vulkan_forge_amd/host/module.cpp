@@ -727,6 +727,21 @@ public:
         check(rc);
         return out;
     }
+    // extension: anisotropic filtering of the mip sampling (argument rules: vulkan_forge_amd/_drape.py)
+    void set_drape_anisotropy(py::object max_anisotropy)
+    {
+        const uint32_t a = py::module_::import("vulkan_forge_amd._drape").attr("aniso_params")(max_anisotropy).cast<uint32_t>();
+        Borrow b(busy);
+        check(vf_terrain_set_drape_anisotropy(t, a));
+        frame_current = false;
+    }
+    uint32_t drape_anisotropy()
+    {
+        Borrow b(busy);
+        uint32_t a = 0;
+        check(vf_terrain_drape_anisotropy(t, &a));
+        return a;
+    }
     // extension: viewshed analysis (argument rules: vulkan_forge_amd/_viewshed.py)
     void set_viewshed(py::object observer, py::object enabled, py::object eye_height, py::object target_height, py::object radius,
                       py::object visible_rgba, py::object hidden_rgba, py::object softness, py::object bias)
@@ -1275,6 +1290,12 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "None while mipmaps are off, else dict(levels, sizes=[(w, h), ...], bias, bytes, builds); levels 0 without a drape.")
         .def("read_drape_level", &T::read_drape_level, py::arg("level"),
              "Level 1 <= level < levels of the pyramid as (h, w, 4) float16: premultiplied linear (r, g, b, a).  Builds it if stale.")
+        .def("set_drape_anisotropy", &T::set_drape_anisotropy, py::arg("max_anisotropy") = 1,
+             "Anisotropic filtering of the mip sampling (DESIGN.md 4p): a pixel whose footprint on the image is longer than wide takes\n"
+             "up to max_anisotropy (1, 2, 4, 8 or 16) samples along the longer axis at the level of detail of the shorter, so oblique\n"
+             "ground keeps its detail.  A setting of the handle, 1 by default, that survives set_drape, clear_drape and mipmaps off / on;\n"
+             "it has no effect while mipmaps are off and never rebuilds the pyramid.")
+        .def("drape_anisotropy", &T::drape_anisotropy, "The largest anisotropy as set (1: off).")
         .def("set_viewshed", &T::set_viewshed, py::arg("observer"), py::kw_only(), py::arg("enabled") = true, py::arg("eye_height") = VF_VIEWSHED_EYE_HEIGHT,
              py::arg("target_height") = VF_VIEWSHED_TARGET_HEIGHT, py::arg("radius") = py::none(), py::arg("visible_rgba") = py::make_tuple(64, 255, 96, 96),
              py::arg("hidden_rgba") = py::make_tuple(0, 0, 0, 0), py::arg("softness") = VF_VIEWSHED_SOFTNESS, py::arg("bias") = VF_VIEWSHED_BIAS,
