@@ -874,6 +874,52 @@ int vf_terrain_read_samples(vf_terrain *t, uint8_t *dst);
 int vf_terrain_samples_device(vf_terrain *t, void *dev_dst, void *stream);
 int vf_terrain_debug_resolve_stage(vf_terrain *t, uint32_t repeats, float *ms);
 
+/* ---- atmospheric haze: a distance and height fog pass over the terrain ------------------------------
+ * A setting of the handle, off by default.  With haze enabled vf_terrain_render draws the frame as before, with the visibility store
+ * on, then -- behind the shadow, ambient and drape passes and the three tints, in front of the resolve of a supersampled handle and
+ * of the overlays, which are composited on top and are not hazed -- blends the haze colour over every covered pixel (every sample of
+ * a supersampled handle) with the opacity
+ *     a = min(1 - exp(-density l g), max_opacity) alpha8 / 255,     l = max(d - start, 0),
+ * d the view depth of the surface point (the geometry buffers' depth, clip w) and g the height factor: 1 with falloff == 0 (uniform
+ * haze); with falloff > 0 the air's density at world height y is density exp(-(y - base) / falloff) and g is the mean of that
+ * exponential along the straight line from the eye's height to the point's.  The blend is the viewshed tint's, on linear values with
+ * the exact sRGB encoder; a pixel whose a is not > 0 keeps the frame's bytes.  background != 0: pixels without terrain are blended
+ * too, with a = max_opacity alpha8 / 255, the limit of a surface infinitely far away, and keep their alpha byte; 0: they are never
+ * touched.  The arithmetic is fixed bit for bit and does not follow vf_terrain_set_shade_precision (which also states
+ * the exponential).  The colour is {r, g, b, a} bytes.
+ *
+ * vf_terrain_set_haze: stores every parameter, also with enable == 0 (the opacity calls below use them).  VF_ERR_INVALID, with a
+ * message that says why and nothing changed: density, start or falloff negative or not finite; base not finite; max_opacity outside
+ * [0, 1]; rgba == NULL.  Whole-frame handles only: enabling on a band- or tile-sharded handle, sharding a handle with haze enabled,
+ * and vf_terrain_render_batch / _batch_host on a handle with haze enabled are VF_ERR_INVALID and change nothing.  The setting survives
+ * height uploads, new uniforms, the drape and the vertex fields; it holds no cached field: per frame only the eye's height is formed
+ * again, on the host.  A handle that never enables haze allocates and launches nothing for it.
+ * vf_terrain_clear_haze: off, the defaults are back, the opacity plane is freed.
+ * vf_terrain_haze_info: the settings as stored and, once uniforms are set (has_eye), eye_y of the live uniforms: y of -R^T t of the
+ * view matrix.
+ * vf_terrain_read_haze_opacity: a of every pixel (0 where the pass leaves the pixel) for the frame rendered last and the stored
+ * settings, enabled or not, into host memory: (H, W) float32 of the raster size -- the sample size on a supersampled handle.
+ * Produced as the geometry buffers are, only when asked: the frame is drawn again into scratch buffers with its visibility.
+ * vf_terrain_haze_opacity_device: the same into device memory on `stream` (NULL: the context's stream); later calls on the handle
+ * are ordered behind it by the library.
+ * vf_terrain_debug_haze_stage: diagnostics -- the average time (HIP events, ms) of `repeats` launches of the haze pass alone with the
+ * stored settings on the frame rendered last (drawn again into scratch buffers), after one warm-up launch. */
+#define VF_HAZE_RGBA 0xFFEBD7C8u   /* (200, 215, 235, 255) as r | g << 8 | b << 16 | a << 24 */
+typedef struct vf_haze_info {
+    int32_t enabled, background;
+    float density, start, falloff /* 0: uniform */, base, max_opacity;
+    uint8_t rgba[4];
+    int32_t has_eye;          /* uniforms are set: eye_y is valid */
+    float eye_y;
+} vf_haze_info;
+int vf_terrain_set_haze(vf_terrain *t, int enable, float density, const uint8_t rgba[4], float start, float falloff /* 0: uniform */, float base,
+                        float max_opacity, int background);
+int vf_terrain_clear_haze(vf_terrain *t);
+int vf_terrain_haze_info(vf_terrain *t, vf_haze_info *out);
+int vf_terrain_read_haze_opacity(vf_terrain *t, float *dst);
+int vf_terrain_haze_opacity_device(vf_terrain *t, float *dev, void *stream);
+int vf_terrain_debug_haze_stage(vf_terrain *t, uint32_t repeats, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,8 @@ SYMBOLS = [
     "vf_terrain_debug_sun_exposure_stage",
     "vf_terrain_create_supersampled", "vf_terrain_supersampling", "vf_terrain_read_samples", "vf_terrain_samples_device",
     "vf_terrain_debug_resolve_stage",
+    "vf_terrain_set_haze", "vf_terrain_clear_haze", "vf_terrain_haze_info", "vf_terrain_read_haze_opacity", "vf_terrain_haze_opacity_device",
+    "vf_terrain_debug_haze_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -85,6 +87,11 @@ class CumulativeViewshedInfo(C.Structure):
 class SunExposureInfo(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("count", C.c_uint32), ("counted", C.c_uint32), ("weight_total", C.c_float), ("incidence", C.c_int32),
                 ("batch", C.c_uint32), ("softness", C.c_float), ("bias", C.c_float), ("high_rgba", C.c_uint8 * 4), ("low_rgba", C.c_uint8 * 4)]
+
+
+class HazeInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("background", C.c_int32), ("density", C.c_float), ("start", C.c_float), ("falloff", C.c_float),
+                ("base", C.c_float), ("max_opacity", C.c_float), ("rgba", C.c_uint8 * 4), ("has_eye", C.c_int32), ("eye_y", C.c_float)]
 
 
 DIST_UNIQUE_ID_BYTES = 128
@@ -210,6 +217,12 @@ _PROTOS = {
     "vf_terrain_read_samples": (_i, [_vp, _vp]),
     "vf_terrain_samples_device": (_i, [_vp, _vp, _vp]),
     "vf_terrain_debug_resolve_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_haze": (_i, [_vp, _i, _f, C.POINTER(C.c_uint8), _f, _f, _f, _f, _i]),
+    "vf_terrain_clear_haze": (_i, [_vp]),
+    "vf_terrain_haze_info": (_i, [_vp, C.POINTER(HazeInfo)]),
+    "vf_terrain_read_haze_opacity": (_i, [_vp, _vp]),
+    "vf_terrain_haze_opacity_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_debug_haze_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -568,6 +581,43 @@ class Terrain:
         """The resolve kernel as timed launches of its own (diagnostics): average ms of `repeats` launches."""
         ms = _f()
         self._check(self.lib.vf_terrain_debug_resolve_stage(self.t, int(repeats), C.byref(ms)))
+        return ms.value
+
+    # ---- atmospheric haze (include/vf_hip.h, DESIGN.md 4q) ----
+    def set_haze(self, density, *, rgba=(200, 215, 235, 255), start=0.0, falloff=None, base=0.0, max_opacity=1.0, background=False, enabled=True):
+        """Atmospheric haze: blend `rgba` over the terrain by view depth beyond `start`; falloff (world units of y): the
+        density falls off exponentially with height above `base`, None: uniform haze; background: pixels without terrain take
+        max_opacity.  Every parameter is stored by every call, also one that disables, and steers haze_opacity() too."""
+        from ._haze import haze_args
+        en, dens, col, st, fo, ba, mo, bg = haze_args(density, rgba, start, falloff, base, max_opacity, background, enabled)
+        self._check(self.lib.vf_terrain_set_haze(self.t, en, dens, (C.c_uint8 * 4)(*col), st, fo, ba, mo, bg))
+
+    def clear_haze(self):
+        """Haze off, its parameters the defaults again, its opacity plane freed."""
+        self._check(self.lib.vf_terrain_clear_haze(self.t))
+
+    def haze_info(self):
+        """The haze settings as stored and eye_y of the live uniforms (None before uniforms are set): a dict."""
+        from ._haze import haze_info
+        v = HazeInfo()
+        self._check(self.lib.vf_terrain_haze_info(self.t, C.byref(v)))
+        return haze_info(v.enabled, v.background, v.density, v.start, v.falloff, v.base, v.max_opacity, tuple(v.rgba), v.has_eye, v.eye_y)
+
+    def haze_opacity(self):
+        """The haze opacity of every pixel of the frame rendered last, 0 where the pass leaves the pixel: (H, W) float32 of the raster
+        size (the sample size on a supersampled handle)."""
+        out = np.empty((self.SH, self.SW), np.float32)
+        self._check(self.lib.vf_terrain_read_haze_opacity(self.t, out.ctypes.data))
+        return out
+
+    def haze_opacity_device(self, dev, stream=None):
+        """The same into device memory (a torch tensor's data_ptr(), H x W floats) on `stream`."""
+        self._check(self.lib.vf_terrain_haze_opacity_device(self.t, dev, stream))
+
+    def haze_stage(self, repeats=20):
+        """The haze pass alone as timed launches (diagnostics): average ms of `repeats` launches."""
+        ms = _f()
+        self._check(self.lib.vf_terrain_debug_haze_stage(self.t, int(repeats), C.byref(ms)))
         return ms.value
 
     def read_gbuffer(self, planes=("depth", "position", "normal", "primitive")):

@@ -12,6 +12,7 @@
 #include "vf_cumulative_viewshed.h"   // templates only
 #include "vf_sun_exposure.h"          // templates only
 #include "vf_resolve.h"               // templates only
+#include "vf_haze.h"                  // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -500,6 +501,13 @@ struct vf_terrain {
         std::vector<ExposureSun> recs;   // the host's copy of d_suns (the source of its upload)
         uint32_t batch = 0;              // the batch size of the last computation
     } se;
+    // atmospheric haze: a setting of the handle, no cached field; the plane is made by the first opacity read
+    struct Haze {
+        bool enabled = false, background = false;
+        float density = 0.0f, start = 0.0f, falloff = 0.0f /* 0: uniform */, base = 0.0f, max_opacity = 1.0f;
+        uint32_t rgba = VF_HAZE_RGBA;    // r | g << 8 | b << 16 | a << 24
+        DevBuf<float> d_plane;           // (H, W) opacities behind vf_terrain_read_haze_opacity
+    } hz;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -1055,7 +1063,7 @@ void vf_terrain_destroy(vf_terrain *t)
     (void)hipDeviceSynchronize();
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    t->d_gb.release(); t->d_pick.release();
+    t->d_gb.release(); t->d_pick.release(); t->hz.d_plane.release();
     shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t); exposure_release(t);
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
@@ -1234,6 +1242,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->cv.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     if (t->se.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     if (t->ss > 1u && nranks != 1) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
+    if (t->hz.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1363,6 +1372,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
+    if (t->hz.enabled) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1805,6 +1815,7 @@ static Relight drape_pass_of(const vf_terrain *t) { return !t->dm.enabled ? kDra
 static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int haze_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 
 // The resolve of a supersampled handle's samples into its frame (vf_resolve.h).  Defined with the other supersampling calls below: the template is
 // instantiated there, behind the tile kernels and what they call, whose code -- PC-relative call offsets included -- keeps its place
@@ -1831,7 +1842,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool viewshed = t->vs.enabled && !diag;
     const bool cumulative = t->cv.enabled && !diag;
     const bool exposure = t->se.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure;
+    const bool haze = t->hz.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure || haze;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1911,7 +1923,11 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
         const int vrc = viewshed_pass(t, s, P, V, S.work_count + 3, raster);
         if (vrc != VF_OK) return vrc;
     }
-    if (resolve) {                                         // the samples -> the frame: every output pixel is rewritten, whatever the tiles drew
+    if (haze && ntiles) {                                  // atmospheric haze: between the eye and the painted surface, so behind the tints; under the resolve and the overlays
+        const int hrc = haze_pass(t, s, P, V, S.work_count + 3, raster);
+        if (hrc != VF_OK) return hrc;
+    }
+    if (resolve) {                                        // the samples -> the frame: every output pixel is rewritten, whatever the tiles drew
         resolve_launch(t, s, t->d_rgba);
         VF_HIP_TRY(hipGetLastError());
     }
@@ -2047,6 +2063,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
+    if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
@@ -2070,6 +2087,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
+    if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
@@ -4162,6 +4180,141 @@ int vf_terrain_debug_sun_exposure_stage(vf_terrain *t, uint32_t repeats, float *
     if (rc != VF_OK) return rc;
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("sun exposure diagnostics: ") + hipGetErrorString(err));
     *ms = a;
+    return VF_OK;
+}
+
+// ---- atmospheric haze (vf_haze.h) ---------------------------------------------------------
+
+// contract item 4: y of -R^T t of the column-major view matrix, as mat_vec reads it
+static float haze_eye_y(const float *u) { return -std::fmaf(u[6], u[14], std::fmaf(u[5], u[13], u[4] * u[12])); }
+
+static HazeParams haze_params(const vf_terrain *t, const float *u)
+{
+    const vf_terrain::Haze &H = t->hz;
+    HazeParams Z = {};
+    Z.decode = t->ctx->d_decode;
+    Z.rgba = H.rgba; Z.density = H.density; Z.start = H.start; Z.falloff = H.falloff; Z.base = H.base; Z.max_opacity = H.max_opacity;
+    Z.eye_y = haze_eye_y(u);
+    Z.background = H.background ? 1u : 0u;
+    return Z;
+}
+
+// Both CLIPPED instantiations, in k_resolve's launch shape (gb_grid): into the colour buffer `rgba`, or (rgba == NULL) the opacities into `plane`
+static void haze_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, const float *u, uint32_t *rgba,
+                        float *plane)
+{
+    const dim3 grid = gb_grid(t), threads(256);
+    const HazeParams Z = haze_params(t, u);
+    const float *thr = t->ctx->d_thresh;
+    const uint32_t *vis = t->d_vis;
+    if (rgba) {
+        hipLaunchKernelGGL((k_haze<false, false>), grid, threads, 0, s, P, V, thr, vis, Z, redo, rgba, (float *)nullptr);
+        hipLaunchKernelGGL((k_haze<true, false>), grid, threads, 0, s, P, V, thr, vis, Z, redo, rgba, (float *)nullptr);
+    } else {
+        hipLaunchKernelGGL((k_haze<false, true>), grid, threads, 0, s, P, V, thr, vis, Z, redo, (uint32_t *)nullptr, plane);
+        hipLaunchKernelGGL((k_haze<true, true>), grid, threads, 0, s, P, V, thr, vis, Z, redo, (uint32_t *)nullptr, plane);
+    }
+}
+
+// The haze of a frame, on the draw stream behind its tile kernels (which stored the visibility), the relight passes and the tints
+static int haze_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    haze_launch(t, s, P, V, redo, t->inputs.u, rgba, nullptr);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_haze(vf_terrain *t, int enable, float density, const uint8_t rgba[4], float start, float falloff, float base, float max_opacity,
+                        int background)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!rgba) return fail(VF_ERR_INVALID, "NULL argument: the haze colour");
+    if (!(std::isfinite(density) && density >= 0.0f)) return fail(VF_ERR_INVALID, "density must be a finite number >= 0");
+    if (!(std::isfinite(start) && start >= 0.0f)) return fail(VF_ERR_INVALID, "start must be a finite number >= 0");
+    if (!(std::isfinite(falloff) && falloff >= 0.0f)) return fail(VF_ERR_INVALID, "falloff must be a finite number > 0, or 0 for uniform haze");
+    if (!std::isfinite(base)) return fail(VF_ERR_INVALID, "base must be finite");
+    if (!(max_opacity >= 0.0f && max_opacity <= 1.0f)) return fail(VF_ERR_INVALID, "max_opacity must lie in [0, 1]");
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "haze needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    vf_terrain::Haze &H = t->hz;
+    const uint32_t c = pack_rgba8(rgba);
+    if (H.enabled != (enable != 0) || H.density != density || H.rgba != c || H.start != start || H.falloff != falloff || H.base != base
+        || H.max_opacity != max_opacity || H.background != (background != 0))
+        t->inputs_gen++;
+    H.enabled = enable != 0; H.background = background != 0;
+    H.density = density; H.rgba = c; H.start = start; H.falloff = falloff; H.base = base; H.max_opacity = max_opacity;
+    return VF_OK;
+}
+
+int vf_terrain_clear_haze(vf_terrain *t)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (t->hz.enabled) t->inputs_gen++;
+    t->hz.d_plane.release();
+    t->hz = vf_terrain::Haze();
+    return VF_OK;
+}
+
+int vf_terrain_haze_info(vf_terrain *t, vf_haze_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::Haze &H = t->hz;
+    *out = vf_haze_info();
+    out->enabled = H.enabled ? 1 : 0; out->background = H.background ? 1 : 0;
+    out->density = H.density; out->start = H.start; out->falloff = H.falloff; out->base = H.base; out->max_opacity = H.max_opacity;
+    for (int k = 0; k < 4; ++k) out->rgba[k] = (uint8_t)(H.rgba >> (8 * k));
+    out->has_eye = t->have_uniforms ? 1 : 0;
+    if (t->have_uniforms) out->eye_y = haze_eye_y(t->inputs.u);
+    return VF_OK;
+}
+
+// The opacity plane, produced as the geometry buffers are: the frame rendered last drawn again with its visibility (gb_frame), then
+// k_haze<., true> on `s` with the stored settings, enabled or not
+static int haze_plane(vf_terrain *t, float *dev, hipStream_t s)
+{
+    GbFrame F;
+    if (int rc = gb_frame(t, F)) return rc;
+    haze_launch(t, s ? s : t->ctx->stream, F.P, F.V, t->ps[t->last_set].work_count + 3, (t->have_frame ? t->drawn_inputs : t->inputs).u, nullptr, dev);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_read_haze_opacity(vf_terrain *t, float *dst)
+{
+    if (!t || !dst) return fail(VF_ERR_INVALID, "NULL argument");
+    const size_t npx = (size_t)t->W * t->H;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (t->hz.d_plane.reserve(npx, npx) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, "haze opacity allocation failed"); }
+    hipStream_t s = t->ctx->stream;
+    if (int rc = haze_plane(t, t->hz.d_plane.p, s)) return rc;
+    VF_HIP_TRY(hipMemcpyAsync(dst, t->hz.d_plane.p, npx * sizeof(float), hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));
+    return VF_OK;
+}
+
+int vf_terrain_haze_opacity_device(vf_terrain *t, float *dev, void *stream)
+{
+    if (!t || !dev) return fail(VF_ERR_INVALID, "NULL argument");
+    hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
+    if (int rc = haze_plane(t, dev, s)) return rc;
+    VF_HIP_TRY(gb_order_after(t, s));
+    return VF_OK;
+}
+
+int vf_terrain_debug_haze_stage(vf_terrain *t, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (repeats == 0) repeats = 1;
+    RelightStage G;
+    if (int rc = G.open(t)) return rc;
+    float mean = 0.0f;
+    const hipError_t err = time_launches(G.s, repeats, mean, [&](bool) { haze_launch(t, G.s, G.F.P, G.F.V, G.redo, G.u, t->d_rgba_scratch, nullptr); return hipGetLastError(); });
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("haze diagnostics: ") + hipGetErrorString(err));
+    *ms = mean;
     return VF_OK;
 }
 

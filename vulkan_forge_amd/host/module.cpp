@@ -913,6 +913,46 @@ public:
         check(vf_terrain_debug_sun_exposure_scans(t, &count));
         return count;
     }
+    // extension: atmospheric haze (argument rules: vulkan_forge_amd/_haze.py)
+    void set_haze(py::object density, py::object rgba, py::object start, py::object falloff, py::object base, py::object max_opacity,
+                  py::object background, py::object enabled)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._haze").attr("haze_args")(density, rgba, start, falloff, base, max_opacity, background, enabled);
+        uint8_t col[4];
+        py::tuple tc = a[2].cast<py::tuple>();
+        for (int k = 0; k < 4; ++k) col[k] = tc[k].cast<uint8_t>();
+        Borrow b(busy);
+        check(vf_terrain_set_haze(t, a[0].cast<int>(), a[1].cast<float>(), col, a[3].cast<float>(), a[4].cast<float>(), a[5].cast<float>(),
+                                  a[6].cast<float>(), a[7].cast<int>()));
+        frame_current = false;
+    }
+    void clear_haze()
+    {
+        Borrow b(busy);
+        check(vf_terrain_clear_haze(t));
+        frame_current = false;
+    }
+    py::object haze_info()
+    {
+        Borrow b(busy);
+        vf_haze_info v;
+        check(vf_terrain_haze_info(t, &v));
+        return py::module_::import("vulkan_forge_amd._haze").attr("haze_info")(
+            v.enabled, v.background, v.density, v.start, v.falloff, v.base, v.max_opacity,
+            py::make_tuple(v.rgba[0], v.rgba[1], v.rgba[2], v.rgba[3]), v.has_eye, v.eye_y);
+    }
+    // like render_depth it describes the frame for the current uniforms: drawn first unless the frame drawn last already is that frame
+    py::array_t<float> haze_opacity()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)SH, (py::ssize_t)SW });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        int rc = draw_current();
+        if (rc == VF_OK) rc = vf_terrain_read_haze_opacity(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1345,6 +1385,19 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "dict(enabled, suns (N), counted, weight_total, incidence, batch, softness, bias, high_rgba, low_rgba).")
         .def("debug_sun_exposure_batch", &T::debug_sun_exposure_batch, py::arg("batch") = 0)
         .def("debug_sun_exposure_scans", &T::debug_sun_exposure_scans)
+        .def("set_haze", &T::set_haze, py::arg("density"), py::kw_only(), py::arg("rgba") = py::make_tuple(200, 215, 235, 255), py::arg("start") = 0.0f,
+             py::arg("falloff") = py::none(), py::arg("base") = 0.0f, py::arg("max_opacity") = 1.0f, py::arg("background") = false,
+             py::arg("enabled") = true,
+             "Atmospheric haze (DESIGN.md 4q): blend `rgba` over the terrain with opacity 1 - exp(-density * path), the path being the\n"
+             "view depth beyond `start`.  falloff (world units of y): the density falls off exponentially with height above `base`;\n"
+             "None: uniform haze.  max_opacity caps the opacity; background: pixels without terrain take max_opacity, so the far edge of\n"
+             "the terrain fades into the sky.  Haze covers shadows, the drape and the tints; overlays are composited on top and are not\n"
+             "hazed.  Every parameter is stored by every call, also one that disables, and steers haze_opacity() too.")
+        .def("clear_haze", &T::clear_haze, "Haze off, its parameters the defaults again, its opacity plane freed.")
+        .def("haze_info", &T::haze_info, "dict: the haze settings as stored (falloff None: uniform) and eye_y, the eye's height for the current camera.")
+        .def("haze_opacity", &T::haze_opacity,
+             "(height, width) float32 (the sample size on a supersampled object): the haze opacity of every pixel of the current frame for\n"
+             "the stored settings, enabled or not; 0 where the pass leaves the pixel.")
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
