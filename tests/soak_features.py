@@ -7,22 +7,46 @@ tests/test_gpu_feature_soak.py (the GPU slice) and tests/test_feature_soak_cases
 
     case(seed)              a case description: pure numpy and the models' surface sampling, no GPU, no oracle
     CORNERS                 hand-written case descriptions: the edges that must not be left to the draw
-    expected(case, state)   the reference frame and planes of a handle state, composed from the models in the library's order:
-                            oracle frame -> ambient / shadow shade pass -> draped image -> overlays
+    expected(case, state)   the reference frame and planes of a handle state: the oracle's frame, the passes in the library's order,
+                            which supersample_model.chain alone writes down, then the overlays
     run(first, cases, ...)  the GPU side, case by case
 
+The late passes ride on the same handle, between the overlays and the mutation: the drape's mip pyramid and
+anisotropic taps, the viewshed, cumulative-viewshed and sun-exposure fields and tints, the haze; then a second mutation of their own,
+and for a case with a factor above 1 a supersampled second handle.  Steps A - E of run_case:
+    A  the three vertex fields, bit for bit, their passes off; the cumulative and exposure fields again at another batch size
+    B  the passes on in exact precision: the frame (twice), the haze opacity plane, drape_mip_info() and one pyramid level
+    C  fast precision.  The handle exposes no frame from between its passes, and needs none: the relight and drape passes write the
+       same bytes in either precision (step 3 found that without mips; with the mips and the anisotropic taps on it is asserted here,
+       not derived from step 3), and every other pixel is the plain fast frame's, so the fast frame before the late passes is known,
+       and the tints and the haze, which do not follow the precision, must give their models' bytes over it -- on written pixels and
+       others alike.  The pixels an overlay touches are left out of the colour comparison altogether, the 1 LSB bound included (the
+       overlays blend over bytes that may be 1 LSB off, and where a layer is opaque nothing of the frame beneath is left to compare);
+       the alpha channel is compared everywhere
+    D  the mutation (step 5) and the late mutation: the frame, and the rise of the three scan counters and of the pyramid's builds
+       against STALE_VIEWSHED, STALE_CUMULATIVE, STALE_EXPOSURE and MIP_BUILDS
+    E  supersample=f: the samples, the resolved frame under the overlays (none occluding) and the samples' visibility, again after the
+       late mutation
+
 usage: soak_features.py [first_seed] [cases] [time_budget_s]"""
-import math, os, sys, time, zlib
+import hashlib, math, os, sys, time, zlib
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model", "shadow_model", "ambient_model", "drape_model"):
+for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model", "shadow_model", "ambient_model", "drape_model",
+           "drape_mip_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "supersample_model", "haze_model"):
     sys.path.insert(0, os.path.join(HERE, _m))
 import numpy as np
 import ambient_model as abm  # noqa: E402
 import contour_model as cm  # noqa: E402
+import cumulative_viewshed_model as cvm  # noqa: E402
+import drape_mip_model as dmm  # noqa: E402
 import drape_model as drm  # noqa: E402
 import gbuffer_model as gbm  # noqa: E402
+import haze_model as hzm  # noqa: E402
 import shadow_model as shm  # noqa: E402
+import sun_exposure_model as sem  # noqa: E402
+import supersample_model as ssm  # noqa: E402
+import viewshed_model as vsm  # noqa: E402
 
 ocm = cm.ocm
 f32 = np.float32
@@ -43,6 +67,65 @@ DRAPE_SIZES = (1, 2, 3, 7, 37, 64, 255, 256, 257, 300)
 DRAPE_EXTENTS = ("whole", "interior", "overhanging", "one_side", "off_grid")
 DRAPE_FILTERS = ("linear", "nearest")
 DRAPE_STREAM = 0xD4A9E                                        # the drape's own generator is default_rng([seed, DRAPE_STREAM])
+# the late passes: the drape's mips and anisotropy, the three tints with their vertex fields, haze, supersampling.
+# Their generator is default_rng([seed, LATE_STREAM]): no key a case had before them depends on it (OLD_KEYS, digest)
+LATE_STREAM = 0x1A7E
+LATE_PASSES = ("mips", "viewshed", "cumulative", "exposure", "haze")
+LATE_MUTATIONS = ("observer_moves", "observer_same_vertex", "radius", "cumulative_reorder", "suns_reweight", "incidence_flip", "haze_off", "mips_off",
+                  "mips_bias", "anisotropy", "tint_colours_only", "heights_again")
+MIP_MUTATIONS = ("mips_off", "mips_bias", "anisotropy")
+MIP_BIASES = (0.0, -1.0, 1.5, 16.0, -16.0)
+ANISOTROPIES = (1, 2, 4, 8, 16)
+FACTORS = (1, 1, 2, 3, 4)
+OBSERVER_COUNTS = (1, 2, 7, 33)
+SUN_COUNTS = (1, 3, 12)
+OBSERVER_BATCHES = (0, 1, 3)
+SUN_BATCHES = (0, 1, 2)
+SOFTNESS = (1e-6, 0.02, 0.5)                                  # (the C ABI refuses a softness of 0: the hard edge is the smallest step that it takes)
+SAMPLE_CAP = 1 << 20                                          # f f W H above this: f = 1 (a bound on the cost of the CPU models, not a measurement)
+# which vertex fields vf_hip.h says a mutation (of either kind) makes stale, when the field's tint is on: the viewshed's after the
+# heights, the exaggeration, the observer's vertex or a scan parameter, not the colours, the radius, the camera or the sun; the
+# cumulative one's after the heights, the exaggeration, the observers' vertices or the radius in cells -- its key is the LIST of
+# vertices, compared bit for bit (DESIGN.md 4m item 6 with the cache rule of 4h), so the same observers in another order compute it
+# again unless the list of their vertices reads the same (run_case asks the model); the exposure's after the heights, the spacing, the
+# exaggeration, a sun, a weight, incidence, softness or bias, not the handle's own sun.  The pyramid is built by the first frame after
+# a new image (every set_drape call hands one over) or after enabling, if it has a level above 0, and by nothing else.
+STALE_VIEWSHED = ("heights", "exaggeration", "observer_moves", "heights_again")
+STALE_CUMULATIVE = ("heights", "exaggeration", "radius", "cumulative_reorder", "heights_again")
+STALE_EXPOSURE = ("heights", "exaggeration", "suns_reweight", "incidence_flip", "heights_again")
+MIP_BUILDS = ("drape_replace", "drape_opacity_zero")
+OLD_KEYS = ("name", "W", "H", "grid", "tex", "amp", "smooth", "nan_texel", "heights", "eye", "target", "fovy", "znear", "zfar", "exaggeration", "spacing", "sun",
+            "cmap", "mode", "mutation", "features", "shadows", "ambient", "overlays", "mutation_args", "drape")
+
+
+def _feed(h, v):
+    if isinstance(v, np.ndarray):
+        h.update(f"A{v.dtype.str}{v.shape}".encode())
+        h.update(np.ascontiguousarray(v).tobytes())
+    elif isinstance(v, dict):
+        h.update(f"D{len(v)}".encode())
+        for k in sorted(v):
+            _feed(h, k)
+            _feed(h, v[k])
+    elif isinstance(v, (list, tuple)):
+        h.update(f"L{len(v)}".encode())
+        for x in v:
+            _feed(h, x)
+    else:
+        if isinstance(v, np.generic):
+            v = v.item()
+        assert v is None or isinstance(v, (bool, int, float, str)), type(v)
+        h.update(f"S{type(v).__name__}:{v!r};".encode())
+
+
+def digest(cases, keys=OLD_KEYS):
+    """sha256 over `keys` of the cases, in order: names, types, values and the bytes of every array (dicts by sorted key)"""
+    h = hashlib.sha256()
+    for c in cases:
+        for k in keys:
+            _feed(h, k)
+            _feed(h, c[k])
+    return h.hexdigest()
 
 
 def _heights(rng, shape, amp, smooth):
@@ -211,9 +294,182 @@ def _drape(rng, must):
     return None if absent and not must else d
 
 
-def _make(rng, name, fix, drape_rng, draped=False):
+def vertex_xz(i, j, n, spacing, off=(0.0, 0.0)):
+    """world (x, z) of grid vertex (i, j) of n x n, `off` cells beside it"""
+    step = 3.0 / (n - 1)
+    return float(f32((-1.5 + (i + off[0]) * step) * spacing)), float(f32((-1.5 + (j + off[1]) * step) * spacing))
+
+
+def snap(c, observer):
+    """the vertex (i, j) the library snaps an observer of the case to"""
+    return vsm.observer_vertex(observer, max(f32(c["spacing"]), f32(1e-8)), max(c["grid"], 2))
+
+
+_NEEDS = {"observer_moves": "viewshed", "observer_same_vertex": "viewshed", "radius": "viewshed", "cumulative_reorder": "cumulative",
+          "suns_reweight": "exposure", "incidence_flip": "exposure", "haze_off": "haze", "mips_off": "mips", "mips_bias": "mips", "anisotropy": "mips"}
+
+
+def _late(rng, c, surf, fix, all_on=False):
+    """The late passes of a case, from their own generator -> (late, late_mutation, late_mutation_args).  `late`: mips (on / off as
+    `on` says), mip_bias, max_anisotropy, the parameters of viewshed, cumulative, exposure and haze as supersample_model.chain takes
+    them (cumulative and exposure with the batch size their field is read again at), `on` (which of LATE_PASSES are drawn), supersample.
+    fix["late"] is laid over the draw (a dict over a dict key by key); every corner has all passes on (`all_on`).  A seed's mutation
+    is the drawn one if it can show in the frame (can_show below), else the next of a drawn order that can."""
+    G, sp, W, H = c["grid"], c["spacing"], c["W"], c["H"]
+    n = max(G, 2)
+    D = c["drape"]
+    # a mutation of the mip sampling shows only where an image is left to sample after the case's first mutation
+    mips_ok = D is not None and c["mutation"] not in DRAPE_MUTATIONS and D["opacity"] > 0 and min(D["image"].shape[:2]) >= 7 and D["extent_kind"] != "off_grid"
+    eligible = [m for m in LATE_MUTATIONS if m not in MIP_MUTATIONS or mips_ok]
+    # (the mip mutations are open to fewer cases and get three lots each)
+    lots = np.array([3.0 if m in MIP_MUTATIONS else 1.0 for m in eligible])
+    kind = eligible[int(rng.choice(len(eligible), p=lots / lots.sum()))]
+    kind = fix.get("late_mutation", kind)
+    radii = (None, 0.4 * sp, 1.2 * sp, 10.0)
+    nanv = np.argwhere(np.isnan(surf))                        # (j, i) of the vertices without a height
+
+    def observers(k):
+        return rng.uniform(-1.9 * sp, 1.9 * sp, (k, 2)).astype(f32)       # the terrain spans +-1.5 spacing: beyond it an observer is clamped
+
+    def on_nan():
+        j, i = nanv[int(rng.integers(0, len(nanv)))]
+        return vertex_xz(int(i), int(j), n, sp)
+
+    def scan():
+        return dict(eye_height=float(rng.choice([0.0, 0.05, 1.0])), target_height=float(rng.choice([0.0, 0.02])), softness=float(rng.choice(SOFTNESS)),
+                    bias=float(rng.choice([0.0, 0.002, 0.05])))
+
+    def radius(but=()):
+        """one of `radii`; `but`: another than these, and a short one unless one of these is short (a change that shows)"""
+        short = any(r in radii[1:3] for r in but) or not but
+        pick = [r for r in radii if r not in but and (short or r in radii[1:3])]
+        return pick[int(rng.integers(0, len(pick)))]
+
+    def colours():
+        """(high / visible, low / hidden): the low one mostly with alpha 0, as the defaults have it, so that the tint leaves what
+        nobody sees and no sun reaches as it was"""
+        return _rgba(rng, int(rng.choice([255, 160, 96, 0], p=[0.3, 0.3, 0.3, 0.1]))), _rgba(rng, int(rng.choice([0, 255, 96], p=[0.6, 0.2, 0.2])))
+
+    def weights(k, up):
+        w = rng.random(k).astype(f32)
+        if k > 1 and up.any():
+            w[int(rng.choice(np.flatnonzero(up)))] = 0.0       # one exact 0, on a sun that counts
+        return w
+
+    L = dict(mip_bias=float(rng.choice(MIP_BIASES)), max_anisotropy=int(rng.choice(ANISOTROPIES)))
+    o = observers(1)[0]
+    if len(nanv) and (rng.random() < 0.5 or fix.get("observer_on_nan")):
+        o = on_nan()
+    a, b = colours()
+    L["viewshed"] = dict(observer=(float(o[0]), float(o[1])), radius=radius(), visible_rgba=a, hidden_rgba=b, **scan())
+    N = int(rng.choice(OBSERVER_COUNTS))
+    if kind == "cumulative_reorder":
+        N = max(N, 7)                                         # (two observers that duplicate each other have one order)
+    obs = observers(N)
+    order = rng.permutation(N)
+    if N > 1:
+        obs[order[0]] = obs[order[1]]                         # one duplicates another
+    if len(nanv):
+        obs[order[-1]] = on_nan()
+    a, b = colours()
+    # (mostly a short radius: the count is 0 over part of the ground, and the tint leaves it as it was)
+    L["cumulative"] = dict(observers=obs, radius=(radii + radii[1:3])[int(rng.integers(0, 6))], high_rgba=a, low_rgba=b, batch=int(rng.choice(OBSERVER_BATCHES)), **scan())
+    N = int(rng.choice(SUN_COUNTS))
+    # (a day's arc: low suns on one side of the sky, whose shadows overlap and leave part of the ground without any sun)
+    el, az = rng.uniform(2.0, 25.0, N), rng.uniform(0.0, 360.0) + rng.uniform(-15.0, 15.0, N)
+    if N > 1:
+        el[int(rng.integers(0, N))] = -rng.uniform(1.0, 30.0)  # one below the horizon
+    a, b = colours()
+    L["exposure"] = dict(suns=np.array([shm.sun_vector(e, z) for e, z in zip(el, az)], f32), weights=weights(N, el > 0) if rng.random() < 0.6 else None,
+                         incidence=bool(rng.random() < 0.7), softness=float(rng.choice(SOFTNESS)), bias=float(rng.choice([0.0, 0.002, 0.05])),
+                         high_rgba=a, low_rgba=b, batch=int(rng.choice(SUN_BATCHES)))
+    falloff = [None, 0.3, 4.0][int(rng.integers(0, 3))]
+    L["haze"] = dict(density=float(rng.choice([0.05, 0.5, 5.0])), start=float(rng.choice([0.0, 0.5 * float(np.linalg.norm(c["eye"]))])), falloff=falloff,
+                     base=float(rng.choice([1.0, 0.6])), max_opacity=float(rng.choice([1.0, 0.6])), background=bool(rng.random() < 0.5), rgba=_rgba(rng))
+    on = [p for p in LATE_PASSES if rng.random() < (2.0 / 3.0 if p == "mips" else 0.6)]
+    rest = [p for p in rng.permutation(LATE_PASSES) if p not in on]
+    on += [str(p) for p in rest[:max(0, 2 - len(on))]]         # at least two
+    f = int(rng.choice(FACTORS))
+    for k, v in fix.get("late", {}).items():
+        L[k] = dict(L[k], **v) if isinstance(v, dict) else v
+    f = L.get("supersample", 1 if all_on else f)
+    L["supersample"] = 1 if f * max(W, H) > 16384 or f * f * W * H > SAMPLE_CAP else f
+    # the mutation's payload (after the corner's own values: an observer moves from where it is)
+    V = L["viewshed"]
+    v0 = snap(c, V["observer"])
+    moved = V["observer"]
+    for _ in range(64):
+        moved = tuple(float(v) for v in observers(1)[0])
+        if snap(c, moved) != v0:
+            break
+    else:
+        moved = vertex_xz(n - 1 - v0[0], n - 1 - v0[1], n, sp)
+    same = [p for p in (vertex_xz(v0[0], v0[1], n, sp, off) for off in ((0.2, 0.2), (-0.2, -0.2), (0.2, -0.2), (-0.2, 0.2)))
+            if snap(c, p) == v0 and p != tuple(V["observer"])]
+    t2 = (int(rng.integers(1, 80)), int(rng.integers(1, 80)))
+    E = L["exposure"]
+    args = dict({
+        "radius": dict(viewshed=radius((V["radius"],)), cumulative=radius((L["cumulative"]["radius"],))),
+        "order": np.roll(np.arange(len(L["cumulative"]["observers"])), 1),
+        "weights": weights(len(E["suns"]), E["suns"][:, 1] > 0),
+        "mip_bias": -16.0 if L["mip_bias"] > 0 else 16.0,
+        "max_anisotropy": 16 if L["max_anisotropy"] == 1 else 1,
+        "colours": dict(viewshed=colours(), cumulative=colours(), exposure=colours()),
+        "heights": _heights(rng, t2, float(rng.choice([0.2, 1.0, 3.0])), bool(rng.random() < 0.5)),
+    }, **fix.get("late_mutation_args", {}))
+    # A mutation must show in the frame (the two that must not aside; tests/test_feature_soak_cases.py asserts both), so a seed whose
+    # drawn one cannot -- by what the vertex field models say of the surface the handle holds after the case's first mutation, no
+    # frame needed -- takes the next of a drawn order that can.  A corner's mutation is written down and stays
+    h1 = c["mutation_args"]["heights"] if c["mutation"] == "heights" else c["heights"]
+    u1 = np.zeros(44, f32)
+    u1[36], u1[38] = sp, c["mutation_args"]["exaggeration"] if c["mutation"] == "exaggeration" else c["exaggeration"]
+
+    def tints(hi, lo):
+        return tuple(hi) != tuple(lo) and (hi[3] > 0 or lo[3] > 0)
+
+    def can_show(k):
+        X = L["exposure"]
+        if k == "cumulative_reorder":
+            return len(L["cumulative"]["observers"]) >= 7
+        if k == "observer_same_vertex":
+            return bool(same)
+        if k == "anisotropy":                                 # (at a bias of 16 every tap reads the one texel of the coarsest level)
+            return L["mip_bias"] < 16.0
+        if k in ("heights_again", "radius") and u1[38] == 0.0:   # (a surface without relief is the same under any heights, and all of it
+            return False                                      # is seen from anywhere: of a radius only the rim of the disc would move)
+        if k in ("observer_moves", "radius"):
+            seen = vsm.field(u1, h1, G, V["observer"], **{q: V[q] for q in _SCAN})[0]
+            if k == "observer_moves":
+                return tints(V["visible_rgba"], V["hidden_rgba"]) and bool((vsm.field(u1, h1, G, moved, **{q: V[q] for q in _SCAN})[0] != seen).any())
+            ring = np.logical_xor(*[np.ones((n, n), bool) if r is None else cvm.in_range(n, v0, cvm.rc(r, max(f32(sp), f32(1e-8)), n)) for r in (V["radius"], args["radius"]["viewshed"])])
+            return bool((ring & (((seen > 0) & (V["visible_rgba"][3] > 0)) | ((seen < 1) & (V["hidden_rgba"][3] > 0)))).any())
+        if k in ("suns_reweight", "incidence_flip"):
+            after = dict(X, weights=args["weights"]) if k == "suns_reweight" else dict(X, incidence=not X["incidence"])
+            share = []
+            for Y in (X, after):
+                wtot = sem.weight_total(Y["suns"], Y["weights"])
+                if not wtot > 0:
+                    return False
+                share.append(sem.fraction(sem.field(u1, h1, G, Y["suns"], Y["weights"], incidence=Y["incidence"], softness=Y["softness"], bias=Y["bias"]), wtot))
+            return tints(X["high_rgba"], X["low_rgba"]) and bool((share[0] != share[1]).any())
+        return True
+
+    if "late_mutation" not in fix:
+        order = [eligible[i] for i in rng.permutation(len(eligible))]
+        kind = next(k for k in [kind] + order if can_show(k))
+    args["observer"] = {"observer_moves": moved, "observer_same_vertex": same[0] if same else tuple(V["observer"])}.get(kind)
+    if kind in _NEEDS and _NEEDS[kind] not in on:
+        on.append(_NEEDS[kind])
+    if kind == "tint_colours_only" and not {"viewshed", "cumulative", "exposure"} & set(on):
+        on.append("viewshed")
+    L["on"] = LATE_PASSES if all_on else tuple(p for p in LATE_PASSES if p in on)
+    return L, kind, args
+
+
+def _make(rng, name, fix, drape_rng, draped=False, late_rng=None):
     """A case description; `fix` overrides what the draw would choose (CORNERS).  The drape comes from `drape_rng`, a generator of
-    its own: what `rng` gives a seed or a corner does not depend on it; `draped`: never without one (every corner)."""
+    its own: what `rng` gives a seed or a corner does not depend on it; `draped`: never without one (every corner).  The late
+    passes come from `late_rng` in the same way."""
     c = {"name": name}
 
     def put(key, draw):
@@ -280,6 +536,7 @@ def _make(rng, name, fix, drape_rng, draped=False):
     # the draped image: drawn whole, then a corner's own fields laid over it (its "replace" replaces the payload whole)
     d = _drape(drape_rng, draped or mutation in DRAPE_MUTATIONS)
     c["drape"] = None if d is None else dict(d, **fix.get("drape", {}))
+    c["late"], c["late_mutation"], c["late_mutation_args"] = _late(late_rng, c, surf, fix, all_on=draped)
     return c
 
 
@@ -287,7 +544,8 @@ def case(seed):
     """The case of a seed: frame, grid, texture, camera and uniforms drawn as test_random_scenes_fuzz draws them, a sun, colormap,
     shade mode, shadow and ambient parameters, which of them are on, the overlay calls, one mutation and (from a generator of its
     own) a draped image or none."""
-    return _make(np.random.default_rng(seed), f"seed{seed}", {"mutation": MUTATIONS[seed % len(MUTATIONS)]}, np.random.default_rng([seed, DRAPE_STREAM]))
+    return _make(np.random.default_rng(seed), f"seed{seed}", {"mutation": MUTATIONS[seed % len(MUTATIONS)]}, np.random.default_rng([seed, DRAPE_STREAM]),
+                 late_rng=np.random.default_rng([seed, LATE_STREAM]))
 
 
 _CAMERA = dict(eye=(3.0, 2.0, 3.0), target=(0.0, 0.0, 0.0), fovy=45.0, znear=0.1, zfar=100.0)
@@ -306,7 +564,19 @@ def _build(k, name, fix):
     base.update(fix)
     if "spacing" in fix and "eye" not in fix:                 # keep the terrain in view
         base["eye"] = tuple(v * fix["spacing"] for v in _CAMERA["eye"])
-    return _make(np.random.default_rng(90000 + k), name, base, np.random.default_rng([90000 + k, DRAPE_STREAM]), draped=True)
+    # the late passes of a corner: the haze begins at the eye's distance from its target, about the middle of the terrain's depths, so
+    # that it writes part of the frame; a short radius and the incidence cosine leave part of the ground to the other two tints;
+    late = {"haze": dict(start=float(np.linalg.norm(np.subtract(base["eye"], base["target"]))), density=0.5),
+            "cumulative": dict(radius=0.4 * base["spacing"], high_rgba=cvm.DEFAULT_HIGH, low_rgba=cvm.DEFAULT_LOW),
+            # (one low sun, whose long shadows leave part of the ground without any, and one below the horizon)
+            "exposure": dict(suns=np.array([shm.sun_vector(6.0, 40.0 * k), shm.sun_vector(-10.0, 40.0 * k + 180.0)], f32), weights=None, incidence=True,
+                             high_rgba=sem.DEFAULT_HIGH, low_rgba=sem.DEFAULT_LOW),
+            "viewshed": dict(visible_rgba=vsm.DEFAULT_VISIBLE, hidden_rgba=vsm.DEFAULT_HIDDEN)}   # (translucent: no tint hides the passes under it)
+    for key, v in fix.get("late", {}).items():
+        late[key] = dict(late.get(key, {}), **v) if isinstance(v, dict) else v
+    base["late"] = late
+    return _make(np.random.default_rng(90000 + k), name, base, np.random.default_rng([90000 + k, DRAPE_STREAM]), draped=True,
+                 late_rng=np.random.default_rng([90000 + k, LATE_STREAM]))
 
 
 def _amb(reach, dirs, strength=0.6):
@@ -380,7 +650,54 @@ _SPECS = [
             drape=dict(image=distinct_image(64, 37), extent=(-0.7, -0.5, 0.9, 0.8), extent_kind="interior", opacity=1.0, filter="nearest")),
     _corner(28, "drape_denser_than_the_frame", W=15, H=17, mutation="drape_clear", ambient=_amb(16.0, _FAN),
             drape=dict(image=drape_image(np.random.default_rng(28), 300, 300, 4), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
+    # the late passes' own edges (tests/test_feature_soak_cases.py asserts what each is named for): every pass on,
+    # the soak's small frames except where the edge is the frame
+    # (the four vertices of grid 2 all see each other: the radius, which reaches along the sides and not across the diagonal, is
+    # what shows that the observer moved)
+    _corner(30, "late_grid2_observer_on_a_corner_vertex", grid=2, W=33, H=31, tex=(2, 2), ambient=_amb(1.0, _round(4)), late_mutation="observer_moves",
+            late=dict(viewshed=dict(observer=(-1.5, -1.5), eye_height=0.05, radius=3.5))),
+    _corner(31, "late_grid3_thirty_three_observers", grid=3, W=33, H=31, ambient=_amb(16.0, _FAN), late_mutation="cumulative_reorder",
+            late=dict(cumulative=dict(observers=np.random.default_rng(31).uniform(-1.9, 1.9, (33, 2)).astype(f32), batch=3))),
+    _corner(32, "late_all_nan_texture", W=33, H=31, heights=np.full((5, 6), np.nan, f32), ambient=_amb(16.0, _round(8)), mutation="heights", late_mutation="suns_reweight",
+            late=dict(cumulative=dict(radius=None), exposure=dict(incidence=False))),    # (no radius: every observer counts everywhere; no cosine: that of a NaN is 0)
+    _corner(33, "late_observer_on_the_nan_vertex", W=48, H=40, tex=(9, 7), nan_texel=True, ambient=_amb(16.0, _FAN), observer_on_nan=True, late_mutation="observer_same_vertex"),
+    _corner(34, "late_exaggeration0_eye_height0", W=48, H=40, exaggeration=0.0, ambient=_amb(16.0, _round(8)), mutation="exaggeration", mutation_args={"exaggeration": 1.5},
+            late_mutation="tint_colours_only", late=dict(viewshed=dict(eye_height=0.0), cumulative=dict(eye_height=0.0))),
+    _corner(35, "late_exaggeration_minus2", W=48, H=40, exaggeration=-2.0, ambient=_amb(16.0, _FAN), late_mutation="heights_again"),
+    _corner(36, "late_frame_of_one_column", W=1, H=70, grid=17, ambient=_amb(16.0, _FAN), late_mutation="incidence_flip"),
+    # (a field of view of 0.3 degrees over the one row's height: its 130 pixels run across the terrain through the target)
+    _corner(37, "late_frame_of_one_row", W=130, H=1, grid=16, fovy=0.3, ambient=_amb(1.5, _round(3)), late_mutation="haze_off"),
+    # the camera of drape_near_plane_through_the_terrain: the tints and the haze read the interpolated position of clipped primitives
+    _corner(38, "late_near_plane_through_the_terrain", grid=9, eye=(0.9, 0.7, 0.8), target=(-0.4, -0.2, -0.3), znear=0.4, fovy=60.0,
+            ambient=_amb(16.0, _FAN, strength=0.6), late_mutation="radius",
+            drape=dict(image=distinct_image(37, 64), extent=(-0.9, -1.0, 0.6, 0.7), extent_kind="interior", opacity=0.37, filter="linear"),
+            late=dict(viewshed=dict(observer=(-0.4, -0.3), eye_height=1.0, radius=None, visible_rgba=(40, 250, 90, 160), hidden_rgba=(250, 30, 30, 96)),
+                      cumulative=dict(radius=None, high_rgba=(30, 60, 250, 160), low_rgba=(0, 0, 0, 0)), haze=dict(start=0.0, density=0.5, falloff=None))),
+    _corner(39, "late_sky_camera_haze_on_the_background", W=48, H=40, eye=(3.0, 2.0, 3.0), target=(3.6, 4.0, 3.4), ambient=_amb(16.0, _FAN), late_mutation="haze_off",
+            late=dict(haze=dict(background=True, rgba=(200, 215, 235, 255), max_opacity=0.6))),
+    _corner(40, "late_every_sun_below_the_horizon", W=48, H=40, ambient=_amb(16.0, _FAN), late_mutation="tint_colours_only",
+            late=dict(exposure=dict(suns=np.array([shm.sun_vector(-5.0, 20.0), shm.sun_vector(-40.0, 200.0), (0.3, 0.0, 1.0)], f32), weights=None))),
+    # (a cell of grid 9 is 0.375 wide: a disc of some six pixels around the observer's vertex)
+    _corner(41, "late_radius_below_one_cell", grid=9, ambient=_amb(16.0, _FAN), late_mutation="observer_moves",
+            late=dict(viewshed=dict(radius=0.3, observer=(0.1, -0.2), visible_rgba=(40, 250, 90, 255)), cumulative=dict(radius=0.3))),
+    _corner(42, "late_drape_1x1_mips_on", W=48, H=40, ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="observer_moves",
+            drape=dict(image=np.array([[(200, 90, 33, 180)]], np.uint8), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
+    _corner(43, "late_dense_drape_bias_minus16", W=15, H=17, ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="mips_bias", late_mutation_args={"mip_bias": 3.0},
+            late=dict(mip_bias=-16.0, max_anisotropy=1),
+            drape=dict(image=dmm.case_image(43, (300, 300)), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
+    _corner(44, "late_dense_drape_bias_16", W=15, H=17, ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="mips_bias", late_mutation_args={"mip_bias": -16.0},
+            late=dict(mip_bias=16.0, max_anisotropy=1),
+            drape=dict(image=dmm.case_image(43, (300, 300)), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
+    _corner(45, "late_anisotropy16_grazing_camera", W=48, H=40, eye=(3.2, 0.45, 0.3), ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="anisotropy",
+            late=dict(mip_bias=0.0, max_anisotropy=16),
+            # (the image stretched sixteenfold along z under the low eye: footprints longer than sixteen times their width)
+            drape=dict(image=dmm.case_image(45, (300, 256)), extent=(-1.5, -24.0, 1.5, 24.0), extent_kind="stretched", opacity=1.0, filter="linear")),
+    _corner(46, "late_supersample4_frame1x1", W=1, H=1, ambient=_amb(16.0, _FAN), late_mutation="incidence_flip", late=dict(supersample=4)),
+    _corner(47, "late_supersample3_frame15x17", W=15, H=17, ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="mips_off",
+            late=dict(supersample=3, max_anisotropy=8, mip_bias=0.0),
+            drape=dict(image=dmm.case_image(43, (300, 300)), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
 ]
+OLD_CORNERS = 29                                              # the corners older than the late passes: their old keys are pinned (digest)
 
 
 class _Corners:
@@ -434,7 +751,63 @@ def uniforms(c, sun=None, exaggeration=None):
 def initial_state(c):
     """the handle's state before any feature is on: what `expected` and `run` step through"""
     return dict(heights=c["heights"], u=uniforms(c), shadows=False, ambient=False, shadow_params=dict(c["shadows"]), ambient_params=dict(c["ambient"]),
-                overlays=False, occlusion={}, drape=None)
+                overlays=False, occlusion={}, drape=None, late=None)
+
+
+def lated(c, state):
+    """the state with the case's late passes on: mips (with the bias), max_anisotropy, and for each of viewshed, cumulative,
+    exposure and haze its parameters, or None while it is off"""
+    L = c["late"]
+    return dict(state, late=dict(mips="mips" in L["on"], mip_bias=L["mip_bias"], max_anisotropy=L["max_anisotropy"],
+                                 **{p: dict(L[p]) if p in L["on"] else None for p in LATE_PASSES[1:]}))
+
+
+def late_mutated(c, state):
+    """the state (with its late passes on) after the case's late mutation"""
+    kind, a = c["late_mutation"], c["late_mutation_args"]
+    L = dict(state["late"])
+    s = dict(state, late=L)
+    if kind in ("observer_moves", "observer_same_vertex"):
+        L["viewshed"] = dict(L["viewshed"], observer=a["observer"])
+    elif kind == "radius":
+        L["viewshed"] = dict(L["viewshed"], radius=a["radius"]["viewshed"])
+        if L["cumulative"] is not None:
+            L["cumulative"] = dict(L["cumulative"], radius=a["radius"]["cumulative"])
+    elif kind == "cumulative_reorder":
+        L["cumulative"] = dict(L["cumulative"], observers=np.ascontiguousarray(L["cumulative"]["observers"][a["order"]]))
+    elif kind == "suns_reweight":
+        L["exposure"] = dict(L["exposure"], weights=a["weights"])
+    elif kind == "incidence_flip":
+        L["exposure"] = dict(L["exposure"], incidence=not L["exposure"]["incidence"])
+    elif kind == "haze_off":
+        L["haze"] = None
+    elif kind == "mips_off":
+        L["mips"] = False
+    elif kind == "mips_bias":
+        L["mip_bias"] = a["mip_bias"]
+    elif kind == "anisotropy":
+        L["max_anisotropy"] = a["max_anisotropy"]
+    elif kind == "tint_colours_only":
+        for p, (hi, lo) in (("viewshed", ("visible_rgba", "hidden_rgba")), ("cumulative", ("high_rgba", "low_rgba")), ("exposure", ("high_rgba", "low_rgba"))):
+            if L[p] is not None:
+                L[p] = dict(L[p], **dict(zip((hi, lo), a["colours"][p])))
+    elif kind == "heights_again":
+        s["heights"] = a["heights"]
+    return s
+
+
+def chain_features(c, state):
+    """the state as the features of supersample_model.chain"""
+    A, D, L = state["ambient_params"], state["drape"], state["late"] or {}
+    drape = None if D is None else dict(D, mips=bool(L.get("mips")), bias=L.get("mip_bias", 0.0), max_anisotropy=L.get("max_anisotropy", 1))
+    return dict(shade_mode=c["mode"], shadows=dict(state["shadow_params"]) if state["shadows"] else None, ambient=dict(A) if state["ambient"] else None,
+                drape=drape, exposure=L.get("exposure"), cumulative=L.get("cumulative"), viewshed=L.get("viewshed"),
+                haze=L.get("haze"))
+
+
+def unoccluded(c):
+    """the case with no overlay layer occluding: what a supersampled handle accepts (include/vf_hip.h)"""
+    return dict(c, overlays=[(kind, dict(kw, occlude=False) if "occlude" in kw else kw) for kind, kw in c["overlays"]])
 
 
 def the_drape(d):
@@ -508,20 +881,20 @@ def layers(c, state):
 
 
 def expected(c, state, cache=None):
-    """The reference of a handle state, in the order the library documents: the oracle's frame and visibility; the shade pass
-    (ambient_model.frame with the shadow field when both are on, shadow_model.frame for shadows alone); the overlays
-    the draped image over that frame (drape_model.frame, with the state's shadow and sky-view fields and strength when those
-    features are on); the overlays (occlusion_model.composite of the contour model's layers).  `cache` (a dict of one case) keeps
-    the oracle's frames and the results, for a caller that asks for a state twice.  -> dict rgba (the oracle's frame), vis, shaded,
-    mask (the pixels the shade pass writes again), draped (the frame behind the drape pass: `shaded` without a drape), drape_mask
-    (the pixels the drape writes again), frame (what the handle must show), layers (or None)."""
+    """The reference of a handle state: the oracle's frame and visibility, then the passes in the library's order, which is written
+    down once, in supersample_model.chain (the relight pass, the draped image through its mips and anisotropic taps, the exposure,
+    cumulative and viewshed tints, the haze), then the overlays (occlusion_model.composite of the contour model's layers).  `cache` (a
+    dict of one case) keeps the oracle's frames, the vertex fields and the results, for a caller that asks for a state twice.
+    -> dict rgba (the oracle's frame), vis, shaded, mask (the pixels the shade pass writes again), draped (the frame behind the drape
+    pass: `shaded` without a drape), drape_mask (the pixels the drape writes again), late (the frame behind the last late pass:
+    `draped` without one), haze_opacity, stages (everything chain records), frame (what the handle must show), layers (or None)."""
     import oracle
     W, H, G, h, u = c["W"], c["H"], c["grid"], state["heights"], state["u"]
     key = (u.tobytes(), h.tobytes(), h.shape)
     A, D = state["ambient_params"], state["drape"]
     whole = (key, state["shadows"], state["ambient"], state["overlays"], tuple(sorted(state["shadow_params"].items())),
              A["strength"], A["reach"], A["directions"].tobytes(), tuple(sorted(state["occlusion"].items())),
-             None if D is None else (D["image"].tobytes(), D["image"].shape, D["extent"], D["opacity"], D["filter"]))
+             None if D is None else (D["image"].tobytes(), D["image"].shape, D["extent"], D["opacity"], D["filter"]), ssm._key(state["late"]))
     if cache is not None and whole in cache:
         return cache[whole]
     if cache is not None and key in cache:
@@ -531,32 +904,27 @@ def expected(c, state, cache=None):
         rgba = rgba.reshape(H, W, 4)
         if cache is not None:
             cache[key] = (rgba, vis)
-    out = {"rgba": rgba, "vis": vis, "shaded": rgba, "mask": np.zeros((H, W), bool), "layers": None}
-    shade = ("shade",) + whole[:3] + whole[4:8]               # the fields and the shade pass: the same under any drape and any overlays
-    if cache is not None and shade in cache:
-        lit, sky, out["shaded"], out["mask"] = cache[shade]
-    else:
-        lit = shm.field(u, h, G, **state["shadow_params"]) if state["shadows"] else None
-        sky = None
-        if state["ambient"]:
-            sky = abm.field(u, h, G, A["directions"], A["reach"])
-            out["shaded"], out["mask"] = abm.frame(rgba, vis, u, h, G, lut(c["cmap"]), sky, A["strength"], lit=lit, shade_mode=c["mode"])
-        elif state["shadows"]:
-            out["shaded"], out["mask"] = shm.frame(rgba, vis, u, h, G, lut(c["cmap"]), lit, shade_mode=c["mode"])
-        if cache is not None:
-            cache[shade] = (lit, sky, out["shaded"], out["mask"])
-    out["draped"], out["drape_mask"] = out["shaded"], np.zeros((H, W), bool)
-    if D is not None:
-        out["draped"], out["drape_mask"] = drm.frame(out["shaded"], vis, u, h, G, lut(c["cmap"]), D["image"], extent=D["extent"], opacity=D["opacity"],
-                                                     filter=D["filter"], lit=lit, sky=sky, strength=A["strength"],
-                                                     shade_mode=c["mode"])
-    out["frame"] = out["draped"]
+    st = {}
+    late = ssm.chain(rgba, vis, u, h, G, lut(c["cmap"]), stages=st, memo=cache, **chain_features(c, state))
+    out = {"rgba": rgba, "vis": vis, "shaded": st["shaded"], "mask": st["mask"], "draped": st["draped"], "drape_mask": st["drape_mask"], "late": late,
+           "haze_opacity": st["haze_opacity"], "stages": st, "frame": late, "layers": None}
     if state["overlays"]:
         out["layers"] = layers(c, state)
-        out["frame"] = ocm.composite(out["draped"], vis, u, h, G, out["layers"])
+        out["frame"] = ocm.composite(late, vis, u, h, G, out["layers"])
     if cache is not None:
         cache[whole] = out
     return out
+
+
+def expected_supersampled(c, state, f, cache=None):
+    """The reference of a handle made with supersample=f in `state` (no layer occluding): the same chain at (f W, f H), the resolve,
+    the overlays at (W, H) -> dict samples, vis (both at the sample size), haze_opacity, resolved, frame"""
+    u, h, G = state["u"], state["heights"], c["grid"]
+    st = {}
+    s, vis = ssm.samples(c["W"], c["H"], f, u, h, G, lut(c["cmap"]), stages=st, memo=cache, **chain_features(c, state))
+    resolved = ssm.resolve(s, f)
+    L = layers(unoccluded(c), dict(state, occlusion={})) if state["overlays"] else None
+    return dict(samples=s, vis=vis, haze_opacity=st["haze_opacity"], resolved=resolved, frame=ssm.composite(resolved, u, h, G, L))
 
 
 def planes(c, state, vis):
@@ -577,6 +945,50 @@ def shares(c, cache=None):
                 draped=(int(d.sum()) / covered) if covered and c["drape"] is not None else None,
                 masks_cross=bool((m & d).any() and (m & ~d).any() and (d & ~m).any()),
                 overlays_show=bool((e["frame"] != e["draped"]).any()))
+
+
+def late_shares(c, cache=None):
+    """what the reference alone says about a case's late passes: on; covered (pixels); changed: per pass that is on, the share of
+    the covered pixels it changes (mips: against the same drape sampled without them; None without a covered pixel, and for mips
+    without a drape); field_mixed: the viewshed field has values below 0.5 and values of 1; haze_partial: an opacity strictly between
+    0 and max_opacity; lod_above_0: a draped pixel samples above level 0; many_taps: a draped pixel takes more than one tap;
+    covered_before_late_mutation (pixels, in the state after the case's first mutation, where run_case applies the late one);
+    mutation_shows: the frame behind the late passes (under the overlays, whose draw is older and may cover anything) differs after
+    the late mutation from the one before it"""
+    L = c["late"]
+    s1 = featured(c, initial_state(c), overlays=True)
+    s2 = lated(c, s1)
+    e1, e2 = expected(c, s1, cache), expected(c, s2, cache)
+    st, cov = e2["stages"], e2["vis"] != 0
+    covered = int(cov.sum())
+    changed, before = {}, e2["draped"]
+    if "mips" in L["on"]:
+        changed["mips"] = int(((e2["draped"] != e1["draped"]).any(axis=2) & cov).sum()) / covered if covered and c["drape"] is not None else None
+    for p in ("exposure", "cumulative", "viewshed", "haze"):
+        if p in L["on"]:
+            changed[p] = int(((st[p + "_frame"] != before).any(axis=2) & cov).sum()) / covered if covered else None
+            before = st[p + "_frame"]
+    seen = st.get("viewshed_field")
+    a, smp, m = e2["haze_opacity"], st["drape_sample"], e2["drape_mask"]
+    s3 = mutated(c, s2)
+    e3 = expected(c, s3, cache)
+    return dict(on=L["on"], supersample=L["supersample"], covered=covered, changed=changed,
+                field_mixed=None if seen is None else bool((seen < 0.5).any() and (seen == 1).any()),
+                haze_partial=bool(((a > 0) & (a < f32(L["haze"]["max_opacity"]))).any()) if "haze" in L["on"] else None,
+                lod_above_0=None if smp is None or not m.any() else bool((smp[m][:, 6] > 0).any()),
+                many_taps=None if smp is None or smp.shape[2] < 10 or not m.any() else bool((smp[m][:, 7] > 1).any()),
+                covered_before_late_mutation=int((e3["vis"] != 0).sum()),
+                mutation_shows=bool((expected(c, late_mutated(c, s3), cache)["late"] != e3["late"]).any()))
+
+
+def describe_late(stat):
+    """the late passes' shares over a list of late_shares() results, as text"""
+    out = []
+    for p in LATE_PASSES:
+        ch = [s["changed"][p] for s in stat if s["changed"].get(p) is not None]
+        out.append(f"{p} on in {sum(p in s['on'] for s in stat)} of {len(stat)}, changes a pixel in {sum(v > 0 for v in ch)} and 10-90 % in "
+                   f"{sum(0.1 < v < 0.9 for v in ch)} of {len(ch)} covered")
+    return "; ".join(out)
 
 
 # ---- the GPU side ----------------------------------------------------------------------------------------------------
@@ -716,9 +1128,62 @@ def run_case(c, seed=None, cache=None):
         differ(4, "frame drawn again", (frame(t) != e["frame"]).any(axis=2))
         compare_planes(4, state, e["vis"])                    # (the planes and the visibility know nothing of the drape)
         differ(4, "visibility", t.read_visibility() != e["vis"])
-        # 5. the mutation
+        # A. the late passes' vertex fields: their parameters set, the passes off
+        P, u, h, lut_ = c["late"], state["u"], state["heights"], lut(c["cmap"])
+        _set_late(t, c, state)
+        V, M, X = P["viewshed"], P["cumulative"], P["exposure"]
+        seen, vtx = vsm.field(u, h, G, V["observer"], **{k: V[k] for k in _SCAN})
+        differ("A", "viewshed field", _bits(t.viewshed_field()) != _bits(seen))
+        info, n = t.viewshed_info(), max(G, 2)
+        with np.errstate(invalid="ignore"):
+            xyz = (vertex_xz(vtx[0], vtx[1], n, c["spacing"])[0], float(shm.heights(u, h, G)[vtx[1], vtx[0]] * u[38]), vertex_xz(vtx[0], vtx[1], n, c["spacing"])[1])
+        # (the position has no bit-exact statement in the contract: the model's vertex, and its place to a few binary32 steps)
+        if info["vertex"] != tuple(vtx) or not np.allclose(info["observer_xyz"], xyz, rtol=1e-5, atol=1e-6, equal_nan=True):
+            bad.append((seed, "A", f"viewshed_info() vertex {info['vertex']} at {info['observer_xyz']} against {tuple(vtx)} at {xyz}", 1, []))
+        cnt, verts = cvm.field(u, h, G, M["observers"], radius=M["radius"], **{k: M[k] for k in _SCAN})
+        differ("A", "cumulative viewshed field", _bits(t.cumulative_viewshed_field()) != _bits(cnt))
+        if t.cumulative_viewshed_info()["vertices"].tolist() != [list(v) for v in verts]:
+            bad.append((seed, "A", "cumulative_viewshed_info() vertices against the model's", 1, []))
+        t.cumulative_viewshed_batch(M["batch"])
+        differ("A", f"cumulative viewshed field at batch size {M['batch']}", _bits(t.cumulative_viewshed_field()) != _bits(cnt))
+        expo = sem.field(u, h, G, X["suns"], X["weights"], incidence=X["incidence"], softness=X["softness"], bias=X["bias"])
+        differ("A", "sun exposure field", _bits(t.sun_exposure_field()) != _bits(expo))
+        t.sun_exposure_batch(X["batch"])
+        differ("A", f"sun exposure field at batch size {X['batch']}", _bits(t.sun_exposure_field()) != _bits(expo))
+        # B. the late passes on, exact precision, the overlays still on; the second frame is the one planned ahead
+        state = lated(c, state)
+        _set_late(t, c, state)
+        e = expected(c, state, cache)
+        for again in ("", " drawn again"):
+            differ("B", "frame" + again, (frame(t) != e["frame"]).any(axis=2))
+        # (the opacity plane follows the stored settings, enabled or not)
+        differ("B", "haze opacity", _bits(t.haze_opacity()) != _bits(hzm.frame(e["late"], e["vis"], u, h, G, **P["haze"])[1]))
+        info, D = t.drape_mip_info(), state["drape"]
+        if not state["late"]["mips"]:
+            if info is not None:
+                bad.append((seed, "B", f"drape_mip_info() {info} with mipmaps off", 1, []))
+        else:
+            sz = [] if D is None else dmm.sizes(D["image"].shape[1], D["image"].shape[0])
+            if info is None or info["levels"] != len(sz) or [tuple(s) for s in info["sizes"]] != sz or info["builds"] != int(len(sz) >= 2):
+                bad.append((seed, "B", f"drape_mip_info() {info} against the sizes {sz} and {int(len(sz) >= 2)} builds", 1, []))
+            elif len(sz) >= 2:
+                k = 1 + zlib.crc32(c["name"].encode()) % (len(sz) - 1)
+                differ("B", f"pyramid level {k}", (t.read_drape_level(k).view(np.uint16) != dmm.pyramid(D["image"])[k].view(np.uint16)).any(axis=2))
+        # C. fast precision.  The fast frame before the late passes is known without reading it: the relit and draped pixels are the
+        # exact ones (with mips and anisotropy on, that is asserted here for the first time) and every other pixel is the plain fast
+        # frame's.  The tints and the haze do not follow the precision, so off the pixels an overlay touches the frame is their
+        # models' over that frame, bit for bit, written pixels and others alike
+        t.set_shade_precision(1)
+        got = frame(t)
+        before = np.where((e["mask"] | e["drape_mask"])[..., None], e["draped"], plain)
+        want = ssm.chain(before, e["vis"], u, h, G, lut_, memo=cache, **dict(chain_features(c, state), shadows=None, ambient=None, drape=None))
+        touched = ((ocm.composite(want, e["vis"], u, h, G, e["layers"]) != want) | (ocm.composite(255 - want, e["vis"], u, h, G, e["layers"]) != 255 - want)).any(axis=2)
+        differ("C", "fast frame off the overlays against the late passes' models over the fast frame before them", (got != want).any(axis=2) & ~touched)
+        differ("C", "fast frame's alpha", got[..., 3] != e["frame"][..., 3])
+        t.set_shade_precision(0)
+        # D (and 5). the mutation, then the late mutation
         kind, a = c["mutation"], c["mutation_args"]
-        scans = (t.shadow_scans(), t.ambient_scans())
+        scans, late_scans = (t.shadow_scans(), t.ambient_scans()), _late_counters(t)
         state = mutated(c, state)
         if kind == "heights":
             t.set_height(state["heights"])
@@ -742,6 +1207,13 @@ def run_case(c, seed=None, cache=None):
         must = (int(state["shadows"] and kind in STALE_SHADOW), int(state["ambient"] and kind in STALE_AMBIENT))
         if rose != must:
             bad.append((seed, 5, f"after {kind} the shadow / sky-view field was computed {rose} times, the contract says {must}", 1, []))
+        late_scans = _late_stale(bad, seed, 5, kind, t, state, late_scans)
+        before = state
+        kind = c["late_mutation"]
+        state = late_mutated(c, state)
+        _apply_late_mutation(t, c, state)
+        differ("D", f"frame after {kind}", (frame(t) != expected(c, state, cache)["frame"]).any(axis=2))
+        _late_stale(bad, seed, "D", kind, t, state, late_scans, _reordered(c, before, state))
         # 6. the drape cleared: the frame of the same state without one
         if state["drape"] is not None:
             state = dict(state, drape=None)
@@ -751,7 +1223,83 @@ def run_case(c, seed=None, cache=None):
             bad.append((seed, 6, f"drape_info() {t.drape_info()} after clear_drape", 1, []))
     finally:
         t.close()
+    # E. a supersampled second handle: the same heights, uniforms, features, drape and late passes, no layer occluding; then the late mutation
+    f = c["late"]["supersample"]
+    if f > 1:
+        state = lated(c, featured(c, initial_state(c), overlays=True))
+        t = cabi.Terrain(W, H, G, lut(c["cmap"]), supersample=f)
+        try:
+            t.set_uniforms(state["u"]); t.set_shade_mode(c["mode"]); t.set_height(state["heights"]); t.set_shade_precision(0)
+            _set_features(t, state)
+            _set_drape(t, state["drape"])
+            _set_late(t, c, state)
+            _add_overlays(t, unoccluded(c))
+            for step in ("E", "E after " + c["late_mutation"]):
+                if step != "E":
+                    state = late_mutated(c, state)
+                    _apply_late_mutation(t, c, state)
+                e = expected_supersampled(c, state, f, cache)
+                t.render()
+                differ(step, "samples", (t.read_samples() != e["samples"]).any(axis=2))
+                differ(step, "frame against the resolve and the overlays", (t.read_rgba().reshape(H, W, 4) != e["frame"]).any(axis=2))
+                differ(step, "visibility of the samples", t.read_visibility() != e["vis"])
+        finally:
+            t.close()
     return bad
+
+
+_SCAN = ("eye_height", "target_height", "softness", "bias")
+
+
+def _set_late(t, c, state):
+    """The late passes' settings on the handle, all of them by every call (a setting sent again as it stands must cost nothing): a
+    pass is on where the state has it, with the state's parameters; an off pass keeps the case's"""
+    P, L = c["late"], state["late"] or {}
+    t.set_drape_mipmaps(bool(L.get("mips")), bias=L.get("mip_bias", P["mip_bias"]))
+    t.set_drape_anisotropy(L.get("max_anisotropy", P["max_anisotropy"]))
+    V, M, X, Z = (L.get(p) or P[p] for p in LATE_PASSES[1:])
+    t.set_viewshed(V["observer"], enabled=L.get("viewshed") is not None, radius=V["radius"], visible_rgba=V["visible_rgba"], hidden_rgba=V["hidden_rgba"],
+                   **{k: V[k] for k in _SCAN})
+    t.set_cumulative_viewshed(M["observers"], enabled=L.get("cumulative") is not None, radius=M["radius"], high_rgba=M["high_rgba"], low_rgba=M["low_rgba"],
+                              **{k: M[k] for k in _SCAN})
+    t.set_sun_exposure(X["suns"], weights=X["weights"], incidence=X["incidence"], enabled=L.get("exposure") is not None, softness=X["softness"], bias=X["bias"],
+                       high_rgba=X["high_rgba"], low_rgba=X["low_rgba"])
+    t.set_haze(Z["density"], enabled=L.get("haze") is not None, **{k: Z[k] for k in ("rgba", "start", "falloff", "base", "max_opacity", "background")})
+
+
+def _apply_late_mutation(t, c, state):
+    """the late mutation's state on the handle"""
+    if c["late_mutation"] == "heights_again":
+        t.set_height(state["heights"])
+    else:
+        _set_late(t, c, state)
+
+
+def _late_counters(t):
+    """(viewshed, cumulative, exposure scans, pyramid builds) over the handle's life; the builds also while mipmaps are off"""
+    return (t.viewshed_scans(), t.cumulative_viewshed_scans(), t.sun_exposure_scans(), t.drape_mip_builds())
+
+
+def _reordered(c, before, after):
+    """whether the list of the cumulative observers' vertices reads differently: what the field's key holds of them"""
+    a, b = before["late"]["cumulative"], after["late"]["cumulative"]
+    return a is not None and [snap(c, o) for o in a["observers"]] != [snap(c, o) for o in b["observers"]]
+
+
+def _late_stale(bad, seed, step, kind, t, state, counters, reordered=True):
+    """after mutation `kind` and a frame: the three late vertex fields and the pyramid were computed as often as the contract says
+    (STALE_VIEWSHED, ...: of a pass that is on) -> the counters now"""
+    L, D = state["late"], state["drape"]
+    now = _late_counters(t)
+    rose = tuple(int(a - b) for a, b in zip(now, counters))
+    levels = 0 if D is None else len(dmm.sizes(D["image"].shape[1], D["image"].shape[0]))
+    must = (int(L["viewshed"] is not None and kind in STALE_VIEWSHED),
+            int(L["cumulative"] is not None and kind in STALE_CUMULATIVE and (kind != "cumulative_reorder" or reordered)),
+            int(L["exposure"] is not None and kind in STALE_EXPOSURE),
+            int(L["mips"] and kind in MIP_BUILDS and levels >= 2))
+    if rose != must:
+        bad.append((seed, step, f"after {kind} the viewshed / cumulative / exposure field and the pyramid were computed {rose} times, the contract says {must}", 1, []))
+    return now
 
 
 FRESH_SEED = 50000                                            # the script's default window: apart from the suite's (test_gpu_feature_soak.py)
@@ -764,11 +1312,12 @@ def run(first=FRESH_SEED, cases=200, budget=400.0, verbose=True, corners=True):
     (the tuples of run_case), summary."""
     t0 = time.time()
     say = (lambda *a: print(*a, flush=True)) if verbose else (lambda *a: None)
-    bad, done, skipped, stat = [], 0, 0, []
+    bad, done, skipped, stat, late = [], 0, 0, [], []
 
     def one(c, seed):
         cache = {}
         stat.append(shares(c, cache))
+        late.append(late_shares(c, cache))
         b = run_case(c, seed, cache)
         for m in b:
             say(f"MISMATCH {m[0]} step {m[1]}: {m[2]}: {m[3]} differ, first at {m[4]}  ({c['W']}x{c['H']} grid={c['grid']} {c['features']} mutation={c['mutation']})")
@@ -795,7 +1344,7 @@ def run(first=FRESH_SEED, cases=200, budget=400.0, verbose=True, corners=True):
             say(f"{done} cases, {len(bad)} mismatches, {time.time() - t0:.0f} s")
     share = skipped / max(done + skipped, 1)
     summary = (f"feature soak: {ncorners} corners and {done} cases from seed {first}, {skipped} skipped for a degenerate camera ({100.0 * share:.0f} %, "
-               f"bound {100.0 * MAX_SKIPPED:.0f} %): {len(bad)} mismatches; {describe(stat)}; {time.time() - t0:.0f} s")
+               f"bound {100.0 * MAX_SKIPPED:.0f} %): {len(bad)} mismatches; {describe(stat)}; the late passes: {describe_late(late)}, supersampled {sum(c['supersample'] > 1 for c in late)}; {time.time() - t0:.0f} s")
     say(summary)
     return {"cases": done, "corners": ncorners, "skipped": skipped, "too_many_skipped": share > MAX_SKIPPED, "bad": bad, "summary": summary}
 

@@ -1,7 +1,8 @@
 """The CPU model of supersampled terrain frames: numpy over the existing models.
 
     out = ssm.resolve(samples, f)                  # (f H, f W, 4) uint8 -> (H, W, 4) uint8: the contract of the resolve kernel
-    s, vis = ssm.samples(W, H, f, uniforms, height, grid, lut, **features)         # the existing models at (f W, f H), in the library's order
+    out = ssm.chain(rgba, vis, uniforms, height, grid, lut, **features)            # the passes over a terrain frame, in the library's order
+    s, vis = ssm.samples(W, H, f, uniforms, height, grid, lut, **features)         # the oracle's frame at (f W, f H), then the chain
     out = ssm.frame(W, H, f, uniforms, height, grid, lut, layers=None, **features) # samples -> resolve -> the overlay models at (W, H)
     p = ssm.representative(plane, f)               # plane[f // 2::f, f // 2::f]: the sample pick() answers for
 
@@ -15,10 +16,12 @@ features (all optional, each as the public setters take them):
     shade_mode   0 / 1
     shadows      dict(strength, softness, bias)
     ambient      dict(directions (D, 2), reach, strength)
-    drape        dict(image, extent, opacity, filter, mips=False, bias=0.0)
+    drape        dict(image, extent, opacity, filter, mips=False, bias=0.0, max_anisotropy=1)
     exposure     dict(suns, weights, incidence, softness, bias, high_rgba, low_rgba)
     cumulative   dict(observers, radius, eye_height, target_height, softness, bias, high_rgba, low_rgba)
     viewshed     dict(observer, radius, eye_height, target_height, softness, bias, visible_rgba, hidden_rgba)
+    haze         dict(density, rgba, start, falloff, base, max_opacity, background)
+and in `drape`, with mips, max_anisotropy=1.
 """
 from __future__ import annotations
 
@@ -31,7 +34,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 TESTS = os.path.dirname(HERE)
 sys.path.insert(0, os.path.dirname(TESTS))
 for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "shadow_model", "ambient_model", "drape_model", "drape_mip_model",
-           "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model"):
+           "drape_aniso_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "gbuffer_model", "haze_model"):
     sys.path.insert(0, os.path.join(TESTS, _m))
 
 F32 = np.float32
@@ -84,56 +87,106 @@ def representative(plane, f):
     return np.asarray(plane)[f // 2::f, f // 2::f]
 
 
-def samples(W, H, f, uniforms, height, grid, lut, shade_mode=0, shadows=None, ambient=None, drape=None, exposure=None, cumulative=None,
-            viewshed=None, nthreads=8):
-    """The terrain and its passes at the sample size (f W, f H), composed from the models in the library's order: the oracle's frame ->
-    the ambient / shadow relight -> the draped image (through its mips if asked) -> the sun-exposure, cumulative and viewshed tints.
-    -> (samples (f H, f W, 4) uint8, vis (f H, f W) uint32)"""
-    import oracle
+def _memo(memo, key, make):
+    """make() once per key of `memo` (a dict, or None: no memory)"""
+    if memo is None:
+        return make()
+    if key not in memo:
+        memo[key] = make()
+    return memo[key]
+
+
+def _key(v):
+    """a hashable form of a feature's parameters (arrays by their bytes)"""
+    if isinstance(v, dict):
+        return tuple((k, _key(v[k])) for k in sorted(v))
+    if isinstance(v, (list, tuple)):
+        return tuple(_key(x) for x in v)
+    if isinstance(v, np.ndarray):
+        return (v.dtype.str, v.shape, v.tobytes())
+    return v
+
+
+def chain(rgba, vis, uniforms, height, grid, lut, shade_mode=0, shadows=None, ambient=None, drape=None, exposure=None, cumulative=None,
+          viewshed=None, haze=None, stages=None, memo=None):
+    """THE statement of the library's order of passes over a terrain frame `rgba` (H, W, 4) with visibility `vis`, at whatever size
+    they have: the ambient / shadow relight -> the draped image (through its mips, and their anisotropic taps, if asked) -> the
+    sun-exposure, cumulative and viewshed tints -> the haze.  -> the frame behind the last pass.  `stages` (a dict) receives what lies
+    between: lit, sky; shaded, mask; draped, drape_mask, drape_sample (mips on: the mip / anisotropy model's sample planes); per late
+    pass `<name>_frame` (the frame behind it) and `<name>_field`; haze_opacity.  `memo` (a dict) keeps the vertex fields, which do
+    not depend on the camera or the size, for a caller that runs the chain more than once."""
     import ambient_model as abm
     import cumulative_viewshed_model as cvm
+    import drape_aniso_model as dam
     import drape_mip_model as dmm
     import drape_model as drm
+    import haze_model as hzm
     import shadow_model as shm
     import sun_exposure_model as sem
     import viewshed_model as vsm
+    u = np.ascontiguousarray(uniforms, F32).reshape(44)
+    h = np.ascontiguousarray(height, F32)
+    vis = np.ascontiguousarray(vis, np.uint32)
+    out = np.ascontiguousarray(rgba, np.uint8).reshape(vis.shape + (4,))
+    st = {} if stages is None else stages
+    surface = (float(u[36]), float(u[38]), h.shape, h.tobytes(), int(grid))      # what a vertex field sees of the uniforms and the heights
+    lit = _memo(memo, ("lit", surface, u[32:35].tobytes(), _key(shadows)), lambda: shm.field(u, h, grid, **shadows)) if shadows is not None else None
+    sky, strength = None, 0.0
+    st["mask"] = np.zeros(vis.shape, bool)
+    if ambient is not None:
+        strength = ambient["strength"]
+        sky = _memo(memo, ("sky", surface, _key(ambient["directions"]), ambient["reach"]), lambda: abm.field(u, h, grid, ambient["directions"], ambient["reach"]))
+        out, st["mask"] = abm.frame(out, vis, u, h, grid, lut, sky, strength, lit=lit, shade_mode=shade_mode)
+    elif shadows is not None:
+        out, st["mask"] = shm.frame(out, vis, u, h, grid, lut, lit, shade_mode=shade_mode)
+    st["lit"], st["sky"], st["shaded"] = lit, sky, out
+    st["drape_mask"], st["drape_sample"] = np.zeros(vis.shape, bool), None
+    if drape is not None:
+        kw = dict(extent=drape.get("extent"), opacity=drape.get("opacity", 1.0), filter=drape.get("filter", "linear"), lit=lit, sky=sky,
+                  strength=strength, shade_mode=shade_mode)
+        if drape.get("mips") and drape.get("max_anisotropy", 1) > 1:
+            out, st["drape_mask"], st["drape_sample"] = dam.frame(out, vis, u, h, grid, lut, drape["image"], bias=drape.get("bias", 0.0),
+                                                                  max_anisotropy=drape["max_anisotropy"], want_sample=True, **kw)
+        elif drape.get("mips"):
+            out, st["drape_mask"], st["drape_sample"] = dmm.frame(out, vis, u, h, grid, lut, drape["image"], bias=drape.get("bias", 0.0), want_sample=True, **kw)
+        else:
+            out, st["drape_mask"] = drm.frame(out, vis, u, h, grid, lut, drape["image"], **kw)
+    st["draped"] = out
+    if exposure is not None:
+        field = {k: exposure[k] for k in ("incidence", "softness", "bias") if k in exposure}
+        tint = {k: exposure[k] for k in ("high_rgba", "low_rgba") if k in exposure}
+        e = _memo(memo, ("exposure", surface, _key(exposure["suns"]), _key(exposure.get("weights")), _key(field)),
+                  lambda: sem.field(u, h, grid, exposure["suns"], exposure.get("weights"), **field))
+        out, _ = sem.frame(out, vis, u, h, grid, e, sem.weight_total(exposure["suns"], exposure.get("weights")), **tint)
+        st["exposure_field"], st["exposure_frame"] = e, out
+    if cumulative is not None:
+        field = {k: cumulative[k] for k in ("radius", "eye_height", "target_height", "softness", "bias") if k in cumulative}
+        tint = {k: cumulative[k] for k in ("high_rgba", "low_rgba") if k in cumulative}
+        cnt = _memo(memo, ("cumulative", surface, _key(cumulative["observers"]), _key(field)), lambda: cvm.field(u, h, grid, cumulative["observers"], **field)[0])
+        out, _ = cvm.frame(out, vis, u, h, grid, cnt, len(cumulative["observers"]), **tint)
+        st["cumulative_field"], st["cumulative_frame"] = cnt, out
+    if viewshed is not None:
+        field = {k: viewshed[k] for k in ("eye_height", "target_height", "softness", "bias") if k in viewshed}
+        tint = {k: viewshed[k] for k in ("radius", "visible_rgba", "hidden_rgba") if k in viewshed}
+        seen, v = _memo(memo, ("viewshed", surface, _key(viewshed["observer"]), _key(field)), lambda: vsm.field(u, h, grid, viewshed["observer"], **field))
+        out, _ = vsm.frame(out, vis, u, h, grid, seen, v, **tint)
+        st["viewshed_field"], st["viewshed_vertex"], st["viewshed_frame"] = seen, v, out
+    st["haze_opacity"] = np.zeros(vis.shape, F32)
+    if haze is not None:
+        out, st["haze_opacity"] = hzm.frame(out, vis, u, h, grid, **haze)
+        st["haze_frame"] = out
+    return np.ascontiguousarray(out, np.uint8)
+
+
+def samples(W, H, f, uniforms, height, grid, lut, shade_mode=0, nthreads=8, stages=None, memo=None, **features):
+    """The terrain and its passes at the sample size (f W, f H): the oracle's frame, then `chain` with the features.
+    -> (samples (f H, f W, 4) uint8, vis (f H, f W) uint32)"""
+    import oracle
     sw, sh = int(f) * int(W), int(f) * int(H)
     u = np.ascontiguousarray(uniforms, F32).reshape(44)
     h = np.ascontiguousarray(height, F32)
     rgba, vis = oracle.render_terrain(u, sw, sh, grid, h, lut, want_vis=True, nthreads=min(nthreads, oracle.max_threads()), shade_mode=shade_mode)
-    out = rgba.reshape(sh, sw, 4)
-    lit = shm.field(u, h, grid, **shadows) if shadows is not None else None
-    sky, strength = None, 0.0
-    if ambient is not None:
-        strength = ambient["strength"]
-        sky = abm.field(u, h, grid, ambient["directions"], ambient["reach"])
-        out, _ = abm.frame(out, vis, u, h, grid, lut, sky, strength, lit=lit, shade_mode=shade_mode)
-    elif shadows is not None:
-        out, _ = shm.frame(out, vis, u, h, grid, lut, lit, shade_mode=shade_mode)
-    if drape is not None:
-        kw = dict(extent=drape.get("extent"), opacity=drape.get("opacity", 1.0), filter=drape.get("filter", "linear"), lit=lit, sky=sky,
-                  strength=strength, shade_mode=shade_mode)
-        if drape.get("mips"):
-            out, _ = dmm.frame(out, vis, u, h, grid, lut, drape["image"], bias=drape.get("bias", 0.0), **kw)
-        else:
-            out, _ = drm.frame(out, vis, u, h, grid, lut, drape["image"], **kw)
-    if exposure is not None:
-        field = {k: exposure[k] for k in ("incidence", "softness", "bias") if k in exposure}
-        tint = {k: exposure[k] for k in ("high_rgba", "low_rgba") if k in exposure}
-        e = sem.field(u, h, grid, exposure["suns"], exposure.get("weights"), **field)
-        out, _ = sem.frame(out, vis, u, h, grid, e, sem.weight_total(exposure["suns"], exposure.get("weights")), **tint)
-    if cumulative is not None:
-        field = {k: cumulative[k] for k in ("radius", "eye_height", "target_height", "softness", "bias") if k in cumulative}
-        tint = {k: cumulative[k] for k in ("high_rgba", "low_rgba") if k in cumulative}
-        cnt = cvm.field(u, h, grid, cumulative["observers"], **field)
-        cnt = cnt[0] if isinstance(cnt, tuple) else cnt
-        out, _ = cvm.frame(out, vis, u, h, grid, cnt, len(cumulative["observers"]), **tint)
-    if viewshed is not None:
-        field = {k: viewshed[k] for k in ("eye_height", "target_height", "softness", "bias") if k in viewshed}
-        tint = {k: viewshed[k] for k in ("radius", "visible_rgba", "hidden_rgba") if k in viewshed}
-        seen, v = vsm.field(u, h, grid, viewshed["observer"], **field)
-        out, _ = vsm.frame(out, vis, u, h, grid, seen, v, **tint)
-    return np.ascontiguousarray(out, np.uint8), vis
+    return chain(rgba.reshape(sh, sw, 4), vis, u, h, grid, lut, shade_mode=shade_mode, stages=stages, memo=memo, **features), vis
 
 
 def composite(frame, uniforms, height, grid, layers):

@@ -59,7 +59,7 @@ def test_methods_exist_on_both_classes(cls):
         assert re.search(r"drape_mip_info\(self: [\w.]+\) -> ", T.drape_mip_info.__doc__), T.drape_mip_info.__doc__
         assert re.search(rf"read_drape_level\(self: [\w.]+, level: {A}\) -> ", T.read_drape_level.__doc__), T.read_drape_level.__doc__
     from vulkan_forge_amd import cabi
-    for m in ("set_drape_mipmaps", "drape_mip_info", "read_drape_level", "drape_mip_build_stage"):
+    for m in ("set_drape_mipmaps", "drape_mip_info", "drape_mip_builds", "read_drape_level", "drape_mip_build_stage"):
         assert callable(getattr(cabi.Terrain, m)), m
 
 

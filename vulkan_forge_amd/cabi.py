@@ -908,6 +908,12 @@ class Terrain:
         self._check(self.lib.vf_terrain_drape_info(self.t, C.byref(iw), C.byref(ih), None, None, None))
         return mip_info(on.value != 0, levels.value, bias.value, nbytes.value, builds.value, iw.value, ih.value)
 
+    def drape_mip_builds(self):
+        """How often the pyramid has been built over the handle's life; unlike drape_mip_info(), also while mipmaps are off."""
+        builds = _u32()
+        self._check(self.lib.vf_terrain_drape_mip_info(self.t, None, None, None, None, C.byref(builds)))
+        return int(builds.value)
+
     def read_drape_level(self, level):
         """Level 1 <= level < levels of the pyramid as (h, w, 4) float16: premultiplied linear (r, g, b, a).  Builds it if stale."""
         from ._drape import mip_level
