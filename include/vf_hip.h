@@ -263,6 +263,23 @@ int vf_terrain_add_polygons(vf_terrain *t, const float *xyz, const uint32_t *rin
  * sharded handle. */
 #define VF_OCCLUSION_DEPTH_BIAS 1e-2f
 int vf_terrain_set_layer_occlusion(vf_terrain *t, uint32_t layer_id, int occlude, float depth_bias);
+/* Hazed overlay layers (new; opt-in, per layer; DESIGN.md 4r has the conventions bit for bit).  Overlays are not hazed unless their
+ * layer asks: with on != 0 a point, line or contour layer takes the handle's atmospheric haze (vf_terrain_set_haze, below).  At every
+ * pixel a feature of the layer covers, its colour is first blended towards the haze colour by the haze opacity of the feature's own
+ * depth and world height there -- the 1/w and y/w of a point's centre, or of a segment's clipped ends interpolated along it, through
+ * the same opacity function as the terrain's pass (density, start, falloff, base, max_opacity, the colour's alpha; `background` plays
+ * no part) -- and then goes over the pixel with the feature's own alpha, which is not changed.
+ * vf_terrain_set_layer_haze: sets (on != 0) or clears the layer's flag; updates the layer's records in place (no upload).  The flag
+ *   rests with the layer until vf_terrain_clear_overlays.  It does nothing while the handle's haze is disabled, cleared, never set or
+ *   has density 0: such frames are the unhazed ones byte for byte and launch what they launched before.  While haze is enabled every
+ *   frame uses the handle's current haze parameters: no layer is added again after vf_terrain_set_haze.  A layer may both occlude and
+ *   take the haze, and supersampled handles take hazed layers (the overlay pass runs at the output size).  The first hazed layer of a
+ *   handle allocates one 16-byte side record per primitive, filled on the frames that haze overlays.  Always the exact arithmetic:
+ *   it does not follow vf_terrain_set_shade_precision.  VF_ERR_INVALID, nothing changed: an unknown layer, a polygon layer (a polygon
+ *   layer cannot take the haze: polygon fills have no depth), a sharded handle.
+ * vf_terrain_layer_haze: *on = 1 if the layer's flag is set, else 0.  VF_ERR_INVALID for an unknown layer. */
+int vf_terrain_set_layer_haze(vf_terrain *t, uint32_t layer_id, int on);
+int vf_terrain_layer_haze(vf_terrain *t, uint32_t layer_id, int *on);
 /* Contour lines (new; isolines of the rendered surface, DESIGN.md 4e has the contract bit for bit).  The lines are extracted on the
  * device from the surface the handle draws -- the displaced height h of every grid vertex on the renderer's own triangulation, not the
  * uploaded texture -- and appended as one layer of draped line records, which every later frame draws like a line layer's.

@@ -1,5 +1,5 @@
 """Argument rules of the overlay methods (Scene / TerrainSpike .add_points / .add_lines / .add_polygons / .add_contours /
-.set_layer_occlusion), pack_lines and pack_polygons.
+.set_layer_occlusion / .set_layer_haze), pack_lines and pack_polygons.
 
 The extension calls these before it hands the arrays to the C-ABI (include/vf_hip.h, overlays); they need numpy only, no device.
 """
@@ -89,6 +89,13 @@ def occlusion_args(occlude, depth_bias):
     if not np.isfinite(b) or b < 0.0 or b > float(np.finfo(np.float32).max):
         raise ValueError(f"depth_bias must be a finite number >= 0, got {b}")
     return bool(occlude), b
+
+
+def haze_arg(haze, what="haze"):
+    """-> haze as a bool, for add_points / add_lines / add_contours (haze=) and set_layer_haze (on=)"""
+    if not isinstance(haze, (bool, np.bool_)):
+        raise TypeError(f"{what} must be a bool, got {type(haze).__name__}")
+    return bool(haze)
 
 
 def pack_lines(paths):

@@ -28,7 +28,7 @@ SYMBOLS = [
     "vf_terrain_set_height_device", "vf_terrain_set_shade_mode", "vf_terrain_set_shade_precision", "vf_terrain_set_raster_groups", "vf_terrain_raster_groups", "vf_terrain_set_shard", "vf_terrain_local_rows", "vf_terrain_set_tile_shard",
     "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
     "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
-    "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_set_layer_occlusion", "vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
+    "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_set_layer_occlusion", "vf_terrain_set_layer_haze", "vf_terrain_layer_haze", "vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
     "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_band_masks", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_tile_lists", "vf_terrain_debug_set_tile_list_capacity", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
     "vf_stitch_bands_device", "vf_stitch_tiles_device",
     "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
@@ -120,6 +120,8 @@ _PROTOS = {
     "vf_terrain_add_lines": (_i, [_vp, _vp, _vp, _u32, _f, _vp, _i, _i, C.POINTER(_u32)]),
     "vf_terrain_add_polygons": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _f, _i, C.POINTER(_u32)]),
     "vf_terrain_set_layer_occlusion": (_i, [_vp, _u32, _i, _f]),
+    "vf_terrain_set_layer_haze": (_i, [_vp, _u32, _i]),
+    "vf_terrain_layer_haze": (_i, [_vp, _u32, C.POINTER(C.c_int)]),
     "vf_terrain_add_contours": (_i, [_vp, _vp, _u32, _f, _vp, _f, _i, _i, _f, C.POINTER(_u32), C.POINTER(_u32)]),
     "vf_terrain_height_bounds": (_i, [_vp, C.POINTER(_f), C.POINTER(_f)]),
     "vf_terrain_layer_primitive_count": (_i, [_vp, _u32, C.POINTER(_u32)]),
@@ -422,6 +424,15 @@ class Terrain:
     def set_layer_occlusion(self, layer, occlude, depth_bias=1e-2):
         """Hide a point / line layer's pixels behind the terrain; depth_bias >= 0, the default VF_OCCLUSION_DEPTH_BIAS."""
         self._check(self.lib.vf_terrain_set_layer_occlusion(self.t, int(layer), int(bool(occlude)), float(depth_bias)))
+
+    def set_layer_haze(self, layer, on=True):
+        """A point / line / contour layer takes the handle's atmospheric haze, or stops taking it."""
+        self._check(self.lib.vf_terrain_set_layer_haze(self.t, int(layer), int(bool(on))))
+
+    def layer_haze(self, layer):
+        on = C.c_int()
+        self._check(self.lib.vf_terrain_layer_haze(self.t, int(layer), C.byref(on)))
+        return bool(on.value)
 
     def add_contours(self, levels, width_px=1.0, rgba=(0, 0, 0, 255), lift=0.0, join=0, occlude=False, depth_bias=1e-2):
         """Contour layer extracted on the device from the rendered surface: levels ascending float32; join 0 round /

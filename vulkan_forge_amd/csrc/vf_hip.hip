@@ -13,6 +13,7 @@
 #include "vf_sun_exposure.h"          // templates only
 #include "vf_resolve.h"               // templates only
 #include "vf_haze.h"                  // templates only
+#include "vf_overlay_haze.h"          // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -647,10 +648,13 @@ struct vf_terrain {
         DevBuf<unsigned long long> pg_total; // [1] the frame's mask words (zero between frames)
         DevBuf<uint32_t> mask;               // (feature, bin) backdrop masks, bit r: parity of row r's crossings right of the bin
         // occlusion (vf_terrain_set_layer_occlusion)
-        struct Layer { uint32_t lo, hi; bool polygon, occlude; };
+        struct Layer { uint32_t lo, hi; bool polygon, occlude; bool haze = false; };
         std::vector<Layer> layer;            // each layer's record range; a layer's id is its index
         uint32_t occluding = 0;              // layers with occlusion on: the frame stores its visibility and composites with depth
         DevBuf<float4> dep;                  // [nprims] per primitive (rw_a, rw_b - rw_a, kb, 0) of occluding primitives (k_ov_setup)
+        // hazed layers (vf_terrain_set_layer_haze)
+        uint32_t hazed = 0;                  // layers that take the haze: a frame with haze enabled composites them under it
+        DevBuf<float4> hzrec;                // [nprims] per primitive (rw_a, rw_b - rw_a, yq_a or y_c, yq_b - yq_a or ah) (k_ov_haze_setup); made by the first hazed layer
     } ov;
     // Contour extraction (vf_terrain_add_contours / vf_terrain_height_bounds, vf_contour.h): made by the first such call, freed with the
     // overlays -- a handle that never asks for contours holds none of it and launches nothing for them.
@@ -917,7 +921,7 @@ static void ov_release(vf_terrain *t)
     vf_terrain::Overlays &O = t->ov;
     void *ptrs[] = { O.d_cnt, O.d_start };
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    O.in.release(); O.prim.release(); O.box.release(); O.list.release(); O.dep.release();
+    O.in.release(); O.prim.release(); O.box.release(); O.list.release(); O.dep.release(); O.hzrec.release();
     O.pg_hdr.release(); O.pg_fbox.release(); O.pg_fbin.release(); O.pg_total.release(); O.mask.release();
     if (O.h_total) (void)hipHostFree(O.h_total);
     if (O.counted) (void)hipEventDestroy(O.counted);
@@ -1753,14 +1757,22 @@ static int plan_frame(vf_terrain *t, hipStream_t s, FramePlan &K, bool streaming
 // The overlay pass of a frame (vf_overlay.h), on the draw stream behind the tile kernels.  The pair list is sized by the frame's pair
 // count, which the host reads back between the scan and the scatter: a handle with overlays waits once per frame for that word.
 // With an occluding layer the tile kernels have stored the frame's visibility in d_vis (draw_frame), and the composite reads it.
+// With a hazed layer on a handle whose haze is enabled with a density above zero, k_ov_haze_setup fills the layers'
+// side records and k_ov_composite_haze composites; every other frame launches what it did before hazed layers existed.
+// (their launches stand behind the haze pass's, at the end of this file: the kernels that were there before keep their places)
+static void ov_haze_setup_launch(vf_terrain *t, hipStream_t s, const FrameParams &P);
+static void ov_haze_composite_launch(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, uint32_t nbx, uint32_t nbins, bool occlude);
 static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V)
 {
     vf_terrain::Overlays &O = t->ov;
     const uint32_t nbx = (t->oW + kOvBin - 1u) / kOvBin, nby = (t->oH + kOvBin - 1u) / kOvBin, nbins = nbx * nby;   // (P is the output size's: output_params)
     const dim3 per_prim((O.nprims + 255u) / 256u), threads(256);
     const bool occlude = O.occluding != 0u;
+    const bool hazed = O.hazed != 0u && t->hz.enabled && t->hz.density > 0.0f;
+    if (hazed && (!O.hzrec.p || O.hzrec.cap < O.nprims)) return fail(VF_ERR_HIP, "overlays: the hazed layers' side records are missing");
     hipLaunchKernelGGL(k_ov_setup, per_prim, threads, 0, s, P, axis(t), O.nprims, O.in.p, O.prim.p, O.box.p, O.d_cnt, nbx,
                        occlude ? O.dep.p : nullptr);
+    if (hazed) ov_haze_setup_launch(t, s, P);
     const dim3 per_slot((O.pg_hi - O.pg_lo + 255u) / 256u);
     if (O.nfill) {                                          // fill edges and headers: binned with the rest
         hipLaunchKernelGGL(k_pg_setup, per_slot, threads, 0, s, P, axis(t), O.pg_lo, O.pg_hi, O.in.p, O.prim.p, O.box.p, O.d_cnt, nbx, O.pg_fbox.p);
@@ -1793,7 +1805,8 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
     e = O.list.reserve(total, (size_t)total + total / 2u + 4096u);
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay pair list allocation failed: ") + hipGetErrorString(e));
     hipLaunchKernelGGL(k_ov_scatter, per_prim, threads, 0, s, O.nprims, O.box.p, nbx, O.d_start, O.d_cnt, O.list.p);
-    if (occlude)
+    if (hazed) ov_haze_composite_launch(t, s, P, V, nbx, nbins, occlude);
+    else if (occlude)
         hipLaunchKernelGGL(k_ov_composite_occlude, dim3(nbins), threads, 0, s, t->oW, t->oH, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p, t->ctx->d_decode,
                            t->ctx->d_thresh, O.mask.p, t->d_rgba, P, V, t->d_vis, O.dep.p);
     else
@@ -2238,6 +2251,7 @@ static int ov_append(vf_terrain *t, size_t nadd, const OvProducer &produce, cons
     if (e == hipSuccess) e = O.prim.reserve(need, cap);
     if (e == hipSuccess) e = O.box.reserve(need, cap);
     if (e == hipSuccess && (O.dep.p || O.occluding || occlude)) e = O.dep.reserve(need, cap, 0, true);
+    if (e == hipSuccess && (O.hzrec.p || O.hazed)) e = O.hzrec.reserve(need, cap);      // (per-frame values: k_ov_haze_setup writes every record)
     if (e != hipSuccess) return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e));
     if (!hdr.empty()) {
         const size_t fill_cap = std::max<size_t>({ nfill, 2u * O.pg_hdr.cap, 256u });
@@ -4221,6 +4235,64 @@ static int haze_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const S
 {
     haze_launch(t, s, P, V, redo, t->inputs.u, rgba, nullptr);
     VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+// ---- hazed overlay layers (vf_overlay_haze.h) -----------------------------------------------
+
+// overlay_pass's launches on a frame that hazes overlay layers: the side records behind k_ov_setup ...
+static void ov_haze_setup_launch(vf_terrain *t, hipStream_t s, const FrameParams &P)
+{
+    vf_terrain::Overlays &O = t->ov;
+    hipLaunchKernelGGL(k_ov_haze_setup<0>, dim3((O.nprims + 255u) / 256u), dim3(256), 0, s, P, axis(t), O.nprims, O.in.p, O.hzrec.p,
+                       haze_params(t, t->inputs.u));
+}
+
+// ... and the composite in place of k_ov_composite / k_ov_composite_occlude, with the handle's current haze and the frame's eye
+static void ov_haze_composite_launch(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, uint32_t nbx, uint32_t nbins, bool occlude)
+{
+    vf_terrain::Overlays &O = t->ov;
+    const HazeParams Z = haze_params(t, t->inputs.u);
+    const dim3 threads(256);
+    if (occlude)
+        hipLaunchKernelGGL(k_ov_composite_haze<true>, dim3(nbins), threads, 0, s, t->oW, t->oH, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p,
+                           t->ctx->d_decode, t->ctx->d_thresh, O.mask.p, t->d_rgba, P, V, t->d_vis, O.dep.p, O.hzrec.p, Z);
+    else
+        hipLaunchKernelGGL(k_ov_composite_haze<false>, dim3(nbins), threads, 0, s, t->oW, t->oH, nbx, O.prim.p, O.d_cnt, O.d_start, O.list.p,
+                           t->ctx->d_decode, t->ctx->d_thresh, O.mask.p, t->d_rgba, P, V, (const uint32_t *)nullptr, (const float4 *)nullptr,
+                           O.hzrec.p, Z);
+}
+
+// A point / line / contour layer takes the handle's atmospheric haze, or stops taking it: a flag on its records.  The
+// side records are made by the first hazed layer and grow with the primitives from then on (ov_append).
+int vf_terrain_set_layer_haze(vf_terrain *t, uint32_t layer_id, int on)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (int rc = ov_usable(t)) return rc;
+    vf_terrain::Overlays &O = t->ov;
+    if (layer_id >= O.layer.size()) return fail(VF_ERR_INVALID, "no overlay layer with that id");
+    vf_terrain::Overlays::Layer &L = O.layer[layer_id];
+    if (L.polygon) return fail(VF_ERR_INVALID, "a polygon layer cannot take the haze: polygon fills have no depth");
+    VF_HIP_TRY(wait_frame(t));                                // (a frame in flight reads the records)
+    if (on) {
+        const hipError_t e = O.hzrec.reserve(O.in.cap, O.in.cap);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, std::string("overlay allocation failed: ") + hipGetErrorString(e)); }
+    }
+    if (L.hi > L.lo) {
+        hipLaunchKernelGGL(k_ov_haze_flag<0>, dim3((L.hi - L.lo + 255u) / 256u), dim3(256), 0, t->ctx->stream, L.lo, L.hi, O.in.p, on ? 1u : 0u);
+        VF_HIP_TRY(hipGetLastError());
+        VF_HIP_TRY(hipStreamSynchronize(t->ctx->stream));
+    }
+    if (L.haze != (on != 0)) O.hazed += on ? 1u : (uint32_t)-1;
+    L.haze = on != 0;
+    return VF_OK;
+}
+
+int vf_terrain_layer_haze(vf_terrain *t, uint32_t layer_id, int *on)
+{
+    if (!t || !on) return fail(VF_ERR_INVALID, "NULL argument");
+    if (layer_id >= t->ov.layer.size()) return fail(VF_ERR_INVALID, "no overlay layer with that id");
+    *on = t->ov.layer[layer_id].haze ? 1 : 0;
     return VF_OK;
 }
 

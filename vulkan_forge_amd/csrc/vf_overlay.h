@@ -39,6 +39,7 @@ constexpr uint32_t kOvMaxPrims = 1u << 24;      // primitive budget of a handle 
 constexpr uint32_t kOvCircle = 0u, kOvSquare = 1u, kOvSegment = 2u;
 constexpr uint32_t kOvKindMask = 3u, kOvDrape = 4u, kOvExt0 = 8u, kOvExt1 = 16u;
 constexpr uint32_t kOvOcclude = 32u;            // point / segment of an occluding layer: hidden behind the terrain (pad[0] = bits of kb)
+constexpr uint32_t kOvHaze = 64u;               // point / segment of a hazed layer: it takes the handle's atmospheric haze
 // polygon fill records (OvIn kind kOvPoly): kPgHeader marks a feature's header, kPgClose an edge's closing-segment slot
 constexpr uint32_t kOvPoly = 3u, kPgHeader = kOvExt0, kPgClose = kOvExt1;
 constexpr uint32_t kOvFillHdr = 3u, kOvFillEdge = 4u, kOvNone = 7u;  // OvPrim kinds of fill records (kOvNone: nothing this frame)
@@ -95,13 +96,20 @@ __device__ __forceinline__ float ov_drape(const FrameParams &P, const AxisTables
     return (hd + (1.0f - fx) * (hc - hd)) + (1.0f - fz) * (hb - hd);
 }
 
-__device__ __forceinline__ void ov_clip(const FrameParams &P, const AxisTables &A, const float p[3], bool drape, float c[4])
+// a vertex in clip space; returns its world height, the y that goes into the view matrix (DESIGN.md 4r reads it)
+__device__ __forceinline__ float ov_clip_y(const FrameParams &P, const AxisTables &A, const float p[3], bool drape, float c[4])
 {
     float y = p[1];
     if (drape) y = ov_drape(P, A, p[0], p[2]) * P.exag + p[1];
     float vp[4];
     mat_vec(P.view, p[0], y, p[2], 1.0f, vp);
     mat_vec(P.proj, vp[0], vp[1], vp[2], vp[3], c);
+    return y;
+}
+
+__device__ __forceinline__ void ov_clip(const FrameParams &P, const AxisTables &A, const float p[3], bool drape, float c[4])
+{
+    (void)ov_clip_y(P, A, p, drape, c);
 }
 
 // pixel index range [lo, hi] of coordinate range [a, b] on an axis of n pixels (conservative; empty: lo > hi)
@@ -476,6 +484,77 @@ __device__ __forceinline__ void ov_flush(OvPixel &S, const float *dec, const uin
     }
 }
 
+// What a pixel of a composite that hazes overlays keeps beside OvPixel: nothing in the other composites
+template <bool HAZE> struct OvHazePixel {};
+template <> struct OvHazePixel<true> {
+    float ah;              // the haze opacity of the primitive that gave S.cov (0: none, or a primitive of a layer that is not hazed)
+    float lin[3];          // the haze colour in linear light
+};
+
+// What such a composite is handed beside the others' arguments: the frame's haze Z (vf_haze.h's HazeParams -- a template parameter,
+// HZ, because that header comes behind the library's last plain kernel, 4d), the side records hz of k_ov_haze_setup and their staging
+// array in LDS.  Empty otherwise, and every use of it is a dependent name: the other instantiations are what they were without it.
+template <bool HAZE, class HZ> struct OvHazeArgs {};
+template <class HZ> struct OvHazeArgs<true, HZ> {
+    const HZ *Z;
+    const float4 *hz;
+    float4 *shz;
+};
+
+// ov_flush for a composite that hazes overlays: the feature's own alpha is not changed
+__device__ __forceinline__ void ov_flush_hazed(OvPixel &S, const OvHazePixel<true> &Hz, const float *dec, const uint32_t *rgba, size_t o)
+{
+    const float ah = Hz.ah;
+    const float *hzl = Hz.lin;
+    if (!(S.cov > 0.0f)) return;
+    if (!S.touched) {
+        const uint32_t px = rgba[o];
+        S.c[0] = dec[px & 255u]; S.c[1] = dec[(px >> 8) & 255u]; S.c[2] = dec[(px >> 16) & 255u];
+        S.touched = true;
+    }
+    const float a = S.cov * ((float)(S.rgba >> 24) / 255.0f);
+    for (int k = 0; k < 3; ++k) {
+        float s = dec[(S.rgba >> (8 * k)) & 255u];
+        if (ah > 0.0f) s = hzl[k] * ah + s * (1.0f - ah);
+        S.c[k] = s * a + S.c[k] * (1.0f - a);
+    }
+}
+
+// The haze opacity of primitive p at pixel centre (qx, qy), from its side record hz (k_ov_haze_setup; rw_a == 0: not hazed).  A
+// segment's is (rw_a, rw_b - rw_a, yq_a, yq_b - yq_a): its depth d = 1 / rw and its world height y at the pixel, perspective-correct
+// along it.  A point's is (rw, 0, y_c, ah): the same at every pixel, formed by the set-up kernel.  HZ is vf_haze.h's HazeParams, and haze_alpha is found there when this is instantiated: that
+// header comes behind the library's last plain kernel (4d), so this one does not include it.
+template <class HZ>
+__device__ __forceinline__ float ov_haze_at(const HZ &Z, const OvPrim &p, const float4 hz, float qx, float qy)
+{
+    if (!(hz.x > 0.0f)) return 0.0f;
+    if (p.kind != kOvSegment) return hz.w;
+    const float u = (qx - p.g.x) * p.g.z + (qy - p.g.y) * p.g.w;
+    const float t = fminf(fmaxf(u / p.h.x, 0.0f), 1.0f);
+    const float rw = fmaf(t, hz.y, hz.x);
+    const float y = fmaf(t, hz.w, hz.z) / rw;
+    return haze_alpha(Z, 1.0f / rw, y);
+}
+
+// terrain_rw (vf_visible.h) for the composite that hazes and occludes: the same statements, always inlined.  terrain_rw is an
+// ordinary inline function; a second kernel calling it changed the register allocation of its first caller, k_ov_composite_occlude
+// (24 instructions of the clipper's scratch path, the count unchanged -- tools/isa_hash.py), so that kernel stays its
+// only caller.  tests/test_gpu_overlay_haze.py holds both to the occlusion model's terrain_q.
+__device__ __forceinline__ float ov_terrain_rw(const FrameParams &P, const SetupView &V, uint32_t prim, int32_t px, int32_t py)
+{
+    const VisibleSite s = visible_site<true>(P, V, prim);
+    if (s.generic) {
+        GVert v[3];
+        load_prim(P, V.hblk, prim, v[0], v[1], v[2]);
+        float attr[3];
+        return clipped_weights(v, P.hw, P.hh, P.W, P.H, px, py, attr);
+    }
+    const VertexRec r0 = V.vtx[s.r0], r1 = V.vtx[s.r1], r2 = V.vtx[s.r2];
+    float q0, q1, q2;
+    record_weights(r0, r1, r2, px, py, q0, q1, q2);
+    return (q0 + q1) + q2;
+}
+
 // bitonic sort of keys[0..m) ascending, m a power of two <= kOvSortCap (whole workgroup)
 __device__ __forceinline__ void ov_sort(uint32_t *keys, uint32_t m)
 {
@@ -501,15 +580,17 @@ __device__ __forceinline__ uint32_t ov_pow2(uint32_t n)
 
 // The compositing workgroup of one bin (k_ov_composite, k_ov_composite_occlude; the LDS arrays are the kernel's).  OCCLUDE (a handle
 // with an occluding layer): P, V and vis give each pixel the terrain's 1/w, dep / sdep each occluding primitive its own;
-// the other instantiation does not read them.
-template <bool OCCLUDE>
+// the other instantiation does not read them.  HAZE (a frame that hazes overlay layers; the kernels are in
+// vf_overlay_haze.h): HA gives each primitive of a hazed layer its depth and height, and the frame's haze.
+template <bool OCCLUDE, bool HAZE = false, class HZ = void>
 __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nbx, const OvPrim *__restrict__ prims,
                                              uint32_t *__restrict__ cnt, const uint32_t *__restrict__ start,
                                              const uint32_t *__restrict__ list, const float *__restrict__ decode,
                                              const float *__restrict__ thresh, const uint32_t *__restrict__ mask,
                                              uint32_t *__restrict__ rgba, const FrameParams *P, const SetupView *V,
                                              const uint32_t *__restrict__ vis, const float4 *__restrict__ dep,
-                                             uint32_t *keys, OvPrim *recs, float4 *sdep, float *sdec, float *sthr, uint32_t &s_n, uint32_t &s_next)
+                                             uint32_t *keys, OvPrim *recs, float4 *sdep, float *sdec, float *sthr, uint32_t &s_n, uint32_t &s_next,
+                                             const OvHazeArgs<HAZE, HZ> HA = {})
 {
     // (built without the tuning switches this kernel takes exactly v0..v39 and a 64-bit shift by v39: the form isa_lint refuses, vf_device.h)
     VF_RESERVE_VGPR(40);
@@ -527,12 +608,18 @@ __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nb
     if constexpr (OCCLUDE) {
         if (on) {
             const uint32_t id = vis[o];
-            if (id) Q = terrain_rw(*P, *V, id - 1u, (int32_t)px, (int32_t)py);
+            if constexpr (HAZE) { if (id) Q = ov_terrain_rw(*P, *V, id - 1u, (int32_t)px, (int32_t)py); }
+            else if (id) Q = terrain_rw(*P, *V, id - 1u, (int32_t)px, (int32_t)py);
         }
     }
     OvPixel S;
     S.c[0] = S.c[1] = S.c[2] = 0.0f; S.touched = false; S.feature = 0xFFFFFFFFu; S.rgba = 0u; S.cov = 0.0f;
     S.fill = false; S.par = 0u; S.d2 = 0.0f;
+    OvHazePixel<HAZE> Hz;
+    if constexpr (HAZE) {
+        Hz.ah = 0.0f;
+        for (int k = 0; k < 3; ++k) Hz.lin[k] = decode[(HA.Z->rgba >> (8 * k)) & 255u];
+    }
     const uint32_t *L = list + start[bin];
     // composite keys[0..m) (sorted): records staged 256 at a time, every pixel walks them in order
     auto run = [&](uint32_t m) {
@@ -541,6 +628,7 @@ __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nb
             if (k0 + tid < m) {
                 recs[tid] = prims[keys[k0 + tid]];
                 if constexpr (OCCLUDE) sdep[tid] = dep[keys[k0 + tid]];
+                if constexpr (HAZE) HA.shz[tid] = HA.hz[keys[k0 + tid]];
                 OvPrim &r = recs[tid];
                 if (r.kind == kOvFillHdr) {                             // this bin's word of the feature's backdrop mask
                     const uint32_t b0 = __float_as_uint(r.g.y), fw = __float_as_uint(r.g.z);
@@ -555,7 +643,8 @@ __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nb
                     const OvPrim &p = recs[k];
                     if (p.feature != S.feature) {
                         pg_fill_cover(S);
-                        ov_flush(S, sdec, rgba, o);
+                        if constexpr (HAZE) { ov_flush_hazed(S, Hz, sdec, rgba, o); Hz.ah = 0.0f; }
+                        else ov_flush(S, sdec, rgba, o);
                         S.feature = p.feature; S.rgba = p.rgba; S.cov = 0.0f; S.fill = false;
                     }
                     if (p.kind <= kOvSegment) {
@@ -571,7 +660,10 @@ __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nb
                                 if (Q > rw * d.z) c = 0.0f;
                             }
                         }
-                        S.cov = fmaxf(S.cov, c);
+                        if constexpr (HAZE) {                           // the first primitive that reaches the feature's maximum speaks for it
+                            if (c > S.cov) { S.cov = c; Hz.ah = ov_haze_at(*HA.Z, p, HA.shz[k], qx, qy); }
+                        }
+                        else S.cov = fmaxf(S.cov, c);
                     }
                     else if (p.kind == kOvFillEdge) {
                         const float ymin = __uint_as_float(p.rgba), ymax = __uint_as_float(p.pad);
@@ -624,7 +716,8 @@ __device__ __forceinline__ void ov_composite(uint32_t W, uint32_t H, uint32_t nb
     }
     if (on) {
         pg_fill_cover(S);
-        ov_flush(S, sdec, rgba, o);
+        if constexpr (HAZE) ov_flush_hazed(S, Hz, sdec, rgba, o);
+        else ov_flush(S, sdec, rgba, o);
         if (S.touched)
             rgba[o] = srgb_encode(S.c[0], sthr) | (srgb_encode(S.c[1], sthr) << 8) | (srgb_encode(S.c[2], sthr) << 16) | 0xFF000000u;
     }

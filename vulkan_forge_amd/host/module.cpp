@@ -446,9 +446,11 @@ public:
     void enable_timing(bool on) { Borrow b(busy); check(vf_terrain_enable_timing(t, on ? 1 : 0)); }
 
     // extension: overlays over the terrain frame (include/vf_hip.h; argument rules: vulkan_forge_amd/_overlays.py)
-    uint32_t add_points(py::object xyz, py::object size_px, py::object rgba, py::object shape, bool drape, py::object occlude, py::object depth_bias)
+    uint32_t add_points(py::object xyz, py::object size_px, py::object rgba, py::object shape, bool drape, py::object occlude, py::object depth_bias,
+                        py::object haze)
     {
         py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("point_args")(xyz, size_px, rgba, shape);
+        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(haze).cast<bool>();
         py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
         py::array pts = a[0].cast<py::array>(), dcol = a[3].cast<py::array>();
         const float dsize = a[1].cast<float>();
@@ -462,11 +464,14 @@ public:
         check(vf_terrain_add_points(t, static_cast<const float *>(pts.data()), (uint32_t)pts.shape(0), sz, cl, dsize,
                                     static_cast<const uint8_t *>(dcol.data()), shp, drape ? 1 : 0, &id));
         if (oc[0].cast<bool>()) check(vf_terrain_set_layer_occlusion(t, id, 1, oc[1].cast<float>()));
+        if (hz) check(vf_terrain_set_layer_haze(t, id, 1));
         return id;
     }
-    uint32_t add_lines(py::object paths, py::object width_px, py::object rgba, py::object cap, bool drape, py::object occlude, py::object depth_bias)
+    uint32_t add_lines(py::object paths, py::object width_px, py::object rgba, py::object cap, bool drape, py::object occlude, py::object depth_bias,
+                       py::object haze)
     {
         py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("line_args")(paths, width_px, rgba, cap);
+        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(haze).cast<bool>();
         py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
         py::array coords = a[0].cast<py::array>(), offsets = a[1].cast<py::array>(), col = a[3].cast<py::array>();
         const float width = a[2].cast<float>();
@@ -477,6 +482,7 @@ public:
         check(vf_terrain_add_lines(t, static_cast<const float *>(coords.data()), static_cast<const uint32_t *>(offsets.data()),
                                    (uint32_t)(offsets.shape(0) - 1), width, static_cast<const uint8_t *>(col.data()), cp, drape ? 1 : 0, &id));
         if (oc[0].cast<bool>()) check(vf_terrain_set_layer_occlusion(t, id, 1, oc[1].cast<float>()));
+        if (hz) check(vf_terrain_set_layer_haze(t, id, 1));
         return id;
     }
     uint32_t add_polygons(py::object polygons, py::object fill_rgba, py::object line_rgba, py::object line_width_px, bool drape)
@@ -500,6 +506,20 @@ public:
         Borrow b(busy);
         check(vf_terrain_set_layer_occlusion(t, layer, oc[0].cast<bool>() ? 1 : 0, oc[1].cast<float>()));
     }
+    // a point / line / contour layer under the atmospheric haze
+    void set_layer_haze(uint32_t layer, py::object on)
+    {
+        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(on, "on").cast<bool>();
+        Borrow b(busy);
+        check(vf_terrain_set_layer_haze(t, layer, hz ? 1 : 0));
+    }
+    bool layer_haze(uint32_t layer)
+    {
+        Borrow b(busy);
+        int on = 0;
+        check(vf_terrain_layer_haze(t, layer, &on));
+        return on != 0;
+    }
     // contour lines of the rendered surface, extracted on the device
     py::tuple height_bounds()
     {
@@ -516,8 +536,9 @@ public:
         return n;
     }
     uint32_t add_contours(py::object levels, py::object interval, py::object base, py::object width_px, py::object rgba, py::object lift,
-                          py::object join, py::object occlude, py::object depth_bias)
+                          py::object join, py::object occlude, py::object depth_bias, py::object haze)
     {
+        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(haze).cast<bool>();
         py::object bounds = py::none();
         if (levels.is_none() && !interval.is_none()) bounds = height_bounds();
         py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("contour_args")(levels, interval, base, width_px, rgba, lift, join, bounds);
@@ -528,6 +549,7 @@ public:
         check(vf_terrain_add_contours(t, static_cast<const float *>(lv.data()), (uint32_t)lv.shape(0), a[1].cast<float>(),
                                       static_cast<const uint8_t *>(col.data()), a[3].cast<float>(), a[4].cast<int>(), oc[0].cast<bool>() ? 1 : 0,
                                       oc[1].cast<float>(), &id, nullptr));
+        if (hz) check(vf_terrain_set_layer_haze(t, id, 1));
         return id;
     }
     void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
@@ -1283,17 +1305,22 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
         .def("last_timings", &T::last_timings)
         .def("add_points", &T::add_points, py::arg("xyz"), py::kw_only(), py::arg("size_px") = 5.0f,
              py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("shape") = "circle", py::arg("drape") = false,
-             py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
+             py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS, py::arg("haze") = false)
         .def("add_lines", &T::add_lines, py::arg("paths"), py::kw_only(), py::arg("width_px") = 2.0f,
              py::arg("rgba") = py::make_tuple(255, 255, 255, 255), py::arg("cap") = "round", py::arg("drape") = false,
-             py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
+             py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS, py::arg("haze") = false)
         .def("set_layer_occlusion", &T::set_layer_occlusion, py::arg("layer"), py::arg("occlude"),
              py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
+        .def("set_layer_haze", &T::set_layer_haze, py::arg("layer"), py::arg("on") = true,
+             "A point, line or contour layer takes the handle's atmospheric haze (set_haze), or stops taking it (DESIGN.md 4r).  The flag\n"
+             "rests with the layer until clear_overlays() and does nothing while haze is disabled or has density 0.")
+        .def("layer_haze", &T::layer_haze, py::arg("layer"))
         .def("add_polygons", &T::add_polygons, py::arg("polygons"), py::kw_only(), py::arg("fill_rgba") = py::make_tuple(255, 255, 255, 255),
              py::arg("line_rgba") = py::none(), py::arg("line_width_px") = 1.0f, py::arg("drape") = false)
         .def("add_contours", &T::add_contours, py::arg("levels") = py::none(), py::kw_only(), py::arg("interval") = py::none(),
              py::arg("base") = 0.0, py::arg("width_px") = 1.0f, py::arg("rgba") = py::make_tuple(0, 0, 0, 255), py::arg("lift") = 0.0f,
-             py::arg("join") = "round", py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS)
+             py::arg("join") = "round", py::arg("occlude") = false, py::arg("depth_bias") = VF_OCCLUSION_DEPTH_BIAS,
+             py::arg("haze") = false)
         .def("height_bounds", &T::height_bounds)
         .def("layer_primitive_count", &T::layer_primitive_count, py::arg("layer"))
         .def("clear_overlays", &T::clear_overlays)
