@@ -256,6 +256,44 @@ struct VertexField {
     void computed(const vf_terrain *t, std::vector<uint32_t> &k);   // the launches are queued: d is the field of `k` (which is taken)
     void release() { d.release(); valid = false; }                  // the buffer goes, the count stays
 };
+
+// A per-vertex field that is a sum over a list, batch by batch: the scans of a batch add q = rint(term * 65536) to
+// d_sum, k_sum_finish turns the sums into `value` and into d_frac, which the tint pass reads between low_rgba and high_rgba.  The
+// feature that holds one keeps what is its own: the list, the key, the batch size rule, the carries and the launches of a batch.
+struct SummedField {
+    uint32_t high_rgba, low_rgba;        // r | g << 8 | b << 16 | a << 24
+    SummedField(uint32_t high, uint32_t low) : high_rgba(high), low_rgba(low) {}    // (the feature's defaults)
+    VertexField value;                  // sum / 65536; the feature states its key
+    DevBuf<uint32_t> d_sum;              // n x n sums of q
+    DevBuf<float> d_frac;                // n x n: min(value / total, 1)
+    uint32_t forced_batch = 0;           // the feature's vf_terrain_debug_*_batch call; 0: from the memory budget
+    uint32_t batch = 0;                  // the batch size of the last computation
+    int reserve(const vf_terrain *t, const char *nomem);            // d_sum and d_frac (value: by its prepare)
+    hipError_t zero(const vf_terrain *t, hipStream_t s);            // queue d_sum = 0
+    // queue k_sum_finish with `total`; then value is the field of `key` (which is taken), computed in batches of `B`
+    int finish(const vf_terrain *t, hipStream_t s, float total, std::vector<uint32_t> &key, uint32_t B);
+    // k_viewshed_tint on d_frac, with no radius: every covered pixel is treated
+    int tint(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba) const;
+    void release() { value.release(); d_sum.release(); d_frac.release(); }
+    void force_batch(uint32_t b)
+    {
+        if (forced_batch != b) value.valid = false;                 // (the next call computes the field again, with this batch size)
+        forced_batch = b;
+    }
+    void colours(uint8_t high[4], uint8_t low[4]) const
+    {
+        for (int k = 0; k < 4; ++k) { high[k] = (uint8_t)(high_rgba >> (8 * k)); low[k] = (uint8_t)(low_rgba >> (8 * k)); }
+    }
+};
+// A feature struct with a SummedField `sum`, its other buffers released: gone, as if the handle never asked (the caller has
+// synchronised); the scan counter and a forced batch size stay
+template <typename Feature> static void summed_reset(Feature &H)
+{
+    H.sum.release();
+    const uint32_t scans = H.sum.value.scans, forced = H.sum.forced_batch;
+    H = Feature();
+    H.sum.value.scans = scans; H.sum.forced_batch = forced;
+}
 static uint32_t key_bits(float f) { uint32_t w; std::memcpy(&w, &f, sizeof w); return w; }
 static std::vector<uint32_t> key_of(std::initializer_list<float> fs)
 {
@@ -470,16 +508,12 @@ struct vf_terrain {
         std::vector<float> xz;           // the observers in the overlays' world frame, (x, z) each; empty: none set
         float eye_height = VF_VIEWSHED_EYE_HEIGHT, target_height = VF_VIEWSHED_TARGET_HEIGHT, radius = 0.0f;
         float softness = VF_VIEWSHED_SOFTNESS, bias = VF_VIEWSHED_BIAS;
-        uint32_t high_rgba = VF_CUMULATIVE_VIEWSHED_HIGH_RGBA, low_rgba = VF_CUMULATIVE_VIEWSHED_LOW_RGBA;
-        uint32_t forced_batch = 0;       // vf_terrain_debug_cumulative_viewshed_batch; 0: from the memory budget
-        DevBuf<uint32_t> d_sum;          // n x n sums of q
-        VertexField count;               // sum / 65536; key: exaggeration, eye_height, target_height, softness, bias, Rc (-1: no radius), the
-                                         // length of the vertex list, the observers' vertices (i, j) each
-        DevBuf<float> d_frac;            // n x n: count / N
+        // the count: total = N; key: exaggeration, eye_height, target_height, softness, bias, Rc (-1: no radius), the length of the
+        // vertex list, the observers' vertices (i, j) each
+        SummedField sum{ VF_CUMULATIVE_VIEWSHED_HIGH_RGBA, VF_CUMULATIVE_VIEWSHED_LOW_RGBA };
         DevBuf<float> d_cmax;            // carries of a batch: B x 4 quadrants x nchunks x nlines
         DevBuf<ViewshedPlan> d_plans;    // one per observer
         std::vector<ViewshedPlan> plans; // the host's copy of d_plans (the source of its upload)
-        uint32_t batch = 0;              // the batch size of the last computation
     } cv;
     // sun exposure: buffers made by the first tinted frame or field read; the sums are formed again only when what they
     // were made from has changed (not for the colours, the camera or the handle's own sun)
@@ -490,17 +524,13 @@ struct vf_terrain {
         uint32_t counted = 0;            // suns with sy > 0
         float wtot = 0.0f;               // the sum of their weights, in list order
         float softness = VF_SHADOW_SOFTNESS, bias = VF_SHADOW_BIAS;
-        uint32_t high_rgba = VF_SUN_EXPOSURE_HIGH_RGBA, low_rgba = VF_SUN_EXPOSURE_LOW_RGBA;
-        uint32_t forced_batch = 0;       // vf_terrain_debug_sun_exposure_batch; 0: from the memory budget
-        DevBuf<uint32_t> d_sum;          // n x n sums of q
-        VertexField exposure;            // sum / 65536; key: spacing, exaggeration, softness, bias, incidence, the length of the list, the
-                                         // suns (x, y, z) each, the weights
-        DevBuf<float> d_frac;            // n x n: min(exposure / wtot, 1)
+        // the exposure: total = wtot; key: spacing, exaggeration, softness, bias, incidence, the length of the list, the suns (x, y, z)
+        // each, the weights
+        SummedField sum{ VF_SUN_EXPOSURE_HIGH_RGBA, VF_SUN_EXPOSURE_LOW_RGBA };
         DevBuf<float2> d_slope;          // n x n (px, pz); only with incidence
         DevBuf<float> d_cmax;            // carries of a batch: B x nchunks x (2n - 1)
         DevBuf<ExposureSun> d_suns;      // the suns that add something: x-major scans, z-major scans, degenerate ones
         std::vector<ExposureSun> recs;   // the host's copy of d_suns (the source of its upload)
-        uint32_t batch = 0;              // the batch size of the last computation
     } se;
     // atmospheric haze: a setting of the handle, no cached field; the plane is made by the first opacity read
     struct Haze {
@@ -953,24 +983,16 @@ static void viewshed_release(vf_terrain *t)
     H.seen.scans = scans;
 }
 
-// the cumulative viewshed: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced batch size stay
+// the cumulative viewshed and sun exposure: gone as summed_reset says
 static void cumulative_release(vf_terrain *t)
 {
-    vf_terrain::CumulativeViewshed &H = t->cv;
-    H.d_sum.release(); H.count.release(); H.d_frac.release(); H.d_cmax.release(); H.d_plans.release();
-    const uint32_t scans = H.count.scans, forced = H.forced_batch;
-    H = vf_terrain::CumulativeViewshed();
-    H.count.scans = scans; H.forced_batch = forced;
+    t->cv.d_cmax.release(); t->cv.d_plans.release();
+    summed_reset(t->cv);
 }
-
-// sun exposure: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced batch size stay
 static void exposure_release(vf_terrain *t)
 {
-    vf_terrain::SunExposure &H = t->se;
-    H.d_sum.release(); H.exposure.release(); H.d_frac.release(); H.d_slope.release(); H.d_cmax.release(); H.d_suns.release();
-    const uint32_t scans = H.exposure.scans, forced = H.forced_batch;
-    H = vf_terrain::SunExposure();
-    H.exposure.scans = scans; H.forced_batch = forced;
+    t->se.d_slope.release(); t->se.d_cmax.release(); t->se.d_suns.release();
+    summed_reset(t->se);
 }
 
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
@@ -3206,9 +3228,9 @@ static const FieldRow kFieldTable[kFields] = {
     { ambient_field, [](vf_terrain *t) -> VertexField & { return t->am.sky; }, nullptr },
     { viewshed_field, [](vf_terrain *t) -> VertexField & { return t->vs.seen; },
       [](const vf_terrain *t) -> const char * { return t->vs.have_observer ? nullptr : "no observer set (vf_terrain_set_viewshed)"; } },
-    { cumulative_field, [](vf_terrain *t) -> VertexField & { return t->cv.count; },
+    { cumulative_field, [](vf_terrain *t) -> VertexField & { return t->cv.sum.value; },
       [](const vf_terrain *t) -> const char * { return t->cv.xz.empty() ? "no observers set (vf_terrain_set_cumulative_viewshed)" : nullptr; } },
-    { exposure_field, [](vf_terrain *t) -> VertexField & { return t->se.exposure; },
+    { exposure_field, [](vf_terrain *t) -> VertexField & { return t->se.sum.value; },
       [](const vf_terrain *t) -> const char * { return t->se.suns.empty() ? "no suns set (vf_terrain_set_sun_exposure)" : nullptr; } },
 };
 
@@ -3256,6 +3278,29 @@ struct ScansHeld {
     }
     ~ScansHeld() { for (int f = 0; t && f < kFields; ++f) kFieldTable[f].cache(t).scans = scans[f]; }
 };
+
+// The vf_terrain_debug_*_stage call of a summed field (kFieldCount, kFieldExposure): its computation, forced and timed.  label: whose
+// diagnostics these are.
+static int summed_stage(vf_terrain *t, Field f, const char *label, uint32_t repeats, float *ms)
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    const FieldRow &R = kFieldTable[f];
+    if (const char *why = R.refusal(t)) return fail(VF_ERR_INVALID, why);
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    if (repeats == 0) repeats = 1;
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    if (int rc = ct_heights_current(t)) return rc;
+    hipStream_t s = t->ctx->stream;
+    ScansHeld held;
+    held.hold(t);
+    int rc = VF_OK;
+    float a = 0.0f;
+    const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = R.compute(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
+    if (rc != VF_OK) return rc;
+    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string(label) + " diagnostics: " + hipGetErrorString(err));
+    *ms = a;
+    return VF_OK;
+}
 
 // What the stage calls below start from: the frame rendered last, drawn again into scratch buffers with its visibility (gb_frame),
 // the uniforms it was drawn with and its `redo` word.
@@ -3786,6 +3831,37 @@ int vf_terrain_debug_viewshed_stage(vf_terrain *t, uint32_t repeats, float ms[2]
                        [&] { viewshed_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
 }
 
+// ---- summed fields: what cumulative viewsheds and sun exposure share ---------------
+
+int SummedField::reserve(const vf_terrain *t, const char *nomem)
+{
+    const size_t nv = (size_t)t->n * t->n;
+    if (d_sum.reserve(nv, nv) != hipSuccess || d_frac.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, nomem); }
+    return VF_OK;
+}
+
+hipError_t SummedField::zero(const vf_terrain *t, hipStream_t s) { return hipMemsetAsync(d_sum.p, 0, (size_t)t->n * t->n * sizeof(uint32_t), s); }
+
+int SummedField::finish(const vf_terrain *t, hipStream_t s, float total, std::vector<uint32_t> &key, uint32_t B)
+{
+    const size_t nv = (size_t)t->n * t->n;
+    hipLaunchKernelGGL((k_sum_finish<0>), dim3((uint32_t)((nv + 255u) / 256u)), dim3(256), 0, s, (const uint32_t *)d_sum.p, (uint32_t)nv, total, value.d.p, d_frac.p);
+    VF_HIP_TRY(hipGetLastError());
+    value.computed(t, key);
+    batch = B;
+    return VF_OK;
+}
+
+int SummedField::tint(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba) const
+{
+    ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
+    T.seen = d_frac.p; T.decode = t->ctx->d_decode;
+    T.visible_rgba = high_rgba; T.hidden_rgba = low_rgba;
+    tint_launch(t, s, P, V, redo, rgba, T);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
 // ---- cumulative viewsheds (vf_cumulative_viewshed.h) ------------------------------------
 
 // The carries of a batch may take this many floats (32 MiB).  Not more: every observer of a batch reads the one height cache, and
@@ -3813,20 +3889,19 @@ static uint32_t cumulative_reach(const vf_terrain *t, float Rc)
 static uint32_t cumulative_batch(const vf_terrain *t, uint32_t N, uint32_t nchunks)
 {
     const size_t per = (size_t)4u * nchunks * (2u * (t->n - 1u) + 1u);
-    const size_t B = t->cv.forced_batch ? t->cv.forced_batch : std::max<size_t>(kCvCarryFloats / per, 1u);
+    const size_t B = t->cv.sum.forced_batch ? t->cv.sum.forced_batch : std::max<size_t>(kCvCarryFloats / per, 1u);
     return (uint32_t)std::min<size_t>(std::min<size_t>(B, kCvMaxBatch), N);
 }
 
-// `count` and d_frac hold the field of the uniforms `u`, the handle's heights, observers and scan parameters once the work queued on
-// `s` is done (the height cache must be current and ordered before `s`).  force: compute it anyway.
+// `sum` holds the field of the uniforms `u`, the handle's heights, observers and scan parameters once the work queued on `s` is done
+// (the height cache must be current and ordered before `s`).  force: compute it anyway.
 static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::CumulativeViewshed &H = t->cv;
     const uint32_t N = (uint32_t)(H.xz.size() / 2u);
     if (!N) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
-    const size_t nv = (size_t)t->n * t->n;
     const char *nomem = "cumulative viewshed field allocation failed";
-    if (H.d_sum.reserve(nv, nv) != hipSuccess || H.d_frac.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, nomem); }
+    if (int rc = H.sum.reserve(t, nomem)) return rc;
     const float spacing = spacing_of(u);
     const bool ranged = H.radius > 0.0f;
     const float Rc = ranged ? cumulative_rc(t, u) : 0.0f;
@@ -3840,7 +3915,7 @@ static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool f
     key.push_back((uint32_t)ij.size());
     key.insert(key.end(), ij.begin(), ij.end());
     bool current;
-    if (int rc = H.count.prepare(t, key, force, nomem, &current)) return rc;
+    if (int rc = H.sum.value.prepare(t, key, force, nomem, &current)) return rc;
     if (current) return VF_OK;
     const uint32_t nlines = 2u * L + 1u, nchunks = (reach + kShChunk - 1u) / kShChunk;
     const uint32_t B = cumulative_batch(t, N, nchunks);
@@ -3860,7 +3935,7 @@ static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool f
         S.exag = u[38]; S.eye_height = H.eye_height; S.target_height = H.target_height; S.softness = H.softness; S.bias = H.bias;
     }
     VF_HIP_TRY(hipMemcpyAsync(H.d_plans.p, H.plans.data(), (size_t)N * sizeof(ViewshedPlan), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
-    VF_HIP_TRY(hipMemsetAsync(H.d_sum.p, 0, nv * sizeof(uint32_t), s));
+    VF_HIP_TRY(H.sum.zero(t, s));
     const float RR = Rc * Rc;
     const uint32_t groups = (nlines + kShLines - 1u) / kShLines;
     const dim3 threads(256);
@@ -3878,32 +3953,17 @@ static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool f
         if (gz.x) hipLaunchKernelGGL((k_cumulative_chunk_max<true>), gz, threads, 0, s, plans, (const float *)t->d_hblk, H.d_cmax.p);
         hipLaunchKernelGGL((k_cumulative_carry<0>), dim3((nlines + 255u) / 256u, 4u * nb), threads, 0, s, plans, H.d_cmax.p);
         // (with no x-major chunk the observer's own vertex would go without its 1: n >= 2 gives every observer a step on both axes)
-        if (gx.x) hipLaunchKernelGGL((k_cumulative_seen<false>), gx, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.d_sum.p);
-        if (gz.x) hipLaunchKernelGGL((k_cumulative_seen<true>), gz, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.d_sum.p);
+        if (gx.x) hipLaunchKernelGGL((k_cumulative_seen<false>), gx, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.sum.d_sum.p);
+        if (gz.x) hipLaunchKernelGGL((k_cumulative_seen<true>), gz, threads, 0, s, plans, (const float *)t->d_hblk, (const float *)H.d_cmax.p, RR, ranged ? 1u : 0u, H.sum.d_sum.p);
     }
-    hipLaunchKernelGGL((k_cumulative_finish<0>), dim3((uint32_t)((nv + 255u) / 256u)), threads, 0, s, (const uint32_t *)H.d_sum.p, (uint32_t)nv, (float)N, H.count.d.p, H.d_frac.p);
-    VF_HIP_TRY(hipGetLastError());
-    H.count.computed(t, key);
-    H.batch = B;
-    return VF_OK;
-}
-
-static void cumulative_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
-{
-    const vf_terrain::CumulativeViewshed &H = t->cv;
-    ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
-    T.seen = H.d_frac.p; T.decode = t->ctx->d_decode;
-    T.visible_rgba = H.high_rgba; T.hidden_rgba = H.low_rgba;
-    tint_launch(t, s, P, V, redo, rgba, T);
+    return H.sum.finish(t, s, (float)N, key, B);
 }
 
 // The cumulative viewshed's tint of a frame: the field if it is stale, then k_viewshed_tint on f = count / N
 static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
     if (int rc = cumulative_field(t, t->inputs.u, s)) return rc;
-    cumulative_launch(t, s, P, V, redo, rgba);
-    VF_HIP_TRY(hipGetLastError());
-    return VF_OK;
+    return t->cv.sum.tint(t, s, P, V, redo, rgba);
 }
 
 int vf_terrain_set_cumulative_viewshed(vf_terrain *t, int enable, const float *observers_xz, uint32_t count, float eye_height, float target_height,
@@ -3931,12 +3991,12 @@ int vf_terrain_set_cumulative_viewshed(vf_terrain *t, int enable, const float *o
     const uint32_t hi = pack_rgba8(high_rgba), lo = pack_rgba8(low_rgba);
     std::vector<float> xz(observers_xz, observers_xz + (size_t)2u * count);
     if (H.enabled != (enable != 0) || H.xz != xz || H.eye_height != eye_height || H.target_height != target_height || H.radius != radius
-        || H.softness != softness || H.bias != bias || H.high_rgba != hi || H.low_rgba != lo)
+        || H.softness != softness || H.bias != bias || H.sum.high_rgba != hi || H.sum.low_rgba != lo)
         t->inputs_gen++;
     H.enabled = enable != 0;
     H.xz.swap(xz);
     H.eye_height = eye_height; H.target_height = target_height; H.radius = radius; H.softness = softness; H.bias = bias;
-    H.high_rgba = hi; H.low_rgba = lo;
+    H.sum.high_rgba = hi; H.sum.low_rgba = lo;
     return VF_OK;
 }
 
@@ -3948,9 +4008,9 @@ int vf_terrain_cumulative_viewshed_info(vf_terrain *t, vf_cumulative_viewshed_in
     if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
     const vf_terrain::CumulativeViewshed &H = t->cv;
     *out = vf_cumulative_viewshed_info();
-    out->enabled = H.enabled ? 1 : 0; out->count = (uint32_t)(H.xz.size() / 2u); out->batch = H.batch;
+    out->enabled = H.enabled ? 1 : 0; out->count = (uint32_t)(H.xz.size() / 2u); out->batch = H.sum.batch;
     out->eye_height = H.eye_height; out->target_height = H.target_height; out->radius = H.radius; out->softness = H.softness; out->bias = H.bias;
-    for (int k = 0; k < 4; ++k) { out->high_rgba[k] = (uint8_t)(H.high_rgba >> (8 * k)); out->low_rgba[k] = (uint8_t)(H.low_rgba >> (8 * k)); }
+    H.sum.colours(out->high_rgba, out->low_rgba);
     return VF_OK;
 }
 
@@ -3968,32 +4028,13 @@ int vf_terrain_read_cumulative_viewshed_vertices(vf_terrain *t, uint32_t *vertic
 int vf_terrain_debug_cumulative_viewshed_batch(vf_terrain *t, uint32_t batch)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->cv.forced_batch != batch) t->cv.count.valid = false;      // (the next call computes the field again, with this batch size)
-    t->cv.forced_batch = batch;
+    t->cv.sum.force_batch(batch);
     return VF_OK;
 }
 
 int vf_terrain_debug_cumulative_viewshed_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldCount, count); }
 
-int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, float *ms)
-{
-    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->cv.xz.empty()) return fail(VF_ERR_INVALID, "no observers set (vf_terrain_set_cumulative_viewshed)");
-    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
-    if (repeats == 0) repeats = 1;
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    if (int rc = ct_heights_current(t)) return rc;
-    hipStream_t s = t->ctx->stream;
-    ScansHeld held;
-    held.hold(t);
-    int rc = VF_OK;
-    float a = 0.0f;
-    const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = cumulative_field(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
-    if (rc != VF_OK) return rc;
-    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("cumulative viewshed diagnostics: ") + hipGetErrorString(err));
-    *ms = a;
-    return VF_OK;
-}
+int vf_terrain_debug_cumulative_viewshed_stage(vf_terrain *t, uint32_t repeats, float *ms) { return summed_stage(t, kFieldCount, "cumulative viewshed", repeats, ms); }
 
 // ---- sun exposure (vf_sun_exposure.h) ---------------------------------------------------
 
@@ -4005,12 +4046,12 @@ constexpr uint32_t kSeMaxBatch = 4096;                        // (the sun's inde
 // suns per launch: as many as the budget for the carries holds, a slot being nchunks x (2n - 1) floats
 static uint32_t exposure_batch(const vf_terrain *t, uint32_t scans, size_t stride)
 {
-    const size_t B = t->se.forced_batch ? t->se.forced_batch : std::max<size_t>(kSeCarryFloats / stride, 1u);
+    const size_t B = t->se.sum.forced_batch ? t->se.sum.forced_batch : std::max<size_t>(kSeCarryFloats / stride, 1u);
     return (uint32_t)std::max<size_t>(std::min<size_t>(std::min<size_t>(B, kSeMaxBatch), scans), 1u);
 }
 
-// `exposure` and d_frac hold the field of the uniforms `u`, the handle's heights, suns, weights and scan parameters once the work
-// queued on `s` is done (the height cache must be current and ordered before `s`).  force: compute it anyway.
+// `sum` holds the field of the uniforms `u`, the handle's heights, suns, weights and scan parameters once the work queued on `s` is
+// done (the height cache must be current and ordered before `s`).  force: compute it anyway.
 static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::SunExposure &H = t->se;
@@ -4018,14 +4059,14 @@ static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool for
     if (!N) return fail(VF_ERR_INVALID, "no suns set (vf_terrain_set_sun_exposure)");
     const size_t nv = (size_t)t->n * t->n;
     const char *nomem = "sun exposure field allocation failed";
-    if (H.d_sum.reserve(nv, nv) != hipSuccess || H.d_frac.reserve(nv, nv) != hipSuccess) { (void)hipGetLastError(); return fail(VF_ERR_NOMEM, nomem); }
+    if (int rc = H.sum.reserve(t, nomem)) return rc;
     const float spacing = spacing_of(u), exag = u[38];
     std::vector<uint32_t> key = key_of({ spacing, exag, H.softness, H.bias, H.incidence ? 1.0f : 0.0f });
     key.push_back(N);
     for (float f : H.suns) key.push_back(key_bits(f));
     for (float f : H.weights) key.push_back(key_bits(f));
     bool current;
-    if (int rc = H.exposure.prepare(t, key, force, nomem, &current)) return rc;
+    if (int rc = H.sum.value.prepare(t, key, force, nomem, &current)) return rc;
     if (current) return VF_OK;
     // the suns that add something, in the order of their launches: x-major scans, z-major scans, degenerate suns (every vertex lit)
     std::vector<ExposureSun> part[3];
@@ -4054,9 +4095,10 @@ static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool for
     }
     if (!H.recs.empty())
         VF_HIP_TRY(hipMemcpyAsync(H.d_suns.p, H.recs.data(), H.recs.size() * sizeof(ExposureSun), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
-    VF_HIP_TRY(hipMemsetAsync(H.d_sum.p, 0, nv * sizeof(uint32_t), s));
+    VF_HIP_TRY(H.sum.zero(t, s));
     const dim3 threads(256);
     const float *hblk = t->d_hblk;
+    uint32_t *sum = H.sum.d_sum.p;
     const float2 *slope = H.incidence ? H.d_slope.p : nullptr;
     if (H.incidence && !H.recs.empty())
         hipLaunchKernelGGL((k_exposure_slopes<0>), dim3((t->n + 31u) / 32u, (t->n + 7u) / 8u), threads, 0, s, hblk, t->n, t->nb, exag, grid_step(t) * spacing, H.d_slope.p);
@@ -4080,33 +4122,23 @@ static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool for
             const dim3 grid(nchunks, (lines[z] + kShLines - 1u) / kShLines, hi[z] - lo[z]);
             const float *carry = H.d_cmax.p + (size_t)(lo[z] - b0) * stride;
             const ExposureSun *ps = H.d_suns.p + lo[z];
-            if (z && H.incidence) hipLaunchKernelGGL((k_exposure_lit<true, true>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
-            else if (z) hipLaunchKernelGGL((k_exposure_lit<true, false>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
-            else if (H.incidence) hipLaunchKernelGGL((k_exposure_lit<false, true>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
-            else hipLaunchKernelGGL((k_exposure_lit<false, false>), grid, threads, 0, s, ps, hblk, carry, stride, slope, H.d_sum.p);
+            if (z && H.incidence) hipLaunchKernelGGL((k_exposure_lit<true, true>), grid, threads, 0, s, ps, hblk, carry, stride, slope, sum);
+            else if (z) hipLaunchKernelGGL((k_exposure_lit<true, false>), grid, threads, 0, s, ps, hblk, carry, stride, slope, sum);
+            else if (H.incidence) hipLaunchKernelGGL((k_exposure_lit<false, true>), grid, threads, 0, s, ps, hblk, carry, stride, slope, sum);
+            else hipLaunchKernelGGL((k_exposure_lit<false, false>), grid, threads, 0, s, ps, hblk, carry, stride, slope, sum);
         }
     }
     const dim3 flat((uint32_t)((nv + 255u) / 256u));
-    if (nflat && H.incidence) hipLaunchKernelGGL((k_exposure_flat<true>), flat, threads, 0, s, (const ExposureSun *)H.d_suns.p + scans, nflat, slope, (uint32_t)nv, H.d_sum.p);
-    else if (nflat) hipLaunchKernelGGL((k_exposure_flat<false>), flat, threads, 0, s, (const ExposureSun *)H.d_suns.p + scans, nflat, slope, (uint32_t)nv, H.d_sum.p);
-    hipLaunchKernelGGL((k_exposure_finish<0>), flat, threads, 0, s, (const uint32_t *)H.d_sum.p, (uint32_t)nv, H.wtot, H.exposure.d.p, H.d_frac.p);
-    VF_HIP_TRY(hipGetLastError());
-    H.exposure.computed(t, key);
-    H.batch = B;
-    return VF_OK;
+    if (nflat && H.incidence) hipLaunchKernelGGL((k_exposure_flat<true>), flat, threads, 0, s, (const ExposureSun *)H.d_suns.p + scans, nflat, slope, (uint32_t)nv, sum);
+    else if (nflat) hipLaunchKernelGGL((k_exposure_flat<false>), flat, threads, 0, s, (const ExposureSun *)H.d_suns.p + scans, nflat, slope, (uint32_t)nv, sum);
+    return H.sum.finish(t, s, H.wtot, key, B);
 }
 
 // The sun exposure's tint of a frame: the field if it is stale, then k_viewshed_tint on f = min(exposure / wtot, 1)
 static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
     if (int rc = exposure_field(t, t->inputs.u, s)) return rc;
-    const vf_terrain::SunExposure &H = t->se;
-    ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
-    T.seen = H.d_frac.p; T.decode = t->ctx->d_decode;
-    T.visible_rgba = H.high_rgba; T.hidden_rgba = H.low_rgba;
-    tint_launch(t, s, P, V, redo, rgba, T);
-    VF_HIP_TRY(hipGetLastError());
-    return VF_OK;
+    return t->se.sum.tint(t, s, P, V, redo, rgba);
 }
 
 int vf_terrain_set_sun_exposure(vf_terrain *t, int enable, const float *suns_xyz, const float *weights, uint32_t count, int incidence, float softness,
@@ -4131,14 +4163,14 @@ int vf_terrain_set_sun_exposure(vf_terrain *t, int enable, const float *suns_xyz
     // (compared as bits, as the field's key is: -0 is not +0)
     const bool same = suns.size() == H.suns.size() && !std::memcmp(suns.data(), H.suns.data(), suns.size() * sizeof(float))
                       && !std::memcmp(w.data(), H.weights.data(), w.size() * sizeof(float));
-    if (H.enabled != (enable != 0) || !same || H.incidence != (incidence != 0) || H.softness != softness || H.bias != bias || H.high_rgba != hi || H.low_rgba != lo)
+    if (H.enabled != (enable != 0) || !same || H.incidence != (incidence != 0) || H.softness != softness || H.bias != bias || H.sum.high_rgba != hi || H.sum.low_rgba != lo)
         t->inputs_gen++;
     H.enabled = enable != 0; H.incidence = incidence != 0;
     H.suns.swap(suns); H.weights.swap(w);
     H.counted = 0; H.wtot = 0.0f;
     for (uint32_t o = 0; o < count; ++o)
         if (H.suns[3u * o + 1u] > 0.0f) { H.counted++; H.wtot += H.weights[o]; }
-    H.softness = softness; H.bias = bias; H.high_rgba = hi; H.low_rgba = lo;
+    H.softness = softness; H.bias = bias; H.sum.high_rgba = hi; H.sum.low_rgba = lo;
     return VF_OK;
 }
 
@@ -4161,41 +4193,22 @@ int vf_terrain_sun_exposure_info(vf_terrain *t, vf_sun_exposure_info *out)
     const vf_terrain::SunExposure &H = t->se;
     *out = vf_sun_exposure_info();
     out->enabled = H.enabled ? 1 : 0; out->incidence = H.incidence ? 1 : 0;
-    out->count = (uint32_t)H.weights.size(); out->counted = H.counted; out->batch = H.batch;
+    out->count = (uint32_t)H.weights.size(); out->counted = H.counted; out->batch = H.sum.batch;
     out->weight_total = H.wtot; out->softness = H.softness; out->bias = H.bias;
-    for (int k = 0; k < 4; ++k) { out->high_rgba[k] = (uint8_t)(H.high_rgba >> (8 * k)); out->low_rgba[k] = (uint8_t)(H.low_rgba >> (8 * k)); }
+    H.sum.colours(out->high_rgba, out->low_rgba);
     return VF_OK;
 }
 
 int vf_terrain_debug_sun_exposure_batch(vf_terrain *t, uint32_t batch)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->se.forced_batch != batch) t->se.exposure.valid = false;   // (the next call computes the field again, with this batch size)
-    t->se.forced_batch = batch;
+    t->se.sum.force_batch(batch);
     return VF_OK;
 }
 
 int vf_terrain_debug_sun_exposure_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldExposure, count); }
 
-int vf_terrain_debug_sun_exposure_stage(vf_terrain *t, uint32_t repeats, float *ms)
-{
-    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->se.suns.empty()) return fail(VF_ERR_INVALID, "no suns set (vf_terrain_set_sun_exposure)");
-    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
-    if (repeats == 0) repeats = 1;
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    if (int rc = ct_heights_current(t)) return rc;
-    hipStream_t s = t->ctx->stream;
-    ScansHeld held;
-    held.hold(t);
-    int rc = VF_OK;
-    float a = 0.0f;
-    const hipError_t err = time_launches(s, repeats, a, [&](bool) { rc = exposure_field(t, t->inputs.u, s, true); return rc == VF_OK ? hipSuccess : hipErrorUnknown; });
-    if (rc != VF_OK) return rc;
-    if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("sun exposure diagnostics: ") + hipGetErrorString(err));
-    *ms = a;
-    return VF_OK;
-}
+int vf_terrain_debug_sun_exposure_stage(vf_terrain *t, uint32_t repeats, float *ms) { return summed_stage(t, kFieldExposure, "sun exposure", repeats, ms); }
 
 // ---- atmospheric haze (vf_haze.h) ---------------------------------------------------------
 

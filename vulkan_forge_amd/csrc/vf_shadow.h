@@ -65,11 +65,16 @@ __device__ __forceinline__ float sh_lit(const ShadowPlan &S, float y, float M, u
     return 1.0f - S.strength * c;
 }
 
-// Chunk (blockIdx.x) of 64 lines (blockIdx.y): the maximum of each line's 64 terms -> cmax[chunk][line].
+// ---- the three stages of the scan, stated once ----
+// Their bodies serve the single field's kernels below and the batched ones of vf_sun_exposure.h, which wrap them: a wrapper finds its
+// plan, passes the base of *that plan's* carries (of this chunk, where a stage works on one) and, for the last stage, a sink that
+// takes every value.  S comes by reference: a by-value kernel argument or a record in device memory.
+
+// Chunk (blockIdx.x) of 64 lines (blockIdx.y): the maximum of each line's 64 terms -> out[line], out = cmax[chunk].
 // ZMAJOR = false: memory runs along the steps -- lane = step, a wave reduces one line at a time.
 // ZMAJOR = true: memory runs across the lines -- lane = line, each wave walks a quarter of the steps, the quarters meet in LDS.
 template <bool ZMAJOR>
-__global__ __launch_bounds__(256) void k_shadow_chunk_max(ShadowPlan S, const float *__restrict__ hblk, float *__restrict__ cmax)
+__device__ __forceinline__ void sh_stage_chunk_max(const ShadowPlan &S, const float *__restrict__ hblk, float *__restrict__ out)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t k0 = blockIdx.x * kShChunk, l0 = blockIdx.y * kShLines;
@@ -80,31 +85,43 @@ __global__ __launch_bounds__(256) void k_shadow_chunk_max(ShadowPlan S, const fl
         part[wave][lane] = m;
         __syncthreads();
         if (wave == 0u && l0 + lane < S.nlines)
-            cmax[(size_t)blockIdx.x * S.nlines + l0 + lane] = fmaxf(fmaxf(part[0][lane], part[1][lane]), fmaxf(part[2][lane], part[3][lane]));
+            out[l0 + lane] = fmaxf(fmaxf(part[0][lane], part[1][lane]), fmaxf(part[2][lane], part[3][lane]));
     } else {
         for (uint32_t g = wave; g < kShLines; g += 4u) {
             const uint32_t line = l0 + g;
             if (line >= S.nlines) break;                       // (wave-uniform)
             float m = sh_term(S, sh_height(S, hblk, line, k0 + lane), k0 + lane);
             for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-            if (lane == 0u) cmax[(size_t)blockIdx.x * S.nlines + line] = m;
+            if (lane == 0u) out[line] = m;
         }
     }
 }
 
-// per line: the chunk maxima -> the maximum of the chunks before each (in place), one thread per line
-template <int UNUSED>
-__global__ __launch_bounds__(256) void k_shadow_carry(uint32_t nlines, uint32_t nchunks, float *__restrict__ cmax)
+template <bool ZMAJOR>
+__global__ __launch_bounds__(256) void k_shadow_chunk_max(ShadowPlan S, const float *__restrict__ hblk, float *__restrict__ cmax)
+{
+    sh_stage_chunk_max<ZMAJOR>(S, hblk, cmax + (size_t)blockIdx.x * S.nlines);
+}
+
+// per line: the chunk maxima -> the maximum of the chunks before each (in place, c = the plan's cmax), one thread per line.  Of the
+// plan this stage needs two numbers, and k_shadow_carry is handed no more than them: they come as they are.
+__device__ __forceinline__ void sh_stage_carry(uint32_t nlines, uint32_t nchunks, float *__restrict__ c)
 {
     const uint32_t line = blockIdx.x * 256u + threadIdx.x;
     if (line >= nlines) return;
     float run = -INFINITY;
-    for (uint32_t c = 0; c < nchunks; ++c) {
-        const size_t o = (size_t)c * nlines + line;
-        const float m = cmax[o];
-        cmax[o] = run;
+    for (uint32_t k = 0; k < nchunks; ++k) {
+        const size_t o = (size_t)k * nlines + line;
+        const float m = c[o];
+        c[o] = run;
         run = fmaxf(run, m);
     }
+}
+
+template <int UNUSED>
+__global__ __launch_bounds__(256) void k_shadow_carry(uint32_t nlines, uint32_t nchunks, float *__restrict__ cmax)
+{
+    sh_stage_carry(nlines, nchunks, cmax);
 }
 
 // float <-> uint32 in the same order (every float but NaN; 0 lies below them all: the identity of the DPP ladder's unsigned max)
@@ -120,9 +137,10 @@ __device__ __forceinline__ float sh_scan_lit(const ShadowPlan &S, float y, float
     return sh_lit(S, y, M, k);
 }
 
-template <bool ZMAJOR>
-__global__ __launch_bounds__(256) void k_shadow_lit(ShadowPlan S, const float *__restrict__ hblk, const float *__restrict__ carry,
-                                                    float *__restrict__ lit)
+// The scan inside chunk (blockIdx.x) of 64 lines (blockIdx.y), seeded with in[line], in = carry[chunk]: sink(line, k, lit) for every
+// step, those without a vertex among them (the sink asks sh_vertex)
+template <bool ZMAJOR, class Sink>
+__device__ __forceinline__ void sh_stage_lit(const ShadowPlan &S, const float *__restrict__ hblk, const float *__restrict__ in, Sink sink)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t k0 = blockIdx.x * kShChunk, l0 = blockIdx.y * kShLines;
@@ -134,23 +152,28 @@ __global__ __launch_bounds__(256) void k_shadow_lit(ShadowPlan S, const float *_
         __syncthreads();
         for (uint32_t g = wave; g < kShLines; g += 4u) {
             const uint32_t line = l0 + g;
-            const float c = line < S.nlines ? carry[(size_t)blockIdx.x * S.nlines + line] : -INFINITY;
+            const float c = line < S.nlines ? in[line] : -INFINITY;
             tile[g * kShPitch + lane] = sh_scan_lit(S, tile[g * kShPitch + lane], c, k0 + lane);
         }
         __syncthreads();
-        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) {
-            uint32_t i, j;
-            if (sh_vertex(S, l0 + lane, k0 + kk, i, j)) lit[(size_t)j * S.n + i] = tile[lane * kShPitch + kk];
-        }
+        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) sink(l0 + lane, k0 + kk, tile[lane * kShPitch + kk]);
     } else {
         for (uint32_t g = wave; g < kShLines; g += 4u) {
             const uint32_t line = l0 + g;
             if (line >= S.nlines) break;                       // (wave-uniform)
-            const float v = sh_scan_lit(S, sh_height(S, hblk, line, k0 + lane), carry[(size_t)blockIdx.x * S.nlines + line], k0 + lane);
-            uint32_t i, j;
-            if (sh_vertex(S, line, k0 + lane, i, j)) lit[(size_t)j * S.n + i] = v;
+            sink(line, k0 + lane, sh_scan_lit(S, sh_height(S, hblk, line, k0 + lane), in[line], k0 + lane));
         }
     }
+}
+
+template <bool ZMAJOR>
+__global__ __launch_bounds__(256) void k_shadow_lit(ShadowPlan S, const float *__restrict__ hblk, const float *__restrict__ carry,
+                                                    float *__restrict__ lit)
+{
+    sh_stage_lit<ZMAJOR>(S, hblk, carry + (size_t)blockIdx.x * S.nlines, [&](uint32_t line, uint32_t k, float v) {
+        uint32_t i, j;
+        if (sh_vertex(S, line, k, i, j)) lit[(size_t)j * S.n + i] = v;
+    });
 }
 
 // a sun without a horizontal component (or none at all): every vertex is lit

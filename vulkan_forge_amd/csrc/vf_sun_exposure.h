@@ -1,7 +1,8 @@
 // vf_sun_exposure.h -- sun exposure: the sum of the shadow fields of N suns, weighted, with an optional incidence cosine.
 //
-// The scan of vf_shadow.h over a batch of suns at once: the same three stages, with the sun's index in blockIdx.z and its ShadowPlan
-// read from a device array of ExposureSun records, so that a batch costs three launches per major axis however many suns it holds.
+// The scan of vf_shadow.h over a batch of suns at once: its three stage bodies (sh_stage_*), wrapped with the sun's index in blockIdx.z
+// and its ShadowPlan read from a device array of ExposureSun records, so that a batch costs three launches per major axis however many
+// suns it holds.
 // Every sun of a batch has its own carries (cmax[slot][chunk][line], `stride` floats per slot).  The last stage does not store lit: it
 // adds q = rint(((lit * c) * w) * 65536) to a field of 32-bit sums with a relaxed device-scope atomic.  One sun has one writer per
 // vertex (a vertex lies on one line of a plan), so the atomics meet only between suns, and integer addition commutes: the sums do not
@@ -69,28 +70,9 @@ template <bool ZMAJOR>
 __global__ __launch_bounds__(256) void k_exposure_chunk_max(const ExposureSun *__restrict__ suns, const float *__restrict__ hblk, float *__restrict__ cmax,
                                                             size_t stride)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const ShadowPlan &S = suns[blockIdx.z].S;
-    const uint32_t k0 = blockIdx.x * kShChunk, l0 = blockIdx.y * kShLines;
-    if (l0 >= S.nlines) return;                                // (a sun with fewer lines than the part's largest)
-    float *out = cmax + (size_t)blockIdx.z * stride + (size_t)blockIdx.x * S.nlines;
-    if constexpr (ZMAJOR) {
-        __shared__ float part[4][kShLines];
-        float m = -INFINITY;
-        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) m = fmaxf(m, sh_term(S, sh_height(S, hblk, l0 + lane, k0 + kk), k0 + kk));
-        part[wave][lane] = m;
-        __syncthreads();
-        if (wave == 0u && l0 + lane < S.nlines)
-            out[l0 + lane] = fmaxf(fmaxf(part[0][lane], part[1][lane]), fmaxf(part[2][lane], part[3][lane]));
-    } else {
-        for (uint32_t g = wave; g < kShLines; g += 4u) {
-            const uint32_t line = l0 + g;
-            if (line >= S.nlines) break;                       // (wave-uniform)
-            float m = sh_term(S, sh_height(S, hblk, line, k0 + lane), k0 + lane);
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-            if (lane == 0u) out[line] = m;
-        }
-    }
+    if (blockIdx.y * kShLines >= S.nlines) return;             // (a sun with fewer lines than the part's largest)
+    sh_stage_chunk_max<ZMAJOR>(S, hblk, cmax + (size_t)blockIdx.z * stride + (size_t)blockIdx.x * S.nlines);
 }
 
 // k_shadow_carry for sun blockIdx.y of the batch
@@ -98,16 +80,7 @@ template <int UNUSED>
 __global__ __launch_bounds__(256) void k_exposure_carry(const ExposureSun *__restrict__ suns, float *__restrict__ cmax, size_t stride)
 {
     const ShadowPlan &S = suns[blockIdx.y].S;
-    const uint32_t line = blockIdx.x * 256u + threadIdx.x;
-    if (line >= S.nlines) return;
-    float *c = cmax + (size_t)blockIdx.y * stride;
-    float run = -INFINITY;
-    for (uint32_t k = 0; k < S.nchunks; ++k) {
-        const size_t o = (size_t)k * S.nlines + line;
-        const float m = c[o];
-        c[o] = run;
-        run = fmaxf(run, m);
-    }
+    sh_stage_carry(S.nlines, S.nchunks, cmax + (size_t)blockIdx.y * stride);
 }
 
 // k_shadow_lit for sun blockIdx.z of the part: the adds are shaped as its stores are -- lane = step along a row for the x-major suns,
@@ -117,31 +90,10 @@ template <bool ZMAJOR, bool INCIDENCE>
 __global__ __launch_bounds__(256) void k_exposure_lit(const ExposureSun *__restrict__ suns, const float *__restrict__ hblk, const float *__restrict__ carry,
                                                       size_t stride, const float2 *__restrict__ slope, uint32_t *__restrict__ sum)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const ExposureSun &E = suns[blockIdx.z];
-    const ShadowPlan &S = E.S;
-    const uint32_t k0 = blockIdx.x * kShChunk, l0 = blockIdx.y * kShLines;
-    if (l0 >= S.nlines) return;
-    const float *in = carry + (size_t)blockIdx.z * stride + (size_t)blockIdx.x * S.nlines;
-    if constexpr (ZMAJOR) {
-        __shared__ float tile[kShLines * kShPitch];
-        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) tile[lane * kShPitch + kk] = sh_height(S, hblk, l0 + lane, k0 + kk);
-        __syncthreads();
-        for (uint32_t g = wave; g < kShLines; g += 4u) {
-            const uint32_t line = l0 + g;
-            const float c = line < S.nlines ? in[line] : -INFINITY;
-            tile[g * kShPitch + lane] = sh_scan_lit(S, tile[g * kShPitch + lane], c, k0 + lane);
-        }
-        __syncthreads();
-        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) se_add<INCIDENCE>(E, l0 + lane, k0 + kk, tile[lane * kShPitch + kk], slope, sum);
-    } else {
-        for (uint32_t g = wave; g < kShLines; g += 4u) {
-            const uint32_t line = l0 + g;
-            if (line >= S.nlines) break;                       // (wave-uniform)
-            const float v = sh_scan_lit(S, sh_height(S, hblk, line, k0 + lane), in[line], k0 + lane);
-            se_add<INCIDENCE>(E, line, k0 + lane, v, slope, sum);
-        }
-    }
+    if (blockIdx.y * kShLines >= E.S.nlines) return;
+    sh_stage_lit<ZMAJOR>(E.S, hblk, carry + (size_t)blockIdx.z * stride + (size_t)blockIdx.x * E.S.nlines,
+                         [&](uint32_t line, uint32_t k, float lit) { se_add<INCIDENCE>(E, line, k, lit, slope, sum); });
 }
 
 // The degenerate suns (no usable horizontal part: lit = 1 everywhere), all `count` of them: one add per vertex
@@ -165,17 +117,21 @@ __global__ __launch_bounds__(256) void k_exposure_slopes(const float *__restrict
     slope[(size_t)j * n + i] = se_slope(hblk, n, nb, exag, cell, i, j);
 }
 
-// sum -> exposure = (float)sum / 65536 (the conversion rounds to nearest even, the scaling is exact) and f = min(exposure / wtot, 1),
-// the field the tint pass reads (0 when no weight counts)
+// The end of a summed field, for this one and for the cumulative viewshed (vf_cumulative_viewshed.h): sum -> value = (float)sum / 65536
+// (the conversion rounds to nearest even, the scaling is exact) and frac = min(value / total, 1), the field the tint pass reads (0
+// when total is not > 0: no sun's weight counts).
+// The cumulative viewshed passes total = (float)N and reads frac as count / N: for it the fminf is the identity and total >= 1.  Every
+// observer adds at most 65536 to a vertex, so sum <= N * 65536; with N <= 65535 that bound is a float, and the conversion is monotonic,
+// so value <= N and value / N <= 1.
 template <int UNUSED>
-__global__ __launch_bounds__(256) void k_exposure_finish(const uint32_t *__restrict__ sum, uint32_t nv, float wtot, float *__restrict__ exposure,
-                                                         float *__restrict__ frac)
+__global__ __launch_bounds__(256) void k_sum_finish(const uint32_t *__restrict__ sum, uint32_t nv, float total, float *__restrict__ value,
+                                                    float *__restrict__ frac)
 {
     const uint32_t v = blockIdx.x * 256u + threadIdx.x;
     if (v >= nv) return;
     const float e = (float)sum[v] * (1.0f / 65536.0f);
-    exposure[v] = e;
-    frac[v] = wtot > 0.0f ? fminf(e / wtot, 1.0f) : 0.0f;
+    value[v] = e;
+    frac[v] = total > 0.0f ? fminf(e / total, 1.0f) : 0.0f;
 }
 
 } // namespace vf

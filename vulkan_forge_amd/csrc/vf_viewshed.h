@@ -99,20 +99,26 @@ __device__ __forceinline__ float vs_seen(const ViewshedPlan &V, float y, float y
     return 1.0f - fminf(fmaxf((e - V.bias) / V.softness, 0.0f), 1.0f);
 }
 
-// Chunk (blockIdx.x) of 64 lines (blockIdx.y) of quadrant 2 ZMAJOR + blockIdx.z: the maximum of each line's 64 terms ->
-// cmax[quadrant][chunk][line].  Lines that have left the grid by the chunk's first step are skipped (k_viewshed_carry and
-// k_viewshed_seen skip them by the same test).
+// ---- the three stages of the scan, stated once ----
+// Their bodies serve the single field's kernels below and the batched ones of vf_cumulative_viewshed.h, which wrap them: a wrapper
+// decodes its plan and quadrant from the grid, passes the base of *that plan's* carries and, for the last stage, a sink that takes
+// every value.  V comes by reference: a by-value kernel argument or a record in device memory.
+
+// the carries of a plan, cmax[quadrant][chunk][line]: where those of chunk `chunk` of quadrant q begin
+__device__ __forceinline__ size_t vs_carries(const ViewshedPlan &V, uint32_t q, uint32_t chunk) { return ((size_t)q * V.nchunks + chunk) * V.nlines; }
+
+// Chunk (blockIdx.x) of 64 lines (blockIdx.y) of quadrant q: the maximum of each line's 64 terms -> out[line], out = the plan's
+// cmax[q][chunk].  Lines that have left the grid by the chunk's first step are skipped (the other two stages skip them by the same
+// test).
 // ZMAJOR = false: memory runs along the steps -- lane = step, a wave reduces one line at a time.
 // ZMAJOR = true: memory runs across the lines -- lane = line, each wave walks a quarter of the steps, the quarters meet in LDS.
 template <bool ZMAJOR>
-__global__ __launch_bounds__(256) void k_viewshed_chunk_max(ViewshedPlan V, const float *__restrict__ hblk, float *__restrict__ cmax)
+__device__ __forceinline__ void vs_stage_chunk_max(const ViewshedPlan &V, uint32_t q, const float *__restrict__ hblk, float *__restrict__ out)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t q = (ZMAJOR ? 2u : 0u) + blockIdx.z;
     const uint32_t k0 = blockIdx.x * kShChunk + 1u, l0 = blockIdx.y * kShLines;
     if (!vs_group_live(V, q, l0, k0)) return;
     const float y_eye = vs_eye(V, hblk);
-    float *out = cmax + ((size_t)q * V.nchunks + blockIdx.x) * V.nlines;
     if constexpr (ZMAJOR) {
         __shared__ float part[4][kShLines];
         float m = -INFINITY;
@@ -139,21 +145,35 @@ __global__ __launch_bounds__(256) void k_viewshed_chunk_max(ViewshedPlan V, cons
     }
 }
 
-// per line of a quadrant (blockIdx.y): the chunk maxima -> the maximum of the chunks before each (in place), one thread per line,
-// as far as the line has vertices
+// quadrant 2 ZMAJOR + blockIdx.z
+template <bool ZMAJOR>
+__global__ __launch_bounds__(256) void k_viewshed_chunk_max(ViewshedPlan V, const float *__restrict__ hblk, float *__restrict__ cmax)
+{
+    const uint32_t q = (ZMAJOR ? 2u : 0u) + blockIdx.z;
+    vs_stage_chunk_max<ZMAJOR>(V, q, hblk, cmax + vs_carries(V, q, blockIdx.x));
+}
+
+// per line of quadrant q: the chunk maxima -> the maximum of the chunks before each (in place, c = the plan's cmax[q]), one thread
+// per line, as far as the line has vertices
+__device__ __forceinline__ void vs_stage_carry(const ViewshedPlan &V, uint32_t q, float *__restrict__ c)
+{
+    const uint32_t line = blockIdx.x * 256u + threadIdx.x;
+    if (line >= V.nlines) return;
+    float run = -INFINITY;
+    for (uint32_t k = 0; k < V.nchunks; ++k) {
+        if (!vs_live(V, q, line, k * kShChunk + 1u)) break;
+        const size_t o = (size_t)k * V.nlines + line;
+        const float m = c[o];
+        c[o] = run;
+        run = fmaxf(run, m);
+    }
+}
+
+// quadrant blockIdx.y
 template <int UNUSED>
 __global__ __launch_bounds__(256) void k_viewshed_carry(ViewshedPlan V, float *__restrict__ cmax)
 {
-    const uint32_t line = blockIdx.x * 256u + threadIdx.x, q = blockIdx.y;
-    if (line >= V.nlines) return;
-    float run = -INFINITY;
-    for (uint32_t c = 0; c < V.nchunks; ++c) {
-        if (!vs_live(V, q, line, c * kShChunk + 1u)) break;
-        const size_t o = ((size_t)q * V.nchunks + c) * V.nlines + line;
-        const float m = cmax[o];
-        cmax[o] = run;
-        run = fmaxf(run, m);
-    }
+    vs_stage_carry(V, blockIdx.y, cmax + vs_carries(V, blockIdx.y, 0u));
 }
 
 // lane = step k0 + lane of one line: its seen from its height y, its distance D and the line's carry into the chunk
@@ -165,31 +185,39 @@ __device__ __forceinline__ float vs_scan_seen(const ViewshedPlan &V, float y, fl
     return vs_seen(V, y, y_eye, D, M);
 }
 
-// the store of step k of a line: only by the line that owns the vertex -- c == c*(k, r), and a vertex on a diagonal belongs to the
-// x-major quadrants -- so every vertex has one writer
+// One writer per vertex: step k of a line of quadrant q writes its vertex (i, j), at minor offset r, only if the line owns it --
+// c == c*(k, r), and a vertex on a diagonal belongs to the x-major quadrants.  False: no vertex there, or another line's.
+__device__ __forceinline__ bool vs_owned(const ViewshedPlan &V, uint32_t q, uint32_t line, uint32_t k, uint32_t &i, uint32_t &j, int32_t &r)
+{
+    if (!vs_vertex(V, q, line, k, i, j, r)) return false;
+    if (q >= 2u && (uint32_t)(r < 0 ? -r : r) >= k) return false;
+    return vs_owner(V, k, r) == line;
+}
+
+// the store of step k of a line
 __device__ __forceinline__ void vs_store(const ViewshedPlan &V, uint32_t q, uint32_t line, uint32_t k, float v, float *__restrict__ seen)
 {
     uint32_t i, j;
     int32_t r;
-    if (!vs_vertex(V, q, line, k, i, j, r)) return;
-    if (q >= 2u && (uint32_t)(r < 0 ? -r : r) >= k) return;
-    if (vs_owner(V, k, r) != line) return;
-    seen[(size_t)j * V.n + i] = v;
+    if (vs_owned(V, q, line, k, i, j, r)) seen[(size_t)j * V.n + i] = v;
 }
 
+// The observer's own vertex lies on no line: one thread of a plan's launches writes its 1 -- the first of quadrant 0's first workgroup
 template <bool ZMAJOR>
-__global__ __launch_bounds__(256) void k_viewshed_seen(ViewshedPlan V, const float *__restrict__ hblk, const float *__restrict__ carry,
-                                                       float *__restrict__ seen)
+__device__ __forceinline__ bool vs_writes_observer(uint32_t q) { return !ZMAJOR && blockIdx.x == 0u && blockIdx.y == 0u && q == 0u && threadIdx.x == 0u; }
+
+// The scan inside chunk (blockIdx.x) of 64 lines (blockIdx.y) of quadrant q, seeded with in[line], in = the plan's carry[q][chunk]:
+// sink(q, line, k, seen) for every step of a live line, those without a vertex or of another line's vertex among them (the sink asks
+// vs_owned)
+template <bool ZMAJOR, class Sink>
+__device__ __forceinline__ void vs_stage_seen(const ViewshedPlan &V, uint32_t q, const float *__restrict__ hblk, const float *__restrict__ in, Sink sink)
 {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t q = (ZMAJOR ? 2u : 0u) + blockIdx.z;
     const uint32_t k0 = blockIdx.x * kShChunk + 1u, l0 = blockIdx.y * kShLines;
-    if (!ZMAJOR && blockIdx.x == 0u && blockIdx.y == 0u && blockIdx.z == 0u && threadIdx.x == 0u) seen[(size_t)V.jo * V.n + V.io] = 1.0f;   // the observer's own vertex
     if (!vs_group_live(V, q, l0, k0)) return;
     const float y_obs = cached_height(hblk, V.nb, V.io, V.jo) * V.exag;
     const float y_eye = y_obs + V.eye_height;
-    const bool blind = !isfinite(y_obs);                       // an observer without a height: the whole field is 1
-    const float *in = carry + ((size_t)q * V.nchunks + blockIdx.x) * V.nlines;
+    const bool blind = !isfinite(y_obs);                       // an observer without a height: 1 wherever a value goes
     if constexpr (ZMAJOR) {
         // rows of the grid are contiguous across the lines: heights come in and seen goes out with lane = line, the scan runs with
         // lane = step, and the 64 x 64 tile changes hands in LDS (distances are formed again where they are used)
@@ -208,7 +236,7 @@ __global__ __launch_bounds__(256) void k_viewshed_seen(ViewshedPlan V, const flo
             tile[g * kShPitch + lane] = blind ? 1.0f : v;
         }
         __syncthreads();
-        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) vs_store(V, q, l0 + lane, k0 + kk, tile[lane * kShPitch + kk], seen);
+        for (uint32_t kk = wave; kk < kShChunk; kk += 4u) sink(q, l0 + lane, k0 + kk, tile[lane * kShPitch + kk]);
     } else {
         for (uint32_t g = wave; g < kShLines; g += 4u) {
             const uint32_t line = l0 + g;
@@ -217,9 +245,20 @@ __global__ __launch_bounds__(256) void k_viewshed_seen(ViewshedPlan V, const flo
             float D;
             const float y = vs_height(V, hblk, q, line, k0 + lane, D);
             const float v = vs_scan_seen(V, y, y_eye, D, in[line]);
-            vs_store(V, q, line, k0 + lane, blind ? 1.0f : v, seen);
+            sink(q, line, k0 + lane, blind ? 1.0f : v);
         }
     }
+}
+
+// quadrant 2 ZMAJOR + blockIdx.z
+template <bool ZMAJOR>
+__global__ __launch_bounds__(256) void k_viewshed_seen(ViewshedPlan V, const float *__restrict__ hblk, const float *__restrict__ carry,
+                                                       float *__restrict__ seen)
+{
+    const uint32_t q = (ZMAJOR ? 2u : 0u) + blockIdx.z;
+    if (vs_writes_observer<ZMAJOR>(q)) seen[(size_t)V.jo * V.n + V.io] = 1.0f;
+    vs_stage_seen<ZMAJOR>(V, q, hblk, carry + vs_carries(V, q, blockIdx.x),
+                          [&](uint32_t q_, uint32_t line, uint32_t k, float v) { vs_store(V, q_, line, k, v, seen); });
 }
 
 // ---- the tint pass (contract item 4) ----
