@@ -937,6 +937,72 @@ int vf_terrain_read_haze_opacity(vf_terrain *t, float *dst);
 int vf_terrain_haze_opacity_device(vf_terrain *t, float *dev, void *stream);
 int vf_terrain_debug_haze_stage(vf_terrain *t, uint32_t repeats, float *ms);
 
+/* ---- flood analysis: what is under water at a level and reachable from its sources, and a water tint --
+ * The flood field is one float32 per grid vertex, (grid, grid) row-major (row j = z index, column i = x index): depth = level - h where
+ * the vertex is flooded, 0 elsewhere.  h is the displaced height of the vertex as the renderer draws it, and `level` is in units of h
+ * before exaggeration, exactly as contour levels are: vf_terrain_add_contours with the same level draws the shoreline.  A vertex is
+ * wet-able when h is finite and h < level; a non-finite vertex is never wet and blocks water.  A vertex is flooded when it is wet-able
+ * and 4-connected to a source through wet-able vertices: grid edges connect, diagonals do not, so a dike one vertex wide holds also
+ * where it runs diagonally.  The sources, by `mode`: VF_FLOOD_EVERYWHERE -- every wet-able vertex is flooded (the plain bathtub);
+ * VF_FLOOD_EDGES -- every wet-able vertex on the border of the grid; VF_FLOOD_SEEDS -- seeds_xz = count pairs (x, z) in the overlays'
+ * world frame, each snapped to a grid vertex as vf_terrain_set_viewshed snaps its observer; duplicates are allowed and a seed on a
+ * vertex that is not wet-able is no source.  The flooded set is the least fixpoint, so the field is fixed bit for bit whatever the
+ * order of evaluation.  It is computed by the first tinted frame or field call that needs it and again only after the
+ * heights, the level, the mode or the seeds' vertices have changed -- not for the colours, depth_full, the camera, the sun or the
+ * exaggeration; the spacing counts only through where the seeds snap.
+ *
+ * vf_terrain_set_flood: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then (behind the
+ * shadow, ambient and drape passes, under the sun-exposure and viewshed tints, the haze, the resolve of a supersampled handle and the
+ * overlays) paints the water: for a covered pixel of a primitive with a flooded vertex and three finite wd = level - h, d = wd
+ * interpolated at the pixel centre; where d > 0, s = min(d / depth_full, 1) and shallow_rgba is blended over the pixel with coverage
+ * 1 - s, then deep_rgba with coverage s, as vf_terrain_set_viewshed blends its colours.  The waterline follows the level inside the
+ * shoreline triangles; the tint is flat (not lit, not shadowed); water can show in a triangle whose only flooded vertex is diagonal to
+ * an unflooded wet-able one.  Geometry buffers and the diagnostics frames are unaffected.  VF_ERR_INVALID, nothing changed: level not
+ * finite; depth_full not > 0 or not finite; an unknown mode; with VF_FLOOD_SEEDS count outside 1 <= count <= 65535, seeds_xz == NULL or
+ * a seed that is not finite (seeds_xz and count are ignored in the other modes).  Whole-frame handles only: enabling on a band- or
+ * tile-sharded handle, sharding a handle with a flood enabled, and vf_terrain_render_batch / _batch_host on such a handle are
+ * VF_ERR_INVALID and change nothing.  The parameters are stored also with enable == 0 (the field calls below use them).  The setting
+ * survives height uploads.  A handle that never calls any of these allocates and launches nothing for them.
+ * vf_terrain_clear_flood: off, the defaults are back and everything made for the flood is freed.
+ * vf_terrain_read_flood_field: the field for the current heights, uniforms, level and sources into host memory (grid * grid floats),
+ * whether or not the flood is enabled for drawing; VF_ERR_INVALID before a flood is set.
+ * vf_terrain_flood_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream); later
+ * calls on the handle are ordered behind the copy by the library.
+ * vf_terrain_flood_info: the setting and, of the last computation of the field (0 before it), the flooded and the wet-able vertices,
+ * the launches of the propagation kernel up to and including the first that changed nothing (0 in mode EVERYWHERE), how many times the
+ * field was computed, and the passes queued per read-back.
+ * vf_terrain_read_flood_seeds: the seeds' vertices (i, j) for the current uniforms, count pairs of uint32. */
+#define VF_FLOOD_EVERYWHERE 0
+#define VF_FLOOD_EDGES 1
+#define VF_FLOOD_SEEDS 2
+#define VF_FLOOD_MAX_SEEDS 65535u
+#define VF_FLOOD_SHALLOW_RGBA 0x80E0B060u   /* (96, 176, 224, 128) as r | g << 8 | b << 16 | a << 24 */
+#define VF_FLOOD_DEEP_RGBA 0xE0A04010u      /* (16, 64, 160, 224) */
+#define VF_FLOOD_DEPTH_FULL 0.1f
+typedef struct vf_flood_info {
+    int32_t enabled, has_flood;
+    int32_t mode;
+    uint32_t count;           /* seeds; 0 in the other modes */
+    float level, depth_full;
+    uint8_t shallow_rgba[4], deep_rgba[4];
+    uint32_t flooded_vertices, wettable_vertices, passes, scans, group;
+} vf_flood_info;
+int vf_terrain_set_flood(vf_terrain *t, int enable, float level, int mode, const float *seeds_xz /* count x 2 */, uint32_t count,
+                         const uint8_t shallow_rgba[4], const uint8_t deep_rgba[4], float depth_full);
+int vf_terrain_clear_flood(vf_terrain *t);
+int vf_terrain_read_flood_field(vf_terrain *t, float *depth);
+int vf_terrain_flood_field_device(vf_terrain *t, float *dev_depth, void *stream);
+int vf_terrain_flood_info(vf_terrain *t, vf_flood_info *out);
+int vf_terrain_read_flood_seeds(vf_terrain *t, uint32_t *vertices /* count x 2 */);
+/* diagnostics: how many times the handle has computed its field so far; and the number of propagation passes queued per read-back of
+ * their `changed` words (0: the default; at most 64; the next call computes the field again); and the average time (HIP events,
+ * ms) of `repeats` computations of the field (ms[0]: every launch and every read-back of the host's loop) and of `repeats` launches of
+ * the tint pass (ms[1]) on the frame rendered last, drawn again into scratch buffers, each after one warm-up; it needs the flood
+ * enabled. */
+int vf_terrain_debug_flood_scans(vf_terrain *t, uint32_t *count);
+int vf_terrain_debug_flood_group(vf_terrain *t, uint32_t group);
+int vf_terrain_debug_flood_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

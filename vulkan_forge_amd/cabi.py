@@ -53,6 +53,8 @@ SYMBOLS = [
     "vf_terrain_debug_resolve_stage",
     "vf_terrain_set_haze", "vf_terrain_clear_haze", "vf_terrain_haze_info", "vf_terrain_read_haze_opacity", "vf_terrain_haze_opacity_device",
     "vf_terrain_debug_haze_stage",
+    "vf_terrain_set_flood", "vf_terrain_clear_flood", "vf_terrain_read_flood_field", "vf_terrain_flood_field_device", "vf_terrain_flood_info",
+    "vf_terrain_read_flood_seeds", "vf_terrain_debug_flood_scans", "vf_terrain_debug_flood_group", "vf_terrain_debug_flood_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -92,6 +94,12 @@ class SunExposureInfo(C.Structure):
 class HazeInfo(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("background", C.c_int32), ("density", C.c_float), ("start", C.c_float), ("falloff", C.c_float),
                 ("base", C.c_float), ("max_opacity", C.c_float), ("rgba", C.c_uint8 * 4), ("has_eye", C.c_int32), ("eye_y", C.c_float)]
+
+
+class FloodInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("has_flood", C.c_int32), ("mode", C.c_int32), ("count", C.c_uint32), ("level", C.c_float),
+                ("depth_full", C.c_float), ("shallow_rgba", C.c_uint8 * 4), ("deep_rgba", C.c_uint8 * 4), ("flooded_vertices", C.c_uint32),
+                ("wettable_vertices", C.c_uint32), ("passes", C.c_uint32), ("scans", C.c_uint32), ("group", C.c_uint32)]
 
 
 DIST_UNIQUE_ID_BYTES = 128
@@ -225,6 +233,15 @@ _PROTOS = {
     "vf_terrain_read_haze_opacity": (_i, [_vp, _vp]),
     "vf_terrain_haze_opacity_device": (_i, [_vp, _vp, _vp]),
     "vf_terrain_debug_haze_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_flood": (_i, [_vp, _i, _f, _i, _vp, _u32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _f]),
+    "vf_terrain_clear_flood": (_i, [_vp]),
+    "vf_terrain_read_flood_field": (_i, [_vp, _vp]),
+    "vf_terrain_flood_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_flood_info": (_i, [_vp, C.POINTER(FloodInfo)]),
+    "vf_terrain_read_flood_seeds": (_i, [_vp, _vp]),
+    "vf_terrain_debug_flood_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_debug_flood_group": (_i, [_vp, _u32]),
+    "vf_terrain_debug_flood_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -630,6 +647,62 @@ class Terrain:
         ms = _f()
         self._check(self.lib.vf_terrain_debug_haze_stage(self.t, int(repeats), C.byref(ms)))
         return ms.value
+
+    def set_flood(self, level, seeds=None, *, enabled=True, shallow_rgba=(96, 176, 224, 128), deep_rgba=(16, 64, 160, 224), depth_full=0.1):
+        """Flood analysis: the ground below `level` (units of h before exaggeration, as contour levels) that water reaches
+        from its sources, as a water tint of the frame.  seeds: None -- every vertex below the level; "edges" -- the water comes in over the
+        border of the grid; (N, 2) points (x, z) of the overlays' world frame.  Every parameter is stored by every call, also one that
+        disables, and steers flood_field() too."""
+        from ._flood import flood_args
+        en, lv, mode, xz, sh, dp, full = flood_args(level, seeds, enabled, shallow_rgba, deep_rgba, depth_full)
+        self._check(self.lib.vf_terrain_set_flood(self.t, en, lv, mode, None if xz is None else xz.ctypes.data, 0 if xz is None else xz.shape[0],
+                                                  (C.c_uint8 * 4)(*sh), (C.c_uint8 * 4)(*dp), full))
+
+    def clear_flood(self):
+        """The flood is off, its parameters are the defaults again and its buffers are freed."""
+        self._check(self.lib.vf_terrain_clear_flood(self.t))
+
+    def flood_field(self):
+        """The depth field for the current heights, uniforms, level and sources: (grid, grid) float32, level - h where flooded, else 0."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_flood_field(self.t, out.ctypes.data))
+        return out
+
+    def flood_field_device(self, dev_depth, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_flood_field_device(self.t, dev_depth, stream))
+
+    def flood_info(self):
+        """dict: the settings, vertices ((N, 2) uint32 of a seed list, else None) and, of the last computation, flooded_vertices,
+        wettable_vertices, passes; scans and the group size."""
+        from ._flood import flood_info
+        v = FloodInfo()
+        self._check(self.lib.vf_terrain_flood_info(self.t, C.byref(v)))
+        vertices = None
+        if v.count:
+            vertices = np.empty((v.count, 2), np.uint32)
+            if self.lib.vf_terrain_read_flood_seeds(self.t, vertices.ctypes.data) != VF_OK:
+                vertices = None                                # (uniforms not set yet)
+        return flood_info(v.enabled, v.has_flood, v.mode, v.count, vertices, v.level, v.depth_full, tuple(v.shallow_rgba), tuple(v.deep_rgba),
+                          v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group)
+
+    def flood_scans(self):
+        """How many times the handle has computed its flood field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_flood_scans(self.t, C.byref(n)))
+        return n.value
+
+    def flood_group(self, group=0):
+        """Force the number of propagation passes queued per read-back (diagnostics); 0: the default again."""
+        self._check(self.lib.vf_terrain_debug_flood_group(self.t, int(group)))
+
+    def flood_stage(self, repeats=5):
+        """(ms of one computation of the field, ms of the tint pass) as timed launches of their own on the frame rendered last
+        (diagnostics); it needs the flood enabled."""
+        ms = (_f * 2)()
+        self._check(self.lib.vf_terrain_debug_flood_stage(self.t, int(repeats), ms))
+        return ms[0], ms[1]
 
     def read_gbuffer(self, planes=("depth", "position", "normal", "primitive")):
         """Geometry buffers of the frame rendered last: dict plane name -> array."""

@@ -14,6 +14,7 @@
 #include "vf_resolve.h"               // templates only
 #include "vf_haze.h"                  // templates only
 #include "vf_overlay_haze.h"          // templates only
+#include "vf_flood.h"                 // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -539,6 +540,24 @@ struct vf_terrain {
         uint32_t rgba = VF_HAZE_RGBA;    // r | g << 8 | b << 16 | a << 24
         DevBuf<float> d_plane;           // (H, W) opacities behind vf_terrain_read_haze_opacity
     } hz;
+    // flood analysis: buffers made by the first tinted frame or field read; the field is computed again only when what
+    // it was made from has changed (not for the colours, depth_full, the camera, the sun or the exaggeration)
+    struct Flood {
+        bool enabled = false, have = false;      // have: a level is set (vf_terrain_set_flood)
+        float level = 0.0f;
+        int mode = VF_FLOOD_EVERYWHERE;
+        std::vector<float> xz;           // VF_FLOOD_SEEDS: the seeds in the overlays' world frame, (x, z) each
+        uint32_t shallow_rgba = VF_FLOOD_SHALLOW_RGBA, deep_rgba = VF_FLOOD_DEEP_RGBA;   // r | g << 8 | b << 16 | a << 24
+        float depth_full = VF_FLOOD_DEPTH_FULL;
+        VertexField depth;               // key: the bits of level, the mode, the length of the vertex list, the seeds' vertices (i, j) each
+        DevBuf<uint64_t> d_wet, d_fl;    // the masks, tile-major (vf_flood.h); they and d_wd stand as long as `depth` does: the tint reads them
+        DevBuf<float> d_wd;              // level - h, n x n
+        DevBuf<uint32_t> d_seeds;        // the seeds' vertices
+        DevBuf<uint32_t> d_ctl;          // kFloodMaxGroup `changed` words, then the two counts (one 64-bit word)
+        std::vector<uint32_t> ij;        // the host's copy of d_seeds (the source of its upload)
+        uint32_t forced_group = 0;       // vf_terrain_debug_flood_group; 0: kFloodGroup
+        uint32_t passes = 0, flooded = 0, wettable = 0;   // of the last computation
+    } fd;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -995,6 +1014,16 @@ static void exposure_release(vf_terrain *t)
     summed_reset(t->se);
 }
 
+// the flood: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced group size stay
+static void flood_release(vf_terrain *t)
+{
+    vf_terrain::Flood &H = t->fd;
+    H.depth.release(); H.d_wet.release(); H.d_fl.release(); H.d_wd.release(); H.d_seeds.release(); H.d_ctl.release();
+    const uint32_t scans = H.depth.scans, forced = H.forced_group;
+    H = vf_terrain::Flood();
+    H.depth.scans = scans; H.forced_group = forced;
+}
+
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
@@ -1090,7 +1119,7 @@ void vf_terrain_destroy(vf_terrain *t)
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     t->d_gb.release(); t->d_pick.release(); t->hz.d_plane.release();
-    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t); exposure_release(t);
+    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t); exposure_release(t); flood_release(t);
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -1269,6 +1298,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->se.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     if (t->ss > 1u && nranks != 1) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
     if (t->hz.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
+    if (t->fd.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a flood enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1399,6 +1429,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     if (t->hz.enabled) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
+    if (t->fd.enabled) return fail(VF_ERR_INVALID, "the handle has a flood enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1851,6 +1882,7 @@ static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, con
 static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int haze_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int flood_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 
 // The resolve of a supersampled handle's samples into its frame (vf_resolve.h).  Defined with the other supersampling calls below: the template is
 // instantiated there, behind the tile kernels and what they call, whose code -- PC-relative call offsets included -- keeps its place
@@ -1878,7 +1910,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool cumulative = t->cv.enabled && !diag;
     const bool exposure = t->se.enabled && !diag;
     const bool haze = t->hz.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure || haze;
+    const bool flood = t->fd.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure || haze || flood;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1945,6 +1978,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
         const int drc = relight_pass(t, s, P, V, S.work_count + 3, raster, drape_pass, shadows, ambient);
         if (drc != VF_OK) return drc;
+    }
+    if (flood && ntiles) {                                 // the flood's water: on the surface, so behind the relight passes and under the analysis tints
+        const int frc = flood_pass(t, s, P, V, S.work_count + 3, raster);
+        if (frc != VF_OK) return frc;
     }
     if (exposure && ntiles) {                              // the sun exposure's tint: behind both viewshed tints
         const int erc = exposure_pass(t, s, P, V, S.work_count + 3, raster);
@@ -2099,6 +2136,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
     if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
+    if (t->fd.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a flood enabled is not supported");
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
@@ -2123,6 +2161,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
     if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
+    if (t->fd.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a flood enabled is not supported");
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
@@ -3215,9 +3254,10 @@ int vf_terrain_set_shadows(vf_terrain *t, int enable, float strength, float soft
 static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
+static int flood_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 
 // The per-vertex fields a caller can have.  A new one is a feature struct that holds a VertexField, its *_field function and a row here.
-enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFieldExposure, kFields };
+enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFieldExposure, kFieldFlood, kFields };
 struct FieldRow {
     int (*compute)(vf_terrain *, const float *, hipStream_t, bool);   // its *_field function
     VertexField &(*cache)(vf_terrain *);                               // its buffer, key and scan counter
@@ -3232,6 +3272,8 @@ static const FieldRow kFieldTable[kFields] = {
       [](const vf_terrain *t) -> const char * { return t->cv.xz.empty() ? "no observers set (vf_terrain_set_cumulative_viewshed)" : nullptr; } },
     { exposure_field, [](vf_terrain *t) -> VertexField & { return t->se.sum.value; },
       [](const vf_terrain *t) -> const char * { return t->se.suns.empty() ? "no suns set (vf_terrain_set_sun_exposure)" : nullptr; } },
+    { flood_field, [](vf_terrain *t) -> VertexField & { return t->fd.depth; },
+      [](const vf_terrain *t) -> const char * { return t->fd.have ? nullptr : "no flood set (vf_terrain_set_flood)"; } },
 };
 
 // Field f for the live uniforms, heights and parameters, complete in its buffer; then to `host`, or to `dev` behind the work on
@@ -4682,6 +4724,211 @@ int vf_triangle_render(vf_ctx *ctx, uint32_t width, uint32_t height, uint8_t *rg
     if (err == hipSuccess) err = hipMemcpy(rgba_host, d, npx * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (err != hipSuccess) return fail(VF_ERR_HIP, std::string("triangle render failed: ") + hipGetErrorString(err));
+    return VF_OK;
+}
+
+// ---- flood analysis (vf_flood.h) -------------------------------------------------------------
+
+// Passes of k_flood_pass queued per read-back of their `changed` words.  16: at grid 4096 the fastest of 1, 4 and 16 on both probes of
+// DESIGN.md 4s (a read-back costs more than a dozen passes that find nothing to do)
+constexpr uint32_t kFloodGroup = 16, kFloodMaxGroup = 64;
+
+static uint32_t flood_tiles(const vf_terrain *t) { return (t->n + kFloodTile - 1u) / kFloodTile; }
+
+// the seeds' vertices (i, j) for the spacing of the uniforms `u`, snapped as the viewshed's observer is
+static void flood_vertices(const vf_terrain *t, const float *u, std::vector<uint32_t> &ij)
+{
+    const vf_terrain::Flood &H = t->fd;
+    const float spacing = spacing_of(u);
+    ij.resize(H.xz.size());
+    for (size_t k = 0; k < H.xz.size(); ++k) ij[k] = viewshed_index(t, H.xz[k], spacing);
+}
+
+// `depth` holds the field of the handle's heights, level and sources once this returns (the height cache must be current and ordered
+// before `s`, as for shadow_field); d_fl and d_wd hold what the tint reads.  The loop to the fixpoint runs here: groups of passes, each
+// with its own `changed` word, until the first pass that changed nothing.  force: compute it anyway.
+static int flood_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
+{
+    vf_terrain::Flood &H = t->fd;
+    if (!H.have) return fail(VF_ERR_INVALID, "no flood set (vf_terrain_set_flood)");
+    std::vector<uint32_t> ij;
+    if (H.mode == VF_FLOOD_SEEDS) flood_vertices(t, u, ij);
+    std::vector<uint32_t> key = key_of({ H.level });
+    key.push_back((uint32_t)H.mode); key.push_back((uint32_t)ij.size());
+    key.insert(key.end(), ij.begin(), ij.end());
+    bool current;
+    if (int rc = H.depth.prepare(t, key, force, "flood field allocation failed", &current)) return rc;
+    if (current) return VF_OK;
+    const uint32_t n = t->n, ftx = flood_tiles(t), tiles = ftx * ftx;
+    const size_t words = (size_t)tiles * kFloodTile, nv = (size_t)n * n, nctl = kFloodMaxGroup + 2u;
+    // (k_flood_depth packs the two counts into the halves of one 64-bit word and vf_flood_info reports them as uint32: vf_terrain_create
+    //  holds the grid to 8192, n x n to 2^26)
+    if (nv >> 32) return fail(VF_ERR_INVALID, "the grid is too large for the flood's 32-bit vertex counts");
+    if (H.d_wet.reserve(words, words) != hipSuccess || H.d_fl.reserve(words, words) != hipSuccess || H.d_wd.reserve(nv, nv) != hipSuccess
+        || H.d_ctl.reserve(nctl, nctl) != hipSuccess || H.d_seeds.reserve(ij.size(), ij.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VF_ERR_NOMEM, "flood mask allocation failed");
+    }
+    const dim3 rows(ftx, ftx * (kFloodTile / 4u)), threads(256);
+    const float *hblk = t->d_hblk;
+    if (H.mode == VF_FLOOD_EVERYWHERE)
+        hipLaunchKernelGGL((k_flood_wet<true>), rows, threads, 0, s, n, t->nb, ftx, ftx * kFloodTile, H.level, hblk, H.d_wet.p, H.d_fl.p, H.d_wd.p);
+    else
+        hipLaunchKernelGGL((k_flood_wet<false>), rows, threads, 0, s, n, t->nb, ftx, ftx * kFloodTile, H.level, hblk, H.d_wet.p, H.d_fl.p, H.d_wd.p);
+    VF_HIP_TRY(hipGetLastError());
+    uint32_t passes = 0;
+    if (H.mode != VF_FLOOD_EVERYWHERE) {
+        if (H.mode == VF_FLOOD_SEEDS) {
+            const uint32_t count = (uint32_t)(ij.size() / 2u);
+            H.ij.swap(ij);
+            VF_HIP_TRY(hipMemcpyAsync(H.d_seeds.p, H.ij.data(), H.ij.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
+            hipLaunchKernelGGL((k_flood_seed<false>), dim3((count + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)H.d_seeds.p, count,
+                               (const uint32_t *)H.d_wet.p, (uint32_t *)H.d_fl.p);
+        } else
+            hipLaunchKernelGGL((k_flood_seed<true>), dim3((4u * n + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)nullptr, 4u * n,
+                               (const uint32_t *)H.d_wet.p, (uint32_t *)H.d_fl.p);
+        VF_HIP_TRY(hipGetLastError());
+        const uint32_t G = std::min(H.forced_group ? H.forced_group : kFloodGroup, kFloodMaxGroup);
+        uint32_t changed[kFloodMaxGroup];
+        // (every pass that changes something floods at least one more vertex: nv + 1 launches cannot be reached)
+        for (bool done = false; !done && passes <= nv;) {
+            VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p, 0, G * sizeof(uint32_t), s));
+            for (uint32_t g = 0; g < G; ++g)
+                hipLaunchKernelGGL((k_flood_pass<0>), dim3(tiles), dim3(64), 0, s, ftx, ftx, (const uint64_t *)H.d_wet.p, H.d_fl.p, H.d_ctl.p + g);
+            VF_HIP_TRY(hipGetLastError());
+            VF_HIP_TRY(hipMemcpyAsync(changed, H.d_ctl.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            VF_HIP_TRY(hipStreamSynchronize(s));
+            for (uint32_t g = 0; g < G && !done; ++g) {
+                ++passes;
+                done = changed[g] == 0u;
+            }
+        }
+        if (passes > nv) return fail(VF_ERR_HIP, "flood propagation did not reach a fixpoint within n x n + 1 passes");   // (cannot happen: see above)
+    }
+    unsigned long long counts = 0ull;
+    VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p + kFloodMaxGroup, 0, sizeof counts, s));
+    hipLaunchKernelGGL((k_flood_depth<0>), dim3(ftx, (n + 3u) / 4u), threads, 0, s, n, ftx, (const uint64_t *)H.d_wet.p, (const uint64_t *)H.d_fl.p,
+                       (const float *)H.d_wd.p, H.depth.d.p, (unsigned long long *)(H.d_ctl.p + kFloodMaxGroup));
+    VF_HIP_TRY(hipGetLastError());
+    VF_HIP_TRY(hipMemcpyAsync(&counts, H.d_ctl.p + kFloodMaxGroup, sizeof counts, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));
+    H.passes = passes; H.flooded = (uint32_t)counts; H.wettable = (uint32_t)(counts >> 32);
+    H.depth.computed(t, key);
+    return VF_OK;
+}
+
+// Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
+static void flood_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    const vf_terrain::Flood &H = t->fd;
+    FloodTint T = {};
+    T.fl = (const uint32_t *)H.d_fl.p; T.wd = H.d_wd.p; T.decode = t->ctx->d_decode;
+    T.ntx = flood_tiles(t);
+    T.shallow_rgba = H.shallow_rgba; T.deep_rgba = H.deep_rgba; T.depth_full = H.depth_full;
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_flood_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    hipLaunchKernelGGL((k_flood_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+}
+
+// The water of a frame, on the draw stream behind its tile kernels (which stored the visibility) and the relight passes: the field if
+// it is stale, then the tint pass over the covered pixels
+static int flood_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    if (int rc = flood_field(t, t->inputs.u, s)) return rc;
+    flood_launch(t, s, P, V, redo, rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_flood(vf_terrain *t, int enable, float level, int mode, const float *seeds_xz, uint32_t count, const uint8_t shallow_rgba[4],
+                         const uint8_t deep_rgba[4], float depth_full)
+{
+    if (!t || !shallow_rgba || !deep_rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!std::isfinite(level)) return fail(VF_ERR_INVALID, "level must be finite");
+    if (!(std::isfinite(depth_full) && depth_full > 0.0f)) return fail(VF_ERR_INVALID, "depth_full must be a finite number > 0");
+    if (mode != VF_FLOOD_EVERYWHERE && mode != VF_FLOOD_EDGES && mode != VF_FLOOD_SEEDS) return fail(VF_ERR_INVALID, "unknown flood mode");
+    if (mode == VF_FLOOD_SEEDS) {
+        if (!seeds_xz) return fail(VF_ERR_INVALID, "NULL argument: the seeds");
+        if (count < 1u || count > VF_FLOOD_MAX_SEEDS) return fail(VF_ERR_INVALID, "a flood takes 1 to 65535 seeds");
+        for (size_t k = 0; k < (size_t)2u * count; ++k)
+            if (!std::isfinite(seeds_xz[k])) return fail(VF_ERR_INVALID, "the seeds must be finite");
+    } else count = 0u;
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "a flood needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    vf_terrain::Flood &H = t->fd;
+    const uint32_t sh = pack_rgba8(shallow_rgba), dp = pack_rgba8(deep_rgba);
+    std::vector<float> xz;
+    if (count) xz.assign(seeds_xz, seeds_xz + (size_t)2u * count);
+    if (H.enabled != (enable != 0) || !H.have || key_bits(H.level) != key_bits(level) || H.mode != mode || H.xz != xz || H.shallow_rgba != sh
+        || H.deep_rgba != dp || H.depth_full != depth_full)
+        t->inputs_gen++;
+    H.enabled = enable != 0; H.have = true;
+    H.level = level; H.mode = mode;
+    H.xz.swap(xz);
+    H.shallow_rgba = sh; H.deep_rgba = dp; H.depth_full = depth_full;
+    return VF_OK;
+}
+
+int vf_terrain_clear_flood(vf_terrain *t)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (t->fd.enabled) t->inputs_gen++;
+    flood_release(t);
+    return VF_OK;
+}
+
+int vf_terrain_read_flood_field(vf_terrain *t, float *depth) { return field_out(t, kFieldFlood, depth, nullptr, nullptr); }
+int vf_terrain_flood_field_device(vf_terrain *t, float *dev_depth, void *stream) { return field_out(t, kFieldFlood, nullptr, dev_depth, stream); }
+
+int vf_terrain_flood_info(vf_terrain *t, vf_flood_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::Flood &H = t->fd;
+    *out = vf_flood_info();
+    out->enabled = H.enabled ? 1 : 0; out->has_flood = H.have ? 1 : 0;
+    out->mode = H.mode; out->count = (uint32_t)(H.xz.size() / 2u);
+    out->level = H.level; out->depth_full = H.depth_full;
+    for (int k = 0; k < 4; ++k) { out->shallow_rgba[k] = (uint8_t)(H.shallow_rgba >> (8 * k)); out->deep_rgba[k] = (uint8_t)(H.deep_rgba >> (8 * k)); }
+    out->flooded_vertices = H.flooded; out->wettable_vertices = H.wettable; out->passes = H.passes; out->scans = H.depth.scans;
+    out->group = std::min(H.forced_group ? H.forced_group : kFloodGroup, kFloodMaxGroup);
+    return VF_OK;
+}
+
+int vf_terrain_read_flood_seeds(vf_terrain *t, uint32_t *vertices)
+{
+    if (!t || !vertices) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->fd.xz.empty()) return fail(VF_ERR_INVALID, "no seeds set (vf_terrain_set_flood with VF_FLOOD_SEEDS)");
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    std::vector<uint32_t> ij;
+    flood_vertices(t, t->inputs.u, ij);
+    std::memcpy(vertices, ij.data(), ij.size() * sizeof(uint32_t));
+    return VF_OK;
+}
+
+int vf_terrain_debug_flood_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldFlood, count); }
+
+int vf_terrain_debug_flood_stage(vf_terrain *t, uint32_t repeats, float ms[2])
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->fd.have || !t->fd.enabled) return fail(VF_ERR_INVALID, "no flood enabled (vf_terrain_set_flood)");
+    if (repeats == 0) repeats = 1;
+    RelightStage G;
+    if (int rc = G.open(t)) return rc;
+    if (int rc = flood_field(t, G.u, G.s)) return rc;          // (the tint's launches below read the masks of the current field)
+    return G.time_pair(repeats, ms, "flood", [&] { return flood_field(t, G.u, G.s, true); },
+                       [&] { flood_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
+}
+
+int vf_terrain_debug_flood_group(vf_terrain *t, uint32_t group)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    if (group > kFloodMaxGroup) return fail(VF_ERR_INVALID, "a group holds at most 64 passes");
+    if (t->fd.forced_group != group) t->fd.depth.valid = false;   // (the next call computes the field again, with this group size)
+    t->fd.forced_group = group;
     return VF_OK;
 }
 

@@ -975,6 +975,68 @@ public:
         if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
         return a;
     }
+    // extension: flood analysis (argument rules: vulkan_forge_amd/_flood.py)
+    void set_flood(py::object level, py::object seeds, py::object enabled, py::object shallow_rgba, py::object deep_rgba, py::object depth_full)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._flood").attr("flood_args")(level, seeds, enabled, shallow_rgba, deep_rgba, depth_full);
+        uint8_t sh[4], dp[4];
+        py::tuple ts = a[4].cast<py::tuple>(), td = a[5].cast<py::tuple>();
+        for (int k = 0; k < 4; ++k) { sh[k] = ts[k].cast<uint8_t>(); dp[k] = td[k].cast<uint8_t>(); }
+        const float *xz = nullptr;
+        uint32_t count = 0;
+        py::array_t<float, py::array::c_style | py::array::forcecast> arr;
+        if (!a[3].is_none()) {
+            arr = a[3].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+            xz = arr.data(); count = (uint32_t)arr.shape(0);
+        }
+        Borrow b(busy);
+        check(vf_terrain_set_flood(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<int>(), xz, count, sh, dp, a[6].cast<float>()));
+        frame_current = false;
+    }
+    void clear_flood()
+    {
+        Borrow b(busy);
+        check(vf_terrain_clear_flood(t));
+        frame_current = false;
+    }
+    py::array_t<float> flood_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_flood_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::object flood_info()
+    {
+        Borrow b(busy);
+        vf_flood_info v;
+        check(vf_terrain_flood_info(t, &v));
+        py::object vertices = py::none();
+        if (v.count) {
+            py::array_t<uint32_t> a({ (py::ssize_t)v.count, (py::ssize_t)2 });
+            if (vf_terrain_read_flood_seeds(t, a.mutable_data()) == VF_OK) vertices = a;   // (else: uniforms not set yet)
+        }
+        return py::module_::import("vulkan_forge_amd._flood").attr("flood_info")(
+            v.enabled, v.has_flood, v.mode, v.count, vertices, v.level, v.depth_full,
+            py::make_tuple(v.shallow_rgba[0], v.shallow_rgba[1], v.shallow_rgba[2], v.shallow_rgba[3]),
+            py::make_tuple(v.deep_rgba[0], v.deep_rgba[1], v.deep_rgba[2], v.deep_rgba[3]),
+            v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group);
+    }
+    void debug_flood_group(uint32_t group)
+    {
+        Borrow b(busy);
+        check(vf_terrain_debug_flood_group(t, group));
+    }
+    uint32_t debug_flood_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_flood_scans(t, &count));
+        return count;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1425,6 +1487,24 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
         .def("haze_opacity", &T::haze_opacity,
              "(height, width) float32 (the sample size on a supersampled object): the haze opacity of every pixel of the current frame for\n"
              "the stored settings, enabled or not; 0 where the pass leaves the pixel.")
+        .def("set_flood", &T::set_flood, py::arg("level"), py::arg("seeds") = py::none(), py::kw_only(), py::arg("enabled") = true,
+             py::arg("shallow_rgba") = py::make_tuple(96, 176, 224, 128), py::arg("deep_rgba") = py::make_tuple(16, 64, 160, 224),
+             py::arg("depth_full") = VF_FLOOD_DEPTH_FULL,
+             "Flood analysis (DESIGN.md 4s): paint the ground that lies below `level` and that water can reach.  level is in units of the\n"
+             "height before exaggeration, as contour levels are: add_contours([level]) draws the shoreline.  seeds=None: every vertex below\n"
+             "the level (the plain bathtub); seeds=\"edges\": water comes in over the border of the grid; seeds=(N, 2) points (x, z) in the\n"
+             "overlays' world frame, 1 <= N <= 65535, each snapped to the nearest grid vertex: water spreads from them through 4-connected\n"
+             "vertices below the level, so ground behind a dike stays dry.  The tint is flat: shallow_rgba at the waterline, deep_rgba where\n"
+             "the water is depth_full deep or more, blended in between.  Every parameter is stored by every call, also one that disables,\n"
+             "and steers flood_field() too.")
+        .def("clear_flood", &T::clear_flood, "The flood is off, its parameters are the defaults again, its buffers are freed.")
+        .def("flood_field", &T::flood_field,
+             "(grid, grid) float32, row j = z index, column i = x index: the water depth level - h where the vertex is flooded, else 0.")
+        .def("flood_info", &T::flood_info,
+             "dict(enabled, level, mode, seeds (N), vertices ((N, 2) uint32 (i, j)), shallow_rgba, deep_rgba, depth_full, flooded_vertices,\n"
+             "wettable_vertices, passes, scans, group); the counts and passes are those of the last computation of the field.")
+        .def("debug_flood_group", &T::debug_flood_group, py::arg("group") = 0)
+        .def("debug_flood_scans", &T::debug_flood_scans)
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
