@@ -1003,6 +1003,75 @@ int vf_terrain_debug_flood_scans(vf_terrain *t, uint32_t *count);
 int vf_terrain_debug_flood_group(vf_terrain *t, uint32_t group);
 int vf_terrain_debug_flood_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
 
+/* ---- spill analysis: the level the water must reach at its sources before a vertex gets wet, and a sink tint --
+ * The spill field is one float32 per grid vertex, (grid, grid) row-major (row j = z index, column i = x index): the minimum, over
+ * 4-connected paths of passable vertices from a source to the vertex, of the maximum h on the path, both ends counted; +inf where no
+ * path arrives and where the vertex is not passable.  h is the displaced height of the vertex as the renderer draws it, in the units
+ * of contour and flood levels.  A vertex is passable when h is finite; a non-finite vertex is never reached and blocks water.  All
+ * comparisons take the total order of key(x) = bits ^ (sign ? 0xFFFFFFFF : 0x80000000): the float order on finite values, -0 below
+ * +0.  The sources, by `mode`: VF_SPILL_EDGES -- every passable vertex on the border of the grid: the field is the depression-filled
+ * surface; VF_SPILL_SEEDS -- seeds_xz = count pairs (x, z) in the overlays' world frame, each snapped to a grid vertex as
+ * vf_terrain_set_flood snaps its seeds; duplicates are allowed and a seed on a vertex that is not passable is no source: the set
+ * spill < L is what vf_terrain_set_flood floods at level L from the same seeds.  The field is the greatest fixpoint of a relaxation
+ * of min and max of input heights, so it is fixed bit for bit whatever the order of evaluation.  The sink depth is
+ * sd = spill - h where that is finite, 0 elsewhere: the depth of the closed basins.  The field is computed by the first tinted frame
+ * or field call that needs it and again only after the heights, the mode or the seeds' vertices have changed -- not for the colours,
+ * depth_full, the camera, the sun or the exaggeration; the spacing counts only through where the seeds snap.
+ *
+ * vf_terrain_set_spill: enable != 0 -- vf_terrain_render draws the frame as before, with the visibility store on, then (directly
+ * behind the flood's water, under the sun-exposure and viewshed tints, the haze, the resolve of a supersampled handle and the overlays)
+ * paints the sinks: for a covered pixel of a primitive with three finite sd that are not all 0, d = sd interpolated at the pixel
+ * centre; where d > 0, s = min(d / depth_full, 1) and shallow_rgba is blended over the pixel with coverage 1 - s, then deep_rgba with
+ * coverage s, as vf_terrain_set_flood blends its colours.  Geometry buffers and the diagnostics frames are unaffected.
+ * VF_ERR_INVALID, nothing changed: depth_full not > 0 or not finite; an unknown mode; with VF_SPILL_SEEDS count outside
+ * 1 <= count <= 65535, seeds_xz == NULL or a seed that is not finite (seeds_xz and count are ignored with VF_SPILL_EDGES).
+ * Whole-frame handles only: enabling on a band- or tile-sharded handle, sharding a handle with the spill enabled, and
+ * vf_terrain_render_batch / _batch_host on such a handle are VF_ERR_INVALID and change nothing.  The parameters are stored also with enable == 0 (the field
+ * calls below use them).  The setting survives height uploads.  A handle that never calls any of these allocates and launches nothing
+ * for them.
+ * vf_terrain_clear_spill: off, the defaults are back and everything made for the spill is freed.
+ * vf_terrain_read_spill_field: the spill field for the current heights, uniforms and sources into host memory (grid * grid floats),
+ * whether or not the spill is enabled for drawing; VF_ERR_INVALID before vf_terrain_set_spill.
+ * vf_terrain_spill_field_device: the same into device memory, copied asynchronously on `stream` (NULL: the context's stream); later
+ * calls on the handle are ordered behind the copy by the library.
+ * vf_terrain_read_sink_depth: the sink depth into host memory (grid * grid floats); VF_ERR_INVALID before vf_terrain_set_spill.
+ * vf_terrain_spill_info: the setting and, of the last computation of the field (0 before it), the vertices a path reaches, the
+ * vertices with a finite sd > 0, the launches of the relaxation kernel up to and including the first that changed nothing, the tiles
+ * that did not leave such a launch at once (their activity word was set), how many times the field was computed, and the passes
+ * queued per read-back.
+ * vf_terrain_read_spill_seeds: the seeds' vertices (i, j) for the current uniforms, count pairs of uint32. */
+#define VF_SPILL_EDGES 1
+#define VF_SPILL_SEEDS 2
+#define VF_SPILL_MAX_SEEDS 65535u
+#define VF_SPILL_SHALLOW_RGBA 0x80E0B060u   /* (96, 176, 224, 128) as r | g << 8 | b << 16 | a << 24 */
+#define VF_SPILL_DEEP_RGBA 0xE0A04010u      /* (16, 64, 160, 224) */
+#define VF_SPILL_DEPTH_FULL 0.1f
+#define VF_SPILL_GROUP_NO_FLAGS 0x80000000u /* vf_terrain_debug_spill_group: or-ed into `group`, every tile runs in every pass */
+typedef struct vf_spill_info {
+    int32_t enabled, has_spill;
+    int32_t mode;
+    uint32_t count;           /* seeds; 0 with VF_SPILL_EDGES */
+    float depth_full;
+    uint8_t shallow_rgba[4], deep_rgba[4];
+    uint32_t reached_vertices, sink_vertices, passes, scans, group, tile_runs;
+} vf_spill_info;
+int vf_terrain_set_spill(vf_terrain *t, int enable, int mode, const float *seeds_xz /* count x 2 */, uint32_t count,
+                         const uint8_t shallow_rgba[4], const uint8_t deep_rgba[4], float depth_full);
+int vf_terrain_clear_spill(vf_terrain *t);
+int vf_terrain_read_spill_field(vf_terrain *t, float *spill);
+int vf_terrain_spill_field_device(vf_terrain *t, float *dev_spill, void *stream);
+int vf_terrain_read_sink_depth(vf_terrain *t, float *depth);
+int vf_terrain_spill_info(vf_terrain *t, vf_spill_info *out);
+int vf_terrain_read_spill_seeds(vf_terrain *t, uint32_t *vertices /* count x 2 */);
+/* diagnostics: how many times the handle has computed its field so far; and the number of relaxation passes queued per read-back of
+ * their `changed` words (0: the default; at most 64; VF_SPILL_GROUP_NO_FLAGS or-ed in: the activity flags are ignored; the next call
+ * computes the field again); and the average time (HIP events, ms) of `repeats` computations of the field (ms[0]: every launch and
+ * every read-back of the host's loop) and of `repeats` launches of the tint pass (ms[1]) on the frame rendered last, drawn again into
+ * scratch buffers, each after one warm-up; it needs the spill enabled. */
+int vf_terrain_debug_spill_scans(vf_terrain *t, uint32_t *count);
+int vf_terrain_debug_spill_group(vf_terrain *t, uint32_t group);
+int vf_terrain_debug_spill_stage(vf_terrain *t, uint32_t repeats, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

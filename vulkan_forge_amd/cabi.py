@@ -55,6 +55,9 @@ SYMBOLS = [
     "vf_terrain_debug_haze_stage",
     "vf_terrain_set_flood", "vf_terrain_clear_flood", "vf_terrain_read_flood_field", "vf_terrain_flood_field_device", "vf_terrain_flood_info",
     "vf_terrain_read_flood_seeds", "vf_terrain_debug_flood_scans", "vf_terrain_debug_flood_group", "vf_terrain_debug_flood_stage",
+    "vf_terrain_set_spill", "vf_terrain_clear_spill", "vf_terrain_read_spill_field", "vf_terrain_spill_field_device", "vf_terrain_read_sink_depth",
+    "vf_terrain_spill_info", "vf_terrain_read_spill_seeds", "vf_terrain_debug_spill_scans", "vf_terrain_debug_spill_group",
+    "vf_terrain_debug_spill_stage",
     "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
     "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
 ]
@@ -100,6 +103,12 @@ class FloodInfo(C.Structure):
     _fields_ = [("enabled", C.c_int32), ("has_flood", C.c_int32), ("mode", C.c_int32), ("count", C.c_uint32), ("level", C.c_float),
                 ("depth_full", C.c_float), ("shallow_rgba", C.c_uint8 * 4), ("deep_rgba", C.c_uint8 * 4), ("flooded_vertices", C.c_uint32),
                 ("wettable_vertices", C.c_uint32), ("passes", C.c_uint32), ("scans", C.c_uint32), ("group", C.c_uint32)]
+
+
+class SpillInfo(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("has_spill", C.c_int32), ("mode", C.c_int32), ("count", C.c_uint32), ("depth_full", C.c_float),
+                ("shallow_rgba", C.c_uint8 * 4), ("deep_rgba", C.c_uint8 * 4), ("reached_vertices", C.c_uint32), ("sink_vertices", C.c_uint32),
+                ("passes", C.c_uint32), ("scans", C.c_uint32), ("group", C.c_uint32), ("tile_runs", C.c_uint32)]
 
 
 DIST_UNIQUE_ID_BYTES = 128
@@ -242,6 +251,16 @@ _PROTOS = {
     "vf_terrain_debug_flood_scans": (_i, [_vp, C.POINTER(_u32)]),
     "vf_terrain_debug_flood_group": (_i, [_vp, _u32]),
     "vf_terrain_debug_flood_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
+    "vf_terrain_set_spill": (_i, [_vp, _i, _i, _vp, _u32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _f]),
+    "vf_terrain_clear_spill": (_i, [_vp]),
+    "vf_terrain_read_spill_field": (_i, [_vp, _vp]),
+    "vf_terrain_spill_field_device": (_i, [_vp, _vp, _vp]),
+    "vf_terrain_read_sink_depth": (_i, [_vp, _vp]),
+    "vf_terrain_spill_info": (_i, [_vp, C.POINTER(SpillInfo)]),
+    "vf_terrain_read_spill_seeds": (_i, [_vp, _vp]),
+    "vf_terrain_debug_spill_scans": (_i, [_vp, C.POINTER(_u32)]),
+    "vf_terrain_debug_spill_group": (_i, [_vp, _u32]),
+    "vf_terrain_debug_spill_stage": (_i, [_vp, _u32, C.POINTER(_f)]),
     "vf_dem_create": (_i, [_vp, C.POINTER(_vp)]),
     "vf_dem_destroy": (None, [_vp]),
     "vf_dem_set_heights_f32": (_i, [_vp, _vp, _u32, _u32, _f]),
@@ -702,6 +721,70 @@ class Terrain:
         (diagnostics); it needs the flood enabled."""
         ms = (_f * 2)()
         self._check(self.lib.vf_terrain_debug_flood_stage(self.t, int(repeats), ms))
+        return ms[0], ms[1]
+
+    def set_spill(self, seeds="edges", *, enabled=True, shallow_rgba=(96, 176, 224, 128), deep_rgba=(16, 64, 160, 224), depth_full=0.1):
+        """Spill analysis: the level the water must reach at the sources before a vertex gets wet, and a tint of the
+        closed basins by their depth spill - h.  seeds: "edges" -- the border of the grid (the depression-filled surface); (N, 2) points
+        (x, z) of the overlays' world frame.  Every parameter is stored by every call, also one that disables, and steers the field
+        calls too."""
+        from ._spill import spill_args
+        en, mode, xz, sh, dp, full = spill_args(seeds, enabled, shallow_rgba, deep_rgba, depth_full)
+        self._check(self.lib.vf_terrain_set_spill(self.t, en, mode, None if xz is None else xz.ctypes.data, 0 if xz is None else xz.shape[0],
+                                                  (C.c_uint8 * 4)(*sh), (C.c_uint8 * 4)(*dp), full))
+
+    def clear_spill(self):
+        """The spill is off, its parameters are the defaults again and its buffers are freed."""
+        self._check(self.lib.vf_terrain_clear_spill(self.t))
+
+    def spill_field(self):
+        """The spill field for the current heights, uniforms and sources: (grid, grid) float32, +inf where no path arrives."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_spill_field(self.t, out.ctypes.data))
+        return out
+
+    def spill_field_device(self, dev_spill, stream=None):
+        """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
+        self._check(self.lib.vf_terrain_spill_field_device(self.t, dev_spill, stream))
+
+    def sink_depth_field(self):
+        """(grid, grid) float32: spill - h where that is finite, 0 elsewhere."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(self.lib.vf_terrain_read_sink_depth(self.t, out.ctypes.data))
+        return out
+
+    def spill_info(self):
+        """dict: the settings, vertices ((N, 2) uint32 of a seed list, else None) and, of the last computation, reached_vertices,
+        sink_vertices, passes, tile_runs; scans and the group size."""
+        from ._spill import spill_info
+        v = SpillInfo()
+        self._check(self.lib.vf_terrain_spill_info(self.t, C.byref(v)))
+        vertices = None
+        if v.count:
+            vertices = np.empty((v.count, 2), np.uint32)
+            if self.lib.vf_terrain_read_spill_seeds(self.t, vertices.ctypes.data) != VF_OK:
+                vertices = None                                # (uniforms not set yet)
+        return spill_info(v.enabled, v.has_spill, v.mode, v.count, vertices, v.depth_full, tuple(v.shallow_rgba), tuple(v.deep_rgba),
+                          v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs)
+
+    def spill_scans(self):
+        """How many times the handle has computed its spill field."""
+        n = _u32()
+        self._check(self.lib.vf_terrain_debug_spill_scans(self.t, C.byref(n)))
+        return n.value
+
+    def spill_group(self, group=0, flags=True):
+        """Force the number of relaxation passes queued per read-back (diagnostics); 0: the default again.  flags=False: the activity
+        flags are ignored, every tile runs in every pass."""
+        self._check(self.lib.vf_terrain_debug_spill_group(self.t, int(group) | (0 if flags else 0x80000000)))
+
+    def spill_stage(self, repeats=5):
+        """(ms of one computation of the field, ms of the tint pass) as timed launches of their own on the frame rendered last
+        (diagnostics); it needs the spill enabled."""
+        ms = (_f * 2)()
+        self._check(self.lib.vf_terrain_debug_spill_stage(self.t, int(repeats), ms))
         return ms[0], ms[1]
 
     def read_gbuffer(self, planes=("depth", "position", "normal", "primitive")):

@@ -15,6 +15,7 @@
 #include "vf_haze.h"                  // templates only
 #include "vf_overlay_haze.h"          // templates only
 #include "vf_flood.h"                 // templates only
+#include "vf_spill.h"                 // templates only
 #include "vf_line_loop.h"
 
 #include <algorithm>
@@ -558,6 +559,25 @@ struct vf_terrain {
         uint32_t forced_group = 0;       // vf_terrain_debug_flood_group; 0: kFloodGroup
         uint32_t passes = 0, flooded = 0, wettable = 0;   // of the last computation
     } fd;
+    // spill analysis: buffers made by the first tinted frame or field read; the field is computed again only when what
+    // it was made from has changed (not for the colours or depth_full)
+    struct Spill {
+        bool enabled = false, have = false;      // have: sources are set (vf_terrain_set_spill)
+        int mode = VF_SPILL_EDGES;
+        std::vector<float> xz;           // VF_SPILL_SEEDS: the seeds in the overlays' world frame, (x, z) each
+        uint32_t shallow_rgba = VF_SPILL_SHALLOW_RGBA, deep_rgba = VF_SPILL_DEEP_RGBA;   // r | g << 8 | b << 16 | a << 24
+        float depth_full = VF_SPILL_DEPTH_FULL;
+        VertexField spill;               // key: the mode, the length of the vertex list, the seeds' vertices (i, j) each
+        DevBuf<float> d_sd;              // spill - h, n x n; stands as long as `spill` does: the tint and the sink-depth read take it
+        DevBuf<uint32_t> d_hk, d_w;      // the keys of h and of the spill, tile-major (vf_spill.h)
+        DevBuf<uint32_t> d_act;          // the activity words: two arrays of one word per tile
+        DevBuf<uint32_t> d_seeds;        // the seeds' vertices
+        DevBuf<uint32_t> d_ctl;          // kSpillMaxGroup `changed` words, then the two counts (one 64-bit word), then tile_runs
+        std::vector<uint32_t> ij;        // the host's copy of d_seeds (the source of its upload)
+        uint32_t forced_group = 0;       // vf_terrain_debug_spill_group; 0: kSpillGroup
+        bool no_flags = false;           // vf_terrain_debug_spill_group with VF_SPILL_GROUP_NO_FLAGS: every tile runs in every pass
+        uint32_t passes = 0, reached = 0, sinks = 0, tile_runs = 0;   // of the last computation
+    } sp;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
     static constexpr uint32_t kBatchRing = 3;
@@ -1024,6 +1044,17 @@ static void flood_release(vf_terrain *t)
     H.depth.scans = scans; H.forced_group = forced;
 }
 
+// the spill: gone, as if the handle never asked (the caller has synchronised); the scan counter and the forced group settings stay
+static void spill_release(vf_terrain *t)
+{
+    vf_terrain::Spill &H = t->sp;
+    H.spill.release(); H.d_sd.release(); H.d_hk.release(); H.d_w.release(); H.d_act.release(); H.d_seeds.release(); H.d_ctl.release();
+    const uint32_t scans = H.spill.scans, forced = H.forced_group;
+    const bool no_flags = H.no_flags;
+    H = vf_terrain::Spill();
+    H.spill.scans = scans; H.forced_group = forced; H.no_flags = no_flags;
+}
+
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
                       int lut_is_srgb, vf_terrain **out)
 {
@@ -1119,7 +1150,7 @@ void vf_terrain_destroy(vf_terrain *t)
     void *ptrs[] = { t->slab, t->d_height_own, t->d_vis, t->d_rgba_scratch, t->d_diag, t->d_xrecv, t->d_xband, t->d_batch[0], t->d_batch[1], t->d_batch[2] };
     for (void *p : ptrs) if (p) (void)hipFree(p);
     t->d_gb.release(); t->d_pick.release(); t->hz.d_plane.release();
-    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t); exposure_release(t); flood_release(t);
+    shadow_release(t); ambient_release(t); viewshed_release(t); cumulative_release(t); exposure_release(t); flood_release(t); spill_release(t);
     drape_release(t);
     for (auto &e : t->batch_drawn) if (e) (void)hipEventDestroy(e);
     for (auto &e : t->batch_copied) if (e) (void)hipEventDestroy(e);
@@ -1299,6 +1330,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (t->ss > 1u && nranks != 1) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
     if (t->hz.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
     if (t->fd.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a flood enabled: it needs a whole-frame handle");
+    if (t->sp.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has the spill enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1430,6 +1462,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (t->se.enabled) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
     if (t->hz.enabled) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
     if (t->fd.enabled) return fail(VF_ERR_INVALID, "the handle has a flood enabled: it needs a whole-frame handle");
+    if (t->sp.enabled) return fail(VF_ERR_INVALID, "the handle has the spill enabled: it needs a whole-frame handle");
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1883,6 +1916,7 @@ static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, c
 static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int haze_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 static int flood_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int spill_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
 
 // The resolve of a supersampled handle's samples into its frame (vf_resolve.h).  Defined with the other supersampling calls below: the template is
 // instantiated there, behind the tile kernels and what they call, whose code -- PC-relative call offsets included -- keeps its place
@@ -1911,7 +1945,8 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     const bool exposure = t->se.enabled && !diag;
     const bool haze = t->hz.enabled && !diag;
     const bool flood = t->fd.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure || haze || flood;
+    const bool spill = t->sp.enabled && !diag;
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure || haze || flood || spill;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -1982,6 +2017,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     if (flood && ntiles) {                                 // the flood's water: on the surface, so behind the relight passes and under the analysis tints
         const int frc = flood_pass(t, s, P, V, S.work_count + 3, raster);
         if (frc != VF_OK) return frc;
+    }
+    if (spill && ntiles) {                                 // the sink tint: directly behind the flood's water
+        const int src = spill_pass(t, s, P, V, S.work_count + 3, raster);
+        if (src != VF_OK) return src;
     }
     if (exposure && ntiles) {                              // the sun exposure's tint: behind both viewshed tints
         const int erc = exposure_pass(t, s, P, V, S.work_count + 3, raster);
@@ -2137,6 +2176,7 @@ int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, vo
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
     if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
     if (t->fd.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a flood enabled is not supported");
+    if (t->sp.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with the spill enabled is not supported");
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
@@ -2162,6 +2202,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
     if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
     if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
     if (t->fd.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a flood enabled is not supported");
+    if (t->sp.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with the spill enabled is not supported");
     if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
@@ -3255,9 +3296,10 @@ static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool for
 static int cumulative_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 static int exposure_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 static int flood_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
+static int spill_field(vf_terrain *t, const float *u, hipStream_t s, bool force = false);
 
 // The per-vertex fields a caller can have.  A new one is a feature struct that holds a VertexField, its *_field function and a row here.
-enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFieldExposure, kFieldFlood, kFields };
+enum Field { kFieldLit, kFieldSky, kFieldSeen, kFieldCount, kFieldExposure, kFieldFlood, kFieldSpill, kFields };
 struct FieldRow {
     int (*compute)(vf_terrain *, const float *, hipStream_t, bool);   // its *_field function
     VertexField &(*cache)(vf_terrain *);                               // its buffer, key and scan counter
@@ -3274,6 +3316,8 @@ static const FieldRow kFieldTable[kFields] = {
       [](const vf_terrain *t) -> const char * { return t->se.suns.empty() ? "no suns set (vf_terrain_set_sun_exposure)" : nullptr; } },
     { flood_field, [](vf_terrain *t) -> VertexField & { return t->fd.depth; },
       [](const vf_terrain *t) -> const char * { return t->fd.have ? nullptr : "no flood set (vf_terrain_set_flood)"; } },
+    { spill_field, [](vf_terrain *t) -> VertexField & { return t->sp.spill; },
+      [](const vf_terrain *t) -> const char * { return t->sp.have ? nullptr : "no spill set (vf_terrain_set_spill)"; } },
 };
 
 // Field f for the live uniforms, heights and parameters, complete in its buffer; then to `host`, or to `dev` behind the work on
@@ -4929,6 +4973,221 @@ int vf_terrain_debug_flood_group(vf_terrain *t, uint32_t group)
     if (group > kFloodMaxGroup) return fail(VF_ERR_INVALID, "a group holds at most 64 passes");
     if (t->fd.forced_group != group) t->fd.depth.valid = false;   // (the next call computes the field again, with this group size)
     t->fd.forced_group = group;
+    return VF_OK;
+}
+
+// ---- spill analysis (vf_spill.h) -------------------------------------------------------------
+
+// Passes of k_spill_pass queued per read-back of their `changed` words (DESIGN.md 4t has the measurement)
+constexpr uint32_t kSpillGroup = 16, kSpillMaxGroup = 64;
+
+static uint32_t spill_tiles(const vf_terrain *t) { return (t->n + kSpillTile - 1u) / kSpillTile; }
+
+// the seeds' vertices (i, j) for the spacing of the uniforms `u`, snapped as the flood's are
+static void spill_vertices(const vf_terrain *t, const float *u, std::vector<uint32_t> &ij)
+{
+    const vf_terrain::Spill &H = t->sp;
+    const float spacing = spacing_of(u);
+    ij.resize(H.xz.size());
+    for (size_t k = 0; k < H.xz.size(); ++k) ij[k] = viewshed_index(t, H.xz[k], spacing);
+}
+
+// `spill` holds the field of the handle's heights and sources once this returns (the height cache must be current and ordered before
+// `s`, as for shadow_field); d_sd holds what the tint reads.  The loop to the fixpoint is the flood's: groups of passes, each with its
+// own `changed` word, until the first pass that changed nothing.  force: compute it anyway.
+static int spill_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
+{
+    vf_terrain::Spill &H = t->sp;
+    if (!H.have) return fail(VF_ERR_INVALID, "no spill set (vf_terrain_set_spill)");
+    std::vector<uint32_t> ij;
+    if (H.mode == VF_SPILL_SEEDS) spill_vertices(t, u, ij);
+    std::vector<uint32_t> key;
+    key.push_back((uint32_t)H.mode); key.push_back((uint32_t)ij.size());
+    key.insert(key.end(), ij.begin(), ij.end());
+    bool current;
+    if (int rc = H.spill.prepare(t, key, force, "spill field allocation failed", &current)) return rc;
+    if (current) return VF_OK;
+    const uint32_t n = t->n, ftx = spill_tiles(t), tiles = ftx * ftx;
+    const size_t words = (size_t)tiles * kSpillTileWords, nv = (size_t)n * n, nctl = kSpillMaxGroup + 3u;
+    // (k_spill_out packs the two counts into the halves of one 64-bit word and vf_spill_info reports them as uint32: vf_terrain_create
+    //  holds the grid to 8192, n x n to 2^26)
+    if (nv >> 32) return fail(VF_ERR_INVALID, "the grid is too large for the spill's 32-bit vertex counts");
+    if (H.d_hk.reserve(words, words) != hipSuccess || H.d_w.reserve(words, words) != hipSuccess || H.d_sd.reserve(nv, nv) != hipSuccess
+        || H.d_act.reserve(2u * (size_t)tiles, 2u * (size_t)tiles) != hipSuccess || H.d_ctl.reserve(nctl, nctl) != hipSuccess
+        || H.d_seeds.reserve(ij.size(), ij.size()) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VF_ERR_NOMEM, "spill buffer allocation failed");
+    }
+    const dim3 cols(tiles, kSpillTile / 4u), threads(256);
+    const float *hblk = t->d_hblk;
+    uint32_t *const runs = H.d_ctl.p + kSpillMaxGroup + 2u;
+    VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p + kSpillMaxGroup, 0, 3u * sizeof(uint32_t), s));
+    if (H.mode == VF_SPILL_EDGES)
+        hipLaunchKernelGGL((k_spill_init<true>), cols, threads, 0, s, n, t->nb, ftx, tiles, hblk, H.d_hk.p, H.d_w.p, H.d_act.p);
+    else {
+        hipLaunchKernelGGL((k_spill_init<false>), cols, threads, 0, s, n, t->nb, ftx, tiles, hblk, H.d_hk.p, H.d_w.p, H.d_act.p);
+        const uint32_t count = (uint32_t)(ij.size() / 2u);
+        H.ij.swap(ij);
+        VF_HIP_TRY(hipMemcpyAsync(H.d_seeds.p, H.ij.data(), H.ij.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
+        hipLaunchKernelGGL((k_spill_seed<0>), dim3((count + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)H.d_seeds.p, count,
+                           (const uint32_t *)H.d_hk.p, H.d_w.p);
+    }
+    VF_HIP_TRY(hipGetLastError());
+    const uint32_t G = std::min(H.forced_group ? H.forced_group : kSpillGroup, kSpillMaxGroup);
+    uint32_t changed[kSpillMaxGroup];
+    uint32_t passes = 0;
+    // (every pass that changes something lowers at least one vertex to one of the at most n x n keys of h: the relaxation ends; the
+    //  bound is the issue's and guards the loop, it is not reached)
+    for (bool done = false; !done && passes <= nv;) {
+        VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p, 0, G * sizeof(uint32_t), s));
+        for (uint32_t g = 0; g < G; ++g) {
+            const uint32_t pass = passes + g + 1u;                 // (pass p reads array p & 1 and sets words of the other one)
+            hipLaunchKernelGGL((k_spill_pass<0>), dim3(tiles), dim3(64), 0, s, ftx, ftx, H.no_flags ? 1u : 0u, (const uint32_t *)H.d_hk.p, H.d_w.p,
+                               H.d_act.p + (size_t)(pass & 1u) * tiles, H.d_act.p + (size_t)((pass + 1u) & 1u) * tiles, H.d_ctl.p + g, runs);
+        }
+        VF_HIP_TRY(hipGetLastError());
+        VF_HIP_TRY(hipMemcpyAsync(changed, H.d_ctl.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        VF_HIP_TRY(hipStreamSynchronize(s));
+        uint32_t g = 0;
+        for (; g < G && !done; ++g) done = changed[g] == 0u;
+        passes += g;
+    }
+    if (passes > nv) return fail(VF_ERR_HIP, "spill relaxation did not reach a fixpoint within n x n + 1 passes");
+    uint32_t tail[3] = {};
+    hipLaunchKernelGGL((k_spill_out<0>), dim3(ftx, (n + 3u) / 4u), threads, 0, s, n, t->nb, ftx, hblk, (const uint32_t *)H.d_w.p, H.spill.d.p, H.d_sd.p,
+                       (unsigned long long *)(H.d_ctl.p + kSpillMaxGroup));
+    VF_HIP_TRY(hipGetLastError());
+    VF_HIP_TRY(hipMemcpyAsync(tail, H.d_ctl.p + kSpillMaxGroup, sizeof tail, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipStreamSynchronize(s));
+    H.passes = passes; H.reached = tail[0]; H.sinks = tail[1]; H.tile_runs = tail[2];
+    H.spill.computed(t, key);
+    return VF_OK;
+}
+
+// Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
+static void spill_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    const vf_terrain::Spill &H = t->sp;
+    SpillTint T = {};
+    T.sd = H.d_sd.p; T.decode = t->ctx->d_decode;
+    T.shallow_rgba = H.shallow_rgba; T.deep_rgba = H.deep_rgba; T.depth_full = H.depth_full;
+    const dim3 grid = gb_grid(t), threads(256);
+    hipLaunchKernelGGL((k_spill_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    hipLaunchKernelGGL((k_spill_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+}
+
+// The sinks of a frame, on the draw stream behind the flood's water: the field if it is stale, then the tint pass over the covered pixels
+static int spill_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    if (int rc = spill_field(t, t->inputs.u, s)) return rc;
+    spill_launch(t, s, P, V, redo, rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+int vf_terrain_set_spill(vf_terrain *t, int enable, int mode, const float *seeds_xz, uint32_t count, const uint8_t shallow_rgba[4],
+                         const uint8_t deep_rgba[4], float depth_full)
+{
+    if (!t || !shallow_rgba || !deep_rgba) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!(std::isfinite(depth_full) && depth_full > 0.0f)) return fail(VF_ERR_INVALID, "depth_full must be a finite number > 0");
+    if (mode != VF_SPILL_EDGES && mode != VF_SPILL_SEEDS) return fail(VF_ERR_INVALID, "unknown spill mode");
+    if (mode == VF_SPILL_SEEDS) {
+        if (!seeds_xz) return fail(VF_ERR_INVALID, "NULL argument: the seeds");
+        if (count < 1u || count > VF_SPILL_MAX_SEEDS) return fail(VF_ERR_INVALID, "the spill takes 1 to 65535 seeds");
+        for (size_t k = 0; k < (size_t)2u * count; ++k)
+            if (!std::isfinite(seeds_xz[k])) return fail(VF_ERR_INVALID, "the seeds must be finite");
+    } else count = 0u;
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "the spill needs a whole-frame handle: sharded handles are not supported");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    vf_terrain::Spill &H = t->sp;
+    const uint32_t sh = pack_rgba8(shallow_rgba), dp = pack_rgba8(deep_rgba);
+    std::vector<float> xz;
+    if (count) xz.assign(seeds_xz, seeds_xz + (size_t)2u * count);
+    if (H.enabled != (enable != 0) || !H.have || H.mode != mode || H.xz != xz || H.shallow_rgba != sh || H.deep_rgba != dp || H.depth_full != depth_full)
+        t->inputs_gen++;
+    H.enabled = enable != 0; H.have = true;
+    H.mode = mode;
+    H.xz.swap(xz);
+    H.shallow_rgba = sh; H.deep_rgba = dp; H.depth_full = depth_full;
+    return VF_OK;
+}
+
+int vf_terrain_clear_spill(vf_terrain *t)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (t->sp.enabled) t->inputs_gen++;
+    spill_release(t);
+    return VF_OK;
+}
+
+int vf_terrain_read_spill_field(vf_terrain *t, float *spill) { return field_out(t, kFieldSpill, spill, nullptr, nullptr); }
+int vf_terrain_spill_field_device(vf_terrain *t, float *dev_spill, void *stream) { return field_out(t, kFieldSpill, nullptr, dev_spill, stream); }
+
+// the public sink depth: sd where it is finite, 0 elsewhere (d_sd stands with the field that field_out has just made current)
+int vf_terrain_read_sink_depth(vf_terrain *t, float *depth)
+{
+    if (!t || !depth) return fail(VF_ERR_INVALID, "NULL argument");
+    const size_t nv = (size_t)t->n * t->n;
+    std::vector<float> spill(nv);
+    if (int rc = field_out(t, kFieldSpill, spill.data(), nullptr, nullptr)) return rc;
+    VF_HIP_TRY(hipMemcpy(depth, t->sp.d_sd.p, nv * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < nv; ++k)
+        if (!std::isfinite(depth[k])) depth[k] = 0.0f;
+    return VF_OK;
+}
+
+int vf_terrain_spill_info(vf_terrain *t, vf_spill_info *out)
+{
+    if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
+    const vf_terrain::Spill &H = t->sp;
+    *out = vf_spill_info();
+    out->enabled = H.enabled ? 1 : 0; out->has_spill = H.have ? 1 : 0;
+    out->mode = H.mode; out->count = (uint32_t)(H.xz.size() / 2u);
+    out->depth_full = H.depth_full;
+    for (int k = 0; k < 4; ++k) { out->shallow_rgba[k] = (uint8_t)(H.shallow_rgba >> (8 * k)); out->deep_rgba[k] = (uint8_t)(H.deep_rgba >> (8 * k)); }
+    out->reached_vertices = H.reached; out->sink_vertices = H.sinks; out->passes = H.passes; out->scans = H.spill.scans;
+    out->group = std::min(H.forced_group ? H.forced_group : kSpillGroup, kSpillMaxGroup);
+    out->tile_runs = H.tile_runs;
+    return VF_OK;
+}
+
+int vf_terrain_read_spill_seeds(vf_terrain *t, uint32_t *vertices)
+{
+    if (!t || !vertices) return fail(VF_ERR_INVALID, "NULL argument");
+    if (t->sp.xz.empty()) return fail(VF_ERR_INVALID, "no seeds set (vf_terrain_set_spill with VF_SPILL_SEEDS)");
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    std::vector<uint32_t> ij;
+    spill_vertices(t, t->inputs.u, ij);
+    std::memcpy(vertices, ij.data(), ij.size() * sizeof(uint32_t));
+    return VF_OK;
+}
+
+int vf_terrain_debug_spill_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldSpill, count); }
+
+int vf_terrain_debug_spill_stage(vf_terrain *t, uint32_t repeats, float ms[2])
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!t->sp.have || !t->sp.enabled) return fail(VF_ERR_INVALID, "no spill enabled (vf_terrain_set_spill)");
+    if (repeats == 0) repeats = 1;
+    RelightStage G;
+    if (int rc = G.open(t)) return rc;
+    if (int rc = spill_field(t, G.u, G.s)) return rc;          // (the tint's launches below read d_sd of the current field)
+    return G.time_pair(repeats, ms, "spill", [&] { return spill_field(t, G.u, G.s, true); },
+                       [&] { spill_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
+}
+
+int vf_terrain_debug_spill_group(vf_terrain *t, uint32_t group)
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    const bool no_flags = (group & VF_SPILL_GROUP_NO_FLAGS) != 0u;
+    group &= ~VF_SPILL_GROUP_NO_FLAGS;
+    if (group > kSpillMaxGroup) return fail(VF_ERR_INVALID, "a group holds at most 64 passes");
+    if (t->sp.forced_group != group || t->sp.no_flags != no_flags) t->sp.spill.valid = false;   // (the next call computes the field again)
+    t->sp.forced_group = group; t->sp.no_flags = no_flags;
     return VF_OK;
 }
 

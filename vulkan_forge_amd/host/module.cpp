@@ -1037,6 +1037,78 @@ public:
         check(vf_terrain_debug_flood_scans(t, &count));
         return count;
     }
+    // extension: spill analysis (argument rules: vulkan_forge_amd/_spill.py)
+    void set_spill(py::object seeds, py::object enabled, py::object shallow_rgba, py::object deep_rgba, py::object depth_full)
+    {
+        py::tuple a = py::module_::import("vulkan_forge_amd._spill").attr("spill_args")(seeds, enabled, shallow_rgba, deep_rgba, depth_full);
+        uint8_t sh[4], dp[4];
+        py::tuple ts = a[3].cast<py::tuple>(), td = a[4].cast<py::tuple>();
+        for (int k = 0; k < 4; ++k) { sh[k] = ts[k].cast<uint8_t>(); dp[k] = td[k].cast<uint8_t>(); }
+        const float *xz = nullptr;
+        uint32_t count = 0;
+        py::array_t<float, py::array::c_style | py::array::forcecast> arr;
+        if (!a[2].is_none()) {
+            arr = a[2].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+            xz = arr.data(); count = (uint32_t)arr.shape(0);
+        }
+        Borrow b(busy);
+        check(vf_terrain_set_spill(t, a[0].cast<int>(), a[1].cast<int>(), xz, count, sh, dp, a[5].cast<float>()));
+        frame_current = false;
+    }
+    void clear_spill()
+    {
+        Borrow b(busy);
+        check(vf_terrain_clear_spill(t));
+        frame_current = false;
+    }
+    py::array_t<float> spill_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_spill_field(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::array_t<float> sink_depth_field()
+    {
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = vf_terrain_read_sink_depth(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    py::object spill_info()
+    {
+        Borrow b(busy);
+        vf_spill_info v;
+        check(vf_terrain_spill_info(t, &v));
+        py::object vertices = py::none();
+        if (v.count) {
+            py::array_t<uint32_t> a({ (py::ssize_t)v.count, (py::ssize_t)2 });
+            if (vf_terrain_read_spill_seeds(t, a.mutable_data()) == VF_OK) vertices = a;   // (else: uniforms not set yet)
+        }
+        return py::module_::import("vulkan_forge_amd._spill").attr("spill_info")(
+            v.enabled, v.has_spill, v.mode, v.count, vertices, v.depth_full,
+            py::make_tuple(v.shallow_rgba[0], v.shallow_rgba[1], v.shallow_rgba[2], v.shallow_rgba[3]),
+            py::make_tuple(v.deep_rgba[0], v.deep_rgba[1], v.deep_rgba[2], v.deep_rgba[3]),
+            v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs);
+    }
+    void debug_spill_group(uint32_t group)
+    {
+        Borrow b(busy);
+        check(vf_terrain_debug_spill_group(t, group));
+    }
+    uint32_t debug_spill_scans()
+    {
+        Borrow b(busy);
+        uint32_t count = 0;
+        check(vf_terrain_debug_spill_scans(t, &count));
+        return count;
+    }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1505,6 +1577,24 @@ py::class_<T> bind_terrain(py::module_ &m, const char *name)
              "wettable_vertices, passes, scans, group); the counts and passes are those of the last computation of the field.")
         .def("debug_flood_group", &T::debug_flood_group, py::arg("group") = 0)
         .def("debug_flood_scans", &T::debug_flood_scans)
+        .def("set_spill", &T::set_spill, py::arg("seeds") = "edges", py::kw_only(), py::arg("enabled") = true,
+             py::arg("shallow_rgba") = py::make_tuple(96, 176, 224, 128), py::arg("deep_rgba") = py::make_tuple(16, 64, 160, 224),
+             py::arg("depth_full") = VF_SPILL_DEPTH_FULL,
+             "Spill analysis (DESIGN.md 4t): the lowest level the water must reach at the sources before a vertex gets wet (the minimax\n"
+             "path height over 4-connected paths of finite vertices), and a tint of the closed basins by their depth spill - h.\n"
+             "seeds=\"edges\": the border of the grid is the source, the field is the depression-filled surface; seeds=(N, 2) points (x, z)\n"
+             "in the overlays' world frame, 1 <= N <= 65535, each snapped to the nearest grid vertex: spill_field() < L is what\n"
+             "set_flood(L, seeds) floods.  The tint is flat: shallow_rgba at the rim, deep_rgba where the basin is depth_full deep or more,\n"
+             "blended in between.  Every parameter is stored by every call, also one that disables, and steers the field calls too.")
+        .def("clear_spill", &T::clear_spill, "The spill is off, its parameters are the defaults again, its buffers are freed.")
+        .def("spill_field", &T::spill_field,
+             "(grid, grid) float32, row j = z index, column i = x index: the spill level of the vertex, +inf where no path arrives.")
+        .def("sink_depth_field", &T::sink_depth_field, "(grid, grid) float32: spill - h where that is finite, 0 elsewhere.")
+        .def("spill_info", &T::spill_info,
+             "dict(enabled, mode, seeds (N), vertices ((N, 2) uint32 (i, j)), shallow_rgba, deep_rgba, depth_full, reached_vertices,\n"
+             "sink_vertices, passes, scans, group, tile_runs); the counts, passes and tile_runs are those of the last computation.")
+        .def("debug_spill_group", &T::debug_spill_group, py::arg("group") = 0)
+        .def("debug_spill_scans", &T::debug_spill_scans)
         .def("set_sun", &T::set_sun, py::arg("elevation_deg"), py::arg("azimuth_deg"))
         .def("set_exposure", &T::set_exposure, py::arg("exposure"));
 }
