@@ -13,8 +13,12 @@ tests/test_gpu_feature_soak.py (the GPU slice) and tests/test_feature_soak_cases
 
 The late passes ride on the same handle, between the overlays and the mutation: the drape's mip pyramid and
 anisotropic taps, the viewshed, cumulative-viewshed and sun-exposure fields and tints, the haze; then a second mutation of their own,
-and for a case with a factor above 1 a supersampled second handle.  Steps A - E of run_case:
-    A  the three vertex fields, bit for bit, their passes off; the cumulative and exposure fields again at another batch size
+and for a case with a factor above 1 a supersampled second handle.  The flood and the spill (the two passes between
+the drape and the exposure tint, whose fields iterate to a fixpoint across launches) ride with them, and get a third mutation of
+their own.  Steps A - E and W of run_case:
+    A  the three vertex fields, bit for bit, their passes off; the cumulative and exposure fields again at another batch size; the
+       flood, spill and sink-depth fields with flood_info() and spill_info() (counts, mode, seeds' vertices, passes and tile runs
+       inside the bounds of the models' tile_passes), and again at another group size, the spill's with or without its activity flags
     B  the passes on in exact precision: the frame (twice), the haze opacity plane, drape_mip_info() and one pyramid level
     C  fast precision.  The handle exposes no frame from between its passes, and needs none: the relight and drape passes write the
        same bytes in either precision (step 3 found that without mips; with the mips and the anisotropic taps on it is asserted here,
@@ -23,17 +27,19 @@ and for a case with a factor above 1 a supersampled second handle.  Steps A - E 
        others alike.  The pixels an overlay touches are left out of the colour comparison altogether, the 1 LSB bound included (the
        overlays blend over bytes that may be 1 LSB off, and where a layer is opaque nothing of the frame beneath is left to compare);
        the alpha channel is compared everywhere
-    D  the mutation (step 5) and the late mutation: the frame, and the rise of the three scan counters and of the pyramid's builds
-       against STALE_VIEWSHED, STALE_CUMULATIVE, STALE_EXPOSURE and MIP_BUILDS
+    D  the mutation (step 5) and the late mutation: the frame, and the rise of the five scan counters and of the pyramid's builds
+       against STALE_VIEWSHED, STALE_CUMULATIVE, STALE_EXPOSURE, STALE_FLOOD, STALE_SPILL and MIP_BUILDS
+    W  the water mutation: the frame (for spill_cleared: the frame without the spill, then with it set again) and the same counters
     E  supersample=f: the samples, the resolved frame under the overlays (none occluding) and the samples' visibility, again after the
-       late mutation
+       late mutation and after the water mutation
 
 usage: soak_features.py [first_seed] [cases] [time_budget_s]"""
 import hashlib, math, os, sys, time, zlib
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model", "shadow_model", "ambient_model", "drape_model",
-           "drape_mip_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "supersample_model", "haze_model"):
+           "drape_mip_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "supersample_model", "haze_model", "flood_model",
+           "spill_model"):
     sys.path.insert(0, os.path.join(HERE, _m))
 import numpy as np
 import ambient_model as abm  # noqa: E402
@@ -41,9 +47,11 @@ import contour_model as cm  # noqa: E402
 import cumulative_viewshed_model as cvm  # noqa: E402
 import drape_mip_model as dmm  # noqa: E402
 import drape_model as drm  # noqa: E402
+import flood_model as fdm  # noqa: E402
 import gbuffer_model as gbm  # noqa: E402
 import haze_model as hzm  # noqa: E402
 import shadow_model as shm  # noqa: E402
+import spill_model as spm  # noqa: E402
 import sun_exposure_model as sem  # noqa: E402
 import supersample_model as ssm  # noqa: E402
 import viewshed_model as vsm  # noqa: E402
@@ -90,10 +98,31 @@ SAMPLE_CAP = 1 << 20                                          # f f W H above th
 # again unless the list of their vertices reads the same (run_case asks the model); the exposure's after the heights, the spacing, the
 # exaggeration, a sun, a weight, incidence, softness or bias, not the handle's own sun.  The pyramid is built by the first frame after
 # a new image (every set_drape call hands one over) or after enabling, if it has a level above 0, and by nothing else.
-STALE_VIEWSHED = ("heights", "exaggeration", "observer_moves", "heights_again")
-STALE_CUMULATIVE = ("heights", "exaggeration", "radius", "cumulative_reorder", "heights_again")
-STALE_EXPOSURE = ("heights", "exaggeration", "suns_reweight", "incidence_flip", "heights_again")
+STALE_VIEWSHED = ("heights", "exaggeration", "observer_moves", "heights_again", "heights_water")
+STALE_CUMULATIVE = ("heights", "exaggeration", "radius", "cumulative_reorder", "heights_again", "heights_water")
+STALE_EXPOSURE = ("heights", "exaggeration", "suns_reweight", "incidence_flip", "heights_again", "heights_water")
 MIP_BUILDS = ("drape_replace", "drape_opacity_zero")
+# the flood and the spill: the two passes between the drape and the exposure tint, flood first.  Their generator is
+# default_rng([seed, WATER_STREAM]): no key a case had before them depends on it (digest; tests/test_feature_soak_cases.py pins it)
+WATER_STREAM = 0x3A7E2
+WATER_PASSES = ("flood", "spill")
+WATER_MUTATIONS = ("level", "flood_mode", "spill_mode", "seeds_move", "seeds_nudged", "water_colours_only", "flood_off", "spill_cleared", "heights_water")
+FLOOD_MODES = ("everywhere", "edges", "seeds")
+SPILL_MODES = ("edges", "seeds")
+SEED_COUNTS = (1, 3, 255, 256, 257)                           # k_flood_seed and k_spill_seed run 256 threads a block
+LEVEL_QUANTILES = (0.5, 0.3, 0.7, 0.1, 0.9)                   # (in the order of preference among equal shares)
+LEVEL_KINDS = ("quantile", "vertex", "below", "above")
+DEPTH_FULLS = (0.05, 1.0, 20.0)                               # depth_full over the range of the surface: small, about one, large
+WATER_GROUPS = (1, 7, 0)                                      # the group size of the second read of each field; 0: the default, no new scan
+# which of the two fields vf_hip.h says a mutation (of any of the three kinds) makes stale, when the field's pass is on.  The flood's
+# key is the level's bits, the mode and the list of the seeds' vertices, over the heights; the spill's the mode and the list of its
+# seeds' vertices, over the heights.  Neither depends on the colours, depth_full, the camera, the sun or the EXAGGERATION (both fields
+# are in units of h before it), nor on a seed that moves inside its vertex's cell; seeds_move makes a field stale where the pass
+# takes a seed list and the list of vertices reads differently (run_case asks the model, as for cumulative_reorder).
+# vf_terrain_clear_spill frees the field with its buffers (the counter stays), so the next frame after set_spill computes it again
+STALE_FLOOD = ("heights", "heights_again", "level", "flood_mode", "seeds_move", "heights_water")
+STALE_SPILL = ("heights", "heights_again", "spill_mode", "seeds_move", "spill_cleared", "heights_water")
+WATER_KEYS = ("water", "water_mutation", "water_mutation_args")
 OLD_KEYS = ("name", "W", "H", "grid", "tex", "amp", "smooth", "nan_texel", "heights", "eye", "target", "fovy", "znear", "zfar", "exaggeration", "spacing", "sun",
             "cmap", "mode", "mutation", "features", "shadows", "ambient", "overlays", "mutation_args", "drape")
 
@@ -466,10 +495,329 @@ def _late(rng, c, surf, fix, all_on=False):
     return L, kind, args
 
 
-def _make(rng, name, fix, drape_rng, draped=False, late_rng=None):
+def seed_vertices(c, seeds):
+    """the vertices (N, 2) uint32 the library snaps a seed list of the case to"""
+    return fdm.seed_vertices(seeds, max(f32(c["spacing"]), f32(1e-8)), max(c["grid"], 2))
+
+
+def _sources(c, seeds):
+    """a seeds entry (None, "edges" or world (x, z) pairs) as the models' field_heights take it: the list as vertices"""
+    return seeds if seeds is None or isinstance(seeds, str) else seed_vertices(c, seeds)
+
+
+def flood_of(c, surface, F):
+    """the flood model's Field of a flood entry on a surface (n, n) of the case's grid"""
+    return fdm.field_heights(surface, F["level"], _sources(c, F["seeds"]))
+
+
+def spill_of(c, surface, S):
+    return spm.field_heights(surface, _sources(c, S["seeds"]))
+
+
+def flood_mode(F):
+    return FLOOD_MODES[fdm.mode_of(F["seeds"])]
+
+
+def spill_mode(S):
+    return SPILL_MODES[spm.mode_of(S["seeds"]) - 1]
+
+
+def surface_at_the_water_mutation(c):
+    """the heights the handle holds when run_case applies the water mutation (after the first and the late one), and their surface"""
+    h = c["late_mutation_args"]["heights"] if c["late_mutation"] == "heights_again" else c["mutation_args"]["heights"] if c["mutation"] == "heights" else c["heights"]
+    return h, cm.surface(h, c["grid"])
+
+
+def projection(c):
+    """(sx, sy, A, B, C, D): the projection of the case's uniform block (u[16:32], column-major) -- clip x = sx x, y = sy y,
+    z = A z + B, w = C z + D of a view-space point -- restated from the camera's numbers so that the generator needs no oracle;
+    tests/test_feature_soak_cases.py holds it to oracle.look_at_uniforms"""
+    sy = 1.0 / math.tan(0.5 * math.radians(c["fovy"]))
+    n, f = c["znear"], c["zfar"]
+    A = f / (n - f) + 0.5
+    return sy * c["H"] / c["W"], sy, A, n * f / (n - f), A - 1.0, n * f / (n - f)
+
+
+def cut_by_a_clip_plane(c, surface, exaggeration):
+    """whether a vertex with a height lies outside 0 <= clip z <= clip w of the case's camera"""
+    n = surface.shape[0]
+    g = (-1.5 + np.arange(n) * (3.0 / (n - 1))) * c["spacing"]
+    X, Z = np.meshgrid(g, g)
+    P = np.stack([X, np.nan_to_num(surface.astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0) * exaggeration, Z], axis=-1)
+    f = np.asarray(c["target"], np.float64) - np.asarray(c["eye"], np.float64)
+    if not np.linalg.norm(f) > 1e-9:
+        return True
+    zc = (P - np.asarray(c["eye"], np.float64)) @ (f / np.linalg.norm(f))
+    _, _, A, B, C, D = projection(c)
+    zcl, wcl = B - A * zc, D - C * zc
+    return bool((((wcl <= 0) | (zcl < 0) | (zcl > wcl)) & np.isfinite(surface)).any())
+
+
+def in_view(c, surface, exaggeration):
+    """-> ((n, n) bool, (n, n) int64): the vertices of `surface` that lie in the case's view volume, between the pixel centres of the
+    outer columns and rows and half a cell beyond, and the pixel each falls in (row-major; the orientation of the axes does not
+    matter to a caller that only asks which vertices share a pixel) -- the camera of oracle.look_at_uniforms (up = +y) in plain
+    arithmetic, so that the generator needs no oracle.  A degenerate camera sees nothing."""
+    n = surface.shape[0]
+    g = (-1.5 + np.arange(n) * (3.0 / (n - 1))) * c["spacing"]
+    X, Z = np.meshgrid(g, g)
+    P = np.stack([X, np.nan_to_num(surface.astype(np.float64), nan=0.0, posinf=0.0, neginf=0.0) * exaggeration, Z], axis=-1)
+    eye = np.asarray(c["eye"], np.float64)
+    f = np.asarray(c["target"], np.float64) - eye
+    r = np.cross(f, (0.0, 1.0, 0.0))
+    if not (np.linalg.norm(f) > 1e-9 and np.linalg.norm(r) > 1e-9 * np.linalg.norm(f)):
+        return np.zeros((n, n), bool), np.zeros((n, n), np.int64)
+    f, r = f / np.linalg.norm(f), r / np.linalg.norm(r)
+    u = np.cross(r, f)
+    d = P - eye
+    zc, xc, yc = d @ f, d @ r, d @ u
+    sx, sy, A, B, C, D = projection(c)
+    half = 0.5 * 3.0 * c["spacing"] / (n - 1)
+    xcl, ycl, zcl, wcl = sx * xc, sy * yc, B - A * zc, D - C * zc       # (view z = -zc: the camera looks down -z)
+    inside = ((wcl > 0) & (zcl >= 0) & (zcl <= wcl) & (np.abs(xcl) <= wcl * (1.0 - 1.0 / c["W"]) + half * sx)
+              & (np.abs(ycl) <= wcl * (1.0 - 1.0 / c["H"]) + half * sy) & np.isfinite(surface))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        px = np.clip(np.floor((np.where(inside, xcl / wcl, 0.0) * 0.5 + 0.5) * c["W"]), 0, c["W"] - 1).astype(np.int64)
+        py = np.clip(np.floor((np.where(inside, ycl / wcl, 0.0) * 0.5 + 0.5) * c["H"]), 0, c["H"] - 1).astype(np.int64)
+    return inside, py * c["W"] + px
+
+
+_WATER_NEEDS = {"level": "flood", "flood_mode": "flood", "flood_off": "flood", "spill_mode": "spill", "spill_cleared": "spill"}
+
+
+def _water(rng, c, surf, fix, wish, all_on=False):
+    """The flood and the spill of a case, from their own generator -> (water, water_mutation, water_mutation_args).  `water`: `flood`
+    (level, seeds, shallow_rgba, deep_rgba, depth_full) and `spill` (the same without the level) as supersample_model.chain takes
+    them, `on` (a non-empty subset of WATER_PASSES; every corner has both: `all_on`), level_kind, and for the second read of each
+    field flood_group, spill_group and spill_flags.  fix["water"] is laid over the draw (a dict over a dict key by key); there a
+    level may be ("vertex", i, j) or ("unique", k) -- that vertex's height, the k-th of the surface's distinct finite heights -- and a
+    seeds entry "lowest_corner", "highest" or "on_nan": one seed on that vertex.  The mutation is `wish` (seed % len(WATER_MUTATIONS)
+    for a seed) if it can do what it must by what the two models say of the surface the handle holds then and by what the case's
+    camera has in view (can_show), else the next of a drawn order that can; fix["water_mutation"] is written down and stays.  The
+    pass a mutation needs is switched on for the mutation that is taken, not for the wish."""
+    G, sp = c["grid"], c["spacing"]
+    n = max(G, 2)
+    fin = surf[np.isfinite(surf)]
+    lo, hi = (float(fin.min()), float(fin.max())) if fin.size else (0.0, 0.0)
+    span = (hi - lo) if hi > lo else 1.0
+    nanv = np.argwhere(~np.isfinite(surf))                    # (j, i) of the vertices without a height
+    fixed = fix.get("water", {})
+    kind = fix.get("water_mutation", wish)
+
+    def at(ji):
+        j, i = ji[int(rng.integers(0, len(ji)))]
+        return vertex_xz(int(i), int(j), n, sp)
+
+    def seeds():
+        """(a seed list, the slots for a seed on a dry vertex): a count from SEED_COUNTS, positions within +-1.9 spacing (beyond +-1.5
+        they clamp to the border), one duplicate and one seed on a vertex without a height, if there is one"""
+        k = int(rng.choice(SEED_COUNTS))
+        s = rng.uniform(-1.9 * sp, 1.9 * sp, (k, 2)).astype(f32)
+        order = rng.permutation(k)
+        coin = bool(rng.random() < 0.5)
+        if k < 3:
+            return s, []
+        s[order[0]] = s[order[1]]
+        if len(nanv) and (k > 3 or coin):
+            s[order[-1]] = at(nanv)
+        return s, [order[-2]] if k > 3 else [order[-1]] if not (len(nanv) and coin) else []
+
+    def colours():
+        """(shallow, deep), as _late's colours(): one of the two sometimes with alpha 0, never both"""
+        a, b = _rgba(rng, int(rng.choice([255, 160, 96, 0], p=[0.3, 0.3, 0.3, 0.1]))), _rgba(rng, int(rng.choice([255, 224, 96, 0], p=[0.3, 0.3, 0.3, 0.1])))
+        return (a, b) if a[3] or b[3] else (a, b[:3] + (224,))
+
+    def depth_full():
+        return max(float(f32(float(rng.choice(DEPTH_FULLS)) * span)), 1e-6)
+
+    def quantiles(surface):
+        f = surface[np.isfinite(surface)]
+        return [float(f32(np.quantile(f.astype(np.float64), q))) for q in LEVEL_QUANTILES] if f.size else [0.0]
+
+    def named_seed(v):
+        if not isinstance(v, str) or v == "edges":
+            return v
+        if v == "lowest_corner":
+            corners = [(0, 0), (n - 1, 0), (0, n - 1), (n - 1, n - 1)]
+            i, j = min(corners, key=lambda ij: float(np.nan_to_num(surf[ij[1], ij[0]], nan=np.inf)))
+        elif v == "highest":
+            j, i = np.argwhere(surf == f32(hi))[0]
+        else:
+            assert v == "on_nan", v
+            j, i = nanv[0]
+        return np.array([vertex_xz(int(i), int(j), n, sp)], f32)
+
+    # the draw, all of it for every case (what a later key gets does not depend on which branch an earlier one took)
+    fmode, smode = str(rng.choice(FLOOD_MODES)), str(rng.choice(SPILL_MODES, p=[0.6, 0.4]))
+    fmode, smode = fixed.get("flood_mode", fmode), fixed.get("spill_mode", smode)
+    (fseeds, fdry), (sseeds, _) = seeds(), seeds()
+    level_kind = str(rng.choice(LEVEL_KINDS, p=[0.76, 0.08, 0.08, 0.08]))
+    pick = int(rng.integers(0, max(fin.size, 1)))
+    on = [p for p in WATER_PASSES if rng.random() < 0.7] or [WATER_PASSES[int(rng.integers(0, 2))]]
+    (fa, fb), (sa, sb) = colours(), colours()
+    over = [float(v) for v in rng.choice(DEPTH_FULLS, 2)]     # depth_full over the surface's range
+    W = dict(flood=dict(shallow_rgba=fa, deep_rgba=fb, depth_full=max(float(f32(over[0] * span)), 1e-6)),
+             spill=dict(shallow_rgba=sa, deep_rgba=sb, depth_full=max(float(f32(over[1] * span)), 1e-6)), depth_full_over_range=tuple(over),
+             flood_group=int(rng.choice(WATER_GROUPS)), spill_group=int(rng.choice(WATER_GROUPS)), spill_flags=bool(rng.random() < 0.6))
+    if all_on:
+        on = list(WATER_PASSES)
+
+    def on_for(k):
+        """the passes that are on if the mutation is k: the drawn ones and the one k needs"""
+        return on + [_WATER_NEEDS[k]] if k in _WATER_NEEDS and _WATER_NEEDS[k] not in on else on
+
+    # the two seed mutations need a pass that is on and takes a seed list: where a seed WISHES for one of them and the draw gave none,
+    # a mode becomes "seeds", before the level is chosen, and stays so if the mutation then gives way to another
+    if kind in ("seeds_move", "seeds_nudged") and "water_mutation" not in fix and not (("flood" in on and fmode == "seeds") or ("spill" in on and smode == "seeds")):
+        if "flood" in on:
+            fmode = "seeds"
+        else:
+            smode = "seeds"
+    W["flood"]["seeds"] = named_seed(fixed.get("flood", {}).get("seeds", {"everywhere": None, "edges": "edges", "seeds": fseeds}[fmode]))
+    W["spill"]["seeds"] = named_seed(fixed.get("spill", {}).get("seeds", {"edges": "edges", "seeds": sseeds}[smode]))
+    # the level: usually the quantile of the finite surface under which the flooded share of the wet-able vertices, from the case's own
+    # sources, is nearest 0.4 (the flood model's field; no GPU) -- the trick _make uses for the sun's elevation
+    level = fixed.get("flood", {}).get("level")
+    if isinstance(level, tuple):
+        level_kind = "vertex"
+        level = float(surf[level[2], level[1]]) if level[0] == "vertex" else float(np.unique(fin)[level[1]])
+    elif level is not None:
+        level_kind = "fixed"
+    elif level_kind == "vertex" and fin.size:
+        level = float(fin[pick])
+    elif level_kind == "below" and fin.size:
+        level = float(f32(lo - max(1.0, 0.01 * abs(lo))))
+    elif level_kind == "above" and fin.size:
+        level = float(f32(hi + max(1.0, 0.01 * abs(hi))))
+    else:
+        level_kind = "quantile"
+        share = []
+        for q in quantiles(surf):
+            F = flood_of(c, surf, dict(level=q, seeds=W["flood"]["seeds"]))
+            share.append(int(F.flooded.sum()) / max(int(F.wet.sum()), 1))
+        # (a level under which the sources flood nothing only where every level is one)
+        level = quantiles(surf)[int(np.argmin([abs(v - 0.4) if v > 0 else 1.0 for v in share]))]
+    W["flood"]["level"] = level
+    dry = np.argwhere(~(surf < f32(level)))
+    if fmode == "seeds" and "seeds" not in fixed.get("flood", {}) and len(dry):
+        for slot in fdry:                                     # one seed on a dry vertex
+            W["flood"]["seeds"][slot] = at(dry)
+    for p in WATER_PASSES:
+        W[p].update({k: v for k, v in fixed.get(p, {}).items() if k not in ("seeds", "level")})
+    for k, v in fixed.items():
+        if k not in WATER_PASSES + ("flood_mode", "spill_mode"):
+            W[k] = v
+    W["level_kind"] = level_kind
+    # the mutation's payload, for the surface the handle holds when it comes
+    h1, s1 = surface_at_the_water_mutation(c)
+    F0, S0 = flood_of(c, s1, W["flood"]), spill_of(c, s1, W["spill"])
+    t2 = (int(rng.integers(1, 80)), int(rng.integers(1, 80)))
+    (fs2, _), (ss2, _) = seeds(), seeds()                     # the seed lists of a changed mode, and of seeds_move
+    (fs3, _), (ss3, _) = seeds(), seeds()
+
+    def nudged(s):
+        out = np.array(s, f32)
+        for k, v in enumerate(seed_vertices(c, s).tolist()):
+            for off in ((0.2, 0.2), (-0.2, -0.2), (0.2, -0.2), (-0.2, 0.2)):
+                p = vertex_xz(v[0], v[1], n, sp, off)
+                if seed_vertices(c, [p]).tolist() == [v] and p != (float(out[k, 0]), float(out[k, 1])):
+                    out[k] = p
+                    break
+        return out
+
+    seen, pixel = in_view(c, s1, c["mutation_args"]["exaggeration"] if c["mutation"] == "exaggeration" else c["exaggeration"])
+    _, held = np.unique(pixel[seen], return_inverse=True)     # per vertex in view: the number of its pixel among those that hold one
+    # (where a clip plane cuts the terrain -- a vertex in front of the near or beyond the far plane -- triangles are cut too, and what
+    #  the vertices say of the pixels is no guide to which pixels are covered (seed 7011: 174 vertices in view over 66 pixels, 7 pixels covered): every pixel must change there, a fifth elsewhere)
+    share = 1 if cut_by_a_clip_plane(c, s1, c["mutation_args"]["exaggeration"] if c["mutation"] == "exaggeration" else c["exaggeration"]) else 5
+
+    def picture(Wt, passes, surface=s1):
+        """A coarse picture of what `passes` tint, per vertex: the colour between shallow and deep by depth over depth_full,
+        quantised, nothing where the alpha is next to 0.  A mutation that should show has another picture on EVERY vertex of two
+        of the pixels that hold a vertex in the camera's view when it comes (in_view: plain arithmetic on the case's camera, no
+        frame; of the one such pixel, if there is only one), and of one in five of them (of all of them under a camera whose near or far
+        plane cuts the terrain): whatever those pixels show of the surface
+        has changed, and the terrain would have to hide four fifths of what the view volume holds to hide them all."""
+        out = []
+        for p in WATER_PASSES:
+            if p in passes and Wt.get(p) is not None:
+                M = flood_of(c, surface, Wt[p]) if p == "flood" else spill_of(c, surface, Wt[p])
+                depth = M.depth if p == "flood" else M.sink
+                t = np.clip(depth / f32(Wt[p]["depth_full"]), 0.0, 1.0)[..., None]
+                rgba = np.array(Wt[p]["shallow_rgba"], np.float64) * (1.0 - t) + np.array(Wt[p]["deep_rgba"], np.float64) * t
+                rgba[~(depth > 0) | (rgba[..., 3] < 16.0)] = 0.0
+                out.append(np.round(rgba / 8.0))
+            else:
+                out.append(np.zeros((n, n, 4)))
+        return np.stack(out)
+
+    def shows(Wt, k):
+        passes = on_for(k)
+        return score(Wt, passes) >= max(min(2, int(held.max()) + 1), (int(held.max()) + 1 + share - 1) // share) if held.size else False
+
+    def score(Wt, passes):
+        """the number of pixels all of whose vertices in view get another picture"""
+        if not held.size:
+            return 0
+        changed = (picture(Wt, passes) != picture(W, passes)).any(axis=(0, 3))[seen]
+        return int((np.bincount(held, weights=changed) == np.bincount(held)).sum())
+
+    q1 = quantiles(s1)
+    levels = [q for q in (q1[int(i)] for i in rng.permutation(len(q1))) if q != level and shows(dict(W, flood=dict(W["flood"], level=q)), "level")]
+    fmodes = [m for name, m in (("everywhere", None), ("edges", "edges"), ("seeds", fs2))
+              if name != flood_mode(W["flood"]) and shows(dict(W, flood=dict(W["flood"], seeds=m)), "flood_mode")]
+    other = ss2 if spill_mode(W["spill"]) == "edges" else "edges"
+    transparent, lot = bool(rng.random() < 0.3), float(rng.random())
+    cols = {p: tuple(col[:3] + (0,) for col in colours()) if transparent else colours() for p in WATER_PASSES}
+    best = max(q1, key=lambda q: score(dict(W, flood=dict(W["flood"], level=q)), on_for("level")) if q != level else -1)     # (for a corner that names `level`)
+    args = dict({
+        "level": levels[0] if levels else best if best != level else float(f32(level + 0.25 * span)),
+        "flood_seeds": fmodes[int(lot * len(fmodes))] if fmodes else fs2,
+        "spill_seeds": other,
+        "moved": dict(flood=fs3, spill=ss3),
+        "nudged": {p: nudged(W[p]["seeds"]) if isinstance(W[p]["seeds"], np.ndarray) else None for p in WATER_PASSES},
+        "colours": cols, "transparent": transparent, "depth_full": dict(flood=depth_full(), spill=depth_full()),
+        "heights": _heights(rng, t2, float(rng.choice([0.2, 1.0, 3.0])), bool(rng.random() < 0.5)),
+    }, **fix.get("water_mutation_args", {}))
+
+    def listed(p):
+        return p in on and isinstance(W[p]["seeds"], np.ndarray)
+
+    def can_show(k):
+        if k == "level":
+            return bool(levels)
+        if k == "flood_mode":
+            return bool(fmodes)
+        if k == "spill_mode":
+            return shows(dict(W, spill=dict(W["spill"], seeds=other)), k)
+        if k == "seeds_move":                                 # a new list of vertices, and another picture, for the passes that take a list
+            lists = [p for p in WATER_PASSES if listed(p)]
+            return (any(seed_vertices(c, args["moved"][p]).tolist() != seed_vertices(c, W[p]["seeds"]).tolist() for p in lists)
+                    and shows(dict(W, **{p: dict(W[p], seeds=args["moved"][p]) for p in lists}), k))
+        if k == "seeds_nudged":                               # other numbers, the same vertices
+            return any(listed(p) and args["nudged"][p].tobytes() != W[p]["seeds"].tobytes()
+                       and seed_vertices(c, args["nudged"][p]).tolist() == seed_vertices(c, W[p]["seeds"]).tolist() for p in WATER_PASSES)
+        if k == "flood_off":
+            return shows(dict(W, flood=None), k)
+        if k == "spill_cleared":
+            return shows(dict(W, spill=None), k)
+        if k == "heights_water":                              # (other ground under the same settings)
+            s2 = cm.surface(args["heights"], G)
+            return bool((flood_of(c, s2, W["flood"]).flooded != F0.flooded).any() or (_bits(spill_of(c, s2, W["spill"]).sink) != _bits(S0.sink)).any())
+        new = {p: dict(W[p], shallow_rgba=cols[p][0], deep_rgba=cols[p][1], depth_full=args["depth_full"][p]) for p in WATER_PASSES}
+        return shows(dict(W, **new), k)                       # (the colours: of water that is there)
+
+    if "water_mutation" not in fix:
+        order = [WATER_MUTATIONS[i] for i in rng.permutation(len(WATER_MUTATIONS))]
+        kind = next((k for k in [kind] + order if can_show(k)), "heights_water")
+    W["on"] = tuple(p for p in WATER_PASSES if p in on_for(kind))
+    return W, kind, args
+
+
+def _make(rng, name, fix, drape_rng, draped=False, late_rng=None, water_rng=None, water_wish=None):
     """A case description; `fix` overrides what the draw would choose (CORNERS).  The drape comes from `drape_rng`, a generator of
     its own: what `rng` gives a seed or a corner does not depend on it; `draped`: never without one (every corner).  The late
-    passes come from `late_rng` in the same way."""
+    passes come from `late_rng` in the same way, the flood and the spill from `water_rng`."""
     c = {"name": name}
 
     def put(key, draw):
@@ -537,15 +885,17 @@ def _make(rng, name, fix, drape_rng, draped=False, late_rng=None):
     d = _drape(drape_rng, draped or mutation in DRAPE_MUTATIONS)
     c["drape"] = None if d is None else dict(d, **fix.get("drape", {}))
     c["late"], c["late_mutation"], c["late_mutation_args"] = _late(late_rng, c, surf, fix, all_on=draped)
+    c["water"], c["water_mutation"], c["water_mutation_args"] = _water(water_rng, c, surf, fix, water_wish, all_on=draped)
     return c
 
 
 def case(seed):
     """The case of a seed: frame, grid, texture, camera and uniforms drawn as test_random_scenes_fuzz draws them, a sun, colormap,
     shade mode, shadow and ambient parameters, which of them are on, the overlay calls, one mutation and (from a generator of its
-    own) a draped image or none."""
+    own each) a draped image or none, the late passes with their mutation, the flood and the spill with theirs."""
     return _make(np.random.default_rng(seed), f"seed{seed}", {"mutation": MUTATIONS[seed % len(MUTATIONS)]}, np.random.default_rng([seed, DRAPE_STREAM]),
-                 late_rng=np.random.default_rng([seed, LATE_STREAM]))
+                 late_rng=np.random.default_rng([seed, LATE_STREAM]), water_rng=np.random.default_rng([seed, WATER_STREAM]),
+                 water_wish=WATER_MUTATIONS[seed % len(WATER_MUTATIONS)])
 
 
 _CAMERA = dict(eye=(3.0, 2.0, 3.0), target=(0.0, 0.0, 0.0), fovy=45.0, znear=0.1, zfar=100.0)
@@ -576,7 +926,8 @@ def _build(k, name, fix):
         late[key] = dict(late.get(key, {}), **v) if isinstance(v, dict) else v
     base["late"] = late
     return _make(np.random.default_rng(90000 + k), name, base, np.random.default_rng([90000 + k, DRAPE_STREAM]), draped=True,
-                 late_rng=np.random.default_rng([90000 + k, LATE_STREAM]))
+                 late_rng=np.random.default_rng([90000 + k, LATE_STREAM]), water_rng=np.random.default_rng([90000 + k, WATER_STREAM]),
+                 water_wish=WATER_MUTATIONS[k % len(WATER_MUTATIONS)])
 
 
 def _amb(reach, dirs, strength=0.6):
@@ -589,6 +940,9 @@ _LONG_FOVY = 2.0 * math.degrees(math.atan(0.5 * 1.5 / 6.0))   # from 6 units abo
 # frame -- beyond the frame and inside its last 16-pixel bin column.  k_pg_setup clipped an edge's bins to the frame, the backdrop mask
 # gives a bin only the crossings beyond its right edge, so pixel column 16 lost that crossing and the fill
 # (tests/test_feature_soak_cases.py asserts where the edge lies).
+_BRIDGE = np.full((9, 9), 2.0, f32)                           # (the texture of water_bridge_vertex_at_the_level, below)
+_BRIDGE[4, 1:8] = -2.0
+_BRIDGE[4, 4] = 0.0
 GAP_RING = np.array([[-0.778, 0.0, -0.354], [0.99, 0.0, -2.121], [2.121, 0.0, -0.99], [0.354, 0.0, 0.778]], f32)
 _SPECS = [
     _corner(0, "grid2_frame1x1_sun_up", grid=2, W=1, H=1, sun=(0.0, 1.0, 0.0), tex=(2, 2), ambient=_amb(1.0, _round(4))),
@@ -696,8 +1050,69 @@ _SPECS = [
     _corner(47, "late_supersample3_frame15x17", W=15, H=17, ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="mips_off",
             late=dict(supersample=3, max_anisotropy=8, mip_bias=0.0),
             drape=dict(image=dmm.case_image(43, (300, 300)), extent=None, extent_kind="whole", opacity=1.0, filter="linear")),
+    # the flood's and the spill's own edges (tests/test_feature_soak_cases.py asserts what each is named for): both
+    # passes on, small frames.  Below grid 64 most lanes and registers of the one 64 x 64 tile lie beyond the grid
+    _corner(50, "water_grid2_all_border", grid=2, W=33, H=31, tex=(2, 2), ambient=_amb(1.0, _round(4)), water_mutation="level",
+            water=dict(flood=dict(seeds="edges", level=("unique", -1)), spill=dict(seeds="edges"))),
+    # (from the lowest corner vertex; the centre's height is the level, and `h < level` is strict: it stays dry)
+    _corner(51, "water_grid3_centre_at_the_level", grid=3, W=33, H=31, ambient=_amb(16.0, _FAN), water_mutation="level",
+            water=dict(flood=dict(seeds="lowest_corner", level=("vertex", 1, 1)), spill=dict(seeds="lowest_corner"))),
+    # white noise of amplitude 3, a texel a vertex and more: sinks by the thousand; a tile short by one row and column, and a whole one
+    _corner(52, "water_grid63_white_noise", grid=63, tex=(79, 79), smooth=False, amp=3.0, ambient=_amb(16.0, _FAN), water_mutation="spill_mode",
+            water=dict(flood=dict(seeds="edges"), spill=dict(seeds="edges"))),
+    _corner(53, "water_grid64_white_noise", grid=64, tex=(79, 79), smooth=False, amp=3.0, ambient=_amb(16.0, _FAN), water_mutation="spill_cleared",
+            water=dict(flood=dict(seeds="edges"), spill=dict(seeds="edges"))),
+    # 3 x 3 tiles, the outer ones two vertices wide, one seed in the middle of the first: the water crosses tile borders pass by pass
+    # while the tiles it has left rest
+    _corner(54, "water_grid130_white_noise_from_one_seed", grid=130, tex=(130, 130), smooth=False, amp=3.0, ambient=_amb(16.0, _FAN), water_mutation="seeds_move",
+            # (the level well above the site-percolation threshold of the noise: the water from the seed crosses the grid)
+            water=dict(flood=dict(seeds=np.array([vertex_xz(20, 20, 130, 1.0)], f32), level=0.6), spill=dict(seeds=np.array([vertex_xz(20, 20, 130, 1.0)], f32)),
+                       flood_group=1, spill_group=7, spill_flags=False),
+            water_mutation_args={"moved": dict(flood=np.array([vertex_xz(120, 70, 130, 1.0)], f32), spill=np.array([vertex_xz(120, 70, 130, 1.0)], f32))}),
+    # nothing is wet-able or passable: counts of 0, a spill of +inf, a sink depth of 0, the frame as it was; the heights mutation brings
+    # ground, and both fields are computed again
+    _corner(55, "water_all_nan_texture", W=33, H=31, heights=np.full((5, 6), np.nan, f32), ambient=_amb(16.0, _round(8)), mutation="heights",
+            late_mutation="tint_colours_only", water_mutation="flood_off", water=dict(flood=dict(seeds="edges", level=0.0), spill=dict(seeds="edges"))),
+    # the only seed of either pass on the one vertex without a height: no source, nothing flooded or reached; heights_water brings one
+    _corner(57, "water_only_seed_on_the_nan_vertex", W=48, H=40, tex=(9, 7), nan_texel=True, ambient=_amb(16.0, _FAN), late_mutation="tint_colours_only",
+            water_mutation="heights_water", water=dict(flood=dict(seeds="on_nan", level=5.0), spill=dict(seeds="on_nan"))),   # (the level above the new heights too: the seed's vertex is wet then)
+    # the staircase of constant_texture_level_on_the_plateau: nine distinct heights, consecutive binary32 numbers.  The level is the
+    # middle one (a tie with every vertex of that plateau, all dry); the spill comes from a seed on the highest plateau, so the ties
+    # below it hold sinks -- from the border there are none
+    _corner(58, "water_plateau_of_ties", heights=np.full((4, 4), 2.0 ** 20, f32), exaggeration=2.0 ** -20, ambient=_amb(16.0, _round(8)), mutation="sun",
+            late_mutation="tint_colours_only", water_mutation="spill_mode",
+            water=dict(flood=dict(seeds="edges", level=("unique", 4), depth_full=0.25), spill=dict(seeds="highest", depth_full=0.25))),
+] + [
+    # the level above everything (all the finite ground is wet-able) and below everything (none is), in each of the three modes
+    _corner(60 + 3 * a + m, f"water_level_{where}_everything_{FLOOD_MODES[m]}", W=48, H=40, ambient=_amb(16.0, _FAN), water_mutation="level",
+            water=dict(flood_mode=FLOOD_MODES[m], flood=dict(level=lv)))
+    for a, (where, lv) in enumerate((("above", 1e6), ("below", -1e6))) for m in range(3)
+] + [
+    # neither field depends on the exaggeration: none is computed again, and the tints follow the surface the frame draws
+    _corner(70, "water_exaggeration0_then_minus2", W=48, H=40, exaggeration=0.0, ambient=_amb(16.0, _round(8)), mutation="exaggeration",
+            mutation_args={"exaggeration": -2.0}, late_mutation="tint_colours_only", water_mutation="water_colours_only"),
+    # the camera of late_near_plane_through_the_terrain: the CLIPPED instantiation of both tint kernels
+    _corner(71, "water_near_plane_through_the_terrain", grid=9, eye=(0.9, 0.7, 0.8), target=(-0.4, -0.2, -0.3), znear=0.4, fovy=60.0,
+            ambient=_amb(16.0, _FAN, strength=0.6), late_mutation="tint_colours_only", water_mutation="flood_off",
+            water=dict(flood=dict(seeds=None, level=0.4, shallow_rgba=(96, 176, 224, 160), deep_rgba=(16, 64, 160, 224)),
+                       spill=dict(seeds=np.array([(1.4, 1.4)], f32), shallow_rgba=(255, 224, 64, 160), deep_rgba=(160, 32, 16, 240)))),
+    # (the level above everything: the one pixel is under water, whichever vertex it shows)
+    _corner(72, "water_frame1x1", W=1, H=1, ambient=_amb(16.0, _FAN), water_mutation="flood_off", water=dict(flood=dict(seeds=None, level=1e6, deep_rgba=(16, 64, 160, 224)))),
+    _corner(73, "water_frame_of_one_column", W=1, H=70, grid=17, ambient=_amb(16.0, _FAN), water_mutation="spill_cleared", water=dict(flood=dict(seeds=None))),
+    _corner(74, "water_frame_of_one_row", W=130, H=1, grid=16, fovy=0.3, ambient=_amb(1.5, _round(3)), water_mutation="flood_off", water=dict(flood=dict(seeds=None))),
+    _corner(75, "water_supersample3_frame15x17", W=15, H=17, ambient=_amb(16.0, _FAN), mutation="sun", late_mutation="tint_colours_only",
+            water_mutation="level", late=dict(supersample=3), water=dict(flood=dict(seeds="edges"))),
+    # a texel a vertex: walls, and a channel along row 4 whose middle vertex lies exactly at the level.  `h < level` is strict, so the
+    # water from the seed at the channel's one end stops in front of it and the other half stays dry: a kernel that takes `<=` floods
+    # the whole channel, and the field and the frame show it, not the counts alone
+    # (corner 87: its drawn overlays leave the channel in sight; tests/test_feature_soak_cases.py asserts that the whole frame shows it)
+    _corner(87, "water_bridge_vertex_at_the_level", grid=9, heights=_BRIDGE, exaggeration=0.05, ambient=_amb(16.0, _FAN), mutation="sun",
+            late_mutation="tint_colours_only", water_mutation="flood_mode", water_mutation_args={"flood_seeds": None},
+            water=dict(flood=dict(seeds=np.array([vertex_xz(1, 4, 9, 1.0)], f32), level=("vertex", 4, 4), shallow_rgba=(96, 176, 224, 200), deep_rgba=(16, 64, 160, 240)),
+                       spill=dict(seeds=np.array([vertex_xz(1, 4, 9, 1.0)], f32)))),
 ]
-OLD_CORNERS = 29                                              # the corners older than the late passes: their old keys are pinned (digest)
+OLD_CORNERS = 29                                             # the corners older than the late passes: their old keys are pinned (digest)
+LATE_CORNERS = 47                                             # ... and those older than the flood and the spill: theirs and their late keys
 
 
 class _Corners:
@@ -751,7 +1166,53 @@ def uniforms(c, sun=None, exaggeration=None):
 def initial_state(c):
     """the handle's state before any feature is on: what `expected` and `run` step through"""
     return dict(heights=c["heights"], u=uniforms(c), shadows=False, ambient=False, shadow_params=dict(c["shadows"]), ambient_params=dict(c["ambient"]),
-                overlays=False, occlusion={}, drape=None, late=None)
+                overlays=False, occlusion={}, drape=None, late=None, water=None)
+
+
+def watered(c, state):
+    """the state with the case's flood and spill on (those of `on`): for each its parameters, or None while it is off; `cleared`:
+    clear_spill was the last call for the spill"""
+    P = c["water"]
+    return dict(state, water=dict(cleared=False, **{p: {k: v for k, v in P[p].items()} if p in P["on"] else None for p in WATER_PASSES}))
+
+
+def water_steps(c, state):
+    """The states (with the water on) the case's water mutation leads through, in order: [(what, state)].  One for every mutation
+    but spill_cleared: the spill cleared, then set again as it was.  A mutation of a pass that is off changes nothing of it."""
+    kind, a = c["water_mutation"], c["water_mutation_args"]
+    Wt = dict(state["water"])
+    s = dict(state, water=Wt)
+    F, S = Wt["flood"], Wt["spill"]
+
+    def listed(P):
+        return P is not None and isinstance(P["seeds"], np.ndarray)
+
+    if kind == "level":
+        Wt["flood"] = dict(F, level=a["level"])
+    elif kind == "flood_mode":
+        Wt["flood"] = dict(F, seeds=a["flood_seeds"])
+    elif kind == "spill_mode":
+        Wt["spill"] = dict(S, seeds=a["spill_seeds"])
+    elif kind in ("seeds_move", "seeds_nudged"):
+        for p in WATER_PASSES:
+            if listed(Wt[p]):
+                Wt[p] = dict(Wt[p], seeds=a["moved" if kind == "seeds_move" else "nudged"][p])
+    elif kind == "water_colours_only":
+        for p in WATER_PASSES:
+            if Wt[p] is not None:
+                Wt[p] = dict(Wt[p], shallow_rgba=a["colours"][p][0], deep_rgba=a["colours"][p][1], depth_full=a["depth_full"][p])
+    elif kind == "flood_off":
+        Wt["flood"] = None
+    elif kind == "spill_cleared":
+        return [("spill cleared", dict(state, water=dict(Wt, spill=None, cleared=True))), ("spill set again", s)]
+    elif kind == "heights_water":
+        s["heights"] = a["heights"]
+    return [(kind, s)]
+
+
+def water_mutated(c, state):
+    """the state after the case's water mutation"""
+    return water_steps(c, state)[-1][1]
 
 
 def lated(c, state):
@@ -798,11 +1259,11 @@ def late_mutated(c, state):
 
 def chain_features(c, state):
     """the state as the features of supersample_model.chain"""
-    A, D, L = state["ambient_params"], state["drape"], state["late"] or {}
+    A, D, L, Wt = state["ambient_params"], state["drape"], state["late"] or {}, state.get("water") or {}
     drape = None if D is None else dict(D, mips=bool(L.get("mips")), bias=L.get("mip_bias", 0.0), max_anisotropy=L.get("max_anisotropy", 1))
     return dict(shade_mode=c["mode"], shadows=dict(state["shadow_params"]) if state["shadows"] else None, ambient=dict(A) if state["ambient"] else None,
-                drape=drape, exposure=L.get("exposure"), cumulative=L.get("cumulative"), viewshed=L.get("viewshed"),
-                haze=L.get("haze"))
+                drape=drape, flood=Wt.get("flood"), spill=Wt.get("spill"), exposure=L.get("exposure"), cumulative=L.get("cumulative"),
+                viewshed=L.get("viewshed"), haze=L.get("haze"))
 
 
 def unoccluded(c):
@@ -882,8 +1343,8 @@ def layers(c, state):
 
 def expected(c, state, cache=None):
     """The reference of a handle state: the oracle's frame and visibility, then the passes in the library's order, which is written
-    down once, in supersample_model.chain (the relight pass, the draped image through its mips and anisotropic taps, the exposure,
-    cumulative and viewshed tints, the haze), then the overlays (occlusion_model.composite of the contour model's layers).  `cache` (a
+    down once, in supersample_model.chain (the relight pass, the draped image through its mips and anisotropic taps, the flood's water,
+    the spill's sink tint, the exposure, cumulative and viewshed tints, the haze), then the overlays (occlusion_model.composite of the contour model's layers).  `cache` (a
     dict of one case) keeps the oracle's frames, the vertex fields and the results, for a caller that asks for a state twice.
     -> dict rgba (the oracle's frame), vis, shaded, mask (the pixels the shade pass writes again), draped (the frame behind the drape
     pass: `shaded` without a drape), drape_mask (the pixels the drape writes again), late (the frame behind the last late pass:
@@ -894,7 +1355,8 @@ def expected(c, state, cache=None):
     A, D = state["ambient_params"], state["drape"]
     whole = (key, state["shadows"], state["ambient"], state["overlays"], tuple(sorted(state["shadow_params"].items())),
              A["strength"], A["reach"], A["directions"].tobytes(), tuple(sorted(state["occlusion"].items())),
-             None if D is None else (D["image"].tobytes(), D["image"].shape, D["extent"], D["opacity"], D["filter"]), ssm._key(state["late"]))
+             None if D is None else (D["image"].tobytes(), D["image"].shape, D["extent"], D["opacity"], D["filter"]), ssm._key(state["late"]),
+             ssm._key(state.get("water")))
     if cache is not None and whole in cache:
         return cache[whole]
     if cache is not None and key in cache:
@@ -988,6 +1450,61 @@ def describe_late(stat):
         ch = [s["changed"][p] for s in stat if s["changed"].get(p) is not None]
         out.append(f"{p} on in {sum(p in s['on'] for s in stat)} of {len(stat)}, changes a pixel in {sum(v > 0 for v in ch)} and 10-90 % in "
                    f"{sum(0.1 < v < 0.9 for v in ch)} of {len(ch)} covered")
+    return "; ".join(out)
+
+
+def behind_the_water(e):
+    """the frame behind the spill's tint of a result of expected(): what the exposure tint, or whatever comes next, is laid over"""
+    st = e["stages"]
+    return st.get("spill_frame", st.get("flood_frame", e["draped"]))
+
+
+def water_shares(c, cache=None):
+    """what the reference alone says about a case's flood and spill: on; flood_mode; proper: the flooded set is a non-empty proper
+    subset of the wet-able vertices; sinks: a vertex has a sink depth above 0; identity: flooded == reached & (spill < level) for the
+    flood's own sources; covered (pixels); changed: per pass that is on, the share of the covered pixels it changes
+    (None without a covered pixel); partial: a blended pixel's depth lies strictly between 0 and depth_full; covered_before_the
+    mutation (pixels, in the state run_case applies it to); mutation_shows: a state the mutation leads through has another frame
+    behind the water (behind_the_water) than the one before it; mutation_shows_behind_the_late_passes: the same of the frame behind
+    the haze, under tints that may be opaque; without_water: the frame after it is that of the state without either pass"""
+    P = c["water"]
+    s2 = watered(c, lated(c, featured(c, initial_state(c), overlays=True)))
+    e2 = expected(c, s2, cache)
+    st, cov = e2["stages"], e2["vis"] != 0
+    covered = int(cov.sum())
+    surf = cm.surface(c["heights"], c["grid"])
+    F = flood_of(c, surf, P["flood"])
+    S = spill_of(c, surf, P["spill"])
+    own = spm.field_heights(surf, _sources(c, P["flood"]["seeds"])) if P["flood"]["seeds"] is not None else None
+    changed, partial, before = {}, {}, e2["draped"]
+    for p, model, field in (("flood", fdm, F), ("spill", spm, S)):
+        if p in P["on"]:
+            changed[p] = int(((st[p + "_frame"] != before).any(axis=2) & cov).sum()) / covered if covered else None
+            d = model.frame(before, e2["vis"], s2["u"], s2["heights"], c["grid"], st[p + "_field"], **{k: P[p][k] for k in ("shallow_rgba", "deep_rgba", "depth_full")})[1]
+            partial[p] = bool(((d > 0) & (d < f32(P[p]["depth_full"]))).any())
+            before = st[p + "_frame"]
+    s3 = late_mutated(c, mutated(c, s2))
+    e3 = expected(c, s3, cache)
+    steps = [expected(c, s, cache) for _, s in water_steps(c, s3)]
+    return dict(on=P["on"], flood_mode=flood_mode(P["flood"]), proper=bool(F.flooded.any() and (F.wet & ~F.flooded).any()), sinks=bool((S.sink > 0).any()),
+                identity=None if own is None else bool(np.array_equal(F.flooded, own.reached & (own.spill < f32(P["flood"]["level"])))),
+                covered=covered, changed=changed, partial=partial, covered_before_the_mutation=int((e3["vis"] != 0).sum()),
+                mutation_shows=any(bool((behind_the_water(e) != behind_the_water(e3)).any()) for e in steps),
+                mutation_shows_behind_the_late_passes=any(bool((e["late"] != e3["late"]).any()) for e in steps),
+                without_water=bool(np.array_equal(steps[-1]["late"], expected(c, dict(water_steps(c, s3)[-1][1], water=None), cache)["late"])))
+
+
+def describe_water(stat):
+    """the flood's and the spill's shares over a list of water_shares() results, as text"""
+    out = []
+    for p in WATER_PASSES:
+        ch = [s["changed"][p] for s in stat if s["changed"].get(p) is not None]
+        out.append(f"{p} on in {sum(p in s['on'] for s in stat)} of {len(stat)}, changes a pixel in {sum(v > 0 for v in ch)} and 10-90 % in "
+                   f"{sum(0.1 < v < 0.9 for v in ch)} of {len(ch)} covered")
+    listed = [s for s in stat if "flood" in s["on"] and s["flood_mode"] != "everywhere"]
+    spilt = [s for s in stat if "spill" in s["on"]]
+    out.append(f"the flooded set is a proper non-empty subset of the wet-able vertices in {sum(s['proper'] for s in listed)} of {len(listed)} floods from edges or seeds, "
+               f"sinks in {sum(s['sinks'] for s in spilt)} of {len(spilt)} spills")
     return "; ".join(out)
 
 
@@ -1150,9 +1667,11 @@ def run_case(c, seed=None, cache=None):
         differ("A", "sun exposure field", _bits(t.sun_exposure_field()) != _bits(expo))
         t.sun_exposure_batch(X["batch"])
         differ("A", f"sun exposure field at batch size {X['batch']}", _bits(t.sun_exposure_field()) != _bits(expo))
-        # B. the late passes on, exact precision, the overlays still on; the second frame is the one planned ahead
-        state = lated(c, state)
+        _water_fields(t, c, state, differ, lambda what: bad.append((seed, "A", what, 1, [])))
+        # B. the late passes and the water on, exact precision, the overlays still on; the second frame is the one planned ahead
+        state = watered(c, lated(c, state))
         _set_late(t, c, state)
+        _set_water(t, c, state)
         e = expected(c, state, cache)
         for again in ("", " drawn again"):
             differ("B", "frame" + again, (frame(t) != e["frame"]).any(axis=2))
@@ -1213,7 +1732,14 @@ def run_case(c, seed=None, cache=None):
         state = late_mutated(c, state)
         _apply_late_mutation(t, c, state)
         differ("D", f"frame after {kind}", (frame(t) != expected(c, state, cache)["frame"]).any(axis=2))
-        _late_stale(bad, seed, "D", kind, t, state, late_scans, _reordered(c, before, state))
+        late_scans = _late_stale(bad, seed, "D", kind, t, state, late_scans, _reordered(c, before, state))
+        # W. the water mutation
+        kind = c["water_mutation"]
+        for what, after in water_steps(c, state):
+            before, state = state, after
+            _apply_water_mutation(t, c, state)
+            differ("W", f"frame after {kind}: {what}", (frame(t) != expected(c, state, cache)["frame"]).any(axis=2))
+        _late_stale(bad, seed, "W", kind, t, state, late_scans, moved=_seeds_moved(c, before, state))
         # 6. the drape cleared: the frame of the same state without one
         if state["drape"] is not None:
             state = dict(state, drape=None)
@@ -1226,18 +1752,22 @@ def run_case(c, seed=None, cache=None):
     # E. a supersampled second handle: the same heights, uniforms, features, drape and late passes, no layer occluding; then the late mutation
     f = c["late"]["supersample"]
     if f > 1:
-        state = lated(c, featured(c, initial_state(c), overlays=True))
+        state = watered(c, lated(c, featured(c, initial_state(c), overlays=True)))
         t = cabi.Terrain(W, H, G, lut(c["cmap"]), supersample=f)
         try:
             t.set_uniforms(state["u"]); t.set_shade_mode(c["mode"]); t.set_height(state["heights"]); t.set_shade_precision(0)
             _set_features(t, state)
             _set_drape(t, state["drape"])
             _set_late(t, c, state)
+            _set_water(t, c, state)
             _add_overlays(t, unoccluded(c))
-            for step in ("E", "E after " + c["late_mutation"]):
-                if step != "E":
+            for step in ("E", "E after " + c["late_mutation"], "E after " + c["water_mutation"]):
+                if step == "E after " + c["late_mutation"]:
                     state = late_mutated(c, state)
                     _apply_late_mutation(t, c, state)
+                elif step != "E":
+                    for _, state in water_steps(c, state):
+                        _apply_water_mutation(t, c, state)
                 e = expected_supersampled(c, state, f, cache)
                 t.render()
                 differ(step, "samples", (t.read_samples() != e["samples"]).any(axis=2))
@@ -1275,9 +1805,88 @@ def _apply_late_mutation(t, c, state):
         _set_late(t, c, state)
 
 
+def _set_water(t, c, state):
+    """The flood's and the spill's settings on the handle, all of them by every call: a pass is on where the state has it, with the
+    state's parameters; an off pass keeps the case's; a cleared spill is cleared"""
+    P, Wt = c["water"], state.get("water") or {}
+    F, S = Wt.get("flood") or P["flood"], Wt.get("spill") or P["spill"]
+    t.set_flood(F["level"], F["seeds"], enabled=Wt.get("flood") is not None, shallow_rgba=F["shallow_rgba"], deep_rgba=F["deep_rgba"], depth_full=F["depth_full"])
+    if Wt.get("cleared"):
+        t.clear_spill()
+    else:
+        t.set_spill(S["seeds"], enabled=Wt.get("spill") is not None, shallow_rgba=S["shallow_rgba"], deep_rgba=S["deep_rgba"], depth_full=S["depth_full"])
+
+
+def _apply_water_mutation(t, c, state):
+    """the water mutation's state on the handle"""
+    if c["water_mutation"] == "heights_water":
+        t.set_height(state["heights"])
+    else:
+        _set_water(t, c, state)
+
+
+def _seeds_moved(c, before, after):
+    """per pass: whether the list of its seeds' vertices reads differently (what the field's key holds of them)"""
+    def vertices(P):
+        return None if P is None or not isinstance(P["seeds"], np.ndarray) else seed_vertices(c, P["seeds"]).tolist()
+    return {p: vertices(before["water"][p]) != vertices(after["water"][p]) for p in WATER_PASSES}
+
+
+def _water_fields(t, c, state, differ, wrong):
+    """Step A of the water: both passes set and off; the three fields against the models bit for bit, flood_info() and spill_info()
+    against the models' counts, modes and vertices, the passes and tile runs inside the bounds of tests/test_gpu_flood.py and
+    tests/test_gpu_spill.py against the models' tile_passes (the kernels may see a neighbour's stores of the same launch, so they never
+    need more passes than the emulation with halos from before the pass; a pass that changes something is followed by another);
+    then each field read again at the case's other group size: the same bits, one more scan for a new group size"""
+    P, u, h, G = c["water"], state["u"], state["heights"], c["grid"]
+    _set_water(t, c, state)
+    tiles = spm.n_tiles(max(G, 2))
+    surf = cm.surface(h, G)
+    F = fdm.field(u, h, G, P["flood"]["level"], P["flood"]["seeds"])
+    S = spm.field(u, h, G, P["spill"]["seeds"])
+    flooded, emulated = fdm.tile_passes(F.wet, fdm.sources(F.wet, "edges" if isinstance(P["flood"]["seeds"], str) else F.vertices)) if P["flood"]["seeds"] is not None else (F.flooded, 0)
+    if not np.array_equal(flooded, F.flooded):
+        wrong("the flood model's tile passes against its search")
+    S2, spill_emulated, _ = spm.tile_passes(surf, "edges" if isinstance(P["spill"]["seeds"], str) else S.vertices)
+    if (_bits(S2.spill) != _bits(S.spill)).any():
+        wrong("the spill model's tile passes against its search")
+
+    def vertices_differ(info, M):
+        return (info["vertices"] is not None or info["seeds"] != 0) if M.vertices is None else not (info["vertices"] is not None and np.array_equal(info["vertices"], M.vertices))
+
+    def flood(what):
+        differ("A", "flood field" + what, _bits(t.flood_field()) != _bits(F.depth))
+        info = t.flood_info()
+        if (info["flooded_vertices"], info["wettable_vertices"], info["mode"]) != (int(F.flooded.sum()), int(F.wet.sum()), flood_mode(P["flood"])) or vertices_differ(info, F):
+            wrong(f"flood_info(){what} {info} against {int(F.flooded.sum())} flooded of {int(F.wet.sum())} wet-able, {flood_mode(P['flood'])}, the model's vertices")
+        if not (min(emulated, 2) <= info["passes"] <= emulated) or info["level"] != float(f32(P["flood"]["level"])):
+            wrong(f"flood_info(){what}: {info['passes']} passes against the emulation's {emulated}, level {info['level']}")
+        return info
+
+    def spill(what, flags=True):
+        differ("A", "spill field" + what, _bits(t.spill_field()) != _bits(S.spill))
+        differ("A", "sink depth field" + what, _bits(t.sink_depth_field()) != _bits(S.sink))
+        info = t.spill_info()
+        if (info["reached_vertices"], info["sink_vertices"], info["mode"]) != (int(S.reached.sum()), int((S.sink > 0).sum()), spill_mode(P["spill"])) or vertices_differ(info, S):
+            wrong(f"spill_info(){what} {info} against {int(S.reached.sum())} reached, {int((S.sink > 0).sum())} sinks, {spill_mode(P['spill'])}, the model's vertices")
+        queued = -(-info["passes"] // max(info["group"], 1)) * info["group"]      # (the passes of the last group behind the fixpoint run too)
+        runs_ok = info["tile_runs"] <= info["passes"] * tiles and (info["tile_runs"] >= 1 or not S.reached.any()) if flags else info["tile_runs"] == queued * tiles
+        if not (min(spill_emulated, 2) <= info["passes"] <= spill_emulated) or not runs_ok:
+            wrong(f"spill_info(){what}: {info['passes']} passes against the emulation's {spill_emulated}, {info['tile_runs']} tile runs of {tiles} tiles, group {info['group']}")
+        return info
+
+    a, b = flood(""), spill("")
+    t.flood_group(P["flood_group"])
+    t.spill_group(P["spill_group"], flags=P["spill_flags"])
+    a2, b2 = flood(f" at group size {P['flood_group']}"), spill(f" at group size {P['spill_group']}, flags {P['spill_flags']}", P["spill_flags"])
+    rose, must = (a2["scans"] - a["scans"], b2["scans"] - b["scans"]), (int(P["flood_group"] != 0), int(P["spill_group"] != 0 or not P["spill_flags"]))
+    if rose != must or (P["flood_group"] and a2["group"] != P["flood_group"]) or (P["spill_group"] and b2["group"] != P["spill_group"]):
+        wrong(f"the flood / spill field was computed {rose} times for the group sizes {P['flood_group']} / {P['spill_group']}, flags {P['spill_flags']}: {must} expected")
+
+
 def _late_counters(t):
-    """(viewshed, cumulative, exposure scans, pyramid builds) over the handle's life; the builds also while mipmaps are off"""
-    return (t.viewshed_scans(), t.cumulative_viewshed_scans(), t.sun_exposure_scans(), t.drape_mip_builds())
+    """(viewshed, cumulative, exposure, flood, spill scans, pyramid builds) over the handle's life; the builds also while mipmaps are off"""
+    return (t.viewshed_scans(), t.cumulative_viewshed_scans(), t.sun_exposure_scans(), t.flood_scans(), t.spill_scans(), t.drape_mip_builds())
 
 
 def _reordered(c, before, after):
@@ -1286,19 +1895,21 @@ def _reordered(c, before, after):
     return a is not None and [snap(c, o) for o in a["observers"]] != [snap(c, o) for o in b["observers"]]
 
 
-def _late_stale(bad, seed, step, kind, t, state, counters, reordered=True):
-    """after mutation `kind` and a frame: the three late vertex fields and the pyramid were computed as often as the contract says
-    (STALE_VIEWSHED, ...: of a pass that is on) -> the counters now"""
-    L, D = state["late"], state["drape"]
+def _late_stale(bad, seed, step, kind, t, state, counters, reordered=True, moved=None):
+    """after mutation `kind` and a frame: the three late vertex fields, the flood and spill fields and the pyramid were computed as
+    often as the contract says (STALE_VIEWSHED, ...: of a pass that is on) -> the counters now"""
+    L, D, Wt = state["late"], state["drape"], state["water"]
     now = _late_counters(t)
     rose = tuple(int(a - b) for a, b in zip(now, counters))
     levels = 0 if D is None else len(dmm.sizes(D["image"].shape[1], D["image"].shape[0]))
     must = (int(L["viewshed"] is not None and kind in STALE_VIEWSHED),
             int(L["cumulative"] is not None and kind in STALE_CUMULATIVE and (kind != "cumulative_reorder" or reordered)),
             int(L["exposure"] is not None and kind in STALE_EXPOSURE),
+            int(Wt["flood"] is not None and kind in STALE_FLOOD and (kind != "seeds_move" or moved["flood"])),
+            int(Wt["spill"] is not None and kind in STALE_SPILL and (kind != "seeds_move" or moved["spill"])),
             int(L["mips"] and kind in MIP_BUILDS and levels >= 2))
     if rose != must:
-        bad.append((seed, step, f"after {kind} the viewshed / cumulative / exposure field and the pyramid were computed {rose} times, the contract says {must}", 1, []))
+        bad.append((seed, step, f"after {kind} the viewshed / cumulative / exposure / flood / spill field and the pyramid were computed {rose} times, the contract says {must}", 1, []))
     return now
 
 
@@ -1312,12 +1923,13 @@ def run(first=FRESH_SEED, cases=200, budget=400.0, verbose=True, corners=True):
     (the tuples of run_case), summary."""
     t0 = time.time()
     say = (lambda *a: print(*a, flush=True)) if verbose else (lambda *a: None)
-    bad, done, skipped, stat, late = [], 0, 0, [], []
+    bad, done, skipped, stat, late, water = [], 0, 0, [], [], []
 
     def one(c, seed):
         cache = {}
         stat.append(shares(c, cache))
         late.append(late_shares(c, cache))
+        water.append(water_shares(c, cache))
         b = run_case(c, seed, cache)
         for m in b:
             say(f"MISMATCH {m[0]} step {m[1]}: {m[2]}: {m[3]} differ, first at {m[4]}  ({c['W']}x{c['H']} grid={c['grid']} {c['features']} mutation={c['mutation']})")
@@ -1344,7 +1956,7 @@ def run(first=FRESH_SEED, cases=200, budget=400.0, verbose=True, corners=True):
             say(f"{done} cases, {len(bad)} mismatches, {time.time() - t0:.0f} s")
     share = skipped / max(done + skipped, 1)
     summary = (f"feature soak: {ncorners} corners and {done} cases from seed {first}, {skipped} skipped for a degenerate camera ({100.0 * share:.0f} %, "
-               f"bound {100.0 * MAX_SKIPPED:.0f} %): {len(bad)} mismatches; {describe(stat)}; the late passes: {describe_late(late)}, supersampled {sum(c['supersample'] > 1 for c in late)}; {time.time() - t0:.0f} s")
+               f"bound {100.0 * MAX_SKIPPED:.0f} %): {len(bad)} mismatches; {describe(stat)}; the late passes: {describe_late(late)}, supersampled {sum(c['supersample'] > 1 for c in late)}; the water: {describe_water(water)}; {time.time() - t0:.0f} s")
     say(summary)
     return {"cases": done, "corners": ncorners, "skipped": skipped, "too_many_skipped": share > MAX_SKIPPED, "bad": bad, "summary": summary}
 

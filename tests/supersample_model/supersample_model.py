@@ -17,6 +17,8 @@ features (all optional, each as the public setters take them):
     shadows      dict(strength, softness, bias)
     ambient      dict(directions (D, 2), reach, strength)
     drape        dict(image, extent, opacity, filter, mips=False, bias=0.0, max_anisotropy=1)
+    flood        dict(level, seeds (None, "edges" or world (x, z) pairs), shallow_rgba, deep_rgba, depth_full)
+    spill        dict(seeds ("edges" or world (x, z) pairs), shallow_rgba, deep_rgba, depth_full)
     exposure     dict(suns, weights, incidence, softness, bias, high_rgba, low_rgba)
     cumulative   dict(observers, radius, eye_height, target_height, softness, bias, high_rgba, low_rgba)
     viewshed     dict(observer, radius, eye_height, target_height, softness, bias, visible_rgba, hidden_rgba)
@@ -34,7 +36,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 TESTS = os.path.dirname(HERE)
 sys.path.insert(0, os.path.dirname(TESTS))
 for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "shadow_model", "ambient_model", "drape_model", "drape_mip_model",
-           "drape_aniso_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "gbuffer_model", "haze_model"):
+           "drape_aniso_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "gbuffer_model", "haze_model", "flood_model",
+           "spill_model"):
     sys.path.insert(0, os.path.join(TESTS, _m))
 
 F32 = np.float32
@@ -107,21 +110,34 @@ def _key(v):
     return v
 
 
-def chain(rgba, vis, uniforms, height, grid, lut, shade_mode=0, shadows=None, ambient=None, drape=None, exposure=None, cumulative=None,
-          viewshed=None, haze=None, stages=None, memo=None):
+def _sources(seeds, u, grid):
+    """what a flood or spill field sees of its sources: the mode, or the seeds' vertices at the uniforms' spacing"""
+    import flood_model as fdm
+    if seeds is None or isinstance(seeds, str):
+        return seeds
+    return _key(fdm.seed_vertices(seeds, fdm.cm.spacing_of(u), max(int(grid), 2)))
+
+
+def chain(rgba, vis, uniforms, height, grid, lut, shade_mode=0, shadows=None, ambient=None, drape=None, flood=None, spill=None, exposure=None,
+          cumulative=None, viewshed=None, haze=None, stages=None, memo=None):
     """THE statement of the library's order of passes over a terrain frame `rgba` (H, W, 4) with visibility `vis`, at whatever size
     they have: the ambient / shadow relight -> the draped image (through its mips, and their anisotropic taps, if asked) -> the
-    sun-exposure, cumulative and viewshed tints -> the haze.  -> the frame behind the last pass.  `stages` (a dict) receives what lies
-    between: lit, sky; shaded, mask; draped, drape_mask, drape_sample (mips on: the mip / anisotropy model's sample planes); per late
+    flood's water -> the spill's sink tint -> the sun-exposure, cumulative and viewshed tints -> the haze.  -> the frame behind the
+    last pass.  `stages` (a dict) receives what lies between: lit, sky; shaded, mask; draped, drape_mask, drape_sample (mips on: the
+    mip / anisotropy model's sample planes); flood_field and spill_field (the models' Field tuples), flood_frame, spill_frame; per late
     pass `<name>_frame` (the frame behind it) and `<name>_field`; haze_opacity.  `memo` (a dict) keeps the vertex fields, which do
-    not depend on the camera or the size, for a caller that runs the chain more than once."""
+    not depend on the camera or the size, for a caller that runs the chain more than once; the flood and spill fields are kept under
+    a key without the exaggeration, which neither depends on (include/vf_hip.h): the heights, the grid, the level and the sources,
+    a seed list as its vertices at the uniforms' spacing."""
     import ambient_model as abm
     import cumulative_viewshed_model as cvm
     import drape_aniso_model as dam
     import drape_mip_model as dmm
     import drape_model as drm
+    import flood_model as fdm
     import haze_model as hzm
     import shadow_model as shm
+    import spill_model as spm
     import sun_exposure_model as sem
     import viewshed_model as vsm
     u = np.ascontiguousarray(uniforms, F32).reshape(44)
@@ -152,6 +168,18 @@ def chain(rgba, vis, uniforms, height, grid, lut, shade_mode=0, shadows=None, am
         else:
             out, st["drape_mask"] = drm.frame(out, vis, u, h, grid, lut, drape["image"], **kw)
     st["draped"] = out
+    ground = (h.shape, h.tobytes(), int(grid))                 # what a flood or spill field sees of the heights: no exaggeration
+    if flood is not None:
+        tint = {k: flood[k] for k in ("shallow_rgba", "deep_rgba", "depth_full") if k in flood}
+        level = float(F32(flood["level"]))
+        F = _memo(memo, ("flood", ground, level, _sources(flood.get("seeds"), u, grid)), lambda: fdm.field(u, h, grid, level, flood.get("seeds")))
+        out, _ = fdm.frame(out, vis, u, h, grid, F, **tint)
+        st["flood_field"], st["flood_frame"] = F, out
+    if spill is not None:
+        tint = {k: spill[k] for k in ("shallow_rgba", "deep_rgba", "depth_full") if k in spill}
+        S = _memo(memo, ("spill", ground, _sources(spill.get("seeds", "edges"), u, grid)), lambda: spm.field(u, h, grid, spill.get("seeds", "edges")))
+        out, _ = spm.frame(out, vis, u, h, grid, S, **tint)
+        st["spill_field"], st["spill_frame"] = S, out
     if exposure is not None:
         field = {k: exposure[k] for k in ("incidence", "softness", "bias") if k in exposure}
         tint = {k: exposure[k] for k in ("high_rgba", "low_rgba") if k in exposure}
