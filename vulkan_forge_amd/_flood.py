@@ -15,6 +15,25 @@ MODES = ("everywhere", "edges", "seeds")
 DEFAULTS = {"shallow_rgba": (96, 176, 224, 128), "deep_rgba": (16, 64, 160, 224), "depth_full": 0.1}
 
 
+def seed_list(seeds, what):
+    """a seed list of set_flood / set_spill -> (N, 2) float32 C-contiguous, 1 <= N <= MAX_SEEDS, finite.  what: the caller's "seeds
+    must be ..." for a value that is no array of numbers."""
+    try:
+        xz = np.asarray(seeds)
+    except Exception:
+        raise TypeError(f"{what}, got {type(seeds).__name__}") from None
+    if xz.dtype == object or xz.dtype.kind not in "fiu":
+        raise TypeError(f"{what}, got dtype {xz.dtype}")
+    if xz.ndim != 2 or xz.shape[1] != 2:
+        raise ValueError(f"seeds must be (N, 2) numbers, got shape {xz.shape}")
+    if not 1 <= xz.shape[0] <= MAX_SEEDS:
+        raise ValueError(f"seeds must hold 1 to {MAX_SEEDS} rows, got {xz.shape[0]}")
+    xz = np.ascontiguousarray(xz, np.float32)
+    if not np.isfinite(xz).all():
+        raise ValueError("seeds must be finite")
+    return xz
+
+
 def flood_args(level, seeds=None, enabled=True, shallow_rgba=(96, 176, 224, 128), deep_rgba=(16, 64, 160, 224), depth_full=0.1):
     """-> (enable 0 / 1, level, mode, seeds (N, 2) float32 C-contiguous or None, shallow (r, g, b, a), deep (r, g, b, a), depth_full) as
     the C call takes them.  seeds: None -- everywhere; "edges"; or (N, 2) numbers (x, z)."""
@@ -33,19 +52,7 @@ def flood_args(level, seeds=None, enabled=True, shallow_rgba=(96, 176, 224, 128)
         mode = EDGES
     else:
         mode = SEEDS
-        try:
-            xz = np.asarray(seeds)
-        except Exception:
-            raise TypeError(f'seeds must be None, "edges" or (N, 2) numbers, got {type(seeds).__name__}') from None
-        if xz.dtype == object or xz.dtype.kind not in "fiu":
-            raise TypeError(f'seeds must be None, "edges" or (N, 2) numbers, got dtype {xz.dtype}')
-        if xz.ndim != 2 or xz.shape[1] != 2:
-            raise ValueError(f"seeds must be (N, 2) numbers, got shape {xz.shape}")
-        if not 1 <= xz.shape[0] <= MAX_SEEDS:
-            raise ValueError(f"seeds must hold 1 to {MAX_SEEDS} rows, got {xz.shape[0]}")
-        xz = np.ascontiguousarray(xz, np.float32)
-        if not np.isfinite(xz).all():
-            raise ValueError("seeds must be finite")
+        xz = seed_list(seeds, 'seeds must be None, "edges" or (N, 2) numbers')
     return (1 if enabled else 0, level, mode, xz, _rgba("shallow_rgba", shallow_rgba), _rgba("deep_rgba", deep_rgba), depth_full)
 
 

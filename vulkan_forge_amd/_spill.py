@@ -6,10 +6,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._flood import MAX_SEEDS, seed_list
 from ._shadows import _number
 from ._viewshed import _rgba
 
-MAX_SEEDS = 65535
 EDGES, SEEDS = 1, 2
 MODES = {EDGES: "edges", SEEDS: "seeds"}
 DEFAULTS = {"shallow_rgba": (96, 176, 224, 128), "deep_rgba": (16, 64, 160, 224), "depth_full": 0.1}
@@ -32,19 +32,7 @@ def spill_args(seeds="edges", enabled=True, shallow_rgba=(96, 176, 224, 128), de
         mode = EDGES
     else:
         mode = SEEDS
-        try:
-            xz = np.asarray(seeds)
-        except Exception:
-            raise TypeError(f'seeds must be "edges" or (N, 2) numbers, got {type(seeds).__name__}') from None
-        if xz.dtype == object or xz.dtype.kind not in "fiu":
-            raise TypeError(f'seeds must be "edges" or (N, 2) numbers, got dtype {xz.dtype}')
-        if xz.ndim != 2 or xz.shape[1] != 2:
-            raise ValueError(f"seeds must be (N, 2) numbers, got shape {xz.shape}")
-        if not 1 <= xz.shape[0] <= MAX_SEEDS:
-            raise ValueError(f"seeds must hold 1 to {MAX_SEEDS} rows, got {xz.shape[0]}")
-        xz = np.ascontiguousarray(xz, np.float32)
-        if not np.isfinite(xz).all():
-            raise ValueError("seeds must be finite")
+        xz = seed_list(seeds, 'seeds must be "edges" or (N, 2) numbers')
     return (1 if enabled else 0, mode, xz, _rgba("shallow_rgba", shallow_rgba), _rgba("deep_rgba", deep_rgba), depth_full)
 
 

@@ -7,9 +7,10 @@
 //   k_flood_seed         the sources' bits into `fl` where `wet` has them (the feature's one atomic: an OR on a 32-bit half)
 //   k_flood_pass         one wave per tile: the halo bits of the four neighbours enter, then the tile runs to its own fixpoint -- a
 //                        Kogge-Stone occluded fill along the rows, one step across them by lane shuffles, until no lane changes.  The
-//                        host repeats the launch until one changes nothing (flood_field, vf_hip.hip)
+//                        host repeats the launch until one changes nothing (SeededFill::fixpoint, vf_hip.hip: the spill's loop too)
 //   k_flood_depth        depth = flooded ? wd : 0 per vertex, and the two counts
-//   k_flood_tint         blends a shallow and a deep colour over the covered pixels of a frame from its stored visibility, flat
+//   k_flood_tint         blends a shallow and a deep colour over the covered pixels of a frame from its stored visibility, flat: the
+//                        tint body (tint_visible) and the blend (vs_depth_tint) are vf_viewshed.h's, shared with k_spill_tint
 //
 // Launched only for a handle that asked for a flood or for the field: the frame path is not touched.  Every device loop has a fixed
 // trip bound, no workgroup waits for another, and bits of `fl` are only ever set: a wave that reads a neighbour's words while that
@@ -192,32 +193,16 @@ __device__ __forceinline__ bool flood_pixel(const FrameParams &P, const SetupVie
     const VisiblePoint<CLIPPED> p = visible_point<CLIPPED>(P, V, s, prim, px, py);
     const float d = point_scalar(P, p, px, py, w0, w1, w2);
     if (!(d > 0.0f)) return false;
-    const float sd = fminf(d / T.depth_full, 1.0f);
-    float c[3] = { dec[rgba & 255u], dec[(rgba >> 8) & 255u], dec[(rgba >> 16) & 255u] };
-    const bool sh = vs_blend(c, dec, T.shallow_rgba, 1.0f - sd);
-    const bool dp = vs_blend(c, dec, T.deep_rgba, sd);
-    if (!sh && !dp) return false;
-    rgba = srgb_encode(c[0], thr) | (srgb_encode(c[1], thr) << 8) | (srgb_encode(c[2], thr) << 16) | 0xFF000000u;
-    return true;
+    return vs_depth_tint(dec, thr, d, T.depth_full, T.shallow_rgba, T.deep_rgba, rgba);
 }
 
-// The frame's visibility (H, W) -> the covered pixels of its colour buffer under water, in the walk of for_each_visible (vf_visible.h).
-// `redo` as for k_viewshed_tint: both instantiations are launched behind a frame and the one the frame does not call for leaves at once.
+// The covered pixels of a frame's colour buffer under water (tint_visible, vf_viewshed.h)
 template <bool CLIPPED>
 __global__ __launch_bounds__(256) void k_flood_tint(FrameParams P, SetupView V, const float *__restrict__ thresh, const uint32_t *__restrict__ vis,
                                                     FloodTint T, const uint32_t *__restrict__ redo, uint32_t *__restrict__ rgba)
 {
-    if ((*redo != 0u) != CLIPPED) return;
-    __shared__ float s_thr[256];
-    __shared__ float s_dec[256];
-    s_thr[threadIdx.x] = thresh[threadIdx.x];
-    s_dec[threadIdx.x] = T.decode[threadIdx.x];
-    __syncthreads();
-    for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
-        if (id == 0u) return;
-        const size_t o = (size_t)py * P.W + px;
-        uint32_t c = rgba[o];
-        if (flood_pixel<CLIPPED>(P, V, T, s_dec, s_thr, id, (int32_t)px, (int32_t)py, c)) rgba[o] = c;
+    tint_visible<CLIPPED>(P, thresh, T.decode, vis, redo, rgba, [&](const float *dec, const float *thr, uint32_t id, int32_t px, int32_t py, uint32_t &c) {
+        return flood_pixel<CLIPPED>(P, V, T, dec, thr, id, px, py, c);
     });
 }
 

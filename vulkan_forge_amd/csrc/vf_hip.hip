@@ -296,6 +296,95 @@ template <typename Feature> static void summed_reset(Feature &H)
     H = Feature();
     H.sum.value.scans = scans; H.sum.forced_batch = forced;
 }
+
+// A per-vertex field that spreads from sources over the height field, pass by pass to a fixpoint, and is shown as a depth tint
+// (DESIGN.md 4s, 4t): what the flood and the spill share.  The feature that holds one keeps what is its own: further inputs, its
+// working buffers, its kernels and counts, and the words of its refusals.
+struct SeededFill {
+    // Passes queued per read-back of their `changed` words.  16: at grid 4096 the fastest of 1, 4 and 16 on both probes of DESIGN.md 4s
+    // and on 4t's (a read-back costs more than a dozen passes that find nothing to do)
+    static constexpr uint32_t kGroup = 16, kMaxGroup = 64;
+    static constexpr int kSeeds = 2;     // the mode of a seed list (VF_FLOOD_SEEDS, VF_SPILL_SEEDS)
+    bool enabled = false, have = false;  // have: the feature's set call has stored its inputs
+    int mode;
+    std::vector<float> xz;               // mode kSeeds: the seeds in the overlays' world frame, (x, z) each; else empty
+    uint32_t shallow_rgba, deep_rgba;    // r | g << 8 | b << 16 | a << 24
+    float depth_full;
+    SeededFill(int mode0, uint32_t shallow, uint32_t deep, float full) : mode(mode0), shallow_rgba(shallow), deep_rgba(deep), depth_full(full) {}   // (the feature's defaults)
+    VertexField field;                   // the feature states what stands in front of key_tail
+    DevBuf<uint32_t> d_seeds;            // the seeds' vertices
+    DevBuf<uint32_t> d_ctl;              // kMaxGroup `changed` words, then the feature's counts
+    std::vector<uint32_t> ij;            // the host's copy of d_seeds (the source of its upload)
+    uint32_t forced_group = 0;           // the feature's vf_terrain_debug_*_group call; 0: kGroup
+    uint32_t passes = 0;                 // of the last computation
+    struct Words { int modes; const char *unknown_mode, *count, *sharded; };   // the feature's modes (bit m: mode m is one), the words of its refusals
+    // What a set call does once its own arguments are in order: the checks on depth_full, the mode and the seed list, the refusal of a
+    // sharded handle, the wait for the frame in flight, the visibility buffer, the values stored.  other_changed: an input of the
+    // feature's own differs from the one held (the caller stores it afterwards).
+    int set(vf_terrain *t, int enable, int new_mode, const float *seeds_xz, uint32_t count, const uint8_t shallow[4], const uint8_t deep[4], float full,
+            bool other_changed, const Words &W);
+    // the seeds' vertices (i, j) for the spacing of the uniforms `u`, snapped as the viewshed's observer is
+    std::vector<uint32_t> vertices(const vf_terrain *t, const float *u) const;
+    int read_seeds(const vf_terrain *t, uint32_t *out, const char *none) const;      // the same for the live uniforms, to a caller
+    // the end of the field's key: the mode, the length of the vertex list, the vertices (which are returned)
+    std::vector<uint32_t> key_tail(const vf_terrain *t, const float *u, std::vector<uint32_t> &key) const
+    {
+        std::vector<uint32_t> v = vertices(t, u);
+        key.push_back((uint32_t)mode); key.push_back((uint32_t)v.size());
+        key.insert(key.end(), v.begin(), v.end());
+        return v;
+    }
+    hipError_t reserve(size_t counts, size_t nseeds) { const hipError_t e = d_ctl.reserve(kMaxGroup + counts, kMaxGroup + counts); return e != hipSuccess ? e : d_seeds.reserve(nseeds, nseeds); }
+    hipError_t upload(std::vector<uint32_t> &v, hipStream_t s)     // v (taken) -> d_seeds (a pageable source: returns when the copy is staged)
+    {
+        ij.swap(v);
+        return hipMemcpyAsync(d_seeds.p, ij.data(), ij.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+    }
+    uint32_t *counts() const { return d_ctl.p + kMaxGroup; }
+    uint32_t group() const { return std::min(forced_group ? forced_group : kGroup, kMaxGroup); }
+    // The loop to the fixpoint: groups of passes, each pass with its own `changed` word, until the first pass that changed nothing;
+    // *count: that pass's number.  queue(p, changed) queues pass p = 1, 2, ... on `s`.  A pass that changes something changes at least
+    // one of nv vertices for good, so pass nv + 1 is not reached: `unreached` is the feature's refusal should it be.
+    template <typename Queue> int fixpoint(hipStream_t s, size_t nv, const char *unreached, uint32_t *count, Queue &&queue) const
+    {
+        const uint32_t G = group();
+        uint32_t changed[kMaxGroup], n = 0;
+        for (bool done = false; !done && n <= nv;) {
+            VF_HIP_TRY(hipMemsetAsync(d_ctl.p, 0, G * sizeof(uint32_t), s));
+            for (uint32_t g = 0; g < G; ++g) queue(n + g + 1u, d_ctl.p + g);
+            VF_HIP_TRY(hipGetLastError());
+            VF_HIP_TRY(hipMemcpyAsync(changed, d_ctl.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            VF_HIP_TRY(hipStreamSynchronize(s));
+            for (uint32_t g = 0; g < G && !done; ++g, ++n) done = changed[g] == 0u;
+        }
+        if (n > nv) return fail(VF_ERR_HIP, unreached);
+        *count = n;
+        return VF_OK;
+    }
+    int force_group(uint32_t g)
+    {
+        if (g > kMaxGroup) return fail(VF_ERR_INVALID, "a group holds at most 64 passes");
+        if (forced_group != g) field.valid = false;                 // (the next call computes the field again, with this group size)
+        forced_group = g;
+        return VF_OK;
+    }
+    template <typename Info> void info(Info *out) const             // what vf_flood_info and vf_spill_info name alike
+    {
+        out->enabled = enabled ? 1 : 0; out->mode = mode; out->count = (uint32_t)(xz.size() / 2u); out->depth_full = depth_full;
+        for (int k = 0; k < 4; ++k) { out->shallow_rgba[k] = (uint8_t)(shallow_rgba >> (8 * k)); out->deep_rgba[k] = (uint8_t)(deep_rgba >> (8 * k)); }
+        out->passes = passes; out->scans = field.scans; out->group = group();
+    }
+    void release() { field.release(); d_seeds.release(); d_ctl.release(); }
+};
+// A feature struct with a SeededFill `fill`, its other buffers released: gone, as if the handle never asked (the caller has
+// synchronised); the scan counter and a forced group size stay
+template <typename Feature> static void fill_reset(Feature &H)
+{
+    H.fill.release();
+    const uint32_t scans = H.fill.field.scans, forced = H.fill.forced_group;
+    H = Feature();
+    H.fill.field.scans = scans; H.fill.forced_group = forced;
+}
 static uint32_t key_bits(float f) { uint32_t w; std::memcpy(&w, &f, sizeof w); return w; }
 static std::vector<uint32_t> key_of(std::initializer_list<float> fs)
 {
@@ -544,39 +633,23 @@ struct vf_terrain {
     // flood analysis: buffers made by the first tinted frame or field read; the field is computed again only when what
     // it was made from has changed (not for the colours, depth_full, the camera, the sun or the exaggeration)
     struct Flood {
-        bool enabled = false, have = false;      // have: a level is set (vf_terrain_set_flood)
+        // the depth; key: the bits of level, then key_tail; the counts behind d_ctl's `changed` words: flooded, wettable (one 64-bit word)
+        SeededFill fill{ VF_FLOOD_EVERYWHERE, VF_FLOOD_SHALLOW_RGBA, VF_FLOOD_DEEP_RGBA, VF_FLOOD_DEPTH_FULL };
         float level = 0.0f;
-        int mode = VF_FLOOD_EVERYWHERE;
-        std::vector<float> xz;           // VF_FLOOD_SEEDS: the seeds in the overlays' world frame, (x, z) each
-        uint32_t shallow_rgba = VF_FLOOD_SHALLOW_RGBA, deep_rgba = VF_FLOOD_DEEP_RGBA;   // r | g << 8 | b << 16 | a << 24
-        float depth_full = VF_FLOOD_DEPTH_FULL;
-        VertexField depth;               // key: the bits of level, the mode, the length of the vertex list, the seeds' vertices (i, j) each
-        DevBuf<uint64_t> d_wet, d_fl;    // the masks, tile-major (vf_flood.h); they and d_wd stand as long as `depth` does: the tint reads them
+        DevBuf<uint64_t> d_wet, d_fl;    // the masks, tile-major (vf_flood.h); they and d_wd stand as long as the field does: the tint reads them
         DevBuf<float> d_wd;              // level - h, n x n
-        DevBuf<uint32_t> d_seeds;        // the seeds' vertices
-        DevBuf<uint32_t> d_ctl;          // kFloodMaxGroup `changed` words, then the two counts (one 64-bit word)
-        std::vector<uint32_t> ij;        // the host's copy of d_seeds (the source of its upload)
-        uint32_t forced_group = 0;       // vf_terrain_debug_flood_group; 0: kFloodGroup
-        uint32_t passes = 0, flooded = 0, wettable = 0;   // of the last computation
+        uint32_t flooded = 0, wettable = 0;      // of the last computation
     } fd;
     // spill analysis: buffers made by the first tinted frame or field read; the field is computed again only when what
     // it was made from has changed (not for the colours or depth_full)
     struct Spill {
-        bool enabled = false, have = false;      // have: sources are set (vf_terrain_set_spill)
-        int mode = VF_SPILL_EDGES;
-        std::vector<float> xz;           // VF_SPILL_SEEDS: the seeds in the overlays' world frame, (x, z) each
-        uint32_t shallow_rgba = VF_SPILL_SHALLOW_RGBA, deep_rgba = VF_SPILL_DEEP_RGBA;   // r | g << 8 | b << 16 | a << 24
-        float depth_full = VF_SPILL_DEPTH_FULL;
-        VertexField spill;               // key: the mode, the length of the vertex list, the seeds' vertices (i, j) each
-        DevBuf<float> d_sd;              // spill - h, n x n; stands as long as `spill` does: the tint and the sink-depth read take it
+        // the spill; key: key_tail alone; the counts behind d_ctl's `changed` words: reached, sinks (one 64-bit word), then tile_runs
+        SeededFill fill{ VF_SPILL_EDGES, VF_SPILL_SHALLOW_RGBA, VF_SPILL_DEEP_RGBA, VF_SPILL_DEPTH_FULL };
+        DevBuf<float> d_sd;              // spill - h, n x n; stands as long as the field does: the tint and the sink-depth read take it
         DevBuf<uint32_t> d_hk, d_w;      // the keys of h and of the spill, tile-major (vf_spill.h)
         DevBuf<uint32_t> d_act;          // the activity words: two arrays of one word per tile
-        DevBuf<uint32_t> d_seeds;        // the seeds' vertices
-        DevBuf<uint32_t> d_ctl;          // kSpillMaxGroup `changed` words, then the two counts (one 64-bit word), then tile_runs
-        std::vector<uint32_t> ij;        // the host's copy of d_seeds (the source of its upload)
-        uint32_t forced_group = 0;       // vf_terrain_debug_spill_group; 0: kSpillGroup
         bool no_flags = false;           // vf_terrain_debug_spill_group with VF_SPILL_GROUP_NO_FLAGS: every tile runs in every pass
-        uint32_t passes = 0, reached = 0, sinks = 0, tile_runs = 0;   // of the last computation
+        uint32_t reached = 0, sinks = 0, tile_runs = 0;   // of the last computation
     } sp;
     uint64_t height_gen = 1;             // counts height uploads
     // vf_terrain_render_batch_host: a ring of device frames the poses are drawn into while earlier ones travel to the host
@@ -1034,25 +1107,18 @@ static void exposure_release(vf_terrain *t)
     summed_reset(t->se);
 }
 
-// the flood: gone, as if the handle never asked (the caller has synchronised); the scan counter and a forced group size stay
+// the flood and the spill: gone as fill_reset says; the spill's other group setting stays too
 static void flood_release(vf_terrain *t)
 {
-    vf_terrain::Flood &H = t->fd;
-    H.depth.release(); H.d_wet.release(); H.d_fl.release(); H.d_wd.release(); H.d_seeds.release(); H.d_ctl.release();
-    const uint32_t scans = H.depth.scans, forced = H.forced_group;
-    H = vf_terrain::Flood();
-    H.depth.scans = scans; H.forced_group = forced;
+    t->fd.d_wet.release(); t->fd.d_fl.release(); t->fd.d_wd.release();
+    fill_reset(t->fd);
 }
-
-// the spill: gone, as if the handle never asked (the caller has synchronised); the scan counter and the forced group settings stay
 static void spill_release(vf_terrain *t)
 {
-    vf_terrain::Spill &H = t->sp;
-    H.spill.release(); H.d_sd.release(); H.d_hk.release(); H.d_w.release(); H.d_act.release(); H.d_seeds.release(); H.d_ctl.release();
-    const uint32_t scans = H.spill.scans, forced = H.forced_group;
-    const bool no_flags = H.no_flags;
-    H = vf_terrain::Spill();
-    H.spill.scans = scans; H.forced_group = forced; H.no_flags = no_flags;
+    t->sp.d_sd.release(); t->sp.d_hk.release(); t->sp.d_w.release(); t->sp.d_act.release();
+    const bool no_flags = t->sp.no_flags;
+    fill_reset(t->sp);
+    t->sp.no_flags = no_flags;
 }
 
 int vf_terrain_create(vf_ctx *ctx, uint32_t width, uint32_t height, uint32_t grid, const uint8_t lut_rgba8[1024],
@@ -1298,6 +1364,73 @@ int vf_terrain_raster_groups(const vf_terrain *t, int *in_use, float ms[2])
     return VF_OK;
 }
 
+// ---- the passes behind the tile kernel -----------------------------------------------------------------------
+// Every pass that rewrites the terrain's pixels from the stored visibility (vf_visible.h), in the order a frame draws them behind its
+// tile kernels: light on the surface, what lies on it (the image, the water, the sinks), the analysis tints with the single observer's
+// on top, the air in front of it all.  Each needs the whole frame on one handle and the frame's own inputs, so a handle that has one
+// on is not sharded and draws no batches.  A new pass is a row here and a place in kRefusalOrder.
+using FramePassRun = int(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
+                        bool shadows, bool ambient);
+static FramePassRun viewshed_pass, cumulative_pass, exposure_pass, haze_pass, flood_pass, spill_pass;
+
+// The drape's shade pass as the handle's settings choose it: through the mip pyramid when mipmaps are on (DESIGN.md 4k), and with
+// anisotropic taps when the largest anisotropy is above 1 as well (4p); the frames and the drape diagnostics both ask here
+static Relight drape_pass_of(const vf_terrain *t) { return !t->dm.enabled ? kDrape : t->dm.aniso > 1u ? kDrapeAniso : kDrapeMip; }
+
+// cast shadows and ambient occlusion are one pass of the relight kernel, whichever of them is on
+static int light_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    return relight_pass(t, s, P, V, redo, rgba, t->am.enabled ? kAmbient : kShadow, t->sh.enabled, t->am.enabled);
+}
+static int drape_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    return relight_pass(t, s, P, V, redo, rgba, drape_pass_of(t), t->sh.enabled, t->am.enabled);
+}
+
+struct FramePass {
+    bool (*on)(const vf_terrain *);
+    FramePassRun *run;
+    const char *sharded, *batched;       // why a handle that has it on is not sharded / draws no batch
+};
+enum { kPassShadows, kPassAmbient, kPassDrape, kPassFlood, kPassSpill, kPassExposure, kPassCumulative, kPassViewshed, kPassHaze, kFramePasses };
+static const FramePass kFramePassTable[kFramePasses] = {
+    { [](const vf_terrain *t) { return t->sh.enabled; }, light_pass, "the handle has shadows enabled: shadows need a whole-frame handle",
+      "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose" },
+    // (with shadows on, their row draws both and, tested first, refuses for both)
+    { [](const vf_terrain *t) { return t->am.enabled && !t->sh.enabled; }, light_pass, "the handle has ambient occlusion enabled: it needs a whole-frame handle",
+      "render_batch on a handle with ambient occlusion enabled is not supported" },
+    { [](const vf_terrain *t) { return t->dr.iw != 0u; }, drape_pass, "the handle holds a draped image: it needs a whole-frame handle",
+      "render_batch on a handle that holds a draped image is not supported" },                    // (4j: behind the shadow / ambient pass)
+    { [](const vf_terrain *t) { return t->fd.fill.enabled; }, flood_pass, "the handle has a flood enabled: it needs a whole-frame handle",
+      "render_batch on a handle with a flood enabled is not supported" },                         // (4s: on the surface, under the analysis tints)
+    { [](const vf_terrain *t) { return t->sp.fill.enabled; }, spill_pass, "the handle has the spill enabled: it needs a whole-frame handle",
+      "render_batch on a handle with the spill enabled is not supported" },                       // (4t: directly behind the flood's water)
+    { [](const vf_terrain *t) { return t->se.enabled; }, exposure_pass, "the handle has sun exposure enabled: it needs a whole-frame handle",
+      "render_batch on a handle with sun exposure enabled is not supported" },                    // (4n: behind both viewshed tints)
+    { [](const vf_terrain *t) { return t->cv.enabled; }, cumulative_pass, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle",
+      "render_batch on a handle with a cumulative viewshed enabled is not supported" },           // (4m: behind the single observer's)
+    { [](const vf_terrain *t) { return t->vs.enabled; }, viewshed_pass, "the handle has a viewshed enabled: it needs a whole-frame handle",
+      "render_batch on a handle with a viewshed enabled is not supported" },                      // (4l)
+    { [](const vf_terrain *t) { return t->hz.enabled; }, haze_pass, "the handle has haze enabled: it needs a whole-frame handle",
+      "render_batch on a handle with haze enabled is not supported" },                            // (4q: between the eye and the painted surface)
+};
+// The refusals are tested in the order the features came, which decides the message when several are on.  Supersampling (4o) is no
+// row -- its resolve rewrites the frame, not the samples -- but is refused among them, behind the first `ss_at` rows.  batch: for
+// render_batch and render_batch_host, else for the shard calls.  NULL: nothing is refused.
+static const int kRefusalOrder[kFramePasses] = { kPassShadows, kPassAmbient, kPassDrape, kPassViewshed, kPassCumulative, kPassExposure, kPassHaze,
+                                                 kPassFlood, kPassSpill };
+static const char *pass_refusal(const vf_terrain *t, bool batch, int ss_at = kFramePasses)
+{
+    for (int k = 0; k < kFramePasses && !(k == ss_at && t->ss > 1u); ++k) {
+        const FramePass &R = kFramePassTable[kRefusalOrder[k]];
+        if (R.on(t)) return batch ? R.batched : R.sharded;
+    }
+    if (t->ss <= 1u) return nullptr;
+    return batch ? "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)"
+                 : "the handle is supersampled: the resolve needs a whole-frame handle";
+}
+
 // The shard layout has changed (the caller has waited for the frame in flight): nothing rendered under the new one yet, and the tile
 // numbering is another -- forget the scheduling feedback of the previous layout
 static int reset_layout_feedback(vf_terrain *t)
@@ -1321,16 +1454,7 @@ int vf_terrain_set_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uint32_t
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!is_pow2(band_h) || band_h < (uint32_t)kTileH) return fail(VF_ERR_INVALID, "band_h must be a power of two >= 64 (the tile height)");
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
-    if (t->sh.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
-    if (t->am.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
-    if (t->dr.iw && nranks != 1) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
-    if (t->vs.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
-    if (t->cv.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
-    if (t->se.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
-    if (t->ss > 1u && nranks != 1) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
-    if (t->hz.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
-    if (t->fd.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has a flood enabled: it needs a whole-frame handle");
-    if (t->sp.enabled && nranks != 1) return fail(VF_ERR_INVALID, "the handle has the spill enabled: it needs a whole-frame handle");
+    if (const char *why = nranks != 1 ? pass_refusal(t, false, 6) : nullptr) return fail(VF_ERR_INVALID, why);   // (supersampling: behind sun exposure)
     VF_HIP_TRY(wait_frame(t));
     t->inputs_gen++;
     t->geom_gen++;                                         // (rank, nranks and the band height decide which blocks k_block_boxes keeps)
@@ -1453,16 +1577,7 @@ int vf_terrain_set_tile_shard(vf_terrain *t, uint32_t rank, uint32_t nranks, uin
     if (nranks == 0 || rank >= nranks) return fail(VF_ERR_INVALID, "rank must be < nranks");
     if (!layout_valid(skew)) return fail(VF_ERR_INVALID, "layout word is neither VF_TILE_LAYOUT(skew < 65536, stripe_log2 <= 15) nor a registered stripe map");
     if (!t->ov.layer.empty()) return fail(VF_ERR_INVALID, "the handle has overlays: sharded compositing is not supported (vf_terrain_clear_overlays first)");
-    if (t->sh.enabled) return fail(VF_ERR_INVALID, "the handle has shadows enabled: shadows need a whole-frame handle");
-    if (t->am.enabled) return fail(VF_ERR_INVALID, "the handle has ambient occlusion enabled: it needs a whole-frame handle");
-    if (t->dr.iw) return fail(VF_ERR_INVALID, "the handle holds a draped image: it needs a whole-frame handle");
-    if (t->vs.enabled) return fail(VF_ERR_INVALID, "the handle has a viewshed enabled: it needs a whole-frame handle");
-    if (t->ss > 1u) return fail(VF_ERR_INVALID, "the handle is supersampled: the resolve needs a whole-frame handle");
-    if (t->cv.enabled) return fail(VF_ERR_INVALID, "the handle has a cumulative viewshed enabled: it needs a whole-frame handle");
-    if (t->se.enabled) return fail(VF_ERR_INVALID, "the handle has sun exposure enabled: it needs a whole-frame handle");
-    if (t->hz.enabled) return fail(VF_ERR_INVALID, "the handle has haze enabled: it needs a whole-frame handle");
-    if (t->fd.enabled) return fail(VF_ERR_INVALID, "the handle has a flood enabled: it needs a whole-frame handle");
-    if (t->sp.enabled) return fail(VF_ERR_INVALID, "the handle has the spill enabled: it needs a whole-frame handle");
+    if (const char *why = pass_refusal(t, false, 4)) return fail(VF_ERR_INVALID, why);      // (supersampling: behind the viewshed)
     VF_HIP_TRY(wait_frame(t));
     std::vector<uint32_t> map((size_t)t->ntx * t->nty);
     uint32_t n = 0;
@@ -1902,22 +2017,6 @@ static int overlay_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, cons
     return VF_OK;
 }
 
-// diag: a visibility / diagnostics frame (render_visibility): stores its visibility, composites no overlays.  A frame of a handle with an
-// occluding overlay layer stores its visibility too, for the overlay pass.
-static int relight_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, Relight pass,
-                        bool shadows, bool ambient);
-
-// The drape's shade pass as the handle's settings choose it: through the mip pyramid when mipmaps are on (DESIGN.md 4k), and with
-// anisotropic taps when the largest anisotropy is above 1 as well (4p); the frames and the drape diagnostics both ask here
-static Relight drape_pass_of(const vf_terrain *t) { return !t->dm.enabled ? kDrape : t->dm.aniso > 1u ? kDrapeAniso : kDrapeMip; }
-
-static int viewshed_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-static int cumulative_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-static int exposure_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-static int haze_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-static int flood_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-static int spill_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
-
 // The resolve of a supersampled handle's samples into its frame (vf_resolve.h).  Defined with the other supersampling calls below: the template is
 // instantiated there, behind the tile kernels and what they call, whose code -- PC-relative call offsets included -- keeps its place
 static void resolve_launch(const vf_terrain *t, hipStream_t s, uint32_t *dst);
@@ -1933,20 +2032,14 @@ static FrameParams output_params(const vf_terrain *t, const FrameParams &P)
     return Q;
 }
 
+// diag: a visibility / diagnostics frame (render_visibility): stores its visibility, composites no overlays and runs no pass of
+// kFramePassTable: the frame as the tile kernel shades it.  A frame of a handle with an occluding overlay layer or with such a pass
+// stores its visibility too, for that pass.
 static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool diag)
 {
     const FrameParams &P = K.P;
-    const bool shadows = t->sh.enabled && !diag;           // (visibility / diagnostics frames: the frame as the tile kernel shades it)
-    const bool ambient = t->am.enabled && !diag;
-    const bool drape = t->dr.iw != 0u && !diag;
-    const Relight drape_pass = drape_pass_of(t);
-    const bool viewshed = t->vs.enabled && !diag;
-    const bool cumulative = t->cv.enabled && !diag;
-    const bool exposure = t->se.enabled && !diag;
-    const bool haze = t->hz.enabled && !diag;
-    const bool flood = t->fd.enabled && !diag;
-    const bool spill = t->sp.enabled && !diag;
-    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || shadows || ambient || drape || viewshed || cumulative || exposure || haze || flood || spill;
+    const bool passes = !diag && std::any_of(std::begin(kFramePassTable), std::end(kFramePassTable), [t](const FramePass &R) { return R.on(t); });
+    const bool write_vis = diag || (t->ov.occluding && t->ov.nprims) || passes;
     vf_terrain::PlanState &S = t->ps[K.set];
     const uint32_t ntiles = K.ntiles, set = K.set;
     uint32_t *const rc_lo = K.rc_lo, *const rc_hi = K.rc_hi, *const seg_count = K.seg_count;
@@ -2006,38 +2099,10 @@ static int draw_frame(vf_terrain *t, hipStream_t s, const FramePlan &K, bool dia
     }
     else VF_HIP_TRY(hipMemsetAsync(seg_count, 0, sizeof(uint32_t), s));   // (a shard without tiles: what k_clear does on its way in)
     if (timing_now) { VF_HIP_TRY(hipEventRecord(ev.end, s)); t->timed_frames++; }
-    if ((shadows || ambient) && ntiles) {                  // cast shadows and ambient occlusion: behind the tile kernels, in front of the overlays
-        const int src = relight_pass(t, s, P, V, S.work_count + 3, raster, ambient ? kAmbient : kShadow, shadows, ambient);
-        if (src != VF_OK) return src;
-    }
-    if (drape && ntiles) {                                 // the draped image: behind the shadow / ambient pass, in front of the overlays
-        const int drc = relight_pass(t, s, P, V, S.work_count + 3, raster, drape_pass, shadows, ambient);
-        if (drc != VF_OK) return drc;
-    }
-    if (flood && ntiles) {                                 // the flood's water: on the surface, so behind the relight passes and under the analysis tints
-        const int frc = flood_pass(t, s, P, V, S.work_count + 3, raster);
-        if (frc != VF_OK) return frc;
-    }
-    if (spill && ntiles) {                                 // the sink tint: directly behind the flood's water
-        const int src = spill_pass(t, s, P, V, S.work_count + 3, raster);
-        if (src != VF_OK) return src;
-    }
-    if (exposure && ntiles) {                              // the sun exposure's tint: behind both viewshed tints
-        const int erc = exposure_pass(t, s, P, V, S.work_count + 3, raster);
-        if (erc != VF_OK) return erc;
-    }
-    if (cumulative && ntiles) {                            // the cumulative viewshed's tint: behind the single observer's
-        const int crc = cumulative_pass(t, s, P, V, S.work_count + 3, raster);
-        if (crc != VF_OK) return crc;
-    }
-    if (viewshed && ntiles) {                              // the viewshed tint: behind the relight passes, in front of the overlays
-        const int vrc = viewshed_pass(t, s, P, V, S.work_count + 3, raster);
-        if (vrc != VF_OK) return vrc;
-    }
-    if (haze && ntiles) {                                  // atmospheric haze: between the eye and the painted surface, so behind the tints; under the resolve and the overlays
-        const int hrc = haze_pass(t, s, P, V, S.work_count + 3, raster);
-        if (hrc != VF_OK) return hrc;
-    }
+    if (passes && ntiles)                                  // behind the tile kernels, under the resolve and the overlays
+        for (const FramePass &R : kFramePassTable) {
+            if (int rc = R.on(t) ? R.run(t, s, P, V, S.work_count + 3, raster) : VF_OK) return rc;
+        }
     if (resolve) {                                        // the samples -> the frame: every output pixel is rewritten, whatever the tiles drew
         resolve_launch(t, s, t->d_rgba);
         VF_HIP_TRY(hipGetLastError());
@@ -2168,16 +2233,7 @@ int vf_terrain_render(vf_terrain *t, void *stream)
 int vf_terrain_render_batch(vf_terrain *t, const float *uniforms, uint32_t n, void *const *dev_rgba, void *stream)
 {
     if (!t || (!uniforms && n)) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
-    if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
-    if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
-    if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
-    if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
-    if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
-    if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
-    if (t->fd.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a flood enabled is not supported");
-    if (t->sp.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with the spill enabled is not supported");
-    if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
+    if (const char *why = pass_refusal(t, true)) return fail(VF_ERR_INVALID, why);
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     hipStream_t s = stream ? (hipStream_t)stream : t->ctx->stream;
     for (uint32_t k = 0; k < n; ++k) {
@@ -2194,16 +2250,7 @@ int vf_terrain_render_batch_host(vf_terrain *t, const float *uniforms, uint32_t 
 {
     if (!t || !uniforms || !host_rgba) return fail(VF_ERR_INVALID, "NULL argument");
     if (t->shard_tiles || t->local_rows != t->H) return fail(VF_ERR_INVALID, "batch read-back needs the whole frame on one handle (pose-parallel ranks are replicas)");
-    if (t->sh.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with shadows enabled is not supported: a sun per pose would need a shadow field per pose");
-    if (t->am.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with ambient occlusion enabled is not supported");
-    if (t->dr.iw) return fail(VF_ERR_INVALID, "render_batch on a handle that holds a draped image is not supported");
-    if (t->vs.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a viewshed enabled is not supported");
-    if (t->cv.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a cumulative viewshed enabled is not supported");
-    if (t->se.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with sun exposure enabled is not supported");
-    if (t->hz.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with haze enabled is not supported");
-    if (t->fd.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with a flood enabled is not supported");
-    if (t->sp.enabled) return fail(VF_ERR_INVALID, "render_batch on a handle with the spill enabled is not supported");
-    if (t->ss > 1u) return fail(VF_ERR_INVALID, "render_batch on a supersampled handle is not supported: render the poses one by one (vf_terrain_render)");
+    if (const char *why = pass_refusal(t, true)) return fail(VF_ERR_INVALID, why);
     for (uint32_t k = 0; k < n; ++k) if (!host_rgba[k]) return fail(VF_ERR_INVALID, "host_rgba holds a NULL destination");
     VF_HIP_TRY(hipSetDevice(t->ctx->device));
     constexpr uint32_t R = vf_terrain::kBatchRing;
@@ -3314,10 +3361,10 @@ static const FieldRow kFieldTable[kFields] = {
       [](const vf_terrain *t) -> const char * { return t->cv.xz.empty() ? "no observers set (vf_terrain_set_cumulative_viewshed)" : nullptr; } },
     { exposure_field, [](vf_terrain *t) -> VertexField & { return t->se.sum.value; },
       [](const vf_terrain *t) -> const char * { return t->se.suns.empty() ? "no suns set (vf_terrain_set_sun_exposure)" : nullptr; } },
-    { flood_field, [](vf_terrain *t) -> VertexField & { return t->fd.depth; },
-      [](const vf_terrain *t) -> const char * { return t->fd.have ? nullptr : "no flood set (vf_terrain_set_flood)"; } },
-    { spill_field, [](vf_terrain *t) -> VertexField & { return t->sp.spill; },
-      [](const vf_terrain *t) -> const char * { return t->sp.have ? nullptr : "no spill set (vf_terrain_set_spill)"; } },
+    { flood_field, [](vf_terrain *t) -> VertexField & { return t->fd.fill.field; },
+      [](const vf_terrain *t) -> const char * { return t->fd.fill.have ? nullptr : "no flood set (vf_terrain_set_flood)"; } },
+    { spill_field, [](vf_terrain *t) -> VertexField & { return t->sp.fill.field; },
+      [](const vf_terrain *t) -> const char * { return t->sp.fill.have ? nullptr : "no spill set (vf_terrain_set_spill)"; } },
 };
 
 // Field f for the live uniforms, heights and parameters, complete in its buffer; then to `host`, or to `dev` behind the work on
@@ -3797,13 +3844,17 @@ static int viewshed_field(vf_terrain *t, const float *u, hipStream_t s, bool for
     return VF_OK;
 }
 
-// Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
-static void tint_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba, const ViewshedTint &T)
+} // extern "C"   (a template has C++ linkage)
+// Both instantiations of a tint kernel (k_viewshed_tint, k_flood_tint, k_spill_tint) with its parameters T, in k_resolve's launch shape (gb_grid)
+template <typename Tint> using TintKernel = void(FrameParams, SetupView, const float *, const uint32_t *, Tint, const uint32_t *, uint32_t *);
+template <typename Tint> static void tint_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba,
+                                                 const Tint &T, TintKernel<Tint> *whole, TintKernel<Tint> *clipped)
 {
     const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_viewshed_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
-    hipLaunchKernelGGL((k_viewshed_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    hipLaunchKernelGGL(whole, grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    hipLaunchKernelGGL(clipped, grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
 }
+extern "C" {
 
 static void viewshed_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
@@ -3815,7 +3866,7 @@ static void viewshed_launch(const vf_terrain *t, hipStream_t s, const FrameParam
     T.xo = -1.5f + (float)viewshed_index(t, H.ox, P.spacing) * step; T.zo = -1.5f + (float)viewshed_index(t, H.oz, P.spacing) * step;
     const float R = H.radius / P.spacing;
     T.RR = R * R; T.radius_on = H.radius > 0.0f ? 1u : 0u;
-    tint_launch(t, s, P, V, redo, rgba, T);
+    tint_launch(t, s, P, V, redo, rgba, T, k_viewshed_tint<false>, k_viewshed_tint<true>);
 }
 
 // The tint of a frame, on the draw stream behind its tile kernels (which stored the visibility) and the relight passes: the field
@@ -3943,7 +3994,7 @@ int SummedField::tint(const vf_terrain *t, hipStream_t s, const FrameParams &P, 
     ViewshedTint T = {};                                       // (no radius: every covered pixel is treated)
     T.seen = d_frac.p; T.decode = t->ctx->d_decode;
     T.visible_rgba = high_rgba; T.hidden_rgba = low_rgba;
-    tint_launch(t, s, P, V, redo, rgba, T);
+    tint_launch(t, s, P, V, redo, rgba, T, k_viewshed_tint<false>, k_viewshed_tint<true>);
     VF_HIP_TRY(hipGetLastError());
     return VF_OK;
 }
@@ -4771,117 +4822,168 @@ int vf_triangle_render(vf_ctx *ctx, uint32_t width, uint32_t height, uint8_t *rg
     return VF_OK;
 }
 
-// ---- flood analysis (vf_flood.h, DESIGN.md 4s) -------------------------------------------------------------
+// ---- seeded fills: what the flood and the spill share (SeededFill) -----------------------
 
-// Passes of k_flood_pass queued per read-back of their `changed` words.  16: at grid 4096 the fastest of 1, 4 and 16 on both probes of
-// DESIGN.md 4s (a read-back costs more than a dozen passes that find nothing to do)
-constexpr uint32_t kFloodGroup = 16, kFloodMaxGroup = 64;
+static_assert(VF_FLOOD_SEEDS == SeededFill::kSeeds && VF_SPILL_SEEDS == SeededFill::kSeeds && VF_FLOOD_MAX_SEEDS == VF_SPILL_MAX_SEEDS, "one seed-list rule");
+
+std::vector<uint32_t> SeededFill::vertices(const vf_terrain *t, const float *u) const
+{
+    const float spacing = spacing_of(u);
+    std::vector<uint32_t> v(xz.size());
+    for (size_t k = 0; k < xz.size(); ++k) v[k] = viewshed_index(t, xz[k], spacing);
+    return v;
+}
+
+int SeededFill::read_seeds(const vf_terrain *t, uint32_t *out, const char *none) const
+{
+    if (xz.empty()) return fail(VF_ERR_INVALID, none);
+    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
+    const std::vector<uint32_t> v = vertices(t, t->inputs.u);
+    std::memcpy(out, v.data(), v.size() * sizeof(uint32_t));
+    return VF_OK;
+}
+
+int SeededFill::set(vf_terrain *t, int enable, int new_mode, const float *seeds_xz, uint32_t count, const uint8_t shallow[4], const uint8_t deep[4], float full,
+                    bool other_changed, const Words &W)
+{
+    if (!(std::isfinite(full) && full > 0.0f)) return fail(VF_ERR_INVALID, "depth_full must be a finite number > 0");
+    if (new_mode < 0 || new_mode > kSeeds || !((W.modes >> new_mode) & 1)) return fail(VF_ERR_INVALID, W.unknown_mode);
+    if (new_mode == kSeeds) {
+        if (!seeds_xz) return fail(VF_ERR_INVALID, "NULL argument: the seeds");
+        if (count < 1u || count > VF_FLOOD_MAX_SEEDS) return fail(VF_ERR_INVALID, W.count);
+        for (size_t k = 0; k < (size_t)2u * count; ++k)
+            if (!std::isfinite(seeds_xz[k])) return fail(VF_ERR_INVALID, "the seeds must be finite");
+    } else count = 0u;
+    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, W.sharded);
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    const uint32_t sh = pack_rgba8(shallow), dp = pack_rgba8(deep);
+    std::vector<float> seeds;
+    if (count) seeds.assign(seeds_xz, seeds_xz + (size_t)2u * count);
+    if (enabled != (enable != 0) || !have || other_changed || mode != new_mode || xz != seeds || shallow_rgba != sh || deep_rgba != dp || depth_full != full)
+        t->inputs_gen++;
+    enabled = enable != 0; have = true;
+    mode = new_mode;
+    xz.swap(seeds);
+    shallow_rgba = sh; deep_rgba = dp; depth_full = full;
+    return VF_OK;
+}
+
+// The tint of a frame by the fill of field f, on the draw stream behind its tile kernels (which stored the visibility): the field if
+// it is stale, then `launch`, the feature's tint pass over the covered pixels
+using FillLaunch = void(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba);
+static int fill_pass(vf_terrain *t, Field f, FillLaunch *launch, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
+{
+    if (int rc = kFieldTable[f].compute(t, t->inputs.u, s, false)) return rc;
+    launch(t, s, P, V, redo, rgba);
+    VF_HIP_TRY(hipGetLastError());
+    return VF_OK;
+}
+
+static SeededFill &flood_fill(vf_terrain *t) { return t->fd.fill; }
+static SeededFill &spill_fill(vf_terrain *t) { return t->sp.fill; }
+
+// The vf_terrain_clear_* call of a fill: off, the defaults again, the buffers freed (`release`)
+static int fill_clear(vf_terrain *t, SeededFill &(*fill)(vf_terrain *), void (*release)(vf_terrain *))
+{
+    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
+    VF_HIP_TRY(hipSetDevice(t->ctx->device));
+    VF_HIP_TRY(wait_frame(t));
+    if (fill(t).enabled) t->inputs_gen++;
+    release(t);
+    return VF_OK;
+}
+
+// The vf_terrain_debug_*_stage call of a fill: ms[0] its field f computed anyway, ms[1] its tint pass on the frame rendered last
+static int fill_stage(vf_terrain *t, Field f, SeededFill &(*fill)(vf_terrain *), const char *label, const char *none, FillLaunch *launch, uint32_t repeats, float ms[2])
+{
+    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
+    if (!fill(t).have || !fill(t).enabled) return fail(VF_ERR_INVALID, none);
+    if (repeats == 0) repeats = 1;
+    RelightStage G;
+    if (int rc = G.open(t)) return rc;
+    if (int rc = kFieldTable[f].compute(t, G.u, G.s, false)) return rc;          // (the tint's launches below read what the current field left)
+    return G.time_pair(repeats, ms, label, [&] { return kFieldTable[f].compute(t, G.u, G.s, true); },
+                       [&] { launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
+}
+
+// ---- flood analysis (vf_flood.h, DESIGN.md 4s) -------------------------------------------------------------
 
 static uint32_t flood_tiles(const vf_terrain *t) { return (t->n + kFloodTile - 1u) / kFloodTile; }
 
-// the seeds' vertices (i, j) for the spacing of the uniforms `u`, snapped as the viewshed's observer is
-static void flood_vertices(const vf_terrain *t, const float *u, std::vector<uint32_t> &ij)
-{
-    const vf_terrain::Flood &H = t->fd;
-    const float spacing = spacing_of(u);
-    ij.resize(H.xz.size());
-    for (size_t k = 0; k < H.xz.size(); ++k) ij[k] = viewshed_index(t, H.xz[k], spacing);
-}
-
-// `depth` holds the field of the handle's heights, level and sources once this returns (the height cache must be current and ordered
-// before `s`, as for shadow_field); d_fl and d_wd hold what the tint reads.  The loop to the fixpoint runs here: groups of passes, each
-// with its own `changed` word, until the first pass that changed nothing.  force: compute it anyway.
+// The field holds the depth of the handle's heights, level and sources once this returns (the height cache must be current and ordered
+// before `s`, as for shadow_field); d_fl and d_wd hold what the tint reads.  force: compute it anyway.
 static int flood_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::Flood &H = t->fd;
-    if (!H.have) return fail(VF_ERR_INVALID, "no flood set (vf_terrain_set_flood)");
-    std::vector<uint32_t> ij;
-    if (H.mode == VF_FLOOD_SEEDS) flood_vertices(t, u, ij);
+    SeededFill &S = H.fill;
+    if (!S.have) return fail(VF_ERR_INVALID, "no flood set (vf_terrain_set_flood)");
     std::vector<uint32_t> key = key_of({ H.level });
-    key.push_back((uint32_t)H.mode); key.push_back((uint32_t)ij.size());
-    key.insert(key.end(), ij.begin(), ij.end());
+    std::vector<uint32_t> ij = S.key_tail(t, u, key);
     bool current;
-    if (int rc = H.depth.prepare(t, key, force, "flood field allocation failed", &current)) return rc;
+    if (int rc = S.field.prepare(t, key, force, "flood field allocation failed", &current)) return rc;
     if (current) return VF_OK;
     const uint32_t n = t->n, ftx = flood_tiles(t), tiles = ftx * ftx;
-    const size_t words = (size_t)tiles * kFloodTile, nv = (size_t)n * n, nctl = kFloodMaxGroup + 2u;
+    const size_t words = (size_t)tiles * kFloodTile, nv = (size_t)n * n;
     // (k_flood_depth packs the two counts into the halves of one 64-bit word and vf_flood_info reports them as uint32: vf_terrain_create
     //  holds the grid to 8192, n x n to 2^26)
     if (nv >> 32) return fail(VF_ERR_INVALID, "the grid is too large for the flood's 32-bit vertex counts");
     if (H.d_wet.reserve(words, words) != hipSuccess || H.d_fl.reserve(words, words) != hipSuccess || H.d_wd.reserve(nv, nv) != hipSuccess
-        || H.d_ctl.reserve(nctl, nctl) != hipSuccess || H.d_seeds.reserve(ij.size(), ij.size()) != hipSuccess) {
+        || S.reserve(2u, ij.size()) != hipSuccess) {
         (void)hipGetLastError();
         return fail(VF_ERR_NOMEM, "flood mask allocation failed");
     }
     const dim3 rows(ftx, ftx * (kFloodTile / 4u)), threads(256);
     const float *hblk = t->d_hblk;
-    if (H.mode == VF_FLOOD_EVERYWHERE)
+    if (S.mode == VF_FLOOD_EVERYWHERE)
         hipLaunchKernelGGL((k_flood_wet<true>), rows, threads, 0, s, n, t->nb, ftx, ftx * kFloodTile, H.level, hblk, H.d_wet.p, H.d_fl.p, H.d_wd.p);
     else
         hipLaunchKernelGGL((k_flood_wet<false>), rows, threads, 0, s, n, t->nb, ftx, ftx * kFloodTile, H.level, hblk, H.d_wet.p, H.d_fl.p, H.d_wd.p);
     VF_HIP_TRY(hipGetLastError());
     uint32_t passes = 0;
-    if (H.mode != VF_FLOOD_EVERYWHERE) {
-        if (H.mode == VF_FLOOD_SEEDS) {
+    if (S.mode != VF_FLOOD_EVERYWHERE) {
+        if (S.mode == VF_FLOOD_SEEDS) {
             const uint32_t count = (uint32_t)(ij.size() / 2u);
-            H.ij.swap(ij);
-            VF_HIP_TRY(hipMemcpyAsync(H.d_seeds.p, H.ij.data(), H.ij.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
-            hipLaunchKernelGGL((k_flood_seed<false>), dim3((count + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)H.d_seeds.p, count,
+            VF_HIP_TRY(S.upload(ij, s));
+            hipLaunchKernelGGL((k_flood_seed<false>), dim3((count + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)S.d_seeds.p, count,
                                (const uint32_t *)H.d_wet.p, (uint32_t *)H.d_fl.p);
         } else
             hipLaunchKernelGGL((k_flood_seed<true>), dim3((4u * n + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)nullptr, 4u * n,
                                (const uint32_t *)H.d_wet.p, (uint32_t *)H.d_fl.p);
         VF_HIP_TRY(hipGetLastError());
-        const uint32_t G = std::min(H.forced_group ? H.forced_group : kFloodGroup, kFloodMaxGroup);
-        uint32_t changed[kFloodMaxGroup];
-        // (every pass that changes something floods at least one more vertex: nv + 1 launches cannot be reached)
-        for (bool done = false; !done && passes <= nv;) {
-            VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p, 0, G * sizeof(uint32_t), s));
-            for (uint32_t g = 0; g < G; ++g)
-                hipLaunchKernelGGL((k_flood_pass<0>), dim3(tiles), dim3(64), 0, s, ftx, ftx, (const uint64_t *)H.d_wet.p, H.d_fl.p, H.d_ctl.p + g);
-            VF_HIP_TRY(hipGetLastError());
-            VF_HIP_TRY(hipMemcpyAsync(changed, H.d_ctl.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            VF_HIP_TRY(hipStreamSynchronize(s));
-            for (uint32_t g = 0; g < G && !done; ++g) {
-                ++passes;
-                done = changed[g] == 0u;
-            }
-        }
-        if (passes > nv) return fail(VF_ERR_HIP, "flood propagation did not reach a fixpoint within n x n + 1 passes");   // (cannot happen: see above)
+        // (every pass that changes something floods at least one more vertex)
+        if (int rc = S.fixpoint(s, nv, "flood propagation did not reach a fixpoint within n x n + 1 passes", &passes, [&](uint32_t, uint32_t *changed) {
+                hipLaunchKernelGGL((k_flood_pass<0>), dim3(tiles), dim3(64), 0, s, ftx, ftx, (const uint64_t *)H.d_wet.p, H.d_fl.p, changed);
+            })) return rc;
     }
     unsigned long long counts = 0ull;
-    VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p + kFloodMaxGroup, 0, sizeof counts, s));
+    VF_HIP_TRY(hipMemsetAsync(S.counts(), 0, sizeof counts, s));
     hipLaunchKernelGGL((k_flood_depth<0>), dim3(ftx, (n + 3u) / 4u), threads, 0, s, n, ftx, (const uint64_t *)H.d_wet.p, (const uint64_t *)H.d_fl.p,
-                       (const float *)H.d_wd.p, H.depth.d.p, (unsigned long long *)(H.d_ctl.p + kFloodMaxGroup));
+                       (const float *)H.d_wd.p, S.field.d.p, (unsigned long long *)S.counts());
     VF_HIP_TRY(hipGetLastError());
-    VF_HIP_TRY(hipMemcpyAsync(&counts, H.d_ctl.p + kFloodMaxGroup, sizeof counts, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipMemcpyAsync(&counts, S.counts(), sizeof counts, hipMemcpyDeviceToHost, s));
     VF_HIP_TRY(hipStreamSynchronize(s));
-    H.passes = passes; H.flooded = (uint32_t)counts; H.wettable = (uint32_t)(counts >> 32);
-    H.depth.computed(t, key);
+    S.passes = passes; H.flooded = (uint32_t)counts; H.wettable = (uint32_t)(counts >> 32);
+    S.field.computed(t, key);
     return VF_OK;
 }
 
-// Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
 static void flood_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
     const vf_terrain::Flood &H = t->fd;
     FloodTint T = {};
     T.fl = (const uint32_t *)H.d_fl.p; T.wd = H.d_wd.p; T.decode = t->ctx->d_decode;
     T.ntx = flood_tiles(t);
-    T.shallow_rgba = H.shallow_rgba; T.deep_rgba = H.deep_rgba; T.depth_full = H.depth_full;
-    const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_flood_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
-    hipLaunchKernelGGL((k_flood_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    T.shallow_rgba = H.fill.shallow_rgba; T.deep_rgba = H.fill.deep_rgba; T.depth_full = H.fill.depth_full;
+    tint_launch(t, s, P, V, redo, rgba, T, k_flood_tint<false>, k_flood_tint<true>);
 }
 
 // The water of a frame, on the draw stream behind its tile kernels (which stored the visibility) and the relight passes: the field if
 // it is stale, then the tint pass over the covered pixels
 static int flood_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
-    if (int rc = flood_field(t, t->inputs.u, s)) return rc;
-    flood_launch(t, s, P, V, redo, rgba);
-    VF_HIP_TRY(hipGetLastError());
-    return VF_OK;
+    return fill_pass(t, kFieldFlood, flood_launch, s, P, V, redo, rgba);
 }
 
 int vf_terrain_set_flood(vf_terrain *t, int enable, float level, int mode, const float *seeds_xz, uint32_t count, const uint8_t shallow_rgba[4],
@@ -4889,42 +4991,15 @@ int vf_terrain_set_flood(vf_terrain *t, int enable, float level, int mode, const
 {
     if (!t || !shallow_rgba || !deep_rgba) return fail(VF_ERR_INVALID, "NULL argument");
     if (!std::isfinite(level)) return fail(VF_ERR_INVALID, "level must be finite");
-    if (!(std::isfinite(depth_full) && depth_full > 0.0f)) return fail(VF_ERR_INVALID, "depth_full must be a finite number > 0");
-    if (mode != VF_FLOOD_EVERYWHERE && mode != VF_FLOOD_EDGES && mode != VF_FLOOD_SEEDS) return fail(VF_ERR_INVALID, "unknown flood mode");
-    if (mode == VF_FLOOD_SEEDS) {
-        if (!seeds_xz) return fail(VF_ERR_INVALID, "NULL argument: the seeds");
-        if (count < 1u || count > VF_FLOOD_MAX_SEEDS) return fail(VF_ERR_INVALID, "a flood takes 1 to 65535 seeds");
-        for (size_t k = 0; k < (size_t)2u * count; ++k)
-            if (!std::isfinite(seeds_xz[k])) return fail(VF_ERR_INVALID, "the seeds must be finite");
-    } else count = 0u;
-    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "a flood needs a whole-frame handle: sharded handles are not supported");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(wait_frame(t));
-    if (enable) { if (int rc = ensure_vis(t)) return rc; }
+    static const SeededFill::Words W = { 1 << VF_FLOOD_EVERYWHERE | 1 << VF_FLOOD_EDGES | 1 << VF_FLOOD_SEEDS, "unknown flood mode",
+                                         "a flood takes 1 to 65535 seeds", "a flood needs a whole-frame handle: sharded handles are not supported" };
     vf_terrain::Flood &H = t->fd;
-    const uint32_t sh = pack_rgba8(shallow_rgba), dp = pack_rgba8(deep_rgba);
-    std::vector<float> xz;
-    if (count) xz.assign(seeds_xz, seeds_xz + (size_t)2u * count);
-    if (H.enabled != (enable != 0) || !H.have || key_bits(H.level) != key_bits(level) || H.mode != mode || H.xz != xz || H.shallow_rgba != sh
-        || H.deep_rgba != dp || H.depth_full != depth_full)
-        t->inputs_gen++;
-    H.enabled = enable != 0; H.have = true;
-    H.level = level; H.mode = mode;
-    H.xz.swap(xz);
-    H.shallow_rgba = sh; H.deep_rgba = dp; H.depth_full = depth_full;
+    if (int rc = H.fill.set(t, enable, mode, seeds_xz, count, shallow_rgba, deep_rgba, depth_full, key_bits(H.level) != key_bits(level), W)) return rc;
+    H.level = level;
     return VF_OK;
 }
 
-int vf_terrain_clear_flood(vf_terrain *t)
-{
-    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(wait_frame(t));
-    if (t->fd.enabled) t->inputs_gen++;
-    flood_release(t);
-    return VF_OK;
-}
-
+int vf_terrain_clear_flood(vf_terrain *t) { return fill_clear(t, flood_fill, flood_release); }
 int vf_terrain_read_flood_field(vf_terrain *t, float *depth) { return field_out(t, kFieldFlood, depth, nullptr, nullptr); }
 int vf_terrain_flood_field_device(vf_terrain *t, float *dev_depth, void *stream) { return field_out(t, kFieldFlood, nullptr, dev_depth, stream); }
 
@@ -4933,197 +5008,115 @@ int vf_terrain_flood_info(vf_terrain *t, vf_flood_info *out)
     if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
     const vf_terrain::Flood &H = t->fd;
     *out = vf_flood_info();
-    out->enabled = H.enabled ? 1 : 0; out->has_flood = H.have ? 1 : 0;
-    out->mode = H.mode; out->count = (uint32_t)(H.xz.size() / 2u);
-    out->level = H.level; out->depth_full = H.depth_full;
-    for (int k = 0; k < 4; ++k) { out->shallow_rgba[k] = (uint8_t)(H.shallow_rgba >> (8 * k)); out->deep_rgba[k] = (uint8_t)(H.deep_rgba >> (8 * k)); }
-    out->flooded_vertices = H.flooded; out->wettable_vertices = H.wettable; out->passes = H.passes; out->scans = H.depth.scans;
-    out->group = std::min(H.forced_group ? H.forced_group : kFloodGroup, kFloodMaxGroup);
+    H.fill.info(out);
+    out->has_flood = H.fill.have ? 1 : 0; out->level = H.level;
+    out->flooded_vertices = H.flooded; out->wettable_vertices = H.wettable;
     return VF_OK;
 }
 
 int vf_terrain_read_flood_seeds(vf_terrain *t, uint32_t *vertices)
 {
     if (!t || !vertices) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->fd.xz.empty()) return fail(VF_ERR_INVALID, "no seeds set (vf_terrain_set_flood with VF_FLOOD_SEEDS)");
-    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
-    std::vector<uint32_t> ij;
-    flood_vertices(t, t->inputs.u, ij);
-    std::memcpy(vertices, ij.data(), ij.size() * sizeof(uint32_t));
-    return VF_OK;
+    return t->fd.fill.read_seeds(t, vertices, "no seeds set (vf_terrain_set_flood with VF_FLOOD_SEEDS)");
 }
 
 int vf_terrain_debug_flood_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldFlood, count); }
 
 int vf_terrain_debug_flood_stage(vf_terrain *t, uint32_t repeats, float ms[2])
 {
-    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->fd.have || !t->fd.enabled) return fail(VF_ERR_INVALID, "no flood enabled (vf_terrain_set_flood)");
-    if (repeats == 0) repeats = 1;
-    RelightStage G;
-    if (int rc = G.open(t)) return rc;
-    if (int rc = flood_field(t, G.u, G.s)) return rc;          // (the tint's launches below read the masks of the current field)
-    return G.time_pair(repeats, ms, "flood", [&] { return flood_field(t, G.u, G.s, true); },
-                       [&] { flood_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
+    return fill_stage(t, kFieldFlood, flood_fill, "flood", "no flood enabled (vf_terrain_set_flood)", flood_launch, repeats, ms);
 }
 
 int vf_terrain_debug_flood_group(vf_terrain *t, uint32_t group)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    if (group > kFloodMaxGroup) return fail(VF_ERR_INVALID, "a group holds at most 64 passes");
-    if (t->fd.forced_group != group) t->fd.depth.valid = false;   // (the next call computes the field again, with this group size)
-    t->fd.forced_group = group;
-    return VF_OK;
+    return t->fd.fill.force_group(group);
 }
 
 // ---- spill analysis (vf_spill.h) -------------------------------------------------------------
 
-// Passes of k_spill_pass queued per read-back of their `changed` words (DESIGN.md 4t has the measurement)
-constexpr uint32_t kSpillGroup = 16, kSpillMaxGroup = 64;
-
 static uint32_t spill_tiles(const vf_terrain *t) { return (t->n + kSpillTile - 1u) / kSpillTile; }
 
-// the seeds' vertices (i, j) for the spacing of the uniforms `u`, snapped as the flood's are
-static void spill_vertices(const vf_terrain *t, const float *u, std::vector<uint32_t> &ij)
-{
-    const vf_terrain::Spill &H = t->sp;
-    const float spacing = spacing_of(u);
-    ij.resize(H.xz.size());
-    for (size_t k = 0; k < H.xz.size(); ++k) ij[k] = viewshed_index(t, H.xz[k], spacing);
-}
-
-// `spill` holds the field of the handle's heights and sources once this returns (the height cache must be current and ordered before
-// `s`, as for shadow_field); d_sd holds what the tint reads.  The loop to the fixpoint is the flood's: groups of passes, each with its
-// own `changed` word, until the first pass that changed nothing.  force: compute it anyway.
+// The field holds the spill of the handle's heights and sources once this returns (the height cache must be current and ordered before
+// `s`, as for shadow_field); d_sd holds what the tint reads.  force: compute it anyway.
 static int spill_field(vf_terrain *t, const float *u, hipStream_t s, bool force)
 {
     vf_terrain::Spill &H = t->sp;
-    if (!H.have) return fail(VF_ERR_INVALID, "no spill set (vf_terrain_set_spill)");
-    std::vector<uint32_t> ij;
-    if (H.mode == VF_SPILL_SEEDS) spill_vertices(t, u, ij);
+    SeededFill &S = H.fill;
+    if (!S.have) return fail(VF_ERR_INVALID, "no spill set (vf_terrain_set_spill)");
     std::vector<uint32_t> key;
-    key.push_back((uint32_t)H.mode); key.push_back((uint32_t)ij.size());
-    key.insert(key.end(), ij.begin(), ij.end());
+    std::vector<uint32_t> ij = S.key_tail(t, u, key);
     bool current;
-    if (int rc = H.spill.prepare(t, key, force, "spill field allocation failed", &current)) return rc;
+    if (int rc = S.field.prepare(t, key, force, "spill field allocation failed", &current)) return rc;
     if (current) return VF_OK;
     const uint32_t n = t->n, ftx = spill_tiles(t), tiles = ftx * ftx;
-    const size_t words = (size_t)tiles * kSpillTileWords, nv = (size_t)n * n, nctl = kSpillMaxGroup + 3u;
+    const size_t words = (size_t)tiles * kSpillTileWords, nv = (size_t)n * n;
     // (k_spill_out packs the two counts into the halves of one 64-bit word and vf_spill_info reports them as uint32: vf_terrain_create
     //  holds the grid to 8192, n x n to 2^26)
     if (nv >> 32) return fail(VF_ERR_INVALID, "the grid is too large for the spill's 32-bit vertex counts");
     if (H.d_hk.reserve(words, words) != hipSuccess || H.d_w.reserve(words, words) != hipSuccess || H.d_sd.reserve(nv, nv) != hipSuccess
-        || H.d_act.reserve(2u * (size_t)tiles, 2u * (size_t)tiles) != hipSuccess || H.d_ctl.reserve(nctl, nctl) != hipSuccess
-        || H.d_seeds.reserve(ij.size(), ij.size()) != hipSuccess) {
+        || H.d_act.reserve(2u * (size_t)tiles, 2u * (size_t)tiles) != hipSuccess || S.reserve(3u, ij.size()) != hipSuccess) {
         (void)hipGetLastError();
         return fail(VF_ERR_NOMEM, "spill buffer allocation failed");
     }
     const dim3 cols(tiles, kSpillTile / 4u), threads(256);
     const float *hblk = t->d_hblk;
-    uint32_t *const runs = H.d_ctl.p + kSpillMaxGroup + 2u;
-    VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p + kSpillMaxGroup, 0, 3u * sizeof(uint32_t), s));
-    if (H.mode == VF_SPILL_EDGES)
+    uint32_t *const runs = S.counts() + 2u;
+    VF_HIP_TRY(hipMemsetAsync(S.counts(), 0, 3u * sizeof(uint32_t), s));
+    if (S.mode == VF_SPILL_EDGES)
         hipLaunchKernelGGL((k_spill_init<true>), cols, threads, 0, s, n, t->nb, ftx, tiles, hblk, H.d_hk.p, H.d_w.p, H.d_act.p);
     else {
         hipLaunchKernelGGL((k_spill_init<false>), cols, threads, 0, s, n, t->nb, ftx, tiles, hblk, H.d_hk.p, H.d_w.p, H.d_act.p);
         const uint32_t count = (uint32_t)(ij.size() / 2u);
-        H.ij.swap(ij);
-        VF_HIP_TRY(hipMemcpyAsync(H.d_seeds.p, H.ij.data(), H.ij.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));   // (pageable source: returns when the copy is staged)
-        hipLaunchKernelGGL((k_spill_seed<0>), dim3((count + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)H.d_seeds.p, count,
+        VF_HIP_TRY(S.upload(ij, s));
+        hipLaunchKernelGGL((k_spill_seed<0>), dim3((count + 255u) / 256u), threads, 0, s, n, ftx, (const uint32_t *)S.d_seeds.p, count,
                            (const uint32_t *)H.d_hk.p, H.d_w.p);
     }
     VF_HIP_TRY(hipGetLastError());
-    const uint32_t G = std::min(H.forced_group ? H.forced_group : kSpillGroup, kSpillMaxGroup);
-    uint32_t changed[kSpillMaxGroup];
     uint32_t passes = 0;
     // (every pass that changes something lowers at least one vertex to one of the at most n x n keys of h: the relaxation ends; the
     //  bound is the issue's and guards the loop, it is not reached)
-    for (bool done = false; !done && passes <= nv;) {
-        VF_HIP_TRY(hipMemsetAsync(H.d_ctl.p, 0, G * sizeof(uint32_t), s));
-        for (uint32_t g = 0; g < G; ++g) {
-            const uint32_t pass = passes + g + 1u;                 // (pass p reads array p & 1 and sets words of the other one)
+    if (int rc = S.fixpoint(s, nv, "spill relaxation did not reach a fixpoint within n x n + 1 passes", &passes, [&](uint32_t pass, uint32_t *changed) {
+            // (pass p reads array p & 1 and sets words of the other one)
             hipLaunchKernelGGL((k_spill_pass<0>), dim3(tiles), dim3(64), 0, s, ftx, ftx, H.no_flags ? 1u : 0u, (const uint32_t *)H.d_hk.p, H.d_w.p,
-                               H.d_act.p + (size_t)(pass & 1u) * tiles, H.d_act.p + (size_t)((pass + 1u) & 1u) * tiles, H.d_ctl.p + g, runs);
-        }
-        VF_HIP_TRY(hipGetLastError());
-        VF_HIP_TRY(hipMemcpyAsync(changed, H.d_ctl.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        VF_HIP_TRY(hipStreamSynchronize(s));
-        uint32_t g = 0;
-        for (; g < G && !done; ++g) done = changed[g] == 0u;
-        passes += g;
-    }
-    if (passes > nv) return fail(VF_ERR_HIP, "spill relaxation did not reach a fixpoint within n x n + 1 passes");
+                               H.d_act.p + (size_t)(pass & 1u) * tiles, H.d_act.p + (size_t)((pass + 1u) & 1u) * tiles, changed, runs);
+        })) return rc;
     uint32_t tail[3] = {};
-    hipLaunchKernelGGL((k_spill_out<0>), dim3(ftx, (n + 3u) / 4u), threads, 0, s, n, t->nb, ftx, hblk, (const uint32_t *)H.d_w.p, H.spill.d.p, H.d_sd.p,
-                       (unsigned long long *)(H.d_ctl.p + kSpillMaxGroup));
+    hipLaunchKernelGGL((k_spill_out<0>), dim3(ftx, (n + 3u) / 4u), threads, 0, s, n, t->nb, ftx, hblk, (const uint32_t *)H.d_w.p, S.field.d.p, H.d_sd.p,
+                       (unsigned long long *)S.counts());
     VF_HIP_TRY(hipGetLastError());
-    VF_HIP_TRY(hipMemcpyAsync(tail, H.d_ctl.p + kSpillMaxGroup, sizeof tail, hipMemcpyDeviceToHost, s));
+    VF_HIP_TRY(hipMemcpyAsync(tail, S.counts(), sizeof tail, hipMemcpyDeviceToHost, s));
     VF_HIP_TRY(hipStreamSynchronize(s));
-    H.passes = passes; H.reached = tail[0]; H.sinks = tail[1]; H.tile_runs = tail[2];
-    H.spill.computed(t, key);
+    S.passes = passes; H.reached = tail[0]; H.sinks = tail[1]; H.tile_runs = tail[2];
+    S.field.computed(t, key);
     return VF_OK;
 }
 
-// Both instantiations of the tint kernel, in k_resolve's launch shape (gb_grid)
 static void spill_launch(const vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
     const vf_terrain::Spill &H = t->sp;
     SpillTint T = {};
     T.sd = H.d_sd.p; T.decode = t->ctx->d_decode;
-    T.shallow_rgba = H.shallow_rgba; T.deep_rgba = H.deep_rgba; T.depth_full = H.depth_full;
-    const dim3 grid = gb_grid(t), threads(256);
-    hipLaunchKernelGGL((k_spill_tint<false>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
-    hipLaunchKernelGGL((k_spill_tint<true>), grid, threads, 0, s, P, V, (const float *)t->ctx->d_thresh, (const uint32_t *)t->d_vis, T, redo, rgba);
+    T.shallow_rgba = H.fill.shallow_rgba; T.deep_rgba = H.fill.deep_rgba; T.depth_full = H.fill.depth_full;
+    tint_launch(t, s, P, V, redo, rgba, T, k_spill_tint<false>, k_spill_tint<true>);
 }
 
 // The sinks of a frame, on the draw stream behind the flood's water: the field if it is stale, then the tint pass over the covered pixels
 static int spill_pass(vf_terrain *t, hipStream_t s, const FrameParams &P, const SetupView &V, const uint32_t *redo, uint32_t *rgba)
 {
-    if (int rc = spill_field(t, t->inputs.u, s)) return rc;
-    spill_launch(t, s, P, V, redo, rgba);
-    VF_HIP_TRY(hipGetLastError());
-    return VF_OK;
+    return fill_pass(t, kFieldSpill, spill_launch, s, P, V, redo, rgba);
 }
 
 int vf_terrain_set_spill(vf_terrain *t, int enable, int mode, const float *seeds_xz, uint32_t count, const uint8_t shallow_rgba[4],
                          const uint8_t deep_rgba[4], float depth_full)
 {
     if (!t || !shallow_rgba || !deep_rgba) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!(std::isfinite(depth_full) && depth_full > 0.0f)) return fail(VF_ERR_INVALID, "depth_full must be a finite number > 0");
-    if (mode != VF_SPILL_EDGES && mode != VF_SPILL_SEEDS) return fail(VF_ERR_INVALID, "unknown spill mode");
-    if (mode == VF_SPILL_SEEDS) {
-        if (!seeds_xz) return fail(VF_ERR_INVALID, "NULL argument: the seeds");
-        if (count < 1u || count > VF_SPILL_MAX_SEEDS) return fail(VF_ERR_INVALID, "the spill takes 1 to 65535 seeds");
-        for (size_t k = 0; k < (size_t)2u * count; ++k)
-            if (!std::isfinite(seeds_xz[k])) return fail(VF_ERR_INVALID, "the seeds must be finite");
-    } else count = 0u;
-    if (enable && (t->shard_tiles || t->nranks != 1)) return fail(VF_ERR_INVALID, "the spill needs a whole-frame handle: sharded handles are not supported");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(wait_frame(t));
-    if (enable) { if (int rc = ensure_vis(t)) return rc; }
-    vf_terrain::Spill &H = t->sp;
-    const uint32_t sh = pack_rgba8(shallow_rgba), dp = pack_rgba8(deep_rgba);
-    std::vector<float> xz;
-    if (count) xz.assign(seeds_xz, seeds_xz + (size_t)2u * count);
-    if (H.enabled != (enable != 0) || !H.have || H.mode != mode || H.xz != xz || H.shallow_rgba != sh || H.deep_rgba != dp || H.depth_full != depth_full)
-        t->inputs_gen++;
-    H.enabled = enable != 0; H.have = true;
-    H.mode = mode;
-    H.xz.swap(xz);
-    H.shallow_rgba = sh; H.deep_rgba = dp; H.depth_full = depth_full;
-    return VF_OK;
+    static const SeededFill::Words W = { 1 << VF_SPILL_EDGES | 1 << VF_SPILL_SEEDS, "unknown spill mode", "the spill takes 1 to 65535 seeds",
+                                         "the spill needs a whole-frame handle: sharded handles are not supported" };
+    return t->sp.fill.set(t, enable, mode, seeds_xz, count, shallow_rgba, deep_rgba, depth_full, false, W);
 }
 
-int vf_terrain_clear_spill(vf_terrain *t)
-{
-    if (!t) return fail(VF_ERR_INVALID, "NULL argument");
-    VF_HIP_TRY(hipSetDevice(t->ctx->device));
-    VF_HIP_TRY(wait_frame(t));
-    if (t->sp.enabled) t->inputs_gen++;
-    spill_release(t);
-    return VF_OK;
-}
-
+int vf_terrain_clear_spill(vf_terrain *t) { return fill_clear(t, spill_fill, spill_release); }
 int vf_terrain_read_spill_field(vf_terrain *t, float *spill) { return field_out(t, kFieldSpill, spill, nullptr, nullptr); }
 int vf_terrain_spill_field_device(vf_terrain *t, float *dev_spill, void *stream) { return field_out(t, kFieldSpill, nullptr, dev_spill, stream); }
 
@@ -5145,49 +5138,32 @@ int vf_terrain_spill_info(vf_terrain *t, vf_spill_info *out)
     if (!t || !out) return fail(VF_ERR_INVALID, "NULL argument");
     const vf_terrain::Spill &H = t->sp;
     *out = vf_spill_info();
-    out->enabled = H.enabled ? 1 : 0; out->has_spill = H.have ? 1 : 0;
-    out->mode = H.mode; out->count = (uint32_t)(H.xz.size() / 2u);
-    out->depth_full = H.depth_full;
-    for (int k = 0; k < 4; ++k) { out->shallow_rgba[k] = (uint8_t)(H.shallow_rgba >> (8 * k)); out->deep_rgba[k] = (uint8_t)(H.deep_rgba >> (8 * k)); }
-    out->reached_vertices = H.reached; out->sink_vertices = H.sinks; out->passes = H.passes; out->scans = H.spill.scans;
-    out->group = std::min(H.forced_group ? H.forced_group : kSpillGroup, kSpillMaxGroup);
-    out->tile_runs = H.tile_runs;
+    H.fill.info(out);
+    out->has_spill = H.fill.have ? 1 : 0;
+    out->reached_vertices = H.reached; out->sink_vertices = H.sinks; out->tile_runs = H.tile_runs;
     return VF_OK;
 }
 
 int vf_terrain_read_spill_seeds(vf_terrain *t, uint32_t *vertices)
 {
     if (!t || !vertices) return fail(VF_ERR_INVALID, "NULL argument");
-    if (t->sp.xz.empty()) return fail(VF_ERR_INVALID, "no seeds set (vf_terrain_set_spill with VF_SPILL_SEEDS)");
-    if (!t->have_uniforms) return fail(VF_ERR_INVALID, "uniforms not set");
-    std::vector<uint32_t> ij;
-    spill_vertices(t, t->inputs.u, ij);
-    std::memcpy(vertices, ij.data(), ij.size() * sizeof(uint32_t));
-    return VF_OK;
+    return t->sp.fill.read_seeds(t, vertices, "no seeds set (vf_terrain_set_spill with VF_SPILL_SEEDS)");
 }
 
 int vf_terrain_debug_spill_scans(vf_terrain *t, uint32_t *count) { return field_scans(t, kFieldSpill, count); }
 
 int vf_terrain_debug_spill_stage(vf_terrain *t, uint32_t repeats, float ms[2])
 {
-    if (!t || !ms) return fail(VF_ERR_INVALID, "NULL argument");
-    if (!t->sp.have || !t->sp.enabled) return fail(VF_ERR_INVALID, "no spill enabled (vf_terrain_set_spill)");
-    if (repeats == 0) repeats = 1;
-    RelightStage G;
-    if (int rc = G.open(t)) return rc;
-    if (int rc = spill_field(t, G.u, G.s)) return rc;          // (the tint's launches below read d_sd of the current field)
-    return G.time_pair(repeats, ms, "spill", [&] { return spill_field(t, G.u, G.s, true); },
-                       [&] { spill_launch(t, G.s, G.F.P, G.F.V, G.redo, t->d_rgba_scratch); });
+    return fill_stage(t, kFieldSpill, spill_fill, "spill", "no spill enabled (vf_terrain_set_spill)", spill_launch, repeats, ms);
 }
 
 int vf_terrain_debug_spill_group(vf_terrain *t, uint32_t group)
 {
     if (!t) return fail(VF_ERR_INVALID, "NULL argument");
     const bool no_flags = (group & VF_SPILL_GROUP_NO_FLAGS) != 0u;
-    group &= ~VF_SPILL_GROUP_NO_FLAGS;
-    if (group > kSpillMaxGroup) return fail(VF_ERR_INVALID, "a group holds at most 64 passes");
-    if (t->sp.forced_group != group || t->sp.no_flags != no_flags) t->sp.spill.valid = false;   // (the next call computes the field again)
-    t->sp.forced_group = group; t->sp.no_flags = no_flags;
+    if (int rc = t->sp.fill.force_group(group & ~VF_SPILL_GROUP_NO_FLAGS)) return rc;
+    if (t->sp.no_flags != no_flags) t->sp.fill.field.valid = false;             // (the next call computes the field again)
+    t->sp.no_flags = no_flags;
     return VF_OK;
 }
 

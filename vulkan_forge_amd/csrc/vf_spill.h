@@ -11,10 +11,11 @@
 //   k_spill_seed         w = hk at a passable seed (the feature's one atomic on the field: a 32-bit atomicMin on the key)
 //   k_spill_pass         one wave per tile: the facing column and row of the four neighbours enter, then the tile runs to its own
 //                        fixpoint -- a sweep along the registers in both directions and one step across the lanes by shuffles, until no
-//                        lane changes.  The host repeats the launch until one changes nothing (spill_field, vf_hip.hip).  Activity
+//                        lane changes.  The host repeats the launch until one changes nothing (SeededFill::fixpoint, vf_hip.hip).  Activity
 //                        flags, one word per tile and pass parity: a tile whose neighbours stored nothing in the last pass leaves at once
 //   k_spill_out          spill (decoded) and sd = spill - h per vertex, row-major, and the two counts
-//   k_spill_tint         blends a shallow and a deep colour over the covered pixels of a frame from its stored visibility, flat
+//   k_spill_tint         blends a shallow and a deep colour over the covered pixels of a frame from its stored visibility, flat: the
+//                        flood's tint with another pixel rule (tint_visible and vs_depth_tint, vf_viewshed.h)
 //
 // Launched only for a handle that asked for the spill: the frame path is not touched.  Every device loop has a fixed trip bound, no
 // workgroup waits for another, there is no LDS in the field kernels, and values of `w` only ever fall: a wave that reads a neighbour's
@@ -181,8 +182,7 @@ struct SpillTint {
     float depth_full;
 };
 
-// Pixel (px, py) with visibility id `id` and colour `rgba`: false when the pass leaves it as the frame drew it.  The blend tail is
-// flood_pixel's, restated: the flood's kernels keep their instructions.
+// Pixel (px, py) with visibility id `id` and colour `rgba`: false when the pass leaves it as the frame drew it
 template <bool CLIPPED>
 __device__ __forceinline__ bool spill_pixel(const FrameParams &P, const SetupView &V, const SpillTint &T, const float *dec, const float *thr,
                                             uint32_t id, int32_t px, int32_t py, uint32_t &rgba)
@@ -195,32 +195,16 @@ __device__ __forceinline__ bool spill_pixel(const FrameParams &P, const SetupVie
     const VisiblePoint<CLIPPED> p = visible_point<CLIPPED>(P, V, s, prim, px, py);
     const float d = point_scalar(P, p, px, py, w0, w1, w2);
     if (!(d > 0.0f)) return false;
-    const float sc = fminf(d / T.depth_full, 1.0f);
-    float c[3] = { dec[rgba & 255u], dec[(rgba >> 8) & 255u], dec[(rgba >> 16) & 255u] };
-    const bool sh = vs_blend(c, dec, T.shallow_rgba, 1.0f - sc);
-    const bool dp = vs_blend(c, dec, T.deep_rgba, sc);
-    if (!sh && !dp) return false;
-    rgba = srgb_encode(c[0], thr) | (srgb_encode(c[1], thr) << 8) | (srgb_encode(c[2], thr) << 16) | 0xFF000000u;
-    return true;
+    return vs_depth_tint(dec, thr, d, T.depth_full, T.shallow_rgba, T.deep_rgba, rgba);
 }
 
-// The frame's visibility (H, W) -> the covered pixels of its colour buffer over a sink, in the walk of for_each_visible (vf_visible.h).
-// `redo` as for k_flood_tint: both instantiations are launched behind a frame and the one the frame does not call for leaves at once.
+// The covered pixels of a frame's colour buffer over a sink (tint_visible, vf_viewshed.h)
 template <bool CLIPPED>
 __global__ __launch_bounds__(256) void k_spill_tint(FrameParams P, SetupView V, const float *__restrict__ thresh, const uint32_t *__restrict__ vis,
                                                     SpillTint T, const uint32_t *__restrict__ redo, uint32_t *__restrict__ rgba)
 {
-    if ((*redo != 0u) != CLIPPED) return;
-    __shared__ float s_thr[256];
-    __shared__ float s_dec[256];
-    s_thr[threadIdx.x] = thresh[threadIdx.x];
-    s_dec[threadIdx.x] = T.decode[threadIdx.x];
-    __syncthreads();
-    for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
-        if (id == 0u) return;
-        const size_t o = (size_t)py * P.W + px;
-        uint32_t c = rgba[o];
-        if (spill_pixel<CLIPPED>(P, V, T, s_dec, s_thr, id, (int32_t)px, (int32_t)py, c)) rgba[o] = c;
+    tint_visible<CLIPPED>(P, thresh, T.decode, vis, redo, rgba, [&](const float *dec, const float *thr, uint32_t id, int32_t px, int32_t py, uint32_t &c) {
+        return spill_pixel<CLIPPED>(P, V, T, dec, thr, id, px, py, c);
     });
 }
 

@@ -282,6 +282,19 @@ __device__ __forceinline__ bool vs_blend(float c[3], const float *dec, uint32_t 
     return true;
 }
 
+// The end of a depth tint (the flood's water, vf_flood.h; the spill's sinks, vf_spill.h): `shallow` and `deep` over the colour `rgba`,
+// the deep one by min(d / depth_full, 1) and the shallow one by the rest; false: neither has an opacity, `rgba` is left
+__device__ __forceinline__ bool vs_depth_tint(const float *dec, const float *thr, float d, float depth_full, uint32_t shallow, uint32_t deep, uint32_t &rgba)
+{
+    const float sd = fminf(d / depth_full, 1.0f);
+    float c[3] = { dec[rgba & 255u], dec[(rgba >> 8) & 255u], dec[(rgba >> 16) & 255u] };
+    const bool sh = vs_blend(c, dec, shallow, 1.0f - sd);
+    const bool dp = vs_blend(c, dec, deep, sd);
+    if (!sh && !dp) return false;
+    rgba = srgb_encode(c[0], thr) | (srgb_encode(c[1], thr) << 8) | (srgb_encode(c[2], thr) << 16) | 0xFF000000u;
+    return true;
+}
+
 // Pixel (px, py) with visibility id `id` and colour `rgba`: false when the pass leaves it as the frame drew it
 template <bool CLIPPED>
 __device__ __forceinline__ bool viewshed_pixel(const FrameParams &P, const SetupView &V, const ViewshedTint &T, const float *dec, const float *thr,
@@ -311,23 +324,34 @@ __device__ __forceinline__ bool viewshed_pixel(const FrameParams &P, const Setup
     return true;
 }
 
-// The frame's visibility (H, W) -> the covered pixels of its colour buffer, tinted, in the walk of for_each_visible (vf_visible.h).
-// `redo` as for k_relight: both instantiations are launched behind a frame and the one the frame does not call for leaves at once.
-template <bool CLIPPED>
-__global__ __launch_bounds__(256) void k_viewshed_tint(FrameParams P, SetupView V, const float *__restrict__ thresh, const uint32_t *__restrict__ vis,
-                                                       ViewshedTint T, const uint32_t *__restrict__ redo, uint32_t *__restrict__ rgba)
+// The body of a tint kernel of 256 threads (this one's, k_flood_tint, k_spill_tint): the frame's visibility (H, W) -> the covered
+// pixels of its colour buffer, each as pixel(dec, thr, id, px, py, colour) leaves it (false: as the frame drew it), in the walk of
+// for_each_visible (vf_visible.h), with the two sRGB tables in LDS.  `redo` as for k_relight: both instantiations are launched
+// behind a frame and the one the frame does not call for leaves at once.
+template <bool CLIPPED, typename Pixel>
+__device__ __forceinline__ void tint_visible(const FrameParams &P, const float *__restrict__ thresh, const float *__restrict__ decode,
+                                             const uint32_t *__restrict__ vis, const uint32_t *__restrict__ redo, uint32_t *__restrict__ rgba, Pixel &&pixel)
 {
     if ((*redo != 0u) != CLIPPED) return;
     __shared__ float s_thr[256];
     __shared__ float s_dec[256];
     s_thr[threadIdx.x] = thresh[threadIdx.x];
-    s_dec[threadIdx.x] = T.decode[threadIdx.x];
+    s_dec[threadIdx.x] = decode[threadIdx.x];
     __syncthreads();
     for_each_visible(P, vis, [&](uint32_t id, uint32_t px, uint32_t py) {
         if (id == 0u) return;
         const size_t o = (size_t)py * P.W + px;
         uint32_t c = rgba[o];
-        if (viewshed_pixel<CLIPPED>(P, V, T, s_dec, s_thr, id, (int32_t)px, (int32_t)py, c)) rgba[o] = c;
+        if (pixel(s_dec, s_thr, id, (int32_t)px, (int32_t)py, c)) rgba[o] = c;
+    });
+}
+
+template <bool CLIPPED>
+__global__ __launch_bounds__(256) void k_viewshed_tint(FrameParams P, SetupView V, const float *__restrict__ thresh, const uint32_t *__restrict__ vis,
+                                                       ViewshedTint T, const uint32_t *__restrict__ redo, uint32_t *__restrict__ rgba)
+{
+    tint_visible<CLIPPED>(P, thresh, T.decode, vis, redo, rgba, [&](const float *dec, const float *thr, uint32_t id, int32_t px, int32_t py, uint32_t &c) {
+        return viewshed_pixel<CLIPPED>(P, V, T, dec, thr, id, px, py, c);
     });
 }
 

@@ -975,22 +975,38 @@ public:
         if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
         return a;
     }
+    // what flood_args / spill_args return about the sources, as the C calls take it: a[i] the seeds ((N, 2) float32 or None), a[i + 1]
+    // and a[i + 2] the shallow and the deep colour
+    struct FillArgs {
+        py::array_t<float, py::array::c_style | py::array::forcecast> arr;     // (holds what xz points to)
+        const float *xz = nullptr;
+        uint32_t count = 0;
+        uint8_t sh[4], dp[4];
+        FillArgs(const py::tuple &a, size_t i)
+        {
+            if (!a[i].is_none()) {
+                arr = a[i].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
+                xz = arr.data(); count = (uint32_t)arr.shape(0);
+            }
+            py::tuple ts = a[i + 1].cast<py::tuple>(), td = a[i + 2].cast<py::tuple>();
+            for (int k = 0; k < 4; ++k) { sh[k] = ts[k].cast<uint8_t>(); dp[k] = td[k].cast<uint8_t>(); }
+        }
+    };
+    // the vertices of `count` seeds as (count, 2) uint32, or None: no seeds, or no uniforms set yet (`read` refuses)
+    py::object seed_vertices(uint32_t count, int (*read)(vf_terrain *, uint32_t *))
+    {
+        if (!count) return py::none();
+        py::array_t<uint32_t> a({ (py::ssize_t)count, (py::ssize_t)2 });
+        if (read(t, a.mutable_data()) != VF_OK) return py::none();
+        return a;
+    }
     // extension: flood analysis (argument rules: vulkan_forge_amd/_flood.py)
     void set_flood(py::object level, py::object seeds, py::object enabled, py::object shallow_rgba, py::object deep_rgba, py::object depth_full)
     {
         py::tuple a = py::module_::import("vulkan_forge_amd._flood").attr("flood_args")(level, seeds, enabled, shallow_rgba, deep_rgba, depth_full);
-        uint8_t sh[4], dp[4];
-        py::tuple ts = a[4].cast<py::tuple>(), td = a[5].cast<py::tuple>();
-        for (int k = 0; k < 4; ++k) { sh[k] = ts[k].cast<uint8_t>(); dp[k] = td[k].cast<uint8_t>(); }
-        const float *xz = nullptr;
-        uint32_t count = 0;
-        py::array_t<float, py::array::c_style | py::array::forcecast> arr;
-        if (!a[3].is_none()) {
-            arr = a[3].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-            xz = arr.data(); count = (uint32_t)arr.shape(0);
-        }
+        const FillArgs f(a, 3);
         Borrow b(busy);
-        check(vf_terrain_set_flood(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<int>(), xz, count, sh, dp, a[6].cast<float>()));
+        check(vf_terrain_set_flood(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<int>(), f.xz, f.count, f.sh, f.dp, a[6].cast<float>()));
         frame_current = false;
     }
     void clear_flood()
@@ -1014,13 +1030,8 @@ public:
         Borrow b(busy);
         vf_flood_info v;
         check(vf_terrain_flood_info(t, &v));
-        py::object vertices = py::none();
-        if (v.count) {
-            py::array_t<uint32_t> a({ (py::ssize_t)v.count, (py::ssize_t)2 });
-            if (vf_terrain_read_flood_seeds(t, a.mutable_data()) == VF_OK) vertices = a;   // (else: uniforms not set yet)
-        }
         return py::module_::import("vulkan_forge_amd._flood").attr("flood_info")(
-            v.enabled, v.has_flood, v.mode, v.count, vertices, v.level, v.depth_full,
+            v.enabled, v.has_flood, v.mode, v.count, seed_vertices(v.count, vf_terrain_read_flood_seeds), v.level, v.depth_full,
             py::make_tuple(v.shallow_rgba[0], v.shallow_rgba[1], v.shallow_rgba[2], v.shallow_rgba[3]),
             py::make_tuple(v.deep_rgba[0], v.deep_rgba[1], v.deep_rgba[2], v.deep_rgba[3]),
             v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group);
@@ -1041,18 +1052,9 @@ public:
     void set_spill(py::object seeds, py::object enabled, py::object shallow_rgba, py::object deep_rgba, py::object depth_full)
     {
         py::tuple a = py::module_::import("vulkan_forge_amd._spill").attr("spill_args")(seeds, enabled, shallow_rgba, deep_rgba, depth_full);
-        uint8_t sh[4], dp[4];
-        py::tuple ts = a[3].cast<py::tuple>(), td = a[4].cast<py::tuple>();
-        for (int k = 0; k < 4; ++k) { sh[k] = ts[k].cast<uint8_t>(); dp[k] = td[k].cast<uint8_t>(); }
-        const float *xz = nullptr;
-        uint32_t count = 0;
-        py::array_t<float, py::array::c_style | py::array::forcecast> arr;
-        if (!a[2].is_none()) {
-            arr = a[2].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
-            xz = arr.data(); count = (uint32_t)arr.shape(0);
-        }
+        const FillArgs f(a, 2);
         Borrow b(busy);
-        check(vf_terrain_set_spill(t, a[0].cast<int>(), a[1].cast<int>(), xz, count, sh, dp, a[5].cast<float>()));
+        check(vf_terrain_set_spill(t, a[0].cast<int>(), a[1].cast<int>(), f.xz, f.count, f.sh, f.dp, a[5].cast<float>()));
         frame_current = false;
     }
     void clear_spill()
@@ -1086,13 +1088,8 @@ public:
         Borrow b(busy);
         vf_spill_info v;
         check(vf_terrain_spill_info(t, &v));
-        py::object vertices = py::none();
-        if (v.count) {
-            py::array_t<uint32_t> a({ (py::ssize_t)v.count, (py::ssize_t)2 });
-            if (vf_terrain_read_spill_seeds(t, a.mutable_data()) == VF_OK) vertices = a;   // (else: uniforms not set yet)
-        }
         return py::module_::import("vulkan_forge_amd._spill").attr("spill_info")(
-            v.enabled, v.has_spill, v.mode, v.count, vertices, v.depth_full,
+            v.enabled, v.has_spill, v.mode, v.count, seed_vertices(v.count, vf_terrain_read_spill_seeds), v.depth_full,
             py::make_tuple(v.shallow_rgba[0], v.shallow_rgba[1], v.shallow_rgba[2], v.shallow_rgba[3]),
             py::make_tuple(v.deep_rgba[0], v.deep_rgba[1], v.deep_rgba[2], v.deep_rgba[3]),
             v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs);
