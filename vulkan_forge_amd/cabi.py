@@ -21,48 +21,6 @@ VF_PLAN_FIRST, VF_PLAN_FRESH, VF_PLAN_MOTION_MAP, VF_PLAN_DILATE, VF_PLAN_QUEUED
 VF_PLAN_TILE_LISTS = 64        # ... and for "the tile kernel read the plan state's per-tile candidate lists" (DESIGN.md 3): Terrain.tile_lists()
 VF_PLAN_GEOMETRY_REUSED = 32   # ... its bit for "the block boxes and set-up records were not rebuilt" (DESIGN.md 3): Terrain.geometry_reused()
 
-# every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py)
-SYMBOLS = [
-    "vf_last_error", "vf_device_count", "vf_device_query", "vf_ctx_create", "vf_ctx_destroy", "vf_ctx_device_info", "vf_ctx_stream",
-    "vf_terrain_create", "vf_terrain_destroy", "vf_terrain_set_uniforms", "vf_terrain_set_height",
-    "vf_terrain_set_height_device", "vf_terrain_set_shade_mode", "vf_terrain_set_shade_precision", "vf_terrain_set_raster_groups", "vf_terrain_raster_groups", "vf_terrain_set_shard", "vf_terrain_local_rows", "vf_terrain_set_tile_shard",
-    "vf_terrain_local_tiles", "vf_terrain_read_tiles", "vf_tile_layout", "vf_terrain_tile_times", "vf_balance_stripes", "vf_tile_layout_register_map", "vf_terrain_set_output_device",
-    "vf_terrain_rgba_device", "vf_terrain_render", "vf_terrain_render_batch", "vf_terrain_render_batch_host", "vf_terrain_sync",
-    "vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_add_polygons", "vf_terrain_set_layer_occlusion", "vf_terrain_set_layer_haze", "vf_terrain_layer_haze", "vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count", "vf_terrain_clear_overlays", "vf_terrain_read_rgba", "vf_terrain_read_png_scanlines", "vf_terrain_read_visibility",
-    "vf_terrain_enable_timing", "vf_terrain_timings", "vf_terrain_frame_times", "vf_terrain_debug_item_stats", "vf_terrain_debug_band_masks", "vf_terrain_debug_set_plan_feedback", "vf_terrain_debug_plan_mode", "vf_terrain_debug_tile_lists", "vf_terrain_debug_set_tile_list_capacity", "vf_terrain_debug_phase_cycles", "vf_grid_generate", "vf_grid_generate_device", "vf_triangle_render",
-    "vf_stitch_bands_device", "vf_stitch_tiles_device",
-    "vf_dist_available", "vf_dist_version", "vf_dist_unique_id", "vf_dist_comm_init", "vf_dist_comm_destroy", "vf_dist_gather_tiles", "vf_dist_gather_bands", "vf_dist_exchange_bands",
-    "vf_terrain_debug_fragment_stage", "vf_host_alloc", "vf_host_free",
-    "vf_terrain_gbuffer_device", "vf_terrain_read_gbuffer", "vf_terrain_pick", "vf_terrain_debug_gbuffer_stage",
-    "vf_terrain_set_shadows", "vf_terrain_read_shadow_field", "vf_terrain_shadow_field_device", "vf_terrain_debug_shadow_stage",
-    "vf_terrain_debug_shadow_scans",
-    "vf_terrain_set_ambient", "vf_terrain_read_sky_view_field", "vf_terrain_sky_view_field_device", "vf_terrain_debug_ambient_stage",
-    "vf_terrain_debug_ambient_scans",
-    "vf_terrain_set_drape", "vf_terrain_set_drape_device", "vf_terrain_clear_drape", "vf_terrain_drape_info", "vf_terrain_debug_drape_stage",
-    "vf_terrain_set_drape_mips", "vf_terrain_drape_mip_info", "vf_terrain_read_drape_level", "vf_terrain_debug_drape_mip_build",
-    "vf_terrain_set_drape_anisotropy", "vf_terrain_drape_anisotropy",
-    "vf_terrain_set_viewshed", "vf_terrain_read_viewshed_field", "vf_terrain_viewshed_field_device", "vf_terrain_viewshed_info",
-    "vf_terrain_debug_viewshed_stage", "vf_terrain_debug_viewshed_scans",
-    "vf_terrain_set_cumulative_viewshed", "vf_terrain_read_cumulative_viewshed_field", "vf_terrain_cumulative_viewshed_field_device",
-    "vf_terrain_cumulative_viewshed_info", "vf_terrain_read_cumulative_viewshed_vertices", "vf_terrain_debug_cumulative_viewshed_batch",
-    "vf_terrain_debug_cumulative_viewshed_scans", "vf_terrain_debug_cumulative_viewshed_stage",
-    "vf_terrain_set_sun_exposure", "vf_terrain_clear_sun_exposure", "vf_terrain_read_sun_exposure_field", "vf_terrain_sun_exposure_field_device",
-    "vf_terrain_sun_exposure_info", "vf_terrain_debug_sun_exposure_batch", "vf_terrain_debug_sun_exposure_scans",
-    "vf_terrain_debug_sun_exposure_stage",
-    "vf_terrain_create_supersampled", "vf_terrain_supersampling", "vf_terrain_read_samples", "vf_terrain_samples_device",
-    "vf_terrain_debug_resolve_stage",
-    "vf_terrain_set_haze", "vf_terrain_clear_haze", "vf_terrain_haze_info", "vf_terrain_read_haze_opacity", "vf_terrain_haze_opacity_device",
-    "vf_terrain_debug_haze_stage",
-    "vf_terrain_set_flood", "vf_terrain_clear_flood", "vf_terrain_read_flood_field", "vf_terrain_flood_field_device", "vf_terrain_flood_info",
-    "vf_terrain_read_flood_seeds", "vf_terrain_debug_flood_scans", "vf_terrain_debug_flood_group", "vf_terrain_debug_flood_stage",
-    "vf_terrain_set_spill", "vf_terrain_clear_spill", "vf_terrain_read_spill_field", "vf_terrain_spill_field_device", "vf_terrain_read_sink_depth",
-    "vf_terrain_spill_info", "vf_terrain_read_spill_seeds", "vf_terrain_debug_spill_scans", "vf_terrain_debug_spill_group",
-    "vf_terrain_debug_spill_stage",
-    "vf_dem_create", "vf_dem_destroy", "vf_dem_set_heights_f32", "vf_dem_set_heights_f64", "vf_dem_stats",
-    "vf_dem_percentile_range", "vf_dem_normalize", "vf_dem_upload_height", "vf_dem_texture_size", "vf_dem_read_patch",
-]
-
-
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 256), ("arch", C.c_char * 64), ("device_ordinal", C.c_int32), ("compute_units", C.c_int32),
                 ("wavefront_size", C.c_int32), ("clock_khz", C.c_int32), ("total_mem_bytes", C.c_uint64),
@@ -272,6 +230,8 @@ _PROTOS = {
     "vf_dem_texture_size": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "vf_dem_read_patch": (_i, [_vp, _u32, _u32, _u32, _u32, _vp]),
 }
+# every symbol include/vf_hip.h declares (checked by tests/test_cabi_symbols.py): the prototypes above are the one list
+SYMBOLS = list(_PROTOS)
 
 
 def load(path: str = DEFAULT_LIB) -> C.CDLL:
@@ -285,6 +245,11 @@ def load(path: str = DEFAULT_LIB) -> C.CDLL:
 
 class VfError(RuntimeError):
     pass
+
+
+def _rgba(c):
+    """a colour, four numbers in 0 .. 255 -> the uint8[4] a C call takes (pass it as it is, or C.cast it to a void pointer)"""
+    return (C.c_uint8 * 4)(*map(int, c))
 
 
 def tile_layout(width, height, rank, nranks, skew=3, lib=None):
@@ -350,6 +315,37 @@ class Terrain:
         if rc != VF_OK:
             msg = self.lib.vf_last_error().decode()
             raise VfError("No suitable GPU adapter" if rc == VF_ERR_NO_DEVICE else msg)
+
+    # ---- the call shapes the methods below share.  Every failure goes through _check: VfError with vf_last_error(). ----
+    def _grid_field(self, read):
+        """A per-vertex field through its vf_terrain_read_* call: (grid, grid) float32 (the library holds at least 2 x 2 vertices)."""
+        n = max(self.grid, 2)
+        out = np.empty((n, n), np.float32)
+        self._check(read(self.t, out.ctypes.data))
+        return out
+
+    def _to_device(self, fn, dev, stream):
+        """A vf_terrain_*_device call: into the device address `dev`, asynchronous on `stream` (None: the context's)."""
+        self._check(fn(self.t, dev, stream))
+
+    def _count(self, fn):
+        """One uint32 the handle keeps on the host: a scan counter, a count, a setting."""
+        n = _u32()
+        self._check(fn(self.t, C.byref(n)))
+        return n.value
+
+    def _stage(self, fn, repeats, n=1):
+        """A vf_terrain_debug_*_stage call, which times `repeats` launches: its n figures in ms -- a float for n = 1, else a tuple."""
+        ms = (_f * n)()
+        self._check(fn(self.t, int(repeats), ms))
+        return ms[0] if n == 1 else tuple(ms)
+
+    def _vertices(self, count, read):
+        """The vertices of a list of `count` seeds or observers, (count, 2) uint32; None: no list, or no uniforms set yet (`read` refuses)."""
+        if not count:
+            return None
+        out = np.empty((count, 2), np.uint32)
+        return out if read(self.t, out.ctypes.data) == VF_OK else None
 
     def close(self):
         if self.t:
@@ -423,7 +419,7 @@ class Terrain:
         sizes = None if np.isscalar(size_px) else np.ascontiguousarray(size_px, dtype=np.float32).reshape(n)
         cols = np.ascontiguousarray(rgba, dtype=np.uint8)
         per = cols.ndim == 2
-        default = (C.c_uint8 * 4)(*([255] * 4 if per else [int(v) for v in cols.reshape(4)]))
+        default = _rgba([255] * 4 if per else cols.reshape(4))
         layer = _u32()
         self._check(self.lib.vf_terrain_add_points(self.t, xyz.ctypes.data, n, None if sizes is None else sizes.ctypes.data,
                                                    cols.ctypes.data if per else None, float(size_px) if sizes is None else 0.0,
@@ -434,7 +430,7 @@ class Terrain:
         """Polyline layer: coords (M, 3), offsets (P + 1,) uint32 (vulkan_forge.pack_lines); cap 0 butt / 1 square / 2 round."""
         coords = np.ascontiguousarray(coords, dtype=np.float32).reshape(-1, 3)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint32)
-        col = (C.c_uint8 * 4)(*[int(v) for v in rgba])
+        col = _rgba(rgba)
         layer = _u32()
         self._check(self.lib.vf_terrain_add_lines(self.t, coords.ctypes.data, offsets.ctypes.data, max(len(offsets) - 1, 0),
                                                   float(width_px), C.cast(col, _vp), int(cap), int(bool(drape)), C.byref(layer)))
@@ -449,8 +445,8 @@ class Terrain:
         feats = np.ascontiguousarray(feature_offsets, dtype=np.uint32)
         fills = None if fill_rgba is None else np.ascontiguousarray(fill_rgba, dtype=np.uint8)
         per = fills is not None and fills.ndim == 2
-        default = None if fills is None or per else C.cast((C.c_uint8 * 4)(*[int(v) for v in fills.reshape(4)]), _vp)
-        line = None if line_rgba is None else C.cast((C.c_uint8 * 4)(*[int(v) for v in line_rgba]), _vp)
+        default = None if fills is None or per else C.cast(_rgba(fills.reshape(4)), _vp)
+        line = None if line_rgba is None else C.cast(_rgba(line_rgba), _vp)
         layer = _u32()
         self._check(self.lib.vf_terrain_add_polygons(self.t, coords.ctypes.data, rings.ctypes.data, max(len(rings) - 1, 0), feats.ctypes.data,
                                                      max(len(feats) - 1, 0), fills.ctypes.data if per else None, default, line,
@@ -474,7 +470,7 @@ class Terrain:
         """Contour layer extracted on the device from the rendered surface: levels ascending float32; join 0 round /
         1 none.  Returns (layer id, number of segments)."""
         levels = np.ascontiguousarray(levels, dtype=np.float32).reshape(-1)
-        col = (C.c_uint8 * 4)(*[int(v) for v in rgba])
+        col = _rgba(rgba)
         layer, nseg = _u32(), _u32()
         self._check(self.lib.vf_terrain_add_contours(self.t, levels.ctypes.data, len(levels), float(width_px), C.cast(col, _vp), float(lift),
                                                      int(join), int(bool(occlude)), float(depth_bias), C.byref(layer), C.byref(nseg)))
@@ -487,9 +483,7 @@ class Terrain:
         return lo.value, hi.value
 
     def layer_primitive_count(self, layer):
-        n = _u32()
-        self._check(self.lib.vf_terrain_layer_primitive_count(self.t, int(layer), C.byref(n)))
-        return n.value
+        return self._count(lambda t, n: self.lib.vf_terrain_layer_primitive_count(t, int(layer), n))
 
     def clear_overlays(self):
         self._check(self.lib.vf_terrain_clear_overlays(self.t))
@@ -503,9 +497,7 @@ class Terrain:
         return out
 
     def local_tiles(self):
-        n = _u32()
-        self._check(self.lib.vf_terrain_local_tiles(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_local_tiles)
 
     def read_tiles(self):
         """(local_tiles, 64, 64, 4) uint8, the tile-major buffer of a tile-sharded handle."""
@@ -559,9 +551,7 @@ class Terrain:
         return {k: getattr(ft, k) for k, _ in FragmentTiming._fields_}
 
     def local_rows(self):
-        r = _u32()
-        self._check(self.lib.vf_terrain_local_rows(self.t, C.byref(r)))
-        return r.value
+        return self._count(self.lib.vf_terrain_local_rows)
 
     def set_output_device(self, dptr):
         self._check(self.lib.vf_terrain_set_output_device(self.t, _vp(dptr)))
@@ -622,13 +612,11 @@ class Terrain:
 
     def samples_device(self, dev_dst, stream=None):
         """The same into device memory (a torch tensor's data_ptr(), f H x f W x 4 bytes); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_samples_device(self.t, dev_dst, stream))
+        self._to_device(self.lib.vf_terrain_samples_device, dev_dst, stream)
 
     def resolve_stage(self, repeats=50):
         """The resolve kernel as timed launches of its own (diagnostics): average ms of `repeats` launches."""
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_resolve_stage(self.t, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(self.lib.vf_terrain_debug_resolve_stage, repeats)
 
     # ---- atmospheric haze (include/vf_hip.h, DESIGN.md 4q) ----
     def set_haze(self, density, *, rgba=(200, 215, 235, 255), start=0.0, falloff=None, base=0.0, max_opacity=1.0, background=False, enabled=True):
@@ -637,7 +625,7 @@ class Terrain:
         max_opacity.  Every parameter is stored by every call, also one that disables, and steers haze_opacity() too."""
         from ._haze import haze_args
         en, dens, col, st, fo, ba, mo, bg = haze_args(density, rgba, start, falloff, base, max_opacity, background, enabled)
-        self._check(self.lib.vf_terrain_set_haze(self.t, en, dens, (C.c_uint8 * 4)(*col), st, fo, ba, mo, bg))
+        self._check(self.lib.vf_terrain_set_haze(self.t, en, dens, _rgba(col), st, fo, ba, mo, bg))
 
     def clear_haze(self):
         """Haze off, its parameters the defaults again, its opacity plane freed."""
@@ -659,13 +647,11 @@ class Terrain:
 
     def haze_opacity_device(self, dev, stream=None):
         """The same into device memory (a torch tensor's data_ptr(), H x W floats) on `stream`."""
-        self._check(self.lib.vf_terrain_haze_opacity_device(self.t, dev, stream))
+        self._to_device(self.lib.vf_terrain_haze_opacity_device, dev, stream)
 
     def haze_stage(self, repeats=20):
         """The haze pass alone as timed launches (diagnostics): average ms of `repeats` launches."""
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_haze_stage(self.t, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(self.lib.vf_terrain_debug_haze_stage, repeats)
 
     def set_flood(self, level, seeds=None, *, enabled=True, shallow_rgba=(96, 176, 224, 128), deep_rgba=(16, 64, 160, 224), depth_full=0.1):
         """Flood analysis: the ground below `level` (units of h before exaggeration, as contour levels) that water reaches
@@ -675,7 +661,7 @@ class Terrain:
         from ._flood import flood_args
         en, lv, mode, xz, sh, dp, full = flood_args(level, seeds, enabled, shallow_rgba, deep_rgba, depth_full)
         self._check(self.lib.vf_terrain_set_flood(self.t, en, lv, mode, None if xz is None else xz.ctypes.data, 0 if xz is None else xz.shape[0],
-                                                  (C.c_uint8 * 4)(*sh), (C.c_uint8 * 4)(*dp), full))
+                                                  _rgba(sh), _rgba(dp), full))
 
     def clear_flood(self):
         """The flood is off, its parameters are the defaults again and its buffers are freed."""
@@ -683,14 +669,11 @@ class Terrain:
 
     def flood_field(self):
         """The depth field for the current heights, uniforms, level and sources: (grid, grid) float32, level - h where flooded, else 0."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_flood_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_flood_field)
 
     def flood_field_device(self, dev_depth, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_flood_field_device(self.t, dev_depth, stream))
+        self._to_device(self.lib.vf_terrain_flood_field_device, dev_depth, stream)
 
     def flood_info(self):
         """dict: the settings, vertices ((N, 2) uint32 of a seed list, else None) and, of the last computation, flooded_vertices,
@@ -698,19 +681,12 @@ class Terrain:
         from ._flood import flood_info
         v = FloodInfo()
         self._check(self.lib.vf_terrain_flood_info(self.t, C.byref(v)))
-        vertices = None
-        if v.count:
-            vertices = np.empty((v.count, 2), np.uint32)
-            if self.lib.vf_terrain_read_flood_seeds(self.t, vertices.ctypes.data) != VF_OK:
-                vertices = None                                # (uniforms not set yet)
-        return flood_info(v.enabled, v.has_flood, v.mode, v.count, vertices, v.level, v.depth_full, tuple(v.shallow_rgba), tuple(v.deep_rgba),
-                          v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group)
+        return flood_info(v.enabled, v.has_flood, v.mode, v.count, self._vertices(v.count, self.lib.vf_terrain_read_flood_seeds), v.level, v.depth_full,
+                          tuple(v.shallow_rgba), tuple(v.deep_rgba), v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group)
 
     def flood_scans(self):
         """How many times the handle has computed its flood field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_flood_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_flood_scans)
 
     def flood_group(self, group=0):
         """Force the number of propagation passes queued per read-back (diagnostics); 0: the default again."""
@@ -719,9 +695,7 @@ class Terrain:
     def flood_stage(self, repeats=5):
         """(ms of one computation of the field, ms of the tint pass) as timed launches of their own on the frame rendered last
         (diagnostics); it needs the flood enabled."""
-        ms = (_f * 2)()
-        self._check(self.lib.vf_terrain_debug_flood_stage(self.t, int(repeats), ms))
-        return ms[0], ms[1]
+        return self._stage(self.lib.vf_terrain_debug_flood_stage, repeats, 2)
 
     def set_spill(self, seeds="edges", *, enabled=True, shallow_rgba=(96, 176, 224, 128), deep_rgba=(16, 64, 160, 224), depth_full=0.1):
         """Spill analysis: the level the water must reach at the sources before a vertex gets wet, and a tint of the
@@ -731,7 +705,7 @@ class Terrain:
         from ._spill import spill_args
         en, mode, xz, sh, dp, full = spill_args(seeds, enabled, shallow_rgba, deep_rgba, depth_full)
         self._check(self.lib.vf_terrain_set_spill(self.t, en, mode, None if xz is None else xz.ctypes.data, 0 if xz is None else xz.shape[0],
-                                                  (C.c_uint8 * 4)(*sh), (C.c_uint8 * 4)(*dp), full))
+                                                  _rgba(sh), _rgba(dp), full))
 
     def clear_spill(self):
         """The spill is off, its parameters are the defaults again and its buffers are freed."""
@@ -739,21 +713,15 @@ class Terrain:
 
     def spill_field(self):
         """The spill field for the current heights, uniforms and sources: (grid, grid) float32, +inf where no path arrives."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_spill_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_spill_field)
 
     def spill_field_device(self, dev_spill, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_spill_field_device(self.t, dev_spill, stream))
+        self._to_device(self.lib.vf_terrain_spill_field_device, dev_spill, stream)
 
     def sink_depth_field(self):
         """(grid, grid) float32: spill - h where that is finite, 0 elsewhere."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_sink_depth(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_sink_depth)
 
     def spill_info(self):
         """dict: the settings, vertices ((N, 2) uint32 of a seed list, else None) and, of the last computation, reached_vertices,
@@ -761,19 +729,12 @@ class Terrain:
         from ._spill import spill_info
         v = SpillInfo()
         self._check(self.lib.vf_terrain_spill_info(self.t, C.byref(v)))
-        vertices = None
-        if v.count:
-            vertices = np.empty((v.count, 2), np.uint32)
-            if self.lib.vf_terrain_read_spill_seeds(self.t, vertices.ctypes.data) != VF_OK:
-                vertices = None                                # (uniforms not set yet)
-        return spill_info(v.enabled, v.has_spill, v.mode, v.count, vertices, v.depth_full, tuple(v.shallow_rgba), tuple(v.deep_rgba),
-                          v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs)
+        return spill_info(v.enabled, v.has_spill, v.mode, v.count, self._vertices(v.count, self.lib.vf_terrain_read_spill_seeds), v.depth_full,
+                          tuple(v.shallow_rgba), tuple(v.deep_rgba), v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs)
 
     def spill_scans(self):
         """How many times the handle has computed its spill field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_spill_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_spill_scans)
 
     def spill_group(self, group=0, flags=True):
         """Force the number of relaxation passes queued per read-back (diagnostics); 0: the default again.  flags=False: the activity
@@ -783,9 +744,7 @@ class Terrain:
     def spill_stage(self, repeats=5):
         """(ms of one computation of the field, ms of the tint pass) as timed launches of their own on the frame rendered last
         (diagnostics); it needs the spill enabled."""
-        ms = (_f * 2)()
-        self._check(self.lib.vf_terrain_debug_spill_stage(self.t, int(repeats), ms))
-        return ms[0], ms[1]
+        return self._stage(self.lib.vf_terrain_debug_spill_stage, repeats, 2)
 
     def read_gbuffer(self, planes=("depth", "position", "normal", "primitive")):
         """Geometry buffers of the frame rendered last: dict plane name -> array."""
@@ -812,9 +771,7 @@ class Terrain:
         """The geometry-buffer kernel as timed launches of its own (diagnostics): average ms of `repeats` launches."""
         from ._gbuffer import PLANES, plane_args
         mask = sum(1 << list(PLANES).index(k) for k in plane_args(planes))
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_gbuffer_stage(self.t, mask, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(lambda t, reps, ms: self.lib.vf_terrain_debug_gbuffer_stage(t, mask, reps, ms), repeats)
 
     def set_shadows(self, enabled=True, *, strength=0.7, softness=0.02, bias=0.002):
         """Cast sun shadows on the terrain.  The three parameters are stored by every call, also one that disables, and
@@ -824,26 +781,19 @@ class Terrain:
 
     def shadow_field(self):
         """The shadow field for the current heights, uniforms and parameters: (grid, grid) float32, lit in [0, 1]."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_shadow_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_shadow_field)
 
     def shadow_field_device(self, dev_lit, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_shadow_field_device(self.t, dev_lit, stream))
+        self._to_device(self.lib.vf_terrain_shadow_field_device, dev_lit, stream)
 
     def shadow_stage(self, repeats=20):
         """(scan ms, shade-pass ms) of the frame rendered last, as timed launches of their own (diagnostics)."""
-        ms = (_f * 2)()
-        self._check(self.lib.vf_terrain_debug_shadow_stage(self.t, int(repeats), ms))
-        return ms[0], ms[1]
+        return self._stage(self.lib.vf_terrain_debug_shadow_stage, repeats, 2)
 
     def shadow_scans(self):
         """How many times the handle has computed its shadow field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_shadow_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_shadow_scans)
 
     def set_ambient_occlusion(self, enabled=True, *, strength=0.6, reach=64.0, directions=16):
         """Ambient occlusion from a sky-view scan of the height field.  `directions`: how many of the default set, or
@@ -855,26 +805,19 @@ class Terrain:
 
     def sky_view_field(self):
         """The sky-view field for the current heights, uniforms and parameters: (grid, grid) float32, sky in [0, 1], 1 = open sky."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_sky_view_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_sky_view_field)
 
     def sky_view_field_device(self, dev_sky, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_sky_view_field_device(self.t, dev_sky, stream))
+        self._to_device(self.lib.vf_terrain_sky_view_field_device, dev_sky, stream)
 
     def ambient_stage(self, repeats=20):
         """(field ms, shade-pass ms) of the frame rendered last, as timed launches of their own (diagnostics)."""
-        ms = (_f * 2)()
-        self._check(self.lib.vf_terrain_debug_ambient_stage(self.t, int(repeats), ms))
-        return ms[0], ms[1]
+        return self._stage(self.lib.vf_terrain_debug_ambient_stage, repeats, 2)
 
     def ambient_scans(self):
         """How many times the handle has computed its sky-view field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_ambient_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_ambient_scans)
 
     def set_viewshed(self, observer, *, enabled=True, eye_height=0.05, target_height=0.0, radius=None, visible_rgba=(64, 255, 96, 96),
                      hidden_rgba=(0, 0, 0, 0), softness=0.02, bias=0.002):
@@ -883,7 +826,7 @@ class Terrain:
         from ._viewshed import viewshed_args
         en, x, z, eye, tgt, rad, vis, hid, soft, bias = viewshed_args(observer, enabled, eye_height, target_height, radius, visible_rgba, hidden_rgba,
                                                                       softness, bias)
-        self._check(self.lib.vf_terrain_set_viewshed(self.t, en, (_f * 2)(x, z), eye, tgt, rad, (C.c_uint8 * 4)(*vis), (C.c_uint8 * 4)(*hid), soft, bias))
+        self._check(self.lib.vf_terrain_set_viewshed(self.t, en, (_f * 2)(x, z), eye, tgt, rad, _rgba(vis), _rgba(hid), soft, bias))
 
     def clear_viewshed(self):
         """Forget the observer: the viewshed is off, its parameters are the defaults again and its buffers are freed."""
@@ -891,14 +834,11 @@ class Terrain:
 
     def viewshed_field(self):
         """The viewshed field for the current heights, uniforms, observer and parameters: (grid, grid) float32, 1 = seen, 0 = hidden."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_viewshed_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_viewshed_field)
 
     def viewshed_field_device(self, dev_seen, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_viewshed_field_device(self.t, dev_seen, stream))
+        self._to_device(self.lib.vf_terrain_viewshed_field_device, dev_seen, stream)
 
     def viewshed_info(self):
         """dict: enabled, vertex (i, j), observer_xyz (world), eye_y, and the parameters."""
@@ -910,15 +850,11 @@ class Terrain:
 
     def viewshed_stage(self, repeats=20):
         """(scan ms, tint-pass ms) of the frame rendered last, as timed launches of their own (diagnostics)."""
-        ms = (_f * 2)()
-        self._check(self.lib.vf_terrain_debug_viewshed_stage(self.t, int(repeats), ms))
-        return ms[0], ms[1]
+        return self._stage(self.lib.vf_terrain_debug_viewshed_stage, repeats, 2)
 
     def viewshed_scans(self):
         """How many times the handle has computed its viewshed field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_viewshed_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_viewshed_scans)
 
     def set_cumulative_viewshed(self, observers, *, enabled=True, eye_height=0.05, target_height=0.0, radius=None, high_rgba=(64, 255, 96, 160),
                                 low_rgba=(0, 0, 0, 0), softness=0.02, bias=0.002):
@@ -928,8 +864,8 @@ class Terrain:
         from ._cumulative_viewshed import cumulative_viewshed_args
         en, obs, eye, tgt, rad, high, low, soft, bias = cumulative_viewshed_args(observers, enabled, eye_height, target_height, radius, high_rgba,
                                                                                  low_rgba, softness, bias)
-        self._check(self.lib.vf_terrain_set_cumulative_viewshed(self.t, en, obs.ctypes.data, obs.shape[0], eye, tgt, rad, (C.c_uint8 * 4)(*high),
-                                                                (C.c_uint8 * 4)(*low), soft, bias))
+        self._check(self.lib.vf_terrain_set_cumulative_viewshed(self.t, en, obs.ctypes.data, obs.shape[0], eye, tgt, rad, _rgba(high), _rgba(low),
+                                                                soft, bias))
 
     def clear_cumulative_viewshed(self):
         """Forget the observers: the cumulative viewshed is off, its parameters are the defaults again and its buffers are freed."""
@@ -937,25 +873,18 @@ class Terrain:
 
     def cumulative_viewshed_field(self):
         """The count field for the current heights, uniforms, observers and parameters: (grid, grid) float32 in [0, N]."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_cumulative_viewshed_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_cumulative_viewshed_field)
 
     def cumulative_viewshed_field_device(self, dev_count, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_cumulative_viewshed_field_device(self.t, dev_count, stream))
+        self._to_device(self.lib.vf_terrain_cumulative_viewshed_field_device, dev_count, stream)
 
     def cumulative_viewshed_info(self):
         """dict: enabled, observers (N), batch, vertices ((N, 2) uint32, None before observers and uniforms are set), and the parameters."""
         from ._cumulative_viewshed import cumulative_viewshed_info
         v = CumulativeViewshedInfo()
         self._check(self.lib.vf_terrain_cumulative_viewshed_info(self.t, C.byref(v)))
-        vertices = None
-        if v.count:
-            vertices = np.empty((v.count, 2), np.uint32)
-            if self.lib.vf_terrain_read_cumulative_viewshed_vertices(self.t, vertices.ctypes.data) != VF_OK:
-                vertices = None                                # (uniforms not set yet)
+        vertices = self._vertices(v.count, self.lib.vf_terrain_read_cumulative_viewshed_vertices)
         return cumulative_viewshed_info(v.enabled, v.count, v.batch, vertices, v.eye_height, v.target_height, v.radius, v.softness, v.bias,
                                         tuple(v.high_rgba), tuple(v.low_rgba))
 
@@ -965,15 +894,11 @@ class Terrain:
 
     def cumulative_viewshed_scans(self):
         """How many times the handle has computed its cumulative viewshed field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_cumulative_viewshed_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_cumulative_viewshed_scans)
 
     def cumulative_viewshed_stage(self, repeats=5):
         """ms of one computation of the field, as timed launches of their own (diagnostics)."""
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_cumulative_viewshed_stage(self.t, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(self.lib.vf_terrain_debug_cumulative_viewshed_stage, repeats)
 
     def set_sun_exposure(self, suns, *, weights=None, incidence=False, enabled=True, softness=0.02, bias=0.002, high_rgba=(255, 208, 64, 160),
                          low_rgba=(0, 0, 0, 0)):
@@ -984,8 +909,7 @@ class Terrain:
         en, s, w, inc, soft, bias, high, low = sun_exposure_args(suns, weights, incidence, enabled, softness, bias, high_rgba, low_rgba)
         if s.shape[1] != 3:
             raise ValueError("the C ABI takes suns as (N, 3) direction vectors")
-        self._check(self.lib.vf_terrain_set_sun_exposure(self.t, en, s.ctypes.data, w.ctypes.data, s.shape[0], inc, soft, bias, (C.c_uint8 * 4)(*high),
-                                                         (C.c_uint8 * 4)(*low)))
+        self._check(self.lib.vf_terrain_set_sun_exposure(self.t, en, s.ctypes.data, w.ctypes.data, s.shape[0], inc, soft, bias, _rgba(high), _rgba(low)))
 
     def clear_sun_exposure(self):
         """Forget the suns: sun exposure is off, its parameters are the defaults again and its buffers are freed."""
@@ -993,14 +917,11 @@ class Terrain:
 
     def sun_exposure_field(self):
         """The exposure field for the current heights, uniforms, suns and parameters: (grid, grid) float32 in [0, sum of weights]."""
-        n = max(self.grid, 2)
-        out = np.empty((n, n), np.float32)
-        self._check(self.lib.vf_terrain_read_sun_exposure_field(self.t, out.ctypes.data))
-        return out
+        return self._grid_field(self.lib.vf_terrain_read_sun_exposure_field)
 
     def sun_exposure_field_device(self, dev_exposure, stream=None):
         """The same into device memory (a torch tensor's data_ptr()); the copy is asynchronous on `stream`."""
-        self._check(self.lib.vf_terrain_sun_exposure_field_device(self.t, dev_exposure, stream))
+        self._to_device(self.lib.vf_terrain_sun_exposure_field_device, dev_exposure, stream)
 
     def sun_exposure_info(self):
         """dict: enabled, suns (N), counted, weight_total, incidence, batch, softness, bias and the colours."""
@@ -1016,15 +937,11 @@ class Terrain:
 
     def sun_exposure_scans(self):
         """How many times the handle has computed its sun exposure field."""
-        n = _u32()
-        self._check(self.lib.vf_terrain_debug_sun_exposure_scans(self.t, C.byref(n)))
-        return n.value
+        return self._count(self.lib.vf_terrain_debug_sun_exposure_scans)
 
     def sun_exposure_stage(self, repeats=5):
         """ms of one computation of the field, as timed launches of their own (diagnostics)."""
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_sun_exposure_stage(self.t, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(self.lib.vf_terrain_debug_sun_exposure_stage, repeats)
 
     def set_drape(self, image, *, extent=None, opacity=1.0, filter="linear"):
         """Drape an image on the terrain as its albedo.  image: (ih, iw, 4) or (ih, iw, 3) uint8, sRGB bytes with
@@ -1055,9 +972,7 @@ class Terrain:
 
     def drape_stage(self, repeats=20):
         """Shade-pass ms of the drape for the frame rendered last, as timed launches of their own (diagnostics)."""
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_drape_stage(self.t, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(self.lib.vf_terrain_debug_drape_stage, repeats)
 
     def set_drape_mipmaps(self, enabled=True, *, bias=0.0):
         """Sample the draped image through a mip pyramid at the level of detail of each pixel's footprint.  bias is
@@ -1094,9 +1009,7 @@ class Terrain:
 
     def drape_mip_build_stage(self, repeats=20):
         """Build ms of the whole mip pyramid of the drape held, as timed launches of their own (diagnostics)."""
-        ms = _f()
-        self._check(self.lib.vf_terrain_debug_drape_mip_build(self.t, int(repeats), C.byref(ms)))
-        return ms.value
+        return self._stage(self.lib.vf_terrain_debug_drape_mip_build, repeats)
 
     def set_drape_anisotropy(self, max_anisotropy=1):
         """Anisotropic filtering of the mip sampling: up to max_anisotropy (1, 2, 4, 8 or 16) samples along the longer
@@ -1107,9 +1020,7 @@ class Terrain:
 
     def drape_anisotropy(self):
         """The largest anisotropy as set (1: off)."""
-        a = _u32()
-        self._check(self.lib.vf_terrain_drape_anisotropy(self.t, C.byref(a)))
-        return a.value
+        return self._count(self.lib.vf_terrain_drape_anisotropy)
 
     def enable_timing(self, on=True, stats=True, sampled=False):
         """stats=False: HIP events only, the kernels run exactly as untimed (no per-item statistics; blocks_* read 0);
@@ -1152,9 +1063,8 @@ class Terrain:
     def plan_mode(self, geometry=False):
         """VF_PLAN_* bits: how the frame rendered last was planned.  Whether the plan state's geometry was rebuilt or reused changes nothing
         in the plan, so VF_PLAN_GEOMETRY_REUSED is reported only on request (geometry=True: the word as the library gives it)."""
-        m = _u32()
-        self._check(self.lib.vf_terrain_debug_plan_mode(self.t, C.byref(m)))
-        return m.value if geometry else m.value & ~(VF_PLAN_GEOMETRY_REUSED | VF_PLAN_TILE_LISTS)
+        m = self._count(self.lib.vf_terrain_debug_plan_mode)
+        return m if geometry else m & ~(VF_PLAN_GEOMETRY_REUSED | VF_PLAN_TILE_LISTS)
 
     def tile_lists(self):
         """Debug / tests: the per-tile candidate lists of the plan state the last frame was drawn from, as a dict:

@@ -188,6 +188,19 @@ py::array_t<float> mat4_to_numpy(const Mat4 &m)
     return a;
 }
 
+// ---- what the bound methods say more than once --------------------------------------------------------------------
+// The callable `fn` of the rules in vulkan_forge_amd/<module>.py.  A call of it touches Python objects: never under a released GIL.  An
+// `*_args` / `*_params` rule may refuse its arguments, so a method calls it BEFORE it borrows the object (the two that need a figure
+// of the handle first, contour_args and mip_level, get it in a borrow of its own or say why not); the `*_info` rules only shape a result.
+py::object rules(const char *module, const char *fn) { return py::module_::import((std::string("vulkan_forge_amd.") + module).c_str()).attr(fn); }
+// a colour as the rules return it, a tuple of four ints, -> the bytes a C call takes; and four values of an info record -> a tuple
+void rgba4(const py::object &colour, uint8_t out[4])
+{
+    py::tuple c = colour.cast<py::tuple>();
+    for (int k = 0; k < 4; ++k) out[k] = c[k].cast<uint8_t>();
+}
+template <class T> py::tuple tuple4(const T *v) { return py::make_tuple(v[0], v[1], v[2], v[3]); }
+
 // ---- TerrainSpike / Scene -----------------------------------------------------------------------
 class TerrainObject {
 public:
@@ -195,7 +208,7 @@ public:
     // supersample: f x f samples per pixel, resolved on the GPU (argument rules: vulkan_forge_amd/_supersample.py)
     TerrainObject(int kind, uint32_t width, uint32_t height, py::object grid, py::object colormap, py::object supersample) : W(width), H(height)
     {
-        ss = py::module_::import("vulkan_forge_amd._supersample").attr("supersample_args")(width, height, supersample).cast<uint32_t>();
+        ss = rules("_supersample", "supersample_args")(width, height, supersample).cast<uint32_t>();
         SW = ss * W; SH = ss * H;
         uint32_t g = grid.is_none() ? 128u : grid.cast<uint32_t>();
         n = g < 2 ? 2 : g;
@@ -449,9 +462,8 @@ public:
     uint32_t add_points(py::object xyz, py::object size_px, py::object rgba, py::object shape, bool drape, py::object occlude, py::object depth_bias,
                         py::object haze)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("point_args")(xyz, size_px, rgba, shape);
-        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(haze).cast<bool>();
-        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
+        py::tuple a = rules("_overlays", "point_args")(xyz, size_px, rgba, shape);
+        const LayerTail tail(occlude, depth_bias, haze);
         py::array pts = a[0].cast<py::array>(), dcol = a[3].cast<py::array>();
         const float dsize = a[1].cast<float>();
         py::object sizes = a[2], cols = a[4];
@@ -459,35 +471,32 @@ public:
         const float *sz = sizes.is_none() ? nullptr : static_cast<const float *>(sizes.cast<py::array>().data());
         const uint8_t *cl = cols.is_none() ? nullptr : static_cast<const uint8_t *>(cols.cast<py::array>().data());
         Borrow b(busy);
-        if (oc[0].cast<bool>()) refuse_occlusion_if_supersampled();   // (before the layer exists: a refusal leaves the object as it was)
+        tail.refuse_early(ss);
         uint32_t id = 0;
         check(vf_terrain_add_points(t, static_cast<const float *>(pts.data()), (uint32_t)pts.shape(0), sz, cl, dsize,
                                     static_cast<const uint8_t *>(dcol.data()), shp, drape ? 1 : 0, &id));
-        if (oc[0].cast<bool>()) check(vf_terrain_set_layer_occlusion(t, id, 1, oc[1].cast<float>()));
-        if (hz) check(vf_terrain_set_layer_haze(t, id, 1));
+        tail.apply(t, id, true);
         return id;
     }
     uint32_t add_lines(py::object paths, py::object width_px, py::object rgba, py::object cap, bool drape, py::object occlude, py::object depth_bias,
                        py::object haze)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("line_args")(paths, width_px, rgba, cap);
-        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(haze).cast<bool>();
-        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
+        py::tuple a = rules("_overlays", "line_args")(paths, width_px, rgba, cap);
+        const LayerTail tail(occlude, depth_bias, haze);
         py::array coords = a[0].cast<py::array>(), offsets = a[1].cast<py::array>(), col = a[3].cast<py::array>();
         const float width = a[2].cast<float>();
         const int cp = a[4].cast<int>();
         Borrow b(busy);
-        if (oc[0].cast<bool>()) refuse_occlusion_if_supersampled();
+        tail.refuse_early(ss);
         uint32_t id = 0;
         check(vf_terrain_add_lines(t, static_cast<const float *>(coords.data()), static_cast<const uint32_t *>(offsets.data()),
                                    (uint32_t)(offsets.shape(0) - 1), width, static_cast<const uint8_t *>(col.data()), cp, drape ? 1 : 0, &id));
-        if (oc[0].cast<bool>()) check(vf_terrain_set_layer_occlusion(t, id, 1, oc[1].cast<float>()));
-        if (hz) check(vf_terrain_set_layer_haze(t, id, 1));
+        tail.apply(t, id, true);
         return id;
     }
     uint32_t add_polygons(py::object polygons, py::object fill_rgba, py::object line_rgba, py::object line_width_px, bool drape)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("polygon_args")(polygons, fill_rgba, line_rgba, line_width_px);
+        py::tuple a = rules("_overlays", "polygon_args")(polygons, fill_rgba, line_rgba, line_width_px);
         py::array coords = a[0].cast<py::array>(), rings = a[1].cast<py::array>(), feats = a[2].cast<py::array>();
         py::object dfill = a[3], fills = a[4], line = a[5];
         const float width = a[6].cast<float>();
@@ -502,14 +511,14 @@ public:
     // occlusion of a point / line layer by the terrain
     void set_layer_occlusion(uint32_t layer, py::object occlude, py::object depth_bias)
     {
-        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
+        py::tuple oc = rules("_overlays", "occlusion_args")(occlude, depth_bias);
         Borrow b(busy);
         check(vf_terrain_set_layer_occlusion(t, layer, oc[0].cast<bool>() ? 1 : 0, oc[1].cast<float>()));
     }
     // a point / line / contour layer under the atmospheric haze
     void set_layer_haze(uint32_t layer, py::object on)
     {
-        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(on, "on").cast<bool>();
+        const bool hz = rules("_overlays", "haze_arg")(on, "on").cast<bool>();
         Borrow b(busy);
         check(vf_terrain_set_layer_haze(t, layer, hz ? 1 : 0));
     }
@@ -530,53 +539,40 @@ public:
     }
     uint32_t layer_primitive_count(uint32_t layer)
     {
-        Borrow b(busy);
-        uint32_t n = 0;
-        check(vf_terrain_layer_primitive_count(t, layer, &n));
-        return n;
+        return counter([layer](vf_terrain *h, uint32_t *count) { return vf_terrain_layer_primitive_count(h, layer, count); });
     }
     uint32_t add_contours(py::object levels, py::object interval, py::object base, py::object width_px, py::object rgba, py::object lift,
                           py::object join, py::object occlude, py::object depth_bias, py::object haze)
     {
-        const bool hz = py::module_::import("vulkan_forge_amd._overlays").attr("haze_arg")(haze).cast<bool>();
+        const LayerTail tail(occlude, depth_bias, haze);
         py::object bounds = py::none();
         if (levels.is_none() && !interval.is_none()) bounds = height_bounds();
-        py::tuple a = py::module_::import("vulkan_forge_amd._overlays").attr("contour_args")(levels, interval, base, width_px, rgba, lift, join, bounds);
-        py::tuple oc = py::module_::import("vulkan_forge_amd._overlays").attr("occlusion_args")(occlude, depth_bias);
+        py::tuple a = rules("_overlays", "contour_args")(levels, interval, base, width_px, rgba, lift, join, bounds);
         py::array lv = a[0].cast<py::array>(), col = a[2].cast<py::array>();
         Borrow b(busy);
         uint32_t id = 0;
+        // (the library's call takes the occlusion itself, and refuses it on a supersampled handle before it makes the layer)
         check(vf_terrain_add_contours(t, static_cast<const float *>(lv.data()), (uint32_t)lv.shape(0), a[1].cast<float>(),
-                                      static_cast<const uint8_t *>(col.data()), a[3].cast<float>(), a[4].cast<int>(), oc[0].cast<bool>() ? 1 : 0,
-                                      oc[1].cast<float>(), &id, nullptr));
-        if (hz) check(vf_terrain_set_layer_haze(t, id, 1));
+                                      static_cast<const uint8_t *>(col.data()), a[3].cast<float>(), a[4].cast<int>(), tail.occlude ? 1 : 0,
+                                      tail.depth_bias, &id, nullptr));
+        tail.apply(t, id, false);
         return id;
     }
-    void clear_overlays() { Borrow b(busy); check(vf_terrain_clear_overlays(t)); }
+    void clear_overlays() { clear(vf_terrain_clear_overlays, false); }   // (overlays composite behind the stored frame: it stays current)
 
     // extension: supersampling
     uint32_t supersample() const { return ss; }
     uint32_t samples() const { return ss * ss; }
     py::tuple sample_size() const { return py::make_tuple(SW, SH); }
     // the samples of the current frame before the resolve: terrain and passes, no overlays, (f H, f W, 4) uint8
-    py::array_t<uint8_t> render_samples()
-    {
-        Borrow b(busy);
-        py::array_t<uint8_t> a({ (py::ssize_t)SH, (py::ssize_t)SW, (py::ssize_t)4 });
-        uint8_t *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        int rc = draw_current();
-        if (rc == VF_OK) rc = vf_terrain_read_samples(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    py::array_t<uint8_t> render_samples() { return frame_plane<uint8_t>({ (py::ssize_t)SH, (py::ssize_t)SW, 4 }, vf_terrain_read_samples); }
 
     // extension: geometry buffers -- per-pixel depth, world position, normal and primitive id (argument rules:
     // vulkan_forge_amd/_gbuffer.py).  Like render_rgba they describe the frame for the current uniforms: it is drawn first unless the
     // frame this object drew last already is that frame.
     py::dict render_gbuffer(py::object planes)
     {
-        py::tuple names = py::module_::import("vulkan_forge_amd._gbuffer").attr("plane_args")(planes);
+        py::tuple names = rules("_gbuffer", "plane_args")(planes);
         Borrow b(busy);
         py::dict out;
         float *f[3] = { nullptr, nullptr, nullptr };
@@ -600,19 +596,12 @@ public:
     }
     py::array_t<float> render_depth()
     {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)SH, (py::ssize_t)SW });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        int rc = draw_current();
-        if (rc == VF_OK) rc = vf_terrain_read_gbuffer(t, dst, nullptr, nullptr, nullptr);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
+        return frame_plane<float>({ (py::ssize_t)SH, (py::ssize_t)SW },
+                                  [](vf_terrain *h, float *depth) { return vf_terrain_read_gbuffer(h, depth, nullptr, nullptr, nullptr); });
     }
     py::dict pick(py::object pixels)
     {
-        py::module_ rules = py::module_::import("vulkan_forge_amd._gbuffer");
-        py::array px = rules.attr("pixel_args")(pixels, W, H).cast<py::array>();
+        py::array px = rules("_gbuffer", "pixel_args")(pixels, W, H).cast<py::array>();
         const uint32_t count = (uint32_t)px.shape(0);
         Borrow b(busy);
         py::array_t<uint32_t> words({ (py::ssize_t)count, (py::ssize_t)8 });
@@ -624,64 +613,34 @@ public:
             if (rc == VF_OK) rc = vf_terrain_pick(t, src, count, dst);
             if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
         }
-        return rules.attr("pick_result")(words).cast<py::dict>();
+        return rules("_gbuffer", "pick_result")(words).cast<py::dict>();
     }
 
     // extension: cast sun shadows (argument rules: vulkan_forge_amd/_shadows.py)
     void set_shadows(bool enabled, float strength, float softness, float bias)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._shadows").attr("shadow_args")(enabled, strength, softness, bias);
+        py::tuple a = rules("_shadows", "shadow_args")(enabled, strength, softness, bias);
         Borrow b(busy);
         check(vf_terrain_set_shadows(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<float>(), a[3].cast<float>()));
         frame_current = false;
     }
-    py::array_t<float> shadow_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_shadow_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
-    uint32_t debug_shadow_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_shadow_scans(t, &count));
-        return count;
-    }
+    py::array_t<float> shadow_field() { return vertex_field(vf_terrain_read_shadow_field); }
+    uint32_t debug_shadow_scans() { return counter(vf_terrain_debug_shadow_scans); }
     // extension: ambient occlusion from a sky-view scan (argument rules: vulkan_forge_amd/_ambient.py)
     void set_ambient_occlusion(bool enabled, float strength, float reach, py::object directions)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._ambient").attr("ambient_args")(enabled, strength, reach, directions);
+        py::tuple a = rules("_ambient", "ambient_args")(enabled, strength, reach, directions);
         py::array dirs = a[4].cast<py::array>();             // (D, 2) float32, contiguous
         Borrow b(busy);
         check(vf_terrain_set_ambient(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<float>(), a[3].cast<uint32_t>(), static_cast<const float *>(dirs.data())));
         frame_current = false;
     }
-    py::array_t<float> sky_view_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_sky_view_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
-    uint32_t debug_ambient_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_ambient_scans(t, &count));
-        return count;
-    }
+    py::array_t<float> sky_view_field() { return vertex_field(vf_terrain_read_sky_view_field); }
+    uint32_t debug_ambient_scans() { return counter(vf_terrain_debug_ambient_scans); }
     // extension: a draped image layer (argument rules: vulkan_forge_amd/_drape.py)
     void set_drape(py::object image, py::object extent, py::object opacity, py::object filter)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._drape").attr("drape_args")(image, extent, opacity, filter);
+        py::tuple a = rules("_drape", "drape_args")(image, extent, opacity, filter);
         py::array img = a[0].cast<py::array>();              // (ih, iw, channels) uint8, contiguous
         py::array ext = a[4].cast<py::array>();              // (4,) float32
         const uint32_t iw = a[1].cast<uint32_t>(), ih = a[2].cast<uint32_t>(), channels = a[3].cast<uint32_t>();
@@ -698,12 +657,7 @@ public:
         check(rc);
         frame_current = false;
     }
-    void clear_drape()
-    {
-        Borrow b(busy);
-        check(vf_terrain_clear_drape(t));
-        frame_current = false;
-    }
+    void clear_drape() { clear(vf_terrain_clear_drape); }
     py::object drape_info()
     {
         Borrow b(busy);
@@ -711,12 +665,12 @@ public:
         float ext[4] = { 0.0f, 0.0f, 0.0f, 0.0f }, op = 0.0f;
         int code = 0;
         check(vf_terrain_drape_info(t, &iw, &ih, ext, &op, &code));
-        return py::module_::import("vulkan_forge_amd._drape").attr("drape_info")(iw, ih, py::make_tuple(ext[0], ext[1], ext[2], ext[3]), op, code);
+        return rules("_drape", "drape_info")(iw, ih, tuple4(ext), op, code);
     }
     // extension: a mip pyramid under the draped image (argument rules: vulkan_forge_amd/_drape.py)
     void set_drape_mipmaps(py::object enabled, py::object bias)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._drape").attr("mip_params")(enabled, bias);
+        py::tuple a = rules("_drape", "mip_params")(enabled, bias);
         Borrow b(busy);
         check(vf_terrain_set_drape_mips(t, a[0].cast<int>(), a[1].cast<float>()));
         frame_current = false;
@@ -730,14 +684,14 @@ public:
         uint64_t bytes = 0;
         check(vf_terrain_drape_mip_info(t, &enabled, &levels, &bias, &bytes, &builds));
         check(vf_terrain_drape_info(t, &iw, &ih, nullptr, nullptr, nullptr));
-        return py::module_::import("vulkan_forge_amd._drape").attr("mip_info")(enabled != 0, levels, bias, bytes, builds, iw, ih);
+        return rules("_drape", "mip_info")(enabled != 0, levels, bias, bytes, builds, iw, ih);
     }
     py::array read_drape_level(py::object level)
     {
         Borrow b(busy);
         uint32_t levels = 0, w = 0, h = 0;
         check(vf_terrain_drape_mip_info(t, nullptr, &levels, nullptr, nullptr, nullptr));
-        const uint32_t k = py::module_::import("vulkan_forge_amd._drape").attr("mip_level")(level, levels).cast<uint32_t>();
+        const uint32_t k = rules("_drape", "mip_level")(level, levels).cast<uint32_t>();   // (needs the handle's level count: inside the borrow)
         check(vf_terrain_read_drape_level(t, k, nullptr, &w, &h));
         py::array out(py::dtype("float16"), std::vector<py::ssize_t>{ (py::ssize_t)h, (py::ssize_t)w, 4 });
         uint16_t *dst = static_cast<uint16_t *>(out.mutable_data());
@@ -752,28 +706,20 @@ public:
     // extension: anisotropic filtering of the mip sampling (argument rules: vulkan_forge_amd/_drape.py)
     void set_drape_anisotropy(py::object max_anisotropy)
     {
-        const uint32_t a = py::module_::import("vulkan_forge_amd._drape").attr("aniso_params")(max_anisotropy).cast<uint32_t>();
+        const uint32_t a = rules("_drape", "aniso_params")(max_anisotropy).cast<uint32_t>();
         Borrow b(busy);
         check(vf_terrain_set_drape_anisotropy(t, a));
         frame_current = false;
     }
-    uint32_t drape_anisotropy()
-    {
-        Borrow b(busy);
-        uint32_t a = 0;
-        check(vf_terrain_drape_anisotropy(t, &a));
-        return a;
-    }
+    uint32_t drape_anisotropy() { return counter(vf_terrain_drape_anisotropy); }
     // extension: viewshed analysis (argument rules: vulkan_forge_amd/_viewshed.py)
     void set_viewshed(py::object observer, py::object enabled, py::object eye_height, py::object target_height, py::object radius,
                       py::object visible_rgba, py::object hidden_rgba, py::object softness, py::object bias)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._viewshed").attr("viewshed_args")(observer, enabled, eye_height, target_height, radius,
-                                                                                           visible_rgba, hidden_rgba, softness, bias);
+        py::tuple a = rules("_viewshed", "viewshed_args")(observer, enabled, eye_height, target_height, radius, visible_rgba, hidden_rgba, softness, bias);
         const float xz[2] = { a[1].cast<float>(), a[2].cast<float>() };
         uint8_t vis[4], hid[4];
-        py::tuple tv = a[6].cast<py::tuple>(), th = a[7].cast<py::tuple>();
-        for (int k = 0; k < 4; ++k) { vis[k] = tv[k].cast<uint8_t>(); hid[k] = th[k].cast<uint8_t>(); }
+        rgba4(a[6], vis); rgba4(a[7], hid);
         Borrow b(busy);
         check(vf_terrain_set_viewshed(t, a[0].cast<int>(), xz, a[3].cast<float>(), a[4].cast<float>(), a[5].cast<float>(), vis, hid,
                                       a[8].cast<float>(), a[9].cast<float>()));
@@ -785,44 +731,26 @@ public:
         check(vf_terrain_set_viewshed(t, 0, nullptr, 0.0f, 0.0f, 0.0f, nullptr, nullptr, 1.0f, 0.0f));
         frame_current = false;
     }
-    py::array_t<float> viewshed_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_viewshed_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    py::array_t<float> viewshed_field() { return vertex_field(vf_terrain_read_viewshed_field); }
     py::object viewshed_info()
     {
         Borrow b(busy);
         vf_viewshed_info v;
         check(vf_terrain_viewshed_info(t, &v));
-        return py::module_::import("vulkan_forge_amd._viewshed").attr("viewshed_info")(
+        return rules("_viewshed", "viewshed_info")(
             v.enabled, v.has_observer, py::make_tuple(v.vertex[0], v.vertex[1]), py::make_tuple(v.observer_xyz[0], v.observer_xyz[1], v.observer_xyz[2]),
-            v.eye_y, v.eye_height, v.target_height, v.radius, v.softness, v.bias,
-            py::make_tuple(v.visible_rgba[0], v.visible_rgba[1], v.visible_rgba[2], v.visible_rgba[3]),
-            py::make_tuple(v.hidden_rgba[0], v.hidden_rgba[1], v.hidden_rgba[2], v.hidden_rgba[3]));
+            v.eye_y, v.eye_height, v.target_height, v.radius, v.softness, v.bias, tuple4(v.visible_rgba), tuple4(v.hidden_rgba));
     }
-    uint32_t debug_viewshed_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_viewshed_scans(t, &count));
-        return count;
-    }
+    uint32_t debug_viewshed_scans() { return counter(vf_terrain_debug_viewshed_scans); }
     // extension: cumulative viewsheds (argument rules: vulkan_forge_amd/_cumulative_viewshed.py)
     void set_cumulative_viewshed(py::object observers, py::object enabled, py::object eye_height, py::object target_height, py::object radius,
                                  py::object high_rgba, py::object low_rgba, py::object softness, py::object bias)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._cumulative_viewshed").attr("cumulative_viewshed_args")(
-            observers, enabled, eye_height, target_height, radius, high_rgba, low_rgba, softness, bias);
+        py::tuple a = rules("_cumulative_viewshed", "cumulative_viewshed_args")(observers, enabled, eye_height, target_height, radius, high_rgba, low_rgba,
+                                                                                softness, bias);
         auto obs = a[1].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
         uint8_t high[4], low[4];
-        py::tuple th = a[5].cast<py::tuple>(), tl = a[6].cast<py::tuple>();
-        for (int k = 0; k < 4; ++k) { high[k] = th[k].cast<uint8_t>(); low[k] = tl[k].cast<uint8_t>(); }
+        rgba4(a[5], high); rgba4(a[6], low);
         Borrow b(busy);
         check(vf_terrain_set_cumulative_viewshed(t, a[0].cast<int>(), obs.data(), (uint32_t)obs.shape(0), a[2].cast<float>(), a[3].cast<float>(),
                                                  a[4].cast<float>(), high, low, a[7].cast<float>(), a[8].cast<float>()));
@@ -834,49 +762,23 @@ public:
         check(vf_terrain_set_cumulative_viewshed(t, 0, nullptr, 0, 0.0f, 0.0f, 0.0f, nullptr, nullptr, 1.0f, 0.0f));
         frame_current = false;
     }
-    py::array_t<float> cumulative_viewshed_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_cumulative_viewshed_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    py::array_t<float> cumulative_viewshed_field() { return vertex_field(vf_terrain_read_cumulative_viewshed_field); }
     py::object cumulative_viewshed_info()
     {
         Borrow b(busy);
         vf_cumulative_viewshed_info v;
         check(vf_terrain_cumulative_viewshed_info(t, &v));
-        py::object vertices = py::none();
-        if (v.count) {
-            py::array_t<uint32_t> a({ (py::ssize_t)v.count, (py::ssize_t)2 });
-            if (vf_terrain_read_cumulative_viewshed_vertices(t, a.mutable_data()) == VF_OK) vertices = a;   // (else: uniforms not set yet)
-        }
-        return py::module_::import("vulkan_forge_amd._cumulative_viewshed").attr("cumulative_viewshed_info")(
-            v.enabled, v.count, v.batch, vertices, v.eye_height, v.target_height, v.radius, v.softness, v.bias,
-            py::make_tuple(v.high_rgba[0], v.high_rgba[1], v.high_rgba[2], v.high_rgba[3]),
-            py::make_tuple(v.low_rgba[0], v.low_rgba[1], v.low_rgba[2], v.low_rgba[3]));
+        return rules("_cumulative_viewshed", "cumulative_viewshed_info")(
+            v.enabled, v.count, v.batch, listed_vertices(v.count, vf_terrain_read_cumulative_viewshed_vertices), v.eye_height, v.target_height, v.radius,
+            v.softness, v.bias, tuple4(v.high_rgba), tuple4(v.low_rgba));
     }
-    void debug_cumulative_viewshed_batch(uint32_t batch)
-    {
-        Borrow b(busy);
-        check(vf_terrain_debug_cumulative_viewshed_batch(t, batch));
-    }
-    uint32_t debug_cumulative_viewshed_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_cumulative_viewshed_scans(t, &count));
-        return count;
-    }
+    void debug_cumulative_viewshed_batch(uint32_t batch) { Borrow b(busy); check(vf_terrain_debug_cumulative_viewshed_batch(t, batch)); }
+    uint32_t debug_cumulative_viewshed_scans() { return counter(vf_terrain_debug_cumulative_viewshed_scans); }
     // extension: sun exposure (argument rules: vulkan_forge_amd/_sun_exposure.py)
     void set_sun_exposure(py::object suns, py::object weights, py::object incidence, py::object enabled, py::object softness, py::object bias,
                           py::object high_rgba, py::object low_rgba)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._sun_exposure").attr("sun_exposure_args")(suns, weights, incidence, enabled, softness, bias,
-                                                                                                     high_rgba, low_rgba);
+        py::tuple a = rules("_sun_exposure", "sun_exposure_args")(suns, weights, incidence, enabled, softness, bias, high_rgba, low_rgba);
         auto given = a[1].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
         auto w = a[2].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
         const size_t count = (size_t)given.shape(0);
@@ -890,91 +792,46 @@ public:
         }
         else std::copy(g, g + 3u * count, xyz.begin());
         uint8_t high[4], low[4];
-        py::tuple th = a[6].cast<py::tuple>(), tl = a[7].cast<py::tuple>();
-        for (int k = 0; k < 4; ++k) { high[k] = th[k].cast<uint8_t>(); low[k] = tl[k].cast<uint8_t>(); }
+        rgba4(a[6], high); rgba4(a[7], low);
         Borrow b(busy);
         check(vf_terrain_set_sun_exposure(t, a[0].cast<int>(), xyz.data(), w.data(), (uint32_t)count, a[3].cast<int>(), a[4].cast<float>(),
                                           a[5].cast<float>(), high, low));
         frame_current = false;
     }
-    void clear_sun_exposure()
-    {
-        Borrow b(busy);
-        check(vf_terrain_clear_sun_exposure(t));
-        frame_current = false;
-    }
-    py::array_t<float> sun_exposure_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_sun_exposure_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    void clear_sun_exposure() { clear(vf_terrain_clear_sun_exposure); }
+    py::array_t<float> sun_exposure_field() { return vertex_field(vf_terrain_read_sun_exposure_field); }
     py::object sun_exposure_info()
     {
         Borrow b(busy);
         vf_sun_exposure_info v;
         check(vf_terrain_sun_exposure_info(t, &v));
-        return py::module_::import("vulkan_forge_amd._sun_exposure").attr("sun_exposure_info")(
-            v.enabled, v.count, v.counted, v.weight_total, v.incidence, v.batch, v.softness, v.bias,
-            py::make_tuple(v.high_rgba[0], v.high_rgba[1], v.high_rgba[2], v.high_rgba[3]),
-            py::make_tuple(v.low_rgba[0], v.low_rgba[1], v.low_rgba[2], v.low_rgba[3]));
+        return rules("_sun_exposure", "sun_exposure_info")(v.enabled, v.count, v.counted, v.weight_total, v.incidence, v.batch, v.softness, v.bias,
+                                                           tuple4(v.high_rgba), tuple4(v.low_rgba));
     }
-    void debug_sun_exposure_batch(uint32_t batch)
-    {
-        Borrow b(busy);
-        check(vf_terrain_debug_sun_exposure_batch(t, batch));
-    }
-    uint32_t debug_sun_exposure_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_sun_exposure_scans(t, &count));
-        return count;
-    }
+    void debug_sun_exposure_batch(uint32_t batch) { Borrow b(busy); check(vf_terrain_debug_sun_exposure_batch(t, batch)); }
+    uint32_t debug_sun_exposure_scans() { return counter(vf_terrain_debug_sun_exposure_scans); }
     // extension: atmospheric haze (argument rules: vulkan_forge_amd/_haze.py)
     void set_haze(py::object density, py::object rgba, py::object start, py::object falloff, py::object base, py::object max_opacity,
                   py::object background, py::object enabled)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._haze").attr("haze_args")(density, rgba, start, falloff, base, max_opacity, background, enabled);
+        py::tuple a = rules("_haze", "haze_args")(density, rgba, start, falloff, base, max_opacity, background, enabled);
         uint8_t col[4];
-        py::tuple tc = a[2].cast<py::tuple>();
-        for (int k = 0; k < 4; ++k) col[k] = tc[k].cast<uint8_t>();
+        rgba4(a[2], col);
         Borrow b(busy);
         check(vf_terrain_set_haze(t, a[0].cast<int>(), a[1].cast<float>(), col, a[3].cast<float>(), a[4].cast<float>(), a[5].cast<float>(),
                                   a[6].cast<float>(), a[7].cast<int>()));
         frame_current = false;
     }
-    void clear_haze()
-    {
-        Borrow b(busy);
-        check(vf_terrain_clear_haze(t));
-        frame_current = false;
-    }
+    void clear_haze() { clear(vf_terrain_clear_haze); }
     py::object haze_info()
     {
         Borrow b(busy);
         vf_haze_info v;
         check(vf_terrain_haze_info(t, &v));
-        return py::module_::import("vulkan_forge_amd._haze").attr("haze_info")(
-            v.enabled, v.background, v.density, v.start, v.falloff, v.base, v.max_opacity,
-            py::make_tuple(v.rgba[0], v.rgba[1], v.rgba[2], v.rgba[3]), v.has_eye, v.eye_y);
+        return rules("_haze", "haze_info")(v.enabled, v.background, v.density, v.start, v.falloff, v.base, v.max_opacity, tuple4(v.rgba), v.has_eye, v.eye_y);
     }
     // like render_depth it describes the frame for the current uniforms: drawn first unless the frame drawn last already is that frame
-    py::array_t<float> haze_opacity()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)SH, (py::ssize_t)SW });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        int rc = draw_current();
-        if (rc == VF_OK) rc = vf_terrain_read_haze_opacity(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    py::array_t<float> haze_opacity() { return frame_plane<float>({ (py::ssize_t)SH, (py::ssize_t)SW }, vf_terrain_read_haze_opacity); }
     // what flood_args / spill_args return about the sources, as the C calls take it: a[i] the seeds ((N, 2) float32 or None), a[i + 1]
     // and a[i + 2] the shallow and the deep colour
     struct FillArgs {
@@ -988,12 +845,12 @@ public:
                 arr = a[i].cast<py::array_t<float, py::array::c_style | py::array::forcecast>>();
                 xz = arr.data(); count = (uint32_t)arr.shape(0);
             }
-            py::tuple ts = a[i + 1].cast<py::tuple>(), td = a[i + 2].cast<py::tuple>();
-            for (int k = 0; k < 4; ++k) { sh[k] = ts[k].cast<uint8_t>(); dp[k] = td[k].cast<uint8_t>(); }
+            rgba4(a[i + 1], sh); rgba4(a[i + 2], dp);
         }
     };
-    // the vertices of `count` seeds as (count, 2) uint32, or None: no seeds, or no uniforms set yet (`read` refuses)
-    py::object seed_vertices(uint32_t count, int (*read)(vf_terrain *, uint32_t *))
+    // the vertices of `count` listed points -- the seeds of a fill, the observers of the cumulative viewshed -- as (count, 2) uint32, or
+    // None: nothing listed, or no uniforms set yet (`read` refuses).  The caller holds the borrow.
+    py::object listed_vertices(uint32_t count, int (*read)(vf_terrain *, uint32_t *))
     {
         if (!count) return py::none();
         py::array_t<uint32_t> a({ (py::ssize_t)count, (py::ssize_t)2 });
@@ -1003,109 +860,48 @@ public:
     // extension: flood analysis (argument rules: vulkan_forge_amd/_flood.py)
     void set_flood(py::object level, py::object seeds, py::object enabled, py::object shallow_rgba, py::object deep_rgba, py::object depth_full)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._flood").attr("flood_args")(level, seeds, enabled, shallow_rgba, deep_rgba, depth_full);
+        py::tuple a = rules("_flood", "flood_args")(level, seeds, enabled, shallow_rgba, deep_rgba, depth_full);
         const FillArgs f(a, 3);
         Borrow b(busy);
         check(vf_terrain_set_flood(t, a[0].cast<int>(), a[1].cast<float>(), a[2].cast<int>(), f.xz, f.count, f.sh, f.dp, a[6].cast<float>()));
         frame_current = false;
     }
-    void clear_flood()
-    {
-        Borrow b(busy);
-        check(vf_terrain_clear_flood(t));
-        frame_current = false;
-    }
-    py::array_t<float> flood_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_flood_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    void clear_flood() { clear(vf_terrain_clear_flood); }
+    py::array_t<float> flood_field() { return vertex_field(vf_terrain_read_flood_field); }
     py::object flood_info()
     {
         Borrow b(busy);
         vf_flood_info v;
         check(vf_terrain_flood_info(t, &v));
-        return py::module_::import("vulkan_forge_amd._flood").attr("flood_info")(
-            v.enabled, v.has_flood, v.mode, v.count, seed_vertices(v.count, vf_terrain_read_flood_seeds), v.level, v.depth_full,
-            py::make_tuple(v.shallow_rgba[0], v.shallow_rgba[1], v.shallow_rgba[2], v.shallow_rgba[3]),
-            py::make_tuple(v.deep_rgba[0], v.deep_rgba[1], v.deep_rgba[2], v.deep_rgba[3]),
-            v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group);
+        return rules("_flood", "flood_info")(
+            v.enabled, v.has_flood, v.mode, v.count, listed_vertices(v.count, vf_terrain_read_flood_seeds), v.level, v.depth_full,
+            tuple4(v.shallow_rgba), tuple4(v.deep_rgba), v.flooded_vertices, v.wettable_vertices, v.passes, v.scans, v.group);
     }
-    void debug_flood_group(uint32_t group)
-    {
-        Borrow b(busy);
-        check(vf_terrain_debug_flood_group(t, group));
-    }
-    uint32_t debug_flood_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_flood_scans(t, &count));
-        return count;
-    }
+    void debug_flood_group(uint32_t group) { Borrow b(busy); check(vf_terrain_debug_flood_group(t, group)); }
+    uint32_t debug_flood_scans() { return counter(vf_terrain_debug_flood_scans); }
     // extension: spill analysis (argument rules: vulkan_forge_amd/_spill.py)
     void set_spill(py::object seeds, py::object enabled, py::object shallow_rgba, py::object deep_rgba, py::object depth_full)
     {
-        py::tuple a = py::module_::import("vulkan_forge_amd._spill").attr("spill_args")(seeds, enabled, shallow_rgba, deep_rgba, depth_full);
+        py::tuple a = rules("_spill", "spill_args")(seeds, enabled, shallow_rgba, deep_rgba, depth_full);
         const FillArgs f(a, 2);
         Borrow b(busy);
         check(vf_terrain_set_spill(t, a[0].cast<int>(), a[1].cast<int>(), f.xz, f.count, f.sh, f.dp, a[5].cast<float>()));
         frame_current = false;
     }
-    void clear_spill()
-    {
-        Borrow b(busy);
-        check(vf_terrain_clear_spill(t));
-        frame_current = false;
-    }
-    py::array_t<float> spill_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_spill_field(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
-    py::array_t<float> sink_depth_field()
-    {
-        Borrow b(busy);
-        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
-        float *dst = a.mutable_data();
-        py::gil_scoped_release nogil;
-        const int rc = vf_terrain_read_sink_depth(t, dst);
-        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
-        return a;
-    }
+    void clear_spill() { clear(vf_terrain_clear_spill); }
+    py::array_t<float> spill_field() { return vertex_field(vf_terrain_read_spill_field); }
+    py::array_t<float> sink_depth_field() { return vertex_field(vf_terrain_read_sink_depth); }
     py::object spill_info()
     {
         Borrow b(busy);
         vf_spill_info v;
         check(vf_terrain_spill_info(t, &v));
-        return py::module_::import("vulkan_forge_amd._spill").attr("spill_info")(
-            v.enabled, v.has_spill, v.mode, v.count, seed_vertices(v.count, vf_terrain_read_spill_seeds), v.depth_full,
-            py::make_tuple(v.shallow_rgba[0], v.shallow_rgba[1], v.shallow_rgba[2], v.shallow_rgba[3]),
-            py::make_tuple(v.deep_rgba[0], v.deep_rgba[1], v.deep_rgba[2], v.deep_rgba[3]),
-            v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs);
+        return rules("_spill", "spill_info")(
+            v.enabled, v.has_spill, v.mode, v.count, listed_vertices(v.count, vf_terrain_read_spill_seeds), v.depth_full,
+            tuple4(v.shallow_rgba), tuple4(v.deep_rgba), v.reached_vertices, v.sink_vertices, v.passes, v.scans, v.group, v.tile_runs);
     }
-    void debug_spill_group(uint32_t group)
-    {
-        Borrow b(busy);
-        check(vf_terrain_debug_spill_group(t, group));
-    }
-    uint32_t debug_spill_scans()
-    {
-        Borrow b(busy);
-        uint32_t count = 0;
-        check(vf_terrain_debug_spill_scans(t, &count));
-        return count;
-    }
+    void debug_spill_group(uint32_t group) { Borrow b(busy); check(vf_terrain_debug_spill_group(t, group)); }
+    uint32_t debug_spill_scans() { return counter(vf_terrain_debug_spill_scans); }
     // extension: Renderer's sun and exposure setters (src/lib.rs:441-473) on the terrain objects; neither changes a default
     void set_sun(float elevation_deg, float azimuth_deg)
     {
@@ -1133,12 +929,74 @@ public:
     std::string debug_lut_format() const { return lut_format; }   // src/terrain/mod.rs:493-496
 
 private:
-    // add_points / add_lines make the layer first and set its occlusion afterwards: on a supersampled object the library would refuse the
-    // second step with the layer already there, so the first is not taken and the library's refusal is raised here, in its words
-    void refuse_occlusion_if_supersampled()
+    // ---- the call shapes the methods above share; each keeps, in one place, what a copy could get wrong ----
+    // A per-vertex field as (n, n) float32.  The GIL is released around `read` alone: it computes a stale field on the device and touches no
+    // Python object.  It is held again before a refusal is raised, and the borrow goes back on either way out.
+    py::array_t<float> vertex_field(int (*read)(vf_terrain *, float *))
     {
-        if (ss > 1u) throw std::runtime_error("the handle is supersampled: occluding overlay layers are not supported (their depth test reads the frame's visibility per output pixel)");
+        Borrow b(busy);
+        py::array_t<float> a({ (py::ssize_t)n, (py::ssize_t)n });
+        float *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        const int rc = read(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
     }
+    // A plane of the frame for the current uniforms, heights and settings: the same, with the frame drawn first unless the frame drawn last
+    // already is that frame (draw_current).  Only render_samples, render_depth, haze_opacity, render_gbuffer and pick draw before they read.
+    template <class T, class Read>
+    py::array_t<T> frame_plane(std::vector<py::ssize_t> shape, Read read)
+    {
+        Borrow b(busy);
+        py::array_t<T> a(std::move(shape));
+        T *dst = a.mutable_data();
+        py::gil_scoped_release nogil;
+        int rc = draw_current();
+        if (rc == VF_OK) rc = read(t, dst);
+        if (rc != VF_OK) { py::gil_scoped_acquire gil; raise_vf(rc); }
+        return a;
+    }
+    // One uint32 the handle keeps on the host -- a scan counter, a layer's primitive count, a setting: no device work, the GIL stays held.
+    template <class Get>
+    uint32_t counter(Get get)
+    {
+        Borrow b(busy);
+        uint32_t v = 0;
+        check(get(t, &v));
+        return v;
+    }
+    // A vf_terrain_clear_* call.  What it drops was part of the frame, so the frame is stale -- except for overlays (redraw = false),
+    // which are composited behind the stored frame.  clear_viewshed and clear_cumulative_viewshed are not here: the library clears those
+    // through their set call, and so do they.
+    void clear(int (*fn)(vf_terrain *), bool redraw = true)
+    {
+        Borrow b(busy);
+        check(fn(t));
+        if (redraw) frame_current = false;
+    }
+    // What add_points, add_lines and add_contours take behind their own arguments: occlude, depth_bias, haze.  The rules read them in the
+    // constructor, before the object is borrowed.  add_points / add_lines make the layer first and set its occlusion afterwards: on a
+    // supersampled object the library would refuse the second step with the layer already there, so refuse_early raises the library's
+    // refusal, in its words, before the first is taken.  apply: the caller holds the borrow and the layer exists.
+    struct LayerTail {
+        bool occlude = false, haze = false;
+        float depth_bias = 0.0f;
+        LayerTail(const py::object &occlude_, const py::object &depth_bias_, const py::object &haze_)
+        {
+            haze = rules("_overlays", "haze_arg")(haze_).cast<bool>();
+            py::tuple oc = rules("_overlays", "occlusion_args")(occlude_, depth_bias_);
+            occlude = oc[0].cast<bool>(); depth_bias = oc[1].cast<float>();
+        }
+        void refuse_early(uint32_t supersampling) const
+        {
+            if (occlude && supersampling > 1u) throw std::runtime_error("the handle is supersampled: occluding overlay layers are not supported (their depth test reads the frame's visibility per output pixel)");
+        }
+        void apply(vf_terrain *h, uint32_t layer, bool occlusion_too) const
+        {
+            if (occlusion_too && occlude) check(vf_terrain_set_layer_occlusion(h, layer, 1, depth_bias));
+            if (haze) check(vf_terrain_set_layer_haze(h, layer, 1));
+        }
+    };
     void push_uniforms()
     {
         last = to_uniforms(globals, view, proj);
