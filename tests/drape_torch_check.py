@@ -1,14 +1,8 @@
 """vf_terrain_set_drape_device from a torch tensor on a stream of the caller's draws the frame of the CPU model and of
 vf_terrain_set_drape (run by tests/test_gpu_drape.py in a process of its own)."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "drape_model"))
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 
 
 def main():

@@ -1,14 +1,8 @@
 """vf_terrain_flood_field_device into a torch tensor on a stream of the caller's equals vf_terrain_read_flood_field and the CPU model
 (run by tests/test_gpu_flood.py in a process of its own)."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "flood_model"))
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 
 
 def main():

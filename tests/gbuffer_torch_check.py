@@ -1,13 +1,8 @@
 """vf_terrain_gbuffer_device into torch tensors on a stream of the caller's equals vf_terrain_read_gbuffer (run by
 tests/test_gpu_gbuffer.py in a process of its own)."""
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 
 
 def bits(a):

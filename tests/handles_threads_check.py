@@ -18,12 +18,10 @@ import sys
 import threading
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-import numpy as np  # noqa: E402
+import numpy as np
 
-import soak_handles as sh  # noqa: E402
+import soak_handles as sh
+import support  # noqa: F401  (the repository root on sys.path)
 
 JOIN_S = 60.0
 FAILED = []

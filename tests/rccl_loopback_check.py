@@ -1,6 +1,6 @@
 """Run by tests/test_gpu_rccl_loopback.py in a fresh interpreter (torch must load its HIP runtime before the library does)."""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 import numpy as np
 
 

@@ -2,14 +2,10 @@
 vf_terrain_set_output_device with a torch tensor of H x W x 4 receives the resolved frame, vf_terrain_samples_device fills a tensor
 of f H x f W x 4 with what vf_terrain_read_samples returns, on a stream of the caller's, and vf_terrain_rgba_device names the frame."""
 import ctypes
-import os
-import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "supersample_model"))
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 
 
 def main():

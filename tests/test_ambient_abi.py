@@ -1,65 +1,40 @@
 """Ambient occlusion without a device: the header, cabi.SYMBOLS and the library agree on the new entry points, the
 Python methods exist on both classes with the documented signatures, and the argument rules refuse what they should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_ambient", "vf_terrain_read_sky_view_field", "vf_terrain_sky_view_field_device", "vf_terrain_debug_ambient_stage",
-         "vf_terrain_debug_ambient_scans"]
+ENTRY_POINTS = {"vf_terrain_set_ambient": ["t", "enable", "strength", "reach", "ndirs", "dirs_xz"],
+                "vf_terrain_read_sky_view_field": ["t", "sky"],
+                "vf_terrain_sky_view_field_device": ["t", "dev_sky", "stream"],
+                "vf_terrain_debug_ambient_stage": ["t", "repeats", "ms"],
+                "vf_terrain_debug_ambient_scans": ["t", "count"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_ambient"] == ["t", "enable", "strength", "reach", "ndirs", "dirs_xz"]
-    assert names["vf_terrain_read_sky_view_field"] == ["t", "sky"]
-    assert names["vf_terrain_sky_view_field_device"] == ["t", "dev_sky", "stream"]
-    assert names["vf_terrain_debug_ambient_stage"] == ["t", "repeats", "ms"]
-    assert names["vf_terrain_debug_ambient_scans"] == ["t", "count"]
-    loaded = cabi.load()
-    assert len(loaded.vf_terrain_set_ambient.argtypes) == 6 and len(loaded.vf_terrain_read_sky_view_field.argtypes) == 2
-    assert len(loaded.vf_terrain_sky_view_field_device.argtypes) == 3 and len(loaded.vf_terrain_debug_ambient_stage.argtypes) == 3
-    for k, v in (("STRENGTH", "0.6f"), ("REACH", "64.0f"), ("DIRECTIONS", "16")):
-        assert re.search(rf"#define VF_AMBIENT_{k} {v}\b", src), k
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("AMBIENT", (("STRENGTH", "0.6f"), ("REACH", "64.0f"), ("DIRECTIONS", "16")))
 
 
 def test_null_handles_are_refused_without_a_device():
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    ms = (ctypes.c_float * 2)()
-    count = ctypes.c_uint32()
-    assert lib.vf_terrain_set_ambient(None, 1, 0.6, 64.0, 16, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_sky_view_field(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_sky_view_field_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_ambient_stage(None, 1, ms) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_ambient_scans(None, ctypes.byref(count)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_ambient", (1, 0.6, 64.0, 16, None)),
+                             ("vf_terrain_read_sky_view_field", (out.ctypes.data,)),
+                             ("vf_terrain_sky_view_field_device", (None, None)),
+                             ("vf_terrain_debug_ambient_stage", (1, (ctypes.c_float * 2)())),
+                             ("vf_terrain_debug_ambient_scans", (ctypes.byref(ctypes.c_uint32()),))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_ambient_occlusion.__doc__
-        F = r"(float|typing\.SupportsFloat \| typing\.SupportsIndex)"
-        assert re.search(rf"set_ambient_occlusion\(self: [\w.]+, enabled: bool = True, \*, strength: {F} = 0.60\d+, reach: {F} = 64.0, directions: (object|typing\.Any) = 16\) -> None", doc), doc
-        assert re.search(r"sky_view_field\(self: [\w.]+\) -> numpy", T.sky_view_field.__doc__), T.sky_view_field.__doc__
-    from vulkan_forge_amd import cabi
-    assert callable(cabi.Terrain.set_ambient_occlusion) and callable(cabi.Terrain.sky_view_field) and callable(cabi.Terrain.sky_view_field_device)
+    F = r"(float|typing\.SupportsFloat \| typing\.SupportsIndex)"
+    abi.check_method_docs(cls, {
+        "set_ambient_occlusion": rf"set_ambient_occlusion\(self: [\w.]+, enabled: bool = True, \*, strength: {F} = 0.60\d+, reach: {F} = 64.0, directions: (object|typing\.Any) = 16\) -> None",
+        "sky_view_field": r"sky_view_field\(self: [\w.]+\) -> numpy"},
+        cabi_methods=("set_ambient_occlusion", "sky_view_field", "sky_view_field_device"))
 
 
 def test_the_default_directions():

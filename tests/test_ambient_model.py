@@ -3,36 +3,20 @@ the contract agrees bit for bit, the field commutes with the grid's mirrors and 
 on a plane and down a tilted one, a single step gives the hand-computed value, the reach is isotropic, and the scenes the GPU tests
 draw are partly occluded."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "ambient_model"))
-import ambient_model as abm  # noqa: E402
-import shadow_model as shm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
+from support import bits, smooth
+import ambient_model as abm
+import shadow_model as shm
+from overlay_scenes import CAMERAS, GRID, heights
 
 f32 = np.float32
 # general directions in every octant, the axes, exact diagonals
 DIRS = np.array([(0.9, 0.31), (0.31, 0.9), (-0.31, 0.9), (-0.9, 0.31), (-0.9, -0.31), (-0.31, -0.9), (0.31, -0.9), (0.9, -0.31),
                  (1, 0), (-1, 0), (0, 1), (0, -1), (1, 1), (-1, 1), (1, -1), (-1, -1)], f32)
-
-
-def smooth(n, seed=1):
-    rng = np.random.default_rng(seed)
-    x = np.linspace(0, 1, n, dtype=np.float64)
-    X, Z = np.meshgrid(x, x)
-    h = sum(rng.normal() * 0.2 / f * np.sin(2 * np.pi * f * (X * np.cos(a) + Z * np.sin(a)) + p)
-            for f, a, p in zip((1, 2, 3, 5), rng.uniform(0, 6.3, 4), rng.uniform(0, 6.3, 4)))
-    return h.astype(f32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def brute_force(h, dirs, spacing, exag, reach):

@@ -1,45 +1,33 @@
 """The contour entry points (include/vf_hip.h) are declared, listed in cabi.SYMBOLS, exported by libvf_hip.so, refuse a NULL handle,
 and add_contours' argument rules (vulkan_forge_amd/_overlays.py contour_args) hold (no GPU needed)."""
 import ctypes
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["vf_terrain_add_contours", "vf_terrain_height_bounds", "vf_terrain_layer_primitive_count"]
+import abi_support as abi
+
+ENTRY_POINTS = {"vf_terrain_add_contours": ["t", "levels", "nlevels", "width_px", "rgba", "lift", "join", "occlude", "depth_bias", "layer_id", "nsegments"],
+                "vf_terrain_height_bounds": ["t", "lo", "hi"],
+                "vf_terrain_layer_primitive_count": ["t", "layer_id", "count"]}
 
 
 def test_contour_entry_points_are_declared_listed_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vf_hip.h")).read(), flags=re.S)
-    sys.path.insert(0, ROOT)
-    from vulkan_forge_amd import cabi
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\b" + n + r"\s*\(", src), f"{n} not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and n in cabi._PROTOS, n
-        assert hasattr(lib, n), f"libvf_hip.so does not export {n}"
-    for macro in ("VF_JOIN_ROUND", "VF_JOIN_NONE"):
-        assert re.search(r"#define\s+" + macro + r"\b", src), macro
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("JOIN", (("ROUND", 0), ("NONE", 1)))
 
 
 def test_contour_calls_refuse_a_null_handle():
-    sys.path.insert(0, ROOT)
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
     lv = np.float32([0.0, 1.0])
     col = ctypes.cast((ctypes.c_uint8 * 4)(0, 0, 0, 255), ctypes.c_void_p)
     lo, hi, n = ctypes.c_float(), ctypes.c_float(), ctypes.c_uint32()
-    assert lib.vf_terrain_add_contours(None, lv.ctypes.data, 2, 1.0, col, 0.0, 0, 0, 0.01, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_height_bounds(None, ctypes.byref(lo), ctypes.byref(hi)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_layer_primitive_count(None, 0, ctypes.byref(n)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_add_contours", (lv.ctypes.data, 2, 1.0, col, 0.0, 0, 0, 0.01, None, None)),
+                             ("vf_terrain_height_bounds", (ctypes.byref(lo), ctypes.byref(hi))),
+                             ("vf_terrain_layer_primitive_count", (0, ctypes.byref(n)))])
 
 
 def test_scene_and_terrain_spike_have_the_methods():
     pytest.importorskip("vulkan_forge_amd._vulkan_forge")
-    sys.path.insert(0, ROOT)
     import vulkan_forge as vf
     for cls in (vf.Scene, vf.TerrainSpike):
         for m in ("add_contours", "height_bounds", "layer_primitive_count"):
@@ -53,7 +41,6 @@ def args(levels=None, interval=None, base=0.0, width_px=1.0, rgba=(0, 0, 0, 255)
 
 
 def test_contour_args_levels():
-    sys.path.insert(0, ROOT)
     lv, width, col, lift, join = args(np.array([0.0, 0.5, 2.0]), width_px=3, rgba=(1, 2, 3, 4), lift=0.25, join="none")
     assert lv.dtype == np.float32 and lv.tolist() == [0.0, 0.5, 2.0] and lv.flags.c_contiguous
     assert (width, lift, join) == (3.0, 0.25, 1) and col.dtype == np.uint8 and col.tolist() == [1, 2, 3, 4]
@@ -88,7 +75,6 @@ def test_contour_args_levels():
 
 
 def test_contour_args_style():
-    sys.path.insert(0, ROOT)
     lv = np.float32([0.0])
     with pytest.raises(ValueError, match="join"):
         args(lv, join="bevel")
@@ -111,7 +97,6 @@ def test_contour_args_style():
 
 
 def test_contour_args_interval():
-    sys.path.insert(0, ROOT)
     lv = args(interval=0.25, bounds=(-0.3, 0.8))[0]
     assert lv.dtype == np.float32 and lv.tolist() == [-0.25, 0.0, 0.25, 0.5, 0.75]
     assert args(interval=0.25, base=0.05, bounds=(0.05, 0.55))[0].tolist() == np.float32([0.05, 0.3, 0.55]).tolist()   # both ends included

@@ -2,16 +2,13 @@
 for bit and in order, the chaining of segments into closed joints, the interpolated height of every crossing point, and the segment
 count against an independent numpy count -- on random, ramp and plateau-on-a-level surfaces, on grids whose cell count is and is not a
 multiple of 8.  No GPU needed."""
-import os
-import sys
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "contour_model"))
-import contour_model as cm  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import contour_model as cm
 
 F = np.float32
 U = 2.0 ** -24                                                # unit roundoff of binary32

@@ -2,95 +2,61 @@
 header documents them, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what
 they should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_cumulative_viewshed", "vf_terrain_read_cumulative_viewshed_field", "vf_terrain_cumulative_viewshed_field_device",
-         "vf_terrain_cumulative_viewshed_info", "vf_terrain_read_cumulative_viewshed_vertices", "vf_terrain_debug_cumulative_viewshed_batch",
-         "vf_terrain_debug_cumulative_viewshed_scans", "vf_terrain_debug_cumulative_viewshed_stage"]
+ENTRY_POINTS = {"vf_terrain_set_cumulative_viewshed": ["t", "enable", "observers_xz", "count", "eye_height", "target_height", "radius", "high_rgba",
+                                                       "low_rgba", "softness", "bias"],
+                "vf_terrain_read_cumulative_viewshed_field": ["t", "count"],
+                "vf_terrain_cumulative_viewshed_field_device": ["t", "dev_count", "stream"],
+                "vf_terrain_cumulative_viewshed_info": ["t", "out"],
+                "vf_terrain_read_cumulative_viewshed_vertices": ["t", "vertices"],
+                "vf_terrain_debug_cumulative_viewshed_batch": ["t", "batch"],
+                "vf_terrain_debug_cumulative_viewshed_scans": ["t", "count"],
+                "vf_terrain_debug_cumulative_viewshed_stage": ["t", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
     from vulkan_forge_amd import cabi
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_cumulative_viewshed"] == ["t", "enable", "observers_xz", "count", "eye_height", "target_height", "radius", "high_rgba",
-                                                           "low_rgba", "softness", "bias"]
-    assert names["vf_terrain_read_cumulative_viewshed_field"] == ["t", "count"]
-    assert names["vf_terrain_cumulative_viewshed_field_device"] == ["t", "dev_count", "stream"]
-    assert names["vf_terrain_cumulative_viewshed_info"] == ["t", "out"]
-    assert names["vf_terrain_read_cumulative_viewshed_vertices"] == ["t", "vertices"]
-    assert names["vf_terrain_debug_cumulative_viewshed_batch"] == ["t", "batch"]
-    assert names["vf_terrain_debug_cumulative_viewshed_scans"] == ["t", "count"]
-    assert names["vf_terrain_debug_cumulative_viewshed_stage"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    for k, v in (("MAX_OBSERVERS", "65535u"), ("HIGH_RGBA", "0xA060FF40u"), ("LOW_RGBA", "0x00000000u")):
-        assert re.search(rf"#define VF_CUMULATIVE_VIEWSHED_{k} {v}(\s|$)", src), k
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("CUMULATIVE_VIEWSHED", (("MAX_OBSERVERS", "65535u"), ("HIGH_RGBA", "0xA060FF40u"), ("LOW_RGBA", "0x00000000u")))
     assert 0xA060FF40 == 64 | 255 << 8 | 96 << 16 | 160 << 24
-    # the struct the info call fills, field for field
-    body = re.search(r"typedef struct vf_cumulative_viewshed_info \{(.*?)\} vf_cumulative_viewshed_info;", src, flags=re.S).group(1)
-    fields = [re.sub(r"\[\d+\]", "", f.strip()) for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert fields == [f for f, _ in cabi.CumulativeViewshedInfo._fields_]
-    assert ctypes.sizeof(cabi.CumulativeViewshedInfo) == 4 * 8 + 8
+    abi.check_info_struct("vf_cumulative_viewshed_info", cabi.CumulativeViewshedInfo, 4 * 8 + 8)
 
 
 def test_the_header_documents_the_calls():
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    block = text[text.index("cumulative viewsheds: how many of N observers see each vertex"):]
-    for n in NAMES[:5]:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4m", "VF_ERR_INVALID", "whether or not the cumulative viewshed is enabled", "NULL: the context's", "1 <= count <= 65535",
-                 "rint(seen * 65536)", "Many observers per handle"):
-        assert word in block, word
+    abi.check_header_documents("cumulative viewsheds: how many of N observers see each vertex", list(ENTRY_POINTS)[:5],
+                               ("DESIGN.md 4m", "VF_ERR_INVALID", "whether or not the cumulative viewshed is enabled", "NULL: the context's", "1 <= count <= 65535",
+                                "rint(seen * 65536)", "Many observers per handle"))
 
 
 def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    ms = ctypes.c_float()
-    count = ctypes.c_uint32()
-    info = cabi.CumulativeViewshedInfo()
     xz, col = np.zeros((2, 2), np.float32), (ctypes.c_uint8 * 4)(1, 2, 3, 4)
-    assert lib.vf_terrain_set_cumulative_viewshed(None, 1, xz.ctypes.data, 2, 0.05, 0.0, 0.0, col, col, 0.02, 0.002) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_cumulative_viewshed_field(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_cumulative_viewshed_field_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_cumulative_viewshed_info(None, ctypes.byref(info)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_cumulative_viewshed_vertices(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_cumulative_viewshed_batch(None, 4) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_cumulative_viewshed_scans(None, ctypes.byref(count)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_cumulative_viewshed_stage(None, 1, ctypes.byref(ms)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_cumulative_viewshed", (1, xz.ctypes.data, 2, 0.05, 0.0, 0.0, col, col, 0.02, 0.002)),
+                             ("vf_terrain_read_cumulative_viewshed_field", (out.ctypes.data,)),
+                             ("vf_terrain_cumulative_viewshed_field_device", (None, None)),
+                             ("vf_terrain_cumulative_viewshed_info", (ctypes.byref(cabi.CumulativeViewshedInfo()),)),
+                             ("vf_terrain_read_cumulative_viewshed_vertices", (out.ctypes.data,)),
+                             ("vf_terrain_debug_cumulative_viewshed_batch", (4,)),
+                             ("vf_terrain_debug_cumulative_viewshed_scans", (ctypes.byref(ctypes.c_uint32()),)),
+                             ("vf_terrain_debug_cumulative_viewshed_stage", (1, ctypes.byref(ctypes.c_float())))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    from vulkan_forge_amd import cabi
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_cumulative_viewshed.__doc__
-        assert re.search(r"set_cumulative_viewshed\(self: [\w.]+, observers: object, \*, enabled: object = True, eye_height: object = 0.05\d*, "
-                         r"target_height: object = 0.0, radius: object = None, high_rgba: object = \(64, 255, 96, 160\), "
-                         r"low_rgba: object = \(0, 0, 0, 0\), softness: object = 0.019\d+, bias: object = 0.002\d*\) -> None", doc), doc
-        assert re.search(r"clear_cumulative_viewshed\(self: [\w.]+\) -> None", T.clear_cumulative_viewshed.__doc__)
-        assert re.search(r"cumulative_viewshed_field\(self: [\w.]+\) -> numpy", T.cumulative_viewshed_field.__doc__)
-        assert re.search(r"cumulative_viewshed_info\(self: [\w.]+\) -> object", T.cumulative_viewshed_info.__doc__)
-    for name in ("set_cumulative_viewshed", "clear_cumulative_viewshed", "cumulative_viewshed_field", "cumulative_viewshed_info"):
-        assert callable(getattr(cabi.Terrain, name)), name
+    abi.check_method_docs(cls, {
+        "set_cumulative_viewshed": r"set_cumulative_viewshed\(self: [\w.]+, observers: object, \*, enabled: object = True, eye_height: object = 0.05\d*, "
+                                   r"target_height: object = 0.0, radius: object = None, high_rgba: object = \(64, 255, 96, 160\), "
+                                   r"low_rgba: object = \(0, 0, 0, 0\), softness: object = 0.019\d+, bias: object = 0.002\d*\) -> None",
+        "clear_cumulative_viewshed": r"clear_cumulative_viewshed\(self: [\w.]+\) -> None",
+        "cumulative_viewshed_field": r"cumulative_viewshed_field\(self: [\w.]+\) -> numpy",
+        "cumulative_viewshed_info": r"cumulative_viewshed_info\(self: [\w.]+\) -> object"},
+        cabi_methods=("set_cumulative_viewshed", "clear_cumulative_viewshed", "cumulative_viewshed_field", "cumulative_viewshed_info"))
 
 
 def test_argument_rules():

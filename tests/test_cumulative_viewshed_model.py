@@ -3,26 +3,15 @@ one observer gives the quantised single field; the order of the observers change
 everywhere; the hand-worked wall of the viewshed model with an observer on either side gives the worked sums; a larger radius never
 lowers a count and the radius mask is a disc of grid vertices; a blind observer adds 1 everywhere in range; and the scene the GPU tests
 compute is not a trivial one."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "viewshed_model"))
-sys.path.insert(0, os.path.join(HERE, "cumulative_viewshed_model"))
-import cumulative_viewshed_model as cvm  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
-from overlay_scenes import heights  # noqa: E402
-from test_gpu_viewshed import PARAMS  # noqa: E402
-from test_viewshed_model import smooth  # noqa: E402
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+from support import smooth
+import cumulative_viewshed_model as cvm
+import viewshed_model as vsm
+from overlay_scenes import heights
+from test_gpu_viewshed import PARAMS
 
 
 def scene_uniforms(exag=0.6, spacing=1.0):

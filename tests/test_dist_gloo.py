@@ -3,12 +3,11 @@ uses (vulkan_forge_amd/dist.py), and rank 0 must hold the single-rank frame byte
 pixels come from the oracle here (no GPU in this tier); the band logic and the exchange are the product's."""
 import os
 import socket
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from support import ROOT
 
 
 def _free_port():
@@ -16,7 +15,6 @@ def _free_port():
 
 
 def _worker(rank, world, port, W, H, G, band, q):
-    sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch
     import torch.distributed as dist
@@ -68,7 +66,6 @@ def test_band_layout_properties():
 
 # ---- interleaved tiles (the bench's N > 1 layout) -------------------------------------------------------------
 def _tile_worker(rank, world, port, W, H, G, q):
-    sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch
     import torch.distributed as dist
@@ -160,7 +157,6 @@ def test_tile_layout_properties():
 
 # ---- tile shards stitched in parallel: all-to-all + one band per rank + in-place band gather (dist.BandStitchExchange) ----------
 def _band_worker(rank, world, port, W, H, G, q, stripe=0, owner=None):
-    sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch
     import torch.distributed as dist

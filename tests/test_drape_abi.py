@@ -1,71 +1,47 @@
 """The draped image layer without a device: the header, cabi's tables and the library agree on the new entry points and
 constants, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what they should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_drape", "vf_terrain_set_drape_device", "vf_terrain_clear_drape", "vf_terrain_drape_info", "vf_terrain_debug_drape_stage"]
-CONSTANTS = {"VF_DRAPE_SIZE_MAX": 16384, "VF_DRAPE_NEAREST": 0, "VF_DRAPE_LINEAR": 1}
+ENTRY_POINTS = {"vf_terrain_set_drape": ["t", "rgba", "iw", "ih", "channels", "extent", "opacity", "filter"],
+                "vf_terrain_set_drape_device": ["t", "dev_rgba", "iw", "ih", "extent", "opacity", "filter", "stream"],
+                "vf_terrain_clear_drape": ["t"],
+                "vf_terrain_drape_info": ["t", "iw", "ih", "extent", "opacity", "filter"],
+                "vf_terrain_debug_drape_stage": ["t", "repeats", "ms"]}
+CONSTANTS = {"SIZE_MAX": 16384, "NEAREST": 0, "LINEAR": 1}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and n in cabi._PROTOS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_drape"] == ["t", "rgba", "iw", "ih", "channels", "extent", "opacity", "filter"]
-    assert names["vf_terrain_set_drape_device"] == ["t", "dev_rgba", "iw", "ih", "extent", "opacity", "filter", "stream"]
-    assert names["vf_terrain_clear_drape"] == ["t"]
-    assert names["vf_terrain_drape_info"] == ["t", "iw", "ih", "extent", "opacity", "filter"]
-    assert names["vf_terrain_debug_drape_stage"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
+    from vulkan_forge_amd import _drape, cabi
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("DRAPE", CONSTANTS.items())
     for k, v in CONSTANTS.items():
-        assert re.search(rf"#define {k} {v}\b", src), k
-        assert getattr(cabi, k) == v, k
-    from vulkan_forge_amd import _drape
+        assert getattr(cabi, "VF_DRAPE_" + k) == v, k
     assert (_drape.SIZE_MAX, _drape.NEAREST, _drape.LINEAR) == (16384, 0, 1)
     assert _drape.FILTERS == {"nearest": 0, "linear": 1}
 
 
 def test_null_arguments_are_refused_without_a_device():
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
     img = np.zeros((2, 2, 4), np.uint8)
-    ms = ctypes.c_float()
-    iw = ctypes.c_uint32()
-    assert lib.vf_terrain_set_drape(None, img.ctypes.data, 2, 2, 4, None, 1.0, 1) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_set_drape_device(None, img.ctypes.data, 2, 2, None, 1.0, 1, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_clear_drape(None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_drape_info(None, ctypes.byref(iw), None, None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_drape_stage(None, 1, ctypes.byref(ms)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_drape", (img.ctypes.data, 2, 2, 4, None, 1.0, 1)),
+                             ("vf_terrain_set_drape_device", (img.ctypes.data, 2, 2, None, 1.0, 1, None)),
+                             ("vf_terrain_clear_drape", ()),
+                             ("vf_terrain_drape_info", (ctypes.byref(ctypes.c_uint32()), None, None, None, None)),
+                             ("vf_terrain_debug_drape_stage", (1, ctypes.byref(ctypes.c_float())))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_drape.__doc__
-        A = r"(object|typing\.Any)"
-        assert re.search(rf"set_drape\(self: [\w.]+, image: {A}, \*, extent: {A} = None, opacity: {A} = 1.0, filter: {A} = 'linear'\) -> None", doc), doc
-        assert re.search(r"clear_drape\(self: [\w.]+\) -> None", T.clear_drape.__doc__), T.clear_drape.__doc__
-        assert re.search(r"drape_info\(self: [\w.]+\) -> ", T.drape_info.__doc__), T.drape_info.__doc__
-    from vulkan_forge_amd import cabi
-    for m in ("set_drape", "set_drape_device", "clear_drape", "drape_info", "drape_stage"):
-        assert callable(getattr(cabi.Terrain, m)), m
+    A = r"(object|typing\.Any)"
+    abi.check_method_docs(cls, {
+        "set_drape": rf"set_drape\(self: [\w.]+, image: {A}, \*, extent: {A} = None, opacity: {A} = 1.0, filter: {A} = 'linear'\) -> None",
+        "clear_drape": r"clear_drape\(self: [\w.]+\) -> None",
+        "drape_info": r"drape_info\(self: [\w.]+\) -> "},
+        cabi_methods=("set_drape", "set_drape_device", "clear_drape", "drape_info", "drape_stage"))
 
 
 def test_argument_rules():

@@ -2,36 +2,26 @@
 the two entry points and the constant, NULL handles are refused, the Python methods exist on both classes of both packages with the
 documented signatures, and the argument rule accepts and refuses what it should."""
 import ctypes
-import os
+import inspect
 import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_drape_anisotropy", "vf_terrain_drape_anisotropy"]
+ENTRY_POINTS = {"vf_terrain_set_drape_anisotropy": ["t", "max_anisotropy"], "vf_terrain_drape_anisotropy": ["t", "max_anisotropy"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and n in cabi._PROTOS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [a.split()[-1].lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_drape_anisotropy"] == ["t", "max_anisotropy"]
-    assert names["vf_terrain_drape_anisotropy"] == ["t", "max_anisotropy"]
+    from vulkan_forge_amd import _drape, cabi
+    abi.check_entry_points(ENTRY_POINTS)
+    src = abi.code()
+    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in ENTRY_POINTS}
     assert re.search(r"vf_terrain \*t, uint32_t max_anisotropy", proto["vf_terrain_set_drape_anisotropy"])
     assert re.search(r"const vf_terrain \*t, uint32_t \*max_anisotropy", proto["vf_terrain_drape_anisotropy"])
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == 2, n
-    assert re.search(r"#define VF_DRAPE_ANISOTROPY_MAX 16\b", src) and cabi.VF_DRAPE_ANISOTROPY_MAX == 16
-    from vulkan_forge_amd import _drape
+    abi.check_defines("DRAPE", (("ANISOTROPY_MAX", "16"),))
+    assert cabi.VF_DRAPE_ANISOTROPY_MAX == 16
     assert _drape.ANISOTROPY_MAX == 16 and _drape.ANISOTROPIES == (1, 2, 4, 8, 16)
 
 
@@ -39,33 +29,26 @@ def test_null_arguments_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
     lib = cabi.load()
     a = ctypes.c_uint32(7)
-    assert lib.vf_terrain_set_drape_anisotropy(None, 4) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_drape_anisotropy", (4,))])
     assert lib.vf_last_error().decode() == "NULL argument"
-    assert lib.vf_terrain_drape_anisotropy(None, ctypes.byref(a)) == cabi.VF_ERR_INVALID and a.value == 7
-    assert lib.vf_terrain_drape_anisotropy(None, None) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_drape_anisotropy", (ctypes.byref(a),)), ("vf_terrain_drape_anisotropy", (None,))])
+    assert a.value == 7
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    A = r"(object|typing\.Any)"
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_drape_anisotropy.__doc__
-        assert re.search(rf"set_drape_anisotropy\(self: [\w.]+, max_anisotropy: {A} = 1\) -> None", doc), doc
-        assert re.search(r"drape_anisotropy\(self: [\w.]+\) -> int", T.drape_anisotropy.__doc__), T.drape_anisotropy.__doc__
     from vulkan_forge_amd import cabi
-    for m in ("set_drape_anisotropy", "drape_anisotropy"):
-        assert callable(getattr(cabi.Terrain, m)), m
-    import inspect
+    A = r"(object|typing\.Any)"
+    abi.check_method_docs(cls, {
+        "set_drape_anisotropy": rf"set_drape_anisotropy\(self: [\w.]+, max_anisotropy: {A} = 1\) -> None",
+        "drape_anisotropy": r"drape_anisotropy\(self: [\w.]+\) -> int"},
+        cabi_methods=("set_drape_anisotropy", "drape_anisotropy"))
     assert str(inspect.signature(cabi.Terrain.set_drape_anisotropy)) == "(self, max_anisotropy=1)"
     assert str(inspect.signature(cabi.Terrain.drape_anisotropy)) == "(self)"
 
 
 def test_argument_rules():
     from vulkan_forge_amd._drape import aniso_params
-    import inspect
     assert str(inspect.signature(aniso_params)) == "(max_anisotropy=1)"
     assert aniso_params() == 1
     for a in (1, 2, 4, 8, 16):

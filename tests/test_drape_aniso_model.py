@@ -2,22 +2,19 @@
 filtering must do: the largest anisotropy 1 is the mip model bit for bit, the plan equals a numpy restatement on hand-worked
 footprints, a constant image gives the isotropic frame, the level of detail never rises, the tap count is the footprint's ratio on the
 surface, the frame comes closer to a supersampled reference, and the cases the GPU tests draw reach every branch."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "drape_aniso_model"))
-import drape_aniso_model as dam  # noqa: E402
-from test_drape_model import VIRIDIS, constant_lut, plain, uniforms  # noqa: E402
-from overlay_scenes import GRID, heights  # noqa: E402
+import support  # noqa: F401  (first: the repository root and the model directories on sys.path)
+import drape_aniso_model as dam
+from support import uniforms
+from test_drape_model import VIRIDIS, constant_lut, plain
+from overlay_scenes import GRID, heights
 
 dmm = dam.dmm
 drm = dmm.drm
-import gbuffer_model as gbm  # noqa: E402
+import gbuffer_model as gbm
 
 f32 = np.float32
 AS = (2, 4, 8, 16)

@@ -2,65 +2,43 @@
 points and constants, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what
 they should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_drape_mips", "vf_terrain_drape_mip_info", "vf_terrain_read_drape_level", "vf_terrain_debug_drape_mip_build"]
+ENTRY_POINTS = {"vf_terrain_set_drape_mips": ["t", "enabled", "bias"],
+                "vf_terrain_drape_mip_info": ["t", "enabled", "levels", "bias", "bytes", "builds"],
+                "vf_terrain_read_drape_level": ["t", "level", "out", "w", "h"],
+                "vf_terrain_debug_drape_mip_build": ["t", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    assert "716 MB" in src                                    # the pyramid's memory at the size limit is stated
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and n in cabi._PROTOS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_drape_mips"] == ["t", "enabled", "bias"]
-    assert names["vf_terrain_drape_mip_info"] == ["t", "enabled", "levels", "bias", "bytes", "builds"]
-    assert names["vf_terrain_read_drape_level"] == ["t", "level", "out", "w", "h"]
-    assert names["vf_terrain_debug_drape_mip_build"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    assert re.search(r"#define VF_DRAPE_MIP_BIAS_MAX 16\.0f", src) and cabi.VF_DRAPE_MIP_BIAS_MAX == 16.0
-    assert re.search(r"#define VF_DRAPE_MIP_LEVELS_MAX 15\b", src) and cabi.VF_DRAPE_MIP_LEVELS_MAX == 15
-    from vulkan_forge_amd import _drape
+    from vulkan_forge_amd import _drape, cabi
+    assert "716 MB" in abi.header_text()                      # the pyramid's memory at the size limit is stated
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("DRAPE_MIP", (("BIAS_MAX", "16.0f"), ("LEVELS_MAX", "15")))
+    assert cabi.VF_DRAPE_MIP_BIAS_MAX == 16.0 and cabi.VF_DRAPE_MIP_LEVELS_MAX == 15
     assert (_drape.MIP_BIAS_MAX, _drape.MIP_LEVELS_MAX) == (16.0, 15)
 
 
 def test_null_arguments_are_refused_without_a_device():
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
     w = ctypes.c_uint32()
-    assert lib.vf_terrain_set_drape_mips(None, 1, 0.0) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_drape_mip_info(None, None, ctypes.byref(w), None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_drape_level(None, 1, None, ctypes.byref(w), ctypes.byref(w)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_drape_mip_build(None, 1, None) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_drape_mips", (1, 0.0)),
+                             ("vf_terrain_drape_mip_info", (None, ctypes.byref(w), None, None, None)),
+                             ("vf_terrain_read_drape_level", (1, None, ctypes.byref(w), ctypes.byref(w))),
+                             ("vf_terrain_debug_drape_mip_build", (1, None))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
     A = r"(object|typing\.Any)"
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_drape_mipmaps.__doc__
-        assert re.search(rf"set_drape_mipmaps\(self: [\w.]+, enabled: {A} = True, \*, bias: {A} = 0.0\) -> None", doc), doc
-        assert re.search(r"drape_mip_info\(self: [\w.]+\) -> ", T.drape_mip_info.__doc__), T.drape_mip_info.__doc__
-        assert re.search(rf"read_drape_level\(self: [\w.]+, level: {A}\) -> ", T.read_drape_level.__doc__), T.read_drape_level.__doc__
-    from vulkan_forge_amd import cabi
-    for m in ("set_drape_mipmaps", "drape_mip_info", "drape_mip_builds", "read_drape_level", "drape_mip_build_stage"):
-        assert callable(getattr(cabi.Terrain, m)), m
+    abi.check_method_docs(cls, {
+        "set_drape_mipmaps": rf"set_drape_mipmaps\(self: [\w.]+, enabled: {A} = True, \*, bias: {A} = 0.0\) -> None",
+        "drape_mip_info": r"drape_mip_info\(self: [\w.]+\) -> ",
+        "read_drape_level": rf"read_drape_level\(self: [\w.]+, level: {A}\) -> "},
+        cabi_methods=("set_drape_mipmaps", "drape_mip_info", "drape_mip_builds", "read_drape_level", "drape_mip_build_stage"))
 
 
 def test_argument_rules():

@@ -2,21 +2,17 @@
 independent numpy restatement bit for bit, a constant image gives the unmipped frame (and the oracle's) at any bias, a magnified
 image gives the unmipped frame, the level of detail is the footprint on the surface, the bias shifts it, the nearest filter picks
 the level stated, and the cases the GPU tests draw reach every branch of the sampler."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "drape_mip_model"))
-import drape_mip_model as dmm  # noqa: E402
-from test_drape_model import VIRIDIS, constant_lut, plain  # noqa: E402
-from overlay_scenes import GRID, heights  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import drape_mip_model as dmm
+from test_drape_model import VIRIDIS, constant_lut, plain
+from overlay_scenes import GRID, heights
 
 drm = dmm.drm
-import gbuffer_model as gbm  # noqa: E402
+import gbuffer_model as gbm
 
 f32 = np.float32
 PYRAMID_SIZES = [(37, 53), (1, 1), (2, 3), (5, 1), (211, 157), (16384, 2), (2, 16384)]
@@ -134,7 +130,7 @@ def test_the_footprint_is_the_surfaces(cam):
     lower neighbour, where the three carry the same visibility id: the piecewise-linear logarithm lies at most 0.0431 below, never
     above; the rest of [-0.06, +0.02] is binary32 rounding of positions and differences."""
     import oracle
-    from test_drape_model import uniforms
+    from support import uniforms
     W, H, grid = 257, 131, 24                                 # (a coarse grid: at the scenes' 1024 no primitive spans two pixels)
     u = uniforms(W, H, cam)
     assert u[36] == 1.0

@@ -3,31 +3,19 @@ gives the oracle's frame bit for bit, a transparent one writes nothing, the near
 position falls in, filtering is premultiplied, the fragment arithmetic with shadows and ambient occlusion equals a numpy restatement,
 and the scenes the GPU tests draw are partly draped."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "gbuffer_model"))
-sys.path.insert(0, os.path.join(HERE, "drape_model"))
-import drape_model as drm  # noqa: E402
-import gbuffer_model as gbm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
+import support
+import drape_model as drm
+import gbuffer_model as gbm
+from overlay_scenes import GRID, heights
 
 abm, shm = drm.abm, drm.shm
 f32 = np.float32
 VIRIDIS = np.load(os.path.join(HERE, "golden", "colormaps_rgba8.npz"))["viridis"]
-
-
-def uniforms(W, H, cam, sun=None):
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS[cam]), f32).reshape(44)
-    if sun is not None:
-        u[32:35] = sun
-    return u
 
 
 _plain = {}
@@ -38,7 +26,7 @@ def plain(W, H, cam, lut=VIRIDIS, mode=0, h=None, sun=None):
     import oracle
     key = (W, H, cam, lut.tobytes(), mode, None if h is None else h.tobytes(), None if sun is None else tuple(sun))
     if key not in _plain:
-        u = uniforms(W, H, cam, sun)
+        u = support.uniforms(W, H, cam, sun=sun)
         rgba, vis = oracle.render_terrain(u, W, H, GRID, heights() if h is None else h, lut, want_vis=True, nthreads=8,
                                           shade_mode=oracle.SHADE_SPEC_T32 if mode else oracle.SHADE_REFERENCE)
         _plain[key] = (u, rgba.reshape(H, W, 4), vis)

@@ -2,96 +2,64 @@
 documents them, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what they
 should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_flood", "vf_terrain_clear_flood", "vf_terrain_read_flood_field", "vf_terrain_flood_field_device", "vf_terrain_flood_info",
-         "vf_terrain_read_flood_seeds", "vf_terrain_debug_flood_scans", "vf_terrain_debug_flood_group", "vf_terrain_debug_flood_stage"]
+ENTRY_POINTS = {"vf_terrain_set_flood": ["t", "enable", "level", "mode", "seeds_xz", "count", "shallow_rgba", "deep_rgba", "depth_full"],
+                "vf_terrain_clear_flood": ["t"],
+                "vf_terrain_read_flood_field": ["t", "depth"],
+                "vf_terrain_flood_field_device": ["t", "dev_depth", "stream"],
+                "vf_terrain_flood_info": ["t", "out"],
+                "vf_terrain_read_flood_seeds": ["t", "vertices"],
+                "vf_terrain_debug_flood_scans": ["t", "count"],
+                "vf_terrain_debug_flood_group": ["t", "group"],
+                "vf_terrain_debug_flood_stage": ["t", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
     from vulkan_forge_amd import cabi
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_flood"] == ["t", "enable", "level", "mode", "seeds_xz", "count", "shallow_rgba", "deep_rgba", "depth_full"]
-    assert names["vf_terrain_clear_flood"] == ["t"]
-    assert names["vf_terrain_read_flood_field"] == ["t", "depth"]
-    assert names["vf_terrain_flood_field_device"] == ["t", "dev_depth", "stream"]
-    assert names["vf_terrain_flood_info"] == ["t", "out"]
-    assert names["vf_terrain_read_flood_seeds"] == ["t", "vertices"]
-    assert names["vf_terrain_debug_flood_scans"] == ["t", "count"]
-    assert names["vf_terrain_debug_flood_group"] == ["t", "group"]
-    assert names["vf_terrain_debug_flood_stage"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    for k, v in (("EVERYWHERE", "0"), ("EDGES", "1"), ("SEEDS", "2"), ("MAX_SEEDS", "65535u"), ("SHALLOW_RGBA", "0x80E0B060u"),
-                 ("DEEP_RGBA", "0xE0A04010u"), ("DEPTH_FULL", "0.1f")):
-        assert re.search(rf"#define VF_FLOOD_{k} {v}(\s|$)", src), k
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("FLOOD", (("EVERYWHERE", "0"), ("EDGES", "1"), ("SEEDS", "2"), ("MAX_SEEDS", "65535u"), ("SHALLOW_RGBA", "0x80E0B060u"),
+                                ("DEEP_RGBA", "0xE0A04010u"), ("DEPTH_FULL", "0.1f")))
     assert 0x80E0B060 == 96 | 176 << 8 | 224 << 16 | 128 << 24 and 0xE0A04010 == 16 | 64 << 8 | 160 << 16 | 224 << 24
-    # the struct the info call fills, field for field
-    body = re.search(r"typedef struct vf_flood_info \{(.*?)\} vf_flood_info;", src, flags=re.S).group(1)
-    fields = [re.sub(r"\[\d+\]", "", f.strip()) for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert fields == [f for f, _ in cabi.FloodInfo._fields_]
-    assert ctypes.sizeof(cabi.FloodInfo) == 4 * 6 + 8 + 4 * 5
+    abi.check_info_struct("vf_flood_info", cabi.FloodInfo, 4 * 6 + 8 + 4 * 5)
 
 
 def test_the_header_documents_the_calls():
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    block = text[text.index("flood analysis: what is under water at a level"):]
-    for n in NAMES[:6]:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4s", "VF_ERR_INVALID", "whether or not the flood is enabled", "NULL: the context's", "1 <= count <= 65535",
-                 "4-connected", "least fixpoint", "before exaggeration", "vf_terrain_add_contours", "Whole-frame handles only",
-                 "survives height uploads", "allocates and launches nothing"):
-        assert word in block, word
+    abi.check_header_documents("flood analysis: what is under water at a level", list(ENTRY_POINTS)[:6],
+                               ("DESIGN.md 4s", "VF_ERR_INVALID", "whether or not the flood is enabled", "NULL: the context's", "1 <= count <= 65535",
+                                "4-connected", "least fixpoint", "before exaggeration", "vf_terrain_add_contours", "Whole-frame handles only",
+                                "survives height uploads", "allocates and launches nothing"))
 
 
 def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    count = ctypes.c_uint32()
-    info = cabi.FloodInfo()
     xz, col = np.zeros((2, 2), np.float32), (ctypes.c_uint8 * 4)(1, 2, 3, 4)
-    assert lib.vf_terrain_set_flood(None, 1, 0.0, 2, xz.ctypes.data, 2, col, col, 0.1) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_clear_flood(None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_flood_field(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_flood_field_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_flood_info(None, ctypes.byref(info)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_flood_seeds(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_flood_scans(None, ctypes.byref(count)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_flood_group(None, 4) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_flood_stage(None, 1, (ctypes.c_float * 2)()) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_flood", (1, 0.0, 2, xz.ctypes.data, 2, col, col, 0.1)),
+                             ("vf_terrain_clear_flood", ()),
+                             ("vf_terrain_read_flood_field", (out.ctypes.data,)),
+                             ("vf_terrain_flood_field_device", (None, None)),
+                             ("vf_terrain_flood_info", (ctypes.byref(cabi.FloodInfo()),)),
+                             ("vf_terrain_read_flood_seeds", (out.ctypes.data,)),
+                             ("vf_terrain_debug_flood_scans", (ctypes.byref(ctypes.c_uint32()),)),
+                             ("vf_terrain_debug_flood_group", (4,)),
+                             ("vf_terrain_debug_flood_stage", (1, (ctypes.c_float * 2)()))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    from vulkan_forge_amd import cabi
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_flood.__doc__
-        assert re.search(r"set_flood\(self: [\w.]+, level: object, seeds: object = None, \*, enabled: object = True, "
-                         r"shallow_rgba: object = \(96, 176, 224, 128\), deep_rgba: object = \(16, 64, 160, 224\), "
-                         r"depth_full: object = 0.100\d*\) -> None", doc), doc
-        assert re.search(r"clear_flood\(self: [\w.]+\) -> None", T.clear_flood.__doc__)
-        assert re.search(r"flood_field\(self: [\w.]+\) -> numpy", T.flood_field.__doc__)
-        assert re.search(r"flood_info\(self: [\w.]+\) -> object", T.flood_info.__doc__)
-    for name in ("set_flood", "clear_flood", "flood_field", "flood_field_device", "flood_info", "flood_scans", "flood_group"):
-        assert callable(getattr(cabi.Terrain, name)), name
+    abi.check_method_docs(cls, {
+        "set_flood": r"set_flood\(self: [\w.]+, level: object, seeds: object = None, \*, enabled: object = True, "
+                     r"shallow_rgba: object = \(96, 176, 224, 128\), deep_rgba: object = \(16, 64, 160, 224\), "
+                     r"depth_full: object = 0.100\d*\) -> None",
+        "clear_flood": r"clear_flood\(self: [\w.]+\) -> None",
+        "flood_field": r"flood_field\(self: [\w.]+\) -> numpy",
+        "flood_info": r"flood_info\(self: [\w.]+\) -> object"},
+        cabi_methods=("set_flood", "clear_flood", "flood_field", "flood_field_device", "flood_info", "flood_scans", "flood_group"))
 
 
 def test_argument_rules():

@@ -4,32 +4,16 @@ seeds; non-finite vertices block; the eight symmetries of the square; `edges` an
 passes of the kernels, emulated in numpy, equal the search; a hand-worked tinted pixel; and the inputs of the GPU tests
 (tests/test_gpu_flood.py) meet the conditions that keep those comparisons from being vacuous."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "flood_model"))
-import flood_model as fdm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
+from support import bits, smooth
+import flood_model as fdm
+from overlay_scenes import CAMERAS, GRID, heights
 
 cm = fdm.cm
-
-
-def smooth(n, seed=1):
-    rng = np.random.default_rng(seed)
-    x = np.linspace(0, 1, n, dtype=np.float64)
-    X, Z = np.meshgrid(x, x)
-    h = sum(rng.normal() * 0.2 / f * np.sin(2 * np.pi * f * (X * np.cos(a) + Z * np.sin(a)) + p)
-            for f, a, p in zip((1, 2, 3, 5), rng.uniform(0, 6.3, 4), rng.uniform(0, 6.3, 4)))
-    return h.astype(np.float32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def vertices(mask):

@@ -1,53 +1,33 @@
 """Geometry buffers without a device: the header, cabi.SYMBOLS and the library agree on the new entry points, the
 Python methods exist on both classes with the documented signatures, and the argument rules refuse what they should."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_gbuffer_device", "vf_terrain_read_gbuffer", "vf_terrain_pick"]
+ENTRY_POINTS = {"vf_terrain_gbuffer_device": ["t", "dev_depth", "dev_position", "dev_normal", "dev_primitive", "stream"],
+                "vf_terrain_read_gbuffer": ["t", "depth", "position", "normal", "primitive"],
+                "vf_terrain_pick": ["t", "pixels_xy", "n", "out8"],
+                "vf_terrain_debug_gbuffer_stage": ["t", "planes", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES + ["vf_terrain_debug_gbuffer_stage"]:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    assert [a.split()[-1].lstrip("*") for a in proto["vf_terrain_gbuffer_device"].split(",")] == ["t", "dev_depth", "dev_position", "dev_normal", "dev_primitive", "stream"]
-    assert [a.split()[-1].lstrip("*") for a in proto["vf_terrain_read_gbuffer"].split(",")] == ["t", "depth", "position", "normal", "primitive"]
-    assert [a.split()[-1].lstrip("*") for a in proto["vf_terrain_pick"].split(",")] == ["t", "pixels_xy", "n", "out8"]
-    loaded = cabi.load()
-    assert len(loaded.vf_terrain_gbuffer_device.argtypes) == 6 and len(loaded.vf_terrain_read_gbuffer.argtypes) == 5
-    assert len(loaded.vf_terrain_pick.argtypes) == 4
+    abi.check_entry_points(ENTRY_POINTS)
 
 
 def test_null_handles_are_refused_without_a_device():
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(8, np.float32)
-    assert lib.vf_terrain_read_gbuffer(None, out.ctypes.data, None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_gbuffer_device(None, None, None, None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_pick(None, None, 0, None) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_read_gbuffer", (out.ctypes.data, None, None, None)),
+                             ("vf_terrain_gbuffer_device", (None, None, None, None, None)),
+                             ("vf_terrain_pick", (None, 0, None))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.render_gbuffer.__doc__
-        assert "planes: object = ('depth', 'position', 'normal', 'primitive')" in doc and "-> dict" in doc, doc
-        assert re.search(r"render_depth\(self: [\w.]+\) -> numpy", T.render_depth.__doc__), T.render_depth.__doc__
-        assert re.search(r"pick\(self: [\w.]+, pixels: object\) -> dict", T.pick.__doc__), T.pick.__doc__
+    abi.check_method_docs(cls, {
+        "render_gbuffer": r"planes: object = \('depth', 'position', 'normal', 'primitive'\)(.|\n)*-> dict",
+        "render_depth": r"render_depth\(self: [\w.]+\) -> numpy",
+        "pick": r"pick\(self: [\w.]+, pixels: object\) -> dict"})
 
 
 def test_plane_rules():

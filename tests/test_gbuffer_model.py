@@ -6,17 +6,13 @@ item 4) but lies on the unsnapped one in the world, so projecting it back misses
 the triangle's depth range.  The bounds below are twice the largest errors of the model over the six fixed scenes of this file
 (measured: 0.002666 px, relative w error 3.83e-7; DESIGN.md 4f has the table); the factor two is room for a later scene.
 """
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "gbuffer_model"))
-import gbuffer_model as gbm  # noqa: E402
-import oracle  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import gbuffer_model as gbm
+import oracle
 
 ocm, om = gbm.ocm, gbm.om
 GRID = 256

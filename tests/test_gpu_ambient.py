@@ -2,59 +2,19 @@
 that are no multiple of the tile, with reaches that cross none, one and two tile boundaries, for the default directions, an irregular
 list, a single direction and a row of NaN heights, through both entry points; the frame over three cameras, two sizes, both shade
 modes and both precisions, alone, with cast shadows and under overlays; the field is cached; and nothing else moves."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-sys.path.insert(0, os.path.join(HERE, "ambient_model"))
-import ambient_model as abm  # noqa: E402
-import shadow_model as shm  # noqa: E402
-from ambient_model import FIELD_CASES, IRREGULAR, SCENE_PARAMS, SCENE_SUN_DEG, scene_directions, scene_heights  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
+import support
+import ambient_model as abm
+import shadow_model as shm
+from ambient_model import FIELD_CASES, IRREGULAR, SCENE_PARAMS, SCENE_SUN_DEG, scene_directions, scene_heights
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import assert_field, bits, terrain, uniforms, vf, viridis  # noqa: F401
 
 SHADOW_PARAMS = abm.SCENE_SHADOWS
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def uniforms(W, H, cam="default", sun=None, exag=None):
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS[cam]), np.float32).reshape(44)
-    if sun is not None:
-        u[32:35] = sun
-    if exag is not None:
-        u[38] = exag
-    return u
-
-
-def terrain(W, H, grid, h, lut=None):
-    from vulkan_forge_amd import cabi
-    t = cabi.Terrain(W, H, grid, np.zeros(1024, np.uint8) if lut is None else lut)
-    t.set_height(h)
-    return t
-
-
-def assert_field(got, want, what):
-    d = bits(got) != bits(want)
-    assert not d.any(), f"{what}: {int(d.sum())} vertices differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:4]} against {want[d][:4]}"
 
 
 @pytest.mark.parametrize("grid,exag,reach,D", FIELD_CASES)
@@ -94,13 +54,7 @@ def test_field_for_an_irregular_direction_list_and_a_row_of_nan_heights():
 
 
 def test_field_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "ambient_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "AMBIENT TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
+    support.run_check("ambient_torch_check.py", "AMBIENT TORCH OK")
 
 
 def model_frame(u, W, H, h, mode, shadows=False):
@@ -114,10 +68,8 @@ def model_frame(u, W, H, h, mode, shadows=False):
 
 
 def assert_frame(got, want, what, where=None):
-    d = (got != want).any(axis=2)
-    if where is not None:
-        d &= where
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}"
+    # byte for byte, at the pixels of the mask `where` if one is given
+    support.assert_frame(got if where is None else np.where(where[..., None], got, want), want, what)
 
 
 @pytest.mark.parametrize("mode", ["reference", "spec_t32"])

@@ -24,6 +24,7 @@ import pytest
 import band_mask_model as bm
 import plan_model as pm
 from conftest import DEFAULT_CAMERA, FILL_CAMERA, heightmap
+from support import cabi  # noqa: F401
 from test_gpu_parity import CLIP_CAM, EXACT, FAST, RGBA_TOL
 
 pytestmark = pytest.mark.gpu
@@ -34,13 +35,6 @@ SHARDED = dict(W=200, H=320, G=65, cam=DEFAULT_CAMERA, exag=1.0, seed=5)
 INSIDE = dict(W=320, H=240, G=32, cam=CLIP_CAM, exag=1.0, seed=6)
 STALE = dict(W=320, H=256, G=64)
 CAM_B = ((-2.4, 1.1, 2.9), (0.1, 0.0, -0.2), (0.0, 1.0, 0.0), 55.0, 0.1, 100.0)
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as C
-    C.load()
-    return C
 
 
 def uniforms(oracle, W, H, cam, exag=1.0, sun=None):

@@ -6,18 +6,15 @@ occluding point layer refused on a supersampled object was never made.  Frame 64
 the fills -- the kernels have their own tests; what varies here is the route to them."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-from overlay_scenes import CAMERAS, heights  # noqa: E402
+import support
+from overlay_scenes import CAMERAS, heights
+from support import bits
 
 W, H, GRID = 64, 48, 17
 SHADOWS = dict(strength=0.8, softness=0.05, bias=0.01)
@@ -49,10 +46,6 @@ UNSET = {
     "flood_field": "no flood set (vf_terrain_set_flood)",
     "spill_field": "no spill set (vf_terrain_set_spill)",
 }
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def set_analyses(x):
@@ -126,8 +119,7 @@ def torch_check():
 
 
 def test_the_field_device_calls_return_those_bits_in_torch_tensors():
-    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "BINDING SURFACES TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check(os.path.basename(__file__), "BINDING SURFACES TORCH OK")
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])

@@ -4,28 +4,18 @@ texel, vertices and plateaus exactly on a level, grids 100 and 257; the counts a
 a snapshot that follows the exaggeration; over-budget requests and sharded handles are refused with nothing changed."""
 import ctypes
 import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "contour_model"))
-import contour_model as cm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights, scene  # noqa: E402
+import support
+import contour_model as cm
+from overlay_scenes import CAMERAS, GRID, heights, scene
+from support import vf  # noqa: F401
 
 ocm = cm.ocm
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
 
 
 def oracle_vis(u, W, H, h, grid):
@@ -126,7 +116,7 @@ def test_small_grids_a_nan_texel_and_levels_through_vertices(vf, grid):
 
 def terrain(W, H, grid, h, u):
     from vulkan_forge_amd import cabi
-    lut = np.load(os.path.join(HERE, "golden", "colormaps_rgba8.npz"))["viridis"]
+    lut = np.load(os.path.join(support.HERE, "golden", "colormaps_rgba8.npz"))["viridis"]
     t = cabi.Terrain(W, H, grid, lut)
     t.set_height(h)
     t.set_uniforms(u)

@@ -4,28 +4,18 @@ the chunks and one larger than the grid, at every batch size; over non-finite he
 over two cameras, two sizes and both precisions with either colour alone and both; over shadows, ambient occlusion, a drape and under
 the single observer's tint; under overlays; and nothing else moves -- the frame with the feature off or cleared, geometry buffers,
 visibility, the single observer's viewshed, the scan counter of a resting scene, the refusals."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-sys.path.insert(0, os.path.join(HERE, "viewshed_model"))
-sys.path.insert(0, os.path.join(HERE, "cumulative_viewshed_model"))
-import cumulative_viewshed_model as cvm  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
-from overlay_scenes import CAMERAS, apply, heights  # noqa: E402
-from test_gpu_viewshed import OBSERVERS, PARAMS, assert_field, assert_frame, bits, terrain, uniforms, viridis  # noqa: E402
-from viewshed_model import SCENE_OBSERVER, SCENE_PARAMS  # noqa: E402
+import support
+import cumulative_viewshed_model as cvm
+import viewshed_model as vsm
+from overlay_scenes import CAMERAS, apply, heights
+from support import assert_field, assert_frame, bits, terrain, uniforms, vf, viridis  # noqa: F401
+from test_gpu_viewshed import OBSERVERS, PARAMS
+from viewshed_model import SCENE_OBSERVER, SCENE_PARAMS
 
 RED, GREEN, BLUE = (255, 0, 0, 128), (64, 255, 96, 160), (0, 60, 255, 200)
 FRAME_GRID = 257
@@ -34,20 +24,14 @@ FRAME_OBSERVERS = np.random.default_rng(12).uniform(-1.4, 1.4, (12, 2)).astype(n
 FRAME_N = len(FRAME_OBSERVERS)
 
 
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
 _counts = {}
 
 
 def frame_count(u, h):
     """the model's count field of the frames' scene (it depends on the spacing and the exaggeration alone: computed once)"""
-    key = (float(u[36]), float(u[38]), h.tobytes()[:64], h.shape)
+    key = (float(u[36]), float(u[38]), support.digest(h))
     if key not in _counts:
-        _counts[key] = cvm.field(u, h, FRAME_GRID, FRAME_OBSERVERS, **SCENE_PARAMS)[0]
+        _counts[key] = support.frozen(cvm.field(u, h, FRAME_GRID, FRAME_OBSERVERS, **SCENE_PARAMS)[0])
     return _counts[key]
 
 
@@ -58,11 +42,6 @@ def frame_scene(vf, W, H, h, cam="default", precision=None):
         s.set_shade_precision(precision)
     s.set_camera_look_at(*CAMERAS[cam])
     return s
-
-
-def oracle_frame(u, W, H, h):
-    import oracle
-    return oracle.render_terrain(u, W, H, FRAME_GRID, h, viridis(), want_vis=True, nthreads=8, shade_mode=oracle.SHADE_REFERENCE)
 
 
 # ---- the field ----
@@ -166,8 +145,7 @@ def test_non_finite_heights_and_an_observer_on_a_hole():
 
 
 def test_field_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "cumulative_viewshed_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "CUMULATIVE VIEWSHED TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("cumulative_viewshed_torch_check.py", "CUMULATIVE VIEWSHED TORCH OK")
 
 
 # ---- frames ----
@@ -185,7 +163,7 @@ def test_frames_equal_the_model_in_both_precisions(vf, cam, size):
         s = frame_scene(vf, W, H, h, cam, precision)
         plain = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-        rgba, vis = oracle_frame(u, W, H, h)
+        rgba, vis = support.oracle_frame(u, W, H, FRAME_GRID, h)
         if precision == "exact":
             assert np.array_equal(plain, rgba.reshape(H, W, 4))                # (the exact frame is the oracle's)
         cnt = frame_count(u, h)
@@ -225,7 +203,7 @@ def test_the_tint_lies_over_the_relight_passes_and_under_the_single_observers(vf
             s.set_viewshed(SCENE_OBSERVER, **SCENE_PARAMS, **single)
         frames[tinted] = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-    _, vis = oracle_frame(u, W, H, h)
+    _, vis = support.oracle_frame(u, W, H, FRAME_GRID, h)
     plain = frame_scene(vf, W, H, h, "default", "exact").render_rgba()
     assert (frames["none"] != plain).any()
     under, _ = cvm.frame(frames["none"], vis, u, h, FRAME_GRID, frame_count(u, h), FRAME_N, high_rgba=BLUE, low_rgba=RED)
@@ -253,7 +231,7 @@ def test_overlays_composite_over_the_tinted_frame(vf):
     calls = [("add_points", (pts,), dict(size_px=4.0, rgba=(255, 0, 0, 200), drape=True, occlude=True)),
              ("add_lines", (paths,), dict(width_px=2.0, rgba=(0, 255, 0, 200), drape=True))]
     L = apply(vf, s, calls, ocm.Layers())
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, FRAME_GRID, h)
     base, _ = cvm.frame(rgba, vis, u, h, FRAME_GRID, frame_count(u, h), FRAME_N, high_rgba=GREEN, low_rgba=RED)
     want = ocm.composite(base, vis, u, h, FRAME_GRID, L)
     got = s.render_rgba()

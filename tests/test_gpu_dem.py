@@ -11,7 +11,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-import vulkan_forge as vf          # noqa: E402
+import vulkan_forge as vf
 
 
 def ramp(dtype, shape):

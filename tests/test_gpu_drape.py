@@ -2,69 +2,31 @@
 shade modes, both precisions, both filters, RGB and RGBA, image sizes from one texel to the limit strips, full, interior and
 overhanging extents, two opacities, with cast shadows and ambient occlusion, under overlays, after one image replaces another;
 and nothing else moves."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-sys.path.insert(0, os.path.join(HERE, "drape_model"))
-import drape_model as drm  # noqa: E402
-import occlusion_model as ocm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
+import support
+import drape_model as drm
+import occlusion_model as ocm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import bits, vf, viridis  # noqa: F401
 
 abm, shm = drm.abm, drm.shm
 SIZES = [(257, 131), (640, 363)]                              # neither width is a multiple of 32, neither height one of 8
 EXTENTS = {"full": None, "interior": (-0.7, -0.5, 0.9, 0.8), "overhanging": drm.EXTENT}
 
 
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-_oracle = {}
-
-
-def oracle_frame(u, W, H, h, mode):
-    """the oracle's exact frame and visibility of a case, computed once"""
-    import oracle
-    key = (u.tobytes(), W, H, h.tobytes(), mode)
-    if key not in _oracle:
-        rgba, vis = oracle.render_terrain(u, W, H, GRID, h, viridis(), want_vis=True, nthreads=8,
-                                          shade_mode=oracle.SHADE_SPEC_T32 if mode == "spec_t32" else oracle.SHADE_REFERENCE)
-        _oracle[key] = (rgba.reshape(H, W, 4), vis)
-    return _oracle[key]
-
-
 def model(u, W, H, h, mode, img, **kw):
-    rgba, vis = oracle_frame(u, W, H, h, mode)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
     frame, again = drm.frame(rgba, vis, u, h, GRID, viridis(), img, shade_mode=1 if mode == "spec_t32" else 0, **kw)
     return frame, again, vis
 
 
 def assert_frame(got, want, what, where=None):
-    d = (got != want).any(axis=2)
-    if where is not None:
-        d &= where
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}"
+    # byte for byte, at the pixels of the mask `where` if one is given
+    support.assert_frame(got if where is None else np.where(where[..., None], got, want), want, what)
 
 
 def assert_draped(s, plain, precision, want, what):
@@ -154,7 +116,7 @@ def test_with_shadows_and_ambient_occlusion(vf, cam, mode, features):
         if want is None:
             lit = shm.field(u, h, GRID, **abm.SCENE_SHADOWS) if shadows else None
             sky = abm.field(u, h, GRID, abm.scene_directions(), abm.SCENE_PARAMS["reach"]) if ambient else None
-            rgba, vis = oracle_frame(u, W, H, h, mode)
+            rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
             # the drape goes over the frame the shadow / ambient pass left: its model first
             base, _ = abm.frame(rgba, vis, u, h, GRID, viridis(), sky if ambient else np.ones((GRID, GRID), np.float32), strength, lit=lit,
                                 shade_mode=1 if mode == "spec_t32" else 0)
@@ -244,7 +206,6 @@ def test_nothing_else_moves(vf):
 
 def test_refusals_change_nothing(vf):
     from vulkan_forge_amd import cabi
-    import oracle
     W, H = 128, 128
     h = heights(2, (32, 32))
     img = drm.image()
@@ -254,7 +215,7 @@ def test_refusals_change_nothing(vf):
         s.set_drape(img)
     s.set_shard(0, 1, 64)
     assert s.drape_info() is None
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    u = support.uniforms(W, H)
     t = cabi.Terrain(W, H, 32, viridis())
     t.set_height(h)
     t.set_uniforms(u)
@@ -305,9 +266,8 @@ def test_the_stage_calls_hand_the_scan_counters_back():
     """drape_stage brings the shadow and sky-view fields up to date itself, ambient_stage the shadow field: diagnostic launches are
     not the handle's, whichever call makes them"""
     from vulkan_forge_amd import cabi
-    import oracle
     W, H = 257, 131
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    u = support.uniforms(W, H)
     u[32:35] = shm.sun_vector(*abm.SCENE_SUN_DEG)
     t = cabi.Terrain(W, H, 32, viridis())
     t.set_height(heights(2, (32, 32)))
@@ -330,5 +290,4 @@ def test_the_stage_calls_hand_the_scan_counters_back():
 
 
 def test_the_image_from_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "drape_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DRAPE TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("drape_torch_check.py", "DRAPE TORCH OK")

@@ -3,24 +3,19 @@ bit: frames for three cameras, two sizes, every anisotropy, both shade modes, bo
 opacities, image sizes from one texel to the limit strips, with cast shadows and ambient occlusion, under overlays, through the
 clipper, on a supersampled handle; anisotropy 1 and mipmaps off are the frames they were; the setting is the handle's, builds no
 pyramid and moves nothing else."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-sys.path.insert(0, os.path.join(HERE, "drape_aniso_model"))
-import drape_aniso_model as dam  # noqa: E402
-import occlusion_model as ocm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
-from test_gpu_drape import assert_draped, assert_frame, bits, oracle_frame, overlay_calls, viridis  # noqa: E402
-from test_gpu_drape_mips import sized_image, sweep_case  # noqa: E402
+import support
+import drape_aniso_model as dam
+import occlusion_model as ocm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import bits, vf, viridis  # noqa: F401
+from test_gpu_drape import assert_draped, assert_frame, overlay_calls
+from test_gpu_drape_mips import sized_image, sweep_case
 
 dmm = dam.dmm
 drm = dmm.drm
@@ -28,20 +23,14 @@ abm, shm = drm.abm, drm.shm
 AS = (2, 4, 8, 16)
 
 
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
 def model(u, W, H, h, mode, img, A, **kw):
-    rgba, vis = oracle_frame(u, W, H, h, mode)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
     frame, again = dam.frame(rgba, vis, u, h, GRID, viridis(), img, shade_mode=1 if mode == "spec_t32" else 0, max_anisotropy=A, **kw)
     return frame, again, vis
 
 
 def mip_model(u, W, H, h, mode, img, **kw):
-    rgba, vis = oracle_frame(u, W, H, h, mode)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
     frame, again = dmm.frame(rgba, vis, u, h, GRID, viridis(), img, shade_mode=1 if mode == "spec_t32" else 0, **kw)
     return frame, again, vis
 
@@ -142,7 +131,7 @@ def test_with_shadows_and_ambient_occlusion(vf, cam, mode, features):
         if want is None:
             lit = shm.field(u, h, GRID, **abm.SCENE_SHADOWS) if shadows else None
             sky = abm.field(u, h, GRID, abm.scene_directions(), abm.SCENE_PARAMS["reach"]) if ambient else None
-            rgba, vis = oracle_frame(u, W, H, h, mode)
+            rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
             base, _ = abm.frame(rgba, vis, u, h, GRID, viridis(), sky if ambient else np.ones((GRID, GRID), np.float32), strength, lit=lit,
                                 shade_mode=1 if mode == "spec_t32" else 0)
             frame, again, smp = dam.frame(base, vis, u, h, GRID, viridis(), dmm.case_image(), lit=lit, sky=sky, strength=strength, bias=0.5,
@@ -178,7 +167,7 @@ def test_the_clipped_instantiation_runs(vf):
     h = heights()
     s = aniso_scene(vf, W, H, h, "near", "exact", 8, bias=0.25)
     u = s.debug_uniforms_f32()
-    rgba, vis = oracle_frame(u, W, H, h, "reference")
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, "reference")
     cut = dam.clipped_mask(vis, u, h, GRID)
     assert cut.any()
     for filt in ("linear", "nearest"):
@@ -263,11 +252,10 @@ def test_nothing_else_moves(vf):
 
 def test_refusals_change_nothing(vf):
     from vulkan_forge_amd import cabi
-    import oracle
     W, H = 128, 128
     h = heights(2, (32, 32))
     img = dmm.case_image()
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    u = support.uniforms(W, H)
     t = cabi.Terrain(W, H, 32, viridis())
     t.set_height(h)
     t.set_uniforms(u)
@@ -310,7 +298,7 @@ def test_through_the_c_abi_and_the_spike(vf):
     tex = (rng.random((23, 31), dtype=np.float32) * 0.5 - 0.25).astype(np.float32)
     img = dmm.case_image()
     kw = dict(extent=(-2.0, -9.0, 2.2, 9.5), opacity=0.8, filter="linear")
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    u = support.uniforms(W, H)
     rgba, vis = oracle.render_terrain(u, W, H, grid, tex, viridis(), want_vis=True, nthreads=8, shade_mode=oracle.SHADE_REFERENCE)
     rgba = rgba.reshape(H, W, 4)
     t = cabi.Terrain(W, H, grid, viridis())

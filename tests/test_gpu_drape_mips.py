@@ -2,24 +2,17 @@
 the pyramid at every level, frames for three cameras, two sizes, both shade modes, both precisions, both filters, three biases,
 two opacities, image sizes from one texel to the limit strips, with cast shadows and ambient occlusion, under overlays, through the
 clipper; mipmaps at bias -16 and mipmaps off are the unmipped drape; the pyramid is built once per image; nothing else moves."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-sys.path.insert(0, os.path.join(HERE, "drape_mip_model"))
-import drape_mip_model as dmm  # noqa: E402
-import occlusion_model as ocm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
-from test_gpu_drape import assert_draped, assert_frame, bits, oracle_frame, overlay_calls, viridis  # noqa: E402
+import support
+import drape_mip_model as dmm
+import occlusion_model as ocm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import bits, vf, viridis  # noqa: F401
+from test_gpu_drape import assert_draped, assert_frame, overlay_calls
 
 drm = dmm.drm
 abm, shm = drm.abm, drm.shm
@@ -27,20 +20,14 @@ SIZES = [(257, 131), (640, 363)]
 PYRAMID_SIZES = [(37, 53), (1, 1), (2, 3), (5, 1), (211, 157), (16384, 2), (2, 16384), dmm.CASE_SIZE]
 
 
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
 def model(u, W, H, h, mode, img, **kw):
-    rgba, vis = oracle_frame(u, W, H, h, mode)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
     frame, again = dmm.frame(rgba, vis, u, h, GRID, viridis(), img, shade_mode=1 if mode == "spec_t32" else 0, **kw)
     return frame, again, vis
 
 
 def flat_model(u, W, H, h, mode, img, **kw):
-    rgba, vis = oracle_frame(u, W, H, h, mode)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
     frame, again = drm.frame(rgba, vis, u, h, GRID, viridis(), img, shade_mode=1 if mode == "spec_t32" else 0, **kw)
     return frame, again, vis
 
@@ -152,7 +139,7 @@ def test_with_shadows_and_ambient_occlusion(vf, cam, mode, features):
         if want is None:
             lit = shm.field(u, h, GRID, **abm.SCENE_SHADOWS) if shadows else None
             sky = abm.field(u, h, GRID, abm.scene_directions(), abm.SCENE_PARAMS["reach"]) if ambient else None
-            rgba, vis = oracle_frame(u, W, H, h, mode)
+            rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
             base, _ = abm.frame(rgba, vis, u, h, GRID, viridis(), sky if ambient else np.ones((GRID, GRID), np.float32), strength, lit=lit,
                                 shade_mode=1 if mode == "spec_t32" else 0)
             frame, again = dmm.frame(base, vis, u, h, GRID, viridis(), dmm.case_image(), lit=lit, sky=sky, strength=strength, bias=0.5,
@@ -186,7 +173,7 @@ def test_the_clipped_instantiation_runs(vf):
     h = heights()
     s = scene(vf, W, H, h, "near", "exact")
     u = s.debug_uniforms_f32()
-    rgba, vis = oracle_frame(u, W, H, h, "reference")
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h, "reference")
     assert dmm.clipped_pixels(vis, u, h, GRID) > 0
     s.set_drape_mipmaps(True, bias=0.25)
     for filt in ("linear", "nearest"):
@@ -267,11 +254,10 @@ def test_nothing_else_moves(vf):
 
 def test_refusals_change_nothing(vf):
     from vulkan_forge_amd import cabi
-    import oracle
     W, H = 128, 128
     h = heights(2, (32, 32))
     img = drm.image()
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
+    u = support.uniforms(W, H)
     t = cabi.Terrain(W, H, 32, viridis())
     t.set_height(h)
     t.set_uniforms(u)
@@ -315,8 +301,7 @@ def test_refusals_change_nothing(vf):
 
 
 def test_the_image_from_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "drape_mip_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "DRAPE MIP TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("drape_mip_torch_check.py", "DRAPE MIP TORCH OK")
 
 
 def sweep_case(k):

@@ -4,28 +4,21 @@ heights; five for the exaggeration, which the flood and the spill (fields in uni
 move inside their vertices' cells, and none for a diagnostic call; a forgotten viewshed observer does not restart its counter.  Every
 field is held to its CPU model bit for bit after every change.  Grid 130: the scans' 64-step chunks carry across a boundary, and the
 flood and the spill run 3 x 3 tiles."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _model in ("overlay_model", "polygon_model", "occlusion_model", "shadow_model", "ambient_model", "viewshed_model", "cumulative_viewshed_model",
-               "sun_exposure_model", "contour_model", "flood_model", "spill_model"):
-    sys.path.insert(0, os.path.join(HERE, _model))
-import ambient_model as abm  # noqa: E402
-import cumulative_viewshed_model as cvm  # noqa: E402
-import flood_model as fdm  # noqa: E402
-import shadow_model as shm  # noqa: E402
-import spill_model as spm  # noqa: E402
-import sun_exposure_model as sem  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
-from overlay_scenes import heights  # noqa: E402
-from test_gpu_viewshed import assert_field, terrain, uniforms, viridis  # noqa: E402
+from support import assert_field, terrain, uniforms, viridis
+import ambient_model as abm
+import cumulative_viewshed_model as cvm
+import flood_model as fdm
+import shadow_model as shm
+import spill_model as spm
+import sun_exposure_model as sem
+import viewshed_model as vsm
+from overlay_scenes import heights
 
 W, H, GRID = 96, 64, 130
 SHADOWS = dict(strength=0.8, softness=0.05, bias=0.01)

@@ -3,19 +3,16 @@ the tile kernel, pinned from outside: clear_* leaves the scan counter and the fo
 features on, render_batch, render_batch_host, set_tile_shard and set_shard refuse with the message of the feature they test first,
 which is not the order the passes are drawn in.  One handle of grid 65 (two tiles a side in both fills) and a frame of 64 x 64."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "flood_model", "spill_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import spill_model as spm  # noqa: E402
-from overlay_scenes import CAMERAS, heights  # noqa: E402
+import support
+import spill_model as spm
+from overlay_scenes import heights
+from support import bits
 
 fdm, cm = spm.fdm, spm.cm
 W = H = 64
@@ -23,20 +20,13 @@ GRID = 65
 TINT = dict(shallow_rgba=(0, 255, 255, 200), deep_rgba=(20, 20, 20, 90), depth_full=0.3)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def uniforms():
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS["default"]), np.float32).reshape(44)
-    u[38] = 0.6
-    return u
+    return support.uniforms(W, H, exag=0.6)
 
 
 def terrain(supersample=None):
     from vulkan_forge_amd import cabi
-    lut = np.load(os.path.join(HERE, "golden", "colormaps_rgba8.npz"))["viridis"]
+    lut = np.load(os.path.join(support.HERE, "golden", "colormaps_rgba8.npz"))["viridis"]
     t = cabi.Terrain(W, H, GRID, lut, supersample=supersample)
     t.set_height(heights(**fdm.FIELD_TEXTURE))
     t.set_uniforms(uniforms())

@@ -6,61 +6,19 @@ over three cameras, two sizes, both shade modes and both precisions; over shadow
 under overlays with the shoreline's contour on top; on a supersampled handle; and nothing else moves -- the frame with the flood off
 or cleared, geometry buffers, visibility, the scan counter of a resting scene, the refusals.  tests/test_flood_model.py holds these
 inputs to the conditions that keep the comparisons from being vacuous."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "shadow_model", "viewshed_model", "contour_model", "haze_model",
-           "supersample_model", "flood_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import flood_model as fdm  # noqa: E402
-from flood_model import SCENE_LEVEL, SCENE_SEEDS  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights, scene  # noqa: E402
+import support
+import flood_model as fdm
+from flood_model import SCENE_LEVEL, SCENE_SEEDS
+from overlay_scenes import CAMERAS, GRID, heights, scene
+from support import assert_field, assert_frame, bits, terrain, uniforms, vf, viridis  # noqa: F401
 
 cm = fdm.cm
 SHALLOW, DEEP = (96, 176, 224, 128), (16, 64, 160, 224)
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def uniforms(W, H, cam="default", exag=None, spacing=None, sun=None):
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS[cam]), np.float32).reshape(44)
-    if exag is not None:
-        u[38] = exag
-    if spacing is not None:
-        u[36] = spacing
-    if sun is not None:
-        u[32:35] = sun
-    return u
-
-
-def terrain(W, H, grid, h, lut=None):
-    from vulkan_forge_amd import cabi
-    t = cabi.Terrain(W, H, grid, np.zeros(1024, np.uint8) if lut is None else lut)
-    t.set_height(h)
-    return t
-
-
-def assert_field(got, want, what):
-    assert got.shape == want.shape and got.dtype == np.float32, what
-    d = bits(got) != bits(want)
-    assert not d.any(), f"{what}: {int(d.sum())} vertices differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:4]} against {want[d][:4]}"
 
 
 def assert_info(info, F, what):
@@ -104,8 +62,7 @@ def test_field_equals_the_model(grid):
 
 
 def test_field_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "flood_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "FLOOD TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("flood_torch_check.py", "FLOOD TORCH OK")
 
 
 def test_a_serpentine_channel_at_three_group_sizes():
@@ -171,38 +128,14 @@ def test_a_wall_of_non_finite_heights_across_a_tile_border(bad):
 
 # ---- the tinted frame ----
 
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
-
-
-_oracle = {}
-
-
-def oracle_frame(u, W, H, h, mode="reference"):
-    """the oracle's frame and visibility (computed once per case, and left unchanged)"""
-    import oracle
-    key = (u.tobytes(), W, H, h.tobytes()[:64], mode)
-    if key not in _oracle:
-        rgba, vis = oracle.render_terrain(u, W, H, GRID, h, viridis(), want_vis=True, nthreads=8,
-                                          shade_mode=oracle.SHADE_SPEC_T32 if mode == "spec_t32" else oracle.SHADE_REFERENCE)
-        _oracle[key] = (rgba.reshape(H, W, 4), vis)
-    return _oracle[key]
-
-
 _fields = {}
 
 
 def scene_field(u, h, seeds):
-    key = (float(u[36]), h.tobytes()[:64], repr(seeds))
+    key = (float(u[36]), support.digest(h), repr(seeds))
     if key not in _fields:
-        _fields[key] = fdm.field(u, h, GRID, SCENE_LEVEL, seeds)
+        _fields[key] = support.frozen(fdm.field(u, h, GRID, SCENE_LEVEL, seeds))
     return _fields[key]
-
-
-def assert_frame(got, want, what):
-    d = (got != want).any(axis=2)
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}"
 
 
 # the defaults from the border; other colours and a shallower depth_full from the seed list; the deep colour alone
@@ -221,7 +154,7 @@ def test_frames_equal_the_model_in_both_precisions(vf, cam, size, mode):
         s.set_shade_mode(mode)
         plain = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-        rgba, vis = oracle_frame(u, W, H, h, mode)
+        rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
         if precision == "exact":
             assert np.array_equal(plain, rgba)                                   # (the exact frame is the oracle's)
         covered = vis != 0
@@ -265,7 +198,7 @@ def test_the_water_lies_over_shadows_and_a_drape_and_under_the_viewshed_tint_and
             s.set_haze(**haze)
         frames[stage] = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-    _, vis = oracle_frame(u, W, H, h)
+    _, vis = support.oracle_frame(u, W, H, GRID, h)
     F = scene_field(u, h, SCENE_SEEDS[0])
     water, d = fdm.frame(frames["under"], vis, u, h, GRID, F)
     plain = scene(vf, W, H, h, "default", "exact").render_rgba()
@@ -290,7 +223,7 @@ def test_overlays_and_the_shoreline_contour_composite_over_the_water(vf):
     L.points(pts, size_px=5.0, rgba=(255, 0, 0, 200), drape=True, occlude=True)
     s.add_contours(np.asarray([SCENE_LEVEL], np.float32), width_px=1.5, rgba=(255, 255, 255, 255))
     L.contours(h, GRID, u, [SCENE_LEVEL], width_px=1.5, rgba=(255, 255, 255, 255))
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h)
     F = scene_field(u, h, SCENE_SEEDS[0])
     base, d = fdm.frame(rgba, vis, u, h, GRID, F)
     want = cm.ocm.composite(base, vis, u, h, GRID, L)

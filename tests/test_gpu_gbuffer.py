@@ -2,37 +2,23 @@
 frame, bit for bit -- both shade precisions, three cameras, every subset of planes, pick, the C-ABI and device destinations -- and
 leave the handle's frames, timing and output as they were."""
 import itertools
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "gbuffer_model"))
-import gbuffer_model as gbm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights, scene  # noqa: E402
+import support
+import gbuffer_model as gbm
+from overlay_scenes import CAMERAS, GRID, heights, scene
+from support import bits, vf  # noqa: F401
 
 PLANES = ("depth", "position", "normal", "primitive")
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
 
 
 def oracle_vis(u, W, H, h):
     import oracle
     return oracle.render_terrain(u, W, H, GRID, h, np.zeros(1024, np.uint8), want_vis=True, nthreads=8)[1]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def assert_planes_equal(got, want, what=""):
@@ -204,6 +190,4 @@ def test_the_planes_belong_to_the_frame_that_was_rendered():
 def test_device_destinations_on_a_stream_of_the_callers():
     """vf_terrain_gbuffer_device into torch tensors on a torch stream equals the host read (a fresh process: torch is imported before
     the library there, one HIP runtime per process)"""
-    import subprocess
-    r = subprocess.run([sys.executable, os.path.join(HERE, "gbuffer_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "GBUFFER TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("gbuffer_torch_check.py", "GBUFFER TORCH OK")

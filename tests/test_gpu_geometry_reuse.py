@@ -19,6 +19,7 @@ import pytest
 
 import plan_model as pm
 from conftest import DEFAULT_CAMERA, FILL_CAMERA, heightmap
+from support import cabi  # noqa: F401
 from test_gpu_parity import EXACT, FAST, RGBA_TOL
 
 pytestmark = pytest.mark.gpu
@@ -30,13 +31,6 @@ CAM_B = ((-2.4, 1.1, 2.9), (0.1, 0.0, -0.2), (0.0, 1.0, 0.0), 55.0, 0.1, 100.0)
 REFERENCE, SPEC_T32 = 0, 1
 FRAME_BYTES = W * H * 4
 SLOTS = 16                        # device frames of a sequence that reads nothing back between its frames
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as mod
-    mod.load()
-    return mod
 
 
 @pytest.fixture(scope="module")

@@ -4,21 +4,15 @@ haze, three falloffs (the difference branch of the height factor, both branches,
 and the background on; at 1 x 1 and 130 x 3; over shadows, ambient occlusion, a drape and the three tints; under overlays; on
 supersampled handles; into device memory on a caller's stream; and nothing else moves -- the frame with haze never set, disabled or
 cleared, visibility, geometry buffers, pick, the refusals."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "shadow_model", "viewshed_model", "supersample_model", "gbuffer_model", "haze_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import haze_model as hzm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
+import support
+import haze_model as hzm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import assert_frame, bits, vf, viridis  # noqa: F401
 
 SIZES = [(96, 64), (71, 45)]
 ORANGE = (255, 120, 40, 128)
@@ -32,43 +26,6 @@ def cases(cam):
     for f in hzm.SCENE_FALLOFFS:
         out[f"falloff {f}"] = dict(P, falloff=f, base=hzm.SCENE_BASE)
     return out
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
-
-
-_oracle = {}
-
-
-def oracle_frame(u, W, H, h, mode="reference"):
-    """the oracle's frame and visibility: computed once per case, shared, left unchanged"""
-    import oracle
-    key = (u.tobytes(), W, H, h.tobytes()[:64], mode)
-    if key not in _oracle:
-        rgba, vis = oracle.render_terrain(u, W, H, GRID, h, viridis(), want_vis=True, nthreads=8,
-                                          shade_mode=oracle.SHADE_SPEC_T32 if mode == "spec_t32" else oracle.SHADE_REFERENCE)
-        rgba = rgba.reshape(H, W, 4)
-        rgba.setflags(write=False)
-        vis.setflags(write=False)
-        _oracle[key] = (rgba, vis)
-    return _oracle[key]
-
-
-def assert_frame(got, want, what):
-    d = (got != want).any(axis=2)
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:2].tolist()} against {want[d][:2].tolist()}"
 
 
 def assert_plane(got, want, what):
@@ -88,7 +45,7 @@ def test_frames_and_opacities_equal_the_model_in_both_precisions(vf, cam, size, 
         s.set_shade_mode(mode)
         plain = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-        rgba, vis = oracle_frame(u, W, H, h, mode)
+        rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
         if precision == "exact":
             assert np.array_equal(plain, rgba)                                   # (the exact frame is the oracle's)
         covered = vis != 0
@@ -118,7 +75,7 @@ def test_frames_of_one_pixel_and_of_three_rows(vf, size, cam):
     s = scene(vf, W, H, h, cam, "exact")
     plain = s.render_rgba().copy()
     u = s.debug_uniforms_f32()
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h)
     assert np.array_equal(plain, rgba)
     for name in ("no start", "falloff 0.3", "translucent background"):
         kw = cases(cam)[name]
@@ -171,7 +128,7 @@ def test_haze_lies_over_shadows_ambient_occlusion_a_drape_and_the_three_tints(vf
             s.set_haze(**kw)
         frames[hazed] = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h)
     want, a = hzm.frame(frames[False], vis, u, h, GRID, **kw)
     assert (frames[False] != rgba).any() and (want != frames[False]).any()
     assert_frame(frames[True], want, "haze over shadows, ambient occlusion, a drape and the three tints")
@@ -194,7 +151,7 @@ def test_overlays_composite_over_the_hazed_frame_and_are_not_hazed(vf):
              ("add_lines", (paths,), dict(width_px=3.0, rgba=(0, 255, 0, 200), drape=True)),
              ("add_polygons", (poly,), dict(fill_rgba=(0, 90, 255, 160)))]
     L = apply(vf, s, calls, ocm.Layers())
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h)
     base, _ = hzm.frame(rgba, vis, u, h, GRID, **kw)
     want = ocm.composite(base, vis, u, h, GRID, L)
     assert (base != rgba).any() and (want != base).any()
@@ -230,8 +187,7 @@ def test_supersampled_handles_haze_their_samples(vf, f):
 
 
 def test_opacities_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "haze_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "HAZE TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("haze_torch_check.py", "HAZE TORCH OK")
 
 
 def test_the_frame_the_gbuffers_the_visibility_and_pick_are_unchanged(vf):
@@ -272,7 +228,7 @@ def test_the_frame_the_gbuffers_the_visibility_and_pick_are_unchanged(vf):
     assert s.haze_info()["eye_y"] == float(hzm.eye_y(u1)) != float(hzm.eye_y(u0))
     h2 = heights(9)
     s.set_height_from_r32f(h2)
-    rgba, vis = oracle_frame(u1, W, H, h2)
+    rgba, vis = support.oracle_frame(u1, W, H, GRID, h2)
     assert_frame(s.render_rgba(), hzm.frame(rgba, vis, u1, h2, GRID, **kw)[0], "new heights and camera")
     s.set_height_from_r32f(h)
     s.set_camera_look_at(*CAMERAS["default"])

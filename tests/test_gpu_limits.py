@@ -11,27 +11,15 @@ equal to their models bit for bit.  No tolerance of its own.
 
 tests/limit_cases.py describes the cases; tests/test_limit_cases.py shows on the CPU that each reaches the edge it is named for.
 One handle at a time: a 16384 x 16384 handle holds more than 1 GiB of device memory."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import limit_cases as lc
+from support import cabi  # noqa: F401
 from test_gpu_parity import EXACT, assert_parity, hip_frame, note_fast
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _m in ("overlay_model", "polygon_model", "shadow_model", "ambient_model", "contour_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as C
-    C.load()
-    return C
 
 
 def threads(oracle):
@@ -180,7 +168,7 @@ def _field_cases():
 def test_sky_view_field_at_the_reach_and_direction_limits(cabi, oracle, grid, exag, reach, D):
     import ambient_model as abm
     from overlay_scenes import CAMERAS
-    from test_gpu_ambient import assert_field
+    from support import assert_field
     h = abm.limit_heights()
     u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, 64, 64, *CAMERAS["default"]), np.float32).reshape(44)
     u[38] = exag

@@ -1,33 +1,17 @@
 """Occluding overlay layers on the GPU equal the CPU model (tests/occlusion_model) applied to the same handle's frame
 drawn without overlays and the oracle's visibility of it, bit for bit -- both shade precisions, three cameras, layers that mix
 occluding, plain and polygon layers, every read-back path, frames in flight, and switching occlusion between frames."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-import occlusion_model as ocm  # noqa: E402
-from overlay_scenes import GRID, apply, heights, scene  # noqa: E402
+from support import ridge, vf  # noqa: F401
+import occlusion_model as ocm
+from overlay_scenes import GRID, apply, heights, scene
 
 RIDGE = ((0.0, 1.0, 3.0), (0.0, 0.3, 0.0), (0.0, 1.0, 0.0), 50.0, 0.1, 100.0)     # from in front of ridge(), over its crest
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def ridge(shape=(64, 64)):
-    z = np.linspace(-1.5, 1.5, shape[0])
-    return np.broadcast_to((1.5 * np.exp(-(z / 0.25) ** 2))[:, None], shape).astype(np.float32)
 
 
 def oracle_vis(u, W, H, h):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import plan_model as pm
+from support import cabi  # noqa: F401
 from test_gpu_plan_feedback import Rig, camera, oracle_frame
 
 pytestmark = pytest.mark.gpu
@@ -16,13 +17,6 @@ COARSE = (200, 136, 33)           # 4 x 3 tiles, the last column and the last ro
 FINE = (300, 200, 137)            # 5 x 4 tiles, triangles of a few pixels
 CLOSE = ((0.0, 0.4, 0.0), (0.5, 0.0, 0.4), (0.0, 1.0, 0.0), 70.0, 0.05, 100.0)   # grid 33 from just above the surface: triangles up to 78 lines on their SHORT side at 200 x 136
 CUTS = (0, 1, 2, 4)               # whole tiles, strips of 32, 16 and 4 pixels
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as C
-    C.load()
-    return C
 
 
 def uniforms(oracle, size, cam):

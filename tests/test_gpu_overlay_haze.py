@@ -6,31 +6,21 @@ haze colour; a contour layer; hazed and unhazed layers interleaved over polygons
 does; a bin with more primitives than one sort window; 1 x 1 and 130 x 3 frames; supersampled handles; the flag switched off and on;
 new haze parameters and new heights without touching the layers; haze off in every way; and the refusals.
 tests/test_overlay_haze_model.py holds the frames drawn here to the conditions that keep these comparisons from being vacuous."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "haze_model", "overlay_haze_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import overlay_haze_model as ohm  # noqa: E402
-import overlay_haze_scenes as sc  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
+import support
+import overlay_haze_model as ohm
+import overlay_haze_scenes as sc
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import assert_frame, vf  # noqa: F401
 
 ocm = ohm.ocm
 F32 = np.float32
 TRIANGLE = [np.array([[-0.9, 0.05, -0.8], [1.0, 0.05, -0.6], [0.1, 0.05, 1.1]], F32)]
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
 
 
 _vis = {}
@@ -39,17 +29,12 @@ _vis = {}
 def oracle_vis(u, W, H, h):
     """the oracle's visibility: computed once per case, shared, left unchanged"""
     import oracle
-    key = (u.tobytes(), W, H, h.tobytes()[:64])
+    key = (u.tobytes(), W, H, support.digest(h))
     if key not in _vis:
         vis = oracle.render_terrain(u, W, H, GRID, h, np.zeros(1024, np.uint8), want_vis=True, nthreads=8)[1]
         vis.setflags(write=False)
         _vis[key] = vis
     return _vis[key]
-
-
-def assert_frame(got, want, what):
-    d = (got != want).any(axis=2)
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:2].tolist()} against {want[d][:2].tolist()}"
 
 
 def bases_of(s, settings):

@@ -1,23 +1,15 @@
 """Overlays on the GPU (vf_overlay.h) equal the CPU model (tests/overlay_model) applied to the same handle's frame drawn without them,
 bit for bit -- every read-back path, batches of poses, partial bins, near-plane crossings, and a million points in one bin."""
 import io
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "overlay_model"))
-import overlay_model as om  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
+from support import vf  # noqa: F401
+import overlay_model as om
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
 
 
 def workload(seed=11, npts=10_000, npaths=2_000):

@@ -13,19 +13,13 @@ import numpy as np
 import pytest
 
 from conftest import DEFAULT_CAMERA, FILL_CAMERA, GOLDEN, heightmap
+from support import cabi  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 RGBA_TOL = 1   # LSB per channel (BASELINE.json north_star: "RGBA within +-1 LSB of reference")
 EXACT, FAST = 0, 1   # vf_terrain_set_shade_precision: EXACT reproduces the oracle bit for bit (0 LSB), FAST (default) stays within RGBA_TOL
 FAST_DIFF = np.zeros(4, np.int64)   # channel values of the FAST frames seen by hip_frame / compare_both: differing from the oracle by 0, 1, 2, >2 LSB
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as C
-    C.load()
-    return C
 
 
 def note_fast(rgba_fast, ref_rgba):

@@ -5,19 +5,16 @@ pixel" is the property under test; what the feedback IS no longer depends on the
 
 A frame here: inject, render, read the colour and the item codes, then read the visibility -- which draws the frame again with the
 visibility-storing tile kernel, planned from the same injected words in the other plan state."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import plan_model as pm
 from conftest import heightmap
+from support import cabi  # noqa: F401
 from test_gpu_parity import EXACT, FAST, RGBA_TOL
 
 pytestmark = pytest.mark.gpu
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "overlay_model"))
 
 SMALL = (300, 200, 65)            # 5 x 4 tiles: the last column 44 pixels wide, the last row 8 high
 # The frame-filling camera of overlay_scenes shows the terrain as a patch about 1.05 frame heights wide, so upright frames fill best.  The
@@ -27,13 +24,6 @@ BUDGET = (704, 896, 129)          # 145 of 11 x 14 tiles, all full-width: 137 ti
 LARGE = (2752, 3392, 257)         # 2071 of 43 x 53 tiles.  The split budget turns a tile away only once fewer than 15 of its 2048 items are left,
                                   # so it grants at least 2034: 2063 busy tiles make more than one 4096-item run of the sort whatever the atomics' order
 HEIGHT_SEED = 5
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as C
-    C.load()
-    return C
 
 
 def camera(oracle, name, W, H):

@@ -1,25 +1,15 @@
 """Polygon overlays on the GPU (vf_overlay.h, k_pg_* and the fill walk of k_ov_composite) equal the CPU model (tests/polygon_model)
 applied to the same handle's frame drawn without them, bit for bit -- every read-back path, batches of poses, near-plane crossings,
 screen-covering fills, rings off every screen edge, vertices on pixel-centre rows, a 200 000-vertex ring, and a bin past the sort cap."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-import polygon_model as pm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
+from support import vf  # noqa: F401
+import polygon_model as pm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
 
 
 def blob(rng, c, r, n, y):

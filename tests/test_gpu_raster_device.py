@@ -14,13 +14,12 @@ only.  Whole terrain frames reach a narrow family of triangles; these tests reac
 Every comparison is equality."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import raster_lattice as rl
-from conftest import ROOT
+from support import ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -34,8 +33,7 @@ def _build(exe):
     """hipcc with the library's own flags (an executable: no -shared / -fPIC); like build(), without the -mllvm tuning switches
     when this compiler refuses them.  Then the 64-bit-shift lint of tools/isa_lint.py, which applies to test kernels as well."""
     import __graft_entry__ as g
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_lint
+    from tools import isa_lint
     strip = ("-shared", "-fPIC")
     cmd = [g._hipcc(), *[f for f in g.HIPCC_FLAGS if f not in strip], SRC, "-o", exe]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

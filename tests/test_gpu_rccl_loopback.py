@@ -8,12 +8,10 @@ import os
 import numpy as np
 import pytest
 
+import support
+
 pytestmark = pytest.mark.gpu
 
 
 def test_rccl_single_rank_loopback_exchange():
-    import subprocess, sys
-    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "rccl_loopback_check.py")],
-                       capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0 and "LOOPBACK OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("rccl_loopback_check.py", "LOOPBACK OK", timeout=600, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))

@@ -2,24 +2,17 @@
 octant and on every special direction, on grids that are and are not a multiple of 8 and long enough for many chunks, through both
 entry points; the shadowed frame over three cameras, two sizes, both shade modes and both precisions; with overlays on top; and
 nothing else moves -- geometry buffers, the frame with shadows off, the refusals."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-import overlay_model as om  # noqa: E402
-import shadow_model as shm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
-from shadow_model import SCENE_PARAMS, SCENE_SUN_DEG  # noqa: E402
+import support
+import overlay_model as om
+import shadow_model as shm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from shadow_model import SCENE_PARAMS, SCENE_SUN_DEG
+from support import assert_field, bits, terrain, uniforms, vf, viridis  # noqa: F401
 
 # (x, y, z): the eight octants of the horizontal plane at general azimuths, the four axes, the exact diagonals, straight up,
 # on the horizon and below it
@@ -28,38 +21,6 @@ SUNS = [(0.9, 0.5, 0.31), (0.31, 0.5, 0.9), (-0.31, 0.4, 0.9), (-0.9, 0.7, 0.31)
         (0.5, 0.4, 0.5), (-0.5, 0.4, 0.5), (0.5, 0.4, -0.5), (-0.5, 0.4, -0.5),
         (0.0, 1.0, 0.0), (0.7, 0.0, 0.2), (0.2, -0.3, 0.7)]
 PARAMS = dict(strength=0.8, softness=0.05, bias=0.01)
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def uniforms(W, H, cam="default", sun=None, exag=None):
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS[cam]), np.float32).reshape(44)
-    if sun is not None:
-        u[32:35] = sun
-    if exag is not None:
-        u[38] = exag
-    return u
-
-
-def terrain(W, H, grid, h, lut=None):
-    from vulkan_forge_amd import cabi
-    t = cabi.Terrain(W, H, grid, np.zeros(1024, np.uint8) if lut is None else lut)
-    t.set_height(h)
-    return t
-
-
-def assert_field(got, want, what):
-    d = bits(got) != bits(want)
-    assert not d.any(), f"{what}: {int(d.sum())} vertices differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:4]} against {want[d][:4]}"
 
 
 @pytest.mark.parametrize("grid", [1024, 1025, 203, 1500])
@@ -83,17 +44,11 @@ def test_field_equals_the_model(grid):
 
 
 def test_field_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "shadow_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "SHADOW TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def viridis():
-    """the 256 sRGB texels of the scenes' default colormap (an extension of vulkan_forge_amd, not of the drop-in module)"""
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
+    support.run_check("shadow_torch_check.py", "SHADOW TORCH OK")
 
 
 def oracle_frame(vf, u, W, H, h, mode):
+    # (not support.oracle_frame: these frames go up to 1920 x 1080, and a process-wide cache should not keep twelve of them)
     import oracle
     return oracle.render_terrain(u, W, H, GRID, h, viridis(), want_vis=True, nthreads=8,
                                  shade_mode=oracle.SHADE_SPEC_T32 if mode == "spec_t32" else oracle.SHADE_REFERENCE)
@@ -107,10 +62,8 @@ def model_frame(vf, u, W, H, h, mode):
 
 
 def assert_frame(got, want, what, where=None):
-    d = (got != want).any(axis=2)
-    if where is not None:
-        d &= where
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}"
+    # byte for byte, at the pixels of the mask `where` if one is given
+    support.assert_frame(got if where is None else np.where(where[..., None], got, want), want, what)
 
 
 @pytest.mark.parametrize("mode", ["reference", "spec_t32"])

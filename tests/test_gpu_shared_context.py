@@ -15,18 +15,12 @@ import numpy as np
 import pytest
 
 import soak_handles as sh
+from support import cabi  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 P_ON = ("shadows", "ambient", "flood", "spill")              # the relight pass; two fields that iterate to a fixpoint with the host in the loop
 SUN_B, CAM_B = sh.SUNS[1], 3
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as mod
-    mod.load()
-    return mod
 
 
 @pytest.fixture

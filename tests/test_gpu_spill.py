@@ -7,61 +7,19 @@ precisions; over shadows, a drape and the flood's water; under the viewshed tint
 supersampled handle; and nothing else moves -- the frame with the spill off or cleared, geometry buffers, visibility, the scan counter
 of a resting scene, the refusals.  tests/test_spill_model.py holds these inputs to the conditions that keep the comparisons from being
 vacuous."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "shadow_model", "viewshed_model", "contour_model", "haze_model",
-           "supersample_model", "flood_model", "spill_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import spill_model as spm  # noqa: E402
-from spill_model import SCENE_SEEDS  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights, scene  # noqa: E402
+import support
+import spill_model as spm
+from spill_model import SCENE_SEEDS
+from overlay_scenes import CAMERAS, GRID, heights, scene
+from support import assert_field, assert_frame, bits, terrain, uniforms, vf, viridis  # noqa: F401
 
 fdm, cm = spm.fdm, spm.cm
 SHALLOW, DEEP = (96, 176, 224, 128), (16, 64, 160, 224)
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def uniforms(W, H, cam="default", exag=None, spacing=None, sun=None):
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS[cam]), np.float32).reshape(44)
-    if exag is not None:
-        u[38] = exag
-    if spacing is not None:
-        u[36] = spacing
-    if sun is not None:
-        u[32:35] = sun
-    return u
-
-
-def terrain(W, H, grid, h, lut=None):
-    from vulkan_forge_amd import cabi
-    t = cabi.Terrain(W, H, grid, np.zeros(1024, np.uint8) if lut is None else lut)
-    t.set_height(h)
-    return t
-
-
-def assert_field(got, want, what):
-    assert got.shape == want.shape and got.dtype == np.float32, what
-    d = bits(got) != bits(want)
-    assert not d.any(), f"{what}: {int(d.sum())} vertices differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:4]} against {want[d][:4]}"
 
 
 def assert_fields(t, F, what):
@@ -106,8 +64,7 @@ def test_fields_equal_the_model(grid):
 
 
 def test_fields_into_device_memory_on_a_stream_of_the_callers_and_the_flood_identity():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "spill_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "SPILL TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("spill_torch_check.py", "SPILL TORCH OK")
 
 
 @pytest.mark.parametrize("slope", [+1.0, -1.0])
@@ -174,38 +131,14 @@ def test_walls_of_non_finite_heights_on_and_beside_a_tile_border(bad):
 
 # ---- the tinted frame ----
 
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
-
-
-_oracle = {}
-
-
-def oracle_frame(u, W, H, h, mode="reference"):
-    """the oracle's frame and visibility (computed once per case, and left unchanged)"""
-    import oracle
-    key = (u.tobytes(), W, H, h.tobytes()[:64], mode)
-    if key not in _oracle:
-        rgba, vis = oracle.render_terrain(u, W, H, GRID, h, viridis(), want_vis=True, nthreads=8,
-                                          shade_mode=oracle.SHADE_SPEC_T32 if mode == "spec_t32" else oracle.SHADE_REFERENCE)
-        _oracle[key] = (rgba.reshape(H, W, 4), vis)
-    return _oracle[key]
-
-
 _fields = {}
 
 
 def scene_field(u, h, seeds):
-    key = (float(u[36]), h.tobytes()[:64], repr(seeds))
+    key = (float(u[36]), support.digest(h), repr(seeds))
     if key not in _fields:
-        _fields[key] = spm.field(u, h, GRID, seeds)
+        _fields[key] = support.frozen(spm.field(u, h, GRID, seeds))
     return _fields[key]
-
-
-def assert_frame(got, want, what):
-    d = (got != want).any(axis=2)
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}"
 
 
 # the defaults from the border; other colours and a shallower depth_full from the seed list; the deep colour alone
@@ -224,7 +157,7 @@ def test_frames_equal_the_model_in_both_precisions(vf, cam, size, mode):
         s.set_shade_mode(mode)
         plain = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-        rgba, vis = oracle_frame(u, W, H, h, mode)
+        rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
         if precision == "exact":
             assert np.array_equal(plain, rgba)                                   # (the exact frame is the oracle's)
         covered = vis != 0
@@ -271,7 +204,7 @@ def test_the_tint_lies_over_shadows_a_drape_and_the_water_and_under_the_viewshed
             s.set_haze(**haze)
         frames[stage] = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-    _, vis = oracle_frame(u, W, H, h)
+    _, vis = support.oracle_frame(u, W, H, GRID, h)
     water, dw = fdm.frame(frames["under"], vis, u, h, GRID, fdm.field(u, h, GRID, fdm.SCENE_LEVEL, SCENE_SEEDS[1]))
     sinks, ds = spm.frame(water, vis, u, h, GRID, scene_field(u, h, "edges"), **sink_tint)
     plain = scene(vf, W, H, h, "default", "exact").render_rgba()
@@ -298,7 +231,7 @@ def test_an_occluding_overlay_layer_composites_over_the_tint(vf):
     L = cm.Layers()
     s.add_points(pts, size_px=5.0, rgba=(255, 0, 0, 200), drape=True, occlude=True)
     L.points(pts, size_px=5.0, rgba=(255, 0, 0, 200), drape=True, occlude=True)
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h)
     base, d = spm.frame(rgba, vis, u, h, GRID, scene_field(u, h, "edges"))
     want = cm.ocm.composite(base, vis, u, h, GRID, L)
     got = s.render_rgba()

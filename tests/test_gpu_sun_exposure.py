@@ -5,30 +5,18 @@ grid; one sun by angles against the handle's own shadow field; over non-finite h
 over two cameras, two sizes and both precisions with either colour alone and both; over shadows, ambient occlusion and a drape and
 under both viewshed tints; under overlays; and nothing else moves -- the frame with the feature off, cleared or merely set, geometry
 buffers, visibility, the other four fields, the scan counter of a resting scene, the refusals."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-sys.path.insert(0, os.path.join(HERE, "viewshed_model"))
-sys.path.insert(0, os.path.join(HERE, "cumulative_viewshed_model"))
-sys.path.insert(0, os.path.join(HERE, "sun_exposure_model"))
-import cumulative_viewshed_model as cvm  # noqa: E402
-import sun_exposure_model as sem  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
-from overlay_scenes import CAMERAS, apply, heights  # noqa: E402
-from test_gpu_viewshed import assert_field, assert_frame, bits, terrain, uniforms, viridis  # noqa: E402
-from viewshed_model import SCENE_OBSERVER, SCENE_PARAMS as VIEW_PARAMS  # noqa: E402
+import support
+import cumulative_viewshed_model as cvm
+import sun_exposure_model as sem
+import viewshed_model as vsm
+from overlay_scenes import CAMERAS, apply, heights
+from support import assert_field, assert_frame, bits, terrain, uniforms, vf, viridis  # noqa: F401
+from viewshed_model import SCENE_OBSERVER, SCENE_PARAMS as VIEW_PARAMS
 
 shm = sem.shm
 RED, GOLD, BLUE = (255, 0, 0, 128), (255, 208, 64, 160), (0, 60, 255, 200)
@@ -39,12 +27,6 @@ FRAME_WEIGHTS = np.append(np.random.default_rng(31).uniform(0.3, 1.0, 12), 1.0).
 FRAME_PARAMS = dict(softness=0.1, bias=0.3)
 FRAME_WTOT = sem.weight_total(FRAME_SUNS, FRAME_WEIGHTS)
 SCENE_H = heights(4, (97, 131))
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
 
 
 _wants = {}
@@ -63,9 +45,9 @@ _fields = {}
 
 def frame_field(u, h, incidence=False):
     """the model's exposure field of the frames' scene (it depends on the spacing and the exaggeration alone: computed once)"""
-    key = (float(u[36]), float(u[38]), h.tobytes()[:64], h.shape, incidence)
+    key = (float(u[36]), float(u[38]), support.digest(h), incidence)
     if key not in _fields:
-        _fields[key] = sem.field(u, h, FRAME_GRID, FRAME_SUNS, FRAME_WEIGHTS, incidence=incidence, **FRAME_PARAMS)
+        _fields[key] = support.frozen(sem.field(u, h, FRAME_GRID, FRAME_SUNS, FRAME_WEIGHTS, incidence=incidence, **FRAME_PARAMS))
     return _fields[key]
 
 
@@ -76,11 +58,6 @@ def frame_scene(vf, W, H, h, cam="default", precision=None):
         s.set_shade_precision(precision)
     s.set_camera_look_at(*CAMERAS[cam])
     return s
-
-
-def oracle_frame(u, W, H, h):
-    import oracle
-    return oracle.render_terrain(u, W, H, FRAME_GRID, h, viridis(), want_vis=True, nthreads=8, shade_mode=oracle.SHADE_REFERENCE)
 
 
 # ---- the field ----
@@ -176,8 +153,7 @@ def test_non_finite_heights():
 
 
 def test_field_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "sun_exposure_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "SUN EXPOSURE TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("sun_exposure_torch_check.py", "SUN EXPOSURE TORCH OK")
 
 
 # ---- frames ----
@@ -195,7 +171,7 @@ def test_frames_equal_the_model_in_both_precisions(vf, cam, size):
         s = frame_scene(vf, W, H, h, cam, precision)
         plain = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-        rgba, vis = oracle_frame(u, W, H, h)
+        rgba, vis = support.oracle_frame(u, W, H, FRAME_GRID, h)
         if precision == "exact":
             assert np.array_equal(plain, rgba.reshape(H, W, 4))                # (the exact frame is the oracle's)
         e = frame_field(u, h)
@@ -242,7 +218,7 @@ def test_the_tint_lies_over_the_relight_passes_and_under_both_viewshed_tints(vf)
             s.set_viewshed(SCENE_OBSERVER, **VIEW_PARAMS, **single)
         frames[tinted] = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-    _, vis = oracle_frame(u, W, H, h)
+    _, vis = support.oracle_frame(u, W, H, FRAME_GRID, h)
     plain = frame_scene(vf, W, H, h, "default", "exact").render_rgba()
     assert (frames["none"] != plain).any()
     e = frame_field(u, h)
@@ -274,7 +250,7 @@ def test_overlays_composite_over_the_tinted_frame(vf):
     calls = [("add_points", (pts,), dict(size_px=4.0, rgba=(255, 0, 0, 200), drape=True, occlude=True)),
              ("add_lines", (paths,), dict(width_px=2.0, rgba=(0, 255, 0, 200), drape=True))]
     L = apply(vf, s, calls, ocm.Layers())
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, FRAME_GRID, h)
     base, _ = sem.frame(rgba, vis, u, h, FRAME_GRID, frame_field(u, h), FRAME_WTOT, high_rgba=GOLD, low_rgba=BLUE)
     want = ocm.composite(base, vis, u, h, FRAME_GRID, L)
     got = s.render_rgba()

@@ -4,20 +4,14 @@ at the output size; at sizes chosen for the resolve's edges -- 71 x 45 (odd; nei
 f = 3 rows not 16-byte aligned), 64 x 64 (exact tiles), 1 x 1, 130 x 3 (wider than one wave's row segment, shorter than a tile) --
 for f = 2, 3, 4; with every pass and every kind of overlay at once; geometry buffers and pick; the read-backs; every kind of change;
 the refusals."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("supersample_model", "overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import supersample_model as ssm  # noqa: E402
+import support
+import supersample_model as ssm
+from support import vf, viridis  # noqa: F401
 
 F32 = np.float32
 GRID = 33
@@ -31,17 +25,6 @@ CAMERAS = {
 
 def heights(seed=11, shape=(33, 33)):
     return (np.random.default_rng(seed).random(shape, dtype=F32) * 0.6 - 0.3).astype(F32)
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
 
 
 def scene(vf, W, H, f, h, cam="default", precision="exact", grid=GRID):
@@ -68,9 +51,9 @@ _models = {}
 
 def model(W, H, f, cam, h, u):
     """the model of the plain frame (computed once per case, and left unchanged)"""
-    key = (W, H, f, cam, h.tobytes()[:64], u.tobytes())
+    key = (W, H, f, cam, support.digest(h), u.tobytes())
     if key not in _models:
-        _models[key] = ssm.frame(W, H, f, u, h, GRID, viridis())
+        _models[key] = support.frozen(ssm.frame(W, H, f, u, h, GRID, viridis()))
     return _models[key]
 
 
@@ -245,8 +228,7 @@ def test_render_png_decodes_to_the_frame(vf, f, tmp_path):
 def test_device_destinations():
     """set_output_device with a torch tensor of W x H x 4 receives the frame and samples_device fills an f W x f H x 4 tensor (a
     fresh process: torch is imported before the library there, one HIP runtime per process)"""
-    r = subprocess.run([sys.executable, os.path.join(HERE, "supersample_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "SUPERSAMPLE TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    support.run_check("supersample_torch_check.py", "SUPERSAMPLE TORCH OK")
 
 
 # ---- 6. change, then render ----

@@ -16,6 +16,7 @@ import pytest
 
 import plan_model as pm
 from conftest import DEFAULT_CAMERA, FILL_CAMERA, heightmap
+from support import cabi  # noqa: F401
 from test_gpu_parity import EXACT
 
 pytestmark = pytest.mark.gpu
@@ -26,13 +27,6 @@ GRAZING = ((0.0, 0.5, 6.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 20.0, 0.1, 100.0) 
 FAR = ((3.0, 6.0, 3.0), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 30.0, 0.1, 100.0)         # grid 1025 inside one 64 x 64 tile: > 4096 entries in 128 rows
 INSIDE = ((0.2, 0.0, 0.3), (0.0, 0.0, -0.5), (0.0, 1.0, 0.0), 60.0, 0.01, 100.0)    # the eye between the terrain's heights
 NEAR_CUT = ((1.2, 0.4, 1.2), (0.0, 0.0, 0.0), (0.0, 1.0, 0.0), 60.0, 0.6, 100.0)    # the near plane cuts the terrain
-
-
-@pytest.fixture(scope="module")
-def cabi():
-    from vulkan_forge_amd import cabi as mod
-    mod.load()
-    return mod
 
 
 _REF = {}

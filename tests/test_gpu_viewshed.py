@@ -3,64 +3,21 @@ the corners, the edges, inside and outside the grid, on grids that need carries,
 entry points; the tinted frame over three cameras, two sizes, both shade modes and both precisions, with and without a radius and
 with either tint alone; over shadows, ambient occlusion and a drape; under overlays; and nothing else moves -- the frame with the
 viewshed off or cleared, geometry buffers, visibility, the scan counter of a resting scene, the refusals."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-sys.path.insert(0, os.path.join(HERE, "viewshed_model"))
-import viewshed_model as vsm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, apply, heights, scene  # noqa: E402
-from viewshed_model import SCENE_OBSERVER, SCENE_PARAMS  # noqa: E402
+import support
+import viewshed_model as vsm
+from overlay_scenes import CAMERAS, GRID, apply, heights, scene
+from support import assert_field, assert_frame, bits, terrain, uniforms, vf, viridis  # noqa: F401
+from viewshed_model import SCENE_OBSERVER, SCENE_PARAMS
 
 # (x, z) in world units at spacing 1: the four corners, two edge midpoints, the centre, an off-centre vertex, outside the grid (clamped)
 OBSERVERS = [(-1.5, -1.5), (1.5, -1.5), (-1.5, 1.5), (1.5, 1.5), (0.0, -1.5), (1.5, 0.1), (0.0, 0.0), (0.41, -0.87), (7.0, -0.3)]
 PARAMS = dict(eye_height=0.4, target_height=0.02, softness=0.05, bias=0.01)
 RED, GREEN = (255, 0, 0, 128), (64, 255, 96, 96)
-
-
-@pytest.fixture(scope="module")
-def vf():
-    import vulkan_forge
-    return vulkan_forge
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def uniforms(W, H, cam="default", exag=None, spacing=None, sun=None):
-    import oracle
-    u = np.array(oracle.look_at_uniforms(oracle.KIND_SCENE, W, H, *CAMERAS[cam]), np.float32).reshape(44)
-    if exag is not None:
-        u[38] = exag
-    if spacing is not None:
-        u[36] = spacing
-    if sun is not None:
-        u[32:35] = sun
-    return u
-
-
-def terrain(W, H, grid, h, lut=None):
-    from vulkan_forge_amd import cabi
-    t = cabi.Terrain(W, H, grid, np.zeros(1024, np.uint8) if lut is None else lut)
-    t.set_height(h)
-    return t
-
-
-def assert_field(got, want, what):
-    d = bits(got) != bits(want)
-    assert not d.any(), f"{what}: {int(d.sum())} vertices differ, first at {np.argwhere(d)[:4].tolist()}: {got[d][:4]} against {want[d][:4]}"
 
 
 @pytest.mark.parametrize("grid,observers", [(130, OBSERVERS), (203, OBSERVERS), (257, OBSERVERS), (1025, OBSERVERS[7:8])])
@@ -85,24 +42,7 @@ def test_field_equals_the_model(grid, observers):
 
 
 def test_field_into_device_memory_on_a_stream_of_the_callers():
-    r = subprocess.run([sys.executable, os.path.join(HERE, "viewshed_torch_check.py")], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "VIEWSHED TORCH OK" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-
-
-def viridis():
-    import vulkan_forge_amd
-    return vulkan_forge_amd.colormap_rgba8("viridis")
-
-
-def oracle_frame(u, W, H, h, mode="reference"):
-    import oracle
-    return oracle.render_terrain(u, W, H, GRID, h, viridis(), want_vis=True, nthreads=8,
-                                 shade_mode=oracle.SHADE_SPEC_T32 if mode == "spec_t32" else oracle.SHADE_REFERENCE)
-
-
-def assert_frame(got, want, what):
-    d = (got != want).any(axis=2)
-    assert not d.any(), f"{what}: {int(d.sum())} pixels differ, first at {np.argwhere(d)[:4].tolist()}"
+    support.run_check("viewshed_torch_check.py", "VIEWSHED TORCH OK")
 
 
 # both tints; the hidden tint alone, inside a radius; the visible tint alone; both inside a larger radius
@@ -123,7 +63,7 @@ def test_frames_equal_the_model_in_both_precisions(vf, cam, size, mode):
         plain = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
         if seen is None:
-            rgba, vis = oracle_frame(u, W, H, h, mode)
+            rgba, vis = support.oracle_frame(u, W, H, GRID, h, mode)
             seen, v = vsm.field(u, h, GRID, SCENE_OBSERVER, **SCENE_PARAMS)
             assert np.array_equal(plain, rgba.reshape(H, W, 4))                # (the exact frame is the oracle's)
         covered = vis != 0
@@ -162,7 +102,7 @@ def test_the_tint_lies_over_shadows_ambient_occlusion_and_a_drape(vf):
             s.set_viewshed(SCENE_OBSERVER, **SCENE_PARAMS, visible_rgba=GREEN, hidden_rgba=RED, radius=1.5)
         frames[tinted] = s.render_rgba().copy()
         u = s.debug_uniforms_f32()
-    _, vis = oracle_frame(u, W, H, h)
+    _, vis = support.oracle_frame(u, W, H, GRID, h)
     seen, v = vsm.field(u, h, GRID, SCENE_OBSERVER, **SCENE_PARAMS)
     want, sv = vsm.frame(frames[False], vis, u, h, GRID, seen, v, visible_rgba=GREEN, hidden_rgba=RED, radius=1.5)
     plain = scene(vf, W, H, h, "default", "exact").render_rgba()
@@ -189,7 +129,7 @@ def test_overlays_composite_over_the_tinted_frame(vf):
              ("add_polygons", (poly,), dict(fill_rgba=(0, 90, 255, 160))),
              ("add_points", (marker,), dict(size_px=9.0, rgba=(255, 255, 0, 255)))]
     L = apply(vf, s, calls, ocm.Layers())
-    rgba, vis = oracle_frame(u, W, H, h)
+    rgba, vis = support.oracle_frame(u, W, H, GRID, h)
     seen, v = vsm.field(u, h, GRID, SCENE_OBSERVER, **SCENE_PARAMS)
     assert info["vertex"] == v and info["enabled"] is True and info["eye_y"] == pytest.approx(info["observer_xyz"][1] + SCENE_PARAMS["eye_height"])
     base, _ = vsm.frame(rgba, vis, u, h, GRID, seen, v, visible_rgba=GREEN, hidden_rgba=RED)

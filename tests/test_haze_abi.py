@@ -2,89 +2,59 @@
 documents them, NULL handles are refused, the Python methods exist on both classes with the documented signatures, and the argument
 rules refuse what they should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_haze", "vf_terrain_clear_haze", "vf_terrain_haze_info", "vf_terrain_read_haze_opacity", "vf_terrain_haze_opacity_device",
-         "vf_terrain_debug_haze_stage"]
+ENTRY_POINTS = {"vf_terrain_set_haze": ["t", "enable", "density", "rgba", "start", "falloff", "base", "max_opacity", "background"],
+                "vf_terrain_clear_haze": ["t"],
+                "vf_terrain_haze_info": ["t", "out"],
+                "vf_terrain_read_haze_opacity": ["t", "dst"],
+                "vf_terrain_haze_opacity_device": ["t", "dev", "stream"],
+                "vf_terrain_debug_haze_stage": ["t", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
     from vulkan_forge_amd import cabi
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_haze"] == ["t", "enable", "density", "rgba", "start", "falloff", "base", "max_opacity", "background"]
-    assert names["vf_terrain_clear_haze"] == ["t"]
-    assert names["vf_terrain_haze_info"] == ["t", "out"]
-    assert names["vf_terrain_read_haze_opacity"] == ["t", "dst"]
-    assert names["vf_terrain_haze_opacity_device"] == ["t", "dev", "stream"]
-    assert names["vf_terrain_debug_haze_stage"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    assert re.search(r"#define VF_HAZE_RGBA 0xFFEBD7C8u(\s|$)", src)
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("HAZE", (("RGBA", "0xFFEBD7C8u"),))
     assert 0xFFEBD7C8 == 200 | 215 << 8 | 235 << 16 | 255 << 24
-    body = re.search(r"typedef struct vf_haze_info \{(.*?)\} vf_haze_info;", src, flags=re.S).group(1)
-    fields = [re.sub(r"\[\d+\]", "", f.strip()) for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert fields == [f for f, _ in cabi.HazeInfo._fields_]
+    fields = abi.check_info_struct("vf_haze_info", cabi.HazeInfo, 4 * 10)
     assert fields == ["enabled", "background", "density", "start", "falloff", "base", "max_opacity", "rgba", "has_eye", "eye_y"]
-    assert ctypes.sizeof(cabi.HazeInfo) == 4 * 10
 
 
 def test_the_header_documents_the_calls():
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    block = text[text.index("atmospheric haze: a distance and height fog pass"):]
-    for n in NAMES:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4q", "VF_ERR_INVALID", "max_opacity outside\n * [0, 1]", "rgba == NULL", "vf_terrain_render_batch / _batch_host",
-                 "the sample size on a supersampled handle", "NULL: the context's stream", "are not hazed", "keep their alpha byte",
-                 "does not follow vf_terrain_set_shade_precision", "allocates and launches nothing"):
-        assert word in block, word
+    abi.check_header_documents("atmospheric haze: a distance and height fog pass", list(ENTRY_POINTS),
+                               ("DESIGN.md 4q", "VF_ERR_INVALID", "max_opacity outside\n * [0, 1]", "rgba == NULL", "vf_terrain_render_batch / _batch_host",
+                                "the sample size on a supersampled handle", "NULL: the context's stream", "are not hazed", "keep their alpha byte",
+                                "does not follow vf_terrain_set_shade_precision", "allocates and launches nothing"))
 
 
 def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    ms = ctypes.c_float()
-    info = cabi.HazeInfo()
     col = (ctypes.c_uint8 * 4)(1, 2, 3, 4)
-    assert lib.vf_terrain_set_haze(None, 1, 0.25, col, 0.0, 0.0, 0.0, 1.0, 0) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_clear_haze(None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_haze_info(None, ctypes.byref(info)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_haze_opacity(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_haze_opacity_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_haze_stage(None, 1, ctypes.byref(ms)) == cabi.VF_ERR_INVALID
-    assert b"NULL" in lib.vf_last_error()
+    abi.check_null_refusals([("vf_terrain_set_haze", (1, 0.25, col, 0.0, 0.0, 0.0, 1.0, 0)),
+                             ("vf_terrain_clear_haze", ()),
+                             ("vf_terrain_haze_info", (ctypes.byref(cabi.HazeInfo()),)),
+                             ("vf_terrain_read_haze_opacity", (out.ctypes.data,)),
+                             ("vf_terrain_haze_opacity_device", (None, None)),
+                             ("vf_terrain_debug_haze_stage", (1, ctypes.byref(ctypes.c_float())))])
+    assert b"NULL" in cabi.load().vf_last_error()
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    from vulkan_forge_amd import cabi
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_haze.__doc__
-        assert re.search(r"set_haze\(self: [\w.]+, density: object, \*, rgba: object = \(200, 215, 235, 255\), start: object = 0.0, "
-                         r"falloff: object = None, base: object = 0.0, max_opacity: object = 1.0, background: object = False, "
-                         r"enabled: object = True\) -> None", doc), doc
-        assert re.search(r"clear_haze\(self: [\w.]+\) -> None", T.clear_haze.__doc__)
-        assert re.search(r"haze_info\(self: [\w.]+\) -> object", T.haze_info.__doc__)
-        assert re.search(r"haze_opacity\(self: [\w.]+\) -> numpy", T.haze_opacity.__doc__)
-    for name in ("set_haze", "clear_haze", "haze_info", "haze_opacity", "haze_opacity_device", "haze_stage"):
-        assert callable(getattr(cabi.Terrain, name)), name
+    abi.check_method_docs(cls, {
+        "set_haze": r"set_haze\(self: [\w.]+, density: object, \*, rgba: object = \(200, 215, 235, 255\), start: object = 0.0, "
+                    r"falloff: object = None, base: object = 0.0, max_opacity: object = 1.0, background: object = False, "
+                    r"enabled: object = True\) -> None",
+        "clear_haze": r"clear_haze\(self: [\w.]+\) -> None",
+        "haze_info": r"haze_info\(self: [\w.]+\) -> object",
+        "haze_opacity": r"haze_opacity\(self: [\w.]+\) -> numpy"},
+        cabi_methods=("set_haze", "clear_haze", "haze_info", "haze_opacity", "haze_opacity_device", "haze_stage"))
 
 
 def test_argument_rules():

@@ -2,18 +2,13 @@
 exact at 0 and monotone; both branches of the height factor agree with float64 at and around the threshold between them; hand-worked
 pixels come out as worked; the scenes the GPU tests draw are part hazed, reach the clipped path and both branches; and a float64
 restatement of the whole contract agrees with the model to one byte step."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "haze_model"))
-import haze_model as hzm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import haze_model as hzm
+from overlay_scenes import CAMERAS, GRID, heights
 
 gbm = hzm.gbm
 ocm = gbm.ocm

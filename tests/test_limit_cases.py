@@ -4,7 +4,6 @@ both outer tile columns of the full frame's compared bands, 256 stripes with non
 cases: tests/test_ambient_model.py), a NaN texel in the last column of a 32768-texel texture, millions of contour segments within and
 beyond the record budget.  The soak corners at the frame limit are held the same way in tests/test_feature_soak_cases.py."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -12,8 +11,7 @@ import pytest
 import limit_cases as lc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-for _m in ("overlay_model", "contour_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 
 
 def outer_tiles(cov):

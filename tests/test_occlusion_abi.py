@@ -4,30 +4,27 @@ import ctypes
 import importlib.util
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi_support as abi
+from support import ROOT
+
 _spec = importlib.util.spec_from_file_location("vf_overlay_rules", os.path.join(ROOT, "vulkan_forge_amd", "_overlays.py"))
 ov = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(ov)
 
 
 def test_set_layer_occlusion_is_declared_listed_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vf_hip.h")).read(), flags=re.S)
-    assert re.search(r"int\s+vf_terrain_set_layer_occlusion\s*\(\s*vf_terrain\s*\*\s*t\s*,\s*uint32_t\s+layer_id\s*,\s*int\s+occlude\s*,"
-                     r"\s*float\s+depth_bias\s*\)\s*;", src)
-    assert re.search(r"#define\s+VF_OCCLUSION_DEPTH_BIAS\s+1e-2f", src)
-    sys.path.insert(0, ROOT)
     from vulkan_forge_amd import cabi
-    assert "vf_terrain_set_layer_occlusion" in cabi.SYMBOLS
+    abi.check_entry_points({"vf_terrain_set_layer_occlusion": ["t", "layer_id", "occlude", "depth_bias"]})
+    assert re.search(r"int\s+vf_terrain_set_layer_occlusion\s*\(\s*vf_terrain\s*\*\s*t\s*,\s*uint32_t\s+layer_id\s*,\s*int\s+occlude\s*,"
+                     r"\s*float\s+depth_bias\s*\)\s*;", abi.code())
+    abi.check_defines("OCCLUSION", (("DEPTH_BIAS", "1e-2f"),))
     restype, argtypes = cabi._PROTOS["vf_terrain_set_layer_occlusion"]
     assert restype is ctypes.c_int and argtypes == [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float]
-    assert hasattr(ctypes.CDLL(cabi.DEFAULT_LIB), "vf_terrain_set_layer_occlusion")
-    lib = cabi.load()
-    assert lib.vf_terrain_set_layer_occlusion(None, 0, 1, 0.01) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_layer_occlusion", (0, 1, 0.01))])
 
 
 def test_occlusion_argument_rules():
@@ -47,7 +44,6 @@ def test_occlusion_argument_rules():
 
 def test_the_methods_take_occlusion_arguments():
     pytest.importorskip("vulkan_forge_amd._vulkan_forge")
-    sys.path.insert(0, ROOT)
     import vulkan_forge as vf
     for cls in (vf.Scene, vf.TerrainSpike):
         assert hasattr(cls, "set_layer_occlusion")

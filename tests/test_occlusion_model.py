@@ -1,16 +1,12 @@
 """The occlusion CPU model (tests/occlusion_model) against the contract of DESIGN.md 4d, on frames and visibility drawn by the oracle:
 the model is what the GPU frames are held to bit for bit (tests/test_gpu_occlusion.py).  No GPU needed."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "occlusion_model"))
-import occlusion_model as ocm  # noqa: E402
-import oracle  # noqa: E402
+from support import ridge
+import occlusion_model as ocm
+import oracle
 
 pm, om = ocm.pm, ocm.om
 GRID = 256
@@ -26,14 +22,6 @@ CAMERAS = {
 def bumpy(seed=7, shape=(67, 71)):
     rng = np.random.default_rng(seed)
     return (rng.random(shape, dtype=np.float32) * 0.6 - 0.3).astype(np.float32)
-
-
-def ridge(shape=(64, 64)):
-    """a wall 1.5 high across the terrain at z = 0 (texture rows map to z)"""
-    h = np.zeros(shape, np.float32)
-    z = np.linspace(-1.5, 1.5, shape[0])
-    h[:] = (1.5 * np.exp(-(z / 0.25) ** 2))[:, None]
-    return h
 
 
 def terrain(cam, h, W=240, H=160):

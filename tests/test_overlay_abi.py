@@ -1,46 +1,34 @@
 """The overlay entry points (include/vf_hip.h) are declared, listed in cabi.SYMBOLS, exported by libvf_hip.so, and argument errors
 that need no device are reported as such (no GPU needed)."""
 import ctypes
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ["vf_terrain_add_points", "vf_terrain_add_lines", "vf_terrain_clear_overlays"]
+import abi_support as abi
+
+ENTRY_POINTS = {"vf_terrain_add_points": ["t", "xyz", "n", "size_px", "rgba", "default_size", "default_rgba", "shape", "drape", "layer_id"],
+                "vf_terrain_add_lines": ["t", "xyz", "path_offsets", "npaths", "width_px", "rgba", "cap", "drape", "layer_id"],
+                "vf_terrain_clear_overlays": ["t"]}
 
 
 def test_overlay_entry_points_are_declared_listed_and_exported():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vf_hip.h")).read(), flags=re.S)
-    sys.path.insert(0, ROOT)
-    from vulkan_forge_amd import cabi
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\b" + n + r"\s*\(", src), f"{n} not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and n in cabi._PROTOS, n
-        assert hasattr(lib, n), f"libvf_hip.so does not export {n}"
-    for macro in ("VF_SHAPE_CIRCLE", "VF_SHAPE_SQUARE", "VF_CAP_BUTT", "VF_CAP_SQUARE", "VF_CAP_ROUND"):
-        assert re.search(r"#define\s+" + macro + r"\b", src), macro
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("SHAPE", (("CIRCLE", 0), ("SQUARE", 1)))
+    abi.check_defines("CAP", (("BUTT", 0), ("SQUARE", 1), ("ROUND", 2)))
 
 
 def test_overlay_calls_refuse_a_null_handle():
-    sys.path.insert(0, ROOT)
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
-    one = np.zeros(3, np.float32)
-    col = (ctypes.c_uint8 * 4)(255, 255, 255, 255)
-    assert lib.vf_terrain_add_points(None, one.ctypes.data, 1, None, None, 4.0, ctypes.cast(col, ctypes.c_void_p), 0, 0, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_clear_overlays(None) == cabi.VF_ERR_INVALID
+    one, two = np.zeros(3, np.float32), np.zeros(6, np.float32)
     offs = np.array([0, 2], np.uint32)
-    two = np.zeros(6, np.float32)
-    assert lib.vf_terrain_add_lines(None, two.ctypes.data, offs.ctypes.data, 1, 2.0, ctypes.cast(col, ctypes.c_void_p), 2, 0, None) == cabi.VF_ERR_INVALID
+    col = ctypes.cast((ctypes.c_uint8 * 4)(255, 255, 255, 255), ctypes.c_void_p)
+    abi.check_null_refusals([("vf_terrain_add_points", (one.ctypes.data, 1, None, None, 4.0, col, 0, 0, None)),
+                             ("vf_terrain_clear_overlays", ()),
+                             ("vf_terrain_add_lines", (two.ctypes.data, offs.ctypes.data, 1, 2.0, col, 2, 0, None))])
 
 
 def test_pack_lines_and_argument_rules():
     pytest.importorskip("vulkan_forge_amd._vulkan_forge")
-    sys.path.insert(0, ROOT)
     import vulkan_forge as vf
     from vulkan_forge_amd import _overlays as ov
     coords, offs = vf.pack_lines([np.array([[0, 0, 0], [0, 0, 0], [1, 2, 3], [1, 2, 3], [4, 5, 6]], np.float64),

@@ -2,48 +2,31 @@
 the header documents them and leaves the haze paragraph's sentence true, NULL handles are refused, the Python methods exist on both
 classes of both packages with the documented signatures, and the argument rule refuses what is no bool."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_layer_haze", "vf_terrain_layer_haze"]
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "vf_hip.h")).read()
+ENTRY_POINTS = {"vf_terrain_set_layer_haze": ["t", "layer_id", "on"], "vf_terrain_layer_haze": ["t", "layer_id", "on"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [a.split()[-1].lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_layer_haze"] == ["t", "layer_id", "on"]
-    assert names["vf_terrain_layer_haze"] == ["t", "layer_id", "on"]
+    abi.check_entry_points(ENTRY_POINTS)
+    src = abi.code()
+    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in ENTRY_POINTS}
     assert "int *on" in proto["vf_terrain_layer_haze"] and "int on" in proto["vf_terrain_set_layer_haze"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == 3, n
 
 
 def test_the_header_documents_the_calls():
-    text = header()
-    block = text[text.index("Hazed overlay layers (new"):text.index("int vf_terrain_layer_haze")]
-    for n in NAMES:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4r", "are not hazed unless their\n * layer asks", "VF_ERR_INVALID", "a polygon\n *   layer cannot take the haze: polygon fills have no depth",
-                 "vf_terrain_clear_overlays", "density 0", "byte for byte", "supersampled handles", "both occlude and\n *   take the haze",
-                 "does not follow vf_terrain_set_shade_precision"):
-        assert word in block, word
+    abi.check_header_documents("Hazed overlay layers (new", list(ENTRY_POINTS),
+                               ("DESIGN.md 4r", "are not hazed unless their\n * layer asks", "VF_ERR_INVALID",
+                                "a polygon\n *   layer cannot take the haze: polygon fills have no depth",
+                                "vf_terrain_clear_overlays", "density 0", "byte for byte", "supersampled handles", "both occlude and\n *   take the haze",
+                                "does not follow vf_terrain_set_shade_precision"), until="int vf_terrain_layer_haze")
     # the haze paragraph stands as it was: overlays are not hazed -- by default
+    text = abi.header_text()
     haze = text[text.index("atmospheric haze: a distance and height fog pass"):]
     assert "are not hazed" in haze and "vf_terrain_set_layer_haze" not in haze
 
@@ -52,26 +35,20 @@ def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
     lib = cabi.load()
     on = ctypes.c_int(7)
-    assert lib.vf_terrain_set_layer_haze(None, 0, 1) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_layer_haze", (0, 1))])
     assert b"NULL" in lib.vf_last_error()
-    assert lib.vf_terrain_layer_haze(None, 0, ctypes.byref(on)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_layer_haze", (0, ctypes.byref(on)))])
     assert b"NULL" in lib.vf_last_error() and on.value == 7
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    from vulkan_forge_amd import cabi
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        assert re.search(r"set_layer_haze\(self: [\w.]+, layer: (typing\.SupportsInt|int)[^,]*, on: object = True\) -> None", T.set_layer_haze.__doc__), T.set_layer_haze.__doc__
-        assert re.search(r"layer_haze\(self: [\w.]+, layer: [^)]*\) -> bool", T.layer_haze.__doc__), T.layer_haze.__doc__
-        for name in ("add_points", "add_lines", "add_contours"):
-            assert re.search(r"haze: object = False\) -> int", getattr(T, name).__doc__), getattr(T, name).__doc__
-        assert "haze" not in T.add_polygons.__doc__
-    for name in ("set_layer_haze", "layer_haze"):
-        assert callable(getattr(cabi.Terrain, name)), name
+    abi.check_method_docs(cls, {
+        "set_layer_haze": r"set_layer_haze\(self: [\w.]+, layer: (typing\.SupportsInt|int)[^,]*, on: object = True\) -> None",
+        "layer_haze": r"layer_haze\(self: [\w.]+, layer: [^)]*\) -> bool",
+        "add_points": r"haze: object = False\) -> int", "add_lines": r"haze: object = False\) -> int", "add_contours": r"haze: object = False\) -> int",
+        "add_polygons": r"\A(?!(.|\n)*haze)"},
+        cabi_methods=("set_layer_haze", "layer_haze"))
 
 
 def test_argument_rules():

@@ -2,28 +2,19 @@
 model's bit for bit, a hand-worked pixel, a receding segment, depth and height at the pixel against float64, the primitive that speaks
 for a feature, a near-clipped end, the stencil, layers without the flag -- and, for every (camera, size, setting) of
 tests/test_gpu_overlay_haze.py, the conditions that keep its comparison from being vacuous.  No GPU needed."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "haze_model", "overlay_haze_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
-import haze_model as hzm  # noqa: E402
-import oracle  # noqa: E402
-import overlay_haze_model as ohm  # noqa: E402
-import overlay_haze_scenes as sc  # noqa: E402
+from support import bits
+import haze_model as hzm
+import oracle
+import overlay_haze_model as ohm
+import overlay_haze_scenes as sc
 
 ocm, om = ohm.ocm, ohm.om
 GRID = sc.GRID
 F32 = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 def uniforms(cam, W, H):

@@ -1,13 +1,11 @@
 """The overlay CPU model (tests/overlay_model) against the contract of DESIGN.md "Overlays": the model is what the GPU frames are
 held to bit for bit (tests/test_gpu_overlays.py), so its own behaviour is pinned here on hand-checkable cases."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "overlay_model"))
-import overlay_model as om  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import overlay_model as om
 
 W = H = 64
 BG = np.array([90, 60, 30, 255], np.uint8)

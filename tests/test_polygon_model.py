@@ -3,14 +3,13 @@ add_polygons: the model is what the GPU frames are held to bit for bit (tests/te
 against an independent float64 evaluation and hand-worked cases.  No GPU needed."""
 import importlib.util
 import os
-import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "polygon_model"))
-import polygon_model as pm  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import polygon_model as pm
 om = pm.om
 
 _spec = importlib.util.spec_from_file_location("vf_overlay_rules", os.path.join(os.path.dirname(HERE), "vulkan_forge_amd", "_overlays.py"))

@@ -1,35 +1,17 @@
 """The cast-shadow CPU model (tests/shadow_model) against what shadows must do: flat ground is lit, a ridge casts a strip
 of the right length, the field commutes with the grid's symmetries exactly, a higher sun never darkens a vertex, a float64 march
 along the same lines agrees, non-finite heights neither cast nor take a shadow, and the scene the GPU tests draw is part in shadow."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-import shadow_model as shm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
+from support import bits, smooth
+import shadow_model as shm
+from overlay_scenes import CAMERAS, GRID, heights
 
 SUNS = [(0.9, 0.5, 0.31), (0.31, 0.5, 0.9), (-0.31, 0.4, 0.9), (-0.9, 0.7, 0.31), (-0.9, 0.3, -0.31), (-0.31, 0.6, -0.9), (0.31, 0.45, -0.9), (0.9, 0.55, -0.31),
         (1.0, 0.6, 0.0), (-1.0, 0.6, 0.0), (0.0, 0.6, 1.0), (0.0, 0.6, -1.0), (0.5, 0.4, 0.5), (-0.5, 0.4, 0.5), (0.5, 0.4, -0.5), (-0.5, 0.4, -0.5),
         (0.0, 1.0, 0.0), (0.7, 0.0, 0.2), (0.2, -0.3, 0.7)]
-
-
-def smooth(n, seed=1):
-    rng = np.random.default_rng(seed)
-    x = np.linspace(0, 1, n, dtype=np.float64)
-    X, Z = np.meshgrid(x, x)
-    h = sum(rng.normal() * 0.2 / f * np.sin(2 * np.pi * f * (X * np.cos(a) + Z * np.sin(a)) + p)
-            for f, a, p in zip((1, 2, 3, 5), rng.uniform(0, 6.3, 4), rng.uniform(0, 6.3, 4)))
-    return h.astype(np.float32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_flat_terrain_is_lit():

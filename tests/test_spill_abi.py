@@ -2,103 +2,72 @@
 documents them, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what they
 should."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_spill", "vf_terrain_clear_spill", "vf_terrain_read_spill_field", "vf_terrain_spill_field_device", "vf_terrain_read_sink_depth",
-         "vf_terrain_spill_info", "vf_terrain_read_spill_seeds", "vf_terrain_debug_spill_scans", "vf_terrain_debug_spill_group",
-         "vf_terrain_debug_spill_stage"]
+ENTRY_POINTS = {"vf_terrain_set_spill": ["t", "enable", "mode", "seeds_xz", "count", "shallow_rgba", "deep_rgba", "depth_full"],
+                "vf_terrain_clear_spill": ["t"],
+                "vf_terrain_read_spill_field": ["t", "spill"],
+                "vf_terrain_spill_field_device": ["t", "dev_spill", "stream"],
+                "vf_terrain_read_sink_depth": ["t", "depth"],
+                "vf_terrain_spill_info": ["t", "out"],
+                "vf_terrain_read_spill_seeds": ["t", "vertices"],
+                "vf_terrain_debug_spill_scans": ["t", "count"],
+                "vf_terrain_debug_spill_group": ["t", "group"],
+                "vf_terrain_debug_spill_stage": ["t", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
     from vulkan_forge_amd import cabi
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_spill"] == ["t", "enable", "mode", "seeds_xz", "count", "shallow_rgba", "deep_rgba", "depth_full"]
-    assert names["vf_terrain_clear_spill"] == ["t"]
-    assert names["vf_terrain_read_spill_field"] == ["t", "spill"]
-    assert names["vf_terrain_spill_field_device"] == ["t", "dev_spill", "stream"]
-    assert names["vf_terrain_read_sink_depth"] == ["t", "depth"]
-    assert names["vf_terrain_spill_info"] == ["t", "out"]
-    assert names["vf_terrain_read_spill_seeds"] == ["t", "vertices"]
-    assert names["vf_terrain_debug_spill_scans"] == ["t", "count"]
-    assert names["vf_terrain_debug_spill_group"] == ["t", "group"]
-    assert names["vf_terrain_debug_spill_stage"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    for k, v in (("EDGES", "1"), ("SEEDS", "2"), ("MAX_SEEDS", "65535u"), ("SHALLOW_RGBA", "0x80E0B060u"), ("DEEP_RGBA", "0xE0A04010u"),
-                 ("DEPTH_FULL", "0.1f"), ("GROUP_NO_FLAGS", "0x80000000u")):
-        assert re.search(rf"#define VF_SPILL_{k} {v}(\s|$)", src), k
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("SPILL", (("EDGES", "1"), ("SEEDS", "2"), ("MAX_SEEDS", "65535u"), ("SHALLOW_RGBA", "0x80E0B060u"), ("DEEP_RGBA", "0xE0A04010u"),
+                                ("DEPTH_FULL", "0.1f"), ("GROUP_NO_FLAGS", "0x80000000u")))
+    src = abi.code()
     assert not re.search(r"#define VF_SPILL_EVERYWHERE", src)  # there is no such mode: its field would be h
     for k in ("EDGES", "SEEDS"):                               # the two modes carry the flood's numbers
         assert re.search(rf"#define VF_SPILL_{k} (\d)", src).group(1) == re.search(rf"#define VF_FLOOD_{k} (\d)", src).group(1)
-    # the struct the info call fills, field for field
-    body = re.search(r"typedef struct vf_spill_info \{(.*?)\} vf_spill_info;", src, flags=re.S).group(1)
-    fields = [re.sub(r"\[\d+\]", "", f.strip()) for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert fields == [f for f, _ in cabi.SpillInfo._fields_]
-    assert ctypes.sizeof(cabi.SpillInfo) == 4 * 5 + 8 + 4 * 6
+    abi.check_info_struct("vf_spill_info", cabi.SpillInfo, 4 * 5 + 8 + 4 * 6)
 
 
 def test_the_header_documents_the_calls():
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    block = text[text.index("spill analysis: the level the water must reach"):]
-    for n in NAMES[:7]:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4t", "VF_ERR_INVALID", "whether or not the spill is enabled", "NULL: the context's", "1 <= count <= 65535",
-                 "4-connected", "greatest fixpoint", "-0 below", "0xFFFFFFFF : 0x80000000", "vf_terrain_set_flood", "Whole-frame handles only",
-                 "survives height uploads", "allocates and launches nothing", "+inf where no", "depression-filled"):
-        assert word in block, word
+    abi.check_header_documents("spill analysis: the level the water must reach", list(ENTRY_POINTS)[:7],
+                               ("DESIGN.md 4t", "VF_ERR_INVALID", "whether or not the spill is enabled", "NULL: the context's", "1 <= count <= 65535",
+                                "4-connected", "greatest fixpoint", "-0 below", "0xFFFFFFFF : 0x80000000", "vf_terrain_set_flood", "Whole-frame handles only",
+                                "survives height uploads", "allocates and launches nothing", "+inf where no", "depression-filled"))
 
 
 def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    count = ctypes.c_uint32()
-    info = cabi.SpillInfo()
     xz, col = np.zeros((2, 2), np.float32), (ctypes.c_uint8 * 4)(1, 2, 3, 4)
-    assert lib.vf_terrain_set_spill(None, 1, 2, xz.ctypes.data, 2, col, col, 0.1) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_clear_spill(None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_spill_field(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_spill_field_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_sink_depth(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_spill_info(None, ctypes.byref(info)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_spill_seeds(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_spill_scans(None, ctypes.byref(count)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_spill_group(None, 4) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_spill_stage(None, 1, (ctypes.c_float * 2)()) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_spill", (1, 2, xz.ctypes.data, 2, col, col, 0.1)),
+                             ("vf_terrain_clear_spill", ()),
+                             ("vf_terrain_read_spill_field", (out.ctypes.data,)),
+                             ("vf_terrain_spill_field_device", (None, None)),
+                             ("vf_terrain_read_sink_depth", (out.ctypes.data,)),
+                             ("vf_terrain_spill_info", (ctypes.byref(cabi.SpillInfo()),)),
+                             ("vf_terrain_read_spill_seeds", (out.ctypes.data,)),
+                             ("vf_terrain_debug_spill_scans", (ctypes.byref(ctypes.c_uint32()),)),
+                             ("vf_terrain_debug_spill_group", (4,)),
+                             ("vf_terrain_debug_spill_stage", (1, (ctypes.c_float * 2)()))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    from vulkan_forge_amd import cabi
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_spill.__doc__
-        assert re.search(r"set_spill\(self: [\w.]+, seeds: object = 'edges', \*, enabled: object = True, "
-                         r"shallow_rgba: object = \(96, 176, 224, 128\), deep_rgba: object = \(16, 64, 160, 224\), "
-                         r"depth_full: object = 0.100\d*\) -> None", doc), doc
-        assert re.search(r"clear_spill\(self: [\w.]+\) -> None", T.clear_spill.__doc__)
-        assert re.search(r"spill_field\(self: [\w.]+\) -> numpy", T.spill_field.__doc__)
-        assert re.search(r"sink_depth_field\(self: [\w.]+\) -> numpy", T.sink_depth_field.__doc__)
-        assert re.search(r"spill_info\(self: [\w.]+\) -> object", T.spill_info.__doc__)
-    for name in ("set_spill", "clear_spill", "spill_field", "spill_field_device", "sink_depth_field", "spill_info", "spill_scans", "spill_group",
-                 "spill_stage"):
-        assert callable(getattr(cabi.Terrain, name)), name
+    abi.check_method_docs(cls, {
+        "set_spill": r"set_spill\(self: [\w.]+, seeds: object = 'edges', \*, enabled: object = True, "
+                     r"shallow_rgba: object = \(96, 176, 224, 128\), deep_rgba: object = \(16, 64, 160, 224\), "
+                     r"depth_full: object = 0.100\d*\) -> None",
+        "clear_spill": r"clear_spill\(self: [\w.]+\) -> None",
+        "spill_field": r"spill_field\(self: [\w.]+\) -> numpy",
+        "sink_depth_field": r"sink_depth_field\(self: [\w.]+\) -> numpy",
+        "spill_info": r"spill_info\(self: [\w.]+\) -> object"},
+        cabi_methods=("set_spill", "clear_spill", "spill_field", "spill_field_device", "sink_depth_field", "spill_info", "spill_scans", "spill_group",
+                      "spill_stage"))
 
 
 def test_argument_rules():

@@ -5,38 +5,21 @@ symmetries of the square; a +-0 tie; the tile passes of the kernels, emulated, e
 identity -- spill < level is what the flood model floods; and the inputs of the GPU tests (tests/test_gpu_spill.py) meet the conditions
 that keep those comparisons from being vacuous."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "spill_model"))
-import spill_model as spm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
+from support import bits, smooth
+import spill_model as spm
+from overlay_scenes import CAMERAS, GRID, heights
 
 fdm, cm = spm.fdm, spm.cm
 INF = np.float32(np.inf)
 
 
-def smooth(n, seed=1):
-    rng = np.random.default_rng(seed)
-    x = np.linspace(0, 1, n, dtype=np.float64)
-    X, Z = np.meshgrid(x, x)
-    h = sum(rng.normal() * 0.2 / f * np.sin(2 * np.pi * f * (X * np.cos(a) + Z * np.sin(a)) + p)
-            for f, a, p in zip((1, 2, 3, 5), rng.uniform(0, 6.3, 4), rng.uniform(0, 6.3, 4)))
-    return h.astype(np.float32)
-
-
 def rough(n, seed=2):
     return (smooth(n, seed) + np.random.default_rng(seed).normal(0, 0.05, (n, n))).astype(np.float32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def same(a, b):

@@ -2,96 +2,62 @@
 documents them, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what they
 should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_sun_exposure", "vf_terrain_clear_sun_exposure", "vf_terrain_read_sun_exposure_field", "vf_terrain_sun_exposure_field_device",
-         "vf_terrain_sun_exposure_info", "vf_terrain_debug_sun_exposure_batch", "vf_terrain_debug_sun_exposure_scans",
-         "vf_terrain_debug_sun_exposure_stage"]
+ENTRY_POINTS = {"vf_terrain_set_sun_exposure": ["t", "enable", "suns_xyz", "weights", "count", "incidence", "softness", "bias", "high_rgba", "low_rgba"],
+                "vf_terrain_clear_sun_exposure": ["t"],
+                "vf_terrain_read_sun_exposure_field": ["t", "exposure"],
+                "vf_terrain_sun_exposure_field_device": ["t", "dev_exposure", "stream"],
+                "vf_terrain_sun_exposure_info": ["t", "out"],
+                "vf_terrain_debug_sun_exposure_batch": ["t", "batch"],
+                "vf_terrain_debug_sun_exposure_scans": ["t", "count"],
+                "vf_terrain_debug_sun_exposure_stage": ["t", "repeats", "ms"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
     from vulkan_forge_amd import cabi
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_sun_exposure"] == ["t", "enable", "suns_xyz", "weights", "count", "incidence", "softness", "bias", "high_rgba", "low_rgba"]
-    assert names["vf_terrain_clear_sun_exposure"] == ["t"]
-    assert names["vf_terrain_read_sun_exposure_field"] == ["t", "exposure"]
-    assert names["vf_terrain_sun_exposure_field_device"] == ["t", "dev_exposure", "stream"]
-    assert names["vf_terrain_sun_exposure_info"] == ["t", "out"]
-    assert names["vf_terrain_debug_sun_exposure_batch"] == ["t", "batch"]
-    assert names["vf_terrain_debug_sun_exposure_scans"] == ["t", "count"]
-    assert names["vf_terrain_debug_sun_exposure_stage"] == ["t", "repeats", "ms"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    for k, v in (("MAX_SUNS", "65535u"), ("HIGH_RGBA", "0xA040D0FFu"), ("LOW_RGBA", "0x00000000u")):
-        assert re.search(rf"#define VF_SUN_EXPOSURE_{k} {v}(\s|$)", src), k
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("SUN_EXPOSURE", (("MAX_SUNS", "65535u"), ("HIGH_RGBA", "0xA040D0FFu"), ("LOW_RGBA", "0x00000000u")))
     assert 0xA040D0FF == 255 | 208 << 8 | 64 << 16 | 160 << 24
-    # the struct the info call fills, field for field
-    body = re.search(r"typedef struct vf_sun_exposure_info \{(.*?)\} vf_sun_exposure_info;", src, flags=re.S).group(1)
-    fields = [re.sub(r"\[\d+\]", "", f.strip()) for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert fields == [f for f, _ in cabi.SunExposureInfo._fields_]
+    fields = abi.check_info_struct("vf_sun_exposure_info", cabi.SunExposureInfo, 4 * 8 + 8)
     assert fields == ["enabled", "count", "counted", "weight_total", "incidence", "batch", "softness", "bias", "high_rgba", "low_rgba"]
-    assert ctypes.sizeof(cabi.SunExposureInfo) == 4 * 8 + 8
 
 
 def test_the_header_documents_the_calls():
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    block = text[text.index("sun exposure: the weighted sum of the shadow fields of N suns"):]
-    for n in NAMES[:5]:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4n", "VF_ERR_INVALID", "whether or not sun exposure is enabled", "NULL: the context's", "1 <= count <= 65535",
-                 "rint(lit * c * w * 65536)", "is not counted", "weights in\n * [0, 1]", "or NULL: all 1"):
-        assert word in block, word
+    abi.check_header_documents("sun exposure: the weighted sum of the shadow fields of N suns", list(ENTRY_POINTS)[:5],
+                               ("DESIGN.md 4n", "VF_ERR_INVALID", "whether or not sun exposure is enabled", "NULL: the context's", "1 <= count <= 65535",
+                                "rint(lit * c * w * 65536)", "is not counted", "weights in\n * [0, 1]", "or NULL: all 1"))
 
 
 def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    ms = ctypes.c_float()
-    count = ctypes.c_uint32()
-    info = cabi.SunExposureInfo()
     xyz, w, col = np.ones((2, 3), np.float32), np.ones(2, np.float32), (ctypes.c_uint8 * 4)(1, 2, 3, 4)
-    assert lib.vf_terrain_set_sun_exposure(None, 1, xyz.ctypes.data, w.ctypes.data, 2, 0, 0.02, 0.002, col, col) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_clear_sun_exposure(None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_sun_exposure_field(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_sun_exposure_field_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_sun_exposure_info(None, ctypes.byref(info)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_sun_exposure_batch(None, 4) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_sun_exposure_scans(None, ctypes.byref(count)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_sun_exposure_stage(None, 1, ctypes.byref(ms)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_sun_exposure", (1, xyz.ctypes.data, w.ctypes.data, 2, 0, 0.02, 0.002, col, col)),
+                             ("vf_terrain_clear_sun_exposure", ()),
+                             ("vf_terrain_read_sun_exposure_field", (out.ctypes.data,)),
+                             ("vf_terrain_sun_exposure_field_device", (None, None)),
+                             ("vf_terrain_sun_exposure_info", (ctypes.byref(cabi.SunExposureInfo()),)),
+                             ("vf_terrain_debug_sun_exposure_batch", (4,)),
+                             ("vf_terrain_debug_sun_exposure_scans", (ctypes.byref(ctypes.c_uint32()),)),
+                             ("vf_terrain_debug_sun_exposure_stage", (1, ctypes.byref(ctypes.c_float())))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    from vulkan_forge_amd import cabi
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_sun_exposure.__doc__
-        assert re.search(r"set_sun_exposure\(self: [\w.]+, suns: object, \*, weights: object = None, incidence: object = False, enabled: object = True, "
-                         r"softness: object = 0.019\d+, bias: object = 0.002\d*, high_rgba: object = \(255, 208, 64, 160\), "
-                         r"low_rgba: object = \(0, 0, 0, 0\)\) -> None", doc), doc
-        assert re.search(r"clear_sun_exposure\(self: [\w.]+\) -> None", T.clear_sun_exposure.__doc__)
-        assert re.search(r"sun_exposure_field\(self: [\w.]+\) -> numpy", T.sun_exposure_field.__doc__)
-        assert re.search(r"sun_exposure_info\(self: [\w.]+\) -> object", T.sun_exposure_info.__doc__)
-    for name in ("set_sun_exposure", "clear_sun_exposure", "sun_exposure_field", "sun_exposure_field_device", "sun_exposure_info", "sun_exposure_batch",
-                 "sun_exposure_scans", "sun_exposure_stage"):
-        assert callable(getattr(cabi.Terrain, name)), name
+    abi.check_method_docs(cls, {
+        "set_sun_exposure": r"set_sun_exposure\(self: [\w.]+, suns: object, \*, weights: object = None, incidence: object = False, enabled: object = True, "
+                            r"softness: object = 0.019\d+, bias: object = 0.002\d*, high_rgba: object = \(255, 208, 64, 160\), "
+                            r"low_rgba: object = \(0, 0, 0, 0\)\) -> None",
+        "clear_sun_exposure": r"clear_sun_exposure\(self: [\w.]+\) -> None",
+        "sun_exposure_field": r"sun_exposure_field\(self: [\w.]+\) -> numpy",
+        "sun_exposure_info": r"sun_exposure_info\(self: [\w.]+\) -> object"},
+        cabi_methods=("set_sun_exposure", "clear_sun_exposure", "sun_exposure_field", "sun_exposure_field_device", "sun_exposure_info", "sun_exposure_batch",
+                      "sun_exposure_scans", "sun_exposure_stage"))
 
 
 def test_argument_rules():

@@ -3,21 +3,14 @@ gives the quantised shadow field; the order of the suns changes no bit; flat gro
 the horizon and suns of weight 0 add nothing; a hand-worked wall with a sun on either side gives the worked sums; the incidence
 cosine of a tilted plane is the analytic one; halving the weights never raises a sum; and the scene the GPU tests compute is not a
 trivial one."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "shadow_model"))
-sys.path.insert(0, os.path.join(HERE, "sun_exposure_model"))
-import shadow_model as shm  # noqa: E402
-import sun_exposure_model as sem  # noqa: E402
-from overlay_scenes import heights  # noqa: E402
-from test_shadow_model import smooth  # noqa: E402
+from support import smooth
+import shadow_model as shm
+import sun_exposure_model as sem
+from overlay_scenes import heights
 
 F32 = np.float32
 

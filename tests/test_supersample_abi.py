@@ -2,16 +2,15 @@
 the constant, the ctypes prototypes have the header's argument counts, NULL handles are refused, and the Python argument rules raise
 ValueError before the library is called."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
 ARGS = {
-    "vf_terrain_create_supersampled": ["ctx", "width", "height", "grid", "lut_rgba8[1024]", "lut_is_srgb", "factor", "out"],
+    "vf_terrain_create_supersampled": ["ctx", "width", "height", "grid", "lut_rgba8", "lut_is_srgb", "factor", "out"],
     "vf_terrain_supersampling": ["t", "factor", "sample_width", "sample_height"],
     "vf_terrain_read_samples": ["t", "dst"],
     "vf_terrain_samples_device": ["t", "dev_dst", "stream"],
@@ -19,43 +18,26 @@ ARGS = {
 }
 
 
-def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "vf_hip.h")).read(), flags=re.S)
-
-
 def test_header_cabi_and_library_agree_on_the_entry_points():
-    from vulkan_forge_amd import cabi
-    src = header()
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    loaded = cabi.load()
-    for n, args in ARGS.items():
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-        proto = re.search(n + r"\s*\(([^)]*)\)", src).group(1)
-        assert [a.split()[-1].lstrip("*") for a in proto.split(",")] == args
-        assert len(getattr(loaded, n).argtypes) == len(args), n
-    assert re.search(r"\bint\s+vf_terrain_create\s*\(", src)                  # (stays, and means factor 1)
+    abi.check_entry_points(ARGS)
+    assert re.search(r"vf_terrain_create_supersampled\s*\([^)]*\blut_rgba8\[1024\],", abi.code())
+    abi.prototypes(["vf_terrain_create"])                                      # (stays, and means factor 1)
 
 
 def test_the_constant():
     from vulkan_forge_amd import _supersample, cabi
-    m = re.search(r"#define\s+VF_SUPERSAMPLE_MAX\s+(\d+)", header())
+    m = re.search(r"#define\s+VF_SUPERSAMPLE_MAX\s+(\d+)", abi.code())
     assert m and int(m.group(1)) == 4 == cabi.VF_SUPERSAMPLE_MAX == _supersample.SUPERSAMPLE_MAX
 
 
 def test_null_handles_are_refused_without_a_device():
-    from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(16, np.uint8)
-    f = ctypes.c_uint32()
-    ms = ctypes.c_float()
-    t = ctypes.c_void_p()
     lut = np.zeros(1024, np.uint8)
-    assert lib.vf_terrain_create_supersampled(None, 8, 8, 8, lut.ctypes.data, 1, 2, ctypes.byref(t)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_supersampling(None, ctypes.byref(f), None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_samples(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_samples_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_resolve_stage(None, 1, ctypes.byref(ms)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_create_supersampled", (8, 8, 8, lut.ctypes.data, 1, 2, ctypes.byref(ctypes.c_void_p()))),
+                             ("vf_terrain_supersampling", (ctypes.byref(ctypes.c_uint32()), None, None)),
+                             ("vf_terrain_read_samples", (out.ctypes.data,)),
+                             ("vf_terrain_samples_device", (None, None)),
+                             ("vf_terrain_debug_resolve_stage", (1, ctypes.byref(ctypes.c_float())))])
 
 
 def test_the_argument_rules():

@@ -3,16 +3,13 @@ identity at f = 1, uniform blocks of every byte, the mean in linear light, alpha
 frame with a ridge against the background, that the resolved frame has intermediate pixels along the silhouette where the 1x frame
 has none."""
 import os
-import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "supersample_model"))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-import supersample_model as ssm  # noqa: E402
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
+import supersample_model as ssm
 
 F32 = np.float32
 

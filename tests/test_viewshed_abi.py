@@ -2,86 +2,55 @@
 header documents them, the Python methods exist on both classes with the documented signatures, and the argument rules refuse what
 they should."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import abi_support as abi
 
-NAMES = ["vf_terrain_set_viewshed", "vf_terrain_read_viewshed_field", "vf_terrain_viewshed_field_device", "vf_terrain_viewshed_info",
-         "vf_terrain_debug_viewshed_stage", "vf_terrain_debug_viewshed_scans"]
+ENTRY_POINTS = {"vf_terrain_set_viewshed": ["t", "enable", "observer_xz", "eye_height", "target_height", "radius", "visible_rgba", "hidden_rgba",
+                                            "softness", "bias"],
+                "vf_terrain_read_viewshed_field": ["t", "seen"],
+                "vf_terrain_viewshed_field_device": ["t", "dev_seen", "stream"],
+                "vf_terrain_viewshed_info": ["t", "out"],
+                "vf_terrain_debug_viewshed_stage": ["t", "repeats", "ms"],
+                "vf_terrain_debug_viewshed_scans": ["t", "count"]}
 
 
 def test_header_cabi_and_library_agree_on_the_entry_points():
     from vulkan_forge_amd import cabi
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    lib = ctypes.CDLL(cabi.DEFAULT_LIB)
-    for n in NAMES:
-        assert re.search(r"\bint\s+" + n + r"\s*\(", src), f"{n} is not declared in include/vf_hip.h"
-        assert n in cabi.SYMBOLS and hasattr(lib, n), n
-    proto = {n: re.search(n + r"\s*\(([^)]*)\)", src).group(1) for n in NAMES}
-    names = {n: [re.sub(r"\[\d*\]", "", a.split()[-1]).lstrip("*") for a in proto[n].split(",")] for n in NAMES}
-    assert names["vf_terrain_set_viewshed"] == ["t", "enable", "observer_xz", "eye_height", "target_height", "radius", "visible_rgba", "hidden_rgba",
-                                                "softness", "bias"]
-    assert names["vf_terrain_read_viewshed_field"] == ["t", "seen"]
-    assert names["vf_terrain_viewshed_field_device"] == ["t", "dev_seen", "stream"]
-    assert names["vf_terrain_viewshed_info"] == ["t", "out"]
-    assert names["vf_terrain_debug_viewshed_stage"] == ["t", "repeats", "ms"]
-    assert names["vf_terrain_debug_viewshed_scans"] == ["t", "count"]
-    loaded = cabi.load()
-    for n in NAMES:
-        assert len(getattr(loaded, n).argtypes) == len(names[n]), n
-    for k, v in (("EYE_HEIGHT", "0.05f"), ("TARGET_HEIGHT", "0.0f"), ("SOFTNESS", "0.02f"), ("BIAS", "0.002f"), ("VISIBLE_RGBA", "0x6060FF40u"),
-                 ("HIDDEN_RGBA", "0x00000000u")):
-        assert re.search(rf"#define VF_VIEWSHED_{k} {v}(\s|$)", src), k
-    # the struct the info call fills, field for field
-    body = re.search(r"typedef struct vf_viewshed_info \{(.*?)\} vf_viewshed_info;", src, flags=re.S).group(1)
-    fields = [re.sub(r"\[\d+\]", "", f.strip()) for decl in body.split(";") if decl.strip() for f in decl.strip().split(None, 1)[1].split(",")]
-    assert fields == [f for f, _ in cabi.ViewshedInfo._fields_]
-    assert ctypes.sizeof(cabi.ViewshedInfo) == 4 * 13 + 8
+    abi.check_entry_points(ENTRY_POINTS)
+    abi.check_defines("VIEWSHED", (("EYE_HEIGHT", "0.05f"), ("TARGET_HEIGHT", "0.0f"), ("SOFTNESS", "0.02f"), ("BIAS", "0.002f"), ("VISIBLE_RGBA", "0x6060FF40u"),
+                                   ("HIDDEN_RGBA", "0x00000000u")))
+    abi.check_info_struct("vf_viewshed_info", cabi.ViewshedInfo, 4 * 13 + 8)
 
 
 def test_the_header_documents_the_calls():
-    text = open(os.path.join(ROOT, "include", "vf_hip.h")).read()
-    block = text[text.index("viewshed analysis: a line-of-sight field"):]
-    for n in NAMES[:4]:
-        assert re.search(r"\* " + n + r":", block), f"{n} has no paragraph in the header's comment"
-    for word in ("DESIGN.md 4l", "VF_ERR_INVALID", "whether or not the viewshed is enabled", "NULL: the context's stream", "one observer per handle".capitalize()):
-        assert word in block, word
+    abi.check_header_documents("viewshed analysis: a line-of-sight field", list(ENTRY_POINTS)[:4],
+                               ("DESIGN.md 4l", "VF_ERR_INVALID", "whether or not the viewshed is enabled", "NULL: the context's stream", "One observer per handle"))
 
 
 def test_null_handles_are_refused_without_a_device():
     from vulkan_forge_amd import cabi
-    lib = cabi.load()
     out = np.zeros(4, np.float32)
-    ms = (ctypes.c_float * 2)()
-    count = ctypes.c_uint32()
-    info = cabi.ViewshedInfo()
     xz, col = (ctypes.c_float * 2)(0.0, 0.0), (ctypes.c_uint8 * 4)(1, 2, 3, 4)
-    assert lib.vf_terrain_set_viewshed(None, 1, xz, 0.05, 0.0, 0.0, col, col, 0.02, 0.002) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_read_viewshed_field(None, out.ctypes.data) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_viewshed_field_device(None, None, None) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_viewshed_info(None, ctypes.byref(info)) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_viewshed_stage(None, 1, ms) == cabi.VF_ERR_INVALID
-    assert lib.vf_terrain_debug_viewshed_scans(None, ctypes.byref(count)) == cabi.VF_ERR_INVALID
+    abi.check_null_refusals([("vf_terrain_set_viewshed", (1, xz, 0.05, 0.0, 0.0, col, col, 0.02, 0.002)),
+                             ("vf_terrain_read_viewshed_field", (out.ctypes.data,)),
+                             ("vf_terrain_viewshed_field_device", (None, None)),
+                             ("vf_terrain_viewshed_info", (ctypes.byref(cabi.ViewshedInfo()),)),
+                             ("vf_terrain_debug_viewshed_stage", (1, (ctypes.c_float * 2)())),
+                             ("vf_terrain_debug_viewshed_scans", (ctypes.byref(ctypes.c_uint32()),))])
 
 
 @pytest.mark.parametrize("cls", ["Scene", "TerrainSpike"])
 def test_methods_exist_on_both_classes(cls):
-    import vulkan_forge
-    import vulkan_forge_amd
-    for pkg in (vulkan_forge, vulkan_forge_amd):
-        T = getattr(pkg, cls)
-        doc = T.set_viewshed.__doc__
-        assert re.search(r"set_viewshed\(self: [\w.]+, observer: object, \*, enabled: object = True, eye_height: object = 0.05\d*, "
-                         r"target_height: object = 0.0, radius: object = None, visible_rgba: object = \(64, 255, 96, 96\), "
-                         r"hidden_rgba: object = \(0, 0, 0, 0\), softness: object = 0.019\d+, bias: object = 0.002\d*\) -> None", doc), doc
-        assert re.search(r"clear_viewshed\(self: [\w.]+\) -> None", T.clear_viewshed.__doc__), T.clear_viewshed.__doc__
-        assert re.search(r"viewshed_field\(self: [\w.]+\) -> numpy", T.viewshed_field.__doc__), T.viewshed_field.__doc__
-        assert re.search(r"viewshed_info\(self: [\w.]+\) -> object", T.viewshed_info.__doc__), T.viewshed_info.__doc__
+    abi.check_method_docs(cls, {
+        "set_viewshed": r"set_viewshed\(self: [\w.]+, observer: object, \*, enabled: object = True, eye_height: object = 0.05\d*, "
+                        r"target_height: object = 0.0, radius: object = None, visible_rgba: object = \(64, 255, 96, 96\), "
+                        r"hidden_rgba: object = \(0, 0, 0, 0\), softness: object = 0.019\d+, bias: object = 0.002\d*\) -> None",
+        "clear_viewshed": r"clear_viewshed\(self: [\w.]+\) -> None",
+        "viewshed_field": r"viewshed_field\(self: [\w.]+\) -> numpy",
+        "viewshed_info": r"viewshed_info\(self: [\w.]+\) -> object"})
 
 
 def test_argument_rules():

@@ -3,31 +3,13 @@ exactly one owning (line, step); a hand-worked wall hides what lies behind it by
 target is seen, non-finite heights neither occlude nor hide; the field commutes with the eight symmetries of the square exactly; the
 three-launch decomposition of the kernels, emulated in numpy, equals the sequential walk; a float64 restatement agrees; and the scene
 the GPU tests draw is part hidden."""
-import os
-import sys
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, os.path.join(HERE, "overlay_model"))
-sys.path.insert(0, os.path.join(HERE, "viewshed_model"))
-import viewshed_model as vsm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402
-
-
-def smooth(n, seed=1):
-    rng = np.random.default_rng(seed)
-    x = np.linspace(0, 1, n, dtype=np.float64)
-    X, Z = np.meshgrid(x, x)
-    h = sum(rng.normal() * 0.2 / f * np.sin(2 * np.pi * f * (X * np.cos(a) + Z * np.sin(a)) + p)
-            for f, a, p in zip((1, 2, 3, 5), rng.uniform(0, 6.3, 4), rng.uniform(0, 6.3, 4)))
-    return h.astype(np.float32)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+from support import bits, smooth
+import viewshed_model as vsm
+from overlay_scenes import CAMERAS, GRID, heights
 
 
 def r_of(L, c, k):

@@ -1,10 +1,7 @@
 """Round 6, VERDICT r05 item 1 step 0: the image-order visibility walk (per pixel, descending primitive id, first exact hit wins) was
 modelled on the CPU before any kernel was written (tests/walk_model/).  The model's enumeration of candidate cells must be COMPLETE
 -- its winners equal the oracle's visibility -- or its step counts (profiles/r06_walk_step0.log: the no-go) would be meaningless."""
-import os
-import sys
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "walk_model"))
+import support  # noqa: F401  (tests/walk_model on sys.path)
 
 
 def test_the_walk_model_finds_the_oracles_winner_at_every_pixel(capsys):

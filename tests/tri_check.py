@@ -1,7 +1,7 @@
 """Triangle smoke path of a given library against the oracle at several sizes, with the shape of any difference.
 usage (GPU box): python tests/tri_check.py path/to/libvf.so"""
 import os, sys, ctypes as C
-sys.path.insert(0, os.getcwd())
+import support  # noqa: F401  (the repository root and the model directories on sys.path)
 import numpy as np
 import oracle
 from vulkan_forge_amd import cabi
