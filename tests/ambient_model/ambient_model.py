@@ -10,18 +10,11 @@ shadows are on as well; `rewritten` marks the pixels whose interpolated lit or a
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "shadow_model"))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
-import overlay_scenes  # noqa: E402
-import shadow_model as shm  # noqa: E402
-om = shm.om
+import model_support as ms
+import overlay_scenes
+import shadow_model as shm
 
 # The GPU field tests: (grid, exaggeration, reach, D) on overlay_scenes.heights(4, (97, 131)) -- a grid that is no multiple of 8 or 64,
 # a reach that crosses one tile boundary, one that crosses two, many chunks plus one, and a single direction.
@@ -70,24 +63,14 @@ def scene_heights(seed=7):
     return (overlay_scenes.heights(seed) * np.float32(0.01)).astype(np.float32)
 
 
-_lib = None
+SIGNATURES = {
+    "abm_field_heights": "i32(f32*, f32*, u32, f32*, u32, f32, f32, f32)",
+    "abm_frame": "i32(u8*, u8*, u32*, u32, u32, f32*, f32*, u32, u32, u32, u8*, i32, f32*?, f32*, f32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libabmodel.so", os.path.join(HERE, "ambient_model.c"),
-                           [os.path.join(T, "shadow_model", "shadow_model.c"), os.path.join(T, "gbuffer_model", "gbuffer_model.c"),
-                            os.path.join(T, "occlusion_model", "occlusion_model.c"), os.path.join(T, "polygon_model", "polygon_model.c"),
-                            os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.abm_field_heights.argtypes = [vp, vp, u32, vp, u32, f, f, f]
-        L.abm_field_heights.restype = i
-        L.abm_frame.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp, vp, f]
-        L.abm_frame.restype = i
-        _lib = L
-    return _lib
+    return ms.load("ambient_model", SIGNATURES)
 
 
 def field_heights(h, dirs, spacing=1.0, exag=1.0, reach=64.0):
@@ -96,29 +79,20 @@ def field_heights(h, dirs, spacing=1.0, exag=1.0, reach=64.0):
     assert h.ndim == 2 and h.shape[0] == h.shape[1]
     dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 2)
     sky = np.empty_like(h)
-    rc = lib().abm_field_heights(sky.ctypes.data, h.ctypes.data, h.shape[0], dirs.ctypes.data, len(dirs), spacing, exag, reach)
-    if rc != 0:
+    if lib().abm_field_heights(sky, h, h.shape[0], dirs, len(dirs), spacing, exag, reach) != 0:
         raise ValueError("a direction without a horizontal part, or a non-finite one")
     return sky
 
 
 def field(uniforms, height, grid, dirs, reach=64.0):
     """the field of the renderer's surface for the uniforms' spacing (u[36], at least 1e-8) and exaggeration (u[38])"""
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    u = ms.u44(uniforms)
     return field_heights(shm.heights(u, height, grid), dirs, float(max(u[36], np.float32(1e-8))), float(u[38]), reach)
 
 
 def frame(rgba, vis, uniforms, height, grid, lut_rgba8, sky, strength, lit=None, shade_mode=0):
     """-> (the frame with ambient occlusion (H, W, 4) uint8, rewritten (H, W) bool)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
-    sky = np.ascontiguousarray(sky, np.float32)
-    lit = None if lit is None else np.ascontiguousarray(lit, np.float32)
-    mask = np.empty((H, W), np.uint8)
-    assert lib().abm_frame(out.ctypes.data, mask.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0],
-                           grid, lut.ctypes.data, int(shade_mode), None if lit is None else lit.ctypes.data, sky.ctypes.data, strength) == 0
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
+    mask = np.empty(vis.shape, np.uint8)
+    assert lib().abm_frame(out, mask, vis, *scene, grid, ms.lut(lut_rgba8), int(shade_mode), ms.field(lit), ms.field(sky), strength) == 0
     return out, mask.astype(bool)

@@ -10,41 +10,29 @@ circle at the segment's p0; y of both ends = lift; size = clamp(width_px, 1, 64)
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "occlusion_model"))
-import occlusion_model as ocm  # noqa: E402
-om = ocm.om
+import model_support as ms
+import occlusion_model as ocm
+import overlay_model as om
+
 OVIN = om.OVIN
 
-_lib = None
+SIGNATURES = {
+    "ctm_heights": "void(f32*, u32, u32, u32, f32*)",
+    "ctm_extract": "u64(f32*, u32, f32, f32*, u32, f32, u32, u32, u32, u32, f32, i32, i32, rec48*?, u64)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = om.build_model("libctmodel.so", os.path.join(HERE, "contour_model.c"),
-                           [os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")])
-        vp, u32, u64, f, i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float, C.c_int
-        L.ctm_heights.argtypes = [vp, u32, u32, u32, vp]
-        L.ctm_heights.restype = None
-        L.ctm_extract.argtypes = [vp, u32, f, vp, u32, f, u32, u32, u32, u32, f, i, i, vp, u64]
-        L.ctm_extract.restype = u64
-        _lib = L
-    return _lib
+    return ms.load("contour_model", SIGNATURES)
 
 
 def surface(height, grid):
     """-> (n, n) float32, [j, i] = the displaced height h of grid vertex (i, j): the surface the renderer draws"""
-    tex = np.ascontiguousarray(height, np.float32)
     n = max(int(grid), 2)
     h = np.empty((n, n), np.float32)
-    lib().ctm_heights(tex.ctypes.data, tex.shape[1], tex.shape[0], grid, h.ctypes.data)
+    lib().ctm_heights(*ms.texture(height), grid, h)
     return h
 
 
@@ -67,11 +55,11 @@ def extract(h, spacing, levels, width_px=1.0, rgba=(0, 0, 0, 255), lift=0.0, joi
     lv = np.ascontiguousarray(levels, np.float32)
     flags = om.DRAPE | (ocm.OCCLUDE if occlude else 0)
     pad0 = ocm.kb_bits(depth_bias) if occlude else 0
-    args = (h.ctypes.data, n, float(spacing), lv.ctypes.data, len(lv), float(om._half(width_px)), om._rgba_word(rgba), flags, int(feature), pad0,
+    args = (h, n, float(spacing), lv, len(lv), float(om._half(width_px)), om._rgba_word(rgba), flags, int(feature), pad0,
             float(np.float32(lift)), int(join == "round"), int(bool(bracket)))
     nseg = int(lib().ctm_extract(*args, None, 0))
     recs = np.zeros(nseg * (2 if join == "round" else 1), OVIN)
-    assert int(lib().ctm_extract(*args, recs.ctypes.data, len(recs))) == nseg
+    assert int(lib().ctm_extract(*args, recs, len(recs))) == nseg
     return recs, nseg
 
 

@@ -10,14 +10,10 @@ The sum is an integer sum, count = (float32)sum / 65536, and the frame is the vi
 """
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "viewshed_model"))
-import viewshed_model as vsm  # noqa: E402
+import shadow_model as shm
+import viewshed_model as vsm
 
 DEFAULTS = dict(vsm.DEFAULTS)
 DEFAULT_HIGH, DEFAULT_LOW = (64, 255, 96, 160), (0, 0, 0, 0)
@@ -28,7 +24,6 @@ F32 = np.float32
 def scene_observers(extra=61, seed=70):
     """The GPU tests' observers at spacing 1: the nine of tests/test_gpu_viewshed.py (corners, edges, inside, outside the grid) and
     `extra` seeded uniform ones over the grid's extent -> (9 + extra, 2) float32"""
-    sys.path.insert(0, os.path.dirname(HERE))
     from test_gpu_viewshed import OBSERVERS
     rng = np.random.default_rng(seed)
     return np.concatenate([np.array(OBSERVERS, np.float32), rng.uniform(-1.5, 1.5, (extra, 2)).astype(np.float32)])
@@ -80,7 +75,7 @@ def field(uniforms, height, grid, observers, radius=None, eye_height=0.05, targe
     n = max(int(grid), 2)
     spacing = max(u[36], F32(1e-8))
     vertices = [vsm.observer_vertex(o, spacing, n) for o in np.asarray(observers, F32).reshape(-1, 2)]
-    total = sum_heights(vsm.shm.heights(u, height, grid), vertices, float(u[38]), None if radius is None else rc(radius, spacing, n),
+    total = sum_heights(shm.heights(u, height, grid), vertices, float(u[38]), None if radius is None else rc(radius, spacing, n),
                         eye_height, target_height, softness, bias)
     return (count(total), vertices, total) if want_sum else (count(total), vertices)
 

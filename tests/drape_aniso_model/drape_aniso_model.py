@@ -12,17 +12,11 @@ tap count N, the major axis (0 = x, 1 = y) and whether a tap was clamped to the 
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "drape_mip_model"))
-import drape_mip_model as dmm  # noqa: E402
-drm = dmm.drm
-om = drm.om
+import drape_mip_model as dmm
+import drape_model as drm
+import model_support as ms
 
 ANISOTROPIES = (1, 2, 4, 8, 16)
 # Where the case image (drape_mip_model.case_image) lies for each camera in the anisotropy tests: each extent is stretched along one
@@ -35,36 +29,23 @@ CASE_EXTENT = {"default": (-1.42, -47.7, 1.97, 48.45), "fill": (-8.0, -2.4, 8.5,
 # an extent inside the grid, so that taps near its edge leave the image rectangle and are clamped
 INTERIOR_EXTENT = (-0.7, -0.5, 0.9, 0.8)
 
-_lib = None
+SIGNATURES = {
+    "dam_frame": "i32(u8*, u8*, f32*?, u32*, u32, u32, f32*, f32*, u32, u32, u32, u8*, i32, u8*, u32, u32, u16*, f32*, f32, i32, f32, u32, f32*?, f32*?, f32)",
+    "dam_clipped_mask": "i32(u8*, u32*, u32, u32, f32*, f32*, u32, u32, u32)",
+    "dam_plan": "void(f32, f32, u32, f32, i32*, f32*, u32*)",
+    "dam_offset": "f32(u32, u32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libdranisomodel.so", os.path.join(HERE, "drape_aniso_model.c"),
-                           [os.path.join(T, "drape_mip_model", "drape_mip_model.c"), os.path.join(T, "drape_model", "drape_model.c"),
-                            os.path.join(T, "ambient_model", "ambient_model.c"), os.path.join(T, "shadow_model", "shadow_model.c"),
-                            os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.dam_frame.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp, u32, u32, vp, vp, f, i, f, u32, vp, vp, f]
-        L.dam_frame.restype = i
-        L.dam_clipped_mask.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32]
-        L.dam_clipped_mask.restype = i
-        L.dam_plan.argtypes = [f, f, u32, f, C.POINTER(i), C.POINTER(f), C.POINTER(u32)]
-        L.dam_plan.restype = None
-        L.dam_offset.argtypes = [u32, u32]
-        L.dam_offset.restype = f
-        _lib = L
-    return _lib
+    return ms.load("drape_aniso_model", SIGNATURES)
 
 
 def plan(ax, ay, max_anisotropy, bias=0.0):
     """items 1 - 4 on the squared lengths of the footprint's screen axes -> (ymajor, lod, N)"""
-    ym, lod, n = C.c_int(), C.c_float(), C.c_uint32()
-    lib().dam_plan(float(ax), float(ay), int(max_anisotropy), float(bias), C.byref(ym), C.byref(lod), C.byref(n))
-    return bool(ym.value), np.float32(lod.value), int(n.value)
+    ym, lod, n = np.zeros(1, np.int32), np.zeros(1, np.float32), np.zeros(1, np.uint32)
+    lib().dam_plan(float(ax), float(ay), int(max_anisotropy), float(bias), ym, lod, n)
+    return bool(ym[0]), lod[0], int(n[0])
 
 
 def offset(n, i):
@@ -74,12 +55,9 @@ def offset(n, i):
 
 def clipped_mask(vis, uniforms, height, grid):
     """(H, W) bool: the covered pixels that show a primitive cut by the near or the far plane (the kernels' generic path)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
+    _, vis, *scene = ms.frame(None, vis, uniforms, height)
     mask = np.empty(vis.shape, np.uint8)
-    assert lib().dam_clipped_mask(mask.ctypes.data, vis.ctypes.data, vis.shape[1], vis.shape[0], u.ctypes.data, tex.ctypes.data, tex.shape[1],
-                                  tex.shape[0], grid) == 0
+    assert lib().dam_clipped_mask(mask, vis, *scene, grid) == 0
     return mask.astype(bool)
 
 
@@ -87,22 +65,11 @@ def frame(rgba, vis, uniforms, height, grid, lut_rgba8, image, extent=None, opac
           lit=None, sky=None, strength=0.0, shade_mode=0, want_sample=False):
     """-> (the draped frame (H, W, 4) uint8, rewritten (H, W) bool[, sample (H, W, 10) float32])"""
     assert max_anisotropy in ANISOTROPIES and filter in ("linear", "nearest")
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
     img = drm.rgba8(image)
-    pyr, _ = dmm._flat(img)
-    ext = np.ascontiguousarray(drm.FULL_EXTENT if extent is None else extent, np.float32).reshape(4)
-    lit = None if lit is None else np.ascontiguousarray(lit, np.float32)
-    sky = None if sky is None else np.ascontiguousarray(sky, np.float32)
-    mask = np.empty((H, W), np.uint8)
-    sample = np.empty((H, W, 10), np.float32) if want_sample else None
-    assert lib().dam_frame(out.ctypes.data, mask.ctypes.data, None if sample is None else sample.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data,
-                           tex.ctypes.data, tex.shape[1], tex.shape[0], grid, lut.ctypes.data, int(shade_mode), img.ctypes.data, img.shape[1],
-                           img.shape[0], pyr.ctypes.data, ext.ctypes.data, float(opacity), 1 if filter == "linear" else 0, float(bias),
-                           int(max_anisotropy), None if lit is None else lit.ctypes.data, None if sky is None else sky.ctypes.data,
-                           float(strength)) == 0
+    mask = np.empty(vis.shape, np.uint8)
+    sample = np.empty(vis.shape + (10,), np.float32) if want_sample else None
+    assert lib().dam_frame(out, mask, sample, vis, *scene, grid, ms.lut(lut_rgba8), int(shade_mode), img, img.shape[1], img.shape[0],
+                           dmm._flat(img)[0], drm.extent4(extent), float(opacity), 1 if filter == "linear" else 0, float(bias),
+                           int(max_anisotropy), ms.field(lit), ms.field(sky), float(strength)) == 0
     return (out, mask.astype(bool), sample) if want_sample else (out, mask.astype(bool))

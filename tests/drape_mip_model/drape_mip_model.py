@@ -11,16 +11,10 @@ where the footprint gives none, +inf for an infinite one) of the pixels written 
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "drape_model"))
-import drape_model as drm  # noqa: E402
-om = drm.om
+import drape_model as drm
+import model_support as ms
 
 # The image the mip tests drape (seeded, opaque and transparent texels, odd and no power of two) and where it lies for each camera:
 # chosen so that each camera's rewritten pixels at (257, 131) and bias 0 hold magnified (or top-level) pixels, at least three
@@ -60,31 +54,17 @@ def sizes(iw, ih):
     return out
 
 
-_lib = None
+SIGNATURES = {
+    "dmm_pyramid": "i32(u16*, u8*, u32, u32)",
+    "dmm_frame": "i32(u8*, u8*, f32*?, u32*, u32, u32, f32*, f32*, u32, u32, u32, u8*, i32, u8*, u32, u32, u16*, f32*, f32, i32, f32, f32*?, f32*?, f32)",
+    "dmm_clipped_pixels": "i32(u32*, u32, u32, f32*, f32*, u32, u32, u32)",
+    "dmm_half_bits": "u16(f32)",
+    "dmm_half_value": "f32(u16)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libdrmipmodel.so", os.path.join(HERE, "drape_mip_model.c"),
-                           [os.path.join(T, "drape_model", "drape_model.c"),
-                            os.path.join(T, "ambient_model", "ambient_model.c"), os.path.join(T, "shadow_model", "shadow_model.c"),
-                            os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.dmm_pyramid.argtypes = [vp, vp, u32, u32]
-        L.dmm_pyramid.restype = i
-        L.dmm_frame.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp, u32, u32, vp, vp, f, i, f, vp, vp, f]
-        L.dmm_frame.restype = i
-        L.dmm_clipped_pixels.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32]
-        L.dmm_clipped_pixels.restype = i
-        L.dmm_half_bits.argtypes = [f]
-        L.dmm_half_bits.restype = C.c_uint16
-        L.dmm_half_value.argtypes = [C.c_uint16]
-        L.dmm_half_value.restype = f
-        _lib = L
-    return _lib
+    return ms.load("drape_mip_model", SIGNATURES)
 
 
 _pyramids = {}
@@ -97,7 +77,7 @@ def _flat(img):
         ih, iw = img.shape[:2]
         sz = sizes(iw, ih)
         buf = np.zeros(max(1, 4 * sum(w * h for w, h in sz[1:])), np.uint16)
-        assert lib().dmm_pyramid(buf.ctypes.data, img.ctypes.data, iw, ih) == len(sz)
+        assert lib().dmm_pyramid(buf, img, iw, ih) == len(sz)
         _pyramids[key] = (buf, sz)
     return _pyramids[key]
 
@@ -114,10 +94,7 @@ def pyramid(image):
 
 def clipped_pixels(vis, uniforms, height, grid):
     """how many covered pixels show a primitive cut by the near or the far plane (the kernels' generic path)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    n = lib().dmm_clipped_pixels(vis.ctypes.data, vis.shape[1], vis.shape[0], u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid)
+    n = lib().dmm_clipped_pixels(*ms.frame(None, vis, uniforms, height)[1:], grid)
     assert n >= 0
     return n
 
@@ -125,22 +102,12 @@ def clipped_pixels(vis, uniforms, height, grid):
 def frame(rgba, vis, uniforms, height, grid, lut_rgba8, image, extent=None, opacity=1.0, filter="linear", bias=0.0, lit=None, sky=None,
           strength=0.0, shade_mode=0, want_sample=False):
     """-> (the draped frame (H, W, 4) uint8, rewritten (H, W) bool[, sample (H, W, 7) float32])"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
     img = drm.rgba8(image)
-    pyr, _ = _flat(img)
-    ext = np.ascontiguousarray(drm.FULL_EXTENT if extent is None else extent, np.float32).reshape(4)
-    lit = None if lit is None else np.ascontiguousarray(lit, np.float32)
-    sky = None if sky is None else np.ascontiguousarray(sky, np.float32)
-    mask = np.empty((H, W), np.uint8)
-    sample = np.empty((H, W, 7), np.float32) if want_sample else None
+    mask = np.empty(vis.shape, np.uint8)
+    sample = np.empty(vis.shape + (7,), np.float32) if want_sample else None
     assert filter in ("linear", "nearest")
-    assert lib().dmm_frame(out.ctypes.data, mask.ctypes.data, None if sample is None else sample.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data,
-                           tex.ctypes.data, tex.shape[1], tex.shape[0], grid, lut.ctypes.data, int(shade_mode), img.ctypes.data, img.shape[1],
-                           img.shape[0], pyr.ctypes.data, ext.ctypes.data, float(opacity), 1 if filter == "linear" else 0, float(bias),
-                           None if lit is None else lit.ctypes.data, None if sky is None else sky.ctypes.data, float(strength)) == 0
+    assert lib().dmm_frame(out, mask, sample, vis, *scene, grid, ms.lut(lut_rgba8), int(shade_mode), img, img.shape[1], img.shape[0], _flat(img)[0],
+                           drm.extent4(extent), float(opacity), 1 if filter == "linear" else 0, float(bias), ms.field(lit), ms.field(sky),
+                           float(strength)) == 0
     return (out, mask.astype(bool), sample) if want_sample else (out, mask.astype(bool))

@@ -11,17 +11,11 @@ again and `sample` (H, W, 6) float32 holds their filtered premultiplied (r, g, b
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "ambient_model"))
-import ambient_model as abm  # noqa: E402
-shm = abm.shm
-om = abm.om
+import ambient_model as abm  # noqa: F401  (tests reach these two as drm.abm and drm.shm)
+import model_support as ms
+import shadow_model as shm  # noqa: F401
 
 FULL_EXTENT = (-1.5, -1.5, 1.5, 1.5)
 # The tests' image and where it lies: 37 x 53 texels (iw x ih) over a part of the grid and beyond its z edge (the grid ends at 1.5).
@@ -50,22 +44,13 @@ def opaque_image(size, seed=3):
     return img
 
 
-_lib = None
+SIGNATURES = {
+    "drm_frame": "i32(u8*, u8*, f32*?, u32*, u32, u32, f32*, f32*, u32, u32, u32, u8*, i32, u8*, u32, u32, f32*, f32, i32, f32*?, f32*?, f32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libdrmodel.so", os.path.join(HERE, "drape_model.c"),
-                           [os.path.join(T, "ambient_model", "ambient_model.c"), os.path.join(T, "shadow_model", "shadow_model.c"),
-                            os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.drm_frame.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp, u32, u32, vp, f, i, vp, vp, f]
-        L.drm_frame.restype = i
-        _lib = L
-    return _lib
+    return ms.load("drape_model", SIGNATURES)
 
 
 def rgba8(img):
@@ -77,24 +62,19 @@ def rgba8(img):
     return np.ascontiguousarray(img)
 
 
+def extent4(extent):
+    """the image's (x0, z0, x1, z1) as four float32; None: the whole grid"""
+    return np.ascontiguousarray(FULL_EXTENT if extent is None else extent, np.float32).reshape(4)
+
+
 def frame(rgba, vis, uniforms, height, grid, lut_rgba8, image, extent=None, opacity=1.0, filter="linear", lit=None, sky=None, strength=0.0,
           shade_mode=0, want_sample=False):
     """-> (the draped frame (H, W, 4) uint8, rewritten (H, W) bool[, sample (H, W, 6) float32])"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
     img = rgba8(image)
-    ext = np.ascontiguousarray(FULL_EXTENT if extent is None else extent, np.float32).reshape(4)
-    lit = None if lit is None else np.ascontiguousarray(lit, np.float32)
-    sky = None if sky is None else np.ascontiguousarray(sky, np.float32)
-    mask = np.empty((H, W), np.uint8)
-    sample = np.empty((H, W, 6), np.float32) if want_sample else None
+    mask = np.empty(vis.shape, np.uint8)
+    sample = np.empty(vis.shape + (6,), np.float32) if want_sample else None
     assert filter in ("linear", "nearest")
-    assert lib().drm_frame(out.ctypes.data, mask.ctypes.data, None if sample is None else sample.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data,
-                           tex.ctypes.data, tex.shape[1], tex.shape[0], grid, lut.ctypes.data, int(shade_mode), img.ctypes.data, img.shape[1],
-                           img.shape[0], ext.ctypes.data, float(opacity), 1 if filter == "linear" else 0,
-                           None if lit is None else lit.ctypes.data, None if sky is None else sky.ctypes.data, float(strength)) == 0
+    assert lib().drm_frame(out, mask, sample, vis, *scene, grid, ms.lut(lut_rgba8), int(shade_mode), img, img.shape[1], img.shape[0],
+                           extent4(extent), float(opacity), 1 if filter == "linear" else 0, ms.field(lit), ms.field(sky), float(strength)) == 0
     return (out, mask.astype(bool), sample) if want_sample else (out, mask.astype(bool))

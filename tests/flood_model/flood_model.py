@@ -11,45 +11,29 @@ each blended pixel's interpolated depth, -1 where the pass leaves the pixel.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
 from collections import namedtuple
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "viewshed_model"))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "contour_model"))
-import contour_model as cm  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
-om = vsm.om
+import contour_model as cm
+import model_support as ms
+import overlay_model as om  # noqa: F401  (tests reach it as fdm.om)
+import viewshed_model as vsm
 
 TILE = 64
 EVERYWHERE, EDGES, SEEDS = 0, 1, 2
 DEFAULT_SHALLOW, DEFAULT_DEEP, DEFAULT_DEPTH_FULL = (96, 176, 224, 128), (16, 64, 160, 224), 0.1
 Field = namedtuple("Field", "depth flooded wet wd vertices")
 
-_lib = None
+SIGNATURES = {
+    "fdm_field": "i64(u8*, u8*, f32*, f32*, f32*, u32, f32, i32, u32*?, u32)",
+    "fdm_label_tiles": "i64(i32*, u8*, u32, u32)",
+    "fdm_frame": "i32(u8*, f32*, u32*, u32, u32, f32*, f32*, u32, u32, u32, u8*, f32*, u32, u32, f32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libfdmodel.so", os.path.join(HERE, "flood_model.c"),
-                           [os.path.join(T, "viewshed_model", "viewshed_model.c"), os.path.join(T, "shadow_model", "shadow_model.c"),
-                            os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.fdm_field.argtypes = [vp, vp, vp, vp, vp, u32, f, i, vp, u32]
-        L.fdm_field.restype = C.c_int64
-        L.fdm_label_tiles.argtypes = [vp, vp, u32, u32]
-        L.fdm_label_tiles.restype = C.c_int64
-        L.fdm_frame.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, vp, u32, u32, f]
-        L.fdm_frame.restype = i
-        _lib = L
-    return _lib
+    return ms.load("flood_model", SIGNATURES)
 
 
 def mode_of(seeds):
@@ -70,8 +54,7 @@ def field_heights(h, level, seeds=None):
     ij = np.ascontiguousarray(seeds, np.uint32).reshape(-1, 2) if mode == SEEDS else None
     wet, fl = np.empty((n, n), np.uint8), np.empty((n, n), np.uint8)
     wd, depth = np.empty((n, n), np.float32), np.empty((n, n), np.float32)
-    got = lib().fdm_field(wet.ctypes.data, fl.ctypes.data, wd.ctypes.data, depth.ctypes.data, h.ctypes.data, n, float(np.float32(level)), mode,
-                          ij.ctypes.data if ij is not None else None, len(ij) if ij is not None else 0)
+    got = lib().fdm_field(wet, fl, wd, depth, h, n, float(np.float32(level)), mode, ij, len(ij) if ij is not None else 0)
     assert got == int(fl.sum()) and got >= 0
     return Field(depth, fl.astype(bool), wet.astype(bool), wd, ij)
 
@@ -103,7 +86,7 @@ def label_tiles(wet, tile=TILE):
     """(n, n) int32: 0 where not wet-able, else the number of the vertex's 4-connected component inside its tile"""
     w = np.ascontiguousarray(wet, np.uint8)
     lab = np.empty(w.shape, np.int32)
-    assert lib().fdm_label_tiles(lab.ctypes.data, w.ctypes.data, w.shape[0], tile) >= 0
+    assert lib().fdm_label_tiles(lab, w, w.shape[0], tile) >= 0
     return lab
 
 
@@ -146,16 +129,10 @@ def tiles_reached(flooded, tile=TILE):
 
 def frame(rgba, vis, uniforms, height, grid, F, shallow_rgba=DEFAULT_SHALLOW, deep_rgba=DEFAULT_DEEP, depth_full=DEFAULT_DEPTH_FULL):
     """-> (the frame with the water (H, W, 4) uint8, d (H, W) float32)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    fl = np.ascontiguousarray(F.flooded, np.uint8)
-    wd = np.ascontiguousarray(F.wd, np.float32)
-    d = np.empty((H, W), np.float32)
-    assert lib().fdm_frame(out.ctypes.data, d.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
-                           fl.ctypes.data, wd.ctypes.data, vsm.pack(shallow_rgba), vsm.pack(deep_rgba), float(depth_full)) == 0
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
+    d = np.empty(vis.shape, np.float32)
+    assert lib().fdm_frame(out, d, vis, *scene, grid, np.ascontiguousarray(F.flooded, np.uint8), ms.field(F.wd), ms.pack(shallow_rgba),
+                           ms.pack(deep_rgba), float(depth_full)) == 0
     return out, d
 
 

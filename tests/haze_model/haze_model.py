@@ -9,16 +9,10 @@
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "gbuffer_model"))
-import gbuffer_model as gbm  # noqa: E402
-om = gbm.om
+import gbuffer_model as gbm  # noqa: F401  (tests reach it as hzm.gbm)
+import model_support as ms
 
 DEFAULTS = dict(rgba=(200, 215, 235, 255), start=0.0, falloff=None, base=0.0, max_opacity=1.0, background=False)
 SERIES_BELOW = 0.5            # |s| below this: the series branch of g (HZ_SERIES_BELOW)
@@ -32,55 +26,34 @@ SCENE_PARAMS = {"default": dict(density=0.6, start=4.5), "fill": dict(density=0.
 SCENE_FALLOFFS = (0.3, 4.0, 50.0)
 SCENE_BASE = 0.2
 
-_lib = None
+SIGNATURES = {
+    "hzm_det_exp": "f32(f32)",
+    "hzm_det_exp_n": "void(f32*, f32*, u32)",
+    "hzm_eye_y": "f32(f32*)",
+    "hzm_g_branch": "f32(f32, f32, i32)",
+    "hzm_g": "f32(f32, f32, f32, f32)",
+    "hzm_g_which": "i32(f32, f32, f32, f32)",
+    "hzm_alpha": "f32(f32, f32, f32, f32, f32, f32, f32, f32, u32)",
+    "hzm_blend": "void(u8*, u32, f32)",
+    "hzm_frame": "i32(u8*, f32*, i8*?, u32*, u32, u32, f32*, f32*, u32, u32, u32, f32, u32, f32, f32, f32, f32, i32)",
+}
+pack = ms.pack
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libhzmodel.so", os.path.join(HERE, "haze_model.c"),
-                           [os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.hzm_det_exp.argtypes = [f]
-        L.hzm_det_exp.restype = f
-        L.hzm_det_exp_n.argtypes = [vp, vp, u32]
-        L.hzm_det_exp_n.restype = None
-        L.hzm_eye_y.argtypes = [vp]
-        L.hzm_eye_y.restype = f
-        L.hzm_g_branch.argtypes = [f, f, i]
-        L.hzm_g_branch.restype = f
-        L.hzm_g.argtypes = [f, f, f, f]
-        L.hzm_g.restype = f
-        L.hzm_g_which.argtypes = [f, f, f, f]
-        L.hzm_g_which.restype = i
-        L.hzm_alpha.argtypes = [f, f, f, f, f, f, f, f, u32]
-        L.hzm_alpha.restype = f
-        L.hzm_blend.argtypes = [vp, u32, f]
-        L.hzm_blend.restype = None
-        L.hzm_frame.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, f, u32, f, f, f, f, i]
-        L.hzm_frame.restype = i
-        _lib = L
-    return _lib
-
-
-def pack(rgba):
-    r, g, b, a = (int(v) for v in rgba)
-    return r | g << 8 | b << 16 | a << 24
+    return ms.load("haze_model", SIGNATURES)
 
 
 def det_exp(x):
     """the contract's exponential (item 8) of a float or an array of floats in [-87, 16] -> float32"""
     x = np.ascontiguousarray(x, np.float32)
     out = np.empty_like(x)
-    lib().hzm_det_exp_n(out.ctypes.data, x.ctypes.data, x.size)
+    lib().hzm_det_exp_n(out, x, x.size)
     return out[()]
 
 
 def eye_y(uniforms):
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    return np.float32(lib().hzm_eye_y(u.ctypes.data))
+    return np.float32(lib().hzm_eye_y(ms.u44(uniforms)))
 
 
 def g_branch(k_e, k_p, branch=-1):
@@ -101,7 +74,7 @@ def alpha(d, y, eye, density, rgba=DEFAULTS["rgba"], start=0.0, falloff=None, ba
 def blend(pixel_rgb, rgba, a):
     """three colour bytes under the haze colour with opacity a (item 6) -> three bytes"""
     px = np.array(list(pixel_rgb)[:3], np.uint8)
-    lib().hzm_blend(px.ctypes.data, pack(rgba), float(a))
+    lib().hzm_blend(px, pack(rgba), float(a))
     return tuple(int(v) for v in px)
 
 
@@ -109,15 +82,9 @@ def frame(frame_rgba, vis, uniforms, height, grid, density, rgba=DEFAULTS["rgba"
           background=False, want_branch=False):
     """frame_rgba: the frame without haze; the other keywords are set_haze's (rgba: the haze colour)
     -> (the hazed frame (H, W, 4) uint8, a (H, W) float32[, which (H, W) int8])"""
-    colour = rgba
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(frame_rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    a = np.empty((H, W), np.float32)
-    which = np.empty((H, W), np.int8) if want_branch else None
-    assert lib().hzm_frame(out.ctypes.data, a.ctypes.data, which.ctypes.data if want_branch else None, vis.ctypes.data, W, H, u.ctypes.data,
-                           tex.ctypes.data, tex.shape[1], tex.shape[0], grid, float(density), pack(colour), float(start),
-                           0.0 if falloff is None else float(falloff), float(base), float(max_opacity), 1 if background else 0) == 0
+    out, vis, *scene = ms.frame(frame_rgba, vis, uniforms, height)
+    a = np.empty(vis.shape, np.float32)
+    which = np.empty(vis.shape, np.int8) if want_branch else None
+    assert lib().hzm_frame(out, a, which, vis, *scene, grid, float(density), pack(rgba), float(start), 0.0 if falloff is None else float(falloff),
+                           float(base), float(max_opacity), 1 if background else 0) == 0
     return (out, a, which) if want_branch else (out, a)

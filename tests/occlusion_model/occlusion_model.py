@@ -11,36 +11,23 @@ vf_terrain_set_layer_occlusion writes them.
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "polygon_model"))
-import polygon_model as pm  # noqa: E402
-om = pm.om
+import model_support as ms
+import overlay_model as om
+import polygon_model as pm
 
 OCCLUDE = 32
 DEPTH_BIAS = 1e-2                                             # the library's default (include/vf_hip.h VF_OCCLUSION_DEPTH_BIAS)
 
-_lib = None
+SIGNATURES = {
+    "ocm_composite": "i32(u8*, u32*, u32, u32, f32*, f32*, u32, u32, u32, rec48*, u32, u32, u32*, u32*, u8*, u32*, u32*, f32*)",
+    "ocm_terrain_q": "i32(f32*, u8*, u32*, u32, u32, f32*, f32*, u32, u32, u32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = om.build_model("libocmodel.so", os.path.join(HERE, "occlusion_model.c"),
-                           [os.path.join(os.path.dirname(HERE), "polygon_model", "polygon_model.c"),
-                            os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")])
-        vp, u32, i = C.c_void_p, C.c_uint32, C.c_int
-        L.ocm_composite.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
-        L.ocm_composite.restype = i
-        L.ocm_terrain_q.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32]
-        L.ocm_terrain_q.restype = i
-        _lib = L
-    return _lib
+    return ms.load("occlusion_model", SIGNATURES)
 
 
 def kb_bits(depth_bias):
@@ -92,37 +79,17 @@ class Layers(pm.Layers):
 def composite(frame, vis, uniforms, height, grid, layers):
     """frame (H, W, 4) uint8, vis (H, W) uint32 -> a new frame with the layers composited over it (the contract, on the CPU)."""
     out = np.array(frame, np.uint8, copy=True, order="C")
-    H, W = out.shape[:2]
-    vis = np.ascontiguousarray(vis, np.uint32)
-    assert vis.shape == (H, W)
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    recs = np.ascontiguousarray(layers.array())
-    fills = getattr(layers, "fills", [])
-    feat = np.array([f[0] for f in fills], np.uint32)
-    cols = np.array([f[1] for f in fills], np.uint32)
-    drape = np.array([f[2] for f in fills], np.uint8)
-    rings = [r for f in fills for r in f[3]]
-    fr = np.zeros(len(fills) + 1, np.uint32)
-    fr[1:] = np.cumsum([len(f[3]) for f in fills])
-    offs, xyz = pm._pack(rings)
-    rc = lib().ocm_composite(out.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
-                             recs.ctypes.data, len(recs), len(fills), feat.ctypes.data, cols.ctypes.data, drape.ctypes.data,
-                             fr.ctypes.data, offs.ctypes.data, xyz.ctypes.data)
-    assert rc == 0
+    _, vis, *scene = ms.frame(None, vis, uniforms, height)
+    assert vis.shape == out.shape[:2]
+    assert lib().ocm_composite(out, vis, *scene, grid, *pm.fill_args(layers)) == 0
     return out
 
 
 def terrain_q(vis, uniforms, height, grid):
     """-> (Q (H, W) float32: the terrain's interpolated 1/w at each pixel centre, 0 on background; clipped (H, W) bool: the pixel's
     primitive has a vertex outside 0 <= z <= w, so it took the generic path)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    Q = np.zeros((H, W), np.float32)
-    clipped = np.zeros((H, W), np.uint8)
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    rc = lib().ocm_terrain_q(Q.ctypes.data, clipped.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1],
-                             tex.shape[0], grid)
-    assert rc == 0
+    _, vis, *scene = ms.frame(None, vis, uniforms, height)
+    Q = np.zeros(vis.shape, np.float32)
+    clipped = np.zeros(vis.shape, np.uint8)
+    assert lib().ocm_terrain_q(Q, clipped, vis, *scene, grid) == 0
     return Q, clipped.astype(bool)

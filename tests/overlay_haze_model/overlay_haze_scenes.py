@@ -2,16 +2,10 @@
 from being vacuous ("What was verified"): the frame sizes, the haze settings per camera and the hazed layers, as
 (method, args, kwargs) calls for overlay_scenes.apply.  The grid, the heights and the cameras are overlay_scenes' (tests/test_gpu_haze.py's).
 """
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-for _m in ("overlay_model", "haze_model"):
-    sys.path.insert(0, os.path.join(os.path.dirname(HERE), _m))
-import haze_model as hzm  # noqa: E402
-from overlay_scenes import CAMERAS, GRID, heights  # noqa: E402,F401
+import haze_model as hzm
+from overlay_scenes import CAMERAS, GRID, heights  # noqa: F401
 
 SIZES = [(96, 64), (71, 45)]
 CAMS = ["default", "fill", "near"]

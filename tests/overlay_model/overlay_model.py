@@ -10,14 +10,9 @@ for round caps, at both ends; square caps extend the first and last segment by t
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+import model_support as ms
 
 OVIN = np.dtype([("p0", "<f4", (3,)), ("p1", "<f4", (3,)), ("size", "<f4"), ("flags", "<u4"), ("rgba", "<u4"), ("feature", "<u4"),
                  ("pad", "<u4", (2,))])
@@ -26,47 +21,24 @@ CIRCLE, SQUARE, SEGMENT, DRAPE, EXT0, EXT1 = 0, 1, 2, 4, 8, 16
 SHAPES = {"circle": CIRCLE, "square": SQUARE}
 CAPS = ("butt", "square", "round")
 
-_lib = None
-
-
-def build_model(out_name, src, deps=()):
-    """-> the CPU model `src` (C) loaded from build/`out_name`, compiled again when that is older than `src` or any of `deps` (the
-    model sources it includes)"""
-    out = os.path.join(ROOT, "build", out_name)
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in (src, *deps)):
-        tmp = out + f".{os.getpid()}.tmp"
-        subprocess.check_call(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", src, "-o", tmp, "-lm"])
-        os.replace(tmp, out)
-    return C.CDLL(out)
+SIGNATURES = {
+    "ovm_composite": "i32(u8*, u32, u32, f32*, f32*, u32, u32, u32, rec48*, u32)",
+    "ovm_decode": "f32(u32)",
+    "ovm_encode": "u32(f32)",
+    "ovm_drape": "f32(f32*, f32*, u32, u32, u32, f32, f32)",
+    "ovm_vertex_height": "f32(f32*, u32, u32, u32, u32, u32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = build_model("libovmodel.so", os.path.join(HERE, "overlay_model.c"))
-        vp, u32, f = C.c_void_p, C.c_uint32, C.c_float
-        L.ovm_composite.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32]
-        L.ovm_composite.restype = C.c_int
-        L.ovm_decode.argtypes = [u32]
-        L.ovm_decode.restype = f
-        L.ovm_encode.argtypes = [f]
-        L.ovm_encode.restype = u32
-        L.ovm_drape.argtypes = [vp, vp, u32, u32, u32, f, f]
-        L.ovm_drape.restype = f
-        L.ovm_vertex_height.argtypes = [vp, u32, u32, u32, u32, u32]
-        L.ovm_vertex_height.restype = f
-        _lib = L
-    return _lib
+    return ms.load("overlay_model", SIGNATURES)
 
 
 def _half(v):
     return np.float32(min(max(np.float32(v), np.float32(1.0)), np.float32(64.0))) * np.float32(0.5)
 
 
-def _rgba_word(c):
-    c = [int(v) for v in c]
-    return c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24)
+_rgba_word = ms.pack
 
 
 class Layers:
@@ -135,12 +107,8 @@ def composite(frame, uniforms, height, grid, layers):
     """frame (H, W, 4) uint8 -> a new frame with the layers composited over it (the contract, on the CPU)."""
     out = np.array(frame, np.uint8, copy=True, order="C")
     H, W = out.shape[:2]
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
     recs = np.ascontiguousarray(layers.array() if isinstance(layers, Layers) else layers)
-    rc = lib().ovm_composite(out.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
-                             recs.ctypes.data, len(recs))
-    assert rc == 0
+    assert lib().ovm_composite(out, W, H, ms.u44(uniforms), *ms.texture(height), grid, recs, len(recs)) == 0
     return out
 
 
@@ -153,11 +121,8 @@ def encode(c):
 
 
 def drape(uniforms, height, grid, x, z):
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    return lib().ovm_drape(u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid, float(x), float(z))
+    return lib().ovm_drape(ms.u44(uniforms), *ms.texture(height), grid, float(x), float(z))
 
 
 def vertex_height(height, grid, i, j):
-    tex = np.ascontiguousarray(height, np.float32)
-    return lib().ovm_vertex_height(tex.ctypes.data, tex.shape[1], tex.shape[0], grid, i, j)
+    return lib().ovm_vertex_height(*ms.texture(height), grid, i, j)

@@ -10,33 +10,20 @@ as given (vulkan_forge.pack_polygons does the duplicate and closing-vertex remov
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "overlay_model"))
-import overlay_model as om  # noqa: E402
+import model_support as ms
+import overlay_model as om
 
-_lib = None
+SIGNATURES = {
+    "pgm_composite": "i32(u8*, u32, u32, f32*, f32*, u32, u32, u32, rec48*, u32, u32, u32*, u32*, u8*, u32*, u32*, f32*)",
+    "pgm_fill_coverage": "i32(f32*, u32, u32, f32*, f32*, u32, u32, u32, u32, u32*, f32*, i32)",
+    "pgm_ring_edges": "i32(f32*, u32, u32, f32*, f32*, u32, u32, u32, f32*, u32, i32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        L = om.build_model("libpgmodel.so", os.path.join(HERE, "polygon_model.c"),
-                           [os.path.join(os.path.dirname(HERE), "overlay_model", "overlay_model.c")])
-        vp, u32, i = C.c_void_p, C.c_uint32, C.c_int
-        L.pgm_composite.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, vp, vp, vp, vp, vp, vp]
-        L.pgm_composite.restype = i
-        L.pgm_fill_coverage.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, u32, vp, vp, i]
-        L.pgm_fill_coverage.restype = i
-        L.pgm_ring_edges.argtypes = [vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, i]
-        L.pgm_ring_edges.restype = i
-        _lib = L
-    return _lib
+    return ms.load("polygon_model", SIGNATURES)
 
 
 def _rings(poly):
@@ -74,38 +61,32 @@ def _pack(rings):
     return offs, xyz
 
 
+def fill_args(layers):
+    """the records and the fill features of `layers` as the composites of this, the occlusion and the hazed-overlay model take them:
+    (records, their count, the number of fills, their features, colours, drape flags, ring ranges, the rings' vertex offsets, xyz)"""
+    recs = np.ascontiguousarray(layers.array())
+    fills = getattr(layers, "fills", [])
+    feat = np.array([f[0] for f in fills], np.uint32)
+    cols = np.array([f[1] for f in fills], np.uint32)
+    drape = np.array([f[2] for f in fills], np.uint8)
+    fr = np.zeros(len(fills) + 1, np.uint32)
+    fr[1:] = np.cumsum([len(f[3]) for f in fills])
+    return (recs, len(recs), len(fills), feat, cols, drape, fr, *_pack([r for f in fills for r in f[3]]))
+
+
 def composite(frame, uniforms, height, grid, layers):
     """frame (H, W, 4) uint8 -> a new frame with the layers composited over it (the contract, on the CPU)."""
     out = np.array(frame, np.uint8, copy=True, order="C")
     H, W = out.shape[:2]
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    recs = np.ascontiguousarray(layers.array())
-    fills = layers.fills
-    feat = np.array([f[0] for f in fills], np.uint32)
-    cols = np.array([f[1] for f in fills], np.uint32)
-    drape = np.array([f[2] for f in fills], np.uint8)
-    rings = [r for f in fills for r in f[3]]
-    fr = np.zeros(len(fills) + 1, np.uint32)
-    fr[1:] = np.cumsum([len(f[3]) for f in fills])
-    offs, xyz = _pack(rings)
-    rc = lib().pgm_composite(out.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
-                             recs.ctypes.data, len(recs), len(fills), feat.ctypes.data, cols.ctypes.data, drape.ctypes.data,
-                             fr.ctypes.data, offs.ctypes.data, xyz.ctypes.data)
-    assert rc == 0
+    assert lib().pgm_composite(out, W, H, ms.u44(uniforms), *ms.texture(height), grid, *fill_args(layers)) == 0
     return out
 
 
 def fill_coverage(W, H, uniforms, height, grid, polygon, drape=False):
     """(H, W) float32 coverage of one polygon's fill"""
     cov = np.zeros((H, W), np.float32)
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
     rings = _rings(polygon)
-    offs, xyz = _pack(rings)
-    rc = lib().pgm_fill_coverage(cov.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid, len(rings),
-                                 offs.ctypes.data, xyz.ctypes.data, int(bool(drape)))
-    assert rc == 0
+    assert lib().pgm_fill_coverage(cov, W, H, ms.u44(uniforms), *ms.texture(height), grid, len(rings), *_pack(rings), int(bool(drape))) == 0
     return cov
 
 
@@ -116,9 +97,6 @@ def ring_edges(W, H, uniforms, height, grid, ring, drape=False):
     """(n, 10) float32: one ring's screen edge set after near-plane clipping, columns EDGE"""
     ring = np.ascontiguousarray(ring, np.float32).reshape(-1, 3)
     out = np.zeros((2 * len(ring), 10), np.float32)
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    n = lib().pgm_ring_edges(out.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid, ring.ctypes.data,
-                             len(ring), int(bool(drape)))
+    n = lib().pgm_ring_edges(out, W, H, ms.u44(uniforms), *ms.texture(height), grid, ring, len(ring), int(bool(drape)))
     assert n >= 0
     return out[:n]

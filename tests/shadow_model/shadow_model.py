@@ -10,16 +10,9 @@
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "gbuffer_model"))
-import gbuffer_model as gbm  # noqa: E402
-om = gbm.om
+import model_support as ms
 
 DEFAULTS = dict(strength=0.7, softness=0.02, bias=0.002)
 # The GPU tests' scene (overlay_scenes.heights() on GRID vertices) is white noise on four-vertex plateaus: slopes of about 100.  Under
@@ -36,25 +29,15 @@ def sun_vector(elevation_deg, azimuth_deg):
     v = np.array([np.cos(el) * np.cos(az), np.sin(el), np.cos(el) * np.sin(az)], np.float32)
     return v / np.sqrt((v * v).sum(dtype=np.float32))
 
-_lib = None
+SIGNATURES = {
+    "shm_field_heights": "i32(f32*, f32*, u32, f32*, f32, f32, f32, f32, f32)",
+    "shm_heights": "i32(f32*, f32*, f32*, u32, u32, u32)",
+    "shm_frame": "i32(u8*, u8*, u32*, u32, u32, f32*, f32*, u32, u32, u32, u8*, i32, f32*)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libshmodel.so", os.path.join(HERE, "shadow_model.c"),
-                           [os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.shm_field_heights.argtypes = [vp, vp, u32, vp, f, f, f, f, f]
-        L.shm_field_heights.restype = i
-        L.shm_heights.argtypes = [vp, vp, vp, u32, u32, u32]
-        L.shm_heights.restype = i
-        L.shm_frame.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, i, vp]
-        L.shm_frame.restype = i
-        _lib = L
-    return _lib
+    return ms.load("shadow_model", SIGNATURES)
 
 
 def field_heights(h, sun, spacing=1.0, exag=1.0, strength=0.7, softness=0.02, bias=0.002):
@@ -63,36 +46,27 @@ def field_heights(h, sun, spacing=1.0, exag=1.0, strength=0.7, softness=0.02, bi
     assert h.ndim == 2 and h.shape[0] == h.shape[1]
     sun = np.ascontiguousarray(sun, np.float32).reshape(3)
     lit = np.empty_like(h)
-    assert lib().shm_field_heights(lit.ctypes.data, h.ctypes.data, h.shape[0], sun.ctypes.data, spacing, exag, strength, softness, bias) == 0
+    assert lib().shm_field_heights(lit, h, h.shape[0], sun, spacing, exag, strength, softness, bias) == 0
     return lit
 
 
 def heights(uniforms, height, grid):
     """the displaced heights the renderer draws, (n, n) float32"""
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
     n = max(int(grid), 2)
     h = np.empty((n, n), np.float32)
-    assert lib().shm_heights(h.ctypes.data, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid) == 0
+    assert lib().shm_heights(h, ms.u44(uniforms), *ms.texture(height), grid) == 0
     return h
 
 
 def field(uniforms, height, grid, strength=0.7, softness=0.02, bias=0.002):
     """the field of the renderer's surface for the uniforms' sun, spacing (u[36], at least 1e-8) and exaggeration (u[38])"""
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
+    u = ms.u44(uniforms)
     return field_heights(heights(u, height, grid), u[32:35], float(max(u[36], np.float32(1e-8))), float(u[38]), strength, softness, bias)
 
 
 def frame(rgba, vis, uniforms, height, grid, lut_rgba8, lit, shade_mode=0):
     """-> (the shadowed frame (H, W, 4) uint8, shadowed (H, W) bool)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    lut = np.ascontiguousarray(lut_rgba8, np.uint8).reshape(1024)
-    lit = np.ascontiguousarray(lit, np.float32)
-    mask = np.empty((H, W), np.uint8)
-    assert lib().shm_frame(out.ctypes.data, mask.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0],
-                           grid, lut.ctypes.data, int(shade_mode), lit.ctypes.data) == 0
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
+    mask = np.empty(vis.shape, np.uint8)
+    assert lib().shm_frame(out, mask, vis, *scene, grid, ms.lut(lut_rgba8), int(shade_mode), ms.field(lit)) == 0
     return out, mask.astype(bool)

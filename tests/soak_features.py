@@ -35,28 +35,24 @@ their own.  Steps A - E and W of run_case:
 
 usage: soak_features.py [first_seed] [cases] [time_budget_s]"""
 import hashlib, math, os, sys, time, zlib
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "gbuffer_model", "shadow_model", "ambient_model", "drape_model",
-           "drape_mip_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "supersample_model", "haze_model", "flood_model",
-           "spill_model"):
-    sys.path.insert(0, os.path.join(HERE, _m))
 import numpy as np
-import ambient_model as abm  # noqa: E402
-import contour_model as cm  # noqa: E402
-import cumulative_viewshed_model as cvm  # noqa: E402
-import drape_mip_model as dmm  # noqa: E402
-import drape_model as drm  # noqa: E402
-import flood_model as fdm  # noqa: E402
-import gbuffer_model as gbm  # noqa: E402
-import haze_model as hzm  # noqa: E402
-import shadow_model as shm  # noqa: E402
-import spill_model as spm  # noqa: E402
-import sun_exposure_model as sem  # noqa: E402
-import supersample_model as ssm  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
+import model_support  # noqa: F401  (first: the repository root and the model directories on sys.path)
+import ambient_model as abm
+import contour_model as cm
+import cumulative_viewshed_model as cvm
+import drape_mip_model as dmm
+import drape_model as drm
+import flood_model as fdm
+import gbuffer_model as gbm
+import haze_model as hzm
+import occlusion_model as ocm
+import shadow_model as shm
+import spill_model as spm
+import sun_exposure_model as sem
+import supersample_model as ssm
+import viewshed_model as vsm
 
-ocm = cm.ocm
+HERE = os.path.dirname(os.path.abspath(__file__))
 f32 = np.float32
 MUTATIONS = ("heights", "sun", "exaggeration", "clear_overlays", "layer_occlusion", "shadows_off", "reach", "drape_replace", "drape_opacity_zero",
              "drape_clear")

@@ -14,28 +14,25 @@ frame under supersample_model.chain (the library's order of passes) and the over
 
 usage: soak_handles.py [first_seed] [cases] [time_budget_s]"""
 import ctypes as C
-import os
 import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
 import numpy as np
 
-import soak_features as sf  # noqa: E402  (puts the models' folders on the path)
-import ambient_model as abm  # noqa: E402
-import contour_model as cm  # noqa: E402
-import cumulative_viewshed_model as cvm  # noqa: E402
-import flood_model as fdm  # noqa: E402
-import gbuffer_model as gbm  # noqa: E402
-import shadow_model as shm  # noqa: E402
-import spill_model as spm  # noqa: E402
-import sun_exposure_model as sem  # noqa: E402
-import supersample_model as ssm  # noqa: E402
-import viewshed_model as vsm  # noqa: E402
+import model_support  # noqa: F401  (first: the repository root and the model directories on sys.path)
+import ambient_model as abm
+import contour_model as cm
+import cumulative_viewshed_model as cvm
+import flood_model as fdm
+import gbuffer_model as gbm
+import occlusion_model as ocm
+import shadow_model as shm
+import soak_features as sf
+import spill_model as spm
+import sun_exposure_model as sem
+import supersample_model as ssm
+import viewshed_model as vsm
 
-ocm = cm.ocm
 f32 = np.float32
 EXACT = 0
 NOT_READY = 600                                               # hipErrorNotReady: what hipStreamQuery says of a stream with work in flight

@@ -11,47 +11,30 @@ is not), .reached (n, n) bool, .vertices (the seeds' vertices, (N, 2), or None).
 """
 from __future__ import annotations
 
-import ctypes as C
-import os
-import sys
 from collections import namedtuple
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "flood_model"))
-import flood_model as fdm  # noqa: E402
-cm, vsm, om = fdm.cm, fdm.vsm, fdm.om
+import contour_model as cm
+import flood_model as fdm
+import model_support as ms
 
 TILE = 64
 EDGES, SEEDS = 1, 2
 DEFAULT_SHALLOW, DEFAULT_DEEP, DEFAULT_DEPTH_FULL = (96, 176, 224, 128), (16, 64, 160, 224), 0.1
 Field = namedtuple("Field", "spill sink sd reached vertices")
 
-_lib = None
+SIGNATURES = {
+    "spm_key": "u32(f32)",
+    "spm_unkey": "f32(u32)",
+    "spm_field": "i64(f32*, f32*, f32*, f32*, u32, i32, u32*?, u32)",
+    "spm_tile_passes": "i64(f32*, f32*, f32*, f32*, u32, i32, u32*?, u32, u32, u32*, u32)",
+    "spm_frame": "i32(u8*, f32*, u32*, u32, u32, f32*, f32*, u32, u32, u32, f32*, u32, u32, f32)",
+}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        T = os.path.dirname(HERE)
-        L = om.build_model("libspmodel.so", os.path.join(HERE, "spill_model.c"),
-                           [os.path.join(T, "viewshed_model", "viewshed_model.c"), os.path.join(T, "shadow_model", "shadow_model.c"),
-                            os.path.join(T, "gbuffer_model", "gbuffer_model.c"), os.path.join(T, "occlusion_model", "occlusion_model.c"),
-                            os.path.join(T, "polygon_model", "polygon_model.c"), os.path.join(T, "overlay_model", "overlay_model.c")])
-        vp, u32, f, i = C.c_void_p, C.c_uint32, C.c_float, C.c_int
-        L.spm_key.argtypes = [f]
-        L.spm_key.restype = u32
-        L.spm_unkey.argtypes = [u32]
-        L.spm_unkey.restype = f
-        L.spm_field.argtypes = [vp, vp, vp, vp, u32, i, vp, u32]
-        L.spm_field.restype = C.c_int64
-        L.spm_tile_passes.argtypes = [vp, vp, vp, vp, u32, i, vp, u32, u32, vp, u32]
-        L.spm_tile_passes.restype = C.c_int64
-        L.spm_frame.argtypes = [vp, vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, u32, u32, f]
-        L.spm_frame.restype = i
-        _lib = L
-    return _lib
+    return ms.load("spill_model", SIGNATURES)
 
 
 def mode_of(seeds):
@@ -82,8 +65,7 @@ def _args(h, seeds):
 def field_heights(h, seeds="edges"):
     """h (n, n) float32 vertex heights (row = z index, column = x index), seeds "edges" / vertices (i, j) -> Field (the search)"""
     h, n, mode, ij, (spill, sd, sink) = _args(h, seeds)
-    got = lib().spm_field(spill.ctypes.data, sd.ctypes.data, sink.ctypes.data, h.ctypes.data, n, mode,
-                          ij.ctypes.data if ij is not None else None, len(ij) if ij is not None else 0)
+    got = lib().spm_field(spill, sd, sink, h, n, mode, ij, len(ij) if ij is not None else 0)
     assert got >= 0
     reached = np.isfinite(spill)
     assert got == int(reached.sum())
@@ -96,8 +78,7 @@ def tile_passes(h, seeds="edges", tile=TILE):
     h, n, mode, ij, (spill, sd, sink) = _args(h, seeds)
     cap = 4096
     changed = np.zeros(cap, np.uint32)
-    passes = lib().spm_tile_passes(spill.ctypes.data, sd.ctypes.data, sink.ctypes.data, h.ctypes.data, n, mode,
-                                   ij.ctypes.data if ij is not None else None, len(ij) if ij is not None else 0, tile, changed.ctypes.data, cap)
+    passes = lib().spm_tile_passes(spill, sd, sink, h, n, mode, ij, len(ij) if ij is not None else 0, tile, changed, cap)
     assert 0 < passes <= cap
     return Field(spill, sink, sd, np.isfinite(spill), ij), int(passes), changed[:passes].copy()
 
@@ -116,15 +97,9 @@ def n_tiles(n, tile=TILE):
 
 def frame(rgba, vis, uniforms, height, grid, F, shallow_rgba=DEFAULT_SHALLOW, deep_rgba=DEFAULT_DEEP, depth_full=DEFAULT_DEPTH_FULL):
     """-> (the frame with the sink tint (H, W, 4) uint8, d (H, W) float32)"""
-    vis = np.ascontiguousarray(vis, np.uint32)
-    H, W = vis.shape
-    out = np.ascontiguousarray(rgba, np.uint8).reshape(H, W, 4).copy()
-    u = np.ascontiguousarray(uniforms, np.float32).reshape(44)
-    tex = np.ascontiguousarray(height, np.float32)
-    sd = np.ascontiguousarray(F.sd, np.float32)
-    d = np.empty((H, W), np.float32)
-    assert lib().spm_frame(out.ctypes.data, d.ctypes.data, vis.ctypes.data, W, H, u.ctypes.data, tex.ctypes.data, tex.shape[1], tex.shape[0], grid,
-                           sd.ctypes.data, vsm.pack(shallow_rgba), vsm.pack(deep_rgba), float(depth_full)) == 0
+    out, vis, *scene = ms.frame(rgba, vis, uniforms, height)
+    d = np.empty(vis.shape, np.float32)
+    assert lib().spm_frame(out, d, vis, *scene, grid, ms.field(F.sd), ms.pack(shallow_rgba), ms.pack(deep_rgba), float(depth_full)) == 0
     return out, d
 
 

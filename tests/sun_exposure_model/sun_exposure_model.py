@@ -13,15 +13,10 @@ of f = min(exposure / wtot, 1) without a radius.  Every operation is a binary32 
 """
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(os.path.dirname(HERE), "viewshed_model"))
-import viewshed_model as vsm  # noqa: E402
-shm = vsm.shm
+import shadow_model as shm
+import viewshed_model as vsm
 
 DEFAULTS = dict(softness=0.02, bias=0.002)
 DEFAULT_HIGH, DEFAULT_LOW = (255, 208, 64, 160), (0, 0, 0, 0)

@@ -27,18 +27,9 @@ and in `drape`, with mips, max_anisotropy=1.
 """
 from __future__ import annotations
 
-import os
-import sys
-
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-TESTS = os.path.dirname(HERE)
-sys.path.insert(0, os.path.dirname(TESTS))
-for _m in ("overlay_model", "polygon_model", "occlusion_model", "contour_model", "shadow_model", "ambient_model", "drape_model", "drape_mip_model",
-           "drape_aniso_model", "viewshed_model", "cumulative_viewshed_model", "sun_exposure_model", "gbuffer_model", "haze_model", "flood_model",
-           "spill_model"):
-    sys.path.insert(0, os.path.join(TESTS, _m))
+import model_support as ms
 
 F32 = np.float32
 FACTORS = (1, 2, 3, 4)
@@ -112,10 +103,11 @@ def _key(v):
 
 def _sources(seeds, u, grid):
     """what a flood or spill field sees of its sources: the mode, or the seeds' vertices at the uniforms' spacing"""
+    import contour_model as cm
     import flood_model as fdm
     if seeds is None or isinstance(seeds, str):
         return seeds
-    return _key(fdm.seed_vertices(seeds, fdm.cm.spacing_of(u), max(int(grid), 2)))
+    return _key(fdm.seed_vertices(seeds, cm.spacing_of(u), max(int(grid), 2)))
 
 
 def chain(rgba, vis, uniforms, height, grid, lut, shade_mode=0, shadows=None, ambient=None, drape=None, flood=None, spill=None, exposure=None,
@@ -140,7 +132,7 @@ def chain(rgba, vis, uniforms, height, grid, lut, shade_mode=0, shadows=None, am
     import spill_model as spm
     import sun_exposure_model as sem
     import viewshed_model as vsm
-    u = np.ascontiguousarray(uniforms, F32).reshape(44)
+    u = ms.u44(uniforms)
     h = np.ascontiguousarray(height, F32)
     vis = np.ascontiguousarray(vis, np.uint32)
     out = np.ascontiguousarray(rgba, np.uint8).reshape(vis.shape + (4,))
@@ -211,7 +203,7 @@ def samples(W, H, f, uniforms, height, grid, lut, shade_mode=0, nthreads=8, stag
     -> (samples (f H, f W, 4) uint8, vis (f H, f W) uint32)"""
     import oracle
     sw, sh = int(f) * int(W), int(f) * int(H)
-    u = np.ascontiguousarray(uniforms, F32).reshape(44)
+    u = ms.u44(uniforms)
     h = np.ascontiguousarray(height, F32)
     rgba, vis = oracle.render_terrain(u, sw, sh, grid, h, lut, want_vis=True, nthreads=min(nthreads, oracle.max_threads()), shade_mode=shade_mode)
     return chain(rgba.reshape(sh, sw, 4), vis, u, h, grid, lut, shade_mode=shade_mode, stages=stages, memo=memo, **features), vis

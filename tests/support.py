@@ -3,7 +3,6 @@ frame (one cache for the whole process), the `vf` / `cabi` fixtures and the run 
 
 Importing this module imports nothing native (no oracle, vulkan_forge, vulkan_forge_amd or torch): test modules are collected before
 the session fixture has built those, so everything that needs them is imported inside the functions."""
-import glob
 import hashlib
 import os
 import subprocess
@@ -12,13 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-
-for _p in (*sorted(glob.glob(os.path.join(HERE, "*_model" + os.sep))), ROOT):     # (once: a second import finds them there)
-    _p = _p.rstrip(os.sep)
-    if _p not in sys.path:
-        sys.path.insert(0, _p)
+from model_support import HERE, ROOT            # (importing it puts the repository root and the model directories on sys.path)
 
 
 @pytest.fixture(scope="module")

@@ -93,7 +93,7 @@ def float64_normals(u, h, ids):
     nm1 = GRID - 1
     step = np.float32(3.0) / np.float32(nm1)
     tex = np.ascontiguousarray(h, np.float32)
-    hgt = lambda i, j: float(om.lib().ovm_vertex_height(tex.ctypes.data, tex.shape[1], tex.shape[0], GRID, int(i), int(j)))
+    hgt = lambda i, j: float(om.lib().ovm_vertex_height(tex, tex.shape[1], tex.shape[0], GRID, int(i), int(j)))
     xz = lambda i: float(np.float32(-1.5) + np.float32(i) * step) * float(max(u[36], np.float32(1e-8)))
     out = np.zeros((len(ids), 3))
     for k, vid in enumerate(ids):

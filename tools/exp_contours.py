@@ -24,8 +24,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests", "contour_model"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import model_support  # noqa: E402,F401  (the repository root and the model directories on sys.path)
 
 
 def terrain_heights(G, seed=20261016):

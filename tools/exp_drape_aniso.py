@@ -20,9 +20,9 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import model_support  # noqa: E402,F401  (the repository root and the model directories on sys.path)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests", "drape_aniso_model"))
 from exp_drape import CAMERAS, SUN, opaque_image  # noqa: E402
 
 AS = (1, 2, 4, 8, 16)
