@@ -1,6 +1,6 @@
 """Feature soak on the GPU box: seeded random scenes through every pass that runs after the tile kernel -- geometry buffers and pick,
-the shadow field and the sky-view field, their shade passes, the draped image, point / line / polygon / contour overlays with occlusion
--- on one handle per case, followed by one mutation of the handle (a height upload, a new sun, another image, ...), each step compared with the CPU models
+the shadow field and the sky-view field, their shade passes, the draped image, point / line / polygon / contour overlays with occlusion,
+of which the point, line and contour layers may take the haze -- on one handle per case, followed by one mutation of the handle (a height upload, a new sun, another image, ...), each step compared with the CPU models
 (tests/*_model) run on the oracle's frame.  Every comparison is equality; the one exception is the FAST frame's stated 1 LSB
 (include/vf_hip.h).  A sibling of tests/soak_parity.py: test infrastructure, nothing of it is shipped.  A script, and the library of
 tests/test_gpu_feature_soak.py (the GPU slice) and tests/test_feature_soak_cases.py (the slice is not vacuous; CPU only).
@@ -8,14 +8,19 @@ tests/test_gpu_feature_soak.py (the GPU slice) and tests/test_feature_soak_cases
     case(seed)              a case description: pure numpy and the models' surface sampling, no GPU, no oracle
     CORNERS                 hand-written case descriptions: the edges that must not be left to the draw
     expected(case, state)   the reference frame and planes of a handle state: the oracle's frame, the passes in the library's order,
-                            which supersample_model.chain alone writes down, then the overlays
+                            which supersample_model.chain alone writes down, then the overlays under the state's haze
+                            (overlay_haze_model.composite: the soak has no arithmetic of its own)
     run(first, cases, ...)  the GPU side, case by case
 
 The late passes ride on the same handle, between the overlays and the mutation: the drape's mip pyramid and
 anisotropic taps, the viewshed, cumulative-viewshed and sun-exposure fields and tints, the haze; then a second mutation of their own,
 and for a case with a factor above 1 a supersampled second handle.  The flood and the spill (the two passes between
 the drape and the exposure tint, whose fields iterate to a fixpoint across launches) ride with them, and get a third mutation of
-their own.  Steps A - E and W of run_case:
+their own.  Hazed overlay layers ride on the overlays: a case's `hazed` entry says which of its point, line and contour
+layers are flagged and whether directly after their add or after all adds, and puts a ladder of twelve hazed draped circles from under
+the eye through the target behind them; step 4 sets the flags while the haze is still off (the unflagged bytes, layer_haze() of every
+layer), every later frame is compared under the flags, and a fourth mutation (flag_flip, flags_all_off, haze_params,
+occlusion_on_hazed, readd, polygon_refused) comes in a step of its own.  Steps A - E, H and W of run_case:
     A  the three vertex fields, bit for bit, their passes off; the cumulative and exposure fields again at another batch size; the
        flood, spill and sink-depth fields with flood_info() and spill_info() (counts, mode, seeds' vertices, passes and tile runs
        inside the bounds of the models' tile_passes), and again at another group size, the spill's with or without its activity flags
@@ -27,11 +32,14 @@ their own.  Steps A - E and W of run_case:
        others alike.  The pixels an overlay touches are left out of the colour comparison altogether, the 1 LSB bound included (the
        overlays blend over bytes that may be 1 LSB off, and where a layer is opaque nothing of the frame beneath is left to compare);
        the alpha channel is compared everywhere
+    H  the hazed mutation, while everything is on: the frame, layer_haze() of every layer; for readd clear_overlays with flags set,
+       layer_haze refused for the old ids, every call added again unflagged, then again with the flags set the other way round
+       (early <-> late); for polygon_refused the two messages and an unchanged frame
     D  the mutation (step 5) and the late mutation: the frame, and the rise of the five scan counters and of the pyramid's builds
        against STALE_VIEWSHED, STALE_CUMULATIVE, STALE_EXPOSURE, STALE_FLOOD, STALE_SPILL and MIP_BUILDS
     W  the water mutation: the frame (for spill_cleared: the frame without the spill, then with it set again) and the same counters
-    E  supersample=f: the samples, the resolved frame under the overlays (none occluding) and the samples' visibility, again after the
-       late mutation and after the water mutation
+    E  supersample=f: the samples, the resolved frame under the overlays (none occluding; the flags and the ladder as on the first
+       handle) and the samples' visibility, again after the late mutation and after the water mutation
 
 usage: soak_features.py [first_seed] [cases] [time_budget_s]"""
 import hashlib, math, os, sys, time, zlib
@@ -46,6 +54,7 @@ import flood_model as fdm
 import gbuffer_model as gbm
 import haze_model as hzm
 import occlusion_model as ocm
+import overlay_haze_model as ohm
 import shadow_model as shm
 import spill_model as spm
 import sun_exposure_model as sem
@@ -119,6 +128,16 @@ WATER_GROUPS = (1, 7, 0)                                      # the group size o
 STALE_FLOOD = ("heights", "heights_again", "level", "flood_mode", "seeds_move", "heights_water")
 STALE_SPILL = ("heights", "heights_again", "spill_mode", "seeds_move", "spill_cleared", "heights_water")
 WATER_KEYS = ("water", "water_mutation", "water_mutation_args")
+# hazed overlay layers: which point, line and contour layers take the haze, when their flag is set, a ladder of hazed
+# points across the frame's depths, and a mutation of the flags.  Their generator is default_rng([seed, HAZED_STREAM]): no key a
+# case had before them depends on it (digest; tests/test_feature_soak_cases.py pins it)
+HAZED_STREAM = 0x4A2ED
+HAZED_MUTATIONS = ("flag_flip", "flags_all_off", "haze_params", "occlusion_on_hazed", "readd", "polygon_refused")
+HAZED_KEYS = ("hazed", "hazed_mutation", "hazed_mutation_args")
+FLAG_SHARE = 0.6                                              # the probability of a layer's flag (at least one is set)
+LADDER_RUNGS = 12
+POLYGON_REFUSED = "a polygon layer cannot take the haze: polygon fills have no depth"
+UNKNOWN_LAYER = "no overlay layer with that id"
 OLD_KEYS = ("name", "W", "H", "grid", "tex", "amp", "smooth", "nan_texel", "heights", "eye", "target", "fovy", "znear", "zfar", "exaggeration", "spacing", "sun",
             "cmap", "mode", "mutation", "features", "shadows", "ambient", "overlays", "mutation_args", "drape")
 
@@ -810,10 +829,133 @@ def _water(rng, c, surf, fix, wish, all_on=False):
     return W, kind, args
 
 
-def _make(rng, name, fix, drape_rng, draped=False, late_rng=None, water_rng=None, water_wish=None):
+def eligible(c):
+    """the indices of the case's overlay calls whose layer can take the haze: every call that is not a polygon call"""
+    return [k for k, (kind, _) in enumerate(c["overlays"]) if kind != "polygons"]
+
+
+def ladder_index(c):
+    """the layer id of the ladder: it is added after the case's own calls"""
+    return len(c["overlays"])
+
+
+def _ladder(c, rgba, occlude):
+    """The ladder of a case (the keywords of a point layer): LADDER_RUNGS draped circles of 5 px on the ground line from under the eye
+    through the target to where that line leaves the terrain's square (+-1.5 spacing) -- to twice the target's distance where it
+    does not cross the square beyond the target.  Hazed primitives across the frame's depths, whatever the older draw put where."""
+    eye, target = np.asarray(c["eye"], np.float64), np.asarray(c["target"], np.float64)
+    g0, d = eye[[0, 2]], (target - eye)[[0, 2]]
+    if not np.linalg.norm(d) > 1e-9:
+        d = np.array([1.0, 0.0])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        leave = np.where(d != 0.0, (np.sign(d) * 1.5 * c["spacing"] - g0) / d, np.inf).min()
+    far = float(leave) if np.isfinite(leave) and leave > 1.0 else 2.0
+    t = np.linspace(0.0, far, LADDER_RUNGS)
+    xyz = np.column_stack([g0[0] + t * d[0], np.full(LADDER_RUNGS, 0.02), g0[1] + t * d[1]]).astype(f32)
+    return dict(xyz=xyz, size_px=5.0, rgba=tuple(rgba), shape="circle", drape=True, occlude=bool(occlude), depth_bias=1e-2)
+
+
+def haze_at_the_hazed_mutation(c):
+    """the haze of the handle when run_case applies the hazed mutation (step H, before the first mutation), or None while it is off"""
+    return dict(c["late"]["haze"]) if "haze" in c["late"]["on"] else None
+
+
+def _hazed(rng, c, fix, wish, parity):
+    """Which of a case's layers take the haze, from a generator of its own -> (hazed, hazed_mutation, hazed_mutation_args).  `hazed`:
+    flags and early (one bool each per call of eligible(c), in that order: whether the layer is flagged -- at least one is -- and
+    whether its flag is set directly after its add, while later layers are still to come, or after all adds) and the ladder (_ladder:
+    flagged, opaque, occluding where `parity` is even).  fix["hazed"] is laid over the draw: flags and early as {call index: bool}
+    (negative: from the end; a kind's name: every call of that kind), only=True: every flag it does not name is off.  The mutation is `wish` (seed % len(HAZED_MUTATIONS)
+    for a seed) if it can do what it must: flag_flip needs the haze on when it comes and a drawn layer that, flagged, covers a pixel
+    with S.ah > 0 and whose flip changes the frame of the drawn flags (the model's counts and frames over an empty visibility: no
+    oracle frame here, the terrain hides nothing), haze_params the haze on; else the next of a drawn order that can.  fix["hazed_mutation"] is written down and stays."""
+    E = eligible(c)
+    n = len(c["overlays"])
+    fixed = fix.get("hazed", {})
+    kind = fix.get("hazed_mutation", wish)
+    # the draw, all of it for every case
+    flags = [bool(v) for v in rng.random(len(E)) < FLAG_SHARE]
+    spare = int(rng.integers(0, len(E)))
+    early = [bool(v) for v in rng.random(len(E)) < 0.5]
+    colour = _rgba(rng, 255)
+    order = [HAZED_MUTATIONS[i] for i in rng.permutation(len(HAZED_MUTATIONS))]
+    flip_order = [E[i] for i in rng.permutation(len(E))]
+    occ_order = [E[i] for i in rng.permutation(len(E))]
+    bias = float(rng.choice([0.0, 1e-2, 0.2]))
+    lots = rng.random(3)
+    Z = c["late"]["haze"]
+
+    def another(options, now, lot):
+        rest = [v for v in options if v != now]
+        return rest[int(lot * len(rest))]
+
+    new = dict(density=another((0.05, 0.5, 5.0), Z["density"], lots[0]), start=0.5 * float(np.linalg.norm(c["eye"])) if Z["start"] == 0.0 else 0.0,
+               falloff=another((None, 0.3, 4.0), Z["falloff"], lots[1]), rgba=_rgba(rng))
+    if not any(flags):
+        flags[spare] = True
+    if fixed.get("only"):
+        flags = [False] * len(E)
+    for key, mine in (("flags", flags), ("early", early)):
+        for k, v in fixed.get(key, {}).items():               # (a kind's name: every call of that kind)
+            for j in [j for j in E if c["overlays"][j][0] == k] if isinstance(k, str) else [k % n]:
+                mine[E.index(j)] = bool(v)
+    assert any(flags), c["name"]
+    H = dict(flags=tuple(flags), early=tuple(early), ladder=_ladder(c, colour, parity % 2 == 0))
+    made = []
+
+    def lit(k):
+        """whether layer k, flagged alone, covers a pixel with S.ah > 0 under the haze the handle has at step H, the terrain hiding nothing"""
+        Zh = haze_at_the_hazed_mutation(c)
+        if Zh is None:
+            return False
+        try:
+            u = uniforms(c)
+        except RuntimeError:                                  # (a degenerate camera: run() skips the seed)
+            return False
+        if not made:
+            made.append(layers(dict(c, hazed=H), dict(occlusion={}, hazed=dict(flags={}, ladder=False))))
+        L = made[0]
+        L.set_haze(L.index[k], True)
+        blank = np.zeros((c["H"], c["W"]), np.uint32)
+        pairs, _, clear = ohm.composite(np.zeros((c["H"], c["W"], 4), np.uint8), blank, u, c["heights"], c["grid"], L, haze=Zh, want_counts=True)[1]
+        L.set_haze(L.index[k], False)
+        if not pairs > clear:
+            return False
+        # ... and a later layer does not draw over all of it: the flip changes the frame of the drawn flags (seed 7014's first choice did not)
+        frames = []
+        for flip in (False, True):
+            for j, on in list(zip(E, flags)) + [(n, True)]:
+                L.set_haze(L.index[j], on != (flip and j == k))
+            frames.append(ohm.composite(np.full((c["H"], c["W"], 4), 128, np.uint8), blank, u, c["heights"], c["grid"], L, haze=Zh))
+        for j in E + [n]:
+            L.set_haze(L.index[j], False)
+        return bool((frames[0] != frames[1]).any())
+
+    chosen = {}
+
+    def can_stand(k):
+        if k == "flag_flip":
+            chosen["layer"] = next((j for j in flip_order if lit(j)), None)
+            return chosen["layer"] is not None
+        if k == "haze_params":
+            return haze_at_the_hazed_mutation(c) is not None
+        return True
+
+    if "hazed_mutation" not in fix:
+        kind = next(k for k in [kind] + order if can_stand(k))
+    elif kind == "flag_flip" and "layer" not in fix.get("hazed_mutation_args", {}):
+        can_stand(kind)                                       # (a corner's flip that names no layer: one that shows, if there is one)
+    on = dict(zip(E, flags))
+    hazed_pl = [j for j in occ_order if on[j] and c["overlays"][j][0] in ("points", "lines")]
+    args = dict({"layer": chosen.get("layer") if chosen.get("layer") is not None else flip_order[0], "haze": new,
+                 "occlusion_layer": hazed_pl[0] if hazed_pl else n, "depth_bias": bias}, **fix.get("hazed_mutation_args", {}))
+    return H, kind, args
+
+
+def _make(rng, name, fix, drape_rng, draped=False, late_rng=None, water_rng=None, water_wish=None, hazed_rng=None, hazed_wish=None, parity=0):
     """A case description; `fix` overrides what the draw would choose (CORNERS).  The drape comes from `drape_rng`, a generator of
     its own: what `rng` gives a seed or a corner does not depend on it; `draped`: never without one (every corner).  The late
-    passes come from `late_rng` in the same way, the flood and the spill from `water_rng`."""
+    passes come from `late_rng` in the same way, the flood and the spill from `water_rng`, the hazed layers from `hazed_rng`."""
     c = {"name": name}
 
     def put(key, draw):
@@ -882,16 +1024,19 @@ def _make(rng, name, fix, drape_rng, draped=False, late_rng=None, water_rng=None
     c["drape"] = None if d is None else dict(d, **fix.get("drape", {}))
     c["late"], c["late_mutation"], c["late_mutation_args"] = _late(late_rng, c, surf, fix, all_on=draped)
     c["water"], c["water_mutation"], c["water_mutation_args"] = _water(water_rng, c, surf, fix, water_wish, all_on=draped)
+    c["hazed"], c["hazed_mutation"], c["hazed_mutation_args"] = _hazed(hazed_rng, c, fix, hazed_wish, parity)
     return c
 
 
 def case(seed):
     """The case of a seed: frame, grid, texture, camera and uniforms drawn as test_random_scenes_fuzz draws them, a sun, colormap,
     shade mode, shadow and ambient parameters, which of them are on, the overlay calls, one mutation and (from a generator of its
-    own each) a draped image or none, the late passes with their mutation, the flood and the spill with theirs."""
+    own each) a draped image or none, the late passes with their mutation, the flood and the spill with theirs, the hazed layers
+    with theirs."""
     return _make(np.random.default_rng(seed), f"seed{seed}", {"mutation": MUTATIONS[seed % len(MUTATIONS)]}, np.random.default_rng([seed, DRAPE_STREAM]),
                  late_rng=np.random.default_rng([seed, LATE_STREAM]), water_rng=np.random.default_rng([seed, WATER_STREAM]),
-                 water_wish=WATER_MUTATIONS[seed % len(WATER_MUTATIONS)])
+                 water_wish=WATER_MUTATIONS[seed % len(WATER_MUTATIONS)], hazed_rng=np.random.default_rng([seed, HAZED_STREAM]),
+                 hazed_wish=HAZED_MUTATIONS[seed % len(HAZED_MUTATIONS)], parity=seed)
 
 
 _CAMERA = dict(eye=(3.0, 2.0, 3.0), target=(0.0, 0.0, 0.0), fovy=45.0, znear=0.1, zfar=100.0)
@@ -923,7 +1068,8 @@ def _build(k, name, fix):
     base["late"] = late
     return _make(np.random.default_rng(90000 + k), name, base, np.random.default_rng([90000 + k, DRAPE_STREAM]), draped=True,
                  late_rng=np.random.default_rng([90000 + k, LATE_STREAM]), water_rng=np.random.default_rng([90000 + k, WATER_STREAM]),
-                 water_wish=WATER_MUTATIONS[k % len(WATER_MUTATIONS)])
+                 water_wish=WATER_MUTATIONS[k % len(WATER_MUTATIONS)], hazed_rng=np.random.default_rng([90000 + k, HAZED_STREAM]),
+                 hazed_wish=HAZED_MUTATIONS[k % len(HAZED_MUTATIONS)], parity=k)
 
 
 def _amb(reach, dirs, strength=0.6):
@@ -1109,6 +1255,103 @@ _SPECS = [
 ]
 OLD_CORNERS = 29                                             # the corners older than the late passes: their old keys are pinned (digest)
 LATE_CORNERS = 47                                             # ... and those older than the flood and the spill: theirs and their late keys
+WATER_CORNERS = 68                                            # ... and those older than the hazed layers: all their keys but the hazed ones
+
+
+# the hazed layers' own edges (tests/test_feature_soak_cases.py asserts what each is named for): every pass on, small
+# frames.  A corner's own layers follow the eight drawn calls (DRAWN + j) or, where the record counts matter, replace them
+DRAWN = 8
+
+
+def _hz(**kw):
+    """the haze of a hazed corner: from the eye on, uniform, opaque at most, unless `kw` says otherwise"""
+    return dict(haze=dict(dict(start=0.0, density=0.3, falloff=None, base=0.0, max_opacity=1.0, rgba=(200, 215, 235, 255), background=False), **kw))
+
+
+def _pts(xyz, size_px, drape, rgba=(255, 60, 40, 255), shape="circle", occlude=False, depth_bias=1e-2):
+    return ("points", dict(xyz=np.asarray(xyz, f32).reshape(-1, 3), size_px=size_px, rgba=rgba, shape=shape, drape=drape, occlude=occlude, depth_bias=depth_bias))
+
+
+def _lns(paths, width_px, cap, drape, rgba=(250, 220, 30, 255), occlude=False, depth_bias=1e-2):
+    return ("lines", dict(paths=[np.asarray(p, f32).reshape(-1, 3) for p in paths], width_px=width_px, rgba=rgba, cap=cap, drape=drape, occlude=occlude,
+                          depth_bias=depth_bias))
+
+
+def _own(*flags, early=()):
+    """the `hazed` entry of a corner: only its own layers DRAWN + j, j in `flags`, take the haze; those in `early` directly after their add"""
+    return dict(only=True, flags={DRAWN + j: True for j in flags}, early={DRAWN + j: j in early for j in flags})
+
+
+_P, _Q = (0.3, 0.3, 0.2), (-0.8, 0.1, 0.6)
+_EYE, _TARGET = np.array(_CAMERA["eye"]), np.array(_CAMERA["target"])
+_BEHIND = _EYE + 0.7 * (_EYE - _TARGET) + [0.01, 0.02, 0.03]  # (as _overlays draws it: from the target to behind the eye)
+_THROUGH_THE_EYE = [_lns([[_TARGET, _BEHIND]], 7.0, "round", False), _lns([[(0.0, 0.02, 0.0), (_BEHIND[0], 0.02, _BEHIND[2])]], 3.0, "butt", True, rgba=(40, 250, 90, 255))]
+_NEAR = dict(grid=9, eye=(0.9, 0.7, 0.8), target=(-0.4, -0.2, -0.3), znear=0.4, fovy=60.0)     # (the camera of drape_near_plane_through_the_terrain)
+_LATTICE = np.array([(x, 0.02, z) for x in np.linspace(-1.4, 1.4, 9) for z in np.linspace(-1.4, 1.4, 9)], f32)
+_ACROSS = [(-1.4, 0.02, -1.2), (0.0, 0.02, 0.1), (1.4, 0.02, 1.3)]
+_NOISE = dict(grid=65, tex=(65, 65), smooth=False, amp=1.0, W=96, H=64)
+_CLOUD = np.random.default_rng(110).uniform(-1.4, 1.4, (300, 3)).astype(f32) * np.array([1.0, 0.0, 1.0], f32) + np.array([0.0, 0.02, 0.0], f32)
+_SIX_LEVELS = ("contours", dict(levels=np.linspace(-0.3, 0.3, 6).astype(f32), width_px=1.0, rgba=(20, 20, 20, 255), lift=0.0, join="round", occlude=False, depth_bias=1e-2))
+_PATCH = ("polygons", dict(polygons=[[_ring((0.2, -0.1), 0.5, 5, 0.02)]], fill_rgba=(0, 90, 255, 150), line_rgba=(0, 0, 0, 255), line_width_px=1.0, drape=True))
+_BIG = [_pts([(0.0, 0.02, 0.0)], 64.0, True), _lns([[(-1.0, 0.02, -1.0), (1.0, 0.02, 1.0)]], 80.0, "round", True)]
+_SPECS += [
+    # a zero-length segment under every cap, alone in its path and in front of a longer one, half a pixel and 80 pixels wide
+    _corner(100, "hazed_zero_length_segments_every_cap", ambient=_amb(16.0, _FAN), late=_hz(falloff=4.0), hazed_mutation="flag_flip", hazed_mutation_args={"layer": DRAWN + 2},
+            more_overlays=[_lns([[_P, _P], [_P, _P, _Q]], w, cap, False, rgba=(250, 40 + 90 * j, 30, 255)) for w in (80.0, 0.5) for j, cap in enumerate(CAPS)],
+            hazed=_own(0, 1, 2, 3, 4, 5, early=(0, 3))),
+    # a free and a draped path from the target to behind the eye under a shallow layer of haze: the clipped end's interpolated y decides
+    # the opacity; then under fovy 170 and a density of 5, where it saturates at max_opacity
+    _corner(101, "hazed_paths_through_the_eye_falloff0p3", ambient=_amb(16.0, _FAN), late=_hz(falloff=0.3, density=0.5), hazed_mutation="haze_params",
+            more_overlays=_THROUGH_THE_EYE, hazed=_own(0, 1, early=(0,))),
+    _corner(102, "hazed_paths_through_the_eye_fovy170_saturated", fovy=170.0, ambient=_amb(16.0, _FAN), late=_hz(falloff=0.3, density=5.0, max_opacity=0.6),
+            hazed_mutation="flags_all_off", more_overlays=_THROUGH_THE_EYE, hazed=_own(0, 1)),
+    # the near plane through the terrain: a hazed occluding layer beside an unhazed occluding one (ov_terrain_rw on clipped triangles)
+    _corner(103, "hazed_near_plane_through_the_terrain", **_NEAR, ambient=_amb(16.0, _FAN, strength=0.6), late=_hz(density=0.5), hazed_mutation="occlusion_on_hazed",
+            hazed_mutation_args={"occlusion_layer": DRAWN, "depth_bias": 0.0},
+            more_overlays=[_pts(_LATTICE, 6.0, True, occlude=True), _lns([_ACROSS], 3.0, "round", True, occlude=True, depth_bias=0.0)], hazed=_own(0, early=(0,))),
+    # draped hazed points and a draped hazed path over vertices without a height: what is drawn is what the model says
+    _corner(104, "hazed_draped_over_one_nan_texel", tex=(9, 7), nan_texel=True, ambient=_amb(16.0, _FAN), late=_hz(falloff=4.0), hazed_mutation="flag_flip",
+            hazed_mutation_args={"layer": DRAWN}, more_overlays=[_pts(_LATTICE, 6.0, True), _lns([_ACROSS], 3.0, "square", True)], hazed=_own(0, 1, early=(1,))),
+    _corner(105, "hazed_draped_over_the_all_nan_texture", heights=np.full((5, 6), np.nan, f32), ambient=_amb(16.0, _round(8)), mutation="heights", late=_hz(falloff=4.0),
+            hazed_mutation="readd", more_overlays=[_pts(_LATTICE, 6.0, True), _lns([_ACROSS], 3.0, "square", True)], hazed=_own(0, 1)),
+] + [
+    # no opacity, three ways: the frame is the unflagged bytes; haze_params brings `start` to 0
+    _corner(106 + j, f"hazed_no_opacity_{name}", ambient=_amb(16.0, _FAN), late=_hz(**kw), hazed_mutation="haze_params",
+            hazed_mutation_args={"haze": dict(density=0.5, start=0.0, falloff=None, rgba=(200, 215, 235, 255))},
+            more_overlays=[_pts(_LATTICE, 6.0, True), _lns([_ACROSS], 3.0, "round", False)], hazed=_own(0, 1, early=(0,)))
+    for j, (name, kw) in enumerate((("start_beyond_every_depth", dict(start=1e6)), ("max_opacity_0", dict(max_opacity=0.0)), ("colour_of_alpha_0", dict(rgba=(200, 215, 235, 0)))))
+] + [
+    # the side array behind its allocation: one point flagged early, then a contour layer of six levels over white noise -- thousands of
+    # GPU-extracted records -- flagged late, then 300 one-pixel points; and every layer unflagged until one flag on the last
+    _corner(110, "hazed_side_array_grows_behind_an_early_flag", **_NOISE, ambient=_amb(16.0, _FAN), late=_hz(falloff=4.0), hazed_mutation="flag_flip",
+            hazed_mutation_args={"layer": 1}, overlays=[_pts([(0.1, 0.02, -0.2)], 9.0, True), _SIX_LEVELS, _pts(_CLOUD, 1.0, True, rgba=(255, 255, 255, 255)), _PATCH],
+            mutation_args={"layer": 0}, hazed=dict(flags={0: True, 1: True, 2: True}, early={0: True, 1: False, 2: False})),
+    _corner(111, "hazed_one_flag_on_the_last_layer", **_NOISE, ambient=_amb(16.0, _FAN), late=_hz(falloff=4.0), hazed_mutation="readd",
+            overlays=[_pts([(0.1, 0.02, -0.2)], 9.0, True), _SIX_LEVELS, _PATCH, _pts(_CLOUD, 1.0, True, rgba=(255, 255, 255, 255))],
+            mutation_args={"layer": 0}, hazed=dict(only=True, flags={3: True}, early={3: False})),
+    # the contour layer of the 2^20 staircase, a level on a plateau, hazed; the height upload comes under its snapshot
+    _corner(112, "hazed_contours_on_the_staircase", heights=np.full((4, 4), 2.0 ** 20, f32), exaggeration=2.0 ** -20, ambient=_amb(16.0, _round(8)), mutation="heights",
+            late=_hz(falloff=4.0), hazed_mutation="flags_all_off", hazed=dict(only=True, flags={"contours": True}, early={"contours": True})),
+    # frames of one pixel, one column and one row under a 64-px point and an 80-px line
+    _corner(113, "hazed_frame1x1", W=1, H=1, ambient=_amb(16.0, _FAN), late=_hz(), hazed_mutation="flags_all_off", more_overlays=_BIG, hazed=_own(0, 1)),
+    _corner(114, "hazed_frame_of_one_column", W=1, H=70, grid=17, ambient=_amb(16.0, _FAN), late=_hz(), hazed_mutation="occlusion_on_hazed",
+            hazed_mutation_args={"occlusion_layer": DRAWN + 1}, more_overlays=_BIG, hazed=_own(0, 1, early=(0,))),
+    _corner(115, "hazed_frame_of_one_row", W=130, H=1, grid=16, fovy=0.3, ambient=_amb(1.5, _round(3)), late=_hz(), hazed_mutation="polygon_refused",
+            more_overlays=_BIG, hazed=_own(0, 1, early=(1,))),
+    # supersampled handles take the flags and the ladder
+    _corner(116, "hazed_supersample3_frame15x17", W=15, H=17, ambient=_amb(16.0, _FAN), mutation="sun", late=dict(_hz(falloff=4.0), supersample=3), hazed_mutation="flag_flip",
+            hazed=dict(flags={"points": True, "lines": True, "contours": True})),
+    _corner(117, "hazed_supersample4_frame1x1", W=1, H=1, ambient=_amb(16.0, _FAN), late=dict(_hz(), supersample=4), hazed_mutation="haze_params",
+            water_mutation="seeds_nudged", water=dict(spill=dict(seeds=np.array([(0.1, 0.1)], f32))),      # (a water mutation that must not show: one pixel shows little)
+            more_overlays=_BIG, hazed=dict(flags={"points": True, "lines": True, "contours": True, DRAWN: True, DRAWN + 1: True})),
+    # no relief and a narrow grid, an inverted relief and a wide one: a draped and a free hazed layer each
+    _corner(118, "hazed_exaggeration0_spacing0p3", exaggeration=0.0, spacing=0.3, ambient=_amb(16.0, _round(8)), mutation="exaggeration", mutation_args={"exaggeration": -2.0},
+            late=_hz(density=1.0), hazed_mutation="occlusion_on_hazed", hazed_mutation_args={"occlusion_layer": DRAWN},
+            more_overlays=[_pts(_LATTICE * f32(0.3), 6.0, True), _lns([np.array(_ACROSS) * 0.3 + [0.0, 0.1, 0.0]], 3.0, "round", False)], hazed=_own(0, 1, early=(0,))),
+    _corner(119, "hazed_exaggeration_minus2_spacing2p5", exaggeration=-2.0, spacing=2.5, amp=0.2, ambient=_amb(16.0, _FAN), mutation="exaggeration", late=_hz(density=0.1),
+            hazed_mutation="readd", more_overlays=[_pts(_LATTICE * f32(2.5), 6.0, True), _lns([np.array(_ACROSS) * 2.5 + [0.0, 0.3, 0.0]], 3.0, "round", False)],
+            hazed=_own(0, 1, early=(1,))),
+]
 
 
 class _Corners:
@@ -1162,7 +1405,43 @@ def uniforms(c, sun=None, exaggeration=None):
 def initial_state(c):
     """the handle's state before any feature is on: what `expected` and `run` step through"""
     return dict(heights=c["heights"], u=uniforms(c), shadows=False, ambient=False, shadow_params=dict(c["shadows"]), ambient_params=dict(c["ambient"]),
-                overlays=False, occlusion={}, drape=None, late=None, water=None)
+                overlays=False, occlusion={}, drape=None, late=None, water=None, hazed=None)
+
+
+def hazed_on(c, state, flags=None):
+    """the state with the case's layers flagged as its `hazed` entry says and the ladder added behind them (run_case's step 4):
+    hazed = dict(flags: {call index: bool} of eligible(c), ladder: the ladder's flag); None: no flag, no ladder.  `flags`: every
+    flag, the ladder's too, takes this value instead"""
+    F = c["hazed"]["flags"] if flags is None else [flags] * len(c["hazed"]["flags"])
+    return dict(state, hazed=dict(flags=dict(zip(eligible(c), F)), ladder=True if flags is None else flags))
+
+
+def hazed_steps(c, state):
+    """The states (overlays on, the flags and the ladder in `hazed`) the case's hazed mutation leads through, in order: [(what,
+    state)].  One for every mutation but readd: every call added again unflagged, then again with the flags as they were.
+    polygon_refused leaves the state as it is."""
+    kind, a = c["hazed_mutation"], c["hazed_mutation_args"]
+    Hz = dict(state["hazed"], flags=dict(state["hazed"]["flags"]))
+    s = dict(state, hazed=Hz)
+    if kind == "flag_flip":
+        Hz["flags"][a["layer"]] = not Hz["flags"][a["layer"]]
+    elif kind == "flags_all_off":
+        return [(kind, hazed_on(c, state, flags=False))]
+    elif kind == "haze_params":
+        s["late"] = dict(state["late"], haze=dict(state["late"]["haze"], **a["haze"]))
+    elif kind == "occlusion_on_hazed":
+        k = a["occlusion_layer"]
+        now = state["occlusion"][k][0] if k in state["occlusion"] else (c["hazed"]["ladder"] if k == ladder_index(c) else c["overlays"][k][1])["occlude"]
+        s["occlusion"] = {**state["occlusion"], k: (not now, a["depth_bias"])}
+    elif kind == "readd":
+        again = dict(state, occlusion={})
+        return [("every call added again, unflagged", hazed_on(c, again, flags=False)), ("added again, the flags set the other way round", dict(again, hazed=Hz))]
+    return [(kind, s)]
+
+
+def hazed_mutated(c, state):
+    """the state after the case's hazed mutation"""
+    return hazed_steps(c, state)[-1][1]
 
 
 def watered(c, state):
@@ -1264,7 +1543,8 @@ def chain_features(c, state):
 
 def unoccluded(c):
     """the case with no overlay layer occluding: what a supersampled handle accepts (include/vf_hip.h)"""
-    return dict(c, overlays=[(kind, dict(kw, occlude=False) if "occlude" in kw else kw) for kind, kw in c["overlays"]])
+    return dict(c, overlays=[(kind, dict(kw, occlude=False) if "occlude" in kw else kw) for kind, kw in c["overlays"]],
+                hazed=dict(c["hazed"], ladder=dict(c["hazed"]["ladder"], occlude=False)))
 
 
 def the_drape(d):
@@ -1289,7 +1569,7 @@ def mutated(c, state):
     elif kind == "exaggeration":
         s["u"] = uniforms(c, sun=state["u"][32:35], exaggeration=a["exaggeration"])
     elif kind == "clear_overlays":
-        s["overlays"], s["occlusion"] = False, {}
+        s["overlays"], s["occlusion"], s["hazed"] = False, {}, None       # (the flags and the ladder go with the layers)
     elif kind == "layer_occlusion":
         k = a["layer"]
         s["occlusion"] = {**state["occlusion"], k: (not c["overlays"][k][1]["occlude"], a["depth_bias"])}
@@ -1310,28 +1590,34 @@ def layers(c, state):
     """The models' layers of the case's overlay calls.  The snapshot rule of vf_terrain_add_contours (include/vf_hip.h): a contour layer
     is made from the heights and the spacing the handle held when it was added -- the case's own, every mutation comes later -- so a
     later height upload does not move its records; they are draped, so the composite, which gets the state's heights and uniforms,
-    follows a later exaggeration."""
-    L = cm.Layers()
+    follows a later exaggeration.  The layers are overlay_haze_model's: a layer the state flags (state["hazed"], with the ladder behind
+    the case's own calls) takes the haze, and so does a contour layer's snapshot.  L.index: call index -> the model's layer."""
+    L = ohm.Layers()
+    Hz = state.get("hazed")
+    flags = Hz["flags"] if Hz else {}
     L.segments = {}                                           # call index -> segments of a contour layer
     u0 = uniforms(c)
     index = {}                                                # layer id of the library -> index among the models' point / line layers
     for k, (kind, kw) in enumerate(c["overlays"]):
         if kind == "points":
-            L.points(kw["xyz"], **{a: v for a, v in kw.items() if a != "xyz"})
+            L.points(kw["xyz"], haze=bool(flags.get(k)), **{a: v for a, v in kw.items() if a != "xyz"})
         elif kind == "lines":
-            L.lines(kw["paths"], **{a: v for a, v in kw.items() if a != "paths"})
+            L.lines(kw["paths"], haze=bool(flags.get(k)), **{a: v for a, v in kw.items() if a != "paths"})
         elif kind == "polygons":
             L.polygons(kw["polygons"], **{a: v for a, v in kw.items() if a != "polygons"})
             continue
         else:
-            L.contours(c["heights"], c["grid"], u0, kw["levels"], **{a: v for a, v in kw.items() if a != "levels"})
+            L.contours(c["heights"], c["grid"], u0, kw["levels"], haze=bool(flags.get(k)), **{a: v for a, v in kw.items() if a != "levels"})
             L.segments[k] = L.nsegments
         index[k] = len(L.ranges) - 1
-    L.counts = {}
-    for k, (kind, kw) in enumerate(c["overlays"]):
-        if kind != "polygons":
-            a, b = L.ranges[index[k]]
-            L.counts[k] = sum(len(r) for r in L.recs[a:b])
+    if Hz is not None:
+        kw = c["hazed"]["ladder"]
+        L.points(kw["xyz"], haze=bool(Hz["ladder"]), **{a: v for a, v in kw.items() if a != "xyz"})
+        index[ladder_index(c)] = len(L.ranges) - 1
+    L.index, L.counts = index, {}
+    for k in index:
+        a, b = L.ranges[index[k]]
+        L.counts[k] = sum(len(r) for r in L.recs[a:b])
     for k, (occlude, bias) in state["occlusion"].items():
         L.set_occlusion(index[k], occlude, bias)
     return L
@@ -1340,7 +1626,8 @@ def layers(c, state):
 def expected(c, state, cache=None):
     """The reference of a handle state: the oracle's frame and visibility, then the passes in the library's order, which is written
     down once, in supersample_model.chain (the relight pass, the draped image through its mips and anisotropic taps, the flood's water,
-    the spill's sink tint, the exposure, cumulative and viewshed tints, the haze), then the overlays (occlusion_model.composite of the contour model's layers).  `cache` (a
+    the spill's sink tint, the exposure, cumulative and viewshed tints, the haze), then the overlays (overlay_haze_model.composite of
+    its layers under the state's haze: occlusion_model.composite's bytes without a flag or without the haze).  `cache` (a
     dict of one case) keeps the oracle's frames, the vertex fields and the results, for a caller that asks for a state twice.
     -> dict rgba (the oracle's frame), vis, shaded, mask (the pixels the shade pass writes again), draped (the frame behind the drape
     pass: `shaded` without a drape), drape_mask (the pixels the drape writes again), late (the frame behind the last late pass:
@@ -1352,7 +1639,7 @@ def expected(c, state, cache=None):
     whole = (key, state["shadows"], state["ambient"], state["overlays"], tuple(sorted(state["shadow_params"].items())),
              A["strength"], A["reach"], A["directions"].tobytes(), tuple(sorted(state["occlusion"].items())),
              None if D is None else (D["image"].tobytes(), D["image"].shape, D["extent"], D["opacity"], D["filter"]), ssm._key(state["late"]),
-             ssm._key(state.get("water")))
+             ssm._key(state.get("water")), None if state.get("hazed") is None else (tuple(sorted(state["hazed"]["flags"].items())), state["hazed"]["ladder"]))
     if cache is not None and whole in cache:
         return cache[whole]
     if cache is not None and key in cache:
@@ -1368,7 +1655,7 @@ def expected(c, state, cache=None):
            "haze_opacity": st["haze_opacity"], "stages": st, "frame": late, "layers": None}
     if state["overlays"]:
         out["layers"] = layers(c, state)
-        out["frame"] = ocm.composite(late, vis, u, h, G, out["layers"])
+        out["frame"] = ohm.composite(late, vis, u, h, G, out["layers"], haze=the_haze(state))
     if cache is not None:
         cache[whole] = out
     return out
@@ -1382,7 +1669,14 @@ def expected_supersampled(c, state, f, cache=None):
     s, vis = ssm.samples(c["W"], c["H"], f, u, h, G, lut(c["cmap"]), stages=st, memo=cache, **chain_features(c, state))
     resolved = ssm.resolve(s, f)
     L = layers(unoccluded(c), dict(state, occlusion={})) if state["overlays"] else None
-    return dict(samples=s, vis=vis, haze_opacity=st["haze_opacity"], resolved=resolved, frame=ssm.composite(resolved, u, h, G, L))
+    # (as supersample_model.composite: at the output size, over a zero visibility; the hazed layers under the state's haze)
+    over = resolved if L is None else ohm.composite(resolved, np.zeros((c["H"], c["W"]), np.uint32), u, h, G, L, haze=the_haze(state))
+    return dict(samples=s, vis=vis, haze_opacity=st["haze_opacity"], resolved=resolved, frame=over)
+
+
+def the_haze(state):
+    """the haze of a state as overlay_haze_model.composite takes it: set_haze's keywords, or None while the haze is off"""
+    return (state.get("late") or {}).get("haze")
 
 
 def planes(c, state, vis):
@@ -1490,6 +1784,61 @@ def water_shares(c, cache=None):
                 without_water=bool(np.array_equal(steps[-1]["late"], expected(c, dict(water_steps(c, s3)[-1][1], water=None), cache)["late"])))
 
 
+def hazed_counts(c, state, cache=None, only=None):
+    """overlay_haze_model's counts over the state's reference: (the (hazed feature, covered pixel) pairs, those with 0 < S.ah <
+    max_opacity, those with S.ah == 0).  `only` (a call index, or ladder_index): as if that layer alone were flagged"""
+    e = expected(c, state, cache)
+    L = e["layers"] if only is None else layers(c, dict(state, hazed=dict(flags={only: True}, ladder=only == ladder_index(c))))
+    return ohm.composite(e["late"], e["vis"], state["u"], state["heights"], c["grid"], L, haze=the_haze(state), want_counts=True)[1]
+
+
+def flagged_kinds(c):
+    """what the case's flagged drawn layers are: the points' shapes, the lines' caps (cap_butt, ...), contours"""
+    out = set()
+    for k, on in zip(eligible(c), c["hazed"]["flags"]):
+        kind, kw = c["overlays"][k]
+        if on:
+            out.add(kw["shape"] if kind == "points" else "cap_" + kw["cap"] if kind == "lines" else kind)
+    return out
+
+
+def hazed_shares(c, cache=None):
+    """what the reference alone says about a case's hazed layers, in the state run_case's steps B and H meet (everything on, before
+    the first mutation): haze_on; pairs, middle, clear (hazed_counts); differs: the frame is not that of the same layers unflagged;
+    kinds (flagged_kinds); occluding: a flagged drawn layer occludes; early_then_add: a flag is set while layers are still to come
+    (the ladder always is); mutation; covers (flag_flip: the flipped layer, flagged alone, has a covered pixel with S.ah > 0, the
+    terrain in front of it taken into account); mutation_shows: a state the mutation leads through has another frame; stated
+    (flags_all_off: the frame after it is occlusion_model.composite's over the same layers; polygon_refused: the frame before it)"""
+    s2 = hazed_on(c, watered(c, lated(c, featured(c, initial_state(c), overlays=True))))
+    e2 = expected(c, s2, cache)
+    pairs, middle, clear = hazed_counts(c, s2, cache)
+    kind, a = c["hazed_mutation"], c["hazed_mutation_args"]
+    steps = [expected(c, s, cache) for _, s in hazed_steps(c, s2)]
+    stated = None
+    if kind == "flags_all_off":
+        stated = bool(np.array_equal(steps[-1]["frame"], ocm.composite(e2["late"], e2["vis"], s2["u"], s2["heights"], c["grid"], e2["layers"])))
+    elif kind == "polygon_refused":
+        stated = bool(np.array_equal(steps[-1]["frame"], e2["frame"]))
+    covers = None
+    if kind == "flag_flip":
+        p, _, cl = hazed_counts(c, s2, cache, only=a["layer"])
+        covers = p > cl
+    flagged = [k for k, on in zip(eligible(c), c["hazed"]["flags"]) if on]
+    return dict(haze_on=the_haze(s2) is not None, pairs=pairs, middle=middle, clear=clear,
+                differs=bool((e2["frame"] != expected(c, hazed_on(c, s2, flags=False), cache)["frame"]).any()), kinds=flagged_kinds(c),
+                occluding=any(c["overlays"][k][1]["occlude"] for k in flagged),
+                early_then_add=any(e for k, e in zip(eligible(c), c["hazed"]["early"]) if k in flagged), mutation=kind, covers=covers,
+                mutation_shows=any(bool((e["frame"] != e2["frame"]).any()) for e in steps), stated=stated)
+
+
+def describe_hazed(stat):
+    """the hazed layers' shares over a list of hazed_shares() results, as text"""
+    on = [s for s in stat if s["haze_on"]]
+    return (f"the haze on in {len(on)} of {len(stat)}: a hazed feature covers a pixel in {sum(s['pairs'] > 0 for s in on)}, a quarter of the pairs strictly inside "
+            f"in {sum(4 * s['middle'] >= s['pairs'] > 0 for s in on)}, a pair with S.ah == 0 in {sum(s['clear'] > 0 for s in on)}, the frame differs from the "
+            f"unflagged one in {sum(s['differs'] for s in on)}")
+
+
 def describe_water(stat):
     """the flood's and the spill's shares over a list of water_shares() results, as text"""
     out = []
@@ -1514,10 +1863,14 @@ def _where(d):
     return int(d.sum()), np.argwhere(d)[:4].tolist()
 
 
-def _add_overlays(t, c):
-    """the case's overlay calls on the handle -> (layer ids, contour segment counts by call index)"""
-    ids, nseg = {}, {}
-    for k, (kind, kw) in enumerate(c["overlays"]):
+def _add_overlays(t, c, hazed=None, swap=False):
+    """the case's overlay calls on the handle -> (layer ids, contour segment counts by call index).  `hazed` (a state's entry): the
+    ladder is added behind them, and the flags are set as the case's `early` says -- `swap`: the other way round -- directly after
+    the layer's add (the side array is allocated at the record array's capacity of that moment and grows with every later append,
+    a contour layer's GPU-extracted records among them) or after all adds"""
+    ids, nseg, late = {}, {}, []
+    early = dict(zip(eligible(c), c["hazed"]["early"])) if hazed is not None else {}
+    for k, (kind, kw) in enumerate(list(c["overlays"]) + ([("points", c["hazed"]["ladder"])] if hazed is not None else [])):
         if kind == "points":
             ids[k] = t.add_points(kw["xyz"], size_px=kw["size_px"], rgba=kw["rgba"], shape=SHAPES.index(kw["shape"]), drape=kw["drape"])
         elif kind == "lines":
@@ -1535,7 +1888,58 @@ def _add_overlays(t, c):
         if kind in ("points", "lines") and kw["occlude"]:
             t.set_layer_occlusion(ids[k], True, kw["depth_bias"])
         assert ids[k] == k
+        if hazed is not None and (hazed["ladder"] if k == ladder_index(c) else hazed["flags"].get(k)):
+            if k != ladder_index(c) and early[k] != swap:
+                t.set_layer_haze(ids[k], True)
+            else:
+                late.append(k)
+    for k in late:
+        t.set_layer_haze(ids[k], True)
     return ids, nseg
+
+
+def _flags_differ(t, c, state, ids):
+    """layer_haze() of every layer of the handle against the state's flags (a polygon layer: never) -> the layers that differ"""
+    Hz = state["hazed"]
+    want = {k: bool(Hz["ladder"] if k == ladder_index(c) else Hz["flags"].get(k, False)) for k in ids}
+    return [k for k in ids if t.layer_haze(ids[k]) is not want[k]]
+
+
+def _refused(call, message):
+    """whether `call` raises with `message` (vf_last_error's text)"""
+    try:
+        call()
+    except RuntimeError as e:
+        return message in str(e)
+    return False
+
+
+def _apply_hazed_mutation(t, c, after, ids, wrong):
+    """one step of the hazed mutation on the handle -> the layer ids then"""
+    kind, a = c["hazed_mutation"], c["hazed_mutation_args"]
+    if kind == "flag_flip":
+        t.set_layer_haze(ids[a["layer"]], after["hazed"]["flags"][a["layer"]])
+    elif kind == "flags_all_off":
+        for k in ids:
+            if k == ladder_index(c) or k in after["hazed"]["flags"]:
+                t.set_layer_haze(ids[k], False)
+    elif kind == "haze_params":
+        _set_late(t, c, after)
+    elif kind == "occlusion_on_hazed":
+        t.set_layer_occlusion(ids[a["occlusion_layer"]], *after["occlusion"][a["occlusion_layer"]])
+    elif kind == "readd":
+        t.clear_overlays()                                    # (with flags set the first time, with none the second)
+        for k in ids:
+            if not _refused(lambda: t.layer_haze(ids[k]), UNKNOWN_LAYER):
+                wrong(f"layer_haze({ids[k]}) after clear_overlays is not refused with '{UNKNOWN_LAYER}'")
+        ids, _ = _add_overlays(t, c, after["hazed"], swap=True)
+    elif kind == "polygon_refused":
+        polygon = next(k for k, (kind_, _) in enumerate(c["overlays"]) if kind_ == "polygons")
+        if not _refused(lambda: t.set_layer_haze(ids[polygon], True), POLYGON_REFUSED):
+            wrong(f"set_layer_haze on the polygon layer {ids[polygon]} is not refused with '{POLYGON_REFUSED}'")
+        if not _refused(lambda: t.set_layer_haze(len(ids), True), UNKNOWN_LAYER):
+            wrong(f"set_layer_haze on the unknown layer {len(ids)} is not refused with '{UNKNOWN_LAYER}'")
+    return ids
 
 
 def _set_features(t, state):
@@ -1626,8 +2030,8 @@ def run_case(c, seed=None, cache=None):
                 differ(3, "other pixels against the frame before" + again, (got != plain).any(axis=2) & ~e["mask"] & ~e["drape_mask"])
         # 4. exact precision, the overlays
         t.set_shade_precision(0)
-        ids, nseg = _add_overlays(t, c)
-        state = dict(state, overlays=True)
+        state = hazed_on(c, dict(state, overlays=True))       # (the haze is not on yet: the flags and the ladder, the unflagged bytes)
+        ids, nseg = _add_overlays(t, c, state["hazed"])
         e = expected(c, state, cache)
         L = e["layers"]
         for k in nseg:
@@ -1639,6 +2043,8 @@ def run_case(c, seed=None, cache=None):
                 bad.append((seed, 4, f"layer {k}: {n} primitives against {L.counts[k]}", 1, []))
         differ(4, "frame", (frame(t) != e["frame"]).any(axis=2))
         differ(4, "frame drawn again", (frame(t) != e["frame"]).any(axis=2))
+        if _flags_differ(t, c, state, ids):
+            bad.append((seed, 4, f"layer_haze() of the layers {_flags_differ(t, c, state, ids)} against the flags set", 1, []))
         compare_planes(4, state, e["vis"])                    # (the planes and the visibility know nothing of the drape)
         differ(4, "visibility", t.read_visibility() != e["vis"])
         # A. the late passes' vertex fields: their parameters set, the passes off
@@ -1692,10 +2098,19 @@ def run_case(c, seed=None, cache=None):
         got = frame(t)
         before = np.where((e["mask"] | e["drape_mask"])[..., None], e["draped"], plain)
         want = ssm.chain(before, e["vis"], u, h, G, lut_, memo=cache, **dict(chain_features(c, state), shadows=None, ambient=None, drape=None))
-        touched = ((ocm.composite(want, e["vis"], u, h, G, e["layers"]) != want) | (ocm.composite(255 - want, e["vis"], u, h, G, e["layers"]) != 255 - want)).any(axis=2)
+        touched = ((ohm.composite(want, e["vis"], u, h, G, e["layers"], haze=the_haze(state)) != want)
+                   | (ohm.composite(255 - want, e["vis"], u, h, G, e["layers"], haze=the_haze(state)) != 255 - want)).any(axis=2)
         differ("C", "fast frame off the overlays against the late passes' models over the fast frame before them", (got != want).any(axis=2) & ~touched)
         differ("C", "fast frame's alpha", got[..., 3] != e["frame"][..., 3])
         t.set_shade_precision(0)
+        # H. the hazed mutation, while everything is on: the frame, layer_haze() of every layer and, for polygon_refused, the messages
+        kind = c["hazed_mutation"]
+        for what, after in hazed_steps(c, state):
+            ids = _apply_hazed_mutation(t, c, after, ids, lambda text: bad.append((seed, "H", text, 1, [])))
+            state = after
+            differ("H", f"frame after {kind}: {what}", (frame(t) != expected(c, state, cache)["frame"]).any(axis=2))
+            if _flags_differ(t, c, state, ids):
+                bad.append((seed, "H", f"after {kind} ({what}): layer_haze() of the layers {_flags_differ(t, c, state, ids)} against the flags set", 1, []))
         # D (and 5). the mutation, then the late mutation
         kind, a = c["mutation"], c["mutation_args"]
         scans, late_scans = (t.shadow_scans(), t.ambient_scans()), _late_counters(t)
@@ -1748,7 +2163,7 @@ def run_case(c, seed=None, cache=None):
     # E. a supersampled second handle: the same heights, uniforms, features, drape and late passes, no layer occluding; then the late mutation
     f = c["late"]["supersample"]
     if f > 1:
-        state = watered(c, lated(c, featured(c, initial_state(c), overlays=True)))
+        state = hazed_on(c, watered(c, lated(c, featured(c, initial_state(c), overlays=True))))
         t = cabi.Terrain(W, H, G, lut(c["cmap"]), supersample=f)
         try:
             t.set_uniforms(state["u"]); t.set_shade_mode(c["mode"]); t.set_height(state["heights"]); t.set_shade_precision(0)
@@ -1756,7 +2171,7 @@ def run_case(c, seed=None, cache=None):
             _set_drape(t, state["drape"])
             _set_late(t, c, state)
             _set_water(t, c, state)
-            _add_overlays(t, unoccluded(c))
+            _add_overlays(t, unoccluded(c), state["hazed"])       # (the flags and the ladder, none occluding)
             for step in ("E", "E after " + c["late_mutation"], "E after " + c["water_mutation"]):
                 if step == "E after " + c["late_mutation"]:
                     state = late_mutated(c, state)
@@ -1919,13 +2334,14 @@ def run(first=FRESH_SEED, cases=200, budget=400.0, verbose=True, corners=True):
     (the tuples of run_case), summary."""
     t0 = time.time()
     say = (lambda *a: print(*a, flush=True)) if verbose else (lambda *a: None)
-    bad, done, skipped, stat, late, water = [], 0, 0, [], [], []
+    bad, done, skipped, stat, late, water, hazed = [], 0, 0, [], [], [], []
 
     def one(c, seed):
         cache = {}
         stat.append(shares(c, cache))
         late.append(late_shares(c, cache))
         water.append(water_shares(c, cache))
+        hazed.append(hazed_shares(c, cache))
         b = run_case(c, seed, cache)
         for m in b:
             say(f"MISMATCH {m[0]} step {m[1]}: {m[2]}: {m[3]} differ, first at {m[4]}  ({c['W']}x{c['H']} grid={c['grid']} {c['features']} mutation={c['mutation']})")
@@ -1952,7 +2368,7 @@ def run(first=FRESH_SEED, cases=200, budget=400.0, verbose=True, corners=True):
             say(f"{done} cases, {len(bad)} mismatches, {time.time() - t0:.0f} s")
     share = skipped / max(done + skipped, 1)
     summary = (f"feature soak: {ncorners} corners and {done} cases from seed {first}, {skipped} skipped for a degenerate camera ({100.0 * share:.0f} %, "
-               f"bound {100.0 * MAX_SKIPPED:.0f} %): {len(bad)} mismatches; {describe(stat)}; the late passes: {describe_late(late)}, supersampled {sum(c['supersample'] > 1 for c in late)}; the water: {describe_water(water)}; {time.time() - t0:.0f} s")
+               f"bound {100.0 * MAX_SKIPPED:.0f} %): {len(bad)} mismatches; {describe(stat)}; the late passes: {describe_late(late)}, supersampled {sum(c['supersample'] > 1 for c in late)}; the water: {describe_water(water)}; the hazed layers: {describe_hazed(hazed)}; {time.time() - t0:.0f} s")
     say(summary)
     return {"cases": done, "corners": ncorners, "skipped": skipped, "too_many_skipped": share > MAX_SKIPPED, "bad": bad, "summary": summary}
 

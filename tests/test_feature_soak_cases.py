@@ -1,7 +1,9 @@
 """The GPU feature soak's slice (tests/test_gpu_feature_soak.py) is not vacuous: the reference alone (soak_features.case / expected,
 no GPU), over exactly the corners and seeds that module runs, covers pixels, rewrites part of them, drapes an image over part of
 them, draws overlays, meets every mutation, and is deterministic; the draped image's corners, the late passes' and the flood's and
-the spill's hold the edges they are named for; no key a case had before a later generator was added has moved."""
+the spill's hold the edges they are named for; hazed overlay layers cover pixels at opacities strictly inside (0, max_opacity), at
+0 and at the cap, every mutation of their flags occurs and does what it must, and their corners hold their edges; no key a case had
+before a later generator was added has moved."""
 import collections
 
 import numpy as np
@@ -195,7 +197,7 @@ def test_no_key_older_than_the_late_passes_has_moved():
     than the late passes, computed on the commit before the late passes' generator existed"""
     assert sf.digest(sf.case(seed) for seed in SEEDS) == "f937961fa73b2d474bdd3770e7f18db5bce0b3b6af714a22f5821d21b8e7b39a"
     assert sf.digest(sf.CORNERS[i] for i in range(sf.OLD_CORNERS)) == "3f3093f0c0906104c579ceba1b54a8a70fcc15e084847e712536ec3337eee5e4"
-    assert set(sf.case(FIRST_SEED)) == set(sf.OLD_KEYS) | {"late", "late_mutation", "late_mutation_args"} | set(sf.WATER_KEYS)
+    assert set(sf.case(FIRST_SEED)) == set(sf.OLD_KEYS) | {"late", "late_mutation", "late_mutation_args"} | set(sf.WATER_KEYS) | set(sf.HAZED_KEYS)
 
 
 def test_no_key_older_than_the_water_has_moved():
@@ -204,7 +206,7 @@ def test_no_key_older_than_the_water_has_moved():
     keys = sf.OLD_KEYS + ("late", "late_mutation", "late_mutation_args")
     assert sf.digest((sf.case(seed) for seed in SEEDS), keys) == "892ae0c5ec28ccc65906b24782d9cb8918876aed223e07055d63e4e1c27e931d"
     assert sf.digest((sf.CORNERS[i] for i in range(sf.LATE_CORNERS)), keys) == "0d26e23f448e1c352b24e892425bfca31c16341e693a9fcd2dfa731f655952bb"
-    assert not any(n.startswith("water_") for n in sf.CORNERS.names[:sf.LATE_CORNERS]) and all(n.startswith("water_") for n in sf.CORNERS.names[sf.LATE_CORNERS:])
+    assert not any(n.startswith("water_") for n in sf.CORNERS.names[:sf.LATE_CORNERS]) and all(n.startswith("water_") for n in sf.CORNERS.names[sf.LATE_CORNERS:sf.WATER_CORNERS])
 
 
 @pytest.fixture(scope="module")
@@ -814,3 +816,218 @@ def test_the_chain_keeps_the_water_apart_and_its_fields_without_the_exaggeration
     tint = lambda P: {k: P[k] for k in ("shallow_rgba", "deep_rgba", "depth_full")}
     other = sf.fdm.frame(sf.spm.frame(full["draped"], full["vis"], u, h, G, st["spill_field"], **tint(W["spill"]))[0], full["vis"], u, h, G, st["flood_field"], **tint(W["flood"]))[0]
     assert (other != st["spill_frame"]).any()
+
+
+# ---- hazed overlay layers ------------------------------------------------------------------------------------------------
+
+def test_no_key_older_than_the_hazed_layers_has_moved():
+    """the digest of OLD_KEYS, the three late keys and WATER_KEYS of the slice's seeds and of the 68 corners older than the hazed
+    layers, computed on the commit before their generator existed"""
+    keys = sf.OLD_KEYS + ("late", "late_mutation", "late_mutation_args") + sf.WATER_KEYS
+    assert sf.digest((sf.case(seed) for seed in SEEDS), keys) == "49c31bc9520d16792a9bf824fb8314eccff6c50a9431e46d998eabc362896c63"
+    assert sf.digest((sf.CORNERS[i] for i in range(sf.WATER_CORNERS)), keys) == "c09a7566456a36ca4ff6f2c9f11d21671b2ab9ff3bf268464d2c05aa8efc8e50"
+    assert sf.WATER_CORNERS == 68 and set(sf.case(FIRST_SEED)) == set(keys) | set(sf.HAZED_KEYS)
+    assert not any(n.startswith("hazed_") for n in sf.CORNERS.names[:sf.WATER_CORNERS]) and all(n.startswith("hazed_") for n in sf.CORNERS.names[sf.WATER_CORNERS:])
+
+
+@pytest.fixture(scope="module")
+def hazed(oracle):
+    """hazed_shares() of every seed of the slice and of every corner, computed once: (cases by name, shares by name)"""
+    cases = {c["name"]: c for c in [sf.case(seed) for seed in SEEDS] + list(sf.CORNERS)}
+    return cases, {name: sf.hazed_shares(c, {}) for name, c in cases.items()}
+
+
+def everything_on(c, **hazed):
+    return sf.hazed_on(c, sf.watered(c, sf.lated(c, sf.featured(c, sf.initial_state(c), overlays=True))), **hazed)
+
+
+def test_without_a_flag_or_without_the_haze_the_frame_is_the_occlusion_models(oracle):
+    """expected() composites through overlay_haze_model: with no flag set, or with haze=None, its bytes are occlusion_model.composite's
+    over the same layers, the ladder among them -- on eight seeds and every corner"""
+    for c in [sf.case(seed) for seed in list(SEEDS)[:8]] + list(sf.CORNERS):
+        cache = {}
+        for state in (everything_on(c, flags=False), sf.hazed_on(c, sf.featured(c, sf.initial_state(c), overlays=True)),
+                      dict(everything_on(c), late=dict(everything_on(c)["late"], haze=None))):
+            e = sf.expected(c, state, cache)
+            assert len(e["layers"].ranges) == len(sf.eligible(c)) + 1            # (the ladder is there)
+            assert np.array_equal(e["frame"], sf.ocm.composite(e["late"], e["vis"], state["u"], state["heights"], c["grid"], e["layers"])), (c["name"], state["hazed"])
+        ss = dict(everything_on(c, flags=False))
+        if c["late"]["supersample"] > 1 and c["W"] * c["H"] <= 4096:
+            f = c["late"]["supersample"]
+            e = sf.expected_supersampled(c, ss, f, cache)
+            L = sf.layers(sf.unoccluded(c), dict(ss, occlusion={}))
+            assert np.array_equal(e["frame"], sf.ssm.composite(e["resolved"], ss["u"], ss["heights"], c["grid"], L)), c["name"]
+
+
+def test_the_slice_hazes_part_of_what_its_layers_cover(hazed):
+    """conditions on the draw (soak_features._hazed: FLAG_SHARE, the ladder), over the 48 seeds with the drawn flags and the ladder,
+    from the models alone: the draw is what to tune, never a bound"""
+    cases, stat = hazed
+    seeds = [stat[f"seed{s}"] for s in SEEDS]
+    print("\n" + sf.describe_hazed(seeds) + "\nwith the corners: " + sf.describe_hazed(list(stat.values())))
+    on = [s for s in seeds if s["haze_on"]]
+    assert len(on) == 36
+    assert sum(s["pairs"] > 0 for s in on) >= 30                                # measured 36 of 36
+    assert sum(4 * s["middle"] >= s["pairs"] > 0 for s in on) >= 18             # measured 29
+    assert sum(s["clear"] > 0 for s in on) >= 4                                 # measured 7
+    assert sum(s["differs"] for s in on) >= 30                                  # measured 36
+    for s in seeds:                                                             # (without the haze a flag changes no byte)
+        assert s["haze_on"] or not (s["pairs"] or s["differs"])
+    c48 = [cases[f"seed{s}"] for s in SEEDS]
+    assert all(any(c["hazed"]["flags"]) and len(c["hazed"]["flags"]) == len(c["hazed"]["early"]) == len(sf.eligible(c)) == 6 for c in c48)
+    assert set().union(*[s["kinds"] for s in seeds]) == {"circle", "square", "cap_butt", "cap_square", "cap_round", "contours"}
+    assert sum(s["occluding"] for s in seeds) >= 8                              # measured 44 (a drawn layer; the ladder occludes in every other seed besides)
+    assert sum(s["early_then_add"] for s in seeds) >= 12                        # measured 42
+    assert sum(c["hazed"]["ladder"]["occlude"] for c in c48) == 24
+    for c in cases.values():                                                    # the ladder: twelve opaque draped circles of 5 px from under the eye through the target
+        lad = c["hazed"]["ladder"]
+        assert lad["xyz"].shape == (sf.LADDER_RUNGS, 3) and lad["size_px"] == 5.0 and lad["rgba"][3] == 255 and lad["drape"] and lad["shape"] == "circle"
+        g = lad["xyz"][:, [0, 2]].astype(np.float64)
+        assert np.allclose(g[0], [c["eye"][0], c["eye"][2]], atol=1e-5) and np.isfinite(g).all()
+        d, t = g[-1] - g[0], np.subtract([c["target"][0], c["target"][2]], g[0])
+        assert abs(d[0] * t[1] - d[1] * t[0]) <= 1e-4 * max(1.0, float(np.abs(d).max()) * float(np.abs(t).max())), c["name"]     # (the target lies on its line)
+
+
+def test_every_hazed_mutation_occurs_and_does_what_it_must(hazed):
+    """flag_flip changes the frame in every case, seed or corner, whose flipped layer -- flagged alone, the terrain in front of it
+    taken into account -- has a covered pixel with S.ah > 0 when the mutation comes; the cases without one are counted.
+    flags_all_off leaves occlusion_model.composite's bytes over the same layers, polygon_refused the frame before it.  A failure is
+    settled in soak_features._hazed (can_stand), never here."""
+    cases, stat = hazed
+    kinds = collections.Counter(cases[f"seed{s}"]["hazed_mutation"] for s in SEEDS)
+    assert all(kinds[k] >= 3 for k in sf.HAZED_MUTATIONS), kinds               # measured: flag_flip 4, the others 8 to 10 of the 48 seeds
+    for n, c in cases.items():
+        kind, a, on = c["hazed_mutation"], c["hazed_mutation_args"], dict(zip(sf.eligible(c), c["hazed"]["flags"]))
+        assert kind not in ("flag_flip", "haze_params") or stat[n]["haze_on"], n
+        assert kind != "flag_flip" or a["layer"] in on, n
+        if kind == "occlusion_on_hazed":                                        # a flagged point or line layer: a drawn one, or the ladder
+            k = a["occlusion_layer"]
+            assert k == sf.ladder_index(c) or (on[k] and c["overlays"][k][0] in ("points", "lines")), n
+        if kind == "haze_params":                                               # another density, start and falloff
+            Z = c["late"]["haze"]
+            assert all(a["haze"][k] != Z[k] for k in ("density", "start", "falloff")) or n.startswith("hazed_"), n
+    flips = [n for n, c in cases.items() if c["hazed_mutation"] == "flag_flip"]
+    blank = [n for n in flips if not stat[n]["covers"]]
+    print(f"\n{len(flips)} cases flip a flag, of which {len(blank)} cover no pixel with S.ah > 0 on the flipped layer: {blank}")
+    assert len(flips) - len(blank) >= 8                                         # measured: 17 of 17 (four seeds, thirteen corners)
+    assert [n for n in flips if n not in blank and not stat[n]["mutation_shows"]] == []
+    stated = [n for n, c in cases.items() if c["hazed_mutation"] in ("flags_all_off", "polygon_refused")]
+    assert len(stated) >= 20 and all(stat[n]["stated"] for n in stated)
+    off = [n for n in stated if cases[n]["hazed_mutation"] == "flags_all_off" and stat[n]["haze_on"]]
+    assert sum(stat[n]["mutation_shows"] for n in off) >= 0.8 * len(off)       # (and switching every flag off is seen)
+
+
+def probe_ends(c, state, layer, record=0):
+    """overlay_haze_model.probe of one record of one of the case's layers: the ends after clipping and the record itself"""
+    L = sf.layers(c, state)
+    a, b = L.ranges[L.index[layer]]
+    recs = np.concatenate(L.recs[a:b])
+    rec = recs[(recs["flags"] & 3) == 2][record]              # (a segment: a round cap's ends are records of their own)
+    return sf.ohm.probe(c["W"], c["H"], state["u"], state["heights"], c["grid"], rec, 0, 0, sf.the_haze(state)), rec
+
+
+def alone(c, state, layer):
+    """(pairs, middle, clear) of one layer flagged alone"""
+    return sf.hazed_counts(c, state, only=layer)
+
+
+def test_the_hazed_corners_hold_the_edges_they_are_named_for(hazed):
+    cases, stat = hazed
+    by = {n: c for n, c in cases.items() if n.startswith("hazed_")}
+    assert len(by) == 19 and all(c["late"]["on"] == sf.LATE_PASSES and max(c["W"], c["H"]) <= 130 and c["grid"] <= 65 for c in by.values())
+    for n, c in by.items():                                   # the corners' own layers follow the eight drawn calls, or replace them
+        assert len(c["overlays"]) >= sf.DRAWN or n in ("hazed_side_array_grows_behind_an_early_flag", "hazed_one_flag_on_the_last_layer"), n
+    # a zero-length segment alone in its path covers pixels under the round cap at either width (a segment without length has no
+    # direction to extend a butt or a square cap along: the model draws nothing of those)
+    c = by["hazed_zero_length_segments_every_cap"]
+    state = everything_on(c)
+    widths = set()
+    for j in range(6):
+        kind, kw = c["overlays"][sf.DRAWN + j]
+        assert kind == "lines" and [len(p) for p in kw["paths"]] == [2, 3] and (kw["paths"][0][0] == kw["paths"][0][1]).all() and (kw["paths"][1][0] == kw["paths"][1][1]).all()
+        widths.add(kw["width_px"])
+        only = dict(c, overlays=c["overlays"][:sf.DRAWN + j] + [(kind, dict(kw, paths=kw["paths"][:1]))] + c["overlays"][sf.DRAWN + j + 1:])
+        pairs = alone(only, state, sf.DRAWN + j)[0]
+        print(f"\nzero-length segment, cap {kw['cap']}, width {kw['width_px']}: {pairs} covered pixels")
+        assert (pairs > 0) == (kw["cap"] == "round"), (kw["cap"], kw["width_px"], pairs)
+    assert widths == {0.5, 80.0} and {c["overlays"][sf.DRAWN + j][1]["cap"] for j in range(6)} == set(sf.CAPS)
+    # the paths through the eye: the near plane cuts them, and the clipped end's y is not the vertex's
+    for n in ("hazed_paths_through_the_eye_falloff0p3", "hazed_paths_through_the_eye_fovy170_saturated"):
+        c = by[n]
+        state = everything_on(c)
+        assert c["late"]["haze"]["falloff"] == 0.3
+        for layer in (sf.DRAWN, sf.DRAWN + 1):
+            p, rec = probe_ends(c, state, layer)
+            print(f"\n{n} layer {layer}: clipped ends y {float(p['y_a']):.4f} .. {float(p['y_b']):.4f}, 1/w {float(p['rw_a']):.4f} .. {float(p['rw_b']):.4f}")
+            assert p["rw_a"] > 0 and p["rw_b"] > 0
+            if layer == sf.DRAWN:                              # (the free path: its y is the record's own)
+                assert abs(float(p["y_b"]) - float(rec["p1"][1])) > 0.01 and abs(float(p["y_a"]) - float(rec["p0"][1])) < 1e-6
+        assert stat[n]["pairs"] > 0
+    s = stat["hazed_paths_through_the_eye_fovy170_saturated"]
+    assert by["hazed_paths_through_the_eye_fovy170_saturated"]["fovy"] == 170.0 and s["pairs"] > s["middle"] + s["clear"]      # (pairs at max_opacity)
+    # the near-plane camera: a hazed occluding layer beside an unhazed occluding one, and the terrain hides part of the hazed one
+    c = by["hazed_near_plane_through_the_terrain"]
+    state = everything_on(c)
+    (_, a), (_, b) = c["overlays"][sf.DRAWN], c["overlays"][sf.DRAWN + 1]
+    on = dict(zip(sf.eligible(c), c["hazed"]["flags"]))
+    assert a["occlude"] and b["occlude"] and on[sf.DRAWN] and not on[sf.DRAWN + 1] and c["hazed_mutation_args"]["occlusion_layer"] == sf.DRAWN and c["znear"] == 0.4
+    hidden = alone(c, dict(state, occlusion={sf.DRAWN: (False, 0.0)}), sf.DRAWN)[0] - alone(c, state, sf.DRAWN)[0]
+    print(f"\nthe near-plane corner: the terrain hides {hidden} covered pixels of the hazed occluding layer")
+    assert hidden > 0 and alone(c, state, sf.DRAWN)[0] > 0
+    # vertices without a height under draped hazed layers
+    c = by["hazed_draped_over_one_nan_texel"]
+    assert int(np.isnan(c["heights"]).sum()) == 1 and stat[c["name"]]["pairs"] > 0 and all(c["overlays"][sf.DRAWN + j][1]["drape"] for j in (0, 1))
+    c = by["hazed_draped_over_the_all_nan_texture"]
+    assert np.isnan(c["heights"]).all() and stat[c["name"]]["pairs"] == 0 and c["mutation"] == "heights"          # (the height upload brings ground under them)
+    after = sf.mutated(c, everything_on(c))
+    assert sf.hazed_counts(c, after)[0] > 0
+    # no opacity, three ways: pairs, every one with S.ah == 0, the unflagged bytes; haze_params brings start to 0
+    for n in ("hazed_no_opacity_start_beyond_every_depth", "hazed_no_opacity_max_opacity_0", "hazed_no_opacity_colour_of_alpha_0"):
+        s, c = stat[n], by[n]
+        assert s["pairs"] > 0 and s["clear"] == s["pairs"] and not s["differs"] and c["hazed_mutation"] == "haze_params" and c["hazed_mutation_args"]["haze"]["start"] == 0.0, n
+    Z = [by[n]["late"]["haze"] for n in ("hazed_no_opacity_start_beyond_every_depth", "hazed_no_opacity_max_opacity_0", "hazed_no_opacity_colour_of_alpha_0")]
+    assert Z[0]["start"] == 1e6 and Z[1]["max_opacity"] == 0.0 and Z[2]["rgba"][3] == 0
+    # the side array: the records behind the early flag are more than four times those before it
+    c = by["hazed_side_array_grows_behind_an_early_flag"]
+    L = sf.layers(c, everything_on(c))
+    before = sum(len(r) for r in L.recs[:L.ranges[L.index[0]][1]])
+    total = sum(len(r) for r in L.recs)
+    print(f"\nthe growth corner: {before} records when the first flag is set, {total} in the end, {L.segments[1]} contour segments")
+    assert c["grid"] == 65 and not c["smooth"] and c["hazed"]["early"][0] and not c["hazed"]["early"][1] and len(c["overlays"][1][1]["levels"]) == 6
+    assert total > 4 * before and L.segments[1] >= 2000 and len(c["overlays"][2][1]["xyz"]) == 300 and c["overlays"][2][1]["size_px"] == 1.0
+    c = by["hazed_one_flag_on_the_last_layer"]
+    assert c["hazed"]["flags"] == (False, False, True) and c["hazed"]["early"][2] is False and c["hazed_mutation"] == "readd" and c["overlays"][-1][0] == "points"
+    # the staircase: a hazed contour layer with a level on a plateau
+    c = by["hazed_contours_on_the_staircase"]
+    surf = sf.cm.surface(c["heights"], c["grid"])
+    k = next(i for i, (kind, _) in enumerate(c["overlays"]) if kind == "contours")
+    assert dict(zip(sf.eligible(c), c["hazed"]["flags"]))[k] and max(int((surf == v).sum()) for v in c["overlays"][k][1]["levels"]) > 20
+    assert c["mutation"] == "heights" and alone(c, everything_on(c), k)[0] > 0
+    # frames of one pixel, one column and one row under a 64-px point and an 80-px line
+    for n, size in (("hazed_frame1x1", (1, 1)), ("hazed_frame_of_one_column", (1, 70)), ("hazed_frame_of_one_row", (130, 1))):
+        c = by[n]
+        assert (c["W"], c["H"]) == size and c["overlays"][sf.DRAWN][1]["size_px"] == 64.0 and c["overlays"][sf.DRAWN + 1][1]["width_px"] == 80.0
+        assert alone(c, everything_on(c), sf.DRAWN)[0] > 0 and alone(c, everything_on(c), sf.DRAWN + 1)[0] > 0, n
+    assert by["hazed_frame_of_one_row"]["fovy"] == sf.CORNERS.named("late_frame_of_one_row")["fovy"]
+    for n, f, size in (("hazed_supersample3_frame15x17", 3, (15, 17)), ("hazed_supersample4_frame1x1", 4, (1, 1))):
+        c = by[n]
+        assert c["late"]["supersample"] == f and (c["W"], c["H"]) == size and stat[n]["pairs"] > 0
+        e = sf.expected_supersampled(c, everything_on(c), f)
+        assert (e["frame"] != sf.expected_supersampled(c, everything_on(c, flags=False), f)["frame"]).any(), n
+    for n, ex, sp in (("hazed_exaggeration0_spacing0p3", 0.0, 0.3), ("hazed_exaggeration_minus2_spacing2p5", -2.0, 2.5)):
+        c = by[n]
+        assert (c["exaggeration"], c["spacing"]) == (ex, sp) and c["overlays"][sf.DRAWN][1]["drape"] and not c["overlays"][sf.DRAWN + 1][1]["drape"]
+        assert alone(c, everything_on(c), sf.DRAWN)[0] > 0 and alone(c, everything_on(c), sf.DRAWN + 1)[0] > 0, n
+
+
+def test_expected_is_deterministic_with_the_hazed_state(oracle):
+    for c in [sf.case(FIRST_SEED + 3), sf.CORNERS.named("hazed_side_array_grows_behind_an_early_flag")]:
+        on = everything_on(c)
+        for state in [on] + [s for _, s in sf.hazed_steps(c, on)] + [sf.mutated(c, sf.hazed_mutated(c, on))]:
+            a, b = sf.expected(c, state), sf.expected(sf.case(int(c["name"][4:])) if c["name"].startswith("seed") else c, state)
+            assert a["frame"].tobytes() == b["frame"].tobytes()
+    # a cached entry made under other flags is never returned
+    c, cache = sf.CORNERS.named("hazed_zero_length_segments_every_cap"), {}
+    on = everything_on(c)
+    seen = {sf.expected(c, s, cache)["frame"].tobytes() for s in (on, everything_on(c, flags=False), sf.hazed_mutated(c, on), dict(on, hazed=None))}
+    assert len(seen) == 4 and sf.expected(c, on, cache)["frame"].tobytes() == sf.expected(c, on)["frame"].tobytes()

@@ -2,8 +2,10 @@
 blocks of four seeded random cases.  Every pass that runs after the tile kernel -- geometry buffers and pick, the shadow and
 sky-view fields and their shade passes, the draped image with its mip pyramid and anisotropic taps, the viewshed, cumulative-viewshed
 and sun-exposure fields and their tints, the flood's and the spill's fields (at two group sizes, the spill's with and without its
-activity flags), the water and the sink tint, the haze, point / line / polygon / contour overlays with occlusion -- equals its CPU
-model on the oracle's frame, on one handle, before and after three mutations of the handle and after the drape is cleared; the vertex
+activity flags), the water and the sink tint, the haze, point / line / polygon / contour overlays with occlusion, their point, line
+and contour layers under the haze where a case flags them (set_layer_haze directly after a layer's add or after all adds, a ladder
+of hazed points across the frame's depths) -- equals its CPU model on the oracle's frame, on one handle, before and after four
+mutations of the handle and after the drape is cleared; the vertex
 fields and the pyramid are computed as often as include/vf_hip.h says; a case with a factor above 1 runs the same passes on a
 supersampled second handle.  Fixed seeds (a failure reproduces from the commit alone); VF_FEATURE_SOAK_FIRST_SEED moves the window.
 tests/test_feature_soak_cases.py asserts, without a GPU, that these very cases are not vacuous."""
